@@ -8,7 +8,8 @@ device).  One "step" = one pass of the fused HIP filter+sum kernel over the whol
 16-byte {sum,count} states are summed with one RCCL all-reduce per step, issued asynchronously.
 
 Contract: `python bench.py --gpus N --steps K --warmup W`; N>1 is launched by torch.distributed.run (one rank per GPU).
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes the result of the last timed step under DIR (inputs are seeded, so two
+builds can be compared output for output).
 """
 import argparse
 import json
@@ -42,7 +43,11 @@ def main():
     ap.add_argument("--sharded-timeout", type=float, default=240.0, help="N>1: seconds the sharded GROUP BY / join section may take before the line is printed without it")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group even at world size 1 (exercises the RCCL code path on one GPU)")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, the measured configuration) or gloo (rehearsal of the N>1 code path on one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the {sum, count} state of the last timed step as DIR/<name>.npy (float64), "
+                                                          "to compare two builds output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # the hosts of this pool only support dmabuf IPC: without it RCCL's peer buffers fail with hipIpcGetMemHandle: invalid argument.
     # Exported by the launch environment already; set before HIP starts in case a launcher drops it
@@ -156,6 +161,8 @@ def main():
         want_sum = int(a[a < THRESHOLD].sum().item())
         want_cnt = int((a < THRESHOLD).sum().item())
         assert (int(res[W][0]), int(res[W][1])) == (want_sum, want_cnt), (res[W], want_sum, want_cnt)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res[W + K - 1], np)
 
     total_rows = n * world * K
     value = total_rows / elapsed
@@ -803,6 +810,18 @@ def config_c5(args, ctx, ch, torch, np, dev, stream, with_cpu):
                                          "right-side tables, own aggregation states merged at the end (dimension filters and builds included)"}
         out["parity"] = "every (year, nation) group: profit and row count bit-exact on the sample"
     return out
+
+
+def dump_outputs(out_dir, state, np):
+    """--dump-outputs: what a caller of the timed path receives, sum(a) (Int64) and count(), as float64 arrays.  A float64 holds
+    integers exactly only up to 2^53 and the sum of 1 B rows passes that, so sum_words.npy adds the sum's two's-complement bits as
+    two exact 32-bit halves {high, low}."""
+    os.makedirs(out_dir, exist_ok=True)
+    s, c = int(state[0]), int(state[1])
+    bits = s % 2**64
+    np.save(os.path.join(out_dir, "sum.npy"), np.array([s], dtype=np.float64))
+    np.save(os.path.join(out_dir, "count.npy"), np.array([c], dtype=np.float64))
+    np.save(os.path.join(out_dir, "sum_words.npy"), np.array([bits >> 32, bits & 0xFFFFFFFF], dtype=np.float64))
 
 
 def cpu_baseline(a, sample_rows, ctx, ch):
