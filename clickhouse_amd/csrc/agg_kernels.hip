@@ -734,7 +734,7 @@ __global__ __launch_bounds__(GBP_THREADS) void k_gb_hist(const void * __restrict
 // nontemporal load; otherwise rows are strided by the workgroup size and loaded one by one through the type switches.
 template <u32 GBP_TILE, typename KT, bool WIDE>
 __global__ __launch_bounds__(GBP_THREADS) void k_gb_scatter(const void * __restrict__ keys, int key_type, u64 row_begin, u64 n, u64 rows_per_wg,
-                                                            u32 P, const u64 * __restrict__ offsets, GbpCols cols, KT * __restrict__ out_keys, u64 mult, int gmajor = 0)
+                                                            u32 P, const u64 * __restrict__ offsets, GbpCols cols, KT * __restrict__ out_keys, u64 mult)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char gb_lds[];
     u64 * stage_word = (u64 *)gb_lds;
@@ -747,7 +747,7 @@ __global__ __launch_bounds__(GBP_THREADS) void k_gb_scatter(const void * __restr
 
     for (u32 p = threadIdx.x; p < P; p += GBP_THREADS)
     {
-        cursor[p] = offsets[gmajor ? (u64)blockIdx.x * P + p : (u64)p * gridDim.x + blockIdx.x];
+        cursor[p] = offsets[(u64)p * gridDim.x + blockIdx.x];
         tile_cnt[p] = 0;
     }
     __syncthreads();
@@ -1424,8 +1424,9 @@ __device__ __forceinline__ u32 tiles_load_block(const u32 * __restrict__ run_ind
 // finished by a plain loop after the pipelined one.
 // tile_index: u16 [n_tiles][P + 1]; the two entries of (tile, p) are read as one unaligned 32-bit load.
 // OPS: the compile-time state update code of k_agg_part_lds (one argument word: operations 1, 3, 5, 6).
-// AOS: the sorted copy is one array of 12-byte {word, key} records (words0 = its base; k_rp_tilesort AOS), 4-byte keys only.
-template <typename KT, u32 OPS, u32 TILE, bool AOS = false>
+// The sorted copy is k_rp_tilesort's array of {word, key} records: 12 bytes for 4-byte keys, 16 for 8-byte keys (words0 = its base;
+// `keys` is not read).
+template <typename KT, u32 OPS, u32 TILE>
 __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, const KT * __restrict__ keys, const u64 * __restrict__ words0,
                                                         const u32 * __restrict__ run_index, u32 n_tiles, u32 P, u64 * __restrict__ pending, u32 S, u32 cnt32,
                                                         const u64 * __restrict__ unit_list, const u32 * __restrict__ qstart, u32 * __restrict__ qctr, int experiment)
@@ -1596,7 +1597,7 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
             {
                 u32 i = row_of(m * 64 + lane, cs, dl);
                 i = i < (u32)last_row ? i : (u32)last_row; // (the lanes beyond the step's rows computed anything)
-                if constexpr (AOS && sizeof(KT) == 4)
+                if constexpr (sizeof(KT) == 4)
                 {
                     // (the word as ONE 8-byte load from its 4-byte aligned place: combining two loaded halves is an operation on the
                     //  loaded registers, which the scheduler puts right behind the loads -- and the wave then waits for them there)
@@ -1605,17 +1606,12 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
                     av[m] = gbp_ops_use(OPS, 1, 3) ? (u64)__builtin_nontemporal_load((const u64_a4 *)r) : 0;
                     kv[m] = (KT)__builtin_nontemporal_load(r + 2);
                 }
-                else if constexpr (AOS)
+                else
                 {
                     typedef u64 v2q __attribute__((ext_vector_type(2)));
                     const v2q rec = __builtin_nontemporal_load((const v2q *)words0 + i); // {word, key}
                     av[m] = rec.x;
                     kv[m] = (KT)rec.y;
-                }
-                else
-                {
-                    kv[m] = __builtin_nontemporal_load(&keys[i]);
-                    av[m] = gbp_ops_use(OPS, 1, 3) ? __builtin_nontemporal_load(&words0[i]) : 0;
                 }
             }
         };
@@ -1643,15 +1639,13 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
                 for (u32 v = NS * 64 + lane; v < total; v += 64)
                 {
                     const u32 i = row_of(v, cs, dl);
-                    if constexpr (AOS && sizeof(KT) == 4)
+                    if constexpr (sizeof(KT) == 4)
                     {
                         const u32 * r = (const u32 *)words0 + (u64)i * 3;
                         update_row((KT)r[2], gbp_ops_use(OPS, 1, 3) ? (u64)r[0] | ((u64)r[1] << 32) : 0, i, std::false_type{}, cs, dl);
                     }
-                    else if constexpr (AOS)
-                        update_row((KT)words0[2 * (u64)i + 1], words0[2 * (u64)i], i, std::false_type{}, cs, dl);
                     else
-                        update_row(keys[i], gbp_ops_use(OPS, 1, 3) ? words0[i] : 0, i, std::false_type{}, cs, dl);
+                        update_row((KT)words0[2 * (u64)i + 1], words0[2 * (u64)i], i, std::false_type{}, cs, dl);
                 }
         };
         {
@@ -2500,6 +2494,44 @@ static size_t agg_part_cell_bytes_masked(const chgpu_agg * a, u64 n, u32 agg_mas
     return b;
 }
 
+// The compile-time update code of the state words (OPS of k_agg_part_lds / k_agg_tiles_lds; 7 = a fixed-point Float64 sum, 9 = its
+// high word).  0 = no code: more than four words, a word the descriptor leaves untouched, a third argument word (pre >= 2), or a
+// fixed-point sum of the second one.
+static u32 agg_update_code(const AggDesc & d, u32 cnt32)
+{
+    if (d.n_words > 4)
+        return 0;
+    u32 word_op[AGG_MAX_WORDS] = {0};
+    for (u32 j = 0; j < d.n_aggs; ++j)
+    {
+        const u32 w = d.a[j].word;
+        if (d.a[j].kind == CHGPU_AGG_COUNT)
+            word_op[w] = ((cnt32 >> w) & 1) ? 5 : 6;
+        else
+        {
+            if (d.a[j].pre >= 2)
+                return 0;
+            word_op[w] = (d.a[j].arg_type == CHGPU_F64 ? 3 : 1) + d.a[j].pre;
+            if ((d.word_fx >> w) & 1)
+            {
+                if (d.a[j].pre != 0)
+                    return 0;
+                word_op[w] = 7, word_op[d.fx_hi[w]] = 9;
+            }
+            if (d.a[j].kind == CHGPU_AGG_AVG)
+                word_op[w + 1] = ((cnt32 >> (w + 1)) & 1) ? 5 : 6;
+        }
+    }
+    u32 ops = 0;
+    for (u32 w = 0; w < d.n_words; ++w)
+    {
+        if (word_op[w] == 0)
+            return 0;
+        ops |= word_op[w] << (4 * w);
+    }
+    return ops;
+}
+
 static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n, u32 P, u32 S, u32 cnt32,
                                u32 agg_mask, u64 chunk_rows, bool probe_only = false)
 {
@@ -2549,10 +2581,8 @@ static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const c
     u32 * run_index = (u32 *)((char *)tidx + idx_b);
     void * pkeys = (char *)run_index + ridx_b;
     // the sorted copy as {word, key} records (one piece per run and tile for the gather instead of two); the records take the key region
-    // and the word region together, and `pwords` is then the base of the record array
-    const bool no_aos = chgpu_opt(ctx, "tune_gb_no_aos", 0) != 0;
-    const bool aos = !no_aos;
-    u64 * pwords = aos ? (u64 *)pkeys : (u64 *)((char *)pkeys + keys_b);
+    // and the word region together, and `pwords` is the base of the record array
+    u64 * pwords = (u64 *)pkeys;
     // the aggregate pass reads the widened words of the sorted copy
     for (u32 j = 0; j < a->n_aggs; ++j)
         if (a->kinds[j] != CHGPU_AGG_COUNT && ((agg_mask >> j) & 1))
@@ -2570,33 +2600,7 @@ static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const c
         d.n_aggs = m;
         agg_localise_desc(a, &d, &cnt32); // the pass's own state words 0 .. n-1 (the caller sized S and P for exactly those)
     }
-    // the compile-time update code (see k_agg_part_lds, OPS)
-    u32 ops = 0;
-    {
-        u32 word_op[AGG_MAX_WORDS] = {0};
-        bool ok = d.n_words <= 4;
-        for (u32 j = 0; j < d.n_aggs && ok; ++j)
-        {
-            const u32 w = d.a[j].word;
-            if (d.a[j].kind == CHGPU_AGG_COUNT)
-                word_op[w] = ((cnt32 >> w) & 1) ? 5 : 6;
-            else
-            {
-                word_op[w] = d.a[j].arg_type == CHGPU_F64 ? 3 : 1;
-                if ((d.word_fx >> w) & 1)
-                    word_op[w] = 7, word_op[d.fx_hi[w]] = 9;
-                if (d.a[j].kind == CHGPU_AGG_AVG)
-                    word_op[w + 1] = ((cnt32 >> (w + 1)) & 1) ? 5 : 6;
-            }
-        }
-        for (u32 w = 0; w < d.n_words && ok; ++w)
-        {
-            ok = ok && word_op[w] != 0;
-            ops |= word_op[w] << (4 * w);
-        }
-        if (!ok)
-            ops = 0;
-    }
+    const u32 ops = agg_update_code(d, cnt32);
     if (ops != 0x51 && ops != 0x15 && ops != 0x1 && ops != 0x53 && ops != 0x3 && ops != 0x61 && ops != 0x16 && ops != 0x97 && ops != 0x957 && ops != 0x967)
         return CHGPU_ERR_NOT_IMPLEMENTED;
     if (probe_only)
@@ -2610,31 +2614,27 @@ static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const c
     CHGPU_HIP(hipMemsetAsync(scratch, 0, tot_b + unit_b + pend_b, ctx->stream));
     int rc = CHGPU_OK;
     const size_t lds_sort = rp_tilesort_lds_bytes(TILE, P, key_w);
-#define GB_TILESORT(TILE_, KT_, AT_, EX_, AOS_)                                                                                                  \
+#define GB_TILESORT(TILE_, KT_, AT_, EX_)                                                                                                        \
     do                                                                                                                                          \
     {                                                                                                                                           \
-        auto kern = k_rp_tilesort<TILE_, KT_, GbpPartFn<KT_>, RP_THREADS, AT_, EX_, AOS_>;                                                       \
+        auto kern = k_rp_tilesort<TILE_, KT_, GbpPartFn<KT_>, RP_THREADS, AT_, EX_>;                                                             \
         rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE; \
         if (rc == CHGPU_OK)                                                                                                                     \
             hipLaunchKernelGGL(kern, dim3(G), dim3(RP_THREADS), lds_sort, ctx->stream, (const KT_ *)key_col->data + row_begin, (const AT_ *)arg_cols[arg_j]->data + row_begin, n, \
                                rows_per_wg, P, (KT_ *)pkeys, pwords, tidx, part_total, GbpPartFn<KT_>{P, GBP_MULT});                             \
     } while (0)
-#define GB_TILESORT_ARG(TILE_, KT_, AOS_)                             \
-    do                                                                \
-    {                                                                 \
-        if (arg_w == 8) GB_TILESORT(TILE_, KT_, u64, 0, AOS_);        \
-        else if (arg_ex == 3) GB_TILESORT(TILE_, KT_, u32, 3, AOS_);  \
-        else if (arg_ex == 4) GB_TILESORT(TILE_, KT_, u32, 4, AOS_);  \
-        else GB_TILESORT(TILE_, KT_, u32, 0, AOS_);                   \
+#define GB_TILESORT_ARG(TILE_, KT_)                             \
+    do                                                          \
+    {                                                           \
+        if (arg_w == 8) GB_TILESORT(TILE_, KT_, u64, 0);        \
+        else if (arg_ex == 3) GB_TILESORT(TILE_, KT_, u32, 3);  \
+        else if (arg_ex == 4) GB_TILESORT(TILE_, KT_, u32, 4);  \
+        else GB_TILESORT(TILE_, KT_, u32, 0);                   \
     } while (0)
-    if (aos && key32)
-        GB_TILESORT_ARG(12288, u32, true);
-    else if (aos)
-        GB_TILESORT_ARG(8192, u64, true);
-    else if (key32)
-        GB_TILESORT_ARG(12288, u32, false);
+    if (key32)
+        GB_TILESORT_ARG(12288, u32);
     else
-        GB_TILESORT_ARG(8192, u64, false);
+        GB_TILESORT_ARG(8192, u64);
 #undef GB_TILESORT_ARG
 #undef GB_TILESORT
     if (rc == CHGPU_OK)
@@ -2644,44 +2644,36 @@ static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const c
         const u32 n4 = (u32)__builtin_popcount(cnt32), n8 = d.n_words - n4;
         const size_t keys_lds = ((size_t)key_w * (S + 1) + 7) & ~(size_t)7;
         const size_t lds_ag = keys_lds + (size_t)(S + 1) * (8 * n8 + 4 * n4) + 16;
-#define GB_TILES(KT_, OPS_, TILE_, AOS_)                                                                                                              \
+#define GB_TILES(KT_, OPS_, TILE_)                                                                                                                    \
     do                                                                                                                                                \
     {                                                                                                                                                 \
-        auto kern = k_agg_tiles_lds<KT_, OPS_, TILE_, AOS_>;                                                                                           \
+        auto kern = k_agg_tiles_lds<KT_, OPS_, TILE_>;                                                                                                 \
         rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ag) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE; \
         if (rc == CHGPU_OK)                                                                                                                           \
             hipLaunchKernelGGL(kern, dim3(G), dim3(1024), lds_ag, ctx->stream, a->t, d, (const KT_ *)pkeys, (const u64 *)pwords, (const u32 *)run_index, n_tiles, P, \
                                pending, S, cnt32, (const u64 *)unit_list, (const u32 *)unit_qstart, unit_ctr, tiles_experiment);                      \
     } while (0)
-#define GB_TILES_OPS(KT_, TILE_, AOS_)                        \
-    switch (ops)                                              \
-    {                                                         \
-        case 0x51: GB_TILES(KT_, 0x51, TILE_, AOS_); break;   \
-        case 0x15: GB_TILES(KT_, 0x15, TILE_, AOS_); break;   \
-        case 0x1: GB_TILES(KT_, 0x1, TILE_, AOS_); break;     \
-        case 0x53: GB_TILES(KT_, 0x53, TILE_, AOS_); break;   \
-        case 0x3: GB_TILES(KT_, 0x3, TILE_, AOS_); break;     \
-        case 0x61: GB_TILES(KT_, 0x61, TILE_, AOS_); break;   \
-        case 0x97: GB_TILES(KT_, 0x97, TILE_, AOS_); break;   \
-        case 0x957: GB_TILES(KT_, 0x957, TILE_, AOS_); break; \
-        case 0x967: GB_TILES(KT_, 0x967, TILE_, AOS_); break; \
-        default: GB_TILES(KT_, 0x16, TILE_, AOS_); break;     \
+#define GB_TILES_OPS(KT_, TILE_)                        \
+    switch (ops)                                        \
+    {                                                   \
+        case 0x51: GB_TILES(KT_, 0x51, TILE_); break;   \
+        case 0x15: GB_TILES(KT_, 0x15, TILE_); break;   \
+        case 0x1: GB_TILES(KT_, 0x1, TILE_); break;     \
+        case 0x53: GB_TILES(KT_, 0x53, TILE_); break;   \
+        case 0x3: GB_TILES(KT_, 0x3, TILE_); break;     \
+        case 0x61: GB_TILES(KT_, 0x61, TILE_); break;   \
+        case 0x97: GB_TILES(KT_, 0x97, TILE_); break;   \
+        case 0x957: GB_TILES(KT_, 0x957, TILE_); break; \
+        case 0x967: GB_TILES(KT_, 0x967, TILE_); break; \
+        default: GB_TILES(KT_, 0x16, TILE_); break;     \
     }
-        if (aos && key32)
+        if (key32)
         {
-            GB_TILES_OPS(u32, 12288, true)
-        }
-        else if (aos)
-        {
-            GB_TILES_OPS(u64, 8192, true)
-        }
-        else if (key32)
-        {
-            GB_TILES_OPS(u32, 12288, false)
+            GB_TILES_OPS(u32, 12288)
         }
         else
         {
-            GB_TILES_OPS(u64, 8192, false)
+            GB_TILES_OPS(u64, 8192)
         }
 #undef GB_TILES_OPS
 #undef GB_TILES
@@ -2691,7 +2683,7 @@ static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const c
     if (rc == CHGPU_OK && hipGetLastError() != hipSuccess)
         rc = CHGPU_ERR_DEVICE;
     if (rc == CHGPU_OK)
-        rc = aos ? agg_finish_rounds_aos(a, d, (const u32 *)pwords, key32 ? 0 : 1, n_pad, pending) : agg_finish_rounds(a, d, pkeys, key32 ? CHGPU_U32 : CHGPU_U64, 0, n_pad, pending);
+        rc = agg_finish_rounds_aos(a, d, (const u32 *)pwords, key32 ? 0 : 1, n_pad, pending);
     else
     {
         (void)hipGetLastError();
@@ -2776,16 +2768,7 @@ static int agg_add_block_partitioned(chgpu_agg * a, const chgpu_col * key_col, c
     }
     if (probe_only)
         return CHGPU_ERR_NOT_IMPLEMENTED;
-    const int gmajor_x = CHGPU_EXPERIMENT(ctx, "experiment_gmajor") ? 1 : 0; // timing experiment only (-DCHGPU_EXPERIMENTS builds): the aggregate pass still reads p-major
-    // (carried tails measured SLOWER than plain runs -- 8.5 / 7.3 vs 6.4 ms at C3 -- and wrote more, not fewer, bytes (PMC WRITE_SIZE 21 GB
-    //  vs 13 GB): a partition's line is then written by two instructions a barrier apart; kept selectable for A/B runs)
-    const int carry_mode = chgpu_opt(ctx, "tune_gb_carry", 0);
-    // (two scatter workgroups per CU in carry mode 2: the histogram is cut into the same row ranges)
-    const bool carry_shape = carry_mode && K == 1 && P <= 256 && n < (1ull << 32);
-    // (experiment: several smaller scatter workgroups per CU so that one's rank / scan phases overlap another's loads and stores)
-    const int wgs_per_cu_x = chgpu_opt(ctx, "tune_gb_scatter_wgs", 1);
-    const bool multi_wg = !carry_mode && (wgs_per_cu_x == 2 || wgs_per_cu_x == 4) && K == 1 && key32 && P <= 256;
-    const u32 G = (u32)ctx->num_cus * (multi_wg ? (u32)wgs_per_cu_x : carry_shape && carry_mode == 2 ? 2 : GBP_WG_PER_CU);
+    const u32 G = (u32)ctx->num_cus * GBP_WG_PER_CU;
     u64 rows_per_wg = (n + G - 1) / G;
     // the scatter's LDS image is tile*(8*K + key bytes) + 24*P bytes and must stay under ~159 KiB (160 KiB per workgroup, 64 B static)
     const size_t row_lds = 8 * K + (key32 ? 4 : 8);
@@ -2794,8 +2777,6 @@ static int agg_add_block_partitioned(chgpu_agg * a, const chgpu_col * key_col, c
     for (u32 cand : {8192u, 12288u})
         if (cand <= tile_cap && cand * row_lds + (size_t)P * 24 + 64 <= 159 * 1024)
             tile = cand;
-    if (multi_wg)
-        tile = 12288 / (u32)wgs_per_cu_x;
     rows_per_wg = (rows_per_wg + tile - 1) / tile * tile;
     const bool debug = chgpu_opt(ctx, "debug", 0) != 0;
     if (debug)
@@ -2864,7 +2845,7 @@ static int agg_add_block_partitioned(chgpu_agg * a, const chgpu_col * key_col, c
     const bool no_wide = chgpu_opt(ctx, "tune_gb_nowide", 0) != 0;
     wide = wide && !no_wide;
     if (wide && key_w == 4)
-        hipLaunchKernelGGL((k_rp_hist_wide<u32, GbpPartFn<u32>>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, (const u32 *)key_col->data + row_begin, n, rows_per_wg, P, counts, GbpPartFn<u32>{P, mult}, gmajor_x);
+        hipLaunchKernelGGL((k_rp_hist_wide<u32, GbpPartFn<u32>>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, (const u32 *)key_col->data + row_begin, n, rows_per_wg, P, counts, GbpPartFn<u32>{P, mult});
     else if (wide)
         hipLaunchKernelGGL((k_rp_hist_wide<u64, GbpPartFn<u64>>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, (const u64 *)key_col->data + row_begin, n, rows_per_wg, P, counts, GbpPartFn<u64>{P, mult});
     else
@@ -2881,30 +2862,12 @@ static int agg_add_block_partitioned(chgpu_agg * a, const chgpu_col * key_col, c
         rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE; \
         if (rc == CHGPU_OK)                                                                                                                     \
             hipLaunchKernelGGL(kern, dim3(G), dim3(GBP_THREADS), lds_sc, ctx->stream, (const void *)key_col->data, a->key_type, row_begin, n, rows_per_wg, P, \
-                               (const u64 *)offsets, gc, (KT_ *)pkeys, mult, gmajor_x);                                                              \
+                               (const u64 *)offsets, gc, (KT_ *)pkeys, mult);                                                                        \
     } while (0)
-        // carried-tail scatter (radix_partition.h): one 8-byte word, wide loads, P <= 256, < 2^32 rows.  carry_mode 2 = 512 threads x
-        // 4096-row tiles x 8-row pieces, two workgroups per CU; 1 = 1024 x 8192 x 16-row pieces, one per CU
-        const bool old_scatter = chgpu_opt(ctx, "tune_gb_old_scatter", 0) != 0;
-        if (!carry_mode && !old_scatter && wide && K == 1 && n + RP_SCATTER_SLACK < (1ull << 32) && P + 1 <= 2 * RP_THREADS)
+        if (wide && K == 1 && n + RP_SCATTER_SLACK < (1ull << 32) && P + 1 <= 2 * RP_THREADS)
         {
             // the branch-free scatter (radix_partition.h): one 8-byte word, wide loads
-            if (multi_wg)
-            {
-#define GB_MULTI(TILE_, THR_)                                                                                                                   \
-    do                                                                                                                                          \
-    {                                                                                                                                           \
-        auto kern = k_rp_scatter<TILE_, u32, true, GbpPartFn<u32>, THR_>;                                                                        \
-        const size_t lds_b = rp_scatter_lds_bytes(TILE_, P, 4, true);                                                                            \
-        rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE; \
-        if (rc == CHGPU_OK)                                                                                                                     \
-            hipLaunchKernelGGL(kern, dim3(G), dim3(THR_), lds_b, ctx->stream, (const u32 *)key_col->data + row_begin, (const u64 *)gc.src[0] + row_begin, n, rows_per_wg, P, \
-                               (const u64 *)offsets, (u32 *)pkeys, gc.dst[0], GbpPartFn<u32>{P, mult});                                          \
-    } while (0)
-                if (wgs_per_cu_x == 2) GB_MULTI(6144, 512); else GB_MULTI(3072, 256);
-#undef GB_MULTI
-            }
-            else if (key32 && rp_scatter_lds_bytes(12288, P, 4, true) <= 159 * 1024)
+            if (key32 && rp_scatter_lds_bytes(12288, P, 4, true) <= 159 * 1024)
             {
                 auto kern = k_rp_scatter<12288, u32, true, GbpPartFn<u32>>;
                 const size_t lds_b = rp_scatter_lds_bytes(12288, P, 4, true);
@@ -2931,22 +2894,6 @@ static int agg_add_block_partitioned(chgpu_agg * a, const chgpu_col * key_col, c
                     hipLaunchKernelGGL(kern, dim3(G), dim3(RP_THREADS), lds_b, ctx->stream, (const u64 *)key_col->data + row_begin, (const u64 *)gc.src[0] + row_begin, n, rows_per_wg, P,
                                        (const u64 *)offsets, (u64 *)pkeys, gc.dst[0], GbpPartFn<u64>{P, mult});
             }
-        }
-        else if (carry_mode && wide && K == 1 && P <= 256 && n < (1ull << 32))
-        {
-#define GB_CARRY(KT_, TILE_, THR_, CG_)                                                                                                          \
-    do                                                                                                                                          \
-    {                                                                                                                                           \
-        auto kern = k_rp_scatter_carry<TILE_, KT_, true, GbpPartFn<KT_>, THR_, CG_>;                                                             \
-        const size_t lds_cy = rp_scatter_carry_lds_bytes(TILE_, P, CG_, sizeof(KT_), true);                                                      \
-        rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_cy) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE; \
-        if (rc == CHGPU_OK)                                                                                                                     \
-            hipLaunchKernelGGL(kern, dim3(G), dim3(THR_), lds_cy, ctx->stream, (const KT_ *)key_col->data + row_begin, (const u64 *)gc.src[0] + row_begin, n, rows_per_wg, P, \
-                               (const u64 *)offsets, (KT_ *)pkeys, gc.dst[0], GbpPartFn<KT_>{P, mult});                                          \
-    } while (0)
-            if (carry_mode == 2) { if (key32) GB_CARRY(u32, 4096, 512, 8); else GB_CARRY(u64, 2048, 512, 8); }
-            else                 { if (key32) GB_CARRY(u32, 8192, 1024, 16); else GB_CARRY(u64, 4096, 1024, 16); }
-#undef GB_CARRY
         }
         else if (tile == 12288) { if (key32) GB_SCATTER(12288, u32); else GB_SCATTER(12288, u64); }
         else if (tile == 8192) { if (key32) GB_SCATTER(8192, u32); else GB_SCATTER(8192, u64); }
@@ -3019,40 +2966,8 @@ static int agg_add_block_partitioned(chgpu_agg * a, const chgpu_col * key_col, c
         hipLaunchKernelGGL(k_gb_units, dim3(1), dim3(1024), 0, ctx->stream, (const u64 *)offsets, G, P, n, chunk_rows, unit_start, unit_ctr);
         const u64 rows_per_chunk = chunk_rows;
         u32 grid = (u32)ctx->num_cus;
-        // the update of the state words as a compile-time code where the common shapes allow it (see k_agg_part_lds, OPS)
-        u32 ops = 0;
-        const bool no_ops = chgpu_opt(ctx, "tune_gb_noops", 0) != 0;
-        {
-            u32 word_op[AGG_MAX_WORDS] = {0};
-            bool ok = !no_ops && a->n_words <= 4;
-            for (u32 j = 0; j < d.n_aggs && ok; ++j)
-            {
-                const u32 w = d.a[j].word;
-                const bool c32 = (cnt32 >> w) & 1;
-                if (d.a[j].kind == CHGPU_AGG_COUNT)
-                    word_op[w] = c32 ? 5 : 6;
-                else
-                {
-                    const bool f = d.a[j].arg_type == CHGPU_F64;
-                    ok = ok && d.a[j].pre < 2;
-                    word_op[w] = (f ? 3 : 1) + d.a[j].pre;
-                    if ((a->word_fx >> w) & 1)
-                    {
-                        ok = ok && d.a[j].pre == 0; // (a fixed-point sum of the second argument word: generic kernel)
-                        word_op[w] = 7, word_op[a->fx_hi[w]] = 9;
-                    }
-                    if (d.a[j].kind == CHGPU_AGG_AVG)
-                        word_op[w + 1] = ((cnt32 >> (w + 1)) & 1) ? 5 : 6;
-                }
-            }
-            for (u32 w = 0; w < a->n_words && ok; ++w)
-            {
-                ok = ok && word_op[w] != 0; // (a pass over a subset of the functions leaves words untouched: generic kernel)
-                ops |= word_op[w] << (4 * w);
-            }
-            if (!ok)
-                ops = 0;
-        }
+        // the update of the state words as a compile-time code where the common shapes allow it
+        const u32 ops = chgpu_opt(ctx, "tune_gb_noops", 0) ? 0 : agg_update_code(d, cnt32);
 #define GB_AGG(KT_, OPS_)                                                                                                                              \
     do                                                                                                                                                \
     {                                                                                                                                                 \
@@ -3169,6 +3084,205 @@ static int agg_add_block_materialised(chgpu_agg * a, const chgpu_col * key_col, 
     return rc;
 }
 
+// executeWithoutKeyImpl (Aggregator.cpp:1276-1321): addBatchSinglePlace per function
+static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 row_begin, u64 row_end, const chgpu_col * filter)
+{
+    chgpu_ctx * ctx = a->ctx;
+    const u64 n = row_end - row_begin;
+    u64 kept = n;
+    if (filter)
+    {
+        // addBatchSinglePlace under a condition (addManyConditional, AggregateFunctionSum.h:138-236); count = countBytesInFilter
+        chgpu_col * fv = nullptr;
+        CHGPU_TRY(chgpu_col_slice(ctx, filter, row_begin, n, &fv));
+        const int rc = chgpu_count_bytes_in_filter(ctx, fv, &kept);
+        chgpu_col_free(fv);
+        CHGPU_TRY(rc);
+    }
+    for (u32 j = 0; j < a->n_aggs; ++j)
+    {
+        u64 * st = &a->host_words[a->word_off[j]];
+        if (a->kinds[j] == CHGPU_AGG_COUNT)
+            st[0] += kept;
+        else if (a->kinds[j] == CHGPU_AGG_MIN || a->kinds[j] == CHGPU_AGG_MAX || a->kinds[j] == CHGPU_AGG_ANY)
+        {
+            if (kept == 0 || n == 0)
+                continue;
+            void * scratch = nullptr;
+            CHGPU_TRY(chgpu_scratch(ctx, 256, &scratch));
+            unsigned long long * dev = (unsigned long long *)scratch;
+            const u8 * cond = filter ? (const u8 *)filter->data : nullptr;
+            u64 v = 0;
+            if (a->kinds[j] != CHGPU_AGG_ANY)
+            {
+                CHGPU_HIP(hipMemsetAsync(dev, 0, 8, ctx->stream));
+                hipLaunchKernelGGL(k_nokey_extremum, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const void *)arg_cols[j]->data, a->arg_types[j], row_begin, n, cond,
+                                   a->kinds[j] == CHGPU_AGG_MIN ? 1 : 0, dev);
+                ctx->counters[6] += 1;
+                CHGPU_HIP(hipGetLastError());
+                CHGPU_TRY(chgpu_read_back(ctx, dev, &v, 8));
+                st[0] = v > st[0] ? v : st[0]; // order keys under an unsigned max (see agg_order_key); zero = no value yet
+            }
+            else if (st[0] == 0) // setIfFirst: only a state without a value takes one
+            {
+                CHGPU_HIP(hipMemsetAsync(dev, 0xFF, 8, ctx->stream));
+                hipLaunchKernelGGL(k_nokey_first_row, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, row_begin, n, cond, dev);
+                CHGPU_HIP(hipGetLastError());
+                CHGPU_TRY(chgpu_read_back(ctx, dev, &v, 8));
+                if (v != ~0ull)
+                {
+                    hipLaunchKernelGGL(k_nokey_load, dim3(1), dim3(64), 0, ctx->stream, (const void *)arg_cols[j]->data, a->arg_types[j], row_begin + v, (u64 *)dev);
+                    CHGPU_HIP(hipGetLastError());
+                    u64 bits = 0;
+                    CHGPU_TRY(chgpu_read_back(ctx, dev, &bits, 8));
+                    st[0] = ~(a->any_seq + v);
+                    st[1] = bits;
+                }
+                ctx->counters[6] += 2;
+            }
+        }
+        else
+        {
+            if (filter)
+                CHGPU_TRY(chgpu_sum_add_many_conditional(ctx, arg_cols[j], filter, row_begin, row_end, st));
+            else
+                CHGPU_TRY(chgpu_sum_add_many(ctx, arg_cols[j], row_begin, row_end, st));
+            if (a->kinds[j] == CHGPU_AGG_AVG)
+                st[1] += kept;
+        }
+    }
+    a->any_seq += n;
+    a->nokey_kept += kept;
+    return CHGPU_OK;
+}
+
+// RANGE mode of the partition-aggregate kernel: 4/8-byte keys; a launch takes at most GBP_MAX_K argument columns of one
+// width (8, 4 or 1 B), so the aggregate functions are split into PASSES over the same rows -- each pass re-reads the key
+// column and updates its own state words of the same groups (TPC-H Q1's seven sums and averages: 4 passes x ~20 B/row
+// instead of one trip through the generic kernel, which is 6x slower per row).
+static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n, const chgpu_col * filter,
+                                const AggDesc & d, u64 * pending, u64 n_words64, u32 lds_cells)
+{
+    chgpu_ctx * ctx = a->ctx;
+    struct Pass
+    {
+        u32 n = 0;           // argument columns in this pass
+        u32 agg[GBP_MAX_K];  // their aggregate indices
+        size_t aw = 8;
+    };
+    Pass passes[AGG_MAX_AGGS];
+    u32 n_passes = 0;
+    for (u32 j = 0; j < a->n_aggs; ++j)
+    {
+        if (a->kinds[j] == CHGPU_AGG_COUNT)
+            continue;
+        const size_t w = chgpu_type_size(a->arg_types[j]);
+        u32 p = 0;
+        for (; p < n_passes; ++p) // first pass of this width with a free slot
+            if (passes[p].aw == w && passes[p].n < GBP_MAX_K)
+                break;
+        if (p == n_passes)
+        {
+            passes[n_passes].aw = w;
+            ++n_passes;
+        }
+        passes[p].agg[passes[p].n++] = j;
+    }
+    if (n_passes == 0)
+        n_passes = 1; // only count(): one pass without argument columns
+
+    const bool key32 = chgpu_type_size(a->key_type) <= 4, key8 = chgpu_type_size(a->key_type) == 1, key16 = chgpu_type_size(a->key_type) == 2;
+    u32 cnt32 = 0;
+    (void)agg_part_cell_bytes(a, n, &cnt32);
+    const u32 n4 = (u32)__builtin_popcount(cnt32), n8 = a->n_words - n4;
+    // cells: four times the promised groups (4096 when nothing was promised), bounded by ~150 KiB of LDS; tables of up
+    // to ~76 KiB let two 1024-thread workgroups share a CU
+    const u32 s_dflt = (u32)chgpu_opt(ctx, "tune_agg_ranged_s", 4096);
+    u32 S = s_dflt;
+    if (a->size_hint)
+        for (S = 1024; S < 4 * a->size_hint && S < lds_cells; S <<= 1)
+            ;
+    if (S > lds_cells)
+        S = lds_cells;
+    const size_t keys_lds = ((size_t)(key32 ? 4 : 8) * (S + 1) + 7) & ~(size_t)7;
+    const size_t lds_ag = keys_lds + (size_t)(S + 1) * (8 * n8 + 4 * n4) + 16;
+    const u32 wg_per_cu = lds_ag <= 76 * 1024 ? 2 : 1;
+    // flushes may claim up to grid * (S+1) cells above max fill: keep that inside the slack (capacity/2)
+    const u64 max_grid = (a->t.capacity / 2) / (S + 1);
+    u64 chunks = (u64)ctx->num_cus * wg_per_cu;
+    if (chunks > max_grid)
+        chunks = max_grid ? max_grid : 1;
+    if (chunks > (n + 4095) / 4096)
+        chunks = (n + 4095) / 4096;
+    const u64 rows_per_chunk = ((n + chunks - 1) / chunks + 63) / 64 * 64;
+    chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
+    const u8 * cond_ptr = filter ? (const u8 *)filter->data + row_begin : nullptr;
+    for (u32 p = 0; p < n_passes; ++p)
+    {
+        // this pass's descriptor: its argument functions, plus every count() in the first pass; state word indices are
+        // the aggregator's own, so all passes meet in the same cells
+        AggDesc dp = d;
+        dp.n_aggs = 0;
+        const void * rwords[GBP_MAX_K] = {nullptr, nullptr};
+        for (u32 c = 0; c < passes[p].n; ++c)
+        {
+            const u32 j = passes[p].agg[c];
+            dp.a[dp.n_aggs] = d.a[j];
+            dp.a[dp.n_aggs].pre = c;
+            ++dp.n_aggs;
+            rwords[c] = (const char *)arg_cols[j]->data + row_begin * passes[p].aw;
+        }
+        if (p == 0)
+            for (u32 j = 0; j < a->n_aggs; ++j)
+                if (a->kinds[j] == CHGPU_AGG_COUNT)
+                    dp.a[dp.n_aggs++] = d.a[j];
+        const u32 rk = passes[p].n;
+        const size_t aw = passes[p].aw;
+        bool need_ext = false; // a signed narrow integer or Float32 argument in this pass
+        for (u32 c = 0; c < passes[p].n; ++c)
+        {
+            const int at = a->arg_types[passes[p].agg[c]];
+            need_ext = need_ext || at == CHGPU_I8 || at == CHGPU_I16 || at == CHGPU_I32 || at == CHGPU_F32;
+        }
+        CHGPU_HIP(hipMemsetAsync(pending, 0, n_words64 * sizeof(u64), ctx->stream));
+#define RANGE_LAUNCH_X(KT_, AW_, KS_, X_)                                                                                                              \
+    do                                                                                                                                                \
+    {                                                                                                                                                 \
+        CHGPU_HIP(hipFuncSetAttribute((const void *)k_agg_part_lds<KT_, AW_, KS_, X_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ag));     \
+        hipLaunchKernelGGL((k_agg_part_lds<KT_, AW_, KS_, X_>), dim3((u32)chunks), dim3(1024), lds_ag, ctx->stream, a->t, dp, (const KS_ *)key_col->data + row_begin, \
+                           rwords[0], rwords[1], (const u64 *)nullptr, 1u, (u32)chunks, n, pending, S, rk, cnt32, rows_per_chunk, (const u32 *)nullptr,  \
+                           (u32 *)nullptr, cond_ptr);                                                                                                 \
+    } while (0)
+#define RANGE_LAUNCH_KS(KT_, AW_, KS_) do { if ((AW_) < 8 && need_ext) RANGE_LAUNCH_X(KT_, AW_, KS_, true); else RANGE_LAUNCH_X(KT_, AW_, KS_, false); } while (0)
+#define RANGE_LAUNCH(KT_, AW_) RANGE_LAUNCH_KS(KT_, AW_, KT_)
+        if (key8)
+        {
+            if (aw == 8) RANGE_LAUNCH_KS(u32, 8, u8); else if (aw == 4) RANGE_LAUNCH_KS(u32, 4, u8); else if (aw == 2) RANGE_LAUNCH_KS(u32, 2, u8); else RANGE_LAUNCH_KS(u32, 1, u8);
+        }
+        else if (key16) // UInt16 (Date) / Int16 keys
+        {
+            if (aw == 8) RANGE_LAUNCH_KS(u32, 8, u16); else if (aw == 4) RANGE_LAUNCH_KS(u32, 4, u16); else if (aw == 2) RANGE_LAUNCH_KS(u32, 2, u16); else RANGE_LAUNCH_KS(u32, 1, u16);
+        }
+        else if (key32)
+        {
+            if (aw == 8) RANGE_LAUNCH(u32, 8); else if (aw == 4) RANGE_LAUNCH(u32, 4); else if (aw == 2) RANGE_LAUNCH(u32, 2); else RANGE_LAUNCH(u32, 1);
+        }
+        else
+        {
+            if (aw == 8) RANGE_LAUNCH(u64, 8); else if (aw == 4) RANGE_LAUNCH(u64, 4); else if (aw == 2) RANGE_LAUNCH(u64, 2); else RANGE_LAUNCH(u64, 1);
+        }
+#undef RANGE_LAUNCH
+#undef RANGE_LAUNCH_KS
+#undef RANGE_LAUNCH_X
+        ctx->counters[6] += 1;
+        CHGPU_HIP(hipGetLastError());
+        // rows this pass could not place (table at max fill) are retried with THIS pass's functions only
+        CHGPU_TRY(agg_finish_rounds(a, dp, key_col->data, a->key_type, row_begin, n, pending));
+    }
+    ctx->counters[5] += n;
+    return CHGPU_OK;
+}
+
 static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 row_end,
                               const chgpu_col * filter)
 {
@@ -3192,74 +3306,7 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
                       (unsigned long long)arg_cols[j]->rows, (unsigned long long)row_end);
     }
     if (a->key_type < 0)
-    {
-        // executeWithoutKeyImpl (Aggregator.cpp:1276-1321): addBatchSinglePlace per function
-        u64 kept = n;
-        if (filter)
-        {
-            // addBatchSinglePlace under a condition (addManyConditional, AggregateFunctionSum.h:138-236); count = countBytesInFilter
-            chgpu_col * fv = nullptr;
-            CHGPU_TRY(chgpu_col_slice(ctx, filter, row_begin, n, &fv));
-            const int rc = chgpu_count_bytes_in_filter(ctx, fv, &kept);
-            chgpu_col_free(fv);
-            CHGPU_TRY(rc);
-        }
-        for (u32 j = 0; j < a->n_aggs; ++j)
-        {
-            u64 * st = &a->host_words[a->word_off[j]];
-            if (a->kinds[j] == CHGPU_AGG_COUNT)
-                st[0] += kept;
-            else if (a->kinds[j] == CHGPU_AGG_MIN || a->kinds[j] == CHGPU_AGG_MAX || a->kinds[j] == CHGPU_AGG_ANY)
-            {
-                if (kept == 0 || n == 0)
-                    continue;
-                void * scratch = nullptr;
-                CHGPU_TRY(chgpu_scratch(ctx, 256, &scratch));
-                unsigned long long * dev = (unsigned long long *)scratch;
-                const u8 * cond = filter ? (const u8 *)filter->data : nullptr;
-                u64 v = 0;
-                if (a->kinds[j] != CHGPU_AGG_ANY)
-                {
-                    CHGPU_HIP(hipMemsetAsync(dev, 0, 8, ctx->stream));
-                    hipLaunchKernelGGL(k_nokey_extremum, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const void *)arg_cols[j]->data, a->arg_types[j], row_begin, n, cond,
-                                       a->kinds[j] == CHGPU_AGG_MIN ? 1 : 0, dev);
-                    ctx->counters[6] += 1;
-                    CHGPU_HIP(hipGetLastError());
-                    CHGPU_TRY(chgpu_read_back(ctx, dev, &v, 8));
-                    st[0] = v > st[0] ? v : st[0]; // order keys under an unsigned max (see agg_order_key); zero = no value yet
-                }
-                else if (st[0] == 0) // setIfFirst: only a state without a value takes one
-                {
-                    CHGPU_HIP(hipMemsetAsync(dev, 0xFF, 8, ctx->stream));
-                    hipLaunchKernelGGL(k_nokey_first_row, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, row_begin, n, cond, dev);
-                    CHGPU_HIP(hipGetLastError());
-                    CHGPU_TRY(chgpu_read_back(ctx, dev, &v, 8));
-                    if (v != ~0ull)
-                    {
-                        hipLaunchKernelGGL(k_nokey_load, dim3(1), dim3(64), 0, ctx->stream, (const void *)arg_cols[j]->data, a->arg_types[j], row_begin + v, (u64 *)dev);
-                        CHGPU_HIP(hipGetLastError());
-                        u64 bits = 0;
-                        CHGPU_TRY(chgpu_read_back(ctx, dev, &bits, 8));
-                        st[0] = ~(a->any_seq + v);
-                        st[1] = bits;
-                    }
-                    ctx->counters[6] += 2;
-                }
-            }
-            else
-            {
-                if (filter)
-                    CHGPU_TRY(chgpu_sum_add_many_conditional(ctx, arg_cols[j], filter, row_begin, row_end, st));
-                else
-                    CHGPU_TRY(chgpu_sum_add_many(ctx, arg_cols[j], row_begin, row_end, st));
-                if (a->kinds[j] == CHGPU_AGG_AVG)
-                    st[1] += kept;
-            }
-        }
-        a->any_seq += n;
-        a->nokey_kept += kept;
-        return CHGPU_OK;
-    }
+        return agg_add_nokey(a, arg_cols, row_begin, row_end, filter);
     CHGPU_REQUIRE(key_col, CHGPU_ERR_BAD_ARGUMENTS, "key column is NULL");
     CHGPU_REQUIRE(key_col->type == a->key_type, CHGPU_ERR_BAD_ARGUMENTS, "key column has type %d, expected %d", key_col->type, a->key_type);
     CHGPU_REQUIRE(row_end <= key_col->rows, CHGPU_ERR_SIZES_MISMATCH, "key column has %llu rows, block ends at %llu",
@@ -3428,132 +3475,10 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
     CHGPU_TRY(agg_ensure_table(a));
     // strategy: LDS-staged unless the caller promised a large cardinality (where nearly every key misses the LDS table)
     const bool use_lds = a->size_hint <= 65536; // beyond that nearly every key misses a workgroup's LDS table
-    // RANGE mode of the partition-aggregate kernel: 4/8-byte keys; a launch takes at most GBP_MAX_K argument columns of one
-    // width (8, 4 or 1 B), so the aggregate functions are split into PASSES over the same rows -- each pass re-reads the key
-    // column and updates its own state words of the same groups (TPC-H Q1's seven sums and averages: 4 passes x ~20 B/row
-    // instead of one trip through the generic kernel, which is 6x slower per row).
-    bool ranged = use_lds && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0); // keys of 1, 2, 4 or 8 bytes: every key type
-
+    // RANGE mode of the partition-aggregate kernel (agg_add_block_ranged)
+    const bool ranged = use_lds && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0); // keys of 1, 2, 4 or 8 bytes: every key type
     if (ranged)
-    {
-        struct Pass
-        {
-            u32 n = 0;           // argument columns in this pass
-            u32 agg[GBP_MAX_K];  // their aggregate indices
-            size_t aw = 8;
-        };
-        Pass passes[AGG_MAX_AGGS];
-        u32 n_passes = 0;
-        for (u32 j = 0; j < a->n_aggs; ++j)
-        {
-            if (a->kinds[j] == CHGPU_AGG_COUNT)
-                continue;
-            const size_t w = chgpu_type_size(a->arg_types[j]);
-            u32 p = 0;
-            for (; p < n_passes; ++p) // first pass of this width with a free slot
-                if (passes[p].aw == w && passes[p].n < GBP_MAX_K)
-                    break;
-            if (p == n_passes)
-            {
-                passes[n_passes].aw = w;
-                ++n_passes;
-            }
-            passes[p].agg[passes[p].n++] = j;
-        }
-        if (n_passes == 0)
-            n_passes = 1; // only count(): one pass without argument columns
-
-        const bool key32 = chgpu_type_size(a->key_type) <= 4, key8 = chgpu_type_size(a->key_type) == 1, key16 = chgpu_type_size(a->key_type) == 2;
-        u32 cnt32 = 0;
-        (void)agg_part_cell_bytes(a, n, &cnt32);
-        const u32 n4 = (u32)__builtin_popcount(cnt32), n8 = a->n_words - n4;
-        // cells: four times the promised groups (4096 when nothing was promised), bounded by ~150 KiB of LDS; tables of up
-        // to ~76 KiB let two 1024-thread workgroups share a CU
-        const u32 s_dflt = (u32)chgpu_opt(ctx, "tune_agg_ranged_s", 4096);
-        u32 S = s_dflt;
-        if (a->size_hint)
-            for (S = 1024; S < 4 * a->size_hint && S < lds_cells; S <<= 1)
-                ;
-        if (S > lds_cells)
-            S = lds_cells;
-        const size_t keys_lds = ((size_t)(key32 ? 4 : 8) * (S + 1) + 7) & ~(size_t)7;
-        const size_t lds_ag = keys_lds + (size_t)(S + 1) * (8 * n8 + 4 * n4) + 16;
-        const u32 wg_per_cu = lds_ag <= 76 * 1024 ? 2 : 1;
-        // flushes may claim up to grid * (S+1) cells above max fill: keep that inside the slack (capacity/2)
-        const u64 max_grid = (a->t.capacity / 2) / (S + 1);
-        u64 chunks = (u64)ctx->num_cus * wg_per_cu;
-        if (chunks > max_grid)
-            chunks = max_grid ? max_grid : 1;
-        if (chunks > (n + 4095) / 4096)
-            chunks = (n + 4095) / 4096;
-        const u64 rows_per_chunk = ((n + chunks - 1) / chunks + 63) / 64 * 64;
-        chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
-        const u8 * cond_ptr = filter ? (const u8 *)filter->data + row_begin : nullptr;
-        for (u32 p = 0; p < n_passes; ++p)
-        {
-            // this pass's descriptor: its argument functions, plus every count() in the first pass; state word indices are
-            // the aggregator's own, so all passes meet in the same cells
-            AggDesc dp = d;
-            dp.n_aggs = 0;
-            const void * rwords[GBP_MAX_K] = {nullptr, nullptr};
-            for (u32 c = 0; c < passes[p].n; ++c)
-            {
-                const u32 j = passes[p].agg[c];
-                dp.a[dp.n_aggs] = d.a[j];
-                dp.a[dp.n_aggs].pre = c;
-                ++dp.n_aggs;
-                rwords[c] = (const char *)arg_cols[j]->data + row_begin * passes[p].aw;
-            }
-            if (p == 0)
-                for (u32 j = 0; j < a->n_aggs; ++j)
-                    if (a->kinds[j] == CHGPU_AGG_COUNT)
-                        dp.a[dp.n_aggs++] = d.a[j];
-            const u32 rk = passes[p].n;
-            const size_t aw = passes[p].aw;
-            bool need_ext = false; // a signed narrow integer or Float32 argument in this pass
-            for (u32 c = 0; c < passes[p].n; ++c)
-            {
-                const int at = a->arg_types[passes[p].agg[c]];
-                need_ext = need_ext || at == CHGPU_I8 || at == CHGPU_I16 || at == CHGPU_I32 || at == CHGPU_F32;
-            }
-            CHGPU_HIP(hipMemsetAsync(pending, 0, n_words64 * sizeof(u64), ctx->stream));
-#define RANGE_LAUNCH_X(KT_, AW_, KS_, X_)                                                                                                              \
-    do                                                                                                                                                \
-    {                                                                                                                                                 \
-        CHGPU_HIP(hipFuncSetAttribute((const void *)k_agg_part_lds<KT_, AW_, KS_, X_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ag));     \
-        hipLaunchKernelGGL((k_agg_part_lds<KT_, AW_, KS_, X_>), dim3((u32)chunks), dim3(1024), lds_ag, ctx->stream, a->t, dp, (const KS_ *)key_col->data + row_begin, \
-                           rwords[0], rwords[1], (const u64 *)nullptr, 1u, (u32)chunks, n, pending, S, rk, cnt32, rows_per_chunk, (const u32 *)nullptr,  \
-                           (u32 *)nullptr, cond_ptr);                                                                                                 \
-    } while (0)
-#define RANGE_LAUNCH_KS(KT_, AW_, KS_) do { if ((AW_) < 8 && need_ext) RANGE_LAUNCH_X(KT_, AW_, KS_, true); else RANGE_LAUNCH_X(KT_, AW_, KS_, false); } while (0)
-#define RANGE_LAUNCH(KT_, AW_) RANGE_LAUNCH_KS(KT_, AW_, KT_)
-            if (key8)
-            {
-                if (aw == 8) RANGE_LAUNCH_KS(u32, 8, u8); else if (aw == 4) RANGE_LAUNCH_KS(u32, 4, u8); else if (aw == 2) RANGE_LAUNCH_KS(u32, 2, u8); else RANGE_LAUNCH_KS(u32, 1, u8);
-            }
-            else if (key16) // UInt16 (Date) / Int16 keys
-            {
-                if (aw == 8) RANGE_LAUNCH_KS(u32, 8, u16); else if (aw == 4) RANGE_LAUNCH_KS(u32, 4, u16); else if (aw == 2) RANGE_LAUNCH_KS(u32, 2, u16); else RANGE_LAUNCH_KS(u32, 1, u16);
-            }
-            else if (key32)
-            {
-                if (aw == 8) RANGE_LAUNCH(u32, 8); else if (aw == 4) RANGE_LAUNCH(u32, 4); else if (aw == 2) RANGE_LAUNCH(u32, 2); else RANGE_LAUNCH(u32, 1);
-            }
-            else
-            {
-                if (aw == 8) RANGE_LAUNCH(u64, 8); else if (aw == 4) RANGE_LAUNCH(u64, 4); else if (aw == 2) RANGE_LAUNCH(u64, 2); else RANGE_LAUNCH(u64, 1);
-            }
-#undef RANGE_LAUNCH
-#undef RANGE_LAUNCH_KS
-#undef RANGE_LAUNCH_X
-            ctx->counters[6] += 1;
-            CHGPU_HIP(hipGetLastError());
-            // rows this pass could not place (table at max fill) are retried with THIS pass's functions only
-            CHGPU_TRY(agg_finish_rounds(a, dp, key_col->data, a->key_type, row_begin, n, pending));
-        }
-        ctx->counters[5] += n;
-        return CHGPU_OK;
-    }
+        return agg_add_block_ranged(a, key_col, arg_cols, row_begin, n, filter, d, pending, n_words64, lds_cells);
     if (use_lds)
     {
         // LDS cells per workgroup: the largest power of two with (1 + n_words) * 8 * (S+1) <= AGG_LDS_BYTES

@@ -1,4 +1,4 @@
-// radix_partition.h — the two kernels of an exact (histogram-first) radix partition with carried tails, shared by the GROUP BY
+// radix_partition.h — the kernels of an exact (histogram-first) radix partition and of the tile sort, shared by the GROUP BY
 // (agg_kernels.hip: rows -> partitions that fit an LDS table) and the join probe (join_kernels.hip: probe keys -> table regions that
 // fit an XCD's L2).  The partition function is a functor so both callers run the same code.
 #pragma once
@@ -11,7 +11,7 @@ static constexpr u32 RP_SCATTER_SLACK = 12288; // rows of slack k_rp_scatter nee
 // Same histogram with 16-byte nontemporal key loads (4- and 8-byte keys whose first row is 16-byte aligned): four loads
 // per lane are issued before the first LDS atomic.
 template <typename KT, typename PartFn>
-__global__ __launch_bounds__(RP_THREADS) void k_rp_hist_wide(const KT * __restrict__ keys, u64 n, u64 rows_per_wg, u32 P, u32 * __restrict__ counts, PartFn part_fn, int gmajor = 0)
+__global__ __launch_bounds__(RP_THREADS) void k_rp_hist_wide(const KT * __restrict__ keys, u64 n, u64 rows_per_wg, u32 P, u32 * __restrict__ counts, PartFn part_fn)
 {
     constexpr u32 GBP_THREADS = RP_THREADS;
     constexpr u32 GBP_MAX_P = RP_MAX_P;
@@ -54,223 +54,11 @@ __global__ __launch_bounds__(RP_THREADS) void k_rp_hist_wide(const KT * __restri
         atomicAdd(&cnt[part_fn(keys[i])], 1u);
     __syncthreads();
     for (u32 p = threadIdx.x; p < P; p += GBP_THREADS)
-        counts[gmajor ? (u64)blockIdx.x * P + p : (u64)p * gridDim.x + blockIdx.x] = cnt[p];
+        counts[(u64)p * gridDim.x + blockIdx.x] = cnt[p];
 }
-
-// The same pass with the partial lines of every partition run CARRIED from tile to tile in LDS, so that global memory only ever
-// sees whole, aligned 16-row pieces of a partition's output (64 B of 4-byte keys, 128 B of 8-byte words): a run of ~32-48 rows
-// that starts and ends anywhere leaves a partial line at both ends, the L2 evicts it before the next tile (22 us and 4.7 MB of
-// stores per XCD later) completes it, and HBM pays a read-modify-write for it -- 1.5-1.85x the bytes of the rows (PMC WRITE_SIZE).
-// Per partition the workgroup keeps: base = the output row where its carried rows start (16-row aligned after the first flush),
-// ccnt <= 15 carried rows in carry_key / carry_word.  A tile's sorted rows of partition p continue at base + ccnt; everything
-// below the last 16-row boundary is written, the tail becomes the new carry.  Old carries are written by 16 consecutive lanes
-// per partition together with the stage rows that complete their line (same tile, microseconds apart: the L2 merges them).
-// One 8-byte argument word, WIDE loads only (the shape of config C3); P <= 256.
-// dynamic LDS: stage_word u64[TILE] | carry_word u64[P*CG] (both only with HAS_WORD) | stage_key KT[TILE] | carry_key KT[P*CG] |
-//              base | delta | obase | ccnt | tile_cnt | tile_off | ocnt, each u32[P]      (rp_scatter_carry_lds_bytes)
-// PartFn: u32 operator()(KT key) const -> partition in [0, P).  HAS_WORD = false: keys only (words / out_words unused).
-// THREADS x TILE: 1024 x 8192 runs one workgroup per CU; 512 x 4096 with CG = 8 fits two (<= 80 KiB of LDS each), whose memory and
-// LDS phases then overlap -- a single workgroup drains its stores (s_waitcnt vmcnt(0)) before every tile.  Output rows are 32-bit
-// (the callers bound a call below 2^32 rows).
-template <u32 GBP_TILE, typename KT, bool HAS_WORD, typename PartFn, u32 THREADS = RP_THREADS, u32 CG = 16>
-__global__ __launch_bounds__(THREADS) void k_rp_scatter_carry(const KT * __restrict__ keys, const u64 * __restrict__ words, u64 n, u64 rows_per_wg, u32 P,
-                                                              const u64 * __restrict__ offsets, KT * __restrict__ out_keys, u64 * __restrict__ out_words, PartFn part_fn)
-{
-    constexpr u32 GBP_THREADS = THREADS;
-    extern __shared__ __attribute__((aligned(16))) unsigned char gb_lds[];
-    u64 * stage_word = (u64 *)gb_lds;
-    u64 * carry_word = stage_word + (HAS_WORD ? GBP_TILE : 0);
-    KT * stage_key = (KT *)(carry_word + (HAS_WORD ? (size_t)P * CG : 0));
-    KT * carry_key = stage_key + GBP_TILE;
-    u32 * base = (u32 *)(carry_key + (size_t)P * CG);
-    u32 * delta = base + P;
-    u32 * obase = delta + P;
-    u32 * ccnt = obase + P;
-    u32 * tile_cnt = ccnt + P;
-    u32 * tile_off = tile_cnt + P;
-    u32 * ocnt = tile_off + P;
-    __shared__ u32 wave_tot[GBP_THREADS / 64];
-
-    for (u32 p = threadIdx.x; p < P; p += GBP_THREADS)
-    {
-        base[p] = (u32)offsets[(u64)p * gridDim.x + blockIdx.x];
-        ccnt[p] = 0;
-        tile_cnt[p] = 0;
-    }
-    __syncthreads();
-    const u64 r0 = (u64)blockIdx.x * rows_per_wg;
-    const u64 r1 = r0 + rows_per_wg < n ? r0 + rows_per_wg : n;
-    constexpr u32 RPT = GBP_TILE / GBP_THREADS;
-    static_assert(RPT % 2 == 0, "row pairs");
-    KT key[RPT];
-    u64 argw[HAS_WORD ? RPT : 1];
-    typedef u64 v2q __attribute__((ext_vector_type(2)));
-    typedef u32 v2d __attribute__((ext_vector_type(2)));
-    auto row_of = [&](u64 tb, u32 j) -> u64 { return tb + (u64)(j >> 1) * (2 * GBP_THREADS) + 2 * threadIdx.x + (j & 1); };
-    auto load_tile = [&](u64 tb) {
-#pragma unroll
-        for (u32 j = 0; j < RPT; j += 2)
-        {
-            const u64 i = row_of(tb, j);
-            if (i + 1 < r1)
-            {
-                if constexpr (sizeof(KT) == 4)
-                {
-                    const v2d kk = __builtin_nontemporal_load((const v2d *)(keys + i));
-                    key[j] = kk.x, key[j + 1] = kk.y;
-                }
-                else
-                {
-                    const v2q kk = __builtin_nontemporal_load((const v2q *)(keys + i));
-                    key[j] = kk.x, key[j + 1] = kk.y;
-                }
-                if constexpr (HAS_WORD)
-                {
-                    const v2q a = __builtin_nontemporal_load((const v2q *)(words + i));
-                    argw[j] = a.x, argw[j + 1] = a.y;
-                }
-            }
-            else
-            {
-                const bool in = i < r1;
-                key[j] = in ? keys[i] : (KT)0;
-                key[j + 1] = 0;
-                if constexpr (HAS_WORD)
-                {
-                    argw[j] = in ? words[i] : 0;
-                    argw[j + 1] = 0;
-                }
-            }
-        }
-    };
-    if (r0 < r1)
-        load_tile(r0);
-    for (u64 tbase = r0; tbase < r1; tbase += GBP_TILE)
-    {
-        u32 part[RPT], rank[RPT];
-        // 1. a rank inside the tile's partition bucket
-#pragma unroll
-        for (u32 j = 0; j < RPT; ++j)
-        {
-            part[j] = ~0u;
-            if (row_of(tbase, j) < r1)
-            {
-                part[j] = part_fn(key[j]);
-                rank[j] = atomicAdd(&tile_cnt[part[j]], 1u);
-            }
-        }
-        __syncthreads();
-        // 2. exclusive scan of tile_cnt[P] -> tile_off[P] (P <= 2 * threads); per partition: where its rows go and what stays
-        {
-            const u32 e0 = threadIdx.x * 2, e1 = e0 + 1;
-            const u32 c0 = e0 < P ? tile_cnt[e0] : 0, c1 = e1 < P ? tile_cnt[e1] : 0;
-            const u32 v = c0 + c1;
-            const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-            u32 inc = v;
-#pragma unroll
-            for (int dlt = 1; dlt < 64; dlt <<= 1)
-            {
-                const u32 o = __shfl_up(inc, dlt, WAVE);
-                if (lane >= (u32)dlt)
-                    inc += o;
-            }
-            if (lane == 63)
-                wave_tot[wave] = inc;
-            __syncthreads();
-            u32 off = inc - v;
-            for (u32 w = 0; w < wave; ++w)
-                off += wave_tot[w];
-            auto plan = [&](u32 p, u32 toff, u32 nnew) {
-                const u32 b = base[p];
-                const u32 c = ccnt[p];
-                const u32 end = b + c + nnew;
-                const u32 fe = end & ~(CG - 1);
-                const bool flush = fe > b;
-                tile_off[p] = toff;
-                delta[p] = b + c - toff;          // stage position -> output row (modulo 2^32: the sum with a position is exact)
-                obase[p] = b;
-                ocnt[p] = flush ? c : 0;          // old carry rows that leave now (all of them: they sit below fe)
-                base[p] = flush ? fe : b;         // rows at or above it stay in LDS as carry slot (row - base)
-                ccnt[p] = end - (flush ? fe : b);
-                tile_cnt[p] = 0;
-            };
-            if (e0 < P)
-                plan(e0, off, c0);
-            if (e1 < P)
-                plan(e1, off + c0, c1);
-            static_assert(2 * THREADS >= 256, "the scan covers two partitions per thread");
-        }
-        __syncthreads();
-        // 3. counting sort into the LDS staging arrays; the carried rows that leave are written out by 16 lanes per partition
-#pragma unroll
-        for (u32 j = 0; j < RPT; ++j)
-        {
-            if (part[j] == ~0u)
-                continue;
-            const u32 pos = tile_off[part[j]] + rank[j];
-            stage_key[pos] = key[j];
-            if constexpr (HAS_WORD)
-                stage_word[pos] = argw[j];
-        }
-        for (u32 slot = threadIdx.x; slot < P * CG; slot += GBP_THREADS)
-        {
-            const u32 p = slot / CG, i = slot % CG;
-            if (i < ocnt[p])
-            {
-                const u32 dst = obase[p] + i;
-                out_keys[dst] = carry_key[slot];
-                if constexpr (HAS_WORD)
-                    out_words[dst] = carry_word[slot];
-            }
-        }
-        if (tbase + GBP_TILE < r1)
-            load_tile(tbase + GBP_TILE); // prefetch: lands while this tile is written out
-        __syncthreads();
-        // 4. stage rows below their partition's new base go to global memory (consecutive lanes -> consecutive rows of a run), the
-        //    rest becomes the partition's carry
-        const u32 tile_rows = (u32)(r1 - tbase < GBP_TILE ? r1 - tbase : GBP_TILE);
-        for (u32 pos = threadIdx.x; pos < tile_rows; pos += GBP_THREADS)
-        {
-            const KT k = stage_key[pos];
-            const u32 p = part_fn(k);
-            const u32 dst = delta[p] + pos;
-            const u32 nb = base[p];
-            if (dst < nb)
-            {
-                out_keys[dst] = k;
-                if constexpr (HAS_WORD)
-                    out_words[dst] = stage_word[pos];
-            }
-            else
-            {
-                const u32 cs = p * CG + (dst - nb);
-                carry_key[cs] = k;
-                if constexpr (HAS_WORD)
-                    carry_word[cs] = stage_word[pos];
-            }
-        }
-        // no barrier: the next tile's step 1 touches only tile_cnt[] (cleared in step 2); its step 2 -- the first writer of the
-        // per-partition plan -- and its step 3 -- the first reader of the carries written above -- sit behind the barrier that ends
-        // step 1, which every wave reaches only after it has finished step 4 of this tile
-    }
-    __syncthreads();
-    // the last partial pieces
-    for (u32 slot = threadIdx.x; slot < P * CG; slot += GBP_THREADS)
-    {
-        const u32 p = slot / CG, i = slot % CG;
-        if (i < ccnt[p])
-        {
-            const u32 dst = base[p] + i;
-            out_keys[dst] = carry_key[slot];
-            if constexpr (HAS_WORD)
-                out_words[dst] = carry_word[slot];
-        }
-    }
-}
-
 
 // ---------------------------------------------------------------------------------------------
-// k_rp_scatter: the partition pass without carried tails, written so that NO branch surrounds an LDS or memory operation inside a
+// k_rp_scatter: the partition pass, written so that NO branch surrounds an LDS or memory operation inside a
 // step.  The first version of this pass handled every row inside its own `if (row < end)` region; hipcc then waits for each LDS
 // round trip before it issues the next (s_waitcnt lgkmcnt(0) at every control-flow join), a wave spends its time parked
 // (SQ_WAIT_ANY = 72 % of its cycles, PMC) and with one 1024-thread workgroup per CU there is nobody else to run.  Here rows beyond
@@ -279,8 +67,8 @@ __global__ __launch_bounds__(THREADS) void k_rp_scatter_carry(const KT * __restr
 // before the first global store.  Output rows are 32-bit (the callers bound a call below 2^32 rows).
 // dynamic LDS: stage_word u64[TILE] (HAS_WORD) | stage_key KT[TILE] | cursor u32[P] | delta u32[P + 1] | tile_cnt u32[P + 1] | tile_off u32[P + 1]
 // ---------------------------------------------------------------------------------------------
-template <u32 GBP_TILE, typename KT, bool HAS_WORD, typename PartFn, u32 THREADS = RP_THREADS>
-__global__ __launch_bounds__(THREADS) void k_rp_scatter(const KT * __restrict__ keys, const u64 * __restrict__ words, u64 n, u64 rows_per_wg, u32 P,
+template <u32 GBP_TILE, typename KT, bool HAS_WORD, typename PartFn>
+__global__ __launch_bounds__(RP_THREADS) void k_rp_scatter(const KT * __restrict__ keys, const u64 * __restrict__ words, u64 n, u64 rows_per_wg, u32 P,
                                                         const u64 * __restrict__ offsets, KT * __restrict__ out_keys, u64 * __restrict__ out_words, PartFn part_fn)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char gb_lds[];
@@ -290,9 +78,9 @@ __global__ __launch_bounds__(THREADS) void k_rp_scatter(const KT * __restrict__ 
     u32 * delta = cursor + P;
     u32 * tile_cnt = delta + (P + 1);
     u32 * tile_off = tile_cnt + (P + 1);
-    __shared__ u32 wave_tot[THREADS / 64];
+    __shared__ u32 wave_tot[RP_THREADS / 64];
 
-    for (u32 p = threadIdx.x; p <= P; p += THREADS)
+    for (u32 p = threadIdx.x; p <= P; p += RP_THREADS)
     {
         if (p < P)
             cursor[p] = (u32)offsets[(u64)p * gridDim.x + blockIdx.x];
@@ -301,13 +89,13 @@ __global__ __launch_bounds__(THREADS) void k_rp_scatter(const KT * __restrict__ 
     __syncthreads();
     const u64 r0 = (u64)blockIdx.x * rows_per_wg;
     const u64 r1 = r0 + rows_per_wg < n ? r0 + rows_per_wg : n;
-    constexpr u32 RPT = GBP_TILE / THREADS;
+    constexpr u32 RPT = GBP_TILE / RP_THREADS;
     static_assert(RPT % 2 == 0, "row pairs");
     KT key[RPT];
     u64 argw[HAS_WORD ? RPT : 1];
     typedef u64 v2q __attribute__((ext_vector_type(2)));
     typedef u32 v2d __attribute__((ext_vector_type(2)));
-    auto row_of = [&](u64 tb, u32 j) -> u64 { return tb + (u64)(j >> 1) * (2 * THREADS) + 2 * threadIdx.x + (j & 1); };
+    auto row_of = [&](u64 tb, u32 j) -> u64 { return tb + (u64)(j >> 1) * (2 * RP_THREADS) + 2 * threadIdx.x + (j & 1); };
     // The loads are unconditional and all vector loads: a pair that would start beyond the range re-reads the range's last whole pair
     // (its rows are invalid -- row_of() >= r1 -- and go to the dummy partition); the lone last row of an odd range is fetched as
     // the second element of the pair that ENDS with it (one row to the left: the hardware takes the misaligned address).  No
@@ -411,7 +199,7 @@ __global__ __launch_bounds__(THREADS) void k_rp_scatter(const KT * __restrict__ 
 #pragma unroll
     for (u32 j = 0; j < RPT; ++j)
     {
-        const u32 dst = (u32)n + j * THREADS + threadIdx.x;
+        const u32 dst = (u32)n + j * RP_THREADS + threadIdx.x;
         out_keys[dst] = 0;
         if constexpr (HAS_WORD)
             out_words[dst] = 0;
@@ -451,7 +239,7 @@ __global__ __launch_bounds__(THREADS) void k_rp_scatter(const KT * __restrict__ 
 #pragma unroll
             for (u32 j = 0; j < HALF; ++j)
             {
-                const u32 pos = (h * HALF + j) * THREADS + threadIdx.x;
+                const u32 pos = (h * HALF + j) * RP_THREADS + threadIdx.x;
                 k4[j] = stage_key[pos];
                 if constexpr (HAS_WORD)
                     w4[j] = stage_word[pos];
@@ -459,14 +247,14 @@ __global__ __launch_bounds__(THREADS) void k_rp_scatter(const KT * __restrict__ 
 #pragma unroll
             for (u32 j = 0; j < HALF; ++j)
             {
-                const u32 pos = (h * HALF + j) * THREADS + threadIdx.x;
+                const u32 pos = (h * HALF + j) * RP_THREADS + threadIdx.x;
                 const u32 p = pos < real_rows ? part_fn(k4[j]) : P;
                 d4[j] = delta[p];
             }
 #pragma unroll
             for (u32 j = 0; j < HALF; ++j)
             {
-                const u32 pos = (h * HALF + j) * THREADS + threadIdx.x;
+                const u32 pos = (h * HALF + j) * RP_THREADS + threadIdx.x;
                 const u32 dst = d4[j] + pos;
                 out_keys[dst] = k4[j];
                 if constexpr (HAS_WORD)
@@ -492,14 +280,15 @@ __global__ __launch_bounds__(THREADS) void k_rp_scatter(const KT * __restrict__ 
 // for 48-row runs) -- short runs are cheap to READ (no partial-line write-back, no merge window).  No histogram pass and no offset
 // scan precede it; part_total[p] += the rows of partition p (one atomic per partition and workgroup, for the consumer's work split).
 // rows_per_wg is a multiple of TILE; out arrays hold ceil(n / TILE) * TILE rows (rows past n sort behind the real rows of the last tile).
-// dynamic LDS: stage_word u64[TILE] | stage_key KT[TILE] | tile_cnt u32[P + 1] | tile_off u32[P + 1] | wg_total u32[P + 1]
+// dynamic LDS: {word, key} records [TILE] (stage_word = their first TILE * 8 bytes, stage_key = the rest) | tile_cnt u32[P + 1] |
+//              tile_off u32[P + 1] | wg_total u32[P + 1]
 // ---------------------------------------------------------------------------------------------
 // AT / EX: the argument column as stored -- u64 (EX 0), or a 4-byte type widened on the way into LDS: EX 0 zero-extended (UInt32),
 // 3 sign-extended (Int32), 4 Float32 -> Float64 bits; the sorted copy always holds 8-byte words.
-// AOS: the sorted copy is ONE array of {word, key} records -- 12 bytes for 4-byte keys, 16 for 8-byte keys (out_words = its base,
-// out_keys unused) -- instead of a key array and a word array: a partition's run is then one contiguous piece per tile, not two -- the consumer's gather touches
-// (576 + 124) / 128 = 5.5 lines per 48-row run instead of 2.5 + 3.9.
-template <u32 GBP_TILE, typename KT, typename PartFn, u32 THREADS = RP_THREADS, typename AT = u64, int EX = 0, bool AOS = false>
+// The sorted copy is ONE array of {word, key} records -- 12 bytes for 4-byte keys, 16 for 8-byte keys; out_words = its base, out_keys
+// is not written -- so a partition's run is one contiguous piece per tile, not two: the consumer's gather touches (576 + 124) / 128 =
+// 5.5 lines per 48-row run instead of 2.5 + 3.9 with a key array and a word array.
+template <u32 GBP_TILE, typename KT, typename PartFn, u32 THREADS = RP_THREADS, typename AT = u64, int EX = 0>
 __global__ __launch_bounds__(THREADS) void k_rp_tilesort(const KT * __restrict__ keys, const AT * __restrict__ words, u64 n, u64 rows_per_wg, u32 P,
                                                          KT * __restrict__ out_keys, u64 * __restrict__ out_words, unsigned short * __restrict__ tile_index,
                                                          unsigned long long * __restrict__ part_total, PartFn part_fn)
@@ -526,8 +315,7 @@ __global__ __launch_bounds__(THREADS) void k_rp_tilesort(const KT * __restrict__
     const u32 shift = r0 ? 2u : 0u;
     const char * kbase = (const char *)(keys + r0 - shift);
     const char * wbase = (const char *)(words + r0 - shift);
-    char * okbase = (char *)(out_keys + r0);
-    char * owbase = AOS ? (char *)out_words + r0 * (8 + sizeof(KT)) : (char *)(out_words + r0);
+    char * owbase = (char *)out_words + r0 * (8 + sizeof(KT));
     char * ixbase = (char *)(tile_index + (r0 / GBP_TILE) * (u64)(P + 1));
     constexpr u32 RPT = GBP_TILE / THREADS;
     static_assert(RPT % 4 == 0, "whole 16-byte pieces per thread");
@@ -625,7 +413,7 @@ __global__ __launch_bounds__(THREADS) void k_rp_tilesort(const KT * __restrict__
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (u32 q = 0; q < KPIECES; ++q)
-        __builtin_nontemporal_store(v4d{0, 0, 0, 0}, (v4d *)((AOS ? owbase + WPIECES * THREADS * 16u : okbase) + (q * THREADS + threadIdx.x) * 16u));
+        __builtin_nontemporal_store(v4d{0, 0, 0, 0}, (v4d *)((owbase + WPIECES * THREADS * 16u) + (q * THREADS + threadIdx.x) * 16u));
 #pragma unroll
     for (u32 q = 0; q < WPIECES; ++q)
         __builtin_nontemporal_store(v2q{0, 0}, (v2q *)(owbase + (q * THREADS + threadIdx.x) * 16u));
@@ -641,7 +429,7 @@ __global__ __launch_bounds__(THREADS) void k_rp_tilesort(const KT * __restrict__
         for (u32 j = 0; j < RPT; ++j)
         {
             const u32 pos = tile_off[part[j]] + rank[j];
-            if constexpr (AOS && sizeof(KT) == 4)
+            if constexpr (sizeof(KT) == 4)
             {
                 u32 * rec = (u32 *)gb_lds + 3 * pos;
                 const u64 w = word_at(trel, j);
@@ -649,23 +437,19 @@ __global__ __launch_bounds__(THREADS) void k_rp_tilesort(const KT * __restrict__
                 rec[1] = (u32)(w >> 32);
                 rec[2] = (u32)key_at(trel, j);
             }
-            else if constexpr (AOS)
+            else
             {
                 u64 * rec = (u64 *)gb_lds + 2 * pos; // 16-byte records {word, key}
                 rec[0] = word_at(trel, j);
                 rec[1] = (u64)key_at(trel, j);
-            }
-            else
-            {
-                stage_key[pos] = key_at(trel, j);
-                stage_word[pos] = word_at(trel, j);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
         load_tile(trel + GBP_TILE); // the next tile, unconditional (beyond the range it re-reads the last pair)
         __builtin_amdgcn_sched_barrier(0);
         __syncthreads();
-        // the sorted tile goes out in row order: 16-byte pieces, consecutive lanes -> consecutive pieces
+        // the sorted tile goes out in row order: 16-byte pieces, consecutive lanes -> consecutive pieces; the LDS image of the records
+        // goes out as it lies, to one base (stage_word's pieces first, then stage_key's)
         {
             v4d kq[KPIECES];
             v2q wq[WPIECES];
@@ -677,12 +461,11 @@ __global__ __launch_bounds__(THREADS) void k_rp_tilesort(const KT * __restrict__
                 wq[q] = *(const v2q *)((const char *)stage_word + (q * THREADS + threadIdx.x) * 16u);
             const u32 eo = tile_off[e_idx];
 #pragma unroll
-            // (AOS: the LDS image -- word region then key region -- is one record array and goes out as it lies, to one base)
             for (u32 q = 0; q < KPIECES; ++q)
-                __builtin_nontemporal_store(kq[q], (v4d *)((AOS ? owbase + trel * (8u + (u32)sizeof(KT)) + WPIECES * THREADS * 16u : okbase + trel * (u32)sizeof(KT)) + (q * THREADS + threadIdx.x) * 16u));
+                __builtin_nontemporal_store(kq[q], (v4d *)((owbase + trel * (8u + (u32)sizeof(KT)) + WPIECES * THREADS * 16u) + (q * THREADS + threadIdx.x) * 16u));
 #pragma unroll
             for (u32 q = 0; q < WPIECES; ++q)
-                __builtin_nontemporal_store(wq[q], (v2q *)(owbase + trel * (AOS ? 8u + (u32)sizeof(KT) : 8u) + (q * THREADS + threadIdx.x) * 16u));
+                __builtin_nontemporal_store(wq[q], (v2q *)(owbase + trel * (8u + (u32)sizeof(KT)) + (q * THREADS + threadIdx.x) * 16u));
             *(unsigned short *)(ixbase + (tile_no * (P + 1) + e_idx) * 2u) = (unsigned short)eo; // no branch around a store
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -871,9 +654,4 @@ static inline size_t rp_tilesort_lds_bytes(u32 tile, u32 P, size_t key_bytes)
 static inline size_t rp_scatter_lds_bytes(u32 tile, u32 P, size_t key_bytes, bool has_word)
 {
     return (size_t)tile * (key_bytes + (has_word ? 8 : 0)) + (size_t)P * 4 + (size_t)(P + 1) * 12 + 64;
-}
-
-static inline size_t rp_scatter_carry_lds_bytes(u32 tile, u32 P, u32 cg, size_t key_bytes, bool has_word)
-{
-    return (size_t)tile * (key_bytes + (has_word ? 8 : 0)) + (size_t)P * cg * (key_bytes + (has_word ? 8 : 0)) + (size_t)P * 28 + 64;
 }

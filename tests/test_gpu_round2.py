@@ -175,7 +175,7 @@ def test_pinned_async_upload_overlaps_and_orders(ch, ctx):
         K.check(K.lib().chgpu_host_free(host))
 
 
-# ---- GROUP BY partitioned path: carried-tail scatter, 32-bit partition hash, compile-time state updates -----------------------------
+# ---- GROUP BY partitioned path: branch-free scatter, 32-bit partition hash, compile-time state updates --------------------------------
 @pytest.mark.parametrize("key_dtype,pattern", [(np.uint32, "uniform"), (np.uint32, "stride"), (np.int32, "zipf"), (np.uint64, "uniform"), (np.uint16, "uniform")])
 @pytest.mark.parametrize("aggs_name", ["sum_count", "count_sum", "sum", "avg_f64", "sum_sum_count"])
 def test_groupby_partitioned_shapes_match_numpy(ch, ctx, key_dtype, pattern, aggs_name):
