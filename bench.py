@@ -10,6 +10,10 @@ device).  One "step" = one pass of the fused HIP filter+sum kernel over the whol
 Contract: `python bench.py --gpus N --steps K --warmup W`; N>1 is launched by torch.distributed.run (one rank per GPU).
 Rank 0 prints ONE JSON line.  `--dump-outputs DIR` also writes the result of the last timed step under DIR (inputs are seeded, so two
 builds can be compared output for output).
+
+A plain run does only what the headline needs: input, warm-up, timed steps, the line.  `--full` adds everything else the line has
+carried: the headline checked against a torch recomputation, the CPU baselines, and the other configs on the same clock (N=1: C3,
+C4, C5, Q11, C2 from host Blocks; N>1 or --force-dist: the sharded GROUP BY, join and SSB plan).
 """
 import argparse
 import json
@@ -31,16 +35,18 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rows", type=int, default=1_000_000_000, help="rows per GPU (default: the 1 B rows of configs[1])")
-    ap.add_argument("--cpu-sample-rows", type=int, default=1_000_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-configs", action="store_true", help="skip the C3 (GROUP BY) and C4 (hash join) sections of the line (N=1 only)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run its reference check, the CPU baselines and the other "
+                                                         "configs (the options below that say --full choose among these)")
+    ap.add_argument("--cpu-sample-rows", type=int, default=1_000_000_000, help="--full: rows of the headline's CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the configs sections of the line")
     ap.add_argument("--c3-rows", type=int, default=1_000_000_000)
     ap.add_argument("--c4-probe-rows", type=int, default=100_000_000)
     ap.add_argument("--c4-build-rows", type=int, default=10_000_000)
-    ap.add_argument("--no-c5", action="store_true", help="skip the SSB Q4.1-style section (configs[4], one GPU's share)")
+    ap.add_argument("--no-c5", action="store_true", help="--full: skip the SSB Q4.1-style section (configs[4], one GPU's share)")
     ap.add_argument("--c5-rows", type=int, default=750_000_000)
-    ap.add_argument("--only-c5", action="store_true", help="of the configs, run only C5 (the profile of the SSB plan on its own: profiles/collect.sh)")
-    ap.add_argument("--sharded-timeout", type=float, default=240.0, help="N>1: seconds the sharded GROUP BY / join section may take before the line is printed without it")
+    ap.add_argument("--only-c5", action="store_true", help="--full: of the configs, run only C5 (the profile of the SSB plan on its own: profiles/collect.sh)")
+    ap.add_argument("--sharded-timeout", type=float, default=240.0, help="--full, N>1: seconds the sharded GROUP BY / join section may take before the line is printed without it")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group even at world size 1 (exercises the RCCL code path on one GPU)")
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, the measured configuration) or gloo (rehearsal of the N>1 code path on one GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the {sum, count} state of the last timed step as DIR/<name>.npy (float64), "
@@ -48,6 +54,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.only_c5 and not args.full:
+        ap.error("--only-c5 chooses among the --full sections: give --full too")
 
     # the hosts of this pool only support dmabuf IPC: without it RCCL's peer buffers fail with hipIpcGetMemHandle: invalid argument.
     # Exported by the launch environment already; set before HIP starts in case a launcher drops it
@@ -154,10 +162,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)  # MAX over ranks
         elapsed, kern_avg_ms = float(t[0].item()), float(t[1].item())
 
-    # ---- sanity: every step produced the same, correct state (checked outside the timed region) ----
+    # ---- sanity: every step produced the same state, with --full also the correct one (checked outside the timed region) ----
     res = results.cpu().numpy()
     assert (res == res[W]).all(), "steps disagree"
-    if world == 1:
+    if args.full and world == 1:
         want_sum = int(a[a < THRESHOLD].sum().item())
         want_cnt = int((a < THRESHOLD).sum().item())
         assert (int(res[W][0]), int(res[W][1])) == (want_sum, want_cnt), (res[W], want_sum, want_cnt)
@@ -227,6 +235,12 @@ def main():
             print(json.dumps(line), flush=True)
             if dist is not None:
                 os.dup2(2, 1)  # anything RCCL says while shutting down goes to stderr again
+
+    if not args.full:
+        emit(out)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     if world == 1 and dist is None:
         if not args.no_cpu_baseline:
@@ -791,7 +805,7 @@ def config_c5(args, ctx, ch, torch, np, dev, stream, with_cpu):
         if ts.get("algorithmic_bytes") == algo:
             out["roofline"]["traffic"] = ts.get("C5_hbm_bytes_per_run")
             out["roofline"]["traffic_source"] = (f"profiles/{ts.get('tag', '')}_traffic_ssb.json (= profiles/traffic_ssb.json): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                                                 "passes of `bench.py --only-c5`, tools/gpu_pmc_c5.sh")
+                                                 "passes of `bench.py --full --only-c5`, tools/gpu_pmc_c5.sh")
     except Exception:
         pass
     if with_cpu:

@@ -97,7 +97,7 @@ if "C4_one_gpu" in cfg and cfg["C4_one_gpu"].get("probe_calls"):
     res["C4_hbm_bytes_per_call"] = per_call
     res["C4"] = {"build_calls": c4["build_calls"], "probe_calls": c4["probe_calls"], "algorithmic_bytes": c4["roofline"]["algorithmic_bytes"],
                  "kernels_total_over_all_calls": split}
-res["source"] = f"profiles/{tag}_traffic.json: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes (separate runs) of `python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline`, profiles/collect.sh {tag}"
+res["source"] = f"profiles/{tag}_traffic.json: rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes (separate runs) of `python3 bench.py --steps 20 --warmup 3 --full --no-cpu-baseline --no-c5`, profiles/collect.sh {tag}"
 with open(os.path.join(out, f"{tag}_traffic.json"), "w") as fo:
     json.dump(res, fo, indent=1)
 # the per-operator views on their own (same numbers)

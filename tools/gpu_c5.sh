@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/gpu_c5.sh <tag> -- on the MI355X box: chain + SSB parity tests, then the SSB plan (bench.py --only-c5) under rocprofv3 --kernel-trace --stats
+# tools/gpu_c5.sh <tag> -- on the MI355X box: chain + SSB parity tests, then the SSB plan (bench.py --full --only-c5) under rocprofv3 --kernel-trace --stats
 set -o pipefail
 TAG=${1:-c5}
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
@@ -12,7 +12,7 @@ tail -4 $OUT/tests.log
 [ $rc -ne 0 ] && exit $rc
 cd /tmp && export TMPDIR=/tmp
 rm -rf $OUT/prof
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o c5 -- python3 $ROOT/bench.py --only-c5 --no-cpu-baseline > $OUT/bench_c5.log 2>&1 || { tail -5 $OUT/bench_c5.log; exit 1; }
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o c5 -- python3 $ROOT/bench.py --full --only-c5 --no-cpu-baseline > $OUT/bench_c5.log 2>&1 || { tail -5 $OUT/bench_c5.log; exit 1; }
 grep -o '"C5_one_gpu_share".*' $OUT/bench_c5.log | cut -c1-400
 python3 - <<PY
 import csv

@@ -1,4 +1,4 @@
-# HBM traffic of the SSB plan (C5) on its own: FETCH_SIZE and WRITE_SIZE passes of `bench.py --only-c5` (separate runs, --kernel-trace only),
+# HBM traffic of the SSB plan (C5) on its own: FETCH_SIZE and WRITE_SIZE passes of `bench.py --full --only-c5` (separate runs, --kernel-trace only),
 # summed over the plan's kernels and divided by the number of plan runs.  Run on the GPU box:  gpurun -- 'bash tools/gpu_pmc_c5.sh r03'
 TAG=${1:-r03}
 ROOT=${GRAFT_REPO_ROOT:-$PWD}
@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/c5_fetch /tmp/c5_write
-ARGS="--steps 2 --warmup 1 --no-cpu-baseline --only-c5"
+ARGS="--steps 2 --warmup 1 --full --no-cpu-baseline --only-c5"
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/c5_fetch -- python3 $ROOT/bench.py $ARGS > $OUT/${TAG}_c5_pmc_bench.json 2> $OUT/${TAG}_c5_pmc.err || exit 1
 timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/c5_write -- python3 $ROOT/bench.py $ARGS > /dev/null 2>> $OUT/${TAG}_c5_pmc.err || exit 1
 python3 - $TAG <<'PY'
