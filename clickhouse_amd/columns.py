@@ -26,7 +26,7 @@ def sum_result_dtype(tag: int):
     return np.float64
 
 
-_OPTION_ENV_PREFIXES = ("CHGPU_TUNE_", "CHGPU_EXPERIMENT_", "CHGPU_TEST_", "CHGPU_AGG_NO_PARTITION", "CHGPU_DEBUG")
+_OPTION_ENV_PREFIXES = ("CHGPU_TUNE_", "CHGPU_TEST_", "CHGPU_AGG_NO_PARTITION", "CHGPU_DEBUG")
 
 
 def options_from_env(environ=None) -> dict:

@@ -1429,7 +1429,7 @@ __device__ __forceinline__ u32 tiles_load_block(const u32 * __restrict__ run_ind
 template <typename KT, u32 OPS, u32 TILE>
 __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, const KT * __restrict__ keys, const u64 * __restrict__ words0,
                                                         const u32 * __restrict__ run_index, u32 n_tiles, u32 P, u64 * __restrict__ pending, u32 S, u32 cnt32,
-                                                        const u64 * __restrict__ unit_list, const u32 * __restrict__ qstart, u32 * __restrict__ qctr, int experiment)
+                                                        const u64 * __restrict__ unit_list, const u32 * __restrict__ qstart, u32 * __restrict__ qctr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     typedef typename std::conditional<sizeof(KT) == 4, unsigned int, unsigned long long>::type CasT;
@@ -1617,16 +1617,6 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
         };
         auto process = [&](const u32 (&cs)[PR + 1], const u32 (&dl)[PR], const KT (&kv)[NS], const u64 (&av)[NS]) {
             const u32 total = cs[PR];
-            if (CHGPU_EXPERIMENT_VALUE(experiment) == 1) // timing experiment: the gather alone
-            {
-                u64 acc = 0;
-#pragma unroll
-                for (u32 m = 0; m < NS; ++m)
-                    acc += (u64)kv[m] ^ av[m];
-                if (acc == 0x123456789abcdefull)
-                    lzero = 1;
-                return;
-            }
 #pragma unroll
             for (u32 m = 0; m < NS; ++m)
             {
@@ -2607,7 +2597,6 @@ static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const c
         return CHGPU_OK; // the plan takes this shape (nothing was launched)
     const u32 G = (u32)ctx->num_cus;
     const u64 rows_per_wg = ((n + G - 1) / G + TILE - 1) / TILE * TILE;
-    const int tiles_experiment = CHGPU_EXPERIMENT(ctx, "experiment_tiles"); // timing experiments only (wrong results): -DCHGPU_EXPERIMENTS builds
     const bool debug = chgpu_opt(ctx, "debug", 0) != 0;
     if (debug)
         fprintf(stderr, "chgpu: tile-sorted GROUP BY n=%llu hint=%llu S=%u P=%u tile=%u ops=0x%x\n", (unsigned long long)n, (unsigned long long)a->size_hint, S, P, TILE, ops);
@@ -2651,7 +2640,7 @@ static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const c
         rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ag) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE; \
         if (rc == CHGPU_OK)                                                                                                                           \
             hipLaunchKernelGGL(kern, dim3(G), dim3(1024), lds_ag, ctx->stream, a->t, d, (const KT_ *)pkeys, (const u64 *)pwords, (const u32 *)run_index, n_tiles, P, \
-                               pending, S, cnt32, (const u64 *)unit_list, (const u32 *)unit_qstart, unit_ctr, tiles_experiment);                      \
+                               pending, S, cnt32, (const u64 *)unit_list, (const u32 *)unit_qstart, unit_ctr);                                        \
     } while (0)
 #define GB_TILES_OPS(KT_, TILE_)                        \
     switch (ops)                                        \

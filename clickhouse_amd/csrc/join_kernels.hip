@@ -734,26 +734,23 @@ __global__ __launch_bounds__(JT) void k_join_probe_filter(JoinTable t, int anti,
 // The same filter-only probe for DENSE 4-byte keys (dimension surrogate keys: the prefilter bitmap IS the key set) with the bitmap
 // staged in LDS.  From L2 the look-ups run at ~1.6e11/s chip-wide -- 64 lanes = 64 separate L2 requests -- i.e. 4.8 ms for the
 // 750 M lineorder rows of SSB against the 0.6 ms the keys and filter bytes take to stream; LDS serves the same random bit reads an
-// order of magnitude faster.  A slice of JPL_SLICE_BITS bits (150 KiB) fits; a larger key domain takes one pass per slice, pass d > 0
-// OR-ing into the filter bytes of the passes before it (the anti inversion and the count of kept rows belong to the last pass).
-// Four rows per lane and load: 16 bytes of keys, 4 null-map bytes, 4 filter bytes.
+// order of magnitude faster.  This kernel takes a key domain of one slice of JPL_SLICE_BITS bits (150 KiB); a larger one takes
+// k_join_probe_filter_lds_multi.  Four rows per lane and load: 16 bytes of keys, 4 null-map bytes, 4 filter bytes.
 static constexpr u32 JPL_SLICE_BITS = 150u * 1024u * 8u;
 template <bool HAS_NULL>
-__global__ __launch_bounds__(1024) void k_join_probe_filter_lds(const u32 * __restrict__ pf_words, u32 slice_lo, u32 slice_bits, int anti, int first_pass, int last_pass,
-                                                                int has_zero, const u32 * __restrict__ keys, const u8 * __restrict__ null_map, u64 n,
-                                                                u8 * __restrict__ filter, JoinCtrl * __restrict__ ctrl)
+__global__ __launch_bounds__(1024) void k_join_probe_filter_lds(const u32 * __restrict__ pf_words, u32 slice_bits, int anti, int has_zero, const u32 * __restrict__ keys,
+                                                                const u8 * __restrict__ null_map, u64 n, u8 * __restrict__ filter, JoinCtrl * __restrict__ ctrl)
 {
     extern __shared__ __attribute__((aligned(16))) u32 jpl_bits[];
     const u32 n_words = (slice_bits + 31) / 32;
     for (u32 w = threadIdx.x; w < n_words; w += 1024)
-        jpl_bits[w] = pf_words[slice_lo / 32 + w]; // slice_lo is a multiple of 32
+        jpl_bits[w] = pf_words[w];
     __syncthreads();
     auto found_in_slice = [&](u32 k) -> u32 {
-        const u32 rel = k - slice_lo;
-        const bool in = k != 0 && rel < slice_bits;
-        const u32 r = in ? rel : 0;
+        const bool in = k != 0 && k < slice_bits;
+        const u32 r = in ? k : 0;
         const u32 bit = (jpl_bits[r >> 5] >> (r & 31)) & 1u;
-        return (in ? bit : 0u) | ((first_pass && k == 0 && has_zero) ? 1u : 0u); // the zero key lives out of line (HashTable.h:874-898)
+        return (in ? bit : 0u) | ((k == 0 && has_zero) ? 1u : 0u); // the zero key lives out of line (HashTable.h:874-898)
     };
     typedef u32 v4u __attribute__((ext_vector_type(4)));
     const u64 nq = n / 4; // whole groups of four rows; the last n % 4 rows are done at the end
@@ -764,7 +761,7 @@ __global__ __launch_bounds__(1024) void k_join_probe_filter_lds(const u32 * __re
     for (u64 qb = q0 + threadIdx.x; qb < q1; qb += (u64)U * 1024)
     {
         v4u kk[U];
-        u32 nm[U], old[U];
+        u32 nm[U];
 #pragma unroll
         for (int u = 0; u < U; ++u)
         {
@@ -772,13 +769,12 @@ __global__ __launch_bounds__(1024) void k_join_probe_filter_lds(const u32 * __re
             const u64 qc = q < q1 ? q : q1 - 1;
             kk[u] = __builtin_nontemporal_load((const v4u *)keys + qc);
             nm[u] = HAS_NULL ? __builtin_nontemporal_load((const u32 *)null_map + qc) : 0u;
-            old[u] = first_pass ? 0u : ((const u32 *)filter)[qc];
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
         {
             const u64 q = qb + (u64)u * 1024;
-            u32 acc = old[u];
+            u32 acc = 0;
             const u32 k4[4] = {kk[u].x, kk[u].y, kk[u].z, kk[u].w};
 #pragma unroll
             for (int b = 0; b < 4; ++b)
@@ -786,54 +782,47 @@ __global__ __launch_bounds__(1024) void k_join_probe_filter_lds(const u32 * __re
                 const bool ok = !HAS_NULL || ((nm[u] >> (8 * b)) & 0xffu) == 0; // HashJoinMethodsImpl.h:451-452
                 acc |= (ok ? found_in_slice(k4[b]) : 0u) << (8 * b);
             }
-            if (last_pass)
-            {
-                acc = anti ? acc ^ 0x01010101u : acc; // :515-519, :535-536
-                kept += (u32)__popc(acc);
-            }
+            acc = anti ? acc ^ 0x01010101u : acc; // :515-519, :535-536
             if (q < q1)
+            {
+                kept += (u32)__popc(acc);
                 ((u32 *)filter)[q] = acc;
-            else if (last_pass)
-                kept -= (u32)__popc(acc); // (a clamped duplicate of the last group)
+            }
         }
     }
-    if (last_pass && blockIdx.x == 0 && threadIdx.x < (u32)(n & 3))
+    if (blockIdx.x == 0 && threadIdx.x < (u32)(n & 3))
     {
         // the last n % 4 rows, against the whole bitmap in global memory
         const u64 i = nq * 4 + threadIdx.x;
         const u32 k = keys[i];
         const bool ok = !(HAS_NULL && null_map[i]);
-        const bool found = ok && (k == 0 ? has_zero != 0 : (k < slice_lo + slice_bits && ((pf_words[k >> 5] >> (k & 31)) & 1u) != 0)); // (the last slice ends the bitmap)
+        const bool found = ok && (k == 0 ? has_zero != 0 : (k < slice_bits && ((pf_words[k >> 5] >> (k & 31)) & 1u) != 0));
         const u8 f = anti ? !found : found;
         filter[i] = f;
         kept += f;
     }
-    if (last_pass)
-    {
 #pragma unroll
-        for (int dlt = 32; dlt >= 1; dlt >>= 1)
-            kept += __shfl_xor(kept, dlt, 64);
-        if ((threadIdx.x & 63) == 0 && kept)
-            atomicAdd((unsigned long long *)&ctrl->n_out, (unsigned long long)kept);
-    }
+    for (int dlt = 32; dlt >= 1; dlt >>= 1)
+        kept += __shfl_xor(kept, dlt, 64);
+    if ((threadIdx.x & 63) == 0 && kept)
+        atomicAdd((unsigned long long *)&ctrl->n_out, (unsigned long long)kept);
 }
 
-// The same probe for a key set of SEVERAL slices in ONE sweep over the rows.  k_join_probe_filter_lds takes one pass over all rows per
-// slice (keys read again from HBM each time, the filter bytes of the passes before read back and rewritten); here a workgroup takes a PART
-// of 64 Ki rows through all slices before it moves on: the part's keys come from HBM once and from L2 / Infinity Cache for the other
-// slices, the hit bits of a thread's 64 rows wait in two registers between slices (a row's key lies in exactly one slice), and the filter
-// bytes are written once, after the last slice.  Between slices the workgroup reloads its 150 KiB of LDS from the bitmap (L2-resident);
-// consecutive parts walk the slices in opposite directions, so the slice a part ends with is the one the next part starts with.
-// JPM_QPT: quads (of four rows) per thread and part
-template <bool HAS_NULL, u32 JPM_QPT = 16>
+// The same probe for a key set of SEVERAL slices in ONE sweep over the rows.  One pass over all rows per slice would read the keys again
+// from HBM each time and read back and rewrite the filter bytes of the passes before; here a workgroup takes a PART of 64 Ki rows through
+// all slices before it moves on: the part's keys come from HBM once and from L2 / Infinity Cache for the other slices, the hit bits of a
+// thread's 64 rows wait in two registers between slices (a row's key lies in exactly one slice), and the filter bytes are written once,
+// after the last slice.  Between slices the workgroup reloads its 150 KiB of LDS from the bitmap (L2-resident); consecutive parts walk
+// the slices in opposite directions, so the slice a part ends with is the one the next part starts with.
+template <bool HAS_NULL>
 __global__ __launch_bounds__(1024) void k_join_probe_filter_lds_multi(const u32 * __restrict__ pf_words, u32 dense_bits, u32 n_slices, int anti, int has_zero,
                                                                       const u32 * __restrict__ keys, const u8 * __restrict__ null_map, u64 n,
                                                                       u8 * __restrict__ filter, JoinCtrl * __restrict__ ctrl)
 {
     extern __shared__ __attribute__((aligned(16))) u32 jpl_bits[];
     typedef u32 v4u __attribute__((ext_vector_type(4)));
+    constexpr u32 JPM_QPT = 16;                // quads (of four rows) per thread and part: a thread's hit bits fill one 64-bit register
     constexpr u32 JPM_PART_Q = 1024 * JPM_QPT; // quads per part
-    static_assert(JPM_QPT % 4 == 0 && JPM_QPT <= 16, "a thread's hit bits live in one 64-bit register");
     const u64 nq = n / 4; // whole groups of four rows; the last n % 4 rows are done at the end
     const u64 n_parts = (nq + JPM_PART_Q - 1) / JPM_PART_Q;
     u32 kept = 0;
@@ -1195,6 +1184,124 @@ extern "C" int chgpu_join_add_block(chgpu_join * j, const chgpu_col * key_col, c
 }
 
 // ---------------------------------------------------------------------------------------------
+// The join's two-level partition, shared by the slice build, the LDS-staged probe, both sides of the radix join and (first level only)
+// the region probe: k_rp_hist_wide + scan + k_rp_scatter into P contiguous first-level partitions, then k_rp_tilesort_keys of every
+// tile by its second-level bucket.  What is partitioned picks both tiles: a key that carries an 8-byte word (build rows: row id or
+// payload) stages 16 bytes per row in LDS, a key alone (probe keys) 8.
+// ---------------------------------------------------------------------------------------------
+static constexpr u32 jpart_scatter_tile(bool word) { return word ? 8192 : 12288; }
+static constexpr u32 jpart_sort_tile(bool word) { return word ? 8192 : 16384; }
+
+static u32 jceil_log2(u64 x)
+{
+    u32 lg = 0;
+    while ((1ull << lg) < x)
+        ++lg;
+    return lg;
+}
+
+// The partition functors of a table placed by intHash64: the first level is the top bits of the home slot, the second level the next
+// bits, counted from the first-level partition of the tile's first key
+struct JoinRegionFn
+{
+    u64 mask;
+    u32 shift;
+    __device__ __forceinline__ u32 operator()(u64 key) const { return (u32)((dev_intHash64(key) & mask) >> shift); }
+};
+struct JoinBucket2Fn
+{
+    u64 mask;
+    u32 shift2; // home slot -> second-level region (slice) number
+    u32 lg_p2;  // slices per first-level partition
+    __device__ __forceinline__ u32 operator()(u64 key, u64 first) const
+    {
+        const u32 r = (u32)((dev_intHash64(key) & mask) >> shift2), r0 = (u32)((dev_intHash64(first) & mask) >> shift2) >> lg_p2 << lg_p2;
+        return r - r0; // 0 .. 2 * P2 - 1 for the tile's own and the next first-level partition (keys sort by partition, so r >= r0)
+    }
+};
+
+// Carves 256-byte aligned pieces off one scratch allocation.  A caller runs its carve twice, over base 0 to size the allocation and
+// over the allocation itself, so the size cannot drift from the layout.
+struct JoinCarve
+{
+    uintptr_t at;
+    template <typename T> T * take(u64 count)
+    {
+        T * r = (T *)at;
+        at += (count * sizeof(T) + 255) / 256 * 256;
+        return r;
+    }
+};
+
+// The buffers of one partition (words1 / words2: nullptr without a word; keys2 / words2 / tidx: nullptr for the first level alone)
+struct JoinPart
+{
+    u32 * counts;          // [P * G] keys per (partition, workgroup)
+    u64 * offsets;         // [P * G] their exclusive scan: where each run starts
+    u64 * total;           // the scan's total
+    void * tmp;            // the scan's temporaries
+    u64 * keys1, * words1; // the first level
+    u64 * keys2, * words2; // the second level: every tile sorted by bucket
+    unsigned short * tidx; // [tiles][PB + 1] where each bucket's run starts inside its tile
+};
+// PB: second-level buckets per tile (0: the first level alone)
+static JoinPart join_part_carve(JoinCarve & c, u64 n, u32 G, u32 P, u32 PB, bool word)
+{
+    const u64 m = (u64)P * G, tile = jpart_sort_tile(word), tiles = (n + tile - 1) / tile;
+    JoinPart b{};
+    b.counts = c.take<u32>(m);
+    b.offsets = c.take<u64>(m + 1);
+    b.total = c.take<u64>(1);
+    b.tmp = c.take<char>(chgpu_scan_tmp_bytes(m));
+    b.keys1 = c.take<u64>(n + RP_SCATTER_SLACK);
+    if (word)
+        b.words1 = c.take<u64>(n + RP_SCATTER_SLACK);
+    if (PB)
+    {
+        b.keys2 = c.take<u64>(tiles * tile + 8); // (+ slack: an empty run at the very end of the last tile is addressed one row past it)
+        if (word)
+            b.words2 = c.take<u64>(tiles * tile + 8);
+        b.tidx = c.take<unsigned short>(tiles * (PB + 1) + 8);
+    }
+    return b;
+}
+
+// The first level: keys (and words) -> b.keys1 (b.words1) in P contiguous partitions; b.offsets[p * G + g] is where workgroup g's run
+// of partition p starts
+template <bool WORD, typename Fn1>
+static int join_partition(chgpu_ctx * ctx, const JoinPart & b, const u64 * keys, const u64 * words, u64 n, u32 P, Fn1 fn1)
+{
+    constexpr u32 TILE = jpart_scatter_tile(WORD);
+    const u32 G = (u32)ctx->num_cus;
+    const u64 m = (u64)P * G;
+    const u64 rows_per_wg = ((n + G - 1) / G + 63) / 64 * 64;
+    hipLaunchKernelGGL((k_rp_hist_wide<u64, Fn1>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, keys, n, rows_per_wg, P, b.counts, fn1);
+    CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, b.counts, b.offsets, m, b.total, b.tmp, chgpu_scan_tmp_bytes(m)));
+    const size_t lds = rp_scatter_lds_bytes(TILE, P, 8, WORD);
+    auto scat = k_rp_scatter<TILE, u64, WORD, Fn1>;
+    CHGPU_HIP(hipFuncSetAttribute((const void *)scat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(scat, dim3(G), dim3(RP_THREADS), lds, ctx->stream, keys, words, n, rows_per_wg, P, (const u64 *)b.offsets, b.keys1, b.words1, fn1);
+    return CHGPU_OK;
+}
+
+// Both levels: the first, then every tile of b.keys1 (b.words1) sorted into PB buckets -> b.keys2 (b.words2) and b.tidx.  A tile that
+// spans more than two first-level partitions raises *stray.
+template <bool WORD, typename Fn1, typename Fn2>
+static int join_partition2(chgpu_ctx * ctx, const JoinPart & b, const u64 * keys, const u64 * words, u64 n, u32 P, Fn1 fn1, u32 PB, Fn2 fn2, u32 * stray)
+{
+    CHGPU_TRY(join_partition<WORD>(ctx, b, keys, words, n, P, fn1));
+    constexpr u32 TILE = jpart_sort_tile(WORD);
+    const u32 G = (u32)ctx->num_cus;
+    const u64 rows_per_wg = ((n + G - 1) / G + TILE - 1) / TILE * TILE;
+    const size_t lds = (size_t)TILE * (WORD ? 16 : 8) + (size_t)(PB + 1) * 8 + 64;
+    auto sortk = k_rp_tilesort_keys<TILE, Fn2, RP_THREADS, WORD>;
+    CHGPU_HIP(hipFuncSetAttribute((const void *)sortk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(sortk, dim3(G), dim3(RP_THREADS), lds, ctx->stream, (const u64 *)b.keys1, n, rows_per_wg, PB, b.keys2, b.tidx, fn2, stray, (const u64 *)b.words1,
+                       b.words2);
+    return CHGPU_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Unique-key build at streaming speed (the primary-key build sides of star joins).  The generic build claims one cell per row with a
 // device-scope CAS -- ~2e10/s whatever the bandwidth: 0.66 ms for 1e7 rows.  Here the build rows are partitioned down to table slices
 // of 4096 cells with the same two passes as the LDS-staged probe (k_rp_hist_wide + k_rp_scatter into 64 partitions, k_rp_tilesort_keys
@@ -1202,23 +1309,15 @@ extern "C" int chgpu_join_add_block(chgpu_join * j, const chgpu_col * key_col, c
 // probing inside the slice) and written out as one contiguous 64 KiB piece.  A row whose chain runs past its slice's end goes to a
 // short overflow list that a last kernel inserts the generic way.  A duplicate key raises a flag and the generic build runs instead.
 // ---------------------------------------------------------------------------------------------
-struct JoinSliceFn1
+// The probe's functors under names of their own: the build's partition kernels then carry these names in their symbols, which is how
+// profiles/summarize_pmc.py tells them from the probe's.
+struct JoinSliceFn1 : JoinRegionFn
 {
-    u64 mask;
-    u32 shift;
-    __device__ __forceinline__ u32 operator()(u64 key) const { return (u32)((dev_intHash64(key) & mask) >> shift); }
 };
-struct JoinSliceFn2
+struct JoinSliceFn2 : JoinBucket2Fn
 {
-    u64 mask;
-    u32 shift2, lg_p2;
-    __device__ __forceinline__ u32 operator()(u64 key, u64 first) const
-    {
-        const u32 r = (u32)((dev_intHash64(key) & mask) >> shift2), r0 = (u32)((dev_intHash64(first) & mask) >> shift2) >> lg_p2 << lg_p2;
-        return r - r0;
-    }
 };
-static constexpr u32 JBS_LG_CELLS = 12, JBS_CELLS = 1u << JBS_LG_CELLS, JBS_TILE = 8192, JBS_LG_P1 = 6, JBS_THREADS = 512, JBS_MAX_OVERFLOW = 1u << 20;
+static constexpr u32 JBS_LG_CELLS = 12, JBS_CELLS = 1u << JBS_LG_CELLS, JBS_TILE = jpart_sort_tile(true), JBS_LG_P1 = 6, JBS_THREADS = 512, JBS_MAX_OVERFLOW = 1u << 20;
 
 __global__ __launch_bounds__(256) void k_join_iota(u64 * __restrict__ out, u64 n)
 {
@@ -1384,67 +1483,43 @@ static int join_build_slices(chgpu_join * j, JoinTable & t)
     chgpu_ctx * ctx = j->ctx;
     const bool off = chgpu_opt(ctx, "tune_join_no_slice_build", 0) != 0;
     const u64 n = j->total_rows, cap = t.capacity;
-    u32 lg_cap = 0;
-    while ((1ull << lg_cap) < cap)
-        ++lg_cap;
+    const u32 lg_cap = jceil_log2(cap);
     if (off || j->blocks.size() != 1 || j->blocks[0].valid || n < (1u << 20) || n + JBS_TILE + RP_SCATTER_SLACK >= (1ull << 32)
         || lg_cap < JBS_LG_CELLS + JBS_LG_P1 || lg_cap > JBS_LG_CELLS + JBS_LG_P1 + 7 || ((uintptr_t)j->blocks[0].keys % 16) != 0)
         return CHGPU_ERR_NOT_IMPLEMENTED;
     const u32 lg_p2 = lg_cap - JBS_LG_CELLS - JBS_LG_P1, P1 = 1u << JBS_LG_P1, PB = 2u << lg_p2;
-    const JoinSliceFn1 fn1{cap - 1, lg_cap - JBS_LG_P1};
-    const JoinSliceFn2 fn2{cap - 1, JBS_LG_CELLS, lg_p2};
+    const JoinSliceFn1 fn1{{cap - 1, lg_cap - JBS_LG_P1}};
+    const JoinSliceFn2 fn2{{cap - 1, JBS_LG_CELLS, lg_p2}};
     const u32 G = (u32)ctx->num_cus;
-    const u64 rows_per_wg = ((n + G - 1) / G + 63) / 64 * 64;
-    const u64 rows_per_wg2 = ((n + G - 1) / G + JBS_TILE - 1) / JBS_TILE * JBS_TILE;
-    const u64 n_tiles = (n + JBS_TILE - 1) / JBS_TILE, n_pad = n_tiles * JBS_TILE;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const u64 m = (u64)P1 * G;
-    const size_t cnt_b = al(m * 4), off_b = al(m * 8 + 8), tmp_b = chgpu_scan_tmp_bytes(m), a1_b = al((n + RP_SCATTER_SLACK) * 8), a2_b = al(n_pad * 8 + 64),
-                 ix_b = al(n_tiles * (PB + 1) * 2 + 16), ov_b = al((size_t)JBS_MAX_OVERFLOW * 8);
+    u64 * flags_dev, * rid0, * ovf_keys, * ovf_rids; // flags_dev: [2] unit counter | stray flag, [3..4] flags[0..3]
+    JoinPart part;
+    auto carve = [&](uintptr_t base) {
+        JoinCarve c{base};
+        flags_dev = c.take<u64>(8);
+        rid0 = c.take<u64>(n);
+        ovf_keys = c.take<u64>(JBS_MAX_OVERFLOW);
+        ovf_rids = c.take<u64>(JBS_MAX_OVERFLOW);
+        part = join_part_carve(c, n, G, P1, PB, true);
+        return c.at - base;
+    };
     void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, cnt_b + off_b + 256 + tmp_b + 3 * a1_b + 2 * a2_b + ix_b + 2 * ov_b + 256, &scratch));
-    char * p = (char *)scratch;
-    u32 * counts = (u32 *)p; p += cnt_b;
-    u64 * offsets = (u64 *)p; p += off_b;
-    u64 * total_dev = (u64 *)p; p += 256; // [0] scan total, [2] unit counter | stray flag, [3..4] flags[0..3]
-    void * tmp = p; p += tmp_b;
-    u64 * rid0 = (u64 *)p; p += a1_b;
-    u64 * keys1 = (u64 *)p; p += a1_b;
-    u64 * rid1 = (u64 *)p; p += a1_b;
-    u64 * keys2 = (u64 *)p; p += a2_b;
-    u64 * rid2 = (u64 *)p; p += a2_b;
-    unsigned short * tidx = (unsigned short *)p; p += ix_b;
-    u64 * ovf_keys = (u64 *)p; p += ov_b;
-    u64 * ovf_rids = (u64 *)p;
-    u32 * unit_ctr = (u32 *)(total_dev + 2), * stray = unit_ctr + 1, * flags = (u32 *)(total_dev + 3);
-    CHGPU_HIP(hipMemsetAsync(total_dev, 0, 64, ctx->stream));
-    const u64 * keys0 = j->blocks[0].keys;
+    CHGPU_TRY(chgpu_scratch(ctx, carve(0), &scratch));
+    carve((uintptr_t)scratch);
+    u32 * unit_ctr = (u32 *)(flags_dev + 2), * stray = unit_ctr + 1, * flags = (u32 *)(flags_dev + 3);
+    CHGPU_HIP(hipMemsetAsync(flags_dev, 0, 64, ctx->stream));
     hipLaunchKernelGGL(k_join_iota, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, rid0, n);
-    hipLaunchKernelGGL((k_rp_hist_wide<u64, JoinSliceFn1>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, keys0, n, rows_per_wg, P1, counts, fn1);
-    CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, counts, offsets, m, total_dev, tmp, tmp_b));
-    {
-        const size_t lds = rp_scatter_lds_bytes(8192, P1, 8, true);
-        auto scat = k_rp_scatter<8192, u64, true, JoinSliceFn1>;
-        CHGPU_HIP(hipFuncSetAttribute((const void *)scat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(scat, dim3(G), dim3(RP_THREADS), lds, ctx->stream, keys0, (const u64 *)rid0, n, rows_per_wg, P1, (const u64 *)offsets, keys1, rid1, fn1);
-    }
-    {
-        const size_t lds = (size_t)JBS_TILE * 16 + (size_t)(PB + 1) * 8 + 64;
-        auto sortk = k_rp_tilesort_keys<JBS_TILE, JoinSliceFn2, RP_THREADS, true>;
-        CHGPU_HIP(hipFuncSetAttribute((const void *)sortk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(sortk, dim3(G), dim3(RP_THREADS), lds, ctx->stream, (const u64 *)keys1, n, rows_per_wg2, PB, keys2, tidx, fn2, stray, (const u64 *)rid1, rid2);
-    }
+    CHGPU_TRY(join_partition2<true>(ctx, part, j->blocks[0].keys, rid0, n, P1, fn1, PB, fn2, stray));
     {
         const size_t lds = (size_t)JBS_CELLS * 16;
         CHGPU_HIP(hipFuncSetAttribute((const void *)k_join_build_slices, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_join_build_slices, dim3(2 * G), dim3(JBS_THREADS), lds, ctx->stream, t, (const u64 *)keys2, (const u64 *)rid2, n, (const u64 *)offsets, G, lg_p2,
-                           (const unsigned short *)tidx, unit_ctr, flags, ovf_keys, ovf_rids);
+        hipLaunchKernelGGL(k_join_build_slices, dim3(2 * G), dim3(JBS_THREADS), lds, ctx->stream, t, (const u64 *)part.keys2, (const u64 *)part.words2, n,
+                           (const u64 *)part.offsets, G, lg_p2, (const unsigned short *)part.tidx, unit_ctr, flags, ovf_keys, ovf_rids);
     }
     hipLaunchKernelGGL(k_join_insert_pairs, dim3(64), dim3(JT), 0, ctx->stream, t, (const u64 *)ovf_keys, (const u64 *)ovf_rids, (const u32 *)flags);
     ctx->counters[6] += 7;
     CHGPU_HIP(hipGetLastError());
     u64 back[3];
-    CHGPU_TRY(chgpu_read_back(ctx, total_dev + 2, back, 24));
+    CHGPU_TRY(chgpu_read_back(ctx, flags_dev + 2, back, 24));
     const u32 stray_v = (u32)(back[0] >> 32), dup_v = (u32)back[1], too_long = (u32)back[2];
     if (stray_v || dup_v || too_long)
         return CHGPU_ERR_NOT_IMPLEMENTED;
@@ -1750,6 +1825,68 @@ extern "C" int chgpu_join_total_rows(chgpu_join * j, uint64_t * rows, uint64_t *
     return CHGPU_OK;
 }
 
+// LEFT SEMI / LEFT ANTI without right columns: the filter bytes and the number of kept rows alone
+static int join_probe_filter_only(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * null_map, bool anti, chgpu_col ** filter_out, uint64_t * n_out,
+                                  uint64_t * n_left_consumed)
+{
+    chgpu_ctx * ctx = j->ctx;
+    const u64 n = key_col->rows;
+    chgpu_col * fcol = nullptr;
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, n, &fcol));
+    hipError_t e = hipMemsetAsync(&j->t.ctrl->n_out, 0, sizeof(u64), ctx->stream);
+    const u8 * nm = null_map ? (const u8 *)null_map->data : nullptr;
+    // dense 4-byte keys whose key set fits a few LDS slices: k_join_probe_filter_lds(_multi) (the tail of a bitmap beyond max_key is zero)
+    const bool no_lds_filter = chgpu_opt(ctx, "tune_join_no_lds_filter", 0) != 0;
+    const u64 dense_bits = (j->max_key + 32) / 32 * 32;
+    if (e == hipSuccess && !no_lds_filter && j->t.pf && j->max_key <= j->t.pf_mask && chgpu_type_size(j->key_type) == 4 && dense_bits <= 4ull * JPL_SLICE_BITS
+        && n >= (1u << 20) && (uintptr_t)key_col->data % 16 == 0 && (!null_map || (uintptr_t)null_map->data % 4 == 0))
+    {
+        const u32 slices = (u32)((dense_bits + JPL_SLICE_BITS - 1) / JPL_SLICE_BITS);
+        if (slices > 1)
+        {
+            // several slices: one sweep, every part of the rows through all slices
+            auto kern = null_map ? k_join_probe_filter_lds_multi<true> : k_join_probe_filter_lds_multi<false>;
+            e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(JPL_SLICE_BITS / 8));
+            if (e == hipSuccess)
+                hipLaunchKernelGGL(kern, dim3((u32)ctx->num_cus), dim3(1024), (size_t)(JPL_SLICE_BITS / 8), ctx->stream, (const u32 *)j->t.pf, (u32)dense_bits, slices,
+                                   anti ? 1 : 0, j->has_zero ? 1 : 0, (const u32 *)key_col->data, nm, n, (u8 *)fcol->data, j->t.ctrl);
+        }
+        else
+        {
+            auto kern = null_map ? k_join_probe_filter_lds<true> : k_join_probe_filter_lds<false>;
+            e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(JPL_SLICE_BITS / 8));
+            if (e == hipSuccess)
+                hipLaunchKernelGGL(kern, dim3((u32)ctx->num_cus), dim3(1024), (size_t)dense_bits / 8, ctx->stream, (const u32 *)j->t.pf, (u32)dense_bits, anti ? 1 : 0,
+                                   j->has_zero ? 1 : 0, (const u32 *)key_col->data, nm, n, (u8 *)fcol->data, j->t.ctrl);
+        }
+    }
+    else if (e == hipSuccess)
+    {
+        auto kern = j->t.pf ? k_join_probe_filter<true> : k_join_probe_filter<false>;
+        hipLaunchKernelGGL(kern, dim3(chgpu_grid_for(ctx, (n + JPF_R - 1) / JPF_R, JT, 8)), dim3(JT), 0, ctx->stream, j->t, anti ? 1 : 0, (const void *)key_col->data,
+                           j->key_type, nm, n, (u8 *)fcol->data, j->t.ctrl);
+    }
+    if (e == hipSuccess)
+    {
+        ctx->counters[6] += 1;
+        e = hipGetLastError();
+    }
+    JoinCtrl c;
+    int rc = e == hipSuccess ? chgpu_read_back(ctx, j->t.ctrl, &c, sizeof(c)) : chgpu_set_error(CHGPU_ERR_DEVICE, "join probe launch: %s", hipGetErrorString(e));
+    if (rc != CHGPU_OK)
+    {
+        chgpu_col_free(fcol);
+        return rc;
+    }
+    j->left_seq += n;
+    *filter_out = fcol;
+    *n_out = c.n_out;
+    *n_left_consumed = n;
+    ctx->counters[3] += n;
+    ctx->counters[4] += c.n_out;
+    return CHGPU_OK;
+}
+
 extern "C" int chgpu_join_probe(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * null_map, uint64_t max_joined_block_rows,
                                 chgpu_col ** filter_out, chgpu_col ** offsets_out, chgpu_col ** right_rowid_out, uint64_t * n_out,
                                 uint64_t * n_left_consumed)
@@ -1792,77 +1929,7 @@ extern "C" int chgpu_join_probe(chgpu_join * j, const chgpu_col * key_col, const
     }
 
     if (!right_rowid_out)
-    {
-        // filter-only probe (SEMI / ANTI without right columns)
-        chgpu_col * fcol = nullptr;
-        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, n, &fcol));
-        hipError_t e = hipMemsetAsync(&j->t.ctrl->n_out, 0, sizeof(u64), ctx->stream);
-        // dense 4-byte keys whose key set fits a few LDS slices: k_join_probe_filter_lds (the tail of a bitmap beyond max_key is zero)
-        const bool no_lds_filter = chgpu_opt(ctx, "tune_join_no_lds_filter", 0) != 0;
-        const u64 dense_bits = (j->max_key + 32) / 32 * 32;
-        if (e == hipSuccess && !no_lds_filter && j->t.pf && j->max_key <= j->t.pf_mask && chgpu_type_size(j->key_type) == 4 && dense_bits <= 4ull * JPL_SLICE_BITS
-            && n >= (1u << 20) && (uintptr_t)key_col->data % 16 == 0 && (!null_map || (uintptr_t)null_map->data % 4 == 0))
-        {
-            const u32 passes = (u32)((dense_bits + JPL_SLICE_BITS - 1) / JPL_SLICE_BITS);
-            const bool no_multi = chgpu_opt(ctx, "tune_join_no_lds_filter_multi", 0) != 0;
-            if (passes > 1 && !no_multi)
-            {
-                // several slices: one sweep, every part of the rows through all slices (k_join_probe_filter_lds_multi)
-                const u32 qpt = (u32)chgpu_opt(ctx, "tune_join_lds_filter_qpt", 16);
-                auto kern = qpt == 8 ? (null_map ? k_join_probe_filter_lds_multi<true, 8> : k_join_probe_filter_lds_multi<false, 8>)
-                          : qpt == 4 ? (null_map ? k_join_probe_filter_lds_multi<true, 4> : k_join_probe_filter_lds_multi<false, 4>)
-                                     : (null_map ? k_join_probe_filter_lds_multi<true, 16> : k_join_probe_filter_lds_multi<false, 16>);
-                e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(JPL_SLICE_BITS / 8));
-                if (e == hipSuccess)
-                {
-                    hipLaunchKernelGGL(kern, dim3((u32)ctx->num_cus), dim3(1024), (size_t)(JPL_SLICE_BITS / 8), ctx->stream, (const u32 *)j->t.pf, (u32)dense_bits, passes,
-                                       variant == PV_ANTI_LEFT ? 1 : 0, j->has_zero ? 1 : 0, (const u32 *)key_col->data, null_map ? (const u8 *)null_map->data : nullptr, n,
-                                       (u8 *)fcol->data, j->t.ctrl);
-                    ctx->counters[6] += 1;
-                    e = hipGetLastError();
-                }
-            }
-            else
-            for (u32 d = 0; d < passes && e == hipSuccess; ++d)
-            {
-                const u32 lo = d * JPL_SLICE_BITS;
-                const u32 bits = (u32)(dense_bits - lo < JPL_SLICE_BITS ? dense_bits - lo : JPL_SLICE_BITS);
-                const size_t lds_b = (size_t)(bits + 31) / 32 * 4;
-                auto kern = null_map ? k_join_probe_filter_lds<true> : k_join_probe_filter_lds<false>;
-                e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(JPL_SLICE_BITS / 8));
-                if (e == hipSuccess)
-                {
-                    hipLaunchKernelGGL(kern, dim3((u32)ctx->num_cus), dim3(1024), lds_b, ctx->stream, (const u32 *)j->t.pf, lo, bits, variant == PV_ANTI_LEFT ? 1 : 0, d == 0 ? 1 : 0,
-                                       d + 1 == passes ? 1 : 0, j->has_zero ? 1 : 0, (const u32 *)key_col->data, null_map ? (const u8 *)null_map->data : nullptr, n,
-                                       (u8 *)fcol->data, j->t.ctrl);
-                    ctx->counters[6] += 1;
-                    e = hipGetLastError();
-                }
-            }
-        }
-        else if (e == hipSuccess)
-        {
-            auto kern = j->t.pf ? k_join_probe_filter<true> : k_join_probe_filter<false>;
-            hipLaunchKernelGGL(kern, dim3(chgpu_grid_for(ctx, (n + JPF_R - 1) / JPF_R, JT, 8)), dim3(JT), 0, ctx->stream, j->t, variant == PV_ANTI_LEFT ? 1 : 0,
-                               (const void *)key_col->data, j->key_type, null_map ? (const u8 *)null_map->data : nullptr, n, (u8 *)fcol->data, j->t.ctrl);
-            ctx->counters[6] += 1;
-            e = hipGetLastError();
-        }
-        JoinCtrl c;
-        int rc = e == hipSuccess ? chgpu_read_back(ctx, j->t.ctrl, &c, sizeof(c)) : chgpu_set_error(CHGPU_ERR_DEVICE, "join probe launch: %s", hipGetErrorString(e));
-        if (rc != CHGPU_OK)
-        {
-            chgpu_col_free(fcol);
-            return rc;
-        }
-        j->left_seq += n;
-        *filter_out = fcol;
-        *n_out = c.n_out;
-        *n_left_consumed = n;
-        ctx->counters[3] += n;
-        ctx->counters[4] += c.n_out;
-        return CHGPU_OK;
-    }
+        return join_probe_filter_only(j, key_col, null_map, variant == PV_ANTI_LEFT, filter_out, n_out, n_left_consumed);
 
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t sl_b = al(n * 4), cnt_b = al(n * 4), val_b = al(n * 8), tmp_b = chgpu_scan_tmp_bytes(n);
@@ -2143,13 +2210,6 @@ __global__ __launch_bounds__(64) void k_join_probe_agg_finish(const u64 * __rest
 // whatever the bandwidth.  Workgroup -> XCD placement is read from HW_REG_XCC_ID and only steers which queue a workgroup drains
 // first; every workgroup ends up draining all eight queues, so the result never depends on it.
 // ---------------------------------------------------------------------------------------------
-struct JoinRegionFn
-{
-    u64 mask;
-    u32 shift;
-    __device__ __forceinline__ u32 operator()(u64 key) const { return (u32)((dev_intHash64(key) & mask) >> shift); }
-};
-
 static constexpr u32 JPR_CHUNK = 4096; // keys per work item
 static constexpr u32 JPR_XCDS = 8;
 static constexpr u32 JPR_MAX_REGIONS = 512;
@@ -2387,42 +2447,30 @@ static int join_probe_agg_regions(chgpu_join * j, const chgpu_col * key_col, con
     if (right_payload && chgpu_type_is_float(right_payload->type))
         return CHGPU_ERR_NOT_IMPLEMENTED; // a Float64 sum keeps the one-pass probe's fixed reduction order
     const u32 region_kib = (u32)chgpu_opt(ctx, "tune_join_region_kib", 1024);
-    u32 lg_cap = 0;
-    while ((1ull << lg_cap) < cap)
-        ++lg_cap;
     u32 R = 8;
     while (R < JPR_MAX_REGIONS && (cap * 16) / R > (u64)region_kib * 1024)
         R <<= 1;
-    u32 lg_r = 0;
-    while ((1u << lg_r) < R)
-        ++lg_r;
-    const JoinRegionFn fn{cap - 1, lg_cap - lg_r};
+    const JoinRegionFn fn{cap - 1, jceil_log2(cap) - jceil_log2(R)};
     const u32 G = (u32)ctx->num_cus;
-    u64 rows_per_wg = ((n + G - 1) / G + 63) / 64 * 64;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const u64 m = (u64)R * G;
-    const size_t cnt_b = al(m * 4), off_b = al(m * 8 + 8), tmp_b = chgpu_scan_tmp_bytes(m), q_b = al((size_t)JPR_XCDS * (R / JPR_XCDS + 1) * 4 + JPR_XCDS * 4 + 64);
+    u64 * total_dev; // [2..3] the result
+    u32 * qstart;
+    JoinPart part;
+    auto carve = [&](uintptr_t base) {
+        JoinCarve c{base};
+        total_dev = c.take<u64>(8);
+        qstart = c.take<u32>(JPR_XCDS * (R / JPR_XCDS + 1) + JPR_XCDS);
+        part = join_part_carve(c, n, G, R, 0, false);
+        return c.at - base;
+    };
     void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, cnt_b + off_b + 256 + tmp_b + q_b + al((n + RP_SCATTER_SLACK) * 8) + 256, &scratch));
-    u32 * counts = (u32 *)scratch;
-    u64 * offsets = (u64 *)((char *)scratch + cnt_b);
-    u64 * total_dev = (u64 *)((char *)scratch + cnt_b + off_b); // [0] scan total, [2..3] the result
-    void * tmp = (char *)scratch + cnt_b + off_b + 256;
-    u32 * qstart = (u32 *)((char *)tmp + tmp_b);
+    CHGPU_TRY(chgpu_scratch(ctx, carve(0), &scratch));
+    carve((uintptr_t)scratch);
     u32 * qctr = qstart + JPR_XCDS * (R / JPR_XCDS + 1);
-    u64 * pkeys = (u64 *)((char *)qstart + q_b);
+    const u64 * offsets = part.offsets, * pkeys = part.keys1;
     unsigned long long * result2 = (unsigned long long *)(total_dev + 2);
     CHGPU_HIP(hipMemsetAsync(total_dev, 0, 64, ctx->stream));
-    hipLaunchKernelGGL((k_rp_hist_wide<u64, JoinRegionFn>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, (const u64 *)key_col->data, n, rows_per_wg, R, counts, fn);
-    CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, counts, offsets, m, total_dev, tmp, tmp_b));
-    {
-        // keys only, plain runs (radix_partition.h k_rp_scatter; carried tails measured slower and wrote 1.26 GB for 0.8 GB of keys)
-        const size_t lds = rp_scatter_lds_bytes(12288, R, 8, false);
-        auto scat = k_rp_scatter<12288, u64, false, JoinRegionFn>;
-        CHGPU_HIP(hipFuncSetAttribute((const void *)scat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(scat, dim3(G), dim3(RP_THREADS), lds, ctx->stream, (const u64 *)key_col->data, (const u64 *)nullptr, n, rows_per_wg, R, (const u64 *)offsets, pkeys,
-                           (u64 *)nullptr, fn);
-    }
+    // keys only, plain runs (k_rp_scatter; carried tails measured slower and wrote 1.26 GB for 0.8 GB of keys)
+    CHGPU_TRY(join_partition<false>(ctx, part, (const u64 *)key_col->data, nullptr, n, R, fn));
     hipLaunchKernelGGL(k_jp_queues, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)offsets, G, R, n, qstart, qctr);
     const void * pp = right_payload ? right_payload->data : nullptr;
     const int pt = right_payload ? right_payload->type : CHGPU_U64;
@@ -2467,21 +2515,9 @@ static int join_probe_agg_regions(chgpu_join * j, const chgpu_col * key_col, con
 // (k_join_fuse_payload) is not needed.  A linear-probing chain that runs past the slice end finds the next slice's first JPL2_TAIL cells
 // in LDS too, and the global table behind them.
 // ---------------------------------------------------------------------------------------------
-static constexpr u32 JPL2_LG_CELLS = 12, JPL2_CELLS = 1u << JPL2_LG_CELLS, JPL2_TAIL = 256, JPL2_TILE = 16384, JPL2_LG_P1 = 6, JPL2_THREADS = 512;
+static constexpr u32 JPL2_LG_CELLS = 12, JPL2_CELLS = 1u << JPL2_LG_CELLS, JPL2_TAIL = 256, JPL2_TILE = jpart_sort_tile(false), JPL2_LG_P1 = 6, JPL2_THREADS = 512;
 // (4096-cell slices and 512-thread workgroups: two workgroups per CU, so one's staging round trips overlap the other's probing --
 //  8192 cells x 1024 threads, one per CU: 0.68 ms for C4's 1e8 keys)
-
-struct JoinBucket2Fn
-{
-    u64 mask;
-    u32 shift2; // home slot -> second-level region (slice) number
-    u32 lg_p2;  // slices per first-level partition
-    __device__ __forceinline__ u32 operator()(u64 key, u64 first) const
-    {
-        const u32 r = (u32)((dev_intHash64(key) & mask) >> shift2), r0 = (u32)((dev_intHash64(first) & mask) >> shift2) >> lg_p2 << lg_p2;
-        return r - r0; // 0 .. 2 * P2 - 1 for the tile's own and the next first-level partition (keys sort by partition, so r >= r0)
-    }
-};
 
 // The radix join has no table whose placement it must match, so it places keys by ONE 64-bit multiply (top lg_cap bits of key x odd
 // constant) instead of intHash64's two multiplies and three shift-xors: the hash is evaluated once per key in each of the four passes, and
@@ -2538,8 +2574,6 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
         ++lg_cap;
     auto slot_of = [&](u64 key) -> u64 { return FROM_ROWS ? join_radix_slot(key, lg_cap) : (dev_intHash64(key) & mask); };
     auto flat_of = [&](u64 rowid) -> u64 { return n_blocks == 1 ? (rowid & 0xFFFFFFFFull) : block_base[rowid >> 32] + (rowid & 0xFFFFFFFFull); };
-    const int experiment = CHGPU_EXPERIMENT_VALUE(variant >> 8); // timing experiments only, -DCHGPU_EXPERIMENTS builds (CHGPU_EXPERIMENT_JOIN_LDS: 1 = no slice build, 2 = no look-ups)
-    variant &= 0xff;
     const bool miss_counts = variant == PV_ALL_LEFT || variant == PV_ANY_LEFT || variant == PV_ANTI_LEFT;
     const bool anti = variant == PV_ANTI_LEFT;
     if constexpr (!FROM_ROWS)
@@ -2576,7 +2610,7 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
                 cells[c] = jv2{0, 0};
             __syncthreads();
             const u64 bb = s_boff[p1], be = s_boff[p1 + 1];
-            if (bb != be && experiment != 1)
+            if (bb != be)
             {
                 const u32 bt_lo = (u32)(bb / JBS_TILE), bt_hi = (u32)((be - 1) / JBS_TILE);
                 const u32 my_bt = bt_lo + wave <= bt_hi ? (bt_hi - bt_lo - wave) / NWB + 1 : 0;
@@ -2684,7 +2718,7 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
         // This wave's tiles: t_lo + wave, + NW, ...  Lane k fetches the run of tile k (one round trip for all of them instead of one
         // per tile); the keys of tile k + 1 are in flight while tile k is answered from LDS.
         constexpr u32 NW = JPL2_THREADS / 64;
-        const u32 my_tiles = (t_lo + wave <= t_hi && experiment != 2) ? (t_hi - t_lo - wave) / NW + 1 : 0;
+        const u32 my_tiles = t_lo + wave <= t_hi ? (t_hi - t_lo - wave) / NW + 1 : 0;
         // One look-up, straight-line for all but the longest chains: the home cell and its successor are read unconditionally and the
         // answer is selected; the zero key is the same look-up aimed at the extra cell (which holds {1, payload} when present); lanes
         // without a key carry valid = false.  (With a branch per case the loop spent ~100 scalar instructions per 64 look-ups on
@@ -2814,56 +2848,35 @@ static int join_probe_agg_lds(chgpu_join * j, const chgpu_col * key_col, const c
     const u64 n = key_col->rows, cap = j->t.capacity;
     const bool off = chgpu_opt(ctx, "tune_join_no_lds_probe", 0) != 0;
     const u64 min_rows = chgpu_opt(ctx, "tune_join_lds_min_rows", (8ull << 20));
-    u32 lg_cap = 0;
-    while ((1ull << lg_cap) < cap)
-        ++lg_cap;
+    const u32 lg_cap = jceil_log2(cap);
     if (off || !j->unique_keys || j->t.pf || !right_payload || chgpu_type_is_float(right_payload->type) || chgpu_type_size(right_payload->type) != 8
         || chgpu_type_size(j->key_type) != 8 || n < min_rows
         || n + JPL2_TILE + RP_SCATTER_SLACK >= (1ull << 32) || lg_cap < JPL2_LG_CELLS + JPL2_LG_P1 || lg_cap > JPL2_LG_CELLS + JPL2_LG_P1 + 7 || ((uintptr_t)key_col->data % 16) != 0)
         return CHGPU_ERR_NOT_IMPLEMENTED;
-    const u32 lg_r2 = lg_cap - JPL2_LG_CELLS, lg_p2 = lg_r2 - JPL2_LG_P1, P1 = 1u << JPL2_LG_P1, PB = 2u << lg_p2;
+    const u32 lg_p2 = lg_cap - JPL2_LG_CELLS - JPL2_LG_P1, P1 = 1u << JPL2_LG_P1, PB = 2u << lg_p2;
     const JoinRegionFn fn1{cap - 1, lg_cap - JPL2_LG_P1};
     const JoinBucket2Fn fn2{cap - 1, JPL2_LG_CELLS, lg_p2};
     const u32 G = (u32)ctx->num_cus;
-    const u64 rows_per_wg = ((n + G - 1) / G + 63) / 64 * 64;
-    const u64 rows_per_wg2 = ((n + G - 1) / G + JPL2_TILE - 1) / JPL2_TILE * JPL2_TILE;
-    const u64 n_tiles = (n + JPL2_TILE - 1) / JPL2_TILE, n_pad = n_tiles * JPL2_TILE;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const u64 m = (u64)P1 * G;
-    const size_t cnt_b = al(m * 4), off_b = al(m * 8 + 8), tmp_b = chgpu_scan_tmp_bytes(m), k1_b = al((n + RP_SCATTER_SLACK) * 8), k2_b = al(n_pad * 8 + 64), // (+ slack: an empty run at the very end of the last tile is addressed one row past it)
-                 ix_b = al(n_tiles * (PB + 1) * 2 + 16);
+    u64 * total_dev; // [2..3] the result, [4] unit counter + stray flag
+    JoinPart part;
+    auto carve = [&](uintptr_t base) {
+        JoinCarve c{base};
+        total_dev = c.take<u64>(8);
+        part = join_part_carve(c, n, G, P1, PB, false);
+        return c.at - base;
+    };
     void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, cnt_b + off_b + 256 + tmp_b + k1_b + k2_b + ix_b + 256, &scratch));
-    u32 * counts = (u32 *)scratch;
-    u64 * offsets = (u64 *)((char *)scratch + cnt_b);
-    u64 * total_dev = (u64 *)((char *)scratch + cnt_b + off_b); // [0] scan total, [2..3] the result, [4] unit counter + stray flag
-    void * tmp = (char *)scratch + cnt_b + off_b + 256;
-    u64 * keys1 = (u64 *)((char *)tmp + tmp_b);
-    u64 * keys2 = (u64 *)((char *)keys1 + k1_b);
-    unsigned short * tidx = (unsigned short *)((char *)keys2 + k2_b);
+    CHGPU_TRY(chgpu_scratch(ctx, carve(0), &scratch));
+    carve((uintptr_t)scratch);
     unsigned long long * result2 = (unsigned long long *)(total_dev + 2);
     u32 * unit_ctr = (u32 *)(total_dev + 4), * stray = unit_ctr + 1;
     CHGPU_HIP(hipMemsetAsync(total_dev, 0, 64, ctx->stream));
-    hipLaunchKernelGGL((k_rp_hist_wide<u64, JoinRegionFn>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, (const u64 *)key_col->data, n, rows_per_wg, P1, counts, fn1);
-    CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, counts, offsets, m, total_dev, tmp, tmp_b));
-    {
-        const size_t lds = rp_scatter_lds_bytes(12288, P1, 8, false);
-        auto scat = k_rp_scatter<12288, u64, false, JoinRegionFn>;
-        CHGPU_HIP(hipFuncSetAttribute((const void *)scat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(scat, dim3(G), dim3(RP_THREADS), lds, ctx->stream, (const u64 *)key_col->data, (const u64 *)nullptr, n, rows_per_wg, P1, (const u64 *)offsets, keys1,
-                           (u64 *)nullptr, fn1);
-    }
-    {
-        const size_t lds = (size_t)JPL2_TILE * 8 + (size_t)(PB + 1) * 8 + 64;
-        auto sortk = k_rp_tilesort_keys<JPL2_TILE, JoinBucket2Fn>;
-        CHGPU_HIP(hipFuncSetAttribute((const void *)sortk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(sortk, dim3(G), dim3(RP_THREADS), lds, ctx->stream, (const u64 *)keys1, n, rows_per_wg2, PB, keys2, tidx, fn2, stray, (const u64 *)nullptr, (u64 *)nullptr);
-    }
+    CHGPU_TRY(join_partition2<false>(ctx, part, (const u64 *)key_col->data, nullptr, n, P1, fn1, PB, fn2, stray));
     {
         const size_t lds = (size_t)(JPL2_CELLS + JPL2_TAIL + 2) * 16;
         CHGPU_HIP(hipFuncSetAttribute((const void *)k_join_probe_lds<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_join_probe_lds<false>, dim3(2 * G), dim3(JPL2_THREADS), lds, ctx->stream, j->t, variant, (const u64 *)keys2, n, (const u64 *)offsets, G, lg_p2,
-                           (const unsigned short *)tidx, (const u64 *)right_payload->data, (const u64 *)j->block_base_dev, (u64)j->blocks.size(), unit_ctr, stray, result2,
+        hipLaunchKernelGGL(k_join_probe_lds<false>, dim3(2 * G), dim3(JPL2_THREADS), lds, ctx->stream, j->t, variant, (const u64 *)part.keys2, n, (const u64 *)part.offsets, G,
+                           lg_p2, (const unsigned short *)part.tidx, (const u64 *)right_payload->data, (const u64 *)j->block_base_dev, (u64)j->blocks.size(), unit_ctr, stray, result2,
                            (const u64 *)nullptr, (const u64 *)nullptr, (const u64 *)nullptr, (const unsigned short *)nullptr, (u64)0, stray);
     }
     ctx->counters[6] += 5;
@@ -2896,9 +2909,7 @@ static int join_probe_agg_radix(chgpu_join * j, const chgpu_col * key_col, const
         || ((uintptr_t)j->blocks[0].keys % 16) != 0)
         return CHGPU_ERR_NOT_IMPLEMENTED;
     const u64 cap = join_capacity_for(j->ctx, nb);
-    u32 lg_cap = 0;
-    while ((1ull << lg_cap) < cap)
-        ++lg_cap;
+    const u32 lg_cap = jceil_log2(cap);
     if (lg_cap < JPL2_LG_CELLS + JPL2_LG_P1 || lg_cap > JPL2_LG_CELLS + JPL2_LG_P1 + 7)
         return CHGPU_ERR_NOT_IMPLEMENTED;
     static_assert(JPL2_LG_CELLS == JBS_LG_CELLS && JPL2_LG_P1 == JBS_LG_P1, "one slice geometry for both sides");
@@ -2906,71 +2917,32 @@ static int join_probe_agg_radix(chgpu_join * j, const chgpu_col * key_col, const
     const JoinRadixFn1 fn1{lg_cap, lg_cap - JPL2_LG_P1};
     const JoinRadixFn2 fn2{lg_cap, JPL2_LG_CELLS, lg_p2};
     const u32 G = (u32)ctx->num_cus;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const u64 m = (u64)P1 * G;
-    const u64 p_rpw = ((n + G - 1) / G + 63) / 64 * 64, p_rpw2 = ((n + G - 1) / G + JPL2_TILE - 1) / JPL2_TILE * JPL2_TILE;
-    const u64 b_rpw = ((nb + G - 1) / G + 63) / 64 * 64, b_rpw2 = ((nb + G - 1) / G + JBS_TILE - 1) / JBS_TILE * JBS_TILE;
-    const u64 p_tiles = (n + JPL2_TILE - 1) / JPL2_TILE, b_tiles = (nb + JBS_TILE - 1) / JBS_TILE;
-    const size_t cnt_b = al(m * 4), off_b = al(m * 8 + 8), tmp_b = chgpu_scan_tmp_bytes(m);
-    const size_t pk1_b = al((n + RP_SCATTER_SLACK) * 8), pk2_b = al(p_tiles * JPL2_TILE * 8 + 64), pix_b = al(p_tiles * (PB + 1) * 2 + 16);
-    const size_t bk1_b = al((nb + RP_SCATTER_SLACK) * 8), bk2_b = al(b_tiles * JBS_TILE * 8 + 64), bix_b = al(b_tiles * (PB + 1) * 2 + 16);
+    u64 * total_dev; // [2..3] the result, [4] unit counter | stray flag, [5] dup flag
+    JoinPart probe, build;
+    auto carve = [&](uintptr_t base) {
+        JoinCarve c{base};
+        total_dev = c.take<u64>(8);
+        probe = join_part_carve(c, n, G, P1, PB, false);
+        build = join_part_carve(c, nb, G, P1, PB, true);
+        return c.at - base;
+    };
     void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, 2 * (cnt_b + off_b) + 256 + tmp_b + pk1_b + pk2_b + pix_b + 2 * bk1_b + 2 * bk2_b + bix_b + 256, &scratch));
-    char * p = (char *)scratch;
-    u32 * p_counts = (u32 *)p; p += cnt_b;
-    u64 * p_offsets = (u64 *)p; p += off_b;
-    u32 * b_counts = (u32 *)p; p += cnt_b;
-    u64 * b_offsets = (u64 *)p; p += off_b;
-    u64 * total_dev = (u64 *)p; p += 256; // [0] scan total, [2..3] the result, [4] unit counter | stray flag, [5] dup flag
-    void * tmp = p; p += tmp_b;
-    u64 * pk1 = (u64 *)p; p += pk1_b;
-    u64 * pk2 = (u64 *)p; p += pk2_b;
-    unsigned short * pix = (unsigned short *)p; p += pix_b;
-    u64 * bk1 = (u64 *)p; p += bk1_b;
-    u64 * bw1 = (u64 *)p; p += bk1_b;
-    u64 * bk2 = (u64 *)p; p += bk2_b;
-    u64 * bw2 = (u64 *)p; p += bk2_b;
-    unsigned short * bix = (unsigned short *)p;
+    CHGPU_TRY(chgpu_scratch(ctx, carve(0), &scratch));
+    carve((uintptr_t)scratch);
     unsigned long long * result2 = (unsigned long long *)(total_dev + 2);
     u32 * unit_ctr = (u32 *)(total_dev + 4), * stray = unit_ctr + 1, * dupf = (u32 *)(total_dev + 5);
     CHGPU_HIP(hipMemsetAsync(total_dev, 0, 64, ctx->stream));
-    // the build side: rows {key, payload}
-    const u64 * bkeys0 = j->blocks[0].keys;
-    hipLaunchKernelGGL((k_rp_hist_wide<u64, JoinRadixFn1>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, bkeys0, nb, b_rpw, P1, b_counts, fn1);
-    CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, b_counts, b_offsets, m, total_dev, tmp, tmp_b));
-    {
-        const size_t lds = rp_scatter_lds_bytes(8192, P1, 8, true);
-        auto scat = k_rp_scatter<8192, u64, true, JoinRadixFn1>;
-        CHGPU_HIP(hipFuncSetAttribute((const void *)scat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(scat, dim3(G), dim3(RP_THREADS), lds, ctx->stream, bkeys0, (const u64 *)right_payload->data, nb, b_rpw, P1, (const u64 *)b_offsets, bk1, bw1, fn1);
-        const size_t lds2 = (size_t)JBS_TILE * 16 + (size_t)(PB + 1) * 8 + 64;
-        auto sortk = k_rp_tilesort_keys<JBS_TILE, JoinRadixFn2, RP_THREADS, true>;
-        CHGPU_HIP(hipFuncSetAttribute((const void *)sortk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        hipLaunchKernelGGL(sortk, dim3(G), dim3(RP_THREADS), lds2, ctx->stream, (const u64 *)bk1, nb, b_rpw2, PB, bk2, bix, fn2, stray, (const u64 *)bw1, bw2);
-    }
-    // the probe side: keys
-    hipLaunchKernelGGL((k_rp_hist_wide<u64, JoinRadixFn1>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, (const u64 *)key_col->data, n, p_rpw, P1, p_counts, fn1);
-    CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, p_counts, p_offsets, m, total_dev, tmp, tmp_b));
-    {
-        const size_t lds = rp_scatter_lds_bytes(12288, P1, 8, false);
-        auto scat = k_rp_scatter<12288, u64, false, JoinRadixFn1>;
-        CHGPU_HIP(hipFuncSetAttribute((const void *)scat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(scat, dim3(G), dim3(RP_THREADS), lds, ctx->stream, (const u64 *)key_col->data, (const u64 *)nullptr, n, p_rpw, P1, (const u64 *)p_offsets, pk1,
-                           (u64 *)nullptr, fn1);
-        const size_t lds2 = (size_t)JPL2_TILE * 8 + (size_t)(PB + 1) * 8 + 64;
-        auto sortk = k_rp_tilesort_keys<JPL2_TILE, JoinRadixFn2>;
-        CHGPU_HIP(hipFuncSetAttribute((const void *)sortk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-        hipLaunchKernelGGL(sortk, dim3(G), dim3(RP_THREADS), lds2, ctx->stream, (const u64 *)pk1, n, p_rpw2, PB, pk2, pix, fn2, stray, (const u64 *)nullptr, (u64 *)nullptr);
-    }
+    // the build side: rows {key, payload}; then the probe side: keys
+    CHGPU_TRY(join_partition2<true>(ctx, build, j->blocks[0].keys, (const u64 *)right_payload->data, nb, P1, fn1, PB, fn2, stray));
+    CHGPU_TRY(join_partition2<false>(ctx, probe, (const u64 *)key_col->data, nullptr, n, P1, fn1, PB, fn2, stray));
     {
         JoinTable vt{}; // only the capacity is read
         vt.capacity = cap;
         const size_t lds = (size_t)(JPL2_CELLS + JPL2_TAIL + 2) * 16;
         CHGPU_HIP(hipFuncSetAttribute((const void *)k_join_probe_lds<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        const int jexp = CHGPU_EXPERIMENT(ctx, "experiment_join_lds");
-        hipLaunchKernelGGL(k_join_probe_lds<true>, dim3(2 * G), dim3(JPL2_THREADS), lds, ctx->stream, vt, variant | (jexp << 8), (const u64 *)pk2, n, (const u64 *)p_offsets, G, lg_p2,
-                           (const unsigned short *)pix, (const u64 *)nullptr, (const u64 *)nullptr, (u64)1, unit_ctr, stray, result2, (const u64 *)bk2, (const u64 *)bw2,
-                           (const u64 *)b_offsets, (const unsigned short *)bix, nb, dupf);
+        hipLaunchKernelGGL(k_join_probe_lds<true>, dim3(2 * G), dim3(JPL2_THREADS), lds, ctx->stream, vt, variant, (const u64 *)probe.keys2, n, (const u64 *)probe.offsets, G,
+                           lg_p2, (const unsigned short *)probe.tidx, (const u64 *)nullptr, (const u64 *)nullptr, (u64)1, unit_ctr, stray, result2, (const u64 *)build.keys2,
+                           (const u64 *)build.words2, (const u64 *)build.offsets, (const unsigned short *)build.tidx, nb, dupf);
     }
     ctx->counters[6] += 9;
     CHGPU_HIP(hipGetLastError());
@@ -2981,6 +2953,30 @@ static int join_probe_agg_radix(chgpu_join * j, const chgpu_col * key_col, const
     res[0] = back[0];
     res[1] = back[1];
     return CHGPU_OK;
+}
+
+// The one-pass probe of the global table: every plan above can refuse a shape, this one takes them all
+static int join_probe_agg_one_pass(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * null_map, const chgpu_col * right_payload, int variant, u64 res[2])
+{
+    chgpu_ctx * ctx = j->ctx;
+    const u64 n = key_col->rows;
+    const bool is_float = right_payload && chgpu_type_is_float(right_payload->type);
+    const u32 grid = chgpu_grid_for(ctx, (n + 3) / 4, JT, 8);
+    void * scratch = nullptr;
+    CHGPU_TRY(chgpu_scratch(ctx, ((size_t)grid + 1) * 16, &scratch));
+    u64 * partials = (u64 *)scratch;
+    u64 * out2 = partials + 2 * (size_t)grid;
+    const void * pp = right_payload ? right_payload->data : nullptr;
+    const int pt = right_payload ? right_payload->type : CHGPU_U64;
+    const u8 * nm = null_map ? (const u8 *)null_map->data : nullptr;
+    auto kern = j->t.pf ? (is_float ? k_join_probe_agg<true, true> : k_join_probe_agg<true, false>) : (is_float ? k_join_probe_agg<false, true> : k_join_probe_agg<false, false>);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(JT), 0, ctx->stream, j->t, variant, (const void *)key_col->data, j->key_type, nm, n, pp, pt, (const u64 *)j->block_base_dev,
+                       (u64)j->blocks.size(), partials);
+    auto finish = is_float ? k_join_probe_agg_finish<true> : k_join_probe_agg_finish<false>;
+    hipLaunchKernelGGL(finish, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)partials, grid, out2);
+    ctx->counters[6] += 2;
+    CHGPU_HIP(hipGetLastError());
+    return chgpu_read_back(ctx, out2, res, 2 * sizeof(u64));
 }
 
 extern "C" int chgpu_join_probe_agg(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * null_map, const chgpu_col * right_payload,
@@ -3009,7 +3005,6 @@ extern "C" int chgpu_join_probe_agg(chgpu_join * j, const chgpu_col * key_col, c
     else if (j->strictness == CHGPU_STRICT_SEMI) variant = PV_SEMI_LEFT;
     else if (j->strictness == CHGPU_STRICT_ANTI) variant = PV_ANTI_LEFT;
     else variant = PV_ANY_LEFT;
-    const bool is_float = right_payload && chgpu_type_is_float(right_payload->type);
     u64 res[2] = {0, 0};
     int plan = CHGPU_ERR_NOT_IMPLEMENTED;
     j->build_closed = true; // (a probe ends the build phase, as a joinBlock does)
@@ -3030,35 +3025,7 @@ extern "C" int chgpu_join_probe_agg(chgpu_join * j, const chgpu_col * key_col, c
     if (plan != CHGPU_OK && plan != CHGPU_ERR_NOT_IMPLEMENTED)
         return plan;
     if (n && plan != CHGPU_OK)
-    {
-        const u32 grid = chgpu_grid_for(ctx, (n + 3) / 4, JT, 8);
-        void * scratch = nullptr;
-        CHGPU_TRY(chgpu_scratch(ctx, ((size_t)grid + 1) * 16, &scratch));
-        u64 * partials = (u64 *)scratch;
-        u64 * out2 = partials + 2 * (size_t)grid;
-        const void * pp = right_payload ? right_payload->data : nullptr;
-        const int pt = right_payload ? right_payload->type : CHGPU_U64;
-        const u8 * nm = null_map ? (const u8 *)null_map->data : nullptr;
-#define CHGPU_JPA(PFV, FL)                                                                                                                              \
-    hipLaunchKernelGGL((k_join_probe_agg<PFV, FL>), dim3(grid), dim3(JT), 0, ctx->stream, j->t, variant, (const void *)key_col->data, j->key_type, nm, n, pp, pt, \
-                       (const u64 *)j->block_base_dev, (u64)j->blocks.size(), partials)
-        if (j->t.pf)
-        {
-            if (is_float) CHGPU_JPA(true, true); else CHGPU_JPA(true, false);
-        }
-        else
-        {
-            if (is_float) CHGPU_JPA(false, true); else CHGPU_JPA(false, false);
-        }
-#undef CHGPU_JPA
-        if (is_float)
-            hipLaunchKernelGGL(k_join_probe_agg_finish<true>, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)partials, grid, out2);
-        else
-            hipLaunchKernelGGL(k_join_probe_agg_finish<false>, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)partials, grid, out2);
-        ctx->counters[6] += 2;
-        CHGPU_HIP(hipGetLastError());
-        CHGPU_TRY(chgpu_read_back(ctx, out2, res, sizeof(res)));
-    }
+        CHGPU_TRY(join_probe_agg_one_pass(j, key_col, null_map, right_payload, variant, res)); // the global table, one pass
     *count_out = res[0];
     if (sum_out)
         memcpy(sum_out, &res[1], 8);

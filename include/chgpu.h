@@ -99,8 +99,7 @@ int chgpu_ctx_synchronize(chgpu_ctx * ctx);
 int chgpu_ctx_trim(chgpu_ctx * ctx);
 /* Developer options: plan-level A/B switches and launch geometry (names: tools/README.md; e.g. "tune_join_no_radix", "tune_gb_tile").  No
    operator reads the environment: an option is set here, per context, or with ctx == NULL as the process-wide default.  Unknown names ->
-   CHGPU_ERR_BAD_ARGUMENTS.  Results never depend on an option (only the plan taken does); the timing experiments that skip work exist only in
-   builds made with -DCHGPU_EXPERIMENTS. */
+   CHGPU_ERR_BAD_ARGUMENTS.  Results never depend on an option (only the plan taken does). */
 int chgpu_ctx_set_option(chgpu_ctx * ctx, const char * name, int64_t value);
 /* ProfileEvents-style counters of this context (src/Common/ProfileEvents.cpp:1034-1035, 245-247):
    [0] FilterTransformPassedRows [1] FilterTransformPassedBytes [2] JoinBuildTableRowCount

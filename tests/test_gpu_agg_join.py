@@ -517,8 +517,8 @@ def test_join_filter_only_probe_matches_full_probe(ch, ctx, strict_name):
 @pytest.mark.parametrize("strict_name", ["SEMI", "ANTI"])
 @pytest.mark.parametrize("domain,with_nulls", [(50_000, True), (3_000_000, False), (3_000_000, True), (1_228_800, False)])
 def test_join_filter_only_probe_dense_keys_lds_slices(ch, ctx, strict_name, domain, with_nulls):
-    """dense UInt32 keys (dimension surrogate keys) and enough left rows: the key set is probed as an LDS-resident bitmap, one pass per
-    150 KiB slice of the key domain (1 and 3 slices here, and a domain that ends exactly at a slice boundary); left keys beyond the
+    """dense UInt32 keys (dimension surrogate keys) and enough left rows: the key set is probed as an LDS-resident bitmap in 150 KiB
+    slices of the key domain, in one sweep over the rows (1 and 3 slices here, and a domain that ends exactly at a slice boundary); left keys beyond the
     domain, the zero key, NULL keys and a row count that is not a multiple of four included"""
     strict = getattr(ch, "STRICT_" + strict_name)
     rng = np.random.Generator(np.random.PCG64(domain % 1000 + 3))

@@ -53,7 +53,7 @@ if what in ("c3", "both"):
 
     best, avg, A = timed(run)
     gk, (gs, gc) = A.convert_to_block()
-    assert os.environ.get('CHGPU_EXPERIMENT_TILES') or gk.shape[0] == len(A) and int(gc.sum()) == rows and int(gs.astype(np.uint64).sum(dtype=np.uint64)) == int(v.sum().item()) % 2**64
+    assert gk.shape[0] == len(A) and int(gc.sum()) == rows and int(gs.astype(np.uint64).sum(dtype=np.uint64)) == int(v.sum().item()) % 2**64
     out["C3"] = {"rows": rows, "groups": len(A), "best_ms": best, "avg_ms": avg, "frac": 12.0 * rows / (avg * 1e-3) / 8e12}
     del k, v, kc, vc, A
     ctx.trim()
@@ -81,7 +81,7 @@ if what in ("c4", "both"):
     sbk, order = torch.sort(bk)
     pos = torch.searchsorted(sbk, pk).clamp_(max=nb - 1)
     hit = sbk[pos] == pk
-    assert os.environ.get('CHGPU_EXPERIMENT_JOIN_LDS') or (cnt, sm % 2**64) == (int(hit.sum().item()), int(bv[order[pos[hit]]].sum().item()) % 2**64)
+    assert (cnt, sm % 2**64) == (int(hit.sum().item()), int(bv[order[pos[hit]]].sum().item()) % 2**64)
     out["C4"] = {"build_best_ms": bb, "build_avg_ms": ba, "probe_best_ms": pb, "probe_avg_ms": pa, "matches": cnt,
                  "frac": (8.0 * npb + 16.0 * nb + 8.0 * cnt) / ((ba + pa) * 1e-3) / 8e12}
 print(json.dumps(out))
