@@ -2360,6 +2360,14 @@ static u64 agg_estimate_groups(u64 d, u64 m)
     return (u64)hi;
 }
 
+// The `debug` option's line for the finish rounds: how many rounds re-ran rows left pending (0: the plan placed every row itself)
+static int agg_debug_rounds(const chgpu_ctx * ctx, int rounds)
+{
+    if (chgpu_opt(ctx, "debug", 0))
+        fprintf(stderr, "chgpu: GROUP BY finish rounds=%d\n", rounds);
+    return CHGPU_OK;
+}
+
 // The finish rounds of the tile-sorted plan over 12-byte records: the rows k_agg_tiles_lds left pending (LDS table full) go through the
 // HBM table; a row that meets the max-fill limit stays pending for the next round (after the table has grown).
 __global__ __launch_bounds__(AGG_THREADS) void k_agg_tiles_pending_aos(AggTable t, AggDesc d, const u32 * __restrict__ rec, int key64, u64 n, u64 * __restrict__ pending)
@@ -2400,10 +2408,10 @@ static int agg_finish_rounds_aos(chgpu_agg * a, const AggDesc & d, const u32 * r
         AggCtrl c;
         CHGPU_TRY(agg_read_ctrl(a, &c));
         if (!c.overflow && c.n_groups <= a->t.max_fill)
-            return CHGPU_OK;
+            return agg_debug_rounds(ctx, round);
         CHGPU_TRY(agg_grow(a, c.n_groups, c.has_zero != 0));
         if (!c.overflow)
-            return CHGPU_OK;
+            return agg_debug_rounds(ctx, round);
         const u32 grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
         hipLaunchKernelGGL(k_agg_tiles_pending_aos, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, rec, key64, n, pending);
         ctx->counters[6] += 1;
@@ -3206,6 +3214,9 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
     const u64 rows_per_chunk = ((n + chunks - 1) / chunks + 63) / 64 * 64;
     chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
     const u8 * cond_ptr = filter ? (const u8 *)filter->data + row_begin : nullptr;
+    if (chgpu_opt(ctx, "debug", 0))
+        fprintf(stderr, "chgpu: ranged GROUP BY n=%llu hint=%llu S=%u chunks=%llu passes=%u\n", (unsigned long long)n, (unsigned long long)a->size_hint, S,
+                (unsigned long long)chunks, n_passes);
     for (u32 p = 0; p < n_passes; ++p)
     {
         // this pass's descriptor: its argument functions, plus every count() in the first pass; state word indices are
@@ -3362,6 +3373,8 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
     if (a->has_extremum)
     {
         // min / max / any states: one emplace + one atomic per state word and row (the LDS-staged and partitioned plans carry additive words only)
+        if (chgpu_opt(ctx, "debug", 0))
+            fprintf(stderr, "chgpu: direct GROUP BY n=%llu hint=%llu kernel=rows_direct states=extremum\n", (unsigned long long)n, (unsigned long long)a->size_hint);
         CHGPU_TRY(agg_ensure_table(a));
         d.row_seq = a->any_seq - row_begin; // row i of the columns is the (any_seq + i - row_begin)-th row of the aggregation
         hipLaunchKernelGGL(k_agg_rows_direct<AGG_MODE_ALL>, dim3(chgpu_grid_for(ctx, n, AGG_THREADS, 8)), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type,
@@ -3468,6 +3481,8 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
     const bool ranged = use_lds && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0); // keys of 1, 2, 4 or 8 bytes: every key type
     if (ranged)
         return agg_add_block_ranged(a, key_col, arg_cols, row_begin, n, filter, d, pending, n_words64, lds_cells);
+    if (chgpu_opt(ctx, "debug", 0))
+        fprintf(stderr, "chgpu: direct GROUP BY n=%llu hint=%llu kernel=%s\n", (unsigned long long)n, (unsigned long long)a->size_hint, use_lds ? "rows_lds" : "rows_direct");
     if (use_lds)
     {
         // LDS cells per workgroup: the largest power of two with (1 + n_words) * 8 * (S+1) <= AGG_LDS_BYTES
@@ -3504,10 +3519,10 @@ static int agg_finish_rounds(chgpu_agg * a, const AggDesc & d, const void * keys
         AggCtrl c;
         CHGPU_TRY(agg_read_ctrl(a, &c));
         if (!c.overflow && c.n_groups <= a->t.max_fill)
-            return CHGPU_OK;
+            return agg_debug_rounds(ctx, round);
         CHGPU_TRY(agg_grow(a, c.n_groups, c.has_zero != 0));
         if (!c.overflow)
-            return CHGPU_OK;
+            return agg_debug_rounds(ctx, round);
         const u32 grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
         hipLaunchKernelGGL(k_agg_rows_direct<AGG_MODE_PENDING>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, keys, key_type, row_begin, n, pending);
         ctx->counters[6] += 1;

@@ -1476,9 +1476,25 @@ __global__ __launch_bounds__(JT) void k_join_insert_pairs(JoinTable t, const u64
         ((u32 *)flags)[0] = 1;
 }
 
+// Why a plan that ran declined its result (the `debug` option prints these): bit set of the flags its kernels raised
+enum : u32
+{
+    JOIN_DECLINED_STRAY = 1,         // a tile spanned three first-level partitions, or a chain ran past the staged window
+    JOIN_DECLINED_DUP = 2,           // a duplicate build key
+    JOIN_DECLINED_OVERFLOW_FULL = 4, // the slice build's overflow list was too short
+};
+static void join_debug_declined(const chgpu_ctx * ctx, const char * what, u32 declined)
+{
+    if (!chgpu_opt(ctx, "debug", 0))
+        return;
+    fprintf(stderr, "chgpu: %s declined:%s%s%s%s\n", what, declined ? "" : " shape", (declined & JOIN_DECLINED_STRAY) ? " stray" : "",
+            (declined & JOIN_DECLINED_DUP) ? " dup" : "", (declined & JOIN_DECLINED_OVERFLOW_FULL) ? " overflow_list_full" : "");
+}
+
 // -> CHGPU_OK: the table is built (unique keys); NOT_IMPLEMENTED: shape does not fit or a duplicate key exists (the caller runs the
-// generic build over a freshly zeroed table)
-static int join_build_slices(chgpu_join * j, JoinTable & t)
+// generic build over a freshly zeroed table).  *declined: the flags that made a run decline (0: it did not run); *overflow: the rows
+// that went through the overflow list.
+static int join_build_slices(chgpu_join * j, JoinTable & t, u32 * declined, u64 * overflow)
 {
     chgpu_ctx * ctx = j->ctx;
     const bool off = chgpu_opt(ctx, "tune_join_no_slice_build", 0) != 0;
@@ -1521,6 +1537,8 @@ static int join_build_slices(chgpu_join * j, JoinTable & t)
     u64 back[3];
     CHGPU_TRY(chgpu_read_back(ctx, flags_dev + 2, back, 24));
     const u32 stray_v = (u32)(back[0] >> 32), dup_v = (u32)back[1], too_long = (u32)back[2];
+    *declined = (stray_v ? JOIN_DECLINED_STRAY : 0) | (dup_v ? JOIN_DECLINED_DUP : 0) | (too_long ? JOIN_DECLINED_OVERFLOW_FULL : 0);
+    *overflow = back[1] >> 32;
     if (stray_v || dup_v || too_long)
         return CHGPU_ERR_NOT_IMPLEMENTED;
     return CHGPU_OK;
@@ -1615,10 +1633,19 @@ static int join_build_table(chgpu_join * j)
     // generic build over a zeroed table.
     CHGPU_HIP(hipMemsetAsync(m, 0, off_keys, ctx->stream));
     CHGPU_HIP(hipMemsetAsync(t.kv + 2 * cap, 0, 16, ctx->stream));
-    const int fast = join_build_slices(j, t);
+    u32 slices_declined = 0;
+    u64 slices_overflow = 0;
+    const int fast = join_build_slices(j, t, &slices_declined, &slices_overflow);
     if (fast != CHGPU_OK && fast != CHGPU_ERR_NOT_IMPLEMENTED)
         return fast;
     const bool sliced = fast == CHGPU_OK;
+    if (chgpu_opt(ctx, "debug", 0))
+    {
+        if (!sliced && slices_declined)
+            join_debug_declined(ctx, "join build slices", slices_declined);
+        fprintf(stderr, "chgpu: join build plan=%s rows=%llu cap=%llu overflow=%llu\n", sliced ? "slices" : "generic", (unsigned long long)j->total_rows,
+                (unsigned long long)cap, (unsigned long long)slices_overflow);
+    }
     if (!sliced)
         CHGPU_HIP(hipMemsetAsync(m, 0, off_first, ctx->stream)); // ctrl + {key, value} cells
     const bool take_last = !maps_all && j->any_take_last_row;
@@ -2435,7 +2462,7 @@ __global__ __launch_bounds__(JT) void k_join_probe_agg_regions(JoinTable t, int 
 }
 
 // -> CHGPU_OK with res[] filled, or CHGPU_ERR_NOT_IMPLEMENTED when this plan does not apply (the caller then runs the one-pass probe)
-static int join_probe_agg_regions(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * right_payload, int variant, u64 res[2])
+static int join_probe_agg_regions(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * right_payload, int variant, u64 res[2], u32 * regions)
 {
     chgpu_ctx * ctx = j->ctx;
     const u64 n = key_col->rows, cap = j->t.capacity;
@@ -2450,6 +2477,7 @@ static int join_probe_agg_regions(chgpu_join * j, const chgpu_col * key_col, con
     u32 R = 8;
     while (R < JPR_MAX_REGIONS && (cap * 16) / R > (u64)region_kib * 1024)
         R <<= 1;
+    *regions = R;
     const JoinRegionFn fn{cap - 1, jceil_log2(cap) - jceil_log2(R)};
     const u32 G = (u32)ctx->num_cus;
     u64 * total_dev; // [2..3] the result
@@ -2842,7 +2870,7 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
 }
 
 // -> CHGPU_OK with res[] filled, or NOT_IMPLEMENTED (shape does not fit / a tile straddled three partitions): the caller goes on with the region probe
-static int join_probe_agg_lds(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * right_payload, int variant, u64 res[2])
+static int join_probe_agg_lds(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * right_payload, int variant, u64 res[2], u32 * declined)
 {
     chgpu_ctx * ctx = j->ctx;
     const u64 n = key_col->rows, cap = j->t.capacity;
@@ -2883,7 +2911,9 @@ static int join_probe_agg_lds(chgpu_join * j, const chgpu_col * key_col, const c
     CHGPU_HIP(hipGetLastError());
     u64 back[3];
     CHGPU_TRY(chgpu_read_back(ctx, result2, back, 24));
-    if ((back[2] >> 32) != 0) // the stray flag: some tile spanned three first-level partitions (tiny partitions): not this plan
+    const u32 stray_v = (u32)(back[2] >> 32);
+    *declined = stray_v ? JOIN_DECLINED_STRAY : 0;
+    if (stray_v) // the stray flag: some tile spanned three first-level partitions (tiny partitions) or a chain left the window: not this plan
         return CHGPU_ERR_NOT_IMPLEMENTED;
     res[0] = back[0];
     res[1] = back[1];
@@ -2897,7 +2927,7 @@ static int join_probe_agg_lds(chgpu_join * j, const chgpu_col * key_col, const c
 // rows and answers its probe keys.  Neither the global table (0.62 ms to build) nor the per-probe payload gathers exist.  Duplicate
 // build keys, an overflowing window or tiny partitions raise a flag: NOT_IMPLEMENTED, and the caller builds the table after all.
 // ---------------------------------------------------------------------------------------------
-static int join_probe_agg_radix(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * right_payload, int variant, u64 res[2])
+static int join_probe_agg_radix(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * right_payload, int variant, u64 res[2], u32 * declined)
 {
     chgpu_ctx * ctx = j->ctx;
     const bool off = chgpu_opt(ctx, "tune_join_no_radix", 0) != 0;
@@ -2948,7 +2978,9 @@ static int join_probe_agg_radix(chgpu_join * j, const chgpu_col * key_col, const
     CHGPU_HIP(hipGetLastError());
     u64 back[4];
     CHGPU_TRY(chgpu_read_back(ctx, result2, back, 32));
-    if ((back[2] >> 32) != 0 || (u32)back[3] != 0) // stray rows / a duplicate build key: not this plan
+    const u32 stray_v = (u32)(back[2] >> 32), dup_v = (u32)back[3];
+    *declined = (stray_v ? JOIN_DECLINED_STRAY : 0) | (dup_v ? JOIN_DECLINED_DUP : 0);
+    if (stray_v || dup_v) // stray rows / a duplicate build key: not this plan
         return CHGPU_ERR_NOT_IMPLEMENTED;
     res[0] = back[0];
     res[1] = back[1];
@@ -3007,25 +3039,45 @@ extern "C" int chgpu_join_probe_agg(chgpu_join * j, const chgpu_col * key_col, c
     else variant = PV_ANY_LEFT;
     u64 res[2] = {0, 0};
     int plan = CHGPU_ERR_NOT_IMPLEMENTED;
+    const char * answered = "one_pass";
+    u32 declined = 0, regions = 0;
+    const bool debug = chgpu_opt(ctx, "debug", 0) != 0;
     j->build_closed = true; // (a probe ends the build phase, as a joinBlock does)
     if (n && !null_map && !j->finished)
     {
-        plan = join_probe_agg_radix(j, key_col, right_payload, variant, res); // no table at all: both sides partitioned, slices built and probed in LDS
+        plan = join_probe_agg_radix(j, key_col, right_payload, variant, res, &declined); // no table at all: both sides partitioned, slices built and probed in LDS
         if (plan != CHGPU_OK && plan != CHGPU_ERR_NOT_IMPLEMENTED)
             return plan;
+        if (plan == CHGPU_OK)
+            answered = "radix";
+        else
+            join_debug_declined(ctx, "join probe radix", declined);
     }
     if (plan != CHGPU_OK && !j->finished)
         CHGPU_TRY(join_build_table(j));
     if (plan != CHGPU_OK && n && !null_map)
     {
-        plan = join_probe_agg_lds(j, key_col, right_payload, variant, res); // table slices staged in LDS (unique keys, integer payload)
+        declined = 0;
+        plan = join_probe_agg_lds(j, key_col, right_payload, variant, res, &declined); // table slices staged in LDS (unique keys, integer payload)
+        if (plan == CHGPU_OK)
+            answered = "lds";
         if (plan == CHGPU_ERR_NOT_IMPLEMENTED)
-            plan = join_probe_agg_regions(j, key_col, right_payload, variant, res); // table regions resident in L2
+        {
+            join_debug_declined(ctx, "join probe lds", declined);
+            plan = join_probe_agg_regions(j, key_col, right_payload, variant, res, &regions); // table regions resident in L2
+            if (plan == CHGPU_OK)
+                answered = "regions";
+            else if (plan == CHGPU_ERR_NOT_IMPLEMENTED)
+                join_debug_declined(ctx, "join probe regions", 0);
+        }
     }
     if (plan != CHGPU_OK && plan != CHGPU_ERR_NOT_IMPLEMENTED)
         return plan;
     if (n && plan != CHGPU_OK)
         CHGPU_TRY(join_probe_agg_one_pass(j, key_col, null_map, right_payload, variant, res)); // the global table, one pass
+    if (debug && n)
+        fprintf(stderr, "chgpu: join probe plan=%s rows=%llu build_rows=%llu cap=%llu regions=%u\n", answered, (unsigned long long)n, (unsigned long long)j->total_rows,
+                (unsigned long long)join_capacity_for(ctx, j->total_rows), regions);
     *count_out = res[0];
     if (sum_out)
         memcpy(sum_out, &res[1], 8);
