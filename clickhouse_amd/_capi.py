@@ -15,6 +15,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "chgpu.h")
 # enums of include/chgpu.h
 OK = 0
 ERR_SIZES_MISMATCH, ERR_NOT_IMPLEMENTED, ERR_OOM, ERR_LOGICAL, ERR_BAD_ARGUMENTS, ERR_DEVICE, ERR_TOO_MANY_ROWS = -1, -2, -3, -4, -5, -6, -7
+OVERFLOW_THROW, OVERFLOW_BREAK, OVERFLOW_ANY = 0, 1, 2   # group_by_overflow_mode (OverflowMode, src/QueryPipeline/SizeLimits.h)
 I64, U32, U64, F64, U8, I32, U16, I16, I8, F32 = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 EQ, NE, LT, GT, LE, GE = 0, 1, 2, 3, 4, 5
 AGG_COUNT, AGG_SUM, AGG_AVG, AGG_MIN, AGG_MAX, AGG_ANY = 0, 1, 2, 3, 4, 5
@@ -100,6 +101,11 @@ SIGNATURES = {
     "chgpu_agg_export_states": (_i, [_vp, _pp, _pp, _pu64]),
     "chgpu_agg_export_states_two_level": (_i, [_vp, _pp, _pp, _pu64, _pu64]),
     "chgpu_agg_free": (_i, [_vp]),
+    "chgpu_agg_set_limits": (_i, [_vp, _u64, _i, _i]),
+    "chgpu_agg_execute_on_block": (_i, [_vp, _vp, _pp, _u64, _u64, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "chgpu_agg_merge_limited": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "chgpu_agg_merge_states_limited": (_i, [_vp, _vp, _pp, _u64, _i, C.POINTER(_i), C.POINTER(_i)]),
+    "chgpu_agg_overflow_row": (_i, [_vp, _i, _pp, C.POINTER(_i)]),
     "chgpu_join_create": (_i, [_vp, _i, _i, _i, _i, _u64, _pp]),
     "chgpu_join_add_block": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_u32)]),
     "chgpu_join_finish_build": (_i, [_vp]),

@@ -11,10 +11,18 @@ from . import _capi as K
 from .columns import NP_OF, TAG_OF, Column, Context, sum_result_dtype
 
 
+_OVERFLOW_MODES = {"throw": K.OVERFLOW_THROW, "break": K.OVERFLOW_BREAK, "any": K.OVERFLOW_ANY}
+
+
 class Aggregator:
-    def __init__(self, key_dtype, aggs, two_level_threshold: int = 100000, size_hint: int = 0, ctx: Context | None = None):
+    def __init__(self, key_dtype, aggs, two_level_threshold: int = 100000, size_hint: int = 0, ctx: Context | None = None,
+                 max_rows_to_group_by: int = 0, group_by_overflow_mode: str = "throw", overflow_row: bool = False):
         """aggs: list of (kind, arg_dtype or None).  key_dtype None = without_key.  two_level_threshold is accepted for
-        interface parity (Aggregator::Params) — the device table is single-level."""
+        interface parity (Aggregator::Params) — the device table is single-level.  max_rows_to_group_by (0 = no limit),
+        group_by_overflow_mode ("throw" / "break" / "any") and overflow_row are the settings of the same names."""
+        mode = _OVERFLOW_MODES.get(group_by_overflow_mode)
+        if mode is None:
+            raise ValueError(f"group_by_overflow_mode must be one of {sorted(_OVERFLOW_MODES)}, not {group_by_overflow_mode!r}")
         self.ctx = ctx if ctx is not None else Context(0)
         self.key_tag = -1 if key_dtype is None else TAG_OF[np.dtype(key_dtype)]
         self.aggs = [(k, (TAG_OF[np.dtype(d)] if d is not None else K.U64)) for k, d in aggs]
@@ -23,6 +31,10 @@ class Aggregator:
         h = C.c_void_p()
         K.check(K.lib().chgpu_agg_create(self.ctx._h, self.key_tag, len(self.aggs), kinds, types, size_hint, C.byref(h)))
         self._h = h
+        self.limited = bool(max_rows_to_group_by) or bool(overflow_row)
+        self.no_more_keys = False   # AggregatingTransform's, one per stream: this instance is one stream's variants
+        if self.limited:
+            K.check(K.lib().chgpu_agg_set_limits(self._h, int(max_rows_to_group_by), mode, int(bool(overflow_row))))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -44,17 +56,68 @@ class Aggregator:
         n = kcol.size() if kcol is not None else (fcol.size() if fcol is not None else next(a.size() for a in acols if a is not None))
         row_end = n if row_end is None else row_end
         ptrs = (C.c_void_p * max(1, len(acols)))(*[(a._h if a is not None else None) for a in acols])
+        if self.limited:
+            # -> False on group_by_overflow_mode BREAK ("stop reading"); ANY sets self.no_more_keys; THROW raises ERR_TOO_MANY_ROWS
+            nmk, keep = C.c_int(int(self.no_more_keys)), C.c_int(1)
+            K.check(K.lib().chgpu_agg_execute_on_block(self._h, kcol._h if kcol is not None else None, ptrs, row_begin, row_end,
+                                                       fcol._h if fcol is not None else None, C.byref(nmk), C.byref(keep)))
+            self.no_more_keys = bool(nmk.value)
+            return bool(keep.value)
         if fcol is None:
             K.check(K.lib().chgpu_agg_add_block(self._h, kcol._h if kcol is not None else None, ptrs, row_begin, row_end))
         else:
             K.check(K.lib().chgpu_agg_add_block_filtered(self._h, kcol._h if kcol is not None else None, ptrs, row_begin, row_end, fcol._h))
+        return True
 
-    def merge(self, other: "Aggregator"):
-        K.check(K.lib().chgpu_agg_merge(self._h, other._h))
+    def merge(self, other: "Aggregator", no_more_keys: bool = False) -> bool:
+        """mergeDataImpl; under limits one step of mergeSingleLevelDataImpl (merge_limited): False = BREAK, stop merging keyed data.
+        no_more_keys belongs to one sequence of merges (it is local to mergeSingleLevelDataImpl): pass False for its first step and,
+        for each next one, the self.merge_no_more_keys the previous step left."""
+        if not self.limited:
+            K.check(K.lib().chgpu_agg_merge(self._h, other._h))
+            return True
+        nmk, keep = C.c_int(int(bool(no_more_keys))), C.c_int(1)
+        K.check(K.lib().chgpu_agg_merge_limited(self._h, other._h, C.byref(nmk), C.byref(keep)))
+        self.merge_no_more_keys = bool(nmk.value)
+        return bool(keep.value)
 
-    def merge_states(self, keys: Column | None, state_cols, rows: int):
+    def merge_states(self, keys: Column | None, state_cols, rows: int, is_overflows: bool = False) -> bool:
+        """mergeOnBlock; is_overflows: the one-row block of an overflow row.  -> False on BREAK."""
         ptrs = (C.c_void_p * max(1, len(state_cols)))(*[c._h for c in state_cols])
-        K.check(K.lib().chgpu_agg_merge_states(self._h, keys._h if keys is not None else None, ptrs, rows))
+        if not self.limited and not is_overflows:
+            K.check(K.lib().chgpu_agg_merge_states(self._h, keys._h if keys is not None else None, ptrs, rows))
+            return True
+        nmk, keep = C.c_int(int(self.no_more_keys)), C.c_int(1)
+        K.check(K.lib().chgpu_agg_merge_states_limited(self._h, keys._h if keys is not None else None, ptrs, rows, int(bool(is_overflows)),
+                                                       C.byref(nmk), C.byref(keep)))
+        self.no_more_keys = bool(nmk.value)
+        return bool(keep.value)
+
+    def overflow_row(self, final: bool = True):
+        """the overflow row: [one-row result Columns] (final) or [state word Columns]; None when there is none"""
+        n = len(self.aggs) if final else self.n_words
+        res = (C.c_void_p * max(1, n))()
+        has = C.c_int(0)
+        K.check(K.lib().chgpu_agg_overflow_row(self._h, int(bool(final)), res, C.byref(has)))
+        if not has.value:
+            return None
+        return [Column(self.ctx, C.c_void_p(res[k])) for k in range(n)]
+
+    def convert_to_blocks(self, final: bool = True):
+        """Aggregator::convertToBlocks: [merging.AggregatedBlock], the overflow row first (is_overflows, default key) when there is one"""
+        from .merging import AggregatedBlock
+        out = []
+        ovf = self.overflow_row(final)
+        if ovf is not None:
+            kd = NP_OF[self.key_tag] if self.key_tag >= 0 else None
+            out.append(AggregatedBlock(-1, True, (np.zeros(1, dtype=kd) if kd is not None else None), Column.numpy_many(ovf), 1))
+        if final:
+            keys, res = self.convert_to_block()
+            out.append(AggregatedBlock(-1, False, keys, res, len(res[0]) if res else (len(keys) if keys is not None else 0)))
+        else:
+            kc, words, n = self.export_state_columns()
+            out.append(AggregatedBlock(-1, False, kc.numpy() if kc is not None else None, Column.numpy_many(words) if words else [], n))
+        return out
 
     def __len__(self):
         n = C.c_uint64(0)

@@ -90,6 +90,10 @@ struct AggTable
     u64 capacity;    // power of two
     u64 max_fill;    // capacity / 2
     AggCtrl * ctrl;
+    // find-only mode (no_more_keys): keys are looked up, never inserted; the state of a key the table lacks goes to the overflow row
+    // `ovf` ([n_words] words, the layout of one cell) or is dropped when ovf is NULL.  0 for ordinary blocks and for the rehash.
+    u32 find_only = 0;
+    u64 * ovf = nullptr;
 };
 
 struct chgpu_agg
@@ -126,6 +130,13 @@ struct chgpu_agg
     int fx_log_cap = 30;
     int fx_emin = 4096; // smallest (unbiased) exponent among the non-zero values added so far
     u64 host_words[AGG_MAX_WORDS]; // without_key states live on the host (8 B each)
+    // max_rows_to_group_by / group_by_overflow_mode / overflow_row (Aggregator::Params); set before the first block
+    u64 max_rows = 0;
+    int overflow_mode = CHGPU_OVERFLOW_THROW;
+    bool overflow_row = false;
+    bool started = false;          // some block or merge has reached the aggregation
+    void * ovf_mem = nullptr;      // the overflow row's state words on the device (AGG_MAX_WORDS x 8 B), from the first call with overflow_row on
+    size_t ovf_class = 0;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -418,6 +429,144 @@ __device__ __forceinline__ void add_vals_global(const AggTable & t, const AggDes
     }
 }
 
+// ---- find-only mode and the overflow row (Aggregator::executeImplBatch with no_more_keys, Aggregator.cpp:1181-1194) ----
+// In find-only mode only the step where a group's state leaves the workgroup changes -- the flush of an LDS cell, a row's global update:
+// it calls table_find instead of table_emplace, and a miss (AGG_SLOT_MISS) goes to the overflow row.  A workgroup combines its misses in
+// an LDS copy of the overflow row (ovf_*_lds: LDS atomics) and issues at most one global update per state word at its end (ovf_flush):
+// per-row atomics on one global address would serialise.
+static constexpr u64 AGG_SLOT_MISS = ~1ull;
+__device__ __forceinline__ u64 table_find(const AggTable & t, u64 key)
+{
+    if (key == 0)
+        return __hip_atomic_load(&t.ctrl->has_zero, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ? t.capacity : AGG_SLOT_MISS;
+    const u64 mask = t.capacity - 1;
+    u64 slot = dev_intHash64(key) & mask;
+    for (u64 step = 0; step < t.capacity; ++step)
+    {
+        const u64 k = t.keys[slot];
+        if (k == key)
+            return slot;
+        if (k == 0)
+            return AGG_SLOT_MISS;
+        slot = (slot + 1) & mask;
+    }
+    return AGG_SLOT_MISS;
+}
+// emplace, or find in find-only mode (t.find_only is uniform over the launch)
+__device__ __forceinline__ u64 table_place(const AggTable & t, u64 key, bool soft_limit)
+{
+    return t.find_only ? table_find(t, key) : table_emplace(t, key, soft_limit);
+}
+__device__ __forceinline__ void ovf_lds_init(u64 * s)
+{
+    if (threadIdx.x < AGG_MAX_WORDS)
+        s[threadIdx.x] = 0;
+}
+// op: 0 integer add, 1 Float64 add, 2 unsigned max (as global_add_word)
+__device__ __forceinline__ void ovf_lds_word(u64 * s, u64 bits, int op)
+{
+    if (op == 2)
+    {
+        if (bits)
+            atomicMax((unsigned long long *)s, (unsigned long long)bits);
+    }
+    else if (op == 1)
+        atomicAdd((double *)s, __longlong_as_double((long long)bits));
+    else if (bits)
+        atomicAdd((unsigned long long *)s, (unsigned long long)bits);
+}
+// row i's contribution to the overflow row (add_row_global with the LDS copy s[] indexed by table word)
+__device__ __forceinline__ void ovf_row_lds(u64 * s, const AggDesc & d, u64 i)
+{
+    for (u32 j = 0; j < d.n_aggs; ++j)
+    {
+        const AggArg & a = d.a[j];
+        u64 * w = s + d.word_map[a.word];
+        if (a.kind == CHGPU_AGG_COUNT)
+            ovf_lds_word(w, 1, 0);
+        else if (a.kind == CHGPU_AGG_MIN || a.kind == CHGPU_AGG_MAX)
+        {
+            const u64 k = agg_order_key(load_arg_bits(a.ptr, a.arg_type, i), a.arg_type);
+            ovf_lds_word(w, a.kind == CHGPU_AGG_MAX ? k : ~k, 2);
+        }
+        else if (a.kind == CHGPU_AGG_ANY)
+            ovf_lds_word(w, ~(d.row_seq + i), 2);
+        else
+        {
+            if ((d.word_fx >> a.word) & 1)
+                lds_add_fx(w, s + d.word_map[d.fx_hi[a.word]], fx_from_double(load_arg_bits(a.ptr, a.arg_type, i), d.fx_base));
+            else
+                ovf_lds_word(w, load_arg_bits(a.ptr, a.arg_type, i), a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
+            if (a.kind == CHGPU_AGG_AVG)
+                ovf_lds_word(w + 1, 1, 0);
+        }
+    }
+}
+// add_vals_global's update, to the overflow row
+__device__ __forceinline__ void ovf_vals_lds(u64 * s, const AggDesc & d, u64 bits0, u64 bits1, u64 cnt)
+{
+    for (u32 j = 0; j < d.n_aggs; ++j)
+    {
+        const AggArg & a = d.a[j];
+        u64 * w = s + d.word_map[a.word];
+        if (a.kind == CHGPU_AGG_COUNT)
+            ovf_lds_word(w, cnt, 0);
+        else
+        {
+            if ((d.word_fx >> a.word) & 1)
+                lds_add_fx(w, s + d.word_map[d.fx_hi[a.word]], fx_from_double(a.pre == 0 ? bits0 : bits1, d.fx_base));
+            else
+                ovf_lds_word(w, a.pre == 0 ? bits0 : bits1, a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
+            if (a.kind == CHGPU_AGG_AVG)
+                ovf_lds_word(w + 1, cnt, 0);
+        }
+    }
+}
+// local state word w of a flushed LDS cell (bits; hb = its fixed-point high half), to the overflow row
+__device__ __forceinline__ void ovf_cell_word_lds(u64 * s, const AggDesc & d, u32 w, u64 bits, u64 hb)
+{
+    if ((d.word_fx >> w) & 1)
+    {
+        if (bits | hb)
+            lds_add_fx(s + d.word_map[w], s + d.word_map[d.fx_hi[w]], Fx128{bits, hb});
+    }
+    else
+        ovf_lds_word(s + d.word_map[w], bits, (d.word_is_f64 >> w) & 1);
+}
+// The workgroup's combined misses to the overflow row: one global update per state word (call after a barrier, every thread).  Local
+// words 0 .. n_words-1 map to table words through `map`; masks as in AggDesc (word_is_f64: bit w Float64 add, bit 16 + w unsigned max).
+// any_merge: any() {claim, value} pairs that arrive together (merges: the first state that claims the overflow row keeps it,
+// changeFirstTime) -- a row's claim instead combines by max and its value is stored by the winning row later (k_agg_any_resolve).
+__device__ __forceinline__ void ovf_flush(const AggTable & t, const u64 * s, u32 n_words, u32 f64, u32 fx, u32 fx_hi_mask, const unsigned char * fx_hi,
+                                          const unsigned char * map, u32 any_merge)
+{
+    const u32 w = threadIdx.x;
+    if (!t.ovf || w >= n_words || ((fx_hi_mask >> w) & 1) || (w > 0 && ((any_merge >> (w - 1)) & 1)))
+        return;
+    const u32 gw = map ? map[w] : w; // (NULL: the identity)
+    const u64 bits = s[gw];
+    if ((any_merge >> w) & 1)
+    {
+        if (bits && atomicCAS((unsigned long long *)(t.ovf + gw), 0ull, (unsigned long long)bits) == 0ull)
+            __hip_atomic_store((unsigned long long *)(t.ovf + gw + 1), (unsigned long long)s[gw + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    if ((fx >> w) & 1)
+    {
+        const u32 gh = map ? map[fx_hi[w]] : fx_hi[w];
+        if (bits | s[gh])
+            global_add_fx(t.ovf + gw, t.ovf + gh, Fx128{bits, s[gh]});
+        return;
+    }
+    const int op = ((f64 >> (16 + w)) & 1) ? 2 : (int)((f64 >> w) & 1);
+    if (bits != 0)
+        global_add_word(t.ovf + gw, bits, op);
+}
+__device__ __forceinline__ void ovf_flush_desc(const AggTable & t, const u64 * s, const AggDesc & d)
+{
+    ovf_flush(t, s, d.n_words, d.word_is_f64, d.word_fx, d.word_fx_hi, d.fx_hi, d.word_map, 0);
+}
+
 enum { AGG_MODE_ALL = 0, AGG_MODE_PENDING = 1 };
 
 // DIRECT kernel: one global emplace + one atomic per state word per row.
@@ -425,6 +574,12 @@ template <int MODE>
 __global__ __launch_bounds__(AGG_THREADS) void k_agg_rows_direct(AggTable t, AggDesc d, const void * __restrict__ keys, int key_type,
                                                                  u64 row_begin, u64 n, u64 * __restrict__ pending)
 {
+    __shared__ u64 s_ovf[AGG_MAX_WORDS];
+    if (t.ovf)
+    {
+        ovf_lds_init(s_ovf);
+        __syncthreads();
+    }
     const u32 lane = threadIdx.x & 63;
     const u64 wave0 = ((u64)blockIdx.x * AGG_THREADS + threadIdx.x) >> 6;
     const u64 n_waves = ((u64)gridDim.x * AGG_THREADS) >> 6;
@@ -444,9 +599,14 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_rows_direct(AggTable t, Agg
         if (active)
         {
             const u64 i = row_begin + r;
-            const u64 slot = table_emplace(t, load_key_zext(keys, key_type, i), true);
+            const u64 slot = table_place(t, load_key_zext(keys, key_type, i), true);
             if (slot == ~0ull)
                 failed = true;
+            else if (slot == AGG_SLOT_MISS)
+            {
+                if (t.ovf)
+                    ovf_row_lds(s_ovf, d, i);
+            }
             else
                 add_row_global(t, d, slot, i);
         }
@@ -455,6 +615,11 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_rows_direct(AggTable t, Agg
             pending[g] = b;
         if (b != 0 && lane == 0)
             t.ctrl->overflow = 1; // benign race: every writer stores 1
+    }
+    if (t.ovf)
+    {
+        __syncthreads();
+        ovf_flush_desc(t, s_ovf, d);
     }
 }
 
@@ -466,11 +631,13 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
     u64 * lkeys = (u64 *)lds_raw;
     u64 * lwords = lkeys + (S + 1);
     __shared__ u32 lzero;
+    __shared__ u64 s_ovf[AGG_MAX_WORDS];
     const u32 lstride = S + 1;
     for (u32 s = threadIdx.x; s < (d.n_words + 1) * lstride; s += blockDim.x)
         lkeys[s] = 0;
     if (threadIdx.x == 0)
         lzero = 0;
+    ovf_lds_init(s_ovf);
     __syncthreads();
 
     const u32 lane = threadIdx.x & 63;
@@ -577,9 +744,14 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
                 }
                 else
                 {
-                    const u64 slot = table_emplace(t, key, true);
+                    const u64 slot = table_place(t, key, true);
                     if (slot == ~0ull)
                         failed = true;
+                    else if (slot == AGG_SLOT_MISS)
+                    {
+                        if (t.ovf)
+                            ovf_row_lds(s_ovf, d, i);
+                    }
                     else
                         add_row_global(t, d, slot, i);
                 }
@@ -601,10 +773,18 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
         const bool occupied = (s == S) ? (lzero != 0) : (key != 0);
         if (!occupied)
             continue;
-        const u64 slot = table_emplace(t, s == S ? 0 : key, false); // may use the slack above max fill
+        const u64 slot = table_place(t, s == S ? 0 : key, false); // may use the slack above max fill
         if (slot == ~0ull)
         {
             t.ctrl->fatal = 1;
+            continue;
+        }
+        if (slot == AGG_SLOT_MISS)
+        {
+            if (t.ovf)
+                for (u32 w = 0; w < d.n_words; ++w)
+                    if (!((d.word_fx_hi >> w) & 1))
+                        ovf_cell_word_lds(s_ovf, d, w, lwords[w * lstride + s], ((d.word_fx >> w) & 1) ? lwords[d.fx_hi[w] * lstride + s] : 0);
             continue;
         }
         for (u32 w = 0; w < d.n_words; ++w)
@@ -624,6 +804,11 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
             if (f ? (__longlong_as_double((long long)bits) != 0.0 || bits != 0) : (bits != 0))
                 global_add_word(t.words + (u64)d.word_map[w] * gstride + slot, bits, f);
         }
+    }
+    if (t.ovf)
+    {
+        __syncthreads();
+        ovf_flush_desc(t, s_ovf, d);
     }
 }
 
@@ -1030,6 +1215,8 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
     L.keys_bytes = ((u32)sizeof(KT) * L.S1 + 7) & ~7u;
     const u32 lds_bytes = L.keys_bytes + 8 * L.S1 * L.n8 + 4 * L.S1 * (u32)__popc(cnt32);
     __shared__ u32 lzero, sh_unit;
+    __shared__ u64 s_ovf[AGG_MAX_WORDS]; // find-only mode: the workgroup's share of the overflow row (made visible by the loop's first barrier)
+    ovf_lds_init(s_ovf);
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
     const u64 gstride = t.capacity + 1;
     // The aggregate descriptors are decoded ONCE into wave-uniform registers (all loops over them are fully unrolled, so the
@@ -1249,9 +1436,14 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
                     }
                     else
                     {
-                        const u64 slot = table_emplace(t, key, true);
+                        const u64 slot = table_place(t, key, true);
                         if (slot == ~0ull)
                             failed = true;
+                        else if (slot == AGG_SLOT_MISS)
+                        {
+                            if (t.ovf)
+                                ovf_vals_lds(s_ovf, d, b0, b1, 1);
+                        }
                         else
                             add_vals_global(t, d, slot, b0, b1, 1);
                     }
@@ -1287,10 +1479,23 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
             const bool occupied = (s == S) ? (lzero != 0) : (key != 0);
             if (!occupied)
                 continue;
-            const u64 slot = table_emplace(t, s == S ? 0 : key, false);
+            const u64 slot = table_place(t, s == S ? 0 : key, false);
             if (slot == ~0ull)
             {
                 t.ctrl->fatal = 1;
+                continue;
+            }
+            if (slot == AGG_SLOT_MISS)
+            {
+                if (t.ovf)
+                    for (u32 w = 0; w < d.n_words; ++w)
+                    {
+                        if ((d.word_fx_hi >> w) & 1)
+                            continue;
+                        const unsigned char * wp = lds_raw + L.off(w);
+                        const u64 bits = ((cnt32 >> w) & 1) ? (u64)((const u32 *)wp)[s] : ((const u64 *)wp)[s];
+                        ovf_cell_word_lds(s_ovf, d, w, bits, ((d.word_fx >> w) & 1) ? ((const u64 *)(lds_raw + L.off(d.fx_hi[w])))[s] : 0);
+                    }
                 continue;
             }
             for (u32 w = 0; w < d.n_words; ++w)
@@ -1313,6 +1518,8 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
         }
         __syncthreads();
     }
+    if (t.ovf) // (the loop ends on a barrier)
+        ovf_flush_desc(t, s_ovf, d);
 }
 
 // ---- the TILE-SORTED plan (radix_partition.h, k_rp_tilesort): units and the aggregate pass that gathers one run per tile ----
@@ -1441,6 +1648,8 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
     L.keys_bytes = ((u32)sizeof(KT) * L.S1 + 7) & ~7u;
     const u32 lds_bytes = L.keys_bytes + 8 * L.S1 * L.n8 + 4 * L.S1 * (u32)__popc(cnt32);
     __shared__ u32 lzero, sh_unit;
+    __shared__ u64 s_ovf[AGG_MAX_WORDS]; // find-only mode: the workgroup's share of the overflow row (made visible by the loop's first barrier)
+    ovf_lds_init(s_ovf);
     const u32 lane = threadIdx.x & 63;
     const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), n_waves = blockDim.x >> 6;
     const u64 gstride = t.capacity + 1;
@@ -1660,10 +1869,23 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
             const bool occupied = (s == S) ? (lzero != 0) : (key != 0);
             if (!occupied)
                 continue;
-            const u64 slot = table_emplace(t, s == S ? 0 : key, false);
+            const u64 slot = table_place(t, s == S ? 0 : key, false);
             if (slot == ~0ull)
             {
                 t.ctrl->fatal = 1;
+                continue;
+            }
+            if (slot == AGG_SLOT_MISS)
+            {
+                if (t.ovf)
+                    for (u32 w = 0; w < d.n_words; ++w)
+                    {
+                        if ((d.word_fx_hi >> w) & 1)
+                            continue;
+                        const unsigned char * wp = lds_raw + L.off(w);
+                        const u64 bits = ((cnt32 >> w) & 1) ? (u64)((const u32 *)wp)[s] : ((const u64 *)wp)[s];
+                        ovf_cell_word_lds(s_ovf, d, w, bits, ((d.word_fx >> w) & 1) ? ((const u64 *)(lds_raw + L.off(d.fx_hi[w])))[s] : 0);
+                    }
                 continue;
             }
             for (u32 w = 0; w < d.n_words; ++w)
@@ -1686,6 +1908,8 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
         }
         __syncthreads();
     }
+    if (t.ovf) // (the loop ends on a barrier)
+        ovf_flush_desc(t, s_ovf, d);
 }
 
 // Merge (key, state words) tuples into the table: mergeToViaEmplace, also the rehash of a grown table.
@@ -1706,6 +1930,12 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, u32 n_wo
     const u64 n_waves = ((u64)gridDim.x * AGG_THREADS) >> 6;
     const u64 n_groups64 = (n + 63) / 64;
     const u64 gstride = t.capacity + 1;
+    __shared__ u64 s_ovf[AGG_MAX_WORDS]; // find-only merges (never the rehash): the workgroup's share of the overflow row
+    if (t.ovf)
+    {
+        ovf_lds_init(s_ovf);
+        __syncthreads();
+    }
     u32 my_claims = 0; // without a soft limit nobody reads the counter mid-kernel: count in registers, add once per wave
     for (u64 g = wave0; g < n_groups64; g += n_waves)
     {
@@ -1727,14 +1957,44 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, u32 n_wo
                 key = 0;
             if (!(skip_zero_keys && key == 0 && !is_zero_cell))
             {
-                bool claimed;
-                const u64 slot = table_emplace_impl(t, key, soft_limit != 0, claimed);
-                if (soft_limit)
+                bool claimed = false;
+                const u64 slot = t.find_only ? table_find(t, key) : table_emplace_impl(t, key, soft_limit != 0, claimed);
+                if (t.find_only)
+                    ;
+                else if (soft_limit)
                     count_claim(t, claimed); // the only divergent caller: count_claim's ballot sees the lanes in this branch
                 else
                     my_claims += claimed;
                 if (slot == ~0ull)
                     failed = true;
+                else if (slot == AGG_SLOT_MISS)
+                {
+                    // mergeDataNoMoreKeysImpl: the source state of a key dst lacks goes to dst's overflow row (or is dropped:
+                    // mergeDataOnlyExistingKeysImpl)
+                    if (t.ovf)
+                        for (u32 w = 0; w < n_words; ++w)
+                        {
+                            if ((fx.word_fx_hi >> w) & 1)
+                                continue;
+                            const u64 v = src_words[(u64)w * src_stride + i];
+                            if ((fx.word_any >> w) & 1)
+                            {
+                                if (v && atomicCAS((unsigned long long *)&s_ovf[w], 0ull, (unsigned long long)v) == 0ull)
+                                    s_ovf[w + 1] = src_words[(u64)(w + 1) * src_stride + i];
+                                ++w;
+                                continue;
+                            }
+                            if ((fx.word_fx >> w) & 1)
+                            {
+                                const u32 wh = fx.fx_hi[w];
+                                const u64 hv = src_words[(u64)wh * src_stride + i];
+                                if (v | hv)
+                                    lds_add_fx(&s_ovf[w], &s_ovf[wh], Fx128{v, hv});
+                                continue;
+                            }
+                            ovf_lds_word(&s_ovf[w], v, ((word_is_f64 >> (16 + w)) & 1) ? 2 : (int)((word_is_f64 >> w) & 1));
+                        }
+                }
                 else
                     for (u32 w = 0; w < n_words; ++w)
                     {
@@ -1775,6 +2035,11 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, u32 n_wo
             tot += __shfl_xor(tot, dlt, WAVE);
         if (lane == 0 && tot)
             atomicAdd(&t.ctrl->stripe[agg_stripe()][0], (unsigned long long)tot);
+    }
+    if (t.ovf)
+    {
+        __syncthreads();
+        ovf_flush(t, s_ovf, n_words, word_is_f64, fx.word_fx, fx.word_fx_hi, fx.fx_hi, nullptr, fx.word_any);
     }
 }
 
@@ -1909,6 +2174,31 @@ static int agg_ensure_table(chgpu_agg * a, u64 min_cells = 0)
     return agg_alloc_table(a, cap, &a->t, &a->table_mem, &a->table_class);
 }
 
+// find-only mode leaves the table as it is, so nothing else resets the flag a pending row raised (a grown table starts with a clean header)
+static int agg_clear_overflow_flag(chgpu_agg * a)
+{
+    CHGPU_HIP(hipMemsetAsync(&a->t.ctrl->overflow, 0, sizeof(u32), a->ctx->stream));
+    return CHGPU_OK;
+}
+
+// The overflow row's words exist from the first call after overflow_row was turned on (zero states: an aggregation without key that saw
+// no row).  Kept out of the table: exports, finalize and chgpu_agg_size never see it; the rehash leaves it where it is.
+static int agg_ensure_overflow_row(chgpu_agg * a)
+{
+    if (!a->overflow_row || a->key_type < 0 || a->ovf_mem)
+        return CHGPU_OK;
+    CHGPU_TRY(chgpu_pool_alloc(a->ctx, AGG_MAX_WORDS * 8, &a->ovf_mem, &a->ovf_class));
+    CHGPU_HIP(hipMemsetAsync(a->ovf_mem, 0, AGG_MAX_WORDS * 8, a->ctx->stream));
+    return CHGPU_OK;
+}
+
+// Enters / leaves find-only mode for the launches of one call (executeOnBlock with no_more_keys, a find-only merge step)
+static void agg_set_find_only(chgpu_agg * a, bool on)
+{
+    a->t.find_only = on ? 1u : 0u;
+    a->t.ovf = on ? (u64 *)a->ovf_mem : nullptr;
+}
+
 extern "C" int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, const int * agg_kinds, const int * arg_types,
                                 uint64_t size_hint, chgpu_agg ** out)
 {
@@ -1991,6 +2281,8 @@ extern "C" int chgpu_agg_free(chgpu_agg * a)
         return CHGPU_OK;
     if (a->table_mem)
         chgpu_pool_free(a->ctx, a->table_mem, a->table_class);
+    if (a->ovf_mem)
+        chgpu_pool_free(a->ctx, a->ovf_mem, a->ovf_class);
     chgpu_ctx * ctx = a->ctx;
     delete a;
     chgpu_ctx_release(ctx);
@@ -2070,7 +2362,20 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_any_resolve(AggTable t, Agg
         const u64 i = row_begin + r;
         const u64 key = load_key_zext(keys, key_type, i);
         u64 slot = t.capacity; // the zero key's cell
-        if (key != 0)
+        if (t.find_only)
+        {
+            // a find-only block: the table is as the rows saw it, so a row that missed it missed it here too and claimed the overflow row
+            slot = table_find(t, key);
+            if (slot == AGG_SLOT_MISS)
+            {
+                if (t.ovf)
+                    for (u32 j = 0; j < d.n_aggs; ++j)
+                        if (d.a[j].kind == CHGPU_AGG_ANY && t.ovf[d.a[j].word] == ~(d.row_seq + i))
+                            t.ovf[d.a[j].word + 1] = load_arg_bits(d.a[j].ptr, d.a[j].arg_type, i);
+                continue;
+            }
+        }
+        else if (key != 0)
         {
             slot = dev_intHash64(key) & mask;
             for (u64 step = 0; step < t.capacity; ++step)
@@ -2192,15 +2497,23 @@ __global__ __launch_bounds__(256) void k_fx_from_double(const u64 * __restrict__
 
 static int agg_fx_shift(chgpu_agg * a, int sh)
 {
-    if (sh <= 0 || !a->table_mem)
+    if (sh <= 0)
         return CHGPU_OK;
     const u64 cells = a->t.capacity + 1;
     for (u32 w = 0; w < a->n_pub_words; ++w)
         if ((a->word_fx >> w) & 1)
         {
-            hipLaunchKernelGGL(k_fx_shift, dim3(chgpu_grid_for(a->ctx, cells, 256, 8)), dim3(256), 0, a->ctx->stream, a->t.words + (u64)w * cells,
-                               a->t.words + (u64)a->fx_hi[w] * cells, cells, sh);
-            a->ctx->counters[6] += 1;
+            if (a->table_mem)
+            {
+                hipLaunchKernelGGL(k_fx_shift, dim3(chgpu_grid_for(a->ctx, cells, 256, 8)), dim3(256), 0, a->ctx->stream, a->t.words + (u64)w * cells,
+                                   a->t.words + (u64)a->fx_hi[w] * cells, cells, sh);
+                a->ctx->counters[6] += 1;
+            }
+            if (a->ovf_mem) // the overflow row's pair moves with the window too (it may exist before the table: is_overflows blocks)
+            {
+                hipLaunchKernelGGL(k_fx_shift, dim3(1), dim3(256), 0, a->ctx->stream, (u64 *)a->ovf_mem + w, (u64 *)a->ovf_mem + a->fx_hi[w], (u64)1, sh);
+                a->ctx->counters[6] += 1;
+            }
         }
     CHGPU_HIP(hipGetLastError());
     return CHGPU_OK;
@@ -2227,18 +2540,24 @@ static int agg_fx_to_plain(chgpu_agg * a)
 {
     if (!a->word_fx)
         return CHGPU_OK;
-    if (a->table_mem)
-    {
-        const u64 cells = a->t.capacity + 1;
-        for (u32 w = 0; w < a->n_pub_words; ++w)
-            if ((a->word_fx >> w) & 1)
+    const u64 cells = a->t.capacity + 1;
+    for (u32 w = 0; w < a->n_pub_words; ++w)
+        if ((a->word_fx >> w) & 1)
+        {
+            if (a->table_mem)
             {
                 hipLaunchKernelGGL(k_fx_to_double, dim3(chgpu_grid_for(a->ctx, cells, 256, 8)), dim3(256), 0, a->ctx->stream, a->t.words + (u64)w * cells,
                                    a->t.words + (u64)a->fx_hi[w] * cells, cells, a->fx_base, 1);
                 a->ctx->counters[6] += 1;
             }
-        CHGPU_HIP(hipGetLastError());
-    }
+            if (a->ovf_mem) // (with or without a table)
+            {
+                hipLaunchKernelGGL(k_fx_to_double, dim3(1), dim3(256), 0, a->ctx->stream, (u64 *)a->ovf_mem + w, (u64 *)a->ovf_mem + a->fx_hi[w], (u64)1,
+                                   a->fx_base, 1);
+                a->ctx->counters[6] += 1;
+            }
+        }
+    CHGPU_HIP(hipGetLastError());
     a->word_is_f64 |= a->word_fx;
     a->word_fx = 0; // (word_fx_hi stays: the spare words keep being skipped; they hold zeros)
     return CHGPU_OK;
@@ -2372,6 +2691,12 @@ static int agg_debug_rounds(const chgpu_ctx * ctx, int rounds)
 // HBM table; a row that meets the max-fill limit stays pending for the next round (after the table has grown).
 __global__ __launch_bounds__(AGG_THREADS) void k_agg_tiles_pending_aos(AggTable t, AggDesc d, const u32 * __restrict__ rec, int key64, u64 n, u64 * __restrict__ pending)
 {
+    __shared__ u64 s_ovf[AGG_MAX_WORDS];
+    if (t.ovf)
+    {
+        ovf_lds_init(s_ovf);
+        __syncthreads();
+    }
     const u32 lane = threadIdx.x & 63;
     const u64 wave0 = ((u64)blockIdx.x * AGG_THREADS + threadIdx.x) >> 6;
     const u64 n_waves = ((u64)gridDim.x * AGG_THREADS) >> 6;
@@ -2386,9 +2711,14 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tiles_pending_aos(AggTable 
         if (i < n && ((word >> lane) & 1))
         {
             const u32 * r = rec + i * (key64 ? 4 : 3); // records are {word, key}: 12 bytes with a 4-byte key, 16 with an 8-byte key
-            const u64 slot = table_emplace(t, key64 ? (u64)r[2] | ((u64)r[3] << 32) : (u64)r[2], true);
+            const u64 slot = table_place(t, key64 ? (u64)r[2] | ((u64)r[3] << 32) : (u64)r[2], true);
             if (slot == ~0ull)
                 failed = true;
+            else if (slot == AGG_SLOT_MISS)
+            {
+                if (t.ovf)
+                    ovf_vals_lds(s_ovf, d, (u64)r[0] | ((u64)r[1] << 32), 0, 1);
+            }
             else
                 add_vals_global(t, d, slot, (u64)r[0] | ((u64)r[1] << 32), 0, 1);
         }
@@ -2397,6 +2727,11 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tiles_pending_aos(AggTable 
             pending[g] = b;
         if (b != 0 && lane == 0)
             t.ctrl->overflow = 1;
+    }
+    if (t.ovf)
+    {
+        __syncthreads();
+        ovf_flush_desc(t, s_ovf, d);
     }
 }
 
@@ -2409,9 +2744,19 @@ static int agg_finish_rounds_aos(chgpu_agg * a, const AggDesc & d, const u32 * r
         CHGPU_TRY(agg_read_ctrl(a, &c));
         if (!c.overflow && c.n_groups <= a->t.max_fill)
             return agg_debug_rounds(ctx, round);
-        CHGPU_TRY(agg_grow(a, c.n_groups, c.has_zero != 0));
-        if (!c.overflow)
-            return agg_debug_rounds(ctx, round);
+        if (a->t.find_only)
+        {
+            // a find-only block never grows the table: the rows a plan left pending are looked up once more (a look-up cannot fail)
+            if (!c.overflow)
+                return agg_debug_rounds(ctx, round);
+            CHGPU_TRY(agg_clear_overflow_flag(a));
+        }
+        else
+        {
+            CHGPU_TRY(agg_grow(a, c.n_groups, c.has_zero != 0));
+            if (!c.overflow)
+                return agg_debug_rounds(ctx, round);
+        }
         const u32 grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
         hipLaunchKernelGGL(k_agg_tiles_pending_aos, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, rec, key64, n, pending);
         ctx->counters[6] += 1;
@@ -2749,7 +3094,7 @@ static int agg_add_block_partitioned(chgpu_agg * a, const chgpu_col * key_col, c
     // every unit's flush may claim up to S+1 cells without the max-fill check: keep all of them inside the slack
     if (level != 1) // a first partitioning level touches no table: its level-2 calls size it
         CHGPU_TRY(agg_ensure_table(a, 2 * (max_units * (S + 1) + a->n_groups) + 2));
-    for (int guard = 0; level != 1 && guard < 16 && a->t.capacity / 2 < max_units * (S + 1) + a->n_groups; ++guard)
+    for (int guard = 0; level != 1 && !a->t.find_only && guard < 16 && a->t.capacity / 2 < max_units * (S + 1) + a->n_groups; ++guard)
     {
         AggCtrl c0;
         CHGPU_TRY(agg_read_ctrl(a, &c0));
@@ -3288,6 +3633,7 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
 {
     CHGPU_REQUIRE(a, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
     CHGPU_REQUIRE(row_begin <= row_end, CHGPU_ERR_BAD_ARGUMENTS, "row_begin > row_end");
+    a->started = true;
     chgpu_ctx * ctx = a->ctx;
     const u64 n = row_end - row_begin;
     if (filter)
@@ -3313,6 +3659,8 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
                   (unsigned long long)key_col->rows, (unsigned long long)row_end);
     if (n == 0)
         return CHGPU_OK;
+    if (a->t.find_only && a->n_aggs == 0)
+        return CHGPU_OK; // SELECT k ... GROUP BY k with no_more_keys: nothing to find (Aggregator.cpp:1030-1034)
     // Strategy by promised/observed cardinality:
     //   groups <= what one workgroup's LDS table holds (~70 % of its cells)   -> LDS-staged (RANGE mode / k_agg_rows_lds)
     //   more, with enough rows to amortise two extra passes                   -> PARTITIONED
@@ -3324,7 +3672,7 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
     const u64 lds_groups = (u64)lds_cells * 7 / 10;
     if (a->size_hint <= lds_groups && a->n_groups > lds_groups)
         a->size_hint = a->n_groups * 2; // the table already outgrew the LDS strategy
-    if (a->size_hint == 0 && !a->hint_probed && n >= (8ull << 20))
+    if (a->size_hint == 0 && !a->hint_probed && n >= (8ull << 20) && !a->t.find_only) // (a find-only block adds no group: nothing to sample)
     {
         a->hint_probed = true;
         const u64 probe_rows = 1ull << 20;
@@ -3520,9 +3868,19 @@ static int agg_finish_rounds(chgpu_agg * a, const AggDesc & d, const void * keys
         CHGPU_TRY(agg_read_ctrl(a, &c));
         if (!c.overflow && c.n_groups <= a->t.max_fill)
             return agg_debug_rounds(ctx, round);
-        CHGPU_TRY(agg_grow(a, c.n_groups, c.has_zero != 0));
-        if (!c.overflow)
-            return agg_debug_rounds(ctx, round);
+        if (a->t.find_only)
+        {
+            // a find-only block never grows the table: the rows a plan left pending are looked up once more (a look-up cannot fail)
+            if (!c.overflow)
+                return agg_debug_rounds(ctx, round);
+            CHGPU_TRY(agg_clear_overflow_flag(a));
+        }
+        else
+        {
+            CHGPU_TRY(agg_grow(a, c.n_groups, c.has_zero != 0));
+            if (!c.overflow)
+                return agg_debug_rounds(ctx, round);
+        }
         const u32 grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
         hipLaunchKernelGGL(k_agg_rows_direct<AGG_MODE_PENDING>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, keys, key_type, row_begin, n, pending);
         ctx->counters[6] += 1;
@@ -3600,26 +3958,9 @@ static bool agg_same_shape(const chgpu_agg * x, const chgpu_agg * y)
     return true;
 }
 
-extern "C" int chgpu_agg_merge(chgpu_agg * dst, const chgpu_agg * src)
+// Both sides of a merge to ONE fixed-point window (see chgpu_agg_merge)
+static int agg_merge_align_fx(chgpu_agg * dst, const chgpu_agg * src)
 {
-    ChgpuDeviceGuard _dev_guard(dst ? dst->ctx : nullptr);
-    CHGPU_REQUIRE(dst && src, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(agg_same_shape(dst, src), CHGPU_ERR_BAD_ARGUMENTS, "cannot merge aggregation states of different shape");
-    // variants of different pipeline streams live on different contexts: the source's kernels run on ITS stream and must have finished
-    // before this context's stream reads its table (the reference merges after every stream has finished consuming)
-    if (src->ctx != dst->ctx)
-        CHGPU_HIP(hipStreamSynchronize(src->ctx->stream));
-    if (dst->key_type < 0)
-    {
-        // mergeWithoutKeyDataImpl (Aggregator.cpp:2584-2628)
-        for (u32 w = 0; w < dst->n_words;)
-            w += agg_merge_host_word(dst, w, src->host_words);
-        dst->nokey_kept += src->nokey_kept;
-        return CHGPU_OK;
-    }
-    if (!src->table_mem)
-        return CHGPU_OK;
-    CHGPU_REQUIRE(dst->n_words == src->n_words, CHGPU_ERR_BAD_ARGUMENTS, "cannot merge aggregations created under different deterministic_float_sums settings");
     if (dst->word_fx || src->word_fx)
     {
         // fixed-point sums: both sides to ONE window first (the source's states are re-expressed in place: same values, possibly a coarser
@@ -3664,6 +4005,87 @@ extern "C" int chgpu_agg_merge(chgpu_agg * dst, const chgpu_agg * src)
         if (src->ctx != dst->ctx)
             CHGPU_HIP(hipStreamSynchronize(src->ctx->stream)); // (the re-expression ran on the source's stream)
     }
+    return CHGPU_OK;
+}
+
+// mergeWithoutKeyDataImpl for the overflow rows (Aggregator.cpp:2584-2628): src's words (host copy, the window already shared) folded
+// into dst's, on the host -- one row of at most AGG_MAX_WORDS words
+static int agg_fold_overflow_words(chgpu_agg * dst, const u64 * in)
+{
+    if (!dst->ovf_mem)
+    {
+        CHGPU_TRY(chgpu_pool_alloc(dst->ctx, AGG_MAX_WORDS * 8, &dst->ovf_mem, &dst->ovf_class));
+        CHGPU_HIP(hipMemsetAsync(dst->ovf_mem, 0, AGG_MAX_WORDS * 8, dst->ctx->stream));
+    }
+    u64 o[AGG_MAX_WORDS] = {0};
+    CHGPU_TRY(chgpu_read_back(dst->ctx, dst->ovf_mem, o, dst->n_words * 8));
+    for (u32 w = 0; w < dst->n_words; ++w)
+    {
+        if ((dst->word_fx_hi >> w) & 1)
+            continue; // with its low half
+        if ((dst->word_fx >> w) & 1)
+        {
+            const u32 h = dst->fx_hi[w];
+            const u64 lo = o[w] + in[w];
+            o[h] += in[h] + (lo < o[w] ? 1 : 0);
+            o[w] = lo;
+        }
+        else if ((dst->word_any >> w) & 1)
+        {
+            if (o[w] == 0 && in[w] != 0) // changeFirstTime: a state that has a value keeps it
+                o[w] = in[w], o[w + 1] = in[w + 1];
+            ++w;
+        }
+        else if ((dst->word_is_f64 >> (16 + w)) & 1)
+            o[w] = in[w] > o[w] ? in[w] : o[w];
+        else if ((dst->word_is_f64 >> w) & 1)
+        {
+            double x, y;
+            memcpy(&x, &o[w], 8);
+            memcpy(&y, &in[w], 8);
+            x += y;
+            memcpy(&o[w], &x, 8);
+        }
+        else
+            o[w] += in[w];
+    }
+    CHGPU_HIP(hipMemcpyAsync(dst->ovf_mem, o, dst->n_words * 8, hipMemcpyHostToDevice, dst->ctx->stream));
+    CHGPU_HIP(hipStreamSynchronize(dst->ctx->stream)); // (o is on this stack frame)
+    return CHGPU_OK;
+}
+static int agg_merge_overflow_rows(chgpu_agg * dst, const chgpu_agg * src)
+{
+    if (!src->ovf_mem)
+        return CHGPU_OK;
+    u64 in[AGG_MAX_WORDS] = {0};
+    CHGPU_TRY(chgpu_read_back(src->ctx, src->ovf_mem, in, src->n_words * 8));
+    return agg_fold_overflow_words(dst, in);
+}
+
+extern "C" int chgpu_agg_merge(chgpu_agg * dst, const chgpu_agg * src)
+{
+    ChgpuDeviceGuard _dev_guard(dst ? dst->ctx : nullptr);
+    CHGPU_REQUIRE(dst && src, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_REQUIRE(agg_same_shape(dst, src), CHGPU_ERR_BAD_ARGUMENTS, "cannot merge aggregation states of different shape");
+    // variants of different pipeline streams live on different contexts: the source's kernels run on ITS stream and must have finished
+    // before this context's stream reads its table (the reference merges after every stream has finished consuming)
+    if (src->ctx != dst->ctx)
+        CHGPU_HIP(hipStreamSynchronize(src->ctx->stream));
+    if (dst->key_type < 0)
+    {
+        // mergeWithoutKeyDataImpl (Aggregator.cpp:2584-2628)
+        for (u32 w = 0; w < dst->n_words;)
+            w += agg_merge_host_word(dst, w, src->host_words);
+        dst->nokey_kept += src->nokey_kept;
+        return CHGPU_OK;
+    }
+    if (!src->table_mem && !src->ovf_mem)
+        return CHGPU_OK;
+    CHGPU_REQUIRE(dst->n_words == src->n_words, CHGPU_ERR_BAD_ARGUMENTS, "cannot merge aggregations created under different deterministic_float_sums settings");
+    CHGPU_TRY(agg_merge_align_fx(dst, src));
+    CHGPU_TRY(agg_merge_overflow_rows(dst, src));
+    if (!src->table_mem)
+        return CHGPU_OK;
     // the source's zero cell participates only when it is set
     AggCtrl sc;
     CHGPU_TRY(chgpu_read_back(dst->ctx, src->t.ctrl, &sc, sizeof(sc)));
@@ -3756,6 +4178,245 @@ extern "C" int chgpu_agg_merge_states(chgpu_agg * dst, const chgpu_col * key_col
         chgpu_set_error(CHGPU_ERR_DEVICE, "staging copy failed");
     chgpu_col_free(stage);
     return rc;
+}
+
+// ---- max_rows_to_group_by / group_by_overflow_mode / overflow_row ----
+extern "C" int chgpu_agg_set_limits(chgpu_agg * a, uint64_t max_rows_to_group_by, int group_by_overflow_mode, int overflow_row)
+{
+    CHGPU_REQUIRE(a, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_REQUIRE(group_by_overflow_mode >= CHGPU_OVERFLOW_THROW && group_by_overflow_mode <= CHGPU_OVERFLOW_ANY, CHGPU_ERR_BAD_ARGUMENTS,
+                  "unknown group_by_overflow_mode %d", group_by_overflow_mode);
+    CHGPU_REQUIRE(!a->started, CHGPU_ERR_BAD_ARGUMENTS, "GROUP BY limits must be set before the first block");
+    a->max_rows = max_rows_to_group_by;
+    a->overflow_mode = group_by_overflow_mode;
+    a->overflow_row = overflow_row != 0;
+    return CHGPU_OK;
+}
+
+// Aggregator::checkLimits (Aggregator.cpp:1816-1830) on `groups` (zero key included, overflow row excluded): THROW fails, BREAK clears
+// *keep, ANY sets *no_more_keys
+static int agg_check_limits(chgpu_agg * a, u64 groups, int * no_more_keys, int * keep)
+{
+    if (a->max_rows == 0 || groups <= a->max_rows)
+        return CHGPU_OK;
+    switch (a->overflow_mode)
+    {
+        case CHGPU_OVERFLOW_THROW:
+            return chgpu_set_error(CHGPU_ERR_TOO_MANY_ROWS, "Limit for rows to GROUP BY exceeded: has %llu rows, maximum: %llu", (unsigned long long)groups,
+                                   (unsigned long long)a->max_rows);
+        case CHGPU_OVERFLOW_BREAK: *keep = 0; break;
+        default: *no_more_keys = 1; break;
+    }
+    return CHGPU_OK;
+}
+
+extern "C" int chgpu_agg_execute_on_block(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, uint64_t row_begin,
+                                          uint64_t row_end, const chgpu_col * filter_u8, int * no_more_keys, int * keep_reading)
+{
+    ChgpuDeviceGuard _dev_guard(a ? a->ctx : nullptr);
+    CHGPU_REQUIRE(a && no_more_keys && keep_reading, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    *keep_reading = 1;
+    if (a->key_type < 0)
+        return agg_add_block_impl(a, key_col, arg_cols, row_begin, row_end, filter_u8); // without key: limits never trigger
+    CHGPU_TRY(agg_ensure_overflow_row(a));
+    const bool find_only = *no_more_keys != 0;
+    agg_set_find_only(a, find_only);
+    const int rc = agg_add_block_impl(a, key_col, arg_cols, row_begin, row_end, filter_u8);
+    agg_set_find_only(a, false);
+    CHGPU_TRY(rc);
+    if (find_only || a->max_rows == 0)
+        return CHGPU_OK;
+    // every plan ends on a read-back of the table's header (agg_finish_rounds*): a->n_groups is this block's result; a table that does
+    // not exist yet holds no group
+    return agg_check_limits(a, a->table_mem ? a->n_groups : 0, no_more_keys, keep_reading);
+}
+
+extern "C" int chgpu_agg_merge_limited(chgpu_agg * dst, const chgpu_agg * src, int * no_more_keys, int * keep_merging)
+{
+    ChgpuDeviceGuard _dev_guard(dst ? dst->ctx : nullptr);
+    CHGPU_REQUIRE(dst && src && no_more_keys && keep_merging, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    *keep_merging = 1;
+    if (dst->key_type < 0)
+        return chgpu_agg_merge(dst, src);
+    CHGPU_REQUIRE(agg_same_shape(dst, src) && dst->n_words == src->n_words, CHGPU_ERR_BAD_ARGUMENTS, "cannot merge aggregation states of different shape");
+    dst->started = true;
+    // mergeSingleLevelDataImpl: checkLimits on dst's size before the source is merged
+    if (!*no_more_keys)
+    {
+        u64 g = 0;
+        CHGPU_TRY(chgpu_agg_size(dst, &g));
+        CHGPU_TRY(agg_check_limits(dst, g, no_more_keys, keep_merging));
+    }
+    if (!*keep_merging)
+    {
+        // BREAK: no more keyed data; the overflow rows still merge (mergeWithoutKeyDataImpl)
+        if (src->ctx != dst->ctx)
+            CHGPU_HIP(hipStreamSynchronize(src->ctx->stream));
+        if (!src->ovf_mem)
+            return CHGPU_OK;
+        CHGPU_TRY(agg_merge_align_fx(dst, src));
+        return agg_merge_overflow_rows(dst, src);
+    }
+    if (!*no_more_keys)
+        return chgpu_agg_merge(dst, src);
+    // mergeDataNoMoreKeysImpl / mergeDataOnlyExistingKeysImpl: find-only, a missing key's state to dst's overflow row or dropped
+    CHGPU_TRY(agg_ensure_overflow_row(dst));
+    agg_set_find_only(dst, true);
+    const int rc = chgpu_agg_merge(dst, src);
+    agg_set_find_only(dst, false);
+    return rc;
+}
+
+extern "C" int chgpu_agg_merge_states_limited(chgpu_agg * dst, const chgpu_col * key_col, const chgpu_col * const * state_cols, uint64_t rows,
+                                              int is_overflows, int * no_more_keys, int * keep_reading)
+{
+    ChgpuDeviceGuard _dev_guard(dst ? dst->ctx : nullptr);
+    CHGPU_REQUIRE(dst && state_cols && no_more_keys && keep_reading, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    *keep_reading = 1;
+    if (dst->key_type < 0)
+        return chgpu_agg_merge_states(dst, key_col, state_cols, rows);
+    dst->started = true;
+    if (is_overflows)
+    {
+        // a block flagged is_overflows: its (one) row merges into the overflow row (mergeBlockWithoutKeyStreamsImpl)
+        CHGPU_REQUIRE(rows <= 1, CHGPU_ERR_BAD_ARGUMENTS, "an is_overflows block has one row");
+        for (u32 w = 0; w < dst->n_pub_words; ++w)
+        {
+            CHGPU_REQUIRE(state_cols[w], CHGPU_ERR_BAD_ARGUMENTS, "state column %u is NULL", w);
+            CHGPU_REQUIRE(chgpu_type_size(state_cols[w]->type) == 8 && state_cols[w]->rows >= rows, CHGPU_ERR_BAD_ARGUMENTS, "state column %u: 8-byte words, %llu rows", w,
+                          (unsigned long long)rows);
+        }
+        if (rows == 0)
+            return CHGPU_OK;
+        u64 in[AGG_MAX_WORDS] = {0};
+        for (u32 w = 0; w < dst->n_pub_words; ++w)
+            CHGPU_TRY(chgpu_read_back(dst->ctx, state_cols[w]->data, &in[w], 8));
+        if (dst->word_fx)
+        {
+            // Float64 states of fixed-point sums: admitted to the window like any state column, then converted
+            u32 emax = 0, emin = 2047;
+            bool bad = false;
+            for (u32 w = 0; w < dst->n_pub_words && !bad; ++w)
+                if ((dst->word_fx >> w) & 1)
+                {
+                    u32 e = 0, em = 2047;
+                    CHGPU_TRY(agg_fx_stats(dst->ctx, state_cols[w]->data, CHGPU_F64, 0, 1, &e, &em, &bad));
+                    emax = e > emax ? e : emax;
+                    emin = em < emin ? em : emin;
+                }
+            if (bad)
+                CHGPU_TRY(agg_fx_to_plain(dst));
+            else
+                CHGPU_TRY(agg_fx_admit(dst, emax, emin, 1));
+            for (u32 w = 0; w < dst->n_pub_words; ++w)
+                if ((dst->word_fx >> w) & 1)
+                {
+                    const Fx128 x = fx_from_double(in[w], dst->fx_base);
+                    in[w] = x.lo, in[dst->fx_hi[w]] = x.hi;
+                }
+        }
+        return agg_fold_overflow_words(dst, in);
+    }
+    const bool find_only = *no_more_keys != 0;
+    if (find_only)
+        CHGPU_TRY(agg_ensure_overflow_row(dst));
+    agg_set_find_only(dst, find_only);
+    const int rc = chgpu_agg_merge_states(dst, key_col, state_cols, rows);
+    agg_set_find_only(dst, false);
+    CHGPU_TRY(rc);
+    // mergeOnBlock checks the limits after the block, as executeOnBlock does
+    if (find_only || dst->max_rows == 0)
+        return CHGPU_OK;
+    u64 g = 0;
+    CHGPU_TRY(chgpu_agg_size(dst, &g));
+    return agg_check_limits(dst, g, no_more_keys, keep_reading);
+}
+
+// The overflow row: final -> one result per aggregate (the without-key conventions: count / sum 0, avg NaN, min / max / any the type's
+// default when no row reached it), else its raw state words as chgpu_agg_export_states gives them.  One-row columns; *has = 0 when the
+// aggregation has none.
+extern "C" int chgpu_agg_overflow_row(chgpu_agg * a, int final, chgpu_col ** cols, int * has)
+{
+    ChgpuDeviceGuard _dev_guard(a ? a->ctx : nullptr);
+    CHGPU_REQUIRE(a && cols && has, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    *has = 0;
+    if (a->key_type < 0 || !a->ovf_mem)
+        return CHGPU_OK;
+    chgpu_ctx * ctx = a->ctx;
+    u64 o[AGG_MAX_WORDS] = {0};
+    CHGPU_TRY(chgpu_read_back(ctx, a->ovf_mem, o, a->n_words * 8));
+    // fixed-point pairs to their Float64 value (the public word)
+    u64 pub[AGG_MAX_WORDS] = {0};
+    for (u32 w = 0; w < a->n_pub_words; ++w)
+    {
+        pub[w] = o[w];
+        if ((a->word_fx >> w) & 1)
+        {
+            const double x = fx_to_double(o[w], o[a->fx_hi[w]], a->fx_base);
+            memcpy(&pub[w], &x, 8);
+        }
+    }
+    const u32 n_out = final ? a->n_aggs : a->n_pub_words;
+    for (u32 k = 0; k < n_out; ++k)
+        cols[k] = nullptr;
+    int rc = CHGPU_OK;
+    if (!final)
+    {
+        for (u32 w = 0; w < a->n_pub_words && rc == CHGPU_OK; ++w)
+            rc = chgpu_col_upload(ctx, (((a->word_is_f64 | a->word_fx) >> w) & 1) ? CHGPU_F64 : CHGPU_U64, &pub[w], 1, &cols[w]);
+    }
+    else
+        for (u32 j = 0; j < a->n_aggs && rc == CHGPU_OK; ++j)
+        {
+            const u32 w = a->word_off[j];
+            const int at = a->arg_types[j];
+            const bool f = chgpu_type_is_float(at);
+            u64 v = 0;
+            int type = CHGPU_U64;
+            switch (a->kinds[j])
+            {
+                case CHGPU_AGG_COUNT: v = pub[w]; break;
+                case CHGPU_AGG_SUM: v = pub[w], type = chgpu_sum_result_type(at); break;
+                case CHGPU_AGG_AVG:
+                {
+                    double num;
+                    if (f)
+                        memcpy(&num, &pub[w], 8);
+                    else
+                        num = chgpu_sum_result_type(at) == CHGPU_I64 ? (double)(i64)pub[w] : (double)pub[w];
+                    const double r = num / (double)pub[w + 1]; // 0 / 0 = NaN, as without key
+                    memcpy(&v, &r, 8);
+                    type = CHGPU_F64;
+                    break;
+                }
+                default:
+                {
+                    // min / max / any: the value in the argument's type; the type's default when no row reached it
+                    type = at;
+                    if (pub[w])
+                        v = a->kinds[j] == CHGPU_AGG_ANY ? pub[w + 1] : agg_order_key_inverse(a->kinds[j] == CHGPU_AGG_MIN ? ~pub[w] : pub[w], at);
+                    if (at == CHGPU_F32)
+                    {
+                        double x;
+                        memcpy(&x, &v, 8);
+                        const float y = (float)x; // (the widening was exact: so is this)
+                        v = 0;
+                        memcpy(&v, &y, 4);
+                    }
+                    break;
+                }
+            }
+            rc = chgpu_col_upload(ctx, type, &v, 1, &cols[j]); // (little endian: a narrower type takes the low bytes)
+        }
+    if (rc != CHGPU_OK)
+    {
+        for (u32 k = 0; k < n_out; ++k)
+            if (cols[k])
+                chgpu_col_free(cols[k]), cols[k] = nullptr;
+        return rc;
+    }
+    *has = 1;
+    return CHGPU_OK;
 }
 
 __global__ __launch_bounds__(256) void k_widen_keys(const void * keys, int type, u64 n, u64 * out)

@@ -221,6 +221,7 @@ struct Chunk
 {
     Columns columns;
     size_t num_rows = 0;
+    bool is_overflows = false; // AggregatedChunkInfo::is_overflows: the overflow row of a GROUP BY under max_rows_to_group_by
     bool empty() const { return num_rows == 0; }
     void clear() { columns.clear(); num_rows = 0; }
     explicit operator bool() const { return !columns.empty() || num_rows; }
@@ -843,12 +844,21 @@ struct AggregateDescription
     size_t argument = 0;   // position in the chunk
 };
 
+/// Aggregator::Params' GROUP BY limits (max_rows_to_group_by, group_by_overflow_mode, overflow_row); 0 rows = no limit
+struct GroupByLimits
+{
+    uint64_t max_rows_to_group_by = 0;
+    int group_by_overflow_mode = CHGPU_OVERFLOW_THROW;
+    bool overflow_row = false;
+    bool any() const { return max_rows_to_group_by != 0 || overflow_row; }
+};
+
 /// Aggregator + AggregatedDataVariants (Aggregator.h:179-265) for one numeric key or no key.
 class GpuAggregator
 {
 public:
-    GpuAggregator(ContextPtr ctx_, int key_type_, std::vector<AggregateDescription> aggregates_, uint64_t size_hint = 0)
-        : ctx(std::move(ctx_)), key_type(key_type_), aggregates(std::move(aggregates_))
+    GpuAggregator(ContextPtr ctx_, int key_type_, std::vector<AggregateDescription> aggregates_, uint64_t size_hint = 0, GroupByLimits limits_ = {})
+        : ctx(std::move(ctx_)), key_type(key_type_), aggregates(std::move(aggregates_)), limits(limits_)
     {
         std::vector<int> kinds, types;
         for (auto & a : aggregates)
@@ -857,22 +867,76 @@ public:
             types.push_back(a.argument_type);
         }
         check(chgpu_agg_create(ctx->get(), key_type, static_cast<uint32_t>(aggregates.size()), kinds.data(), types.data(), size_hint, &h));
+        if (limits.any())
+        {
+            const int rc = chgpu_agg_set_limits(h, limits.max_rows_to_group_by, limits.group_by_overflow_mode, limits.overflow_row ? 1 : 0);
+            if (rc != CHGPU_OK)
+            {
+                chgpu_agg_free(h);
+                check(rc);
+            }
+        }
     }
     ~GpuAggregator() { chgpu_agg_free(h); }
     GpuAggregator(const GpuAggregator &) = delete;
 
-    /// Aggregator::executeOnBlock(columns, row_begin, row_end, ...): returns false to stop reading (never here)
-    bool executeOnBlock(const Columns & columns, size_t row_begin, size_t row_end, std::optional<size_t> key_position)
+    /// Aggregator::executeOnBlock(columns, row_begin, row_end, ...): returns false to stop reading (group_by_overflow_mode BREAK).
+    /// no_more_keys is the caller's, one per stream (AggregatingTransform::no_more_keys); ANY sets it, THROW raises TOO_MANY_ROWS.
+    bool executeOnBlock(const Columns & columns, size_t row_begin, size_t row_end, std::optional<size_t> key_position, bool & no_more_keys)
     {
         std::vector<const chgpu_col *> args;
         for (auto & a : aggregates)
             args.push_back(a.kind == CHGPU_AGG_COUNT ? nullptr : columns.at(a.argument)->handle());
         const chgpu_col * key = key_position ? columns.at(*key_position)->handle() : nullptr;
-        check(chgpu_agg_add_block(h, key, args.data(), row_begin, row_end));
-        return true;
+        if (!limits.any())
+        {
+            check(chgpu_agg_add_block(h, key, args.data(), row_begin, row_end));
+            return true;
+        }
+        int nmk = no_more_keys ? 1 : 0, keep = 1;
+        check(chgpu_agg_execute_on_block(h, key, args.data(), row_begin, row_end, nullptr, &nmk, &keep));
+        no_more_keys = nmk != 0;
+        return keep != 0;
+    }
+    bool executeOnBlock(const Columns & columns, size_t row_begin, size_t row_end, std::optional<size_t> key_position)
+    {
+        bool no_more_keys = false;
+        return executeOnBlock(columns, row_begin, row_end, key_position, no_more_keys);
     }
     /// mergeDataImpl
     void merge(const GpuAggregator & other) { check(chgpu_agg_merge(h, other.h)); }
+    /// One step of mergeSingleLevelDataImpl under the limits: checkLimits on this (dst) before `other` is merged, with the merge's own
+    /// no_more_keys; false = BREAK (keyed data no longer merged; overflow rows still are)
+    bool mergeLimited(const GpuAggregator & other, bool & no_more_keys)
+    {
+        int nmk = no_more_keys ? 1 : 0, keep = 1;
+        check(chgpu_agg_merge_limited(h, other.h, &nmk, &keep));
+        no_more_keys = nmk != 0;
+        return keep != 0;
+    }
+    const GroupByLimits & getLimits() const { return limits; }
+    /// prepareBlockAndFillWithoutKey(..., is_overflows = true): the overflow row as a one-row chunk (default key), empty when there is none
+    Chunk convertOverflowRow() const
+    {
+        std::vector<chgpu_col *> res(aggregates.size(), nullptr);
+        int has = 0;
+        check(chgpu_agg_overflow_row(h, 1, res.data(), &has));
+        Chunk out;
+        if (!has)
+            return out;
+        out.num_rows = 1;
+        out.is_overflows = true;
+        if (key_type >= 0)
+        {
+            const uint64_t zero = 0; // (little endian: the low bytes are the default of every key width)
+            chgpu_col * k = nullptr;
+            check(chgpu_col_upload(ctx->get(), key_type, &zero, 1, &k));
+            out.columns.push_back(std::make_shared<ColumnVector>(ctx, k));
+        }
+        for (auto * r : res)
+            out.columns.push_back(std::make_shared<ColumnVector>(ctx, r));
+        return out;
+    }
     /// convertToBlocks(final = true): [key column,] one column per aggregate
     Chunk convertToBlock() const
     {
@@ -899,6 +963,7 @@ private:
     ContextPtr ctx;
     int key_type;
     std::vector<AggregateDescription> aggregates;
+    GroupByLimits limits;
     chgpu_agg * h = nullptr;
 };
 
@@ -928,11 +993,15 @@ public:
     std::string getName() const override { return "GpuAggregatingTransform"; }
     void consume(Chunk chunk)
     {
-        if (chunk.num_rows == 0)
+        if (chunk.num_rows == 0 || is_consume_finished)
             return;
         src_rows += chunk.num_rows;
-        many_data->variants.at(current_variant)->executeOnBlock(chunk.columns, 0, chunk.num_rows, key_position); // :664-693
+        // :664-693 -- false (group_by_overflow_mode BREAK): the input is finished early (:681-682)
+        if (!many_data->variants.at(current_variant)->executeOnBlock(chunk.columns, 0, chunk.num_rows, key_position, no_more_keys))
+            is_consume_finished = true;
     }
+    /// the driver stops feeding this stream once it is set (AggregatingTransform's is_consume_finished: the input port is closed)
+    bool isConsumeFinished() const { return is_consume_finished; }
     /// the input port is finished: initGenerate (:695-744)
     void work() override
     {
@@ -942,18 +1011,38 @@ public:
         if (many_data->num_finished.fetch_add(1) + 1 < many_data->variants.size())
             return; // not the last stream: its variant stays in many_data for the one that is
         auto & variants = many_data->variants;
-        for (size_t i = 1; i < variants.size(); ++i) // mergeDataImpl into the first (prepareVariantsToMerge keeps the largest first; sizes need a read-back each)
-            variants[0]->merge(*variants[i]);
+        if (variants[0]->getLimits().any())
+        {
+            // prepareVariantsToMerge: the largest variant first; mergeSingleLevelDataImpl with a no_more_keys of the merge's own, checkLimits
+            // before each source (chgpu_agg_merge_limited)
+            std::stable_sort(variants.begin(), variants.end(), [](const auto & x, const auto & y) { return x->size() > y->size(); });
+            bool merge_no_more_keys = false;
+            for (size_t i = 1; i < variants.size(); ++i)
+                variants[0]->mergeLimited(*variants[i], merge_no_more_keys); // (after BREAK only the overflow rows still merge)
+        }
+        else
+            for (size_t i = 1; i < variants.size(); ++i) // mergeDataImpl into the first (prepareVariantsToMerge keeps the largest first; sizes need a read-back each)
+                variants[0]->merge(*variants[i]);
         is_last = true;
     }
     /// true on exactly one of the streams' transforms after every stream's work(): the one that generates
     bool isGenerating() const { return is_last; }
+    /// The overflow chunk (is_overflows) comes first, then the keyed result.  The reference's converting transform prepares that block
+    /// from the merged overflow rows before it merges the keyed tables (ConvertingAggregatedToChunksTransform, recalled, not checked
+    /// against a checkout); here the variants are merged in work(), and the overflow rows merge with them.
     Chunk generate()
     {
         if (!is_generate_initialized)
             work();
         if (!is_last)
             return Chunk{};
+        if (!overflow_generated)
+        {
+            overflow_generated = true;
+            Chunk ovf = many_data->variants[0]->convertOverflowRow(); // (none without an overflow row: no device work)
+            if (ovf.num_rows)
+                return ovf;
+        }
         return many_data->variants[0]->convertToBlock();
     }
     uint64_t src_rows = 0;
@@ -962,8 +1051,11 @@ private:
     ManyAggregatedDataPtr many_data;
     size_t current_variant;
     std::optional<size_t> key_position;
+    bool no_more_keys = false; // this stream's (AggregatingTransform::no_more_keys)
+    bool is_consume_finished = false;
     bool is_generate_initialized = false;
     bool is_last = false;
+    bool overflow_generated = false;
 };
 
 /// FilterTransform + AggregatingTransform without key, fused: `SELECT sum(val), count() WHERE pred <op> constant` in one pass over the

@@ -72,18 +72,28 @@ class KeyDict:
 class KeysFixedAggregator:
     """Aggregator over keys128 / keys256: executeOnBlock packs and encodes the key columns, the inner aggregator groups by id."""
 
-    def __init__(self, key_dtypes, aggs, size_hint: int = 0, ctx: Context | None = None):
+    def __init__(self, key_dtypes, aggs, size_hint: int = 0, ctx: Context | None = None, max_rows_to_group_by: int = 0,
+                 group_by_overflow_mode: str = "throw", overflow_row: bool = False):
         self.ctx = ctx if ctx is not None else Context(0)
         self.dict = KeyDict(key_dtypes, self.ctx, size_hint)
-        self.inner = Aggregator(np.uint32, aggs, size_hint=size_hint, ctx=self.ctx)
+        self.inner = Aggregator(np.uint32, aggs, size_hint=size_hint, ctx=self.ctx, max_rows_to_group_by=max_rows_to_group_by,
+                                group_by_overflow_mode=group_by_overflow_mode, overflow_row=overflow_row)
 
-    def execute_on_block(self, key_cols, args, row_begin: int = 0, row_end: int | None = None):
-        ids = self.dict.encode(key_cols, True, row_begin, row_end)
+    @property
+    def no_more_keys(self) -> bool:
+        return self.inner.no_more_keys
+
+    def execute_on_block(self, key_cols, args, row_begin: int = 0, row_end: int | None = None) -> bool:
+        # once no_more_keys is set the dictionary stops growing: an absent key gets 0xFFFFFFFF, which the table lacks (a miss)
+        ids = self.dict.encode(key_cols, not self.inner.no_more_keys, row_begin, row_end)
         acols = [self.ctx.column(a) if a is not None else None for a in args]
         if row_begin or row_end is not None:
             n = ids.size()
             acols = [a.cut(row_begin, n) if a is not None else None for a in acols]
-        self.inner.execute_on_block(ids, acols)
+        return self.inner.execute_on_block(ids, acols)
+
+    def overflow_row(self, final: bool = True):
+        return self.inner.overflow_row(final)
 
     def __len__(self):
         return len(self.inner)

@@ -40,7 +40,8 @@ enum
     CHGPU_ERR_LOGICAL = -4,         /* LOGICAL_ERROR */
     CHGPU_ERR_BAD_ARGUMENTS = -5,   /* BAD_ARGUMENTS */
     CHGPU_ERR_DEVICE = -6,          /* a HIP runtime call failed */
-    CHGPU_ERR_TOO_MANY_ROWS = -7    /* TOO_MANY_ROWS (HashJoin.cpp:563-564: block >= 2^32 rows) */
+    CHGPU_ERR_TOO_MANY_ROWS = -7    /* TOO_MANY_ROWS (HashJoin.cpp:563-564: block >= 2^32 rows; Aggregator::checkLimits,
+                                       Aggregator.cpp:1816-1830: max_rows_to_group_by exceeded under group_by_overflow_mode THROW) */
 };
 
 /* ---- column element types (the TypeIndex subset of the hot path, src/Core/TypeId.h) ----
@@ -515,6 +516,37 @@ int chgpu_agg_serialize_states(chgpu_ctx * ctx, int kind, const chgpu_col * word
 int chgpu_agg_deserialize_states(chgpu_ctx * ctx, int kind, const chgpu_col * bytes_u8, uint32_t n_streams, const uint64_t * stream_byte_begin,
                                  const uint64_t * stream_rows, chgpu_col ** word0, chgpu_col ** word1);
 int chgpu_agg_free(chgpu_agg * agg);
+/* ---- max_rows_to_group_by / group_by_overflow_mode / overflow_row (Aggregator::Params, src/QueryPipeline/SizeLimits.h OverflowMode) ----
+   max_rows_to_group_by = 0: no limit (the default).  Set before the first block or merge, else CHGPU_ERR_BAD_ARGUMENTS; an unknown mode
+   too.  Without key (key_type < 0) the limits are accepted and never trigger, and overflow_row has no effect.  With no limit and no
+   overflow row, nothing changes. */
+enum
+{
+    CHGPU_OVERFLOW_THROW = 0,
+    CHGPU_OVERFLOW_BREAK = 1,
+    CHGPU_OVERFLOW_ANY = 2
+};
+int chgpu_agg_set_limits(chgpu_agg * agg, uint64_t max_rows_to_group_by, int group_by_overflow_mode, int overflow_row);
+/* executeOnBlock (Aggregator.cpp:1181-1194, :1611): filter_u8 may be NULL (as chgpu_agg_add_block_filtered).  *no_more_keys is the
+   caller's, one per stream: when it is set every row FINDS its key and inserts none -- a row whose key the table lacks goes to the
+   overflow row (overflow_row on) or is dropped.  Otherwise the block is added in full and checkLimits runs on the number of groups G
+   (zero key included, overflow row excluded): G > max_rows_to_group_by -> THROW: CHGPU_ERR_TOO_MANY_ROWS ("Limit for rows to GROUP BY
+   exceeded: has G rows, maximum: M"; the block stays added), BREAK: *keep_reading = 0 (not latched), ANY: *no_more_keys = 1. */
+int chgpu_agg_execute_on_block(chgpu_agg * agg, const chgpu_col * key_col, const chgpu_col * const * arg_cols, uint64_t row_begin,
+                               uint64_t row_end, const chgpu_col * filter_u8, int * no_more_keys, int * keep_reading);
+/* One step of mergeSingleLevelDataImpl under limits (the caller merges the variants into the largest first, prepareVariantsToMerge):
+   checkLimits on dst's size BEFORE src is merged, with the merge's own *no_more_keys -- THROW fails, BREAK: *keep_merging = 0 and only
+   the overflow rows merge, ANY: find-only from here on (a source state whose key dst lacks goes to dst's overflow row, or is dropped
+   without one).  Overflow rows always merge into dst's. */
+int chgpu_agg_merge_limited(chgpu_agg * dst, const chgpu_agg * src, int * no_more_keys, int * keep_merging);
+/* One mergeOnBlock under limits: find-only when *no_more_keys is set, checkLimits after the block (as executeOnBlock); a block flagged
+   is_overflows (one row) merges into the overflow row. */
+int chgpu_agg_merge_states_limited(chgpu_agg * dst, const chgpu_col * key_col, const chgpu_col * const * state_cols, uint64_t rows,
+                                   int is_overflows, int * no_more_keys, int * keep_reading);
+/* The overflow row (prepareBlockAndFillWithoutKey(..., is_overflows)): final != 0 -> one one-row result column per aggregate, else the
+   raw state words (as chgpu_agg_export_states).  *has = 0 when there is none (no executeOnBlock yet with overflow_row on).  The
+   overflow row is never part of chgpu_agg_size, the exports or chgpu_agg_finalize. */
+int chgpu_agg_overflow_row(chgpu_agg * agg, int final, chgpu_col ** cols, int * has);
 
 /* ================================================================================================
  * a19/a20 hash join  —  IJoin::addBlockToJoin / onBuildPhaseFinish / joinBlock (src/Interpreters/IJoin.h:80-93,142)
