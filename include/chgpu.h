@@ -46,8 +46,8 @@ enum
 
 /* ---- column element types (the TypeIndex subset of the hot path, src/Core/TypeId.h) ----
    Every entry point takes every type unless it says otherwise; arithmetic (chgpu_arith) and the fused expression kernel
-   (chgpu_expr_filter_sum) are limited to the first six and answer CHGPU_ERR_NOT_IMPLEMENTED for UInt16 / Int16 / Int8 /
-   Float32; keys (GROUP BY, join, sharding, packed) are integers. */
+   (chgpu_expr_filter_sum) are limited to the integers among the first six and answer CHGPU_ERR_NOT_IMPLEMENTED for Float64 /
+   UInt16 / Int16 / Int8 / Float32; keys (GROUP BY, join, sharding, packed) are integers. */
 enum
 {
     CHGPU_I64 = 0,
@@ -272,9 +272,11 @@ enum { CHGPU_VAL_COL = 0, CHGPU_VAL_MUL = 1, CHGPU_VAL_PLUS = 2, CHGPU_VAL_MINUS
 int chgpu_and(chgpu_ctx * ctx, const chgpu_col * a_u8, const chgpu_col * b_u8, chgpu_col ** out_u8);
 int chgpu_arith(chgpu_ctx * ctx, int value_op, const chgpu_col * a, const chgpu_col * b, chgpu_col ** out);
 /* Fused `SELECT sum(<value>), count() WHERE p_0 AND p_1 ...` in ONE pass over HBM (ExpressionActions::execute +
- * FilterTransform + AggregatingTransform without key).  cols[n_cols] are the distinct columns touched (<= 4, all of one
- * element width); predicate k is `cols[pred_col[k]] pred_op[k] constant` (constant = 8 raw bytes in pred_scalar_bits[k], typed
- * pred_scalar_type[k]; <= 8 predicates, and-ed); value = cols[val_a] (CHGPU_VAL_COL) or cols[val_a] <op> cols[val_b].
+ * FilterTransform + AggregatingTransform without key).  cols[n_cols] are the distinct columns touched (<= 4; Int64, UInt64,
+ * UInt32, Int32 or UInt8 in any mix of widths, each 16-byte aligned, all of one row count; Float64 / Float32 / 2-byte / Int8
+ * columns, a fifth column, a ninth predicate or a misaligned view -> CHGPU_ERR_NOT_IMPLEMENTED); predicate k is
+ * `cols[pred_col[k]] pred_op[k] constant` (constant = 8 raw bytes in pred_scalar_bits[k], typed pred_scalar_type[k];
+ * <= 8 predicates, and-ed); value = cols[val_a] (CHGPU_VAL_COL) or cols[val_a] <op> cols[val_b].
  * sum_out: 8 bytes, Int64 or UInt64 per the result type rules above (*result_type_out tells which). */
 int chgpu_expr_filter_sum(chgpu_ctx * ctx, uint32_t n_cols, const chgpu_col * const * cols, uint32_t n_preds,
                           const uint32_t * pred_col, const int * pred_op, const int * pred_scalar_type,
