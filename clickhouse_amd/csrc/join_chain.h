@@ -927,6 +927,40 @@ static int join_chain_impl(uint32_t n_steps, chgpu_join * const * joins, const c
     u64 kept = 0;
     const u64 n_units = (n + JC_UNIT_ROWS - 1) / JC_UNIT_ROWS;
     const u64 n_lds_units = la.n_steps ? n / JC_PART_ROWS * JC_UNITS_PER_PART : 0; // k_chain_lds sweeps whole parts; the rest starts alive in k_chain_tail
+    // test hook: at most this many workgroups per kernel, so that the grid-stride walks take many turns over a few million rows
+    const u64 grid_cap = (u64)chgpu_opt(ctx, "test_chain_grid", 0);
+    auto grid_of = [&](u64 want, u64 cap) { return (u32)std::min(want, grid_cap ? std::min(cap, grid_cap) : cap); };
+    const u32 lds_grid = n_lds_units ? grid_of(n_lds_units / JC_UNITS_PER_PART, (u64)ctx->num_cus) : 0;
+    const u32 tail_grid = grid_of((n_units + JCT_WAVES - 1) / JCT_WAVES, (u64)ctx->num_cus * 4);
+    const u32 idx_grid = grid_of((n_units + JCT_WAVES - 1) / JCT_WAVES, (u64)ctx->num_cus * 8);
+    if (chgpu_opt(ctx, "debug", 0))
+    {
+        // per step, in the caller's order: skipped | in the LDS sweep (slices) | in the tail (exact bitmap, hashed prefilter, none), and
+        // what answers: the key set, the key set with its row map, or the finished table
+        std::string plan;
+        for (u32 s = 0; s < n_steps; ++s)
+        {
+            const chgpu_join * j = joins[s];
+            const char * rep = j->finished ? "table" : (j->dm_ready && want_right_rows && want_right_rows[s]) ? "dm" : "ks";
+            char buf[64];
+            u32 at = 0;
+            while (at < la.n_steps && lds_steps[at] != s)
+                ++at;
+            if (at < la.n_steps)
+                snprintf(buf, sizeof(buf), "lds:%u %s", la.s[at].n_slices, rep);
+            else if (std::find(tail_steps.begin(), tail_steps.end(), s) != tail_steps.end())
+            {
+                const bool dense = j->finished ? (j->t.pf && j->max_key <= j->t.pf_mask) : j->ks_ready;
+                snprintf(buf, sizeof(buf), "tail %s %s", dense ? "dense" : (j->finished && j->t.pf) ? "hash" : "nopf", rep);
+            }
+            else
+                snprintf(buf, sizeof(buf), "skip %s", rep);
+            plan += (s ? " | " : "");
+            plan += buf;
+        }
+        fprintf(stderr, "chgpu: join chain rows=%llu parts=%llu lds_grid=%u tail_grid=%u idx_grid=%u steps=[%s]\n", (unsigned long long)n,
+                (unsigned long long)(n_lds_units / JC_UNITS_PER_PART), lds_grid, tail_grid, idx_grid, plan.c_str());
+    }
     auto al = [](size_t b) { return (b + 255) / 256 * 256; };
     const size_t alive_b = al(n_lds_units * 64 * 8), mask_b = al(n_units * 64 * 8), cnt_b = al(n_units * 4 + 4), off_b = al(n_units * 8 + 8), tmp_b = chgpu_scan_tmp_bytes(n_units);
     u64 * mask_words = nullptr, * unit_offsets = nullptr;
@@ -944,15 +978,11 @@ static int join_chain_impl(uint32_t n_steps, chgpu_join * const * joins, const c
         {
             const size_t lds_b = JC_SLICE_BYTES + 16;
             CHGPU_HIP(hipFuncSetAttribute((const void *)k_chain_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
-            const u64 n_parts = n_lds_units / JC_UNITS_PER_PART;
-            const u32 grid = (u32)(n_parts < (u64)ctx->num_cus ? n_parts : (u64)ctx->num_cus);
-            hipLaunchKernelGGL(k_chain_lds, dim3(grid), dim3(JC_THREADS), lds_b, ctx->stream, la, n, alive_words);
+            hipLaunchKernelGGL(k_chain_lds, dim3(lds_grid), dim3(JC_THREADS), lds_b, ctx->stream, la, n, alive_words);
             ctx->counters[6] += 1;
         }
         {
-            const u64 want = (n_units + JCT_WAVES - 1) / JCT_WAVES;
-            const u64 cap = (u64)ctx->num_cus * 4;
-            hipLaunchKernelGGL(k_chain_tail, dim3((u32)(want < cap ? want : cap)), dim3(JCT_THREADS), 0, ctx->stream, ta, n_lds_units ? (const u64 *)alive_words : (const u64 *)nullptr,
+            hipLaunchKernelGGL(k_chain_tail, dim3(tail_grid), dim3(JCT_THREADS), 0, ctx->stream, ta, n_lds_units ? (const u64 *)alive_words : (const u64 *)nullptr,
                                n_lds_units, n, mask_words, unit_counts);
             ctx->counters[6] += 1;
         }
@@ -993,9 +1023,7 @@ static int join_chain_impl(uint32_t n_steps, chgpu_join * const * joins, const c
         return fail(rc);
     if (n && ((kept && idx) || fcol))
     {
-        const u64 want = (n_units + JCT_WAVES - 1) / JCT_WAVES;
-        const u64 cap = (u64)ctx->num_cus * 8;
-        hipLaunchKernelGGL(k_chain_indexes, dim3((u32)(want < cap ? want : cap)), dim3(JCT_THREADS), 0, ctx->stream, (const u64 *)mask_words, (const u64 *)unit_offsets, n,
+        hipLaunchKernelGGL(k_chain_indexes, dim3(idx_grid), dim3(JCT_THREADS), 0, ctx->stream, (const u64 *)mask_words, (const u64 *)unit_offsets, n,
                            (kept && idx) ? (u64 *)idx->data : (u64 *)nullptr, fcol ? (u8 *)fcol->data : (u8 *)nullptr);
         ctx->counters[6] += 1;
         if (gather)

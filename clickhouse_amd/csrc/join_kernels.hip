@@ -20,6 +20,7 @@
 
 #include <cstdlib>
 
+#include <algorithm>
 #include <vector>
 
 static constexpr u32 JT = 256;
