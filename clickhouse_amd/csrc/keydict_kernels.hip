@@ -28,6 +28,7 @@
 
 #include <cstdlib>
 
+#include <string>
 #include <vector>
 
 static constexpr u32 KD_T = 256;
@@ -83,6 +84,7 @@ struct chgpu_keydict
     size_t ctrl_class = 0;
     u64 n_ids = 0;
     int weak_tags = 0; // test hook: 20-bit tags, so that the collision rounds run
+    u64 chunk_rows = 0; // test hook: rows of the first emplace chunk instead of KD_FIRST_CHUNK_ROWS (the longest chunk is 16 of them, as 64 Mi is of 4 Mi)
 };
 
 // packFixed (AggregationCommon.h:91-158): column j's element of row r copied to bytes [offset_j, offset_j + size_j) of the key.  The
@@ -559,6 +561,8 @@ extern "C" int chgpu_keydict_create(chgpu_ctx * ctx, uint32_t key_bytes, uint64_
     d->W = key_bytes / 8;
     d->t.W = d->W;
     d->weak_tags = chgpu_opt(ctx, "test_keydict_weak_tags", 0) ? 1 : 0; // test hook: 20-bit tags, so that tag collisions happen
+    const long long chunk_rows = chgpu_opt(ctx, "test_keydict_chunk_rows", 0); // test hook: several chunks without tens of millions of rows
+    d->chunk_rows = chunk_rows > 0 ? (u64)chunk_rows : 0;
     chgpu_ctx_retain(ctx);
     const int rc = kd_reserve(d, size_hint ? size_hint : 1024, 0);
     if (rc != CHGPU_OK)
@@ -624,15 +628,23 @@ extern "C" int chgpu_keydict_encode(chgpu_keydict * d, uint32_t n_cols, const ch
         return code;
     };
     int rc = CHGPU_OK;
+    // the `debug` option's plan line: what this call did, per chunk (host side only; the tests read it)
+    const bool debug = chgpu_opt(ctx, "debug", 0) != 0;
+    std::string dbg_grid, dbg_rounds, dbg_lookup;
+    u32 dbg_chunks = 0, dbg_resized = 0, dbg_grown = 0; // resized: before a chunk, for its grid; grown: rows deferred at the limit
+    const u64 ids_at_entry = d->n_ids;
     // emplace: a short first chunk, then longer ones -- a key met in an earlier chunk is compared in place by k_kd_claim, only rows that meet
     // a key claimed in their own chunk go through k_kd_verify, and most keys of a block show up in its first few million rows
-    u64 chunk = insert ? KD_FIRST_CHUNK_ROWS : KD_CHUNK_ROWS;
-    for (u64 c0 = 0, m = 0; c0 < n && rc == CHGPU_OK; c0 += m, chunk = chunk * 4 < KD_CHUNK_ROWS ? chunk * 4 : KD_CHUNK_ROWS)
+    const u64 first_chunk = d->chunk_rows ? d->chunk_rows : KD_FIRST_CHUNK_ROWS, max_chunk = d->chunk_rows ? d->chunk_rows * 16 : KD_CHUNK_ROWS;
+    u64 chunk = insert ? first_chunk : max_chunk;
+    for (u64 c0 = 0, m = 0; c0 < n && rc == CHGPU_OK; c0 += m, chunk = chunk * 4 < max_chunk ? chunk * 4 : max_chunk)
     {
         m = n - c0 < chunk + chunk / 2 ? n - c0 : chunk; // a short tail joins the last chunk
         const u32 grid = chgpu_grid_for(ctx, m, KD_T, 8);
+        const u64 cap_before = d->t.capacity;
         if (insert && (rc = kd_reserve(d, d->n_ids, (u64)grid * KD_T)) != CHGPU_OK)
             break;
+        dbg_resized += d->t.capacity != cap_before;
         auto al = [](size_t b) { return (b + 255) / 256 * 256; };
         void * scratch = nullptr;
         if ((rc = chgpu_scratch(ctx, 2 * al(m * 8), &scratch)) != CHGPU_OK)
@@ -640,7 +652,7 @@ extern "C" int chgpu_keydict_encode(chgpu_keydict * d, uint32_t n_cols, const ch
         u64 * cand = (u64 *)scratch;
         u64 * resume = (u64 *)((char *)cand + al(m * 8));
         u32 * rid = (u32 *)out->data + c0;
-        int restart = 0;
+        int restart = 0, rounds_run = 0;
         // cells at most 1/8 full and a dictionary that holds something: most rows find their key in their home cell -- the loop-free
         // look-up settles those, k_kd_claim then sees the chunk as a later round does (only the rows left over; none: it returns at once)
         const bool lookup_first = d->n_ids != 0 && d->n_ids * 8 <= d->t.capacity;
@@ -655,6 +667,7 @@ extern "C" int chgpu_keydict_encode(chgpu_keydict * d, uint32_t n_cols, const ch
         }
         for (int round = 0; round < 96; ++round)
         {
+            rounds_run = round + 1;
             d->t.ids_before = (u32)d->n_ids;
             hipLaunchKernelGGL(k_kd_claim, dim3(grid), dim3(KD_T), 0, ctx->stream, d->t, kc, row_begin + c0, m, insert ? 1 : 0, round + (lookup_first ? 1 : 0), restart, d->weak_tags,
                                lookup_first && round == 0 ? 1 : 0, rid, cand, resume);
@@ -684,13 +697,26 @@ extern "C" int chgpu_keydict_encode(chgpu_keydict * d, uint32_t n_cols, const ch
             {
                 rc = kd_reserve(d, 4 * d->t.limit, (u64)grid * KD_T);
                 restart = 1;
+                dbg_grown += 1;
             }
             if (rc == CHGPU_OK && round == 95)
                 rc = chgpu_set_error(CHGPU_ERR_LOGICAL, "wide-key dictionary did not settle in 96 rounds");
             if (rc != CHGPU_OK)
                 break;
         }
+        if (debug)
+        {
+            const char * sep = dbg_chunks ? "," : "";
+            dbg_grid += sep + std::to_string(grid);
+            dbg_rounds += sep + std::to_string(rounds_run);
+            dbg_lookup += sep + std::to_string(lookup_first ? 1 : 0);
+        }
+        dbg_chunks += 1;
     }
+    if (debug)
+        fprintf(stderr, "chgpu: keydict plan=%s W=%u n=%llu cap=%llu limit=%llu chunks=%u grid=%s rounds=%s lookup=%s resized=%u grown=%u ids=%llu->%llu rc=%d\n", insert ? "emplace" : "find", d->W,
+                (unsigned long long)n, (unsigned long long)d->t.capacity, (unsigned long long)d->t.limit, dbg_chunks, dbg_chunks ? dbg_grid.c_str() : "-",
+                dbg_chunks ? dbg_rounds.c_str() : "-", dbg_chunks ? dbg_lookup.c_str() : "-", dbg_resized, dbg_grown, (unsigned long long)ids_at_entry, (unsigned long long)d->n_ids, rc);
     if (rc == CHGPU_OK && hipGetLastError() != hipSuccess)
         rc = chgpu_set_error(CHGPU_ERR_DEVICE, "keydict launch failed");
     if (rc != CHGPU_OK)

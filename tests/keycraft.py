@@ -247,3 +247,94 @@ def gb_keys32_top(rng, n, top_bits, top, mult=GBP_MULT):
     and one LDS cell too for P * S <= 2^top_bits"""
     low = _distinct_free(rng, n, 32 - top_bits, exclude=(0,) if top == 0 else ())
     return gbp_inv32((np.uint64(top) << np.uint64(32 - top_bits)) | low, mult).astype(np.uint32)
+
+
+# ---- the wide-key dictionary (keys128 / keys256) ---------------------------------------------------------------------------------
+# kd_tag: keydict_kernels.hip:127-128 (word 0: xor, multiply, xorshift-31), :131-132 (every later word: xor, multiply, xorshift-29),
+# :135 (the 20-bit test hook), :136 (low bit forced to 1); the home cell: keydict_kernels.hip:165, :227 and :419
+KD_TAG_XOR0 = 0x9E3779B97F4A7C15
+KD_TAG_MUL0 = 0xBF58476D1CE4E5B9
+KD_TAG_SHIFT0 = 31
+KD_TAG_MUL = 0x94D049BB133111EB
+KD_TAG_SHIFT = 29
+KD_WEAK_MASK = 0xFFFFF
+KD_HOME_MULT = 0x9E3779B97F4A7C15
+KD_HOME_SHIFT = 20
+KD_NO_ID = 0xFFFFFFFF
+
+
+def _xs(x, s):
+    x = _u64(x)
+    return x ^ (x >> np.uint64(s))
+
+
+def _xs_inv(y, s):
+    """undo x ^= x >> s: x = y ^ (y >> s) ^ (y >> 2s) ^ ..."""
+    y = _u64(y)
+    x = y
+    for _ in range(64 // s + 1):
+        x = y ^ (x >> np.uint64(s))
+    return x
+
+
+def keydict_running_hash(words):
+    """kd_tag's running value after the words given: uint64[n, q], q >= 1 leading words of the packed key"""
+    words = _u64(words)
+    h = _xs(_mul(words[..., 0] ^ np.uint64(KD_TAG_XOR0), KD_TAG_MUL0), KD_TAG_SHIFT0)
+    for q in range(1, words.shape[-1]):
+        h = _xs(_mul(h ^ words[..., q], KD_TAG_MUL), KD_TAG_SHIFT)
+    return h
+
+
+def keydict_tag(words, weak=False):
+    """kd_tag of packed keys uint64[n, W] (W = 2: keys128, W = 4: keys256); weak: the 20-bit form of the test hook"""
+    h = keydict_running_hash(words)
+    if weak:
+        h = h & np.uint64(KD_WEAK_MASK)
+    return h | np.uint64(1)
+
+
+def keydict_home(tags, capacity):
+    """the home cell of a tag in a table of `capacity` cells (a power of two)"""
+    return (_mul(_u64(tags) >> np.uint64(1), KD_HOME_MULT) >> np.uint64(KD_HOME_SHIFT)) & np.uint64(capacity - 1)
+
+
+def keydict_last_word(prefix_words, tag, zero_words_after=0):
+    """the 64-bit word which, put behind the leading words uint64[n, q], gives a key whose full tag is exactly `tag` (odd); with
+    zero_words_after = z the key goes on with z zero words (a keys256 key of three UInt64 columns: q = 2, z = 1).  Every step of kd_tag
+    is a bijection of the running value, so this undoes them from the end: the xorshift-29, the multiply, the xor."""
+    tag = _u64(tag)
+    assert np.all(tag & np.uint64(1) == 1)
+    inv = inv_odd(KD_TAG_MUL)
+    h = tag
+    for _ in range(zero_words_after):
+        h = _mul(_xs_inv(h, KD_TAG_SHIFT), inv)        # the value before a zero word was mixed in
+    return _mul(_xs_inv(h, KD_TAG_SHIFT), inv) ^ keydict_running_hash(prefix_words)
+
+
+def keydict_same_tag_keys(rng, n, w, tag, cols=None):
+    """n distinct packed keys uint64[n, w] with one full 64-bit tag; cols < w: only the first `cols` words are free, the rest zero"""
+    cols = w if cols is None else cols
+    assert 2 <= cols <= w
+    prefix = np.stack([_distinct_free(rng, n, 64) for _ in range(cols - 1)], axis=1)     # distinct prefixes: distinct keys
+    last = keydict_last_word(prefix, np.full(n, tag, dtype=np.uint64), w - cols)
+    keys = np.concatenate([prefix, last[:, None], np.zeros((n, w - cols), dtype=np.uint64)], axis=1)
+    assert np.all(keydict_tag(keys) == np.uint64(tag))
+    return keys
+
+
+def keydict_tag_with_home(rng, cell_bits, lg, n=1):
+    """n distinct tags whose home cell has `cell_bits` in its low `lg` bits: the cell `cell_bits & (capacity - 1)` of every capacity up to
+    2^lg at once (all ones: the last cell of each).  tag >> 1 is what is multiplied, so it has to stay below 2^63: the free bits are
+    drawn again until it does."""
+    assert 0 <= cell_bits < (1 << lg) and KD_HOME_SHIFT + lg <= 64
+    inv = inv_odd(KD_HOME_MULT)
+    got = np.empty(0, dtype=np.uint64)
+    while got.shape[0] < n:
+        free = rng.integers(0, 2**64 - 1, size=4 * n + 16, dtype=np.uint64, endpoint=True)
+        keep = ~(np.uint64(((1 << lg) - 1) << KD_HOME_SHIFT))
+        y = (free & keep) | (np.uint64(cell_bits) << np.uint64(KD_HOME_SHIFT))
+        t = _mul(y, inv)
+        t = t[t < np.uint64(1 << 63)]
+        got = np.unique(np.concatenate([got, (t << np.uint64(1)) | np.uint64(1)]))
+    return rng.permutation(got)[:n]

@@ -445,31 +445,6 @@ def test_groupby_tile_sorted_plan_edge_cases(ch, ctx, key_dtype, case):
         assert np.array_equal(gs[order].astype(np.uint64), want)
 
 
-@pytest.mark.parametrize("key_dtypes", [(np.uint64, np.uint64), (np.uint64, np.uint32, np.uint16), (np.uint64, np.uint64, np.uint64, np.uint32, np.uint8)])
-def test_keys_fixed_group_by_matches_oracle(ch, ctx, oracle_mod, key_dtypes):
-    O = oracle_mod
-    rng = np.random.Generator(np.random.PCG64(11))
-    aggs = [(ch.AGG_SUM, np.int64), (ch.AGG_COUNT, None)]
-    G = ch.KeysFixedAggregator(key_dtypes, aggs, ctx=ctx)
-    R = O.KeysFixedAggregator(key_dtypes, aggs)
-    for n in (70_001, 1, 300_000):                                    # several blocks: ids persist, the table grows
-        cols = [rng.integers(0, 40, size=n).astype(d) for d in key_dtypes]
-        cols[0][: n // 50] = 0
-        for c in cols[1:]:
-            c[: n // 50] = 0                                          # the all-zero key
-        v = rng.integers(-2**62, 2**62, size=n, dtype=np.int64)
-        G.execute_on_block(cols, [v, None])
-        R.execute_on_block(cols, [v, None])
-    gk, (gs, gc) = G.convert_to_block()
-    rk, (rs, rc) = R.convert_to_block()
-    assert len(G) == len(rk[0])
-    go = np.lexsort([k.astype(np.uint64) for k in gk])
-    ro = np.lexsort([k.astype(np.uint64) for k in rk])
-    for a, b in zip(gk, rk):
-        assert a.dtype == b.dtype and np.array_equal(a[go], b[ro])
-    assert np.array_equal(gs[go], rs[ro]) and np.array_equal(gc[go], rc[ro])
-
-
 def test_keys_fixed_00120_two_key_group_by_on_gpu(ch, ctx, oracle_mod, golden):
     """the reference's 00120_join_and_group_by as what it is: GROUP BY (UInt64, UInt32) -- 12 key bytes, the keys128 method"""
     L = oracle_mod.lib()
@@ -481,83 +456,6 @@ def test_keys_fixed_00120_two_key_group_by_on_gpu(ch, ctx, oracle_mod, golden):
     (k1, k2), (s,) = A.convert_to_block()
     rows = sorted([[str(int(x)), str(int(y)), str(int(z))] for x, y, z in zip(k1, k2, s)], key=lambda r: (int(r[0]), int(r[1])))
     assert rows == golden["rows"]["00120_join_and_group_by"]["rows"]
-
-
-def test_keys_fixed_join_and_selector(ch, ctx, oracle_mod):
-    O = oracle_mod
-    rng = np.random.Generator(np.random.PCG64(12))
-    bk = [rng.integers(0, 300, size=20_000, dtype=np.uint64), rng.integers(0, 5, size=20_000).astype(np.uint32), rng.integers(0, 3, size=20_000).astype(np.uint16)]
-    pk = [rng.integers(0, 400, size=50_000, dtype=np.uint64), rng.integers(0, 6, size=50_000).astype(np.uint32), rng.integers(0, 3, size=50_000).astype(np.uint16)]
-    bv = rng.integers(-2**40, 2**40, size=20_000, dtype=np.int64)
-    j = ch.KeysFixedHashJoin([np.uint64, np.uint32, np.uint16], ch.JOIN_INNER, ch.STRICT_ALL, ctx=ctx)
-    j.add_block(bk)
-    c, s = j.probe_count_sum(pk, ctx.upload(bv))
-    m = O.WideKeyMap(16)
-    bid = m.batch(O.pack_fixed(bk, 16), True).astype(np.int64)
-    pid = m.batch(O.pack_fixed(pk, 16), False)
-    mult = np.bincount(bid, minlength=len(m))
-    sums = np.zeros(len(m), dtype=np.uint64)
-    np.add.at(sums, bid, bv.astype(np.uint64))
-    hit = pid != np.uint64(2**64 - 1)
-    assert c == int(mult[pid[hit].astype(np.int64)].sum()) and s % 2**64 == int(sums[pid[hit].astype(np.int64)].sum(dtype=np.uint64))
-    # the shard of a wide key by the reference's own hash: UInt128HashCRC32 -> two-level bucket & (shards - 1)
-    ids = j.dict.encode(bk, insert=False)
-    sel = j.dict.selector(ids, 8).numpy()
-    packed = O.pack_fixed(bk, 16)
-    want = np.array([((O.hash_keys_fixed(r) >> 24) & 0xFF) & 7 for r in packed[:2000]], dtype=np.uint32)
-    assert np.array_equal(sel[:2000], want)
-
-
-def test_keys_fixed_tag_collisions_are_resolved_exactly(ch, oracle_mod):
-    """with 20-bit tags (test hook) dozens of different keys share a tag: the verification rounds must still give exact ids"""
-    import os
-    import subprocess
-    import sys
-    code = '''
-import numpy as np, clickhouse_amd as ch
-ctx = ch.Context(0)
-rng = np.random.Generator(np.random.PCG64(5))
-a = rng.integers(0, 30000, size=400_000, dtype=np.uint64); b = rng.integers(0, 3, size=400_000, dtype=np.uint64)
-d = ch.KeyDict([np.uint64, np.uint64], ctx)
-ids = d.encode([a, b]).numpy()
-pairs = np.stack([a, b], axis=1)
-uniq = np.unique(pairs, axis=0)
-assert len(d) == uniq.shape[0], (len(d), uniq.shape[0])
-first = {}
-for i, (x, y) in enumerate(pairs.tolist()):
-    assert first.setdefault(int(ids[i]), (x, y)) == (x, y)
-assert len(first) == uniq.shape[0]
-k0, k1 = [c.numpy() for c in d.key_columns(ctx.upload(ids))]
-assert np.array_equal(k0, a) and np.array_equal(k1, b)
-print("ok")
-'''
-    env = dict(os.environ, CHGPU_TEST_KEYDICT_WEAK_TAGS="1", PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stdout + r.stderr
-
-
-def test_keys_fixed_dictionary_grows_when_rows_defer_at_its_limit(ch, ctx):
-    """the table is sized for the keys it holds, not for the rows of a chunk: 3 M distinct keys into a dictionary made for 1024 run past
-    limit = capacity / 2 twice (rows defer, the table grows fourfold, the deferred rows run again); ids stay dense, stable and exact"""
-    rng = np.random.Generator(np.random.PCG64(21))
-    n = 3_000_000
-    a = rng.permutation(n).astype(np.uint64) * np.uint64(2654435761)
-    b = (np.arange(n, dtype=np.uint64) * np.uint64(40503)) ^ np.uint64(0xDEADBEEF)
-    d = ch.KeyDict([np.uint64, np.uint64], ctx)
-    ids = d.encode([a, b]).numpy()
-    assert len(d) == n and np.array_equal(np.sort(ids), np.arange(n, dtype=np.uint32))          # dense: every id exactly once
-    k0, k1 = [c.numpy() for c in d.key_columns(ctx.upload(ids))]
-    assert np.array_equal(k0, a) and np.array_equal(k1, b)
-    # a second block: old keys (compared in place, no second kernel), new keys and repeats of the new keys inside the block
-    a2 = np.concatenate([a[::7], a[:1000] + np.uint64(1), a[:1000] + np.uint64(1)])
-    b2 = np.concatenate([b[::7], b[:1000], b[:1000]])
-    ids2 = d.encode([a2, b2]).numpy()
-    m = a[::7].shape[0]
-    assert np.array_equal(ids2[:m], ids[::7]) and len(d) == n + 1000
-    assert np.array_equal(ids2[m:m + 1000], ids2[m + 1000:]) and np.array_equal(np.sort(ids2[m:m + 1000]), np.arange(n, n + 1000, dtype=np.uint32))
-    # findKey: present keys keep their ids, absent ones get NO_ID
-    probe = d.encode([np.concatenate([a[:500], a[:500] + np.uint64(3)]), np.concatenate([b[:500], b[:500]])], insert=False).numpy()
-    assert np.array_equal(probe[:500], ids[:500]) and (probe[500:] == 0xFFFFFFFF).all() and len(d) == n + 1000
 
 
 # ---- partial states on the wire ------------------------------------------------------------------------------------------------------

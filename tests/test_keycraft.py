@@ -153,3 +153,94 @@ def test_gb_keys32_on_one_partition_and_one_cell():
     k = kc.gb_keys32_top(_rng(), 300_000, 10, 77)
     _distinct_nonzero(k)
     assert np.unique(kc.gbp_part32(k, 1024)).shape[0] == 1
+
+
+# ---- the wide-key dictionary's tag and home cell -----------------------------------------------------------------------------------
+KEYDICT_SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "clickhouse_amd", "csrc", "keydict_kernels.hip")
+
+
+def _kd_tag_py(words, weak=False):
+    """kd_tag in plain Python ints"""
+    h = ((words[0] ^ 0x9E3779B97F4A7C15) * 0xBF58476D1CE4E5B9) % 2**64
+    h ^= h >> 31
+    for w in words[1:]:
+        h = ((h ^ w) * 0x94D049BB133111EB) % 2**64
+        h ^= h >> 29
+    if weak:
+        h &= 0xFFFFF
+    return h | 1
+
+
+def _kd_home_py(tag, capacity):
+    return ((((tag >> 1) * 0x9E3779B97F4A7C15) % 2**64) >> 20) & (capacity - 1)
+
+
+def test_keydict_constants_match_the_kernel_source():
+    """a change of the mix or of the home cell in keydict_kernels.hip must fail here, not silently un-craft the GPU cases"""
+    import re
+    src = open(KEYDICT_SRC).read()
+    body = re.search(r"u64 kd_tag\(const u64 \* w, u32 W, int weak\)\s*\{(.*?)\n\}", src, re.S).group(1)
+    code = [ln.split("//")[0].strip() for ln in body.splitlines()]
+    code = [ln for ln in code if ln and ln not in ("{", "}")]
+    assert code == [
+        f"u64 h = (w[0] ^ 0x{kc.KD_TAG_XOR0:016X}ull) * 0x{kc.KD_TAG_MUL0:016X}ull;",
+        f"h ^= h >> {kc.KD_TAG_SHIFT0};",
+        "for (u32 q = 1; q < W; ++q)",
+        f"h = (h ^ w[q]) * 0x{kc.KD_TAG_MUL:016X}ull;",
+        f"h ^= h >> {kc.KD_TAG_SHIFT};",
+        "if (weak)",
+        f"h &= 0x{kc.KD_WEAK_MASK:X};",
+        "return h | 1ull;",
+    ], code
+    home = f">> 1) * 0x{kc.KD_HOME_MULT:016X}ull >> {kc.KD_HOME_SHIFT}) & mask"
+    assert src.count(home) == 3                       # k_kd_lookup, k_kd_claim, k_kd_rehash: one placement everywhere
+    assert src.count("0x9E3779B97F4A7C15ull >>") == 3
+    assert f"KD_NO_ID = 0x{kc.KD_NO_ID:X}u;" in src
+    lines = src.splitlines()                          # the lines keycraft.py names
+    assert "0xBF58476D1CE4E5B9ull" in lines[126] and "0x94D049BB133111EBull" in lines[130] and "0xFFFFF" in lines[134] and "| 1ull" in lines[135]
+    assert all(home in lines[k] for k in (164, 226, 418))
+
+
+@pytest.mark.parametrize("w", [2, 4])
+def test_keydict_tag_and_home_against_python_ints(w):
+    rng = _rng()
+    words = np.concatenate([np.zeros((1, w), dtype=np.uint64), np.full((1, w), 2**64 - 1, dtype=np.uint64),
+                            rng.integers(0, 2**64 - 1, size=(2000, w), dtype=np.uint64, endpoint=True)])
+    for weak in (False, True):
+        tags = kc.keydict_tag(words, weak)
+        assert [int(t) for t in tags] == [_kd_tag_py(r, weak) for r in words.tolist()]
+        for cap in (2048, 1 << 17, 1 << 24):
+            assert [int(h) for h in kc.keydict_home(tags, cap)] == [_kd_home_py(int(t), cap) for t in tags]
+
+
+@pytest.mark.parametrize("w,cols", [(2, 2), (4, 4), (4, 3)])
+def test_keydict_last_word_gives_the_chosen_tag(w, cols):
+    """the inverse against the forward function in Python ints, 2000 tags: the crafted key has exactly the tag asked for"""
+    rng = _rng()
+    tags = rng.integers(0, 2**64 - 1, size=2000, dtype=np.uint64, endpoint=True) | np.uint64(1)
+    prefix = rng.integers(0, 2**64 - 1, size=(2000, cols - 1), dtype=np.uint64, endpoint=True)
+    last = kc.keydict_last_word(prefix, tags, w - cols)
+    for p, l, t in zip(prefix.tolist(), last.tolist(), tags.tolist()):
+        assert _kd_tag_py(p + [l] + [0] * (w - cols)) == t
+    fam = kc.keydict_same_tag_keys(rng, 40, w, int(tags[0]), cols)
+    assert fam.shape == (40, w) and np.unique(fam, axis=0).shape[0] == 40 and np.all(fam[:, cols:] == 0)
+    assert {_kd_tag_py(r) for r in fam.tolist()} == {int(tags[0])}
+
+
+def test_keydict_tag_with_home_is_the_same_cell_of_every_capacity():
+    rng = _rng()
+    lg = 24
+    for bits in ((1 << lg) - 1, (1 << lg) - 2, (1 << lg) - 3, 0, 0x5A5A5):
+        tags = kc.keydict_tag_with_home(rng, bits, lg, 2000)
+        assert np.unique(tags).shape[0] == 2000 and np.all(tags & np.uint64(1) == 1)
+        for t in tags[:400].tolist():
+            assert (t >> 1) < 2**63
+            for c in range(11, lg + 1):
+                assert _kd_home_py(t, 1 << c) == bits & ((1 << c) - 1)
+        for c in (11, 17, lg):
+            assert np.all(kc.keydict_home(tags, 1 << c) == np.uint64(bits & ((1 << c) - 1)))
+    # both together: many keys, one tag, on the last cell of every table
+    tag = int(kc.keydict_tag_with_home(rng, (1 << lg) - 1, lg)[0])
+    for w in (2, 4):
+        fam = kc.keydict_same_tag_keys(rng, 17, w, tag)
+        assert np.all(kc.keydict_home(kc.keydict_tag(fam), 2048) == 2047)
