@@ -377,54 +377,67 @@ __device__ __host__ __forceinline__ u64 agg_order_key_inverse(u64 key, int type)
     }
 }
 
-// add row i's contribution of every aggregate to the cell `slot` (IAggregateFunction::add per function)
-__device__ __forceinline__ void add_row_global(const AggTable & t, const AggDesc & d, u64 slot, u64 i)
+// Where a group's state lives.  A sink has three members: at(w) = the address of TABLE word w, add_word(p, bits, op) (op as in
+// global_add_word) and add_fx(lo, hi, x).  GlobalSink is a cell of the HBM table; LdsRowSink (below, with the overflow row) is a
+// workgroup's LDS copy of the overflow row.
+struct GlobalSink
 {
-    const u64 stride = t.capacity + 1;
+    u64 * words;
+    u64 stride, slot;
+    __device__ __forceinline__ GlobalSink(const AggTable & t, u64 slot_) : words(t.words), stride(t.capacity + 1), slot(slot_) {}
+    __device__ __forceinline__ u64 * at(u32 w) const { return words + (u64)w * stride + slot; }
+    __device__ __forceinline__ void add_word(u64 * p, u64 bits, int op) const { global_add_word(p, bits, op); }
+    __device__ __forceinline__ void add_fx(u64 * lo, u64 * hi, Fx128 x) const { global_add_fx(lo, hi, x); }
+};
+
+// add row i's contribution of every aggregate to the group's state in `sink` (IAggregateFunction::add per function)
+template <typename Sink>
+__device__ __forceinline__ void add_row(const Sink & sink, const AggDesc & d, u64 i)
+{
     for (u32 j = 0; j < d.n_aggs; ++j)
     {
         const AggArg & a = d.a[j];
-        u64 * w = t.words + (u64)d.word_map[a.word] * stride + slot;
+        u64 * w = sink.at(d.word_map[a.word]);
         if (a.kind == CHGPU_AGG_COUNT)
-            global_add_word(w, 1, false);
+            sink.add_word(w, 1, 0);
         else if (a.kind == CHGPU_AGG_MIN || a.kind == CHGPU_AGG_MAX)
         {
             const u64 k = agg_order_key(load_arg_bits(a.ptr, a.arg_type, i), a.arg_type);
-            global_add_word(w, a.kind == CHGPU_AGG_MAX ? k : ~k, 2);
+            sink.add_word(w, a.kind == CHGPU_AGG_MAX ? k : ~k, 2);
         }
         else if (a.kind == CHGPU_AGG_ANY)
-            global_add_word(w, ~(d.row_seq + i), 2); // the claim of the earliest row; its value follows in k_agg_any_resolve
+            sink.add_word(w, ~(d.row_seq + i), 2); // the claim of the earliest row; its value follows in k_agg_any_resolve
         else
         {
             if ((d.word_fx >> a.word) & 1)
-                global_add_fx(w, t.words + (u64)d.word_map[d.fx_hi[a.word]] * stride + slot, fx_from_double(load_arg_bits(a.ptr, a.arg_type, i), d.fx_base));
+                sink.add_fx(w, sink.at(d.word_map[d.fx_hi[a.word]]), fx_from_double(load_arg_bits(a.ptr, a.arg_type, i), d.fx_base));
             else
-                global_add_word(w, load_arg_bits(a.ptr, a.arg_type, i), a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
+                sink.add_word(w, load_arg_bits(a.ptr, a.arg_type, i), a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
             if (a.kind == CHGPU_AGG_AVG)
-                global_add_word(w + stride, 1, false); // denominator
+                sink.add_word(sink.at(d.word_map[a.word] + 1), 1, 0); // denominator
         }
     }
 }
 
 // The same update from values already in registers: `bits0/bits1` are the 8-byte argument words selected by AggArg::pre,
 // `cnt` the number of rows they stand for.
-__device__ __forceinline__ void add_vals_global(const AggTable & t, const AggDesc & d, u64 slot, u64 bits0, u64 bits1, u64 cnt)
+template <typename Sink>
+__device__ __forceinline__ void add_vals(const Sink & sink, const AggDesc & d, u64 bits0, u64 bits1, u64 cnt)
 {
-    const u64 stride = t.capacity + 1;
     for (u32 j = 0; j < d.n_aggs; ++j)
     {
         const AggArg & a = d.a[j];
-        u64 * w = t.words + (u64)d.word_map[a.word] * stride + slot;
+        u64 * w = sink.at(d.word_map[a.word]);
         if (a.kind == CHGPU_AGG_COUNT)
-            global_add_word(w, cnt, false);
+            sink.add_word(w, cnt, 0);
         else
         {
             if ((d.word_fx >> a.word) & 1)
-                global_add_fx(w, t.words + (u64)d.word_map[d.fx_hi[a.word]] * stride + slot, fx_from_double(a.pre == 0 ? bits0 : bits1, d.fx_base));
+                sink.add_fx(w, sink.at(d.word_map[d.fx_hi[a.word]]), fx_from_double(a.pre == 0 ? bits0 : bits1, d.fx_base));
             else
-                global_add_word(w, a.pre == 0 ? bits0 : bits1, a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
+                sink.add_word(w, a.pre == 0 ? bits0 : bits1, a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
             if (a.kind == CHGPU_AGG_AVG)
-                global_add_word(w + stride, cnt, false); // denominator
+                sink.add_word(sink.at(d.word_map[a.word] + 1), cnt, 0); // denominator
         }
     }
 }
@@ -432,7 +445,7 @@ __device__ __forceinline__ void add_vals_global(const AggTable & t, const AggDes
 // ---- find-only mode and the overflow row (Aggregator::executeImplBatch with no_more_keys, Aggregator.cpp:1181-1194) ----
 // In find-only mode only the step where a group's state leaves the workgroup changes -- the flush of an LDS cell, a row's global update:
 // it calls table_find instead of table_emplace, and a miss (AGG_SLOT_MISS) goes to the overflow row.  A workgroup combines its misses in
-// an LDS copy of the overflow row (ovf_*_lds: LDS atomics) and issues at most one global update per state word at its end (ovf_flush):
+// an LDS copy of the overflow row (LdsRowSink: LDS atomics) and issues at most one global update per state word at its end (ovf_flush):
 // per-row atomics on one global address would serialise.
 static constexpr u64 AGG_SLOT_MISS = ~1ull;
 __device__ __forceinline__ u64 table_find(const AggTable & t, u64 key)
@@ -475,63 +488,43 @@ __device__ __forceinline__ void ovf_lds_word(u64 * s, u64 bits, int op)
     else if (bits)
         atomicAdd((unsigned long long *)s, (unsigned long long)bits);
 }
-// row i's contribution to the overflow row (add_row_global with the LDS copy s[] indexed by table word)
-__device__ __forceinline__ void ovf_row_lds(u64 * s, const AggDesc & d, u64 i)
+// the LDS copy s[] of the overflow row as a sink, indexed by table word.  One deliberate difference from GlobalSink: an integer add
+// of zero is skipped here (ovf_lds_word) and issued there.
+struct LdsRowSink
 {
-    for (u32 j = 0; j < d.n_aggs; ++j)
-    {
-        const AggArg & a = d.a[j];
-        u64 * w = s + d.word_map[a.word];
-        if (a.kind == CHGPU_AGG_COUNT)
-            ovf_lds_word(w, 1, 0);
-        else if (a.kind == CHGPU_AGG_MIN || a.kind == CHGPU_AGG_MAX)
-        {
-            const u64 k = agg_order_key(load_arg_bits(a.ptr, a.arg_type, i), a.arg_type);
-            ovf_lds_word(w, a.kind == CHGPU_AGG_MAX ? k : ~k, 2);
-        }
-        else if (a.kind == CHGPU_AGG_ANY)
-            ovf_lds_word(w, ~(d.row_seq + i), 2);
-        else
-        {
-            if ((d.word_fx >> a.word) & 1)
-                lds_add_fx(w, s + d.word_map[d.fx_hi[a.word]], fx_from_double(load_arg_bits(a.ptr, a.arg_type, i), d.fx_base));
-            else
-                ovf_lds_word(w, load_arg_bits(a.ptr, a.arg_type, i), a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
-            if (a.kind == CHGPU_AGG_AVG)
-                ovf_lds_word(w + 1, 1, 0);
-        }
-    }
-}
-// add_vals_global's update, to the overflow row
-__device__ __forceinline__ void ovf_vals_lds(u64 * s, const AggDesc & d, u64 bits0, u64 bits1, u64 cnt)
-{
-    for (u32 j = 0; j < d.n_aggs; ++j)
-    {
-        const AggArg & a = d.a[j];
-        u64 * w = s + d.word_map[a.word];
-        if (a.kind == CHGPU_AGG_COUNT)
-            ovf_lds_word(w, cnt, 0);
-        else
-        {
-            if ((d.word_fx >> a.word) & 1)
-                lds_add_fx(w, s + d.word_map[d.fx_hi[a.word]], fx_from_double(a.pre == 0 ? bits0 : bits1, d.fx_base));
-            else
-                ovf_lds_word(w, a.pre == 0 ? bits0 : bits1, a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
-            if (a.kind == CHGPU_AGG_AVG)
-                ovf_lds_word(w + 1, cnt, 0);
-        }
-    }
-}
-// local state word w of a flushed LDS cell (bits; hb = its fixed-point high half), to the overflow row
-__device__ __forceinline__ void ovf_cell_word_lds(u64 * s, const AggDesc & d, u32 w, u64 bits, u64 hb)
+    u64 * s;
+    __device__ __forceinline__ u64 * at(u32 w) const { return s + w; }
+    __device__ __forceinline__ void add_word(u64 * p, u64 bits, int op) const { ovf_lds_word(p, bits, op); }
+    __device__ __forceinline__ void add_fx(u64 * lo, u64 * hi, Fx128 x) const { lds_add_fx(lo, hi, x); }
+};
+// local state word w of a flushed LDS cell (bits; hb = its fixed-point high half), to the group's state in `sink`
+template <typename Sink>
+__device__ __forceinline__ void add_cell_word(const Sink & sink, const AggDesc & d, u32 w, u64 bits, u64 hb)
 {
     if ((d.word_fx >> w) & 1)
     {
         if (bits | hb)
-            lds_add_fx(s + d.word_map[w], s + d.word_map[d.fx_hi[w]], Fx128{bits, hb});
+            sink.add_fx(sink.at(d.word_map[w]), sink.at(d.word_map[d.fx_hi[w]]), Fx128{bits, hb});
+    }
+    else if (bits != 0)
+        sink.add_word(sink.at(d.word_map[w]), bits, (d.word_is_f64 >> w) & 1);
+}
+// Place a row or leave it pending: `add(sink)` adds the row's contribution to the cell of `key`, or, in find-only mode, to the overflow
+// row `s_ovf` (when there is one) if the table lacks the key.  Returns true when the row must wait for a bigger table.
+template <typename Add>
+__device__ __forceinline__ bool place_and_add(const AggTable & t, u64 * s_ovf, u64 key, bool soft_limit, Add add)
+{
+    const u64 slot = table_place(t, key, soft_limit);
+    if (slot == ~0ull)
+        return true;
+    if (slot == AGG_SLOT_MISS)
+    {
+        if (t.ovf)
+            add(LdsRowSink{s_ovf});
     }
     else
-        ovf_lds_word(s + d.word_map[w], bits, (d.word_is_f64 >> w) & 1);
+        add(GlobalSink(t, slot));
+    return false;
 }
 // The workgroup's combined misses to the overflow row: one global update per state word (call after a barrier, every thread).  Local
 // words 0 .. n_words-1 map to table words through `map`; masks as in AggDesc (word_is_f64: bit w Float64 add, bit 16 + w unsigned max).
@@ -567,6 +560,89 @@ __device__ __forceinline__ void ovf_flush_desc(const AggTable & t, const u64 * s
     ovf_flush(t, s, d.n_words, d.word_is_f64, d.word_fx, d.word_fx_hi, d.fx_hi, d.word_map, 0);
 }
 
+// ---- the workgroup's LDS table of the LDS-staged kernels ----
+// Layout: keys KT[S+1] (padded to 8 B) | every 8-byte word u64[S+1] in word order | every 4-byte word u32[S+1]; cell S is the zero
+// key's.  Bit w of cnt32: state word w is a row COUNT kept as 32 bits (see k_agg_part_lds).
+struct PartLds
+{
+    u32 S1, cnt32, n8, keys_bytes;
+    __host__ __device__ PartLds(u32 key_bytes, u32 S, u32 n_words, u32 cnt32_)
+        : S1(S + 1), cnt32(cnt32_), n8(n_words - (u32)__builtin_popcount(cnt32_)), keys_bytes((key_bytes * (S + 1) + 7) & ~7u)
+    {
+    }
+    // the table's size; a kernel zeroes whole 8-byte words up to bytes() / 8 + 1 of them, so the host allocates bytes() + 16
+    __host__ __device__ u32 bytes() const { return keys_bytes + 8 * S1 * n8 + 4 * S1 * (u32)__builtin_popcount(cnt32); }
+    __device__ __forceinline__ u32 off(u32 w) const
+    {
+        const u32 low = (1u << w) - 1;
+        if ((cnt32 >> w) & 1)
+            return keys_bytes + 8 * S1 * n8 + 4 * S1 * (u32)__popc(cnt32 & low);
+        return keys_bytes + 8 * S1 * (u32)__popc(~cnt32 & low);
+    }
+};
+
+// Find-or-claim the LDS cell of `key`: linear probing from cell `start`, at most `probes` cells.  The zero key has cell S (and sets
+// lzero).  Returns the cell, or ~0 when the table is full around `start`.
+template <typename KT>
+__device__ __forceinline__ u32 lds_find_or_claim(KT * lkeys, KT key, u32 start, int probes, u32 S, u32 & lzero)
+{
+    typedef typename std::conditional<sizeof(KT) == 4, unsigned int, unsigned long long>::type CasT;
+    if (key == 0)
+    {
+        lzero = 1;
+        return S;
+    }
+    u32 s = start;
+#pragma unroll 1
+    for (int probe = 0; probe < probes; ++probe)
+    {
+        KT k = lkeys[s];
+        if (k == 0)
+            k = (KT)atomicCAS((CasT *)&lkeys[s], (CasT)0, (CasT)key), k = (k == 0) ? key : k;
+        if (k == key)
+            return s;
+        s = (s + 1) & (S - 1);
+    }
+    return ~0u;
+}
+
+// Flush the workgroup's LDS table into the HBM table: one emplace per occupied cell (it may use the slack above max fill) and one global
+// update per state word, the high half of a fixed-point sum travelling with its low half.  Find-only mode: the cell of a key the table
+// lacks goes to the overflow row s_ovf.  Every thread calls it, after a barrier.
+template <typename KT>
+__device__ __forceinline__ void lds_flush(const AggTable & t, const AggDesc & d, const unsigned char * lds_raw, const PartLds & L, u32 S, const u32 & lzero, u64 * s_ovf)
+{
+    const KT * lkeys = (const KT *)lds_raw;
+    for (u32 s = threadIdx.x; s <= S; s += blockDim.x)
+    {
+        const u64 key = (u64)lkeys[s];
+        const bool occupied = (s == S) ? (lzero != 0) : (key != 0);
+        if (!occupied)
+            continue;
+        const u64 slot = table_place(t, s == S ? 0 : key, false);
+        if (slot == ~0ull)
+        {
+            t.ctrl->fatal = 1;
+            continue;
+        }
+        const bool miss = slot == AGG_SLOT_MISS;
+        if (miss && !t.ovf)
+            continue;
+        for (u32 w = 0; w < d.n_words; ++w)
+        {
+            if ((d.word_fx_hi >> w) & 1)
+                continue; // flushed with its low half
+            const unsigned char * wp = lds_raw + L.off(w);
+            const u64 bits = ((L.cnt32 >> w) & 1) ? (u64)((const u32 *)wp)[s] : ((const u64 *)wp)[s];
+            const u64 hb = ((d.word_fx >> w) & 1) ? ((const u64 *)(lds_raw + L.off(d.fx_hi[w])))[s] : 0;
+            if (miss)
+                add_cell_word(LdsRowSink{s_ovf}, d, w, bits, hb);
+            else
+                add_cell_word(GlobalSink(t, slot), d, w, bits, hb);
+        }
+    }
+}
+
 enum { AGG_MODE_ALL = 0, AGG_MODE_PENDING = 1 };
 
 // DIRECT kernel: one global emplace + one atomic per state word per row.
@@ -599,16 +675,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_rows_direct(AggTable t, Agg
         if (active)
         {
             const u64 i = row_begin + r;
-            const u64 slot = table_place(t, load_key_zext(keys, key_type, i), true);
-            if (slot == ~0ull)
-                failed = true;
-            else if (slot == AGG_SLOT_MISS)
-            {
-                if (t.ovf)
-                    ovf_row_lds(s_ovf, d, i);
-            }
-            else
-                add_row_global(t, d, slot, i);
+            failed = place_and_add(t, s_ovf, load_key_zext(keys, key_type, i), true, [&](auto sink) { add_row(sink, d, i); });
         }
         const u64 b = __ballot(failed);
         if (lane == 0)
@@ -623,7 +690,8 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_rows_direct(AggTable t, Agg
     }
 }
 
-// LDS-STAGED kernel.  Dynamic LDS: lkeys[S+1] then lwords[n_words][S+1]; cell S is the zero key's.
+// LDS-STAGED kernel.  Dynamic LDS: lkeys[S+1] then lwords[n_words][S+1]; cell S is the zero key's (PartLds with 8-byte keys and no
+// 32-bit counts: the flush reads it as such).
 __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, const void * __restrict__ keys, int key_type,
                                                               u64 row_begin, u64 n, u64 * __restrict__ pending, u32 S)
 {
@@ -693,29 +761,7 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
                 const u64 i = row_begin + g * 64 + lane;
                 const u64 key = keyv[q];
                 // ---- LDS emplace: linear probing, give up after 32 cells (a nearly full LDS table) -> HBM path ----
-                u32 ls = ~0u;
-                if (key == 0)
-                {
-                    ls = S;
-                    lzero = 1;
-                }
-                else
-                {
-                    u32 s = (u32)(dev_intHash64(key) >> 40) & (S - 1);
-#pragma unroll 1
-                    for (int probe = 0; probe < 32; ++probe)
-                    {
-                        u64 k = lkeys[s];
-                        if (k == 0)
-                            k = atomicCAS((unsigned long long *)&lkeys[s], 0ull, (unsigned long long)key), k = (k == 0) ? key : k;
-                        if (k == key)
-                        {
-                            ls = s;
-                            break;
-                        }
-                        s = (s + 1) & (S - 1);
-                    }
-                }
+                const u32 ls = lds_find_or_claim<u64>(lkeys, key, (u32)(dev_intHash64(key) >> 40) & (S - 1), 32, S, lzero);
                 if (ls != ~0u)
                 {
 #pragma unroll
@@ -744,16 +790,7 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
                 }
                 else
                 {
-                    const u64 slot = table_place(t, key, true);
-                    if (slot == ~0ull)
-                        failed = true;
-                    else if (slot == AGG_SLOT_MISS)
-                    {
-                        if (t.ovf)
-                            ovf_row_lds(s_ovf, d, i);
-                    }
-                    else
-                        add_row_global(t, d, slot, i);
+                    failed = place_and_add(t, s_ovf, key, true, [&](auto sink) { add_row(sink, d, i); });
                 }
             }
             const u64 b = __ballot(failed);
@@ -766,45 +803,7 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
     __syncthreads();
 
     // ---- flush the workgroup's partial states: one emplace + n_words atomics per distinct key ----
-    const u64 gstride = t.capacity + 1;
-    for (u32 s = threadIdx.x; s <= S; s += blockDim.x)
-    {
-        const u64 key = lkeys[s];
-        const bool occupied = (s == S) ? (lzero != 0) : (key != 0);
-        if (!occupied)
-            continue;
-        const u64 slot = table_place(t, s == S ? 0 : key, false); // may use the slack above max fill
-        if (slot == ~0ull)
-        {
-            t.ctrl->fatal = 1;
-            continue;
-        }
-        if (slot == AGG_SLOT_MISS)
-        {
-            if (t.ovf)
-                for (u32 w = 0; w < d.n_words; ++w)
-                    if (!((d.word_fx_hi >> w) & 1))
-                        ovf_cell_word_lds(s_ovf, d, w, lwords[w * lstride + s], ((d.word_fx >> w) & 1) ? lwords[d.fx_hi[w] * lstride + s] : 0);
-            continue;
-        }
-        for (u32 w = 0; w < d.n_words; ++w)
-        {
-            if ((d.word_fx_hi >> w) & 1)
-                continue; // flushed with its low half
-            const u64 bits = lwords[w * lstride + s];
-            if ((d.word_fx >> w) & 1)
-            {
-                const u32 wh = d.fx_hi[w];
-                const u64 hb = lwords[wh * lstride + s];
-                if (bits | hb)
-                    global_add_fx(t.words + (u64)d.word_map[w] * gstride + slot, t.words + (u64)d.word_map[wh] * gstride + slot, Fx128{bits, hb});
-                continue;
-            }
-            const bool f = (d.word_is_f64 >> w) & 1;
-            if (f ? (__longlong_as_double((long long)bits) != 0.0 || bits != 0) : (bits != 0))
-                global_add_word(t.words + (u64)d.word_map[w] * gstride + slot, bits, f);
-        }
-    }
+    lds_flush<u64>(t, d, lds_raw, PartLds(8, S, d.n_words, 0), S, lzero, s_ovf);
     if (t.ovf)
     {
         __syncthreads();
@@ -1145,7 +1144,6 @@ __global__ __launch_bounds__(1024) void k_gb_units(const u64 * __restrict__ offs
 // state word w is a row COUNT kept as 32 bits (a call never sees 2^32 rows; the host checks).  For the C3 shape
 // (UInt32 key, sum, count) a cell is 4+8+4 = 16 B, so 8192 cells fit and 256 partitions suffice for 1 M groups --
 // half as many partitions means partition runs twice as long in the scatter, whose cost is dominated by short runs.
-// Layout: keys KT[S+1] (padded to 8 B) | every 8-byte word u64[S+1] in word order | every 4-byte word u32[S+1].
 // widening of a zero-extended narrow argument load (see ex0/ex1 in k_agg_part_lds)
 __device__ __forceinline__ u64 part_extend(u64 raw, int ex)
 {
@@ -1179,17 +1177,33 @@ __host__ __device__ constexpr u32 gbp_ops_find(u32 ops, u32 code)
     return 0;
 }
 
-struct PartLds
+// the compile-time state update of one row at LDS cell ls: b0 / b1 = argument word 0 / 1, w_off[w] = PartLds::off(w).  (fx_base by
+// reference: handed over by value, a descriptor field is fetched ahead of the walk, not where operation 7 uses it, and the 8-byte-key
+// tile kernels with a fixed-point sum then need one more VGPR)
+template <u32 OPS>
+__device__ __forceinline__ void lds_update_ops(unsigned char * lds_raw, const u32 (&w_off)[4], u32 ls, u64 b0, u64 b1, const int & fx_base)
 {
-    u32 S1, cnt32, n8, keys_bytes;
-    __device__ __forceinline__ u32 off(u32 w) const
+#pragma unroll
+    for (u32 w = 0; w < 4; ++w)
     {
-        const u32 low = (1u << w) - 1;
-        if ((cnt32 >> w) & 1)
-            return keys_bytes + 8 * S1 * n8 + 4 * S1 * (u32)__popc(cnt32 & low);
-        return keys_bytes + 8 * S1 * (u32)__popc(~cnt32 & low);
+        const u32 op = (OPS >> (4 * w)) & 15u;
+        if (op == 0)
+            break;
+        unsigned char * wp = lds_raw + w_off[w];
+        if (op == 1 || op == 2)
+            atomicAdd((unsigned long long *)wp + ls, (unsigned long long)(op == 1 ? b0 : b1));
+        else if (op == 7)
+            lds_add_fx((u64 *)wp + ls, (u64 *)(lds_raw + w_off[gbp_ops_find(OPS, 9)]) + ls, fx_from_double(b0, fx_base));
+        else if (op == 9)
+            continue;
+        else if (op == 3 || op == 4)
+            atomicAdd((double *)wp + ls, __longlong_as_double((long long)(op == 3 ? b0 : b1)));
+        else if (op == 5)
+            atomicAdd((unsigned int *)wp + ls, 1u);
+        else
+            atomicAdd((unsigned long long *)wp + ls, 1ull);
     }
-};
+}
 
 // AW: bytes per element of the argument columns (8 in PARTITION mode -- the buffers hold widened words; 8, 4 or 1 in RANGE mode,
 // where the source columns are read as they are and 4-byte signed arguments are sign-extended after the load)
@@ -1206,19 +1220,13 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
                                                        const u8 * __restrict__ cond)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    typedef typename std::conditional<sizeof(KT) == 4, unsigned int, unsigned long long>::type CasT;
     KT * lkeys = (KT *)lds_raw;
-    PartLds L;
-    L.S1 = S + 1;
-    L.cnt32 = cnt32;
-    L.n8 = d.n_words - (u32)__popc(cnt32);
-    L.keys_bytes = ((u32)sizeof(KT) * L.S1 + 7) & ~7u;
-    const u32 lds_bytes = L.keys_bytes + 8 * L.S1 * L.n8 + 4 * L.S1 * (u32)__popc(cnt32);
+    const PartLds L((u32)sizeof(KT), S, d.n_words, cnt32);
+    const u32 lds_bytes = L.bytes();
     __shared__ u32 lzero, sh_unit;
     __shared__ u64 s_ovf[AGG_MAX_WORDS]; // find-only mode: the workgroup's share of the overflow row (made visible by the loop's first barrier)
     ovf_lds_init(s_ovf);
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    const u64 gstride = t.capacity + 1;
     // The aggregate descriptors are decoded ONCE into wave-uniform registers (all loops over them are fully unrolled, so the
     // indices are constants): fetching d.a[j] inside the row loop meant an s_load per function and row group, and its
     // s_waitcnt lgkmcnt(0) also drains every LDS operation the wave has in flight -- the pass was issue-bound at ~170
@@ -1362,54 +1370,12 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
                         if (ex1)
                             b1 = part_extend(b1, ex1);
                     }
-                    u32 ls = ~0u;
-                    if (key == 0)
-                    {
-                        ls = S;
-                        lzero = 1;
-                    }
-                    else
-                    {
-                        u32 s = gbp_cell<KT>((KT)key, offsets ? P : 1u, S); // bits disjoint from the partition id
-#pragma unroll 1
-                        for (int probe = 0; probe < 64; ++probe)
-                        {
-                            KT k = lkeys[s];
-                            if (k == 0)
-                                k = (KT)atomicCAS((CasT *)&lkeys[s], (CasT)0, (CasT)key), k = (k == 0) ? (KT)key : k;
-                            if (k == (KT)key)
-                            {
-                                ls = s;
-                                break;
-                            }
-                            s = (s + 1) & (S - 1);
-                        }
-                    }
+                    // (start cell: bits disjoint from the partition id)
+                    const u32 ls = lds_find_or_claim<KT>(lkeys, (KT)key, gbp_cell<KT>((KT)key, offsets ? P : 1u, S), 64, S, lzero);
                     if (ls != ~0u)
                     {
                         if constexpr (OPS != 0)
-                        {
-#pragma unroll
-                            for (u32 w = 0; w < 4; ++w)
-                            {
-                                const u32 op = (OPS >> (4 * w)) & 15u;
-                                if (op == 0)
-                                    break;
-                                unsigned char * wp = lds_raw + w_off[w];
-                                if (op == 1 || op == 2)
-                                    atomicAdd((unsigned long long *)wp + ls, (unsigned long long)(op == 1 ? b0 : b1));
-                                else if (op == 7)
-                                    lds_add_fx((u64 *)wp + ls, (u64 *)(lds_raw + w_off[gbp_ops_find(OPS, 9)]) + ls, fx_from_double(b0, fx_base));
-                                else if (op == 9)
-                                    continue;
-                                else if (op == 3 || op == 4)
-                                    atomicAdd((double *)wp + ls, __longlong_as_double((long long)(op == 3 ? b0 : b1)));
-                                else if (op == 5)
-                                    atomicAdd((unsigned int *)wp + ls, 1u);
-                                else
-                                    atomicAdd((unsigned long long *)wp + ls, 1ull);
-                            }
-                        }
+                            lds_update_ops<OPS>(lds_raw, w_off, ls, b0, b1, fx_base);
                         else
 #pragma unroll
                         for (u32 j = 0; j < AGG_MAX_AGGS; ++j)
@@ -1436,16 +1402,7 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
                     }
                     else
                     {
-                        const u64 slot = table_place(t, key, true);
-                        if (slot == ~0ull)
-                            failed = true;
-                        else if (slot == AGG_SLOT_MISS)
-                        {
-                            if (t.ovf)
-                                ovf_vals_lds(s_ovf, d, b0, b1, 1);
-                        }
-                        else
-                            add_vals_global(t, d, slot, b0, b1, 1);
+                        failed = place_and_add(t, s_ovf, key, true, [&](auto sink) { add_vals(sink, d, b0, b1, 1); });
                     }
                 }
                 const u64 b = __ballot(failed);
@@ -1473,49 +1430,7 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
             }
         }
         __syncthreads();
-        for (u32 s = threadIdx.x; s <= S; s += blockDim.x)
-        {
-            const u64 key = (u64)lkeys[s];
-            const bool occupied = (s == S) ? (lzero != 0) : (key != 0);
-            if (!occupied)
-                continue;
-            const u64 slot = table_place(t, s == S ? 0 : key, false);
-            if (slot == ~0ull)
-            {
-                t.ctrl->fatal = 1;
-                continue;
-            }
-            if (slot == AGG_SLOT_MISS)
-            {
-                if (t.ovf)
-                    for (u32 w = 0; w < d.n_words; ++w)
-                    {
-                        if ((d.word_fx_hi >> w) & 1)
-                            continue;
-                        const unsigned char * wp = lds_raw + L.off(w);
-                        const u64 bits = ((cnt32 >> w) & 1) ? (u64)((const u32 *)wp)[s] : ((const u64 *)wp)[s];
-                        ovf_cell_word_lds(s_ovf, d, w, bits, ((d.word_fx >> w) & 1) ? ((const u64 *)(lds_raw + L.off(d.fx_hi[w])))[s] : 0);
-                    }
-                continue;
-            }
-            for (u32 w = 0; w < d.n_words; ++w)
-            {
-                if ((d.word_fx_hi >> w) & 1)
-                    continue; // flushed with its low half
-                const unsigned char * wp = lds_raw + L.off(w);
-                const u64 bits = ((cnt32 >> w) & 1) ? (u64)((const u32 *)wp)[s] : ((const u64 *)wp)[s];
-                if ((d.word_fx >> w) & 1)
-                {
-                    const u32 wh = d.fx_hi[w];
-                    const u64 hb = ((const u64 *)(lds_raw + L.off(wh)))[s];
-                    if (bits | hb)
-                        global_add_fx(t.words + (u64)d.word_map[w] * gstride + slot, t.words + (u64)d.word_map[wh] * gstride + slot, Fx128{bits, hb});
-                    continue;
-                }
-                if (bits != 0)
-                    global_add_word(t.words + (u64)d.word_map[w] * gstride + slot, bits, (d.word_is_f64 >> w) & 1);
-            }
-        }
+        lds_flush<KT>(t, d, lds_raw, L, S, lzero, s_ovf);
         __syncthreads();
     }
     if (t.ovf) // (the loop ends on a barrier)
@@ -1639,20 +1554,14 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
                                                         const u64 * __restrict__ unit_list, const u32 * __restrict__ qstart, u32 * __restrict__ qctr)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    typedef typename std::conditional<sizeof(KT) == 4, unsigned int, unsigned long long>::type CasT;
     KT * lkeys = (KT *)lds_raw;
-    PartLds L;
-    L.S1 = S + 1;
-    L.cnt32 = cnt32;
-    L.n8 = d.n_words - (u32)__popc(cnt32);
-    L.keys_bytes = ((u32)sizeof(KT) * L.S1 + 7) & ~7u;
-    const u32 lds_bytes = L.keys_bytes + 8 * L.S1 * L.n8 + 4 * L.S1 * (u32)__popc(cnt32);
+    const PartLds L((u32)sizeof(KT), S, d.n_words, cnt32);
+    const u32 lds_bytes = L.bytes();
     __shared__ u32 lzero, sh_unit;
     __shared__ u64 s_ovf[AGG_MAX_WORDS]; // find-only mode: the workgroup's share of the overflow row (made visible by the loop's first barrier)
     ovf_lds_init(s_ovf);
     const u32 lane = threadIdx.x & 63;
     const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), n_waves = blockDim.x >> 6;
-    const u64 gstride = t.capacity + 1;
     const u64 last_row = (u64)n_tiles * TILE - 1;
     u32 w_off[4];
 #pragma unroll
@@ -1718,52 +1627,10 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
         };
         // the LDS update of one row; the row is virtual row v of the step (PACKED_ = true_type) or row v of the sorted copy itself; its index is only needed when the LDS table is full
         auto update_row = [&](KT key, u64 b0, u32 v, auto packed, const u32 (&cs)[PR + 1], const u32 (&dl)[PR]) {
-            u32 ls = ~0u;
-            if (key == 0)
-            {
-                ls = S;
-                lzero = 1;
-            }
-            else
-            {
-                u32 s = gbp_cell<KT>(key, P, S); // bits disjoint from the partition id
-#pragma unroll 1
-                for (int probe = 0; probe < 64; ++probe)
-                {
-                    KT k = lkeys[s];
-                    if (k == 0)
-                        k = (KT)atomicCAS((CasT *)&lkeys[s], (CasT)0, (CasT)key), k = (k == 0) ? key : k;
-                    if (k == key)
-                    {
-                        ls = s;
-                        break;
-                    }
-                    s = (s + 1) & (S - 1);
-                }
-            }
+            // (start cell: bits disjoint from the partition id)
+            const u32 ls = lds_find_or_claim<KT>(lkeys, key, gbp_cell<KT>(key, P, S), 64, S, lzero);
             if (ls != ~0u)
-            {
-#pragma unroll
-                for (u32 w = 0; w < 4; ++w)
-                {
-                    const u32 op = (OPS >> (4 * w)) & 15u;
-                    if (op == 0)
-                        break;
-                    unsigned char * wp = lds_raw + w_off[w];
-                    if (op == 1)
-                        atomicAdd((unsigned long long *)wp + ls, (unsigned long long)b0);
-                    else if (op == 7)
-                        lds_add_fx((u64 *)wp + ls, (u64 *)(lds_raw + w_off[gbp_ops_find(OPS, 9)]) + ls, fx_from_double(b0, d.fx_base));
-                    else if (op == 9)
-                        continue;
-                    else if (op == 3)
-                        atomicAdd((double *)wp + ls, __longlong_as_double((long long)b0));
-                    else if (op == 5)
-                        atomicAdd((unsigned int *)wp + ls, 1u);
-                    else
-                        atomicAdd((unsigned long long *)wp + ls, 1ull);
-                }
-            }
+                lds_update_ops<OPS>(lds_raw, w_off, ls, b0, 0, d.fx_base); // (this kernel's operations never read argument word 1)
             else
             {
                 // the LDS table is full around this key's cell (more groups than promised): the row is left to the finish rounds, which
@@ -1863,49 +1730,7 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
             }
         }
         __syncthreads();
-        for (u32 s = threadIdx.x; s <= S; s += blockDim.x)
-        {
-            const u64 key = (u64)lkeys[s];
-            const bool occupied = (s == S) ? (lzero != 0) : (key != 0);
-            if (!occupied)
-                continue;
-            const u64 slot = table_place(t, s == S ? 0 : key, false);
-            if (slot == ~0ull)
-            {
-                t.ctrl->fatal = 1;
-                continue;
-            }
-            if (slot == AGG_SLOT_MISS)
-            {
-                if (t.ovf)
-                    for (u32 w = 0; w < d.n_words; ++w)
-                    {
-                        if ((d.word_fx_hi >> w) & 1)
-                            continue;
-                        const unsigned char * wp = lds_raw + L.off(w);
-                        const u64 bits = ((cnt32 >> w) & 1) ? (u64)((const u32 *)wp)[s] : ((const u64 *)wp)[s];
-                        ovf_cell_word_lds(s_ovf, d, w, bits, ((d.word_fx >> w) & 1) ? ((const u64 *)(lds_raw + L.off(d.fx_hi[w])))[s] : 0);
-                    }
-                continue;
-            }
-            for (u32 w = 0; w < d.n_words; ++w)
-            {
-                if ((d.word_fx_hi >> w) & 1)
-                    continue; // flushed with its low half
-                const unsigned char * wp = lds_raw + L.off(w);
-                const u64 bits = ((cnt32 >> w) & 1) ? (u64)((const u32 *)wp)[s] : ((const u64 *)wp)[s];
-                if ((d.word_fx >> w) & 1)
-                {
-                    const u32 wh = d.fx_hi[w];
-                    const u64 hb = ((const u64 *)(lds_raw + L.off(wh)))[s];
-                    if (bits | hb)
-                        global_add_fx(t.words + (u64)d.word_map[w] * gstride + slot, t.words + (u64)d.word_map[wh] * gstride + slot, Fx128{bits, hb});
-                    continue;
-                }
-                if (bits != 0)
-                    global_add_word(t.words + (u64)d.word_map[w] * gstride + slot, bits, (d.word_is_f64 >> w) & 1);
-            }
-        }
+        lds_flush<KT>(t, d, lds_raw, L, S, lzero, s_ovf);
         __syncthreads();
     }
     if (t.ovf) // (the loop ends on a barrier)
@@ -1920,6 +1745,33 @@ struct AggFxWords
     u32 word_fx, word_fx_hi, word_any;
     unsigned char fx_hi[AGG_MAX_WORDS];
 };
+// source tuple i's state words into the group's state in `sink` (table words: a merge has no word map)
+template <typename Sink>
+__device__ __forceinline__ void merge_tuple_words(const Sink & sink, u32 n_words, u32 word_is_f64, const AggFxWords & fx, const u64 * __restrict__ src_words,
+                                                  u64 src_stride, u64 i)
+{
+    for (u32 w = 0; w < n_words; ++w)
+    {
+        if ((fx.word_fx_hi >> w) & 1)
+            continue; // merged with its low half
+        const u64 v = src_words[(u64)w * src_stride + i];
+        if ((fx.word_any >> w) & 1)
+        {
+            // any(): changeFirstTime (SingleValueData.cpp) -- a state that has a value keeps it; {claim, value} move together
+            if (v && atomicCAS((unsigned long long *)sink.at(w), 0ull, (unsigned long long)v) == 0ull)
+                *sink.at(w + 1) = src_words[(u64)(w + 1) * src_stride + i];
+            ++w;
+            continue;
+        }
+        if ((fx.word_fx >> w) & 1)
+        {
+            const u32 wh = fx.fx_hi[w];
+            sink.add_fx(sink.at(w), sink.at(wh), Fx128{v, src_words[(u64)wh * src_stride + i]});
+            continue;
+        }
+        sink.add_word(sink.at(w), v, (int)((word_is_f64 >> w) & 1) | (int)(((word_is_f64 >> (16 + w)) & 1) << 1)); // upper half of the mask: max words
+    }
+}
 template <int MODE>
 __global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, u32 n_words, u32 word_is_f64, AggFxWords fx, const u64 * __restrict__ src_keys,
                                                             const u64 * __restrict__ src_words, u64 src_stride, u64 n, int skip_zero_keys,
@@ -1929,7 +1781,6 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, u32 n_wo
     const u64 wave0 = ((u64)blockIdx.x * AGG_THREADS + threadIdx.x) >> 6;
     const u64 n_waves = ((u64)gridDim.x * AGG_THREADS) >> 6;
     const u64 n_groups64 = (n + 63) / 64;
-    const u64 gstride = t.capacity + 1;
     __shared__ u64 s_ovf[AGG_MAX_WORDS]; // find-only merges (never the rehash): the workgroup's share of the overflow row
     if (t.ovf)
     {
@@ -1972,53 +1823,10 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, u32 n_wo
                     // mergeDataNoMoreKeysImpl: the source state of a key dst lacks goes to dst's overflow row (or is dropped:
                     // mergeDataOnlyExistingKeysImpl)
                     if (t.ovf)
-                        for (u32 w = 0; w < n_words; ++w)
-                        {
-                            if ((fx.word_fx_hi >> w) & 1)
-                                continue;
-                            const u64 v = src_words[(u64)w * src_stride + i];
-                            if ((fx.word_any >> w) & 1)
-                            {
-                                if (v && atomicCAS((unsigned long long *)&s_ovf[w], 0ull, (unsigned long long)v) == 0ull)
-                                    s_ovf[w + 1] = src_words[(u64)(w + 1) * src_stride + i];
-                                ++w;
-                                continue;
-                            }
-                            if ((fx.word_fx >> w) & 1)
-                            {
-                                const u32 wh = fx.fx_hi[w];
-                                const u64 hv = src_words[(u64)wh * src_stride + i];
-                                if (v | hv)
-                                    lds_add_fx(&s_ovf[w], &s_ovf[wh], Fx128{v, hv});
-                                continue;
-                            }
-                            ovf_lds_word(&s_ovf[w], v, ((word_is_f64 >> (16 + w)) & 1) ? 2 : (int)((word_is_f64 >> w) & 1));
-                        }
+                        merge_tuple_words(LdsRowSink{s_ovf}, n_words, word_is_f64, fx, src_words, src_stride, i);
                 }
                 else
-                    for (u32 w = 0; w < n_words; ++w)
-                    {
-                        if ((fx.word_fx_hi >> w) & 1)
-                            continue; // merged with its low half
-                        if ((fx.word_any >> w) & 1)
-                        {
-                            // any(): changeFirstTime (SingleValueData.cpp) -- a state that has a value keeps it; {claim, value} move together
-                            const u64 claim = src_words[(u64)w * src_stride + i];
-                            if (claim && atomicCAS((unsigned long long *)(t.words + (u64)w * gstride + slot), 0ull, (unsigned long long)claim) == 0ull)
-                                t.words[(u64)(w + 1) * gstride + slot] = src_words[(u64)(w + 1) * src_stride + i];
-                            ++w;
-                            continue;
-                        }
-                        if ((fx.word_fx >> w) & 1)
-                        {
-                            const u32 wh = fx.fx_hi[w];
-                            global_add_fx(t.words + (u64)w * gstride + slot, t.words + (u64)wh * gstride + slot,
-                                          Fx128{src_words[(u64)w * src_stride + i], src_words[(u64)wh * src_stride + i]});
-                            continue;
-                        }
-                        global_add_word(t.words + (u64)w * gstride + slot, src_words[(u64)w * src_stride + i],
-                                        (int)((word_is_f64 >> w) & 1) | (int)(((word_is_f64 >> (16 + w)) & 1) << 1)); // upper half of the mask: max words
-                    }
+                    merge_tuple_words(GlobalSink(t, slot), n_words, word_is_f64, fx, src_words, src_stride, i);
             }
         }
         const u64 b = __ballot(failed);
@@ -2310,8 +2118,6 @@ static void agg_fill_desc(const chgpu_agg * a, const chgpu_col * const * arg_col
         d->a[j].pre = 0;
     }
 }
-
-static int agg_finish_rounds(chgpu_agg * a, const AggDesc & d, const void * keys, int key_type, u64 row_begin, u64 n, u64 * pending);
 
 // min / max / any WITHOUT key (executeWithoutKeyImpl, Aggregator.cpp:1276-1321: addBatchSinglePlace): one order-key maximum over the rows of
 // the block that pass `cond`; the first such row for any()
@@ -2711,16 +2517,8 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tiles_pending_aos(AggTable 
         if (i < n && ((word >> lane) & 1))
         {
             const u32 * r = rec + i * (key64 ? 4 : 3); // records are {word, key}: 12 bytes with a 4-byte key, 16 with an 8-byte key
-            const u64 slot = table_place(t, key64 ? (u64)r[2] | ((u64)r[3] << 32) : (u64)r[2], true);
-            if (slot == ~0ull)
-                failed = true;
-            else if (slot == AGG_SLOT_MISS)
-            {
-                if (t.ovf)
-                    ovf_vals_lds(s_ovf, d, (u64)r[0] | ((u64)r[1] << 32), 0, 1);
-            }
-            else
-                add_vals_global(t, d, slot, (u64)r[0] | ((u64)r[1] << 32), 0, 1);
+            failed = place_and_add(t, s_ovf, key64 ? (u64)r[2] | ((u64)r[3] << 32) : (u64)r[2], true,
+                                   [&](auto sink) { add_vals(sink, d, (u64)r[0] | ((u64)r[1] << 32), 0, 1); });
         }
         const u64 b = __ballot(failed);
         if (lane == 0)
@@ -2735,7 +2533,10 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tiles_pending_aos(AggTable 
     }
 }
 
-static int agg_finish_rounds_aos(chgpu_agg * a, const AggDesc & d, const u32 * rec, int key64, u64 n, u64 * pending)
+// resize on overflow (HashTable.h:921-944): grow + rehash, then re-run only the rows left pending, until none is.  relaunch(grid):
+// the plan's kernel over its n rows that places the rows marked pending.
+template <typename Relaunch>
+static int agg_finish_rounds_with(chgpu_agg * a, u64 n, Relaunch relaunch)
 {
     chgpu_ctx * ctx = a->ctx;
     for (int round = 0; round < 64; ++round)
@@ -2757,12 +2558,25 @@ static int agg_finish_rounds_aos(chgpu_agg * a, const AggDesc & d, const u32 * r
             if (!c.overflow)
                 return agg_debug_rounds(ctx, round);
         }
-        const u32 grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
-        hipLaunchKernelGGL(k_agg_tiles_pending_aos, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, rec, key64, n, pending);
+        relaunch(chgpu_grid_for(ctx, n, AGG_THREADS, 8));
         ctx->counters[6] += 1;
         CHGPU_HIP(hipGetLastError());
     }
     return chgpu_set_error(CHGPU_ERR_LOGICAL, "aggregation table did not converge after 64 growth rounds");
+}
+
+static int agg_finish_rounds(chgpu_agg * a, const AggDesc & d, const void * keys, int key_type, u64 row_begin, u64 n, u64 * pending)
+{
+    return agg_finish_rounds_with(a, n, [&](u32 grid) {
+        hipLaunchKernelGGL(k_agg_rows_direct<AGG_MODE_PENDING>, dim3(grid), dim3(AGG_THREADS), 0, a->ctx->stream, a->t, d, keys, key_type, row_begin, n, pending);
+    });
+}
+
+static int agg_finish_rounds_aos(chgpu_agg * a, const AggDesc & d, const u32 * rec, int key64, u64 n, u64 * pending)
+{
+    return agg_finish_rounds_with(a, n, [&](u32 grid) {
+        hipLaunchKernelGGL(k_agg_tiles_pending_aos, dim3(grid), dim3(AGG_THREADS), 0, a->ctx->stream, a->t, d, rec, key64, n, pending);
+    });
 }
 
 // The TILE-SORTED plan of a partitioned executeOnBlock (k_rp_tilesort + k_agg_tiles_lds): one level, one 8-byte argument column
@@ -2983,9 +2797,7 @@ static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const c
     {
         hipLaunchKernelGGL(k_tile_units, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long *)part_total, P, chunk_rows, n_tiles, unit_list, max_units, unit_qstart, unit_ctr);
         hipLaunchKernelGGL(k_tile_index_transpose, dim3((n_tiles + 63) / 64, (P + 63) / 64), dim3(256), 0, ctx->stream, (const unsigned short *)tidx, n_tiles, P, run_index);
-        const u32 n4 = (u32)__builtin_popcount(cnt32), n8 = d.n_words - n4;
-        const size_t keys_lds = ((size_t)key_w * (S + 1) + 7) & ~(size_t)7;
-        const size_t lds_ag = keys_lds + (size_t)(S + 1) * (8 * n8 + 4 * n4) + 16;
+        const size_t lds_ag = (size_t)PartLds(key_w, S, d.n_words, cnt32).bytes() + 16;
 #define GB_TILES(KT_, OPS_, TILE_)                                                                                                                    \
     do                                                                                                                                                \
     {                                                                                                                                                 \
@@ -3050,7 +2862,6 @@ static int agg_add_block_partitioned(chgpu_agg * a, const chgpu_col * key_col, c
     const bool key32 = chgpu_type_size(a->key_type) <= 4; // 4-byte (or narrower) keys are stored as 4 bytes in the partition buffers
     u32 cnt32 = 0;
     size_t cell_b = agg_part_cell_bytes(a, n, &cnt32);
-    const u32 n4 = (u32)__builtin_popcount(cnt32), n8 = a->n_words - n4;
     // a pass over ONE argument word of a subset of the functions goes through the tile-sorted plan with cells that hold only its words
     const bool local_pass = word_pass != 0 && level == 0 && K == 1 && agg_mask != ~0u;
     if (local_pass)
@@ -3303,8 +3114,7 @@ static int agg_add_block_partitioned(chgpu_agg * a, const chgpu_col * key_col, c
         rc = hipMemsetAsync(pending, 0, pend_b, ctx->stream) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE;
     if (rc == CHGPU_OK)
     {
-        const size_t keys_lds = ((size_t)(key32 ? 4 : 8) * (S + 1) + 7) & ~(size_t)7;
-        const size_t lds_ag = keys_lds + (size_t)(S + 1) * (8 * n8 + 4 * n4) + 16; // the kernel zeroes whole 8-byte words
+        const size_t lds_ag = (size_t)PartLds(key32 ? 4 : 8, S, a->n_words, cnt32).bytes() + 16; // the kernel zeroes whole 8-byte words
         hipLaunchKernelGGL(k_gb_units, dim3(1), dim3(1024), 0, ctx->stream, (const u64 *)offsets, G, P, n, chunk_rows, unit_start, unit_ctr);
         const u64 rows_per_chunk = chunk_rows;
         u32 grid = (u32)ctx->num_cus;
@@ -3536,7 +3346,6 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
     const bool key32 = chgpu_type_size(a->key_type) <= 4, key8 = chgpu_type_size(a->key_type) == 1, key16 = chgpu_type_size(a->key_type) == 2;
     u32 cnt32 = 0;
     (void)agg_part_cell_bytes(a, n, &cnt32);
-    const u32 n4 = (u32)__builtin_popcount(cnt32), n8 = a->n_words - n4;
     // cells: four times the promised groups (4096 when nothing was promised), bounded by ~150 KiB of LDS; tables of up
     // to ~76 KiB let two 1024-thread workgroups share a CU
     const u32 s_dflt = (u32)chgpu_opt(ctx, "tune_agg_ranged_s", 4096);
@@ -3546,8 +3355,7 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
             ;
     if (S > lds_cells)
         S = lds_cells;
-    const size_t keys_lds = ((size_t)(key32 ? 4 : 8) * (S + 1) + 7) & ~(size_t)7;
-    const size_t lds_ag = keys_lds + (size_t)(S + 1) * (8 * n8 + 4 * n4) + 16;
+    const size_t lds_ag = (size_t)PartLds(key32 ? 4 : 8, S, a->n_words, cnt32).bytes() + 16;
     const u32 wg_per_cu = lds_ag <= 76 * 1024 ? 2 : 1;
     // flushes may claim up to grid * (S+1) cells above max fill: keep that inside the slack (capacity/2)
     const u64 max_grid = (a->t.capacity / 2) / (S + 1);
@@ -3857,38 +3665,6 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
 
     return agg_finish_rounds(a, d, key_col->data, a->key_type, row_begin, n, pending);
 }
-
-// resize on overflow (HashTable.h:921-944): grow + rehash, then re-run only the rows left pending, until none is
-static int agg_finish_rounds(chgpu_agg * a, const AggDesc & d, const void * keys, int key_type, u64 row_begin, u64 n, u64 * pending)
-{
-    chgpu_ctx * ctx = a->ctx;
-    for (int round = 0; round < 64; ++round)
-    {
-        AggCtrl c;
-        CHGPU_TRY(agg_read_ctrl(a, &c));
-        if (!c.overflow && c.n_groups <= a->t.max_fill)
-            return agg_debug_rounds(ctx, round);
-        if (a->t.find_only)
-        {
-            // a find-only block never grows the table: the rows a plan left pending are looked up once more (a look-up cannot fail)
-            if (!c.overflow)
-                return agg_debug_rounds(ctx, round);
-            CHGPU_TRY(agg_clear_overflow_flag(a));
-        }
-        else
-        {
-            CHGPU_TRY(agg_grow(a, c.n_groups, c.has_zero != 0));
-            if (!c.overflow)
-                return agg_debug_rounds(ctx, round);
-        }
-        const u32 grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
-        hipLaunchKernelGGL(k_agg_rows_direct<AGG_MODE_PENDING>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, keys, key_type, row_begin, n, pending);
-        ctx->counters[6] += 1;
-        CHGPU_HIP(hipGetLastError());
-    }
-    return chgpu_set_error(CHGPU_ERR_LOGICAL, "aggregation table did not converge after 64 growth rounds");
-}
-
 
 // merge tuples (keys + state word columns) with overflow handling
 static int agg_merge_tuples(chgpu_agg * a, const u64 * src_keys, const u64 * src_words, u64 src_stride, u64 n, int skip_zero_keys, u64 zero_slot_index)
