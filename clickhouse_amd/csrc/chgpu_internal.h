@@ -225,6 +225,26 @@ __device__ __forceinline__ u32 wave_reduce_add_u32(u32 v)
     return v;
 }
 
+__device__ __forceinline__ u64 wave_reduce_max_u64(u64 v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+    {
+        const u64 o = shfl_down_u64(v, d);
+        v = o > v ? o : v;
+    }
+    return v; // valid in lane 0
+}
+
+// the sum in EVERY lane (butterfly), for a wave that goes on to branch on it
+__device__ __forceinline__ u32 wave_allreduce_add_u32(u32 v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+        v += __shfl_xor(v, d, WAVE);
+    return v;
+}
+
 // murmur finalizer == the reference's intHash64 (src/Common/HashTable/Hash.h:27-36): the device tables' placement hash.
 __device__ __forceinline__ u64 dev_intHash64(u64 x)
 {

@@ -223,18 +223,8 @@ __device__ __forceinline__ u32 jc_find_slot(const ChainTailStep & st, u64 key)
 {
     if (key == 0)
         return st.has_zero ? (u32)st.capacity : NO_SLOT;
-    const u64 mask = st.capacity - 1;
-    u64 slot = dev_intHash64(key) & mask;
-    for (u64 step = 0; step < st.capacity; ++step)
-    {
-        const u64 k = st.kv[2 * slot];
-        if (k == key)
-            return (u32)slot;
-        if (k == 0)
-            return NO_SLOT;
-        slot = (slot + 1) & mask;
-    }
-    return NO_SLOT;
+    u64 unused;
+    return jt_walk<false>(st.kv, st.capacity, key, dev_intHash64(key) & (st.capacity - 1), 0, unused);
 }
 
 __device__ __forceinline__ bool jc_tail_found(const ChainTailStep & st, u64 key)
@@ -255,14 +245,6 @@ __device__ __forceinline__ bool jc_tail_found(const ChainTailStep & st, u64 key)
 static constexpr u32 JCT_THREADS = 256, JCT_WAVES = JCT_THREADS / 64, JCT_U = 4;
 static constexpr u32 JCT_QUEUE = 1024;   // queue entries per wave: a quarter of a unit (more alive rows than that: four passes, quarter by quarter)
 static constexpr u32 JCT_COAL_MIN = 96;  // alive rows of a unit from which a dense-bitmap step reads the unit's keys whole instead of row by row
-
-__device__ __forceinline__ u32 jc_wave_sum(u32 v)
-{
-#pragma unroll
-    for (int dlt = 32; dlt >= 1; dlt >>= 1)
-        v += __shfl_xor(v, dlt, 64);
-    return v;
-}
 
 // One dense-bitmap step over a whole unit whose keys are 4 bytes wide: the unit's 16 KiB of keys are read with full-width loads (a lane
 // takes its own sixteen quads, as in k_chain_lds), and only the bitmap words are gathered -- for the alive rows; a dead row reads word 0, so
@@ -344,12 +326,12 @@ __global__ __launch_bounds__(JCT_THREADS) void k_chain_tail(ChainTailArgs a, con
                     word &= ~(1ull << bit);
         }
         // steps over an exact bitmap while many rows are alive: the unit's keys read whole
-        u32 total = jc_wave_sum((u32)__popcll(word));
+        u32 total = wave_allreduce_add_u32((u32)__popcll(word));
         while (s < a.n_steps && whole && total >= JCT_COAL_MIN && a.s[s].dense && (a.s[s].key_type == CHGPU_U32 || a.s[s].key_type == CHGPU_I32)
                && ((uintptr_t)a.s[s].keys & 15) == 0 && ((uintptr_t)a.s[s].null_map & 3) == 0)
         {
             word = jc_tail_step_coalesced(a.s[s], word, row0, lane);
-            total = jc_wave_sum((u32)__popcll(word));
+            total = wave_allreduce_add_u32((u32)__popcll(word));
             ++s;
         }
         sv[lane] = 0;
@@ -431,7 +413,7 @@ __global__ __launch_bounds__(JCT_THREADS) void k_chain_tail(ChainTailArgs a, con
         }
         const u64 out = ((u64)sv[2 * lane + 1] << 32) | sv[2 * lane]; // rows row0 + 64 * lane ... + 63
         mask_words[unit * 64 + lane] = out;
-        const u32 cnt = jc_wave_sum((u32)__popcll(out));
+        const u32 cnt = wave_allreduce_add_u32((u32)__popcll(out)); // (only lane 0 needs it, but wave_reduce_add_u32 costs this kernel 6 VGPRs)
         if (lane == 0)
             unit_counts[unit] = cnt;
     }
@@ -553,22 +535,7 @@ __global__ __launch_bounds__(JT) void k_chain_gather(ChainEmitArgs a, const u64 
                         rid = st.kv[2 * st.capacity + 1];
                 }
                 else
-                {
-                    const u64 mask = st.capacity - 1;
-                    u64 slot = dev_intHash64(key) & mask;
-                    for (u64 step = 0; step < st.capacity; ++step)
-                    {
-                        const jv2 cell = *(const jv2 *)(st.kv + 2 * slot); // {key, value}: one 16-byte read
-                        if (cell.x == key)
-                        {
-                            rid = cell.y;
-                            break;
-                        }
-                        if (cell.x == 0)
-                            break;
-                        slot = (slot + 1) & mask;
-                    }
-                }
+                    jt_walk<true>(st.kv, st.capacity, key, dev_intHash64(key) & (st.capacity - 1), 0, rid); // {key, value}: one 16-byte read per cell; a miss leaves NO_ROW
             }
             if (a.payload_in[s])
             {

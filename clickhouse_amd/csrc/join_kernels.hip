@@ -30,6 +30,7 @@ static constexpr u32 NO_SLOT = ~0u;
 static constexpr u64 JV_MULTI = 1ull << 63;
 static constexpr u64 JV_CNT_SAT = (1ull << 23) - 1;
 static constexpr u64 JV_START_MASK = (1ull << 40) - 1;
+typedef u64 jv2 __attribute__((ext_vector_type(2))); // a {key, value} cell: one 16-byte access
 
 struct JoinCtrl
 {
@@ -85,6 +86,43 @@ __device__ __forceinline__ bool jt_pf_maybe(const PfView & v, u64 key)
         return false;
     const u64 pos = jt_pf_pos(v, key);
     return (v.words[pos >> 5] >> (pos & 31)) & 1;
+}
+
+// cell s holds a key (cell `capacity` is the zero key's, answered by has_zero)
+__device__ __forceinline__ bool jt_occupied(const JoinTable & t, u64 s) { return s == t.capacity ? (t.ctrl->has_zero != 0) : (t.kv[2 * s] != 0); }
+
+// The packed probe value of a found cell: the row id itself (one row), or MULTI | count | CSR start.  A count that does not fit its 23 bits
+// saturates and is read from t.cnt[slot] instead.
+__device__ __forceinline__ u64 jv_pack(u32 count, u64 start) { return JV_MULTI | ((u64)(count < JV_CNT_SAT ? count : JV_CNT_SAT) << 40) | (start & JV_START_MASK); }
+__device__ __forceinline__ bool jv_single(u64 v) { return !(v & JV_MULTI); }
+__device__ __forceinline__ const u64 * jv_run(const JoinTable & t, u64 v) { return t.rowids + (v & JV_START_MASK); } // !jv_single(v)
+// RowRefList::rows of the matched cell
+__device__ __forceinline__ u32 jv_rows(const JoinTable & t, u64 v, u32 slot)
+{
+    if (jv_single(v))
+        return 1;
+    const u64 c = (v >> 40) & JV_CNT_SAT;
+    return c < JV_CNT_SAT ? (u32)c : t.cnt[slot];
+}
+// fn(row id) for the first `rows` rows of the cell (a single row: that one)
+template <typename Fn>
+__device__ __forceinline__ void jv_for_each_row(const JoinTable & t, u64 v, u32 rows, Fn && fn)
+{
+    if (jv_single(v))
+    {
+        fn(v);
+        return;
+    }
+    const u64 * run = jv_run(t, v);
+    for (u32 k = 0; k < rows; ++k)
+        fn(run[k]);
+}
+
+// row id (block << 32 | row) -> position in the payload columns glued over all blocks.  The block must exist: callers that can meet the
+// default row of a miss check `rowid >> 32 < n_blocks` first.
+__device__ __forceinline__ u64 join_flat_row(const u64 * block_base, u64 n_blocks, u64 rowid)
+{
+    return n_blocks == 1 ? (rowid & 0xFFFFFFFFull) : block_base[rowid >> 32] + (rowid & 0xFFFFFFFFull);
 }
 
 struct BuildBlock
@@ -214,13 +252,8 @@ __global__ __launch_bounds__(JT) void k_join_stage_keys(const void * __restrict_
             out_keys[i] = k;
             row(i, k);
         }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-    {
-        const u64 x = __shfl_xor(m, o);
-        m = x > m ? x : m;
-        zero |= __shfl_xor(zero, o);
-    }
+    m = wave_reduce_max_u64(m);
+    zero = __any(zero) ? 1u : 0u;
     __shared__ unsigned long long s_m;
     __shared__ u32 s_zero;
     if (threadIdx.x == 0)
@@ -275,28 +308,60 @@ __device__ __forceinline__ u32 jt_emplace(const JoinTable & t, u64 key, bool & c
     return NO_SLOT; // unreachable: capacity >= 2 * rows
 }
 
+// The open-addressing walk over [capacity] {key, value} cells for a NON-ZERO key: compare, stop at an empty cell, step.  It starts at
+// `slot` with `step` cells already looked at by the caller (a staged look-up that has read the home cell itself) and returns the key's
+// slot or NO_SLOT.  CELL: every step reads the whole 16-byte cell and a hit leaves the value word in `value` (the key and its answer in
+// one transaction); otherwise only the 8-byte key word is read and `value` is left alone.
+template <bool CELL>
+__device__ __forceinline__ u32 jt_walk(const u64 * kv, u64 capacity, u64 key, u64 slot, u64 step, u64 & value)
+{
+    const u64 mask = capacity - 1;
+    u32 at = NO_SLOT;
+    for (; step < capacity; ++step)
+    {
+        u64 k;
+        if constexpr (CELL)
+        {
+            const jv2 c = *(const jv2 *)(kv + 2 * slot);
+            k = c.x;
+            if (k == key)
+                value = c.y;
+        }
+        else
+            k = kv[2 * slot];
+        if (k == key)
+            at = (u32)slot;
+        if (k == key || k == 0)
+            break;
+        slot = (slot + 1) & mask;
+    }
+    return at;
+}
+
+// -> the key's slot or NO_SLOT: the zero key's rule (it lives in cell `capacity`), the prefilter, the walk from the home slot
 // PF: the table has a prefilter (kernels are instantiated both ways and the host picks: with the test compiled in but
 // disabled at run time, the C4 probe -- whose 1e7-row build side has no prefilter -- ran 37 % slower)
-template <bool PF>
-__device__ __forceinline__ u32 jt_find(const JoinTable & t, const PfView & pf, u64 key)
+template <bool PF, bool CELL>
+__device__ __forceinline__ u32 jt_lookup(const JoinTable & t, const PfView & pf, u64 key, u64 & value)
 {
     if (key == 0)
-        return t.ctrl->has_zero ? (u32)t.capacity : NO_SLOT;
+    {
+        if (!t.ctrl->has_zero)
+            return NO_SLOT;
+        if constexpr (CELL)
+            value = t.kv[2 * t.capacity + 1];
+        return (u32)t.capacity;
+    }
     if constexpr (PF)
         if (!jt_pf_maybe(pf, key))
             return NO_SLOT;
-    const u64 mask = t.capacity - 1;
-    u64 slot = dev_intHash64(key) & mask;
-    for (u64 step = 0; step < t.capacity; ++step)
-    {
-        const u64 k = t.kv[2 * slot];
-        if (k == key)
-            return (u32)slot;
-        if (k == 0)
-            return NO_SLOT;
-        slot = (slot + 1) & mask;
-    }
-    return NO_SLOT;
+    return jt_walk<CELL>(t.kv, t.capacity, key, dev_intHash64(key) & (t.capacity - 1), 0, value);
+}
+template <bool PF>
+__device__ __forceinline__ u32 jt_find(const JoinTable & t, const PfView & pf, u64 key)
+{
+    u64 unused;
+    return jt_lookup<PF, false>(t, pf, key, unused);
 }
 
 // build pass 1: claim cells, count rows per key, record the owning row.
@@ -343,23 +408,12 @@ __global__ __launch_bounds__(JT) void k_join_insert(JoinTable t, const u64 * __r
         my_claims += claimed;
     }
     // (a same-address atomic per wave and iteration costs ~10 ns each: 1.5 ms of a 1e7-row build)
-    u32 tot = my_claims, dups = my_dups;
-#pragma unroll
-    for (int dlt = 32; dlt >= 1; dlt >>= 1)
-    {
-        tot += __shfl_xor(tot, dlt, 64);
-        dups += __shfl_xor(dups, dlt, 64);
-    }
+    const u32 tot = wave_reduce_add_u32(my_claims), dups = wave_reduce_add_u32(my_dups);
     if ((threadIdx.x & 63) == 0 && tot)
         atomicAdd(&t.ctrl->n_keys, (unsigned long long)tot);
     if ((threadIdx.x & 63) == 0 && dups && t.ctrl->pad == 0)
         atomicOr(&t.ctrl->pad, 1u);
-#pragma unroll
-    for (int dlt = 32; dlt >= 1; dlt >>= 1)
-    {
-        const u64 o = __shfl_xor(my_max, dlt, 64);
-        my_max = o > my_max ? o : my_max;
-    }
+    my_max = wave_reduce_max_u64(my_max);
     if ((threadIdx.x & 63) == 0 && my_max)
         atomicMax(&t.ctrl->max_key, (unsigned long long)my_max);
 }
@@ -370,8 +424,7 @@ __global__ __launch_bounds__(JT) void k_join_merge_claims(JoinTable t, int maps_
 {
     for (u64 s = (u64)blockIdx.x * JT + threadIdx.x; s <= t.capacity; s += (u64)gridDim.x * JT)
     {
-        const bool occupied = s == t.capacity ? (t.ctrl->has_zero != 0) : (t.kv[2 * s] != 0);
-        if (!occupied)
+        if (!jt_occupied(t, s))
             continue;
         const u64 claim = t.kv[2 * s + 1];
         if (maps_all)
@@ -426,7 +479,7 @@ __global__ __launch_bounds__(JT) void k_join_finalize_values(JoinTable t, int ma
     const PfView pf = jt_pf_view(t); // every insert kernel has finished: max_key is final
     for (u64 s = (u64)blockIdx.x * JT + threadIdx.x; s <= t.capacity; s += (u64)gridDim.x * JT)
     {
-        const bool occupied = s == t.capacity ? (t.ctrl->has_zero != 0) : (t.kv[2 * s] != 0);
+        const bool occupied = jt_occupied(t, s);
         u64 v = NO_ROW;
         if (occupied && s != t.capacity && t.pf)
         {
@@ -449,7 +502,7 @@ __global__ __launch_bounds__(JT) void k_join_finalize_values(JoinTable t, int ma
                 if (c == 1)
                     v = t.rowids[t.start[s]];
                 else
-                    v = JV_MULTI | ((u64)(c < JV_CNT_SAT ? c : JV_CNT_SAT) << 40) | (t.start[s] & JV_START_MASK);
+                    v = jv_pack(c, t.start[s]);
             }
         }
         t.kv[2 * s + 1] = v;
@@ -478,12 +531,7 @@ __global__ __launch_bounds__(JT) void k_join_max_key(const u64 * __restrict__ ke
     u64 m = 0;
     for (u64 i = (u64)blockIdx.x * JT + threadIdx.x; i < n; i += (u64)gridDim.x * JT)
         m = keys[i] > m ? keys[i] : m;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-    {
-        const u64 x = __shfl_xor(m, o);
-        m = x > m ? x : m;
-    }
+    m = wave_reduce_max_u64(m);
     if ((threadIdx.x & 63) == 0 && m)
         atomicMax(out, (unsigned long long)m);
 }
@@ -495,6 +543,64 @@ __global__ __launch_bounds__(JT) void k_fill_u64(u64 * p, u64 n, u64 v)
 }
 
 enum { PV_ALL_INNER, PV_ALL_LEFT, PV_ANY_LEFT, PV_SEMI_LEFT, PV_ANTI_LEFT, PV_ANY_INNER, PV_ONCE_RIGHT, PV_ANTI_RIGHT };
+
+// addNotFoundRow<add_missing>: a left row without a match is still a row of the result -- with a default right row (payload 0) for
+// LEFT ALL / LEFT ANY, as the kept row of ANTI
+__device__ __forceinline__ bool pv_miss_counts(int variant) { return variant == PV_ALL_LEFT || variant == PV_ANY_LEFT || variant == PV_ANTI_LEFT; }
+// What one left key adds to a fused probe's count before its right rows are looked at: a miss counts itself where misses count; a hit
+// of ANTI adds nothing.  -> true when the matched right rows are to be added (a row with a NULL key finds nothing,
+// HashJoinMethodsImpl.h:451-452, but is still a left row of LEFT / ANTI joins: callers pass found = false for it)
+__device__ __forceinline__ bool pv_account(int variant, bool found, u64 & cnt)
+{
+    if (!found)
+    {
+        cnt += pv_miss_counts(variant) ? 1 : 0;
+        return false;
+    }
+    return variant != PV_ANTI_LEFT;
+}
+
+// a filter-only probe's kept rows -> ctrl->n_out: one atomic per wave that kept any
+__device__ __forceinline__ void join_add_kept(JoinCtrl * ctrl, u32 kept)
+{
+    kept = wave_reduce_add_u32(kept);
+    if ((threadIdx.x & 63) == 0 && kept)
+        atomicAdd((unsigned long long *)&ctrl->n_out, (unsigned long long)kept);
+}
+
+// A JT-thread workgroup's {count, sum} in a fixed order: lane partials -> wave (shuffle tree) -> workgroup (LDS, wave order).  `sbits`
+// carries the sum -- an integer, or the bits of a Float64 (FLOAT).  -> true in thread 0, whose cnt / sbits then hold the workgroup's.
+template <bool FLOAT>
+__device__ __forceinline__ bool join_fold_workgroup(u64 & cnt, u64 & sbits)
+{
+    __shared__ u64 sh_c[JT / 64], sh_s[JT / 64];
+    cnt = wave_reduce_add_u64(cnt);
+    if constexpr (FLOAT)
+        sbits = (u64)__double_as_longlong(wave_reduce_add_f64(__longlong_as_double((long long)sbits)));
+    else
+        sbits = wave_reduce_add_u64(sbits);
+    if ((threadIdx.x & 63) == 0)
+    {
+        sh_c[threadIdx.x >> 6] = cnt;
+        sh_s[threadIdx.x >> 6] = sbits;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0)
+        return false;
+    u64 c = 0, si = 0;
+    double sf = 0.0;
+    for (u32 w = 0; w < JT / 64; ++w)
+    {
+        c += sh_c[w];
+        if constexpr (FLOAT)
+            sf += __longlong_as_double((long long)sh_s[w]);
+        else
+            si += sh_s[w];
+    }
+    cnt = c;
+    sbits = FLOAT ? (u64)__double_as_longlong(sf) : si;
+    return true;
+}
 
 // probe pass 0 (INNER ANY only): every matching left row bids for its right cell with its sequence number
 template <bool PF>
@@ -521,7 +627,6 @@ __global__ __launch_bounds__(JT) void k_join_probe_bid(JoinTable t, const void *
 // key loads, then four prefilter words, then four home cells in flight.  One row per lane and a probe loop per row left the kernel
 // parked on s_waitcnt (2.55 ms for 1e8 probes of a 1e6-key table that needs 0.5 ms of traffic); only a row whose home cell holds
 // another key walks on, by itself.
-typedef u64 jpc_v2 __attribute__((ext_vector_type(2)));
 template <bool PF>
 __global__ __launch_bounds__(JT) void k_join_probe_count(JoinTable t, int variant, const void * __restrict__ keys, int key_type,
                                                          const u8 * __restrict__ null_map, u64 n, u64 seq_base, int slots_known,
@@ -582,13 +687,13 @@ __global__ __launch_bounds__(JT) void k_join_probe_count(JoinTable t, int varian
                 for (int q = 0; q < R; ++q)
                     look[q] = look[q] && ((pw[q] >> (pos[q] & 31)) & 1u);
             }
-            jpc_v2 c[R], c2[R];
+            jv2 c[R], c2[R];
 #pragma unroll
             for (int q = 0; q < R; ++q)
             {
                 home[q] = dev_intHash64(key[q]) & mask;
-                c[q] = *(const jpc_v2 *)(t.kv + 2 * (look[q] ? home[q] : 0));
-                c2[q] = *(const jpc_v2 *)(t.kv + 2 * (look[q] ? (home[q] + 1) & mask : 0)); // the next cell too: nearly always the same 64-byte sector
+                c[q] = *(const jv2 *)(t.kv + 2 * (look[q] ? home[q] : 0));
+                c2[q] = *(const jv2 *)(t.kv + 2 * (look[q] ? (home[q] + 1) & mask : 0)); // the next cell too: nearly always the same 64-byte sector
             }
 #pragma unroll
             for (int q = 0; q < R; ++q)
@@ -610,10 +715,11 @@ __global__ __launch_bounds__(JT) void k_join_probe_count(JoinTable t, int varian
                     }
                     else if (c2[q].x != 0)
                     {
-                        u64 sl = (home[q] + 2) & mask; // other keys in both cells: the rest of the walk
+                        // other keys in both cells: the rest of the walk (open-coded: through jt_walk this kernel needs 2 more VGPRs)
+                        u64 sl = (home[q] + 2) & mask;
                         for (u64 step = 2; step < t.capacity; ++step)
                         {
-                            const jpc_v2 cc = *(const jpc_v2 *)(t.kv + 2 * sl);
+                            const jv2 cc = *(const jv2 *)(t.kv + 2 * sl);
                             if (cc.x == key[q])
                             {
                                 slot[q] = (u32)sl;
@@ -650,17 +756,7 @@ __global__ __launch_bounds__(JT) void k_join_probe_count(JoinTable t, int varian
             const u64 i = i0 + (u64)q * stride;
             const bool found = slot[q] != NO_SLOT;
             const u64 v = val[q];
-            u32 rows_here = 0; // RowRefList::rows of the matched cell
-            if (found)
-            {
-                if (!(v & JV_MULTI))
-                    rows_here = 1;
-                else
-                {
-                    const u64 cn = (v >> 40) & JV_CNT_SAT;
-                    rows_here = cn < JV_CNT_SAT ? (u32)cn : t.cnt[slot[q]];
-                }
-            }
+            const u32 rows_here = found ? jv_rows(t, v, slot[q]) : 0;
             u32 c = 0;
             u8 f = 0;
             switch (variant)
@@ -725,96 +821,21 @@ __global__ __launch_bounds__(JT) void k_join_probe_filter(JoinTable t, int anti,
             kept += f;
         }
     }
-#pragma unroll
-    for (int dlt = 32; dlt >= 1; dlt >>= 1)
-        kept += __shfl_xor(kept, dlt, 64);
-    if ((threadIdx.x & 63) == 0 && kept)
-        atomicAdd((unsigned long long *)&ctrl->n_out, (unsigned long long)kept);
+    join_add_kept(ctrl, kept);
 }
 
 // The same filter-only probe for DENSE 4-byte keys (dimension surrogate keys: the prefilter bitmap IS the key set) with the bitmap
-// staged in LDS.  From L2 the look-ups run at ~1.6e11/s chip-wide -- 64 lanes = 64 separate L2 requests -- i.e. 4.8 ms for the
-// 750 M lineorder rows of SSB against the 0.6 ms the keys and filter bytes take to stream; LDS serves the same random bit reads an
-// order of magnitude faster.  This kernel takes a key domain of one slice of JPL_SLICE_BITS bits (150 KiB); a larger one takes
-// k_join_probe_filter_lds_multi.  Four rows per lane and load: 16 bytes of keys, 4 null-map bytes, 4 filter bytes.
-static constexpr u32 JPL_SLICE_BITS = 150u * 1024u * 8u;
-template <bool HAS_NULL>
-__global__ __launch_bounds__(1024) void k_join_probe_filter_lds(const u32 * __restrict__ pf_words, u32 slice_bits, int anti, int has_zero, const u32 * __restrict__ keys,
-                                                                const u8 * __restrict__ null_map, u64 n, u8 * __restrict__ filter, JoinCtrl * __restrict__ ctrl)
-{
-    extern __shared__ __attribute__((aligned(16))) u32 jpl_bits[];
-    const u32 n_words = (slice_bits + 31) / 32;
-    for (u32 w = threadIdx.x; w < n_words; w += 1024)
-        jpl_bits[w] = pf_words[w];
-    __syncthreads();
-    auto found_in_slice = [&](u32 k) -> u32 {
-        const bool in = k != 0 && k < slice_bits;
-        const u32 r = in ? k : 0;
-        const u32 bit = (jpl_bits[r >> 5] >> (r & 31)) & 1u;
-        return (in ? bit : 0u) | ((k == 0 && has_zero) ? 1u : 0u); // the zero key lives out of line (HashTable.h:874-898)
-    };
-    typedef u32 v4u __attribute__((ext_vector_type(4)));
-    const u64 nq = n / 4; // whole groups of four rows; the last n % 4 rows are done at the end
-    const u64 q_per_wg = (nq + gridDim.x - 1) / gridDim.x;
-    const u64 q0 = (u64)blockIdx.x * q_per_wg, q1 = q0 + q_per_wg < nq ? q0 + q_per_wg : nq;
-    u32 kept = 0;
-    constexpr int U = 4;
-    for (u64 qb = q0 + threadIdx.x; qb < q1; qb += (u64)U * 1024)
-    {
-        v4u kk[U];
-        u32 nm[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-        {
-            const u64 q = qb + (u64)u * 1024;
-            const u64 qc = q < q1 ? q : q1 - 1;
-            kk[u] = __builtin_nontemporal_load((const v4u *)keys + qc);
-            nm[u] = HAS_NULL ? __builtin_nontemporal_load((const u32 *)null_map + qc) : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-        {
-            const u64 q = qb + (u64)u * 1024;
-            u32 acc = 0;
-            const u32 k4[4] = {kk[u].x, kk[u].y, kk[u].z, kk[u].w};
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-            {
-                const bool ok = !HAS_NULL || ((nm[u] >> (8 * b)) & 0xffu) == 0; // HashJoinMethodsImpl.h:451-452
-                acc |= (ok ? found_in_slice(k4[b]) : 0u) << (8 * b);
-            }
-            acc = anti ? acc ^ 0x01010101u : acc; // :515-519, :535-536
-            if (q < q1)
-            {
-                kept += (u32)__popc(acc);
-                ((u32 *)filter)[q] = acc;
-            }
-        }
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (u32)(n & 3))
-    {
-        // the last n % 4 rows, against the whole bitmap in global memory
-        const u64 i = nq * 4 + threadIdx.x;
-        const u32 k = keys[i];
-        const bool ok = !(HAS_NULL && null_map[i]);
-        const bool found = ok && (k == 0 ? has_zero != 0 : (k < slice_bits && ((pf_words[k >> 5] >> (k & 31)) & 1u) != 0));
-        const u8 f = anti ? !found : found;
-        filter[i] = f;
-        kept += f;
-    }
-#pragma unroll
-    for (int dlt = 32; dlt >= 1; dlt >>= 1)
-        kept += __shfl_xor(kept, dlt, 64);
-    if ((threadIdx.x & 63) == 0 && kept)
-        atomicAdd((unsigned long long *)&ctrl->n_out, (unsigned long long)kept);
-}
-
-// The same probe for a key set of SEVERAL slices in ONE sweep over the rows.  One pass over all rows per slice would read the keys again
+// staged in LDS, a slice of JPL_SLICE_BITS bits (150 KiB) of the key domain at a time.  From L2 the look-ups run at ~1.6e11/s
+// chip-wide -- 64 lanes = 64 separate L2 requests -- i.e. 4.8 ms for the 750 M lineorder rows of SSB against the 0.6 ms the keys and
+// filter bytes take to stream; LDS serves the same random bit reads an order of magnitude faster.
+// A key set of one OR several slices is probed in ONE sweep over the rows.  One pass over all rows per slice would read the keys again
 // from HBM each time and read back and rewrite the filter bytes of the passes before; here a workgroup takes a PART of 64 Ki rows through
-// all slices before it moves on: the part's keys come from HBM once and from L2 / Infinity Cache for the other slices, the hit bits of a
-// thread's 64 rows wait in two registers between slices (a row's key lies in exactly one slice), and the filter bytes are written once,
-// after the last slice.  Between slices the workgroup reloads its 150 KiB of LDS from the bitmap (L2-resident); consecutive parts walk
-// the slices in opposite directions, so the slice a part ends with is the one the next part starts with.
+// all slices before it moves on: the part's keys (16 bytes = four rows per lane and load, plain loads) come from HBM once and from L2 /
+// Infinity Cache for the other slices, the hit bits of a thread's 64 rows wait in two registers between slices (a row's key lies in
+// exactly one slice), and the null-map bytes are read and the filter bytes written once, with the last slice.  Between slices the
+// workgroup reloads its 150 KiB of LDS from the bitmap (L2-resident); consecutive parts walk the slices in opposite directions, so the
+// slice a part ends with is the one the next part starts with -- a single slice is staged once per workgroup.
+static constexpr u32 JPL_SLICE_BITS = 150u * 1024u * 8u;
 template <bool HAS_NULL>
 __global__ __launch_bounds__(1024) void k_join_probe_filter_lds_multi(const u32 * __restrict__ pf_words, u32 dense_bits, u32 n_slices, int anti, int has_zero,
                                                                       const u32 * __restrict__ keys, const u8 * __restrict__ null_map, u64 n,
@@ -919,11 +940,7 @@ __global__ __launch_bounds__(1024) void k_join_probe_filter_lds_multi(const u32 
         filter[i] = f;
         kept += f;
     }
-#pragma unroll
-    for (int dlt = 32; dlt >= 1; dlt >>= 1)
-        kept += __shfl_xor(kept, dlt, 64);
-    if ((threadIdx.x & 63) == 0 && kept)
-        atomicAdd((unsigned long long *)&ctrl->n_out, (unsigned long long)kept);
+    join_add_kept(ctrl, kept);
 }
 
 // probe pass 2b: where does max_joined_block_rows cut?  offsets are inclusive cumulative counts.
@@ -969,12 +986,12 @@ __global__ __launch_bounds__(JT) void k_join_emit(JoinTable t, int variant, cons
             right_rowid[base] = NO_ROW; // default row (addNotFoundRow -> insertDefault)
             continue;
         }
-        if (!(v & JV_MULTI))
+        if (jv_single(v))
         {
             right_rowid[base] = v;
             continue;
         }
-        const u64 * run = t.rowids + (v & JV_START_MASK);
+        const u64 * run = jv_run(t, v);
         for (u32 k = 0; k < c; ++k)
             right_rowid[base + k] = run[k];
     }
@@ -995,7 +1012,7 @@ __global__ __launch_bounds__(JT) void k_join_mark_used(const u64 * __restrict__ 
         const u64 b = r >> 32;
         if (r == NO_ROW || b >= n_blocks)
             continue; // the default row of a LEFT / FULL miss
-        const u64 f = block_base[b] + (r & 0xFFFFFFFFull);
+        const u64 f = join_flat_row(block_base, n_blocks, r);
         if (f < total_rows)
             used[f] = 1; // plain store: every writer stores the same value
     }
@@ -1013,24 +1030,14 @@ __global__ __launch_bounds__(JT) void k_join_mark_used_keys(JoinTable t, const u
             continue;
         const u64 v = val_of_left[i];
         auto mark = [&](u64 r) {
-            const u64 b = r >> 32;
-            if (b < n_blocks)
+            if ((r >> 32) < n_blocks)
             {
-                const u64 f = block_base[b] + (r & 0xFFFFFFFFull);
+                const u64 f = join_flat_row(block_base, n_blocks, r);
                 if (f < total_rows)
                     used[f] = 1;
             }
         };
-        if (!(v & JV_MULTI))
-        {
-            mark(v);
-            continue;
-        }
-        const u64 c0 = (v >> 40) & JV_CNT_SAT;
-        const u32 c = c0 < JV_CNT_SAT ? (u32)c0 : t.cnt[slot];
-        const u64 * run = t.rowids + (v & JV_START_MASK);
-        for (u32 k = 0; k < c; ++k)
-            mark(run[k]);
+        jv_for_each_row(t, v, jv_rows(t, v, slot), mark);
     }
 }
 
@@ -1245,6 +1252,23 @@ struct JoinPart
     u64 * keys2, * words2; // the second level: every tile sorted by bucket
     unsigned short * tidx; // [tiles][PB + 1] where each bucket's run starts inside its tile
 };
+// The scratch of one plan: an 8-word header, then what `carve(JoinCarve &)` takes.  -> *header, zeroed on the stream.
+template <typename Fn>
+static int join_scratch(chgpu_ctx * ctx, u64 ** header, Fn && carve)
+{
+    auto run = [&](uintptr_t base) {
+        JoinCarve c{base};
+        *header = c.take<u64>(8);
+        carve(c);
+        return c.at - base;
+    };
+    void * scratch = nullptr;
+    CHGPU_TRY(chgpu_scratch(ctx, run(0), &scratch));
+    run((uintptr_t)scratch);
+    CHGPU_HIP(hipMemsetAsync(*header, 0, 64, ctx->stream));
+    return CHGPU_OK;
+}
+
 // PB: second-level buckets per tile (0: the first level alone)
 static JoinPart join_part_carve(JoinCarve & c, u64 n, u32 G, u32 P, u32 PB, bool word)
 {
@@ -1320,10 +1344,138 @@ struct JoinSliceFn2 : JoinBucket2Fn
 };
 static constexpr u32 JBS_LG_CELLS = 12, JBS_CELLS = 1u << JBS_LG_CELLS, JBS_TILE = jpart_sort_tile(true), JBS_LG_P1 = 6, JBS_THREADS = 512, JBS_MAX_OVERFLOW = 1u << 20;
 
+// The slice geometry of a table of `cap` cells: JSL_P1 first-level partitions of 2^lg_p2 slices each, PB second-level buckets per tile
+// (a tile may span two first-level partitions).  fits: between one slice and 128 per partition.
+struct JoinSliceGeom
+{
+    bool fits;
+    u32 lg_cap, lg_p2, P1, PB;
+};
+static JoinSliceGeom join_slice_geom(u64 cap)
+{
+    JoinSliceGeom g{};
+    g.lg_cap = jceil_log2(cap);
+    g.fits = g.lg_cap >= JBS_LG_CELLS + JBS_LG_P1 && g.lg_cap <= JBS_LG_CELLS + JBS_LG_P1 + 7;
+    g.lg_p2 = g.fits ? g.lg_cap - JBS_LG_CELLS - JBS_LG_P1 : 0;
+    g.P1 = 1u << JBS_LG_P1;
+    g.PB = 2u << g.lg_p2;
+    return g;
+}
+
 __global__ __launch_bounds__(256) void k_join_iota(u64 * __restrict__ out, u64 n)
 {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
         out[i] = i; // row id of block 0: (0 << 32) | row
+}
+
+// ---------------------------------------------------------------------------------------------
+// The work unit of the two-level partition, for the kernels that take a table slice by slice (k_join_build_slices, k_join_probe_lds):
+// slice r2 = second-level region p2 of first-level partition p1; its rows are among [rb, re) of the partitioned array, tile-sorted by
+// second-level bucket; its cells start at cell `slice` of the table.  Both kernels use one geometry: JBS_CELLS cells per slice, JSL_P1
+// first-level partitions.
+// ---------------------------------------------------------------------------------------------
+static constexpr u32 JSL_P1 = 1u << JBS_LG_P1;
+struct SliceUnit
+{
+    u32 p1, p2;
+    u64 rb, re, slice;
+};
+
+// s_off[p] = where first-level partition p starts (s_off[JSL_P1] = n); visible after the caller's next barrier
+__device__ __forceinline__ void jpart_stage_offsets(u64 * s_off, const u64 * __restrict__ off1, u32 G, u64 n, u32 threads)
+{
+    for (u32 p = threadIdx.x; p <= JSL_P1; p += threads)
+        s_off[p] = p < JSL_P1 ? off1[(u64)p * G] : n;
+}
+
+// The workgroup takes the next unit number off the counter; `meanwhile` runs between the two barriers (what a kernel has to clear for
+// the new unit).  A number >= JSL_P1 << lg_p2: no unit is left (every workgroup reaches this exit).  The caller tests that itself and
+// then decodes the number with slice_unit: with the test in here, returned as a bool, both kernels needed 8-10 more VGPRs, and
+// k_join_probe_lds<false> lost an occupancy step.
+template <typename Fn>
+__device__ __forceinline__ u32 slice_unit_claim(u32 * unit_ctr, Fn && meanwhile)
+{
+    __shared__ u32 sh_unit;
+    __syncthreads(); // everyone is done with the previous unit (its number and what it kept in LDS)
+    if (threadIdx.x == 0)
+        sh_unit = atomicAdd(unit_ctr, 1u);
+    meanwhile();
+    __syncthreads();
+    return sh_unit;
+}
+__device__ __forceinline__ SliceUnit slice_unit(u32 r2, const u64 * s_off, u32 lg_p2)
+{
+    SliceUnit u;
+    u.p1 = r2 >> lg_p2;
+    u.p2 = r2 & ((1u << lg_p2) - 1);
+    u.rb = s_off[u.p1];
+    u.re = s_off[u.p1 + 1];
+    u.slice = (u64)r2 * JBS_CELLS;
+    return u;
+}
+
+// The unit's run inside tile `tile` (of TILE rows, sorted by k_rp_tilesort_keys into PB buckets): rows [start, start + len) of the tile.
+// A tile's buckets count from the first-level partition that owns the tile's first row: the largest p with s_off[p] <= row0 (empty
+// partitions share their start with the next one: the largest such p is the owner).  A tile spanning three partitions has no bucket for
+// this unit (len = 0): k_rp_tilesort_keys raised the stray flag and the host discards the run.
+__device__ __forceinline__ void jpart_tile_run(const u64 * s_off, const SliceUnit & u, u32 tile, u32 TILE, const unsigned short * __restrict__ tile_index, u32 PB, u32 & start,
+                                               u32 & len)
+{
+    const u64 row0 = (u64)tile * TILE;
+    u32 lo = 0, hi = JSL_P1 - 1;
+    while (lo < hi)
+    {
+        const u32 mid = (lo + hi + 1) >> 1;
+        if (s_off[mid] <= row0)
+            lo = mid;
+        else
+            hi = mid - 1;
+    }
+    const u32 bucket = (u.p1 - lo) * (PB >> 1) + u.p2;
+    start = len = 0;
+    if (bucket < PB)
+    {
+        const u32 a = tile_index[(u64)tile * (PB + 1) + bucket], b = tile_index[(u64)tile * (PB + 1) + bucket + 1];
+        start = a;
+        len = b - a;
+    }
+}
+
+// A wave's tiles are tile0, tile0 + stride, ...: lane k fetches the run of the k-th of them, `left` in all (one round trip for up to 64
+// tiles instead of one per tile) ...
+__device__ __forceinline__ void jpart_lane_runs(const u64 * s_off, const SliceUnit & u, u32 tile0, u32 stride, u32 left, u32 TILE, const unsigned short * __restrict__ tile_index,
+                                                u32 PB, u32 & st_l, u32 & ln_l)
+{
+    st_l = ln_l = 0;
+    const u32 lane = threadIdx.x & 63;
+    if (lane < left)
+        jpart_tile_run(s_off, u, tile0 + lane * stride, TILE, tile_index, PB, st_l, ln_l);
+}
+// ... and every lane reads run k out of lane k: its first row in the partitioned array and its length (k >= nk: no rows, at a valid address)
+__device__ __forceinline__ void jpart_run_of(u32 st_l, u32 ln_l, u32 k, u32 nk, u32 tile0, u32 stride, u32 TILE, u64 & row, u32 & len)
+{
+    const u32 kk = k < nk ? k : nk - 1;
+    const u32 st = (u32)__builtin_amdgcn_readlane((int)st_l, (int)kk);
+    len = k < nk ? (u32)__builtin_amdgcn_readlane((int)ln_l, (int)kk) : 0;
+    row = (u64)(tile0 + kk * stride) * TILE + st;
+}
+
+// Claims a cell for `want` in a slice staged in LDS, whose key words lie STRIDE words apart: compare-and-swap, linear probing from cell c
+// up to cell `end`.  c is left at the cell that answered; what happens to a chain that runs out of cells is the caller's policy.
+enum { LDS_CLAIMED, LDS_DUPLICATE, LDS_RAN_OUT };
+template <u32 STRIDE>
+__device__ __forceinline__ int lds_claim(u64 * keyw, u32 & c, u32 end, u64 want)
+{
+    while (c < end)
+    {
+        const u64 old = atomicCAS((unsigned long long *)&keyw[STRIDE * c], 0ull, (unsigned long long)want);
+        if (old == 0)
+            return LDS_CLAIMED;
+        if (old == want)
+            return LDS_DUPLICATE;
+        ++c;
+    }
+    return LDS_RAN_OUT;
 }
 
 // flags[0] = a duplicate key was met, [1] = overflow entries, [2] = the overflow list was too short
@@ -1331,16 +1483,13 @@ __global__ __launch_bounds__(JBS_THREADS) void k_join_build_slices(JoinTable t, 
                                                                    u32 lg_p2, const unsigned short * __restrict__ tile_index, u32 * __restrict__ unit_ctr, u32 * __restrict__ flags,
                                                                    u64 * __restrict__ ovf_keys, u64 * __restrict__ ovf_rids)
 {
-    typedef u64 bv2 __attribute__((ext_vector_type(2)));
     extern __shared__ __attribute__((aligned(16))) unsigned char jbs_lds[];
     u64 * ck = (u64 *)jbs_lds;       // [JBS_CELLS] keys
     u64 * cv = ck + JBS_CELLS;       // [JBS_CELLS] row ids
-    constexpr u32 P1 = 1u << JBS_LG_P1, NW = JBS_THREADS / 64;
-    __shared__ u64 s_off[P1 + 1];
-    __shared__ u32 sh_unit;
-    const u32 P2 = 1u << lg_p2, R2 = P1 << lg_p2, PB = 2 * P2;
-    for (u32 p = threadIdx.x; p <= P1; p += JBS_THREADS)
-        s_off[p] = p < P1 ? off1[(u64)p * G] : n;
+    constexpr u32 NW = JBS_THREADS / 64;
+    __shared__ u64 s_off[JSL_P1 + 1];
+    const u32 PB = 2u << lg_p2;
+    jpart_stage_offsets(s_off, off1, G, n, JBS_THREADS);
     const u32 lane = threadIdx.x & 63;
     const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const u64 mask = t.capacity - 1;
@@ -1349,38 +1498,23 @@ __global__ __launch_bounds__(JBS_THREADS) void k_join_build_slices(JoinTable t, 
     bool dup = false;
     for (;;)
     {
-        __syncthreads(); // the previous slice has been written out
-        if (threadIdx.x == 0)
-            sh_unit = atomicAdd(unit_ctr, 1u);
-        for (u32 c = threadIdx.x; c < JBS_CELLS; c += JBS_THREADS)
-            ck[c] = 0;
-        __syncthreads();
-        const u32 r2 = sh_unit;
-        if (r2 >= R2)
-            break; // (every workgroup reaches this exit)
-        const u32 p1 = r2 >> lg_p2, p2 = r2 & (P2 - 1);
-        const u64 rb = s_off[p1], re = s_off[p1 + 1];
-        const u64 slice = (u64)r2 * JBS_CELLS;
-        if (rb != re)
+        // (the first barrier in there: the previous slice has been written out)
+        const u32 r2 = slice_unit_claim(unit_ctr, [&] {
+            for (u32 c = threadIdx.x; c < JBS_CELLS; c += JBS_THREADS)
+                ck[c] = 0;
+        });
+        if (r2 >= (JSL_P1 << lg_p2))
+            break;
+        const SliceUnit u = slice_unit(r2, s_off, lg_p2);
+        if (u.rb != u.re)
         {
-            const u32 t_lo = (u32)(rb / JBS_TILE), t_hi = (u32)((re - 1) / JBS_TILE);
+            const u32 t_lo = (u32)(u.rb / JBS_TILE), t_hi = (u32)((u.re - 1) / JBS_TILE);
             for (u32 tile = t_lo + wave; tile <= t_hi; tile += NW)
             {
                 const u64 row0 = (u64)tile * JBS_TILE;
-                u32 lo = 0, hi = P1 - 1; // the first-level partition that owns the tile's first row
-                while (lo < hi)
-                {
-                    const u32 mid = (lo + hi + 1) >> 1;
-                    if (s_off[mid] <= row0)
-                        lo = mid;
-                    else
-                        hi = mid - 1;
-                }
-                const u32 bucket = (p1 - lo) * P2 + p2;
-                if (bucket >= PB)
-                    continue; // (k_rp_tilesort_keys raised the stray flag)
-                const u32 a = tile_index[(u64)tile * (PB + 1) + bucket], b = tile_index[(u64)tile * (PB + 1) + bucket + 1];
-                for (u32 o = lane; o < b - a; o += 64)
+                u32 a, len;
+                jpart_tile_run(s_off, u, tile, JBS_TILE, tile_index, PB, a, len);
+                for (u32 o = lane; o < len; o += 64)
                 {
                     const u64 key = keys2[row0 + a + o], rid = rids2[row0 + a + o];
                     my_max = key > my_max ? key : my_max;
@@ -1396,35 +1530,26 @@ __global__ __launch_bounds__(JBS_THREADS) void k_join_build_slices(JoinTable t, 
                             dup = true;
                         continue;
                     }
-                    u32 c = (u32)((dev_intHash64(key) & mask) - slice);
-                    for (;;)
+                    u32 c = (u32)((dev_intHash64(key) & mask) - u.slice);
+                    const int claim = lds_claim<1>(ck, c, JBS_CELLS, key);
+                    if (claim == LDS_CLAIMED)
                     {
-                        if (c >= JBS_CELLS)
+                        cv[c] = rid; // nobody reads it before the barrier below
+                        ++inserted;
+                    }
+                    else if (claim == LDS_DUPLICATE)
+                        dup = true;
+                    else
+                    {
+                        // the chain leaves the slice: the row goes to the overflow list
+                        const u32 at = atomicAdd(&flags[1], 1u);
+                        if (at < JBS_MAX_OVERFLOW)
                         {
-                            // the chain leaves the slice: the row goes to the overflow list
-                            const u32 at = atomicAdd(&flags[1], 1u);
-                            if (at < JBS_MAX_OVERFLOW)
-                            {
-                                ovf_keys[at] = key;
-                                ovf_rids[at] = rid;
-                            }
-                            else
-                                flags[2] = 1;
-                            break;
+                            ovf_keys[at] = key;
+                            ovf_rids[at] = rid;
                         }
-                        const u64 old = atomicCAS((unsigned long long *)&ck[c], 0ull, (unsigned long long)key);
-                        if (old == 0)
-                        {
-                            cv[c] = rid; // nobody reads it before the barrier below
-                            ++inserted;
-                            break;
-                        }
-                        if (old == key)
-                        {
-                            dup = true;
-                            break;
-                        }
-                        ++c;
+                        else
+                            flags[2] = 1;
                     }
                 }
             }
@@ -1434,17 +1559,11 @@ __global__ __launch_bounds__(JBS_THREADS) void k_join_build_slices(JoinTable t, 
         for (u32 c = threadIdx.x; c < JBS_CELLS; c += JBS_THREADS)
         {
             const u64 k = ck[c];
-            __builtin_nontemporal_store(bv2{k, k ? cv[c] : 0ull}, (bv2 *)(t.kv + 2 * (slice + c)));
+            __builtin_nontemporal_store(jv2{k, k ? cv[c] : 0ull}, (jv2 *)(t.kv + 2 * (u.slice + c)));
         }
     }
-    u32 tot = inserted;
-#pragma unroll
-    for (int dlt = 32; dlt >= 1; dlt >>= 1)
-    {
-        tot += __shfl_xor(tot, dlt, 64);
-        const u64 o = __shfl_xor(my_max, dlt, 64);
-        my_max = o > my_max ? o : my_max;
-    }
+    const u32 tot = wave_reduce_add_u32(inserted);
+    my_max = wave_reduce_max_u64(my_max);
     if (lane == 0 && tot)
         atomicAdd(&t.ctrl->n_keys, (unsigned long long)tot);
     if (lane == 0 && my_max)
@@ -1500,30 +1619,23 @@ static int join_build_slices(chgpu_join * j, JoinTable & t, u32 * declined, u64 
     chgpu_ctx * ctx = j->ctx;
     const bool off = chgpu_opt(ctx, "tune_join_no_slice_build", 0) != 0;
     const u64 n = j->total_rows, cap = t.capacity;
-    const u32 lg_cap = jceil_log2(cap);
-    if (off || j->blocks.size() != 1 || j->blocks[0].valid || n < (1u << 20) || n + JBS_TILE + RP_SCATTER_SLACK >= (1ull << 32)
-        || lg_cap < JBS_LG_CELLS + JBS_LG_P1 || lg_cap > JBS_LG_CELLS + JBS_LG_P1 + 7 || ((uintptr_t)j->blocks[0].keys % 16) != 0)
+    const JoinSliceGeom geom = join_slice_geom(cap);
+    if (off || j->blocks.size() != 1 || j->blocks[0].valid || n < (1u << 20) || n + JBS_TILE + RP_SCATTER_SLACK >= (1ull << 32) || !geom.fits
+        || ((uintptr_t)j->blocks[0].keys % 16) != 0)
         return CHGPU_ERR_NOT_IMPLEMENTED;
-    const u32 lg_p2 = lg_cap - JBS_LG_CELLS - JBS_LG_P1, P1 = 1u << JBS_LG_P1, PB = 2u << lg_p2;
+    const u32 lg_cap = geom.lg_cap, lg_p2 = geom.lg_p2, P1 = geom.P1, PB = geom.PB;
     const JoinSliceFn1 fn1{{cap - 1, lg_cap - JBS_LG_P1}};
     const JoinSliceFn2 fn2{{cap - 1, JBS_LG_CELLS, lg_p2}};
     const u32 G = (u32)ctx->num_cus;
     u64 * flags_dev, * rid0, * ovf_keys, * ovf_rids; // flags_dev: [2] unit counter | stray flag, [3..4] flags[0..3]
     JoinPart part;
-    auto carve = [&](uintptr_t base) {
-        JoinCarve c{base};
-        flags_dev = c.take<u64>(8);
+    CHGPU_TRY(join_scratch(ctx, &flags_dev, [&](JoinCarve & c) {
         rid0 = c.take<u64>(n);
         ovf_keys = c.take<u64>(JBS_MAX_OVERFLOW);
         ovf_rids = c.take<u64>(JBS_MAX_OVERFLOW);
         part = join_part_carve(c, n, G, P1, PB, true);
-        return c.at - base;
-    };
-    void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, carve(0), &scratch));
-    carve((uintptr_t)scratch);
+    }));
     u32 * unit_ctr = (u32 *)(flags_dev + 2), * stray = unit_ctr + 1, * flags = (u32 *)(flags_dev + 3);
-    CHGPU_HIP(hipMemsetAsync(flags_dev, 0, 64, ctx->stream));
     hipLaunchKernelGGL(k_join_iota, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, rid0, n);
     CHGPU_TRY(join_partition2<true>(ctx, part, j->blocks[0].keys, rid0, n, P1, fn1, PB, fn2, stray));
     {
@@ -1805,8 +1917,7 @@ __global__ __launch_bounds__(JT) void k_join_flatten(const u64 * __restrict__ ro
     for (u64 i = (u64)blockIdx.x * JT + threadIdx.x; i < n; i += (u64)gridDim.x * JT)
     {
         const u64 r = rowid[i];
-        const u64 b = r >> 32;
-        out[i] = (r == NO_ROW || b >= n_blocks) ? NO_ROW : block_base[b] + (r & 0xFFFFFFFFull);
+        out[i] = (r == NO_ROW || (r >> 32) >= n_blocks) ? NO_ROW : join_flat_row(block_base, n_blocks, r);
     }
 }
 
@@ -1853,6 +1964,17 @@ extern "C" int chgpu_join_total_rows(chgpu_join * j, uint64_t * rows, uint64_t *
     return CHGPU_OK;
 }
 
+// what a probe does per left row, from the join's kind and strictness
+static int join_probe_variant(const chgpu_join * j)
+{
+    if (j->strictness == CHGPU_STRICT_ALL) return jf_left_kind(j) == CHGPU_JOIN_LEFT ? PV_ALL_LEFT : PV_ALL_INNER;
+    if (jf_right_once(j)) return PV_ONCE_RIGHT;
+    if (j->kind == CHGPU_JOIN_RIGHT) return PV_ANTI_RIGHT;
+    if (j->strictness == CHGPU_STRICT_SEMI) return PV_SEMI_LEFT;
+    if (j->strictness == CHGPU_STRICT_ANTI) return PV_ANTI_LEFT;
+    return jf_left_kind(j) == CHGPU_JOIN_LEFT ? PV_ANY_LEFT : PV_ANY_INNER;
+}
+
 // LEFT SEMI / LEFT ANTI without right columns: the filter bytes and the number of kept rows alone
 static int join_probe_filter_only(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * null_map, bool anti, chgpu_col ** filter_out, uint64_t * n_out,
                                   uint64_t * n_left_consumed)
@@ -1863,30 +1985,20 @@ static int join_probe_filter_only(chgpu_join * j, const chgpu_col * key_col, con
     CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, n, &fcol));
     hipError_t e = hipMemsetAsync(&j->t.ctrl->n_out, 0, sizeof(u64), ctx->stream);
     const u8 * nm = null_map ? (const u8 *)null_map->data : nullptr;
-    // dense 4-byte keys whose key set fits a few LDS slices: k_join_probe_filter_lds(_multi) (the tail of a bitmap beyond max_key is zero)
+    // dense 4-byte keys whose key set fits a few LDS slices: k_join_probe_filter_lds_multi (the tail of a bitmap beyond max_key is zero)
     const bool no_lds_filter = chgpu_opt(ctx, "tune_join_no_lds_filter", 0) != 0;
     const u64 dense_bits = (j->max_key + 32) / 32 * 32;
     if (e == hipSuccess && !no_lds_filter && j->t.pf && j->max_key <= j->t.pf_mask && chgpu_type_size(j->key_type) == 4 && dense_bits <= 4ull * JPL_SLICE_BITS
         && n >= (1u << 20) && (uintptr_t)key_col->data % 16 == 0 && (!null_map || (uintptr_t)null_map->data % 4 == 0))
     {
+        // one sweep, every part of the rows through all slices.  A single slice too: a kernel of its own for that case measured slower
+        // (profiles/join_filter_single_vs_multi.json)
         const u32 slices = (u32)((dense_bits + JPL_SLICE_BITS - 1) / JPL_SLICE_BITS);
-        if (slices > 1)
-        {
-            // several slices: one sweep, every part of the rows through all slices
-            auto kern = null_map ? k_join_probe_filter_lds_multi<true> : k_join_probe_filter_lds_multi<false>;
-            e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(JPL_SLICE_BITS / 8));
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(kern, dim3((u32)ctx->num_cus), dim3(1024), (size_t)(JPL_SLICE_BITS / 8), ctx->stream, (const u32 *)j->t.pf, (u32)dense_bits, slices,
-                                   anti ? 1 : 0, j->has_zero ? 1 : 0, (const u32 *)key_col->data, nm, n, (u8 *)fcol->data, j->t.ctrl);
-        }
-        else
-        {
-            auto kern = null_map ? k_join_probe_filter_lds<true> : k_join_probe_filter_lds<false>;
-            e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(JPL_SLICE_BITS / 8));
-            if (e == hipSuccess)
-                hipLaunchKernelGGL(kern, dim3((u32)ctx->num_cus), dim3(1024), (size_t)dense_bits / 8, ctx->stream, (const u32 *)j->t.pf, (u32)dense_bits, anti ? 1 : 0,
-                                   j->has_zero ? 1 : 0, (const u32 *)key_col->data, nm, n, (u8 *)fcol->data, j->t.ctrl);
-        }
+        auto kern = null_map ? k_join_probe_filter_lds_multi<true> : k_join_probe_filter_lds_multi<false>;
+        e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(JPL_SLICE_BITS / 8));
+        if (e == hipSuccess)
+            hipLaunchKernelGGL(kern, dim3((u32)ctx->num_cus), dim3(1024), (size_t)(JPL_SLICE_BITS / 8), ctx->stream, (const u32 *)j->t.pf, (u32)dense_bits, slices,
+                               anti ? 1 : 0, j->has_zero ? 1 : 0, (const u32 *)key_col->data, nm, n, (u8 *)fcol->data, j->t.ctrl);
     }
     else if (e == hipSuccess)
     {
@@ -1936,13 +2048,7 @@ extern "C" int chgpu_join_probe(chgpu_join * j, const chgpu_col * key_col, const
     if (filter_out) *filter_out = nullptr;
     if (offsets_out) *offsets_out = nullptr;
     if (right_rowid_out) *right_rowid_out = nullptr;
-    int variant;
-    if (j->strictness == CHGPU_STRICT_ALL) variant = jf_left_kind(j) == CHGPU_JOIN_LEFT ? PV_ALL_LEFT : PV_ALL_INNER;
-    else if (jf_right_once(j)) variant = PV_ONCE_RIGHT;
-    else if (j->kind == CHGPU_JOIN_RIGHT) variant = PV_ANTI_RIGHT;
-    else if (j->strictness == CHGPU_STRICT_SEMI) variant = PV_SEMI_LEFT;
-    else if (j->strictness == CHGPU_STRICT_ANTI) variant = PV_ANTI_LEFT;
-    else variant = jf_left_kind(j) == CHGPU_JOIN_LEFT ? PV_ANY_LEFT : PV_ANY_INNER;
+    const int variant = join_probe_variant(j);
     if (!need_repl)
         max_joined_block_rows = 0; // the early stop only exists for need_replication (HashJoinMethodsImpl.h:434-444)
 
@@ -2061,40 +2167,6 @@ extern "C" int chgpu_join_probe(chgpu_join * j, const chgpu_col * key_col, const
 // Every lane keeps R rows in flight (the table and payload reads are dependent random accesses); the {key, value} cell is fetched
 // with one 16-byte load.
 // ---------------------------------------------------------------------------------------------
-typedef u64 jv2 __attribute__((ext_vector_type(2)));
-
-template <bool PF>
-__device__ __forceinline__ bool jt_find_value(const JoinTable & t, const PfView & pf, u64 key, u64 & value, u32 & slot_out)
-{
-    if (key == 0)
-    {
-        if (!t.ctrl->has_zero)
-            return false;
-        slot_out = (u32)t.capacity;
-        value = t.kv[2 * t.capacity + 1];
-        return true;
-    }
-    if constexpr (PF)
-        if (!jt_pf_maybe(pf, key))
-            return false;
-    const u64 mask = t.capacity - 1;
-    u64 slot = dev_intHash64(key) & mask;
-    for (u64 step = 0; step < t.capacity; ++step)
-    {
-        const jv2 c = *(const jv2 *)(t.kv + 2 * slot);
-        if (c.x == key)
-        {
-            value = c.y;
-            slot_out = (u32)slot;
-            return true;
-        }
-        if (c.x == 0)
-            return false;
-        slot = (slot + 1) & mask;
-    }
-    return false;
-}
-
 // payload value at flat row f, widened to the 8-byte sum operand (integers sign/zero-extended, floats as Float64 bits)
 __device__ __forceinline__ u64 jload_payload(const void * p, int type, u64 f)
 {
@@ -2122,11 +2194,10 @@ __global__ __launch_bounds__(JT) void k_join_probe_agg(JoinTable t, int variant,
     constexpr int R = 4;
     u64 cnt = 0, isum = 0;
     double fsum = 0.0;
-    auto flat_of = [&](u64 rowid) -> u64 { return n_blocks == 1 ? (rowid & 0xFFFFFFFFull) : block_base[rowid >> 32] + (rowid & 0xFFFFFFFFull); };
     auto add_row = [&](u64 rowid) {
         if (!payload)
             return;
-        const u64 b = jload_payload(payload, payload_type, flat_of(rowid));
+        const u64 b = jload_payload(payload, payload_type, join_flat_row(block_base, n_blocks, rowid));
         if constexpr (FLOAT)
             fsum += __longlong_as_double((long long)b);
         else
@@ -2147,67 +2218,27 @@ __global__ __launch_bounds__(JT) void k_join_probe_agg(JoinTable t, int variant,
         }
         u64 val[R];
         u32 slot[R];
-        bool found[R];
 #pragma unroll
         for (int q = 0; q < R; ++q)
-            found[q] = ok[q] && jt_find_value<PF>(t, pf, key[q], val[q], slot[q]);
+            slot[q] = ok[q] ? jt_lookup<PF, true>(t, pf, key[q], val[q]) : NO_SLOT;
 #pragma unroll
         for (int q = 0; q < R; ++q)
         {
             if (i0 + (u64)q * stride >= n)
                 continue;
-            // a row with a NULL key finds nothing (HashJoinMethodsImpl.h:451-452) but is still a left row of LEFT / ANTI joins
-            if (!found[q])
-            {
-                // addNotFoundRow<add_missing>: a default right row (payload 0) for LEFT ALL / LEFT ANY, the kept row of ANTI
-                cnt += (variant == PV_ALL_LEFT || variant == PV_ANY_LEFT || variant == PV_ANTI_LEFT) ? 1 : 0;
+            if (!pv_account(variant, slot[q] != NO_SLOT, cnt))
                 continue;
-            }
-            if (variant == PV_ANTI_LEFT)
-                continue;
-            const u64 v = val[q];
-            if (!(v & JV_MULTI))
-            {
-                cnt += 1;
-                add_row(v);
-                continue;
-            }
-            const u64 c0 = (v >> 40) & JV_CNT_SAT;
-            const u32 c = c0 < JV_CNT_SAT ? (u32)c0 : t.cnt[slot[q]];
-            const u64 * run = t.rowids + (v & JV_START_MASK);
+            const u32 c = jv_rows(t, val[q], slot[q]);
             cnt += c;
-            for (u32 k = 0; k < c; ++k)
-                add_row(run[k]);
+            jv_for_each_row(t, val[q], c, add_row);
         }
     }
-    // fixed-order reduction: lane partials -> wave (shuffle tree) -> workgroup (LDS, wave order) -> one partial per workgroup
-    __shared__ u64 sh_c[JT / 64], sh_s[JT / 64];
-    cnt = wave_reduce_add_u64(cnt);
-    u64 sbits;
-    if constexpr (FLOAT)
-        sbits = (u64)__double_as_longlong(wave_reduce_add_f64(fsum));
-    else
-        sbits = wave_reduce_add_u64(isum);
-    if ((threadIdx.x & 63) == 0)
+    // one partial per workgroup
+    u64 sbits = FLOAT ? (u64)__double_as_longlong(fsum) : isum;
+    if (join_fold_workgroup<FLOAT>(cnt, sbits))
     {
-        sh_c[threadIdx.x >> 6] = cnt;
-        sh_s[threadIdx.x >> 6] = sbits;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        u64 c = 0, si = 0;
-        double sf = 0.0;
-        for (u32 w = 0; w < JT / 64; ++w)
-        {
-            c += sh_c[w];
-            if constexpr (FLOAT)
-                sf += __longlong_as_double((long long)sh_s[w]);
-            else
-                si += sh_s[w];
-        }
-        partials[2 * (u64)blockIdx.x] = c;
-        partials[2 * (u64)blockIdx.x + 1] = FLOAT ? (u64)__double_as_longlong(sf) : si;
+        partials[2 * (u64)blockIdx.x] = cnt;
+        partials[2 * (u64)blockIdx.x + 1] = sbits;
     }
 }
 
@@ -2271,14 +2302,9 @@ __global__ __launch_bounds__(JT) void k_join_fuse_payload(JoinTable t, const voi
     for (u64 s = (u64)blockIdx.x * JT + threadIdx.x; s <= t.capacity; s += (u64)gridDim.x * JT)
     {
         const u64 k = t.kv[2 * s];
-        const bool occupied = s == t.capacity ? (t.ctrl->has_zero != 0) : (k != 0);
         u64 v = 0;
-        if (occupied)
-        {
-            const u64 rowid = t.kv[2 * s + 1];
-            const u64 flat = n_blocks == 1 ? (rowid & 0xFFFFFFFFull) : block_base[rowid >> 32] + (rowid & 0xFFFFFFFFull);
-            v = jload_payload(payload, payload_type, flat);
-        }
+        if (jt_occupied(t, s))
+            v = jload_payload(payload, payload_type, join_flat_row(block_base, n_blocks, t.kv[2 * s + 1]));
         *(jv2 *)(kvp + 2 * s) = jv2{k, v};
     }
 }
@@ -2294,7 +2320,6 @@ __global__ __launch_bounds__(JT) void k_join_probe_agg_regions(JoinTable t, int 
         pf = jt_pf_view(t);
     __shared__ u64 sh_begin, sh_end;
     __shared__ u32 sh_more;
-    __shared__ u64 sh_c[JT / 64], sh_s[JT / 64];
     const u32 per = R / JPR_XCDS;
     // the queue tables and the region boundaries live in LDS: the lane that fetches a work item then makes no dependent global read
     __shared__ u32 s_qs[JPR_XCDS * (JPR_MAX_REGIONS / JPR_XCDS + 1)];
@@ -2305,7 +2330,6 @@ __global__ __launch_bounds__(JT) void k_join_probe_agg_regions(JoinTable t, int 
         s_roff[r] = r < R ? offsets[(u64)r * G] : n;
     const u32 xcc = __builtin_amdgcn_s_getreg(((4 - 1) << 11) | (0 << 6) | 20) & (JPR_XCDS - 1); // HW_REG_XCC_ID[3:0]
     u64 cnt = 0, isum = 0;
-    auto flat_of = [&](u64 rowid) -> u64 { return n_blocks == 1 ? (rowid & 0xFFFFFFFFull) : block_base[rowid >> 32] + (rowid & 0xFFFFFFFFull); };
     for (u32 dx = 0; dx < JPR_XCDS; ++dx)
     {
         const u32 x = (xcc + dx) & (JPR_XCDS - 1);
@@ -2388,28 +2412,10 @@ __global__ __launch_bounds__(JT) void k_join_probe_agg_regions(JoinTable t, int 
                     else if (cell[q].x != 0)
                     {
                         // the home cell belongs to another key: walk on (rare at the table's load factor; misses end at the first empty cell)
-                        u64 s2 = (slot0[q] + 1) & mask;
-                        for (u64 step = 1; step < t.capacity; ++step)
-                        {
-                            const jv2 c = *(const jv2 *)(t.kv + 2 * s2);
-                            if (c.x == key[q])
-                            {
-                                found = true;
-                                v = c.y;
-                                sl = (u32)s2;
-                                break;
-                            }
-                            if (c.x == 0)
-                                break;
-                            s2 = (s2 + 1) & mask;
-                        }
+                        sl = jt_walk<true>(t.kv, t.capacity, key[q], (slot0[q] + 1) & mask, 1, v);
+                        found = sl != NO_SLOT;
                     }
-                    if (!found)
-                    {
-                        cnt += (variant == PV_ALL_LEFT || variant == PV_ANY_LEFT || variant == PV_ANTI_LEFT) ? 1 : 0;
-                        continue;
-                    }
-                    if (variant == PV_ANTI_LEFT)
+                    if (!pv_account(variant, found, cnt))
                         continue;
                     if constexpr (FUSED)
                     {
@@ -2417,20 +2423,18 @@ __global__ __launch_bounds__(JT) void k_join_probe_agg_regions(JoinTable t, int 
                         isum += v; // the value word IS the payload
                         continue;
                     }
-                    if (!(v & JV_MULTI))
+                    if (jv_single(v))
                     {
+                        // its payload read waits for the other keys' (below)
                         cnt += 1;
                         pay[q] = payload != nullptr;
-                        pay_row[q] = flat_of(v);
+                        pay_row[q] = join_flat_row(block_base, n_blocks, v);
                         continue;
                     }
-                    const u64 c0 = (v >> 40) & JV_CNT_SAT;
-                    const u32 c = c0 < JV_CNT_SAT ? (u32)c0 : t.cnt[sl];
-                    const u64 * run = t.rowids + (v & JV_START_MASK);
+                    const u32 c = jv_rows(t, v, sl);
                     cnt += c;
                     if (payload)
-                        for (u32 k = 0; k < c; ++k)
-                            isum += jload_payload(payload, payload_type, flat_of(run[k]));
+                        jv_for_each_row(t, v, c, [&](u64 r) { isum += jload_payload(payload, payload_type, join_flat_row(block_base, n_blocks, r)); });
                 }
                 // the single-row matches' payload reads, issued back to back
                 if constexpr (!FUSED)
@@ -2441,24 +2445,10 @@ __global__ __launch_bounds__(JT) void k_join_probe_agg_regions(JoinTable t, int 
         }
     }
     // integer count and wrap-around sum: the order of the additions does not matter
-    cnt = wave_reduce_add_u64(cnt);
-    isum = wave_reduce_add_u64(isum);
-    if ((threadIdx.x & 63) == 0)
+    if (join_fold_workgroup<false>(cnt, isum))
     {
-        sh_c[threadIdx.x >> 6] = cnt;
-        sh_s[threadIdx.x >> 6] = isum;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        u64 c = 0, si = 0;
-        for (u32 w = 0; w < JT / 64; ++w)
-        {
-            c += sh_c[w];
-            si += sh_s[w];
-        }
-        atomicAdd(&result2[0], (unsigned long long)c);
-        atomicAdd(&result2[1], (unsigned long long)si);
+        atomicAdd(&result2[0], (unsigned long long)cnt);
+        atomicAdd(&result2[1], (unsigned long long)isum);
     }
 }
 
@@ -2484,26 +2474,23 @@ static int join_probe_agg_regions(chgpu_join * j, const chgpu_col * key_col, con
     u64 * total_dev; // [2..3] the result
     u32 * qstart;
     JoinPart part;
-    auto carve = [&](uintptr_t base) {
-        JoinCarve c{base};
-        total_dev = c.take<u64>(8);
+    CHGPU_TRY(join_scratch(ctx, &total_dev, [&](JoinCarve & c) {
         qstart = c.take<u32>(JPR_XCDS * (R / JPR_XCDS + 1) + JPR_XCDS);
         part = join_part_carve(c, n, G, R, 0, false);
-        return c.at - base;
-    };
-    void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, carve(0), &scratch));
-    carve((uintptr_t)scratch);
+    }));
     u32 * qctr = qstart + JPR_XCDS * (R / JPR_XCDS + 1);
     const u64 * offsets = part.offsets, * pkeys = part.keys1;
     unsigned long long * result2 = (unsigned long long *)(total_dev + 2);
-    CHGPU_HIP(hipMemsetAsync(total_dev, 0, 64, ctx->stream));
     // keys only, plain runs (k_rp_scatter; carried tails measured slower and wrote 1.26 GB for 0.8 GB of keys)
     CHGPU_TRY(join_partition<false>(ctx, part, (const u64 *)key_col->data, nullptr, n, R, fn));
     hipLaunchKernelGGL(k_jp_queues, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)offsets, G, R, n, qstart, qctr);
     const void * pp = right_payload ? right_payload->data : nullptr;
     const int pt = right_payload ? right_payload->type : CHGPU_U64;
     const u32 grid = (u32)ctx->num_cus * 4;
+    auto probe = [&](auto kern, const JoinTable & t) {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(JT), 0, ctx->stream, t, variant, (const u64 *)pkeys, n, (const u64 *)offsets, G, R, (const u32 *)qstart, qctr, pp, pt,
+                           (const u64 *)j->block_base_dev, (u64)j->blocks.size(), result2);
+    };
     const bool no_fuse = chgpu_opt(ctx, "tune_join_no_fused_payload", 0) != 0;
     if (j->unique_keys && right_payload && !j->t.pf && !no_fuse)
     {
@@ -2516,20 +2503,14 @@ static int join_probe_agg_regions(chgpu_join * j, const chgpu_col * key_col, con
                            (u64 *)fm);
         JoinTable ft = j->t;
         ft.kv = (u64 *)fm;
-        hipLaunchKernelGGL((k_join_probe_agg_regions<false, true>), dim3(grid), dim3(JT), 0, ctx->stream, ft, variant, (const u64 *)pkeys, n, (const u64 *)offsets, G, R,
-                           (const u32 *)qstart, qctr, pp, pt, (const u64 *)j->block_base_dev, (u64)j->blocks.size(), result2);
+        probe(k_join_probe_agg_regions<false, true>, ft);
         ctx->counters[6] += 5;
         const hipError_t e = hipGetLastError();
         chgpu_pool_free(ctx, fm, fcls); // reuse is stream-ordered behind the probe
         CHGPU_REQUIRE(e == hipSuccess, CHGPU_ERR_DEVICE, "join probe launch: %s", hipGetErrorString(e));
         return chgpu_read_back(ctx, result2, res, 16);
     }
-    if (j->t.pf)
-        hipLaunchKernelGGL(k_join_probe_agg_regions<true>, dim3(grid), dim3(JT), 0, ctx->stream, j->t, variant, (const u64 *)pkeys, n, (const u64 *)offsets, G, R,
-                           (const u32 *)qstart, qctr, pp, pt, (const u64 *)j->block_base_dev, (u64)j->blocks.size(), result2);
-    else
-        hipLaunchKernelGGL(k_join_probe_agg_regions<false>, dim3(grid), dim3(JT), 0, ctx->stream, j->t, variant, (const u64 *)pkeys, n, (const u64 *)offsets, G, R,
-                           (const u32 *)qstart, qctr, pp, pt, (const u64 *)j->block_base_dev, (u64)j->blocks.size(), result2);
+    probe(j->t.pf ? k_join_probe_agg_regions<true> : k_join_probe_agg_regions<false>, j->t);
     ctx->counters[6] += 4;
     CHGPU_HIP(hipGetLastError());
     return chgpu_read_back(ctx, result2, res, 16);
@@ -2545,6 +2526,7 @@ static int join_probe_agg_regions(chgpu_join * j, const chgpu_col * key_col, con
 // in LDS too, and the global table behind them.
 // ---------------------------------------------------------------------------------------------
 static constexpr u32 JPL2_LG_CELLS = 12, JPL2_CELLS = 1u << JPL2_LG_CELLS, JPL2_TAIL = 256, JPL2_TILE = jpart_sort_tile(false), JPL2_LG_P1 = 6, JPL2_THREADS = 512;
+static_assert(JPL2_LG_CELLS == JBS_LG_CELLS && JPL2_LG_P1 == JBS_LG_P1, "one slice geometry for the slice build and the LDS probe (SliceUnit, join_slice_geom)");
 // (4096-cell slices and 512-thread workgroups: two workgroups per CU, so one's staging round trips overlap the other's probing --
 //  8192 cells x 1024 threads, one per CU: 0.68 ms for C4's 1e8 keys)
 
@@ -2584,17 +2566,13 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
     // make every wait for the prefetched keys a full drain.
     extern __shared__ __attribute__((aligned(16))) unsigned char jpl2_lds[];
     jv2 * cells = (jv2 *)jpl2_lds; // [JPL2_CELLS + JPL2_TAIL] the slice and the cells behind it, then [1] the zero key {present, payload}
-    constexpr u32 P1 = 1u << JPL2_LG_P1, WIN = JPL2_CELLS + JPL2_TAIL;
-    __shared__ u64 s_off[P1 + 1];
-    __shared__ u32 sh_unit;
-    const u32 P2 = 1u << lg_p2, R2 = P1 << lg_p2, PB = 2 * P2;
-    __shared__ u64 s_boff[P1 + 1];
-    for (u32 p = threadIdx.x; p <= P1; p += JPL2_THREADS)
-    {
-        s_off[p] = p < P1 ? off1[(u64)p * G] : n;
-        if constexpr (FROM_ROWS)
-            s_boff[p] = p < P1 ? boff1[(u64)p * G] : nb;
-    }
+    constexpr u32 WIN = JPL2_CELLS + JPL2_TAIL;
+    __shared__ u64 s_off[JSL_P1 + 1];
+    const u32 PB = 2u << lg_p2;
+    __shared__ u64 s_boff[JSL_P1 + 1];
+    jpart_stage_offsets(s_off, off1, G, n, JPL2_THREADS);
+    if constexpr (FROM_ROWS)
+        jpart_stage_offsets(s_boff, boff1, G, nb, JPL2_THREADS);
     const u32 lane = threadIdx.x & 63;
     const u32 wave = (u32)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const u64 mask = t.capacity - 1;
@@ -2602,33 +2580,24 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
     while ((1ull << lg_cap) < t.capacity)
         ++lg_cap;
     auto slot_of = [&](u64 key) -> u64 { return FROM_ROWS ? join_radix_slot(key, lg_cap) : (dev_intHash64(key) & mask); };
-    auto flat_of = [&](u64 rowid) -> u64 { return n_blocks == 1 ? (rowid & 0xFFFFFFFFull) : block_base[rowid >> 32] + (rowid & 0xFFFFFFFFull); };
-    const bool miss_counts = variant == PV_ALL_LEFT || variant == PV_ANY_LEFT || variant == PV_ANTI_LEFT;
-    const bool anti = variant == PV_ANTI_LEFT;
     if constexpr (!FROM_ROWS)
         if (threadIdx.x == 0)
         {
             const bool hz = t.ctrl->has_zero != 0; // the zero key lives out of line (cell `capacity`)
-            cells[WIN] = jv2{hz ? 1ull : 0ull, hz ? payload[flat_of(t.kv[2 * t.capacity + 1])] : 0ull};
+            cells[WIN] = jv2{hz ? 1ull : 0ull, hz ? payload[join_flat_row(block_base, n_blocks, t.kv[2 * t.capacity + 1])] : 0ull};
             cells[WIN + 1] = jv2{0, 0};
         }
     u64 cnt = 0, isum = 0;
     bool stray = false, dup = false;
     for (;;)
     {
-        __syncthreads(); // the previous unit's cells have been read by everyone
-        if (threadIdx.x == 0)
-            sh_unit = atomicAdd(unit_ctr, 1u);
-        __syncthreads();
-        const u32 r2 = sh_unit;
-        if (r2 >= R2)
-            break; // (every workgroup reaches this exit)
-        const u32 p1 = r2 >> lg_p2, p2 = r2 & (P2 - 1);
-        const u64 rb = s_off[p1], re = s_off[p1 + 1];
-        if (rb == re)
+        const u32 r2 = slice_unit_claim(unit_ctr, [] {}); // (its first barrier: the previous unit's cells have been read by everyone)
+        if (r2 >= (JSL_P1 << lg_p2))
+            break;
+        const SliceUnit u = slice_unit(r2, s_off, lg_p2);
+        if (u.rb == u.re)
             continue; // no probe key lands in this partition
         // stage the slice, {key, row id} -> {key, payload}: all the cell loads first, then all the payload loads (two round trips, not 2 x 9)
-        const u64 slice = (u64)r2 * JPL2_CELLS;
         if constexpr (FROM_ROWS)
         {
             // build the slice's cells from its build rows: LDS compare-and-swap, linear probing inside the window (it is private to this
@@ -2638,60 +2607,29 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
             for (u32 c = threadIdx.x; c <= WIN + 1; c += JPL2_THREADS)
                 cells[c] = jv2{0, 0};
             __syncthreads();
-            const u64 bb = s_boff[p1], be = s_boff[p1 + 1];
+            const u64 bb = s_boff[u.p1], be = s_boff[u.p1 + 1];
             if (bb != be)
             {
                 const u32 bt_lo = (u32)(bb / JBS_TILE), bt_hi = (u32)((be - 1) / JBS_TILE);
                 const u32 my_bt = bt_lo + wave <= bt_hi ? (bt_hi - bt_lo - wave) / NWB + 1 : 0;
                 auto insert_row = [&](u64 key, u64 pay) {
-                    u32 c = key == 0 ? WIN : (u32)(slot_of(key) - slice);
-                    const u64 want = key == 0 ? 1ull : key; // the zero key's cell holds {present, payload}
-                    for (;;)
-                    {
-                        const u64 old = atomicCAS((unsigned long long *)&cw[2 * c], 0ull, (unsigned long long)want);
-                        if (old == 0)
-                        {
-                            cw[2 * c + 1] = pay; // nobody reads it before the barrier below
-                            break;
-                        }
-                        if (old == want || key == 0)
-                        {
-                            dup = true;
-                            break;
-                        }
-                        if (++c >= WIN)
-                        {
-                            stray = true; // the window is too short for this chain: not this plan
-                            break;
-                        }
-                    }
+                    const bool zk = key == 0; // the zero key's cell, behind the window, holds {present, payload}
+                    u32 c = zk ? WIN : (u32)(slot_of(key) - u.slice);
+                    const int claim = lds_claim<2>(cw, c, zk ? WIN + 1 : WIN, zk ? 1ull : key);
+                    if (claim == LDS_CLAIMED)
+                        cw[2 * c + 1] = pay; // nobody reads it before the barrier below
+                    else if (claim == LDS_DUPLICATE)
+                        dup = true;
+                    else
+                        stray = true; // the window is too short for this chain: not this plan
                 };
                 // as on the probe side: lane k fetches the run of this wave's k-th build tile, then the rows of TBB tiles are loaded
                 // together (a run is ~60 rows: tile by tile the wave sat out an index and a row round trip per tile -- half the kernel)
                 for (u32 kb = 0; kb < my_bt; kb += 64)
                 {
-                    u32 st_l = 0, ln_l = 0;
-                    if (kb + lane < my_bt)
-                    {
-                        const u32 tile = bt_lo + wave + (kb + lane) * NWB;
-                        const u64 row0 = (u64)tile * JBS_TILE;
-                        u32 lo = 0, hi = P1 - 1;
-                        while (lo < hi)
-                        {
-                            const u32 mid = (lo + hi + 1) >> 1;
-                            if (s_boff[mid] <= row0)
-                                lo = mid;
-                            else
-                                hi = mid - 1;
-                        }
-                        const u32 bucket = (p1 - lo) * P2 + p2;
-                        if (bucket < PB) // (else: stray flag raised by the tile sort)
-                        {
-                            const u32 ia = btidx[(u64)tile * (PB + 1) + bucket], ib = btidx[(u64)tile * (PB + 1) + bucket + 1];
-                            st_l = ia;
-                            ln_l = ib - ia;
-                        }
-                    }
+                    const u32 tile0 = bt_lo + wave + kb * NWB;
+                    u32 st_l, ln_l;
+                    jpart_lane_runs(s_boff, u, tile0, NWB, my_bt - kb, JBS_TILE, btidx, PB, st_l, ln_l);
                     const u32 nkb = my_bt - kb < 64 ? my_bt - kb : 64;
                     constexpr u32 TBB = 4;
                     for (u32 k0 = 0; k0 < nkb; k0 += TBB)
@@ -2701,10 +2639,7 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
 #pragma unroll
                         for (u32 q = 0; q < TBB; ++q)
                         {
-                            const u32 kk = k0 + q < nkb ? k0 + q : nkb - 1;
-                            const u32 st = (u32)__builtin_amdgcn_readlane((int)st_l, (int)kk);
-                            blen[q] = k0 + q < nkb ? (u32)__builtin_amdgcn_readlane((int)ln_l, (int)kk) : 0;
-                            brow[q] = (u64)(bt_lo + wave + (kb + kk) * NWB) * JBS_TILE + st;
+                            jpart_run_of(st_l, ln_l, k0 + q, nkb, tile0, NWB, JBS_TILE, brow[q], blen[q]);
                             const u64 at = brow[q] + (lane < blen[q] ? lane : 0);
                             bkey[q] = bkeys2[at];
                             bpay[q] = bwords2[at];
@@ -2729,11 +2664,11 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
             for (u32 i = 0; i < NC; ++i)
             {
                 const u32 c = threadIdx.x + i * JPL2_THREADS;
-                cl[i] = *(const jv2 *)(t.kv + 2 * ((slice + (c < WIN ? c : 0)) & mask));
+                cl[i] = *(const jv2 *)(t.kv + 2 * ((u.slice + (c < WIN ? c : 0)) & mask));
             }
 #pragma unroll
             for (u32 i = 0; i < NC; ++i)
-                cl[i].y = payload[cl[i].x != 0 ? flat_of(cl[i].y) : 0];
+                cl[i].y = payload[cl[i].x != 0 ? join_flat_row(block_base, n_blocks, cl[i].y) : 0];
 #pragma unroll
             for (u32 i = 0; i < NC; ++i)
             {
@@ -2743,7 +2678,7 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
             }
         }
         __syncthreads();
-        const u32 t_lo = (u32)(rb / JPL2_TILE), t_hi = (u32)((re - 1) / JPL2_TILE);
+        const u32 t_lo = (u32)(u.rb / JPL2_TILE), t_hi = (u32)((u.re - 1) / JPL2_TILE);
         // This wave's tiles: t_lo + wave, + NW, ...  Lane k fetches the run of tile k (one round trip for all of them instead of one
         // per tile); the keys of tile k + 1 are in flight while tile k is answered from LDS.
         constexpr u32 NW = JPL2_THREADS / 64;
@@ -2756,7 +2691,7 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
         auto probe_one = [&](u64 key, bool valid) {
             const bool zk = key == 0;
             const u64 want = zk ? 1ull : key;
-            u32 c = zk ? WIN : (u32)(slot_of(key) - slice); // the home slot: inside the slice by construction
+            u32 c = zk ? WIN : (u32)(slot_of(key) - u.slice); // the home slot: inside the slice by construction
             const jv2 c0 = cells[c], c1 = cells[c + 1];
             bool found = c0.x == want;
             u64 v = c0.y;
@@ -2777,53 +2712,31 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
                     v = cell.y;
                 }
             }
-            cnt += !valid ? 0 : found ? (anti ? 0 : 1) : (miss_counts ? 1 : 0);
-            isum += (valid && found && !anti) ? v : 0;
+            // (the build keys are unique: a hit is one row, whose value word IS the payload)
+            u64 add = 0;
+            const bool take = pv_account(variant, found, add);
+            cnt += valid ? add + (take ? 1 : 0) : 0;
+            isum += (valid && take) ? v : 0;
         };
         for (u32 kb = 0; kb < my_tiles; kb += 64)
         {
-            u32 st_l = 0, ln_l = 0;
-            if (kb + lane < my_tiles)
-            {
-                const u32 tile = t_lo + wave + (kb + lane) * NW;
-                const u64 row0 = (u64)tile * JPL2_TILE;
-                u32 lo = 0, hi = P1 - 1; // the first-level partition that owns the tile's first row: the largest p with s_off[p] <= row0
-                while (lo < hi)          // (empty partitions share their start with the next one: the largest such p is the owner)
-                {
-                    const u32 mid = (lo + hi + 1) >> 1;
-                    if (s_off[mid] <= row0)
-                        lo = mid;
-                    else
-                        hi = mid - 1;
-                }
-                const u32 bucket = (p1 - lo) * P2 + p2;
-                if (bucket < PB) // (else: a tile spanning three partitions -- k_rp_tilesort_keys raised the stray flag, the host discards this run)
-                {
-                    const u32 ia = tile_index[(u64)tile * (PB + 1) + bucket], ib = tile_index[(u64)tile * (PB + 1) + bucket + 1];
-                    st_l = ia;
-                    ln_l = ib - ia;
-                }
-            }
+            const u32 tile0 = t_lo + wave + kb * NW;
+            u32 st_l, ln_l;
+            jpart_lane_runs(s_off, u, tile0, NW, my_tiles - kb, JPL2_TILE, tile_index, PB, st_l, ln_l);
             const u32 nk = my_tiles - kb < 64 ? my_tiles - kb : 64;
             constexpr u32 U = 2;
-            auto run_of = [&](u32 k, u64 & row, u32 & len) {
-                const u32 kk = k < nk ? k : nk - 1;
-                const u32 st = (u32)__builtin_amdgcn_readlane((int)st_l, (int)kk);
-                len = k < nk ? (u32)__builtin_amdgcn_readlane((int)ln_l, (int)kk) : 0;
-                row = (u64)(t_lo + wave + (kb + kk) * NW) * JPL2_TILE + st;
-            };
             auto load_keys = [&](u64 row, u32 len, u32 o0, u64 (&key)[U]) {
 #pragma unroll
-                for (u32 u = 0; u < U; ++u)
+                for (u32 u2 = 0; u2 < U; ++u2)
                 {
-                    const u32 o = o0 + u * 64 + lane;
-                    key[u] = __builtin_nontemporal_load(&keys2[row + (o < len ? o : 0)]);
+                    const u32 o = o0 + u2 * 64 + lane;
+                    key[u2] = __builtin_nontemporal_load(&keys2[row + (o < len ? o : 0)]);
                 }
             };
             auto probe_keys = [&](u32 len, u32 o0, const u64 (&key)[U]) {
 #pragma unroll
-                for (u32 u = 0; u < U; ++u)
-                    probe_one(key[u], o0 + u * 64 + lane < len);
+                for (u32 u2 = 0; u2 < U; ++u2)
+                    probe_one(key[u2], o0 + u2 * 64 + lane < len);
             };
             // batches of TB tiles: all their key loads are issued before the first look-up (a run is only ~128 keys = two loads per lane:
             // tile by tile, even double-buffered, the wave had two tiles' worth of loads in flight and waited out the latency each time)
@@ -2835,7 +2748,7 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
 #pragma unroll
                 for (u32 q = 0; q < TB; ++q)
                 {
-                    run_of(k0 + q, row[q], len[q]);
+                    jpart_run_of(st_l, ln_l, k0 + q, nk, tile0, NW, JPL2_TILE, row[q], len[q]);
                     load_keys(row[q], len[q], 0, key[q]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -2853,12 +2766,8 @@ __global__ __launch_bounds__(JPL2_THREADS) void k_join_probe_lds(JoinTable t, in
             }
         }
     }
-#pragma unroll
-    for (int dlt = 32; dlt >= 1; dlt >>= 1)
-    {
-        cnt += __shfl_xor(cnt, dlt, 64);
-        isum += __shfl_xor(isum, dlt, 64);
-    }
+    cnt = wave_reduce_add_u64(cnt);
+    isum = wave_reduce_add_u64(isum);
     if (lane == 0 && (cnt || isum))
     {
         atomicAdd(&result2[0], (unsigned long long)cnt);
@@ -2877,29 +2786,19 @@ static int join_probe_agg_lds(chgpu_join * j, const chgpu_col * key_col, const c
     const u64 n = key_col->rows, cap = j->t.capacity;
     const bool off = chgpu_opt(ctx, "tune_join_no_lds_probe", 0) != 0;
     const u64 min_rows = chgpu_opt(ctx, "tune_join_lds_min_rows", (8ull << 20));
-    const u32 lg_cap = jceil_log2(cap);
+    const JoinSliceGeom geom = join_slice_geom(cap);
     if (off || !j->unique_keys || j->t.pf || !right_payload || chgpu_type_is_float(right_payload->type) || chgpu_type_size(right_payload->type) != 8
-        || chgpu_type_size(j->key_type) != 8 || n < min_rows
-        || n + JPL2_TILE + RP_SCATTER_SLACK >= (1ull << 32) || lg_cap < JPL2_LG_CELLS + JPL2_LG_P1 || lg_cap > JPL2_LG_CELLS + JPL2_LG_P1 + 7 || ((uintptr_t)key_col->data % 16) != 0)
+        || chgpu_type_size(j->key_type) != 8 || n < min_rows || n + JPL2_TILE + RP_SCATTER_SLACK >= (1ull << 32) || !geom.fits || ((uintptr_t)key_col->data % 16) != 0)
         return CHGPU_ERR_NOT_IMPLEMENTED;
-    const u32 lg_p2 = lg_cap - JPL2_LG_CELLS - JPL2_LG_P1, P1 = 1u << JPL2_LG_P1, PB = 2u << lg_p2;
+    const u32 lg_cap = geom.lg_cap, lg_p2 = geom.lg_p2, P1 = geom.P1, PB = geom.PB;
     const JoinRegionFn fn1{cap - 1, lg_cap - JPL2_LG_P1};
     const JoinBucket2Fn fn2{cap - 1, JPL2_LG_CELLS, lg_p2};
     const u32 G = (u32)ctx->num_cus;
     u64 * total_dev; // [2..3] the result, [4] unit counter + stray flag
     JoinPart part;
-    auto carve = [&](uintptr_t base) {
-        JoinCarve c{base};
-        total_dev = c.take<u64>(8);
-        part = join_part_carve(c, n, G, P1, PB, false);
-        return c.at - base;
-    };
-    void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, carve(0), &scratch));
-    carve((uintptr_t)scratch);
+    CHGPU_TRY(join_scratch(ctx, &total_dev, [&](JoinCarve & c) { part = join_part_carve(c, n, G, P1, PB, false); }));
     unsigned long long * result2 = (unsigned long long *)(total_dev + 2);
     u32 * unit_ctr = (u32 *)(total_dev + 4), * stray = unit_ctr + 1;
-    CHGPU_HIP(hipMemsetAsync(total_dev, 0, 64, ctx->stream));
     CHGPU_TRY(join_partition2<false>(ctx, part, (const u64 *)key_col->data, nullptr, n, P1, fn1, PB, fn2, stray));
     {
         const size_t lds = (size_t)(JPL2_CELLS + JPL2_TAIL + 2) * 16;
@@ -2940,29 +2839,21 @@ static int join_probe_agg_radix(chgpu_join * j, const chgpu_col * key_col, const
         || ((uintptr_t)j->blocks[0].keys % 16) != 0)
         return CHGPU_ERR_NOT_IMPLEMENTED;
     const u64 cap = join_capacity_for(j->ctx, nb);
-    const u32 lg_cap = jceil_log2(cap);
-    if (lg_cap < JPL2_LG_CELLS + JPL2_LG_P1 || lg_cap > JPL2_LG_CELLS + JPL2_LG_P1 + 7)
+    const JoinSliceGeom geom = join_slice_geom(cap);
+    if (!geom.fits)
         return CHGPU_ERR_NOT_IMPLEMENTED;
-    static_assert(JPL2_LG_CELLS == JBS_LG_CELLS && JPL2_LG_P1 == JBS_LG_P1, "one slice geometry for both sides");
-    const u32 lg_p2 = lg_cap - JPL2_LG_CELLS - JPL2_LG_P1, P1 = 1u << JPL2_LG_P1, PB = 2u << lg_p2;
+    const u32 lg_cap = geom.lg_cap, lg_p2 = geom.lg_p2, P1 = geom.P1, PB = geom.PB;
     const JoinRadixFn1 fn1{lg_cap, lg_cap - JPL2_LG_P1};
     const JoinRadixFn2 fn2{lg_cap, JPL2_LG_CELLS, lg_p2};
     const u32 G = (u32)ctx->num_cus;
     u64 * total_dev; // [2..3] the result, [4] unit counter | stray flag, [5] dup flag
     JoinPart probe, build;
-    auto carve = [&](uintptr_t base) {
-        JoinCarve c{base};
-        total_dev = c.take<u64>(8);
+    CHGPU_TRY(join_scratch(ctx, &total_dev, [&](JoinCarve & c) {
         probe = join_part_carve(c, n, G, P1, PB, false);
         build = join_part_carve(c, nb, G, P1, PB, true);
-        return c.at - base;
-    };
-    void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, carve(0), &scratch));
-    carve((uintptr_t)scratch);
+    }));
     unsigned long long * result2 = (unsigned long long *)(total_dev + 2);
     u32 * unit_ctr = (u32 *)(total_dev + 4), * stray = unit_ctr + 1, * dupf = (u32 *)(total_dev + 5);
-    CHGPU_HIP(hipMemsetAsync(total_dev, 0, 64, ctx->stream));
     // the build side: rows {key, payload}; then the probe side: keys
     CHGPU_TRY(join_partition2<true>(ctx, build, j->blocks[0].keys, (const u64 *)right_payload->data, nb, P1, fn1, PB, fn2, stray));
     CHGPU_TRY(join_partition2<false>(ctx, probe, (const u64 *)key_col->data, nullptr, n, P1, fn1, PB, fn2, stray));
@@ -3033,11 +2924,7 @@ extern "C" int chgpu_join_probe_agg(chgpu_join * j, const chgpu_col * key_col, c
     }
     chgpu_ctx * ctx = j->ctx;
     const u64 n = key_col->rows;
-    int variant;
-    if (j->strictness == CHGPU_STRICT_ALL) variant = jf_left_kind(j) == CHGPU_JOIN_LEFT ? PV_ALL_LEFT : PV_ALL_INNER;
-    else if (j->strictness == CHGPU_STRICT_SEMI) variant = PV_SEMI_LEFT;
-    else if (j->strictness == CHGPU_STRICT_ANTI) variant = PV_ANTI_LEFT;
-    else variant = PV_ANY_LEFT;
+    const int variant = join_probe_variant(j); // (no RIGHT / FULL, no INNER ANY here: ALL_INNER, ALL_LEFT, ANY_LEFT, SEMI_LEFT or ANTI_LEFT)
     u64 res[2] = {0, 0};
     int plan = CHGPU_ERR_NOT_IMPLEMENTED;
     const char * answered = "one_pass";

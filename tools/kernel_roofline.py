@@ -26,7 +26,7 @@ ALG = [
     ("k_agg_part_lds<unsigned int, 8", 12 * R, "GROUP BY LDS aggregation of partitions (12 B/row), 1 M groups"),
     ("k_agg_part_lds<unsigned long, 8", 16 * R, "GROUP BY LDS-staged over the source columns (RANGE mode, 16 B/row), 1000 groups"),
     ("k_join_probe_filter<true>", 5 * R, "filter-only LEFT SEMI probe, dense prefilter (4 B key in, 1 B out)"),
-    ("k_join_probe_filter_lds", 5 * R, "filter-only LEFT SEMI probe, key set staged in LDS slices (round 2; 4 B key in, 1 B out per pass)"),
+    ("k_join_probe_filter_lds_multi", 5 * R, "filter-only LEFT SEMI probe, key set staged in LDS slices, one sweep over the rows (4 B key in, 1 B out)"),
     ("k_join_insert", 8 * 10_000_000, "join build: insert 1e7 keys (8 B/row)"),
     ("k_join_fill", 12 * 10_000_000, "join build: CSR fill"),
     ("k_join_probe_count", 8 * (R // 4), "join probe: lookup (8 B/row in)"),
