@@ -8,7 +8,7 @@
 //   k_filter_sum        FilterTransform::doTransform + AggregateFunctionSumData::addMany/Count
 //                                                                src/Processors/Transforms/FilterTransform.cpp:136-256,
 //                                                                src/AggregateFunctions/AggregateFunctionSum.h:62-103
-//   k_index/k_replicate ColumnVector<T>::indexImpl / replicate    src/Columns/ColumnVector.cpp:1121-1143, 879-907
+//   k_index/k_replicate_multi ColumnVector<T>::indexImpl / replicate    src/Columns/ColumnVector.cpp:1121-1143, 879-907
 #include "chgpu_internal.h"
 #include <vector>
 
@@ -240,8 +240,80 @@ __device__ __forceinline__ typename AccOf<T>::type widen(T a)
 
 __device__ __forceinline__ u64 acc_bits(u64 v) { return v; }
 __device__ __forceinline__ u64 acc_bits(double v) { return (u64)__double_as_longlong(v); }
+template <typename Acc>
+__device__ __forceinline__ Acc acc_from_bits(u64 b)
+{
+    if constexpr (std::is_same<Acc, double>::value)
+        return __longlong_as_double((long long)b);
+    else
+        return b;
+}
 __device__ __forceinline__ u64 wave_reduce_acc(u64 v) { return wave_reduce_add_u64(v); }
 __device__ __forceinline__ double wave_reduce_acc(double v) { return wave_reduce_add_f64(v); }
+
+// ---------------------------------------------------------------------------------------------
+// host dispatch: a run-time type, width or small integer becomes the argument type of a generic lambda
+// ---------------------------------------------------------------------------------------------
+// the eight integer column types: fn(T{}) -> int
+template <typename F>
+static int dispatch_int_type(int type, F && fn)
+{
+    switch (type)
+    {
+        case CHGPU_I64: return fn(i64{});
+        case CHGPU_U64: return fn(u64{});
+        case CHGPU_U32: return fn(u32{});
+        case CHGPU_I32: return fn(i32{});
+        case CHGPU_U8: return fn(u8{});
+        case CHGPU_U16: return fn(u16{});
+        case CHGPU_I16: return fn(i16{});
+        case CHGPU_I8: return fn(i8{});
+        default: return chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "unsupported column type %d", type);
+    }
+}
+
+// element width 8 / 4 / 2 / 1 bytes, for kernels that only move elements: fn(u64{} / u32{} / u16{} / u8{})
+template <typename F>
+static void dispatch_width(size_t bytes, F && fn)
+{
+    switch (bytes)
+    {
+        case 8: return fn(u64{});
+        case 4: return fn(u32{});
+        case 2: return fn(u16{});
+        default: return fn(u8{});
+    }
+}
+
+// v in [LO, HI] (a column count, a width mask): fn(std::integral_constant<int, v>{})
+template <int LO, int HI, typename F>
+static void dispatch_const(u32 v, F && fn)
+{
+    if constexpr (LO < HI)
+        if (v > (u32)LO)
+            return dispatch_const<LO + 1, HI>(v, fn);
+    fn(std::integral_constant<int, LO>{});
+}
+
+// (column type, folded comparison): fn(T{}, pred) -> int with IntRangePred over the eight integer types, or one of the six
+// F64Pred<op> over Float32 / Float64
+template <typename F>
+static int dispatch_cmp(int type, const CmpSpec & spec, F && fn)
+{
+    if (!spec.is_f64)
+        return dispatch_int_type(type, [&](auto tag) { return fn(tag, spec.ip); });
+    auto fp = [&](auto p) { return type == CHGPU_F32 ? fn(float{}, p) : fn(double{}, p); };
+    switch (spec.op)
+    {
+        case CHGPU_EQ: return fp(F64Pred<CHGPU_EQ>{spec.fs});
+        case CHGPU_NE: return fp(F64Pred<CHGPU_NE>{spec.fs});
+        case CHGPU_LT: return fp(F64Pred<CHGPU_LT>{spec.fs});
+        case CHGPU_GT: return fp(F64Pred<CHGPU_GT>{spec.fs});
+        case CHGPU_LE: return fp(F64Pred<CHGPU_LE>{spec.fs});
+        case CHGPU_GE: return fp(F64Pred<CHGPU_GE>{spec.fs});
+    }
+    return chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "bad op");
+}
 
 // ---------------------------------------------------------------------------------------------
 // fused predicate -> sum(val), count()      (the dominant kernel of config C2: 8 B/row, one pass)
@@ -259,6 +331,35 @@ static constexpr int FS_WG_PER_CU = 2;
 #define FS_UNROLL_SAME 4
 #endif
 
+// wave -> workgroup reduction of an FS_THREADS workgroup; one partial per workgroup, folded in fixed order by k_filter_sum_finish.
+// Lane 0 adds the wave partials in wave order 0..3 starting from zero, so a Float64 sum depends on the grid alone.
+template <typename Acc>
+__device__ __forceinline__ void fs_fold_workgroup(Acc s, u64 c, u64 * __restrict__ part_sum, u64 * __restrict__ part_cnt)
+{
+    __shared__ u64 lds_s[FS_THREADS / WAVE];
+    __shared__ u64 lds_c[FS_THREADS / WAVE];
+    s = wave_reduce_acc(s);
+    c = wave_reduce_add_u64(c);
+    if ((threadIdx.x & 63) == 0)
+    {
+        lds_s[threadIdx.x >> 6] = acc_bits(s);
+        lds_c[threadIdx.x >> 6] = c;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+    {
+        Acc ss = 0;
+        u64 cc = 0;
+        for (int w = 0; w < FS_THREADS / WAVE; ++w)
+        {
+            ss += acc_from_bits<Acc>(lds_s[w]);
+            cc += lds_c[w];
+        }
+        part_sum[blockIdx.x] = acc_bits(ss);
+        part_cnt[blockIdx.x] = cc;
+    }
+}
+
 template <typename T, int VEC, bool SAME, bool HAS_COND, typename Pred>
 __global__ __launch_bounds__(FS_THREADS) void k_filter_sum(const T * __restrict__ pred_col, const T * __restrict__ val_col,
                                                            const u8 * __restrict__ cond, u64 n, Pred p,
@@ -274,6 +375,14 @@ __global__ __launch_bounds__(FS_THREADS) void k_filter_sum(const T * __restrict_
     const CV * __restrict__ cv = (const CV *)cond;
     Acc s = 0;
     u64 c = 0;
+    // one row: a = predicate element, x = value element, m = mask byte (read only under HAS_COND)
+    auto fold = [&](T a, T x, u8 m) {
+        bool pass = p(a);
+        if constexpr (HAS_COND)
+            pass = pass && (m != 0);
+        s += pass ? widen<T>(x) : Acc(0);
+        c += pass ? 1 : 0;
+    };
 
     // main loop: the workgroup reads UNROLL * 256 consecutive vectors per iteration; every load is issued before the
     // first use (sched_barrier pins that order)
@@ -298,14 +407,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_filter_sum(const T * __restrict_
         for (int k = 0; k < UNROLL; ++k)
 #pragma unroll
             for (int e = 0; e < VEC; ++e)
-            {
-                bool pass = p(a[k].v[e]);
-                if constexpr (HAS_COND)
-                    pass = pass && (m[k].v[e] != 0);
-                T x = SAME ? a[k].v[e] : b[k].v[e];
-                s += pass ? widen<T>(x) : Acc(0);
-                c += pass ? 1 : 0;
-            }
+                fold(a[k].v[e], SAME ? a[k].v[e] : b[k].v[e], HAS_COND ? m[k].v[e] : u8(1));
     }
     // remainder vectors (< one chunk per workgroup), grid-strided
     const u64 tid = (u64)blockIdx.x * FS_THREADS + threadIdx.x;
@@ -321,124 +423,65 @@ __global__ __launch_bounds__(FS_THREADS) void k_filter_sum(const T * __restrict_
             m = cv[i];
 #pragma unroll
         for (int e = 0; e < VEC; ++e)
-        {
-            bool pass = p(a.v[e]);
-            if constexpr (HAS_COND)
-                pass = pass && (m.v[e] != 0);
-            T x = SAME ? a.v[e] : b.v[e];
-            s += pass ? widen<T>(x) : Acc(0);
-            c += pass ? 1 : 0;
-        }
+            fold(a.v[e], SAME ? a.v[e] : b.v[e], HAS_COND ? m.v[e] : u8(1));
     }
     // scalar tail (n % VEC rows)
     {
         const u64 r = nvec * VEC + tid;
         if (r < n)
-        {
-            bool pass = p(pred_col[r]);
-            if constexpr (HAS_COND)
-                pass = pass && (cond[r] != 0);
-            T x = SAME ? pred_col[r] : val_col[r];
-            s += pass ? widen<T>(x) : Acc(0);
-            c += pass ? 1 : 0;
-        }
+            fold(pred_col[r], SAME ? pred_col[r] : val_col[r], HAS_COND ? cond[r] : u8(1));
     }
-
-    // wave -> workgroup reduction; one partial per workgroup, folded in fixed order by k_filter_sum_finish
-    __shared__ u64 lds_s[FS_THREADS / WAVE];
-    __shared__ u64 lds_c[FS_THREADS / WAVE];
-    s = wave_reduce_acc(s);
-    c = wave_reduce_add_u64(c);
-    if ((threadIdx.x & 63) == 0)
-    {
-        lds_s[threadIdx.x >> 6] = acc_bits(s);
-        lds_c[threadIdx.x >> 6] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        u64 cc = 0;
-        if constexpr (std::is_same<Acc, double>::value)
-        {
-            double ss = 0;
-            for (int w = 0; w < FS_THREADS / WAVE; ++w)
-            {
-                ss += __longlong_as_double((long long)lds_s[w]);
-                cc += lds_c[w];
-            }
-            part_sum[blockIdx.x] = acc_bits(ss);
-        }
-        else
-        {
-            u64 ss = 0;
-            for (int w = 0; w < FS_THREADS / WAVE; ++w)
-            {
-                ss += lds_s[w];
-                cc += lds_c[w];
-            }
-            part_sum[blockIdx.x] = ss;
-        }
-        part_cnt[blockIdx.x] = cc;
-    }
+    fs_fold_workgroup(s, c, part_sum, part_cnt);
 }
 
+// one workgroup: the partials of a grid, strided over the lanes, through the same fold -> result {sum bits, count}
 template <bool IS_F64>
-__global__ __launch_bounds__(256) void k_filter_sum_finish(const u64 * __restrict__ part_sum, const u64 * __restrict__ part_cnt,
-                                                           u32 n_parts, u64 * __restrict__ result /* {sum bits, count} */)
+__global__ __launch_bounds__(FS_THREADS) void k_filter_sum_finish(const u64 * __restrict__ part_sum, const u64 * __restrict__ part_cnt,
+                                                                  u32 n_parts, u64 * __restrict__ result /* {sum bits, count} */)
 {
-    __shared__ u64 lds_s[4];
-    __shared__ u64 lds_c[4];
+    typedef typename std::conditional<IS_F64, double, u64>::type Acc;
+    Acc s = 0;
     u64 c = 0;
-    u64 sb;
-    if constexpr (IS_F64)
+    for (u32 i = threadIdx.x; i < n_parts; i += FS_THREADS)
     {
-        double s = 0;
-        for (u32 i = threadIdx.x; i < n_parts; i += 256)
-        {
-            s += __longlong_as_double((long long)part_sum[i]);
-            c += part_cnt[i];
-        }
-        s = wave_reduce_add_f64(s);
-        sb = acc_bits(s);
+        s += acc_from_bits<Acc>(part_sum[i]);
+        c += part_cnt[i];
     }
-    else
-    {
-        u64 s = 0;
-        for (u32 i = threadIdx.x; i < n_parts; i += 256)
-        {
-            s += part_sum[i];
-            c += part_cnt[i];
-        }
-        sb = wave_reduce_add_u64(s);
-    }
-    c = wave_reduce_add_u64(c);
-    if ((threadIdx.x & 63) == 0)
-    {
-        lds_s[threadIdx.x >> 6] = sb;
-        lds_c[threadIdx.x >> 6] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        u64 cc = lds_c[0] + lds_c[1] + lds_c[2] + lds_c[3];
-        if constexpr (IS_F64)
-        {
-            double ss = 0;
-            for (int w = 0; w < 4; ++w)
-                ss += __longlong_as_double((long long)lds_s[w]);
-            result[0] = acc_bits(ss);
-        }
-        else
-            result[0] = lds_s[0] + lds_s[1] + lds_s[2] + lds_s[3];
-        result[1] = cc;
-    }
+    fs_fold_workgroup(s, c, result, result + 1); // blockIdx.x == 0
+}
+
+// Scratch for one sum / count call: room for the partials of the largest grid (8 workgroups per CU) and, behind them, the
+// {sum bits, count} result slot.  The launchers below ask chgpu_scratch again for their own, smaller partials; a request that
+// fits the buffer returns the same pointer, so the slot handed out here stays valid.
+static int fs_result_slot(chgpu_ctx * ctx, u64 ** part_dev, u64 ** result_dev)
+{
+    const size_t part_bytes = (size_t)ctx->num_cus * 8 * 2 * sizeof(u64);
+    void * scratch = nullptr;
+    CHGPU_TRY(chgpu_scratch(ctx, part_bytes + 64, &scratch));
+    if (part_dev)
+        *part_dev = (u64 *)scratch;
+    *result_dev = (u64 *)((char *)scratch + part_bytes);
+    return CHGPU_OK;
+}
+
+static int fs_read_result(chgpu_ctx * ctx, const u64 * result_dev, void * sum_bits_out, u64 * count_out)
+{
+    u64 res[2];
+    CHGPU_TRY(chgpu_read_back(ctx, result_dev, res, sizeof(res)));
+    memcpy(sum_bits_out, &res[0], 8);
+    *count_out = res[1];
+    return CHGPU_OK;
 }
 
 template <typename T, typename Pred>
 static int launch_filter_sum_t(chgpu_ctx * ctx, const void * pred, const void * val, const u8 * cond, u64 n, Pred p, u64 * result_dev)
 {
     constexpr int VECW = 16 / sizeof(T);
+    constexpr bool NO_PRED = std::is_same<Pred, TruePred>::value;
     const bool same = (pred == val);
+    // What the C ABI can ask for, and so what is instantiated: no predicate means one column, summed whole or under a mask
+    // (chgpu_sum_add_many / _conditional, and filter_sum_mixed below); a predicate never comes with a mask.
+    CHGPU_REQUIRE(NO_PRED ? same : !cond, CHGPU_ERR_LOGICAL, "filter+sum: %s", NO_PRED ? "no predicate over two columns" : "a predicate together with a mask");
     const bool aligned = (((uintptr_t)pred | (uintptr_t)val) & 15) == 0 && (!cond || ((uintptr_t)cond % VECW) == 0);
     // persistent grid: FS_WG_PER_CU 256-thread workgroups per CU (see the measurement note above k_filter_sum)
     const u32 wg_same = tune_env(ctx, "tune_fs_wg", FS_WG_PER_CU), wg_two = tune_env(ctx, "tune_fs2_wg", FS_WG_PER_CU);
@@ -447,80 +490,62 @@ static int launch_filter_sum_t(chgpu_ctx * ctx, const void * pred, const void * 
     CHGPU_TRY(chgpu_scratch(ctx, (size_t)grid * 2 * sizeof(u64), &scratch));
     u64 * part_sum = (u64 *)scratch;
     u64 * part_cnt = part_sum + grid;
-    const T * pp = (const T *)pred;
-    const T * vp = (const T *)val;
-#define FS_LAUNCH(VEC, SAME, HC) \
-    hipLaunchKernelGGL((k_filter_sum<T, VEC, SAME, HC, Pred>), dim3(grid), dim3(FS_THREADS), 0, ctx->stream, pp, vp, cond, n, p, part_sum, part_cnt)
-    if (aligned)
+    auto launch = [&](auto same_c, auto cond_c) {
+        constexpr bool SAME = decltype(same_c)::value, HC = decltype(cond_c)::value;
+        if (aligned)
+            hipLaunchKernelGGL((k_filter_sum<T, VECW, SAME, HC, Pred>), dim3(grid), dim3(FS_THREADS), 0, ctx->stream, (const T *)pred, (const T *)val, cond, n, p, part_sum, part_cnt);
+        else
+            hipLaunchKernelGGL((k_filter_sum<T, 1, SAME, HC, Pred>), dim3(grid), dim3(FS_THREADS), 0, ctx->stream, (const T *)pred, (const T *)val, cond, n, p, part_sum, part_cnt);
+    };
+    if constexpr (NO_PRED)
     {
-        if (cond) { if (same) FS_LAUNCH(VECW, true, true); else FS_LAUNCH(VECW, false, true); }
-        else      { if (same) FS_LAUNCH(VECW, true, false); else FS_LAUNCH(VECW, false, false); }
+        if (cond) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{});
     }
     else
     {
-        if (cond) { if (same) FS_LAUNCH(1, true, true); else FS_LAUNCH(1, false, true); }
-        else      { if (same) FS_LAUNCH(1, true, false); else FS_LAUNCH(1, false, false); }
+        if (same) launch(std::true_type{}, std::false_type{}); else launch(std::false_type{}, std::false_type{});
     }
-#undef FS_LAUNCH
-    hipLaunchKernelGGL((k_filter_sum_finish<std::is_same<typename AccOf<T>::type, double>::value>), dim3(1), dim3(256), 0, ctx->stream, part_sum, part_cnt, grid, result_dev);
+    hipLaunchKernelGGL((k_filter_sum_finish<std::is_same<typename AccOf<T>::type, double>::value>), dim3(1), dim3(FS_THREADS), 0, ctx->stream, part_sum, part_cnt, grid, result_dev);
     ctx->counters[6] += 2;
     CHGPU_HIP(hipGetLastError());
     return CHGPU_OK;
 }
 
-template <typename Pred>
-static int launch_filter_sum_int(chgpu_ctx * ctx, int type, const void * pred, const void * val, const u8 * cond, u64 n, Pred p, u64 * result_dev)
-{
-    switch (type)
-    {
-        case CHGPU_I64: return launch_filter_sum_t<i64, Pred>(ctx, pred, val, cond, n, p, result_dev);
-        case CHGPU_U64: return launch_filter_sum_t<u64, Pred>(ctx, pred, val, cond, n, p, result_dev);
-        case CHGPU_U32: return launch_filter_sum_t<u32, Pred>(ctx, pred, val, cond, n, p, result_dev);
-        case CHGPU_I32: return launch_filter_sum_t<i32, Pred>(ctx, pred, val, cond, n, p, result_dev);
-        case CHGPU_U8: return launch_filter_sum_t<u8, Pred>(ctx, pred, val, cond, n, p, result_dev);
-        case CHGPU_U16: return launch_filter_sum_t<u16, Pred>(ctx, pred, val, cond, n, p, result_dev);
-        case CHGPU_I16: return launch_filter_sum_t<i16, Pred>(ctx, pred, val, cond, n, p, result_dev);
-        case CHGPU_I8: return launch_filter_sum_t<i8, Pred>(ctx, pred, val, cond, n, p, result_dev);
-        default: return chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "unsupported column type %d", type);
-    }
-}
-
 static int launch_filter_sum(chgpu_ctx * ctx, int type, const void * pred, const void * val, const u8 * cond, u64 n,
                              const CmpSpec * spec /* NULL = no predicate */, u64 * result_dev)
 {
-    if (!spec)
-    {
-        if (type == CHGPU_F64)
-            return launch_filter_sum_t<double, TruePred>(ctx, pred, val, cond, n, TruePred(), result_dev);
-        if (type == CHGPU_F32)
-            return launch_filter_sum_t<float, TruePred>(ctx, pred, val, cond, n, TruePred(), result_dev);
-        return launch_filter_sum_int<TruePred>(ctx, type, pred, val, cond, n, TruePred(), result_dev);
-    }
-    if (spec->is_f64)
-    {
-        switch (spec->op)
-        {
-#define F64CASE(OP) case OP: return type == CHGPU_F32 ? launch_filter_sum_t<float, F64Pred<OP>>(ctx, pred, val, cond, n, F64Pred<OP>{spec->fs}, result_dev) \
-                                                   : launch_filter_sum_t<double, F64Pred<OP>>(ctx, pred, val, cond, n, F64Pred<OP>{spec->fs}, result_dev);
-            F64CASE(CHGPU_EQ) F64CASE(CHGPU_NE) F64CASE(CHGPU_LT) F64CASE(CHGPU_GT) F64CASE(CHGPU_LE) F64CASE(CHGPU_GE)
-#undef F64CASE
-        }
-        return chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "bad op");
-    }
-    return launch_filter_sum_int<IntRangePred>(ctx, type, pred, val, cond, n, spec->ip, result_dev);
+    if (spec)
+        return dispatch_cmp(type, *spec, [&](auto tag, auto p) { return launch_filter_sum_t<decltype(tag)>(ctx, pred, val, cond, n, p, result_dev); });
+    auto sum = [&](auto tag) { return launch_filter_sum_t<decltype(tag)>(ctx, pred, val, cond, n, TruePred(), result_dev); };
+    if (type == CHGPU_F64)
+        return sum(double{});
+    if (type == CHGPU_F32)
+        return sum(float{});
+    return dispatch_int_type(type, sum);
 }
 
-// Predicate and value columns of different types: the one-pass kernel is instantiated per type, so the predicate is first
-// materialised as a UInt8 mask (k_cmp_mask) and the value column summed under it (addManyConditional,
-// AggregateFunctionSum.h:138-236) -- what the reference does, minus its filtered copy.  9 + w B/row instead of 8 + w.
 extern "C" int chgpu_cmp_const(chgpu_ctx * ctx, const chgpu_col * col, int op, int scalar_type, const void * scalar, chgpu_col ** mask_out);
-static int filter_sum_mixed(chgpu_ctx * ctx, const chgpu_col * pred, int op, int scalar_type, const void * scalar, const chgpu_col * val, u64 * result_dev)
+
+// The checked dispatch behind chgpu_filter_sum and chgpu_filter_sum_async.  Predicate and value columns of different types: the
+// one-pass kernel is instantiated per type, so the predicate is first materialised as a UInt8 mask (k_cmp_mask) and the value
+// column summed under it (addManyConditional, AggregateFunctionSum.h:138-236) -- what the reference does, minus its filtered
+// copy.  9 + w B/row instead of 8 + w.
+static int filter_sum_dispatch(chgpu_ctx * ctx, const chgpu_col * pred, int op, int scalar_type, const void * scalar, const chgpu_col * val, u64 * result_dev)
 {
-    chgpu_col * mask = nullptr;
-    CHGPU_TRY(chgpu_cmp_const(ctx, pred, op, scalar_type, scalar, &mask));
-    const int rc = launch_filter_sum(ctx, val->type, val->data, val->data, (const u8 *)mask->data, val->rows, nullptr, result_dev);
-    chgpu_col_free(mask); // back to the pool: reuse is ordered behind the kernel on the context's stream
-    return rc;
+    CHGPU_REQUIRE(pred->rows == val->rows, CHGPU_ERR_SIZES_MISMATCH, "Size of predicate column (%llu) doesn't match size of value column (%llu)",
+                  (unsigned long long)pred->rows, (unsigned long long)val->rows);
+    ctx->counters[5] += pred->rows;
+    if (pred->type != val->type)
+    {
+        chgpu_col * mask = nullptr;
+        CHGPU_TRY(chgpu_cmp_const(ctx, pred, op, scalar_type, scalar, &mask));
+        const int rc = launch_filter_sum(ctx, val->type, val->data, val->data, (const u8 *)mask->data, val->rows, nullptr, result_dev);
+        chgpu_col_free(mask); // back to the pool: reuse is ordered behind the kernel on the context's stream
+        return rc;
+    }
+    CmpSpec spec;
+    CHGPU_TRY(make_cmp_spec(pred->type, op, scalar_type, scalar, &spec));
+    return launch_filter_sum(ctx, pred->type, pred->data, val->data, nullptr, pred->rows, &spec, result_dev);
 }
 
 extern "C" int chgpu_filter_sum_async(chgpu_ctx * ctx, const chgpu_col * pred, int op, int scalar_type, const void * scalar,
@@ -528,15 +553,8 @@ extern "C" int chgpu_filter_sum_async(chgpu_ctx * ctx, const chgpu_col * pred, i
 {
     ChgpuDeviceGuard _dev_guard(ctx);
     CHGPU_REQUIRE(ctx && pred && val && result, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(pred->rows == val->rows, CHGPU_ERR_SIZES_MISMATCH, "Size of predicate column (%llu) doesn't match size of value column (%llu)",
-                  (unsigned long long)pred->rows, (unsigned long long)val->rows);
     CHGPU_REQUIRE(result->type == CHGPU_U64 && result->rows >= 2, CHGPU_ERR_BAD_ARGUMENTS, "result must be a UInt64 column of 2 rows");
-    ctx->counters[5] += pred->rows;
-    if (pred->type != val->type)
-        return filter_sum_mixed(ctx, pred, op, scalar_type, scalar, val, (u64 *)result->data);
-    CmpSpec spec;
-    CHGPU_TRY(make_cmp_spec(pred->type, op, scalar_type, scalar, &spec));
-    return launch_filter_sum(ctx, pred->type, pred->data, val->data, nullptr, pred->rows, &spec, (u64 *)result->data);
+    return filter_sum_dispatch(ctx, pred, op, scalar_type, scalar, val, (u64 *)result->data);
 }
 
 extern "C" int chgpu_filter_sum(chgpu_ctx * ctx, const chgpu_col * pred, int op, int scalar_type, const void * scalar,
@@ -544,28 +562,12 @@ extern "C" int chgpu_filter_sum(chgpu_ctx * ctx, const chgpu_col * pred, int op,
 {
     ChgpuDeviceGuard _dev_guard(ctx);
     CHGPU_REQUIRE(ctx && pred && val && sum_out && count_out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(pred->rows == val->rows, CHGPU_ERR_SIZES_MISMATCH, "Size of predicate column (%llu) doesn't match size of value column (%llu)",
-                  (unsigned long long)pred->rows, (unsigned long long)val->rows);
-    void * scratch = nullptr;
-    // result slot lives behind the partials: ask for the partials' worth first so the pointer stays valid
-    const u32 grid_cap = (u32)ctx->num_cus * 8;
-    CHGPU_TRY(chgpu_scratch(ctx, (size_t)grid_cap * 2 * sizeof(u64) + 64, &scratch));
-    u64 * result_dev = (u64 *)((char *)scratch + (size_t)grid_cap * 2 * sizeof(u64));
-    if (pred->type != val->type)
-        CHGPU_TRY(filter_sum_mixed(ctx, pred, op, scalar_type, scalar, val, result_dev));
-    else
-    {
-        CmpSpec spec;
-        CHGPU_TRY(make_cmp_spec(pred->type, op, scalar_type, scalar, &spec));
-        CHGPU_TRY(launch_filter_sum(ctx, pred->type, pred->data, val->data, nullptr, pred->rows, &spec, result_dev));
-    }
-    u64 res[2];
-    CHGPU_TRY(chgpu_read_back(ctx, result_dev, res, sizeof(res)));
-    memcpy(sum_out, &res[0], 8);
-    *count_out = res[1];
-    ctx->counters[0] += res[1];
-    ctx->counters[1] += res[1] * chgpu_type_size(val->type);
-    ctx->counters[5] += pred->rows;
+    u64 * result_dev = nullptr;
+    CHGPU_TRY(fs_result_slot(ctx, nullptr, &result_dev));
+    CHGPU_TRY(filter_sum_dispatch(ctx, pred, op, scalar_type, scalar, val, result_dev));
+    CHGPU_TRY(fs_read_result(ctx, result_dev, sum_out, count_out));
+    ctx->counters[0] += *count_out;
+    ctx->counters[1] += *count_out * chgpu_type_size(val->type);
     return CHGPU_OK;
 }
 
@@ -584,17 +586,15 @@ static int sum_add_many_impl(chgpu_ctx * ctx, const chgpu_col * col, const chgpu
     const u64 n = row_end - row_begin;
     const void * p = (const char *)col->data + row_begin * es;
     const u8 * c = cond ? (const u8 *)cond->data + row_begin : nullptr;
-    void * scratch = nullptr;
-    const u32 grid_cap = (u32)ctx->num_cus * 8;
-    CHGPU_TRY(chgpu_scratch(ctx, (size_t)grid_cap * 2 * sizeof(u64) + 64, &scratch));
-    u64 * result_dev = (u64 *)((char *)scratch + (size_t)grid_cap * 2 * sizeof(u64));
+    u64 * result_dev = nullptr;
+    CHGPU_TRY(fs_result_slot(ctx, nullptr, &result_dev));
     CHGPU_TRY(launch_filter_sum(ctx, col->type, p, p, c, n, nullptr, result_dev));
-    u64 res[2];
-    CHGPU_TRY(chgpu_read_back(ctx, result_dev, res, sizeof(res)));
+    u64 sum_bits, count;
+    CHGPU_TRY(fs_read_result(ctx, result_dev, &sum_bits, &count));
     if (chgpu_type_is_float(col->type))
     {
         double batch, st;
-        memcpy(&batch, &res[0], 8);
+        memcpy(&batch, &sum_bits, 8);
         memcpy(&st, state8, 8);
         st += batch;
         memcpy(state8, &st, 8);
@@ -603,7 +603,7 @@ static int sum_add_many_impl(chgpu_ctx * ctx, const chgpu_col * col, const chgpu
     {
         u64 st;
         memcpy(&st, state8, 8);
-        st += res[0];
+        st += sum_bits;
         memcpy(state8, &st, 8);
     }
     ctx->counters[5] += n;
@@ -726,36 +726,8 @@ extern "C" int chgpu_cmp_const(chgpu_ctx * ctx, const chgpu_col * col, int op, i
     chgpu_col * m = nullptr;
     CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, col->rows, &m));
     int rc = CHGPU_OK;
-    const u64 n = col->rows;
-    u8 * c = (u8 *)m->data;
-    if (n)
-    {
-        if (spec.is_f64)
-        {
-            switch (spec.op)
-            {
-#define F64CASE(OP) case OP: rc = col->type == CHGPU_F32 ? launch_cmp_t<float, F64Pred<OP>>(ctx, col->data, n, F64Pred<OP>{spec.fs}, c) \
-                                                       : launch_cmp_t<double, F64Pred<OP>>(ctx, col->data, n, F64Pred<OP>{spec.fs}, c); break;
-                F64CASE(CHGPU_EQ) F64CASE(CHGPU_NE) F64CASE(CHGPU_LT) F64CASE(CHGPU_GT) F64CASE(CHGPU_LE) F64CASE(CHGPU_GE)
-#undef F64CASE
-            }
-        }
-        else
-        {
-            switch (col->type)
-            {
-                case CHGPU_I64: rc = launch_cmp_t<i64, IntRangePred>(ctx, col->data, n, spec.ip, c); break;
-                case CHGPU_U64: rc = launch_cmp_t<u64, IntRangePred>(ctx, col->data, n, spec.ip, c); break;
-                case CHGPU_U32: rc = launch_cmp_t<u32, IntRangePred>(ctx, col->data, n, spec.ip, c); break;
-                case CHGPU_I32: rc = launch_cmp_t<i32, IntRangePred>(ctx, col->data, n, spec.ip, c); break;
-                case CHGPU_U8: rc = launch_cmp_t<u8, IntRangePred>(ctx, col->data, n, spec.ip, c); break;
-                case CHGPU_U16: rc = launch_cmp_t<u16, IntRangePred>(ctx, col->data, n, spec.ip, c); break;
-                case CHGPU_I16: rc = launch_cmp_t<i16, IntRangePred>(ctx, col->data, n, spec.ip, c); break;
-                case CHGPU_I8: rc = launch_cmp_t<i8, IntRangePred>(ctx, col->data, n, spec.ip, c); break;
-                default: rc = chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "unsupported column type");
-            }
-        }
-    }
+    if (col->rows)
+        rc = dispatch_cmp(col->type, spec, [&](auto tag, auto p) { return launch_cmp_t<decltype(tag)>(ctx, col->data, col->rows, p, (u8 *)m->data); });
     if (rc != CHGPU_OK)
     {
         chgpu_col_free(m);
@@ -798,7 +770,7 @@ extern "C" int chgpu_filter_description_nullable(chgpu_ctx * ctx, const chgpu_co
 // ---------------------------------------------------------------------------------------------
 static constexpr u32 CHUNK_ROWS = 1024;
 
-__device__ __forceinline__ u32 count_nonzero_bytes16(const uint4 v)
+__device__ __forceinline__ u32 count_nonzero_bytes16(const u32x4 v)
 {
     auto nz = [](u32 x) { return __popc((x | ((x & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u); };
     return nz(v.x) + nz(v.y) + nz(v.z) + nz(v.w);
@@ -815,7 +787,7 @@ __global__ __launch_bounds__(256) void k_mask_chunk_counts(const u8 * __restrict
         const u64 base = chunk * CHUNK_ROWS + (u64)lane * 16;
         u32 c = 0;
         if (aligned && base + 16 <= n)
-            c = count_nonzero_bytes16(*(const uint4 *)(mask + base));
+            c = count_nonzero_bytes16(*(const u32x4 *)(mask + base));
         else
             for (u32 k = 0; k < 16; ++k)
                 if (base + k < n)
@@ -826,135 +798,100 @@ __global__ __launch_bounds__(256) void k_mask_chunk_counts(const u8 * __restrict
     }
 }
 
-template <typename T, bool STAGED = false>
-__global__ __launch_bounds__(256) void k_filter_scatter(const T * __restrict__ data, const u8 * __restrict__ mask, u64 n,
-                                                        const u64 * __restrict__ chunk_offsets, u64 n_chunks, T * __restrict__ out)
-{
-    // STAGED: see k_filter_scatter_multi
-    __shared__ T stage[STAGED ? 4 : 1][STAGED ? CHUNK_ROWS : 1];
-    T * const st = stage[STAGED ? (threadIdx.x >> 6) : 0];
-    constexpr int R = 16 / sizeof(T);        // rows per lane per group
-    constexpr u32 GROUP = 64 * R;            // rows per wave per group
-    constexpr int G = CHUNK_ROWS / GROUP;    // groups per chunk
-    typedef Vec<T, R> V;
-    typedef Vec<u8, R> MV;
-    const u32 lane = threadIdx.x & 63;
-    const u64 wave0 = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6;
-    const u64 n_waves = ((u64)gridDim.x * 256) >> 6;
-    const bool aligned = (((uintptr_t)data) & 15) == 0 && (((uintptr_t)mask) % R) == 0;
-
-    for (u64 chunk = wave0; chunk < n_chunks; chunk += n_waves)
-    {
-        u64 pos = chunk_offsets[chunk];
-        const u64 cbase = chunk * CHUNK_ROWS;
-        if (aligned && cbase + CHUNK_ROWS <= n)
-        {
-            V x[G];
-            MV m[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g)
-            {
-                const u64 row = cbase + (u64)g * GROUP + (u64)lane * R;
-                x[g] = *(const V *)(data + row);
-                m[g] = *(const MV *)(mask + row);
-            }
-            if constexpr (STAGED)
-            {
-                u32 run = 0;
-#pragma unroll
-                for (int g = 0; g < G; ++g)
-                {
-                    u32 before = 0, total = 0;
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-                    {
-                        const u64 b = __ballot(m[g].v[r] != 0);
-                        before += mbcnt(b);
-                        total += __popcll(b);
-                    }
-                    u32 o = run + before;
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-                        if (m[g].v[r] != 0)
-                            st[o++] = x[g].v[r];
-                    run += total;
-                }
-                T * const dst = out + pos;
-                for (u32 i = lane; i < run; i += 64) // LDS operations of one wave complete in order: no barrier
-                    dst[i] = st[i];
-            }
-            else
-            {
-#pragma unroll
-                for (int g = 0; g < G; ++g)
-                {
-                    u32 before = 0, total = 0;
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-                    {
-                        const u64 b = __ballot(m[g].v[r] != 0);
-                        before += mbcnt(b);
-                        total += __popcll(b);
-                    }
-                    u64 o = pos + before;
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-                        if (m[g].v[r] != 0)
-                            out[o++] = x[g].v[r]; // plain store: L2 merges the partial lines (nontemporal stores here: +25 % time)
-                    pos += total;
-                }
-            }
-        }
-        else
-        {
-            // ragged tail chunk / unaligned view: same order, guarded scalar accesses
-            for (int g = 0; g < G; ++g)
-            {
-                const u64 row = cbase + (u64)g * GROUP + (u64)lane * R;
-                T xv[R];
-                bool keep[R];
-                u32 before = 0, total = 0;
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                {
-                    const bool in = row + r < n;
-                    keep[r] = in && mask[in ? row + r : 0] != 0;
-                    if (keep[r])
-                        xv[r] = data[row + r];
-                    const u64 b = __ballot(keep[r]);
-                    before += mbcnt(b);
-                    total += __popcll(b);
-                }
-                u64 o = pos + before;
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                    if (keep[r])
-                        out[o++] = xv[r];
-                pos += total;
-            }
-        }
-    }
-}
-
-// The same compaction for NC columns of one element width at once (IColumn::filter over every column of a Block,
-// FilterTransform.cpp:190-206): the mask bytes are loaded and balloted ONCE per group of rows and every column's rows go out with
-// the same ranks -- per column the pass then costs sizeof(T) * (1 + selectivity) bytes per row instead of 1 + that.
+// Columns of one element width, NC at a time: what the multi-column filter and replicate kernels take by value.
 template <typename T, int NC>
-struct FilterCols
+struct ColSet
 {
     const T * data[NC];
     T * out[NC];
 };
-template <typename T, int NC, bool STAGED = false>
-__global__ __launch_bounds__(256) void k_filter_scatter_multi(FilterCols<T, NC> c, const u8 * __restrict__ mask, u64 n, const u64 * __restrict__ chunk_offsets, u64 n_chunks)
+
+// One wave takes a chunk in G groups of 64 * R rows: lane l holds rows l * R .. l * R + R - 1 of a group (one 16-B load).
+template <typename T>
+struct ScatterGeo
 {
-    // STAGED: the kept rows of a chunk are compacted in a wave-private LDS buffer first and leave as full 64-lane stores of consecutive
-    // elements (run / 64 store instructions per column instead of one sparse store per row slot)
+    static constexpr int R = 16 / sizeof(T);
+    static constexpr u32 GROUP = 64 * R;
+    static constexpr int G = CHUNK_ROWS / GROUP;
+};
+
+// Where a lane's kept rows of a group go: `before` = kept rows of the lanes below, `total` = kept rows of the whole group.
+// keep(r): this lane's row r is kept.  Every lane of the wave must call it.
+struct GroupRank
+{
+    u32 before, total;
+};
+template <int R, typename Keep>
+__device__ __forceinline__ GroupRank rank_kept(Keep keep)
+{
+    GroupRank k{0, 0};
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+    {
+        const u64 b = __ballot(keep(r));
+        k.before += mbcnt(b);
+        k.total += __popcll(b);
+    }
+    return k;
+}
+
+// this lane's kept rows of one group of one column, in row order, to dst[o], dst[o + 1], ...
+template <int R, typename T, typename Keep, typename Row>
+__device__ __forceinline__ void emit_kept(T * dst, u32 o, Keep keep, Row row)
+{
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+        if (keep(r))
+            dst[o++] = row(r);
+}
+
+// STAGED (4- and 8-byte columns): the kept rows of a chunk are compacted in a wave-private LDS buffer first and leave as full 64-lane
+// stores of consecutive elements (run / 64 store instructions per column instead of one sparse store per row slot).  1- and 2-byte
+// columns store straight to memory: plain stores, L2 merges the partial lines (nontemporal stores there: +25 % time).
+template <typename T>
+constexpr bool FILTER_STAGED = sizeof(T) >= 4;
+
+template <typename T>
+__device__ __forceinline__ void flush_stage(const T * st, T * dst, u32 run, u32 lane)
+{
+    for (u32 i = lane; i < run; i += 64) // LDS operations of one wave complete in order: no barrier
+        dst[i] = st[i];
+}
+
+// ragged tail chunk / unaligned view: same order, guarded scalar accesses
+template <typename T, int NC>
+__device__ __forceinline__ void scatter_chunk_ragged(const ColSet<T, NC> & c, const u8 * __restrict__ mask, u64 n, u64 cbase, u64 pos, u32 lane)
+{
+    typedef ScatterGeo<T> Geo;
+    constexpr int R = Geo::R;
+    for (int g = 0; g < Geo::G; ++g)
+    {
+        const u64 row = cbase + (u64)g * Geo::GROUP + (u64)lane * R;
+        bool keep[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+        {
+            const bool in = row + r < n;
+            keep[r] = in && mask[in ? row + r : 0] != 0;
+        }
+        const GroupRank rank = rank_kept<R>([&](int r) { return keep[r]; });
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            emit_kept<R>(c.out[k] + pos, rank.before, [&](int r) { return keep[r]; }, [&](int r) { return c.data[k][row + r]; });
+        pos += rank.total;
+    }
+}
+
+// NC columns of one element width at once (IColumn::filter over every column of a Block, FilterTransform.cpp:190-206): the mask
+// bytes are loaded and balloted ONCE per group of rows and every column's rows go out with the same ranks -- per column the pass
+// then costs sizeof(T) * (1 + selectivity) bytes per row instead of 1 + that.
+template <typename T, int NC, bool STAGED = FILTER_STAGED<T>>
+__global__ __launch_bounds__(256) void k_filter_scatter_multi(ColSet<T, NC> c, const u8 * __restrict__ mask, u64 n, const u64 * __restrict__ chunk_offsets, u64 n_chunks)
+{
     __shared__ T stage[STAGED ? 4 : 1][STAGED ? CHUNK_ROWS : 1];
     T * const st = stage[STAGED ? (threadIdx.x >> 6) : 0];
-    constexpr int R = 16 / sizeof(T);
-    constexpr u32 GROUP = 64 * R;
-    constexpr int G = CHUNK_ROWS / GROUP;
+    typedef ScatterGeo<T> Geo;
+    constexpr int R = Geo::R, G = Geo::G;
     typedef Vec<T, R> V;
     typedef Vec<u8, R> MV;
     const u32 lane = threadIdx.x & 63;
@@ -966,30 +903,23 @@ __global__ __launch_bounds__(256) void k_filter_scatter_multi(FilterCols<T, NC> 
         aligned = aligned && (((uintptr_t)c.data[k]) & 15) == 0;
     for (u64 chunk = wave0; chunk < n_chunks; chunk += n_waves)
     {
-        const u64 pos0 = chunk_offsets[chunk];
+        const u64 pos = chunk_offsets[chunk];
         const u64 cbase = chunk * CHUNK_ROWS;
         if (aligned && cbase + CHUNK_ROWS <= n)
         {
             MV m[G];
 #pragma unroll
             for (int g = 0; g < G; ++g)
-                m[g] = *(const MV *)(mask + cbase + (u64)g * GROUP + (u64)lane * R);
-            // rank of this lane's first kept row of every group, and what to add per kept row
+                m[g] = *(const MV *)(mask + cbase + (u64)g * Geo::GROUP + (u64)lane * R);
+            // rank inside the chunk of this lane's first kept row of every group
             u32 first[G];
             u32 run = 0;
 #pragma unroll
             for (int g = 0; g < G; ++g)
             {
-                u32 before = 0, total = 0;
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                {
-                    const u64 b = __ballot(m[g].v[r] != 0);
-                    before += mbcnt(b);
-                    total += __popcll(b);
-                }
-                first[g] = run + before;
-                run += total;
+                const GroupRank rank = rank_kept<R>([&](int r) { return m[g].v[r] != 0; });
+                first[g] = run + rank.before;
+                run += rank.total;
             }
 #pragma unroll
             for (int k = 0; k < NC; ++k)
@@ -997,70 +927,70 @@ __global__ __launch_bounds__(256) void k_filter_scatter_multi(FilterCols<T, NC> 
                 V x[G];
 #pragma unroll
                 for (int g = 0; g < G; ++g)
-                    x[g] = *(const V *)(c.data[k] + cbase + (u64)g * GROUP + (u64)lane * R);
+                    x[g] = *(const V *)(c.data[k] + cbase + (u64)g * Geo::GROUP + (u64)lane * R);
+                T * const dst = c.out[k] + pos;
+#pragma unroll
+                for (int g = 0; g < G; ++g)
+                    emit_kept<R>(STAGED ? st : dst, first[g], [&](int r) { return m[g].v[r] != 0; }, [&](int r) { return x[g].v[r]; });
                 if constexpr (STAGED)
-                {
-#pragma unroll
-                    for (int g = 0; g < G; ++g)
-                    {
-                        u32 o = first[g];
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-                            if (m[g].v[r] != 0)
-                                st[o++] = x[g].v[r];
-                    }
-                    T * const dst = c.out[k] + pos0;
-                    for (u32 i = lane; i < run; i += 64) // LDS operations of one wave complete in order: no barrier
-                        dst[i] = st[i];
-                }
-                else
-                {
-#pragma unroll
-                    for (int g = 0; g < G; ++g)
-                    {
-                        u64 o = pos0 + first[g];
-#pragma unroll
-                        for (int r = 0; r < R; ++r)
-                            if (m[g].v[r] != 0)
-                                c.out[k][o++] = x[g].v[r];
-                    }
-                }
+                    flush_stage(st, dst, run, lane);
             }
         }
         else
-        {
-            // ragged tail chunk / unaligned view: same order, guarded scalar accesses
-            u64 pos = pos0;
-            for (int g = 0; g < G; ++g)
-            {
-                const u64 row = cbase + (u64)g * GROUP + (u64)lane * R;
-                bool keep[R];
-                u32 before = 0, total = 0;
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-                {
-                    const bool in = row + r < n;
-                    keep[r] = in && mask[in ? row + r : 0] != 0;
-                    const u64 b = __ballot(keep[r]);
-                    before += mbcnt(b);
-                    total += __popcll(b);
-                }
-#pragma unroll
-                for (int k = 0; k < NC; ++k)
-                {
-                    u64 o = pos + before;
-#pragma unroll
-                    for (int r = 0; r < R; ++r)
-                        if (keep[r])
-                            c.out[k][o++] = c.data[k][row + r];
-                }
-                pos += total;
-            }
-        }
+            scatter_chunk_ragged(c, mask, n, cbase, pos, lane);
     }
 }
 
-__device__ __forceinline__ u32 count_nonzero_bytes16(const uint4 v);
+// One column.  This is k_filter_scatter_multi<T, 1> with the data loaded next to the mask, before the ballots, instead of after
+// them; everything else is shared.  It stays a body of its own because whether that order matters for a single column can only be
+// settled by timing both on the device (tools/bench_filter_multi.py, its 1-column case), and that timing has not been taken yet:
+// until it is, the loads stay where they were.
+template <typename T, bool STAGED = FILTER_STAGED<T>>
+__global__ __launch_bounds__(256) void k_filter_scatter(const T * __restrict__ data, const u8 * __restrict__ mask, u64 n,
+                                                        const u64 * __restrict__ chunk_offsets, u64 n_chunks, T * __restrict__ out)
+{
+    __shared__ T stage[STAGED ? 4 : 1][STAGED ? CHUNK_ROWS : 1];
+    T * const st = stage[STAGED ? (threadIdx.x >> 6) : 0];
+    typedef ScatterGeo<T> Geo;
+    constexpr int R = Geo::R, G = Geo::G;
+    typedef Vec<T, R> V;
+    typedef Vec<u8, R> MV;
+    const u32 lane = threadIdx.x & 63;
+    const u64 wave0 = ((u64)blockIdx.x * 256 + threadIdx.x) >> 6;
+    const u64 n_waves = ((u64)gridDim.x * 256) >> 6;
+    const bool aligned = (((uintptr_t)data) & 15) == 0 && (((uintptr_t)mask) % R) == 0;
+    for (u64 chunk = wave0; chunk < n_chunks; chunk += n_waves)
+    {
+        const u64 pos = chunk_offsets[chunk];
+        const u64 cbase = chunk * CHUNK_ROWS;
+        if (aligned && cbase + CHUNK_ROWS <= n)
+        {
+            V x[G];
+            MV m[G];
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+            {
+                const u64 row = cbase + (u64)g * Geo::GROUP + (u64)lane * R;
+                x[g] = *(const V *)(data + row);
+                m[g] = *(const MV *)(mask + row);
+            }
+            T * const dst = out + pos;
+            u32 run = 0;
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+            {
+                auto keep = [&](int r) { return m[g].v[r] != 0; };
+                const GroupRank rank = rank_kept<R>(keep);
+                emit_kept<R>(STAGED ? st : dst, run + rank.before, keep, [&](int r) { return x[g].v[r]; });
+                run += rank.total;
+            }
+            if constexpr (STAGED)
+                flush_stage(st, dst, run, lane);
+        }
+        else
+            scatter_chunk_ragged(ColSet<T, 1>{{data}, {out}}, mask, n, cbase, pos, lane);
+    }
+}
 
 // countBytesInFilter (ColumnsCommon.cpp:31-58): non-zero bytes of the mask.  16-byte nontemporal loads, four in flight per
 // lane, a 5-op bit trick per 4 bytes (the generic filter+sum kernel instantiated for UInt8 did ~3 VALU ops per BYTE and ran
@@ -1070,27 +1000,21 @@ __global__ __launch_bounds__(256) void k_count_nonzero(const u8 * __restrict__ m
     constexpr int U = 4;
     u64 c = 0;
     const u64 nvec = n / 16;
-    typedef u32 v4u __attribute__((ext_vector_type(4)));
-    const v4u * __restrict__ mv = (const v4u *)mask;
-    auto nz16 = [](const v4u v) {
-        uint4 q;
-        q.x = v.x, q.y = v.y, q.z = v.z, q.w = v.w;
-        return count_nonzero_bytes16(q);
-    };
+    const u32x4 * __restrict__ mv = (const u32x4 *)mask;
     const u64 stride = (u64)gridDim.x * 256;
     u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     for (; i + (u64)(U - 1) * stride < nvec; i += (u64)U * stride)
     {
-        v4u v[U];
+        u32x4 v[U];
 #pragma unroll
         for (int k = 0; k < U; ++k)
             v[k] = __builtin_nontemporal_load(&mv[i + (u64)k * stride]);
 #pragma unroll
         for (int k = 0; k < U; ++k)
-            c += nz16(v[k]);
+            c += count_nonzero_bytes16(v[k]);
     }
     for (; i < nvec; i += stride)
-        c += nz16(mv[i]);
+        c += count_nonzero_bytes16(mv[i]);
     for (u64 r = nvec * 16 + (u64)blockIdx.x * 256 + threadIdx.x; r < n; r += stride)
         c += mask[r] != 0;
     c = wave_reduce_add_u64(c);
@@ -1120,14 +1044,11 @@ extern "C" int chgpu_count_bytes_in_filter(chgpu_ctx * ctx, const chgpu_col * ma
         CmpSpec spec;
         const u8 zero = 0;
         CHGPU_TRY(make_cmp_spec(CHGPU_U8, CHGPU_NE, CHGPU_U8, &zero, &spec));
-        const u32 grid_cap = (u32)ctx->num_cus * 8;
-        CHGPU_TRY(chgpu_scratch(ctx, (size_t)grid_cap * 2 * sizeof(u64) + 64, &scratch));
-        u64 * res2 = (u64 *)((char *)scratch + (size_t)grid_cap * 2 * sizeof(u64));
+        u64 * res2 = nullptr;
+        CHGPU_TRY(fs_result_slot(ctx, nullptr, &res2));
         CHGPU_TRY(launch_filter_sum(ctx, CHGPU_U8, mask->data, mask->data, nullptr, mask->rows, &spec, res2));
-        u64 res[2];
-        CHGPU_TRY(chgpu_read_back(ctx, res2, res, sizeof(res)));
-        *count = res[1];
-        return CHGPU_OK;
+        u64 sum_bits;
+        return fs_read_result(ctx, res2, &sum_bits, count);
     }
     u64 res = 0;
     CHGPU_TRY(chgpu_read_back(ctx, result_dev, &res, sizeof(res)));
@@ -1168,39 +1089,16 @@ static int filter_plan(chgpu_ctx * ctx, const chgpu_col * mask, FilterPlan * fp)
     fp->grid = chgpu_grid_for(ctx, n_chunks * 64, 256, wg_sc);
     return CHGPU_OK;
 }
-// 4- and 8-byte columns: kept rows compacted in LDS, full-width stores (A/B: CHGPU_TUNE_FILTER_NO_STAGED)
-static bool filter_staged(const chgpu_ctx * ctx)
-{
-    const bool on = chgpu_opt(ctx, "tune_filter_no_staged", 0) == 0;
-    return on;
-}
 static int filter_apply(chgpu_ctx * ctx, const chgpu_col * col, const chgpu_col * mask, const FilterPlan & fp, chgpu_col ** out)
 {
     chgpu_col * res = nullptr;
     CHGPU_TRY(chgpu_col_new(ctx, col->type, fp.total, &res));
     if (fp.total)
     {
-        switch (chgpu_type_size(col->type))
-        {
-            case 8:
-                if (filter_staged(ctx))
-                    hipLaunchKernelGGL((k_filter_scatter<u64, true>), dim3(fp.grid), dim3(256), 0, ctx->stream, (const u64 *)col->data, (const u8 *)mask->data, fp.n, fp.offsets, fp.n_chunks, (u64 *)res->data);
-                else
-                    hipLaunchKernelGGL((k_filter_scatter<u64, false>), dim3(fp.grid), dim3(256), 0, ctx->stream, (const u64 *)col->data, (const u8 *)mask->data, fp.n, fp.offsets, fp.n_chunks, (u64 *)res->data);
-                break;
-            case 4:
-                if (filter_staged(ctx))
-                    hipLaunchKernelGGL((k_filter_scatter<u32, true>), dim3(fp.grid), dim3(256), 0, ctx->stream, (const u32 *)col->data, (const u8 *)mask->data, fp.n, fp.offsets, fp.n_chunks, (u32 *)res->data);
-                else
-                    hipLaunchKernelGGL((k_filter_scatter<u32, false>), dim3(fp.grid), dim3(256), 0, ctx->stream, (const u32 *)col->data, (const u8 *)mask->data, fp.n, fp.offsets, fp.n_chunks, (u32 *)res->data);
-                break;
-            case 2:
-                hipLaunchKernelGGL(k_filter_scatter<u16>, dim3(fp.grid), dim3(256), 0, ctx->stream, (const u16 *)col->data, (const u8 *)mask->data, fp.n, fp.offsets, fp.n_chunks, (u16 *)res->data);
-                break;
-            default:
-                hipLaunchKernelGGL(k_filter_scatter<u8>, dim3(fp.grid), dim3(256), 0, ctx->stream, (const u8 *)col->data, (const u8 *)mask->data, fp.n, fp.offsets, fp.n_chunks, (u8 *)res->data);
-                break;
-        }
+        dispatch_width(chgpu_type_size(col->type), [&](auto tag) {
+            typedef decltype(tag) T;
+            hipLaunchKernelGGL(k_filter_scatter<T>, dim3(fp.grid), dim3(256), 0, ctx->stream, (const T *)col->data, (const u8 *)mask->data, fp.n, fp.offsets, fp.n_chunks, (T *)res->data);
+        });
         ctx->counters[6] += 1;
     }
     hipError_t e = hipGetLastError();
@@ -1251,10 +1149,10 @@ __global__ __launch_bounds__(256) void k_filter_emit_indices(const u8 * __restri
         {
             const u64 i = chunk * CHUNK_ROWS + st * 64 + lane;
             const bool keep = i < n && mask[i] != 0;
-            const u64 b = __ballot(keep);
+            const GroupRank rank = rank_kept<1>([&](int) { return keep; });
             if (keep)
-                out[pos + mbcnt(b)] = i;
-            pos += (u64)__popcll(b);
+                out[pos + rank.before] = i;
+            pos += rank.total;
         }
     }
 }
@@ -1290,6 +1188,60 @@ extern "C" int chgpu_filter_to_indices(chgpu_ctx * ctx, const chgpu_col * mask, 
     return CHGPU_OK;
 }
 
+// A Block's columns, for the kernels that take several columns of one element width at once: the 8-byte and then the 4-byte
+// columns go to fn(width, idx, nc) up to max_nc at a time (never one alone), every column left over goes alone, in column order.
+// idx[0..nc) are the columns' positions in `cols`.  An error from fn ends the walk.
+template <typename F>
+static int for_each_width_batch(const chgpu_col * const * cols, u32 n_cols, u32 max_nc, F && fn)
+{
+    std::vector<char> done(n_cols, 0);
+    for (size_t w : {(size_t)8, (size_t)4})
+    {
+        if (max_nc < 2)
+            break;
+        std::vector<u32> same;
+        for (u32 k = 0; k < n_cols; ++k)
+            if (chgpu_type_size(cols[k]->type) == w)
+                same.push_back(k);
+        for (size_t b = 0; b + 1 < same.size();)
+        {
+            const u32 nc = (u32)(same.size() - b >= max_nc ? max_nc : same.size() - b);
+            CHGPU_TRY(fn(w, &same[b], nc));
+            for (u32 q = 0; q < nc; ++q)
+                done[same[b + q]] = 1;
+            b += nc;
+        }
+    }
+    for (u32 k = 0; k < n_cols; ++k)
+        if (!done[k])
+            CHGPU_TRY(fn(chgpu_type_size(cols[k]->type), &k, 1u));
+    return CHGPU_OK;
+}
+
+template <typename T, int NC>
+static ColSet<T, NC> make_col_set(const chgpu_col * const * cols, chgpu_col * const * outs, const u32 * idx)
+{
+    ColSet<T, NC> c;
+    for (int q = 0; q < NC; ++q)
+    {
+        c.data[q] = (const T *)cols[idx[q]]->data;
+        c.out[q] = (T *)outs[idx[q]]->data;
+    }
+    return c;
+}
+
+// error exit of the calls that fill an array of output columns: give back what was made so far
+static int free_outs(chgpu_col ** outs, u32 n_cols, int rc)
+{
+    for (u32 q = 0; q < n_cols; ++q)
+        if (outs[q])
+        {
+            chgpu_col_free(outs[q]);
+            outs[q] = nullptr;
+        }
+    return rc;
+}
+
 extern "C" int chgpu_filter_columns(chgpu_ctx * ctx, uint32_t n_cols, const chgpu_col * const * cols, const chgpu_col * mask,
                                     int64_t result_size_hint, chgpu_col ** outs, uint64_t * out_rows)
 {
@@ -1307,74 +1259,31 @@ extern "C" int chgpu_filter_columns(chgpu_ctx * ctx, uint32_t n_cols, const chgp
     FilterPlan fp;
     if (mask->rows)
         CHGPU_TRY(filter_plan(ctx, mask, &fp)); // the mask is counted and scanned ONCE for the whole Block
-    auto fail = [&](int rc) {
-        for (u32 q = 0; q < n_cols; ++q)
-            if (outs[q])
-            {
-                chgpu_col_free(outs[q]);
-                outs[q] = nullptr;
-            }
-        return rc;
-    };
     // columns of one element width go through k_filter_scatter_multi up to six at a time: one read of the mask for all of them
-    const bool no_multi = chgpu_opt(ctx, "tune_filter_no_multi", 0) != 0;
-    const bool staged = filter_staged(ctx);
-    std::vector<char> done(n_cols, 0);
-    if (mask->rows && fp.total && !no_multi)
-        for (size_t w : {(size_t)8, (size_t)4})
-        {
-            std::vector<u32> same;
-            for (u32 k = 0; k < n_cols; ++k)
-                if (chgpu_type_size(cols[k]->type) == w)
-                    same.push_back(k);
-            for (size_t b = 0; b + 1 < same.size();)
-            {
-                const u32 nc = (u32)(same.size() - b >= 6 ? 6 : same.size() - b);
-                if (nc < 2)
-                    break;
-                for (u32 q = 0; q < nc; ++q)
-                {
-                    const int rc = chgpu_col_new(ctx, cols[same[b + q]]->type, fp.total, &outs[same[b + q]]);
-                    if (rc != CHGPU_OK)
-                        return fail(rc);
-                }
-#define FILTER_MULTI(T_, NC_)                                                                                                                  \
-    do                                                                                                                                         \
-    {                                                                                                                                          \
-        FilterCols<T_, NC_> fc;                                                                                                                \
-        for (u32 q = 0; q < NC_; ++q)                                                                                                          \
-        {                                                                                                                                      \
-            fc.data[q] = (const T_ *)cols[same[b + q]]->data;                                                                                  \
-            fc.out[q] = (T_ *)outs[same[b + q]]->data;                                                                                         \
-        }                                                                                                                                      \
-        if (staged)                                                                                                                            \
-            hipLaunchKernelGGL((k_filter_scatter_multi<T_, NC_, true>), dim3(fp.grid), dim3(256), 0, ctx->stream, fc, (const u8 *)mask->data, fp.n, (const u64 *)fp.offsets, fp.n_chunks); \
-        else                                                                                                                                   \
-            hipLaunchKernelGGL((k_filter_scatter_multi<T_, NC_, false>), dim3(fp.grid), dim3(256), 0, ctx->stream, fc, (const u8 *)mask->data, fp.n, (const u64 *)fp.offsets, fp.n_chunks); \
-    } while (0)
-                if (w == 8) { if (nc == 6) FILTER_MULTI(u64, 6); else if (nc == 5) FILTER_MULTI(u64, 5); else if (nc == 4) FILTER_MULTI(u64, 4); else if (nc == 3) FILTER_MULTI(u64, 3); else FILTER_MULTI(u64, 2); }
-                else        { if (nc == 6) FILTER_MULTI(u32, 6); else if (nc == 5) FILTER_MULTI(u32, 5); else if (nc == 4) FILTER_MULTI(u32, 4); else if (nc == 3) FILTER_MULTI(u32, 3); else FILTER_MULTI(u32, 2); }
-#undef FILTER_MULTI
-                ctx->counters[6] += 1;
-                if (hipGetLastError() != hipSuccess)
-                    return fail(chgpu_set_error(CHGPU_ERR_DEVICE, "filter launch failed"));
-                for (u32 q = 0; q < nc; ++q)
-                {
-                    done[same[b + q]] = 1;
-                    ctx->counters[0] += fp.total;
-                    ctx->counters[1] += fp.total * w;
-                }
-                b += nc;
-            }
-        }
-    for (u32 k = 0; k < n_cols; ++k)
-    {
-        if (done[k])
-            continue;
-        const int rc = mask->rows ? filter_apply(ctx, cols[k], mask, fp, &outs[k]) : chgpu_col_new(ctx, cols[k]->type, 0, &outs[k]);
-        if (rc != CHGPU_OK)
-            return fail(rc);
-    }
+    const bool multi = fp.total && chgpu_opt(ctx, "tune_filter_no_multi", 0) == 0;
+    const int rc = for_each_width_batch(cols, n_cols, multi ? 6 : 1, [&](size_t w, const u32 * idx, u32 nc) -> int {
+        if (nc == 1)
+            return mask->rows ? filter_apply(ctx, cols[idx[0]], mask, fp, &outs[idx[0]]) : chgpu_col_new(ctx, cols[idx[0]]->type, 0, &outs[idx[0]]);
+        for (u32 q = 0; q < nc; ++q)
+            CHGPU_TRY(chgpu_col_new(ctx, cols[idx[q]]->type, fp.total, &outs[idx[q]]));
+        auto launch = [&](auto tag) {
+            typedef decltype(tag) T;
+            dispatch_const<2, 6>(nc, [&](auto nc_c) {
+                constexpr int NC = decltype(nc_c)::value;
+                hipLaunchKernelGGL((k_filter_scatter_multi<T, NC>), dim3(fp.grid), dim3(256), 0, ctx->stream, make_col_set<T, NC>(cols, outs, idx),
+                                   (const u8 *)mask->data, fp.n, (const u64 *)fp.offsets, fp.n_chunks);
+            });
+        };
+        if (w == 8) launch(u64{}); else launch(u32{});
+        ctx->counters[6] += 1;
+        if (hipGetLastError() != hipSuccess)
+            return chgpu_set_error(CHGPU_ERR_DEVICE, "filter launch failed");
+        ctx->counters[0] += fp.total * nc;
+        ctx->counters[1] += fp.total * w * nc;
+        return CHGPU_OK;
+    });
+    if (rc != CHGPU_OK)
+        return free_outs(outs, n_cols, rc);
     *out_rows = fp.total;
     return CHGPU_OK;
 }
@@ -1412,74 +1321,24 @@ extern "C" int chgpu_index(chgpu_ctx * ctx, const chgpu_col * col, const chgpu_c
     if (limit)
     {
         const u32 grid = chgpu_grid_for(ctx, limit, 256, 8);
-        const size_t es = chgpu_type_size(col->type);
-#define IDX_LAUNCH(T, I) hipLaunchKernelGGL((k_index<T, I>), dim3(grid), dim3(256), 0, ctx->stream, (const T *)col->data, (const I *)indexes->data, limit, col->rows, default_for_missing, (T *)res->data)
-        if (indexes->type == CHGPU_U64)
-        {
-            if (es == 8) IDX_LAUNCH(u64, u64); else if (es == 4) IDX_LAUNCH(u32, u64); else if (es == 2) IDX_LAUNCH(u16, u64); else IDX_LAUNCH(u8, u64);
-        }
-        else
-        {
-            if (es == 8) IDX_LAUNCH(u64, u32); else if (es == 4) IDX_LAUNCH(u32, u32); else if (es == 2) IDX_LAUNCH(u16, u32); else IDX_LAUNCH(u8, u32);
-        }
-#undef IDX_LAUNCH
+        dispatch_width(chgpu_type_size(col->type), [&](auto tag) {
+            typedef decltype(tag) T;
+            auto launch = [&](auto itag) {
+                typedef decltype(itag) I;
+                hipLaunchKernelGGL((k_index<T, I>), dim3(grid), dim3(256), 0, ctx->stream, (const T *)col->data, (const I *)indexes->data, limit, col->rows, default_for_missing, (T *)res->data);
+            };
+            if (indexes->type == CHGPU_U64) launch(u64{}); else launch(u32{});
+        });
         ctx->counters[6] += 1;
     }
     *out = res;
     return CHGPU_OK;
 }
 
-template <typename T>
-__global__ __launch_bounds__(256) void k_replicate(const T * __restrict__ data, const u64 * __restrict__ offsets, u64 n, T * __restrict__ out)
-{
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
-    {
-        const u64 end = offsets[i];
-        const u64 begin = i ? offsets[i - 1] : 0;
-        const T v = data[i];
-        for (u64 o = begin; o < end; ++o)
-            out[o] = v;
-    }
-}
-
-extern "C" int chgpu_replicate(chgpu_ctx * ctx, const chgpu_col * col, const chgpu_col * offsets, chgpu_col ** out)
-{
-    ChgpuDeviceGuard _dev_guard(ctx);
-    CHGPU_REQUIRE(ctx && col && offsets && out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(offsets->type == CHGPU_U64, CHGPU_ERR_BAD_ARGUMENTS, "offsets must be UInt64");
-    CHGPU_REQUIRE(offsets->rows == col->rows, CHGPU_ERR_SIZES_MISMATCH, "Size of offsets doesn't match size of column."); // ColumnVector.cpp:881-883
-    u64 total = 0;
-    if (col->rows)
-        CHGPU_TRY(chgpu_read_back(ctx, (const u64 *)offsets->data + (col->rows - 1), &total, sizeof(total)));
-    chgpu_col * res = nullptr;
-    CHGPU_TRY(chgpu_col_new(ctx, col->type, total, &res));
-    if (total)
-    {
-        const u32 grid = chgpu_grid_for(ctx, col->rows, 256, 8);
-        switch (chgpu_type_size(col->type))
-        {
-            case 8: hipLaunchKernelGGL(k_replicate<u64>, dim3(grid), dim3(256), 0, ctx->stream, (const u64 *)col->data, (const u64 *)offsets->data, col->rows, (u64 *)res->data); break;
-            case 4: hipLaunchKernelGGL(k_replicate<u32>, dim3(grid), dim3(256), 0, ctx->stream, (const u32 *)col->data, (const u64 *)offsets->data, col->rows, (u32 *)res->data); break;
-            case 2: hipLaunchKernelGGL(k_replicate<u16>, dim3(grid), dim3(256), 0, ctx->stream, (const u16 *)col->data, (const u64 *)offsets->data, col->rows, (u16 *)res->data); break;
-            default: hipLaunchKernelGGL(k_replicate<u8>, dim3(grid), dim3(256), 0, ctx->stream, (const u8 *)col->data, (const u64 *)offsets->data, col->rows, (u8 *)res->data); break;
-        }
-        ctx->counters[6] += 1;
-    }
-    *out = res;
-    return CHGPU_OK;
-}
-
-// The same for every column of a Block (joinBlock replicates all left columns with one offsets_to_replicate,
-// HashJoinMethodsImpl.h:186-194): one read-back of the total, and columns of one element width go through one kernel up to four at a
-// time -- the 8-byte offsets are read once for all of them instead of once per column.
+// Row i of every column goes out offsets[i] - offsets[i - 1] times.  NC columns of one element width at once: the 8-byte offsets are
+// read once for all of them instead of once per column.
 template <typename T, int NC>
-struct ReplCols
-{
-    const T * data[NC];
-    T * out[NC];
-};
-template <typename T, int NC>
-__global__ __launch_bounds__(256) void k_replicate_multi(ReplCols<T, NC> c, const u64 * __restrict__ offsets, u64 n)
+__global__ __launch_bounds__(256) void k_replicate_multi(ColSet<T, NC> c, const u64 * __restrict__ offsets, u64 n)
 {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
     {
@@ -1496,6 +1355,46 @@ __global__ __launch_bounds__(256) void k_replicate_multi(ReplCols<T, NC> c, cons
     }
 }
 
+// cols[idx[0..nc)], all `w` bytes wide and already allocated in `outs`, through one kernel; a batch of several is 4 or 8 bytes wide
+static void launch_replicate(chgpu_ctx * ctx, size_t w, const chgpu_col * const * cols, chgpu_col * const * outs, const u32 * idx, u32 nc, const chgpu_col * offsets)
+{
+    const u64 n = offsets->rows;
+    const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
+    auto launch = [&](auto tag, auto nc_c) {
+        typedef decltype(tag) T;
+        constexpr int NC = decltype(nc_c)::value;
+        hipLaunchKernelGGL((k_replicate_multi<T, NC>), dim3(grid), dim3(256), 0, ctx->stream, make_col_set<T, NC>(cols, outs, idx), (const u64 *)offsets->data, n);
+    };
+    if (nc == 1)
+        dispatch_width(w, [&](auto tag) { launch(tag, std::integral_constant<int, 1>{}); });
+    else
+        dispatch_const<2, 4>(nc, [&](auto nc_c) { if (w == 8) launch(u64{}, nc_c); else launch(u32{}, nc_c); });
+    ctx->counters[6] += 1;
+}
+
+extern "C" int chgpu_replicate(chgpu_ctx * ctx, const chgpu_col * col, const chgpu_col * offsets, chgpu_col ** out)
+{
+    ChgpuDeviceGuard _dev_guard(ctx);
+    CHGPU_REQUIRE(ctx && col && offsets && out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_REQUIRE(offsets->type == CHGPU_U64, CHGPU_ERR_BAD_ARGUMENTS, "offsets must be UInt64");
+    CHGPU_REQUIRE(offsets->rows == col->rows, CHGPU_ERR_SIZES_MISMATCH, "Size of offsets doesn't match size of column."); // ColumnVector.cpp:881-883
+    u64 total = 0;
+    if (col->rows)
+        CHGPU_TRY(chgpu_read_back(ctx, (const u64 *)offsets->data + (col->rows - 1), &total, sizeof(total)));
+    chgpu_col * res = nullptr;
+    CHGPU_TRY(chgpu_col_new(ctx, col->type, total, &res));
+    if (total)
+    {
+        const u32 first = 0;
+        launch_replicate(ctx, chgpu_type_size(col->type), &col, &res, &first, 1, offsets);
+    }
+    *out = res;
+    return CHGPU_OK;
+}
+
+// The same for every column of a Block (joinBlock replicates all left columns with one offsets_to_replicate,
+// HashJoinMethodsImpl.h:186-194): one read-back of the total, and columns of one element width go through one kernel up to four at a
+// time.
 extern "C" int chgpu_replicate_columns(chgpu_ctx * ctx, uint32_t n_cols, const chgpu_col * const * cols, const chgpu_col * offsets, chgpu_col ** outs)
 {
     ChgpuDeviceGuard _dev_guard(ctx);
@@ -1511,71 +1410,20 @@ extern "C" int chgpu_replicate_columns(chgpu_ctx * ctx, uint32_t n_cols, const c
     u64 total = 0;
     if (n)
         CHGPU_TRY(chgpu_read_back(ctx, (const u64 *)offsets->data + (n - 1), &total, sizeof(total)));
-    auto fail = [&](int rc) {
-        for (u32 q = 0; q < n_cols; ++q)
-            if (outs[q])
-            {
-                chgpu_col_free(outs[q]);
-                outs[q] = nullptr;
-            }
-        return rc;
-    };
     for (u32 k = 0; k < n_cols; ++k)
     {
         const int rc = chgpu_col_new(ctx, cols[k]->type, total, &outs[k]);
         if (rc != CHGPU_OK)
-            return fail(rc);
+            return free_outs(outs, n_cols, rc);
     }
     if (!total)
         return CHGPU_OK;
-    const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
-    std::vector<char> done(n_cols, 0);
-    for (size_t w : {(size_t)8, (size_t)4})
-    {
-        std::vector<u32> same;
-        for (u32 k = 0; k < n_cols; ++k)
-            if (chgpu_type_size(cols[k]->type) == w)
-                same.push_back(k);
-        for (size_t b = 0; b + 1 < same.size();)
-        {
-            const u32 nc = (u32)(same.size() - b >= 4 ? 4 : same.size() - b);
-            if (nc < 2)
-                break;
-#define REPL_MULTI(T_, NC_)                                                                                                        \
-    do                                                                                                                             \
-    {                                                                                                                              \
-        ReplCols<T_, NC_> rc_;                                                                                                     \
-        for (u32 q = 0; q < NC_; ++q)                                                                                              \
-        {                                                                                                                          \
-            rc_.data[q] = (const T_ *)cols[same[b + q]]->data;                                                                     \
-            rc_.out[q] = (T_ *)outs[same[b + q]]->data;                                                                            \
-        }                                                                                                                          \
-        hipLaunchKernelGGL((k_replicate_multi<T_, NC_>), dim3(grid), dim3(256), 0, ctx->stream, rc_, (const u64 *)offsets->data, n); \
-    } while (0)
-            if (w == 8) { if (nc == 4) REPL_MULTI(u64, 4); else if (nc == 3) REPL_MULTI(u64, 3); else REPL_MULTI(u64, 2); }
-            else        { if (nc == 4) REPL_MULTI(u32, 4); else if (nc == 3) REPL_MULTI(u32, 3); else REPL_MULTI(u32, 2); }
-#undef REPL_MULTI
-            ctx->counters[6] += 1;
-            for (u32 q = 0; q < nc; ++q)
-                done[same[b + q]] = 1;
-            b += nc;
-        }
-    }
-    for (u32 k = 0; k < n_cols; ++k)
-    {
-        if (done[k])
-            continue;
-        switch (chgpu_type_size(cols[k]->type))
-        {
-            case 8: hipLaunchKernelGGL(k_replicate<u64>, dim3(grid), dim3(256), 0, ctx->stream, (const u64 *)cols[k]->data, (const u64 *)offsets->data, n, (u64 *)outs[k]->data); break;
-            case 4: hipLaunchKernelGGL(k_replicate<u32>, dim3(grid), dim3(256), 0, ctx->stream, (const u32 *)cols[k]->data, (const u64 *)offsets->data, n, (u32 *)outs[k]->data); break;
-            case 2: hipLaunchKernelGGL(k_replicate<u16>, dim3(grid), dim3(256), 0, ctx->stream, (const u16 *)cols[k]->data, (const u64 *)offsets->data, n, (u16 *)outs[k]->data); break;
-            default: hipLaunchKernelGGL(k_replicate<u8>, dim3(grid), dim3(256), 0, ctx->stream, (const u8 *)cols[k]->data, (const u64 *)offsets->data, n, (u8 *)outs[k]->data); break;
-        }
-        ctx->counters[6] += 1;
-    }
+    (void)for_each_width_batch(cols, n_cols, 4, [&](size_t w, const u32 * idx, u32 nc) {
+        launch_replicate(ctx, w, cols, outs, idx, nc, offsets);
+        return CHGPU_OK;
+    });
     if (hipGetLastError() != hipSuccess)
-        return fail(chgpu_set_error(CHGPU_ERR_DEVICE, "replicate launch failed"));
+        return free_outs(outs, n_cols, chgpu_set_error(CHGPU_ERR_DEVICE, "replicate launch failed"));
     return CHGPU_OK;
 }
 
@@ -1702,18 +1550,63 @@ struct ExprSpec
     u32 val_a, val_b;
 };
 
+// the range test on a key of K = u32 or u64 (K's low bits of the folded constants), before the inversion
+template <typename K>
+__device__ __forceinline__ bool key_in_range(K x, K flip, K lo, K span)
+{
+    return ((x ^ flip) - lo) <= span;
+}
+template <typename K>
+__device__ __forceinline__ bool expr_in_range(const ExprPred & p, K x)
+{
+    return key_in_range<K>(x, (K)p.flip, (K)p.lo, (K)p.span);
+}
+
 template <typename T>
 __device__ __forceinline__ bool expr_pass(const ExprPred & p, T x)
 {
+    bool in;
     if constexpr (sizeof(T) <= 4)
-    {
-        const u32 key = (u32)x ^ (u32)p.flip; // the sign flip for signed 4-byte types is folded to bit 31
-        return ((key - (u32)p.lo) <= (u32)p.span) != (p.invert != 0);
-    }
+        in = expr_in_range<u32>(p, (u32)x); // the sign flip for signed 4-byte types is folded to bit 31
     else
+        in = expr_in_range<u64>(p, (u64)x);
+    return in != (p.invert != 0);
+}
+
+// column k's elements become the value expression's operands where it names that column (wave-uniform branches); a 64-bit operand
+// array takes them sign- or zero-extended, a 32-bit one as they are
+template <typename X, typename V, int N>
+__device__ __forceinline__ void expr_take_values(const ExprSpec & sp, u32 k, const X (&x)[N], V (&va)[N], V (&vb)[N])
+{
+    auto take = [&](V (&v)[N]) {
+#pragma unroll
+        for (int e = 0; e < N; ++e)
+            v[e] = (V)ext64(x[e]);
+    };
+    if (sp.val_a == k)
+        take(va);
+    if (sp.value_op != CHGPU_VAL_COL && sp.val_b == k)
+        take(vb);
+}
+
+// the closing fold of N rows: value = a, or a OP b, summed and counted where the row passed.  32-bit operands are widened here by
+// their column's signedness.
+template <typename V, int N>
+__device__ __forceinline__ void expr_fold_rows(const ExprSpec & sp, const bool (&pass)[N], const V (&va)[N], const V (&vb)[N], bool a_signed, bool b_signed,
+                                               u64 & s, u64 & c)
+{
+#pragma unroll
+    for (int e = 0; e < N; ++e)
     {
-        const u64 key = (u64)x ^ p.flip;
-        return ((key - p.lo) <= p.span) != (p.invert != 0);
+        u64 xa = va[e], xb = vb[e];
+        if constexpr (sizeof(V) == 4)
+        {
+            xa = a_signed ? (u64)(i64)(i32)va[e] : (u64)va[e];
+            xb = b_signed ? (u64)(i64)(i32)vb[e] : (u64)vb[e];
+        }
+        const u64 v = sp.value_op == CHGPU_VAL_COL ? xa : apply_val(sp.value_op, xa, xb);
+        s += pass[e] ? v : 0;
+        c += pass[e] ? 1 : 0;
     }
 }
 
@@ -1755,30 +1648,13 @@ __global__ __launch_bounds__(FS_THREADS) void k_expr_filter_sum(ExprSpec sp, u64
                     for (int e = 0; e < E; ++e)
                         pass[e] = pass[e] && expr_pass<T>(pr, x[e]);
                 }
-            if (sp.val_a == k)
-            {
-#pragma unroll
-                for (int e = 0; e < E; ++e)
-                    va[e] = ext64(x[e]);
-            }
-            if (sp.value_op != CHGPU_VAL_COL && sp.val_b == k)
-            {
-#pragma unroll
-                for (int e = 0; e < E; ++e)
-                    vb[e] = ext64(x[e]);
-            }
+            expr_take_values(sp, k, x, va, vb);
         };
         column(0, x0);
         if (sp.n_cols > 1) column(1, x1);
         if (sp.n_cols > 2) column(2, x2);
         if (sp.n_cols > 3) column(3, x3);
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-        {
-            const u64 v = sp.value_op == CHGPU_VAL_COL ? va[e] : apply_val(sp.value_op, va[e], vb[e]);
-            s += pass[e] ? v : 0;
-            c += pass[e] ? 1 : 0;
-        }
+        expr_fold_rows(sp, pass, va, vb, false, false, s, c);
     };
 
     constexpr u64 CHUNK = (u64)UNROLL * FS_THREADS;
@@ -1830,27 +1706,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_expr_filter_sum(ExprSpec sp, u64
         reduce_rows(x0, x1, x2, x3, 1);
     }
 
-    __shared__ u64 lds_s[FS_THREADS / WAVE];
-    __shared__ u64 lds_c[FS_THREADS / WAVE];
-    s = wave_reduce_add_u64(s);
-    c = wave_reduce_add_u64(c);
-    if ((threadIdx.x & 63) == 0)
-    {
-        lds_s[threadIdx.x >> 6] = s;
-        lds_c[threadIdx.x >> 6] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        u64 ss = 0, cc = 0;
-        for (int w = 0; w < FS_THREADS / WAVE; ++w)
-        {
-            ss += lds_s[w];
-            cc += lds_c[w];
-        }
-        part_sum[blockIdx.x] = ss;
-        part_cnt[blockIdx.x] = cc;
-    }
+    fs_fold_workgroup(s, c, part_sum, part_cnt);
 }
 
 // Columns of DIFFERENT integer widths, general case (any mix of 1-, 4- and 8-byte columns): one row per lane and step, four
@@ -1911,60 +1767,19 @@ __global__ __launch_bounds__(FS_THREADS) void k_expr_filter_sum_mixed(ExprSpec s
                     continue;
                 const ExprPred pr = sp.pred[q];
 #pragma unroll
-                for (int u = 0; u < U; ++u)
-                {
-                    // narrow columns: the 32-bit key test on the low word (exactly expr_pass<u32/i32/u8>); wide: the 64-bit one
-                    const bool ok = narrow ? ((((u32)x[u] ^ (u32)pr.flip) - (u32)pr.lo) <= (u32)pr.span) : (((x[u] ^ pr.flip) - pr.lo) <= pr.span);
-                    pass[u] = pass[u] && (ok != (pr.invert != 0));
-                }
+                for (int u = 0; u < U; ++u) // narrow columns: the 32-bit key test on the low word; wide: the 64-bit one
+                    pass[u] = pass[u] && ((narrow ? expr_in_range<u32>(pr, (u32)x[u]) : expr_in_range<u64>(pr, x[u])) != (pr.invert != 0));
             }
-            if (sp.val_a == k)
-            {
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    va[u] = x[u];
-            }
-            if (sp.value_op != CHGPU_VAL_COL && sp.val_b == k)
-            {
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    vb[u] = x[u];
-            }
+            expr_take_values(sp, k, x, va, vb);
         };
         column(0, x0);
         if (sp.n_cols > 1) column(1, x1);
         if (sp.n_cols > 2) column(2, x2);
         if (sp.n_cols > 3) column(3, x3);
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-        {
-            const u64 v = sp.value_op == CHGPU_VAL_COL ? va[u] : apply_val(sp.value_op, va[u], vb[u]);
-            s += pass[u] ? v : 0;
-            c += pass[u] ? 1 : 0;
-        }
+        expr_fold_rows(sp, pass, va, vb, false, false, s, c);
     }
 
-    __shared__ u64 lds_s[FS_THREADS / WAVE];
-    __shared__ u64 lds_c[FS_THREADS / WAVE];
-    s = wave_reduce_add_u64(s);
-    c = wave_reduce_add_u64(c);
-    if ((threadIdx.x & 63) == 0)
-    {
-        lds_s[threadIdx.x >> 6] = s;
-        lds_c[threadIdx.x >> 6] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        u64 ss = 0, cc = 0;
-        for (int w = 0; w < FS_THREADS / WAVE; ++w)
-        {
-            ss += lds_s[w];
-            cc += lds_c[w];
-        }
-        part_sum[blockIdx.x] = ss;
-        part_cnt[blockIdx.x] = cc;
-    }
+    fs_fold_workgroup(s, c, part_sum, part_cnt);
 }
 
 // The common mixed case -- every column 1 or 4 bytes wide (SSB lineorder) -- with ALL loads of an iteration issued before the
@@ -1981,7 +1796,6 @@ __global__ __launch_bounds__(FS_THREADS) void k_expr_filter_sum_narrow(ExprSpec 
 #define EXN_UNROLL 2 // 4 units per lane needed 256 VGPRs (1 wave/SIMD)
 #endif
     constexpr int U = EXN_UNROLL, E = 4 * U;
-    typedef u32 v4u __attribute__((ext_vector_type(4)));
     u64 s = 0, c = 0;
     const u64 n_units = n / 4;
     constexpr u64 CHUNK = (u64)U * FS_THREADS;
@@ -2000,7 +1814,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_expr_filter_sum_narrow(ExprSpec 
         p_inv[q] = on ? sp.pred[q].invert : 0;
         p_col[q] = on ? sp.pred[q].col : 0xFFu;
     }
-    auto load_col = [&](auto kc, u64 unit0, v4u (&raw)[U]) {
+    auto load_col = [&](auto kc, u64 unit0, u32x4 (&raw)[U]) {
         constexpr u32 k = decltype(kc)::value;
         if constexpr (((WMASK >> k) & 1) == 0)
         {
@@ -2012,34 +1826,23 @@ __global__ __launch_bounds__(FS_THREADS) void k_expr_filter_sum_narrow(ExprSpec 
         {
 #pragma unroll
             for (int u = 0; u < U; ++u)
-                raw[u] = __builtin_nontemporal_load((const v4u *)sp.col[k] + unit0 + (u64)u * FS_THREADS);
+                raw[u] = __builtin_nontemporal_load((const u32x4 *)sp.col[k] + unit0 + (u64)u * FS_THREADS);
         }
     };
-    // decode + test + extract for one column; x holds the zero/sign-extended 32-bit pattern of each element
+    // test + extract for one column; x holds the zero/sign-extended 32-bit pattern of each element
     auto column_t = [&](auto tag, u32 k, const u32 (&x)[E], bool (&pass)[E], u32 (&va)[E], u32 (&vb)[E]) {
-        (void)tag; // the element's signedness only matters for the value (finish()); the key test is width-native u32
+        (void)tag; // the element's signedness only matters for the value (expr_fold_rows); the key test is width-native u32
 #pragma unroll
         for (u32 q = 0; q < EX_MAX_PREDS; ++q)
             if (p_col[q] == k)
             {
 #pragma unroll
                 for (int e = 0; e < E; ++e)
-                    pass[e] = pass[e] && ((((x[e] ^ p_flip[q]) - p_lo[q]) <= p_span[q]) != (p_inv[q] != 0));
+                    pass[e] = pass[e] && (key_in_range<u32>(x[e], p_flip[q], p_lo[q], p_span[q]) != (p_inv[q] != 0));
             }
-        if (sp.val_a == k)
-        {
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-                va[e] = x[e]; // widened in finish() by the column's signedness
-        }
-        if (sp.value_op != CHGPU_VAL_COL && sp.val_b == k)
-        {
-#pragma unroll
-            for (int e = 0; e < E; ++e)
-                vb[e] = x[e];
-        }
+        expr_take_values(sp, k, x, va, vb);
     };
-    auto column = [&](u32 k, const v4u (&raw)[U], bool (&pass)[E], u32 (&va)[E], u32 (&vb)[E]) {
+    auto column = [&](u32 k, const u32x4 (&raw)[U], bool (&pass)[E], u32 (&va)[E], u32 (&vb)[E]) {
         u32 x[E];
         if (sp.col_type[k] == CHGPU_U8)
         {
@@ -2063,20 +1866,10 @@ __global__ __launch_bounds__(FS_THREADS) void k_expr_filter_sum_narrow(ExprSpec 
         }
     };
     const bool a_signed = sp.col_type[sp.val_a] == CHGPU_I32, b_signed = sp.col_type[sp.val_b < EX_MAX_COLS ? sp.val_b : 0] == CHGPU_I32;
-    auto finish = [&](const bool (&pass)[E], const u32 (&va)[E], const u32 (&vb)[E]) {
-#pragma unroll
-        for (int e = 0; e < E; ++e)
-        {
-            const u64 xa = a_signed ? (u64)(i64)(i32)va[e] : (u64)va[e], xb = b_signed ? (u64)(i64)(i32)vb[e] : (u64)vb[e];
-            const u64 v = sp.value_op == CHGPU_VAL_COL ? xa : apply_val(sp.value_op, xa, xb);
-            s += pass[e] ? v : 0;
-            c += pass[e] ? 1 : 0;
-        }
-    };
     for (u64 ch = blockIdx.x; ch < n_chunks; ch += gridDim.x)
     {
         const u64 unit0 = ch * CHUNK + threadIdx.x;
-        v4u r0[U] = {}, r1[U] = {}, r2[U] = {}, r3[U] = {};
+        u32x4 r0[U] = {}, r1[U] = {}, r2[U] = {}, r3[U] = {};
         load_col(std::integral_constant<u32, 0>{}, unit0, r0);
         load_col(std::integral_constant<u32, 1>{}, unit0, r1);
         load_col(std::integral_constant<u32, 2>{}, unit0, r2);
@@ -2091,7 +1884,7 @@ __global__ __launch_bounds__(FS_THREADS) void k_expr_filter_sum_narrow(ExprSpec 
         if (sp.n_cols > 1) column(1, r1, pass, va, vb);
         if (sp.n_cols > 2) column(2, r2, pass, va, vb);
         if (sp.n_cols > 3) column(3, r3, pass, va, vb);
-        finish(pass, va, vb);
+        expr_fold_rows(sp, pass, va, vb, a_signed, b_signed, s, c);
     }
     // tail rows one by one
     const u64 tid = (u64)blockIdx.x * FS_THREADS + threadIdx.x;
@@ -2105,34 +1898,14 @@ __global__ __launch_bounds__(FS_THREADS) void k_expr_filter_sum_narrow(ExprSpec 
             pass[e] = e == 0, va[e] = 0, vb[e] = 0;
         for (u32 k = 0; k < sp.n_cols; ++k)
         {
-            v4u raw[U] = {};
+            u32x4 raw[U] = {};
             raw[0].x = sp.col_type[k] == CHGPU_U8 ? (u32)((const u8 *)sp.col[k])[r] : ((const u32 *)sp.col[k])[r];
             column(k, raw, pass, va, vb);
         }
-        finish(pass, va, vb);
+        expr_fold_rows(sp, pass, va, vb, a_signed, b_signed, s, c);
     }
 
-    __shared__ u64 lds_s[FS_THREADS / WAVE];
-    __shared__ u64 lds_c[FS_THREADS / WAVE];
-    s = wave_reduce_add_u64(s);
-    c = wave_reduce_add_u64(c);
-    if ((threadIdx.x & 63) == 0)
-    {
-        lds_s[threadIdx.x >> 6] = s;
-        lds_c[threadIdx.x >> 6] = c;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-    {
-        u64 ss = 0, cc = 0;
-        for (int w = 0; w < FS_THREADS / WAVE; ++w)
-        {
-            ss += lds_s[w];
-            cc += lds_c[w];
-        }
-        part_sum[blockIdx.x] = ss;
-        part_cnt[blockIdx.x] = cc;
-    }
+    fs_fold_workgroup(s, c, part_sum, part_cnt);
 }
 
 extern "C" int chgpu_expr_filter_sum(chgpu_ctx * ctx, uint32_t n_cols, const chgpu_col * const * cols, uint32_t n_preds,
@@ -2232,43 +2005,33 @@ extern "C" int chgpu_expr_filter_sum(chgpu_ctx * ctx, uint32_t n_cols, const chg
     // per lane: 2.36 ms vs 3.02 ms with 3; 3-4 units per lane 2.7 ms)
     const u32 ex_wg = tune_env(ctx, "tune_expr_wg", 3), exn_wg = tune_env(ctx, "tune_exprn_wg", 6);
     const u32 grid = chgpu_grid_for(ctx, (n + vecw - 1) / vecw, FS_THREADS, (!one_type && narrow) ? exn_wg : ex_wg);
-    void * scratch = nullptr;
-    const u32 grid_cap = (u32)ctx->num_cus * 8;
-    CHGPU_TRY(chgpu_scratch(ctx, (size_t)grid_cap * 2 * sizeof(u64) + 64, &scratch));
-    u64 * part_sum = (u64 *)scratch;
+    u64 *part_sum = nullptr, *result_dev = nullptr;
+    CHGPU_TRY(fs_result_slot(ctx, &part_sum, &result_dev));
     u64 * part_cnt = part_sum + grid;
-    u64 * result_dev = (u64 *)((char *)scratch + (size_t)grid_cap * 2 * sizeof(u64));
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(FS_THREADS), 0, ctx->stream, sp, n, part_sum, part_cnt); };
     if (!one_type && narrow)
     {
         u32 wmask = 0;
         for (u32 k = 0; k < EX_MAX_COLS; ++k)
             wmask |= (chgpu_type_size(cols[k < n_cols ? k : 0]->type) == 4 ? 1u : 0u) << k;
-#define EXN(M) case M: hipLaunchKernelGGL(k_expr_filter_sum_narrow<M>, dim3(grid), dim3(FS_THREADS), 0, ctx->stream, sp, n, part_sum, part_cnt); break;
-        switch (wmask)
-        {
-            EXN(0) EXN(1) EXN(2) EXN(3) EXN(4) EXN(5) EXN(6) EXN(7) EXN(8) EXN(9) EXN(10) EXN(11) EXN(12) EXN(13) EXN(14) EXN(15)
-        }
-#undef EXN
+        dispatch_const<0, 15>(wmask, [&](auto m) { launch(k_expr_filter_sum_narrow<(u32)decltype(m)::value>); });
     }
     else if (!one_type)
-        hipLaunchKernelGGL(k_expr_filter_sum_mixed, dim3(grid), dim3(FS_THREADS), 0, ctx->stream, sp, n, part_sum, part_cnt);
+        launch(k_expr_filter_sum_mixed);
     else
-    switch (type)
-    {
-        case CHGPU_I64: hipLaunchKernelGGL(k_expr_filter_sum<i64>, dim3(grid), dim3(FS_THREADS), 0, ctx->stream, sp, n, part_sum, part_cnt); break;
-        case CHGPU_U64: hipLaunchKernelGGL(k_expr_filter_sum<u64>, dim3(grid), dim3(FS_THREADS), 0, ctx->stream, sp, n, part_sum, part_cnt); break;
-        case CHGPU_U32: hipLaunchKernelGGL(k_expr_filter_sum<u32>, dim3(grid), dim3(FS_THREADS), 0, ctx->stream, sp, n, part_sum, part_cnt); break;
-        case CHGPU_I32: hipLaunchKernelGGL(k_expr_filter_sum<i32>, dim3(grid), dim3(FS_THREADS), 0, ctx->stream, sp, n, part_sum, part_cnt); break;
-        default: hipLaunchKernelGGL(k_expr_filter_sum<u8>, dim3(grid), dim3(FS_THREADS), 0, ctx->stream, sp, n, part_sum, part_cnt); break;
-    }
-    hipLaunchKernelGGL(k_filter_sum_finish<false>, dim3(1), dim3(256), 0, ctx->stream, part_sum, part_cnt, grid, result_dev);
+        switch (type)
+        {
+            case CHGPU_I64: launch(k_expr_filter_sum<i64>); break;
+            case CHGPU_U64: launch(k_expr_filter_sum<u64>); break;
+            case CHGPU_U32: launch(k_expr_filter_sum<u32>); break;
+            case CHGPU_I32: launch(k_expr_filter_sum<i32>); break;
+            default: return chgpu_set_error(CHGPU_ERR_LOGICAL, "fused expression: no same-type kernel for column type %d", type); // UInt8 takes the narrow kernel
+        }
+    hipLaunchKernelGGL(k_filter_sum_finish<false>, dim3(1), dim3(FS_THREADS), 0, ctx->stream, part_sum, part_cnt, grid, result_dev);
     ctx->counters[6] += 2;
     ctx->counters[5] += n;
     CHGPU_HIP(hipGetLastError());
-    u64 res[2];
-    CHGPU_TRY(chgpu_read_back(ctx, result_dev, res, sizeof(res)));
-    memcpy(sum_out, &res[0], 8);
-    *count_out = res[1];
-    ctx->counters[0] += res[1];
+    CHGPU_TRY(fs_read_result(ctx, result_dev, sum_out, count_out));
+    ctx->counters[0] += *count_out;
     return CHGPU_OK;
 }

@@ -53,6 +53,33 @@ def test_filter_ragged_sizes_and_unaligned_views(ch, ctx, oracle_mod, rows):
         assert np.array_equal(got, oracle_mod.filter_column(data[start:start + n], filt[start:start + n]))
 
 
+@pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.uint32, np.uint64])
+def test_filter_single_column_every_width_view_start_and_chunk_edge(ch, ctx, dtype):
+    """filter, filter_columns([c]) and filter_to_indices for each element width, on views that start 0, 1 and 3 rows into the upload
+    (off the data's 16-byte alignment and, for the narrow types, off the mask's R-alignment), at one chunk less a row, exactly one
+    chunk, a one-row ragged chunk and several chunks with a ragged tail (CHUNK_ROWS = 1024), under masks that keep nothing,
+    everything (byte 7) and about a third (non-zero bytes up to 255)"""
+    rng = np.random.Generator(np.random.PCG64(1000 + np.dtype(dtype).itemsize))
+    top = 3 * 1024 + 17 + 3
+    data = rng.integers(0, np.iinfo(dtype).max, size=top, dtype=dtype, endpoint=True)
+    third = np.where(rng.integers(0, 3, size=top) == 0, rng.integers(1, 256, size=top), 0).astype(np.uint8)
+    third[rng.integers(0, top, size=64)] = 255
+    col = ctx.upload(data)
+    for filt in (np.zeros(top, dtype=np.uint8), np.full(top, 7, dtype=np.uint8), third):
+        m = ctx.upload(filt)
+        for start in (0, 1, 3):
+            for rows in (1023, 1024, 1025, 3 * 1024 + 17):
+                c, f = data[start:start + rows], filt[start:start + rows]
+                cv, mv = col.cut(start, rows), m.cut(start, rows)
+                where = (np.dtype(dtype).name, int(filt[0]), start, rows)
+                one = cv.filter(mv).numpy()
+                assert one.dtype == c.dtype and np.array_equal(one, c[f != 0]), where
+                many = ch.filter_columns([cv], mv)
+                assert len(many) == 1 and many[0].numpy().dtype == c.dtype and np.array_equal(many[0].numpy(), one), where
+                idx = ch.filter_to_indices(mv).numpy()
+                assert idx.dtype == np.uint64 and np.array_equal(idx, np.flatnonzero(f).astype(np.uint64)), where
+
+
 @pytest.mark.parametrize("n_u32,n_8", [(2, 0), (5, 2), (7, 5), (1, 3), (4, 4)])
 def test_filter_columns_same_width_columns_share_one_mask_pass(ch, ctx, oracle_mod, n_u32, n_8):
     """columns of one element width are compacted four (three, two) at a time by one kernel that reads the mask once; every batch
@@ -298,7 +325,7 @@ def test_filter_description_nullable(ch, ctx, oracle_mod):
 
 def test_index_and_replicate(ch, ctx, oracle_mod):
     rng = np.random.Generator(np.random.PCG64(9))
-    for dtype in (np.int64, np.uint32, np.uint8, np.float64):
+    for dtype in (np.int64, np.uint32, np.uint8, np.float64, np.uint16):
         data = _rand(rng, dtype, 10000)
         col = ctx.upload(data)
         idx = rng.integers(0, 10000, size=5000, dtype=np.uint64)

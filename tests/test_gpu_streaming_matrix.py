@@ -15,10 +15,9 @@ tests/test_streaming_cases.py).  Integer sums are compared bit for bit with the 
 with |x| <= 2^20 and at most 2^25 rows, so every partial sum is exact in Float64 in any order and the device must match the oracle
 bit for bit as well; the rounding path and the IEEE specials have their own tests.
 
-Unreachable from the C ABI, hence absent: for k_filter_sum two columns together with a mask, and IntRangePred / F64Pred together
-with a mask (a mask only ever comes with TruePred over one column); for chgpu_expr_filter_sum the k_expr_filter_sum<u8> arm (a call
-whose columns are all UInt8 takes k_expr_filter_sum_narrow<0>).  A view that is not 16-byte aligned is refused by
-chgpu_expr_filter_sum, so the hand-fused kernels have no VEC = 1 form.
+That is everything instantiated: launch_filter_sum_t states which k_filter_sum combinations the C ABI can reach (a mask only ever
+comes with TruePred over one column), and a chgpu_expr_filter_sum call whose columns are all UInt8 takes k_expr_filter_sum_narrow<0>.
+A view that is not 16-byte aligned is refused by chgpu_expr_filter_sum, so the hand-fused kernels have no VEC = 1 form.
 
 Row counts depend on the device's CU count, so they are looped over inside the tests; every assertion message carries the type,
 the layout, the operator and the row count.

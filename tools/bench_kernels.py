@@ -38,7 +38,7 @@ for rep in range(2):
     idx = ctx.upload(np.random.default_rng(1).integers(0, rows, size=rows // 4, dtype=np.uint64))
     ac.index(idx)                                       # k_index (random gather)
     offs = ctx.upload(np.cumsum(np.random.default_rng(2).integers(0, 3, size=rows // 8)).astype(np.uint64))
-    ac.cut(0, rows // 8).replicate(offs)                # k_replicate
+    ac.cut(0, rows // 8).replicate(offs)                # k_replicate_multi<T, 1>
     A = ch.Aggregator(np.uint32, [(ch.AGG_SUM, np.int64), (ch.AGG_COUNT, None)], size_hint=1_000_000, ctx=ctx)
     A.execute_on_block(kc, [ac, None])                  # k_gb_hist, k_gb_scatter, k_agg_part_lds
     A.convert_to_block()                                # k_occupied_mask + filter kernels
