@@ -1737,6 +1737,46 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
         ovf_flush_desc(t, s_ovf, d);
 }
 
+// The finish rounds of the tile-sorted plan over 12-byte records: the rows k_agg_tiles_lds left pending (LDS table full) go through the
+// HBM table; a row that meets the max-fill limit stays pending for the next round (after the table has grown).
+__global__ __launch_bounds__(AGG_THREADS) void k_agg_tiles_pending_aos(AggTable t, AggDesc d, const u32 * __restrict__ rec, int key64, u64 n, u64 * __restrict__ pending)
+{
+    __shared__ u64 s_ovf[AGG_MAX_WORDS];
+    if (t.ovf)
+    {
+        ovf_lds_init(s_ovf);
+        __syncthreads();
+    }
+    const u32 lane = threadIdx.x & 63;
+    const u64 wave0 = ((u64)blockIdx.x * AGG_THREADS + threadIdx.x) >> 6;
+    const u64 n_waves = ((u64)gridDim.x * AGG_THREADS) >> 6;
+    const u64 n_groups64 = (n + 63) / 64;
+    for (u64 g = wave0; g < n_groups64; g += n_waves)
+    {
+        const u64 word = pending[g];
+        if (word == 0)
+            continue;
+        const u64 i = g * 64 + lane;
+        bool failed = false;
+        if (i < n && ((word >> lane) & 1))
+        {
+            const u32 * r = rec + i * (key64 ? 4 : 3); // records are {word, key}: 12 bytes with a 4-byte key, 16 with an 8-byte key
+            failed = place_and_add(t, s_ovf, key64 ? (u64)r[2] | ((u64)r[3] << 32) : (u64)r[2], true,
+                                   [&](auto sink) { add_vals(sink, d, (u64)r[0] | ((u64)r[1] << 32), 0, 1); });
+        }
+        const u64 b = __ballot(failed);
+        if (lane == 0)
+            pending[g] = b;
+        if (b != 0 && lane == 0)
+            t.ctrl->overflow = 1;
+    }
+    if (t.ovf)
+    {
+        __syncthreads();
+        ovf_flush_desc(t, s_ovf, d);
+    }
+}
+
 // Merge (key, state words) tuples into the table: mergeToViaEmplace, also the rehash of a grown table.
 // src_words[w] + i*1 ; src keys are u64; key==0 entries are skipped when skip_zero_keys (table arrays: empty cells),
 // zero_slot_index: index in the source arrays of the out-of-line zero key (or ~0).
@@ -1968,13 +2008,14 @@ static int agg_grow(chgpu_agg * a, u64 min_groups, bool has_zero)
     return CHGPU_OK;
 }
 
+// size_hint: the groups promised for the rows of the call that makes the table.
 // min_cells: what the first strategy to touch the table wants it to hold (the partitioned path's flush slack): a table that
 // does not exist yet is created that large at once instead of being created small and rehashed empty a moment later
-static int agg_ensure_table(chgpu_agg * a, u64 min_cells = 0)
+static int agg_ensure_table(chgpu_agg * a, u64 size_hint, u64 min_cells = 0)
 {
     if (a->table_mem)
         return CHGPU_OK;
-    u64 cap = pow2_ceil(a->size_hint * 2);
+    u64 cap = pow2_ceil(size_hint * 2);
     if (cap < AGG_MIN_CAPACITY)
         cap = AGG_MIN_CAPACITY;
     if (cap < min_cells)
@@ -2432,25 +2473,110 @@ static int agg_fx_prepare_block(chgpu_agg * a, const chgpu_col * const * arg_col
     return agg_fx_admit(a, emax, emin, n);
 }
 
-// Compact LDS cell of the partition-aggregate kernel for this aggregator's shape (see PartLds): bytes per cell and which
-// state words are 32-bit counts.
-static size_t agg_part_cell_bytes(const chgpu_agg * a, u64 n, u32 * cnt32_out)
+// ---------------------------------------------------------------------------------------------
+// GROUP BY host plans.  Each plan is DECIDED into a plain struct by a function that makes no HIP call (OK, or NOT_IMPLEMENTED = the
+// shape does not fit), its scratch is LAID OUT by one carving function, and its kernels are LAUNCHED by a run function that reads
+// both.  Between deciding the partition geometry and testing the tile-sorted fit the table is sized (agg_partition_size_table).
+// ---------------------------------------------------------------------------------------------
+
+// What a plan is told about its rows besides the columns: the key and argument types as the columns hold them and the groups promised
+// for them.  The aggregator's own for a caller's block; a level-2 call of the two-level plan reads partition buffers (4/8-byte keys,
+// arguments widened to 8 bytes) and gets its share of the promise.
+struct AggInput
 {
-    const bool key32 = chgpu_type_size(a->key_type) <= 4;
-    u32 cnt32 = 0;
-    const bool no_cnt32 = chgpu_opt(a->ctx, "tune_gb_nocnt32", 0) != 0;
-    if (n < (1ull << 32) && !no_cnt32)
-        for (u32 j = 0; j < a->n_aggs; ++j)
-        {
-            if (a->kinds[j] == CHGPU_AGG_COUNT)
-                cnt32 |= 1u << a->word_off[j];
-            else if (a->kinds[j] == CHGPU_AGG_AVG)
-                cnt32 |= 1u << (a->word_off[j] + 1);
-        }
-    const u32 n4 = (u32)__builtin_popcount(cnt32), n8 = a->n_words - n4;
+    int key_type;
+    int arg_types[AGG_MAX_AGGS];
+    u64 size_hint;
+};
+
+static AggInput agg_input_of(const chgpu_agg * a)
+{
+    AggInput in;
+    in.key_type = a->key_type;
+    memcpy(in.arg_types, a->arg_types, sizeof(in.arg_types));
+    in.size_hint = a->size_hint;
+    return in;
+}
+
+// Raise the kernel's dynamic LDS limit to `lds_bytes` and launch it (the attribute is set before every launch).  A failure sets the
+// error message and clears the sticky launch error, so that it does not surface in the next call.
+template <typename Kern, typename... Args>
+static int launch_lds(const char * what, Kern kern, dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, Args... args)
+{
+    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e == hipSuccess)
+    {
+        hipLaunchKernelGGL(kern, grid, block, lds_bytes, stream, args...);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess)
+        return CHGPU_OK;
+    (void)hipGetLastError();
+    return chgpu_set_error(CHGPU_ERR_DEVICE, "%s launch failed: %s", what, hipGetErrorString(e));
+}
+
+// Carves one scratch allocation into regions: take<T>(count) gives the next region and advances by its size rounded up to 256 bytes
+// (take_packed: by its size as it is); bytes() is the total to ask chgpu_scratch for.  A layout function runs twice over the same
+// statements: over a null base for the size, then over the allocation for the pointers.
+struct ScratchCarver
+{
+    uintptr_t base;
+    size_t off = 0;
+    static size_t al(size_t b) { return (b + 255) / 256 * 256; }
+    template <typename T>
+    T * take(size_t count)
+    {
+        T * p = (T *)(base + off);
+        off += al(count * sizeof(T));
+        return p;
+    }
+    template <typename T>
+    T * take_packed(size_t count)
+    {
+        T * p = (T *)(base + off);
+        off += count * sizeof(T);
+        return p;
+    }
+    size_t bytes() const { return al(off); }
+};
+
+// 4-byte (or narrower, stored as 4 bytes) or 8-byte keys of the partition buffers: fn(u32{} / u64{})
+template <typename F>
+static void dispatch_key(bool key32, F && fn)
+{
+    if (key32)
+        fn(u32{});
+    else
+        fn(u64{});
+}
+
+// Bytes of the compact LDS cell of the partition-aggregate kernel (see PartLds) that holds the state words of the functions in
+// `agg_mask`, and which of the aggregator's words are 32-bit counts there: the key as wide as the partition buffers' keys, COUNT words
+// as 32 bits while the call has fewer than 2^32 rows.  The full mask is the aggregator's own layout with EVERY word of it: the spare
+// high words that fixed-point sums leave behind when they go back to doubles (agg_fx_to_plain) are still there, while a pass over some
+// of the functions numbers its words afresh (agg_localise_desc) and leaves them out.
+static size_t agg_part_cell_bytes(const chgpu_agg * a, int key_type, u64 n, u32 * cnt32_out, u32 agg_mask = ~0u)
+{
+    const u32 c32 = n < (1ull << 32) && !chgpu_opt(a->ctx, "tune_gb_nocnt32", 0) ? 1 : 0;
+    u32 cnt32 = 0, words = 0;
+    for (u32 j = 0; j < a->n_aggs; ++j)
+    {
+        if (!((agg_mask >> j) & 1))
+            continue;
+        const u32 w = a->word_off[j];
+        const bool pair = a->kinds[j] == CHGPU_AGG_AVG || a->kinds[j] == CHGPU_AGG_ANY;
+        words += 1 + (pair ? 1 : 0) + ((a->word_fx >> w) & 1);
+        if (a->kinds[j] == CHGPU_AGG_COUNT)
+            cnt32 |= c32 << w;
+        else if (a->kinds[j] == CHGPU_AGG_AVG)
+            cnt32 |= c32 << (w + 1);
+    }
+    if (agg_mask == ~0u)
+        words = a->n_words;
     if (cnt32_out)
         *cnt32_out = cnt32;
-    return (key32 ? 4 : 8) + 8 * n8 + 4 * n4;
+    const u32 n4 = (u32)__builtin_popcount(cnt32);
+    return (chgpu_type_size(key_type) <= 4 ? 4 : 8) + 8 * (words - n4) + 4 * n4;
 }
 
 // Largest power-of-two cell count whose table fits ~150 KiB of LDS (at most 8192).
@@ -2491,46 +2617,6 @@ static int agg_debug_rounds(const chgpu_ctx * ctx, int rounds)
     if (chgpu_opt(ctx, "debug", 0))
         fprintf(stderr, "chgpu: GROUP BY finish rounds=%d\n", rounds);
     return CHGPU_OK;
-}
-
-// The finish rounds of the tile-sorted plan over 12-byte records: the rows k_agg_tiles_lds left pending (LDS table full) go through the
-// HBM table; a row that meets the max-fill limit stays pending for the next round (after the table has grown).
-__global__ __launch_bounds__(AGG_THREADS) void k_agg_tiles_pending_aos(AggTable t, AggDesc d, const u32 * __restrict__ rec, int key64, u64 n, u64 * __restrict__ pending)
-{
-    __shared__ u64 s_ovf[AGG_MAX_WORDS];
-    if (t.ovf)
-    {
-        ovf_lds_init(s_ovf);
-        __syncthreads();
-    }
-    const u32 lane = threadIdx.x & 63;
-    const u64 wave0 = ((u64)blockIdx.x * AGG_THREADS + threadIdx.x) >> 6;
-    const u64 n_waves = ((u64)gridDim.x * AGG_THREADS) >> 6;
-    const u64 n_groups64 = (n + 63) / 64;
-    for (u64 g = wave0; g < n_groups64; g += n_waves)
-    {
-        const u64 word = pending[g];
-        if (word == 0)
-            continue;
-        const u64 i = g * 64 + lane;
-        bool failed = false;
-        if (i < n && ((word >> lane) & 1))
-        {
-            const u32 * r = rec + i * (key64 ? 4 : 3); // records are {word, key}: 12 bytes with a 4-byte key, 16 with an 8-byte key
-            failed = place_and_add(t, s_ovf, key64 ? (u64)r[2] | ((u64)r[3] << 32) : (u64)r[2], true,
-                                   [&](auto sink) { add_vals(sink, d, (u64)r[0] | ((u64)r[1] << 32), 0, 1); });
-        }
-        const u64 b = __ballot(failed);
-        if (lane == 0)
-            pending[g] = b;
-        if (b != 0 && lane == 0)
-            t.ctrl->overflow = 1;
-    }
-    if (t.ovf)
-    {
-        __syncthreads();
-        ovf_flush_desc(t, s_ovf, d);
-    }
 }
 
 // resize on overflow (HashTable.h:921-944): grow + rehash, then re-run only the rows left pending, until none is.  relaunch(grid):
@@ -2579,13 +2665,10 @@ static int agg_finish_rounds_aos(chgpu_agg * a, const AggDesc & d, const u32 * r
     });
 }
 
-// The TILE-SORTED plan of a partitioned executeOnBlock (k_rp_tilesort + k_agg_tiles_lds): one level, one 8-byte argument column
-// (or none besides counts), 4- or 8-byte keys, a compile-time state update.  Two passes over the rows instead of three (no histogram),
-// and the partition pass writes whole lines in row order.  NOT_IMPLEMENTED = the shape does not fit (the caller runs the scatter plan).
 // The descriptor of a pass over a subset of the functions (d->a[0 .. n_aggs) already compacted to them): its state words renumbered
 // 0 .. n-1 in the order of the functions (a fixed-point sum's high half behind the regular words, as in the aggregator), word_map[] back
 // to the table's words, every per-word mask re-expressed in the local numbering; *cnt32 (which words are 32-bit counts in LDS) likewise.
-static void agg_localise_desc(const chgpu_agg * a, AggDesc * d, u32 * cnt32)
+static void agg_localise_desc(AggDesc * d, u32 * cnt32)
 {
     const u32 g_cnt32 = *cnt32, g_fx = d->word_fx, g_f64 = d->word_is_f64;
     unsigned char g_hi[AGG_MAX_WORDS];
@@ -2625,30 +2708,6 @@ static void agg_localise_desc(const chgpu_agg * a, AggDesc * d, u32 * cnt32)
     d->word_fx_hi = l_fx_hi;
     d->word_is_f64 = l_f64;
     *cnt32 = l_cnt32;
-    (void)a;
-}
-// bytes of the compact LDS cell that holds only the state words of the functions in `agg_mask` (see agg_part_cell_bytes)
-static size_t agg_part_cell_bytes_masked(const chgpu_agg * a, u64 n, u32 agg_mask)
-{
-    const bool key32 = chgpu_type_size(a->key_type) <= 4;
-    const bool c32 = n < (1ull << 32) && !chgpu_opt(a->ctx, "tune_gb_nocnt32", 0);
-    size_t b = key32 ? 4 : 8;
-    for (u32 j = 0; j < a->n_aggs; ++j)
-    {
-        if (!((agg_mask >> j) & 1))
-            continue;
-        if (a->kinds[j] == CHGPU_AGG_COUNT)
-            b += c32 ? 4 : 8;
-        else
-        {
-            b += 8;
-            if ((a->word_fx >> a->word_off[j]) & 1)
-                b += 8;
-            if (a->kinds[j] == CHGPU_AGG_AVG)
-                b += c32 ? 4 : 8;
-        }
-    }
-    return b;
 }
 
 // The compile-time update code of the state words (OPS of k_agg_part_lds / k_agg_tiles_lds; 7 = a fixed-point Float64 sum, 9 = its
@@ -2689,161 +2748,488 @@ static u32 agg_update_code(const AggDesc & d, u32 cnt32)
     return ops;
 }
 
-static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n, u32 P, u32 S, u32 cnt32,
-                               u32 agg_mask, u64 chunk_rows, bool probe_only = false)
+// The update codes each aggregate kernel is instantiated for: the acceptance test of a plan and the switch of its launch read the
+// same list.  1 = sum, 3 = sum(Float64), 5 / 6 = a 32- / 64-bit count, 2 = a sum of the second argument word, 97 = a fixed-point pair.
+using GbTileOps = OneOf<0x51, 0x15, 0x1, 0x53, 0x3, 0x61, 0x16, 0x97, 0x957, 0x967>; // k_agg_tiles_lds: no other code runs
+using GbPartOps = OneOf<0x51, 0x15, 0x1, 0x5, 0x53, 0x3, 0x21, 0x521, 0x97, 0x957>;  // k_agg_part_lds: every other code takes OPS = 0
+
+// Every count() of the aggregation (bit j = function j).  A block that goes over its rows in several passes or calls, each with some
+// of the functions, counts in the first of them.
+static u32 agg_count_mask(const chgpu_agg * a)
 {
-    chgpu_ctx * ctx = a->ctx;
-    const size_t key_w = chgpu_type_size(a->key_type);
-    if ((key_w != 4 && key_w != 8) || P > 512 || ((uintptr_t)key_col->data + row_begin * key_w) % 16 != 0)
+    u32 mask = 0;
+    for (u32 j = 0; j < a->n_aggs; ++j)
+        if (a->kinds[j] == CHGPU_AGG_COUNT)
+            mask |= 1u << j;
+    return mask;
+}
+
+// The functions of `agg_mask` alone in the descriptor (in their order); their state word indices stay the aggregator's own.
+static void agg_desc_keep(AggDesc * d, u32 agg_mask)
+{
+    u32 m = 0;
+    for (u32 j = 0; j < d->n_aggs; ++j)
+        if ((agg_mask >> j) & 1)
+            d->a[m++] = d->a[j];
+    d->n_aggs = m;
+}
+
+// The partition geometry of one partitioned call, and -- once the scatter plan is the one that runs -- its launch shape.
+struct GbPartPlan
+{
+    int level = 0;       // 0: one level.  1: the first of two (P == P1 big partitions, no aggregate pass).  2: one big partition's call.
+    u32 K = 0;           // argument words per row of the partition buffers
+    u32 agg_mask = ~0u;  // the functions this call applies
+    bool key32 = false;  // keys of <= 4 bytes: 4-byte keys in the partition buffers
+    u32 P = 0, P1 = 0;   // partitions of this call; big partitions when level == 1
+    u32 S = 0;           // cells of the aggregate pass's LDS table
+    u32 cnt32 = 0;       // state words that are 32-bit counts in LDS
+    u64 mult = GBP_MULT; // the partition hash's multiplier
+    u64 chunk_rows = 0;  // rows per work unit of the aggregate pass
+    u64 max_units = 0;   // sum over partitions of ceil(rows_p / chunk_rows), at most
+    // the scatter plan (agg_scatter_plan)
+    u32 G = 0, tile = 0; // workgroups and tile rows of the partition passes
+    u64 rows_per_wg = 0;
+    bool wide = false;   // 16-byte loads: columns as wide as the buffers, first row 16-byte aligned
+    u32 rp_tile = 0;     // tile of the branch-free scatter (k_rp_scatter) when it runs instead of k_gb_scatter, else 0
+    u32 ops = 0;         // update code of the aggregate pass (0: the generic update)
+    GbpCols gc;
+    AggDesc d;           // argument pointers are set once the partition buffers are laid out
+};
+
+// Decides P, S and the work units from the promised groups.  word_pass: a pass over ONE argument word of a subset of the functions
+// (level 0, K = 1), which goes through the tile-sorted plan with cells that hold only its words.
+static int agg_partition_geometry(const chgpu_agg * a, const AggInput & in, u64 n, u32 K, int level, u32 agg_mask, bool word_pass, GbPartPlan * g)
+{
+    const chgpu_ctx * ctx = a->ctx;
+    g->K = K;
+    g->agg_mask = agg_mask;
+    // LDS table of the aggregate pass (one 1024-thread workgroup per CU): compact cells -- key as wide as the partition
+    // buffer's keys, COUNT words as 32 bits while the call has fewer than 2^32 rows -- and as many cells as fit ~150 KiB
+    g->key32 = chgpu_type_size(in.key_type) <= 4;
+    const u32 S = g->S = agg_part_max_cells(ctx, agg_part_cell_bytes(a, in.key_type, n, &g->cnt32, word_pass ? agg_mask : ~0u));
+    // partitions so that a partition's expected groups fill at most 70 % of the LDS table (fewer partitions = longer runs in
+    // the scatter: an estimate of 1.25 M groups still gets 256 partitions)
+    const u64 part_cap = (u64)S * 7 / 10;
+    const u64 want_p = (in.size_hint + part_cap - 1) / part_cap;
+    u32 P = 64;
+    while (P < (u32)ctx->num_cus && P < GBP_MAX_P) // the aggregate pass runs one workgroup per partition: give every CU one
+        P <<= 1;
+    while (P < want_p && P < GBP_MAX_P)
+        P <<= 1;
+    // More groups than P_max partitions x half an LDS table: TWO LEVELS.  Level 1 cuts the rows into P1 big partitions with an
+    // independent hash (long runs: close to a copy), then every big partition -- already in the 4/8-byte key + 8-byte word
+    // layout -- goes through a level-2 call with its share of the promised groups.
+    // (want_p already allows LDS tables 70 % full: up to ~5.9 M groups one level is the faster plan, 16 vs 24 ms at 5 M)
+    if (want_p > GBP_MAX_P && level == 0 && !chgpu_opt(ctx, "tune_gb_no_two_level", 0))
+    {
+        const u64 sub_groups = (u64)(GBP_MAX_P / 2) * (S / 2); // leaves the second level at half its partition budget
+        u32 P1 = 2;
+        while ((u64)P1 * sub_groups < in.size_hint && P1 < 256)
+            P1 <<= 1;
+        if ((u64)P1 * sub_groups * 2 < in.size_hint || n / P1 < (1u << 20))
+            return CHGPU_ERR_NOT_IMPLEMENTED; // beyond two levels, or partitions too small to be worth three passes each
+        P = g->P1 = P1;
+        g->mult = GBP_MULT1;
+        level = 1;
+    }
+    else if (level == 0 && (u64)P * (S / 2) < in.size_hint / 4) // hopelessly more groups than P * S: partitioning would not localise them
         return CHGPU_ERR_NOT_IMPLEMENTED;
-    const bool key32 = key_w == 4;
-    const u32 TILE = key32 ? 12288u : 8192u;
-    if (n < (u64)TILE * ctx->num_cus || n + TILE >= (1ull << 32)) // (k_agg_tiles_lds indexes the sorted copy with 32 bits)
+    g->level = level;
+    g->P = P;
+    // work units of the aggregate pass: half an average partition each, so a uniform input gives every workgroup two
+    // units and a partition swollen by a hot key is spread over many workgroups; each unit flushes its LDS table once
+    const u32 unit_div = (u32)chgpu_opt(ctx, "tune_gb_unitdiv", 2);
+    g->chunk_rows = (n / ((u64)P * unit_div) + 63) / 64 * 64;
+    if (g->chunk_rows < 65536)
+        g->chunk_rows = 65536;
+    g->max_units = n / g->chunk_rows + P;
+    return CHGPU_OK;
+}
+
+// The table as the aggregate pass of `g` needs it: every unit's flush may claim up to S+1 cells without the max-fill check, so all of
+// them must fit inside the slack.  size_hint: the promise of this call's rows (a table made here is sized from it).  Runs once the
+// geometry is known and before the tile-sorted fit is tested, for a shape that is refused afterwards too: the capacity decides the
+// row order of the results.
+static int agg_partition_size_table(chgpu_agg * a, const GbPartPlan & g, u64 size_hint)
+{
+    if (g.level == 1) // a first partitioning level touches no table: its level-2 calls size it
+        return CHGPU_OK;
+    CHGPU_TRY(agg_ensure_table(a, size_hint, 2 * (g.max_units * (g.S + 1) + a->n_groups) + 2));
+    for (int guard = 0; !a->t.find_only && guard < 16 && a->t.capacity / 2 < g.max_units * (g.S + 1) + a->n_groups; ++guard)
+    {
+        AggCtrl c0;
+        CHGPU_TRY(agg_read_ctrl(a, &c0));
+        CHGPU_TRY(agg_grow(a, c0.n_groups, c0.has_zero != 0));
+    }
+    return CHGPU_OK;
+}
+
+// The TILE-SORTED plan of a partitioned executeOnBlock (k_rp_tilesort + k_agg_tiles_lds): one level, one 8-byte argument column
+// (or none besides counts), 4- or 8-byte keys, a compile-time state update.  Two passes over the rows instead of three (no histogram),
+// and the partition pass writes whole lines in row order.
+struct GbTilePlan
+{
+    size_t key_w = 0;
+    u32 TILE = 0, n_tiles = 0;
+    int arg_j = -1;      // the one argument column
+    size_t arg_w = 0;    // as it is: 8-byte integers / Float64, or 4 bytes widened inside the partition pass
+    int arg_ex = 0;      // that widening (EX of k_rp_tilesort): 3 = Int32, 4 = Float32, 0 = UInt32 or none
+    u64 chunk_rows = 0;  // rows per work unit
+    u32 max_units = 0;
+    u32 cnt32 = 0;       // in the numbering of d
+    u32 ops = 0;         // one of GbTileOps
+    AggDesc d;           // localised to the pass's functions; argument pointers are set once the records are laid out
+    u64 n_pad() const { return (u64)n_tiles * TILE; }
+};
+
+// NOT_IMPLEMENTED = the shape does not fit (the caller runs the scatter plan).
+static int agg_tile_plan(const chgpu_agg * a, const AggInput & in, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n,
+                         const GbPartPlan & g, GbTilePlan * tp)
+{
+    const size_t key_w = tp->key_w = chgpu_type_size(in.key_type);
+    if ((key_w != 4 && key_w != 8) || g.P > 512 || ((uintptr_t)key_col->data + row_begin * key_w) % 16 != 0)
+        return CHGPU_ERR_NOT_IMPLEMENTED;
+    const u32 TILE = tp->TILE = key_w == 4 ? 12288u : 8192u;
+    if (n < (u64)TILE * a->ctx->num_cus || n + TILE >= (1ull << 32)) // (k_agg_tiles_lds indexes the sorted copy with 32 bits)
         return CHGPU_ERR_NOT_IMPLEMENTED;
     // the one argument column
     int arg_j = -1;
     for (u32 j = 0; j < a->n_aggs; ++j)
-        if (a->kinds[j] != CHGPU_AGG_COUNT && ((agg_mask >> j) & 1))
+        if (a->kinds[j] != CHGPU_AGG_COUNT && ((g.agg_mask >> j) & 1))
         {
             if (arg_j >= 0 && arg_cols[j]->data != arg_cols[arg_j]->data)
                 return CHGPU_ERR_NOT_IMPLEMENTED;
             if (arg_j < 0)
                 arg_j = (int)j;
         }
-    // the argument column as it is: 8-byte integers / Float64, or UInt32 / Int32 / Float32 widened inside the partition pass
-    const int arg_t = arg_j >= 0 ? a->arg_types[arg_j] : -1;
-    const size_t arg_w = arg_j >= 0 ? chgpu_type_size(arg_t) : 0;
-    const int arg_ex = arg_t == CHGPU_I32 ? 3 : arg_t == CHGPU_F32 ? 4 : 0;
-    if (arg_j < 0 || (arg_w != 8 && arg_w != 4) || ((uintptr_t)arg_cols[arg_j]->data + row_begin * arg_w) % (2 * arg_w) != 0)
+    if (arg_j < 0)
         return CHGPU_ERR_NOT_IMPLEMENTED;
-    AggDesc d;
-    agg_fill_desc(a, arg_cols, &d);
-    const u32 n_tiles = (u32)((n + TILE - 1) / TILE);
-    const u64 n_pad = (u64)n_tiles * TILE;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
+    const int arg_t = in.arg_types[arg_j];
+    const size_t arg_w = tp->arg_w = chgpu_type_size(arg_t);
+    tp->arg_j = arg_j;
+    tp->arg_ex = arg_t == CHGPU_I32 ? 3 : arg_t == CHGPU_F32 ? 4 : 0;
+    if ((arg_w != 8 && arg_w != 4) || ((uintptr_t)arg_cols[arg_j]->data + row_begin * arg_w) % (2 * arg_w) != 0)
+        return CHGPU_ERR_NOT_IMPLEMENTED;
+    tp->n_tiles = (u32)((n + TILE - 1) / TILE);
     // (6 % of slack on the unit size: the partitions of a uniform input all get the same number of units, so that units of equal rank
     //  cover equal stretches of tiles -- see k_tile_units)
-    chunk_rows += chunk_rows / 16;
-    const u32 max_units = (u32)(n / chunk_rows + P);
-    const size_t tot_b = al((size_t)P * 8), unit_b = al((size_t)(max_units + 2) * 8 + 128), pend_b = al((n_pad / 64 + 1) * 8),
-                 idx_b = al((size_t)n_tiles * (P + 1) * 2 + 16), ridx_b = al((size_t)n_tiles * P * 4), keys_b = al((size_t)n_pad * key_w), words_b = al((size_t)n_pad * 8);
-    void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, tot_b + unit_b + pend_b + idx_b + ridx_b + keys_b + words_b, &scratch));
-    unsigned long long * part_total = (unsigned long long *)scratch;
-    u64 * unit_list = (u64 *)((char *)scratch + tot_b);
-    u32 * unit_qstart = (u32 *)(unit_list + max_units + 1); // [TILE_QUEUES + 1], then the queues' work counters [TILE_QUEUES]
-    u32 * unit_ctr = unit_qstart + TILE_QUEUES + 1;
-    u64 * pending = (u64 *)((char *)scratch + tot_b + unit_b);
-    unsigned short * tidx = (unsigned short *)((char *)pending + pend_b);
-    u32 * run_index = (u32 *)((char *)tidx + idx_b);
-    void * pkeys = (char *)run_index + ridx_b;
-    // the sorted copy as {word, key} records (one piece per run and tile for the gather instead of two); the records take the key region
-    // and the word region together, and `pwords` is the base of the record array
-    u64 * pwords = (u64 *)pkeys;
+    tp->chunk_rows = g.chunk_rows + g.chunk_rows / 16;
+    tp->max_units = (u32)(n / tp->chunk_rows + g.P);
     // the aggregate pass reads the widened words of the sorted copy
+    AggDesc & d = tp->d;
+    agg_fill_desc(a, arg_cols, &d);
     for (u32 j = 0; j < a->n_aggs; ++j)
-        if (a->kinds[j] != CHGPU_AGG_COUNT && ((agg_mask >> j) & 1))
+        if (a->kinds[j] != CHGPU_AGG_COUNT && ((g.agg_mask >> j) & 1))
         {
-            d.a[j].ptr = pwords;
-            d.a[j].arg_type = chgpu_type_is_float(a->arg_types[j]) ? CHGPU_F64 : CHGPU_U64;
+            d.a[j].arg_type = chgpu_type_is_float(in.arg_types[j]) ? CHGPU_F64 : CHGPU_U64;
             d.a[j].pre = 0;
         }
-    if (agg_mask != ~0u)
+    tp->cnt32 = g.cnt32;
+    if (g.agg_mask != ~0u)
     {
-        u32 m = 0;
-        for (u32 j = 0; j < a->n_aggs; ++j)
-            if ((agg_mask >> j) & 1)
-                d.a[m++] = d.a[j];
-        d.n_aggs = m;
-        agg_localise_desc(a, &d, &cnt32); // the pass's own state words 0 .. n-1 (the caller sized S and P for exactly those)
+        agg_desc_keep(&d, g.agg_mask);
+        agg_localise_desc(&d, &tp->cnt32); // the pass's own state words 0 .. n-1 (a word pass sized S and P for exactly those)
     }
-    const u32 ops = agg_update_code(d, cnt32);
-    if (ops != 0x51 && ops != 0x15 && ops != 0x1 && ops != 0x53 && ops != 0x3 && ops != 0x61 && ops != 0x16 && ops != 0x97 && ops != 0x957 && ops != 0x967)
-        return CHGPU_ERR_NOT_IMPLEMENTED;
-    if (probe_only)
-        return CHGPU_OK; // the plan takes this shape (nothing was launched)
+    tp->ops = agg_update_code(d, tp->cnt32);
+    return GbTileOps::has(tp->ops) ? CHGPU_OK : CHGPU_ERR_NOT_IMPLEMENTED;
+}
+
+struct GbTileScratch
+{
+    unsigned long long * part_total; // [P] rows per partition
+    u64 * unit_list;                 // [max_units + 1], then u32 unit_qstart[TILE_QUEUES + 1] and the queues' work counters u32 [TILE_QUEUES]
+    u64 * pending;
+    size_t zero_bytes;               // the three regions above: zeroed before the passes
+    unsigned short * tidx;
+    u32 * run_index;
+    u64 * rec;                       // the sorted copy as {word, key} records (one piece per run and tile for the gather instead of two): the
+                                     // key region and the word region of a structure-of-arrays copy taken together
+    size_t bytes;
+};
+
+static GbTileScratch agg_tile_scratch(void * base, const GbTilePlan & tp, u32 P)
+{
+    ScratchCarver c{(uintptr_t)base};
+    GbTileScratch s;
+    s.part_total = c.take<unsigned long long>(P);
+    s.unit_list = c.take<u64>((size_t)tp.max_units + 2 + 16);
+    s.pending = c.take<u64>(tp.n_pad() / 64 + 1);
+    s.zero_bytes = c.off;
+    s.tidx = c.take<unsigned short>((size_t)tp.n_tiles * (P + 1) + 8);
+    s.run_index = c.take<u32>((size_t)tp.n_tiles * P);
+    s.rec = (u64 *)c.take<char>((size_t)tp.n_pad() * tp.key_w);
+    (void)c.take<u64>(tp.n_pad());
+    s.bytes = c.bytes();
+    return s;
+}
+
+static int agg_tile_run(chgpu_agg * a, const AggInput & in, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n,
+                        const GbPartPlan & g, GbTilePlan & tp)
+{
+    static const char * const what = "tile-sorted aggregation";
+    chgpu_ctx * ctx = a->ctx;
+    const u32 P = g.P, S = g.S, n_tiles = tp.n_tiles;
+    void * scratch = nullptr;
+    CHGPU_TRY(chgpu_scratch(ctx, agg_tile_scratch(nullptr, tp, P).bytes, &scratch));
+    const GbTileScratch s = agg_tile_scratch(scratch, tp, P);
+    u32 * unit_qstart = (u32 *)(s.unit_list + tp.max_units + 1), * unit_ctr = unit_qstart + TILE_QUEUES + 1;
+    AggDesc & d = tp.d;
+    for (u32 m = 0; m < d.n_aggs; ++m)
+        if (d.a[m].kind != CHGPU_AGG_COUNT)
+            d.a[m].ptr = s.rec;
     const u32 G = (u32)ctx->num_cus;
-    const u64 rows_per_wg = ((n + G - 1) / G + TILE - 1) / TILE * TILE;
-    const bool debug = chgpu_opt(ctx, "debug", 0) != 0;
-    if (debug)
-        fprintf(stderr, "chgpu: tile-sorted GROUP BY n=%llu hint=%llu S=%u P=%u tile=%u ops=0x%x\n", (unsigned long long)n, (unsigned long long)a->size_hint, S, P, TILE, ops);
-    CHGPU_HIP(hipMemsetAsync(scratch, 0, tot_b + unit_b + pend_b, ctx->stream));
+    const u64 rows_per_wg = ((n + G - 1) / G + tp.TILE - 1) / tp.TILE * tp.TILE;
+    if (chgpu_opt(ctx, "debug", 0))
+        fprintf(stderr, "chgpu: tile-sorted GROUP BY n=%llu hint=%llu S=%u P=%u tile=%u ops=0x%x arg_w=%zu ex=%d\n", (unsigned long long)n, (unsigned long long)in.size_hint, S, P,
+                tp.TILE, tp.ops, tp.arg_w, tp.arg_ex);
+    CHGPU_HIP(hipMemsetAsync(scratch, 0, s.zero_bytes, ctx->stream));
     int rc = CHGPU_OK;
-    const size_t lds_sort = rp_tilesort_lds_bytes(TILE, P, key_w);
-#define GB_TILESORT(TILE_, KT_, AT_, EX_)                                                                                                        \
-    do                                                                                                                                          \
-    {                                                                                                                                           \
-        auto kern = k_rp_tilesort<TILE_, KT_, GbpPartFn<KT_>, RP_THREADS, AT_, EX_>;                                                             \
-        rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sort) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE; \
-        if (rc == CHGPU_OK)                                                                                                                     \
-            hipLaunchKernelGGL(kern, dim3(G), dim3(RP_THREADS), lds_sort, ctx->stream, (const KT_ *)key_col->data + row_begin, (const AT_ *)arg_cols[arg_j]->data + row_begin, n, \
-                               rows_per_wg, P, (KT_ *)pkeys, pwords, tidx, part_total, GbpPartFn<KT_>{P, GBP_MULT});                             \
-    } while (0)
-#define GB_TILESORT_ARG(TILE_, KT_)                             \
-    do                                                          \
-    {                                                           \
-        if (arg_w == 8) GB_TILESORT(TILE_, KT_, u64, 0);        \
-        else if (arg_ex == 3) GB_TILESORT(TILE_, KT_, u32, 3);  \
-        else if (arg_ex == 4) GB_TILESORT(TILE_, KT_, u32, 4);  \
-        else GB_TILESORT(TILE_, KT_, u32, 0);                   \
-    } while (0)
-    if (key32)
-        GB_TILESORT_ARG(12288, u32);
+    dispatch_key(tp.key_w == 4, [&](auto kt) {
+        using KT = decltype(kt);
+        constexpr u32 TILE = sizeof(KT) == 4 ? 12288u : 8192u;
+        auto sort = [&](auto at, auto ex) {
+            using AT = decltype(at);
+            rc = launch_lds(what, k_rp_tilesort<TILE, KT, GbpPartFn<KT>, RP_THREADS, AT, (int)decltype(ex)::value>, dim3(G), dim3(RP_THREADS),
+                            rp_tilesort_lds_bytes(TILE, P, sizeof(KT)), ctx->stream, (const KT *)key_col->data + row_begin, (const AT *)arg_cols[tp.arg_j]->data + row_begin, n,
+                            rows_per_wg, P, (KT *)s.rec, s.rec, s.tidx, s.part_total, GbpPartFn<KT>{P, GBP_MULT});
+        };
+        if (tp.arg_w == 8)
+            sort(u64{}, std::integral_constant<u32, 0>{});
+        else
+            OneOf<0, 3, 4>::dispatch((u32)tp.arg_ex, [&](auto ex) { sort(u32{}, ex); });
+        if (rc != CHGPU_OK)
+            return;
+        hipLaunchKernelGGL(k_tile_units, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long *)s.part_total, P, tp.chunk_rows, n_tiles, s.unit_list, tp.max_units, unit_qstart, unit_ctr);
+        hipLaunchKernelGGL(k_tile_index_transpose, dim3((n_tiles + 63) / 64, (P + 63) / 64), dim3(256), 0, ctx->stream, (const unsigned short *)s.tidx, n_tiles, P, s.run_index);
+        const size_t lds_ag = (size_t)PartLds(sizeof(KT), S, d.n_words, tp.cnt32).bytes() + 16;
+        GbTileOps::dispatch(tp.ops, [&](auto ops) {
+            rc = launch_lds(what, k_agg_tiles_lds<KT, decltype(ops)::value, TILE>, dim3(G), dim3(1024), lds_ag, ctx->stream, a->t, d, (const KT *)s.rec, (const u64 *)s.rec,
+                            (const u32 *)s.run_index, n_tiles, P, s.pending, S, tp.cnt32, (const u64 *)s.unit_list, (const u32 *)unit_qstart, unit_ctr);
+        });
+    });
+    ctx->counters[6] += 3;
+    CHGPU_TRY(rc);
+    return agg_finish_rounds_aos(a, d, (const u32 *)s.rec, tp.key_w == 4 ? 0 : 1, tp.n_pad(), s.pending);
+}
+
+// The scatter plan's launch shape for geometry `g`: tile and grid of the partition passes, whether the loads are wide, the descriptor
+// of the aggregate pass over the partition buffers and its update code.
+static void agg_scatter_plan(const chgpu_agg * a, const AggInput & in, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n,
+                             GbPartPlan * g)
+{
+    const chgpu_ctx * ctx = a->ctx;
+    const u32 K = g->K, P = g->P;
+    g->G = (u32)ctx->num_cus * GBP_WG_PER_CU;
+    // the scatter's LDS image is tile*(8*K + key bytes) + 24*P bytes and must stay under ~159 KiB (160 KiB per workgroup, 64 B static)
+    const size_t row_lds = 8 * K + (g->key32 ? 4 : 8);
+    const u32 tile_cap = (u32)chgpu_opt(ctx, "tune_gb_tile", 12288);
+    g->tile = 4096;
+    for (u32 cand : {8192u, 12288u})
+        if (cand <= tile_cap && cand * row_lds + (size_t)P * 24 + 64 <= 159 * 1024)
+            g->tile = cand;
+    g->rows_per_wg = ((n + g->G - 1) / g->G + g->tile - 1) / g->tile * g->tile;
+    // the argument columns of this call's functions in the order of their words in the partition buffers; the aggregate pass reads the
+    // widened 8-byte words: integers were sign/zero-extended, Float64 kept its bits
+    g->gc.k = K;
+    agg_fill_desc(a, arg_cols, &g->d);
+    u32 kk = 0;
+    for (u32 j = 0; j < a->n_aggs; ++j)
+    {
+        if (a->kinds[j] == CHGPU_AGG_COUNT || !((g->agg_mask >> j) & 1))
+            continue;
+        g->gc.src[kk] = arg_cols[j]->data;
+        g->gc.type[kk] = in.arg_types[j];
+        g->d.a[j].arg_type = chgpu_type_is_float(in.arg_types[j]) ? CHGPU_F64 : CHGPU_U64;
+        g->d.a[j].pre = kk++;
+    }
+    if (g->agg_mask != ~0u)
+        agg_desc_keep(&g->d, g->agg_mask);
+    // wide loads need key/argument columns whose element width is the buffer width and a 16-byte aligned first row
+    const size_t key_w = chgpu_type_size(in.key_type);
+    bool wide = (key_w == 4 || key_w == 8) && ((uintptr_t)key_col->data + row_begin * key_w) % 16 == 0;
+    for (u32 c = 0; c < K; ++c)
+        wide = wide && chgpu_type_size(g->gc.type[c]) == 8 && ((uintptr_t)g->gc.src[c] + row_begin * 8) % 16 == 0;
+    g->wide = wide && !chgpu_opt(ctx, "tune_gb_nowide", 0);
+    // the branch-free scatter (radix_partition.h): one 8-byte word, wide loads
+    g->rp_tile = 0;
+    if (g->wide && K == 1 && n + RP_SCATTER_SLACK < (1ull << 32) && P + 1 <= 2 * RP_THREADS)
+        g->rp_tile = g->key32 && rp_scatter_lds_bytes(12288, P, 4, true) <= 159 * 1024 ? 12288 : 8192;
+    // the update of the state words as a compile-time code where the common shapes allow it
+    g->ops = chgpu_opt(ctx, "tune_gb_noops", 0) ? 0 : agg_update_code(g->d, g->cnt32);
+    if (!GbPartOps::has(g->ops))
+        g->ops = 0;
+}
+
+struct GbScatterScratch
+{
+    u32 * counts;     // [P * G] rows per partition and workgroup
+    u64 * offsets;    // [P * G + 1] their exclusive scan
+    u64 * total_dev;
+    void * tmp;       // the scan's
+    size_t tmp_b;
+    u64 * pending;    // one bit per row, then u32 unit_start[GBP_MAX_P + 1] and the work counter
+    u32 * unit_start;
+    size_t pend_b;    // pending and unit_start together: zeroed before the aggregate pass
+    void * pkeys;     // the partition buffers: keys (4 or 8 B) | word0 | word1, each of `wstride` rows
+    u64 * pwords;
+    u64 wstride;
+    size_t bytes;
+};
+
+// m = P * G counters; n rows of K argument words
+static GbScatterScratch agg_scatter_scratch(void * base, u64 m, u64 n, u32 K, bool key32)
+{
+    ScratchCarver c{(uintptr_t)base};
+    GbScatterScratch s;
+    s.counts = c.take<u32>(m);
+    s.offsets = c.take<u64>(m + 1);
+    s.total_dev = c.take<u64>(1);
+    s.tmp_b = chgpu_scan_tmp_bytes(m);
+    s.tmp = c.take_packed<char>(s.tmp_b);
+    const size_t pend_off = c.off;
+    s.pending = c.take<u64>((n + 63) / 64 + 1);
+    s.unit_start = c.take<u32>(GBP_MAX_P + 2);
+    s.pend_b = c.off - pend_off;
+    // The partition buffers live in the context's scratch arena, which is kept between calls: a fresh hipMalloc of
+    // 16 GB costs ~0.4 s, fifteen times the kernels it would serve.
+    s.wstride = n + RP_SCATTER_SLACK; // rows per array (k_rp_scatter parks out-of-range rows in the slack)
+    s.pkeys = c.take<char>((size_t)s.wstride * (key32 ? 4 : 8));
+    s.pwords = c.take<u64>((size_t)s.wstride * K);
+    s.bytes = c.bytes();
+    return s;
+}
+
+static int agg_add_block_partitioned(chgpu_agg * a, const AggInput & in, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n, u32 K,
+                                     int level = 0, size_t scratch_off = 0, u32 agg_mask = ~0u);
+
+// Level 1 of the two-level plan, after its scatter: every big partition -- a slice of the partition buffers `s` -- goes through a
+// level-2 call with its share of the promised groups; their scratch starts at sub_off, behind this level's own.
+static int agg_partitioned_level2(chgpu_agg * a, const AggInput & in, const GbPartPlan & g, const GbScatterScratch & s, u64 n, size_t sub_off)
+{
+    chgpu_ctx * ctx = a->ctx;
+    const u32 P1 = g.P1;
+    // partition boundaries: offsets[p * G] for p = 0..P1-1 (the read-back also orders the host behind the scatter)
+    std::vector<u64> starts(P1 + 1);
+    void * stage = nullptr;
+    CHGPU_TRY(chgpu_pinned(ctx, (size_t)P1 * 8, &stage));
+    CHGPU_HIP(hipMemcpy2DAsync(stage, 8, s.offsets, (size_t)g.G * 8, 8, P1, hipMemcpyDeviceToHost, ctx->stream));
+    CHGPU_HIP(hipStreamSynchronize(ctx->stream));
+    memcpy(starts.data(), stage, (size_t)P1 * 8);
+    starts[P1] = n;
+    // the partition buffers as columns: keys of the buffer width, arguments widened to 8 bytes (Float64 kept its bits)
+    chgpu_col kc{};
+    kc.ctx = ctx;
+    kc.type = g.key32 ? CHGPU_U32 : CHGPU_U64;
+    kc.rows = n;
+    kc.data = s.pkeys;
+    chgpu_col ac[GBP_MAX_K]{};
+    const chgpu_col * sub_args[AGG_MAX_AGGS] = {};
+    AggInput sub = in;
+    sub.key_type = kc.type;
+    sub.size_hint = in.size_hint / P1 + in.size_hint / P1 / 4 + 1024;
+    u32 c = 0;
+    for (u32 j = 0; j < a->n_aggs; ++j)
+    {
+        if (a->kinds[j] == CHGPU_AGG_COUNT || !((g.agg_mask >> j) & 1))
+            continue;
+        ac[c].ctx = ctx;
+        ac[c].type = sub.arg_types[j] = chgpu_type_is_float(in.arg_types[j]) ? CHGPU_F64 : CHGPU_U64; // two's complement sums: width is what matters
+        ac[c].rows = n;
+        ac[c].data = s.pwords + (u64)c * s.wstride;
+        sub_args[j] = &ac[c];
+        ++c;
+    }
+    for (u32 q = 0; q < P1; ++q)
+        if (starts[q + 1] > starts[q])
+            CHGPU_TRY(agg_add_block_partitioned(a, sub, &kc, sub_args, starts[q], starts[q + 1] - starts[q], g.K, 2, sub_off, g.agg_mask));
+    return CHGPU_OK;
+}
+
+// The scatter plan: histogram, scan, scatter into the partition buffers, then the LDS aggregate pass over them (or, at level 1, a
+// level-2 call per big partition).
+static int agg_scatter_run(chgpu_agg * a, const AggInput & in, const chgpu_col * key_col, u64 row_begin, u64 n, GbPartPlan & g, size_t scratch_off)
+{
+    static const char * const what = "partitioned aggregation";
+    chgpu_ctx * ctx = a->ctx;
+    const u32 K = g.K, P = g.P, G = g.G, S = g.S;
+    const u64 mult = g.mult, rows_per_wg = g.rows_per_wg;
+    if (chgpu_opt(ctx, "debug", 0))
+        fprintf(stderr, "chgpu: partitioned GROUP BY level=%d n=%llu hint=%llu S=%u P=%u G=%u tile=%u ops=0x%x wide=%d rp_tile=%u\n", g.level, (unsigned long long)n,
+                (unsigned long long)in.size_hint, S, P, G, g.tile, g.ops, g.wide ? 1 : 0, g.rp_tile);
+    const u64 m = (u64)P * G;
+    const size_t own_b = agg_scatter_scratch(nullptr, m, n, K, g.key32).bytes;
+    // a level-1 call reserves the region of its level-2 calls up front (growing the arena later would move it): the same
+    // row count at most, bookkeeping for the largest partition count
+    const size_t sub_b = g.level == 1 ? agg_scatter_scratch(nullptr, (u64)GBP_MAX_P * G, n, K, g.key32).bytes + 4096 : 0;
+    void * scratch_base = nullptr;
+    CHGPU_TRY(chgpu_scratch(ctx, scratch_off + own_b + sub_b, &scratch_base));
+    const GbScatterScratch s = agg_scatter_scratch((char *)scratch_base + scratch_off, m, n, K, g.key32);
+    for (u32 c = 0; c < K; ++c)
+        g.gc.dst[c] = s.pwords + (u64)c * s.wstride;
+    AggDesc & d = g.d;
+    for (u32 j = 0; j < d.n_aggs; ++j)
+        if (d.a[j].kind != CHGPU_AGG_COUNT)
+            d.a[j].ptr = g.gc.dst[d.a[j].pre];
+
+    if (g.wide)
+        dispatch_key(g.key32, [&](auto kt) {
+            using KT = decltype(kt);
+            hipLaunchKernelGGL((k_rp_hist_wide<KT, GbpPartFn<KT>>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, (const KT *)key_col->data + row_begin, n, rows_per_wg, P, s.counts,
+                               GbpPartFn<KT>{P, mult});
+        });
     else
-        GB_TILESORT_ARG(8192, u64);
-#undef GB_TILESORT_ARG
-#undef GB_TILESORT
+        hipLaunchKernelGGL(k_gb_hist, dim3(G), dim3(GBP_THREADS), 0, ctx->stream, (const void *)key_col->data, in.key_type, row_begin, n, rows_per_wg, P, s.counts, mult, g.key32 ? 1 : 0);
+    int rc = chgpu_scan_exclusive_u32_u64(ctx, s.counts, s.offsets, m, s.total_dev, s.tmp, s.tmp_b);
+    if (rc == CHGPU_OK)
+        dispatch_key(g.key32, [&](auto kt) {
+            using KT = decltype(kt);
+            if (g.rp_tile)
+            {
+                using Tiles = std::conditional_t<sizeof(KT) == 4, OneOf<12288, 8192>, OneOf<8192>>;
+                Tiles::dispatch(g.rp_tile, [&](auto t) {
+                    constexpr u32 TILE = decltype(t)::value;
+                    rc = launch_lds(what, k_rp_scatter<TILE, KT, true, GbpPartFn<KT>>, dim3(G), dim3(RP_THREADS), rp_scatter_lds_bytes(TILE, P, sizeof(KT), true), ctx->stream,
+                                    (const KT *)key_col->data + row_begin, (const u64 *)g.gc.src[0] + row_begin, n, rows_per_wg, P, (const u64 *)s.offsets, (KT *)s.pkeys,
+                                    g.gc.dst[0], GbpPartFn<KT>{P, mult});
+                });
+                return;
+            }
+            const size_t lds_sc = (size_t)g.tile * (8 * K + sizeof(KT)) + (size_t)P * 24 + 64;
+            OneOf<4096, 8192, 12288>::dispatch(g.tile, [&](auto t) {
+                dispatch_const<0, 1>(g.wide ? 1 : 0, [&](auto w) {
+                    rc = launch_lds(what, k_gb_scatter<decltype(t)::value, KT, decltype(w)::value != 0>, dim3(G), dim3(GBP_THREADS), lds_sc, ctx->stream,
+                                    (const void *)key_col->data, in.key_type, row_begin, n, rows_per_wg, P, (const u64 *)s.offsets, g.gc, (KT *)s.pkeys, mult);
+                });
+            });
+        });
+    if (g.level == 1)
+    {
+        ctx->counters[6] += 2;
+        CHGPU_TRY(rc);
+        return agg_partitioned_level2(a, in, g, s, n, scratch_off + own_b);
+    }
+    if (rc == CHGPU_OK && hipMemsetAsync(s.pending, 0, s.pend_b, ctx->stream) != hipSuccess)
+        rc = chgpu_set_error(CHGPU_ERR_DEVICE, "%s: clearing the pending rows failed", what);
     if (rc == CHGPU_OK)
     {
-        hipLaunchKernelGGL(k_tile_units, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long *)part_total, P, chunk_rows, n_tiles, unit_list, max_units, unit_qstart, unit_ctr);
-        hipLaunchKernelGGL(k_tile_index_transpose, dim3((n_tiles + 63) / 64, (P + 63) / 64), dim3(256), 0, ctx->stream, (const unsigned short *)tidx, n_tiles, P, run_index);
-        const size_t lds_ag = (size_t)PartLds(key_w, S, d.n_words, cnt32).bytes() + 16;
-#define GB_TILES(KT_, OPS_, TILE_)                                                                                                                    \
-    do                                                                                                                                                \
-    {                                                                                                                                                 \
-        auto kern = k_agg_tiles_lds<KT_, OPS_, TILE_>;                                                                                                 \
-        rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ag) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE; \
-        if (rc == CHGPU_OK)                                                                                                                           \
-            hipLaunchKernelGGL(kern, dim3(G), dim3(1024), lds_ag, ctx->stream, a->t, d, (const KT_ *)pkeys, (const u64 *)pwords, (const u32 *)run_index, n_tiles, P, \
-                               pending, S, cnt32, (const u64 *)unit_list, (const u32 *)unit_qstart, unit_ctr);                                        \
-    } while (0)
-#define GB_TILES_OPS(KT_, TILE_)                        \
-    switch (ops)                                        \
-    {                                                   \
-        case 0x51: GB_TILES(KT_, 0x51, TILE_); break;   \
-        case 0x15: GB_TILES(KT_, 0x15, TILE_); break;   \
-        case 0x1: GB_TILES(KT_, 0x1, TILE_); break;     \
-        case 0x53: GB_TILES(KT_, 0x53, TILE_); break;   \
-        case 0x3: GB_TILES(KT_, 0x3, TILE_); break;     \
-        case 0x61: GB_TILES(KT_, 0x61, TILE_); break;   \
-        case 0x97: GB_TILES(KT_, 0x97, TILE_); break;   \
-        case 0x957: GB_TILES(KT_, 0x957, TILE_); break; \
-        case 0x967: GB_TILES(KT_, 0x967, TILE_); break; \
-        default: GB_TILES(KT_, 0x16, TILE_); break;     \
-    }
-        if (key32)
-        {
-            GB_TILES_OPS(u32, 12288)
-        }
-        else
-        {
-            GB_TILES_OPS(u64, 8192)
-        }
-#undef GB_TILES_OPS
-#undef GB_TILES
+        u32 * unit_ctr = s.unit_start + GBP_MAX_P + 1;
+        hipLaunchKernelGGL(k_gb_units, dim3(1), dim3(1024), 0, ctx->stream, (const u64 *)s.offsets, G, P, n, g.chunk_rows, s.unit_start, unit_ctr);
+        dispatch_key(g.key32, [&](auto kt) {
+            using KT = decltype(kt);
+            const size_t lds_ag = (size_t)PartLds(sizeof(KT), S, a->n_words, g.cnt32).bytes() + 16; // the kernel zeroes whole 8-byte words
+            auto launch = [&](auto ops) {
+                rc = launch_lds(what, k_agg_part_lds<KT, 8, KT, false, decltype(ops)::value>, dim3((u32)ctx->num_cus), dim3(1024), lds_ag, ctx->stream, a->t, d, (const KT *)s.pkeys,
+                                (const void *)s.pwords, (const void *)(s.pwords + s.wstride), (const u64 *)s.offsets, G, P, n, s.pending, S, K, g.cnt32, g.chunk_rows,
+                                (const u32 *)s.unit_start, unit_ctr, (const u8 *)nullptr);
+            };
+            if (!GbPartOps::dispatch(g.ops, launch))
+                launch(std::integral_constant<u32, 0>{}); // the update read from the descriptor
+        });
     }
     ctx->counters[6] += 3;
-    ctx->counters[5] += n;
-    if (rc == CHGPU_OK && hipGetLastError() != hipSuccess)
-        rc = CHGPU_ERR_DEVICE;
-    if (rc == CHGPU_OK)
-        rc = agg_finish_rounds_aos(a, d, (const u32 *)pwords, key32 ? 0 : 1, n_pad, pending);
-    else
-    {
-        (void)hipGetLastError();
-        chgpu_set_error(rc, "tile-sorted aggregation launch failed");
-    }
-    return rc;
+    CHGPU_TRY(rc);
+    return agg_finish_rounds(a, d, s.pkeys, g.key32 ? CHGPU_U32 : CHGPU_U64, 0, n, s.pending);
 }
 
 // PARTITIONED executeOnBlock (see the kernel block comment).  Returns NOT_IMPLEMENTED when the shape does not fit
@@ -2852,321 +3238,100 @@ static int agg_add_block_tiled(chgpu_agg * a, const chgpu_col * key_col, const c
 // into P1 big partitions and runs a level-2 call over each partition buffer slice); level 2 never recurses.
 // agg_mask: the aggregate functions this call applies (bit j = function j); the caller splits more than GBP_MAX_K argument
 // columns into several calls over the same rows, each partitioning the key column with its own two argument columns.
-static int agg_add_block_partitioned(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n, u32 K,
-                                     int level = 0, size_t scratch_off = 0, u32 agg_mask = ~0u, int word_pass = 0 /* 1: a per-word local pass, 2: its probe */)
+static int agg_add_block_partitioned(chgpu_agg * a, const AggInput & in, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n, u32 K,
+                                     int level, size_t scratch_off, u32 agg_mask)
 {
-    const bool probe_only = word_pass == 2;
-    chgpu_ctx * ctx = a->ctx;
-    // LDS table of the aggregate pass (one 1024-thread workgroup per CU): compact cells -- key as wide as the partition
-    // buffer's keys, COUNT words as 32 bits while the call has fewer than 2^32 rows -- and as many cells as fit ~150 KiB
-    const bool key32 = chgpu_type_size(a->key_type) <= 4; // 4-byte (or narrower) keys are stored as 4 bytes in the partition buffers
-    u32 cnt32 = 0;
-    size_t cell_b = agg_part_cell_bytes(a, n, &cnt32);
-    // a pass over ONE argument word of a subset of the functions goes through the tile-sorted plan with cells that hold only its words
-    const bool local_pass = word_pass != 0 && level == 0 && K == 1 && agg_mask != ~0u;
-    if (local_pass)
-        cell_b = agg_part_cell_bytes_masked(a, n, agg_mask);
-    const u32 S = agg_part_max_cells(a->ctx, cell_b);
-    // partitions so that a partition's expected groups fill at most 70 % of the LDS table (fewer partitions = longer runs in
-    // the scatter: an estimate of 1.25 M groups still gets 256 partitions)
-    const u64 part_cap = (u64)S * 7 / 10;
-    u64 want_p = (a->size_hint + part_cap - 1) / part_cap;
-    u32 P = 64;
-    while (P < (u32)ctx->num_cus && P < GBP_MAX_P) // the aggregate pass runs one workgroup per partition: give every CU one
-        P <<= 1;
-    while (P < want_p && P < GBP_MAX_P)
-        P <<= 1;
-    // More groups than P_max partitions x half an LDS table: TWO LEVELS.  Level 1 cuts the rows into P1 big partitions with an
-    // independent hash (long runs: close to a copy), then every big partition -- already in the 4/8-byte key + 8-byte word
-    // layout -- goes through this function again (level 2) with its share of the promised groups.
-    u64 mult = GBP_MULT;
-    u32 P1 = 0;
-    // (want_p already allows LDS tables 70 % full: up to ~5.9 M groups one level is the faster plan, 16 vs 24 ms at 5 M)
-    if (want_p > GBP_MAX_P && level == 0 && !chgpu_opt(ctx, "tune_gb_no_two_level", 0))
-    {
-        const u64 sub_groups = (u64)(GBP_MAX_P / 2) * (S / 2); // leaves the second level at half its partition budget
-        for (P1 = 2; (u64)P1 * sub_groups < a->size_hint && P1 < 256; P1 <<= 1)
-            ;
-        if ((u64)P1 * sub_groups * 2 < a->size_hint || n / P1 < (1u << 20))
-            return CHGPU_ERR_NOT_IMPLEMENTED; // beyond two levels, or partitions too small to be worth three passes each
-        P = P1;
-        mult = GBP_MULT1;
-        level = 1;
-    }
-    else if (level == 0 && (u64)P * (S / 2) < a->size_hint / 4) // hopelessly more groups than P * S: partitioning would not localise them
-        return CHGPU_ERR_NOT_IMPLEMENTED;
-    // work units of the aggregate pass: half an average partition each, so a uniform input gives every workgroup two
-    // units and a partition swollen by a hot key is spread over many workgroups; each unit flushes its LDS table once
-    const u32 unit_div = (u32)chgpu_opt(ctx, "tune_gb_unitdiv", 2);
-    u64 chunk_rows = (n / ((u64)P * unit_div) + 63) / 64 * 64;
-    if (chunk_rows < 65536)
-        chunk_rows = 65536;
-    const u64 max_units = n / chunk_rows + P; // sum over partitions of ceil(rows_p / chunk_rows)
-    // every unit's flush may claim up to S+1 cells without the max-fill check: keep all of them inside the slack
-    if (level != 1) // a first partitioning level touches no table: its level-2 calls size it
-        CHGPU_TRY(agg_ensure_table(a, 2 * (max_units * (S + 1) + a->n_groups) + 2));
-    for (int guard = 0; level != 1 && !a->t.find_only && guard < 16 && a->t.capacity / 2 < max_units * (S + 1) + a->n_groups; ++guard)
-    {
-        AggCtrl c0;
-        CHGPU_TRY(agg_read_ctrl(a, &c0));
-        CHGPU_TRY(agg_grow(a, c0.n_groups, c0.has_zero != 0));
-    }
+    GbPartPlan g;
+    CHGPU_TRY(agg_partition_geometry(a, in, n, K, level, agg_mask, false, &g));
+    CHGPU_TRY(agg_partition_size_table(a, g, in.size_hint));
     // one level, one argument word: the tile-sorted plan (two passes, streaming writes) where its shape fits
-    const bool no_tiled = chgpu_opt(ctx, "tune_gb_no_tiled", 0) != 0;
-    if (level == 0 && K == 1 && !no_tiled)
+    if (g.level == 0 && K == 1 && !chgpu_opt(a->ctx, "tune_gb_no_tiled", 0))
     {
-        const int rc_t = agg_add_block_tiled(a, key_col, arg_cols, row_begin, n, P, S, cnt32, agg_mask, chunk_rows, probe_only);
-        if (rc_t != CHGPU_ERR_NOT_IMPLEMENTED || local_pass) // (a local pass was sized for the tile-sorted plan alone: the caller falls back as a whole)
-            return rc_t;
+        GbTilePlan tp;
+        if (agg_tile_plan(a, in, key_col, arg_cols, row_begin, n, g, &tp) == CHGPU_OK)
+            return agg_tile_run(a, in, key_col, arg_cols, row_begin, n, g, tp);
     }
-    if (probe_only)
+    agg_scatter_plan(a, in, key_col, arg_cols, row_begin, n, &g);
+    return agg_scatter_run(a, in, key_col, row_begin, n, g, scratch_off);
+}
+
+// One pass of a per-word GROUP BY: the functions of `agg_mask` (one argument word, perhaps the counts) through the tile-sorted plan,
+// with partitions and LDS cells sized for their state words alone.  launch = false only asks whether the plan takes the pass; the
+// table is sized either way (see agg_partition_size_table).  NOT_IMPLEMENTED = it does not (a pass sized for this plan has no other).
+static int agg_word_pass(chgpu_agg * a, const AggInput & in, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n, u32 agg_mask,
+                         bool launch)
+{
+    GbPartPlan g;
+    CHGPU_TRY(agg_partition_geometry(a, in, n, 1, 0, agg_mask, true, &g));
+    CHGPU_TRY(agg_partition_size_table(a, g, in.size_hint));
+    if (g.level != 0)
         return CHGPU_ERR_NOT_IMPLEMENTED;
-    const u32 G = (u32)ctx->num_cus * GBP_WG_PER_CU;
-    u64 rows_per_wg = (n + G - 1) / G;
-    // the scatter's LDS image is tile*(8*K + key bytes) + 24*P bytes and must stay under ~159 KiB (160 KiB per workgroup, 64 B static)
-    const size_t row_lds = 8 * K + (key32 ? 4 : 8);
-    const u32 tile_cap = (u32)chgpu_opt(ctx, "tune_gb_tile", 12288);
-    u32 tile = 4096;
-    for (u32 cand : {8192u, 12288u})
-        if (cand <= tile_cap && cand * row_lds + (size_t)P * 24 + 64 <= 159 * 1024)
-            tile = cand;
-    rows_per_wg = (rows_per_wg + tile - 1) / tile * tile;
-    const bool debug = chgpu_opt(ctx, "debug", 0) != 0;
-    if (debug)
-        fprintf(stderr, "chgpu: partitioned GROUP BY level=%d n=%llu hint=%llu S=%u P=%u G=%u tile=%u\n", level, (unsigned long long)n, (unsigned long long)a->size_hint, S, P, G, tile);
+    GbTilePlan tp;
+    CHGPU_TRY(agg_tile_plan(a, in, key_col, arg_cols, row_begin, n, g, &tp));
+    return launch ? agg_tile_run(a, in, key_col, arg_cols, row_begin, n, g, tp) : CHGPU_OK;
+}
 
-    // partition buffers (8-byte keys + K 8-byte words per row) and bookkeeping
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const u64 m = (u64)P * G;
-    const size_t cnt_b = al(m * 4), off_b = al(m * 8 + 8), tmp_b = chgpu_scan_tmp_bytes(m), pend_b = al(((n + 63) / 64) * 8 + 8) + al((GBP_MAX_P + 2) * 4);
-    // The partition buffers live in the context's scratch arena, which is kept between calls: a fresh hipMalloc of
-    // 16 GB costs ~0.4 s, fifteen times the kernels it would serve.
-    const u64 wstride = n + RP_SCATTER_SLACK; // rows per argument-word array (k_rp_scatter parks out-of-range rows in the slack)
-    const size_t keys_b = al((size_t)wstride * (key32 ? 4 : 8));
-    const size_t part_b = keys_b + al((size_t)wstride * 8 * K);
-    const size_t own_b = al(cnt_b + off_b + 256 + tmp_b + pend_b + part_b);
-    // a level-1 call reserves the region of its level-2 calls up front (growing the arena later would move it): the same
-    // row count at most, bookkeeping for the largest partition count
-    const u64 m2 = (u64)GBP_MAX_P * G;
-    const size_t sub_b = level == 1 ? al(al(m2 * 4) + al(m2 * 8 + 8) + 256 + chgpu_scan_tmp_bytes(m2) + pend_b + part_b) + 4096 : 0;
-    void * scratch_base = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, scratch_off + own_b + sub_b, &scratch_base));
-    void * scratch = (char *)scratch_base + scratch_off;
-    u32 * counts = (u32 *)scratch;
-    u64 * offsets = (u64 *)((char *)scratch + cnt_b);
-    u64 * total_dev = (u64 *)((char *)scratch + cnt_b + off_b);
-    void * tmp = (char *)scratch + cnt_b + off_b + 256;
-    u64 * pending = (u64 *)((char *)scratch + cnt_b + off_b + 256 + tmp_b);
-    u32 * unit_start = (u32 *)((char *)pending + al(((n + 63) / 64) * 8 + 8)); // [P + 1] then the work counter
-    u32 * unit_ctr = unit_start + GBP_MAX_P + 1;
-    void * pkeys = (char *)scratch + cnt_b + off_b + 256 + tmp_b + pend_b; // keys (4 or 8 B) | word0 | word1
-    u64 * pwords = (u64 *)((char *)pkeys + keys_b);
-
-    GbpCols gc;
-    gc.k = K;
-    AggDesc d;
-    agg_fill_desc(a, arg_cols, &d);
-    u32 kk = 0;
+// The functions that take an argument, `per_call` at a time in their order, as one mask per call (ks[c]: how many the call carries);
+// every count() rides in the first.  Returns the number of calls.
+static u32 agg_split_calls(const chgpu_agg * a, u32 per_call, u32 * masks, u32 * ks)
+{
+    u32 n_calls = 0;
     for (u32 j = 0; j < a->n_aggs; ++j)
     {
-        if (a->kinds[j] == CHGPU_AGG_COUNT || !((agg_mask >> j) & 1))
+        if (a->kinds[j] == CHGPU_AGG_COUNT)
             continue;
-        gc.src[kk] = arg_cols[j]->data;
-        gc.type[kk] = a->arg_types[j];
-        gc.dst[kk] = pwords + (u64)kk * wstride;
-        // the aggregate pass reads widened 8-byte words: integers were sign/zero-extended, Float64 kept its bits
-        d.a[j].ptr = gc.dst[kk];
-        d.a[j].arg_type = chgpu_type_is_float(a->arg_types[j]) ? CHGPU_F64 : CHGPU_U64;
-        d.a[j].pre = kk;
-        ++kk;
+        if (n_calls == 0 || ks[n_calls - 1] == per_call)
+            masks[n_calls] = 0, ks[n_calls] = 0, ++n_calls;
+        masks[n_calls - 1] |= 1u << j;
+        ++ks[n_calls - 1];
     }
-    if (agg_mask != ~0u)
-    {
-        // keep only this call's functions in the descriptor (their state word indices stay the aggregator's own)
-        u32 m = 0;
-        for (u32 j = 0; j < a->n_aggs; ++j)
-            if ((agg_mask >> j) & 1)
-                d.a[m++] = d.a[j];
-        d.n_aggs = m;
-    }
+    if (n_calls)
+        masks[0] |= agg_count_mask(a);
+    return n_calls;
+}
 
-    // wide loads need key/argument columns whose element width is the buffer width and a 16-byte aligned first row
-    const size_t key_w = chgpu_type_size(a->key_type);
-    bool wide = (key_w == 4 || key_w == 8) && ((uintptr_t)key_col->data + row_begin * key_w) % 16 == 0;
-    for (u32 c = 0; c < K; ++c)
-        wide = wide && chgpu_type_size(gc.type[c]) == 8 && ((uintptr_t)gc.src[c] + row_begin * 8) % 16 == 0;
-    const bool no_wide = chgpu_opt(ctx, "tune_gb_nowide", 0) != 0;
-    wide = wide && !no_wide;
-    if (wide && key_w == 4)
-        hipLaunchKernelGGL((k_rp_hist_wide<u32, GbpPartFn<u32>>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, (const u32 *)key_col->data + row_begin, n, rows_per_wg, P, counts, GbpPartFn<u32>{P, mult});
-    else if (wide)
-        hipLaunchKernelGGL((k_rp_hist_wide<u64, GbpPartFn<u64>>), dim3(G), dim3(RP_THREADS), 0, ctx->stream, (const u64 *)key_col->data + row_begin, n, rows_per_wg, P, counts, GbpPartFn<u64>{P, mult});
-    else
-        hipLaunchKernelGGL(k_gb_hist, dim3(G), dim3(GBP_THREADS), 0, ctx->stream, (const void *)key_col->data, a->key_type, row_begin, n, rows_per_wg, P, counts, mult, key32 ? 1 : 0);
-    int rc = chgpu_scan_exclusive_u32_u64(ctx, counts, offsets, m, total_dev, tmp, tmp_b);
-    if (rc == CHGPU_OK)
+// PARTITIONED strategy: large promised cardinality and enough rows to amortise two extra passes
+static bool agg_partition_gate(const chgpu_agg * a, u64 lds_groups, u64 n)
+{
+    return a->size_hint > lds_groups && n >= (4u << 20) && !chgpu_opt(a->ctx, "agg_no_partition", 0);
+}
+
+// The partitioned plans for a block that passed agg_partition_gate.  NOT_IMPLEMENTED: no plan takes the shape and nothing was added.
+static int agg_add_block_by_partitions(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n)
+{
+    chgpu_ctx * ctx = a->ctx;
+    const AggInput in = agg_input_of(a);
+    u32 masks[AGG_MAX_AGGS], ks[AGG_MAX_AGGS];
+    const u32 n_argwords = agg_split_calls(a, 1, masks, ks);
+    // Two or more argument words: ONE PASS PER WORD through the tile-sorted plan (each pass sorts {key, its word} and aggregates into
+    // cells that hold only its own state words; every count() rides in the first) -- 7 ms per word and 1e9 rows, against 22 ms for
+    // the two-word scatter plan, whose 4096-row tiles leave 8-row runs (tools/bench_two_words.py).  A shape the plan does not take
+    // answers NOT_IMPLEMENTED when asked, before anything was added: the older routes below take over.
+    if (n_argwords >= 2 && !chgpu_opt(ctx, "tune_gb_no_tiled", 0) && !chgpu_opt(ctx, "tune_gb_no_word_passes", 0))
     {
-        const size_t lds_sc = (size_t)tile * row_lds + (size_t)P * 24 + 64;
-#define GB_SCATTER(TILE_, KT_) do { if (wide) GB_SCATTER_W(TILE_, KT_, true); else GB_SCATTER_W(TILE_, KT_, false); } while (0)
-#define GB_SCATTER_W(TILE_, KT_, W_)                                                                                                            \
-    do                                                                                                                                          \
-    {                                                                                                                                           \
-        auto kern = k_gb_scatter<TILE_, KT_, W_>;                                                                                               \
-        rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sc) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE; \
-        if (rc == CHGPU_OK)                                                                                                                     \
-            hipLaunchKernelGGL(kern, dim3(G), dim3(GBP_THREADS), lds_sc, ctx->stream, (const void *)key_col->data, a->key_type, row_begin, n, rows_per_wg, P, \
-                               (const u64 *)offsets, gc, (KT_ *)pkeys, mult);                                                                        \
-    } while (0)
-        if (wide && K == 1 && n + RP_SCATTER_SLACK < (1ull << 32) && P + 1 <= 2 * RP_THREADS)
+        // every pass is asked first whether the plan takes it (nothing may be added before all of them are known to run)
+        int rc = CHGPU_OK;
+        for (u32 c = 0; c < n_argwords && rc == CHGPU_OK; ++c)
+            rc = agg_word_pass(a, in, key_col, arg_cols, row_begin, n, masks[c], false);
+        for (u32 c = 0; c < n_argwords && rc == CHGPU_OK; ++c)
         {
-            // the branch-free scatter (radix_partition.h): one 8-byte word, wide loads
-            if (key32 && rp_scatter_lds_bytes(12288, P, 4, true) <= 159 * 1024)
-            {
-                auto kern = k_rp_scatter<12288, u32, true, GbpPartFn<u32>>;
-                const size_t lds_b = rp_scatter_lds_bytes(12288, P, 4, true);
-                rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE;
-                if (rc == CHGPU_OK)
-                    hipLaunchKernelGGL(kern, dim3(G), dim3(RP_THREADS), lds_b, ctx->stream, (const u32 *)key_col->data + row_begin, (const u64 *)gc.src[0] + row_begin, n, rows_per_wg, P,
-                                       (const u64 *)offsets, (u32 *)pkeys, gc.dst[0], GbpPartFn<u32>{P, mult});
-            }
-            else if (key32)
-            {
-                auto kern = k_rp_scatter<8192, u32, true, GbpPartFn<u32>>;
-                const size_t lds_b = rp_scatter_lds_bytes(8192, P, 4, true);
-                rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE;
-                if (rc == CHGPU_OK)
-                    hipLaunchKernelGGL(kern, dim3(G), dim3(RP_THREADS), lds_b, ctx->stream, (const u32 *)key_col->data + row_begin, (const u64 *)gc.src[0] + row_begin, n, rows_per_wg, P,
-                                       (const u64 *)offsets, (u32 *)pkeys, gc.dst[0], GbpPartFn<u32>{P, mult});
-            }
-            else
-            {
-                auto kern = k_rp_scatter<8192, u64, true, GbpPartFn<u64>>;
-                const size_t lds_b = rp_scatter_lds_bytes(8192, P, 8, true);
-                rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE;
-                if (rc == CHGPU_OK)
-                    hipLaunchKernelGGL(kern, dim3(G), dim3(RP_THREADS), lds_b, ctx->stream, (const u64 *)key_col->data + row_begin, (const u64 *)gc.src[0] + row_begin, n, rows_per_wg, P,
-                                       (const u64 *)offsets, (u64 *)pkeys, gc.dst[0], GbpPartFn<u64>{P, mult});
-            }
+            rc = agg_word_pass(a, in, key_col, arg_cols, row_begin, n, masks[c], true);
+            if (rc == CHGPU_ERR_NOT_IMPLEMENTED) // (the plan said yes when asked: not reached)
+                return chgpu_set_error(CHGPU_ERR_LOGICAL, "a pass of a per-word GROUP BY was refused after its probe");
         }
-        else if (tile == 12288) { if (key32) GB_SCATTER(12288, u32); else GB_SCATTER(12288, u64); }
-        else if (tile == 8192) { if (key32) GB_SCATTER(8192, u32); else GB_SCATTER(8192, u64); }
-        else                   { if (key32) GB_SCATTER(4096, u32); else GB_SCATTER(4096, u64); }
-#undef GB_SCATTER
-#undef GB_SCATTER_W
+        if (rc != CHGPU_ERR_NOT_IMPLEMENTED)
+            return rc;
     }
-    if (level == 1)
-    {
-        ctx->counters[6] += 2;
-        if (rc == CHGPU_OK && hipGetLastError() != hipSuccess)
-            rc = CHGPU_ERR_DEVICE;
-        if (rc != CHGPU_OK)
-        {
-            (void)hipGetLastError();
-            return chgpu_set_error(rc, "partitioned aggregation launch failed");
-        }
-        // partition boundaries: offsets[p * G] for p = 0..P1-1 (the read-back also orders the host behind the scatter)
-        std::vector<u64> starts(P1 + 1);
-        {
-            void * stage = nullptr;
-            CHGPU_TRY(chgpu_pinned(ctx, (size_t)P1 * 8, &stage));
-            CHGPU_HIP(hipMemcpy2DAsync(stage, 8, offsets, (size_t)G * 8, 8, P1, hipMemcpyDeviceToHost, ctx->stream));
-            CHGPU_HIP(hipStreamSynchronize(ctx->stream));
-            memcpy(starts.data(), stage, (size_t)P1 * 8);
-            starts[P1] = n;
-        }
-        // the partition buffers as columns: keys of the buffer width, arguments widened to 8 bytes (Float64 kept its bits)
-        chgpu_col kc{};
-        kc.ctx = ctx;
-        kc.type = key32 ? CHGPU_U32 : CHGPU_U64;
-        kc.rows = n;
-        kc.data = pkeys;
-        chgpu_col ac[GBP_MAX_K]{};
-        const chgpu_col * sub_args[AGG_MAX_AGGS] = {};
-        const int saved_key_type = a->key_type;
-        int saved_arg_types[AGG_MAX_AGGS];
-        const u64 saved_hint = a->size_hint;
-        u32 c = 0;
-        for (u32 j = 0; j < a->n_aggs; ++j)
-        {
-            saved_arg_types[j] = a->arg_types[j];
-            if (a->kinds[j] == CHGPU_AGG_COUNT || !((agg_mask >> j) & 1))
-                continue;
-            ac[c].ctx = ctx;
-            ac[c].type = chgpu_type_is_float(a->arg_types[j]) ? CHGPU_F64 : CHGPU_U64; // two's complement sums: width is what matters
-            ac[c].rows = n;
-            ac[c].data = pwords + (u64)c * wstride;
-            a->arg_types[j] = ac[c].type;
-            sub_args[j] = &ac[c];
-            ++c;
-        }
-        a->key_type = kc.type;
-        a->size_hint = saved_hint / P1 + saved_hint / P1 / 4 + 1024;
-        for (u32 q = 0; q < P1 && rc == CHGPU_OK; ++q)
-            if (starts[q + 1] > starts[q])
-                rc = agg_add_block_partitioned(a, &kc, sub_args, starts[q], starts[q + 1] - starts[q], K, 2, scratch_off + own_b, agg_mask);
-        a->key_type = saved_key_type;
-        a->size_hint = saved_hint;
-        for (u32 j = 0; j < a->n_aggs; ++j)
-            a->arg_types[j] = saved_arg_types[j];
-        return rc;
-    }
-    if (rc == CHGPU_OK)
-        rc = hipMemsetAsync(pending, 0, pend_b, ctx->stream) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE;
-    if (rc == CHGPU_OK)
-    {
-        const size_t lds_ag = (size_t)PartLds(key32 ? 4 : 8, S, a->n_words, cnt32).bytes() + 16; // the kernel zeroes whole 8-byte words
-        hipLaunchKernelGGL(k_gb_units, dim3(1), dim3(1024), 0, ctx->stream, (const u64 *)offsets, G, P, n, chunk_rows, unit_start, unit_ctr);
-        const u64 rows_per_chunk = chunk_rows;
-        u32 grid = (u32)ctx->num_cus;
-        // the update of the state words as a compile-time code where the common shapes allow it
-        const u32 ops = chgpu_opt(ctx, "tune_gb_noops", 0) ? 0 : agg_update_code(d, cnt32);
-#define GB_AGG(KT_, OPS_)                                                                                                                              \
-    do                                                                                                                                                \
-    {                                                                                                                                                 \
-        auto kern = k_agg_part_lds<KT_, 8, KT_, false, OPS_>;                                                                                          \
-        rc = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ag) == hipSuccess ? CHGPU_OK : CHGPU_ERR_DEVICE; \
-        if (rc == CHGPU_OK)                                                                                                                           \
-            hipLaunchKernelGGL(kern, dim3(grid), dim3(1024), lds_ag, ctx->stream, a->t, d, (const KT_ *)pkeys, (const void *)pwords, (const void *)(pwords + wstride), \
-                               (const u64 *)offsets, G, P, n, pending, S, K, cnt32, rows_per_chunk, (const u32 *)unit_start, unit_ctr, (const u8 *)nullptr); \
-    } while (0)
-#define GB_AGG_OPS(KT_)                                      \
-    switch (ops)                                             \
-    {                                                        \
-        case 0x51: GB_AGG(KT_, 0x51); break; /* sum, count */     \
-        case 0x15: GB_AGG(KT_, 0x15); break; /* count, sum */     \
-        case 0x1: GB_AGG(KT_, 0x1); break;   /* sum */            \
-        case 0x5: GB_AGG(KT_, 0x5); break;   /* count */          \
-        case 0x53: GB_AGG(KT_, 0x53); break; /* sum(Float64), count = avg(Float64) */ \
-        case 0x3: GB_AGG(KT_, 0x3); break;   /* sum(Float64) */   \
-        case 0x21: GB_AGG(KT_, 0x21); break; /* sum, sum */       \
-        case 0x521: GB_AGG(KT_, 0x521); break; /* sum, sum, count */ \
-        case 0x97: GB_AGG(KT_, 0x97); break; /* sum(Float64) as a fixed-point pair */ \
-        case 0x957: GB_AGG(KT_, 0x957); break; /* the same + count: avg(Float64) */ \
-        default: GB_AGG(KT_, 0); break;                      \
-    }
-        if (key32)
-        {
-            GB_AGG_OPS(u32)
-        }
-        else
-        {
-            GB_AGG_OPS(u64)
-        }
-#undef GB_AGG_OPS
-#undef GB_AGG
-    }
-    ctx->counters[6] += 3;
-    ctx->counters[5] += n;
-    if (rc == CHGPU_OK && hipGetLastError() != hipSuccess)
-        rc = CHGPU_ERR_DEVICE;
-    if (rc == CHGPU_OK)
-        rc = agg_finish_rounds(a, d, pkeys, key32 ? CHGPU_U32 : CHGPU_U64, 0, n, pending);
-    else
-    {
-        (void)hipGetLastError(); // do not leave a sticky launch error behind for the next call
-        chgpu_set_error(rc, "partitioned aggregation launch failed");
-    }
-    return rc;
+    if (n_argwords <= GBP_MAX_K)
+        return agg_add_block_partitioned(a, in, key_col, arg_cols, row_begin, n, n_argwords);
+    // more argument columns than a partition buffer row carries: several partitioned calls over the same rows, each with
+    // two of them (plus every count() in the first) -- ~12 ms per 1e9 rows and call, against one HBM atomic per row
+    // and state word on the DIRECT path
+    const u32 n_calls = agg_split_calls(a, GBP_MAX_K, masks, ks);
+    int rc = CHGPU_OK;
+    for (u32 c = 0; c < n_calls && rc == CHGPU_OK; ++c)
+        rc = agg_add_block_partitioned(a, in, key_col, arg_cols, row_begin, n, ks[c], 0, 0, masks[c]);
+    return rc; // (NOT_IMPLEMENTED comes from the first call, before anything was applied: the caller takes the other strategies)
 }
 
 static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 row_end,
@@ -3320,7 +3485,8 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
     {
         u32 n = 0;           // argument columns in this pass
         u32 agg[GBP_MAX_K];  // their aggregate indices
-        size_t aw = 8;
+        size_t aw = 8;       // their width
+        bool ext = false;    // one of them is a signed narrow integer or Float32
     };
     Pass passes[AGG_MAX_AGGS];
     u32 n_passes = 0;
@@ -3339,13 +3505,15 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
             ++n_passes;
         }
         passes[p].agg[passes[p].n++] = j;
+        const int at = a->arg_types[j];
+        passes[p].ext = passes[p].ext || at == CHGPU_I8 || at == CHGPU_I16 || at == CHGPU_I32 || at == CHGPU_F32;
     }
     if (n_passes == 0)
         n_passes = 1; // only count(): one pass without argument columns
 
-    const bool key32 = chgpu_type_size(a->key_type) <= 4, key8 = chgpu_type_size(a->key_type) == 1, key16 = chgpu_type_size(a->key_type) == 2;
+    const size_t key_w = chgpu_type_size(a->key_type);
     u32 cnt32 = 0;
-    (void)agg_part_cell_bytes(a, n, &cnt32);
+    (void)agg_part_cell_bytes(a, a->key_type, n, &cnt32);
     // cells: four times the promised groups (4096 when nothing was promised), bounded by ~150 KiB of LDS; tables of up
     // to ~76 KiB let two 1024-thread workgroups share a CU
     const u32 s_dflt = (u32)chgpu_opt(ctx, "tune_agg_ranged_s", 4096);
@@ -3355,7 +3523,7 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
             ;
     if (S > lds_cells)
         S = lds_cells;
-    const size_t lds_ag = (size_t)PartLds(key32 ? 4 : 8, S, a->n_words, cnt32).bytes() + 16;
+    const size_t lds_ag = (size_t)PartLds(key_w <= 4 ? 4 : 8, S, a->n_words, cnt32).bytes() + 16;
     const u32 wg_per_cu = lds_ag <= 76 * 1024 ? 2 : 1;
     // flushes may claim up to grid * (S+1) cells above max fill: keep that inside the slack (capacity/2)
     const u64 max_grid = (a->t.capacity / 2) / (S + 1);
@@ -3368,8 +3536,13 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
     chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
     const u8 * cond_ptr = filter ? (const u8 *)filter->data + row_begin : nullptr;
     if (chgpu_opt(ctx, "debug", 0))
-        fprintf(stderr, "chgpu: ranged GROUP BY n=%llu hint=%llu S=%u chunks=%llu passes=%u\n", (unsigned long long)n, (unsigned long long)a->size_hint, S,
-                (unsigned long long)chunks, n_passes);
+    {
+        std::string aw, ext; // per pass, comma-separated
+        for (u32 p = 0; p < n_passes; ++p)
+            aw += (p ? "," : "") + std::to_string(passes[p].aw), ext += (p ? "," : "") + std::to_string(passes[p].ext ? 1 : 0);
+        fprintf(stderr, "chgpu: ranged GROUP BY n=%llu hint=%llu S=%u chunks=%llu passes=%u key_w=%zu aw=%s ext=%s\n", (unsigned long long)n,
+                (unsigned long long)a->size_hint, S, (unsigned long long)chunks, n_passes, key_w, aw.c_str(), ext.c_str());
+    }
     for (u32 p = 0; p < n_passes; ++p)
     {
         // this pass's descriptor: its argument functions, plus every count() in the first pass; state word indices are
@@ -3385,54 +3558,100 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
             ++dp.n_aggs;
             rwords[c] = (const char *)arg_cols[j]->data + row_begin * passes[p].aw;
         }
-        if (p == 0)
-            for (u32 j = 0; j < a->n_aggs; ++j)
-                if (a->kinds[j] == CHGPU_AGG_COUNT)
-                    dp.a[dp.n_aggs++] = d.a[j];
+        const u32 first_counts = p == 0 ? agg_count_mask(a) : 0;
+        for (u32 j = 0; j < a->n_aggs; ++j)
+            if ((first_counts >> j) & 1)
+                dp.a[dp.n_aggs++] = d.a[j];
         const u32 rk = passes[p].n;
-        const size_t aw = passes[p].aw;
-        bool need_ext = false; // a signed narrow integer or Float32 argument in this pass
-        for (u32 c = 0; c < passes[p].n; ++c)
-        {
-            const int at = a->arg_types[passes[p].agg[c]];
-            need_ext = need_ext || at == CHGPU_I8 || at == CHGPU_I16 || at == CHGPU_I32 || at == CHGPU_F32;
-        }
         CHGPU_HIP(hipMemsetAsync(pending, 0, n_words64 * sizeof(u64), ctx->stream));
-#define RANGE_LAUNCH_X(KT_, AW_, KS_, X_)                                                                                                              \
-    do                                                                                                                                                \
-    {                                                                                                                                                 \
-        CHGPU_HIP(hipFuncSetAttribute((const void *)k_agg_part_lds<KT_, AW_, KS_, X_>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_ag));     \
-        hipLaunchKernelGGL((k_agg_part_lds<KT_, AW_, KS_, X_>), dim3((u32)chunks), dim3(1024), lds_ag, ctx->stream, a->t, dp, (const KS_ *)key_col->data + row_begin, \
-                           rwords[0], rwords[1], (const u64 *)nullptr, 1u, (u32)chunks, n, pending, S, rk, cnt32, rows_per_chunk, (const u32 *)nullptr,  \
-                           (u32 *)nullptr, cond_ptr);                                                                                                 \
-    } while (0)
-#define RANGE_LAUNCH_KS(KT_, AW_, KS_) do { if ((AW_) < 8 && need_ext) RANGE_LAUNCH_X(KT_, AW_, KS_, true); else RANGE_LAUNCH_X(KT_, AW_, KS_, false); } while (0)
-#define RANGE_LAUNCH(KT_, AW_) RANGE_LAUNCH_KS(KT_, AW_, KT_)
-        if (key8)
-        {
-            if (aw == 8) RANGE_LAUNCH_KS(u32, 8, u8); else if (aw == 4) RANGE_LAUNCH_KS(u32, 4, u8); else if (aw == 2) RANGE_LAUNCH_KS(u32, 2, u8); else RANGE_LAUNCH_KS(u32, 1, u8);
-        }
-        else if (key16) // UInt16 (Date) / Int16 keys
-        {
-            if (aw == 8) RANGE_LAUNCH_KS(u32, 8, u16); else if (aw == 4) RANGE_LAUNCH_KS(u32, 4, u16); else if (aw == 2) RANGE_LAUNCH_KS(u32, 2, u16); else RANGE_LAUNCH_KS(u32, 1, u16);
-        }
-        else if (key32)
-        {
-            if (aw == 8) RANGE_LAUNCH(u32, 8); else if (aw == 4) RANGE_LAUNCH(u32, 4); else if (aw == 2) RANGE_LAUNCH(u32, 2); else RANGE_LAUNCH(u32, 1);
-        }
-        else
-        {
-            if (aw == 8) RANGE_LAUNCH(u64, 8); else if (aw == 4) RANGE_LAUNCH(u64, 4); else if (aw == 2) RANGE_LAUNCH(u64, 2); else RANGE_LAUNCH(u64, 1);
-        }
-#undef RANGE_LAUNCH
-#undef RANGE_LAUNCH_KS
-#undef RANGE_LAUNCH_X
+        int rc = CHGPU_OK;
+        // keys of 1, 2, 4 or 8 bytes as the column holds them (KS), hashed as 4- or 8-byte keys (KT); arguments of 8, 4, 2 or 1 bytes,
+        // sign- or float-extended where a narrow one needs it (EXT)
+        dispatch_width(key_w, [&](auto ks) {
+            using KS = decltype(ks);
+            using KT = std::conditional_t<sizeof(KS) == 8, u64, u32>;
+            dispatch_width(passes[p].aw, [&](auto at) {
+                constexpr int AW = (int)sizeof(at);
+                dispatch_const<0, 1>(AW < 8 && passes[p].ext ? 1 : 0, [&](auto x) { // (an 8-byte argument needs no extension)
+                    constexpr bool EXT = decltype(x)::value != 0;
+                    rc = launch_lds("ranged aggregation", k_agg_part_lds<KT, AW, KS, EXT>, dim3((u32)chunks), dim3(1024), lds_ag, ctx->stream, a->t, dp,
+                                    (const KS *)key_col->data + row_begin, rwords[0], rwords[1], (const u64 *)nullptr, 1u, (u32)chunks, n, pending, S, rk, cnt32, rows_per_chunk,
+                                    (const u32 *)nullptr, (u32 *)nullptr, cond_ptr);
+                });
+            });
+        });
         ctx->counters[6] += 1;
-        CHGPU_HIP(hipGetLastError());
+        CHGPU_TRY(rc);
         // rows this pass could not place (table at max fill) are retried with THIS pass's functions only
         CHGPU_TRY(agg_finish_rounds(a, dp, key_col->data, a->key_type, row_begin, n, pending));
     }
-    ctx->counters[5] += n;
+    return CHGPU_OK;
+}
+
+// The strategies that need no filtered copy of the block, chosen by promised / observed cardinality (see agg_add_block_impl).  The
+// caller counts the rows.
+static int agg_add_block_planned(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 n, const chgpu_col * filter,
+                                 u32 lds_cells)
+{
+    chgpu_ctx * ctx = a->ctx;
+    CHGPU_TRY(agg_fx_prepare_block(a, arg_cols, row_begin, n)); // (may widen the fixed-point window: before the descriptor is filled)
+    AggDesc d;
+    agg_fill_desc(a, arg_cols, &d);
+
+    const u64 n_words64 = (n + 63) / 64;
+    void * scratch = nullptr;
+    CHGPU_TRY(chgpu_scratch(ctx, n_words64 * sizeof(u64) + 256, &scratch));
+    u64 * pending = (u64 *)scratch;
+    const u32 rows_grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
+
+    // (min / max / any states go to the DIRECT kernel: the LDS-staged and partitioned plans carry additive words only)
+    if (!a->has_extremum && agg_partition_gate(a, (u64)lds_cells * 7 / 10, n))
+    {
+        const int rc = agg_add_block_by_partitions(a, key_col, arg_cols, row_begin, n);
+        if (rc != CHGPU_ERR_NOT_IMPLEMENTED)
+            return rc;
+    }
+    CHGPU_TRY(agg_ensure_table(a, a->size_hint));
+    // strategy: LDS-staged unless the caller promised a large cardinality (where nearly every key misses the LDS table)
+    const bool use_lds = !a->has_extremum && a->size_hint <= 65536; // beyond that nearly every key misses a workgroup's LDS table
+    // RANGE mode of the partition-aggregate kernel (agg_add_block_ranged)
+    const bool ranged = use_lds && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0); // keys of 1, 2, 4 or 8 bytes: every key type
+    if (ranged)
+        return agg_add_block_ranged(a, key_col, arg_cols, row_begin, n, filter, d, pending, n_words64, lds_cells);
+    if (chgpu_opt(ctx, "debug", 0))
+        fprintf(stderr, "chgpu: direct GROUP BY n=%llu hint=%llu kernel=%s%s\n", (unsigned long long)n, (unsigned long long)a->size_hint, use_lds ? "rows_lds" : "rows_direct",
+                a->has_extremum ? " states=extremum" : "");
+    if (use_lds)
+    {
+        // LDS cells per workgroup: the largest power of two with (1 + n_words) * 8 * (S+1) <= AGG_LDS_BYTES
+        u32 S = 4096;
+        while ((size_t)(S + 1) * 8 * (1 + a->n_words) > AGG_LDS_BYTES && S > 64)
+            S >>= 1;
+        // flushes may claim up to grid * (S+1) cells above max fill: keep that inside the slack (capacity/2)
+        u64 max_grid = (a->t.capacity / 2) / (S + 1);
+        const u32 lds_threads = (u32)chgpu_opt(ctx, "tune_agg_lds_threads", 512);
+        u32 grid = chgpu_grid_for(ctx, n, lds_threads, lds_threads >= 1024 ? 2 : 4);
+        if (grid > max_grid)
+            grid = (u32)(max_grid ? max_grid : 1);
+        const size_t lds = (size_t)(S + 1) * 8 * (1 + a->n_words);
+        hipLaunchKernelGGL(k_agg_rows_lds, dim3(grid), dim3(lds_threads), lds, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n, pending, S);
+    }
+    else
+    {
+        // one emplace + one atomic per state word and row
+        d.row_seq = a->any_seq - row_begin; // any(): row i of the columns is the (any_seq + i - row_begin)-th row of the aggregation
+        hipLaunchKernelGGL(k_agg_rows_direct<AGG_MODE_ALL>, dim3(rows_grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n, pending);
+    }
+    ctx->counters[6] += 1;
+    CHGPU_HIP(hipGetLastError());
+    CHGPU_TRY(agg_finish_rounds(a, d, key_col->data, a->key_type, row_begin, n, pending));
+    if (a->word_any)
+    {
+        hipLaunchKernelGGL(k_agg_any_resolve, dim3(rows_grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n);
+        ctx->counters[6] += 1;
+        CHGPU_HIP(hipGetLastError());
+        a->any_seq += n;
+    }
     return CHGPU_OK;
 }
 
@@ -3476,7 +3695,7 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
     // Callers that gave no size hint (the reference adapts too: consecutive-key cache hit rate, Aggregator.cpp:944-958;
     // two-level conversion, :83-89): the first 1 Mi rows go through the LDS-staged kernel and the number of groups they
     // produced is extrapolated to the whole input.
-    const u32 lds_cells = agg_part_max_cells(a->ctx, agg_part_cell_bytes(a, n, nullptr));
+    const u32 lds_cells = agg_part_max_cells(a->ctx, agg_part_cell_bytes(a, a->key_type, n, nullptr));
     const u64 lds_groups = (u64)lds_cells * 7 / 10;
     if (a->size_hint <= lds_groups && a->n_groups > lds_groups)
         a->size_hint = a->n_groups * 2; // the table already outgrew the LDS strategy
@@ -3496,8 +3715,7 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
     // a WHERE mask is fused only into the RANGE-mode kernel; every other strategy gets the filtered block materialised first
     if (filter)
     {
-        const bool partitioned = a->size_hint > lds_groups && n >= (4u << 20) && !chgpu_opt(ctx, "agg_no_partition", 0);
-        const bool will_range = !partitioned && a->size_hint <= 65536 && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0) && !a->has_extremum;
+        const bool will_range = !agg_partition_gate(a, lds_groups, n) && a->size_hint <= 65536 && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0) && !a->has_extremum;
         if (!will_range)
             return agg_add_block_materialised(a, key_col, arg_cols, row_begin, row_end, filter);
         // The aggregation kernel is issue-bound: it spends nearly the same time on a masked-out row as on a kept one, while
@@ -3517,153 +3735,9 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
                 return agg_add_block_materialised(a, key_col, arg_cols, row_begin, row_end, filter);
         }
     }
-    CHGPU_TRY(agg_fx_prepare_block(a, arg_cols, row_begin, n)); // (may widen the fixed-point window: before the descriptor is filled)
-    AggDesc d;
-    agg_fill_desc(a, arg_cols, &d);
-
-    const u64 n_words64 = (n + 63) / 64;
-    void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, n_words64 * sizeof(u64) + 256, &scratch));
-    u64 * pending = (u64 *)scratch;
-
-    if (a->has_extremum)
-    {
-        // min / max / any states: one emplace + one atomic per state word and row (the LDS-staged and partitioned plans carry additive words only)
-        if (chgpu_opt(ctx, "debug", 0))
-            fprintf(stderr, "chgpu: direct GROUP BY n=%llu hint=%llu kernel=rows_direct states=extremum\n", (unsigned long long)n, (unsigned long long)a->size_hint);
-        CHGPU_TRY(agg_ensure_table(a));
-        d.row_seq = a->any_seq - row_begin; // row i of the columns is the (any_seq + i - row_begin)-th row of the aggregation
-        hipLaunchKernelGGL(k_agg_rows_direct<AGG_MODE_ALL>, dim3(chgpu_grid_for(ctx, n, AGG_THREADS, 8)), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type,
-                           row_begin, n, pending);
-        ctx->counters[6] += 1;
-        ctx->counters[5] += n;
-        CHGPU_HIP(hipGetLastError());
-        CHGPU_TRY(agg_finish_rounds(a, d, key_col->data, a->key_type, row_begin, n, pending));
-        if (a->word_any)
-        {
-            hipLaunchKernelGGL(k_agg_any_resolve, dim3(chgpu_grid_for(ctx, n, AGG_THREADS, 8)), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n);
-            ctx->counters[6] += 1;
-            CHGPU_HIP(hipGetLastError());
-            a->any_seq += n;
-        }
-        return CHGPU_OK;
-    }
-
-    // PARTITIONED strategy: large promised cardinality and enough rows to amortise two extra passes
-    {
-        u32 n_argwords = 0;
-        for (u32 j = 0; j < a->n_aggs; ++j)
-            if (a->kinds[j] != CHGPU_AGG_COUNT)
-                ++n_argwords;
-        // Two or more argument words: ONE PASS PER WORD through the tile-sorted plan (each pass sorts {key, its word} and aggregates into
-        // cells that hold only its own state words; every count() rides in the first) -- 7 ms per word and 1e9 rows, against 22 ms for
-        // the two-word scatter plan, whose 4096-row tiles leave 8-row runs (tools/bench_two_words.py).  A shape the plan does not take
-        // answers NOT_IMPLEMENTED on its first pass, before anything was added: the older routes below take over.
-        if (n_argwords >= 2 && a->size_hint > lds_groups && n >= (4u << 20) && !chgpu_opt(ctx, "agg_no_partition", 0) && !chgpu_opt(ctx, "tune_gb_no_tiled", 0)
-            && !chgpu_opt(ctx, "tune_gb_no_word_passes", 0))
-        {
-            // every pass is asked first whether the plan takes it (nothing may be added before all of them are known to run)
-            int rc = CHGPU_OK;
-            for (int run = 0; run < 2 && rc == CHGPU_OK; ++run)
-            {
-                bool first = true;
-                for (u32 j = 0; j < a->n_aggs && rc == CHGPU_OK; ++j)
-                {
-                    if (a->kinds[j] == CHGPU_AGG_COUNT)
-                        continue;
-                    u32 mask = 1u << j;
-                    if (first)
-                        for (u32 c = 0; c < a->n_aggs; ++c)
-                            if (a->kinds[c] == CHGPU_AGG_COUNT)
-                                mask |= 1u << c;
-                    rc = agg_add_block_partitioned(a, key_col, arg_cols, row_begin, n, 1, 0, 0, mask, /*word_pass*/ run == 0 ? 2 : 1);
-                    if (run == 1 && rc == CHGPU_ERR_NOT_IMPLEMENTED) // (the probe said yes: not reached)
-                        rc = chgpu_set_error(CHGPU_ERR_LOGICAL, "a pass of a per-word GROUP BY was refused after its probe");
-                    if (run == 1 && !first && rc == CHGPU_OK)
-                        ctx->counters[5] -= n; // rows were counted once per pass
-                    first = false;
-                }
-            }
-            if (rc != CHGPU_ERR_NOT_IMPLEMENTED)
-                return rc;
-        }
-        if (a->size_hint > lds_groups && n >= (4u << 20) && n_argwords <= GBP_MAX_K && !chgpu_opt(ctx, "agg_no_partition", 0))
-        {
-            int rc = agg_add_block_partitioned(a, key_col, arg_cols, row_begin, n, n_argwords);
-            if (rc != CHGPU_ERR_NOT_IMPLEMENTED)
-                return rc;
-        }
-        else if (a->size_hint > lds_groups && n >= (4u << 20) && !chgpu_opt(ctx, "agg_no_partition", 0))
-        {
-            // more argument columns than a partition buffer row carries: several partitioned calls over the same rows, each with
-            // two of them (plus every count() in the first) -- ~12 ms per 1e9 rows and call, against one HBM atomic per row
-            // and state word on the DIRECT path
-            u32 masks[AGG_MAX_AGGS], ks[AGG_MAX_AGGS], n_calls = 0;
-            u32 cur = 0, cur_k = 0;
-            for (u32 j = 0; j < a->n_aggs; ++j)
-            {
-                if (a->kinds[j] == CHGPU_AGG_COUNT)
-                    continue;
-                cur |= 1u << j;
-                if (++cur_k == GBP_MAX_K)
-                {
-                    masks[n_calls] = cur, ks[n_calls] = cur_k, ++n_calls;
-                    cur = 0, cur_k = 0;
-                }
-            }
-            if (cur_k)
-                masks[n_calls] = cur, ks[n_calls] = cur_k, ++n_calls;
-            for (u32 j = 0; j < a->n_aggs; ++j)
-                if (a->kinds[j] == CHGPU_AGG_COUNT)
-                    masks[0] |= 1u << j;
-            int rc = CHGPU_OK;
-            for (u32 c = 0; c < n_calls && rc == CHGPU_OK; ++c)
-            {
-                rc = agg_add_block_partitioned(a, key_col, arg_cols, row_begin, n, ks[c], 0, 0, masks[c]);
-                if (rc == CHGPU_ERR_NOT_IMPLEMENTED && c == 0)
-                    break; // nothing applied yet: fall through to the other strategies
-            }
-            if (rc != CHGPU_ERR_NOT_IMPLEMENTED)
-            {
-                ctx->counters[5] -= (u64)(n_calls - 1) * n; // rows were counted once per call
-                return rc;
-            }
-        }
-    }
-    CHGPU_TRY(agg_ensure_table(a));
-    // strategy: LDS-staged unless the caller promised a large cardinality (where nearly every key misses the LDS table)
-    const bool use_lds = a->size_hint <= 65536; // beyond that nearly every key misses a workgroup's LDS table
-    // RANGE mode of the partition-aggregate kernel (agg_add_block_ranged)
-    const bool ranged = use_lds && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0); // keys of 1, 2, 4 or 8 bytes: every key type
-    if (ranged)
-        return agg_add_block_ranged(a, key_col, arg_cols, row_begin, n, filter, d, pending, n_words64, lds_cells);
-    if (chgpu_opt(ctx, "debug", 0))
-        fprintf(stderr, "chgpu: direct GROUP BY n=%llu hint=%llu kernel=%s\n", (unsigned long long)n, (unsigned long long)a->size_hint, use_lds ? "rows_lds" : "rows_direct");
-    if (use_lds)
-    {
-        // LDS cells per workgroup: the largest power of two with (1 + n_words) * 8 * (S+1) <= AGG_LDS_BYTES
-        u32 S = 4096;
-        while ((size_t)(S + 1) * 8 * (1 + a->n_words) > AGG_LDS_BYTES && S > 64)
-            S >>= 1;
-        // flushes may claim up to grid * (S+1) cells above max fill: keep that inside the slack (capacity/2)
-        u64 max_grid = (a->t.capacity / 2) / (S + 1);
-        const u32 lds_threads = (u32)chgpu_opt(ctx, "tune_agg_lds_threads", 512);
-        u32 grid = chgpu_grid_for(ctx, n, lds_threads, lds_threads >= 1024 ? 2 : 4);
-        if (grid > max_grid)
-            grid = (u32)(max_grid ? max_grid : 1);
-        const size_t lds = (size_t)(S + 1) * 8 * (1 + a->n_words);
-        hipLaunchKernelGGL(k_agg_rows_lds, dim3(grid), dim3(lds_threads), lds, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n, pending, S);
-    }
-    else
-    {
-        const u32 grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
-        hipLaunchKernelGGL(k_agg_rows_direct<AGG_MODE_ALL>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n, pending);
-    }
-    ctx->counters[6] += 1;
-    ctx->counters[5] += n;
-    CHGPU_HIP(hipGetLastError());
-
-    return agg_finish_rounds(a, d, key_col->data, a->key_type, row_begin, n, pending);
+    CHGPU_TRY(agg_add_block_planned(a, key_col, arg_cols, row_begin, n, filter, lds_cells));
+    ctx->counters[5] += n; // once per block, however many passes and calls the plan made over its rows
+    return CHGPU_OK;
 }
 
 // merge tuples (keys + state word columns) with overflow handling
@@ -3672,7 +3746,7 @@ static int agg_merge_tuples(chgpu_agg * a, const u64 * src_keys, const u64 * src
     chgpu_ctx * ctx = a->ctx;
     if (n == 0)
         return CHGPU_OK;
-    CHGPU_TRY(agg_ensure_table(a));
+    CHGPU_TRY(agg_ensure_table(a, a->size_hint));
     const u64 n_words64 = (n + 63) / 64;
     void * scratch = nullptr;
     CHGPU_TRY(chgpu_scratch(ctx, n_words64 * sizeof(u64) + 256, &scratch));

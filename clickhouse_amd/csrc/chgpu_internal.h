@@ -10,6 +10,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/chgpu.h"
@@ -178,6 +179,45 @@ size_t chgpu_scan_tmp_bytes(u64 n);
 // stable split of n_cols columns by sel[i] < num_shards (<= 256) into concatenated outputs (partition_kernels.hip); counts[num_shards] on the host
 int chgpu_partition_by_key_byte(chgpu_ctx * ctx, const chgpu_col * keys, u32 shift, u32 n_cols, const chgpu_col * const * cols, chgpu_col ** outs);
 int chgpu_partition_core(chgpu_ctx * ctx, const u32 * sel, u64 n, u32 num_shards, u32 n_cols, const chgpu_col * const * cols, chgpu_col ** outs, u64 * counts);
+
+// ---------------------------------------------------------------------------------------------
+// a run-time value as a template argument (host side): every helper calls `fn` with a tag for the value it was given
+// ---------------------------------------------------------------------------------------------
+// element width 8 / 4 / 2 / 1 bytes, for kernels that only move elements: fn(u64{} / u32{} / u16{} / u8{})
+template <typename F>
+static void dispatch_width(size_t bytes, F && fn)
+{
+    switch (bytes)
+    {
+        case 8: return fn(u64{});
+        case 4: return fn(u32{});
+        case 2: return fn(u16{});
+        default: return fn(u8{});
+    }
+}
+
+// v in [LO, HI] (a column count, a width mask): fn(std::integral_constant<int, v>{})
+template <int LO, int HI, typename F>
+static void dispatch_const(u32 v, F && fn)
+{
+    if constexpr (LO < HI)
+        if (v > (u32)LO)
+            return dispatch_const<LO + 1, HI>(v, fn);
+    fn(std::integral_constant<int, LO>{});
+}
+
+// v among CODES...: fn(std::integral_constant<u32, v>{}) and true; any other value: false, fn is not called.  Declared once as a type,
+// a list is both the test of what a kernel is instantiated for (has) and the switch that picks the instantiation (dispatch).
+template <u32... CODES>
+struct OneOf
+{
+    static bool has(u32 v) { return ((v == CODES) || ...); }
+    template <typename F>
+    static bool dispatch(u32 v, F && fn)
+    {
+        return ((v == CODES ? (fn(std::integral_constant<u32, CODES>{}), true) : false) || ...);
+    }
+};
 
 // ---------------------------------------------------------------------------------------------
 // device helpers

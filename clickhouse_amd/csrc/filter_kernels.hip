@@ -272,29 +272,6 @@ static int dispatch_int_type(int type, F && fn)
     }
 }
 
-// element width 8 / 4 / 2 / 1 bytes, for kernels that only move elements: fn(u64{} / u32{} / u16{} / u8{})
-template <typename F>
-static void dispatch_width(size_t bytes, F && fn)
-{
-    switch (bytes)
-    {
-        case 8: return fn(u64{});
-        case 4: return fn(u32{});
-        case 2: return fn(u16{});
-        default: return fn(u8{});
-    }
-}
-
-// v in [LO, HI] (a column count, a width mask): fn(std::integral_constant<int, v>{})
-template <int LO, int HI, typename F>
-static void dispatch_const(u32 v, F && fn)
-{
-    if constexpr (LO < HI)
-        if (v > (u32)LO)
-            return dispatch_const<LO + 1, HI>(v, fn);
-    fn(std::integral_constant<int, LO>{});
-}
-
 // (column type, folded comparison): fn(T{}, pred) -> int with IntRangePred over the eight integer types, or one of the six
 // F64Pred<op> over Float32 / Float64
 template <typename F>
