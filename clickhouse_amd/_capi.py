@@ -24,10 +24,22 @@ JOIN_INNER, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL = 0, 1, 2, 3
 STRICT_ANY, STRICT_ALL, STRICT_SEMI, STRICT_ANTI = 0, 1, 2, 3
 N_COUNTERS = 8
 VAL_COL, VAL_MUL, VAL_PLUS, VAL_MINUS = 0, 1, 2, 3
+STR_LIKE, STR_CONTAINS, STR_STARTS_WITH, STR_ENDS_WITH = 0, 1, 2, 3
+STR_ROUTE_EQUALS, STR_ROUTE_STARTS_WITH, STR_ROUTE_ENDS_WITH, STR_ROUTE_CONTAINS, STR_ROUTE_GENERAL = 0, 1, 2, 3, 4
+STR_CONST_MAX = 256   # bytes of a string constant / LIKE pattern the kernels carry
 
 _vp, _i, _u32, _u64, _i64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_int64
 _pp = C.POINTER(C.c_void_p)
 _pu64 = C.POINTER(C.c_uint64)
+
+
+
+class LikePlan(C.Structure):
+    """chgpu_like_plan: what a LIKE pattern compiles to (chgpu_like_compile)"""
+    _fields_ = [("route", C.c_int32), ("n_percent", C.c_uint32), ("n_underscore", C.c_uint32), ("literal_bytes", C.c_uint32),
+                ("n_tokens", C.c_uint32), ("token_meta", C.c_uint32 * (STR_CONST_MAX // 32)), ("literal", C.c_uint8 * STR_CONST_MAX),
+                ("tokens", C.c_uint8 * STR_CONST_MAX)]
+
 
 SIGNATURES = {
     "chgpu_abi_version": (_i, []),
@@ -90,6 +102,9 @@ SIGNATURES = {
     "chgpu_unpack_fixed_key": (_i, [_vp, _vp, _u32, _i, _pp]),
     "chgpu_string_dictionary_encode": (_i, [_vp, _vp, _vp, _pp, _pp, _pu64]),
     "chgpu_string_filter": (_i, [_vp, _vp, _vp, _vp, _pp, _pp, _pu64]),
+    "chgpu_string_cmp_const": (_i, [_vp, _vp, _vp, _i, C.c_char_p, _u64, _pp]),
+    "chgpu_string_match_const": (_i, [_vp, _vp, _vp, _i, C.c_char_p, _u64, _i, _pp]),
+    "chgpu_like_compile": (_i, [C.c_char_p, _u64, _vp]),
     "chgpu_lc_remap": (_i, [_vp, _vp, _vp, _pp]),
     "chgpu_agg_create": (_i, [_vp, _i, _u32, C.POINTER(_i), C.POINTER(_i), _u64, _pp]),
     "chgpu_agg_add_block": (_i, [_vp, _vp, _pp, _u64, _u64]),

@@ -409,3 +409,546 @@ extern "C" int chgpu_string_filter(chgpu_ctx * ctx, const chgpu_col * offsets_u6
     *rows_out = kept_rows;
     return CHGPU_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// String predicates against a constant: the WHERE clause over a ColumnString (FunctionsComparison.h StringComparisonImpl::
+// string_vector_constant; FunctionsStringSearch.h / MatchImpl.h for like, position, startsWith, endsWith).  (offsets, chars, constant) -> one
+// 0/1 byte per row.  The constant travels in the kernel argument (no device allocation, no upload) and is staged into LDS once per
+// workgroup, where every lane reads it at its own index.  Three kernels:
+//   k_str_row_const<MODE>   one lane per row: comparison, startsWith, endsWith.  8 bytes per step (str_load8), tail masked; at most
+//                           min(len, constant) bytes of the value matter.  Algorithmic bytes: 8 B offset + <= constant bytes + 1 B per row.
+//   k_str_contains_flat     substring search that never walks rows: the chars buffer is swept in tiles of SM_TILE bytes (one 16-byte load
+//                           per lane into LDS + a halo of needle - 1 bytes of the next tile); every lane tests its 16 start positions
+//                           (first byte in registers, the rest out of LDS).  A hit at byte p belongs to the first row r with offsets[r] > p
+//                           and counts when p + needle <= offsets[r] - 1.  k_str_tile_rows resolves the first row of every tile beforehand
+//                           (one binary search per TILE); the tile's own offsets are staged in LDS, so a hit costs an LDS search over the
+//                           tile's rows.  Result bytes are idempotent plain stores into a mask pre-filled with `negate`.
+//                           Algorithmic bytes: chars once + 1 B per row (+ 8 B per row of offsets, read tile-wise).
+//   k_str_like              any pattern with `_` or an inner `%`: one lane per row, the two-pointer wildcard match (the last `%` and the
+//                           haystack mark are remembered; a mismatch resumes after that `%` with the mark advanced by one byte).
+// ---------------------------------------------------------------------------------------------
+static constexpr u32 SM_MAX = CHGPU_STR_CONST_MAX; // bytes of a constant / tokens of a pattern a kernel argument carries
+static constexpr u32 SM_TILE = 4096;               // bytes of chars per workgroup step: 256 lanes x 16 B
+static constexpr u32 SM_ROWS_LDS = 1024;           // a tile with more rows than this searches its offsets in global memory
+enum { SM_CMP = 0, SM_STARTS = 1, SM_ENDS = 2 };
+
+struct StrConst
+{
+    u64 w[SM_MAX / 8];     // the bytes (little endian words), zero padded
+    u32 meta[SM_MAX / 32]; // k_str_like: bit i set = token i is a wildcard
+    u32 len;
+    u32 pad;
+};
+
+// kernel argument -> LDS with constant indices only (a lane-indexed read of the argument itself would go through scratch)
+__device__ __forceinline__ void str_stage_const(u64 * s_w, const StrConst & c)
+{
+    if (threadIdx.x == 0)
+    {
+#pragma unroll
+        for (u32 k = 0; k < SM_MAX / 8; ++k)
+            s_w[k] = c.w[k];
+    }
+}
+
+__device__ __forceinline__ u64 str_tail_mask(u64 bytes) // 1 <= bytes <= 7
+{
+    return ~0ull >> (8 * (8 - bytes));
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_str_row_const(const u64 * __restrict__ offsets, const u8 * __restrict__ chars, u64 n, const StrConst c, int op, u32 negate,
+                                                       u8 * __restrict__ out)
+{
+    __shared__ u64 s_w[SM_MAX / 8];
+    str_stage_const(s_w, c);
+    __syncthreads();
+    const u64 m = c.len;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
+    {
+        const u64 begin = i ? offsets[i - 1] : 0;
+        const u64 len = offsets[i] - begin - 1;
+        bool res;
+        if (MODE == SM_CMP)
+        {
+            // memcmpSmallAllowOverflow15: the common prefix as unsigned bytes, then the shorter one is smaller
+            const u64 k = len < m ? len : m;
+            const u8 * p = chars + begin;
+            int cmp = 0;
+            for (u64 j = 0; j < k; j += 8)
+            {
+                u64 a = str_load8(p + j), b = s_w[j >> 3];
+                if (k - j < 8)
+                {
+                    const u64 tm = str_tail_mask(k - j);
+                    a &= tm, b &= tm;
+                }
+                if (a != b)
+                {
+                    cmp = __builtin_bswap64(a) < __builtin_bswap64(b) ? -1 : 1; // the first byte is the most significant one
+                    break;
+                }
+            }
+            if (cmp == 0)
+                cmp = len < m ? -1 : len > m ? 1 : 0;
+            res = op == CHGPU_EQ ? cmp == 0 : op == CHGPU_NE ? cmp != 0 : op == CHGPU_LT ? cmp < 0 : op == CHGPU_GT ? cmp > 0 : op == CHGPU_LE ? cmp <= 0 : cmp >= 0;
+        }
+        else
+        {
+            res = len >= m;
+            if (res)
+            {
+                const u8 * p = chars + begin + (MODE == SM_ENDS ? len - m : 0);
+                for (u64 j = 0; j < m; j += 8)
+                {
+                    u64 x = str_load8(p + j) ^ s_w[j >> 3];
+                    if (m - j < 8)
+                        x &= str_tail_mask(m - j);
+                    if (x)
+                    {
+                        res = false;
+                        break;
+                    }
+                }
+            }
+            res = res != (negate != 0);
+        }
+        out[i] = res ? 1 : 0;
+    }
+}
+
+// `_`: one UTF-8 sequence.  The lead byte gives the length; every continuation byte must be 10xxxxxx and lie inside the value.  0 = no match here.
+__device__ __forceinline__ u32 str_utf8_step(const u8 * __restrict__ p, u64 avail)
+{
+    const u32 b = p[0];
+    const u32 l = b < 0x80 ? 1 : (b & 0xE0) == 0xC0 ? 2 : (b & 0xF0) == 0xE0 ? 3 : (b & 0xF8) == 0xF0 ? 4 : 0;
+    if (l == 0 || l > avail)
+        return 0;
+    for (u32 k = 1; k < l; ++k)
+        if ((p[k] & 0xC0) != 0x80)
+            return 0;
+    return l;
+}
+
+__global__ __launch_bounds__(256) void k_str_like(const u64 * __restrict__ offsets, const u8 * __restrict__ chars, u64 n, const StrConst c, u32 negate,
+                                                  u8 * __restrict__ out)
+{
+    __shared__ u64 s_w[SM_MAX / 8];
+    __shared__ u32 s_meta[SM_MAX / 32];
+    str_stage_const(s_w, c);
+    if (threadIdx.x == 0)
+    {
+#pragma unroll
+        for (u32 k = 0; k < SM_MAX / 32; ++k)
+            s_meta[k] = c.meta[k];
+    }
+    __syncthreads();
+    const u8 * s_tok = (const u8 *)s_w;
+    const u32 plen = c.len;
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
+    {
+        const u64 begin = i ? offsets[i - 1] : 0;
+        const u64 len = offsets[i] - begin - 1;
+        const u8 * s = chars + begin;
+        u64 h = 0, mark = 0;
+        u32 p = 0;
+        int star = -1;
+        bool res = false;
+        for (;;)
+        {
+            if (p < plen)
+            {
+                const u32 tok = s_tok[p];
+                const bool meta = (s_meta[p >> 5] >> (p & 31)) & 1;
+                if (meta && tok == '%')
+                {
+                    if (p + 1 == plen) // a trailing % takes whatever is left
+                    {
+                        res = true;
+                        break;
+                    }
+                    star = (int)p, mark = h, ++p;
+                    continue;
+                }
+                if (h >= len)
+                    break; // the value is used up and the pattern still needs a character: a later mark only leaves less
+                if (meta)
+                {
+                    const u32 step = str_utf8_step(s + h, len - h);
+                    if (step)
+                    {
+                        h += step, ++p;
+                        continue;
+                    }
+                }
+                else if (s[h] == tok)
+                {
+                    ++h, ++p;
+                    continue;
+                }
+            }
+            else if (h == len)
+            {
+                res = true;
+                break;
+            }
+            // mismatch: resume after the last %, which takes one byte more
+            if (star < 0 || ++mark > len)
+                break;
+            h = mark, p = (u32)star + 1;
+        }
+        out[i] = (res != (negate != 0)) ? 1 : 0;
+    }
+}
+
+// tile_row[t] = the first row r with offsets[r] > (first chars position of tile t), t = 0 .. ntiles (n when there is none).  Tiles are cut
+// on the 16-byte grid of the chars ADDRESS: tile t covers chars positions [t * SM_TILE - a0, (t + 1) * SM_TILE - a0), a0 = address & 15.
+__global__ __launch_bounds__(256) void k_str_tile_rows(const u64 * __restrict__ offsets, u64 n, u64 a0, u64 ntiles, u64 * __restrict__ tile_row)
+{
+    for (u64 t = (u64)blockIdx.x * 256 + threadIdx.x; t <= ntiles; t += (u64)gridDim.x * 256)
+    {
+        const u64 pos = t ? t * SM_TILE - a0 : 0;
+        u64 lo = 0, hi = n;
+        while (lo < hi)
+        {
+            const u64 mid = lo + ((hi - lo) >> 1);
+            if (offsets[mid] > pos)
+                hi = mid;
+            else
+                lo = mid + 1;
+        }
+        tile_row[t] = lo;
+    }
+}
+
+// 16 bytes at grid position q (a multiple of 16; `grid` is 16-byte aligned) of which only [a0, end) belong to chars: nothing outside is read
+__device__ __forceinline__ uint4 str_load_chunk(const u8 * __restrict__ grid, u64 q, u64 a0, u64 end)
+{
+    if (q >= a0 && q + 16 <= end)
+        return *(const uint4 *)(grid + q);
+    u64 lo = 0, hi = 0;
+    if (q + 16 > a0 && q < end)
+    {
+#pragma unroll
+        for (u32 k = 0; k < 16; ++k)
+            if (q + k >= a0 && q + k < end)
+            {
+                const u64 b = grid[q + k];
+                if (k < 8)
+                    lo |= b << (8 * k);
+                else
+                    hi |= b << (8 * (k - 8));
+            }
+    }
+    return make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32));
+}
+
+// bit k set = byte k of x is zero
+__device__ __forceinline__ u32 str_zero_bytes(u64 x)
+{
+    const u64 l = 0x7F7F7F7F7F7F7F7Full;
+    const u64 z = ~(((x & l) + l) | x | l); // 0x80 in every zero byte, exact
+    return (u32)(((z >> 7) * 0x0102040810204080ull) >> 56);
+}
+
+__global__ __launch_bounds__(256) void k_str_contains_flat(const u64 * __restrict__ offsets, const u8 * __restrict__ chars, u64 n, u64 size,
+                                                           const u64 * __restrict__ tile_row, u64 ntiles, const StrConst c, u8 hit_value, u8 * __restrict__ out)
+{
+    __shared__ uint4 s_tile4[(SM_TILE + SM_MAX + 16) / 16]; // the tile, the halo, 16 zero bytes for the last 8-byte read
+    __shared__ u64 s_w[SM_MAX / 8];
+    __shared__ u32 s_off[SM_ROWS_LDS];
+    str_stage_const(s_w, c);
+    const u32 m = c.len; // >= 1
+    const u32 tid = threadIdx.x;
+    const u64 a0 = (u64)chars & 15;
+    const u8 * grid = chars - a0;
+    const u64 end = a0 + size;
+    const u64 first = 0x0101010101010101ull * (c.w[0] & 0xFF);
+    const u64 * s_tile8 = (const u64 *)s_tile4;
+    for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x)
+    {
+        const u64 r_lo = tile_row[t];
+        if (r_lo >= n) // bytes after the last value
+            break;
+        const u64 r_next = tile_row[t + 1];
+        const u64 r_hi = r_next < n ? r_next : n - 1; // the last row a start position of this tile can belong to
+        const u64 cnt = r_hi - r_lo + 1;
+        const u64 q0 = t * SM_TILE;
+        const u64 pos0 = t ? q0 - a0 : 0;
+        __syncthreads(); // the previous tile's readers are done (and the staged constant is visible)
+        const uint4 v = str_load_chunk(grid, q0 + tid * 16, a0, end);
+        s_tile4[tid] = v;
+        if (tid <= SM_MAX / 16)
+            s_tile4[SM_TILE / 16 + tid] = tid * 16 + 1 < m ? str_load_chunk(grid, q0 + SM_TILE + tid * 16, a0, end) : make_uint4(0, 0, 0, 0);
+        const bool rows_in_lds = cnt <= SM_ROWS_LDS;
+        if (rows_in_lds)
+            for (u32 k = tid; k < cnt; k += 256)
+            {
+                const u64 d = offsets[r_lo + k] - pos0;
+                s_off[k] = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)d;
+            }
+        __syncthreads();
+        u32 cand = str_zero_bytes(((u64)v.x | ((u64)v.y << 32)) ^ first) | (str_zero_bytes(((u64)v.z | ((u64)v.w << 32)) ^ first) << 8);
+        while (cand)
+        {
+            const u32 j = __builtin_ctz(cand);
+            cand &= cand - 1;
+            const u32 o = tid * 16 + j;
+            if (q0 + o < a0)
+                continue; // in front of chars
+            bool eq = true;
+            for (u32 k = 0; k < m; k += 8)
+            {
+                const u32 oo = o + k, sh = (oo & 7) * 8;
+                const u64 lo = s_tile8[oo >> 3], hi = s_tile8[(oo >> 3) + 1];
+                u64 x = (sh ? (lo >> sh) | (hi << (64 - sh)) : lo) ^ s_w[k >> 3];
+                if (m - k < 8)
+                    x &= str_tail_mask(m - k);
+                if (x)
+                {
+                    eq = false;
+                    break;
+                }
+            }
+            if (!eq)
+                continue;
+            // the row of the hit: first row of this tile's rows whose end lies behind the hit
+            const u64 rel = q0 + o - a0 - pos0; // < SM_TILE
+            u64 lo = 0, hi = cnt;
+            u64 row_end_rel = 0;
+            if (rows_in_lds)
+            {
+                while (lo < hi)
+                {
+                    const u64 mid = (lo + hi) >> 1;
+                    if (s_off[mid] > rel)
+                        hi = mid;
+                    else
+                        lo = mid + 1;
+                }
+                if (lo < cnt)
+                    row_end_rel = s_off[lo]; // saturated at 2^32 - 1: such a row ends far behind the hit
+            }
+            else
+            {
+                while (lo < hi)
+                {
+                    const u64 mid = (lo + hi) >> 1;
+                    if (offsets[r_lo + mid] - pos0 > rel)
+                        hi = mid;
+                    else
+                        lo = mid + 1;
+                }
+                if (lo < cnt)
+                    row_end_rel = offsets[r_lo + lo] - pos0;
+            }
+            if (lo < cnt && rel + m + 1 <= row_end_rel) // wholly inside the value: not its terminating zero, not the next row
+                out[r_lo + lo] = hit_value;
+        }
+    }
+}
+
+extern "C" int chgpu_like_compile(const void * pattern, uint64_t pattern_bytes, chgpu_like_plan * out)
+{
+    CHGPU_REQUIRE(out && (pattern || !pattern_bytes), CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    memset(out, 0, sizeof(*out));
+    CHGPU_REQUIRE(pattern_bytes <= CHGPU_STR_CONST_MAX, CHGPU_ERR_NOT_IMPLEMENTED, "a LIKE pattern of %llu bytes (the kernels carry %d): CPU path",
+                  (unsigned long long)pattern_bytes, CHGPU_STR_CONST_MAX);
+    const u8 * p = (const u8 *)pattern;
+    u32 nt = 0;
+    auto push = [&](u8 byte, bool meta) {
+        out->tokens[nt] = byte;
+        if (meta)
+            out->token_meta[nt >> 5] |= 1u << (nt & 31);
+        ++nt;
+    };
+    auto is_meta = [&](u32 k) { return (out->token_meta[k >> 5] >> (k & 31)) & 1u; };
+    for (u64 i = 0; i < pattern_bytes; ++i)
+    {
+        const u8 ch = p[i];
+        if (ch == '\\')
+        {
+            // likePatternToRegexp: a pattern may not end in a lone backslash (CANNOT_PARSE_ESCAPE_SEQUENCE)
+            CHGPU_REQUIRE(i + 1 < pattern_bytes, CHGPU_ERR_BAD_ARGUMENTS, "LIKE pattern ends in a lone backslash (an escape sequence is expected after it)");
+            const u8 d = p[i + 1];
+            if (d == '%' || d == '_' || d == '\\')
+                push(d, false), ++i;
+            else
+                push('\\', false); // a literal backslash; the next byte is read as usual
+        }
+        else if (ch == '%')
+        {
+            ++out->n_percent;
+            if (!(nt && is_meta(nt - 1) && out->tokens[nt - 1] == '%'))
+                push('%', true);
+        }
+        else if (ch == '_')
+            ++out->n_underscore, push('_', true);
+        else
+            push(ch, false);
+    }
+    out->n_tokens = nt;
+    const bool lead = nt && is_meta(0) && out->tokens[0] == '%';
+    u32 b = lead ? 1 : 0, e = nt;
+    const bool trail = e > b && is_meta(e - 1) && out->tokens[e - 1] == '%';
+    if (trail)
+        --e;
+    for (u32 k = b; k < e; ++k)
+        if (is_meta(k))
+        {
+            out->route = CHGPU_STR_ROUTE_GENERAL;
+            return CHGPU_OK;
+        }
+    out->literal_bytes = e - b;
+    memcpy(out->literal, out->tokens + b, e - b);
+    if (b == e && (lead || trail))
+        out->route = CHGPU_STR_ROUTE_CONTAINS; // `%`, `%%`: contains the empty string
+    else
+        out->route = lead && trail ? CHGPU_STR_ROUTE_CONTAINS : lead ? CHGPU_STR_ROUTE_ENDS_WITH : trail ? CHGPU_STR_ROUTE_STARTS_WITH : CHGPU_STR_ROUTE_EQUALS;
+    return CHGPU_OK;
+}
+
+static StrConst str_const_of(const void * bytes, u64 n)
+{
+    StrConst c;
+    memset(&c, 0, sizeof(c));
+    if (n)
+        memcpy(c.w, bytes, n);
+    c.len = (u32)n;
+    return c;
+}
+
+// the arguments every predicate shares; *out receives an empty UInt8 column when there are no rows
+static int str_predicate_begin(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const void * constant, u64 constant_bytes,
+                               chgpu_col ** out_u8)
+{
+    CHGPU_REQUIRE(ctx && offsets_u64 && chars_u8 && out_u8 && (constant || !constant_bytes), CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_REQUIRE(offsets_u64->type == CHGPU_U64 && chars_u8->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "ColumnString = UInt64 offsets + UInt8 chars");
+    CHGPU_REQUIRE(constant_bytes <= CHGPU_STR_CONST_MAX, CHGPU_ERR_NOT_IMPLEMENTED, "a string constant of %llu bytes (the kernels carry %d): CPU path",
+                  (unsigned long long)constant_bytes, CHGPU_STR_CONST_MAX);
+    return CHGPU_OK;
+}
+
+static int str_launch_row(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int mode, int op, const StrConst & c, int negate, chgpu_col * out)
+{
+    const u64 n = offsets_u64->rows;
+    const dim3 grid(chgpu_grid_for(ctx, n, 256, 8)), block(256);
+    const u64 * offs = (const u64 *)offsets_u64->data;
+    const u8 * chars = (const u8 *)chars_u8->data;
+    if (mode == SM_CMP)
+        hipLaunchKernelGGL(k_str_row_const<SM_CMP>, grid, block, 0, ctx->stream, offs, chars, n, c, op, 0u, (u8 *)out->data);
+    else if (mode == SM_STARTS)
+        hipLaunchKernelGGL(k_str_row_const<SM_STARTS>, grid, block, 0, ctx->stream, offs, chars, n, c, 0, (u32)(negate != 0), (u8 *)out->data);
+    else
+        hipLaunchKernelGGL(k_str_row_const<SM_ENDS>, grid, block, 0, ctx->stream, offs, chars, n, c, 0, (u32)(negate != 0), (u8 *)out->data);
+    ctx->counters[6] += 1;
+    return CHGPU_OK;
+}
+
+static int str_launch_contains(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const StrConst & c, int negate, chgpu_col * out)
+{
+    const u64 n = offsets_u64->rows, size = chars_u8->rows;
+    CHGPU_HIP(hipMemsetAsync(out->data, (negate != 0) != (c.len == 0) ? 1 : 0, n, ctx->stream));
+    if (c.len == 0) // the empty needle is found in every row
+        return CHGPU_OK;
+    const u64 a0 = (u64)(uintptr_t)chars_u8->data & 15;
+    const u64 ntiles = (a0 + size + SM_TILE - 1) / SM_TILE;
+    void * tile_row = nullptr;
+    CHGPU_TRY(chgpu_scratch(ctx, (ntiles + 1) * sizeof(u64), &tile_row));
+    hipLaunchKernelGGL(k_str_tile_rows, dim3(chgpu_grid_for(ctx, ntiles + 1, 256, 8)), dim3(256), 0, ctx->stream, (const u64 *)offsets_u64->data, n, a0, ntiles,
+                       (u64 *)tile_row);
+    hipLaunchKernelGGL(k_str_contains_flat, dim3(chgpu_grid_for(ctx, ntiles * 256, 256, 8)), dim3(256), 0, ctx->stream, (const u64 *)offsets_u64->data,
+                       (const u8 *)chars_u8->data, n, size, (const u64 *)tile_row, ntiles, c, (u8)(negate ? 0 : 1), (u8 *)out->data);
+    ctx->counters[6] += 2;
+    return CHGPU_OK;
+}
+
+static int str_launch_like(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const StrConst & c, int negate, chgpu_col * out)
+{
+    const u64 n = offsets_u64->rows;
+    hipLaunchKernelGGL(k_str_like, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const u64 *)offsets_u64->data, (const u8 *)chars_u8->data, n, c,
+                       (u32)(negate != 0), (u8 *)out->data);
+    ctx->counters[6] += 1;
+    return CHGPU_OK;
+}
+
+static int str_predicate_end(int rc, chgpu_col * out, chgpu_col ** out_u8)
+{
+    if (rc == CHGPU_OK && hipGetLastError() != hipSuccess)
+        rc = chgpu_set_error(CHGPU_ERR_DEVICE, "string predicate kernels failed to launch");
+    if (rc != CHGPU_OK)
+    {
+        chgpu_col_free(out);
+        return rc;
+    }
+    *out_u8 = out;
+    return CHGPU_OK;
+}
+
+extern "C" int chgpu_string_cmp_const(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int op, const void * value, uint64_t value_bytes,
+                                      chgpu_col ** out_u8)
+{
+    ChgpuDeviceGuard _dev_guard(ctx);
+    CHGPU_TRY(str_predicate_begin(ctx, offsets_u64, chars_u8, value, value_bytes, out_u8));
+    CHGPU_REQUIRE(op >= CHGPU_EQ && op <= CHGPU_GE, CHGPU_ERR_BAD_ARGUMENTS, "unknown comparison %d", op);
+    CHGPU_TRY(str_validate_offsets(ctx, offsets_u64, chars_u8));
+    chgpu_col * out = nullptr;
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, offsets_u64->rows, &out));
+    if (!offsets_u64->rows)
+        return str_predicate_end(CHGPU_OK, out, out_u8);
+    return str_predicate_end(str_launch_row(ctx, offsets_u64, chars_u8, SM_CMP, op, str_const_of(value, value_bytes), 0, out), out, out_u8);
+}
+
+extern "C" int chgpu_string_match_const(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int kind, const void * pattern,
+                                        uint64_t pattern_bytes, int negate, chgpu_col ** out_u8)
+{
+    ChgpuDeviceGuard _dev_guard(ctx);
+    CHGPU_TRY(str_predicate_begin(ctx, offsets_u64, chars_u8, pattern, pattern_bytes, out_u8));
+    CHGPU_REQUIRE(kind >= CHGPU_STR_LIKE && kind <= CHGPU_STR_ENDS_WITH, CHGPU_ERR_BAD_ARGUMENTS, "unknown string predicate %d", kind);
+    // every kind is a route of the LIKE plan; a needle is its own literal
+    chgpu_like_plan plan;
+    if (kind == CHGPU_STR_LIKE)
+        CHGPU_TRY(chgpu_like_compile(pattern, pattern_bytes, &plan));
+    else
+    {
+        memset(&plan, 0, sizeof(plan));
+        plan.route = kind == CHGPU_STR_CONTAINS ? CHGPU_STR_ROUTE_CONTAINS : kind == CHGPU_STR_STARTS_WITH ? CHGPU_STR_ROUTE_STARTS_WITH : CHGPU_STR_ROUTE_ENDS_WITH;
+        plan.literal_bytes = (u32)pattern_bytes;
+        if (pattern_bytes)
+            memcpy(plan.literal, pattern, pattern_bytes);
+    }
+    // developer option: a contains goes down the general matcher as %needle% (the measurement the router's choice rests on)
+    if (plan.route == CHGPU_STR_ROUTE_CONTAINS && plan.literal_bytes && plan.literal_bytes + 2 <= CHGPU_STR_CONST_MAX && chgpu_opt(ctx, "tune_str_contains_general", 0))
+    {
+        memset(plan.token_meta, 0, sizeof(plan.token_meta));
+        plan.n_tokens = plan.literal_bytes + 2;
+        plan.tokens[0] = plan.tokens[plan.n_tokens - 1] = '%';
+        memcpy(plan.tokens + 1, plan.literal, plan.literal_bytes);
+        plan.token_meta[0] |= 1u;
+        plan.token_meta[(plan.n_tokens - 1) >> 5] |= 1u << ((plan.n_tokens - 1) & 31);
+        plan.route = CHGPU_STR_ROUTE_GENERAL;
+    }
+    CHGPU_TRY(str_validate_offsets(ctx, offsets_u64, chars_u8));
+    chgpu_col * out = nullptr;
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, offsets_u64->rows, &out));
+    if (!offsets_u64->rows)
+        return str_predicate_end(CHGPU_OK, out, out_u8);
+    int rc = CHGPU_OK;
+    if (plan.route == CHGPU_STR_ROUTE_GENERAL)
+    {
+        StrConst c = str_const_of(plan.tokens, plan.n_tokens);
+        memcpy(c.meta, plan.token_meta, sizeof(c.meta));
+        rc = str_launch_like(ctx, offsets_u64, chars_u8, c, negate, out);
+    }
+    else
+    {
+        const StrConst c = str_const_of(plan.literal, plan.literal_bytes);
+        if (plan.route == CHGPU_STR_ROUTE_CONTAINS)
+            rc = str_launch_contains(ctx, offsets_u64, chars_u8, c, negate, out);
+        else if (plan.route == CHGPU_STR_ROUTE_EQUALS)
+            rc = str_launch_row(ctx, offsets_u64, chars_u8, SM_CMP, negate ? CHGPU_NE : CHGPU_EQ, c, 0, out);
+        else
+            rc = str_launch_row(ctx, offsets_u64, chars_u8, plan.route == CHGPU_STR_ROUTE_STARTS_WITH ? SM_STARTS : SM_ENDS, 0, c, negate, out);
+    }
+    return str_predicate_end(rc, out, out_u8);
+}

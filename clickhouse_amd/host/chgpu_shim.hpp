@@ -37,6 +37,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <string_view>
 #include <type_traits>
 #include <unordered_map>
 #include <array>
@@ -792,6 +793,29 @@ struct ColumnString
         for (uint64_t r : first_rows)
             dict->push_back(value_of(r));
         return ColumnLowCardinality{dict, std::make_shared<ColumnVector>(offsets->context(), ids)};
+    }
+
+    /// Predicates against a constant String (binary-safe std::string_view): a UInt8 column of 0/1 per row, i.e. the filter column a
+    /// GpuFilterTransform takes.  compare: equals .. greaterOrEquals (CHGPU_EQ .. CHGPU_GE; FunctionsComparison.h, StringComparisonImpl::
+    /// string_vector_constant); like / contains / startsWith / endsWith: MatchImpl, position() != 0, FunctionStartsEndsWith.  A constant
+    /// longer than CHGPU_STR_CONST_MAX throws NOT_IMPLEMENTED: the caller keeps its CPU function.
+    ColumnPtr compare(int op, std::string_view value) const
+    {
+        chgpu_col * out = nullptr;
+        check(chgpu_string_cmp_const(offsets->context()->get(), offsets->handle(), chars->handle(), op, value.data(), value.size(), &out));
+        return std::make_shared<ColumnVector>(offsets->context(), out);
+    }
+    ColumnPtr like(std::string_view pattern, bool negate = false) const { return match(CHGPU_STR_LIKE, pattern, negate); }
+    ColumnPtr contains(std::string_view needle, bool negate = false) const { return match(CHGPU_STR_CONTAINS, needle, negate); }
+    ColumnPtr startsWith(std::string_view needle, bool negate = false) const { return match(CHGPU_STR_STARTS_WITH, needle, negate); }
+    ColumnPtr endsWith(std::string_view needle, bool negate = false) const { return match(CHGPU_STR_ENDS_WITH, needle, negate); }
+
+private:
+    ColumnPtr match(int kind, std::string_view pattern, bool negate) const
+    {
+        chgpu_col * out = nullptr;
+        check(chgpu_string_match_const(offsets->context()->get(), offsets->handle(), chars->handle(), kind, pattern.data(), pattern.size(), negate ? 1 : 0, &out));
+        return std::make_shared<ColumnVector>(offsets->context(), out);
     }
 };
 

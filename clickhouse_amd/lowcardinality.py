@@ -57,6 +57,22 @@ class ColumnLowCardinality:
         return [self.dictionary[int(i)] for i in idx]
 
 
+def _const_bytes(value) -> bytes:
+    """a constant String argument: str is encoded as UTF-8, bytes-likes are taken as they are (binary-safe)"""
+    return value.encode("utf-8") if isinstance(value, str) else bytes(value)
+
+
+def like_compile(pattern) -> dict:
+    """chgpu_like_compile: what a LIKE pattern compiles to (host only, no context): route (STR_ROUTE_*), the unescaped literal of the
+    four literal routes, the number of % and _ tokens, and the token string the general matcher walks."""
+    pattern = _const_bytes(pattern)
+    plan = K.LikePlan()
+    K.check(K.lib().chgpu_like_compile(pattern, len(pattern), C.byref(plan)))
+    meta = [bool((plan.token_meta[i >> 5] >> (i & 31)) & 1) for i in range(plan.n_tokens)]
+    return {"route": int(plan.route), "literal": bytes(plan.literal[:plan.literal_bytes]), "n_percent": int(plan.n_percent),
+            "n_underscore": int(plan.n_underscore), "tokens": bytes(plan.tokens[:plan.n_tokens]), "token_is_meta": meta}
+
+
 class ColumnString:
     """ColumnString (src/Columns/ColumnString.h:40-49) in HBM: chars (every value followed by a zero byte) + cumulative offsets."""
 
@@ -99,6 +115,37 @@ class ColumnString:
         ctx = self.offsets.ctx
         K.check(K.lib().chgpu_string_filter(ctx._h, self.offsets._h, self.chars._h, filt._h, C.byref(oo), C.byref(oc), C.byref(rows)))
         return ColumnString(Column(ctx, oo), Column(ctx, oc))
+
+    # -- predicates against a constant: a UInt8 Column of 0/1, one per row (the mask filter / and_ / execute_on_block(filter=) take) --
+    def compare(self, op: int, value) -> Column:
+        """equals .. greaterOrEquals (EQ .. GE) against a constant String: unsigned bytes, then the shorter one is the smaller
+        (FunctionsComparison.h, StringComparisonImpl::string_vector_constant)"""
+        value = _const_bytes(value)
+        h = C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(K.lib().chgpu_string_cmp_const(ctx._h, self.offsets._h, self.chars._h, int(op), value, len(value), C.byref(h)))
+        return Column(ctx, h)
+
+    def _match(self, kind: int, pattern, negate: bool) -> Column:
+        pattern = _const_bytes(pattern)
+        h = C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(K.lib().chgpu_string_match_const(ctx._h, self.offsets._h, self.chars._h, kind, pattern, len(pattern), 1 if negate else 0, C.byref(h)))
+        return Column(ctx, h)
+
+    def like(self, pattern, negate: bool = False) -> Column:
+        """like / notLike (MatchImpl): % any run of bytes, _ one UTF-8 character, \\% \\_ \\\\ the literal bytes"""
+        return self._match(K.STR_LIKE, pattern, negate)
+
+    def contains(self, needle, negate: bool = False) -> Column:
+        """position(haystack, needle) != 0; the empty needle matches every row"""
+        return self._match(K.STR_CONTAINS, needle, negate)
+
+    def starts_with(self, needle, negate: bool = False) -> Column:
+        return self._match(K.STR_STARTS_WITH, needle, negate)
+
+    def ends_with(self, needle, negate: bool = False) -> Column:
+        return self._match(K.STR_ENDS_WITH, needle, negate)
 
     def to_list(self) -> list:
         """the values on the host (tests)"""

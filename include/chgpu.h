@@ -476,6 +476,48 @@ int chgpu_string_dictionary_encode(chgpu_ctx * ctx, const chgpu_col * offsets_u6
    whose filter byte is non-zero, in order, as a new ColumnString (offsets rebuilt, bytes moved together). */
 int chgpu_string_filter(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const chgpu_col * filter_u8,
                         chgpu_col ** out_offsets_u64, chgpu_col ** out_chars_u8, uint64_t * rows_out);
+/* ---- String predicates against a constant: a WHERE clause over a ColumnString -> a UInt8 column of 0/1, one byte per row (the mask
+   chgpu_filter* / chgpu_and / chgpu_agg_add_block_filtered / chgpu_string_filter take).  Values, constants and patterns are binary-safe
+   (zero bytes, bytes >= 0x80); `value` / `pattern` are host memory, no terminator, at most CHGPU_STR_CONST_MAX bytes -- a longer one
+   answers CHGPU_ERR_NOT_IMPLEMENTED (the caller keeps its CPU function).  Offsets that break the ColumnString invariant answer
+   CHGPU_ERR_BAD_ARGUMENTS; no rows give an empty column.  The kernels read values 8 bytes at a time (chars needs the same 8 readable
+   bytes after its end as for chgpu_string_dictionary_encode).
+   chgpu_string_cmp_const: equals .. greaterOrEquals (CHGPU_EQ .. CHGPU_GE) of FunctionsComparison.h, StringComparisonImpl::
+     string_vector_constant -> memcmpSmallAllowOverflow15: the first min(len_a, len_b) bytes compared as UNSIGNED bytes, then the shorter
+     string is the smaller one; lengths exclude the terminating zero.
+   chgpu_string_match_const: kind CHGPU_STR_LIKE is like / notLike (MatchImpl over likePatternToRegexp: `%` any run of bytes, `_` exactly one
+     character -- one UTF-8 sequence of 1-4 bytes by its lead byte, every continuation byte 10xxxxxx and inside the value, else no match at
+     that position; newline is a character like any other; `\%` `\_` `\\` are the literal bytes, a backslash before any other byte is a literal
+     backslash, a pattern ending in a lone backslash is CHGPU_ERR_BAD_ARGUMENTS); CHGPU_STR_CONTAINS is position(haystack, needle) != 0 (an
+     occurrence lies wholly inside one value: it never touches the terminating zero or the next row); CHGPU_STR_STARTS_WITH /
+     CHGPU_STR_ENDS_WITH are startsWith / endsWith.  The empty needle matches every row.  negate != 0 inverts the result (notLike, NOT ...). */
+#define CHGPU_STR_CONST_MAX 256
+enum { CHGPU_STR_LIKE = 0, CHGPU_STR_CONTAINS = 1, CHGPU_STR_STARTS_WITH = 2, CHGPU_STR_ENDS_WITH = 3 };
+int chgpu_string_cmp_const(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int op,
+                           const void * value, uint64_t value_bytes, chgpu_col ** out_u8);
+int chgpu_string_match_const(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int kind,
+                             const void * pattern, uint64_t pattern_bytes, int negate, chgpu_col ** out_u8);
+/* What a LIKE pattern compiles to; host only, needs no context (both calls above choose their kernel by it).  A pattern whose only
+   unescaped `%` stand at its ends and that has no unescaped `_` is one of the four literal routes -- `abc` equals, `abc%` startsWith,
+   `%abc` endsWith, `%abc%` contains, `%` / `%%` contains the empty string (always true) -- with literal[literal_bytes] the unescaped bytes;
+   anything else is CHGPU_STR_ROUTE_GENERAL.  tokens[n_tokens] is the pattern as the general matcher walks it, for every route: unescaped
+   bytes, runs of `%` collapsed into one; bit (i & 31) of token_meta[i >> 5] says token i is a wildcard (`%` or `_`) and not a literal.
+   n_percent / n_underscore count the unescaped `%` / `_` of the pattern as written.  A trailing lone backslash answers
+   CHGPU_ERR_BAD_ARGUMENTS, more than CHGPU_STR_CONST_MAX pattern bytes CHGPU_ERR_NOT_IMPLEMENTED. */
+enum { CHGPU_STR_ROUTE_EQUALS = 0, CHGPU_STR_ROUTE_STARTS_WITH = 1, CHGPU_STR_ROUTE_ENDS_WITH = 2, CHGPU_STR_ROUTE_CONTAINS = 3,
+       CHGPU_STR_ROUTE_GENERAL = 4 };
+typedef struct chgpu_like_plan
+{
+    int32_t route;          /* CHGPU_STR_ROUTE_* */
+    uint32_t n_percent;
+    uint32_t n_underscore;
+    uint32_t literal_bytes; /* 0 for the general route */
+    uint32_t n_tokens;
+    uint32_t token_meta[CHGPU_STR_CONST_MAX / 32];
+    uint8_t literal[CHGPU_STR_CONST_MAX];
+    uint8_t tokens[CHGPU_STR_CONST_MAX];
+} chgpu_like_plan;
+int chgpu_like_compile(const void * pattern, uint64_t pattern_bytes, chgpu_like_plan * out);
 int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, const int * agg_kinds, const int * arg_types,
                      uint64_t size_hint, chgpu_agg ** out);
 /* executeOnBlock over rows [row_begin,row_end) of the key column and the argument columns (arg_cols[j] may be NULL
