@@ -1,4 +1,4 @@
-"""Key sets with a chosen placement for the hash-placed GROUP BY and join plans.
+"""Key sets with a chosen placement for the hash-placed GROUP BY and join plans, the wide-key dictionary and the String dictionary.
 
 Every placement function below copies one in the HIP sources, and each is a bijection of the key (xorshift-33 is its own inverse on
 64 bits, the multipliers are odd), so a key with a chosen home slot, slice, partition or LDS cell is made by inverting it rather than
@@ -338,3 +338,100 @@ def keydict_tag_with_home(rng, cell_bits, lg, n=1):
         t = t[t < np.uint64(1 << 63)]
         got = np.unique(np.concatenate([got, (t << np.uint64(1)) | np.uint64(1)]))
     return rng.permutation(got)[:n]
+
+
+# ---- the string dictionary (chgpu_string_dictionary_encode) -----------------------------------------------------------------------
+# str_hash_bytes: string_kernels.hip:27-44 (the seed and the length multiplier :29, the word multiplier and the xorshift :33-34 and
+# :39-40, intHash64 :42, the low bit forced to 1 :43); the home cell: string_kernels.hip:107 and :142; the table size: :207-209.
+# Plain Python ints over bytes: the strings are few and short.
+STR_SEED = 0x9E3779B97F4A7C15
+STR_LEN_MUL = 0xFF51AFD7ED558CCD
+STR_WORD_MUL = 0xC4CEB9FE1A85EC53
+STR_SHIFT = 29
+STR_CAP_MIN = 1024
+STR_CELLS_PER_ROW = 2
+
+
+def _int_hash64_py(x):
+    x ^= x >> 33
+    x = (x * INTHASH_MUL1) & M64
+    x ^= x >> 33
+    x = (x * INTHASH_MUL2) & M64
+    return x ^ (x >> 33)
+
+
+def _int_hash64_inv_py(h):
+    x = ((h ^ (h >> 33)) * inv_odd(INTHASH_MUL2)) & M64
+    x = ((x ^ (x >> 33)) * inv_odd(INTHASH_MUL1)) & M64
+    return x ^ (x >> 33)
+
+
+def _str_mix(h, word):
+    h = ((h ^ word) * STR_WORD_MUL) & M64
+    return h ^ (h >> STR_SHIFT)
+
+
+def _str_running(data):
+    """str_hash_bytes' running value after every byte of `data`, before intHash64"""
+    n = len(data)
+    h = STR_SEED ^ ((n * STR_LEN_MUL) & M64)
+    full = n - n % 8
+    for i in range(0, full, 8):
+        h = _str_mix(h, int.from_bytes(data[i:i + 8], "little"))
+    if n % 8:
+        h = _str_mix(h, int.from_bytes(data[full:], "little"))       # the tail, zero extended: the kernel masks its 8-byte load
+    return h
+
+
+def str_raw_hash(data):
+    """str_hash_bytes before its last line: the value whose bit 0 the tag overwrites"""
+    return _int_hash64_py(_str_running(bytes(data)))
+
+
+def str_hash(data):
+    """str_hash_bytes: the 64-bit tag of a value (without its terminating zero); never 0"""
+    return str_raw_hash(data) | 1
+
+
+def str_table_cap(rows):
+    """cells of the table chgpu_string_dictionary_encode builds for a column of `rows` rows"""
+    cap = STR_CAP_MIN
+    while cap < STR_CELLS_PER_ROW * rows:
+        cap <<= 1
+    return cap
+
+
+def str_home(tag, cap):
+    """the home cell of a tag in a table of `cap` cells"""
+    return (tag >> 1) & (cap - 1)
+
+
+def str_with_raw_hash(raw, prefix=b""):
+    """prefix + 8 bytes whose raw hash is exactly `raw`: every step of str_hash_bytes is a bijection of the last full word (xor, an odd
+    multiplier, the xorshift, intHash64), so they are undone from the end.  The 8 bytes may hold zeros: ColumnString is binary-safe."""
+    prefix = bytes(prefix)
+    assert len(prefix) % 8 == 0 and 0 <= raw <= M64
+    n = len(prefix) + 8
+    h = STR_SEED ^ ((n * STR_LEN_MUL) & M64)
+    for i in range(0, len(prefix), 8):
+        h = _str_mix(h, int.from_bytes(prefix[i:i + 8], "little"))
+    y = _int_hash64_inv_py(raw)
+    y = y ^ (y >> STR_SHIFT) ^ (y >> (2 * STR_SHIFT))                # undoes x ^= x >> 29 (3 * 29 > 64)
+    word = ((y * inv_odd(STR_WORD_MUL)) & M64) ^ h
+    return prefix + word.to_bytes(8, "little")
+
+
+def str_with_home(cell, cap, salt, prefix=b""):
+    """a string homed at `cell` of a table of `cap` cells; distinct salts (below 2^63 / cap) give distinct tags, hence distinct
+    strings.  The salt fills the tag's bits above the home cell's: salts 1 << k are tags that differ in one high bit only."""
+    lg = cap.bit_length() - 1
+    assert cap == 1 << lg and 0 <= cell < cap and 0 <= salt < (1 << (63 - lg))
+    return str_with_raw_hash((salt << (lg + 1)) | (cell << 1) | 1, prefix)
+
+
+def str_tag_twins(tag, prefix_a=b"", prefix_b=b""):
+    """two different strings with one tag: the raw hashes `tag` and `tag ^ 1` differ in bit 0 only, which the tag overwrites"""
+    assert tag & 1
+    a, b = str_with_raw_hash(tag, prefix_a), str_with_raw_hash(tag ^ 1, prefix_b)
+    assert a != b
+    return a, b

@@ -35,17 +35,18 @@ def ctx(ch):
     c.close()
 
 
-def _column(ch, ctx, values, misalign=0):
-    """a ColumnString of `values`; misalign > 0: chars is a view `misalign` bytes into a padded buffer, offsets built for the view"""
-    if not misalign:
+def _column(ch, ctx, values, misalign=0, slack=b""):
+    """a ColumnString of `values`; misalign > 0: chars is a view `misalign` bytes into a padded buffer, offsets built for the view;
+    slack: bytes that belong to chars but to no value (chars.size() > offsets.back())"""
+    if not misalign and not slack:
         col = ch.ColumnString.from_values(ctx, values)
         assert col.chars.size() == 0 or col.chars.device_ptr % 16 == 0
         return col
     lens = np.fromiter((len(v) + 1 for v in values), dtype=np.uint64, count=len(values))
-    chars = np.frombuffer(b"\xee" * misalign + b"".join(v + b"\0" for v in values) + b"\xee" * 32, dtype=np.uint8)
+    chars = np.frombuffer(b"\xee" * misalign + b"".join(v + b"\0" for v in values) + slack + b"\xee" * 32, dtype=np.uint8)
     whole = ctx.upload(chars)
-    view = whole.cut(misalign, int(lens.sum()))
-    assert view.device_ptr % 16 == misalign
+    view = whole.cut(misalign, int(lens.sum()) + len(slack))
+    assert view.device_ptr % 16 == misalign and view.size() == int(lens.sum()) + len(slack)
     return ch.ColumnString(ctx.upload(np.cumsum(lens, dtype=np.uint64)), view, list(values))
 
 
@@ -116,6 +117,17 @@ def test_brand_between_as_two_comparisons(ch, ctx):
     got = ch.and_(col.compare(ch.GE, "MFGR#2221"), col.compare(ch.LE, "MFGR#2228")).numpy()
     want = np.array([b"MFGR#2221" <= v <= b"MFGR#2228" for v in values], dtype=np.uint8)
     assert np.array_equal(got, want) and 0 < want.sum() < len(values)
+
+
+@pytest.mark.parametrize("misalign", [1, 7, 15])
+def test_compare_on_a_misaligned_chars_view(ch, ctx, misalign):
+    # k_str_row_const reads the value 8 bytes per step at whatever address the view gives it
+    rng = random.Random(1)
+    consts = [bytes(rng.randrange(256) for _ in range(n)) for n in LENGTHS] + [b"a" * n for n in LENGTHS] + [b"a", b"a\0", b"\xff", b"a\0b"]
+    values = _edge_values(rng, consts)
+    col = _column(ch, ctx, values, misalign)
+    for const in consts:
+        _check_compare(ch, col, values, const)
 
 
 # ---- contains: the flat kernel's edges -------------------------------------------------------------------------------------------------------
@@ -190,6 +202,65 @@ def test_contains_tiles_of_empty_rows(ch, ctx):
         assert 0 < want.sum() < 10
 
 
+@pytest.mark.parametrize("misalign", [1, 7, 15])
+def test_contains_tiles_of_empty_rows_on_a_misaligned_view(ch, ctx, misalign):
+    # the same column cut off the 16-byte grid: the search of a tile's rows in global memory (more than SM_ROWS_LDS of them) with a0 != 0
+    values = [b"ab"] + [b""] * (2 * SM_TILE + 5) + [b"xab", b"b"] + [b""] * (SM_ROWS_LDS + 300) + [b"ab"] + [b""] * 700 + [b"a", b"b", b"ab"]
+    col = _column(ch, ctx, values, misalign)
+    for needle in (b"ab", b"b", b"a"):
+        want = _check(col, values, "contains", needle, lambda v: needle in v)
+        assert 0 < want.sum() < 10
+    # a needle that starts with the zero byte: every terminator is a candidate and none may count
+    for needle in (b"\0", b"\0\0", b"\0a", b"b\0"):
+        assert _check(col, values, "contains", needle, lambda v: needle in v).sum() == 0
+
+
+def test_contains_zero_needles_on_the_aligned_column_of_empty_rows(ch, ctx):
+    values = [b"ab"] + [b""] * (2 * SM_TILE + 5) + [b"x\0b", b"\0"] + [b""] * (SM_ROWS_LDS + 300) + [b"a\0\0"] + [b""] * 700 + [b"a", b"\0\0", b"ab"]
+    col = _column(ch, ctx, values)
+    assert _check(col, values, "contains", b"\0", lambda v: b"\0" in v).sum() == 4
+    assert _check(col, values, "contains", b"\0\0", lambda v: b"\0\0" in v).sum() == 2
+
+
+def _slack_cases(a0):
+    """(values, slack, needle, ends_on_a_tile_boundary): chars carries 2 x SM_TILE bytes behind the last value, and they hold the needle:
+    completed across the last value's terminating zero, right behind it, again and again at a period that no tile size divides, and
+    as the very last bytes of chars.  The last value ends on a tile boundary of a chars address with low bits a0, or one byte beside it."""
+    out = []
+    for needle in (b"needle", b"e\0n", _needle(17)):
+        m = len(needle)
+        cut = needle.index(0) if 0 in needle else m - 1           # value ..needle[:cut], its zero, slack needle[cut + 1:].. spells a \0 needle
+        head, rest = needle[:cut], (needle[cut + 1:] if 0 in needle else needle[-1:])
+        for total in (2 * SM_TILE - a0, 2 * SM_TILE - a0 - 1, 2 * SM_TILE - a0 + 1, 1000):
+            values = [b"x" + needle[:-1], needle[1:], b"", b"has " + needle + b" inside", b"ends in " + needle, needle[:-1]]
+            fill = total - sum(len(v) + 1 for v in values) - 1 - len(head)
+            values.append(((needle[:1] + b"y" * 7) * (fill // 8 + 1))[:fill] + head)
+            assert sum(len(v) + 1 for v in values) == total
+            unit = needle + b"q" * (1 + m % 2)                    # an odd period: occurrences across every kind of tile boundary
+            assert len(unit) % 2 == 1
+            slack = (rest + unit * (2 * SM_TILE // len(unit) + 1))[:2 * SM_TILE - m] + needle
+            assert len(slack) == 2 * SM_TILE and slack.count(needle) > SM_TILE // len(unit)
+            out.append((values, slack, needle, (total + a0) % SM_TILE == 0))
+    return out
+
+
+@pytest.mark.parametrize("misalign", [0, 1, 7, 15])
+def test_predicates_do_not_see_bytes_behind_the_last_value(ch, ctx, misalign):
+    cases = _slack_cases(misalign)
+    assert sum(c[3] for c in cases) == 3
+    for values, slack, needle, _ in cases:
+        col = _column(ch, ctx, values, misalign, slack)
+        assert col.chars.size() == int(col.offsets.numpy()[-1]) + 2 * SM_TILE
+        want = _check(col, values, "contains", needle, lambda v: needle in v)
+        assert want.tolist() == [0, 0, 0, 1, 1, 0, 0]
+        _check(col, values, "like", b"%" + needle + b"%", lambda v: needle in v)
+        assert _check(col, values, "ends_with", needle, lambda v: v.endswith(needle)).tolist() == [0, 0, 0, 0, 1, 0, 0]
+        _check(col, values, "ends_with", needle[:-1], lambda v: v.endswith(needle[:-1]))
+        if max(needle) < 0x80:                                    # the general matcher, one lane per row
+            p = b"%" + needle + b"_%"
+            assert _check(col, values, "like", p, lambda v: sr.like_regex(p, v)).tolist() == [0, 0, 0, 1, 0, 0, 0]
+
+
 def test_contains_in_one_value_spanning_many_tiles(ch, ctx):
     rng = random.Random(5)
     big = bytearray(rng.choice(b"abcdefgh") for _ in range(65536))
@@ -231,6 +302,17 @@ def test_starts_with_and_ends_with(ch, ctx):
     assert not col.starts_with(b"", negate=True).numpy().any()
 
 
+@pytest.mark.parametrize("misalign", [1, 7, 15])
+def test_starts_with_and_ends_with_on_a_misaligned_chars_view(ch, ctx, misalign):
+    rng = random.Random(9)
+    needles = [bytes(rng.randrange(256) for _ in range(n)) for n in LENGTHS] + [b"a" * n for n in LENGTHS] + [b"a\0", b"\xff"]
+    values = _edge_values(rng, needles)
+    col = _column(ch, ctx, values, misalign)
+    for needle in needles:
+        _check(col, values, "starts_with", needle, lambda v: v.startswith(needle))
+        _check(col, values, "ends_with", needle, lambda v: v.endswith(needle))
+
+
 # ---- LIKE -------------------------------------------------------------------------------------------------------------------------------------
 LIKE_PATTERNS = ["", "%", "%%", "_", "a", "a%", "%a", "%a%", "a%b", "a%b%c", "%a_c%", "_%_", "a\\%b", "a\\_b", "\\\\", "ж_", "_€_", "%€",
                  "a%ab", "%aab", "%a_a", "a\\xb", "%\n%", "_\n"]
@@ -251,6 +333,17 @@ def test_like_fixed_table(ch, ctx):
     assert col.like("a%ab").numpy()[values.index(b"aaab")] == 1
     assert col.like("%aab").numpy()[values.index(b"aaaab")] == 1
     assert col.like("%a_a").numpy()[values.index(b"aaba")] == 1
+
+
+@pytest.mark.parametrize("misalign", [1, 7, 15])
+def test_like_fixed_table_on_a_misaligned_chars_view(ch, ctx, misalign):
+    values = [v.encode("utf-8") for v in LIKE_VALUES]
+    col = _column(ch, ctx, values, misalign)
+    seen = 0
+    for pattern in LIKE_PATTERNS:
+        p = pattern.encode("utf-8")
+        seen += int(_check(col, values, "like", p, lambda v: sr.like_regex(p, v)).sum())
+    assert seen > 100
 
 
 def test_like_seeded_fuzz(ch, ctx):

@@ -244,3 +244,146 @@ def test_keydict_tag_with_home_is_the_same_cell_of_every_capacity():
     for w in (2, 4):
         fam = kc.keydict_same_tag_keys(rng, 17, w, tag)
         assert np.all(kc.keydict_home(kc.keydict_tag(fam), 2048) == 2047)
+
+
+# ---- the string dictionary's hash ---------------------------------------------------------------------------------------------------
+STRING_SRC = os.path.join(os.path.dirname(KEYDICT_SRC), "string_kernels.hip")
+STR_CAPS = [1024, 2048, 1 << 18]
+
+
+def _str_hash_py(data):
+    """str_hash_bytes written out once more, on its own: Python ints, no helper of keycraft"""
+    m = 2**64
+    h = 0x9E3779B97F4A7C15 ^ (len(data) * 0xFF51AFD7ED558CCD % m)
+    i = 0
+    while i + 8 <= len(data):
+        h = (h ^ int.from_bytes(data[i:i + 8], "little")) * 0xC4CEB9FE1A85EC53 % m
+        h ^= h >> 29
+        i += 8
+    if i < len(data):
+        h = (h ^ int.from_bytes(data[i:], "little")) * 0xC4CEB9FE1A85EC53 % m
+        h ^= h >> 29
+    return int(kc.int_hash64(np.array([h], dtype=np.uint64))[0]) | 1
+
+
+def test_string_hash_constants_match_the_kernel_source():
+    """a change of the string hash, of the home cell or of the table size in string_kernels.hip must fail here, not silently un-craft
+    the cases of test_gpu_string_table.py"""
+    import re
+    src = open(STRING_SRC).read()
+    body = re.search(r"u64 str_hash_bytes\(const u8 \* p, u64 len\)\s*\{(.*?)\n\}", src, re.S)
+    assert body, "str_hash_bytes is gone or has another signature: restate it in keycraft.py"
+    body = body.group(1)
+    seed = re.search(r"u64 h = 0x([0-9A-Fa-f]{16})ull \^ \(len \* 0x([0-9A-Fa-f]{16})ull\);", body)
+    assert seed, "the seed line of str_hash_bytes changed"
+    assert (int(seed.group(1), 16), int(seed.group(2), 16)) == (kc.STR_SEED, kc.STR_LEN_MUL)
+    steps = re.findall(r"h = \(h \^ (?:str_load8\(p \+ i\)|tail)\) \* 0x([0-9A-Fa-f]{16})ull;\s*h \^= h >> (\d+);", body)
+    assert [(int(m, 16), int(s)) for m, s in steps] == [(kc.STR_WORD_MUL, kc.STR_SHIFT)] * 2, steps   # the full words, the masked tail
+    assert re.search(r"tail = str_load8\(p \+ i\) & \(~0ull >> \(8 \* \(8 - \(len - i\)\)\)\);", body), "the tail mask changed"
+    assert re.search(r"h = dev_intHash64\(h\);\s*return h \| 1ull;", body), "the last two lines of str_hash_bytes changed"
+    assert len(re.findall(r"u64 s = \(h >> 1\) & mask;", src)) == 2                 # k_str_insert and k_str_resolve: one home cell
+    assert len(re.findall(r"s = \(s \+ 1\) & mask;", src)) == 2                     # linear probing that wraps
+    cap = re.search(r"u64 cap = (\d+);\s*while \(cap < (\d+) \* n\)\s*cap <<= 1;", src)
+    assert cap, "the table size rule of chgpu_string_dictionary_encode changed"
+    assert (int(cap.group(1)), int(cap.group(2))) == (kc.STR_CAP_MIN, kc.STR_CELLS_PER_ROW)
+    assert (kc.STR_SEED, kc.STR_LEN_MUL, kc.STR_WORD_MUL) == (0x9E3779B97F4A7C15, 0xFF51AFD7ED558CCD, 0xC4CEB9FE1A85EC53)
+
+
+def test_string_table_capacity_steps():
+    assert [kc.str_table_cap(n) for n in (0, 1, 511, 512, 513, 1024, 1025, 100_000, 131_072, 131_073)] == \
+        [1024, 1024, 1024, 1024, 2048, 2048, 4096, 1 << 18, 1 << 18, 1 << 19]
+
+
+def test_string_hash_against_python_ints():
+    rng = _rng()
+    values = [b"", b"a", b"a\0", b"\0", b"\0" * 8, b"\xff" * 9] + [rng.integers(0, 256, size=n, dtype=np.uint8).tobytes() for n in range(0, 70)]
+    for v in values:
+        assert kc.str_hash(v) == _str_hash_py(v) and kc.str_hash(v) & 1 and kc.str_hash(v) == kc.str_raw_hash(v) | 1
+        assert kc.str_hash(v) != kc.str_hash(v + b"\0")       # the length is hashed: a zero-extended tail is another value
+    assert len({kc.str_hash(v) for v in values}) == len(set(values))
+
+
+@pytest.mark.parametrize("prefix_len", [0, 8, 16, 64])
+def test_str_with_raw_hash_round_trips(prefix_len):
+    rng = _rng()
+    raws = [0, 1, 2, 2**63, 2**64 - 1] + [int(x) for x in rng.integers(0, 2**64 - 1, size=500, dtype=np.uint64, endpoint=True)]
+    for raw in raws:
+        prefix = rng.integers(0, 256, size=prefix_len, dtype=np.uint8).tobytes()
+        s = kc.str_with_raw_hash(raw, prefix)
+        assert len(s) == prefix_len + 8 and s.startswith(prefix)
+        assert kc.str_raw_hash(s) == raw and _str_hash_py(s) == raw | 1
+    with pytest.raises(AssertionError):
+        kc.str_with_raw_hash(5, b"abc")
+
+
+@pytest.mark.parametrize("cap", STR_CAPS)
+def test_str_with_home_lands_where_asked(cap):
+    for cell in (0, 1, 31, cap - 500, cap - 2, cap - 1):
+        fam = [kc.str_with_home(cell, cap, salt) for salt in range(300)]
+        assert len(set(fam)) == 300 and all(len(s) == 8 for s in fam)
+        assert {kc.str_home(_str_hash_py(s), cap) for s in fam} == {cell}
+        assert len({_str_hash_py(s) for s in fam}) == 300
+    # eight strings homed at cell 1022 of 1024 -- the chain of the wrap case -- and a prefixed one
+    assert kc.str_home(kc.str_hash(kc.str_with_home(cap - 2, cap, 7, b"prefix--")), cap) == cap - 2
+    # salts 1 << k: one home, tags that differ in one high bit only
+    lg = cap.bit_length() - 1
+    base = kc.str_hash(kc.str_with_home(5, cap, 0))
+    for k in (0, 1, 30, 62 - lg):
+        t = kc.str_hash(kc.str_with_home(5, cap, 1 << k))
+        assert t ^ base == 1 << (k + lg + 1) and kc.str_home(t, cap) == 5
+
+
+def test_str_tag_twins_differ_and_share_a_tag():
+    rng = _rng()
+    for tag in [1, 2**64 - 1] + [int(x) | 1 for x in rng.integers(0, 2**64 - 1, size=200, dtype=np.uint64, endpoint=True)]:
+        for pa, pb in ((b"", b""), (b"", b"8 bytes!"), (b"sixteen bytes...", b"")):
+            a, b = kc.str_tag_twins(tag, pa, pb)
+            assert a != b and (len(a), len(b)) == (len(pa) + 8, len(pb) + 8)
+            assert _str_hash_py(a) == _str_hash_py(b) == tag
+            assert {kc.str_raw_hash(a), kc.str_raw_hash(b)} == {tag, tag ^ 1}
+    with pytest.raises(AssertionError):
+        kc.str_tag_twins(2)
+
+
+def test_string_hash_matches_the_kernel_source_compiled_for_the_host(tmp_path):
+    """str_load8, str_hash_bytes and dev_intHash64 cut out of the HIP sources and compiled with the host compiler: the crafted strings have
+    the tags and home cells they were made for under the kernel's own code, and twins share a tag there"""
+    import ctypes
+    import re
+    import subprocess
+    src = open(STRING_SRC).read()
+    internal = open(os.path.join(os.path.dirname(STRING_SRC), "chgpu_internal.h")).read()
+
+    def cut(text, head):
+        m = re.search(r"__device__ __forceinline__ " + re.escape(head) + r"\s*\{.*?\n\}", text, re.S)
+        assert m, head
+        return m.group(0)
+    code = "\n".join(["#include <cstdint>", "typedef uint64_t u64; typedef uint8_t u8;", "#define __device__", "#define __forceinline__ inline",
+                      cut(internal, "u64 dev_intHash64(u64 x)"), cut(src, "u64 str_load8(const u8 * p)"), cut(src, "u64 str_hash_bytes(const u8 * p, u64 len)"),
+                      'extern "C" u64 host_str_hash(const u8 * p, u64 len) { return str_hash_bytes(p, len); }', ""])
+    (tmp_path / "h.cpp").write_text(code)
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", str(tmp_path / "h.cpp"), "-o", str(tmp_path / "h.so")])
+    fn = ctypes.CDLL(str(tmp_path / "h.so")).host_str_hash
+    fn.restype, fn.argtypes = ctypes.c_uint64, [ctypes.c_char_p, ctypes.c_uint64]
+
+    def host(v):
+        return fn(v + b"\xee" * 8, len(v))       # the bytes behind the value are not zero: the tail mask is what drops them
+    rng = _rng()
+    for n in list(range(40)) + [63, 64, 65, 1000]:
+        v = rng.integers(0, 256, size=n, dtype=np.uint8).tobytes()
+        assert host(v) == kc.str_hash(v), n
+    for cap in STR_CAPS:
+        for cell in (0, cap - 2, cap - 1):
+            for salt in (0, 1, 12345):
+                assert kc.str_home(host(kc.str_with_home(cell, cap, salt)), cap) == cell
+    for pa, pb in ((b"", b""), (b"", b"a prefix")):
+        a, b = kc.str_tag_twins(0x0123456789ABCDEF, pa, pb)
+        assert host(a) == host(b) == 0x0123456789ABCDEF
+    # a helper with another multiplier does not craft twins: the check above is not vacuous
+    good = kc.STR_WORD_MUL
+    try:
+        kc.STR_WORD_MUL = kc.KD_TAG_MUL
+        a, b = kc.str_tag_twins(0x0123456789ABCDEF)
+        assert kc.str_hash(a) == kc.str_hash(b) and host(a) != host(b)
+    finally:
+        kc.STR_WORD_MUL = good
