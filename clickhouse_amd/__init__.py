@@ -1,7 +1,7 @@
 """clickhouse_amd — MI355X-native block-processing hot path (filter -> aggregate -> hash join) behind the
 reference's column / function / aggregate / join interfaces.  Requires libchgpu.so (HIP, gfx950): no CPU fallback."""
 from . import _capi
-from ._capi import (AGG_AVG, AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_ANY, ASOF_LESS, ASOF_GREATER, ASOF_LESS_OR_EQUALS, ASOF_GREATER_OR_EQUALS, EQ, F32, F64, GE, GT, I32, I64, JOIN_FULL, JOIN_INNER, JOIN_LEFT, JOIN_RIGHT, LE, LT, NE,
+from ._capi import (AGG_AVG, AGG_COUNT, AGG_SUM, AGG_MIN, AGG_MAX, AGG_ANY, AGG_ARG_MIN, AGG_ARG_MAX, ASOF_LESS, ASOF_GREATER, ASOF_LESS_OR_EQUALS, ASOF_GREATER_OR_EQUALS, EQ, F32, F64, GE, GT, I32, I64, JOIN_FULL, JOIN_INNER, JOIN_LEFT, JOIN_RIGHT, LE, LT, NE,
                     STRICT_ALL, STRICT_ANTI, STRICT_ANY, STRICT_SEMI, I8, I16, U8, U16, U32, U64, ChgpuError)
 from ._capi import VAL_COL, VAL_MINUS, VAL_MUL, VAL_PLUS
 from ._capi import (STR_LIKE, STR_CONTAINS, STR_STARTS_WITH, STR_ENDS_WITH, STR_ROUTE_EQUALS, STR_ROUTE_STARTS_WITH, STR_ROUTE_ENDS_WITH, STR_ROUTE_CONTAINS,

@@ -12,12 +12,14 @@ from .columns import NP_OF, TAG_OF, Column, Context, sum_result_dtype
 
 
 _OVERFLOW_MODES = {"throw": K.OVERFLOW_THROW, "break": K.OVERFLOW_BREAK, "any": K.OVERFLOW_ANY}
+_TWO_ARGS = (K.AGG_ARG_MIN, K.AGG_ARG_MAX)   # argMin(arg, val) / argMax(arg, val): two argument slots of the C ABI, arg then val
 
 
 class Aggregator:
     def __init__(self, key_dtype, aggs, two_level_threshold: int = 100000, size_hint: int = 0, ctx: Context | None = None,
                  max_rows_to_group_by: int = 0, group_by_overflow_mode: str = "throw", overflow_row: bool = False):
-        """aggs: list of (kind, arg_dtype or None).  key_dtype None = without_key.  two_level_threshold is accepted for
+        """aggs: list of (kind, arg_dtype or None); argMin / argMax: (kind, (arg_dtype, val_dtype)), and the matching entry of
+        execute_on_block's args is (arg_array, val_array).  key_dtype None = without_key.  two_level_threshold is accepted for
         interface parity (Aggregator::Params) — the device table is single-level.  max_rows_to_group_by (0 = no limit),
         group_by_overflow_mode ("throw" / "break" / "any") and overflow_row are the settings of the same names."""
         mode = _OVERFLOW_MODES.get(group_by_overflow_mode)
@@ -25,9 +27,12 @@ class Aggregator:
             raise ValueError(f"group_by_overflow_mode must be one of {sorted(_OVERFLOW_MODES)}, not {group_by_overflow_mode!r}")
         self.ctx = ctx if ctx is not None else Context(0)
         self.key_tag = -1 if key_dtype is None else TAG_OF[np.dtype(key_dtype)]
-        self.aggs = [(k, (TAG_OF[np.dtype(d)] if d is not None else K.U64)) for k, d in aggs]
+        # (kind, tag of the result's argument); val_tags[j]: the second argument's tag of a two-argument function, else None
+        self.aggs = [(k, (TAG_OF[np.dtype(d[0] if k in _TWO_ARGS else d)] if d is not None else K.U64)) for k, d in aggs]
+        self.val_tags = [TAG_OF[np.dtype(d[1])] if k in _TWO_ARGS else None for k, d in aggs]
+        slots = [t for (_, t), v in zip(self.aggs, self.val_tags) for t in ((t,) if v is None else (t, v))]
         kinds = (C.c_int * max(1, len(self.aggs)))(*[k for k, _ in self.aggs])
-        types = (C.c_int * max(1, len(self.aggs)))(*[t for _, t in self.aggs])
+        types = (C.c_int * max(1, len(slots)))(*slots)
         h = C.c_void_p()
         K.check(K.lib().chgpu_agg_create(self.ctx._h, self.key_tag, len(self.aggs), kinds, types, size_hint, C.byref(h)))
         self._h = h
@@ -51,7 +56,9 @@ class Aggregator:
         """Aggregator::executeOnBlock(columns, row_begin, row_end, result, key_columns, aggregate_columns, ...).
         filter: a UInt8 WHERE mask over the same rows (a FilterTransform fused in front of the aggregation)."""
         kcol = self.ctx.column(keys) if keys is not None else None
-        acols = [self.ctx.column(a) if a is not None else None for a in args]
+        # one column per argument slot: a two-argument function's (arg, val) pair takes two
+        flat = [x for (k, _), a in zip(self.aggs, args) for x in (a if k in _TWO_ARGS else (a,))]
+        acols = [self.ctx.column(a) if a is not None else None for a in flat]
         fcol = self.ctx.column(filter) if filter is not None else None
         n = kcol.size() if kcol is not None else (fcol.size() if fcol is not None else next(a.size() for a in acols if a is not None))
         row_end = n if row_end is None else row_end
@@ -126,12 +133,13 @@ class Aggregator:
 
     @property
     def n_words(self):
-        return sum(2 if k in (K.AGG_AVG, K.AGG_ANY) else 1 for k, _ in self.aggs)   # (min / max: one order-key word; any: claim + value)
+        # (min / max: one order-key word; any: claim + value; argMin / argMax: val word + has + arg bits)
+        return sum(3 if k in _TWO_ARGS else 2 if k in (K.AGG_AVG, K.AGG_ANY) else 1 for k, _ in self.aggs)
 
     def result_dtypes(self):
         out = []
         for kind, t in self.aggs:
-            out.append(np.uint64 if kind == K.AGG_COUNT else np.float64 if kind == K.AGG_AVG else NP_OF[t] if kind in (K.AGG_MIN, K.AGG_MAX, K.AGG_ANY) else sum_result_dtype(t))
+            out.append(np.uint64 if kind == K.AGG_COUNT else np.float64 if kind == K.AGG_AVG else NP_OF[t] if kind in (K.AGG_MIN, K.AGG_MAX, K.AGG_ANY) + _TWO_ARGS else sum_result_dtype(t))
         return out
 
     def finalize_columns(self):
@@ -208,7 +216,8 @@ class NullableKeyAggregator:
         from .columns import count_bytes_in_filter
         k = self.ctx.column(keys)
         nm = self.ctx.column(null_map)
-        acols = [self.ctx.column(a) if a is not None else None for a in args]
+        # (an argMin / argMax entry is an (arg, val) pair: both are uploaded once and shared by the two aggregations)
+        acols = [tuple(self.ctx.column(x) for x in a) if isinstance(a, tuple) else self.ctx.column(a) if a is not None else None for a in args]
         not_null = self._not.execute(self.ctx, [nm], [1])[0]
         self.keyed.execute_on_block(k, acols, filter=not_null)
         if count_bytes_in_filter(nm):

@@ -58,9 +58,11 @@ static constexpr size_t AGG_HDR_BYTES = (sizeof(AggCtrl) + 255) / 256 * 256;
 
 struct AggArg
 {
-    const void * ptr; // argument column (NULL for count)
+    const void * ptr; // argument column (NULL for count); argMin / argMax: the `arg` column, the one the result comes from
+    const void * val; // argMin / argMax: the `val` column, the one that is compared
     int kind;
     int arg_type;
+    int val_type;
     u32 word;         // first state word
     u32 pre;          // partitioned path: index of this argument's word column in the partition buffers
 };
@@ -78,6 +80,10 @@ struct AggDesc
     unsigned char fx_hi[AGG_MAX_WORDS];
     int fx_base;
     u64 row_seq; // any(): row i of the argument columns is the (row_seq + i)-th row this aggregation has seen (modulo 2^64)
+    // argMin / argMax: the claim a raised extremum falls back to, that of the ordinal behind the block's last row: below the claim of
+    // every row of this and every earlier block (see raise_extremum)
+    u64 arg_sentinel;
+    u32 word_arg; // bit w: words w, w + 1, w + 2 are the {val key, claim, arg} of an argMin / argMax (table words: such rows take the DIRECT kernel)
     // A pass over a SUBSET of the functions (one argument word at a time through the tile-sorted plan) numbers its state words locally
     // (0 .. n_words - 1: the LDS cells hold only those) and finds the table's words through this map; the identity otherwise.
     unsigned char word_map[AGG_MAX_WORDS];
@@ -103,6 +109,9 @@ struct chgpu_agg
     u32 n_aggs = 0, n_words = 0;
     int kinds[AGG_MAX_AGGS];
     int arg_types[AGG_MAX_AGGS];
+    int val_types[AGG_MAX_AGGS]; // argMin / argMax: the type of `val` (arg_types[j] is `arg`'s, the result's)
+    u32 slot[AGG_MAX_AGGS];      // the aggregate's first argument slot: arg_cols[] is indexed by slot, argMin / argMax own two (arg, val)
+    u32 n_slots = 0;
     u32 word_off[AGG_MAX_AGGS];
     u32 word_is_f64 = 0;
     u64 size_hint = 0;
@@ -115,6 +124,9 @@ struct chgpu_agg
     // any(): {claim, value} words.  claim = ~(ordinal of the row that set the value) under an unsigned max: the EARLIEST row of the group
     // wins whatever order the hardware serves the rows in; the value is stored by a second pass from the winner's row (k_agg_any_resolve)
     u32 word_any = 0; // bit w: word w is a claim, word w + 1 its value
+    // argMin / argMax: {val key, claim, arg} words.  The val key combines like a min / max word, the claim names the earliest row (or
+    // merged state) that holds that extremum, the arg is stored from the claim's row (k_agg_arg_rows)
+    u32 word_arg = 0; // bit w: word w is a val key, w + 1 its claim, w + 2 its arg
     u64 any_seq = 0;  // rows seen so far
     u64 nokey_kept = 0; // without key: rows that reached the states (0 = min / max / any have no value: insertResultInto gives the default)
     // deterministic Float64 sums (option deterministic_float_sums, the default): sum / avg over a float argument keep a 128-bit fixed-point
@@ -377,6 +389,32 @@ __device__ __host__ __forceinline__ u64 agg_order_key_inverse(u64 key, int type)
     }
 }
 
+// argMin / argMax compare `val` with the reference's operator > / <, to which the two zeros are equal: the val key folds the zero's
+// sign away (val is never returned, so nothing is lost).  min / max keep agg_order_key: they return the value.
+__device__ __host__ __forceinline__ u64 agg_val_key(u64 bits, int type)
+{
+    if ((type == CHGPU_F64 || type == CHGPU_F32) && (bits << 1) == 0)
+        bits = 0;
+    return agg_order_key(bits, type);
+}
+// argMin / argMax claims.  A row's claim is ~(ordinal + 1): as any()'s, but below ~0, which is kept for "older than every row".  A
+// state that arrives by a merge claims with AGG_MERGE_CLAIM_TOP - its index among the source tuples: below every row's claim (ordinals
+// stay under 2^63), so a destination that holds the same extremum keeps its own, above AGG_MERGE_SENTINEL, and the earliest source wins
+// among several.  The winner then sets the claim to ~0: older than every row to come.
+static constexpr u64 AGG_MERGE_CLAIM_TOP = 0x7FFFFFFFFFFFFFFFull;
+static constexpr u64 AGG_MERGE_SENTINEL = 1;
+__device__ __host__ __forceinline__ u64 agg_arg_row_claim(u64 ordinal) { return ~ordinal - 1; }
+// The first pass of an argMin / argMax update: raise the val key; whoever raised it also pulls the claim down to `sentinel`, because the
+// claim then names a row that holds the OLD extremum.  The rows (states) that hold the final extremum claim after the kernel boundary.
+__device__ __forceinline__ void raise_extremum(u64 * val, u64 * claim, u64 key, u64 sentinel)
+{
+    if (key == 0)
+        return; // the identity
+    const u64 old = __hip_atomic_fetch_max((unsigned long long *)val, (unsigned long long)key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (key > old)
+        __hip_atomic_fetch_min((unsigned long long *)claim, (unsigned long long)sentinel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Where a group's state lives.  A sink has three members: at(w) = the address of TABLE word w, add_word(p, bits, op) (op as in
 // global_add_word) and add_fx(lo, hi, x).  GlobalSink is a cell of the HBM table; LdsRowSink (below, with the overflow row) is a
 // workgroup's LDS copy of the overflow row.
@@ -388,6 +426,7 @@ struct GlobalSink
     __device__ __forceinline__ u64 * at(u32 w) const { return words + (u64)w * stride + slot; }
     __device__ __forceinline__ void add_word(u64 * p, u64 bits, int op) const { global_add_word(p, bits, op); }
     __device__ __forceinline__ void add_fx(u64 * lo, u64 * hi, Fx128 x) const { global_add_fx(lo, hi, x); }
+    __device__ __forceinline__ void raise(u64 * val, u64 * claim, u64 key, u64 sentinel) const { raise_extremum(val, claim, key, sentinel); }
 };
 
 // add row i's contribution of every aggregate to the group's state in `sink` (IAggregateFunction::add per function)
@@ -407,6 +446,11 @@ __device__ __forceinline__ void add_row(const Sink & sink, const AggDesc & d, u6
         }
         else if (a.kind == CHGPU_AGG_ANY)
             sink.add_word(w, ~(d.row_seq + i), 2); // the claim of the earliest row; its value follows in k_agg_any_resolve
+        else if (a.kind == CHGPU_AGG_ARG_MIN || a.kind == CHGPU_AGG_ARG_MAX)
+        {
+            const u64 k = agg_val_key(load_arg_bits(a.val, a.val_type, i), a.val_type);
+            sink.raise(w, sink.at(d.word_map[a.word] + 1), a.kind == CHGPU_AGG_ARG_MAX ? k : ~k, d.arg_sentinel); // claim and arg: k_agg_arg_rows
+        }
         else
         {
             if ((d.word_fx >> a.word) & 1)
@@ -496,6 +540,8 @@ struct LdsRowSink
     __device__ __forceinline__ u64 * at(u32 w) const { return s + w; }
     __device__ __forceinline__ void add_word(u64 * p, u64 bits, int op) const { ovf_lds_word(p, bits, op); }
     __device__ __forceinline__ void add_fx(u64 * lo, u64 * hi, Fx128 x) const { lds_add_fx(lo, hi, x); }
+    // argMin / argMax: the workgroup's largest val key; ovf_flush raises the overflow row's with it (the LDS claim word stays unused)
+    __device__ __forceinline__ void raise(u64 * val, u64 *, u64 key, u64) const { ovf_lds_word(val, key, 2); }
 };
 // local state word w of a flushed LDS cell (bits; hb = its fixed-point high half), to the group's state in `sink`
 template <typename Sink>
@@ -530,14 +576,23 @@ __device__ __forceinline__ bool place_and_add(const AggTable & t, u64 * s_ovf, u
 // words 0 .. n_words-1 map to table words through `map`; masks as in AggDesc (word_is_f64: bit w Float64 add, bit 16 + w unsigned max).
 // any_merge: any() {claim, value} pairs that arrive together (merges: the first state that claims the overflow row keeps it,
 // changeFirstTime) -- a row's claim instead combines by max and its value is stored by the winning row later (k_agg_any_resolve).
+// arg_mask: argMin / argMax val keys (table words): raised like a cell's, with `arg_sentinel`; their claim and arg words follow in the
+// claim and resolve passes.
 __device__ __forceinline__ void ovf_flush(const AggTable & t, const u64 * s, u32 n_words, u32 f64, u32 fx, u32 fx_hi_mask, const unsigned char * fx_hi,
-                                          const unsigned char * map, u32 any_merge)
+                                          const unsigned char * map, u32 any_merge, u32 arg_mask, u64 arg_sentinel)
 {
     const u32 w = threadIdx.x;
     if (!t.ovf || w >= n_words || ((fx_hi_mask >> w) & 1) || (w > 0 && ((any_merge >> (w - 1)) & 1)))
         return;
     const u32 gw = map ? map[w] : w; // (NULL: the identity)
+    if ((((arg_mask << 1) | (arg_mask << 2)) >> gw) & 1)
+        return; // a claim or an arg word
     const u64 bits = s[gw];
+    if ((arg_mask >> gw) & 1)
+    {
+        raise_extremum(t.ovf + gw, t.ovf + gw + 1, bits, arg_sentinel);
+        return;
+    }
     if ((any_merge >> w) & 1)
     {
         if (bits && atomicCAS((unsigned long long *)(t.ovf + gw), 0ull, (unsigned long long)bits) == 0ull)
@@ -557,7 +612,7 @@ __device__ __forceinline__ void ovf_flush(const AggTable & t, const u64 * s, u32
 }
 __device__ __forceinline__ void ovf_flush_desc(const AggTable & t, const u64 * s, const AggDesc & d)
 {
-    ovf_flush(t, s, d.n_words, d.word_is_f64, d.word_fx, d.word_fx_hi, d.fx_hi, d.word_map, 0);
+    ovf_flush(t, s, d.n_words, d.word_is_f64, d.word_fx, d.word_fx_hi, d.fx_hi, d.word_map, 0, d.word_arg, d.arg_sentinel);
 }
 
 // ---- the workgroup's LDS table of the LDS-staged kernels ----
@@ -1783,6 +1838,8 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tiles_pending_aos(AggTable 
 struct AggFxWords
 {
     u32 word_fx, word_fx_hi, word_any;
+    u32 word_arg; // argMin / argMax triples
+    u32 rehash;   // the tuples are the cells of the table being replaced: every key once, into an empty table
     unsigned char fx_hi[AGG_MAX_WORDS];
 };
 // source tuple i's state words into the group's state in `sink` (table words: a merge has no word map)
@@ -1801,6 +1858,21 @@ __device__ __forceinline__ void merge_tuple_words(const Sink & sink, u32 n_words
             if (v && atomicCAS((unsigned long long *)sink.at(w), 0ull, (unsigned long long)v) == 0ull)
                 *sink.at(w + 1) = src_words[(u64)(w + 1) * src_stride + i];
             ++w;
+            continue;
+        }
+        if ((fx.word_arg >> w) & 1)
+        {
+            const u64 has = src_words[(u64)(w + 1) * src_stride + i];
+            if (fx.rehash)
+            {
+                // {val, claim, arg} move unchanged: a claim may be the sentinel of a block whose claim pass is still to come
+                *sink.at(w) = v;
+                *sink.at(w + 1) = has;
+                *sink.at(w + 2) = src_words[(u64)(w + 2) * src_stride + i];
+            }
+            else if (has) // (a state without a value loses every merge); claim and arg: k_agg_arg_tuples
+                sink.raise(sink.at(w), sink.at(w + 1), v, AGG_MERGE_SENTINEL);
+            w += 2;
             continue;
         }
         if ((fx.word_fx >> w) & 1)
@@ -1887,7 +1959,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, u32 n_wo
     if (t.ovf)
     {
         __syncthreads();
-        ovf_flush(t, s_ovf, n_words, word_is_f64, fx.word_fx, fx.word_fx_hi, fx.fx_hi, nullptr, fx.word_any);
+        ovf_flush(t, s_ovf, n_words, word_is_f64, fx.word_fx, fx.word_fx_hi, fx.fx_hi, nullptr, fx.word_any, fx.word_arg, AGG_MERGE_SENTINEL);
     }
 }
 
@@ -1944,6 +2016,8 @@ static AggFxWords agg_fx_words(const chgpu_agg * a)
     f.word_fx = a->word_fx;
     f.word_fx_hi = a->word_fx_hi;
     f.word_any = a->word_any;
+    f.word_arg = a->word_arg;
+    f.rehash = 0;
     memcpy(f.fx_hi, a->fx_hi, sizeof(f.fx_hi));
     return f;
 }
@@ -1996,7 +2070,9 @@ static int agg_grow(chgpu_agg * a, u64 min_groups, bool has_zero)
     // old cells [0, capacity) plus the out-of-line zero cell when it is set; no soft limit: the new table fits them all
     const u64 n = a->t.capacity + (has_zero ? 1 : 0);
     const u32 grid = chgpu_grid_for(a->ctx, n, AGG_THREADS, 8);
-    hipLaunchKernelGGL(k_agg_tuples<AGG_MODE_ALL>, dim3(grid), dim3(AGG_THREADS), 0, a->ctx->stream, nt, a->n_words, a->word_is_f64, agg_fx_words(a),
+    AggFxWords fx = agg_fx_words(a);
+    fx.rehash = 1;
+    hipLaunchKernelGGL(k_agg_tuples<AGG_MODE_ALL>, dim3(grid), dim3(AGG_THREADS), 0, a->ctx->stream, nt, a->n_words, a->word_is_f64, fx,
                        a->t.keys, a->t.words, a->t.capacity + 1, n, 1, has_zero ? a->t.capacity : ~0ull, 0, (u64 *)nullptr);
     a->ctx->counters[6] += 1;
     a->ctx->counters[7] += 1;
@@ -2061,26 +2137,44 @@ extern "C" int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, 
     a->key_type = key_type;
     a->n_aggs = n_aggs;
     a->size_hint = size_hint;
-    u32 w = 0;
+    u32 w = 0, slot = 0;
     for (u32 j = 0; j < n_aggs; ++j)
     {
+        if (w >= AGG_MAX_WORDS)
+        {
+            delete a;
+            return chgpu_set_error(CHGPU_ERR_NOT_IMPLEMENTED, "more than %u state words: CPU path", AGG_MAX_WORDS);
+        }
         const int kind = agg_kinds[j];
-        const int at = (kind == CHGPU_AGG_COUNT || !arg_types) ? CHGPU_U64 : arg_types[j];
+        const bool arg_pair = kind == CHGPU_AGG_ARG_MIN || kind == CHGPU_AGG_ARG_MAX; // two argument slots: arg, then val
+        const int at = (kind == CHGPU_AGG_COUNT || !arg_types) ? CHGPU_U64 : arg_types[slot];
+        const int vt = (arg_pair && arg_types) ? arg_types[slot + 1] : CHGPU_U64;
         const bool any_value = kind == CHGPU_AGG_ANY;
         const bool extremum = kind == CHGPU_AGG_MIN || kind == CHGPU_AGG_MAX || any_value;
-        if (kind != CHGPU_AGG_COUNT && kind != CHGPU_AGG_SUM && kind != CHGPU_AGG_AVG && !extremum)
+        if (kind != CHGPU_AGG_COUNT && kind != CHGPU_AGG_SUM && kind != CHGPU_AGG_AVG && !extremum && !arg_pair)
         {
             delete a;
             return chgpu_set_error(CHGPU_ERR_NOT_IMPLEMENTED, "aggregate function kind %d has no device state: CPU path", kind);
         }
-        if (kind != CHGPU_AGG_COUNT && !chgpu_type_size(at))
+        if (kind != CHGPU_AGG_COUNT && (!chgpu_type_size(at) || !chgpu_type_size(vt)))
         {
             delete a;
-            return chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "bad argument type %d", at);
+            return chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "bad argument type %d", chgpu_type_size(at) ? vt : at);
         }
         a->kinds[j] = kind;
         a->arg_types[j] = at;
+        a->val_types[j] = vt;
+        a->slot[j] = slot;
+        slot += arg_pair ? 2 : 1;
         a->word_off[j] = w;
+        if (arg_pair)
+        {
+            a->has_extremum = true;
+            if (w + 3 <= AGG_MAX_WORDS)
+                a->word_arg |= 1u << w;
+            w += 3;
+            continue;
+        }
         if (extremum)
         {
             a->word_is_f64 |= 1u << (16 + w); // upper half of the mask: the word combines by unsigned max (order keys), never by an add
@@ -2098,6 +2192,7 @@ extern "C" int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, 
         return chgpu_set_error(CHGPU_ERR_NOT_IMPLEMENTED, "more than %u state words: CPU path", AGG_MAX_WORDS);
     }
     a->n_pub_words = w;
+    a->n_slots = slot;
     if (key_type >= 0 && chgpu_opt(ctx, "deterministic_float_sums", 1))
     {
         u32 n_fx = 0;
@@ -2148,13 +2243,19 @@ static void agg_fill_desc(const chgpu_agg * a, const chgpu_col * const * arg_col
     memcpy(d->fx_hi, a->fx_hi, sizeof(d->fx_hi));
     d->fx_base = a->fx_base;
     d->row_seq = 0;
+    d->arg_sentinel = 0;
+    d->word_arg = a->word_arg;
     for (u32 w = 0; w < AGG_MAX_WORDS; ++w)
         d->word_map[w] = (unsigned char)w;
     for (u32 j = 0; j < a->n_aggs; ++j)
     {
-        d->a[j].ptr = (arg_cols && arg_cols[j]) ? arg_cols[j]->data : nullptr;
+        const u32 sl = a->slot[j];
+        const bool arg_pair = a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX;
+        d->a[j].ptr = (arg_cols && arg_cols[sl]) ? arg_cols[sl]->data : nullptr;
+        d->a[j].val = (arg_pair && arg_cols && arg_cols[sl + 1]) ? arg_cols[sl + 1]->data : nullptr;
         d->a[j].kind = a->kinds[j];
         d->a[j].arg_type = a->arg_types[j];
+        d->a[j].val_type = a->val_types[j];
         d->a[j].word = a->word_off[j];
         d->a[j].pre = 0;
     }
@@ -2163,7 +2264,7 @@ static void agg_fill_desc(const chgpu_agg * a, const chgpu_col * const * arg_col
 // min / max / any WITHOUT key (executeWithoutKeyImpl, Aggregator.cpp:1276-1321: addBatchSinglePlace): one order-key maximum over the rows of
 // the block that pass `cond`; the first such row for any()
 __global__ __launch_bounds__(256) void k_nokey_extremum(const void * __restrict__ p, int type, u64 row_begin, u64 n, const u8 * __restrict__ cond, int is_min,
-                                                         unsigned long long * __restrict__ out)
+                                                         int val_key, unsigned long long * __restrict__ out)
 {
     u64 best = 0;
     for (u64 r = (u64)blockIdx.x * 256 + threadIdx.x; r < n; r += (u64)gridDim.x * 256)
@@ -2171,7 +2272,8 @@ __global__ __launch_bounds__(256) void k_nokey_extremum(const void * __restrict_
         const u64 i = row_begin + r;
         if (cond && !cond[i])
             continue;
-        const u64 k = agg_order_key(load_arg_bits(p, type, i), type);
+        const u64 bits = load_arg_bits(p, type, i);
+        const u64 k = val_key ? agg_val_key(bits, type) : agg_order_key(bits, type);
         const u64 v = is_min ? ~k : k;
         best = v > best ? v : best;
     }
@@ -2190,6 +2292,23 @@ __global__ __launch_bounds__(256) void k_nokey_first_row(u64 row_begin, u64 n, c
     for (u64 r = (u64)blockIdx.x * 256 + threadIdx.x; r < n && first == ~0ull; r += (u64)gridDim.x * 256)
         if (!cond || cond[row_begin + r])
             first = r;
+    if (first != ~0ull)
+        atomicMin(out, (unsigned long long)first);
+}
+// argMin / argMax without key: the first row of the block that passes `cond` and holds the val key `want` (k_nokey_extremum's result)
+__global__ __launch_bounds__(256) void k_nokey_first_holder(const void * __restrict__ p, int type, u64 row_begin, u64 n, const u8 * __restrict__ cond, int is_min,
+                                                             u64 want, unsigned long long * __restrict__ out)
+{
+    u64 first = ~0ull;
+    for (u64 r = (u64)blockIdx.x * 256 + threadIdx.x; r < n && first == ~0ull; r += (u64)gridDim.x * 256)
+    {
+        const u64 i = row_begin + r;
+        if (cond && !cond[i])
+            continue;
+        const u64 k = agg_val_key(load_arg_bits(p, type, i), type);
+        if ((is_min ? ~k : k) == want)
+            first = r;
+    }
     if (first != ~0ull)
         atomicMin(out, (unsigned long long)first);
 }
@@ -2239,6 +2358,96 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_any_resolve(AggTable t, Agg
         for (u32 j = 0; j < d.n_aggs; ++j)
             if (d.a[j].kind == CHGPU_AGG_ANY && t.words[(u64)d.a[j].word * stride + slot] == claim)
                 t.words[(u64)(d.a[j].word + 1) * stride + slot] = load_arg_bits(d.a[j].ptr, d.a[j].arg_type, i);
+    }
+}
+
+// ---- argMin / argMax: the claim and resolve passes ----
+// "The earliest row among those that hold the extremum" cannot be folded in one atomic: a group's extremum is only known once every row
+// of the block has been seen.  The block pass (add_row) raised every val key; after that kernel boundary the val keys are final for the
+// block, and PASS 2 lets every row whose key EQUALS its group's claim with agg_arg_row_claim(ordinal) under an unsigned max; after the
+// next boundary the claims are final and PASS 3 lets the row a claim names store its arg.  A claim of an earlier block (or of a merge, ~0) beats every
+// row of this block, so a row that only equals the extremum changes nothing; a raised extremum starts from the block's sentinel, which
+// every row of the block beats.
+// The state of `key` as the block pass left it: its cell, or in a find-only block the overflow row for a key the table lacks (no state
+// when there is no overflow row: the row was dropped).  base[w * stride] is table word w.
+__device__ __forceinline__ bool agg_state_of(const AggTable & t, u64 key, u64 *& base, u64 & stride)
+{
+    const u64 slot = table_find(t, key);
+    if (slot == AGG_SLOT_MISS)
+    {
+        if (!t.find_only || !t.ovf)
+            return false; // (not find-only: every row of the block was placed before this pass, not reached)
+        base = t.ovf;
+        stride = 1;
+        return true;
+    }
+    base = t.words + slot;
+    stride = t.capacity + 1;
+    return true;
+}
+// PASS 2: `claim` under an unsigned max when the state's val key is `key`; PASS 3: the state's arg from `arg_bits` when its claim is
+// `claim`, and the claim itself replaced by `settled` when that is non-zero (merges: ~0).  st = the state's val key word.
+template <int PASS>
+__device__ __forceinline__ void agg_arg_claim_or_resolve(u64 * st, u64 stride, u64 key, u64 claim, u64 arg_bits, u64 settled)
+{
+    if (*st != key)
+        return;
+    unsigned long long * c = (unsigned long long *)(st + stride);
+    if (PASS == 2)
+    {
+        // (the load keeps a group of equal rows from queueing on one address: most of them see a claim above their own)
+        if (__hip_atomic_load(c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < claim)
+            __hip_atomic_fetch_max(c, (unsigned long long)claim, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    else if (*c == claim)
+    {
+        st[2 * stride] = arg_bits;
+        if (settled)
+            *c = settled; // only the winner writes, and no other claim of this pass equals either value
+    }
+}
+template <int PASS>
+__global__ __launch_bounds__(AGG_THREADS) void k_agg_arg_rows(AggTable t, AggDesc d, const void * __restrict__ keys, int key_type, u64 row_begin, u64 n)
+{
+    for (u64 r = (u64)blockIdx.x * AGG_THREADS + threadIdx.x; r < n; r += (u64)gridDim.x * AGG_THREADS)
+    {
+        const u64 i = row_begin + r;
+        u64 * base;
+        u64 stride;
+        if (!agg_state_of(t, load_key_zext(keys, key_type, i), base, stride))
+            continue;
+        for (u32 j = 0; j < d.n_aggs; ++j)
+        {
+            const AggArg & a = d.a[j];
+            if (a.kind != CHGPU_AGG_ARG_MIN && a.kind != CHGPU_AGG_ARG_MAX)
+                continue;
+            const u64 k = agg_val_key(load_arg_bits(a.val, a.val_type, i), a.val_type);
+            agg_arg_claim_or_resolve<PASS>(base + (u64)a.word * stride, stride, a.kind == CHGPU_AGG_ARG_MAX ? k : ~k, agg_arg_row_claim(d.row_seq + i),
+                                           PASS == 3 ? load_arg_bits(a.ptr, a.arg_type, i) : 0, 0);
+        }
+    }
+}
+// The same two passes of a merge, over the source tuples k_agg_tuples folded in: tuple i claims with AGG_MERGE_CLAIM_TOP - i.
+template <int PASS>
+__global__ __launch_bounds__(AGG_THREADS) void k_agg_arg_tuples(AggTable t, u32 n_words, u32 word_arg, const u64 * __restrict__ src_keys,
+                                                                const u64 * __restrict__ src_words, u64 src_stride, u64 n, int skip_zero_keys, u64 zero_slot_index)
+{
+    for (u64 i = (u64)blockIdx.x * AGG_THREADS + threadIdx.x; i < n; i += (u64)gridDim.x * AGG_THREADS)
+    {
+        u64 key = src_keys[i];
+        const bool is_zero_cell = (i == zero_slot_index);
+        if (is_zero_cell)
+            key = 0;
+        if (skip_zero_keys && key == 0 && !is_zero_cell)
+            continue;
+        u64 * base;
+        u64 stride;
+        if (!agg_state_of(t, key, base, stride))
+            continue;
+        for (u32 w = 0; w + 2 < n_words; ++w)
+            if (((word_arg >> w) & 1) && src_words[(u64)(w + 1) * src_stride + i] != 0)
+                agg_arg_claim_or_resolve<PASS>(base + (u64)w * stride, stride, src_words[(u64)w * src_stride + i], AGG_MERGE_CLAIM_TOP - i,
+                                               src_words[(u64)(w + 2) * src_stride + i], ~0ull);
     }
 }
 
@@ -2464,7 +2673,7 @@ static int agg_fx_prepare_block(chgpu_agg * a, const chgpu_col * const * arg_col
             continue;
         u32 e = 0, em = 2047;
         bool bad = false;
-        CHGPU_TRY(agg_fx_stats(a->ctx, arg_cols[j]->data, a->arg_types[j], row_begin, n, &e, &em, &bad));
+        CHGPU_TRY(agg_fx_stats(a->ctx, arg_cols[a->slot[j]]->data, a->arg_types[j], row_begin, n, &e, &em, &bad));
         if (bad)
             return agg_fx_to_plain(a);
         emax = e > emax ? e : emax;
@@ -2565,7 +2774,8 @@ static size_t agg_part_cell_bytes(const chgpu_agg * a, int key_type, u64 n, u32 
             continue;
         const u32 w = a->word_off[j];
         const bool pair = a->kinds[j] == CHGPU_AGG_AVG || a->kinds[j] == CHGPU_AGG_ANY;
-        words += 1 + (pair ? 1 : 0) + ((a->word_fx >> w) & 1);
+        const bool triple = a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX;
+        words += 1 + (pair ? 1 : 0) + (triple ? 2 : 0) + ((a->word_fx >> w) & 1);
         if (a->kinds[j] == CHGPU_AGG_COUNT)
             cnt32 |= c32 << w;
         else if (a->kinds[j] == CHGPU_AGG_AVG)
@@ -3358,8 +3568,8 @@ static int agg_add_block_materialised(chgpu_agg * a, const chgpu_col * key_col, 
 {
     chgpu_ctx * ctx = a->ctx;
     const u64 n = row_end - row_begin;
-    const chgpu_col * src[1 + AGG_MAX_AGGS];
-    chgpu_col * views[2 + AGG_MAX_AGGS] = {};
+    const chgpu_col * src[1 + 2 * AGG_MAX_AGGS];
+    chgpu_col * views[2 + 2 * AGG_MAX_AGGS] = {};
     u32 m = 0;
     int rc = CHGPU_OK;
     auto view = [&](const chgpu_col * c) {
@@ -3370,14 +3580,15 @@ static int agg_add_block_materialised(chgpu_agg * a, const chgpu_col * key_col, 
     };
     view(filter);
     view(key_col);
-    u32 arg_slot[AGG_MAX_AGGS];
+    u32 data_of[2 * AGG_MAX_AGGS]; // by argument slot (an argMin / argMax carries both its columns)
     for (u32 j = 0; j < a->n_aggs; ++j)
         if (a->kinds[j] != CHGPU_AGG_COUNT)
-        {
-            arg_slot[j] = m - 1; // index among the data columns (key = 0)
-            view(arg_cols[j]);
-        }
-    chgpu_col * outs[1 + AGG_MAX_AGGS] = {};
+            for (u32 sl = a->slot[j]; sl < (j + 1 < a->n_aggs ? a->slot[j + 1] : a->n_slots); ++sl)
+            {
+                data_of[sl] = m - 1; // index among the data columns (key = 0)
+                view(arg_cols[sl]);
+            }
+    chgpu_col * outs[1 + 2 * AGG_MAX_AGGS] = {};
     u64 kept = 0;
     const u32 n_data = m ? m - 1 : 0;
     if (rc == CHGPU_OK)
@@ -3388,10 +3599,11 @@ static int agg_add_block_materialised(chgpu_agg * a, const chgpu_col * key_col, 
     }
     if (rc == CHGPU_OK && kept)
     {
-        const chgpu_col * fargs[AGG_MAX_AGGS] = {};
+        const chgpu_col * fargs[2 * AGG_MAX_AGGS] = {};
         for (u32 j = 0; j < a->n_aggs; ++j)
             if (a->kinds[j] != CHGPU_AGG_COUNT)
-                fargs[j] = outs[arg_slot[j]];
+                for (u32 sl = a->slot[j]; sl < (j + 1 < a->n_aggs ? a->slot[j + 1] : a->n_slots); ++sl)
+                    fargs[sl] = outs[data_of[sl]];
         rc = agg_add_block_impl(a, outs[0], fargs, 0, kept, nullptr);
     }
     for (u32 k = 0; k < n_data; ++k)
@@ -3419,8 +3631,42 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
     for (u32 j = 0; j < a->n_aggs; ++j)
     {
         u64 * st = &a->host_words[a->word_off[j]];
+        const chgpu_col * col = a->kinds[j] == CHGPU_AGG_COUNT ? nullptr : arg_cols[a->slot[j]];
         if (a->kinds[j] == CHGPU_AGG_COUNT)
             st[0] += kept;
+        else if (a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX)
+        {
+            // the block's lexicographic extremum of (val key, ~ordinal): the largest val key, its first holder, that row's arg
+            if (kept == 0 || n == 0)
+                continue;
+            const chgpu_col * val = arg_cols[a->slot[j] + 1];
+            const int is_min = a->kinds[j] == CHGPU_AGG_ARG_MIN ? 1 : 0;
+            void * scratch = nullptr;
+            CHGPU_TRY(chgpu_scratch(ctx, 256, &scratch));
+            unsigned long long * dev = (unsigned long long *)scratch;
+            const u8 * cond = filter ? (const u8 *)filter->data : nullptr;
+            const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
+            u64 best = 0, first = ~0ull, bits = 0;
+            CHGPU_HIP(hipMemsetAsync(dev, 0, 8, ctx->stream));
+            hipLaunchKernelGGL(k_nokey_extremum, dim3(grid), dim3(256), 0, ctx->stream, (const void *)val->data, a->val_types[j], row_begin, n, cond, is_min, 1, dev);
+            CHGPU_HIP(hipGetLastError());
+            CHGPU_TRY(chgpu_read_back(ctx, dev, &best, 8));
+            ctx->counters[6] += 1;
+            if (st[1] != 0 && best <= st[0])
+                continue; // setIfGreater / setIfSmaller: only a strictly better val replaces a state that has a value
+            CHGPU_HIP(hipMemsetAsync(dev, 0xFF, 8, ctx->stream));
+            hipLaunchKernelGGL(k_nokey_first_holder, dim3(grid), dim3(256), 0, ctx->stream, (const void *)val->data, a->val_types[j], row_begin, n, cond, is_min, best, dev);
+            CHGPU_HIP(hipGetLastError());
+            CHGPU_TRY(chgpu_read_back(ctx, dev, &first, 8));
+            CHGPU_REQUIRE(first != ~0ull, CHGPU_ERR_LOGICAL, "argMin / argMax: no row holds the block's extremum");
+            hipLaunchKernelGGL(k_nokey_load, dim3(1), dim3(64), 0, ctx->stream, (const void *)col->data, a->arg_types[j], row_begin + first, (u64 *)dev);
+            CHGPU_HIP(hipGetLastError());
+            CHGPU_TRY(chgpu_read_back(ctx, dev, &bits, 8));
+            ctx->counters[6] += 2;
+            st[0] = best;
+            st[1] = agg_arg_row_claim(a->any_seq + first);
+            st[2] = bits;
+        }
         else if (a->kinds[j] == CHGPU_AGG_MIN || a->kinds[j] == CHGPU_AGG_MAX || a->kinds[j] == CHGPU_AGG_ANY)
         {
             if (kept == 0 || n == 0)
@@ -3433,8 +3679,8 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
             if (a->kinds[j] != CHGPU_AGG_ANY)
             {
                 CHGPU_HIP(hipMemsetAsync(dev, 0, 8, ctx->stream));
-                hipLaunchKernelGGL(k_nokey_extremum, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const void *)arg_cols[j]->data, a->arg_types[j], row_begin, n, cond,
-                                   a->kinds[j] == CHGPU_AGG_MIN ? 1 : 0, dev);
+                hipLaunchKernelGGL(k_nokey_extremum, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const void *)col->data, a->arg_types[j], row_begin, n, cond,
+                                   a->kinds[j] == CHGPU_AGG_MIN ? 1 : 0, 0, dev);
                 ctx->counters[6] += 1;
                 CHGPU_HIP(hipGetLastError());
                 CHGPU_TRY(chgpu_read_back(ctx, dev, &v, 8));
@@ -3448,7 +3694,7 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
                 CHGPU_TRY(chgpu_read_back(ctx, dev, &v, 8));
                 if (v != ~0ull)
                 {
-                    hipLaunchKernelGGL(k_nokey_load, dim3(1), dim3(64), 0, ctx->stream, (const void *)arg_cols[j]->data, a->arg_types[j], row_begin + v, (u64 *)dev);
+                    hipLaunchKernelGGL(k_nokey_load, dim3(1), dim3(64), 0, ctx->stream, (const void *)col->data, a->arg_types[j], row_begin + v, (u64 *)dev);
                     CHGPU_HIP(hipGetLastError());
                     u64 bits = 0;
                     CHGPU_TRY(chgpu_read_back(ctx, dev, &bits, 8));
@@ -3461,9 +3707,9 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
         else
         {
             if (filter)
-                CHGPU_TRY(chgpu_sum_add_many_conditional(ctx, arg_cols[j], filter, row_begin, row_end, st));
+                CHGPU_TRY(chgpu_sum_add_many_conditional(ctx, col, filter, row_begin, row_end, st));
             else
-                CHGPU_TRY(chgpu_sum_add_many(ctx, arg_cols[j], row_begin, row_end, st));
+                CHGPU_TRY(chgpu_sum_add_many(ctx, col, row_begin, row_end, st));
             if (a->kinds[j] == CHGPU_AGG_AVG)
                 st[1] += kept;
         }
@@ -3640,6 +3886,7 @@ static int agg_add_block_planned(chgpu_agg * a, const chgpu_col * key_col, const
     {
         // one emplace + one atomic per state word and row
         d.row_seq = a->any_seq - row_begin; // any(): row i of the columns is the (any_seq + i - row_begin)-th row of the aggregation
+        d.arg_sentinel = agg_arg_row_claim(a->any_seq + n);
         hipLaunchKernelGGL(k_agg_rows_direct<AGG_MODE_ALL>, dim3(rows_grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n, pending);
     }
     ctx->counters[6] += 1;
@@ -3650,8 +3897,17 @@ static int agg_add_block_planned(chgpu_agg * a, const chgpu_col * key_col, const
         hipLaunchKernelGGL(k_agg_any_resolve, dim3(rows_grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n);
         ctx->counters[6] += 1;
         CHGPU_HIP(hipGetLastError());
-        a->any_seq += n;
     }
+    if (a->word_arg)
+    {
+        // the claim and resolve passes, each behind a kernel boundary (the finish rounds left every row placed and every val key final)
+        hipLaunchKernelGGL(k_agg_arg_rows<2>, dim3(rows_grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n);
+        hipLaunchKernelGGL(k_agg_arg_rows<3>, dim3(rows_grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n);
+        ctx->counters[6] += 2;
+        CHGPU_HIP(hipGetLastError());
+    }
+    if (a->word_any || a->word_arg)
+        a->any_seq += n;
     return CHGPU_OK;
 }
 
@@ -3673,10 +3929,15 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
     {
         if (a->kinds[j] == CHGPU_AGG_COUNT)
             continue;
-        CHGPU_REQUIRE(arg_cols && arg_cols[j], CHGPU_ERR_BAD_ARGUMENTS, "argument column %u is NULL", j);
-        CHGPU_REQUIRE(arg_cols[j]->type == a->arg_types[j], CHGPU_ERR_BAD_ARGUMENTS, "argument column %u has type %d, expected %d", j, arg_cols[j]->type, a->arg_types[j]);
-        CHGPU_REQUIRE(row_end <= arg_cols[j]->rows, CHGPU_ERR_SIZES_MISMATCH, "argument column %u has %llu rows, block ends at %llu", j,
-                      (unsigned long long)arg_cols[j]->rows, (unsigned long long)row_end);
+        const bool arg_pair = a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX;
+        for (u32 sl = a->slot[j]; sl < a->slot[j] + (arg_pair ? 2u : 1u); ++sl) // (without the two-argument kinds slot j is aggregate j)
+        {
+            const int want = sl == a->slot[j] ? a->arg_types[j] : a->val_types[j];
+            CHGPU_REQUIRE(arg_cols && arg_cols[sl], CHGPU_ERR_BAD_ARGUMENTS, "argument column %u is NULL", sl);
+            CHGPU_REQUIRE(arg_cols[sl]->type == want, CHGPU_ERR_BAD_ARGUMENTS, "argument column %u has type %d, expected %d", sl, arg_cols[sl]->type, want);
+            CHGPU_REQUIRE(row_end <= arg_cols[sl]->rows, CHGPU_ERR_SIZES_MISMATCH, "argument column %u has %llu rows, block ends at %llu", sl,
+                          (unsigned long long)arg_cols[sl]->rows, (unsigned long long)row_end);
+        }
     }
     if (a->key_type < 0)
         return agg_add_nokey(a, arg_cols, row_begin, row_end, filter);
@@ -3761,7 +4022,19 @@ static int agg_merge_tuples(chgpu_agg * a, const u64 * src_keys, const u64 * src
         AggCtrl c;
         CHGPU_TRY(agg_read_ctrl(a, &c));
         if (!c.overflow)
+        {
+            if (a->word_arg)
+            {
+                // argMin / argMax: every val key is final; the source states that hold one claim, then the winner stores its arg
+                hipLaunchKernelGGL(k_agg_arg_tuples<2>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, a->n_words, a->word_arg, src_keys, src_words, src_stride, n,
+                                   skip_zero_keys, zero_slot_index);
+                hipLaunchKernelGGL(k_agg_arg_tuples<3>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, a->n_words, a->word_arg, src_keys, src_words, src_stride, n,
+                                   skip_zero_keys, zero_slot_index);
+                ctx->counters[6] += 2;
+                CHGPU_HIP(hipGetLastError());
+            }
             return CHGPU_OK;
+        }
         CHGPU_TRY(agg_grow(a, c.n_groups, c.has_zero != 0));
         hipLaunchKernelGGL(k_agg_tuples<AGG_MODE_PENDING>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, a->n_words, a->word_is_f64, agg_fx_words(a),
                            src_keys, src_words, src_stride, n, skip_zero_keys, zero_slot_index, 1, pending);
@@ -3782,6 +4055,18 @@ static u32 agg_merge_host_word(chgpu_agg * dst, u32 w, const u64 * src_words)
             dst->host_words[w + 1] = src_words[w + 1];
         }
         return 2;
+    }
+    if ((dst->word_arg >> w) & 1)
+    {
+        // a source that has a value replaces a state without one, or one whose val is strictly worse; {val, arg} move together and
+        // the claim becomes ~0: older than every row to come
+        if (src_words[w + 1] != 0 && (dst->host_words[w + 1] == 0 || src_words[w] > dst->host_words[w]))
+        {
+            dst->host_words[w] = src_words[w];
+            dst->host_words[w + 1] = ~0ull;
+            dst->host_words[w + 2] = src_words[w + 2];
+        }
+        return 3;
     }
     if ((dst->word_is_f64 >> (16 + w)) & 1)
         dst->host_words[w] = src_words[w] > dst->host_words[w] ? src_words[w] : dst->host_words[w]; // min / max order keys
@@ -3885,6 +4170,12 @@ static int agg_fold_overflow_words(chgpu_agg * dst, const u64 * in)
             if (o[w] == 0 && in[w] != 0) // changeFirstTime: a state that has a value keeps it
                 o[w] = in[w], o[w + 1] = in[w + 1];
             ++w;
+        }
+        else if ((dst->word_arg >> w) & 1)
+        {
+            if (in[w + 1] != 0 && (o[w + 1] == 0 || in[w] > o[w])) // as agg_merge_host_word
+                o[w] = in[w], o[w + 1] = ~0ull, o[w + 2] = in[w + 2];
+            w += 2;
         }
         else if ((dst->word_is_f64 >> (16 + w)) & 1)
             o[w] = in[w] > o[w] ? in[w] : o[w];
@@ -4241,9 +4532,11 @@ extern "C" int chgpu_agg_overflow_row(chgpu_agg * a, int final, chgpu_col ** col
                 }
                 default:
                 {
-                    // min / max / any: the value in the argument's type; the type's default when no row reached it
+                    // min / max / any / argMin / argMax: the value in the argument's type; the type's default when no row reached it
                     type = at;
-                    if (pub[w])
+                    if (a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX)
+                        v = pub[w + 1] ? pub[w + 2] : 0; // {val key, has, arg bits}
+                    else if (pub[w])
                         v = a->kinds[j] == CHGPU_AGG_ANY ? pub[w + 1] : agg_order_key_inverse(a->kinds[j] == CHGPU_AGG_MIN ? ~pub[w] : pub[w], at);
                     if (at == CHGPU_F32)
                     {
@@ -4520,8 +4813,10 @@ extern "C" int chgpu_agg_finalize(chgpu_agg * a, chgpu_col ** keys_out, chgpu_co
             res_cols[j] = words[w];
             words[w] = nullptr;
         }
-        else if (a->kinds[j] == CHGPU_AGG_MIN || a->kinds[j] == CHGPU_AGG_MAX || a->kinds[j] == CHGPU_AGG_ANY)
+        else if (a->kinds[j] == CHGPU_AGG_MIN || a->kinds[j] == CHGPU_AGG_MAX || a->kinds[j] == CHGPU_AGG_ANY || a->kinds[j] == CHGPU_AGG_ARG_MIN ||
+                 a->kinds[j] == CHGPU_AGG_ARG_MAX)
         {
+            const bool arg_pair = a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX;
             // insertResultInto: the value itself, in the argument's type (AggregateFunctionsMinMax.cpp)
             chgpu_col * r = nullptr;
             rc = chgpu_col_new(ctx, a->arg_types[j], n, &r);
@@ -4531,10 +4826,10 @@ extern "C" int chgpu_agg_finalize(chgpu_agg * a, chgpu_col ** keys_out, chgpu_co
                 CHGPU_HIP(hipMemsetAsync(r->data, 0, chgpu_type_size(a->arg_types[j]), ctx->stream)); // a state without a value: the type's default
             else if (n)
             {
-                // (any: the value word, as loaded -- no order key to undo)
+                // (any, argMin / argMax: the value word, as loaded -- no order key to undo; a cell only a value-less imported state reached holds 0)
                 hipLaunchKernelGGL(k_extremum_decode, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream,
-                                   (const u64 *)words[a->kinds[j] == CHGPU_AGG_ANY ? w + 1 : w]->data, n, a->arg_types[j],
-                                   a->kinds[j] == CHGPU_AGG_MIN ? 1 : a->kinds[j] == CHGPU_AGG_ANY ? 2 : 0, r->data);
+                                   (const u64 *)words[arg_pair ? w + 2 : a->kinds[j] == CHGPU_AGG_ANY ? w + 1 : w]->data, n, a->arg_types[j],
+                                   a->kinds[j] == CHGPU_AGG_MIN ? 1 : (a->kinds[j] == CHGPU_AGG_ANY || arg_pair) ? 2 : 0, r->data);
                 ctx->counters[6] += 1;
             }
             res_cols[j] = r;

@@ -860,12 +860,32 @@ private:
     ColumnPtr cached_remap;
 };
 
-/// AggregateDescription (src/Interpreters/AggregateDescription.h): function + argument position.
+/// AggregateDescription (src/Interpreters/AggregateDescription.h): function + argument position(s).  argMin / argMax take two
+/// arguments: `argument` is arg (the column the result comes from), `argument2` is val (the column that is compared).
 struct AggregateDescription
 {
     int kind;              // CHGPU_AGG_*
     int argument_type;     // CHGPU_* (ignored for count)
     size_t argument = 0;   // position in the chunk
+    int argument2_type = CHGPU_U64; // argMin / argMax: val's type
+    size_t argument2 = 0;           // ... and its position in the chunk
+
+    bool twoArguments() const { return kind == CHGPU_AGG_ARG_MIN || kind == CHGPU_AGG_ARG_MAX; }
+    /// 8-byte public state words: avg numerator + denominator; any claim + value; argMin / argMax val word + has + arg bits
+    size_t stateWords() const { return twoArguments() ? 3 : (kind == CHGPU_AGG_AVG || kind == CHGPU_AGG_ANY) ? 2 : 1; }
+    /// the C ABI's argument slots of this aggregate: one per argument (arg then val), appended to `types`
+    void appendArgumentTypes(std::vector<int> & types) const
+    {
+        types.push_back(argument_type);
+        if (twoArguments())
+            types.push_back(argument2_type);
+    }
+    void appendArgumentColumns(const Columns & columns, std::vector<const chgpu_col *> & args) const
+    {
+        args.push_back(kind == CHGPU_AGG_COUNT ? nullptr : columns.at(argument)->handle());
+        if (twoArguments())
+            args.push_back(columns.at(argument2)->handle());
+    }
 };
 
 /// Aggregator::Params' GROUP BY limits (max_rows_to_group_by, group_by_overflow_mode, overflow_row); 0 rows = no limit
@@ -888,7 +908,7 @@ public:
         for (auto & a : aggregates)
         {
             kinds.push_back(a.kind);
-            types.push_back(a.argument_type);
+            a.appendArgumentTypes(types);
         }
         check(chgpu_agg_create(ctx->get(), key_type, static_cast<uint32_t>(aggregates.size()), kinds.data(), types.data(), size_hint, &h));
         if (limits.any())
@@ -910,7 +930,7 @@ public:
     {
         std::vector<const chgpu_col *> args;
         for (auto & a : aggregates)
-            args.push_back(a.kind == CHGPU_AGG_COUNT ? nullptr : columns.at(a.argument)->handle());
+            a.appendArgumentColumns(columns, args);
         const chgpu_col * key = key_position ? columns.at(*key_position)->handle() : nullptr;
         if (!limits.any())
         {
@@ -1553,8 +1573,8 @@ public:
         for (auto & a : aggregates)
         {
             kinds.push_back(a.kind);
-            types.push_back(a.argument_type);
-            n_words += (a.kind == CHGPU_AGG_AVG || a.kind == CHGPU_AGG_ANY) ? 2 : 1; // avg: numerator + denominator; any: claim + value
+            a.appendArgumentTypes(types);
+            n_words += a.stateWords();
         }
         check(chgpu_agg_create(ctx->get(), key_type, static_cast<uint32_t>(aggregates.size()), kinds.data(), types.data(), size_hint, &local));
     }
@@ -1569,7 +1589,7 @@ public:
     {
         std::vector<const chgpu_col *> args;
         for (auto & a : aggregates)
-            args.push_back(a.kind == CHGPU_AGG_COUNT ? nullptr : columns.at(a.argument)->handle());
+            a.appendArgumentColumns(columns, args);
         check(chgpu_agg_add_block(local, columns.at(key_position)->handle(), args.data(), row_begin, row_end));
         return true;
     }
@@ -1650,8 +1670,8 @@ public:
         for (auto & a : aggregates)
         {
             kinds.push_back(a.kind);
-            types.push_back(a.argument_type);
-            n_words += (a.kind == CHGPU_AGG_AVG || a.kind == CHGPU_AGG_ANY) ? 2 : 1; // avg: numerator + denominator; any: claim + value
+            a.appendArgumentTypes(types);
+            n_words += a.stateWords();
         }
     }
 

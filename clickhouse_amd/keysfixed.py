@@ -86,10 +86,12 @@ class KeysFixedAggregator:
     def execute_on_block(self, key_cols, args, row_begin: int = 0, row_end: int | None = None) -> bool:
         # once no_more_keys is set the dictionary stops growing: an absent key gets 0xFFFFFFFF, which the table lacks (a miss)
         ids = self.dict.encode(key_cols, not self.inner.no_more_keys, row_begin, row_end)
-        acols = [self.ctx.column(a) if a is not None else None for a in args]
+        # (an argMin / argMax entry is an (arg, val) pair and stays one)
+        each = lambda f, a: tuple(f(x) for x in a) if isinstance(a, tuple) else f(a) if a is not None else None
+        acols = [each(self.ctx.column, a) for a in args]
         if row_begin or row_end is not None:
             n = ids.size()
-            acols = [a.cut(row_begin, n) if a is not None else None for a in acols]
+            acols = [each(lambda c: c.cut(row_begin, n), a) for a in acols]
         return self.inner.execute_on_block(ids, acols)
 
     def overflow_row(self, final: bool = True):

@@ -74,7 +74,26 @@ enum { CHGPU_AGG_COUNT = 0, CHGPU_AGG_SUM = 1, CHGPU_AGG_AVG = 2,
        /* any(x): the value of the group's FIRST row in the order the blocks were added (AggregateFunctionAny.cpp: setIfFirst; merges keep the
           state that already has a value -- changeFirstTime).  Two 8-byte state words {claim, value}: the claim names the earliest row, so the
           result does not depend on the order the hardware serves the rows in. */
-       CHGPU_AGG_ANY = 5 };
+       CHGPU_AGG_ANY = 5,
+       /* argMin(arg, val) / argMax(arg, val) over numeric columns (AggregateFunctionArgMinMax.h; SingleValueData.cpp setIfSmaller /
+          setIfGreater): the `arg` of the FIRST row, in the order rows were added over all blocks, whose `val` is the group's minimum /
+          maximum -- a later row replaces the state only when its val is strictly smaller / greater.  The result has arg's type and arg's
+          bits untouched (Float32 as any() treats it).
+          TWO ARGUMENTS: arg_types (chgpu_agg_create) and every arg_cols array (add_block, add_block_filtered, execute_on_block) are indexed
+          by ARGUMENT SLOT.  These kinds own two consecutive slots, arg then val; every other kind owns one, so with none of these kinds
+          present slot j is aggregate j.  arg and val may each be any of the ten column types.
+          THREE 8-byte public state words per aggregate, in table order {val word, has, arg bits}: val word is val's order key (complemented for
+          argMin, as min / max export theirs), has is 0 for "no value" and non-zero otherwise -- an import reads any non-zero value as "has
+          a value, older than every row to come" -- and arg bits are as any() exports its value.  A merge keeps the destination's {val, arg}
+          unless the source's val is strictly greater (argMax) / smaller (argMin); equal vals keep the destination's, and a row that
+          later only equals a merged-in extremum loses to it.  A state without a value (an overflow row nobody reached, no key and no
+          rows) loses every merge and finalizes to arg's default, 0.
+          Zeros: -0.0 and +0.0 in val are equal to the reference's comparison, so the val order key folds the zero's sign away: such rows
+          tie and the first wins (min / max keep their own key: they return the value).
+          NaN in val takes the place it has in the min / max order key (above +inf / below -inf by its sign), where the reference's answer
+          depends on which row came first -- the same documented deviation as for min / max.
+          Never through chgpu_agg_serialize_states / deserialize_states. */
+       CHGPU_AGG_ARG_MIN = 6, CHGPU_AGG_ARG_MAX = 7 };
 
 /* ---- JoinKind / JoinStrictness subset (src/Core/Joins.h) ---- */
 enum { CHGPU_JOIN_INNER = 0, CHGPU_JOIN_LEFT = 1, CHGPU_JOIN_RIGHT = 2, CHGPU_JOIN_FULL = 3 }; /* RIGHT / FULL: strictness ALL only */
@@ -521,7 +540,7 @@ int chgpu_like_compile(const void * pattern, uint64_t pattern_bytes, chgpu_like_
 int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, const int * agg_kinds, const int * arg_types,
                      uint64_t size_hint, chgpu_agg ** out);
 /* executeOnBlock over rows [row_begin,row_end) of the key column and the argument columns (arg_cols[j] may be NULL
-   for count()) */
+   for count()).  arg_cols is indexed by argument slot: see CHGPU_AGG_ARG_MIN for aggregates with two arguments. */
 int chgpu_agg_add_block(chgpu_agg * agg, const chgpu_col * key_col, const chgpu_col * const * arg_cols,
                         uint64_t row_begin, uint64_t row_end);
 /* The same over the rows of [row_begin,row_end) whose filter byte is non-zero -- a FilterTransform (FilterTransform.cpp:136-256)
