@@ -19,6 +19,7 @@ OVERFLOW_THROW, OVERFLOW_BREAK, OVERFLOW_ANY = 0, 1, 2   # group_by_overflow_mod
 I64, U32, U64, F64, U8, I32, U16, I16, I8, F32 = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9
 EQ, NE, LT, GT, LE, GE = 0, 1, 2, 3, 4, 5
 AGG_COUNT, AGG_SUM, AGG_AVG, AGG_MIN, AGG_MAX, AGG_ANY, AGG_ARG_MIN, AGG_ARG_MAX = 0, 1, 2, 3, 4, 5, 6, 7
+AGG_COND_NONE, AGG_COND_IF, AGG_COND_NULL = 0, 1, 2   # chgpu_agg_set_conditions: the -If combinator / a Nullable argument
 ASOF_LESS, ASOF_GREATER, ASOF_LESS_OR_EQUALS, ASOF_GREATER_OR_EQUALS = 1, 2, 3, 4
 JOIN_INNER, JOIN_LEFT, JOIN_RIGHT, JOIN_FULL = 0, 1, 2, 3
 STRICT_ANY, STRICT_ALL, STRICT_SEMI, STRICT_ANTI = 0, 1, 2, 3
@@ -121,6 +122,9 @@ SIGNATURES = {
     "chgpu_agg_merge_limited": (_i, [_vp, _vp, C.POINTER(_i), C.POINTER(_i)]),
     "chgpu_agg_merge_states_limited": (_i, [_vp, _vp, _pp, _u64, _i, C.POINTER(_i), C.POINTER(_i)]),
     "chgpu_agg_overflow_row": (_i, [_vp, _i, _pp, C.POINTER(_i)]),
+    "chgpu_agg_set_conditions": (_i, [_vp, C.POINTER(_i)]),
+    "chgpu_agg_execute_on_block_conditional": (_i, [_vp, _vp, _pp, _pp, _u64, _u64, _vp, C.POINTER(_i), C.POINTER(_i)]),
+    "chgpu_agg_finalize_nullable": (_i, [_vp, _pp, _pp, _pp, _pu64]),
     "chgpu_join_create": (_i, [_vp, _i, _i, _i, _i, _u64, _pp]),
     "chgpu_join_add_block": (_i, [_vp, _vp, _vp, _vp, C.POINTER(_u32)]),
     "chgpu_join_finish_build": (_i, [_vp]),

@@ -21,6 +21,8 @@
 //               RANGE mode straight over the source columns (k_agg_rows_lds is the older generic form of it);
 //   PARTITIONED k_gb_hist -> scan -> k_gb_scatter -> k_gb_units -> k_agg_part_lds, one or two partitioning levels;
 //   DIRECT      k_agg_rows_direct, one HBM atomic per row and state word.
+// Per-function row masks (the -If combinator, Nullable arguments: chgpu_agg_set_conditions) are tested where a row's
+// contribution is made -- add_row for every per-row path, the update loops of the two LDS-staged kernels -- after the row claimed its cell.
 // Rows that would push the table over max fill are marked in a pending bitmap; the host grows the table (rehash) and
 // re-runs only those rows, which is the reference's resize-on-overflow (HashTable.h:921-944) restructured for a device
 // that cannot realloc inside a kernel.
@@ -65,6 +67,10 @@ struct AggArg
     int val_type;
     u32 word;         // first state word
     u32 pre;          // partitioned path: index of this argument's word column in the partition buffers
+    // -If / -Null combinators: the function sees row i only when (AggDesc::cond[cond][i] != 0) == cond_want
+    signed char cond;       // index into AggDesc::cond, -1 = unconditioned
+    unsigned char cond_want; // 1: -If (the byte is non-zero), 0: Nullable argument (the null-map byte is zero)
+    unsigned char seen;      // 1: word + 1 counts the rows that reached the function (conditioned min / max, NULL-mode sum)
 };
 
 struct AggDesc
@@ -87,6 +93,9 @@ struct AggDesc
     // A pass over a SUBSET of the functions (one argument word at a time through the tile-sorted plan) numbers its state words locally
     // (0 .. n_words - 1: the LDS cells hold only those) and finds the table's words through this map; the identity otherwise.
     unsigned char word_map[AGG_MAX_WORDS];
+    // the distinct condition columns of the block (UInt8, indexed like the arguments); n_conds = 0: no function is conditioned
+    u32 n_conds;
+    const u8 * cond[AGG_MAX_AGGS];
 };
 
 struct AggTable
@@ -149,6 +158,12 @@ struct chgpu_agg
     bool started = false;          // some block or merge has reached the aggregation
     void * ovf_mem = nullptr;      // the overflow row's state words on the device (AGG_MAX_WORDS x 8 B), from the first call with overflow_row on
     size_t ovf_class = 0;
+    // -If / -Null combinators (chgpu_agg_set_conditions): CHGPU_AGG_COND_* per function; word_seen: bit w = word w counts the rows that
+    // reached the function whose value word(s) end at w - 1
+    int cond_modes[AGG_MAX_AGGS] = {0};
+    bool conditioned = false;
+    u32 word_seen = 0;
+    const chgpu_col * const * block_conds = nullptr; // the condition columns of the block being added ([n_aggs], set for the call's duration)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -368,7 +383,8 @@ __device__ __forceinline__ u64 table_emplace(const AggTable & t, u64 key, bool s
 // bit flipped; floats: the IEEE total-order fold, Float32 after its exact widening) -- for max, and its complement for min, combined with
 // an unsigned atomic max.  A freshly zeroed cell is then the identity of both, exactly like the sums' zero: the rehash, the merges and the
 // exports move min / max words with no special case but the combining operation.  (A group only exists because a row created it, so
-// `has()` is always true for it.)  NaNs take their total-order place -- above +inf / below -inf by sign -- where the reference's answer
+// `has()` is always true for it.  Under a per-function condition that no longer holds: a conditioned min / max carries a `seen` word, the
+// number of rows that reached it, and finalize gives the type's default when it is 0 -- DESIGN.md §4.16.2.)  NaNs take their total-order place -- above +inf / below -inf by sign -- where the reference's answer
 // depends on which row came first (`NaN < x` is false either way).
 __device__ __host__ __forceinline__ u64 agg_order_key(u64 bits, int type)
 {
@@ -430,13 +446,30 @@ struct GlobalSink
 };
 
 // add row i's contribution of every aggregate to the group's state in `sink` (IAggregateFunction::add per function)
+// Which condition columns hold a non-zero byte in row i (bit c: AggDesc::cond[c]): every distinct column is loaded once per row,
+// however many functions share it.  (Any non-zero byte counts: 2 and 255 as much as 1.)
+__device__ __forceinline__ u32 cond_row_bits(const AggDesc & d, u64 i)
+{
+    u32 nz = 0;
+    for (u32 c = 0; c < d.n_conds; ++c)
+        nz |= (u32)(__builtin_nontemporal_load(d.cond[c] + i) != 0) << c;
+    return nz;
+}
+// does row i (its condition bits `nz`) reach the function?
+__device__ __forceinline__ bool cond_reaches(const AggArg & a, u32 nz) { return a.cond < 0 || ((nz >> a.cond) & 1u) == a.cond_want; }
+
 template <typename Sink>
 __device__ __forceinline__ void add_row(const Sink & sink, const AggDesc & d, u64 i)
 {
+    const u32 nz = cond_row_bits(d, i);
     for (u32 j = 0; j < d.n_aggs; ++j)
     {
         const AggArg & a = d.a[j];
+        if (!cond_reaches(a, nz))
+            continue; // (the cell is claimed all the same: the group exists, AggregateFunctionIf::add / AggregateFunctionNullUnary::add skip)
         u64 * w = sink.at(d.word_map[a.word]);
+        if (a.seen)
+            sink.add_word(sink.at(d.word_map[a.word] + 1), 1, 0);
         if (a.kind == CHGPU_AGG_COUNT)
             sink.add_word(w, 1, 0);
         else if (a.kind == CHGPU_AGG_MIN || a.kind == CHGPU_AGG_MAX)
@@ -480,8 +513,8 @@ __device__ __forceinline__ void add_vals(const Sink & sink, const AggDesc & d, u
                 sink.add_fx(w, sink.at(d.word_map[d.fx_hi[a.word]]), fx_from_double(a.pre == 0 ? bits0 : bits1, d.fx_base));
             else
                 sink.add_word(w, a.pre == 0 ? bits0 : bits1, a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
-            if (a.kind == CHGPU_AGG_AVG)
-                sink.add_word(sink.at(d.word_map[a.word] + 1), cnt, 0); // denominator
+            if (a.kind == CHGPU_AGG_AVG || a.seen)
+                sink.add_word(sink.at(d.word_map[a.word] + 1), cnt, 0); // denominator; the `seen` word of a NULL-mode sum
         }
     }
 }
@@ -769,6 +802,8 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
     const void * a_ptr[AGG_MAX_AGGS];
     int a_kind[AGG_MAX_AGGS], a_type[AGG_MAX_AGGS];
     u32 a_word[AGG_MAX_AGGS], a_hi[AGG_MAX_AGGS]; // a_hi: the high word of a fixed-point sum (0 = an ordinary state word)
+    int a_cond[AGG_MAX_AGGS];                     // -1: unconditioned; else (condition column << 1) | the value its non-zero test must give
+    bool a_cnt2[AGG_MAX_AGGS];                    // word + 1 counts rows: avg's denominator, a NULL-mode sum's `seen`
     const int fx_base = d.fx_base;
 #pragma unroll
     for (u32 j = 0; j < AGG_MAX_AGGS; ++j)
@@ -779,6 +814,8 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
         a_type[j] = on ? d.a[j].arg_type : 0;
         a_word[j] = on ? d.a[j].word : 0;
         a_hi[j] = (on && d.a[j].kind != CHGPU_AGG_COUNT && ((d.word_fx >> d.a[j].word) & 1)) ? d.fx_hi[d.a[j].word] : 0;
+        a_cond[j] = (on && d.a[j].cond >= 0) ? (d.a[j].cond << 1) | d.a[j].cond_want : -1;
+        a_cnt2[j] = on && (d.a[j].kind == CHGPU_AGG_AVG || d.a[j].seen);
     }
     const u64 wave0 = ((u64)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const u64 n_waves = ((u64)gridDim.x * blockDim.x) >> 6;
@@ -819,11 +856,14 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
                 const u32 ls = lds_find_or_claim<u64>(lkeys, key, (u32)(dev_intHash64(key) >> 40) & (S - 1), 32, S, lzero);
                 if (ls != ~0u)
                 {
+                    const u32 nz = cond_row_bits(d, i); // (no condition column: no load)
 #pragma unroll
                     for (u32 j = 0; j < AGG_MAX_AGGS; ++j)
                     {
                         if (a_kind[j] < 0)
                             break;
+                        if (a_cond[j] >= 0 && ((nz >> (a_cond[j] >> 1)) & 1u) != (u32)(a_cond[j] & 1))
+                            continue; // the cell is claimed, the function skips the row
                         u64 * w = lwords + a_word[j] * lstride + ls;
                         if (a_kind[j] == CHGPU_AGG_COUNT)
                             atomicAdd((unsigned long long *)w, 1ull);
@@ -838,7 +878,7 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
                                 atomicAdd((double *)w, __longlong_as_double((long long)bits));
                             else
                                 atomicAdd((unsigned long long *)w, (unsigned long long)bits);
-                            if (a_kind[j] == CHGPU_AGG_AVG)
+                            if (a_cnt2[j])
                                 atomicAdd((unsigned long long *)(w + lstride), 1ull);
                         }
                     }
@@ -1268,12 +1308,15 @@ __device__ __forceinline__ void lds_update_ops(unsigned char * lds_raw, const u3
 // OPS != 0: the state update is fixed at compile time -- 4 bits per state word, word 0 in the low nibble: 1 / 2 = integer sum of
 // argument word 0 / 1, 3 / 4 = Float64 sum of argument word 0 / 1, 5 = row count kept in 32 bits, 6 = row count in 64 bits.  The
 // run-time descriptor walk costs ~25 scalar + ~10 vector instructions per 64 rows of a pass that is bound by instruction issue.
-template <typename KT, int AW, typename KS = KT, bool EXT = false, u32 OPS = 0>
+// FCOND (RANGE mode, OPS == 0): the functions of this pass share ONE condition column `fcond` (-If / Nullable argument): a row whose
+// byte is not `fwant` (1: non-zero, 0: zero) still claims its cell -- the group exists -- and skips the update.  Compiled out otherwise.
+template <typename KT, int AW, typename KS = KT, bool EXT = false, u32 OPS = 0, bool FCOND = false>
 __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, const KS * __restrict__ keys, const void * __restrict__ words0, const void * __restrict__ words1,
                                                        const u64 * __restrict__ offsets, u32 G, u32 P, u64 n, u64 * __restrict__ pending, u32 S, u32 K, u32 cnt32,
                                                        u64 rows_per_chunk, const u32 * __restrict__ unit_start, u32 * __restrict__ unit_ctr,
-                                                       const u8 * __restrict__ cond)
+                                                       const u8 * __restrict__ cond, const u8 * __restrict__ fcond, u32 fwant)
 {
+    static_assert(!FCOND || OPS == 0, "a conditioned pass takes the generic update loop");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     KT * lkeys = (KT *)lds_raw;
     const PartLds L((u32)sizeof(KT), S, d.n_words, cnt32);
@@ -1315,7 +1358,7 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
                 a_src[j] = (int)d.a[j].pre;
                 const int ex = d.a[j].arg_type == CHGPU_I8 ? 1 : d.a[j].arg_type == CHGPU_I16 ? 2 : d.a[j].arg_type == CHGPU_I32 ? 3 : d.a[j].arg_type == CHGPU_F32 ? 4 : 0;
                 (d.a[j].pre == 0 ? ex0 : ex1) = ex;
-                if (d.a[j].kind == CHGPU_AGG_AVG)
+                if (d.a[j].kind == CHGPU_AGG_AVG || d.a[j].seen) // avg's denominator; a NULL-mode sum's `seen` word
                 {
                     a_off2[j] = L.off(w + 1);
                     a_op2[j] = ((cnt32 >> (w + 1)) & 1) ? 3 : 4;
@@ -1388,6 +1431,8 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
                 u64 i = (gb + q) * 64 + lane;
                 i = i < n ? i : n - 1;
                 cv[q] = cond ? (u32)__builtin_nontemporal_load(&cond[i]) : 1u;
+                if constexpr (FCOND) // bit 8: the row reaches the pass's functions (the WHERE byte stays in the low bits)
+                    cv[q] = (cv[q] & 0xffu) | ((u32)((u32)(__builtin_nontemporal_load(&fcond[i]) != 0) == fwant) << 8);
                 kv[q] = (u64)__builtin_nontemporal_load(&keys[i]);
                 typedef typename std::conditional<AW == 8, u64, typename std::conditional<AW == 4, u32, typename std::conditional<AW == 2, u16, u8>::type>::type>::type AT;
                 // (with a compile-time OPS the loads are unconditional or absent: a run-time `K > 0` puts a branch around each load)
@@ -1414,8 +1459,9 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
                     break;
                 const u64 i = g * 64 + lane;
                 bool failed = false;
-                if (i >= begin && i < end && cv[q] != 0)
+                if (i >= begin && i < end && (FCOND ? (cv[q] & 0xffu) : cv[q]) != 0)
                 {
+                    const bool reached = !FCOND || (cv[q] >> 8) != 0;
                     const u64 key = keyv[q];
                     u64 b0 = argv[q][0], b1 = argv[q][1];
                     if constexpr (EXT)
@@ -1435,7 +1481,7 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
 #pragma unroll
                         for (u32 j = 0; j < AGG_MAX_AGGS; ++j)
                         {
-                            if (a_op[j] == 0)
+                            if (a_op[j] == 0 || !reached)
                                 break;
                             unsigned char * w = lds_raw + a_off[j];
                             const u64 bits = a_src[j] == 0 ? b0 : b1;
@@ -1457,7 +1503,10 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
                     }
                     else
                     {
-                        failed = place_and_add(t, s_ovf, key, true, [&](auto sink) { add_vals(sink, d, b0, b1, 1); });
+                        failed = place_and_add(t, s_ovf, key, true, [&](auto sink) {
+                            if (reached)
+                                add_vals(sink, d, b0, b1, 1);
+                        });
                     }
                 }
                 const u64 b = __ballot(failed);
@@ -2124,48 +2173,22 @@ static void agg_set_find_only(chgpu_agg * a, bool on)
     a->t.ovf = on ? (u64 *)a->ovf_mem : nullptr;
 }
 
-extern "C" int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, const int * agg_kinds, const int * arg_types,
-                                uint64_t size_hint, chgpu_agg ** out)
+// The state words of every function, from kinds / arg_types / val_types / cond_modes: word_off, the word masks, the `seen` words of
+// the conditioned functions and the appended high halves of the fixed-point sums.  Over AGG_MAX_WORDS words: `too_many` and a message.
+static int agg_layout(chgpu_agg * a, int too_many)
 {
-    ChgpuDeviceGuard _dev_guard(ctx);
-    CHGPU_REQUIRE(ctx && out && (agg_kinds || n_aggs == 0), CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(n_aggs <= AGG_MAX_AGGS, CHGPU_ERR_NOT_IMPLEMENTED, "more than %u aggregate functions: CPU path", AGG_MAX_AGGS);
-    CHGPU_REQUIRE(key_type < 0 || (chgpu_type_is_int(key_type)),
-                  CHGPU_ERR_NOT_IMPLEMENTED, "GROUP BY key type %d: CPU path", key_type);
-    chgpu_agg * a = new chgpu_agg();
-    a->ctx = ctx;
-    a->key_type = key_type;
-    a->n_aggs = n_aggs;
-    a->size_hint = size_hint;
-    u32 w = 0, slot = 0;
-    for (u32 j = 0; j < n_aggs; ++j)
+    a->word_is_f64 = a->word_any = a->word_arg = a->word_seen = a->word_fx = a->word_fx_hi = 0;
+    a->has_extremum = false;
+    memset(a->fx_hi, 0, sizeof(a->fx_hi));
+    u32 w = 0;
+    for (u32 j = 0; j < a->n_aggs; ++j)
     {
         if (w >= AGG_MAX_WORDS)
-        {
-            delete a;
-            return chgpu_set_error(CHGPU_ERR_NOT_IMPLEMENTED, "more than %u state words: CPU path", AGG_MAX_WORDS);
-        }
-        const int kind = agg_kinds[j];
+            return chgpu_set_error(too_many, "more than %u state words: CPU path", AGG_MAX_WORDS);
+        const int kind = a->kinds[j];
         const bool arg_pair = kind == CHGPU_AGG_ARG_MIN || kind == CHGPU_AGG_ARG_MAX; // two argument slots: arg, then val
-        const int at = (kind == CHGPU_AGG_COUNT || !arg_types) ? CHGPU_U64 : arg_types[slot];
-        const int vt = (arg_pair && arg_types) ? arg_types[slot + 1] : CHGPU_U64;
         const bool any_value = kind == CHGPU_AGG_ANY;
         const bool extremum = kind == CHGPU_AGG_MIN || kind == CHGPU_AGG_MAX || any_value;
-        if (kind != CHGPU_AGG_COUNT && kind != CHGPU_AGG_SUM && kind != CHGPU_AGG_AVG && !extremum && !arg_pair)
-        {
-            delete a;
-            return chgpu_set_error(CHGPU_ERR_NOT_IMPLEMENTED, "aggregate function kind %d has no device state: CPU path", kind);
-        }
-        if (kind != CHGPU_AGG_COUNT && (!chgpu_type_size(at) || !chgpu_type_size(vt)))
-        {
-            delete a;
-            return chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "bad argument type %d", chgpu_type_size(at) ? vt : at);
-        }
-        a->kinds[j] = kind;
-        a->arg_types[j] = at;
-        a->val_types[j] = vt;
-        a->slot[j] = slot;
-        slot += arg_pair ? 2 : 1;
         a->word_off[j] = w;
         if (arg_pair)
         {
@@ -2182,24 +2205,30 @@ extern "C" int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, 
             if (any_value)
                 a->word_any |= 1u << w;
         }
-        else if (kind != CHGPU_AGG_COUNT && chgpu_type_is_float(at))
+        else if (kind != CHGPU_AGG_COUNT && chgpu_type_is_float(a->arg_types[j]))
             a->word_is_f64 |= 1u << w;
         w += (kind == CHGPU_AGG_AVG || any_value) ? 2 : 1;
+        // the `seen` word: a zeroed min / max word is also the state of a row that holds the type's extremum, and a NULL-mode sum of 0
+        // is not NULL (avg has its denominator, count itself, any / argMin / argMax their claim)
+        const bool seen = a->cond_modes[j] != CHGPU_AGG_COND_NONE &&
+                          (kind == CHGPU_AGG_MIN || kind == CHGPU_AGG_MAX || (kind == CHGPU_AGG_SUM && a->cond_modes[j] == CHGPU_AGG_COND_NULL));
+        if (seen)
+        {
+            if (w < AGG_MAX_WORDS)
+                a->word_seen |= 1u << w;
+            ++w;
+        }
     }
     if (w > AGG_MAX_WORDS)
-    {
-        delete a;
-        return chgpu_set_error(CHGPU_ERR_NOT_IMPLEMENTED, "more than %u state words: CPU path", AGG_MAX_WORDS);
-    }
+        return chgpu_set_error(too_many, "more than %u state words: CPU path", AGG_MAX_WORDS);
     a->n_pub_words = w;
-    a->n_slots = slot;
-    if (key_type >= 0 && chgpu_opt(ctx, "deterministic_float_sums", 1))
+    if (a->key_type >= 0 && chgpu_opt(a->ctx, "deterministic_float_sums", 1))
     {
         u32 n_fx = 0;
-        for (u32 j = 0; j < n_aggs; ++j)
+        for (u32 j = 0; j < a->n_aggs; ++j)
             n_fx += ((a->word_is_f64 >> a->word_off[j]) & 1) ? 1 : 0;
         if (w + n_fx <= AGG_MAX_WORDS) // (more words than the masks hold: such an aggregation keeps its double states)
-            for (u32 j = 0; j < n_aggs; ++j)
+            for (u32 j = 0; j < a->n_aggs; ++j)
             {
                 const u32 lo = a->word_off[j];
                 if (!((a->word_is_f64 >> lo) & 1))
@@ -2212,9 +2241,85 @@ extern "C" int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, 
             }
     }
     a->n_words = w;
+    return CHGPU_OK;
+}
+
+extern "C" int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, const int * agg_kinds, const int * arg_types,
+                                uint64_t size_hint, chgpu_agg ** out)
+{
+    ChgpuDeviceGuard _dev_guard(ctx);
+    CHGPU_REQUIRE(ctx && out && (agg_kinds || n_aggs == 0), CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_REQUIRE(n_aggs <= AGG_MAX_AGGS, CHGPU_ERR_NOT_IMPLEMENTED, "more than %u aggregate functions: CPU path", AGG_MAX_AGGS);
+    CHGPU_REQUIRE(key_type < 0 || (chgpu_type_is_int(key_type)),
+                  CHGPU_ERR_NOT_IMPLEMENTED, "GROUP BY key type %d: CPU path", key_type);
+    chgpu_agg * a = new chgpu_agg();
+    a->ctx = ctx;
+    a->key_type = key_type;
+    a->n_aggs = n_aggs;
+    a->size_hint = size_hint;
+    u32 slot = 0;
+    for (u32 j = 0; j < n_aggs; ++j)
+    {
+        const int kind = agg_kinds[j];
+        const bool arg_pair = kind == CHGPU_AGG_ARG_MIN || kind == CHGPU_AGG_ARG_MAX; // two argument slots: arg, then val
+        const int at = (kind == CHGPU_AGG_COUNT || !arg_types) ? CHGPU_U64 : arg_types[slot];
+        const int vt = (arg_pair && arg_types) ? arg_types[slot + 1] : CHGPU_U64;
+        const bool extremum = kind == CHGPU_AGG_MIN || kind == CHGPU_AGG_MAX || kind == CHGPU_AGG_ANY;
+        if (kind != CHGPU_AGG_COUNT && kind != CHGPU_AGG_SUM && kind != CHGPU_AGG_AVG && !extremum && !arg_pair)
+        {
+            delete a;
+            return chgpu_set_error(CHGPU_ERR_NOT_IMPLEMENTED, "aggregate function kind %d has no device state: CPU path", kind);
+        }
+        if (kind != CHGPU_AGG_COUNT && (!chgpu_type_size(at) || !chgpu_type_size(vt)))
+        {
+            delete a;
+            return chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "bad argument type %d", chgpu_type_size(at) ? vt : at);
+        }
+        a->kinds[j] = kind;
+        a->arg_types[j] = at;
+        a->val_types[j] = vt;
+        a->slot[j] = slot;
+        slot += arg_pair ? 2 : 1;
+    }
+    a->n_slots = slot;
+    const int rc = agg_layout(a, CHGPU_ERR_NOT_IMPLEMENTED);
+    if (rc != CHGPU_OK)
+    {
+        delete a;
+        return rc;
+    }
     memset(a->host_words, 0, sizeof(a->host_words));
     chgpu_ctx_retain(ctx);
     *out = a;
+    return CHGPU_OK;
+}
+
+extern "C" int chgpu_agg_set_conditions(chgpu_agg * a, const int * cond_modes)
+{
+    CHGPU_REQUIRE(a && cond_modes, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_REQUIRE(!a->started, CHGPU_ERR_BAD_ARGUMENTS, "aggregate conditions must be set before the first block or merge");
+    bool any = false;
+    for (u32 j = 0; j < a->n_aggs; ++j)
+    {
+        CHGPU_REQUIRE(cond_modes[j] >= CHGPU_AGG_COND_NONE && cond_modes[j] <= CHGPU_AGG_COND_NULL, CHGPU_ERR_BAD_ARGUMENTS, "unknown condition mode %d of function %u",
+                      cond_modes[j], j);
+        any = any || cond_modes[j] != CHGPU_AGG_COND_NONE;
+    }
+    int before[AGG_MAX_AGGS];
+    memcpy(before, a->cond_modes, sizeof(before));
+    const bool was = a->conditioned;
+    for (u32 j = 0; j < a->n_aggs; ++j)
+        a->cond_modes[j] = cond_modes[j];
+    a->conditioned = any;
+    const int rc = agg_layout(a, CHGPU_ERR_BAD_ARGUMENTS);
+    if (rc != CHGPU_OK)
+    {
+        // (the message is set; the aggregator keeps the layout it had)
+        memcpy(a->cond_modes, before, sizeof(before));
+        a->conditioned = was;
+        (void)agg_layout(a, CHGPU_ERR_BAD_ARGUMENTS);
+        return chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "aggregate conditions need more than %u state words: CPU path", AGG_MAX_WORDS);
+    }
     return CHGPU_OK;
 }
 
@@ -2258,6 +2363,28 @@ static void agg_fill_desc(const chgpu_agg * a, const chgpu_col * const * arg_col
         d->a[j].val_type = a->val_types[j];
         d->a[j].word = a->word_off[j];
         d->a[j].pre = 0;
+        d->a[j].cond = -1;
+        d->a[j].cond_want = 0;
+        d->a[j].seen = 0;
+    }
+    d->n_conds = 0;
+    for (u32 j = 0; j < AGG_MAX_AGGS; ++j)
+        d->cond[j] = nullptr;
+    if (!a->conditioned || !a->block_conds)
+        return;
+    for (u32 j = 0; j < a->n_aggs; ++j)
+    {
+        if (a->cond_modes[j] == CHGPU_AGG_COND_NONE)
+            continue;
+        const u8 * p = (const u8 *)a->block_conds[j]->data;
+        u32 c = 0;
+        while (c < d->n_conds && d->cond[c] != p)
+            ++c;
+        if (c == d->n_conds)
+            d->cond[d->n_conds++] = p; // a column shared by several functions is read once per row
+        d->a[j].cond = (signed char)c;
+        d->a[j].cond_want = a->cond_modes[j] == CHGPU_AGG_COND_IF ? 1 : 0;
+        d->a[j].seen = (unsigned char)((a->word_seen >> (a->word_off[j] + 1)) & 1);
     }
 }
 
@@ -2327,6 +2454,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_any_resolve(AggTable t, Agg
     {
         const u64 i = row_begin + r;
         const u64 key = load_key_zext(keys, key_type, i);
+        const u32 nz = cond_row_bits(d, i); // (a claim only ever came from a row that reached the function: the test saves the state's load)
         u64 slot = t.capacity; // the zero key's cell
         if (t.find_only)
         {
@@ -2336,7 +2464,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_any_resolve(AggTable t, Agg
             {
                 if (t.ovf)
                     for (u32 j = 0; j < d.n_aggs; ++j)
-                        if (d.a[j].kind == CHGPU_AGG_ANY && t.ovf[d.a[j].word] == ~(d.row_seq + i))
+                        if (d.a[j].kind == CHGPU_AGG_ANY && cond_reaches(d.a[j], nz) && t.ovf[d.a[j].word] == ~(d.row_seq + i))
                             t.ovf[d.a[j].word + 1] = load_arg_bits(d.a[j].ptr, d.a[j].arg_type, i);
                 continue;
             }
@@ -2356,7 +2484,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_any_resolve(AggTable t, Agg
         }
         const u64 claim = ~(d.row_seq + i);
         for (u32 j = 0; j < d.n_aggs; ++j)
-            if (d.a[j].kind == CHGPU_AGG_ANY && t.words[(u64)d.a[j].word * stride + slot] == claim)
+            if (d.a[j].kind == CHGPU_AGG_ANY && cond_reaches(d.a[j], nz) && t.words[(u64)d.a[j].word * stride + slot] == claim)
                 t.words[(u64)(d.a[j].word + 1) * stride + slot] = load_arg_bits(d.a[j].ptr, d.a[j].arg_type, i);
     }
 }
@@ -2416,11 +2544,14 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_arg_rows(AggTable t, AggDes
         u64 stride;
         if (!agg_state_of(t, load_key_zext(keys, key_type, i), base, stride))
             continue;
+        const u32 nz = cond_row_bits(d, i);
         for (u32 j = 0; j < d.n_aggs; ++j)
         {
             const AggArg & a = d.a[j];
             if (a.kind != CHGPU_AGG_ARG_MIN && a.kind != CHGPU_AGG_ARG_MAX)
                 continue;
+            if (!cond_reaches(a, nz))
+                continue; // a masked-out row may EQUAL the extremum: it must not claim it
             const u64 k = agg_val_key(load_arg_bits(a.val, a.val_type, i), a.val_type);
             agg_arg_claim_or_resolve<PASS>(base + (u64)a.word * stride, stride, a.kind == CHGPU_AGG_ARG_MAX ? k : ~k, agg_arg_row_claim(d.row_seq + i),
                                            PASS == 3 ? load_arg_bits(a.ptr, a.arg_type, i) : 0, 0);
@@ -2453,8 +2584,10 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_arg_tuples(AggTable t, u32 
 
 // ---- the fixed-point window of the deterministic Float64 sums (see Fx128) ----
 // Over the non-zero finite values (as doubles; a subnormal counts as exponent 1): out[0] = largest biased exponent (0 = no such value),
-// out[2] = 2047 - smallest biased exponent; out[1] = 1 when some value is NaN / +-inf
-__global__ __launch_bounds__(256) void k_fx_exp_stats(const void * __restrict__ p, int type, u64 row_begin, u64 n, u32 * __restrict__ out)
+// out[2] = 2047 - smallest biased exponent; out[1] = 1 when some value is NaN / +-inf.  cond (may be NULL): only the rows whose byte
+// is non-zero (cond_want 1) / zero (cond_want 0) are looked at -- a value the function never sees must not shape its window.
+__global__ __launch_bounds__(256) void k_fx_exp_stats(const void * __restrict__ p, int type, u64 row_begin, u64 n, const u8 * __restrict__ cond, int cond_want,
+                                                       u32 * __restrict__ out)
 {
     u32 emax = 0, emin_c = 0, bad = 0;
     auto take = [&](u64 bits) {
@@ -2469,7 +2602,13 @@ __global__ __launch_bounds__(256) void k_fx_exp_stats(const void * __restrict__ 
         }
     };
     const u64 tid = (u64)blockIdx.x * 256 + threadIdx.x, nthreads = (u64)gridDim.x * 256;
-    if (type == CHGPU_F64 && (((uintptr_t)p + row_begin * 8) & 15) == 0)
+    if (cond)
+    {
+        for (u64 i = tid; i < n; i += nthreads)
+            if ((int)(__builtin_nontemporal_load(cond + row_begin + i) != 0) == cond_want)
+                take(load_arg_bits(p, type, row_begin + i));
+    }
+    else if (type == CHGPU_F64 && (((uintptr_t)p + row_begin * 8) & 15) == 0)
     {
         // a streaming read: two 16-byte nontemporal loads per lane in flight
         typedef u64 v2q __attribute__((ext_vector_type(2)));
@@ -2619,12 +2758,13 @@ static int agg_fx_to_plain(chgpu_agg * a)
     return CHGPU_OK;
 }
 // exponent statistics of `n` values of one column: *emax_biased = 0 when every value is zero (then *emin_biased is 2047)
-static int agg_fx_stats(chgpu_ctx * ctx, const void * data, int type, u64 row_begin, u64 n, u32 * emax_biased, u32 * emin_biased, bool * nonfinite)
+static int agg_fx_stats(chgpu_ctx * ctx, const void * data, int type, u64 row_begin, u64 n, const u8 * cond, int cond_want, u32 * emax_biased, u32 * emin_biased,
+                        bool * nonfinite)
 {
     void * scratch = nullptr;
     CHGPU_TRY(chgpu_scratch(ctx, 256, &scratch));
     CHGPU_HIP(hipMemsetAsync(scratch, 0, 16, ctx->stream));
-    hipLaunchKernelGGL(k_fx_exp_stats, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, data, type, row_begin, n, (u32 *)scratch);
+    hipLaunchKernelGGL(k_fx_exp_stats, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, data, type, row_begin, n, cond, cond_want, (u32 *)scratch);
     ctx->counters[6] += 1;
     CHGPU_HIP(hipGetLastError());
     u32 r[4];
@@ -2673,7 +2813,9 @@ static int agg_fx_prepare_block(chgpu_agg * a, const chgpu_col * const * arg_col
             continue;
         u32 e = 0, em = 2047;
         bool bad = false;
-        CHGPU_TRY(agg_fx_stats(a->ctx, arg_cols[a->slot[j]]->data, a->arg_types[j], row_begin, n, &e, &em, &bad));
+        const chgpu_col * cc = a->cond_modes[j] != CHGPU_AGG_COND_NONE ? a->block_conds[j] : nullptr;
+        CHGPU_TRY(agg_fx_stats(a->ctx, arg_cols[a->slot[j]]->data, a->arg_types[j], row_begin, n, cc ? (const u8 *)cc->data : nullptr,
+                               a->cond_modes[j] == CHGPU_AGG_COND_IF ? 1 : 0, &e, &em, &bad));
         if (bad)
             return agg_fx_to_plain(a);
         emax = e > emax ? e : emax;
@@ -3431,7 +3573,7 @@ static int agg_scatter_run(chgpu_agg * a, const AggInput & in, const chgpu_col *
             auto launch = [&](auto ops) {
                 rc = launch_lds(what, k_agg_part_lds<KT, 8, KT, false, decltype(ops)::value>, dim3((u32)ctx->num_cus), dim3(1024), lds_ag, ctx->stream, a->t, d, (const KT *)s.pkeys,
                                 (const void *)s.pwords, (const void *)(s.pwords + s.wstride), (const u64 *)s.offsets, G, P, n, s.pending, S, K, g.cnt32, g.chunk_rows,
-                                (const u32 *)s.unit_start, unit_ctr, (const u8 *)nullptr);
+                                (const u32 *)s.unit_start, unit_ctr, (const u8 *)nullptr, (const u8 *)nullptr, 0u);
             };
             if (!GbPartOps::dispatch(g.ops, launch))
                 launch(std::integral_constant<u32, 0>{}); // the update read from the descriptor
@@ -3547,10 +3689,15 @@ static int agg_add_block_by_partitions(chgpu_agg * a, const chgpu_col * key_col,
 static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 row_end,
                               const chgpu_col * filter);
 
+// the calls that carry no condition columns, on an aggregator whose functions need them
+#define AGG_REQUIRE_UNCONDITIONED(a)                                                                                   \
+    CHGPU_REQUIRE(!(a) || !(a)->conditioned, CHGPU_ERR_BAD_ARGUMENTS, "the aggregator has conditioned functions: use chgpu_agg_execute_on_block_conditional")
+
 extern "C" int chgpu_agg_add_block(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols,
                                    uint64_t row_begin, uint64_t row_end)
 {
     ChgpuDeviceGuard _dev_guard(a ? a->ctx : nullptr);
+    AGG_REQUIRE_UNCONDITIONED(a);
     return agg_add_block_impl(a, key_col, arg_cols, row_begin, row_end, nullptr);
 }
 
@@ -3558,6 +3705,7 @@ extern "C" int chgpu_agg_add_block_filtered(chgpu_agg * a, const chgpu_col * key
                                             uint64_t row_begin, uint64_t row_end, const chgpu_col * filter_u8)
 {
     ChgpuDeviceGuard _dev_guard(a ? a->ctx : nullptr);
+    AGG_REQUIRE_UNCONDITIONED(a);
     return agg_add_block_impl(a, key_col, arg_cols, row_begin, row_end, filter_u8);
 }
 
@@ -3568,8 +3716,8 @@ static int agg_add_block_materialised(chgpu_agg * a, const chgpu_col * key_col, 
 {
     chgpu_ctx * ctx = a->ctx;
     const u64 n = row_end - row_begin;
-    const chgpu_col * src[1 + 2 * AGG_MAX_AGGS];
-    chgpu_col * views[2 + 2 * AGG_MAX_AGGS] = {};
+    const chgpu_col * src[1 + 3 * AGG_MAX_AGGS];
+    chgpu_col * views[2 + 3 * AGG_MAX_AGGS] = {};
     u32 m = 0;
     int rc = CHGPU_OK;
     auto view = [&](const chgpu_col * c) {
@@ -3588,7 +3736,25 @@ static int agg_add_block_materialised(chgpu_agg * a, const chgpu_col * key_col, 
                 data_of[sl] = m - 1; // index among the data columns (key = 0)
                 view(arg_cols[sl]);
             }
-    chgpu_col * outs[1 + 2 * AGG_MAX_AGGS] = {};
+    // the condition columns travel with the keys and arguments (each distinct column once)
+    u32 cond_of[AGG_MAX_AGGS];
+    const chgpu_col * const * conds = a->conditioned ? a->block_conds : nullptr;
+    for (u32 j = 0; conds && j < a->n_aggs; ++j)
+    {
+        if (a->cond_modes[j] == CHGPU_AGG_COND_NONE)
+            continue;
+        u32 e = 0;
+        while (e < j && !(a->cond_modes[e] != CHGPU_AGG_COND_NONE && conds[e] == conds[j]))
+            ++e;
+        if (e < j)
+        {
+            cond_of[j] = cond_of[e];
+            continue;
+        }
+        cond_of[j] = m - 1;
+        view(conds[j]);
+    }
+    chgpu_col * outs[1 + 3 * AGG_MAX_AGGS] = {};
     u64 kept = 0;
     const u32 n_data = m ? m - 1 : 0;
     if (rc == CHGPU_OK)
@@ -3604,13 +3770,32 @@ static int agg_add_block_materialised(chgpu_agg * a, const chgpu_col * key_col, 
             if (a->kinds[j] != CHGPU_AGG_COUNT)
                 for (u32 sl = a->slot[j]; sl < (j + 1 < a->n_aggs ? a->slot[j + 1] : a->n_slots); ++sl)
                     fargs[sl] = outs[data_of[sl]];
+        const chgpu_col * fconds[AGG_MAX_AGGS] = {};
+        for (u32 j = 0; conds && j < a->n_aggs; ++j)
+            if (a->cond_modes[j] != CHGPU_AGG_COND_NONE)
+                fconds[j] = outs[cond_of[j]];
+        if (conds)
+            a->block_conds = fconds;
         rc = agg_add_block_impl(a, outs[0], fargs, 0, kept, nullptr);
+        if (conds)
+            a->block_conds = conds;
     }
     for (u32 k = 0; k < n_data; ++k)
         chgpu_col_free(outs[k]);
     for (u32 k = 0; k < m; ++k)
         chgpu_col_free(views[k]);
     return rc;
+}
+
+// without key: out[i] = filter[i] (NULL: 1) AND ((cond[i] != 0) == want) over rows [row_begin, row_begin + n), indexed like the columns
+__global__ __launch_bounds__(256) void k_nokey_cond_mask(const u8 * __restrict__ filter, const u8 * __restrict__ cond, int want, u64 row_begin, u64 n,
+                                                         u8 * __restrict__ out)
+{
+    for (u64 r = (u64)blockIdx.x * 256 + threadIdx.x; r < n; r += (u64)gridDim.x * 256)
+    {
+        const u64 i = row_begin + r;
+        out[i] = (u8)((!filter || filter[i]) && (int)(cond[i] != 0) == want);
+    }
 }
 
 // executeWithoutKeyImpl (Aggregator.cpp:1276-1321): addBatchSinglePlace per function
@@ -3628,8 +3813,8 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
         chgpu_col_free(fv);
         CHGPU_TRY(rc);
     }
-    for (u32 j = 0; j < a->n_aggs; ++j)
-    {
+    // one function under one mask (`filter`, which lets `kept` rows through)
+    auto add_function = [&](u32 j, const chgpu_col * filter, u64 kept) -> int {
         u64 * st = &a->host_words[a->word_off[j]];
         const chgpu_col * col = a->kinds[j] == CHGPU_AGG_COUNT ? nullptr : arg_cols[a->slot[j]];
         if (a->kinds[j] == CHGPU_AGG_COUNT)
@@ -3638,7 +3823,7 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
         {
             // the block's lexicographic extremum of (val key, ~ordinal): the largest val key, its first holder, that row's arg
             if (kept == 0 || n == 0)
-                continue;
+                return CHGPU_OK;
             const chgpu_col * val = arg_cols[a->slot[j] + 1];
             const int is_min = a->kinds[j] == CHGPU_AGG_ARG_MIN ? 1 : 0;
             void * scratch = nullptr;
@@ -3653,7 +3838,7 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
             CHGPU_TRY(chgpu_read_back(ctx, dev, &best, 8));
             ctx->counters[6] += 1;
             if (st[1] != 0 && best <= st[0])
-                continue; // setIfGreater / setIfSmaller: only a strictly better val replaces a state that has a value
+                return CHGPU_OK; // setIfGreater / setIfSmaller: only a strictly better val replaces a state that has a value
             CHGPU_HIP(hipMemsetAsync(dev, 0xFF, 8, ctx->stream));
             hipLaunchKernelGGL(k_nokey_first_holder, dim3(grid), dim3(256), 0, ctx->stream, (const void *)val->data, a->val_types[j], row_begin, n, cond, is_min, best, dev);
             CHGPU_HIP(hipGetLastError());
@@ -3670,7 +3855,7 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
         else if (a->kinds[j] == CHGPU_AGG_MIN || a->kinds[j] == CHGPU_AGG_MAX || a->kinds[j] == CHGPU_AGG_ANY)
         {
             if (kept == 0 || n == 0)
-                continue;
+                return CHGPU_OK;
             void * scratch = nullptr;
             CHGPU_TRY(chgpu_scratch(ctx, 256, &scratch));
             unsigned long long * dev = (unsigned long long *)scratch;
@@ -3713,7 +3898,51 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
             if (a->kinds[j] == CHGPU_AGG_AVG)
                 st[1] += kept;
         }
+        return CHGPU_OK;
+    };
+    // every function aggregates under `filter AND its own condition` (-If: the byte is non-zero, Nullable: the null-map byte is zero)
+    const chgpu_col * const * conds = a->conditioned ? a->block_conds : nullptr;
+    chgpu_col * masks[AGG_MAX_AGGS] = {};
+    u64 mask_kept[AGG_MAX_AGGS] = {};
+    int rc = CHGPU_OK;
+    for (u32 j = 0; j < a->n_aggs && rc == CHGPU_OK; ++j)
+    {
+        if (!conds || a->cond_modes[j] == CHGPU_AGG_COND_NONE)
+        {
+            rc = add_function(j, filter, kept);
+            continue;
+        }
+        u32 e = 0; // an earlier function with the same column and mode shares its mask
+        while (e < j && !(masks[e] && conds[e] == conds[j] && a->cond_modes[e] == a->cond_modes[j]))
+            ++e;
+        if (e == j && n)
+        {
+            rc = chgpu_col_new(ctx, CHGPU_U8, row_end, &masks[j]);
+            if (rc != CHGPU_OK)
+                break;
+            hipLaunchKernelGGL(k_nokey_cond_mask, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, filter ? (const u8 *)filter->data : nullptr,
+                               (const u8 *)conds[j]->data, a->cond_modes[j] == CHGPU_AGG_COND_IF ? 1 : 0, row_begin, n, (u8 *)masks[j]->data);
+            ctx->counters[6] += 1;
+            chgpu_col * mv = nullptr;
+            rc = chgpu_col_slice(ctx, masks[j], row_begin, n, &mv);
+            if (rc == CHGPU_OK)
+            {
+                rc = chgpu_count_bytes_in_filter(ctx, mv, &mask_kept[j]);
+                chgpu_col_free(mv);
+            }
+            if (rc != CHGPU_OK)
+                break;
+        }
+        const u32 src = e < j ? e : j;
+        if (n)
+            rc = add_function(j, masks[src], mask_kept[src]);
+        if (rc == CHGPU_OK && ((a->word_seen >> (a->word_off[j] + 1)) & 1))
+            a->host_words[a->word_off[j] + 1] += mask_kept[src];
     }
+    for (u32 j = 0; j < a->n_aggs; ++j)
+        if (masks[j])
+            chgpu_col_free(masks[j]);
+    CHGPU_TRY(rc);
     a->any_seq += n;
     a->nokey_kept += kept;
     return CHGPU_OK;
@@ -3733,29 +3962,43 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
         u32 agg[GBP_MAX_K];  // their aggregate indices
         size_t aw = 8;       // their width
         bool ext = false;    // one of them is a signed narrow integer or Float32
+        int cond = -1;       // the condition column its functions share (index into d.cond; -1: unconditioned) ...
+        u32 want = 0;        // ... and what its non-zero test must give
+        u32 counts = 0;      // the count() functions that ride in it (bit j)
     };
+    // Functions are grouped by argument width AND condition: a pass carries at most one per-function mask.  count() needs no argument:
+    // it rides in the first pass under its own condition (countIf(c) with a sumIf(x, c)), or gets an argument-less pass.
     Pass passes[AGG_MAX_AGGS];
     u32 n_passes = 0;
-    for (u32 j = 0; j < a->n_aggs; ++j)
-    {
-        if (a->kinds[j] == CHGPU_AGG_COUNT)
-            continue;
-        const size_t w = chgpu_type_size(a->arg_types[j]);
-        u32 p = 0;
-        for (; p < n_passes; ++p) // first pass of this width with a free slot
-            if (passes[p].aw == w && passes[p].n < GBP_MAX_K)
-                break;
-        if (p == n_passes)
+    for (int counts = 0; counts < 2; ++counts)
+        for (u32 j = 0; j < a->n_aggs; ++j)
         {
-            passes[n_passes].aw = w;
-            ++n_passes;
+            if ((a->kinds[j] == CHGPU_AGG_COUNT) != (counts != 0))
+                continue;
+            const size_t w = chgpu_type_size(a->arg_types[j]);
+            u32 p = 0;
+            for (; p < n_passes; ++p) // first pass of this condition (and, for an argument, of its width with a free slot)
+                if (passes[p].cond == d.a[j].cond && (d.a[j].cond < 0 || passes[p].want == d.a[j].cond_want) &&
+                    (counts || (passes[p].aw == w && passes[p].n < GBP_MAX_K)))
+                    break;
+            if (p == n_passes)
+            {
+                passes[n_passes].aw = counts ? 8 : w;
+                passes[n_passes].cond = d.a[j].cond;
+                passes[n_passes].want = d.a[j].cond_want;
+                ++n_passes;
+            }
+            if (counts)
+            {
+                passes[p].counts |= 1u << j;
+                continue;
+            }
+            passes[p].agg[passes[p].n++] = j;
+            const int at = a->arg_types[j];
+            passes[p].ext = passes[p].ext || at == CHGPU_I8 || at == CHGPU_I16 || at == CHGPU_I32 || at == CHGPU_F32;
         }
-        passes[p].agg[passes[p].n++] = j;
-        const int at = a->arg_types[j];
-        passes[p].ext = passes[p].ext || at == CHGPU_I8 || at == CHGPU_I16 || at == CHGPU_I32 || at == CHGPU_F32;
-    }
     if (n_passes == 0)
-        n_passes = 1; // only count(): one pass without argument columns
+        n_passes = 1; // no function at all: one pass that only claims the groups
 
     const size_t key_w = chgpu_type_size(a->key_type);
     u32 cnt32 = 0;
@@ -3783,11 +4026,15 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
     const u8 * cond_ptr = filter ? (const u8 *)filter->data + row_begin : nullptr;
     if (chgpu_opt(ctx, "debug", 0))
     {
-        std::string aw, ext; // per pass, comma-separated
+        std::string aw, ext, cnd; // per pass, comma-separated
         for (u32 p = 0; p < n_passes; ++p)
+        {
             aw += (p ? "," : "") + std::to_string(passes[p].aw), ext += (p ? "," : "") + std::to_string(passes[p].ext ? 1 : 0);
-        fprintf(stderr, "chgpu: ranged GROUP BY n=%llu hint=%llu S=%u chunks=%llu passes=%u key_w=%zu aw=%s ext=%s\n", (unsigned long long)n,
-                (unsigned long long)a->size_hint, S, (unsigned long long)chunks, n_passes, key_w, aw.c_str(), ext.c_str());
+            cnd += (p ? "," : "") + (passes[p].cond < 0 ? std::string("-") : std::to_string(passes[p].cond) + (passes[p].want ? "" : "!"));
+        }
+        fprintf(stderr, "chgpu: ranged GROUP BY n=%llu hint=%llu S=%u chunks=%llu passes=%u key_w=%zu aw=%s ext=%s%s%s\n", (unsigned long long)n,
+                (unsigned long long)a->size_hint, S, (unsigned long long)chunks, n_passes, key_w, aw.c_str(), ext.c_str(), a->conditioned ? " conds=" : "",
+                a->conditioned ? cnd.c_str() : "");
     }
     for (u32 p = 0; p < n_passes; ++p)
     {
@@ -3804,10 +4051,10 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
             ++dp.n_aggs;
             rwords[c] = (const char *)arg_cols[j]->data + row_begin * passes[p].aw;
         }
-        const u32 first_counts = p == 0 ? agg_count_mask(a) : 0;
         for (u32 j = 0; j < a->n_aggs; ++j)
-            if ((first_counts >> j) & 1)
+            if ((passes[p].counts >> j) & 1)
                 dp.a[dp.n_aggs++] = d.a[j];
+        const u8 * fcond_ptr = passes[p].cond >= 0 ? d.cond[passes[p].cond] + row_begin : nullptr;
         const u32 rk = passes[p].n;
         CHGPU_HIP(hipMemsetAsync(pending, 0, n_words64 * sizeof(u64), ctx->stream));
         int rc = CHGPU_OK;
@@ -3820,9 +4067,12 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
                 constexpr int AW = (int)sizeof(at);
                 dispatch_const<0, 1>(AW < 8 && passes[p].ext ? 1 : 0, [&](auto x) { // (an 8-byte argument needs no extension)
                     constexpr bool EXT = decltype(x)::value != 0;
-                    rc = launch_lds("ranged aggregation", k_agg_part_lds<KT, AW, KS, EXT>, dim3((u32)chunks), dim3(1024), lds_ag, ctx->stream, a->t, dp,
-                                    (const KS *)key_col->data + row_begin, rwords[0], rwords[1], (const u64 *)nullptr, 1u, (u32)chunks, n, pending, S, rk, cnt32, rows_per_chunk,
-                                    (const u32 *)nullptr, (u32 *)nullptr, cond_ptr);
+                    dispatch_const<0, 1>(fcond_ptr ? 1 : 0, [&](auto fc) {
+                        constexpr bool FCOND = decltype(fc)::value != 0;
+                        rc = launch_lds("ranged aggregation", k_agg_part_lds<KT, AW, KS, EXT, 0, FCOND>, dim3((u32)chunks), dim3(1024), lds_ag, ctx->stream, a->t, dp,
+                                        (const KS *)key_col->data + row_begin, rwords[0], rwords[1], (const u64 *)nullptr, 1u, (u32)chunks, n, pending, S, rk, cnt32,
+                                        rows_per_chunk, (const u32 *)nullptr, (u32 *)nullptr, cond_ptr, fcond_ptr, passes[p].want);
+                    });
                 });
             });
         });
@@ -3851,7 +4101,8 @@ static int agg_add_block_planned(chgpu_agg * a, const chgpu_col * key_col, const
     const u32 rows_grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
 
     // (min / max / any states go to the DIRECT kernel: the LDS-staged and partitioned plans carry additive words only)
-    if (!a->has_extremum && agg_partition_gate(a, (u64)lds_cells * 7 / 10, n))
+    // (conditioned functions: the partition buffers carry no per-function mask, see DESIGN.md §4.16.2 -- such a block takes DIRECT)
+    if (!a->has_extremum && !a->conditioned && agg_partition_gate(a, (u64)lds_cells * 7 / 10, n))
     {
         const int rc = agg_add_block_by_partitions(a, key_col, arg_cols, row_begin, n);
         if (rc != CHGPU_ERR_NOT_IMPLEMENTED)
@@ -3866,7 +4117,7 @@ static int agg_add_block_planned(chgpu_agg * a, const chgpu_col * key_col, const
         return agg_add_block_ranged(a, key_col, arg_cols, row_begin, n, filter, d, pending, n_words64, lds_cells);
     if (chgpu_opt(ctx, "debug", 0))
         fprintf(stderr, "chgpu: direct GROUP BY n=%llu hint=%llu kernel=%s%s\n", (unsigned long long)n, (unsigned long long)a->size_hint, use_lds ? "rows_lds" : "rows_direct",
-                a->has_extremum ? " states=extremum" : "");
+                a->conditioned ? " states=conditioned" : a->has_extremum ? " states=extremum" : "");
     if (use_lds)
     {
         // LDS cells per workgroup: the largest power of two with (1 + n_words) * 8 * (S+1) <= AGG_LDS_BYTES
@@ -3976,7 +4227,7 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
     // a WHERE mask is fused only into the RANGE-mode kernel; every other strategy gets the filtered block materialised first
     if (filter)
     {
-        const bool will_range = !agg_partition_gate(a, lds_groups, n) && a->size_hint <= 65536 && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0) && !a->has_extremum;
+        const bool will_range = (a->conditioned || !agg_partition_gate(a, lds_groups, n)) && a->size_hint <= 65536 && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0) && !a->has_extremum;
         if (!will_range)
             return agg_add_block_materialised(a, key_col, arg_cols, row_begin, row_end, filter);
         // The aggregation kernel is issue-bound: it spends nearly the same time on a masked-out row as on a kept one, while
@@ -4088,7 +4339,7 @@ static bool agg_same_shape(const chgpu_agg * x, const chgpu_agg * y)
     if (x->key_type != y->key_type || x->n_aggs != y->n_aggs)
         return false;
     for (u32 j = 0; j < x->n_aggs; ++j)
-        if (x->kinds[j] != y->kinds[j] || x->arg_types[j] != y->arg_types[j])
+        if (x->kinds[j] != y->kinds[j] || x->arg_types[j] != y->arg_types[j] || x->cond_modes[j] != y->cond_modes[j])
             return false;
     return true;
 }
@@ -4274,7 +4525,7 @@ extern "C" int chgpu_agg_merge_states(chgpu_agg * dst, const chgpu_col * key_col
             if ((dst->word_fx >> w) & 1)
             {
                 u32 e = 0, em = 2047;
-                CHGPU_TRY(agg_fx_stats(ctx, state_cols[w]->data, CHGPU_F64, 0, rows, &e, &em, &bad));
+                CHGPU_TRY(agg_fx_stats(ctx, state_cols[w]->data, CHGPU_F64, 0, rows, nullptr, 0, &e, &em, &bad));
                 emax = e > emax ? e : emax;
                 emin = em < emin ? em : emin;
             }
@@ -4351,11 +4602,9 @@ static int agg_check_limits(chgpu_agg * a, u64 groups, int * no_more_keys, int *
     return CHGPU_OK;
 }
 
-extern "C" int chgpu_agg_execute_on_block(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, uint64_t row_begin,
-                                          uint64_t row_end, const chgpu_col * filter_u8, int * no_more_keys, int * keep_reading)
+static int agg_execute_limited(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, u64 row_begin, u64 row_end,
+                               const chgpu_col * filter_u8, int * no_more_keys, int * keep_reading)
 {
-    ChgpuDeviceGuard _dev_guard(a ? a->ctx : nullptr);
-    CHGPU_REQUIRE(a && no_more_keys && keep_reading, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
     *keep_reading = 1;
     if (a->key_type < 0)
         return agg_add_block_impl(a, key_col, arg_cols, row_begin, row_end, filter_u8); // without key: limits never trigger
@@ -4370,6 +4619,38 @@ extern "C" int chgpu_agg_execute_on_block(chgpu_agg * a, const chgpu_col * key_c
     // every plan ends on a read-back of the table's header (agg_finish_rounds*): a->n_groups is this block's result; a table that does
     // not exist yet holds no group
     return agg_check_limits(a, a->table_mem ? a->n_groups : 0, no_more_keys, keep_reading);
+}
+
+extern "C" int chgpu_agg_execute_on_block(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols, uint64_t row_begin,
+                                          uint64_t row_end, const chgpu_col * filter_u8, int * no_more_keys, int * keep_reading)
+{
+    ChgpuDeviceGuard _dev_guard(a ? a->ctx : nullptr);
+    CHGPU_REQUIRE(a && no_more_keys && keep_reading, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    AGG_REQUIRE_UNCONDITIONED(a);
+    return agg_execute_limited(a, key_col, arg_cols, row_begin, row_end, filter_u8, no_more_keys, keep_reading);
+}
+
+extern "C" int chgpu_agg_execute_on_block_conditional(chgpu_agg * a, const chgpu_col * key_col, const chgpu_col * const * arg_cols,
+                                                      const chgpu_col * const * cond_cols, uint64_t row_begin, uint64_t row_end,
+                                                      const chgpu_col * filter_u8, int * no_more_keys, int * keep_reading)
+{
+    ChgpuDeviceGuard _dev_guard(a ? a->ctx : nullptr);
+    CHGPU_REQUIRE(a, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_REQUIRE((no_more_keys == nullptr) == (keep_reading == nullptr), CHGPU_ERR_BAD_ARGUMENTS, "no_more_keys and keep_reading go together");
+    for (u32 j = 0; a->conditioned && j < a->n_aggs; ++j)
+    {
+        if (a->cond_modes[j] == CHGPU_AGG_COND_NONE)
+            continue;
+        CHGPU_REQUIRE(cond_cols && cond_cols[j], CHGPU_ERR_BAD_ARGUMENTS, "condition column of function %u is NULL", j);
+        CHGPU_REQUIRE(cond_cols[j]->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "condition column of function %u must be a UInt8 column", j);
+        CHGPU_REQUIRE(row_end <= cond_cols[j]->rows, CHGPU_ERR_SIZES_MISMATCH, "condition column of function %u has %llu rows, block ends at %llu", j,
+                      (unsigned long long)cond_cols[j]->rows, (unsigned long long)row_end);
+    }
+    a->block_conds = a->conditioned ? cond_cols : nullptr;
+    const int rc = no_more_keys ? agg_execute_limited(a, key_col, arg_cols, row_begin, row_end, filter_u8, no_more_keys, keep_reading)
+                                : agg_add_block_impl(a, key_col, arg_cols, row_begin, row_end, filter_u8);
+    a->block_conds = nullptr;
+    return rc;
 }
 
 extern "C" int chgpu_agg_merge_limited(chgpu_agg * dst, const chgpu_agg * src, int * no_more_keys, int * keep_merging)
@@ -4441,7 +4722,7 @@ extern "C" int chgpu_agg_merge_states_limited(chgpu_agg * dst, const chgpu_col *
                 if ((dst->word_fx >> w) & 1)
                 {
                     u32 e = 0, em = 2047;
-                    CHGPU_TRY(agg_fx_stats(dst->ctx, state_cols[w]->data, CHGPU_F64, 0, 1, &e, &em, &bad));
+                    CHGPU_TRY(agg_fx_stats(dst->ctx, state_cols[w]->data, CHGPU_F64, 0, 1, nullptr, 0, &e, &em, &bad));
                     emax = e > emax ? e : emax;
                     emin = em < emin ? em : emin;
                 }
@@ -4525,7 +4806,9 @@ extern "C" int chgpu_agg_overflow_row(chgpu_agg * a, int final, chgpu_col ** col
                         memcpy(&num, &pub[w], 8);
                     else
                         num = chgpu_sum_result_type(at) == CHGPU_I64 ? (double)(i64)pub[w] : (double)pub[w];
-                    const double r = num / (double)pub[w + 1]; // 0 / 0 = NaN, as without key
+                    double r = num / (double)pub[w + 1]; // 0 / 0 = NaN, as without key
+                    if (a->cond_modes[j] == CHGPU_AGG_COND_NULL && pub[w + 1] == 0)
+                        r = 0.0; // the nested default of a NULL result
                     memcpy(&v, &r, 8);
                     type = CHGPU_F64;
                     break;
@@ -4536,6 +4819,8 @@ extern "C" int chgpu_agg_overflow_row(chgpu_agg * a, int final, chgpu_col ** col
                     type = at;
                     if (a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX)
                         v = pub[w + 1] ? pub[w + 2] : 0; // {val key, has, arg bits}
+                    else if (a->kinds[j] != CHGPU_AGG_ANY && a->cond_modes[j] != CHGPU_AGG_COND_NONE)
+                        v = pub[w + 1] ? agg_order_key_inverse(a->kinds[j] == CHGPU_AGG_MIN ? ~pub[w] : pub[w], at) : 0; // `seen` rows reached the min / max
                     else if (pub[w])
                         v = a->kinds[j] == CHGPU_AGG_ANY ? pub[w + 1] : agg_order_key_inverse(a->kinds[j] == CHGPU_AGG_MIN ? ~pub[w] : pub[w], at);
                     if (at == CHGPU_F32)
@@ -4789,11 +5074,50 @@ __global__ __launch_bounds__(256) void k_extremum_decode(const u64 * __restrict_
     }
 }
 
-extern "C" int chgpu_agg_finalize(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** res_cols, uint64_t * groups)
+// The state word that tells whether any row reached conditioned function j (0 = none): its `seen` word, avg's denominator, the claim
+// of any / argMin / argMax; ~0 = the function needs none (count; an -If sum, whose empty state already reads 0)
+static u32 agg_reached_word(const chgpu_agg * a, u32 j)
 {
-    ChgpuDeviceGuard _dev_guard(a ? a->ctx : nullptr);
-    CHGPU_REQUIRE(a && res_cols && groups, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    const u32 w = a->word_off[j];
+    switch (a->kinds[j])
+    {
+        case CHGPU_AGG_COUNT: return ~0u;
+        case CHGPU_AGG_SUM: return a->cond_modes[j] == CHGPU_AGG_COND_NULL ? w + 1 : ~0u;
+        case CHGPU_AGG_ANY: return w;
+        default: return w + 1; // avg, min / max, argMin / argMax
+    }
+}
+// The results of a conditioned function whose state no row reached: the nested value becomes the type's default where `zero` says so
+// (min / max decode an empty word to the type's extremum, a NULL-mode avg divides 0 by 0), and the null map gets its byte.
+__global__ __launch_bounds__(256) void k_cond_results(const u64 * __restrict__ reached, u64 n, u32 value_bytes, int zero, void * __restrict__ values,
+                                                      u8 * __restrict__ null_map)
+{
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
+    {
+        const bool empty = reached[i] == 0;
+        if (null_map)
+            null_map[i] = empty ? 1 : 0;
+        if (!empty || !zero)
+            continue;
+        switch (value_bytes)
+        {
+            case 8: ((u64 *)values)[i] = 0; break;
+            case 4: ((u32 *)values)[i] = 0; break;
+            case 2: ((u16 *)values)[i] = 0; break;
+            default: ((u8 *)values)[i] = 0; break;
+        }
+    }
+}
+
+static int agg_finalize_impl(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** res_cols, chgpu_col ** null_maps, uint64_t * groups)
+{
     chgpu_ctx * ctx = a->ctx;
+    for (u32 j = 0; j < a->n_aggs; ++j)
+    {
+        res_cols[j] = nullptr;
+        if (null_maps)
+            null_maps[j] = nullptr;
+    }
     chgpu_col * words[AGG_MAX_WORDS] = {nullptr};
     u64 n = 0;
     CHGPU_TRY(agg_export(a, keys_out, words, &n));
@@ -4822,7 +5146,7 @@ extern "C" int chgpu_agg_finalize(chgpu_agg * a, chgpu_col ** keys_out, chgpu_co
             rc = chgpu_col_new(ctx, a->arg_types[j], n, &r);
             if (rc != CHGPU_OK)
                 break;
-            if (a->key_type < 0 && a->nokey_kept == 0)
+            if (a->key_type < 0 && a->nokey_kept == 0 && a->cond_modes[j] == CHGPU_AGG_COND_NONE) // (a conditioned function: k_cond_results)
                 CHGPU_HIP(hipMemsetAsync(r->data, 0, chgpu_type_size(a->arg_types[j]), ctx->stream)); // a state without a value: the type's default
             else if (n)
             {
@@ -4849,9 +5173,50 @@ extern "C" int chgpu_agg_finalize(chgpu_agg * a, chgpu_col ** keys_out, chgpu_co
             res_cols[j] = r;
         }
     }
+    for (u32 j = 0; j < a->n_aggs && rc == CHGPU_OK; ++j)
+    {
+        const u32 rw = a->cond_modes[j] == CHGPU_AGG_COND_NONE ? ~0u : agg_reached_word(a, j);
+        if (rw == ~0u)
+            continue;
+        const bool null_mode = a->cond_modes[j] == CHGPU_AGG_COND_NULL;
+        if (null_mode && null_maps)
+            rc = chgpu_col_new(ctx, CHGPU_U8, n, &null_maps[j]);
+        const bool zero = a->kinds[j] == CHGPU_AGG_MIN || a->kinds[j] == CHGPU_AGG_MAX || (null_mode && a->kinds[j] == CHGPU_AGG_AVG);
+        if (rc == CHGPU_OK && n && (zero || (null_mode && null_maps)))
+        {
+            hipLaunchKernelGGL(k_cond_results, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const u64 *)words[rw]->data, n,
+                               (u32)chgpu_type_size(res_cols[j]->type), zero ? 1 : 0, res_cols[j]->data, (null_mode && null_maps) ? (u8 *)null_maps[j]->data : nullptr);
+            ctx->counters[6] += 1;
+        }
+    }
     for (u32 w = 0; w < a->n_pub_words; ++w)
         if (words[w])
-            chgpu_col_free(words[w]); // pooled: reuse is stream-ordered behind k_avg_divide
+            chgpu_col_free(words[w]); // pooled: reuse is stream-ordered behind k_avg_divide / k_cond_results
+    if (rc != CHGPU_OK)
+        for (u32 j = 0; j < a->n_aggs; ++j)
+        {
+            if (res_cols[j])
+                chgpu_col_free(res_cols[j]), res_cols[j] = nullptr;
+            if (null_maps && null_maps[j])
+                chgpu_col_free(null_maps[j]), null_maps[j] = nullptr;
+        }
     *groups = n;
     return rc;
+}
+
+extern "C" int chgpu_agg_finalize(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** res_cols, uint64_t * groups)
+{
+    ChgpuDeviceGuard _dev_guard(a ? a->ctx : nullptr);
+    CHGPU_REQUIRE(a && res_cols && groups, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    for (u32 j = 0; j < a->n_aggs; ++j)
+        CHGPU_REQUIRE(a->cond_modes[j] != CHGPU_AGG_COND_NULL || a->kinds[j] == CHGPU_AGG_COUNT, CHGPU_ERR_BAD_ARGUMENTS,
+                      "function %u has a Nullable result: chgpu_agg_finalize would lose its null map, use chgpu_agg_finalize_nullable", j);
+    return agg_finalize_impl(a, keys_out, res_cols, nullptr, groups);
+}
+
+extern "C" int chgpu_agg_finalize_nullable(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** res_cols, chgpu_col ** null_maps, uint64_t * groups)
+{
+    ChgpuDeviceGuard _dev_guard(a ? a->ctx : nullptr);
+    CHGPU_REQUIRE(a && res_cols && null_maps && groups, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    return agg_finalize_impl(a, keys_out, res_cols, null_maps, groups);
 }

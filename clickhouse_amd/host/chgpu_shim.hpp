@@ -869,10 +869,22 @@ struct AggregateDescription
     size_t argument = 0;   // position in the chunk
     int argument2_type = CHGPU_U64; // argMin / argMax: val's type
     size_t argument2 = 0;           // ... and its position in the chunk
+    /// the -If combinator (AggregateFunctionIf: `condition` is the UInt8 condition column) or a Nullable argument
+    /// (AggregateFunctionNull*: `condition` is the argument's null map; two Nullable arguments: the caller ORs their maps)
+    int condition_mode = CHGPU_AGG_COND_NONE; // CHGPU_AGG_COND_*
+    size_t condition = 0;                     // position in the chunk
 
     bool twoArguments() const { return kind == CHGPU_AGG_ARG_MIN || kind == CHGPU_AGG_ARG_MAX; }
-    /// 8-byte public state words: avg numerator + denominator; any claim + value; argMin / argMax val word + has + arg bits
-    size_t stateWords() const { return twoArguments() ? 3 : (kind == CHGPU_AGG_AVG || kind == CHGPU_AGG_ANY) ? 2 : 1; }
+    bool conditioned() const { return condition_mode != CHGPU_AGG_COND_NONE; }
+    /// a Nullable result: value column plus null map (count stays UInt64)
+    bool nullableResult() const { return condition_mode == CHGPU_AGG_COND_NULL && kind != CHGPU_AGG_COUNT; }
+    /// the `seen` word (rows that reached the function) behind a conditioned min / max and a NULL-mode sum
+    bool seenWord() const
+    {
+        return conditioned() && (kind == CHGPU_AGG_MIN || kind == CHGPU_AGG_MAX || (kind == CHGPU_AGG_SUM && condition_mode == CHGPU_AGG_COND_NULL));
+    }
+    /// 8-byte public state words: avg numerator + denominator; any claim + value; argMin / argMax val word + has + arg bits; + seen
+    size_t stateWords() const { return (twoArguments() ? 3 : (kind == CHGPU_AGG_AVG || kind == CHGPU_AGG_ANY) ? 2 : 1) + (seenWord() ? 1 : 0); }
     /// the C ABI's argument slots of this aggregate: one per argument (arg then val), appended to `types`
     void appendArgumentTypes(std::vector<int> & types) const
     {
@@ -887,6 +899,38 @@ struct AggregateDescription
             args.push_back(columns.at(argument2)->handle());
     }
 };
+
+/// chgpu_agg_set_conditions for a freshly created aggregation when some function is conditioned (frees `h` and throws on failure)
+inline bool anyConditioned(const std::vector<AggregateDescription> & aggregates)
+{
+    for (auto & a : aggregates)
+        if (a.conditioned())
+            return true;
+    return false;
+}
+inline void applyConditions(chgpu_agg *& h, const std::vector<AggregateDescription> & aggregates)
+{
+    if (!anyConditioned(aggregates))
+        return;
+    std::vector<int> modes;
+    for (auto & a : aggregates)
+        modes.push_back(a.condition_mode);
+    const int rc = chgpu_agg_set_conditions(h, modes.data());
+    if (rc != CHGPU_OK)
+    {
+        chgpu_agg_free(h);
+        h = nullptr;
+        check(rc);
+    }
+}
+/// the condition columns of a block, one per aggregate (NULL where the function has none)
+inline std::vector<const chgpu_col *> conditionColumns(const std::vector<AggregateDescription> & aggregates, const Columns & columns)
+{
+    std::vector<const chgpu_col *> conds;
+    for (auto & a : aggregates)
+        conds.push_back(a.conditioned() ? columns.at(a.condition)->handle() : nullptr);
+    return conds;
+}
 
 /// Aggregator::Params' GROUP BY limits (max_rows_to_group_by, group_by_overflow_mode, overflow_row); 0 rows = no limit
 struct GroupByLimits
@@ -920,6 +964,7 @@ public:
                 check(rc);
             }
         }
+        applyConditions(h, aggregates);
     }
     ~GpuAggregator() { chgpu_agg_free(h); }
     GpuAggregator(const GpuAggregator &) = delete;
@@ -932,13 +977,21 @@ public:
         for (auto & a : aggregates)
             a.appendArgumentColumns(columns, args);
         const chgpu_col * key = key_position ? columns.at(*key_position)->handle() : nullptr;
+        const bool conditioned = anyConditioned(aggregates);
+        const std::vector<const chgpu_col *> conds = conditioned ? conditionColumns(aggregates, columns) : std::vector<const chgpu_col *>();
         if (!limits.any())
         {
-            check(chgpu_agg_add_block(h, key, args.data(), row_begin, row_end));
+            if (conditioned)
+                check(chgpu_agg_execute_on_block_conditional(h, key, args.data(), conds.data(), row_begin, row_end, nullptr, nullptr, nullptr));
+            else
+                check(chgpu_agg_add_block(h, key, args.data(), row_begin, row_end));
             return true;
         }
         int nmk = no_more_keys ? 1 : 0, keep = 1;
-        check(chgpu_agg_execute_on_block(h, key, args.data(), row_begin, row_end, nullptr, &nmk, &keep));
+        if (conditioned)
+            check(chgpu_agg_execute_on_block_conditional(h, key, args.data(), conds.data(), row_begin, row_end, nullptr, &nmk, &keep));
+        else
+            check(chgpu_agg_execute_on_block(h, key, args.data(), row_begin, row_end, nullptr, &nmk, &keep));
         no_more_keys = nmk != 0;
         return keep != 0;
     }
@@ -981,20 +1034,32 @@ public:
             out.columns.push_back(std::make_shared<ColumnVector>(ctx, r));
         return out;
     }
-    /// convertToBlocks(final = true): [key column,] one column per aggregate
+    /// convertToBlocks(final = true): [key column,] one column per aggregate, then one UInt8 null-map column per aggregate with a
+    /// Nullable result, in aggregate order (the binding wraps value + map into a ColumnNullable)
     Chunk convertToBlock() const
     {
         chgpu_col * keys = nullptr;
-        std::vector<chgpu_col *> res(aggregates.size(), nullptr);
+        std::vector<chgpu_col *> res(aggregates.size(), nullptr), maps(aggregates.size(), nullptr);
         uint64_t groups = 0;
-        check(chgpu_agg_finalize(h, &keys, res.data(), &groups));
+        check(chgpu_agg_finalize_nullable(h, &keys, res.data(), maps.data(), &groups));
         Chunk out;
         out.num_rows = groups;
         if (keys)
             out.columns.push_back(std::make_shared<ColumnVector>(ctx, keys));
         for (auto * r : res)
             out.columns.push_back(std::make_shared<ColumnVector>(ctx, r));
+        for (auto * m : maps)
+            if (m)
+                out.columns.push_back(std::make_shared<ColumnVector>(ctx, m));
         return out;
+    }
+    /// the public state words of one group (the state columns of a not-final block)
+    size_t stateWords() const
+    {
+        size_t n = 0;
+        for (auto & a : aggregates)
+            n += a.stateWords();
+        return n;
     }
     size_t size() const
     {
@@ -1577,6 +1642,7 @@ public:
             n_words += a.stateWords();
         }
         check(chgpu_agg_create(ctx->get(), key_type, static_cast<uint32_t>(aggregates.size()), kinds.data(), types.data(), size_hint, &local));
+        applyConditions(local, aggregates);
     }
     ~GpuShardedAggregator()
     {
@@ -1590,7 +1656,11 @@ public:
         std::vector<const chgpu_col *> args;
         for (auto & a : aggregates)
             a.appendArgumentColumns(columns, args);
-        check(chgpu_agg_add_block(local, columns.at(key_position)->handle(), args.data(), row_begin, row_end));
+        if (anyConditioned(aggregates))
+            check(chgpu_agg_execute_on_block_conditional(local, columns.at(key_position)->handle(), args.data(), conditionColumns(aggregates, columns).data(),
+                                                         row_begin, row_end, nullptr, nullptr, nullptr));
+        else
+            check(chgpu_agg_add_block(local, columns.at(key_position)->handle(), args.data(), row_begin, row_end));
         return true;
     }
 
@@ -1611,7 +1681,10 @@ public:
                 states.columns.push_back(std::make_shared<ColumnVector>(ctx, w));
             Chunk mine = dispatchBlock(*comm, states, 0);
             if (!owner)
+            {
                 check(chgpu_agg_create(ctx->get(), key_type, static_cast<uint32_t>(aggregates.size()), kinds.data(), types.data(), mine.num_rows, &owner));
+                applyConditions(owner, aggregates);
+            }
             std::vector<const chgpu_col *> sc;
             for (size_t w = 0; w < n_words; ++w)
                 sc.push_back(mine.columns[1 + w]->handle());
@@ -1619,14 +1692,17 @@ public:
             final_agg = owner;
         }
         chgpu_col * keys = nullptr;
-        std::vector<chgpu_col *> res(aggregates.size(), nullptr);
+        std::vector<chgpu_col *> res(aggregates.size(), nullptr), maps(aggregates.size(), nullptr);
         uint64_t groups = 0;
-        check(chgpu_agg_finalize(final_agg, &keys, res.data(), &groups));
+        check(chgpu_agg_finalize_nullable(final_agg, &keys, res.data(), maps.data(), &groups));
         Chunk out;
         out.num_rows = groups;
         out.columns.push_back(std::make_shared<ColumnVector>(ctx, keys));
         for (auto * r : res)
             out.columns.push_back(std::make_shared<ColumnVector>(ctx, r));
+        for (auto * m : maps) // (as GpuAggregator::convertToBlock: the null maps of the Nullable results behind the values)
+            if (m)
+                out.columns.push_back(std::make_shared<ColumnVector>(ctx, m));
         return out;
     }
 
@@ -1772,6 +1848,7 @@ private:
             hint += c.num_rows;
         chgpu_agg * agg = nullptr;
         check(chgpu_agg_create(ctx->get(), key_type, static_cast<uint32_t>(aggregates.size()), kinds.data(), types.data(), hint, &agg));
+        applyConditions(agg, aggregates);
         struct Free { void operator()(chgpu_agg * a) const { chgpu_agg_free(a); } };
         std::unique_ptr<chgpu_agg, Free> guard(agg);
         for (auto & c : chunks)
@@ -1784,12 +1861,16 @@ private:
         chgpu_col * keys = nullptr;
         std::vector<chgpu_col *> cols(final_result ? aggregates.size() : n_words, nullptr);
         uint64_t groups = 0;
-        check(final_result ? chgpu_agg_finalize(agg, &keys, cols.data(), &groups) : chgpu_agg_export_states(agg, &keys, cols.data(), &groups));
+        std::vector<chgpu_col *> maps(aggregates.size(), nullptr);
+        check(final_result ? chgpu_agg_finalize_nullable(agg, &keys, cols.data(), maps.data(), &groups) : chgpu_agg_export_states(agg, &keys, cols.data(), &groups));
         Chunk out;
         out.num_rows = groups;
         out.columns.push_back(std::make_shared<ColumnVector>(ctx, keys));
         for (auto * c : cols)
             out.columns.push_back(std::make_shared<ColumnVector>(ctx, c));
+        for (auto * m : maps) // (as GpuAggregator::convertToBlock: the null maps of the Nullable results behind the values)
+            if (m)
+                out.columns.push_back(std::make_shared<ColumnVector>(ctx, m));
         return out;
     }
 

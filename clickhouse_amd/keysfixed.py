@@ -83,7 +83,7 @@ class KeysFixedAggregator:
     def no_more_keys(self) -> bool:
         return self.inner.no_more_keys
 
-    def execute_on_block(self, key_cols, args, row_begin: int = 0, row_end: int | None = None) -> bool:
+    def execute_on_block(self, key_cols, args, row_begin: int = 0, row_end: int | None = None, conds=None) -> bool:
         # once no_more_keys is set the dictionary stops growing: an absent key gets 0xFFFFFFFF, which the table lacks (a miss)
         ids = self.dict.encode(key_cols, not self.inner.no_more_keys, row_begin, row_end)
         # (an argMin / argMax entry is an (arg, val) pair and stays one)
@@ -92,22 +92,29 @@ class KeysFixedAggregator:
         if row_begin or row_end is not None:
             n = ids.size()
             acols = [each(lambda c: c.cut(row_begin, n), a) for a in acols]
-        return self.inner.execute_on_block(ids, acols)
+        # the condition columns / null maps of "if" / "null" aggregates only pass through: they are cut like the arguments
+        if conds is not None:
+            conds = [each(self.ctx.column, c) for c in conds]
+            if row_begin or row_end is not None:
+                conds = [each(lambda c: c.cut(row_begin, ids.size()), c) for c in conds]
+        return self.inner.execute_on_block(ids, acols, conds=conds)
 
-    def overflow_row(self, final: bool = True):
-        return self.inner.overflow_row(final)
+    def overflow_row(self, final: bool = True, null_maps: bool = False):
+        return self.inner.overflow_row(final, null_maps=null_maps)
 
     def __len__(self):
         return len(self.inner)
 
-    def finalize_columns(self):
-        ids, res = self.inner.finalize_columns()
-        return self.dict.key_columns(ids), res
+    def finalize_columns(self, null_maps: bool = False):
+        ids, *rest = self.inner.finalize_columns(null_maps=null_maps)
+        return (self.dict.key_columns(ids), *rest)
 
-    def convert_to_block(self):
-        """-> ([key ndarrays], [result ndarrays]); row order unspecified, as in the reference"""
-        keys, res = self.finalize_columns()
-        return [k.numpy() for k in keys], [r.numpy() for r in res]
+    def convert_to_block(self, null_maps: bool = False):
+        """-> ([key ndarrays], [result ndarrays]); row order unspecified, as in the reference.  null_maps: a third element, one uint8
+        ndarray or None per aggregate"""
+        keys, res, *maps = self.finalize_columns(null_maps=null_maps)
+        out = [k.numpy() for k in keys], [r.numpy() for r in res]
+        return out + ([m.numpy() if m is not None else None for m in maps[0]],) if null_maps else out
 
 
 class KeysFixedHashJoin:
@@ -189,16 +196,16 @@ class FixedStringAggregator:
         self.inner = (KeysFixedAggregator([np.uint64] * ((n + 7) // 8), aggs, size_hint, self.ctx) if self.wide
                       else Aggregator(np.uint64, aggs, size_hint=size_hint, ctx=self.ctx))
 
-    def execute_on_block(self, key: ColumnFixedString, args):
+    def execute_on_block(self, key: ColumnFixedString, args, conds=None):
         assert key.n == self.n
         words = key.words()
-        self.inner.execute_on_block(words if self.wide else words[0], args)
+        self.inner.execute_on_block(words if self.wide else words[0], args, conds=conds)
 
     def __len__(self):
         return len(self.inner)
 
     def convert_to_block(self):
         """-> (keys as an 'S<n>' ndarray, [result ndarrays])"""
-        keys, res = self.inner.finalize_columns()
+        keys, res = self.inner.finalize_columns()[:2]
         words = keys if self.wide else [keys]
         return ColumnFixedString.from_words(self.ctx, words, self.n).numpy(), [r.numpy() for r in res]

@@ -213,15 +213,15 @@ class LowCardinalityAggregator:
         self.dictionary = LowCardinalityDictionary(self.ctx)
         self.agg = Aggregator(np.uint32, aggs, size_hint=size_hint, ctx=self.ctx)
 
-    def execute_on_block(self, keys: ColumnLowCardinality, args, row_begin: int = 0, row_end: int | None = None, filter=None):
-        self.agg.execute_on_block(self.dictionary.map_block(keys), args, row_begin, row_end, filter=filter)
+    def execute_on_block(self, keys: ColumnLowCardinality, args, row_begin: int = 0, row_end: int | None = None, filter=None, conds=None):
+        self.agg.execute_on_block(self.dictionary.map_block(keys), args, row_begin, row_end, filter=filter, conds=conds)
 
     def __len__(self):
         return len(self.agg)
 
-    def convert_to_block(self):
-        ids, res = self.agg.convert_to_block()
-        return self.dictionary.decode(ids), res
+    def convert_to_block(self, null_maps: bool = False):
+        ids, *rest = self.agg.convert_to_block(null_maps=null_maps)
+        return (self.dictionary.decode(ids), *rest)
 
 
 class PackedKeysAggregator:
@@ -246,7 +246,7 @@ class PackedKeysAggregator:
         self._narrow = d.compile()
         self.agg = Aggregator(np.uint64, aggs, size_hint=size_hint, ctx=self.ctx)
 
-    def execute_on_block(self, keys, args, filter=None):
+    def execute_on_block(self, keys, args, filter=None, conds=None):
         from .columns import pack_fixed_keys
         cols = []
         for k, kind, dic in zip(keys, self.kinds, self.dicts):
@@ -257,7 +257,7 @@ class PackedKeysAggregator:
                 cols.append(self._narrow.execute(self.ctx, [ids], [1])[0])
             else:
                 cols.append(self.ctx.column(k))
-        self.agg.execute_on_block(pack_fixed_keys(cols), args, filter=filter)
+        self.agg.execute_on_block(pack_fixed_keys(cols), args, filter=filter, conds=conds)
 
     def __len__(self):
         return len(self.agg)

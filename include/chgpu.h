@@ -610,6 +610,34 @@ int chgpu_agg_merge_states_limited(chgpu_agg * dst, const chgpu_col * key_col, c
    raw state words (as chgpu_agg_export_states).  *has = 0 when there is none (no executeOnBlock yet with overflow_row on).  The
    overflow row is never part of chgpu_agg_size, the exports or chgpu_agg_finalize. */
 int chgpu_agg_overflow_row(chgpu_agg * agg, int final, chgpu_col ** cols, int * has);
+/* ---- the -If combinator and Nullable arguments (AggregateFunctionIf; AggregateFunctionNullUnary, AggregateFunctionCountNotNullUnary) ----
+   Every aggregate function has a condition mode.  A group exists as soon as one of its rows passes the WHERE filter, whatever the
+   per-function masks say (the key is emplaced before any add): masked-out rows count towards max_rows_to_group_by like any other.
+     NONE  every row reaches the function.
+     IF    a row reaches it when its UInt8 condition byte is non-zero (2 and 255 as much as 1).  No row reached it: count 0, sum 0,
+           avg NaN, min / max / any / argMin / argMax the type's default.
+     NULL  a row reaches it when its null-map byte is zero.  The result is Nullable: chgpu_agg_finalize_nullable returns the value
+           column and a UInt8 null map; no row reached it: null-map byte 1 and the type's default as the nested value (avg: 0.0).
+           count stays UInt64 without a map and counts the non-NULL rows.
+   A two-argument function takes one condition column (the caller ORs the null maps); sumIf over a Nullable argument is NULL mode
+   with the map `null OR NOT cond` (AggregateFunctionIfNullUnary).
+   State words: a conditioned min / max and a NULL-mode sum carry one more public word behind their own, `seen` = the number of rows
+   that reached the function (UInt64, merged by addition like a count); it travels through the exports and chgpu_agg_merge_states*
+   like every other word.  More than 16 words in all: CHGPU_ERR_BAD_ARGUMENTS.  The wire bytes of chgpu_agg_serialize_states know
+   nothing about it: an -If state serialises as its nested function's (count / sum / avg); NULL-mode states have no wire form here. */
+enum { CHGPU_AGG_COND_NONE = 0, CHGPU_AGG_COND_IF = 1, CHGPU_AGG_COND_NULL = 2 };
+/* before the first block or merge (else BAD_ARGUMENTS); cond_modes[n_aggs] */
+int chgpu_agg_set_conditions(chgpu_agg * agg, const int * cond_modes);
+/* cond_cols[n_aggs]: UInt8 columns over the same rows as the arguments (NULL where the mode is NONE); the same column may serve several
+   functions.  filter_u8 (WHERE) may be NULL.  no_more_keys / keep_reading may both be NULL: then as chgpu_agg_add_block(_filtered),
+   else as chgpu_agg_execute_on_block.  An aggregator without conditions accepts cond_cols == NULL; one WITH conditions only accepts
+   this call (chgpu_agg_add_block, _filtered and chgpu_agg_execute_on_block answer BAD_ARGUMENTS). */
+int chgpu_agg_execute_on_block_conditional(chgpu_agg * agg, const chgpu_col * key_col, const chgpu_col * const * arg_cols,
+                                           const chgpu_col * const * cond_cols, uint64_t row_begin, uint64_t row_end,
+                                           const chgpu_col * filter_u8, int * no_more_keys, int * keep_reading);
+/* as chgpu_agg_finalize; null_maps[n_aggs] receives a UInt8 column for every NULL-mode function but count, NULL elsewhere.
+   (chgpu_agg_finalize itself applies the defaults too, and answers BAD_ARGUMENTS when a map would be lost.) */
+int chgpu_agg_finalize_nullable(chgpu_agg * agg, chgpu_col ** keys_out, chgpu_col ** res_cols, chgpu_col ** null_maps, uint64_t * groups);
 
 /* ================================================================================================
  * a19/a20 hash join  —  IJoin::addBlockToJoin / onBuildPhaseFinish / joinBlock (src/Interpreters/IJoin.h:80-93,142)
