@@ -58,6 +58,78 @@ struct AggCtrl
 };
 static constexpr size_t AGG_HDR_BYTES = (sizeof(AggCtrl) + 255) / 256 * 256;
 
+// What a function kind needs, one row per CHGPU_AGG_* in the enum's order.  The per-kind update itself stays with add_row / add_vals.
+struct AggKind
+{
+    unsigned char slots;    // argument slots: 0, 1 or 2 (argMin / argMax: arg, then val)
+    unsigned char words;    // value words: 1, 2 or 3 (a conditioned function's `seen` word follows them, see agg_layout)
+    unsigned char extremum; // it combines by a max or a claim, not by an add: its rows take the DIRECT kernel
+    unsigned char result;   // which of its words holds the result (avg: the numerator)
+    unsigned char reached;  // which word is non-zero once a row reached it; AGG_SEEN_WORD (== words): none of its own -- the `seen` word behind them, where the layout gave it one
+};
+static constexpr u32 AGG_N_KINDS = 8;
+static constexpr unsigned char AGG_SEEN_WORD = 1; // `reached` of the one-word kinds
+static constexpr AggKind AGG_KINDS[AGG_N_KINDS] = {
+    {0, 1, 0, 0, AGG_SEEN_WORD}, // count
+    {1, 1, 0, 0, AGG_SEEN_WORD}, // sum
+    {1, 2, 0, 0, 1},             // avg {numerator, denominator}
+    {1, 1, 1, 0, AGG_SEEN_WORD}, // min
+    {1, 1, 1, 0, AGG_SEEN_WORD}, // max
+    {1, 2, 1, 1, 0}, // any {claim, value}
+    {2, 3, 1, 2, 1}, // argMin {val key, claim, arg}
+    {2, 3, 1, 2, 1}, // argMax
+};
+constexpr bool agg_kinds_reached_ok()
+{
+    for (u32 k = 0; k < AGG_N_KINDS; ++k)
+        if (AGG_KINDS[k].reached > AGG_KINDS[k].words || (AGG_KINDS[k].reached == AGG_KINDS[k].words && AGG_KINDS[k].words != AGG_SEEN_WORD))
+            return false;
+    return true;
+}
+static_assert(agg_kinds_reached_ok(), "reached names one of the kind's own words, or -- for a one-word kind only -- the seen word behind it");
+static_assert(CHGPU_AGG_COUNT == 0 && CHGPU_AGG_SUM == 1 && CHGPU_AGG_AVG == 2 && CHGPU_AGG_MIN == 3 && CHGPU_AGG_MAX == 4 && CHGPU_AGG_ANY == 5 &&
+                  CHGPU_AGG_ARG_MIN == 6 && CHGPU_AGG_ARG_MAX == 7,
+              "AGG_KINDS is indexed by CHGPU_AGG_*");
+static constexpr bool agg_kind_known(int kind) { return kind >= 0 && (u32)kind < AGG_N_KINDS; }
+static constexpr const AggKind & agg_kind(int kind) { return AGG_KINDS[kind]; }
+
+// What each state word of an aggregation is: one bit per word and class.  The aggregator holds one, a kernel's descriptor embeds one
+// (a pass over some of the functions: re-expressed in its local numbering, agg_localise_words), the merge kernels take one as it is.
+struct AggWords
+{
+    u32 n_words;     // every word, the appended high halves of the fixed-point sums included
+    u32 n_pub_words; // the first n_pub_words are the words the C ABI shows (state columns, wire format)
+    u32 f64;         // bit w: word w combines by a Float64 add
+    u32 max;         // bit w: word w combines by an unsigned max (min / max order keys, any()'s claim), never by an add
+    // deterministic Float64 sums (see Fx128): bit w of fx = word w is the LOW half of a 128-bit fixed-point sum whose high half is word
+    // fx_hi[w] (one of the words appended behind the regular ones, bit fx_hi[w] of fx_high: never updated on its own)
+    u32 fx, fx_high;
+    u32 any;  // bit w: word w is any()'s claim, word w + 1 its value
+    u32 arg;  // bit w: words w, w + 1, w + 2 are the {val key, claim, arg} of an argMin / argMax
+    u32 seen; // bit w: word w counts the rows that reached the conditioned function whose value word(s) end at w - 1
+    unsigned char fx_hi[AGG_MAX_WORDS];
+    // how word w combines, as global_add_word takes it: 0 integer add, 1 Float64 add, 2 unsigned max
+    __host__ __device__ __forceinline__ int op(u32 w) const { return ((max >> w) & 1) ? 2 : (int)((f64 >> w) & 1); }
+    // the type of public word w's state column (a fixed-point pair leaves as the Float64 it stands for)
+    int pub_type(u32 w) const { return (((f64 | fx) >> w) & 1) ? CHGPU_F64 : CHGPU_U64; }
+};
+
+// An AggWords as k_agg_tuples takes it.  That kernel uses the last SGPR that still gives 8 waves per SIMD and every mask is live across
+// its row loop, so the two combine masks travel in one word there: bit w of `ops` = Float64 add, bit AGG_MAX_WORDS + w = unsigned max.
+// The members a merge never reads stay behind.  Same member names and op(w) as AggWords: ovf_flush takes either.
+struct AggMergeWords
+{
+    u32 n_words, ops, fx, fx_high, any, arg;
+    unsigned char fx_hi[AGG_MAX_WORDS];
+    explicit AggMergeWords(const AggWords & ws)
+        : n_words(ws.n_words), ops(ws.f64 | (ws.max << AGG_MAX_WORDS)), fx(ws.fx), fx_high(ws.fx_high), any(ws.any), arg(ws.arg)
+    {
+        memcpy(fx_hi, ws.fx_hi, sizeof(fx_hi));
+    }
+    __device__ __forceinline__ int op(u32 w) const { return ((ops >> (AGG_MAX_WORDS + w)) & 1) ? 2 : (int)((ops >> w) & 1); }
+};
+static_assert(2 * AGG_MAX_WORDS <= 32, "AggMergeWords::ops holds two masks");
+
 struct AggArg
 {
     const void * ptr; // argument column (NULL for count); argMin / argMax: the `arg` column, the one the result comes from
@@ -75,27 +147,24 @@ struct AggArg
 
 struct AggDesc
 {
-    u32 n_aggs;
-    u32 n_words;
-    AggArg a[AGG_MAX_AGGS];
-    u32 word_is_f64; // bit w set: state word w is Float64
-    // deterministic Float64 sums (see Fx128): bit w set = word w is the LOW half of a 128-bit fixed-point sum whose high half is word
-    // fx_hi[w] (one of the words appended behind the regular ones); values are multiples of 2^fx_base
-    u32 word_fx;
-    u32 word_fx_hi; // the high halves (never updated on their own)
-    unsigned char fx_hi[AGG_MAX_WORDS];
-    int fx_base;
-    u64 row_seq; // any(): row i of the argument columns is the (row_seq + i)-th row this aggregation has seen (modulo 2^64)
-    // argMin / argMax: the claim a raised extremum falls back to, that of the ordinal behind the block's last row: below the claim of
-    // every row of this and every earlier block (see raise_extremum)
-    u64 arg_sentinel;
-    u32 word_arg; // bit w: words w, w + 1, w + 2 are the {val key, claim, arg} of an argMin / argMax (table words: such rows take the DIRECT kernel)
+    // The ORDER of the members is chosen by what the compiler makes of it: the struct is a kernel argument, and the SGPR spills of the
+    // LDS-staged kernels follow its layout (profiles/agg_state_words_resources.md).  Reorder only with the resource table at hand.
     // A pass over a SUBSET of the functions (one argument word at a time through the tile-sorted plan) numbers its state words locally
     // (0 .. n_words - 1: the LDS cells hold only those) and finds the table's words through this map; the identity otherwise.
     unsigned char word_map[AGG_MAX_WORDS];
+    // argMin / argMax: the claim a raised extremum falls back to, that of the ordinal behind the block's last row: below the claim of
+    // every row of this and every earlier block (see raise_extremum)
+    u64 arg_sentinel;
+    u32 n_aggs;
+    int fx_base; // the fixed-point sums' values are multiples of 2^fx_base
+    u64 row_seq; // any(): row i of the argument columns is the (row_seq + i)-th row this aggregation has seen (modulo 2^64)
+    // (`arg` and `any` are in table numbering: such rows take the DIRECT kernel, which numbers nothing locally; the localised form of a
+    // subset pass -- additive functions only -- has neither, nor `seen`)
+    AggWords words;
     // the distinct condition columns of the block (UInt8, indexed like the arguments); n_conds = 0: no function is conditioned
-    u32 n_conds;
     const u8 * cond[AGG_MAX_AGGS];
+    u32 n_conds;
+    AggArg a[AGG_MAX_AGGS];
 };
 
 struct AggTable
@@ -115,14 +184,18 @@ struct chgpu_agg
 {
     chgpu_ctx * ctx = nullptr;
     int key_type = -1;
-    u32 n_aggs = 0, n_words = 0;
+    u32 n_aggs = 0;
     int kinds[AGG_MAX_AGGS];
     int arg_types[AGG_MAX_AGGS];
     int val_types[AGG_MAX_AGGS]; // argMin / argMax: the type of `val` (arg_types[j] is `arg`'s, the result's)
     u32 slot[AGG_MAX_AGGS];      // the aggregate's first argument slot: arg_cols[] is indexed by slot, argMin / argMax own two (arg, val)
     u32 n_slots = 0;
     u32 word_off[AGG_MAX_AGGS];
-    u32 word_is_f64 = 0;
+    // The state words (agg_layout).  any(): claim = ~(ordinal of the row that set the value) under an unsigned max: the EARLIEST row of
+    // the group wins whatever order the hardware serves the rows in; the value is stored by a second pass from the winner's row
+    // (k_agg_any_resolve).  argMin / argMax: the val key combines like a min / max word, the claim names the earliest row (or merged
+    // state) that holds that extremum, the arg is stored from the claim's row (k_agg_arg_rows).
+    AggWords words{};
     u64 size_hint = 0;
     AggTable t{nullptr, nullptr, 0, 0, nullptr};
     void * table_mem = nullptr; // from the context's column pool (stream-ordered reuse: no hipMalloc/hipFree per query)
@@ -130,20 +203,10 @@ struct chgpu_agg
     u64 n_groups = 0; // host copy, refreshed after every call
     bool hint_probed = false; // the cardinality of a hint-less aggregation was sampled on its first large block
     bool has_extremum = false; // some function is min / max / any: rows take the DIRECT kernel (the LDS-staged plans only know how to add)
-    // any(): {claim, value} words.  claim = ~(ordinal of the row that set the value) under an unsigned max: the EARLIEST row of the group
-    // wins whatever order the hardware serves the rows in; the value is stored by a second pass from the winner's row (k_agg_any_resolve)
-    u32 word_any = 0; // bit w: word w is a claim, word w + 1 its value
-    // argMin / argMax: {val key, claim, arg} words.  The val key combines like a min / max word, the claim names the earliest row (or
-    // merged state) that holds that extremum, the arg is stored from the claim's row (k_agg_arg_rows)
-    u32 word_arg = 0; // bit w: word w is a val key, w + 1 its claim, w + 2 its arg
     u64 any_seq = 0;  // rows seen so far
     u64 nokey_kept = 0; // without key: rows that reached the states (0 = min / max / any have no value: insertResultInto gives the default)
     // deterministic Float64 sums (option deterministic_float_sums, the default): sum / avg over a float argument keep a 128-bit fixed-point
-    // state {word, fx_hi[word]} in units of 2^fx_base instead of a double.  n_words counts the appended high halves too; the first
-    // n_pub_words are the words the C ABI shows (state columns, wire format): exports fold a pair back into its Float64 column.
-    u32 n_pub_words = 0;
-    u32 word_fx = 0, word_fx_hi = 0;
-    unsigned char fx_hi[AGG_MAX_WORDS] = {0};
+    // state {word, words.fx_hi[word]} in units of 2^fx_base instead of a double; exports fold a pair back into its Float64 column.
     // window invariant: every state is a sum of at most fx_rows values, each below 2^(127 - fx_log_cap) units of 2^fx_base
     int fx_base = 0;
     bool fx_base_set = false;
@@ -158,11 +221,9 @@ struct chgpu_agg
     bool started = false;          // some block or merge has reached the aggregation
     void * ovf_mem = nullptr;      // the overflow row's state words on the device (AGG_MAX_WORDS x 8 B), from the first call with overflow_row on
     size_t ovf_class = 0;
-    // -If / -Null combinators (chgpu_agg_set_conditions): CHGPU_AGG_COND_* per function; word_seen: bit w = word w counts the rows that
-    // reached the function whose value word(s) end at w - 1
+    // -If / -Null combinators (chgpu_agg_set_conditions): CHGPU_AGG_COND_* per function
     int cond_modes[AGG_MAX_AGGS] = {0};
     bool conditioned = false;
-    u32 word_seen = 0;
     const chgpu_col * const * block_conds = nullptr; // the condition columns of the block being added ([n_aggs], set for the call's duration)
 };
 
@@ -486,8 +547,8 @@ __device__ __forceinline__ void add_row(const Sink & sink, const AggDesc & d, u6
         }
         else
         {
-            if ((d.word_fx >> a.word) & 1)
-                sink.add_fx(w, sink.at(d.word_map[d.fx_hi[a.word]]), fx_from_double(load_arg_bits(a.ptr, a.arg_type, i), d.fx_base));
+            if ((d.words.fx >> a.word) & 1)
+                sink.add_fx(w, sink.at(d.word_map[d.words.fx_hi[a.word]]), fx_from_double(load_arg_bits(a.ptr, a.arg_type, i), d.fx_base));
             else
                 sink.add_word(w, load_arg_bits(a.ptr, a.arg_type, i), a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
             if (a.kind == CHGPU_AGG_AVG)
@@ -509,8 +570,8 @@ __device__ __forceinline__ void add_vals(const Sink & sink, const AggDesc & d, u
             sink.add_word(w, cnt, 0);
         else
         {
-            if ((d.word_fx >> a.word) & 1)
-                sink.add_fx(w, sink.at(d.word_map[d.fx_hi[a.word]]), fx_from_double(a.pre == 0 ? bits0 : bits1, d.fx_base));
+            if ((d.words.fx >> a.word) & 1)
+                sink.add_fx(w, sink.at(d.word_map[d.words.fx_hi[a.word]]), fx_from_double(a.pre == 0 ? bits0 : bits1, d.fx_base));
             else
                 sink.add_word(w, a.pre == 0 ? bits0 : bits1, a.arg_type == CHGPU_F64 || a.arg_type == CHGPU_F32);
             if (a.kind == CHGPU_AGG_AVG || a.seen)
@@ -580,13 +641,13 @@ struct LdsRowSink
 template <typename Sink>
 __device__ __forceinline__ void add_cell_word(const Sink & sink, const AggDesc & d, u32 w, u64 bits, u64 hb)
 {
-    if ((d.word_fx >> w) & 1)
+    if ((d.words.fx >> w) & 1)
     {
         if (bits | hb)
-            sink.add_fx(sink.at(d.word_map[w]), sink.at(d.word_map[d.fx_hi[w]]), Fx128{bits, hb});
+            sink.add_fx(sink.at(d.word_map[w]), sink.at(d.word_map[d.words.fx_hi[w]]), Fx128{bits, hb});
     }
     else if (bits != 0)
-        sink.add_word(sink.at(d.word_map[w]), bits, (d.word_is_f64 >> w) & 1);
+        sink.add_word(sink.at(d.word_map[w]), bits, (d.words.f64 >> w) & 1); // (an LDS cell holds additive words only: no max to test)
 }
 // Place a row or leave it pending: `add(sink)` adds the row's contribution to the cell of `key`, or, in find-only mode, to the overflow
 // row `s_ovf` (when there is one) if the table lacks the key.  Returns true when the row must wait for a bigger table.
@@ -606,22 +667,23 @@ __device__ __forceinline__ bool place_and_add(const AggTable & t, u64 * s_ovf, u
     return false;
 }
 // The workgroup's combined misses to the overflow row: one global update per state word (call after a barrier, every thread).  Local
-// words 0 .. n_words-1 map to table words through `map`; masks as in AggDesc (word_is_f64: bit w Float64 add, bit 16 + w unsigned max).
-// any_merge: any() {claim, value} pairs that arrive together (merges: the first state that claims the overflow row keeps it,
-// changeFirstTime) -- a row's claim instead combines by max and its value is stored by the winning row later (k_agg_any_resolve).
-// arg_mask: argMin / argMax val keys (table words): raised like a cell's, with `arg_sentinel`; their claim and arg words follow in the
+// words 0 .. n_words-1 of `ws` map to table words through `map` (NULL: the identity).
+// merge: any() {claim, value} pairs arrive together (the first state that claims the overflow row keeps it, changeFirstTime) -- a
+// row's claim instead combines by max and its value is stored by the winning row later (k_agg_any_resolve).
+// ws.arg: argMin / argMax val keys (table words): raised like a cell's, with `arg_sentinel`; their claim and arg words follow in the
 // claim and resolve passes.
-__device__ __forceinline__ void ovf_flush(const AggTable & t, const u64 * s, u32 n_words, u32 f64, u32 fx, u32 fx_hi_mask, const unsigned char * fx_hi,
-                                          const unsigned char * map, u32 any_merge, u32 arg_mask, u64 arg_sentinel)
+template <typename Words> // AggWords or AggMergeWords
+__device__ __forceinline__ void ovf_flush(const AggTable & t, const u64 * s, const Words & ws, const unsigned char * map, bool merge, u64 arg_sentinel)
 {
     const u32 w = threadIdx.x;
-    if (!t.ovf || w >= n_words || ((fx_hi_mask >> w) & 1) || (w > 0 && ((any_merge >> (w - 1)) & 1)))
+    const u32 any_merge = merge ? ws.any : 0;
+    if (!t.ovf || w >= ws.n_words || ((ws.fx_high >> w) & 1) || (w > 0 && ((any_merge >> (w - 1)) & 1)))
         return;
-    const u32 gw = map ? map[w] : w; // (NULL: the identity)
-    if ((((arg_mask << 1) | (arg_mask << 2)) >> gw) & 1)
+    const u32 gw = map ? map[w] : w;
+    if ((((ws.arg << 1) | (ws.arg << 2)) >> gw) & 1)
         return; // a claim or an arg word
     const u64 bits = s[gw];
-    if ((arg_mask >> gw) & 1)
+    if ((ws.arg >> gw) & 1)
     {
         raise_extremum(t.ovf + gw, t.ovf + gw + 1, bits, arg_sentinel);
         return;
@@ -632,20 +694,19 @@ __device__ __forceinline__ void ovf_flush(const AggTable & t, const u64 * s, u32
             __hip_atomic_store((unsigned long long *)(t.ovf + gw + 1), (unsigned long long)s[gw + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
-    if ((fx >> w) & 1)
+    if ((ws.fx >> w) & 1)
     {
-        const u32 gh = map ? map[fx_hi[w]] : fx_hi[w];
+        const u32 gh = map ? map[ws.fx_hi[w]] : ws.fx_hi[w];
         if (bits | s[gh])
             global_add_fx(t.ovf + gw, t.ovf + gh, Fx128{bits, s[gh]});
         return;
     }
-    const int op = ((f64 >> (16 + w)) & 1) ? 2 : (int)((f64 >> w) & 1);
     if (bits != 0)
-        global_add_word(t.ovf + gw, bits, op);
+        global_add_word(t.ovf + gw, bits, ws.op(w));
 }
 __device__ __forceinline__ void ovf_flush_desc(const AggTable & t, const u64 * s, const AggDesc & d)
 {
-    ovf_flush(t, s, d.n_words, d.word_is_f64, d.word_fx, d.word_fx_hi, d.fx_hi, d.word_map, 0, d.word_arg, d.arg_sentinel);
+    ovf_flush(t, s, d.words, d.word_map, false, d.arg_sentinel);
 }
 
 // ---- the workgroup's LDS table of the LDS-staged kernels ----
@@ -716,13 +777,13 @@ __device__ __forceinline__ void lds_flush(const AggTable & t, const AggDesc & d,
         const bool miss = slot == AGG_SLOT_MISS;
         if (miss && !t.ovf)
             continue;
-        for (u32 w = 0; w < d.n_words; ++w)
+        for (u32 w = 0; w < d.words.n_words; ++w)
         {
-            if ((d.word_fx_hi >> w) & 1)
+            if ((d.words.fx_high >> w) & 1)
                 continue; // flushed with its low half
             const unsigned char * wp = lds_raw + L.off(w);
             const u64 bits = ((L.cnt32 >> w) & 1) ? (u64)((const u32 *)wp)[s] : ((const u64 *)wp)[s];
-            const u64 hb = ((d.word_fx >> w) & 1) ? ((const u64 *)(lds_raw + L.off(d.fx_hi[w])))[s] : 0;
+            const u64 hb = ((d.words.fx >> w) & 1) ? ((const u64 *)(lds_raw + L.off(d.words.fx_hi[w])))[s] : 0;
             if (miss)
                 add_cell_word(LdsRowSink{s_ovf}, d, w, bits, hb);
             else
@@ -789,7 +850,7 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
     __shared__ u32 lzero;
     __shared__ u64 s_ovf[AGG_MAX_WORDS];
     const u32 lstride = S + 1;
-    for (u32 s = threadIdx.x; s < (d.n_words + 1) * lstride; s += blockDim.x)
+    for (u32 s = threadIdx.x; s < (d.words.n_words + 1) * lstride; s += blockDim.x)
         lkeys[s] = 0;
     if (threadIdx.x == 0)
         lzero = 0;
@@ -813,7 +874,7 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
         a_kind[j] = on ? d.a[j].kind : -1;
         a_type[j] = on ? d.a[j].arg_type : 0;
         a_word[j] = on ? d.a[j].word : 0;
-        a_hi[j] = (on && d.a[j].kind != CHGPU_AGG_COUNT && ((d.word_fx >> d.a[j].word) & 1)) ? d.fx_hi[d.a[j].word] : 0;
+        a_hi[j] = (on && d.a[j].kind != CHGPU_AGG_COUNT && ((d.words.fx >> d.a[j].word) & 1)) ? d.words.fx_hi[d.a[j].word] : 0;
         a_cond[j] = (on && d.a[j].cond >= 0) ? (d.a[j].cond << 1) | d.a[j].cond_want : -1;
         a_cnt2[j] = on && (d.a[j].kind == CHGPU_AGG_AVG || d.a[j].seen);
     }
@@ -898,7 +959,7 @@ __global__ __launch_bounds__(1024) void k_agg_rows_lds(AggTable t, AggDesc d, co
     __syncthreads();
 
     // ---- flush the workgroup's partial states: one emplace + n_words atomics per distinct key ----
-    lds_flush<u64>(t, d, lds_raw, PartLds(8, S, d.n_words, 0), S, lzero, s_ovf);
+    lds_flush<u64>(t, d, lds_raw, PartLds(8, S, d.words.n_words, 0), S, lzero, s_ovf);
     if (t.ovf)
     {
         __syncthreads();
@@ -1319,7 +1380,7 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
     static_assert(!FCOND || OPS == 0, "a conditioned pass takes the generic update loop");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     KT * lkeys = (KT *)lds_raw;
-    const PartLds L((u32)sizeof(KT), S, d.n_words, cnt32);
+    const PartLds L((u32)sizeof(KT), S, d.words.n_words, cnt32);
     const u32 lds_bytes = L.bytes();
     __shared__ u32 lzero, sh_unit;
     __shared__ u64 s_ovf[AGG_MAX_WORDS]; // find-only mode: the workgroup's share of the overflow row (made visible by the loop's first barrier)
@@ -1350,10 +1411,10 @@ __global__ __launch_bounds__(1024) void k_agg_part_lds(AggTable t, AggDesc d, co
             else
             {
                 a_op[j] = (d.a[j].arg_type == CHGPU_F64 || d.a[j].arg_type == CHGPU_F32) ? 2 : 1;
-                if ((d.word_fx >> w) & 1)
+                if ((d.words.fx >> w) & 1)
                 {
                     a_op[j] = 5; // 128-bit fixed-point sum: the low half at a_off, the high half at a_off3
-                    a_off3[j] = L.off(d.fx_hi[w]);
+                    a_off3[j] = L.off(d.words.fx_hi[w]);
                 }
                 a_src[j] = (int)d.a[j].pre;
                 const int ex = d.a[j].arg_type == CHGPU_I8 ? 1 : d.a[j].arg_type == CHGPU_I16 ? 2 : d.a[j].arg_type == CHGPU_I32 ? 3 : d.a[j].arg_type == CHGPU_F32 ? 4 : 0;
@@ -1659,7 +1720,7 @@ __global__ __launch_bounds__(1024) void k_agg_tiles_lds(AggTable t, AggDesc d, c
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     KT * lkeys = (KT *)lds_raw;
-    const PartLds L((u32)sizeof(KT), S, d.n_words, cnt32);
+    const PartLds L((u32)sizeof(KT), S, d.words.n_words, cnt32);
     const u32 lds_bytes = L.bytes();
     __shared__ u32 lzero, sh_unit;
     __shared__ u64 s_ovf[AGG_MAX_WORDS]; // find-only mode: the workgroup's share of the overflow row (made visible by the loop's first barrier)
@@ -1883,25 +1944,18 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tiles_pending_aos(AggTable 
 
 // Merge (key, state words) tuples into the table: mergeToViaEmplace, also the rehash of a grown table.
 // src_words[w] + i*1 ; src keys are u64; key==0 entries are skipped when skip_zero_keys (table arrays: empty cells),
-// zero_slot_index: index in the source arrays of the out-of-line zero key (or ~0).
-struct AggFxWords
-{
-    u32 word_fx, word_fx_hi, word_any;
-    u32 word_arg; // argMin / argMax triples
-    u32 rehash;   // the tuples are the cells of the table being replaced: every key once, into an empty table
-    unsigned char fx_hi[AGG_MAX_WORDS];
-};
+// zero_slot_index: index in the source arrays of the out-of-line zero key (or ~0).  rehash: the tuples are the cells of the table
+// being replaced: every key once, into an empty table.
 // source tuple i's state words into the group's state in `sink` (table words: a merge has no word map)
 template <typename Sink>
-__device__ __forceinline__ void merge_tuple_words(const Sink & sink, u32 n_words, u32 word_is_f64, const AggFxWords & fx, const u64 * __restrict__ src_words,
-                                                  u64 src_stride, u64 i)
+__device__ __forceinline__ void merge_tuple_words(const Sink & sink, const AggMergeWords & ws, u32 rehash, const u64 * __restrict__ src_words, u64 src_stride, u64 i)
 {
-    for (u32 w = 0; w < n_words; ++w)
+    for (u32 w = 0; w < ws.n_words; ++w)
     {
-        if ((fx.word_fx_hi >> w) & 1)
+        if ((ws.fx_high >> w) & 1)
             continue; // merged with its low half
         const u64 v = src_words[(u64)w * src_stride + i];
-        if ((fx.word_any >> w) & 1)
+        if ((ws.any >> w) & 1)
         {
             // any(): changeFirstTime (SingleValueData.cpp) -- a state that has a value keeps it; {claim, value} move together
             if (v && atomicCAS((unsigned long long *)sink.at(w), 0ull, (unsigned long long)v) == 0ull)
@@ -1909,10 +1963,10 @@ __device__ __forceinline__ void merge_tuple_words(const Sink & sink, u32 n_words
             ++w;
             continue;
         }
-        if ((fx.word_arg >> w) & 1)
+        if ((ws.arg >> w) & 1)
         {
             const u64 has = src_words[(u64)(w + 1) * src_stride + i];
-            if (fx.rehash)
+            if (rehash)
             {
                 // {val, claim, arg} move unchanged: a claim may be the sentinel of a block whose claim pass is still to come
                 *sink.at(w) = v;
@@ -1924,17 +1978,17 @@ __device__ __forceinline__ void merge_tuple_words(const Sink & sink, u32 n_words
             w += 2;
             continue;
         }
-        if ((fx.word_fx >> w) & 1)
+        if ((ws.fx >> w) & 1)
         {
-            const u32 wh = fx.fx_hi[w];
+            const u32 wh = ws.fx_hi[w];
             sink.add_fx(sink.at(w), sink.at(wh), Fx128{v, src_words[(u64)wh * src_stride + i]});
             continue;
         }
-        sink.add_word(sink.at(w), v, (int)((word_is_f64 >> w) & 1) | (int)(((word_is_f64 >> (16 + w)) & 1) << 1)); // upper half of the mask: max words
+        sink.add_word(sink.at(w), v, ws.op(w));
     }
 }
 template <int MODE>
-__global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, u32 n_words, u32 word_is_f64, AggFxWords fx, const u64 * __restrict__ src_keys,
+__global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, AggMergeWords ws, u32 rehash, const u64 * __restrict__ src_keys,
                                                             const u64 * __restrict__ src_words, u64 src_stride, u64 n, int skip_zero_keys,
                                                             u64 zero_slot_index, int soft_limit, u64 * __restrict__ pending)
 {
@@ -1984,10 +2038,10 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, u32 n_wo
                     // mergeDataNoMoreKeysImpl: the source state of a key dst lacks goes to dst's overflow row (or is dropped:
                     // mergeDataOnlyExistingKeysImpl)
                     if (t.ovf)
-                        merge_tuple_words(LdsRowSink{s_ovf}, n_words, word_is_f64, fx, src_words, src_stride, i);
+                        merge_tuple_words(LdsRowSink{s_ovf}, ws, rehash, src_words, src_stride, i);
                 }
                 else
-                    merge_tuple_words(GlobalSink(t, slot), n_words, word_is_f64, fx, src_words, src_stride, i);
+                    merge_tuple_words(GlobalSink(t, slot), ws, rehash, src_words, src_stride, i);
             }
         }
         const u64 b = __ballot(failed);
@@ -2008,7 +2062,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_tuples(AggTable t, u32 n_wo
     if (t.ovf)
     {
         __syncthreads();
-        ovf_flush(t, s_ovf, n_words, word_is_f64, fx.word_fx, fx.word_fx_hi, fx.fx_hi, nullptr, fx.word_any, fx.word_arg, AGG_MERGE_SENTINEL);
+        ovf_flush(t, s_ovf, ws, nullptr, true, AGG_MERGE_SENTINEL);
     }
 }
 
@@ -2059,22 +2113,10 @@ static u64 pow2_ceil(u64 x)
     return p;
 }
 
-static AggFxWords agg_fx_words(const chgpu_agg * a)
-{
-    AggFxWords f;
-    f.word_fx = a->word_fx;
-    f.word_fx_hi = a->word_fx_hi;
-    f.word_any = a->word_any;
-    f.word_arg = a->word_arg;
-    f.rehash = 0;
-    memcpy(f.fx_hi, a->fx_hi, sizeof(f.fx_hi));
-    return f;
-}
-
 static int agg_alloc_table(chgpu_agg * a, u64 capacity, AggTable * t, void ** mem, size_t * mem_class)
 {
     const size_t cells = capacity + 1;
-    const size_t bytes = cells * 8 * (1 + a->n_words) + AGG_HDR_BYTES;
+    const size_t bytes = cells * 8 * (1 + a->words.n_words) + AGG_HDR_BYTES;
     void * m = nullptr;
     CHGPU_TRY(chgpu_pool_alloc(a->ctx, bytes, &m, mem_class));
     hipError_t e = hipMemsetAsync(m, 0, bytes, a->ctx->stream); // HashTableAllocator zero-fills (HashTableAllocator.h:11)
@@ -2119,10 +2161,8 @@ static int agg_grow(chgpu_agg * a, u64 min_groups, bool has_zero)
     // old cells [0, capacity) plus the out-of-line zero cell when it is set; no soft limit: the new table fits them all
     const u64 n = a->t.capacity + (has_zero ? 1 : 0);
     const u32 grid = chgpu_grid_for(a->ctx, n, AGG_THREADS, 8);
-    AggFxWords fx = agg_fx_words(a);
-    fx.rehash = 1;
-    hipLaunchKernelGGL(k_agg_tuples<AGG_MODE_ALL>, dim3(grid), dim3(AGG_THREADS), 0, a->ctx->stream, nt, a->n_words, a->word_is_f64, fx,
-                       a->t.keys, a->t.words, a->t.capacity + 1, n, 1, has_zero ? a->t.capacity : ~0ull, 0, (u64 *)nullptr);
+    hipLaunchKernelGGL(k_agg_tuples<AGG_MODE_ALL>, dim3(grid), dim3(AGG_THREADS), 0, a->ctx->stream, nt, AggMergeWords(a->words), 1u, a->t.keys, a->t.words,
+                       a->t.capacity + 1, n, 1, has_zero ? a->t.capacity : ~0ull, 0, (u64 *)nullptr);
     a->ctx->counters[6] += 1;
     a->ctx->counters[7] += 1;
     CHGPU_HIP(hipGetLastError());
@@ -2177,37 +2217,32 @@ static void agg_set_find_only(chgpu_agg * a, bool on)
 // the conditioned functions and the appended high halves of the fixed-point sums.  Over AGG_MAX_WORDS words: `too_many` and a message.
 static int agg_layout(chgpu_agg * a, int too_many)
 {
-    a->word_is_f64 = a->word_any = a->word_arg = a->word_seen = a->word_fx = a->word_fx_hi = 0;
+    AggWords & ws = a->words;
+    ws = AggWords{};
     a->has_extremum = false;
-    memset(a->fx_hi, 0, sizeof(a->fx_hi));
     u32 w = 0;
     for (u32 j = 0; j < a->n_aggs; ++j)
     {
         if (w >= AGG_MAX_WORDS)
             return chgpu_set_error(too_many, "more than %u state words: CPU path", AGG_MAX_WORDS);
         const int kind = a->kinds[j];
-        const bool arg_pair = kind == CHGPU_AGG_ARG_MIN || kind == CHGPU_AGG_ARG_MAX; // two argument slots: arg, then val
-        const bool any_value = kind == CHGPU_AGG_ANY;
-        const bool extremum = kind == CHGPU_AGG_MIN || kind == CHGPU_AGG_MAX || any_value;
+        const AggKind & k = agg_kind(kind);
         a->word_off[j] = w;
-        if (arg_pair)
+        a->has_extremum = a->has_extremum || k.extremum;
+        if (k.words == 3) // {val key, claim, arg}
         {
-            a->has_extremum = true;
             if (w + 3 <= AGG_MAX_WORDS)
-                a->word_arg |= 1u << w;
-            w += 3;
-            continue;
+                ws.arg |= 1u << w;
         }
-        if (extremum)
+        else if (k.extremum)
         {
-            a->word_is_f64 |= 1u << (16 + w); // upper half of the mask: the word combines by unsigned max (order keys), never by an add
-            a->has_extremum = true;
-            if (any_value)
-                a->word_any |= 1u << w;
+            ws.max |= 1u << w; // order keys, any()'s claim
+            if (kind == CHGPU_AGG_ANY)
+                ws.any |= 1u << w;
         }
-        else if (kind != CHGPU_AGG_COUNT && chgpu_type_is_float(a->arg_types[j]))
-            a->word_is_f64 |= 1u << w;
-        w += (kind == CHGPU_AGG_AVG || any_value) ? 2 : 1;
+        else if (k.slots && chgpu_type_is_float(a->arg_types[j]))
+            ws.f64 |= 1u << w;
+        w += k.words;
         // the `seen` word: a zeroed min / max word is also the state of a row that holds the type's extremum, and a NULL-mode sum of 0
         // is not NULL (avg has its denominator, count itself, any / argMin / argMax their claim)
         const bool seen = a->cond_modes[j] != CHGPU_AGG_COND_NONE &&
@@ -2215,32 +2250,30 @@ static int agg_layout(chgpu_agg * a, int too_many)
         if (seen)
         {
             if (w < AGG_MAX_WORDS)
-                a->word_seen |= 1u << w;
+                ws.seen |= 1u << w;
             ++w;
         }
     }
     if (w > AGG_MAX_WORDS)
         return chgpu_set_error(too_many, "more than %u state words: CPU path", AGG_MAX_WORDS);
-    a->n_pub_words = w;
+    ws.n_pub_words = w;
     if (a->key_type >= 0 && chgpu_opt(a->ctx, "deterministic_float_sums", 1))
     {
-        u32 n_fx = 0;
-        for (u32 j = 0; j < a->n_aggs; ++j)
-            n_fx += ((a->word_is_f64 >> a->word_off[j]) & 1) ? 1 : 0;
-        if (w + n_fx <= AGG_MAX_WORDS) // (more words than the masks hold: such an aggregation keeps its double states)
+        // (every Float64 word so far is a function's first: a sum or an avg numerator)
+        if (w + (u32)__builtin_popcount(ws.f64) <= AGG_MAX_WORDS) // (more words than the masks hold: such an aggregation keeps its double states)
             for (u32 j = 0; j < a->n_aggs; ++j)
             {
                 const u32 lo = a->word_off[j];
-                if (!((a->word_is_f64 >> lo) & 1))
+                if (ws.op(lo) != 1)
                     continue;
-                a->word_is_f64 &= ~(1u << lo); // the low half combines by an integer add
-                a->word_fx |= 1u << lo;
-                a->word_fx_hi |= 1u << w;
-                a->fx_hi[lo] = (unsigned char)w;
+                ws.f64 &= ~(1u << lo); // the low half combines by an integer add
+                ws.fx |= 1u << lo;
+                ws.fx_high |= 1u << w;
+                ws.fx_hi[lo] = (unsigned char)w;
                 ++w;
             }
     }
-    a->n_words = w;
+    ws.n_words = w;
     return CHGPU_OK;
 }
 
@@ -2261,16 +2294,15 @@ extern "C" int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, 
     for (u32 j = 0; j < n_aggs; ++j)
     {
         const int kind = agg_kinds[j];
-        const bool arg_pair = kind == CHGPU_AGG_ARG_MIN || kind == CHGPU_AGG_ARG_MAX; // two argument slots: arg, then val
-        const int at = (kind == CHGPU_AGG_COUNT || !arg_types) ? CHGPU_U64 : arg_types[slot];
-        const int vt = (arg_pair && arg_types) ? arg_types[slot + 1] : CHGPU_U64;
-        const bool extremum = kind == CHGPU_AGG_MIN || kind == CHGPU_AGG_MAX || kind == CHGPU_AGG_ANY;
-        if (kind != CHGPU_AGG_COUNT && kind != CHGPU_AGG_SUM && kind != CHGPU_AGG_AVG && !extremum && !arg_pair)
+        if (!agg_kind_known(kind))
         {
             delete a;
             return chgpu_set_error(CHGPU_ERR_NOT_IMPLEMENTED, "aggregate function kind %d has no device state: CPU path", kind);
         }
-        if (kind != CHGPU_AGG_COUNT && (!chgpu_type_size(at) || !chgpu_type_size(vt)))
+        const u32 n_args = agg_kind(kind).slots; // (two: arg, then val)
+        const int at = (n_args == 0 || !arg_types) ? CHGPU_U64 : arg_types[slot];
+        const int vt = (n_args == 2 && arg_types) ? arg_types[slot + 1] : CHGPU_U64;
+        if (n_args && (!chgpu_type_size(at) || !chgpu_type_size(vt)))
         {
             delete a;
             return chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "bad argument type %d", chgpu_type_size(at) ? vt : at);
@@ -2279,7 +2311,7 @@ extern "C" int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, 
         a->arg_types[j] = at;
         a->val_types[j] = vt;
         a->slot[j] = slot;
-        slot += arg_pair ? 2 : 1;
+        slot += n_args ? n_args : 1; // (count() keeps its place in arg_cols: without the two-argument kinds slot j is aggregate j)
     }
     a->n_slots = slot;
     const int rc = agg_layout(a, CHGPU_ERR_NOT_IMPLEMENTED);
@@ -2338,26 +2370,45 @@ extern "C" int chgpu_agg_free(chgpu_agg * a)
     return CHGPU_OK;
 }
 
+// The slots of function j in arg_cols: [a->slot[j], agg_slot_end(a, j)) -- none for count()
+static u32 agg_slot_end(const chgpu_agg * a, u32 j) { return a->slot[j] + agg_kind(a->kinds[j]).slots; }
+
+// Numbers the distinct condition columns of the block being added (a column shared by several functions is read, filtered or turned
+// into a mask once): of[j] = the number of conditioned function j's column, first[c] = the first function that carries column c.
+// by_mode: functions share a number only when their modes agree too (without key: one mask per column and mode).  Returns the count.
+// A column is told by its data pointer: two column objects over the same bytes count as one (the filtered copy and the without-key
+// mask used to tell them by object and made one each; the result is the same, they hold the same bytes).
+static u32 agg_number_conds(const chgpu_agg * a, bool by_mode, u32 * of, u32 * first)
+{
+    u32 n = 0;
+    for (u32 j = 0; j < a->n_aggs; ++j)
+    {
+        if (a->cond_modes[j] == CHGPU_AGG_COND_NONE)
+            continue;
+        u32 c = 0;
+        while (c < n && !(a->block_conds[first[c]]->data == a->block_conds[j]->data && (!by_mode || a->cond_modes[first[c]] == a->cond_modes[j])))
+            ++c;
+        if (c == n)
+            first[n++] = j;
+        of[j] = c;
+    }
+    return n;
+}
+
 static void agg_fill_desc(const chgpu_agg * a, const chgpu_col * const * arg_cols, AggDesc * d)
 {
     d->n_aggs = a->n_aggs;
-    d->n_words = a->n_words;
-    d->word_is_f64 = a->word_is_f64;
-    d->word_fx = a->word_fx;
-    d->word_fx_hi = a->word_fx_hi;
-    memcpy(d->fx_hi, a->fx_hi, sizeof(d->fx_hi));
+    d->words = a->words;
     d->fx_base = a->fx_base;
     d->row_seq = 0;
     d->arg_sentinel = 0;
-    d->word_arg = a->word_arg;
     for (u32 w = 0; w < AGG_MAX_WORDS; ++w)
         d->word_map[w] = (unsigned char)w;
     for (u32 j = 0; j < a->n_aggs; ++j)
     {
         const u32 sl = a->slot[j];
-        const bool arg_pair = a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX;
         d->a[j].ptr = (arg_cols && arg_cols[sl]) ? arg_cols[sl]->data : nullptr;
-        d->a[j].val = (arg_pair && arg_cols && arg_cols[sl + 1]) ? arg_cols[sl + 1]->data : nullptr;
+        d->a[j].val = (agg_kind(a->kinds[j]).slots == 2 && arg_cols && arg_cols[sl + 1]) ? arg_cols[sl + 1]->data : nullptr;
         d->a[j].kind = a->kinds[j];
         d->a[j].arg_type = a->arg_types[j];
         d->a[j].val_type = a->val_types[j];
@@ -2372,19 +2423,17 @@ static void agg_fill_desc(const chgpu_agg * a, const chgpu_col * const * arg_col
         d->cond[j] = nullptr;
     if (!a->conditioned || !a->block_conds)
         return;
+    u32 cond_of[AGG_MAX_AGGS], first[AGG_MAX_AGGS];
+    d->n_conds = agg_number_conds(a, false, cond_of, first);
+    for (u32 c = 0; c < d->n_conds; ++c)
+        d->cond[c] = (const u8 *)a->block_conds[first[c]]->data;
     for (u32 j = 0; j < a->n_aggs; ++j)
     {
         if (a->cond_modes[j] == CHGPU_AGG_COND_NONE)
             continue;
-        const u8 * p = (const u8 *)a->block_conds[j]->data;
-        u32 c = 0;
-        while (c < d->n_conds && d->cond[c] != p)
-            ++c;
-        if (c == d->n_conds)
-            d->cond[d->n_conds++] = p; // a column shared by several functions is read once per row
-        d->a[j].cond = (signed char)c;
+        d->a[j].cond = (signed char)cond_of[j];
         d->a[j].cond_want = a->cond_modes[j] == CHGPU_AGG_COND_IF ? 1 : 0;
-        d->a[j].seen = (unsigned char)((a->word_seen >> (a->word_off[j] + 1)) & 1);
+        d->a[j].seen = (unsigned char)((a->words.seen >> (a->word_off[j] + agg_kind(a->kinds[j]).words)) & 1);
     }
 }
 
@@ -2560,7 +2609,7 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_arg_rows(AggTable t, AggDes
 }
 // The same two passes of a merge, over the source tuples k_agg_tuples folded in: tuple i claims with AGG_MERGE_CLAIM_TOP - i.
 template <int PASS>
-__global__ __launch_bounds__(AGG_THREADS) void k_agg_arg_tuples(AggTable t, u32 n_words, u32 word_arg, const u64 * __restrict__ src_keys,
+__global__ __launch_bounds__(AGG_THREADS) void k_agg_arg_tuples(AggTable t, AggWords ws, const u64 * __restrict__ src_keys,
                                                                 const u64 * __restrict__ src_words, u64 src_stride, u64 n, int skip_zero_keys, u64 zero_slot_index)
 {
     for (u64 i = (u64)blockIdx.x * AGG_THREADS + threadIdx.x; i < n; i += (u64)gridDim.x * AGG_THREADS)
@@ -2575,8 +2624,8 @@ __global__ __launch_bounds__(AGG_THREADS) void k_agg_arg_tuples(AggTable t, u32 
         u64 stride;
         if (!agg_state_of(t, key, base, stride))
             continue;
-        for (u32 w = 0; w + 2 < n_words; ++w)
-            if (((word_arg >> w) & 1) && src_words[(u64)(w + 1) * src_stride + i] != 0)
+        for (u32 w = 0; w + 2 < ws.n_words; ++w)
+            if (((ws.arg >> w) & 1) && src_words[(u64)(w + 1) * src_stride + i] != 0)
                 agg_arg_claim_or_resolve<PASS>(base + (u64)w * stride, stride, src_words[(u64)w * src_stride + i], AGG_MERGE_CLAIM_TOP - i,
                                                src_words[(u64)(w + 2) * src_stride + i], ~0ull);
     }
@@ -2695,18 +2744,18 @@ static int agg_fx_shift(chgpu_agg * a, int sh)
     if (sh <= 0)
         return CHGPU_OK;
     const u64 cells = a->t.capacity + 1;
-    for (u32 w = 0; w < a->n_pub_words; ++w)
-        if ((a->word_fx >> w) & 1)
+    for (u32 w = 0; w < a->words.n_pub_words; ++w)
+        if ((a->words.fx >> w) & 1)
         {
             if (a->table_mem)
             {
                 hipLaunchKernelGGL(k_fx_shift, dim3(chgpu_grid_for(a->ctx, cells, 256, 8)), dim3(256), 0, a->ctx->stream, a->t.words + (u64)w * cells,
-                                   a->t.words + (u64)a->fx_hi[w] * cells, cells, sh);
+                                   a->t.words + (u64)a->words.fx_hi[w] * cells, cells, sh);
                 a->ctx->counters[6] += 1;
             }
             if (a->ovf_mem) // the overflow row's pair moves with the window too (it may exist before the table: is_overflows blocks)
             {
-                hipLaunchKernelGGL(k_fx_shift, dim3(1), dim3(256), 0, a->ctx->stream, (u64 *)a->ovf_mem + w, (u64 *)a->ovf_mem + a->fx_hi[w], (u64)1, sh);
+                hipLaunchKernelGGL(k_fx_shift, dim3(1), dim3(256), 0, a->ctx->stream, (u64 *)a->ovf_mem + w, (u64 *)a->ovf_mem + a->words.fx_hi[w], (u64)1, sh);
                 a->ctx->counters[6] += 1;
             }
         }
@@ -2733,28 +2782,28 @@ static int agg_fx_set_window(chgpu_agg * a, int base, int log_cap)
 // reference's, poisoned groups included); every pair becomes the double it stands for.
 static int agg_fx_to_plain(chgpu_agg * a)
 {
-    if (!a->word_fx)
+    if (!a->words.fx)
         return CHGPU_OK;
     const u64 cells = a->t.capacity + 1;
-    for (u32 w = 0; w < a->n_pub_words; ++w)
-        if ((a->word_fx >> w) & 1)
+    for (u32 w = 0; w < a->words.n_pub_words; ++w)
+        if ((a->words.fx >> w) & 1)
         {
             if (a->table_mem)
             {
                 hipLaunchKernelGGL(k_fx_to_double, dim3(chgpu_grid_for(a->ctx, cells, 256, 8)), dim3(256), 0, a->ctx->stream, a->t.words + (u64)w * cells,
-                                   a->t.words + (u64)a->fx_hi[w] * cells, cells, a->fx_base, 1);
+                                   a->t.words + (u64)a->words.fx_hi[w] * cells, cells, a->fx_base, 1);
                 a->ctx->counters[6] += 1;
             }
             if (a->ovf_mem) // (with or without a table)
             {
-                hipLaunchKernelGGL(k_fx_to_double, dim3(1), dim3(256), 0, a->ctx->stream, (u64 *)a->ovf_mem + w, (u64 *)a->ovf_mem + a->fx_hi[w], (u64)1,
+                hipLaunchKernelGGL(k_fx_to_double, dim3(1), dim3(256), 0, a->ctx->stream, (u64 *)a->ovf_mem + w, (u64 *)a->ovf_mem + a->words.fx_hi[w], (u64)1,
                                    a->fx_base, 1);
                 a->ctx->counters[6] += 1;
             }
         }
     CHGPU_HIP(hipGetLastError());
-    a->word_is_f64 |= a->word_fx;
-    a->word_fx = 0; // (word_fx_hi stays: the spare words keep being skipped; they hold zeros)
+    a->words.f64 |= a->words.fx;
+    a->words.fx = 0; // (fx_high stays: the spare words keep being skipped; they hold zeros)
     return CHGPU_OK;
 }
 // exponent statistics of `n` values of one column: *emax_biased = 0 when every value is zero (then *emin_biased is 2047)
@@ -2804,12 +2853,12 @@ static int agg_fx_admit(chgpu_agg * a, u32 emax_biased, u32 emin_biased, u64 n)
 // before a block's rows are added: look at the float arguments of the fixed-point sums
 static int agg_fx_prepare_block(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 row_begin, u64 n)
 {
-    if (!a->word_fx || n == 0)
+    if (!a->words.fx || n == 0)
         return CHGPU_OK;
     u32 emax = 0, emin = 2047;
     for (u32 j = 0; j < a->n_aggs; ++j)
     {
-        if (a->kinds[j] == CHGPU_AGG_COUNT || !((a->word_fx >> a->word_off[j]) & 1))
+        if (a->kinds[j] == CHGPU_AGG_COUNT || !((a->words.fx >> a->word_off[j]) & 1))
             continue;
         u32 e = 0, em = 2047;
         bool bad = false;
@@ -2905,7 +2954,7 @@ static void dispatch_key(bool key32, F && fn)
 // `agg_mask`, and which of the aggregator's words are 32-bit counts there: the key as wide as the partition buffers' keys, COUNT words
 // as 32 bits while the call has fewer than 2^32 rows.  The full mask is the aggregator's own layout with EVERY word of it: the spare
 // high words that fixed-point sums leave behind when they go back to doubles (agg_fx_to_plain) are still there, while a pass over some
-// of the functions numbers its words afresh (agg_localise_desc) and leaves them out.
+// of the functions numbers its words afresh (agg_localise_words) and leaves them out.
 static size_t agg_part_cell_bytes(const chgpu_agg * a, int key_type, u64 n, u32 * cnt32_out, u32 agg_mask = ~0u)
 {
     const u32 c32 = n < (1ull << 32) && !chgpu_opt(a->ctx, "tune_gb_nocnt32", 0) ? 1 : 0;
@@ -2915,16 +2964,14 @@ static size_t agg_part_cell_bytes(const chgpu_agg * a, int key_type, u64 n, u32 
         if (!((agg_mask >> j) & 1))
             continue;
         const u32 w = a->word_off[j];
-        const bool pair = a->kinds[j] == CHGPU_AGG_AVG || a->kinds[j] == CHGPU_AGG_ANY;
-        const bool triple = a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX;
-        words += 1 + (pair ? 1 : 0) + (triple ? 2 : 0) + ((a->word_fx >> w) & 1);
+        words += agg_kind(a->kinds[j]).words + ((a->words.fx >> w) & 1);
         if (a->kinds[j] == CHGPU_AGG_COUNT)
             cnt32 |= c32 << w;
         else if (a->kinds[j] == CHGPU_AGG_AVG)
             cnt32 |= c32 << (w + 1);
     }
     if (agg_mask == ~0u)
-        words = a->n_words;
+        words = a->words.n_words;
     if (cnt32_out)
         *cnt32_out = cnt32;
     const u32 n4 = (u32)__builtin_popcount(cnt32);
@@ -3017,48 +3064,45 @@ static int agg_finish_rounds_aos(chgpu_agg * a, const AggDesc & d, const u32 * r
     });
 }
 
-// The descriptor of a pass over a subset of the functions (d->a[0 .. n_aggs) already compacted to them): its state words renumbered
-// 0 .. n-1 in the order of the functions (a fixed-point sum's high half behind the regular words, as in the aggregator), word_map[] back
-// to the table's words, every per-word mask re-expressed in the local numbering; *cnt32 (which words are 32-bit counts in LDS) likewise.
-static void agg_localise_desc(AggDesc * d, u32 * cnt32)
+// The descriptor of a pass over a subset of the functions (d->a[0 .. n_aggs) already compacted to them): d->words re-expressed in local
+// numbering -- the functions' words 0 .. n-1 in their order (a fixed-point sum's high half behind the regular words, as in the
+// aggregator), every per-word mask moved along -- and word_map[] back to the table's words; *cnt32 (which words are 32-bit counts in
+// LDS) likewise.
+static void agg_localise_words(AggDesc * d, u32 * cnt32)
 {
-    const u32 g_cnt32 = *cnt32, g_fx = d->word_fx, g_f64 = d->word_is_f64;
-    unsigned char g_hi[AGG_MAX_WORDS];
-    memcpy(g_hi, d->fx_hi, sizeof(g_hi));
-    u32 wl = 0, l_cnt32 = 0, l_fx = 0, l_fx_hi = 0, l_f64 = 0;
-    memset(d->fx_hi, 0, sizeof(d->fx_hi));
+    const AggWords g = d->words;
+    const u32 g_cnt32 = *cnt32;
+    AggWords l{};
+    u32 wl = 0, l_cnt32 = 0;
     u32 fx_lo_local[AGG_MAX_AGGS], n_fx = 0;
-    unsigned char fx_hi_global[AGG_MAX_AGGS];
     for (u32 m = 0; m < d->n_aggs; ++m)
     {
-        const u32 gw = d->a[m].word, words = (d->a[m].kind == CHGPU_AGG_AVG || d->a[m].kind == CHGPU_AGG_ANY) ? 2 : 1;
+        const u32 gw = d->a[m].word, words = agg_kind(d->a[m].kind).words;
         d->a[m].word = wl;
         for (u32 x = 0; x < words; ++x)
         {
             d->word_map[wl + x] = (unsigned char)(gw + x);
             l_cnt32 |= ((g_cnt32 >> (gw + x)) & 1u) << (wl + x);
-            l_f64 |= ((g_f64 >> (gw + x)) & 1u) << (wl + x);
-            l_f64 |= ((g_f64 >> (16 + gw + x)) & 1u) << (16 + wl + x);
+            l.f64 |= ((g.f64 >> (gw + x)) & 1u) << (wl + x);
+            l.max |= ((g.max >> (gw + x)) & 1u) << (wl + x);
         }
-        if ((g_fx >> gw) & 1)
+        if ((g.fx >> gw) & 1)
         {
-            l_fx |= 1u << wl;
-            fx_lo_local[n_fx] = wl;
-            fx_hi_global[n_fx++] = g_hi[gw]; // placed behind the regular words below
+            l.fx |= 1u << wl;
+            fx_lo_local[n_fx++] = wl; // its high half is placed behind the regular words below
         }
         wl += words;
     }
-    for (u32 k = 0; k < n_fx; ++k)
+    l.n_pub_words = wl;
+    for (u32 k = 0; k < n_fx; ++k, ++wl)
     {
-        d->word_map[wl] = fx_hi_global[k];
-        d->fx_hi[fx_lo_local[k]] = (unsigned char)wl;
-        l_fx_hi |= 1u << wl;
-        ++wl;
+        const u32 lo = fx_lo_local[k];
+        d->word_map[wl] = g.fx_hi[d->word_map[lo]];
+        l.fx_hi[lo] = (unsigned char)wl;
+        l.fx_high |= 1u << wl;
     }
-    d->n_words = wl;
-    d->word_fx = l_fx;
-    d->word_fx_hi = l_fx_hi;
-    d->word_is_f64 = l_f64;
+    l.n_words = wl;
+    d->words = l;
     *cnt32 = l_cnt32;
 }
 
@@ -3067,7 +3111,7 @@ static void agg_localise_desc(AggDesc * d, u32 * cnt32)
 // fixed-point sum of the second one.
 static u32 agg_update_code(const AggDesc & d, u32 cnt32)
 {
-    if (d.n_words > 4)
+    if (d.words.n_words > 4)
         return 0;
     u32 word_op[AGG_MAX_WORDS] = {0};
     for (u32 j = 0; j < d.n_aggs; ++j)
@@ -3080,18 +3124,18 @@ static u32 agg_update_code(const AggDesc & d, u32 cnt32)
             if (d.a[j].pre >= 2)
                 return 0;
             word_op[w] = (d.a[j].arg_type == CHGPU_F64 ? 3 : 1) + d.a[j].pre;
-            if ((d.word_fx >> w) & 1)
+            if ((d.words.fx >> w) & 1)
             {
                 if (d.a[j].pre != 0)
                     return 0;
-                word_op[w] = 7, word_op[d.fx_hi[w]] = 9;
+                word_op[w] = 7, word_op[d.words.fx_hi[w]] = 9;
             }
             if (d.a[j].kind == CHGPU_AGG_AVG)
                 word_op[w + 1] = ((cnt32 >> (w + 1)) & 1) ? 5 : 6;
         }
     }
     u32 ops = 0;
-    for (u32 w = 0; w < d.n_words; ++w)
+    for (u32 w = 0; w < d.words.n_words; ++w)
     {
         if (word_op[w] == 0)
             return 0;
@@ -3281,7 +3325,7 @@ static int agg_tile_plan(const chgpu_agg * a, const AggInput & in, const chgpu_c
     if (g.agg_mask != ~0u)
     {
         agg_desc_keep(&d, g.agg_mask);
-        agg_localise_desc(&d, &tp->cnt32); // the pass's own state words 0 .. n-1 (a word pass sized S and P for exactly those)
+        agg_localise_words(&d, &tp->cnt32); // the pass's own state words 0 .. n-1 (a word pass sized S and P for exactly those)
     }
     tp->ops = agg_update_code(d, tp->cnt32);
     return GbTileOps::has(tp->ops) ? CHGPU_OK : CHGPU_ERR_NOT_IMPLEMENTED;
@@ -3354,7 +3398,7 @@ static int agg_tile_run(chgpu_agg * a, const AggInput & in, const chgpu_col * ke
             return;
         hipLaunchKernelGGL(k_tile_units, dim3(1), dim3(1024), 0, ctx->stream, (const unsigned long long *)s.part_total, P, tp.chunk_rows, n_tiles, s.unit_list, tp.max_units, unit_qstart, unit_ctr);
         hipLaunchKernelGGL(k_tile_index_transpose, dim3((n_tiles + 63) / 64, (P + 63) / 64), dim3(256), 0, ctx->stream, (const unsigned short *)s.tidx, n_tiles, P, s.run_index);
-        const size_t lds_ag = (size_t)PartLds(sizeof(KT), S, d.n_words, tp.cnt32).bytes() + 16;
+        const size_t lds_ag = (size_t)PartLds(sizeof(KT), S, d.words.n_words, tp.cnt32).bytes() + 16;
         GbTileOps::dispatch(tp.ops, [&](auto ops) {
             rc = launch_lds(what, k_agg_tiles_lds<KT, decltype(ops)::value, TILE>, dim3(G), dim3(1024), lds_ag, ctx->stream, a->t, d, (const KT *)s.rec, (const u64 *)s.rec,
                             (const u32 *)s.run_index, n_tiles, P, s.pending, S, tp.cnt32, (const u64 *)s.unit_list, (const u32 *)unit_qstart, unit_ctr);
@@ -3569,7 +3613,7 @@ static int agg_scatter_run(chgpu_agg * a, const AggInput & in, const chgpu_col *
         hipLaunchKernelGGL(k_gb_units, dim3(1), dim3(1024), 0, ctx->stream, (const u64 *)s.offsets, G, P, n, g.chunk_rows, s.unit_start, unit_ctr);
         dispatch_key(g.key32, [&](auto kt) {
             using KT = decltype(kt);
-            const size_t lds_ag = (size_t)PartLds(sizeof(KT), S, a->n_words, g.cnt32).bytes() + 16; // the kernel zeroes whole 8-byte words
+            const size_t lds_ag = (size_t)PartLds(sizeof(KT), S, a->words.n_words, g.cnt32).bytes() + 16; // the kernel zeroes whole 8-byte words
             auto launch = [&](auto ops) {
                 rc = launch_lds(what, k_agg_part_lds<KT, 8, KT, false, decltype(ops)::value>, dim3((u32)ctx->num_cus), dim3(1024), lds_ag, ctx->stream, a->t, d, (const KT *)s.pkeys,
                                 (const void *)s.pwords, (const void *)(s.pwords + s.wstride), (const u64 *)s.offsets, G, P, n, s.pending, S, K, g.cnt32, g.chunk_rows,
@@ -3646,6 +3690,22 @@ static u32 agg_split_calls(const chgpu_agg * a, u32 per_call, u32 * masks, u32 *
 static bool agg_partition_gate(const chgpu_agg * a, u64 lds_groups, u64 n)
 {
     return a->size_hint > lds_groups && n >= (4u << 20) && !chgpu_opt(a->ctx, "agg_no_partition", 0);
+}
+
+// The partitioned plans come first for such a block, unless its states are not additive (min / max / any: the LDS-staged and partitioned
+// plans carry additive words only) or carry a per-function mask (the partition buffers have none)
+static bool agg_tries_partitions(const chgpu_agg * a, u64 lds_groups, u64 n)
+{
+    return !a->has_extremum && !a->conditioned && agg_partition_gate(a, lds_groups, n);
+}
+// Does the block take the RANGE-mode kernel (agg_add_block_ranged) -- the only plan a WHERE mask is fused into?  It does when the
+// partitioned plans are not tried, or were and refused the shape (partitions_refused: known only once they were asked), and the states
+// are additive with few enough promised groups for a workgroup's LDS table.  Keys of 1, 2, 4 or 8 bytes: every key type.
+static bool agg_takes_ranged(const chgpu_agg * a, u64 lds_groups, u64 n, bool partitions_refused = false)
+{
+    return (partitions_refused || !agg_tries_partitions(a, lds_groups, n)) && !a->has_extremum &&
+           a->size_hint <= 65536 /* beyond that nearly every key misses a workgroup's LDS table */ && n < (1ull << 32) &&
+           !chgpu_opt(a->ctx, "tune_agg_no_ranged", 0);
 }
 
 // The partitioned plans for a block that passed agg_partition_gate.  NOT_IMPLEMENTED: no plan takes the shape and nothing was added.
@@ -3730,30 +3790,18 @@ static int agg_add_block_materialised(chgpu_agg * a, const chgpu_col * key_col, 
     view(key_col);
     u32 data_of[2 * AGG_MAX_AGGS]; // by argument slot (an argMin / argMax carries both its columns)
     for (u32 j = 0; j < a->n_aggs; ++j)
-        if (a->kinds[j] != CHGPU_AGG_COUNT)
-            for (u32 sl = a->slot[j]; sl < (j + 1 < a->n_aggs ? a->slot[j + 1] : a->n_slots); ++sl)
-            {
-                data_of[sl] = m - 1; // index among the data columns (key = 0)
-                view(arg_cols[sl]);
-            }
-    // the condition columns travel with the keys and arguments (each distinct column once)
-    u32 cond_of[AGG_MAX_AGGS];
-    const chgpu_col * const * conds = a->conditioned ? a->block_conds : nullptr;
-    for (u32 j = 0; conds && j < a->n_aggs; ++j)
-    {
-        if (a->cond_modes[j] == CHGPU_AGG_COND_NONE)
-            continue;
-        u32 e = 0;
-        while (e < j && !(a->cond_modes[e] != CHGPU_AGG_COND_NONE && conds[e] == conds[j]))
-            ++e;
-        if (e < j)
+        for (u32 sl = a->slot[j]; sl < agg_slot_end(a, j); ++sl)
         {
-            cond_of[j] = cond_of[e];
-            continue;
+            data_of[sl] = m - 1; // index among the data columns (key = 0)
+            view(arg_cols[sl]);
         }
-        cond_of[j] = m - 1;
-        view(conds[j]);
-    }
+    // the condition columns travel with the keys and arguments (each distinct column once)
+    u32 cond_of[AGG_MAX_AGGS], cond_first[AGG_MAX_AGGS];
+    const chgpu_col * const * conds = a->conditioned ? a->block_conds : nullptr;
+    const u32 n_conds = conds ? agg_number_conds(a, false, cond_of, cond_first) : 0;
+    const u32 cond0 = m - 1; // condition column c is data column cond0 + c
+    for (u32 c = 0; c < n_conds; ++c)
+        view(conds[cond_first[c]]);
     chgpu_col * outs[1 + 3 * AGG_MAX_AGGS] = {};
     u64 kept = 0;
     const u32 n_data = m ? m - 1 : 0;
@@ -3767,13 +3815,12 @@ static int agg_add_block_materialised(chgpu_agg * a, const chgpu_col * key_col, 
     {
         const chgpu_col * fargs[2 * AGG_MAX_AGGS] = {};
         for (u32 j = 0; j < a->n_aggs; ++j)
-            if (a->kinds[j] != CHGPU_AGG_COUNT)
-                for (u32 sl = a->slot[j]; sl < (j + 1 < a->n_aggs ? a->slot[j + 1] : a->n_slots); ++sl)
-                    fargs[sl] = outs[data_of[sl]];
+            for (u32 sl = a->slot[j]; sl < agg_slot_end(a, j); ++sl)
+                fargs[sl] = outs[data_of[sl]];
         const chgpu_col * fconds[AGG_MAX_AGGS] = {};
         for (u32 j = 0; conds && j < a->n_aggs; ++j)
             if (a->cond_modes[j] != CHGPU_AGG_COND_NONE)
-                fconds[j] = outs[cond_of[j]];
+                fconds[j] = outs[cond0 + cond_of[j]];
         if (conds)
             a->block_conds = fconds;
         rc = agg_add_block_impl(a, outs[0], fargs, 0, kept, nullptr);
@@ -3813,81 +3860,76 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
         chgpu_col_free(fv);
         CHGPU_TRY(rc);
     }
+    // A one-word reduction: the word is filled with the byte `fill` (< 0: left as it is), `launch(word)` starts the kernel, *out = the word
+    auto reduce_word = [&](int fill, auto launch, u64 * out) -> int {
+        void * scratch = nullptr;
+        CHGPU_TRY(chgpu_scratch(ctx, 256, &scratch));
+        if (fill >= 0)
+            CHGPU_HIP(hipMemsetAsync(scratch, fill, 8, ctx->stream));
+        launch((unsigned long long *)scratch);
+        ctx->counters[6] += 1;
+        CHGPU_HIP(hipGetLastError());
+        return chgpu_read_back(ctx, scratch, out, 8);
+    };
+    const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
     // one function under one mask (`filter`, which lets `kept` rows through)
     auto add_function = [&](u32 j, const chgpu_col * filter, u64 kept) -> int {
+        const int kind = a->kinds[j];
+        const AggKind & k = agg_kind(kind);
         u64 * st = &a->host_words[a->word_off[j]];
-        const chgpu_col * col = a->kinds[j] == CHGPU_AGG_COUNT ? nullptr : arg_cols[a->slot[j]];
-        if (a->kinds[j] == CHGPU_AGG_COUNT)
+        const chgpu_col * col = k.slots ? arg_cols[a->slot[j]] : nullptr;
+        const u8 * cond = filter ? (const u8 *)filter->data : nullptr;
+        // the value of row `row` of the block, as the function's argument column holds it
+        auto load_arg = [&](u64 row, u64 * bits) {
+            return reduce_word(-1, [&](unsigned long long * dev) {
+                hipLaunchKernelGGL(k_nokey_load, dim3(1), dim3(64), 0, ctx->stream, (const void *)col->data, a->arg_types[j], row_begin + row, (u64 *)dev);
+            }, bits);
+        };
+        if (kind == CHGPU_AGG_COUNT)
             st[0] += kept;
-        else if (a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX)
+        else if (k.extremum && (kept == 0 || n == 0))
+            return CHGPU_OK;
+        else if (k.slots == 2)
         {
             // the block's lexicographic extremum of (val key, ~ordinal): the largest val key, its first holder, that row's arg
-            if (kept == 0 || n == 0)
-                return CHGPU_OK;
             const chgpu_col * val = arg_cols[a->slot[j] + 1];
-            const int is_min = a->kinds[j] == CHGPU_AGG_ARG_MIN ? 1 : 0;
-            void * scratch = nullptr;
-            CHGPU_TRY(chgpu_scratch(ctx, 256, &scratch));
-            unsigned long long * dev = (unsigned long long *)scratch;
-            const u8 * cond = filter ? (const u8 *)filter->data : nullptr;
-            const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
+            const int is_min = kind == CHGPU_AGG_ARG_MIN ? 1 : 0;
             u64 best = 0, first = ~0ull, bits = 0;
-            CHGPU_HIP(hipMemsetAsync(dev, 0, 8, ctx->stream));
-            hipLaunchKernelGGL(k_nokey_extremum, dim3(grid), dim3(256), 0, ctx->stream, (const void *)val->data, a->val_types[j], row_begin, n, cond, is_min, 1, dev);
-            CHGPU_HIP(hipGetLastError());
-            CHGPU_TRY(chgpu_read_back(ctx, dev, &best, 8));
-            ctx->counters[6] += 1;
+            CHGPU_TRY(reduce_word(0, [&](unsigned long long * dev) {
+                hipLaunchKernelGGL(k_nokey_extremum, dim3(grid), dim3(256), 0, ctx->stream, (const void *)val->data, a->val_types[j], row_begin, n, cond, is_min, 1, dev);
+            }, &best));
             if (st[1] != 0 && best <= st[0])
                 return CHGPU_OK; // setIfGreater / setIfSmaller: only a strictly better val replaces a state that has a value
-            CHGPU_HIP(hipMemsetAsync(dev, 0xFF, 8, ctx->stream));
-            hipLaunchKernelGGL(k_nokey_first_holder, dim3(grid), dim3(256), 0, ctx->stream, (const void *)val->data, a->val_types[j], row_begin, n, cond, is_min, best, dev);
-            CHGPU_HIP(hipGetLastError());
-            CHGPU_TRY(chgpu_read_back(ctx, dev, &first, 8));
+            CHGPU_TRY(reduce_word(0xFF, [&](unsigned long long * dev) {
+                hipLaunchKernelGGL(k_nokey_first_holder, dim3(grid), dim3(256), 0, ctx->stream, (const void *)val->data, a->val_types[j], row_begin, n, cond, is_min, best, dev);
+            }, &first));
             CHGPU_REQUIRE(first != ~0ull, CHGPU_ERR_LOGICAL, "argMin / argMax: no row holds the block's extremum");
-            hipLaunchKernelGGL(k_nokey_load, dim3(1), dim3(64), 0, ctx->stream, (const void *)col->data, a->arg_types[j], row_begin + first, (u64 *)dev);
-            CHGPU_HIP(hipGetLastError());
-            CHGPU_TRY(chgpu_read_back(ctx, dev, &bits, 8));
-            ctx->counters[6] += 2;
+            CHGPU_TRY(load_arg(first, &bits));
             st[0] = best;
             st[1] = agg_arg_row_claim(a->any_seq + first);
             st[2] = bits;
         }
-        else if (a->kinds[j] == CHGPU_AGG_MIN || a->kinds[j] == CHGPU_AGG_MAX || a->kinds[j] == CHGPU_AGG_ANY)
+        else if (kind == CHGPU_AGG_ANY)
         {
-            if (kept == 0 || n == 0)
+            if (st[0] != 0) // setIfFirst: only a state without a value takes one
                 return CHGPU_OK;
-            void * scratch = nullptr;
-            CHGPU_TRY(chgpu_scratch(ctx, 256, &scratch));
-            unsigned long long * dev = (unsigned long long *)scratch;
-            const u8 * cond = filter ? (const u8 *)filter->data : nullptr;
+            u64 v = 0, bits = 0;
+            CHGPU_TRY(reduce_word(0xFF, [&](unsigned long long * dev) {
+                hipLaunchKernelGGL(k_nokey_first_row, dim3(grid), dim3(256), 0, ctx->stream, row_begin, n, cond, dev);
+            }, &v));
+            CHGPU_REQUIRE(v != ~0ull, CHGPU_ERR_LOGICAL, "any: none of the %llu rows the mask keeps was found", (unsigned long long)kept);
+            CHGPU_TRY(load_arg(v, &bits));
+            st[0] = ~(a->any_seq + v);
+            st[1] = bits;
+        }
+        else if (k.extremum)
+        {
             u64 v = 0;
-            if (a->kinds[j] != CHGPU_AGG_ANY)
-            {
-                CHGPU_HIP(hipMemsetAsync(dev, 0, 8, ctx->stream));
-                hipLaunchKernelGGL(k_nokey_extremum, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const void *)col->data, a->arg_types[j], row_begin, n, cond,
-                                   a->kinds[j] == CHGPU_AGG_MIN ? 1 : 0, 0, dev);
-                ctx->counters[6] += 1;
-                CHGPU_HIP(hipGetLastError());
-                CHGPU_TRY(chgpu_read_back(ctx, dev, &v, 8));
-                st[0] = v > st[0] ? v : st[0]; // order keys under an unsigned max (see agg_order_key); zero = no value yet
-            }
-            else if (st[0] == 0) // setIfFirst: only a state without a value takes one
-            {
-                CHGPU_HIP(hipMemsetAsync(dev, 0xFF, 8, ctx->stream));
-                hipLaunchKernelGGL(k_nokey_first_row, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, row_begin, n, cond, dev);
-                CHGPU_HIP(hipGetLastError());
-                CHGPU_TRY(chgpu_read_back(ctx, dev, &v, 8));
-                if (v != ~0ull)
-                {
-                    hipLaunchKernelGGL(k_nokey_load, dim3(1), dim3(64), 0, ctx->stream, (const void *)col->data, a->arg_types[j], row_begin + v, (u64 *)dev);
-                    CHGPU_HIP(hipGetLastError());
-                    u64 bits = 0;
-                    CHGPU_TRY(chgpu_read_back(ctx, dev, &bits, 8));
-                    st[0] = ~(a->any_seq + v);
-                    st[1] = bits;
-                }
-                ctx->counters[6] += 2;
-            }
+            CHGPU_TRY(reduce_word(0, [&](unsigned long long * dev) {
+                hipLaunchKernelGGL(k_nokey_extremum, dim3(grid), dim3(256), 0, ctx->stream, (const void *)col->data, a->arg_types[j], row_begin, n, cond,
+                                   kind == CHGPU_AGG_MIN ? 1 : 0, 0, dev);
+            }, &v));
+            st[0] = v > st[0] ? v : st[0]; // order keys under an unsigned max (see agg_order_key); zero = no value yet
         }
         else
         {
@@ -3895,7 +3937,7 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
                 CHGPU_TRY(chgpu_sum_add_many_conditional(ctx, col, filter, row_begin, row_end, st));
             else
                 CHGPU_TRY(chgpu_sum_add_many(ctx, col, row_begin, row_end, st));
-            if (a->kinds[j] == CHGPU_AGG_AVG)
+            if (kind == CHGPU_AGG_AVG)
                 st[1] += kept;
         }
         return CHGPU_OK;
@@ -3904,6 +3946,9 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
     const chgpu_col * const * conds = a->conditioned ? a->block_conds : nullptr;
     chgpu_col * masks[AGG_MAX_AGGS] = {};
     u64 mask_kept[AGG_MAX_AGGS] = {};
+    u32 mask_of[AGG_MAX_AGGS], mask_first[AGG_MAX_AGGS]; // functions with the same column and mode share the mask of the first of them
+    if (conds)
+        (void)agg_number_conds(a, true, mask_of, mask_first);
     int rc = CHGPU_OK;
     for (u32 j = 0; j < a->n_aggs && rc == CHGPU_OK; ++j)
     {
@@ -3912,15 +3957,13 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
             rc = add_function(j, filter, kept);
             continue;
         }
-        u32 e = 0; // an earlier function with the same column and mode shares its mask
-        while (e < j && !(masks[e] && conds[e] == conds[j] && a->cond_modes[e] == a->cond_modes[j]))
-            ++e;
-        if (e == j && n)
+        const u32 src = mask_first[mask_of[j]];
+        if (src == j && n)
         {
             rc = chgpu_col_new(ctx, CHGPU_U8, row_end, &masks[j]);
             if (rc != CHGPU_OK)
                 break;
-            hipLaunchKernelGGL(k_nokey_cond_mask, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, filter ? (const u8 *)filter->data : nullptr,
+            hipLaunchKernelGGL(k_nokey_cond_mask, dim3(grid), dim3(256), 0, ctx->stream, filter ? (const u8 *)filter->data : nullptr,
                                (const u8 *)conds[j]->data, a->cond_modes[j] == CHGPU_AGG_COND_IF ? 1 : 0, row_begin, n, (u8 *)masks[j]->data);
             ctx->counters[6] += 1;
             chgpu_col * mv = nullptr;
@@ -3933,11 +3976,11 @@ static int agg_add_nokey(chgpu_agg * a, const chgpu_col * const * arg_cols, u64 
             if (rc != CHGPU_OK)
                 break;
         }
-        const u32 src = e < j ? e : j;
         if (n)
             rc = add_function(j, masks[src], mask_kept[src]);
-        if (rc == CHGPU_OK && ((a->word_seen >> (a->word_off[j] + 1)) & 1))
-            a->host_words[a->word_off[j] + 1] += mask_kept[src];
+        const u32 seen_w = a->word_off[j] + agg_kind(a->kinds[j]).words;
+        if (rc == CHGPU_OK && ((a->words.seen >> seen_w) & 1))
+            a->host_words[seen_w] += mask_kept[src];
     }
     for (u32 j = 0; j < a->n_aggs; ++j)
         if (masks[j])
@@ -4012,7 +4055,7 @@ static int agg_add_block_ranged(chgpu_agg * a, const chgpu_col * key_col, const 
             ;
     if (S > lds_cells)
         S = lds_cells;
-    const size_t lds_ag = (size_t)PartLds(key_w <= 4 ? 4 : 8, S, a->n_words, cnt32).bytes() + 16;
+    const size_t lds_ag = (size_t)PartLds(key_w <= 4 ? 4 : 8, S, a->words.n_words, cnt32).bytes() + 16;
     const u32 wg_per_cu = lds_ag <= 76 * 1024 ? 2 : 1;
     // flushes may claim up to grid * (S+1) cells above max fill: keep that inside the slack (capacity/2)
     const u64 max_grid = (a->t.capacity / 2) / (S + 1);
@@ -4100,21 +4143,23 @@ static int agg_add_block_planned(chgpu_agg * a, const chgpu_col * key_col, const
     u64 * pending = (u64 *)scratch;
     const u32 rows_grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
 
-    // (min / max / any states go to the DIRECT kernel: the LDS-staged and partitioned plans carry additive words only)
-    // (conditioned functions: the partition buffers carry no per-function mask, see DESIGN.md §4.16.2 -- such a block takes DIRECT)
-    if (!a->has_extremum && !a->conditioned && agg_partition_gate(a, (u64)lds_cells * 7 / 10, n))
+    // Only the RANGE-mode arm applies `filter`: the caller sends a masked block here only when agg_takes_ranged says it ends there, and
+    // every other arm refuses one instead of dropping its mask.
+    const u64 lds_groups = (u64)lds_cells * 7 / 10;
+    const bool tries_partitions = agg_tries_partitions(a, lds_groups, n);
+    if (tries_partitions)
     {
+        CHGPU_REQUIRE(!filter, CHGPU_ERR_LOGICAL, "a masked block reached the partitioned GROUP BY plans, which apply no mask");
         const int rc = agg_add_block_by_partitions(a, key_col, arg_cols, row_begin, n);
         if (rc != CHGPU_ERR_NOT_IMPLEMENTED)
             return rc;
     }
     CHGPU_TRY(agg_ensure_table(a, a->size_hint));
-    // strategy: LDS-staged unless the caller promised a large cardinality (where nearly every key misses the LDS table)
-    const bool use_lds = !a->has_extremum && a->size_hint <= 65536; // beyond that nearly every key misses a workgroup's LDS table
-    // RANGE mode of the partition-aggregate kernel (agg_add_block_ranged)
-    const bool ranged = use_lds && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0); // keys of 1, 2, 4 or 8 bytes: every key type
-    if (ranged)
+    if (agg_takes_ranged(a, lds_groups, n, tries_partitions))
         return agg_add_block_ranged(a, key_col, arg_cols, row_begin, n, filter, d, pending, n_words64, lds_cells);
+    CHGPU_REQUIRE(!filter, CHGPU_ERR_LOGICAL, "a masked block reached the row-wise GROUP BY kernels, which apply no mask");
+    // LDS-staged unless the caller promised a large cardinality (where nearly every key misses the LDS table)
+    const bool use_lds = !a->has_extremum && a->size_hint <= 65536;
     if (chgpu_opt(ctx, "debug", 0))
         fprintf(stderr, "chgpu: direct GROUP BY n=%llu hint=%llu kernel=%s%s\n", (unsigned long long)n, (unsigned long long)a->size_hint, use_lds ? "rows_lds" : "rows_direct",
                 a->conditioned ? " states=conditioned" : a->has_extremum ? " states=extremum" : "");
@@ -4122,7 +4167,7 @@ static int agg_add_block_planned(chgpu_agg * a, const chgpu_col * key_col, const
     {
         // LDS cells per workgroup: the largest power of two with (1 + n_words) * 8 * (S+1) <= AGG_LDS_BYTES
         u32 S = 4096;
-        while ((size_t)(S + 1) * 8 * (1 + a->n_words) > AGG_LDS_BYTES && S > 64)
+        while ((size_t)(S + 1) * 8 * (1 + a->words.n_words) > AGG_LDS_BYTES && S > 64)
             S >>= 1;
         // flushes may claim up to grid * (S+1) cells above max fill: keep that inside the slack (capacity/2)
         u64 max_grid = (a->t.capacity / 2) / (S + 1);
@@ -4130,7 +4175,7 @@ static int agg_add_block_planned(chgpu_agg * a, const chgpu_col * key_col, const
         u32 grid = chgpu_grid_for(ctx, n, lds_threads, lds_threads >= 1024 ? 2 : 4);
         if (grid > max_grid)
             grid = (u32)(max_grid ? max_grid : 1);
-        const size_t lds = (size_t)(S + 1) * 8 * (1 + a->n_words);
+        const size_t lds = (size_t)(S + 1) * 8 * (1 + a->words.n_words);
         hipLaunchKernelGGL(k_agg_rows_lds, dim3(grid), dim3(lds_threads), lds, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n, pending, S);
     }
     else
@@ -4143,13 +4188,13 @@ static int agg_add_block_planned(chgpu_agg * a, const chgpu_col * key_col, const
     ctx->counters[6] += 1;
     CHGPU_HIP(hipGetLastError());
     CHGPU_TRY(agg_finish_rounds(a, d, key_col->data, a->key_type, row_begin, n, pending));
-    if (a->word_any)
+    if (a->words.any)
     {
         hipLaunchKernelGGL(k_agg_any_resolve, dim3(rows_grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n);
         ctx->counters[6] += 1;
         CHGPU_HIP(hipGetLastError());
     }
-    if (a->word_arg)
+    if (a->words.arg)
     {
         // the claim and resolve passes, each behind a kernel boundary (the finish rounds left every row placed and every val key final)
         hipLaunchKernelGGL(k_agg_arg_rows<2>, dim3(rows_grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, d, key_col->data, a->key_type, row_begin, n);
@@ -4157,7 +4202,7 @@ static int agg_add_block_planned(chgpu_agg * a, const chgpu_col * key_col, const
         ctx->counters[6] += 2;
         CHGPU_HIP(hipGetLastError());
     }
-    if (a->word_any || a->word_arg)
+    if (a->words.any || a->words.arg)
         a->any_seq += n;
     return CHGPU_OK;
 }
@@ -4177,11 +4222,7 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
                       (unsigned long long)filter->rows, (unsigned long long)row_end);
     }
     for (u32 j = 0; j < a->n_aggs; ++j)
-    {
-        if (a->kinds[j] == CHGPU_AGG_COUNT)
-            continue;
-        const bool arg_pair = a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX;
-        for (u32 sl = a->slot[j]; sl < a->slot[j] + (arg_pair ? 2u : 1u); ++sl) // (without the two-argument kinds slot j is aggregate j)
+        for (u32 sl = a->slot[j]; sl < agg_slot_end(a, j); ++sl)
         {
             const int want = sl == a->slot[j] ? a->arg_types[j] : a->val_types[j];
             CHGPU_REQUIRE(arg_cols && arg_cols[sl], CHGPU_ERR_BAD_ARGUMENTS, "argument column %u is NULL", sl);
@@ -4189,7 +4230,6 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
             CHGPU_REQUIRE(row_end <= arg_cols[sl]->rows, CHGPU_ERR_SIZES_MISMATCH, "argument column %u has %llu rows, block ends at %llu", sl,
                           (unsigned long long)arg_cols[sl]->rows, (unsigned long long)row_end);
         }
-    }
     if (a->key_type < 0)
         return agg_add_nokey(a, arg_cols, row_begin, row_end, filter);
     CHGPU_REQUIRE(key_col, CHGPU_ERR_BAD_ARGUMENTS, "key column is NULL");
@@ -4227,8 +4267,7 @@ static int agg_add_block_impl(chgpu_agg * a, const chgpu_col * key_col, const ch
     // a WHERE mask is fused only into the RANGE-mode kernel; every other strategy gets the filtered block materialised first
     if (filter)
     {
-        const bool will_range = (a->conditioned || !agg_partition_gate(a, lds_groups, n)) && a->size_hint <= 65536 && n < (1ull << 32) && !chgpu_opt(ctx, "tune_agg_no_ranged", 0) && !a->has_extremum;
-        if (!will_range)
+        if (!agg_takes_ranged(a, lds_groups, n))
             return agg_add_block_materialised(a, key_col, arg_cols, row_begin, row_end, filter);
         // The aggregation kernel is issue-bound: it spends nearly the same time on a masked-out row as on a kept one, while
         // chgpu_filter_columns runs at HBM speed.  Measured break-even at ~30 % of the rows kept (1e9 rows, 1000 groups,
@@ -4264,8 +4303,7 @@ static int agg_merge_tuples(chgpu_agg * a, const u64 * src_keys, const u64 * src
     CHGPU_TRY(chgpu_scratch(ctx, n_words64 * sizeof(u64) + 256, &scratch));
     u64 * pending = (u64 *)scratch;
     const u32 grid = chgpu_grid_for(ctx, n, AGG_THREADS, 8);
-    hipLaunchKernelGGL(k_agg_tuples<AGG_MODE_ALL>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, a->n_words, a->word_is_f64, agg_fx_words(a),
-                       src_keys, src_words, src_stride, n, skip_zero_keys, zero_slot_index, 1, pending);
+    hipLaunchKernelGGL(k_agg_tuples<AGG_MODE_ALL>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, AggMergeWords(a->words), 0u, src_keys, src_words, src_stride, n, skip_zero_keys, zero_slot_index, 1, pending);
     ctx->counters[6] += 1;
     CHGPU_HIP(hipGetLastError());
     for (int round = 0; round < 64; ++round)
@@ -4274,12 +4312,12 @@ static int agg_merge_tuples(chgpu_agg * a, const u64 * src_keys, const u64 * src
         CHGPU_TRY(agg_read_ctrl(a, &c));
         if (!c.overflow)
         {
-            if (a->word_arg)
+            if (a->words.arg)
             {
                 // argMin / argMax: every val key is final; the source states that hold one claim, then the winner stores its arg
-                hipLaunchKernelGGL(k_agg_arg_tuples<2>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, a->n_words, a->word_arg, src_keys, src_words, src_stride, n,
+                hipLaunchKernelGGL(k_agg_arg_tuples<2>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, a->words, src_keys, src_words, src_stride, n,
                                    skip_zero_keys, zero_slot_index);
-                hipLaunchKernelGGL(k_agg_arg_tuples<3>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, a->n_words, a->word_arg, src_keys, src_words, src_stride, n,
+                hipLaunchKernelGGL(k_agg_arg_tuples<3>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, a->words, src_keys, src_words, src_stride, n,
                                    skip_zero_keys, zero_slot_index);
                 ctx->counters[6] += 2;
                 CHGPU_HIP(hipGetLastError());
@@ -4287,51 +4325,55 @@ static int agg_merge_tuples(chgpu_agg * a, const u64 * src_keys, const u64 * src
             return CHGPU_OK;
         }
         CHGPU_TRY(agg_grow(a, c.n_groups, c.has_zero != 0));
-        hipLaunchKernelGGL(k_agg_tuples<AGG_MODE_PENDING>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, a->n_words, a->word_is_f64, agg_fx_words(a),
-                           src_keys, src_words, src_stride, n, skip_zero_keys, zero_slot_index, 1, pending);
+        hipLaunchKernelGGL(k_agg_tuples<AGG_MODE_PENDING>, dim3(grid), dim3(AGG_THREADS), 0, ctx->stream, a->t, AggMergeWords(a->words), 0u, src_keys, src_words, src_stride, n, skip_zero_keys, zero_slot_index, 1, pending);
         ctx->counters[6] += 1;
         CHGPU_HIP(hipGetLastError());
     }
     return chgpu_set_error(CHGPU_ERR_LOGICAL, "aggregation merge did not converge after 64 growth rounds");
 }
 
-// one without-key state word of `src_words` folded into dst (mergeWithoutKeyDataImpl, Aggregator.cpp:2584-2628); returns the words consumed
-static u32 agg_merge_host_word(chgpu_agg * dst, u32 w, const u64 * src_words)
+// One state row `src` folded into the row `dst` of the same layout, on the host (mergeWithoutKeyDataImpl, Aggregator.cpp:2584-2628):
+// the states of an aggregation without key, an overflow row
+static void agg_combine_row(const AggWords & ws, u64 * dst, const u64 * src)
 {
-    if ((dst->word_any >> w) & 1)
+    for (u32 w = 0; w < ws.n_words; ++w)
     {
-        if (dst->host_words[w] == 0 && src_words[w] != 0) // changeFirstTime: a state that has a value keeps it
+        if ((ws.fx_high >> w) & 1)
+            continue; // with its low half
+        if ((ws.fx >> w) & 1)
         {
-            dst->host_words[w] = src_words[w];
-            dst->host_words[w + 1] = src_words[w + 1];
+            const u32 h = ws.fx_hi[w];
+            const u64 lo = dst[w] + src[w];
+            dst[h] += src[h] + (lo < dst[w] ? 1 : 0);
+            dst[w] = lo;
         }
-        return 2;
-    }
-    if ((dst->word_arg >> w) & 1)
-    {
-        // a source that has a value replaces a state without one, or one whose val is strictly worse; {val, arg} move together and
-        // the claim becomes ~0: older than every row to come
-        if (src_words[w + 1] != 0 && (dst->host_words[w + 1] == 0 || src_words[w] > dst->host_words[w]))
+        else if ((ws.any >> w) & 1)
         {
-            dst->host_words[w] = src_words[w];
-            dst->host_words[w + 1] = ~0ull;
-            dst->host_words[w + 2] = src_words[w + 2];
+            if (dst[w] == 0 && src[w] != 0) // changeFirstTime: a state that has a value keeps it
+                dst[w] = src[w], dst[w + 1] = src[w + 1];
+            ++w;
         }
-        return 3;
+        else if ((ws.arg >> w) & 1)
+        {
+            // a source that has a value replaces a state without one, or one whose val is strictly worse; {val, arg} move together and
+            // the claim becomes ~0: older than every row to come
+            if (src[w + 1] != 0 && (dst[w + 1] == 0 || src[w] > dst[w]))
+                dst[w] = src[w], dst[w + 1] = ~0ull, dst[w + 2] = src[w + 2];
+            w += 2;
+        }
+        else if (ws.op(w) == 2)
+            dst[w] = src[w] > dst[w] ? src[w] : dst[w]; // min / max order keys
+        else if (ws.op(w) == 1)
+        {
+            double x, y;
+            memcpy(&x, &dst[w], 8);
+            memcpy(&y, &src[w], 8);
+            x += y;
+            memcpy(&dst[w], &x, 8);
+        }
+        else
+            dst[w] += src[w];
     }
-    if ((dst->word_is_f64 >> (16 + w)) & 1)
-        dst->host_words[w] = src_words[w] > dst->host_words[w] ? src_words[w] : dst->host_words[w]; // min / max order keys
-    else if ((dst->word_is_f64 >> w) & 1)
-    {
-        double x, y;
-        memcpy(&x, &dst->host_words[w], 8);
-        memcpy(&y, &src_words[w], 8);
-        x += y;
-        memcpy(&dst->host_words[w], &x, 8);
-    }
-    else
-        dst->host_words[w] += src_words[w];
-    return 1;
 }
 
 static bool agg_same_shape(const chgpu_agg * x, const chgpu_agg * y)
@@ -4347,12 +4389,12 @@ static bool agg_same_shape(const chgpu_agg * x, const chgpu_agg * y)
 // Both sides of a merge to ONE fixed-point window (see chgpu_agg_merge)
 static int agg_merge_align_fx(chgpu_agg * dst, const chgpu_agg * src)
 {
-    if (dst->word_fx || src->word_fx)
+    if (dst->words.fx || src->words.fx)
     {
         // fixed-point sums: both sides to ONE window first (the source's states are re-expressed in place: same values, possibly a coarser
         // unit -- the reference's merge consumes its source too), or both back to doubles when one of them met a NaN / infinity
         chgpu_agg * s = const_cast<chgpu_agg *>(src);
-        if (!dst->word_fx || !s->word_fx)
+        if (!dst->words.fx || !s->words.fx)
         {
             CHGPU_TRY(agg_fx_to_plain(dst));
             CHGPU_TRY(agg_fx_to_plain(s));
@@ -4394,8 +4436,8 @@ static int agg_merge_align_fx(chgpu_agg * dst, const chgpu_agg * src)
     return CHGPU_OK;
 }
 
-// mergeWithoutKeyDataImpl for the overflow rows (Aggregator.cpp:2584-2628): src's words (host copy, the window already shared) folded
-// into dst's, on the host -- one row of at most AGG_MAX_WORDS words
+// The overflow rows merge like states without key: src's words (host copy, the window already shared) folded into dst's, on the host
+// -- one row of at most AGG_MAX_WORDS words
 static int agg_fold_overflow_words(chgpu_agg * dst, const u64 * in)
 {
     if (!dst->ovf_mem)
@@ -4404,44 +4446,9 @@ static int agg_fold_overflow_words(chgpu_agg * dst, const u64 * in)
         CHGPU_HIP(hipMemsetAsync(dst->ovf_mem, 0, AGG_MAX_WORDS * 8, dst->ctx->stream));
     }
     u64 o[AGG_MAX_WORDS] = {0};
-    CHGPU_TRY(chgpu_read_back(dst->ctx, dst->ovf_mem, o, dst->n_words * 8));
-    for (u32 w = 0; w < dst->n_words; ++w)
-    {
-        if ((dst->word_fx_hi >> w) & 1)
-            continue; // with its low half
-        if ((dst->word_fx >> w) & 1)
-        {
-            const u32 h = dst->fx_hi[w];
-            const u64 lo = o[w] + in[w];
-            o[h] += in[h] + (lo < o[w] ? 1 : 0);
-            o[w] = lo;
-        }
-        else if ((dst->word_any >> w) & 1)
-        {
-            if (o[w] == 0 && in[w] != 0) // changeFirstTime: a state that has a value keeps it
-                o[w] = in[w], o[w + 1] = in[w + 1];
-            ++w;
-        }
-        else if ((dst->word_arg >> w) & 1)
-        {
-            if (in[w + 1] != 0 && (o[w + 1] == 0 || in[w] > o[w])) // as agg_merge_host_word
-                o[w] = in[w], o[w + 1] = ~0ull, o[w + 2] = in[w + 2];
-            w += 2;
-        }
-        else if ((dst->word_is_f64 >> (16 + w)) & 1)
-            o[w] = in[w] > o[w] ? in[w] : o[w];
-        else if ((dst->word_is_f64 >> w) & 1)
-        {
-            double x, y;
-            memcpy(&x, &o[w], 8);
-            memcpy(&y, &in[w], 8);
-            x += y;
-            memcpy(&o[w], &x, 8);
-        }
-        else
-            o[w] += in[w];
-    }
-    CHGPU_HIP(hipMemcpyAsync(dst->ovf_mem, o, dst->n_words * 8, hipMemcpyHostToDevice, dst->ctx->stream));
+    CHGPU_TRY(chgpu_read_back(dst->ctx, dst->ovf_mem, o, dst->words.n_words * 8));
+    agg_combine_row(dst->words, o, in);
+    CHGPU_HIP(hipMemcpyAsync(dst->ovf_mem, o, dst->words.n_words * 8, hipMemcpyHostToDevice, dst->ctx->stream));
     CHGPU_HIP(hipStreamSynchronize(dst->ctx->stream)); // (o is on this stack frame)
     return CHGPU_OK;
 }
@@ -4450,7 +4457,7 @@ static int agg_merge_overflow_rows(chgpu_agg * dst, const chgpu_agg * src)
     if (!src->ovf_mem)
         return CHGPU_OK;
     u64 in[AGG_MAX_WORDS] = {0};
-    CHGPU_TRY(chgpu_read_back(src->ctx, src->ovf_mem, in, src->n_words * 8));
+    CHGPU_TRY(chgpu_read_back(src->ctx, src->ovf_mem, in, src->words.n_words * 8));
     return agg_fold_overflow_words(dst, in);
 }
 
@@ -4466,14 +4473,13 @@ extern "C" int chgpu_agg_merge(chgpu_agg * dst, const chgpu_agg * src)
     if (dst->key_type < 0)
     {
         // mergeWithoutKeyDataImpl (Aggregator.cpp:2584-2628)
-        for (u32 w = 0; w < dst->n_words;)
-            w += agg_merge_host_word(dst, w, src->host_words);
+        agg_combine_row(dst->words, dst->host_words, src->host_words);
         dst->nokey_kept += src->nokey_kept;
         return CHGPU_OK;
     }
     if (!src->table_mem && !src->ovf_mem)
         return CHGPU_OK;
-    CHGPU_REQUIRE(dst->n_words == src->n_words, CHGPU_ERR_BAD_ARGUMENTS, "cannot merge aggregations created under different deterministic_float_sums settings");
+    CHGPU_REQUIRE(dst->words.n_words == src->words.n_words, CHGPU_ERR_BAD_ARGUMENTS, "cannot merge aggregations created under different deterministic_float_sums settings");
     CHGPU_TRY(agg_merge_align_fx(dst, src));
     CHGPU_TRY(agg_merge_overflow_rows(dst, src));
     if (!src->table_mem)
@@ -4485,30 +4491,64 @@ extern "C" int chgpu_agg_merge(chgpu_agg * dst, const chgpu_agg * src)
     return agg_merge_tuples(dst, src->t.keys, src->t.words, src->t.capacity + 1, n, 1, sc.has_zero ? src->t.capacity : ~0ull);
 }
 
+// The public state columns a merge is given: one per public word, 8 bytes wide, `rows` rows at least.  (An is_overflows block answers
+// a narrow or short column with one message of its own.)
+static int agg_check_state_cols(const chgpu_agg * dst, const chgpu_col * const * state_cols, u64 rows, bool is_overflows)
+{
+    for (u32 w = 0; w < dst->words.n_pub_words; ++w)
+    {
+        CHGPU_REQUIRE(state_cols[w], CHGPU_ERR_BAD_ARGUMENTS, "state column %u is NULL", w);
+        const bool wide = chgpu_type_size(state_cols[w]->type) == 8, tall = state_cols[w]->rows >= rows;
+        if (is_overflows)
+            CHGPU_REQUIRE(wide && tall, CHGPU_ERR_BAD_ARGUMENTS, "state column %u: 8-byte words, %llu rows", w, (unsigned long long)rows);
+        else
+        {
+            CHGPU_REQUIRE(wide, CHGPU_ERR_BAD_ARGUMENTS, "state column %u must be 8 bytes wide", w);
+            CHGPU_REQUIRE(tall, CHGPU_ERR_SIZES_MISMATCH, "state column %u shorter than %llu rows", w, (unsigned long long)rows);
+        }
+    }
+    return CHGPU_OK;
+}
+
+// Float64 sum states arriving in state columns for fixed-point sums: each of the `rows` states is one value for the window -- or, with
+// a NaN / infinity among them, the end of the fixed-point mode (agg_fx_to_plain)
+static int agg_fx_admit_states(chgpu_agg * dst, const chgpu_col * const * state_cols, u64 rows)
+{
+    if (!dst->words.fx)
+        return CHGPU_OK;
+    u32 emax = 0, emin = 2047;
+    for (u32 w = 0; w < dst->words.n_pub_words; ++w)
+        if ((dst->words.fx >> w) & 1)
+        {
+            u32 e = 0, em = 2047;
+            bool bad = false;
+            CHGPU_TRY(agg_fx_stats(dst->ctx, state_cols[w]->data, CHGPU_F64, 0, rows, nullptr, 0, &e, &em, &bad));
+            if (bad)
+                return agg_fx_to_plain(dst);
+            emax = e > emax ? e : emax;
+            emin = em < emin ? em : emin;
+        }
+    return agg_fx_admit(dst, emax, emin, rows);
+}
+
 extern "C" int chgpu_agg_merge_states(chgpu_agg * dst, const chgpu_col * key_col, const chgpu_col * const * state_cols, uint64_t rows)
 {
     ChgpuDeviceGuard _dev_guard(dst ? dst->ctx : nullptr);
     CHGPU_REQUIRE(dst && state_cols, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
     chgpu_ctx * ctx = dst->ctx;
-    for (u32 w = 0; w < dst->n_pub_words; ++w)
-    {
-        CHGPU_REQUIRE(state_cols[w], CHGPU_ERR_BAD_ARGUMENTS, "state column %u is NULL", w);
-        CHGPU_REQUIRE(chgpu_type_size(state_cols[w]->type) == 8, CHGPU_ERR_BAD_ARGUMENTS, "state column %u must be 8 bytes wide", w);
-        CHGPU_REQUIRE(state_cols[w]->rows >= rows, CHGPU_ERR_SIZES_MISMATCH, "state column %u shorter than %llu rows", w, (unsigned long long)rows);
-    }
+    CHGPU_TRY(agg_check_state_cols(dst, state_cols, rows, false));
     if (dst->key_type < 0)
     {
         CHGPU_REQUIRE(rows <= 1, CHGPU_ERR_BAD_ARGUMENTS, "without_key states merge one row at a time");
         if (rows == 0)
             return CHGPU_OK;
         u64 in[AGG_MAX_WORDS] = {0};
-        for (u32 w = 0; w < dst->n_words; ++w)
+        for (u32 w = 0; w < dst->words.n_words; ++w)
             CHGPU_TRY(chgpu_read_back(ctx, state_cols[w]->data, &in[w], 8));
         bool any_set = false;
-        for (u32 w = 0; w < dst->n_words; ++w)
+        for (u32 w = 0; w < dst->words.n_words; ++w)
             any_set = any_set || in[w] != 0;
-        for (u32 w = 0; w < dst->n_words;)
-            w += agg_merge_host_word(dst, w, in);
+        agg_combine_row(dst->words, dst->host_words, in);
         dst->nokey_kept += any_set ? 1 : 0; // (a partial state of an empty input is all zeros)
         return CHGPU_OK;
     }
@@ -4516,27 +4556,10 @@ extern "C" int chgpu_agg_merge_states(chgpu_agg * dst, const chgpu_col * key_col
     CHGPU_REQUIRE(key_col->type == dst->key_type, CHGPU_ERR_BAD_ARGUMENTS, "key column type mismatch");
     if (rows == 0)
         return CHGPU_OK;
-    // Float64 sum states arriving for fixed-point sums: each is one value for the window (or the end of the fixed-point mode)
-    if (dst->word_fx)
-    {
-        u32 emax = 0, emin = 2047;
-        bool bad = false;
-        for (u32 w = 0; w < dst->n_pub_words && !bad; ++w)
-            if ((dst->word_fx >> w) & 1)
-            {
-                u32 e = 0, em = 2047;
-                CHGPU_TRY(agg_fx_stats(ctx, state_cols[w]->data, CHGPU_F64, 0, rows, nullptr, 0, &e, &em, &bad));
-                emax = e > emax ? e : emax;
-                emin = em < emin ? em : emin;
-            }
-        if (bad)
-            CHGPU_TRY(agg_fx_to_plain(dst));
-        else
-            CHGPU_TRY(agg_fx_admit(dst, emax, emin, rows));
-    }
+    CHGPU_TRY(agg_fx_admit_states(dst, state_cols, rows));
     // stage into one SoA buffer [keys u64][words...] so the tuple kernel sees a single stride
     chgpu_col * stage = nullptr;
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, rows * (1 + dst->n_words), &stage));
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, rows * (1 + dst->words.n_words), &stage));
     u64 * sk = (u64 *)stage->data;
     int rc = CHGPU_OK;
     {
@@ -4552,12 +4575,12 @@ extern "C" int chgpu_agg_merge_states(chgpu_agg * dst, const chgpu_col * key_col
                 break;
             }
         }
-        for (u32 w = 0; w < dst->n_pub_words && rc == CHGPU_OK; ++w)
+        for (u32 w = 0; w < dst->words.n_pub_words && rc == CHGPU_OK; ++w)
         {
-            if ((dst->word_fx >> w) & 1)
+            if ((dst->words.fx >> w) & 1)
             {
                 hipLaunchKernelGGL(k_fx_from_double, dim3(grid), dim3(256), 0, ctx->stream, (const u64 *)state_cols[w]->data, (u64)rows, dst->fx_base,
-                                   sk + (u64)(w + 1) * rows, sk + (u64)(dst->fx_hi[w] + 1) * rows);
+                                   sk + (u64)(w + 1) * rows, sk + (u64)(dst->words.fx_hi[w] + 1) * rows);
                 ctx->counters[6] += 1;
                 continue;
             }
@@ -4660,7 +4683,7 @@ extern "C" int chgpu_agg_merge_limited(chgpu_agg * dst, const chgpu_agg * src, i
     *keep_merging = 1;
     if (dst->key_type < 0)
         return chgpu_agg_merge(dst, src);
-    CHGPU_REQUIRE(agg_same_shape(dst, src) && dst->n_words == src->n_words, CHGPU_ERR_BAD_ARGUMENTS, "cannot merge aggregation states of different shape");
+    CHGPU_REQUIRE(agg_same_shape(dst, src) && dst->words.n_words == src->words.n_words, CHGPU_ERR_BAD_ARGUMENTS, "cannot merge aggregation states of different shape");
     dst->started = true;
     // mergeSingleLevelDataImpl: checkLimits on dst's size before the source is merged
     if (!*no_more_keys)
@@ -4702,41 +4725,20 @@ extern "C" int chgpu_agg_merge_states_limited(chgpu_agg * dst, const chgpu_col *
     {
         // a block flagged is_overflows: its (one) row merges into the overflow row (mergeBlockWithoutKeyStreamsImpl)
         CHGPU_REQUIRE(rows <= 1, CHGPU_ERR_BAD_ARGUMENTS, "an is_overflows block has one row");
-        for (u32 w = 0; w < dst->n_pub_words; ++w)
-        {
-            CHGPU_REQUIRE(state_cols[w], CHGPU_ERR_BAD_ARGUMENTS, "state column %u is NULL", w);
-            CHGPU_REQUIRE(chgpu_type_size(state_cols[w]->type) == 8 && state_cols[w]->rows >= rows, CHGPU_ERR_BAD_ARGUMENTS, "state column %u: 8-byte words, %llu rows", w,
-                          (unsigned long long)rows);
-        }
+        CHGPU_TRY(agg_check_state_cols(dst, state_cols, rows, true));
         if (rows == 0)
             return CHGPU_OK;
         u64 in[AGG_MAX_WORDS] = {0};
-        for (u32 w = 0; w < dst->n_pub_words; ++w)
+        for (u32 w = 0; w < dst->words.n_pub_words; ++w)
             CHGPU_TRY(chgpu_read_back(dst->ctx, state_cols[w]->data, &in[w], 8));
-        if (dst->word_fx)
-        {
-            // Float64 states of fixed-point sums: admitted to the window like any state column, then converted
-            u32 emax = 0, emin = 2047;
-            bool bad = false;
-            for (u32 w = 0; w < dst->n_pub_words && !bad; ++w)
-                if ((dst->word_fx >> w) & 1)
-                {
-                    u32 e = 0, em = 2047;
-                    CHGPU_TRY(agg_fx_stats(dst->ctx, state_cols[w]->data, CHGPU_F64, 0, 1, nullptr, 0, &e, &em, &bad));
-                    emax = e > emax ? e : emax;
-                    emin = em < emin ? em : emin;
-                }
-            if (bad)
-                CHGPU_TRY(agg_fx_to_plain(dst));
-            else
-                CHGPU_TRY(agg_fx_admit(dst, emax, emin, 1));
-            for (u32 w = 0; w < dst->n_pub_words; ++w)
-                if ((dst->word_fx >> w) & 1)
-                {
-                    const Fx128 x = fx_from_double(in[w], dst->fx_base);
-                    in[w] = x.lo, in[dst->fx_hi[w]] = x.hi;
-                }
-        }
+        // Float64 states of fixed-point sums: admitted to the window like any state column, then converted
+        CHGPU_TRY(agg_fx_admit_states(dst, state_cols, 1));
+        for (u32 w = 0; w < dst->words.n_pub_words; ++w)
+            if ((dst->words.fx >> w) & 1)
+            {
+                const Fx128 x = fx_from_double(in[w], dst->fx_base);
+                in[w] = x.lo, in[dst->words.fx_hi[w]] = x.hi;
+            }
         return agg_fold_overflow_words(dst, in);
     }
     const bool find_only = *no_more_keys != 0;
@@ -4754,6 +4756,14 @@ extern "C" int chgpu_agg_merge_states_limited(chgpu_agg * dst, const chgpu_col *
     return agg_check_limits(dst, g, no_more_keys, keep_reading);
 }
 
+// The state word that tells whether any row reached function j (0 = none): its `seen` word, avg's denominator, the claim of any /
+// argMin / argMax; ~0 = it has none (count; an -If sum, whose empty state already reads 0; an unconditioned min / max)
+static u32 agg_reached_word(const chgpu_agg * a, u32 j)
+{
+    const AggKind & k = agg_kind(a->kinds[j]);
+    const u32 rw = a->word_off[j] + k.reached;
+    return k.reached < k.words || ((a->words.seen >> rw) & 1) ? rw : ~0u;
+}
 // The overflow row: final -> one result per aggregate (the without-key conventions: count / sum 0, avg NaN, min / max / any the type's
 // default when no row reached it), else its raw state words as chgpu_agg_export_states gives them.  One-row columns; *has = 0 when the
 // aggregation has none.
@@ -4766,31 +4776,32 @@ extern "C" int chgpu_agg_overflow_row(chgpu_agg * a, int final, chgpu_col ** col
         return CHGPU_OK;
     chgpu_ctx * ctx = a->ctx;
     u64 o[AGG_MAX_WORDS] = {0};
-    CHGPU_TRY(chgpu_read_back(ctx, a->ovf_mem, o, a->n_words * 8));
+    CHGPU_TRY(chgpu_read_back(ctx, a->ovf_mem, o, a->words.n_words * 8));
     // fixed-point pairs to their Float64 value (the public word)
     u64 pub[AGG_MAX_WORDS] = {0};
-    for (u32 w = 0; w < a->n_pub_words; ++w)
+    for (u32 w = 0; w < a->words.n_pub_words; ++w)
     {
         pub[w] = o[w];
-        if ((a->word_fx >> w) & 1)
+        if ((a->words.fx >> w) & 1)
         {
-            const double x = fx_to_double(o[w], o[a->fx_hi[w]], a->fx_base);
+            const double x = fx_to_double(o[w], o[a->words.fx_hi[w]], a->fx_base);
             memcpy(&pub[w], &x, 8);
         }
     }
-    const u32 n_out = final ? a->n_aggs : a->n_pub_words;
+    const u32 n_out = final ? a->n_aggs : a->words.n_pub_words;
     for (u32 k = 0; k < n_out; ++k)
         cols[k] = nullptr;
     int rc = CHGPU_OK;
     if (!final)
     {
-        for (u32 w = 0; w < a->n_pub_words && rc == CHGPU_OK; ++w)
-            rc = chgpu_col_upload(ctx, (((a->word_is_f64 | a->word_fx) >> w) & 1) ? CHGPU_F64 : CHGPU_U64, &pub[w], 1, &cols[w]);
+        for (u32 w = 0; w < a->words.n_pub_words && rc == CHGPU_OK; ++w)
+            rc = chgpu_col_upload(ctx, a->words.pub_type(w), &pub[w], 1, &cols[w]);
     }
     else
         for (u32 j = 0; j < a->n_aggs && rc == CHGPU_OK; ++j)
         {
             const u32 w = a->word_off[j];
+            const AggKind & k = agg_kind(a->kinds[j]);
             const int at = a->arg_types[j];
             const bool f = chgpu_type_is_float(at);
             u64 v = 0;
@@ -4816,13 +4827,13 @@ extern "C" int chgpu_agg_overflow_row(chgpu_agg * a, int final, chgpu_col ** col
                 default:
                 {
                     // min / max / any / argMin / argMax: the value in the argument's type; the type's default when no row reached it
+                    // a row reached it: a conditioned min / max has its `seen` word, any / argMin / argMax their claim; a bare min / max
+                    // key is non-zero once set
                     type = at;
-                    if (a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX)
-                        v = pub[w + 1] ? pub[w + 2] : 0; // {val key, has, arg bits}
-                    else if (a->kinds[j] != CHGPU_AGG_ANY && a->cond_modes[j] != CHGPU_AGG_COND_NONE)
-                        v = pub[w + 1] ? agg_order_key_inverse(a->kinds[j] == CHGPU_AGG_MIN ? ~pub[w] : pub[w], at) : 0; // `seen` rows reached the min / max
-                    else if (pub[w])
-                        v = a->kinds[j] == CHGPU_AGG_ANY ? pub[w + 1] : agg_order_key_inverse(a->kinds[j] == CHGPU_AGG_MIN ? ~pub[w] : pub[w], at);
+                    const u32 rw = agg_reached_word(a, j);
+                    const bool reached = pub[rw == ~0u ? w : rw] != 0;
+                    if (reached)
+                        v = k.words > 1 ? pub[w + k.result] : agg_order_key_inverse(a->kinds[j] == CHGPU_AGG_MIN ? ~pub[w] : pub[w], at); // (any, arg: bits as loaded)
                     if (at == CHGPU_F32)
                     {
                         double x;
@@ -4877,13 +4888,13 @@ extern "C" int chgpu_agg_size(chgpu_agg * a, uint64_t * groups)
 static int agg_export(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** word_cols /* [n_words] */, u64 * groups)
 {
     chgpu_ctx * ctx = a->ctx;
-    for (u32 w = 0; w < a->n_words; ++w)
+    for (u32 w = 0; w < a->words.n_words; ++w)
         word_cols[w] = nullptr;
     if (a->key_type < 0)
     {
-        for (u32 w = 0; w < a->n_words; ++w)
+        for (u32 w = 0; w < a->words.n_words; ++w)
         {
-            CHGPU_TRY(chgpu_col_upload(ctx, ((a->word_is_f64 >> w) & 1) ? CHGPU_F64 : CHGPU_U64, &a->host_words[w], 1, &word_cols[w]));
+            CHGPU_TRY(chgpu_col_upload(ctx, a->words.pub_type(w), &a->host_words[w], 1, &word_cols[w]));
         }
         if (keys_out)
             *keys_out = nullptr;
@@ -4894,8 +4905,8 @@ static int agg_export(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** word_co
     {
         if (keys_out)
             CHGPU_TRY(chgpu_col_new(ctx, a->key_type, 0, keys_out));
-        for (u32 w = 0; w < a->n_pub_words; ++w)
-            CHGPU_TRY(chgpu_col_new(ctx, (((a->word_is_f64 | a->word_fx) >> w) & 1) ? CHGPU_F64 : CHGPU_U64, 0, &word_cols[w]));
+        for (u32 w = 0; w < a->words.n_pub_words; ++w)
+            CHGPU_TRY(chgpu_col_new(ctx, a->words.pub_type(w), 0, &word_cols[w]));
         *groups = 0;
         return CHGPU_OK;
     }
@@ -4919,24 +4930,24 @@ static int agg_export(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** word_co
         chgpu_col views[1 + AGG_MAX_WORDS];
         const chgpu_col * vin[1 + AGG_MAX_WORDS];
         chgpu_col * vout[1 + AGG_MAX_WORDS] = {nullptr};
-        for (u32 c = 0; c <= a->n_words; ++c)
+        for (u32 c = 0; c <= a->words.n_words; ++c)
         {
             views[c] = view;
-            views[c].type = c == 0 ? CHGPU_U64 : (((a->word_is_f64 >> (c - 1)) & 1) ? CHGPU_F64 : CHGPU_U64);
+            views[c].type = c == 0 || a->words.op(c - 1) != 1 ? CHGPU_U64 : CHGPU_F64; // (a fixed-point pair: two integer words until it is folded below)
             views[c].data = c == 0 ? (void *)a->t.keys : (void *)(a->t.words + (u64)(c - 1) * cells);
             vin[c] = &views[c];
         }
-        rc = chgpu_filter_columns(ctx, 1 + a->n_words, vin, mask, 0, vout, &n_out);
+        rc = chgpu_filter_columns(ctx, 1 + a->words.n_words, vin, mask, 0, vout, &n_out);
         if (rc == CHGPU_OK)
         {
             k64 = vout[0];
-            for (u32 w = 0; w < a->n_words; ++w)
+            for (u32 w = 0; w < a->words.n_words; ++w)
                 word_cols[w] = vout[1 + w];
         }
     }
     chgpu_col_free(mask);
     auto drop_words = [&]() {
-        for (u32 w = 0; w < a->n_words; ++w)
+        for (u32 w = 0; w < a->words.n_words; ++w)
         {
             chgpu_col_free(word_cols[w]); // the word columns already filtered when a later step failed
             word_cols[w] = nullptr;
@@ -4945,18 +4956,18 @@ static int agg_export(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** word_co
     if (rc == CHGPU_OK)
     {
         // the fixed-point sums leave as the doubles they stand for (one rounding per group); the spare high words stay inside
-        for (u32 w = 0; w < a->n_pub_words; ++w)
-            if ((a->word_fx >> w) & 1)
+        for (u32 w = 0; w < a->words.n_pub_words; ++w)
+            if ((a->words.fx >> w) & 1)
             {
                 if (n_out)
                 {
                     hipLaunchKernelGGL(k_fx_to_double, dim3(chgpu_grid_for(ctx, n_out, 256, 8)), dim3(256), 0, ctx->stream, (u64 *)word_cols[w]->data,
-                                       (u64 *)word_cols[a->fx_hi[w]]->data, n_out, a->fx_base, 0);
+                                       (u64 *)word_cols[a->words.fx_hi[w]]->data, n_out, a->fx_base, 0);
                     ctx->counters[6] += 1;
                 }
                 word_cols[w]->type = CHGPU_F64;
             }
-        for (u32 w = a->n_pub_words; w < a->n_words; ++w)
+        for (u32 w = a->words.n_pub_words; w < a->words.n_words; ++w)
         {
             chgpu_col_free(word_cols[w]); // pooled: reuse is stream-ordered behind the conversion
             word_cols[w] = nullptr;
@@ -5024,7 +5035,7 @@ extern "C" int chgpu_agg_export_states_two_level(chgpu_agg * a, chgpu_col ** key
     chgpu_col * words[AGG_MAX_WORDS] = {nullptr};
     u64 n = 0;
     CHGPU_TRY(agg_export(a, &keys, words, &n));
-    const u32 nw = a->n_pub_words;
+    const u32 nw = a->words.n_pub_words;
     chgpu_col * sorted[AGG_MAX_WORDS + 1] = {nullptr};
     int rc = CHGPU_OK;
     // <= 8 columns per partition call; the key column rides in the first
@@ -5074,19 +5085,6 @@ __global__ __launch_bounds__(256) void k_extremum_decode(const u64 * __restrict_
     }
 }
 
-// The state word that tells whether any row reached conditioned function j (0 = none): its `seen` word, avg's denominator, the claim
-// of any / argMin / argMax; ~0 = the function needs none (count; an -If sum, whose empty state already reads 0)
-static u32 agg_reached_word(const chgpu_agg * a, u32 j)
-{
-    const u32 w = a->word_off[j];
-    switch (a->kinds[j])
-    {
-        case CHGPU_AGG_COUNT: return ~0u;
-        case CHGPU_AGG_SUM: return a->cond_modes[j] == CHGPU_AGG_COND_NULL ? w + 1 : ~0u;
-        case CHGPU_AGG_ANY: return w;
-        default: return w + 1; // avg, min / max, argMin / argMax
-    }
-}
 // The results of a conditioned function whose state no row reached: the nested value becomes the type's default where `zero` says so
 // (min / max decode an empty word to the type's extremum, a NULL-mode avg divides 0 by 0), and the null map gets its byte.
 __global__ __launch_bounds__(256) void k_cond_results(const u64 * __restrict__ reached, u64 n, u32 value_bytes, int zero, void * __restrict__ values,
@@ -5137,10 +5135,9 @@ static int agg_finalize_impl(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** 
             res_cols[j] = words[w];
             words[w] = nullptr;
         }
-        else if (a->kinds[j] == CHGPU_AGG_MIN || a->kinds[j] == CHGPU_AGG_MAX || a->kinds[j] == CHGPU_AGG_ANY || a->kinds[j] == CHGPU_AGG_ARG_MIN ||
-                 a->kinds[j] == CHGPU_AGG_ARG_MAX)
+        else if (agg_kind(a->kinds[j]).extremum)
         {
-            const bool arg_pair = a->kinds[j] == CHGPU_AGG_ARG_MIN || a->kinds[j] == CHGPU_AGG_ARG_MAX;
+            const AggKind & k = agg_kind(a->kinds[j]);
             // insertResultInto: the value itself, in the argument's type (AggregateFunctionsMinMax.cpp)
             chgpu_col * r = nullptr;
             rc = chgpu_col_new(ctx, a->arg_types[j], n, &r);
@@ -5152,8 +5149,7 @@ static int agg_finalize_impl(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** 
             {
                 // (any, argMin / argMax: the value word, as loaded -- no order key to undo; a cell only a value-less imported state reached holds 0)
                 hipLaunchKernelGGL(k_extremum_decode, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream,
-                                   (const u64 *)words[arg_pair ? w + 2 : a->kinds[j] == CHGPU_AGG_ANY ? w + 1 : w]->data, n, a->arg_types[j],
-                                   a->kinds[j] == CHGPU_AGG_MIN ? 1 : (a->kinds[j] == CHGPU_AGG_ANY || arg_pair) ? 2 : 0, r->data);
+                                   (const u64 *)words[w + k.result]->data, n, a->arg_types[j], a->kinds[j] == CHGPU_AGG_MIN ? 1 : k.words > 1 ? 2 : 0, r->data);
                 ctx->counters[6] += 1;
             }
             res_cols[j] = r;
@@ -5189,7 +5185,7 @@ static int agg_finalize_impl(chgpu_agg * a, chgpu_col ** keys_out, chgpu_col ** 
             ctx->counters[6] += 1;
         }
     }
-    for (u32 w = 0; w < a->n_pub_words; ++w)
+    for (u32 w = 0; w < a->words.n_pub_words; ++w)
         if (words[w])
             chgpu_col_free(words[w]); // pooled: reuse is stream-ordered behind k_avg_divide / k_cond_results
     if (rc != CHGPU_OK)
