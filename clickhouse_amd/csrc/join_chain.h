@@ -700,125 +700,133 @@ static int join_build_dense(chgpu_join * j, bool defer_dup = false)
 
 /* See include/chgpu.h.  right_payload_cols[s] != NULL (with want_right_rows[s]): right_rowid_u64[s] receives that column's values at the matched
    rows instead of the row ids. */
-static int join_chain_impl(uint32_t n_steps, chgpu_join * const * joins, const chgpu_col * const * key_cols, const chgpu_col * const * null_maps,
-                           const int * want_right_rows, const chgpu_col * const * right_payload_cols, uint32_t n_carry, const chgpu_col * const * carry_cols,
-                           chgpu_col ** indexes_u64, chgpu_col ** right_rowid_u64, chgpu_col ** carry_out, chgpu_col ** filter_u8, uint64_t * n_kept)
+struct ChainCall
 {
-    CHGPU_REQUIRE(n_steps >= 1 && joins && key_cols && n_kept, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(n_steps <= JC_MAX_STEPS, CHGPU_ERR_NOT_IMPLEMENTED, "a join chain of %u steps (at most %u)", n_steps, JC_MAX_STEPS);
-    CHGPU_REQUIRE(n_carry <= JC_MAX_CARRY, CHGPU_ERR_NOT_IMPLEMENTED, "%u carried columns (at most %u per call)", n_carry, JC_MAX_CARRY);
-    CHGPU_REQUIRE(n_carry == 0 || (carry_cols && carry_out), CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    for (u32 s = 0; s < n_steps; ++s)
-        CHGPU_REQUIRE(joins[s] && key_cols[s], CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    chgpu_ctx * ctx = joins[0]->ctx;
-    ChgpuDeviceGuard _dev_guard(ctx);
-    *n_kept = 0;
-    if (indexes_u64) *indexes_u64 = nullptr;
-    if (filter_u8) *filter_u8 = nullptr;
-    for (u32 s = 0; s < n_steps && right_rowid_u64; ++s)
-        right_rowid_u64[s] = nullptr;
-    for (u32 c = 0; c < n_carry; ++c)
-        carry_out[c] = nullptr;
-    const u64 n = key_cols[0]->rows;
-    for (u32 s = 0; s < n_steps; ++s)
+    uint32_t n_steps;
+    chgpu_join * const * joins;
+    const chgpu_col * const * key_cols;
+    const chgpu_col * const * null_maps;
+    const int * want_right_rows;
+    const chgpu_col * const * right_payload_cols;
+    uint32_t n_carry;
+    const chgpu_col * const * carry_cols;
+    chgpu_col ** indexes_u64;
+    chgpu_col ** right_rowid_u64;
+    chgpu_col ** carry_out;
+    chgpu_col ** filter_u8;
+    uint64_t * n_kept;
+    // (set by chain_validate)
+    chgpu_ctx * ctx;
+    u64 n;
+
+    bool wants_rows(u32 s) const { return want_right_rows && want_right_rows[s]; }
+    const chgpu_col * null_map(u32 s) const { return null_maps ? null_maps[s] : nullptr; }
+    const chgpu_col * payload(u32 s) const { return right_payload_cols ? right_payload_cols[s] : nullptr; }
+};
+
+static int chain_validate(ChainCall & c)
+{
+    CHGPU_REQUIRE(c.n_steps >= 1 && c.joins && c.key_cols && c.n_kept, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_REQUIRE(c.n_steps <= JC_MAX_STEPS, CHGPU_ERR_NOT_IMPLEMENTED, "a join chain of %u steps (at most %u)", c.n_steps, JC_MAX_STEPS);
+    CHGPU_REQUIRE(c.n_carry <= JC_MAX_CARRY, CHGPU_ERR_NOT_IMPLEMENTED, "%u carried columns (at most %u per call)", c.n_carry, JC_MAX_CARRY);
+    CHGPU_REQUIRE(c.n_carry == 0 || (c.carry_cols && c.carry_out), CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    for (u32 s = 0; s < c.n_steps; ++s)
+        CHGPU_REQUIRE(c.joins[s] && c.key_cols[s], CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    c.ctx = c.joins[0]->ctx;
+    *c.n_kept = 0;
+    if (c.indexes_u64) *c.indexes_u64 = nullptr;
+    if (c.filter_u8) *c.filter_u8 = nullptr;
+    for (u32 s = 0; s < c.n_steps && c.right_rowid_u64; ++s)
+        c.right_rowid_u64[s] = nullptr;
+    for (u32 k = 0; k < c.n_carry; ++k)
+        c.carry_out[k] = nullptr;
+    const u64 n = c.n = c.key_cols[0]->rows;
+    for (u32 s = 0; s < c.n_steps; ++s)
     {
-        chgpu_join * j = joins[s];
-        CHGPU_REQUIRE(j->ctx == ctx, CHGPU_ERR_BAD_ARGUMENTS, "the joins of a chain must live on one context");
-        CHGPU_REQUIRE(key_cols[s]->type == j->key_type, CHGPU_ERR_BAD_ARGUMENTS, "left key column %u has type %d, expected %d", s, key_cols[s]->type, j->key_type);
-        CHGPU_REQUIRE(key_cols[s]->rows == n, CHGPU_ERR_SIZES_MISMATCH, "Size of key column %u doesn't match the chain's (%llu vs %llu rows)", s,
-                      (unsigned long long)key_cols[s]->rows, (unsigned long long)n);
-        if (null_maps && null_maps[s])
-            CHGPU_REQUIRE(null_maps[s]->type == CHGPU_U8 && null_maps[s]->rows == n, CHGPU_ERR_SIZES_MISMATCH, "null map size mismatch");
+        chgpu_join * j = c.joins[s];
+        CHGPU_REQUIRE(j->ctx == c.ctx, CHGPU_ERR_BAD_ARGUMENTS, "the joins of a chain must live on one context");
+        CHGPU_REQUIRE(c.key_cols[s]->type == j->key_type, CHGPU_ERR_BAD_ARGUMENTS, "left key column %u has type %d, expected %d", s, c.key_cols[s]->type, j->key_type);
+        CHGPU_REQUIRE(c.key_cols[s]->rows == n, CHGPU_ERR_SIZES_MISMATCH, "Size of key column %u doesn't match the chain's (%llu vs %llu rows)", s,
+                      (unsigned long long)c.key_cols[s]->rows, (unsigned long long)n);
+        if (c.null_map(s))
+            CHGPU_REQUIRE(c.null_map(s)->type == CHGPU_U8 && c.null_map(s)->rows == n, CHGPU_ERR_SIZES_MISMATCH, "null map size mismatch");
         // RIGHT / FULL keep per-row used flags and INNER ANY consumes a right row once (setUsedOnce): stateful, not a pure filter
         CHGPU_REQUIRE(!jf_track_used(j), CHGPU_ERR_NOT_IMPLEMENTED, "RIGHT / FULL joins in a chain");
         CHGPU_REQUIRE(!(j->kind == CHGPU_JOIN_INNER && j->strictness == CHGPU_STRICT_ANY), CHGPU_ERR_NOT_IMPLEMENTED, "INNER ANY in a chain");
-        if (want_right_rows && want_right_rows[s])
-            CHGPU_REQUIRE(right_rowid_u64, CHGPU_ERR_BAD_ARGUMENTS, "right row ids wanted but right_rowid_u64 is NULL");
-        if (right_payload_cols && right_payload_cols[s])
+        if (c.wants_rows(s))
+            CHGPU_REQUIRE(c.right_rowid_u64, CHGPU_ERR_BAD_ARGUMENTS, "right row ids wanted but right_rowid_u64 is NULL");
+        if (c.payload(s))
         {
-            CHGPU_REQUIRE(want_right_rows && want_right_rows[s], CHGPU_ERR_BAD_ARGUMENTS, "a right column for step %u, which adds no right rows", s);
+            CHGPU_REQUIRE(c.wants_rows(s), CHGPU_ERR_BAD_ARGUMENTS, "a right column for step %u, which adds no right rows", s);
             CHGPU_REQUIRE(j->blocks.size() == 1, CHGPU_ERR_NOT_IMPLEMENTED, "right columns are gathered inside the chain for one-block build sides: take the row ids");
-            CHGPU_REQUIRE(right_payload_cols[s]->rows == j->blocks[0].rows, CHGPU_ERR_SIZES_MISMATCH, "Size of the right column of step %u doesn't match the build block", s);
+            CHGPU_REQUIRE(c.payload(s)->rows == j->blocks[0].rows, CHGPU_ERR_SIZES_MISMATCH, "Size of the right column of step %u doesn't match the build block", s);
         }
     }
-    // The right sides that still have to be built.  Their key statistics (gathered while the keys were staged) come over in ONE read-back,
-    // the builds are queued, and the duplicate flags of the row maps come over in a second one: two waits for the whole chain instead of
-    // one or two per join.
-    {
-        chgpu_join * need[JC_MAX_STEPS];
-        u32 n_need = 0;
-        for (u32 s = 0; s < n_steps; ++s)
-        {
-            chgpu_join * j = joins[s];
-            bool seen = false;
-            for (u32 q = 0; q < n_need; ++q)
-                seen = seen || need[q] == j;
-            if (!seen && !j->finished && !j->ks_ready && !j->stats_known && j->key_stats)
-                need[n_need++] = j;
-        }
-        if (n_need)
-        {
-            void * stage = nullptr;
-            CHGPU_TRY(chgpu_pinned(ctx, 16 * JC_MAX_STEPS, &stage));
-            for (u32 q = 0; q < n_need; ++q)
-                CHGPU_HIP(hipMemcpyAsync((char *)stage + 16 * q, need[q]->key_stats, 16, hipMemcpyDeviceToHost, ctx->stream));
-            CHGPU_HIP(hipStreamSynchronize(ctx->stream));
-            for (u32 q = 0; q < n_need; ++q)
-            {
-                memcpy(need[q]->stats_host, (char *)stage + 16 * q, 16);
-                need[q]->stats_known = true;
-            }
-        }
-    }
+    return CHGPU_OK;
+}
+
+// One read-back for the whole chain: `bytes` (<= 16) at src(j) of every distinct join that pick(j) holds for -- one copy each, ONE wait --
+// then got(j, the bytes on the host)
+template <typename Pick, typename Src, typename Got>
+static int chain_read_back(const ChainCall & c, size_t bytes, Pick pick, Src src, Got got)
+{
+    chgpu_join * need[JC_MAX_STEPS];
+    u32 n_need = 0;
+    for (u32 s = 0; s < c.n_steps; ++s)
+        if (std::find(need, need + n_need, c.joins[s]) == need + n_need && pick(c.joins[s]))
+            need[n_need++] = c.joins[s];
+    if (!n_need)
+        return CHGPU_OK;
+    void * stage = nullptr;
+    CHGPU_TRY(chgpu_pinned(c.ctx, 16 * JC_MAX_STEPS, &stage));
+    for (u32 q = 0; q < n_need; ++q)
+        CHGPU_HIP(hipMemcpyAsync((char *)stage + 16 * q, src(need[q]), bytes, hipMemcpyDeviceToHost, c.ctx->stream));
+    CHGPU_HIP(hipStreamSynchronize(c.ctx->stream));
+    for (u32 q = 0; q < n_need; ++q)
+        got(need[q], (const char *)stage + 16 * q);
+    return CHGPU_OK;
+}
+
+// The right sides that still have to be built.  Their key statistics (gathered while the keys were staged) come over in ONE read-back,
+// the builds are queued, and the duplicate flags of the row maps come over in a second one: two waits for the whole chain instead of
+// one or two per join.
+static int chain_prepare_right_sides(const ChainCall & c)
+{
+    CHGPU_TRY(chain_read_back(
+        c, 16, [](const chgpu_join * j) { return !j->finished && !j->ks_ready && !j->stats_known && j->key_stats; }, [](const chgpu_join * j) { return (const void *)j->key_stats; },
+        [](chgpu_join * j, const char * host) {
+            memcpy(j->stats_host, host, 16);
+            j->stats_known = true;
+        }));
     bool to_table[JC_MAX_STEPS] = {false};
-    for (u32 s = 0; s < n_steps; ++s)
+    for (u32 s = 0; s < c.n_steps; ++s)
     {
-        chgpu_join * j = joins[s];
+        chgpu_join * j = c.joins[s];
         if (j->finished)
             continue;
         // a SEMI / ANTI step that adds no column only needs the key SET: the exact bitmap, without the hash table
         int krc = CHGPU_ERR_NOT_IMPLEMENTED;
-        if ((j->strictness == CHGPU_STRICT_SEMI || j->strictness == CHGPU_STRICT_ANTI) && !(want_right_rows && want_right_rows[s]))
+        if ((j->strictness == CHGPU_STRICT_SEMI || j->strictness == CHGPU_STRICT_ANTI) && !c.wants_rows(s))
             krc = join_build_keyset(j);
-        else if (want_right_rows && want_right_rows[s] && j->strictness != CHGPU_STRICT_ANTI && !chgpu_opt(ctx, "tune_join_no_dense_map", 0))
+        else if (c.wants_rows(s) && j->strictness != CHGPU_STRICT_ANTI && !chgpu_opt(c.ctx, "tune_join_no_dense_map", 0))
             krc = join_build_dense(j, /*defer_dup*/ true); // right rows over dense unique keys: the key set + a direct row map
         if (krc != CHGPU_OK && krc != CHGPU_ERR_NOT_IMPLEMENTED)
             return krc;
         to_table[s] = krc != CHGPU_OK;
     }
+    CHGPU_TRY(chain_read_back(
+        c, 4, [](const chgpu_join * j) { return j->dm_pending; }, [](const chgpu_join * j) { return (const void *)(j->key_stats + 2); },
+        [](chgpu_join * j, const char * host) {
+            u32 dup = 0;
+            memcpy(&dup, host, 4);
+            (void)join_finish_dense(j, dup); // (a duplicate key: dm_ready stays false, the table is built below)
+        }));
+    for (u32 s = 0; s < c.n_steps; ++s)
     {
-        chgpu_join * pend[JC_MAX_STEPS];
-        u32 n_pend = 0;
-        for (u32 s = 0; s < n_steps; ++s)
-        {
-            bool seen = false;
-            for (u32 q = 0; q < n_pend; ++q)
-                seen = seen || pend[q] == joins[s];
-            if (!seen && joins[s]->dm_pending)
-                pend[n_pend++] = joins[s];
-        }
-        if (n_pend)
-        {
-            void * stage = nullptr;
-            CHGPU_TRY(chgpu_pinned(ctx, 16 * JC_MAX_STEPS, &stage));
-            for (u32 q = 0; q < n_pend; ++q)
-                CHGPU_HIP(hipMemcpyAsync((char *)stage + 16 * q, pend[q]->key_stats + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
-            CHGPU_HIP(hipStreamSynchronize(ctx->stream));
-            for (u32 q = 0; q < n_pend; ++q)
-            {
-                u32 dup = 0;
-                memcpy(&dup, (char *)stage + 16 * q, 4);
-                (void)join_finish_dense(pend[q], dup); // (a duplicate key: dm_ready stays false, the table is built below)
-            }
-        }
-    }
-    for (u32 s = 0; s < n_steps; ++s)
-    {
-        chgpu_join * j = joins[s];
+        chgpu_join * j = c.joins[s];
         if (!j->finished)
         {
-            const bool wants_rows = want_right_rows && want_right_rows[s];
-            const bool have = wants_rows ? j->dm_ready : (j->ks_ready && (j->strictness == CHGPU_STRICT_SEMI || j->strictness == CHGPU_STRICT_ANTI));
+            const bool have = c.wants_rows(s) ? j->dm_ready : (j->ks_ready && (j->strictness == CHGPU_STRICT_SEMI || j->strictness == CHGPU_STRICT_ANTI));
             if (to_table[s] || !have)
                 CHGPU_TRY(join_build_table(j));
         }
@@ -826,200 +834,225 @@ static int join_chain_impl(uint32_t n_steps, chgpu_join * const * joins, const c
         CHGPU_REQUIRE(j->strictness != CHGPU_STRICT_ALL || j->unique_keys || (!j->finished && j->dm_ready), CHGPU_ERR_NOT_IMPLEMENTED,
                       "ALL join over duplicate build keys in a chain");
     }
-    for (u32 c = 0; c < n_carry; ++c)
-        CHGPU_REQUIRE(carry_cols[c] && carry_cols[c]->rows == n, CHGPU_ERR_SIZES_MISMATCH, "Size of carried column %u doesn't match the chain's", c);
+    return CHGPU_OK;
+}
 
-    // which steps filter at all (LEFT ANY / LEFT ALL keep every left row), and which of them fit the LDS sweep
-    ChainLdsArgs la{};
-    ChainTailArgs ta{};
+// step s of the call as the tail and gather kernels see it
+static ChainTailStep chain_tail_step(const ChainCall & c, u32 s, const JoinKeySet & ks)
+{
+    ChainTailStep t{};
+    t.keys = c.key_cols[s]->data;
+    t.null_map = c.null_map(s) ? (const u8 *)c.null_map(s)->data : nullptr;
+    t.pf = ks.pf;
+    t.kv = ks.kv;
+    t.pf_mask = ks.pf_mask;
+    t.max_key = ks.max_key;
+    t.capacity = ks.capacity;
+    t.key_type = c.joins[s]->key_type;
+    t.anti = c.joins[s]->strictness == CHGPU_STRICT_ANTI ? 1 : 0;
+    t.has_zero = ks.has_zero ? 1 : 0;
+    t.dense = ks.dense ? 1 : 0;
+    t.dense_row = ks.dense_row;
+    return t;
+}
+
+// Which steps filter at all (LEFT ANY / LEFT ALL keep every left row), which of them fit the LDS sweep, and the launch geometry
+struct ChainPlan
+{
     std::vector<u32> lds_steps, tail_steps;
-    for (u32 s = 0; s < n_steps; ++s)
+    ChainLdsArgs la;
+    ChainTailArgs ta; // the filtering steps, LDS steps first
+    u64 n_units, n_lds_units;
+    u32 lds_grid, tail_grid, idx_grid;
+    // per step, in the caller's order: skipped | in the LDS sweep (slices) | in the tail (exact bitmap, hashed prefilter, none), and
+    // what answers: the key set, the key set with its row map, or the finished table
+    char label[JC_MAX_STEPS][64];
+};
+static void chain_plan(const ChainCall & c, ChainPlan & p)
+{
+    const chgpu_ctx * ctx = c.ctx;
+    const u64 n = c.n;
+    p.la = ChainLdsArgs{};
+    p.ta = ChainTailArgs{};
+    auto rep = [&](u32 s) { return c.joins[s]->finished ? "table" : (c.joins[s]->dm_ready && c.wants_rows(s)) ? "dm" : "ks"; };
+    for (u32 s = 0; s < c.n_steps; ++s)
     {
-        chgpu_join * j = joins[s];
+        const chgpu_join * j = c.joins[s];
         const bool filters = jf_left_kind(j) == CHGPU_JOIN_INNER || j->strictness == CHGPU_STRICT_SEMI || j->strictness == CHGPU_STRICT_ANTI;
+        const chgpu_col * nm = c.null_map(s);
         if (!filters)
-            continue;
-        const chgpu_col * nm = null_maps ? null_maps[s] : nullptr;
-        const u64 dense_bits = (j->max_key + 32) / 32 * 32;
-        const bool dense = j->finished ? (j->t.pf && j->max_key <= j->t.pf_mask) : j->ks_ready;
-        const bool lds = dense && chgpu_type_size(j->key_type) == 4 && dense_bits <= (u64)JC_MAX_SLICES * JC_SLICE_BITS && n >= (1u << 20)
-            && (uintptr_t)key_cols[s]->data % 16 == 0 && (!nm || (uintptr_t)nm->data % 4 == 0);
-        (lds ? lds_steps : tail_steps).push_back(s);
+            snprintf(p.label[s], sizeof(p.label[s]), "skip %s", rep(s));
+        else if (join_lds_filter_fits(join_key_set(j), j->key_type, n, c.key_cols[s]->data, nm ? nm->data : nullptr, JC_SLICE_BITS, JC_MAX_SLICES))
+            p.lds_steps.push_back(s);
+        else
+            p.tail_steps.push_back(s);
     }
-    auto fill_tail = [&](ChainTailStep & t, u32 s) {
-        chgpu_join * j = joins[s];
-        t.keys = key_cols[s]->data;
-        t.null_map = null_maps && null_maps[s] ? (const u8 *)null_maps[s]->data : nullptr;
-        t.pf = j->finished ? j->t.pf : j->ks_pf;
-        t.kv = j->finished ? j->t.kv : nullptr;
-        t.pf_mask = j->finished ? j->t.pf_mask : j->ks_bits - 1;
-        t.max_key = j->max_key;
-        t.capacity = j->finished ? j->t.capacity : 0;
-        t.key_type = j->key_type;
-        t.anti = j->strictness == CHGPU_STRICT_ANTI ? 1 : 0;
-        t.has_zero = j->has_zero ? 1 : 0;
-        t.dense = (j->finished ? (j->t.pf && j->max_key <= j->t.pf_mask) : j->ks_ready) ? 1 : 0;
-        t.dense_row = (!j->finished && j->dm_ready) ? j->dm_rows : nullptr;
-    };
-    for (u32 s : lds_steps)
+    for (u32 s : p.lds_steps)
     {
-        chgpu_join * j = joins[s];
-        ChainLdsStep & l = la.s[la.n_steps++];
-        l.keys = (const u32 *)key_cols[s]->data;
-        l.null_map = null_maps && null_maps[s] ? (const u8 *)null_maps[s]->data : nullptr;
-        l.pf = j->finished ? j->t.pf : j->ks_pf;
-        l.dense_bits = (u32)((j->max_key + 32) / 32 * 32);
+        const JoinKeySet ks = join_key_set(c.joins[s]);
+        const ChainTailStep & t = p.ta.s[p.ta.n_steps++] = chain_tail_step(c, s, ks);
+        ChainLdsStep & l = p.la.s[p.la.n_steps++];
+        l.keys = (const u32 *)t.keys;
+        l.null_map = t.null_map;
+        l.pf = t.pf;
+        l.dense_bits = (u32)ks.dense_bits;
         l.n_slices = (l.dense_bits + JC_SLICE_BITS - 1) / JC_SLICE_BITS;
-        l.anti = j->strictness == CHGPU_STRICT_ANTI ? 1 : 0;
-        l.has_zero = j->has_zero ? 1 : 0;
-        fill_tail(ta.s[ta.n_steps++], s);
+        l.anti = t.anti;
+        l.has_zero = t.has_zero;
+        snprintf(p.label[s], sizeof(p.label[s]), "lds:%u %s", l.n_slices, rep(s));
     }
-    ta.first_tail = ta.n_steps;
-    for (u32 s : tail_steps)
-        fill_tail(ta.s[ta.n_steps++], s);
-
-    chgpu_col * idx = nullptr, * fcol = nullptr;
-    chgpu_col * rid[JC_MAX_STEPS] = {nullptr};
-    chgpu_col * car[JC_MAX_CARRY] = {nullptr};
-    auto fail = [&](int code) {
-        chgpu_col_free(idx);
-        chgpu_col_free(fcol);
-        for (u32 s = 0; s < JC_MAX_STEPS; ++s)
-            chgpu_col_free(rid[s]);
-        for (u32 c = 0; c < JC_MAX_CARRY; ++c)
-            chgpu_col_free(car[c]);
-        return code;
-    };
-    int rc = CHGPU_OK;
-    u64 kept = 0;
-    const u64 n_units = (n + JC_UNIT_ROWS - 1) / JC_UNIT_ROWS;
-    const u64 n_lds_units = la.n_steps ? n / JC_PART_ROWS * JC_UNITS_PER_PART : 0; // k_chain_lds sweeps whole parts; the rest starts alive in k_chain_tail
+    p.ta.first_tail = p.ta.n_steps;
+    for (u32 s : p.tail_steps)
+    {
+        const JoinKeySet ks = join_key_set(c.joins[s]);
+        p.ta.s[p.ta.n_steps++] = chain_tail_step(c, s, ks);
+        snprintf(p.label[s], sizeof(p.label[s]), "tail %s %s", ks.dense ? "dense" : (c.joins[s]->finished && ks.pf) ? "hash" : "nopf", rep(s));
+    }
+    p.n_units = (n + JC_UNIT_ROWS - 1) / JC_UNIT_ROWS;
+    p.n_lds_units = p.la.n_steps ? n / JC_PART_ROWS * JC_UNITS_PER_PART : 0; // k_chain_lds sweeps whole parts; the rest starts alive in k_chain_tail
     // test hook: at most this many workgroups per kernel, so that the grid-stride walks take many turns over a few million rows
     const u64 grid_cap = (u64)chgpu_opt(ctx, "test_chain_grid", 0);
     auto grid_of = [&](u64 want, u64 cap) { return (u32)std::min(want, grid_cap ? std::min(cap, grid_cap) : cap); };
-    const u32 lds_grid = n_lds_units ? grid_of(n_lds_units / JC_UNITS_PER_PART, (u64)ctx->num_cus) : 0;
-    const u32 tail_grid = grid_of((n_units + JCT_WAVES - 1) / JCT_WAVES, (u64)ctx->num_cus * 4);
-    const u32 idx_grid = grid_of((n_units + JCT_WAVES - 1) / JCT_WAVES, (u64)ctx->num_cus * 8);
-    if (chgpu_opt(ctx, "debug", 0))
+    p.lds_grid = p.n_lds_units ? grid_of(p.n_lds_units / JC_UNITS_PER_PART, (u64)ctx->num_cus) : 0;
+    p.tail_grid = grid_of((p.n_units + JCT_WAVES - 1) / JCT_WAVES, (u64)ctx->num_cus * 4);
+    p.idx_grid = grid_of((p.n_units + JCT_WAVES - 1) / JCT_WAVES, (u64)ctx->num_cus * 8);
+}
+
+struct ChainScratch
+{
+    u64 * total;        // the number of survivors
+    u64 * alive_words;  // [n_lds_units * 64] k_chain_lds -> k_chain_tail
+    u64 * mask_words;   // [n_units * 64] the chain's result, one bit per row
+    u32 * unit_counts;  // [n_units + 1] survivors per unit
+    u64 * unit_offsets; // [n_units + 1] their exclusive scan
+    void * tmp;         // the scan's temporaries
+    size_t tmp_bytes;
+};
+static ChainScratch chain_carve(JoinCarve & c, u64 n_lds_units, u64 n_units)
+{
+    ChainScratch s{};
+    s.total = c.take<u64>(1);
+    s.alive_words = c.take<u64>(n_lds_units * 64);
+    s.mask_words = c.take<u64>(n_units * 64);
+    s.unit_counts = c.take<u32>(n_units + 1);
+    s.unit_offsets = c.take<u64>(n_units + 1);
+    s.tmp_bytes = chgpu_scan_tmp_bytes(n_units);
+    s.tmp = c.take<char>(s.tmp_bytes);
+    return s;
+}
+
+// k_chain_lds + k_chain_tail + the scan of the units' counts -> s->mask_words, s->unit_offsets and the number of survivors (n > 0)
+static int chain_run_filters(const ChainCall & c, const ChainPlan & p, ChainScratch * s, u64 * kept)
+{
+    chgpu_ctx * ctx = c.ctx;
+    CHGPU_TRY(join_carve_scratch(ctx, [&](JoinCarve & cv) { *s = chain_carve(cv, p.n_lds_units, p.n_units); }));
+    if (p.n_lds_units)
     {
-        // per step, in the caller's order: skipped | in the LDS sweep (slices) | in the tail (exact bitmap, hashed prefilter, none), and
-        // what answers: the key set, the key set with its row map, or the finished table
-        std::string plan;
-        for (u32 s = 0; s < n_steps; ++s)
-        {
-            const chgpu_join * j = joins[s];
-            const char * rep = j->finished ? "table" : (j->dm_ready && want_right_rows && want_right_rows[s]) ? "dm" : "ks";
-            char buf[64];
-            u32 at = 0;
-            while (at < la.n_steps && lds_steps[at] != s)
-                ++at;
-            if (at < la.n_steps)
-                snprintf(buf, sizeof(buf), "lds:%u %s", la.s[at].n_slices, rep);
-            else if (std::find(tail_steps.begin(), tail_steps.end(), s) != tail_steps.end())
-            {
-                const bool dense = j->finished ? (j->t.pf && j->max_key <= j->t.pf_mask) : j->ks_ready;
-                snprintf(buf, sizeof(buf), "tail %s %s", dense ? "dense" : (j->finished && j->t.pf) ? "hash" : "nopf", rep);
-            }
-            else
-                snprintf(buf, sizeof(buf), "skip %s", rep);
-            plan += (s ? " | " : "");
-            plan += buf;
-        }
-        fprintf(stderr, "chgpu: join chain rows=%llu parts=%llu lds_grid=%u tail_grid=%u idx_grid=%u steps=[%s]\n", (unsigned long long)n,
-                (unsigned long long)(n_lds_units / JC_UNITS_PER_PART), lds_grid, tail_grid, idx_grid, plan.c_str());
+        const size_t lds_b = JC_SLICE_BYTES + 16;
+        CHGPU_HIP(hipFuncSetAttribute((const void *)k_chain_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
+        hipLaunchKernelGGL(k_chain_lds, dim3(p.lds_grid), dim3(JC_THREADS), lds_b, ctx->stream, p.la, c.n, s->alive_words);
+        ctx->counters[6] += 1;
     }
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t alive_b = al(n_lds_units * 64 * 8), mask_b = al(n_units * 64 * 8), cnt_b = al(n_units * 4 + 4), off_b = al(n_units * 8 + 8), tmp_b = chgpu_scan_tmp_bytes(n_units);
-    u64 * mask_words = nullptr, * unit_offsets = nullptr;
-    if (n)
-    {
-        void * scratch = nullptr;
-        CHGPU_TRY(chgpu_scratch(ctx, 256 + alive_b + mask_b + cnt_b + off_b + al(tmp_b), &scratch));
-        u64 * total_dev = (u64 *)scratch;
-        u64 * alive_words = (u64 *)((char *)scratch + 256);
-        mask_words = (u64 *)((char *)scratch + 256 + alive_b);
-        u32 * unit_counts = (u32 *)((char *)scratch + 256 + alive_b + mask_b);
-        unit_offsets = (u64 *)((char *)scratch + 256 + alive_b + mask_b + cnt_b);
-        void * tmp = (char *)scratch + 256 + alive_b + mask_b + cnt_b + off_b;
-        if (n_lds_units)
-        {
-            const size_t lds_b = JC_SLICE_BYTES + 16;
-            CHGPU_HIP(hipFuncSetAttribute((const void *)k_chain_lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
-            hipLaunchKernelGGL(k_chain_lds, dim3(lds_grid), dim3(JC_THREADS), lds_b, ctx->stream, la, n, alive_words);
-            ctx->counters[6] += 1;
-        }
-        {
-            hipLaunchKernelGGL(k_chain_tail, dim3(tail_grid), dim3(JCT_THREADS), 0, ctx->stream, ta, n_lds_units ? (const u64 *)alive_words : (const u64 *)nullptr,
-                               n_lds_units, n, mask_words, unit_counts);
-            ctx->counters[6] += 1;
-        }
-        CHGPU_HIP(hipGetLastError());
-        CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, unit_counts, unit_offsets, n_units, total_dev, tmp, tmp_b));
-        CHGPU_TRY(chgpu_read_back(ctx, total_dev, &kept, sizeof(kept)));
-    }
-    // outputs, sized by the survivors
-    if (indexes_u64 && (rc = chgpu_col_new(ctx, CHGPU_U64, kept, &idx)) != CHGPU_OK)
-        return fail(rc);
-    if (filter_u8 && (rc = chgpu_col_new(ctx, CHGPU_U8, n, &fcol)) != CHGPU_OK)
-        return fail(rc);
+    hipLaunchKernelGGL(k_chain_tail, dim3(p.tail_grid), dim3(JCT_THREADS), 0, ctx->stream, p.ta, p.n_lds_units ? (const u64 *)s->alive_words : (const u64 *)nullptr,
+                       p.n_lds_units, c.n, s->mask_words, s->unit_counts);
+    ctx->counters[6] += 1;
+    CHGPU_HIP(hipGetLastError());
+    CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, s->unit_counts, s->unit_offsets, p.n_units, s->total, s->tmp, s->tmp_bytes));
+    return chgpu_read_back(ctx, s->total, kept, sizeof(*kept));
+}
+
+// The outputs, sized by the survivors: row numbers and filter bytes from the bitmask, then the matched right rows and the carried
+// left columns gathered at the survivors.  The columns go to the caller only when everything was launched.
+static int chain_emit(const ChainCall & c, const ChainPlan & p, const ChainScratch & sc, u64 kept)
+{
+    chgpu_ctx * ctx = c.ctx;
+    const u64 n = c.n;
+    JoinOutCol idx, fcol, rid[JC_MAX_STEPS], car[JC_MAX_CARRY];
+    if (c.indexes_u64)
+        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, kept, &idx.col));
+    if (c.filter_u8)
+        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, n, &fcol.col));
     ChainEmitArgs ea{};
-    for (u32 s = 0; s < n_steps; ++s)
-        if (want_right_rows && want_right_rows[s])
+    for (u32 s = 0; s < c.n_steps; ++s)
+        if (c.wants_rows(s))
         {
-            const chgpu_col * pay = right_payload_cols ? right_payload_cols[s] : nullptr;
-            if ((rc = chgpu_col_new(ctx, pay ? pay->type : CHGPU_U64, kept, &rid[s])) != CHGPU_OK)
-                return fail(rc);
-            fill_tail(ea.s[ea.n_rowid], s);
-            ea.rowid_out[ea.n_rowid] = pay ? nullptr : (u64 *)rid[s]->data;
+            const chgpu_col * pay = c.payload(s);
+            CHGPU_TRY(chgpu_col_new(ctx, pay ? pay->type : CHGPU_U64, kept, &rid[s].col));
+            ea.s[ea.n_rowid] = chain_tail_step(c, s, join_key_set(c.joins[s]));
+            ea.rowid_out[ea.n_rowid] = pay ? nullptr : (u64 *)rid[s].col->data;
             ea.payload_in[ea.n_rowid] = pay ? pay->data : nullptr;
-            ea.payload_out[ea.n_rowid] = pay ? rid[s]->data : nullptr;
+            ea.payload_out[ea.n_rowid] = pay ? rid[s].col->data : nullptr;
             ea.payload_size[ea.n_rowid] = pay ? (u32)chgpu_type_size(pay->type) : 0;
             ++ea.n_rowid;
         }
-    for (u32 c = 0; c < n_carry; ++c)
+    for (u32 k = 0; k < c.n_carry; ++k)
     {
-        if ((rc = chgpu_col_new(ctx, carry_cols[c]->type, kept, &car[c])) != CHGPU_OK)
-            return fail(rc);
-        ea.carry_in[c] = carry_cols[c]->data;
-        ea.carry_out[c] = car[c]->data;
-        ea.carry_size[c] = (u32)chgpu_type_size(carry_cols[c]->type);
+        CHGPU_TRY(chgpu_col_new(ctx, c.carry_cols[k]->type, kept, &car[k].col));
+        ea.carry_in[k] = c.carry_cols[k]->data;
+        ea.carry_out[k] = car[k].col->data;
+        ea.carry_size[k] = (u32)chgpu_type_size(c.carry_cols[k]->type);
     }
-    ea.n_carry = n_carry;
+    ea.n_carry = c.n_carry;
     const bool gather = kept && (ea.n_rowid || ea.n_carry);
-    if (!idx && gather && (rc = chgpu_col_new(ctx, CHGPU_U64, kept, &idx)) != CHGPU_OK) // the gather runs over the index list
-        return fail(rc);
-    if (n && ((kept && idx) || fcol))
+    if (!idx.col && gather) // the gather runs over the index list
+        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, kept, &idx.col));
+    if (n && ((kept && idx.col) || fcol.col))
     {
-        hipLaunchKernelGGL(k_chain_indexes, dim3(idx_grid), dim3(JCT_THREADS), 0, ctx->stream, (const u64 *)mask_words, (const u64 *)unit_offsets, n,
-                           (kept && idx) ? (u64 *)idx->data : (u64 *)nullptr, fcol ? (u8 *)fcol->data : (u8 *)nullptr);
+        hipLaunchKernelGGL(k_chain_indexes, dim3(p.idx_grid), dim3(JCT_THREADS), 0, ctx->stream, (const u64 *)sc.mask_words, (const u64 *)sc.unit_offsets, n,
+                           (kept && idx.col) ? (u64 *)idx.col->data : (u64 *)nullptr, fcol.col ? (u8 *)fcol.col->data : (u8 *)nullptr);
         ctx->counters[6] += 1;
         if (gather)
         {
-            hipLaunchKernelGGL(k_chain_gather, dim3(chgpu_grid_for(ctx, kept, JT, 16)), dim3(JT), 0, ctx->stream, ea, (const u64 *)idx->data, kept);
+            hipLaunchKernelGGL(k_chain_gather, dim3(chgpu_grid_for(ctx, kept, JT, 16)), dim3(JT), 0, ctx->stream, ea, (const u64 *)idx.col->data, kept);
             ctx->counters[6] += 1;
         }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess)
-            return fail(chgpu_set_error(CHGPU_ERR_DEVICE, "join chain launch: %s", hipGetErrorString(e)));
+            return chgpu_set_error(CHGPU_ERR_DEVICE, "join chain launch: %s", hipGetErrorString(e));
     }
-    if (!indexes_u64 && idx)
-    {
-        chgpu_col_free(idx); // (stream-ordered pool: the kernels above still own the buffer until they finish)
-        idx = nullptr;
-    }
-    for (u32 s = 0; s < n_steps; ++s)
-        joins[s]->left_seq += n;
-    if (indexes_u64) *indexes_u64 = idx;
-    if (filter_u8) *filter_u8 = fcol;
-    for (u32 s = 0; s < n_steps; ++s)
-        if (rid[s])
-            right_rowid_u64[s] = rid[s];
-    for (u32 c = 0; c < n_carry; ++c)
-        carry_out[c] = car[c];
-    *n_kept = kept;
-    ctx->counters[3] += n * n_steps;
+    for (u32 s = 0; s < c.n_steps; ++s)
+        c.joins[s]->left_seq += n;
+    // (an index list made for the gather alone goes with its holder: the stream-ordered pool leaves the buffer to the kernels above until
+    //  they finish)
+    if (c.indexes_u64) *c.indexes_u64 = idx.release();
+    if (c.filter_u8) *c.filter_u8 = fcol.release();
+    for (u32 s = 0; s < c.n_steps; ++s)
+        if (rid[s].col)
+            c.right_rowid_u64[s] = rid[s].release();
+    for (u32 k = 0; k < c.n_carry; ++k)
+        c.carry_out[k] = car[k].release();
+    *c.n_kept = kept;
+    ctx->counters[3] += n * c.n_steps;
     ctx->counters[4] += kept;
     return CHGPU_OK;
+}
+
+static int join_chain_impl(uint32_t n_steps, chgpu_join * const * joins, const chgpu_col * const * key_cols, const chgpu_col * const * null_maps,
+                           const int * want_right_rows, const chgpu_col * const * right_payload_cols, uint32_t n_carry, const chgpu_col * const * carry_cols,
+                           chgpu_col ** indexes_u64, chgpu_col ** right_rowid_u64, chgpu_col ** carry_out, chgpu_col ** filter_u8, uint64_t * n_kept)
+{
+    ChainCall c{n_steps, joins, key_cols, null_maps, want_right_rows, right_payload_cols, n_carry, carry_cols, indexes_u64, right_rowid_u64, carry_out, filter_u8, n_kept};
+    CHGPU_TRY(chain_validate(c));
+    chgpu_ctx * ctx = c.ctx;
+    ChgpuDeviceGuard _dev_guard(ctx);
+    CHGPU_TRY(chain_prepare_right_sides(c));
+    for (u32 k = 0; k < c.n_carry; ++k)
+        CHGPU_REQUIRE(c.carry_cols[k] && c.carry_cols[k]->rows == c.n, CHGPU_ERR_SIZES_MISMATCH, "Size of carried column %u doesn't match the chain's", k);
+    ChainPlan p;
+    chain_plan(c, p);
+    if (chgpu_opt(ctx, "debug", 0))
+    {
+        std::string steps;
+        for (u32 s = 0; s < c.n_steps; ++s)
+            steps += std::string(s ? " | " : "") + p.label[s];
+        fprintf(stderr, "chgpu: join chain rows=%llu parts=%llu lds_grid=%u tail_grid=%u idx_grid=%u steps=[%s]\n", (unsigned long long)c.n,
+                (unsigned long long)(p.n_lds_units / JC_UNITS_PER_PART), p.lds_grid, p.tail_grid, p.idx_grid, steps.c_str());
+    }
+    ChainScratch sc{};
+    u64 kept = 0;
+    if (c.n)
+        CHGPU_TRY(chain_run_filters(c, p, &sc, &kept));
+    return chain_emit(c, p, sc, kept);
 }
 
 extern "C" int chgpu_join_probe_chain(uint32_t n_steps, chgpu_join * const * joins, const chgpu_col * const * key_cols, const chgpu_col * const * null_maps,

@@ -191,6 +191,58 @@ static inline bool jf_need_filter(const chgpu_join * j)
 }
 static inline bool jf_add_missing(const chgpu_join * j) { return jf_left_kind(j) == CHGPU_JOIN_LEFT && j->strictness != CHGPU_STRICT_SEMI; } // :35
 
+// What answers "is this key on the build side, and at which row": the finished table with its prefilter, or -- before any table is
+// built -- the key set (join_build_keyset) and its row map (join_build_dense).
+struct JoinKeySet
+{
+    const u32 * pf;        // prefilter words or NULL
+    u64 pf_mask;
+    bool dense;            // pf is an exact bitmap over [0, max_key]
+    u64 dense_bits;        // max_key + 1 rounded up to whole words
+    u64 max_key;
+    bool has_zero;
+    const u64 * kv;        // {key, value} cells of the hash table, or NULL
+    u64 capacity;
+    const u32 * dense_row; // or NULL: dense_row[key] = the build row of the key
+};
+static JoinKeySet join_key_set(const chgpu_join * j)
+{
+    JoinKeySet k{};
+    k.pf = j->finished ? j->t.pf : j->ks_pf;
+    k.pf_mask = j->finished ? j->t.pf_mask : j->ks_bits - 1;
+    k.dense = j->finished ? (j->t.pf && j->max_key <= j->t.pf_mask) : j->ks_ready;
+    k.dense_bits = (j->max_key + 32) / 32 * 32;
+    k.max_key = j->max_key;
+    k.has_zero = j->has_zero;
+    k.kv = j->finished ? j->t.kv : nullptr;
+    k.capacity = j->finished ? j->t.capacity : 0;
+    k.dense_row = (!j->finished && j->dm_ready) ? j->dm_rows : nullptr;
+    return k;
+}
+// The LDS bitmap filters (k_join_probe_filter_lds_multi, k_chain_lds) take dense 4-byte keys whose bitmap fits `max_slices` slices of
+// `slice_bits` (the kernel's geometry), read with 16-byte key loads and 4-byte null-map loads, over enough rows to pay for the staging
+static bool join_lds_filter_fits(const JoinKeySet & k, int key_type, u64 n, const void * keys, const void * null_map, u64 slice_bits, u32 max_slices)
+{
+    return k.dense && chgpu_type_size(key_type) == 4 && k.dense_bits <= max_slices * slice_bits && n >= (1u << 20) && (uintptr_t)keys % 16 == 0
+        && (!null_map || (uintptr_t)null_map % 4 == 0);
+}
+
+// An output column under construction: freed on scope exit unless it was released to the caller
+struct JoinOutCol
+{
+    chgpu_col * col = nullptr;
+    JoinOutCol() = default;
+    JoinOutCol(const JoinOutCol &) = delete;
+    JoinOutCol & operator=(const JoinOutCol &) = delete;
+    ~JoinOutCol() { chgpu_col_free(col); }
+    chgpu_col * release()
+    {
+        chgpu_col * c = col;
+        col = nullptr;
+        return c;
+    }
+};
+
 // ---------------------------------------------------------------------------------------------
 // device
 // ---------------------------------------------------------------------------------------------
@@ -1239,6 +1291,13 @@ struct JoinCarve
         at += (count * sizeof(T) + 255) / 256 * 256;
         return r;
     }
+    // the last piece of a layout: nothing follows it, so its end is not padded
+    template <typename T> T * last(u64 count)
+    {
+        T * r = (T *)at;
+        at += count * sizeof(T);
+        return r;
+    }
 };
 
 // The buffers of one partition (words1 / words2: nullptr without a word; keys2 / words2 / tidx: nullptr for the first level alone)
@@ -1252,19 +1311,26 @@ struct JoinPart
     u64 * keys2, * words2; // the second level: every tile sorted by bucket
     unsigned short * tidx; // [tiles][PB + 1] where each bucket's run starts inside its tile
 };
+// What `carve(JoinCarve &)` takes, off the context's scratch: carved over base 0 for the size, then over the scratch itself
+template <typename Fn>
+static int join_carve_scratch(chgpu_ctx * ctx, Fn && carve)
+{
+    JoinCarve size{0};
+    carve(size);
+    void * scratch = nullptr;
+    CHGPU_TRY(chgpu_scratch(ctx, size.at, &scratch));
+    JoinCarve c{(uintptr_t)scratch};
+    carve(c);
+    return CHGPU_OK;
+}
 // The scratch of one plan: an 8-word header, then what `carve(JoinCarve &)` takes.  -> *header, zeroed on the stream.
 template <typename Fn>
 static int join_scratch(chgpu_ctx * ctx, u64 ** header, Fn && carve)
 {
-    auto run = [&](uintptr_t base) {
-        JoinCarve c{base};
+    CHGPU_TRY(join_carve_scratch(ctx, [&](JoinCarve & c) {
         *header = c.take<u64>(8);
         carve(c);
-        return c.at - base;
-    };
-    void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, run(0), &scratch));
-    run((uintptr_t)scratch);
+    }));
     CHGPU_HIP(hipMemsetAsync(*header, 0, 64, ctx->stream));
     return CHGPU_OK;
 }
@@ -1611,14 +1677,18 @@ static void join_debug_declined(const chgpu_ctx * ctx, const char * what, u32 de
             (declined & JOIN_DECLINED_DUP) ? " dup" : "", (declined & JOIN_DECLINED_OVERFLOW_FULL) ? " overflow_list_full" : "");
 }
 
-// -> CHGPU_OK: the table is built (unique keys); NOT_IMPLEMENTED: shape does not fit or a duplicate key exists (the caller runs the
-// generic build over a freshly zeroed table).  *declined: the flags that made a run decline (0: it did not run); *overflow: the rows
+// -> CHGPU_OK: the table is built (unique keys) and its used_by words are cleared; NOT_IMPLEMENTED: shape does not fit or a duplicate
+// key exists (the caller runs the generic build, which zeroes the table itself).  *declined: the flags that made a run decline (0: it did not run); *overflow: the rows
 // that went through the overflow list.
 static int join_build_slices(chgpu_join * j, JoinTable & t, u32 * declined, u64 * overflow)
 {
     chgpu_ctx * ctx = j->ctx;
     const bool off = chgpu_opt(ctx, "tune_join_no_slice_build", 0) != 0;
     const u64 n = j->total_rows, cap = t.capacity;
+    // the slices are written out whole: only the control block and the zero key's cell need clearing first (ahead of the shape test, as
+    // ever: a declined build costs these two small memsets)
+    CHGPU_HIP(hipMemsetAsync(t.ctrl, 0, (size_t)((char *)t.kv - (char *)t.ctrl), ctx->stream));
+    CHGPU_HIP(hipMemsetAsync(t.kv + 2 * cap, 0, 16, ctx->stream));
     const JoinSliceGeom geom = join_slice_geom(cap);
     if (off || j->blocks.size() != 1 || j->blocks[0].valid || n < (1u << 20) || n + JBS_TILE + RP_SCATTER_SLACK >= (1ull << 32) || !geom.fits
         || ((uintptr_t)j->blocks[0].keys % 16) != 0)
@@ -1654,6 +1724,9 @@ static int join_build_slices(chgpu_join * j, JoinTable & t, u32 * declined, u64 
     *overflow = back[1] >> 32;
     if (stray_v || dup_v || too_long)
         return CHGPU_ERR_NOT_IMPLEMENTED;
+    // (unique keys: first_row / cnt are only read for cells that hold several rows -- there are none)
+    if (t.used_by)
+        CHGPU_HIP(hipMemsetAsync(t.used_by, 0xFF, (cap + 1) * 8, ctx->stream));
     return CHGPU_OK;
 }
 
@@ -1676,170 +1749,225 @@ extern "C" int chgpu_join_finish_build(chgpu_join * j)
     return eager ? join_build_table(j) : CHGPU_OK;
 }
 
-static int join_build_table(chgpu_join * j)
+// ---------------------------------------------------------------------------------------------
+// The table build: a plan (what the table holds), a layout (where), one of two builders (the inserts and the memsets they need) and one
+// finish (everything after the inserts).
+// ---------------------------------------------------------------------------------------------
+enum JoinPfKind
 {
-    if (j->finished)
-        return CHGPU_OK;
-    j->build_closed = true;
+    JOIN_PF_NONE,
+    JOIN_PF_HASH,  // 16 bits per build row, one multiplicative hash (exact all the same when the largest key is below the bit count)
+    JOIN_PF_DENSE, // a larger build side of narrow keys: one bit per key value up to the largest key
+};
+struct JoinBuildPlan
+{
+    bool maps_all;  // CSR arrays: every row of a key is kept
+    bool flagged;   // a cell remembers the left row that consumed it
+    bool take_last; // ANY keeps the last row of a key, not the first
+    u64 cap, cells; // cells = cap + 1: the zero key's cell sits behind the table
+    JoinPfKind pf;
+    u64 pf_bits;
+};
+
+// The prefilter's kind and size.  The one device pass of the plan: the dense kind needs the largest staged key.
+static int join_choose_prefilter(chgpu_join * j, JoinBuildPlan * p)
+{
     chgpu_ctx * ctx = j->ctx;
-    // joinDispatch.h:30-68: MapsAll for every ALL join and for every RIGHT join (RIGHT ANY / SEMI / ANTI keep all rows of a key); a cell
-    // remembers the left row that consumed it for INNER ANY and for RIGHT ANY / SEMI / ANTI (setUsedOnce / the per-key flag)
-    const bool maps_all = j->strictness == CHGPU_STRICT_ALL || j->kind == CHGPU_JOIN_RIGHT;
-    const bool flagged = (j->kind == CHGPU_JOIN_INNER && j->strictness == CHGPU_STRICT_ANY) || (j->kind == CHGPU_JOIN_RIGHT && j->strictness != CHGPU_STRICT_ALL);
-    // load factor in (0.175, 0.35]: a probe then resolves at its home cell nearly always (1.1 cells per hit, 1.3 per miss, against 1.75 / 3.6
-    // at 0.6).  Measured at C4: build 1.00 -> 0.90 ms (fewer retried claims), probe 3.40 -> 2.26 ms region-partitioned, 4.83 -> 3.39 ms
-    // one-pass.  The table is immutable after the build and 288 GB of HBM make the doubled footprint (512 MB of cells for 1e7 rows) cheap.
-    const u64 cap = join_capacity_for(j->ctx, j->total_rows);
-    CHGPU_REQUIRE(cap + 1 < 0xFFFFFFFFull, CHGPU_ERR_NOT_IMPLEMENTED, "build side of %llu rows exceeds the 32-bit cell index", (unsigned long long)j->total_rows);
-    const u64 cells = cap + 1;
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    size_t off_keys = 256, off_first = off_keys + al(cells * 16), off_cnt = off_first + al(cells * 8);
-    size_t off_start = off_cnt + (maps_all ? al(cells * 4) : 0);
-    size_t off_used = off_start + (maps_all ? al(cells * 8) : 0);
-    size_t off_rowids = off_used + (flagged ? al(cells * 8) : 0);
-    u64 pf_bits = 1ull << 16;
-    while (pf_bits < 16 * j->total_rows && pf_bits < (1ull << 25))
-        pf_bits <<= 1;
-    bool use_pf = pf_bits >= 16 * j->total_rows && !chgpu_opt(ctx, "tune_join_no_prefilter", 0);
+    p->pf = JOIN_PF_NONE;
+    p->pf_bits = 1ull << 16;
+    while (p->pf_bits < 16 * j->total_rows && p->pf_bits < (1ull << 25))
+        p->pf_bits <<= 1;
+    if (chgpu_opt(ctx, "tune_join_no_prefilter", 0))
+        return CHGPU_OK;
+    if (p->pf_bits >= 16 * j->total_rows)
+    {
+        p->pf = JOIN_PF_HASH;
+        return CHGPU_OK;
+    }
     // A larger build side of narrow DENSE keys (a filtered dimension table joined on its surrogate key: SSB's customer, 6 M of the keys
     // 1..30 M) still gets the exact bitmap if max_key + 1 bits fit the 4 MiB limit: the misses of the probe then stop at a bitmap that
     // lives in L2 / Infinity Cache instead of costing one HBM sector each.
-    if (!use_pf && chgpu_type_size(j->key_type) <= 4 && !chgpu_opt(ctx, "tune_join_no_prefilter", 0) && !chgpu_opt(ctx, "tune_join_no_dense_prefilter", 0))
+    if (chgpu_type_size(j->key_type) > 4 || chgpu_opt(ctx, "tune_join_no_dense_prefilter", 0))
+        return CHGPU_OK;
+    void * scratch0 = nullptr;
+    CHGPU_TRY(chgpu_scratch(ctx, 256, &scratch0));
+    CHGPU_HIP(hipMemsetAsync(scratch0, 0, 8, ctx->stream));
+    for (const BuildBlock & b : j->blocks)
+        if (b.rows)
+            hipLaunchKernelGGL(k_join_max_key, dim3(chgpu_grid_for(ctx, b.rows, JT, 4)), dim3(JT), 0, ctx->stream, (const u64 *)b.keys, b.rows, (unsigned long long *)scratch0);
+    u64 mk = 0;
+    CHGPU_TRY(chgpu_read_back(ctx, scratch0, &mk, sizeof(mk)));
+    if (mk < (1ull << 25))
     {
-        void * scratch0 = nullptr;
-        CHGPU_TRY(chgpu_scratch(ctx, 256, &scratch0));
-        CHGPU_HIP(hipMemsetAsync(scratch0, 0, 8, ctx->stream));
-        for (const BuildBlock & b : j->blocks)
-            if (b.rows)
-                hipLaunchKernelGGL(k_join_max_key, dim3(chgpu_grid_for(ctx, b.rows, JT, 4)), dim3(JT), 0, ctx->stream, (const u64 *)b.keys, b.rows, (unsigned long long *)scratch0);
-        u64 mk = 0;
-        CHGPU_TRY(chgpu_read_back(ctx, scratch0, &mk, sizeof(mk)));
-        if (mk < (1ull << 25))
-        {
-            pf_bits = 1ull << 16;
-            while (pf_bits <= mk)
-                pf_bits <<= 1;
-            use_pf = true;
-        }
+        p->pf = JOIN_PF_DENSE;
+        p->pf_bits = 1ull << 16;
+        while (p->pf_bits <= mk)
+            p->pf_bits <<= 1;
     }
-    size_t off_pf = off_rowids + (maps_all ? al(j->total_rows * 8) : 0);
-    size_t total_b = off_pf + (use_pf ? al(pf_bits / 8) : 0) + 256;
-    void * m = nullptr;
-    CHGPU_TRY(chgpu_pool_alloc(ctx, total_b, &m, &j->table_class)); // pooled: no hipMalloc/hipFree per join
-    j->table_mem = m;
-    JoinTable & t = j->t;
-    t.ctrl = (JoinCtrl *)m;
-    t.kv = (u64 *)((char *)m + off_keys);
-    t.first_row = (u64 *)((char *)m + off_first);
-    t.cnt = maps_all ? (u32 *)((char *)m + off_cnt) : nullptr;
-    t.start = maps_all ? (u64 *)((char *)m + off_start) : nullptr;
-    t.used_by = flagged ? (u64 *)((char *)m + off_used) : nullptr;
-    t.rowids = maps_all ? (u64 *)((char *)m + off_rowids) : nullptr;
-    t.capacity = cap;
-    t.pf = use_pf ? (u32 *)((char *)m + off_pf) : nullptr;
-    t.pf_mask = pf_bits - 1;
-    if (use_pf)
-        CHGPU_HIP(hipMemsetAsync(t.pf, 0, pf_bits / 8, ctx->stream));
-    // unique keys, one right block: the table slices are built in LDS and written out whole (join_build_slices; a prefilter is filled by
-    // k_join_finalize_values afterwards); only the
-    // control block and the zero key's cell need clearing first.  Anything else -- or a duplicate key met on the way -- takes the
-    // generic build over a zeroed table.
-    CHGPU_HIP(hipMemsetAsync(m, 0, off_keys, ctx->stream));
-    CHGPU_HIP(hipMemsetAsync(t.kv + 2 * cap, 0, 16, ctx->stream));
-    u32 slices_declined = 0;
-    u64 slices_overflow = 0;
-    const int fast = join_build_slices(j, t, &slices_declined, &slices_overflow);
-    if (fast != CHGPU_OK && fast != CHGPU_ERR_NOT_IMPLEMENTED)
-        return fast;
-    const bool sliced = fast == CHGPU_OK;
-    if (chgpu_opt(ctx, "debug", 0))
-    {
-        if (!sliced && slices_declined)
-            join_debug_declined(ctx, "join build slices", slices_declined);
-        fprintf(stderr, "chgpu: join build plan=%s rows=%llu cap=%llu overflow=%llu\n", sliced ? "slices" : "generic", (unsigned long long)j->total_rows,
-                (unsigned long long)cap, (unsigned long long)slices_overflow);
-    }
-    if (!sliced)
-        CHGPU_HIP(hipMemsetAsync(m, 0, off_first, ctx->stream)); // ctrl + {key, value} cells
-    const bool take_last = !maps_all && j->any_take_last_row;
-    // first_row: ~0 for atomicMin, 0 for atomicMax(+1)
-    // (unique keys: first_row / cnt are only read for cells that hold several rows -- there are none)
-    if (!sliced)
-    {
-        CHGPU_HIP(hipMemsetAsync(t.first_row, take_last ? 0x00 : 0xFF, cells * 8, ctx->stream));
-        if (maps_all)
-            CHGPU_HIP(hipMemsetAsync(t.cnt, 0, cells * 4, ctx->stream));
-    }
-    if (flagged)
-        CHGPU_HIP(hipMemsetAsync(t.used_by, 0xFF, cells * 8, ctx->stream));
+    return CHGPU_OK;
+}
 
-    // scratch: slot_of_row u32[total_rows] | cursor u32[cells] | total u64 | scan tmp
-    const size_t sor_b = al(j->total_rows * 4 + 4), cur_b = al(cells * 4), tmp_b = chgpu_scan_tmp_bytes(cells);
-    void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, sor_b + cur_b + 256 + tmp_b, &scratch));
-    u32 * slot_of_row = (u32 *)scratch;
-    u32 * cursor = (u32 *)((char *)scratch + sor_b);
-    u64 * total_dev = (u64 *)((char *)scratch + sor_b + cur_b);
-    void * tmp = (char *)scratch + sor_b + cur_b + 256;
+static int join_plan_build(chgpu_join * j, JoinBuildPlan * p)
+{
+    // joinDispatch.h:30-68: MapsAll for every ALL join and for every RIGHT join (RIGHT ANY / SEMI / ANTI keep all rows of a key); a cell
+    // remembers the left row that consumed it for INNER ANY and for RIGHT ANY / SEMI / ANTI (setUsedOnce / the per-key flag)
+    p->maps_all = j->strictness == CHGPU_STRICT_ALL || j->kind == CHGPU_JOIN_RIGHT;
+    p->flagged = (j->kind == CHGPU_JOIN_INNER && j->strictness == CHGPU_STRICT_ANY) || (j->kind == CHGPU_JOIN_RIGHT && j->strictness != CHGPU_STRICT_ALL);
+    p->take_last = !p->maps_all && j->any_take_last_row;
+    // load factor in (0.175, 0.35]: a probe then resolves at its home cell nearly always (1.1 cells per hit, 1.3 per miss, against 1.75 / 3.6
+    // at 0.6).  Measured at C4: build 1.00 -> 0.90 ms (fewer retried claims), probe 3.40 -> 2.26 ms region-partitioned, 4.83 -> 3.39 ms
+    // one-pass.  The table is immutable after the build and 288 GB of HBM make the doubled footprint (512 MB of cells for 1e7 rows) cheap.
+    p->cap = join_capacity_for(j->ctx, j->total_rows);
+    CHGPU_REQUIRE(p->cap + 1 < 0xFFFFFFFFull, CHGPU_ERR_NOT_IMPLEMENTED, "build side of %llu rows exceeds the 32-bit cell index", (unsigned long long)j->total_rows);
+    p->cells = p->cap + 1;
+    return join_choose_prefilter(j, p);
+}
 
-    for (size_t bi = 0; bi < j->blocks.size() && !sliced; ++bi)
+// The table's memory: the only place that knows the offsets.  Over base 0 the pointers are the offsets and `bytes` sizes the allocation.
+struct JoinTableLayout
+{
+    JoinTable t;
+    size_t bytes;
+};
+static JoinTableLayout join_table_layout(const JoinBuildPlan & p, u64 total_rows, uintptr_t base = 0)
+{
+    JoinCarve c{base};
+    JoinTable t{};
+    t.ctrl = (JoinCtrl *)c.take<char>(256);
+    t.kv = c.take<u64>(p.cells * 2);
+    t.first_row = c.take<u64>(p.cells);
+    t.cnt = p.maps_all ? c.take<u32>(p.cells) : nullptr;
+    t.start = p.maps_all ? c.take<u64>(p.cells) : nullptr;
+    t.used_by = p.flagged ? c.take<u64>(p.cells) : nullptr;
+    t.rowids = p.maps_all ? c.take<u64>(total_rows) : nullptr;
+    t.pf = p.pf != JOIN_PF_NONE ? c.take<u32>(p.pf_bits / 32) : nullptr;
+    c.take<char>(256); // (slack behind the last array)
+    t.capacity = p.cap;
+    t.pf_mask = p.pf_bits - 1;
+    return {t, (size_t)(c.at - base)};
+}
+
+// What the generic inserts leave for the CSR fill, and the fill's own temporaries
+struct JoinBuildScratch
+{
+    u32 * slot_of_row; // [total_rows + 1] the cell every build row went to
+    u32 * cursor;      // [cells]
+    u64 * total;
+    void * tmp;        // the scan's temporaries
+    size_t tmp_bytes;
+};
+static JoinBuildScratch join_build_carve(JoinCarve & c, u64 total_rows, u64 cells)
+{
+    JoinBuildScratch s{};
+    s.slot_of_row = c.take<u32>(total_rows + 1);
+    s.cursor = c.take<u32>(cells);
+    s.total = c.take<u64>(1);
+    s.tmp_bytes = chgpu_scan_tmp_bytes(cells);
+    s.tmp = c.last<char>(s.tmp_bytes);
+    return s;
+}
+// (asked for by the generic inserts and again by the finish, which also follows the slice build: the second request finds the scratch
+//  large enough and does nothing)
+static int join_build_scratch(chgpu_join * j, const JoinBuildPlan & p, JoinBuildScratch * s)
+{
+    return join_carve_scratch(j->ctx, [&](JoinCarve & c) { *s = join_build_carve(c, j->total_rows, p.cells); });
+}
+
+// One device-scope claim per row over a zeroed table.  first_row starts at ~0 for atomicMin, 0 for atomicMax(+1).
+static int join_build_generic(chgpu_join * j, const JoinBuildPlan & p)
+{
+    chgpu_ctx * ctx = j->ctx;
+    const JoinTable & t = j->t;
+    CHGPU_HIP(hipMemsetAsync(t.ctrl, 0, (size_t)((char *)t.first_row - (char *)t.ctrl), ctx->stream)); // ctrl + {key, value} cells
+    CHGPU_HIP(hipMemsetAsync(t.first_row, p.take_last ? 0x00 : 0xFF, p.cells * 8, ctx->stream));
+    if (p.maps_all)
+        CHGPU_HIP(hipMemsetAsync(t.cnt, 0, p.cells * 4, ctx->stream));
+    if (p.flagged)
+        CHGPU_HIP(hipMemsetAsync(t.used_by, 0xFF, p.cells * 8, ctx->stream));
+    JoinBuildScratch s;
+    CHGPU_TRY(join_build_scratch(j, p, &s));
+    for (size_t bi = 0; bi < j->blocks.size(); ++bi)
     {
         const BuildBlock & b = j->blocks[bi];
         if (!b.rows)
             continue;
         hipLaunchKernelGGL(k_join_insert, dim3(chgpu_grid_for(ctx, b.rows, JT, 8)), dim3(JT), 0, ctx->stream, t, (const u64 *)b.keys, (const u8 *)b.valid, b.rows,
-                           (u64)bi, maps_all ? 1 : 0, take_last ? 1 : 0, slot_of_row + b.base);
+                           (u64)bi, p.maps_all ? 1 : 0, p.take_last ? 1 : 0, s.slot_of_row + b.base);
         ctx->counters[6] += 1;
     }
-    // first flat row of every right block: row ids (block << 32 | row) -> position in payload columns glued over all blocks.  Uploaded
-    // here so that the read-back below -- which waits for the stream -- also covers this copy out of a host temporary.
-    const u64 nb_blocks = j->blocks.size();
-    std::vector<u64> bases(nb_blocks ? nb_blocks : 1, 0);
-    for (u64 b = 0; b < nb_blocks; ++b)
-        bases[b] = j->blocks[b].base;
+    return CHGPU_OK;
+}
+
+// First flat row of every right block -> dst[max(blocks, 1)]: row ids (block << 32 | row) -> position in payload columns glued over all
+// blocks.  `host` is the copy's source: the caller keeps it until it has waited for the stream.
+static size_t join_block_bases_bytes(const chgpu_join * j) { return (j->blocks.empty() ? 1 : j->blocks.size()) * sizeof(u64); }
+static int join_upload_block_bases(const chgpu_join * j, u64 * dst, std::vector<u64> & host)
+{
+    host.assign(join_block_bases_bytes(j) / sizeof(u64), 0);
+    for (size_t b = 0; b < j->blocks.size(); ++b)
+        host[b] = j->blocks[b].base;
+    CHGPU_HIP(hipMemcpyAsync(dst, host.data(), host.size() * sizeof(u64), hipMemcpyHostToDevice, j->ctx->stream));
+    return CHGPU_OK;
+}
+
+// ALL over duplicate keys: the rows of every key gathered into its CSR run -> j->inserted
+static int join_fill_csr(chgpu_join * j, const JoinBuildPlan & p, const JoinBuildScratch & s)
+{
+    chgpu_ctx * ctx = j->ctx;
+    const JoinTable & t = j->t;
+    CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, t.cnt, t.start, p.cells, s.total, s.tmp, s.tmp_bytes));
+    CHGPU_HIP(hipMemsetAsync(s.cursor, 0, p.cells * 4, ctx->stream));
+    for (size_t bi = 0; bi < j->blocks.size(); ++bi)
     {
-        void * um = nullptr, * bm = nullptr;
-        if (jf_track_used(j))
-        {
-            CHGPU_TRY(chgpu_pool_alloc(ctx, j->total_rows + 64, &um, &j->used_class));
-            j->used = (u8 *)um;
-            CHGPU_HIP(hipMemsetAsync(j->used, 0, j->total_rows + 64, ctx->stream));
-        }
-        CHGPU_TRY(chgpu_pool_alloc(ctx, bases.size() * sizeof(u64), &bm, &j->base_class));
-        j->block_base_dev = (u64 *)bm;
-        CHGPU_HIP(hipMemcpyAsync(j->block_base_dev, bases.data(), bases.size() * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+        const BuildBlock & b = j->blocks[bi];
+        if (!b.rows)
+            continue;
+        hipLaunchKernelGGL(k_join_fill, dim3(chgpu_grid_for(ctx, b.rows, JT, 8)), dim3(JT), 0, ctx->stream, t, (const u32 *)(s.slot_of_row + b.base), b.rows, (u64)bi, s.cursor);
+        ctx->counters[6] += 1;
     }
+    hipLaunchKernelGGL(k_join_root_first, dim3(chgpu_grid_for(ctx, p.cells, JT, 8)), dim3(JT), 0, ctx->stream, t);
+    ctx->counters[6] += 1;
+    return chgpu_read_back(ctx, s.total, &j->inserted, sizeof(u64));
+}
+
+// Everything after the inserts of either builder: the used flags and block bases the probes need, then -- the one decision about it --
+// what is left to do to the cells, from whether any key got a second row and which builder ran.
+static int join_finish_table(chgpu_join * j, const JoinBuildPlan & p, bool sliced)
+{
+    chgpu_ctx * ctx = j->ctx;
+    const JoinTable & t = j->t;
+    JoinBuildScratch s;
+    CHGPU_TRY(join_build_scratch(j, p, &s));
+    if (jf_track_used(j))
+    {
+        void * um = nullptr;
+        CHGPU_TRY(chgpu_pool_alloc(ctx, j->total_rows + 64, &um, &j->used_class));
+        j->used = (u8 *)um;
+        CHGPU_HIP(hipMemsetAsync(j->used, 0, j->total_rows + 64, ctx->stream));
+    }
+    // (uploaded here so that the read-back below -- which waits for the stream -- also covers this copy out of a host temporary)
+    std::vector<u64> bases;
+    void * bm = nullptr;
+    CHGPU_TRY(chgpu_pool_alloc(ctx, join_block_bases_bytes(j), &bm, &j->base_class));
+    j->block_base_dev = (u64 *)bm;
+    CHGPU_TRY(join_upload_block_bases(j, j->block_base_dev, bases));
     // did any key get a second row?  (one small read-back; the common primary-key build then skips four passes over the table)
-    JoinCtrl after_insert;
-    CHGPU_TRY(chgpu_read_back(ctx, t.ctrl, &after_insert, sizeof(after_insert)));
-    const bool unique = after_insert.pad == 0;
+    JoinCtrl c;
+    CHGPU_TRY(chgpu_read_back(ctx, t.ctrl, &c, sizeof(c)));
+    const bool unique = c.pad == 0;
     j->unique_keys = unique;
     if (!unique)
     {
-        hipLaunchKernelGGL(k_join_merge_claims, dim3(chgpu_grid_for(ctx, cells, JT, 8)), dim3(JT), 0, ctx->stream, t, maps_all ? 1 : 0, take_last ? 1 : 0);
+        hipLaunchKernelGGL(k_join_merge_claims, dim3(chgpu_grid_for(ctx, p.cells, JT, 8)), dim3(JT), 0, ctx->stream, t, p.maps_all ? 1 : 0, p.take_last ? 1 : 0);
         ctx->counters[6] += 1;
     }
-    if (maps_all && !unique)
-    {
-        CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, t.cnt, t.start, cells, total_dev, tmp, tmp_b));
-        CHGPU_HIP(hipMemsetAsync(cursor, 0, cells * 4, ctx->stream));
-        for (size_t bi = 0; bi < j->blocks.size(); ++bi)
-        {
-            const BuildBlock & b = j->blocks[bi];
-            if (!b.rows)
-                continue;
-            hipLaunchKernelGGL(k_join_fill, dim3(chgpu_grid_for(ctx, b.rows, JT, 8)), dim3(JT), 0, ctx->stream, t, (const u32 *)(slot_of_row + b.base), b.rows, (u64)bi, cursor);
-            ctx->counters[6] += 1;
-        }
-        hipLaunchKernelGGL(k_join_root_first, dim3(chgpu_grid_for(ctx, cells, JT, 8)), dim3(JT), 0, ctx->stream, t);
-        ctx->counters[6] += 1;
-        CHGPU_TRY(chgpu_read_back(ctx, total_dev, &j->inserted, sizeof(u64)));
-    }
-    else if (maps_all)
-        j->inserted = after_insert.n_keys;
-    // (without duplicates and without a prefilter there is nothing to finalise: the value word of an empty cell is never read)
+    if (p.maps_all && !unique)
+        CHGPU_TRY(join_fill_csr(j, p, s));
+    else if (p.maps_all)
+        j->inserted = c.n_keys;
     if (sliced && unique)
     {
+        // the slices carry their final values: only a prefilter is left to fill
         if (t.pf)
         {
             hipLaunchKernelGGL(k_join_pf_fill, dim3(chgpu_grid_for(ctx, j->blocks[0].rows, JT, 8)), dim3(JT), 0, ctx->stream, t, (const u64 *)j->blocks[0].keys, j->blocks[0].rows);
@@ -1848,13 +1976,13 @@ static int join_build_table(chgpu_join * j)
     }
     else if (!unique || t.pf)
     {
-        hipLaunchKernelGGL(k_join_finalize_values, dim3(chgpu_grid_for(ctx, cells, JT, 8)), dim3(JT), 0, ctx->stream, t, maps_all ? 1 : 0, take_last ? 1 : 0, unique ? 1 : 0);
+        // (without duplicates and without a prefilter there is nothing to finalise: the value word of an empty cell is never read)
+        hipLaunchKernelGGL(k_join_finalize_values, dim3(chgpu_grid_for(ctx, p.cells, JT, 8)), dim3(JT), 0, ctx->stream, t, p.maps_all ? 1 : 0, p.take_last ? 1 : 0, unique ? 1 : 0);
         ctx->counters[6] += 1;
     }
     CHGPU_HIP(hipGetLastError());
     // unique keys: nothing after the inserts touches the control block -- the read-back above already holds the final key count, the
     // largest key and the zero-key flag (one host synchronisation per build instead of three)
-    JoinCtrl c = after_insert;
     if (!unique)
         CHGPU_TRY(chgpu_read_back(ctx, t.ctrl, &c, sizeof(c)));
     j->n_keys = c.n_keys;
@@ -1862,6 +1990,63 @@ static int join_build_table(chgpu_join * j)
     j->has_zero = c.has_zero != 0;
     j->finished = true;
     return CHGPU_OK;
+}
+
+static int join_build_table(chgpu_join * j)
+{
+    if (j->finished)
+        return CHGPU_OK;
+    j->build_closed = true;
+    chgpu_ctx * ctx = j->ctx;
+    JoinBuildPlan p;
+    CHGPU_TRY(join_plan_build(j, &p));
+    void * m = nullptr;
+    CHGPU_TRY(chgpu_pool_alloc(ctx, join_table_layout(p, j->total_rows).bytes, &m, &j->table_class)); // pooled: no hipMalloc/hipFree per join
+    j->table_mem = m;
+    j->t = join_table_layout(p, j->total_rows, (uintptr_t)m).t;
+    if (j->t.pf)
+        CHGPU_HIP(hipMemsetAsync(j->t.pf, 0, p.pf_bits / 8, ctx->stream));
+    // unique keys, one right block: the table slices are built in LDS and written out whole (join_build_slices).  Anything else -- or a
+    // duplicate key met on the way -- takes the generic build.
+    u32 slices_declined = 0;
+    u64 slices_overflow = 0;
+    const int fast = join_build_slices(j, j->t, &slices_declined, &slices_overflow);
+    if (fast != CHGPU_OK && fast != CHGPU_ERR_NOT_IMPLEMENTED)
+        return fast;
+    const bool sliced = fast == CHGPU_OK;
+    if (!sliced && slices_declined)
+        join_debug_declined(ctx, "join build slices", slices_declined);
+    if (!sliced)
+        CHGPU_TRY(join_build_generic(j, p));
+    CHGPU_TRY(join_finish_table(j, p, sliced));
+    if (chgpu_opt(ctx, "debug", 0))
+    {
+        const JoinKeySet ks = join_key_set(j);
+        fprintf(stderr, "chgpu: join build plan=%s rows=%llu cap=%llu overflow=%llu pf=%s unique=%d\n", sliced ? "slices" : "generic", (unsigned long long)j->total_rows,
+                (unsigned long long)p.cap, (unsigned long long)slices_overflow, ks.dense ? "dense" : ks.pf ? "hash" : "none", j->unique_keys ? 1 : 0);
+    }
+    return CHGPU_OK;
+}
+
+// The temporaries of chgpu_join_non_joined_rows over n build rows (pool memory, not the context's scratch)
+struct JoinUnusedScratch
+{
+    u32 * flag; // [n] the row was not used
+    u64 * pos;  // [n] the flags' exclusive scan
+    u64 * total;
+    void * tmp; // the scan's temporaries
+    size_t bytes;
+};
+static JoinUnusedScratch join_unused_carve(JoinCarve c, u64 n)
+{
+    const uintptr_t base = c.at;
+    JoinUnusedScratch u{};
+    u.flag = c.take<u32>(n);
+    u.pos = c.take<u64>(n);
+    u.total = c.take<u64>(1);
+    u.tmp = c.last<char>(chgpu_scan_tmp_bytes(n));
+    u.bytes = c.at - base;
+    return u;
 }
 
 /* IJoin::getNonJoinedBlocks (src/Interpreters/IJoin.h:133-134; NotJoinedHash, HashJoin.cpp:1280-1420) for RIGHT / FULL joins: after the
@@ -1880,15 +2065,14 @@ extern "C" int chgpu_join_non_joined_rows(chgpu_join * j, chgpu_col ** right_row
     u64 total = 0;
     if (n)
     {
-        auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-        const size_t b_flag = al(n * 4), b_pos = al(n * 8), b_tmp = chgpu_scan_tmp_bytes(n);
+        const size_t b_tmp = chgpu_scan_tmp_bytes(n);
         void * mem = nullptr;
         size_t mem_class = 0;
-        CHGPU_TRY(chgpu_pool_alloc(ctx, b_flag + b_pos + 256 + b_tmp, &mem, &mem_class));
-        u32 * flag = (u32 *)mem;
-        u64 * pos = (u64 *)((char *)mem + b_flag);
-        u64 * total_dev = (u64 *)((char *)mem + b_flag + b_pos);
-        void * tmp = (char *)mem + b_flag + b_pos + 256;
+        CHGPU_TRY(chgpu_pool_alloc(ctx, join_unused_carve(JoinCarve{0}, n).bytes, &mem, &mem_class));
+        const JoinUnusedScratch u = join_unused_carve(JoinCarve{(uintptr_t)mem}, n);
+        u32 * flag = u.flag;
+        u64 * pos = u.pos, * total_dev = u.total;
+        void * tmp = u.tmp;
         const u32 grid = chgpu_grid_for(ctx, n, JT, 8);
         hipLaunchKernelGGL(k_join_unused_flags, dim3(grid), dim3(JT), 0, ctx->stream, (const u8 *)j->used, n, flag);
         int rc = chgpu_scan_exclusive_u32_u64(ctx, flag, pos, n, total_dev, tmp, b_tmp);
@@ -1928,12 +2112,11 @@ extern "C" int chgpu_join_flatten_rowids(chgpu_join * j, const chgpu_col * rowid
     CHGPU_REQUIRE(chgpu_type_size(rowids->type) == 8, CHGPU_ERR_BAD_ARGUMENTS, "row ids must be a 64-bit column");
     chgpu_ctx * ctx = j->ctx;
     const u64 nb = j->blocks.size();
-    std::vector<u64> bases(nb ? nb : 1, 0);
-    for (u64 b = 0; b < nb; ++b)
-        bases[b] = j->blocks[b].base;
+    // (a copy of its own in the scratch: the table, whose build uploads j->block_base_dev, may not exist yet and is not built for this)
+    std::vector<u64> bases;
     void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, bases.size() * sizeof(u64), &scratch));
-    CHGPU_HIP(hipMemcpyAsync(scratch, bases.data(), bases.size() * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    CHGPU_TRY(chgpu_scratch(ctx, join_block_bases_bytes(j), &scratch));
+    CHGPU_TRY(join_upload_block_bases(j, (u64 *)scratch, bases));
     CHGPU_HIP(hipStreamSynchronize(ctx->stream)); // `bases` is a host temporary
     chgpu_col * out = nullptr;
     CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, rowids->rows, &out));
@@ -1981,30 +2164,29 @@ static int join_probe_filter_only(chgpu_join * j, const chgpu_col * key_col, con
 {
     chgpu_ctx * ctx = j->ctx;
     const u64 n = key_col->rows;
-    chgpu_col * fcol = nullptr;
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, n, &fcol));
+    JoinOutCol fcol;
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, n, &fcol.col));
     hipError_t e = hipMemsetAsync(&j->t.ctrl->n_out, 0, sizeof(u64), ctx->stream);
     const u8 * nm = null_map ? (const u8 *)null_map->data : nullptr;
     // dense 4-byte keys whose key set fits a few LDS slices: k_join_probe_filter_lds_multi (the tail of a bitmap beyond max_key is zero)
     const bool no_lds_filter = chgpu_opt(ctx, "tune_join_no_lds_filter", 0) != 0;
-    const u64 dense_bits = (j->max_key + 32) / 32 * 32;
-    if (e == hipSuccess && !no_lds_filter && j->t.pf && j->max_key <= j->t.pf_mask && chgpu_type_size(j->key_type) == 4 && dense_bits <= 4ull * JPL_SLICE_BITS
-        && n >= (1u << 20) && (uintptr_t)key_col->data % 16 == 0 && (!null_map || (uintptr_t)null_map->data % 4 == 0))
+    const JoinKeySet ks = join_key_set(j);
+    if (e == hipSuccess && !no_lds_filter && join_lds_filter_fits(ks, j->key_type, n, key_col->data, nm, JPL_SLICE_BITS, 4))
     {
         // one sweep, every part of the rows through all slices.  A single slice too: a kernel of its own for that case measured slower
         // (profiles/join_filter_single_vs_multi.json)
-        const u32 slices = (u32)((dense_bits + JPL_SLICE_BITS - 1) / JPL_SLICE_BITS);
+        const u32 slices = (u32)((ks.dense_bits + JPL_SLICE_BITS - 1) / JPL_SLICE_BITS);
         auto kern = null_map ? k_join_probe_filter_lds_multi<true> : k_join_probe_filter_lds_multi<false>;
         e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(JPL_SLICE_BITS / 8));
         if (e == hipSuccess)
-            hipLaunchKernelGGL(kern, dim3((u32)ctx->num_cus), dim3(1024), (size_t)(JPL_SLICE_BITS / 8), ctx->stream, (const u32 *)j->t.pf, (u32)dense_bits, slices,
-                               anti ? 1 : 0, j->has_zero ? 1 : 0, (const u32 *)key_col->data, nm, n, (u8 *)fcol->data, j->t.ctrl);
+            hipLaunchKernelGGL(kern, dim3((u32)ctx->num_cus), dim3(1024), (size_t)(JPL_SLICE_BITS / 8), ctx->stream, ks.pf, (u32)ks.dense_bits, slices,
+                               anti ? 1 : 0, ks.has_zero ? 1 : 0, (const u32 *)key_col->data, nm, n, (u8 *)fcol.col->data, j->t.ctrl);
     }
     else if (e == hipSuccess)
     {
         auto kern = j->t.pf ? k_join_probe_filter<true> : k_join_probe_filter<false>;
         hipLaunchKernelGGL(kern, dim3(chgpu_grid_for(ctx, (n + JPF_R - 1) / JPF_R, JT, 8)), dim3(JT), 0, ctx->stream, j->t, anti ? 1 : 0, (const void *)key_col->data,
-                           j->key_type, nm, n, (u8 *)fcol->data, j->t.ctrl);
+                           j->key_type, nm, n, (u8 *)fcol.col->data, j->t.ctrl);
     }
     if (e == hipSuccess)
     {
@@ -2012,19 +2194,36 @@ static int join_probe_filter_only(chgpu_join * j, const chgpu_col * key_col, con
         e = hipGetLastError();
     }
     JoinCtrl c;
-    int rc = e == hipSuccess ? chgpu_read_back(ctx, j->t.ctrl, &c, sizeof(c)) : chgpu_set_error(CHGPU_ERR_DEVICE, "join probe launch: %s", hipGetErrorString(e));
-    if (rc != CHGPU_OK)
-    {
-        chgpu_col_free(fcol);
-        return rc;
-    }
+    CHGPU_TRY(e == hipSuccess ? chgpu_read_back(ctx, j->t.ctrl, &c, sizeof(c)) : chgpu_set_error(CHGPU_ERR_DEVICE, "join probe launch: %s", hipGetErrorString(e)));
     j->left_seq += n;
-    *filter_out = fcol;
+    *filter_out = fcol.release();
     *n_out = c.n_out;
     *n_left_consumed = n;
     ctx->counters[3] += n;
     ctx->counters[4] += c.n_out;
     return CHGPU_OK;
+}
+
+// The per-left-row temporaries of chgpu_join_probe
+struct JoinProbeScratch
+{
+    u32 * slot_of_left; // [n] the cell the row bid for
+    u32 * counts;       // [n] joined rows per left row
+    u64 * val_of_left;  // [n] the packed value of the matched cell
+    u64 * total;
+    void * tmp;         // the scan's temporaries
+    size_t tmp_bytes;
+};
+static JoinProbeScratch join_probe_carve(JoinCarve & c, u64 n)
+{
+    JoinProbeScratch s{};
+    s.slot_of_left = c.take<u32>(n);
+    s.counts = c.take<u32>(n);
+    s.val_of_left = c.take<u64>(n);
+    s.total = c.take<u64>(1);
+    s.tmp_bytes = chgpu_scan_tmp_bytes(n);
+    s.tmp = c.last<char>(s.tmp_bytes);
+    return s;
 }
 
 extern "C" int chgpu_join_probe(chgpu_join * j, const chgpu_col * key_col, const chgpu_col * null_map, uint64_t max_joined_block_rows,
@@ -2065,30 +2264,16 @@ extern "C" int chgpu_join_probe(chgpu_join * j, const chgpu_col * key_col, const
     if (!right_rowid_out)
         return join_probe_filter_only(j, key_col, null_map, variant == PV_ANTI_LEFT, filter_out, n_out, n_left_consumed);
 
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t sl_b = al(n * 4), cnt_b = al(n * 4), val_b = al(n * 8), tmp_b = chgpu_scan_tmp_bytes(n);
-    void * scratch = nullptr;
-    CHGPU_TRY(chgpu_scratch(ctx, sl_b + cnt_b + val_b + 256 + tmp_b, &scratch));
-    u32 * slot_of_left = (u32 *)scratch;
-    u32 * counts = (u32 *)((char *)scratch + sl_b);
-    u64 * val_of_left = (u64 *)((char *)scratch + sl_b + cnt_b);
-    u64 * total_dev = (u64 *)((char *)scratch + sl_b + cnt_b + val_b);
-    void * tmp = (char *)scratch + sl_b + cnt_b + val_b + 256;
+    JoinProbeScratch s;
+    CHGPU_TRY(join_carve_scratch(ctx, [&](JoinCarve & c) { s = join_probe_carve(c, n); }));
+    u32 * slot_of_left = s.slot_of_left, * counts = s.counts;
+    u64 * val_of_left = s.val_of_left;
 
-    chgpu_col * filter = nullptr;
-    chgpu_col * offsets = nullptr;
-    chgpu_col * rowid = nullptr;
-    int rc = CHGPU_OK;
-    auto fail = [&](int code) {
-        chgpu_col_free(filter);
-        chgpu_col_free(offsets);
-        chgpu_col_free(rowid);
-        return code;
-    };
-    if (need_filter && (rc = chgpu_col_new(ctx, CHGPU_U8, n, &filter)) != CHGPU_OK)
-        return fail(rc);
-    if ((rc = chgpu_col_new(ctx, CHGPU_U64, n, &offsets)) != CHGPU_OK)
-        return fail(rc);
+    JoinOutCol filter_col, offsets_col, rowid_col;
+    if (need_filter)
+        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, n, &filter_col.col));
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, n, &offsets_col.col));
+    chgpu_col * const filter = filter_col.col, * const offsets = offsets_col.col;
 
     const u32 grid = chgpu_grid_for(ctx, n, JT, 8);
     const void * kp = key_col->data;
@@ -2109,15 +2294,13 @@ extern "C" int chgpu_join_probe(chgpu_join * j, const chgpu_col * key_col, const
                            (const u64 *)j->block_base_dev, (u64)j->blocks.size(), j->total_rows, j->used);
         ctx->counters[6] += 1;
     }
-    if ((rc = chgpu_scan_inclusive_u32_u64(ctx, counts, (u64 *)offsets->data, n, total_dev, tmp, tmp_b)) != CHGPU_OK)
-        return fail(rc);
+    CHGPU_TRY(chgpu_scan_inclusive_u32_u64(ctx, counts, (u64 *)offsets->data, n, s.total, s.tmp, s.tmp_bytes));
     hipLaunchKernelGGL(k_join_cut, dim3(1), dim3(64), 0, ctx->stream, (const u64 *)offsets->data, n, (u64)max_joined_block_rows, j->t.ctrl);
     ctx->counters[6] += 1;
     JoinCtrl c;
-    if ((rc = chgpu_read_back(ctx, j->t.ctrl, &c, sizeof(c))) != CHGPU_OK)
-        return fail(rc);
-    if ((rc = chgpu_col_new(ctx, CHGPU_U64, c.n_out, &rowid)) != CHGPU_OK)
-        return fail(rc);
+    CHGPU_TRY(chgpu_read_back(ctx, j->t.ctrl, &c, sizeof(c)));
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, c.n_out, &rowid_col.col));
+    chgpu_col * const rowid = rowid_col.col;
     if (c.n_out)
     {
         hipLaunchKernelGGL(k_join_emit, dim3(grid), dim3(JT), 0, ctx->stream, j->t, variant, (const u64 *)val_of_left, (const u32 *)counts,
@@ -2133,10 +2316,7 @@ extern "C" int chgpu_join_probe(chgpu_join * j, const chgpu_col * key_col, const
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
-    {
-        chgpu_set_error(CHGPU_ERR_DEVICE, "join probe launch: %s", hipGetErrorString(e));
-        return fail(CHGPU_ERR_DEVICE);
-    }
+        return chgpu_set_error(CHGPU_ERR_DEVICE, "join probe launch: %s", hipGetErrorString(e));
     // (the scratch buffers -- slot_of_left, counts -- are reused by the next call on this context, which launches on the same stream and so
     //  runs after the kernels above; chgpu_scratch drains the stream itself before it ever frees a buffer: no host synchronisation here)
     j->left_seq += c.consumed; // rows not consumed are resubmitted by the caller and bid again
@@ -2145,12 +2325,10 @@ extern "C" int chgpu_join_probe(chgpu_join * j, const chgpu_col * key_col, const
         filter->rows = c.consumed;
     offsets->rows = c.consumed;
     if (need_filter)
-        *filter_out = filter;
-    if (need_repl)
-        *offsets_out = offsets;
-    else
-        chgpu_col_free(offsets);
-    *right_rowid_out = rowid;
+        *filter_out = filter_col.release();
+    if (need_repl) // (otherwise the offsets only served the emit: they go with their holder)
+        *offsets_out = offsets_col.release();
+    *right_rowid_out = rowid_col.release();
     *n_out = c.n_out;
     *n_left_consumed = c.consumed;
     ctx->counters[3] += c.consumed;

@@ -37,8 +37,12 @@ def test_constants_match_the_header():
     assert _const(text, "JC_PART_ROWS") == cc.PART_ROWS
     assert _const(text, "JC_UNIT_ROWS") == cc.UNIT_ROWS
     assert _const(text, "JC_UNITS_PER_PART") == cc.UNITS_PER_PART
-    # the row threshold of the LDS sweep and the key-set limit are literals
-    assert re.search(r"n >= \(1u << (\d+)\)", text).group(1) == str(cc.LDS_MIN_ROWS.bit_length() - 1)
+    # the row threshold of the LDS sweep and the key-set limit are literals (the threshold sits in the gate the chain shares with the
+    # filter-only probe, beside the join's kernels)
+    with open(os.path.join(os.path.dirname(HEADER), "join_kernels.hip")) as f:
+        gate = re.search(r"static bool join_lds_filter_fits\(.*?\n}\n", f.read(), re.S).group(0)
+    assert "join_lds_filter_fits(" in text and "JC_SLICE_BITS, JC_MAX_SLICES)" in text
+    assert re.search(r"n >= \(1u << (\d+)\)", gate).group(1) == str(cc.LDS_MIN_ROWS.bit_length() - 1)
     assert re.search(r"r\[0\] >= \(1ull << (\d+)\)", text).group(1) == str(cc.KEYSET_LIMIT.bit_length() - 1)
     # the grid caps the many-turn case derives its row count from, and the row mapping of the alive words
     assert "(u64)ctx->num_cus * 4" in text and "(u64)ctx->num_cus * 8" in text and "(u64)ctx->num_cus)" in text
