@@ -66,6 +66,11 @@ class ActionsDAG:
         return ExpressionActions(self)
 
 
+def _handles(cols):
+    """cols[position] for every INPUT node (None for unused positions) -> the chgpu_col * array the C ABI takes"""
+    return (C.c_void_p * len(cols))(*[c._h if c is not None else None for c in cols])
+
+
 class ExpressionActions:
     def __init__(self, dag: ActionsDAG):
         arr = (ExprNode * len(dag.nodes))()
@@ -103,7 +108,7 @@ class ExpressionActions:
 
     def execute(self, ctx: Context, cols, out_nodes):
         """cols[position] for every INPUT node (None for unused positions) -> one new Column per out_nodes entry"""
-        arr = (C.c_void_p * len(cols))(*[c._h if c is not None else None for c in cols])
+        arr = _handles(cols)
         outs_n = (C.c_uint32 * len(out_nodes))(*out_nodes)
         outs = (C.c_void_p * len(out_nodes))()
         K.check(K.lib().chgpu_expr_execute(ctx._h, self._h, len(cols), arr, len(out_nodes), outs_n, outs))
@@ -111,7 +116,7 @@ class ExpressionActions:
 
     def filter_execute(self, ctx: Context, cols, filter_node: int, out_nodes):
         """WHERE filter_node + projection of out_nodes in one step -> ([Columns of the surviving rows, in order], rows)"""
-        arr = (C.c_void_p * len(cols))(*[c._h if c is not None else None for c in cols])
+        arr = _handles(cols)
         outs_n = (C.c_uint32 * len(out_nodes))(*out_nodes)
         outs = (C.c_void_p * len(out_nodes))()
         rows = C.c_uint64(0)
@@ -120,7 +125,7 @@ class ExpressionActions:
 
     def filter_minmax(self, ctx: Context, cols, filter_node: int, value_node: int):
         """(min(value_node), max(value_node), count()) over the rows where filter_node != 0 (-1: every row); integer values only"""
-        arr = (C.c_void_p * len(cols))(*[c._h if c is not None else None for c in cols])
+        arr = _handles(cols)
         vt = C.c_int(0)
         lo, hi = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint64)
         cnt = C.c_uint64(0)
@@ -131,7 +136,7 @@ class ExpressionActions:
 
     def filter_sum(self, ctx: Context, cols, filter_node: int = -1, value_node: int = -1):
         """(sum(value_node), count()) over the rows where filter_node != 0, one pass"""
-        arr = (C.c_void_p * len(cols))(*[c._h if c is not None else None for c in cols])
+        arr = _handles(cols)
         rt = C.c_int(0)
         out = np.zeros(1, dtype=np.uint64)
         cnt = C.c_uint64(0)

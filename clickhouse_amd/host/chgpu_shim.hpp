@@ -658,14 +658,7 @@ public:
     /// columns[position] feeds INPUT(position); one new column per entry of `outputs`
     Columns execute(const Columns & columns, const std::vector<ActionsDAG::Node> & outputs) const
     {
-        std::vector<const chgpu_col *> in;
-        ContextPtr ctx;
-        for (auto & c : columns)
-        {
-            in.push_back(c ? c->handle() : nullptr);
-            if (c && !ctx)
-                ctx = c->context();
-        }
+        auto [in, ctx] = handlesAndContext(columns);
         std::vector<chgpu_col *> out(outputs.size(), nullptr);
         check(chgpu_expr_execute(ctx->get(), h, static_cast<uint32_t>(in.size()), in.data(), static_cast<uint32_t>(outputs.size()), outputs.data(), out.data()));
         Columns res;
@@ -676,14 +669,7 @@ public:
     /// SELECT sum(value), count() WHERE filter over one chunk, nothing materialised; returns the raw 8 state bytes and the count
     std::pair<uint64_t, uint64_t> filterSum(const Columns & columns, int filter_node, int value_node, int * result_type = nullptr) const
     {
-        std::vector<const chgpu_col *> in;
-        ContextPtr ctx;
-        for (auto & c : columns)
-        {
-            in.push_back(c ? c->handle() : nullptr);
-            if (c && !ctx)
-                ctx = c->context();
-        }
+        auto [in, ctx] = handlesAndContext(columns);
         uint64_t bits = 0, count = 0;
         check(chgpu_expr_filter_sum_node(ctx->get(), h, static_cast<uint32_t>(in.size()), in.data(), filter_node, value_node, result_type, &bits, &count));
         return {bits, count};
@@ -693,6 +679,16 @@ public:
     struct MinMax { uint64_t min_bits = 0, max_bits = 0, count = 0; int type = 0; };
     MinMax filterMinMax(const Columns & columns, int filter_node, ActionsDAG::Node value_node) const
     {
+        auto [in, ctx] = handlesAndContext(columns);
+        MinMax r;
+        check(chgpu_expr_filter_minmax_node(ctx->get(), h, static_cast<uint32_t>(in.size()), in.data(), filter_node, value_node, &r.type, &r.min_bits, &r.max_bits, &r.count));
+        return r;
+    }
+
+private:
+    /// columns[position] as the C ABI takes them (nullptr for unused positions) and the context of the first column present
+    static std::pair<std::vector<const chgpu_col *>, ContextPtr> handlesAndContext(const Columns & columns)
+    {
         std::vector<const chgpu_col *> in;
         ContextPtr ctx;
         for (auto & c : columns)
@@ -701,12 +697,8 @@ public:
             if (c && !ctx)
                 ctx = c->context();
         }
-        MinMax r;
-        check(chgpu_expr_filter_minmax_node(ctx->get(), h, static_cast<uint32_t>(in.size()), in.data(), filter_node, value_node, &r.type, &r.min_bits, &r.max_bits, &r.count));
-        return r;
+        return {std::move(in), std::move(ctx)};
     }
-
-private:
     chgpu_expr * h = nullptr;
 };
 

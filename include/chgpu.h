@@ -341,7 +341,8 @@ typedef struct chgpu_expr chgpu_expr;
 int chgpu_expr_compile(uint32_t n_nodes, const chgpu_expr_node * nodes, chgpu_expr ** out);
 int chgpu_expr_node_type(const chgpu_expr * expr, uint32_t node, int * type_out);
 /* runs the run-time compiler only (no device): n_outputs > 0 -> the materialising kernel for out_nodes (with filter_node >= 0: the
-   WHERE + projection pair of chgpu_expr_filter_execute), n_outputs == 0 -> the fused filter + sum kernel for (filter_node, value_node) */
+   WHERE + projection pair of chgpu_expr_filter_execute, refused where that call refuses it), n_outputs == 0 -> the fused filter +
+   sum kernel for (filter_node, value_node) */
 int chgpu_expr_precompile(const chgpu_expr * expr, uint32_t n_outputs, const uint32_t * out_nodes, int filter_node, int value_node,
                           uint64_t * code_bytes_out);
 /* materialise out_nodes[n_outputs] (<= 8) as new columns over cols[n_cols] (the INPUT nodes' columns, all of one length) */

@@ -171,6 +171,18 @@ def test_compile_errors():
     with pytest.raises(ch.ChgpuError) as ei:
         d.compile()
     assert ei.value.code == ch._capi.ERR_NOT_IMPLEMENTED
+    # the edges of the function look-up: codes no function has, over valid operands; the same with an operand that does not precede
+    # the node (an unknown code is taken to have two operands); casts to a type tag that does not exist
+    for code, args, want in [(9, (0, 1, -1), ch._capi.ERR_NOT_IMPLEMENTED), (99, (0, 1, -1), ch._capi.ERR_NOT_IMPLEMENTED),
+                             (9, (0, 2, -1), ch._capi.ERR_BAD_ARGUMENTS), (99, (0, 5, -1), ch._capi.ERR_BAD_ARGUMENTS)] + \
+                            [(OE.FN_CAST + to, (0, -1, -1), ch._capi.ERR_NOT_IMPLEMENTED) for to in range(10, 16)]:
+        d = ch.ActionsDAG()
+        d.add_input(0, np.int64)
+        d.add_input(1, np.int64)
+        d.nodes.append((OE.EX_FUNC, code, 0, args, 0))
+        with pytest.raises(ch.ChgpuError) as ei:
+            d.compile()
+        assert ei.value.code == want, (code, args)
 
 
 def _q11_dag(ch):
@@ -192,6 +204,21 @@ def test_runtime_compiler_builds_gfx950_code_without_a_device():
     assert ex.node_dtype(v) == np.uint64 and ex.node_dtype(f) == np.uint8
     assert ex.precompile(filter_node=f, value_node=v) > 1000       # fused filter + sum kernel
     assert ex.precompile(out_nodes=[f, v]) > 1000                  # materialising kernel
+
+
+def test_precompile_validates_the_where_projection_pair_like_filter_execute():
+    """an integer WHERE node and 1..7 outputs, as chgpu_expr_filter_execute demands"""
+    import clickhouse_amd as ch
+    d = ch.ActionsDAG()
+    a = d.add_input(0, np.int64)
+    x = d.add_function("divide", a, d.add_column(3, np.uint8))  # Float64
+    ex = d.compile()
+    assert ex.node_dtype(x) == np.float64
+    assert ex.precompile(out_nodes=[a] * 7, filter_node=a) > 1000
+    for outs, f in (([a], x), ([a] * 8, a)):
+        with pytest.raises(ch.ChgpuError) as ei:
+            ex.precompile(out_nodes=outs, filter_node=f)
+        assert ei.value.code == ch._capi.ERR_BAD_ARGUMENTS, (outs, f)
 
 
 # ------------------------------------------------------------------------------------------------------------------
