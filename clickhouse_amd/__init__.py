@@ -15,5 +15,6 @@ from .lowcardinality import like_compile, ColumnString, ColumnLowCardinality, Lo
 from .hashjoin import HashJoin, AsofJoin, join_probe_chain
 from .merging import AggregatedBlock, MergingAggregatedMemoryEfficientTransform
 from .keysfixed import KeyDict, KeysFixedAggregator, KeysFixedHashJoin, ColumnFixedString, FixedStringAggregator
+from .uniq import UniqExact
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -152,6 +152,14 @@ SIGNATURES = {
     "chgpu_keydict_key_column": (_i, [_vp, _vp, _u32, _i, _pp]),
     "chgpu_keydict_selector": (_i, [_vp, _vp, _u32, _pp]),
     "chgpu_keydict_free": (_i, [_vp]),
+    "chgpu_uniq_create": (_i, [_vp, _i, _i, _u64, _pp]),
+    "chgpu_uniq_add_block": (_i, [_vp, _vp, _vp, _u64, _u64, _vp]),
+    "chgpu_uniq_merge": (_i, [_vp, _vp]),
+    "chgpu_uniq_size": (_i, [_vp, _pu64]),
+    "chgpu_uniq_export_pairs": (_i, [_vp, _pp, _pp, _pu64]),
+    "chgpu_uniq_finalize": (_i, [_vp, _pp, _pp, _pu64]),
+    "chgpu_uniq_counts_for_keys": (_i, [_vp, _vp, _pp]),
+    "chgpu_uniq_free": (_i, [_vp]),
     "chgpu_comm_unique_id": (_i, [_vp]),
     "chgpu_comm_init": (_i, [_vp, _i, _i, _vp, _pp]),
     "chgpu_comm_destroy": (_i, [_vp]),

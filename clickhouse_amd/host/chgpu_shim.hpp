@@ -1068,6 +1068,72 @@ private:
     chgpu_agg * h = nullptr;
 };
 
+/// AggregateFunctionUniqExact / count(DISTINCT x) under GROUP BY: one exact set of (group key, value) pairs in HBM beside the
+/// GpuAggregator that holds the GROUP BY's other aggregates -- one GpuUniqExact per distinct-counted argument, each fed the same
+/// blocks.  key_type < 0: without key.
+class GpuUniqExact
+{
+public:
+    GpuUniqExact(ContextPtr ctx_, int key_type_, int value_type_, uint64_t size_hint = 0) : ctx(std::move(ctx_)), key_type(key_type_), value_type(value_type_)
+    {
+        check(chgpu_uniq_create(ctx->get(), key_type, value_type, size_hint, &h));
+    }
+    ~GpuUniqExact() { chgpu_uniq_free(h); }
+    GpuUniqExact(const GpuUniqExact &) = delete;
+
+    /// executeOnBlock for this one function: the rows of [row_begin, row_end) whose filter byte is non-zero enter the set.  The filter
+    /// column is WHERE, the -If condition and the negated null map and-ed into one UInt8 column (uniqExactIf, Nullable arguments).
+    void add(const Columns & columns, size_t row_begin, size_t row_end, std::optional<size_t> key_position, size_t value_position,
+             std::optional<size_t> filter_position = std::nullopt)
+    {
+        const chgpu_col * key = key_position ? columns.at(*key_position)->handle() : nullptr;
+        const chgpu_col * filt = filter_position ? columns.at(*filter_position)->handle() : nullptr;
+        check(chgpu_uniq_add_block(h, key, columns.at(value_position)->handle(), row_begin, row_end, filt));
+    }
+    /// set union; other stays valid
+    void merge(const GpuUniqExact & other) { check(chgpu_uniq_merge(h, other.h)); }
+    /// distinct pairs held
+    size_t size() const
+    {
+        uint64_t n = 0;
+        check(chgpu_uniq_size(h, &n));
+        return n;
+    }
+    /// final = true: [key column,] the UInt64 count of distinct values per key (without key: one row); final = false: the distinct
+    /// pairs themselves, [key column,] value column -- a peer takes them with add()
+    Chunk convertToBlock(bool final = true) const
+    {
+        chgpu_col * keys = nullptr;
+        chgpu_col * vals = nullptr;
+        uint64_t rows = 0;
+        if (final)
+            check(chgpu_uniq_finalize(h, &keys, &vals, &rows));
+        else
+            check(chgpu_uniq_export_pairs(h, &keys, &vals, &rows));
+        Chunk out;
+        out.num_rows = rows;
+        if (keys)
+            out.columns.push_back(std::make_shared<ColumnVector>(ctx, keys));
+        out.columns.push_back(std::make_shared<ColumnVector>(ctx, vals));
+        return out;
+    }
+    /// the uniqExact column of a GpuAggregator::convertToBlock chunk: keys = that chunk's key column; row i gets the distinct count of
+    /// keys[i], 0 for a group none of whose rows entered this set
+    ColumnPtr countsForKeys(const ColumnVector & keys) const
+    {
+        chgpu_col * counts = nullptr;
+        check(chgpu_uniq_counts_for_keys(h, keys.handle(), &counts));
+        return std::make_shared<ColumnVector>(ctx, counts);
+    }
+    int keyType() const { return key_type; }
+    int valueType() const { return value_type; }
+
+private:
+    ContextPtr ctx;
+    int key_type, value_type;
+    chgpu_uniq * h = nullptr;
+};
+
 /// ManyAggregatedData (AggregatingTransform.h:74-100): one AggregatedDataVariants per pipeline stream, shared by the streams'
 /// AggregatingTransforms; the stream that finishes LAST merges them (num_finished, AggregatingTransform.cpp:728-744).
 struct ManyAggregatedData

@@ -477,6 +477,40 @@ int chgpu_keydict_size(chgpu_keydict * dict, uint64_t * n_keys);
 int chgpu_keydict_key_column(chgpu_keydict * dict, const chgpu_col * ids_u32, uint32_t byte_offset, int type, chgpu_col ** out);
 int chgpu_keydict_selector(chgpu_keydict * dict, const chgpu_col * ids_u32, uint32_t num_shards, chgpu_col ** selector_u32);
 int chgpu_keydict_free(chgpu_keydict * dict);
+/* uniqExact(x) / count(DISTINCT x) under GROUP BY (AggregateFunctionUniqExact: a HashSet<T> per group; count_distinct_implementation =
+   uniqExact).  A chgpu_uniq is ONE exact set of (group key, value) pairs in HBM, beside the chgpu_agg that holds the GROUP BY's other
+   aggregates: one chgpu_uniq per distinct-counted argument.
+   Types: key_type is an integer type (zero-extended to the UInt64 table key as for chgpu_agg; ids of chgpu_keydict_* / chgpu_lc_remap /
+   the String dictionary and keys of chgpu_pack_fixed_keys are ordinary UInt32 / UInt64 keys), a float key answers
+   CHGPU_ERR_NOT_IMPLEMENTED, key_type < 0 is without key; value_type is any of the ten types.  Two values are equal when their bits are
+   (the HashSet cell's bitEquals): +0.0 and -0.0 are two values, NaNs with one payload are one, Float32 is compared as its 32 bits.
+   Every bit pattern is a legal key and a legal value.  size_hint: distinct pairs expected, 0 = unknown (the table grows).
+   chgpu_uniq_add_block: rows [row_begin, row_end) whose filter_u8 byte is non-zero enter (filter_u8 may be NULL: every row).  The filter
+   is WHERE, the -If condition and the negated null map in one byte (chgpu_and / chgpu_filter_description_nullable), so uniqExactIf and a
+   Nullable argument are this same call.  A group exists only through a row that entered.  key_col is ignored without key.
+   chgpu_uniq_merge: set union, src stays valid; both of one (key_type, value_type) and on one device.
+   chgpu_uniq_size: distinct pairs held.
+   chgpu_uniq_export_pairs: the not-final form -- every distinct pair once, as a key column and a value column of the set's types, order
+   unspecified; a peer merges them with chgpu_uniq_add_block, a sharded GROUP BY routes them with chgpu_partition_by_hash on the key
+   column.  Without key keys_out may be NULL (it receives NULL).
+   chgpu_uniq_finalize: one row per key that has a pair -- the key and the UInt64 count of its distinct values, order unspecified;
+   without key exactly one row (0 for the empty set; keys_out may be NULL).  May be called repeatedly and between blocks.
+   chgpu_uniq_counts_for_keys: for every row of `keys` (the set's key type) that key's distinct count, 0 for a key the set lacks: the
+   uniqExact column beside the columns of chgpu_agg_finalize, in that call's row order.
+   Errors: NULL handles and outputs, type mismatches, row_begin > row_end, a range past the column, sets of different types or devices ->
+   CHGPU_ERR_BAD_ARGUMENTS; columns of different lengths -> CHGPU_ERR_SIZES_MISMATCH; more than 2^31 distinct pairs ->
+   CHGPU_ERR_TOO_MANY_ROWS; after CHGPU_ERR_OOM the set holds exactly what it held before the call.  Empty inputs are not errors.
+   The reference's wire bytes (HashSet::write per group) are not produced. */
+typedef struct chgpu_uniq chgpu_uniq;
+int chgpu_uniq_create(chgpu_ctx * ctx, int key_type, int value_type, uint64_t size_hint, chgpu_uniq ** out);
+int chgpu_uniq_add_block(chgpu_uniq * uniq, const chgpu_col * key_col, const chgpu_col * value_col, uint64_t row_begin, uint64_t row_end,
+                         const chgpu_col * filter_u8);
+int chgpu_uniq_merge(chgpu_uniq * dst, const chgpu_uniq * src);
+int chgpu_uniq_size(chgpu_uniq * uniq, uint64_t * pairs);
+int chgpu_uniq_export_pairs(chgpu_uniq * uniq, chgpu_col ** keys_out, chgpu_col ** values_out, uint64_t * pairs);
+int chgpu_uniq_finalize(chgpu_uniq * uniq, chgpu_col ** keys_out, chgpu_col ** counts_u64, uint64_t * groups);
+int chgpu_uniq_counts_for_keys(chgpu_uniq * uniq, const chgpu_col * keys, chgpu_col ** counts_u64);
+int chgpu_uniq_free(chgpu_uniq * uniq);
 /* §8(f) rank 2 — LowCardinality keys (src/Columns/ColumnLowCardinality.h:27-69; low_cardinality_key* variants,
    AggregatedDataVariants.h:119-127; HashMethodSingleLowCardinalityColumn's per-position cache, ColumnsHashing.h:82-260).
    Every Block brings its own dictionary; the host resolves it against the query-wide dictionary into remap_u32[local position]
