@@ -16,5 +16,6 @@ from .hashjoin import HashJoin, AsofJoin, join_probe_chain
 from .merging import AggregatedBlock, MergingAggregatedMemoryEfficientTransform
 from .keysfixed import KeyDict, KeysFixedAggregator, KeysFixedHashJoin, ColumnFixedString, FixedStringAggregator
 from .uniq import UniqExact
+from .quantile import QuantileExact
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -27,6 +27,9 @@ N_COUNTERS = 8
 VAL_COL, VAL_MUL, VAL_PLUS, VAL_MINUS = 0, 1, 2, 3
 STR_LIKE, STR_CONTAINS, STR_STARTS_WITH, STR_ENDS_WITH = 0, 1, 2, 3
 STR_ROUTE_EQUALS, STR_ROUTE_STARTS_WITH, STR_ROUTE_ENDS_WITH, STR_ROUTE_CONTAINS, STR_ROUTE_GENERAL = 0, 1, 2, 3, 4
+QUANTILE_EXACT, QUANTILE_EXACT_LOW, QUANTILE_EXACT_HIGH = 0, 1, 2
+QUANTILE_EXACT_INCLUSIVE, QUANTILE_EXACT_EXCLUSIVE, QUANTILE_EXACT_WEIGHTED = 3, 4, 5   # reserved: NOT_IMPLEMENTED
+QUANTILE_MAX_LEVELS = 16
 STR_CONST_MAX = 256   # bytes of a string constant / LIKE pattern the kernels carry
 
 _vp, _i, _u32, _u64, _i64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_int64
@@ -160,6 +163,14 @@ SIGNATURES = {
     "chgpu_uniq_finalize": (_i, [_vp, _pp, _pp, _pu64]),
     "chgpu_uniq_counts_for_keys": (_i, [_vp, _vp, _pp]),
     "chgpu_uniq_free": (_i, [_vp]),
+    "chgpu_quantile_create": (_i, [_vp, _i, _i, _pp]),
+    "chgpu_quantile_add_block": (_i, [_vp, _vp, _vp, _u64, _u64, _vp]),
+    "chgpu_quantile_merge": (_i, [_vp, _vp]),
+    "chgpu_quantile_size": (_i, [_vp, _pu64]),
+    "chgpu_quantile_export_pairs": (_i, [_vp, _pp, _pp, _pu64]),
+    "chgpu_quantile_finalize": (_i, [_vp, _i, _u32, C.POINTER(C.c_double), _pp, _pp, _pu64]),
+    "chgpu_quantile_for_keys": (_i, [_vp, _i, _u32, C.POINTER(C.c_double), _vp, _pp]),
+    "chgpu_quantile_free": (_i, [_vp]),
     "chgpu_comm_unique_id": (_i, [_vp]),
     "chgpu_comm_init": (_i, [_vp, _i, _i, _vp, _pp]),
     "chgpu_comm_destroy": (_i, [_vp]),

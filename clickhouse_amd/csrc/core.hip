@@ -119,14 +119,15 @@ extern "C" int chgpu_ctx_synchronize(chgpu_ctx * ctx)
 static std::mutex g_opt_mu;
 static std::map<std::string, long long> g_opt_defaults;
 static const char * const CHGPU_OPTION_NAMES[] = {
-    "agg_no_partition", "debug", "deterministic_float_sums", "test_chain_grid", "test_keydict_chunk_rows", "test_keydict_weak_tags", "test_uniq_fail_growth",
+    "agg_no_partition", "debug", "deterministic_float_sums", "test_chain_grid", "test_keydict_chunk_rows", "test_keydict_weak_tags", "test_quantile_fail_alloc", "test_quantile_hist_budget",
+    "test_uniq_fail_growth",
     "tune_agg_lds_threads", "tune_agg_no_ranged", "tune_agg_ranged_s", "tune_cmp_wg", "tune_expr_wg", "tune_exprn_wg", "tune_fcount_wg",
     "tune_filter_no_multi", "tune_fs2_wg", "tune_fs_wg", "tune_fscatter_wg", "tune_gb_kib", "tune_gb_no_tiled",
     "tune_gb_no_word_passes", "tune_gb_no_two_level", "tune_gb_nocnt32", "tune_gb_noops", "tune_gb_nowide", "tune_gb_s", "tune_gb_tile",
     "tune_gb_unitdiv", "tune_jit_unroll", "tune_jit_wg_map", "tune_jit_wg_sum", "tune_join_cap_shift", "tune_join_eager_build",
     "tune_join_lds_min_rows", "tune_join_no_dense_prefilter", "tune_join_no_fused_payload", "tune_join_no_lds_filter",
     "tune_join_no_lds_probe", "tune_join_no_prefilter", "tune_join_no_dense_map", "tune_join_no_radix",
-    "tune_join_no_regions", "tune_join_no_slice_build", "tune_join_region_kib", "tune_join_region_min_rows", "tune_str_contains_general",
+    "tune_join_no_regions", "tune_join_no_slice_build", "tune_join_region_kib", "tune_join_region_min_rows", "tune_quantile_hist_rounds", "tune_quantile_no_lds_scatter", "tune_str_contains_general",
 };
 
 long long chgpu_opt(const chgpu_ctx * ctx, const char * name, long long dflt)

@@ -24,6 +24,7 @@
 //   grows the table (x4 to 2^23 cells, then x2), rebuilds the cells from the store and runs the pending rows again (k_uq_insert_pending).
 #include "chgpu_internal.h"
 
+#include "group_table.h"
 #include "uniq_host.h"
 
 typedef unsigned long long ull;
@@ -476,43 +477,20 @@ __global__ void k_uq_set_u64(u64 * out, u64 v)
     out[0] = v;
 }
 
-// counts_for_keys: a table over the finalised groups, cell = group index + 1 (the group keys are distinct: first empty cell)
+// counts_for_keys: a table over the finalised groups (group_table.h)
 __global__ __launch_bounds__(UQ_T) void k_uq_kc_build(const u64 * __restrict__ gkeys, u64 groups, u32 * __restrict__ cells, u64 cap)
 {
-    const u64 mask = cap - 1;
     for (u64 g = (u64)blockIdx.x * UQ_T + threadIdx.x; g < groups; g += (u64)gridDim.x * UQ_T)
-    {
-        u64 pos = dev_intHash64(gkeys[g]) & mask;
-        for (u64 step = 0; step <= cap; ++step)
-        {
-            if (cells[pos] == 0 && atomicCAS(&cells[pos], 0u, (u32)g + 1) == 0)
-                break;
-            pos = (pos + 1) & mask;
-        }
-    }
+        gt_insert(gkeys, g, cells, cap);
 }
 
 __global__ __launch_bounds__(UQ_T) void k_uq_kc_lookup(const u64 * __restrict__ gkeys, const u64 * __restrict__ gcounts, const u32 * __restrict__ cells, u64 cap,
                                                        const void * __restrict__ keys, u32 key_size, u64 n, u64 * __restrict__ out)
 {
-    const u64 mask = cap - 1;
     for (u64 i = (u64)blockIdx.x * UQ_T + threadIdx.x; i < n; i += (u64)gridDim.x * UQ_T)
     {
-        const u64 key = uq_load(keys, key_size, i);
-        u64 pos = dev_intHash64(key) & mask, count = 0;
-        for (u64 step = 0; step <= cap; ++step)
-        {
-            const u32 c = cells[pos];
-            if (c == 0)
-                break;
-            if (gkeys[c - 1] == key)
-            {
-                count = gcounts[c - 1];
-                break;
-            }
-            pos = (pos + 1) & mask;
-        }
-        out[i] = count;
+        const u32 g = gt_find(gkeys, cells, cap, uq_load(keys, key_size, i));
+        out[i] = g == GT_NONE ? 0 : gcounts[g];
     }
 }
 
@@ -844,9 +822,7 @@ static int uq_key_table(chgpu_uniq * d)
     chgpu_ctx * ctx = d->ctx;
     const u64 groups = d->fin_groups;
     CHGPU_REQUIRE(groups < 0xFFFFFFFFull, CHGPU_ERR_TOO_MANY_ROWS, "uniq: more than 2^32 - 2 groups");
-    u64 cap = 64;
-    while (cap < 2 * groups)
-        cap *= 2;
+    const u64 cap = gt_capacity_for(groups);
     UqMem kc;
     CHGPU_TRY(chgpu_pool_alloc(ctx, cap * 4, &kc.p, &kc.cls));
     int rc = CHGPU_OK;

@@ -1134,6 +1134,85 @@ private:
     chgpu_uniq * h = nullptr;
 };
 
+/// AggregateFunctionQuantile<..., QuantileExact<...>> (quantileExact, quantilesExact, medianExact and the Low / High forms) under
+/// GROUP BY: the multiset of (group key, value) pairs in HBM beside the GpuAggregator that holds the GROUP BY's other aggregates -- one
+/// GpuQuantileExact per argument, each fed the same blocks.  Levels and kind are given when the result is taken, so one state serves
+/// quantileExact(0.5) and quantilesExactHigh(0.9, 0.99) of the same argument.  key_type < 0: without key.
+class GpuQuantileExact
+{
+public:
+    GpuQuantileExact(ContextPtr ctx_, int key_type_, int value_type_) : ctx(std::move(ctx_)), key_type(key_type_), value_type(value_type_)
+    {
+        check(chgpu_quantile_create(ctx->get(), key_type, value_type, &h));
+    }
+    ~GpuQuantileExact() { chgpu_quantile_free(h); }
+    GpuQuantileExact(const GpuQuantileExact &) = delete;
+
+    /// executeOnBlock for this one function: the rows of [row_begin, row_end) whose filter byte is non-zero and whose value is not NaN
+    /// enter.  The filter column is WHERE, the -If condition and the negated null map and-ed into one UInt8 column.
+    void add(const Columns & columns, size_t row_begin, size_t row_end, std::optional<size_t> key_position, size_t value_position,
+             std::optional<size_t> filter_position = std::nullopt)
+    {
+        const chgpu_col * key = key_position ? columns.at(*key_position)->handle() : nullptr;
+        const chgpu_col * filt = filter_position ? columns.at(*filter_position)->handle() : nullptr;
+        check(chgpu_quantile_add_block(h, key, columns.at(value_position)->handle(), row_begin, row_end, filt));
+    }
+    /// multiset union; other stays valid
+    void merge(const GpuQuantileExact & other) { check(chgpu_quantile_merge(h, other.h)); }
+    /// values held, all groups
+    size_t size() const
+    {
+        uint64_t n = 0;
+        check(chgpu_quantile_size(h, &n));
+        return n;
+    }
+    /// final = true: [key column,] one column of the value type per level (without key: one row); final = false: the held values
+    /// themselves, [key column,] value column -- a peer takes them with add() (levels and kind are not looked at)
+    Chunk convertToBlock(const std::vector<double> & levels, int kind = CHGPU_QUANTILE_EXACT, bool final = true) const
+    {
+        chgpu_col * keys = nullptr;
+        uint64_t rows = 0;
+        Chunk out;
+        if (final)
+        {
+            std::vector<chgpu_col *> res(levels.size() ? levels.size() : 1, nullptr);
+            check(chgpu_quantile_finalize(h, kind, static_cast<uint32_t>(levels.size()), levels.data(), &keys, res.data(), &rows));
+            if (keys)
+                out.columns.push_back(std::make_shared<ColumnVector>(ctx, keys));
+            for (size_t i = 0; i < levels.size(); ++i)
+                out.columns.push_back(std::make_shared<ColumnVector>(ctx, res[i]));
+        }
+        else
+        {
+            chgpu_col * vals = nullptr;
+            check(chgpu_quantile_export_pairs(h, &keys, &vals, &rows));
+            if (keys)
+                out.columns.push_back(std::make_shared<ColumnVector>(ctx, keys));
+            out.columns.push_back(std::make_shared<ColumnVector>(ctx, vals));
+        }
+        out.num_rows = rows;
+        return out;
+    }
+    /// the quantile columns of a GpuAggregator::convertToBlock chunk: keys = that chunk's key column; row i of column l gets the answer
+    /// of keys[i] for levels[l], the empty-state value (NaN / 0) for a group none of whose rows entered
+    Columns quantilesForKeys(const ColumnVector & keys, const std::vector<double> & levels, int kind = CHGPU_QUANTILE_EXACT) const
+    {
+        std::vector<chgpu_col *> res(levels.size() ? levels.size() : 1, nullptr);
+        check(chgpu_quantile_for_keys(h, kind, static_cast<uint32_t>(levels.size()), levels.data(), keys.handle(), res.data()));
+        Columns out;
+        for (size_t i = 0; i < levels.size(); ++i)
+            out.push_back(std::make_shared<ColumnVector>(ctx, res[i]));
+        return out;
+    }
+    int keyType() const { return key_type; }
+    int valueType() const { return value_type; }
+
+private:
+    ContextPtr ctx;
+    int key_type, value_type;
+    chgpu_quantile * h = nullptr;
+};
+
 /// ManyAggregatedData (AggregatingTransform.h:74-100): one AggregatedDataVariants per pipeline stream, shared by the streams'
 /// AggregatingTransforms; the stream that finishes LAST merges them (num_finished, AggregatingTransform.cpp:728-744).
 struct ManyAggregatedData

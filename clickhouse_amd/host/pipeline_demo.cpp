@@ -232,6 +232,32 @@ int main(int argc, char ** argv)
             REQUIRE(static_cast<uint64_t>(gs[i]) == it->second.first && gc[i] == it->second.second);
         }
 
+        // ---- SELECT k, ..., quantilesExact(0.5, 0.9)(a) GROUP BY k: the quantile columns beside the aggregator's chunk ------
+        {
+            GpuQuantileExact qa(ctx, CHGPU_U32, CHGPU_I64);
+            qa.add(stripe.columns, 0, n, std::optional<size_t>(1), 0);
+            REQUIRE(qa.size() == n);
+            const std::vector<double> levels{0.5, 0.9};
+            Columns qcols = qa.quantilesForKeys(*r1.columns[0], levels);
+            REQUIRE(qcols.size() == 2);
+            std::map<uint32_t, std::vector<int64_t>> per_key;
+            for (size_t i = 0; i < n; ++i)
+                per_key[k[i]].push_back(a[i]);
+            for (size_t l = 0; l < levels.size(); ++l)
+            {
+                auto got = qcols[l]->getData<int64_t>();
+                REQUIRE(got.size() == gk.size());
+                for (size_t i = 0; i < gk.size(); ++i)
+                {
+                    std::vector<int64_t> & v = per_key[gk[i]];
+                    const size_t r = static_cast<size_t>(levels[l] * static_cast<double>(v.size()));
+                    std::nth_element(v.begin(), v.begin() + r, v.end());
+                    REQUIRE(got[i] == v[r]);
+                }
+            }
+            REQUIRE(qa.convertToBlock(levels).num_rows == want.size());
+        }
+
         // ---- SELECT pk, bv FROM probe ALL INNER JOIN build ON pk = bk -----------------------------------------
         const size_t nb = 50000;
         std::vector<uint64_t> bk(nb);

@@ -511,6 +511,48 @@ int chgpu_uniq_export_pairs(chgpu_uniq * uniq, chgpu_col ** keys_out, chgpu_col 
 int chgpu_uniq_finalize(chgpu_uniq * uniq, chgpu_col ** keys_out, chgpu_col ** counts_u64, uint64_t * groups);
 int chgpu_uniq_counts_for_keys(chgpu_uniq * uniq, const chgpu_col * keys, chgpu_col ** counts_u64);
 int chgpu_uniq_free(chgpu_uniq * uniq);
+/* quantileExact / quantilesExact / medianExact and their Low / High forms under GROUP BY (AggregateFunctionQuantile over QuantileExact:
+   an array of the values per group, push_back at add, nth_element at the end).  A chgpu_quantile holds the multiset of (group key,
+   value) pairs in one flat append-only store in HBM, beside the chgpu_agg that holds the GROUP BY's other aggregates: one per argument.
+   Adding a block is a filtered copy; finalising scatters the values into per-group segments and selects the requested ranks (short
+   segments sorted in LDS, long ones by byte-wise histogram passes).  Levels and kind belong to finalize / for_keys: one state serves
+   any of them, repeatedly and between blocks.
+   Types: keys as for chgpu_uniq (integer types, zero-extended; a float key answers CHGPU_ERR_NOT_IMPLEMENTED; key_type < 0 is without
+   key); value_type is any of the ten types.
+   What enters: a row of [row_begin, row_end) whose filter_u8 byte is non-zero (NULL: every row) and whose value is not NaN.  +-inf,
+   denormals and -0.0 are ordinary values.  A group exists only through a row that entered.
+   Rank: for a level l in [0, 1] and a group of n >= 1 values the answer is the element of 0-based rank r in ascending order:
+     CHGPU_QUANTILE_EXACT       r = l < 1 ? (uint64_t)(l * (double)n) : n - 1        (one IEEE double product, truncated)
+     CHGPU_QUANTILE_EXACT_LOW   l == 0.5: r = n odd ? n / 2 : n / 2 - 1; else as EXACT
+     CHGPU_QUANTILE_EXACT_HIGH  l == 0.5: r = n / 2; else as EXACT
+   The result has the value's type and is one of the group's elements bit for bit; the order is numeric with -0.0 directly before +0.0.
+   An empty state (a key the operator lacks in for_keys, the without-key operator with no value) gives quiet NaN for floats, 0 for
+   integers.  The reserved kinds (Inclusive, Exclusive, Weighted) answer CHGPU_ERR_NOT_IMPLEMENTED.
+   chgpu_quantile_merge: multiset union, src stays valid.  chgpu_quantile_size: values held, all groups.
+   chgpu_quantile_export_pairs: the not-final form -- every held value with its key, order unspecified; a peer takes them with
+   chgpu_quantile_add_block, a sharded GROUP BY routes them with chgpu_partition_by_hash.  Without key keys_out may be NULL.
+   chgpu_quantile_finalize: one row per key that holds a value, order unspecified, res_cols[i] answers levels[i]; without key exactly
+   one row (keys_out may be NULL).  chgpu_quantile_for_keys: for every row of `keys` that key's quantiles: the columns beside those of
+   chgpu_agg_finalize, in that call's row order.
+   Errors: NULL handles and outputs, type mismatches, row_begin > row_end, a range past the column, n_levels == 0 or above
+   CHGPU_QUANTILE_MAX_LEVELS, a level outside [0, 1] or NaN, operators of different types or devices -> CHGPU_ERR_BAD_ARGUMENTS; columns
+   of different lengths -> CHGPU_ERR_SIZES_MISMATCH; 2^32 - 1 values or more -> CHGPU_ERR_TOO_MANY_ROWS; after CHGPU_ERR_OOM the state
+   holds exactly what it held before the call.  Empty inputs are not errors.  The reference's wire bytes are not produced. */
+enum { CHGPU_QUANTILE_EXACT = 0, CHGPU_QUANTILE_EXACT_LOW = 1, CHGPU_QUANTILE_EXACT_HIGH = 2,
+       CHGPU_QUANTILE_EXACT_INCLUSIVE = 3, CHGPU_QUANTILE_EXACT_EXCLUSIVE = 4, CHGPU_QUANTILE_EXACT_WEIGHTED = 5 /* 3..5: reserved */ };
+#define CHGPU_QUANTILE_MAX_LEVELS 16
+typedef struct chgpu_quantile chgpu_quantile;
+int chgpu_quantile_create(chgpu_ctx * ctx, int key_type, int value_type, chgpu_quantile ** out);
+int chgpu_quantile_add_block(chgpu_quantile * quantile, const chgpu_col * key_col, const chgpu_col * value_col, uint64_t row_begin, uint64_t row_end,
+                             const chgpu_col * filter_u8);
+int chgpu_quantile_merge(chgpu_quantile * dst, const chgpu_quantile * src);
+int chgpu_quantile_size(chgpu_quantile * quantile, uint64_t * values);
+int chgpu_quantile_export_pairs(chgpu_quantile * quantile, chgpu_col ** keys_out, chgpu_col ** values_out, uint64_t * rows);
+int chgpu_quantile_finalize(chgpu_quantile * quantile, int kind, uint32_t n_levels, const double * levels, chgpu_col ** keys_out,
+                            chgpu_col ** res_cols, uint64_t * groups);
+int chgpu_quantile_for_keys(chgpu_quantile * quantile, int kind, uint32_t n_levels, const double * levels, const chgpu_col * keys,
+                            chgpu_col ** res_cols);
+int chgpu_quantile_free(chgpu_quantile * quantile);
 /* §8(f) rank 2 — LowCardinality keys (src/Columns/ColumnLowCardinality.h:27-69; low_cardinality_key* variants,
    AggregatedDataVariants.h:119-127; HashMethodSingleLowCardinalityColumn's per-position cache, ColumnsHashing.h:82-260).
    Every Block brings its own dictionary; the host resolves it against the query-wide dictionary into remap_u32[local position]
