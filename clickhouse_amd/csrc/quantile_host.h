@@ -8,6 +8,7 @@
 #include <cstdio>
 
 #include "../../include/chgpu.h"
+#include "pair_host.h"
 
 #ifdef __HIPCC__
 #define QT_HD __host__ __device__ __forceinline__
@@ -157,33 +158,6 @@ static inline int qt_check_levels(int kind, uint32_t n_levels, const double * le
             *msg = "a level outside [0, 1]";
             return CHGPU_ERR_BAD_ARGUMENTS;
         }
-    return CHGPU_OK;
-}
-
-// The row-range and length checks of chgpu_quantile_add_block (those of chgpu_uniq_add_block).  key_rows < 0: without key;
-// filter_rows < 0: no filter.
-static inline int qt_check_rows(int64_t key_rows, uint64_t value_rows, int64_t filter_rows, uint64_t row_begin, uint64_t row_end, const char ** msg)
-{
-    if (key_rows >= 0 && (uint64_t)key_rows != value_rows)
-    {
-        *msg = "key and value columns of different lengths";
-        return CHGPU_ERR_SIZES_MISMATCH;
-    }
-    if (filter_rows >= 0 && (uint64_t)filter_rows != value_rows)
-    {
-        *msg = "filter and value columns of different lengths";
-        return CHGPU_ERR_SIZES_MISMATCH;
-    }
-    if (row_begin > row_end)
-    {
-        *msg = "row_begin > row_end";
-        return CHGPU_ERR_BAD_ARGUMENTS;
-    }
-    if (row_end > value_rows)
-    {
-        *msg = "row range past the end of the column";
-        return CHGPU_ERR_BAD_ARGUMENTS;
-    }
     return CHGPU_OK;
 }
 

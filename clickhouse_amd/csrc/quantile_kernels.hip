@@ -18,9 +18,11 @@
 //            of the values that match the prefix fixed so far (k_qt_hist, 256 counters per level in LDS, then added to the segment's
 //            global counters); one wave per (segment, level) scans the 256 counters, fixes the byte, reduces the rank and clears them
 //            (k_qt_narrow).  No host synchronisation between passes; after the last byte the prefix is the answer.
+// What this operator shares with uniq_kernels.hip (element load, pool memory, entry checks, the groups of the store's keys, the
+// key -> group table) is pair_store.h / group_table.h.
 #include "chgpu_internal.h"
 
-#include "group_table.h"
+#include "pair_store.h"
 #include "quantile_host.h"
 
 typedef unsigned long long ull;
@@ -52,18 +54,6 @@ struct QtLarge
     u32 g;
     u64 unit0;
 };
-
-// raw bits of element i of a key column, zero-extended
-__device__ __forceinline__ u64 qt_load_key(const void * p, u32 size, u64 i)
-{
-    switch (size)
-    {
-        case 1: return ((const u8 *)p)[i];
-        case 2: return ((const u16 *)p)[i];
-        case 4: return ((const u32 *)p)[i];
-        default: return ((const u64 *)p)[i];
-    }
-}
 
 __global__ void k_qt_ctrl_reset(QtCtrl * c, u32 held)
 {
@@ -131,7 +121,7 @@ __global__ __launch_bounds__(QT_T) void k_qt_append(const void * __restrict__ ke
                 if (pos < cap) // never past the store (the host reserved held + n)
                 {
                     if (key_size)
-                        out_k[pos] = qt_load_key(key, key_size, row_begin + b + (u64)r * QT_T + tid);
+                        out_k[pos] = pair_load(key, key_size, row_begin + b + (u64)r * QT_T + tid);
                     out_v[pos] = (T)qt_encode(v[r], sizeof(T), mode);
                     entered += 1;
                 }
@@ -149,14 +139,7 @@ __global__ __launch_bounds__(QT_T) void k_qt_append(const void * __restrict__ ke
     }
 }
 
-// export_pairs: keys back to the key type, values decoded
-template <typename K>
-__global__ __launch_bounds__(QT_T) void k_qt_export_keys(const u64 * __restrict__ in, u64 n, K * __restrict__ out)
-{
-    for (u64 i = (u64)blockIdx.x * QT_T + threadIdx.x; i < n; i += (u64)gridDim.x * QT_T)
-        out[i] = (K)in[i];
-}
-
+// export_pairs: values decoded (the keys go back to the key type through pair_narrow)
 template <typename T>
 __global__ __launch_bounds__(QT_T) void k_qt_export_values(const T * __restrict__ in, u64 n, int mode, T * __restrict__ out)
 {
@@ -170,11 +153,6 @@ __global__ __launch_bounds__(QT_T) void k_qt_fill(QtOut out, u32 n_levels, u64 n
     for (u64 i = (u64)blockIdx.x * QT_T + threadIdx.x; i < n; i += (u64)gridDim.x * QT_T)
         for (u32 l = 0; l < n_levels; ++l)
             ((T *)out.p[l])[i] = v;
-}
-
-__global__ void k_qt_set_u64(u64 * out, u64 v)
-{
-    out[0] = v;
 }
 
 // per group: the 32-bit count, whether the segment is large, its work units
@@ -205,12 +183,6 @@ __global__ __launch_bounds__(QT_T) void k_qt_large_list(const u32 * __restrict__
             s.unit0 = uoff[g];
             out[lidx[g]] = s;
         }
-}
-
-__global__ __launch_bounds__(QT_T) void k_qt_table_build(const u64 * __restrict__ gkeys, u64 groups, u32 * __restrict__ cells, u64 cap)
-{
-    for (u64 g = (u64)blockIdx.x * QT_T + threadIdx.x; g < groups; g += (u64)gridDim.x * QT_T)
-        gt_insert(gkeys, g, cells, cap);
 }
 
 // Every stored value to offsets[g] + cursor[g]++ of the segment array.  Lanes of a wave that hold the leader's group take their places
@@ -593,7 +565,7 @@ __global__ __launch_bounds__(QT_T) void k_qt_gather(const u64 * __restrict__ gke
 {
     for (u64 i = (u64)blockIdx.x * QT_T + threadIdx.x; i < n; i += (u64)gridDim.x * QT_T)
     {
-        const u32 g = gt_find(gkeys, cells, cap, qt_load_key(keys, key_size, i));
+        const u32 g = gt_find(gkeys, cells, cap, pair_load(keys, key_size, i));
         for (u32 l = 0; l < n_levels; ++l)
             ((T *)out.p[l])[i] = g == GT_NONE ? empty : ((const T *)res.p[l])[g];
     }
@@ -602,11 +574,7 @@ __global__ __launch_bounds__(QT_T) void k_qt_gather(const u64 * __restrict__ gke
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-struct QtMem
-{
-    void * p = nullptr;
-    size_t cls = 0;
-};
+static constexpr PairNames QT_NAMES{"quantile", "operator", "an operator"};
 
 // what finalize computed from the store, kept until the store changes
 struct QtFinal
@@ -614,33 +582,23 @@ struct QtFinal
     bool valid = false;
     u64 groups = 0, values = 0, small = 0, large = 0, units = 0;
     chgpu_col * gkeys = nullptr; // UInt64 group keys (keyed operators)
-    QtMem counts;                // u32[groups]
-    QtMem offsets;               // u64[groups + 1]
-    QtMem cells;                 // key -> group table
+    PairMem counts;                // u32[groups]
+    PairMem offsets;               // u64[groups + 1]
+    PairMem cells;                 // key -> group table
     u64 cells_cap = 0;
-    QtMem seg;                   // the segment array (keyed operators; without key the store's values are the one segment)
-    QtMem lseg;                  // QtLarge[large]
+    PairMem seg;                   // the segment array (keyed operators; without key the store's values are the one segment)
+    PairMem lseg;                  // QtLarge[large]
 };
 
-struct chgpu_quantile
+struct chgpu_quantile : PairOp
 {
-    chgpu_ctx * ctx = nullptr;
-    int key_type = -1; // < 0: without key
-    int value_type = 0;
     u32 width = 0;
     int mode = 0;
     u64 held = 0, cap = 0;
-    QtMem k_mem, v_mem, ctrl_mem;
+    PairMem k_mem, v_mem, ctrl_mem;
     QtFinal fin;
     long long fail_alloc = 0, alloc_seq = 0; // test hook: allocation number fail_alloc of a call answers OOM
 };
-
-static void qt_free_mem(chgpu_ctx * ctx, QtMem & m)
-{
-    if (m.p)
-        chgpu_pool_free(ctx, m.p, m.cls);
-    m = QtMem{};
-}
 
 static void qt_begin_call(chgpu_quantile * d)
 {
@@ -654,7 +612,7 @@ static bool qt_refused(chgpu_quantile * d)
     return d->fail_alloc && d->alloc_seq == d->fail_alloc;
 }
 
-static int qt_alloc(chgpu_quantile * d, size_t bytes, QtMem * m)
+static int qt_alloc(chgpu_quantile * d, size_t bytes, PairMem * m)
 {
     if (qt_refused(d))
         return chgpu_set_error(CHGPU_ERR_OOM, "quantile: allocation %lld refused (test_quantile_fail_alloc)", d->alloc_seq);
@@ -672,29 +630,12 @@ static void qt_drop_final(chgpu_quantile * d)
 {
     QtFinal & f = d->fin;
     if (f.gkeys) chgpu_col_free(f.gkeys);
-    qt_free_mem(d->ctx, f.counts);
-    qt_free_mem(d->ctx, f.offsets);
-    qt_free_mem(d->ctx, f.cells);
-    qt_free_mem(d->ctx, f.seg);
-    qt_free_mem(d->ctx, f.lseg);
+    pair_free_mem(d->ctx, f.counts);
+    pair_free_mem(d->ctx, f.offsets);
+    pair_free_mem(d->ctx, f.cells);
+    pair_free_mem(d->ctx, f.seg);
+    pair_free_mem(d->ctx, f.lseg);
     f = QtFinal{};
-}
-
-static int qt_launch_ok(const char * what)
-{
-    if (hipGetLastError() != hipSuccess)
-        return chgpu_set_error(CHGPU_ERR_DEVICE, "quantile: %s launch failed", what);
-    return CHGPU_OK;
-}
-
-static chgpu_col qt_view(chgpu_ctx * ctx, int type, void * data, u64 rows)
-{
-    chgpu_col v;
-    v.ctx = ctx;
-    v.type = type;
-    v.rows = rows;
-    v.data = data;
-    return v;
 }
 
 static u32 qt_grid(chgpu_ctx * ctx, u64 items) { return chgpu_grid_for(ctx, items, QT_T, 8); }
@@ -708,7 +649,7 @@ static int qt_reserve(chgpu_quantile * d, u64 need)
     chgpu_ctx * ctx = d->ctx;
     const bool keyed = d->key_type >= 0;
     const u64 cap = qt_capacity_for(need);
-    QtMem k, v;
+    PairMem k, v;
     int rc = keyed ? qt_alloc(d, cap * 8, &k) : CHGPU_OK;
     if (rc == CHGPU_OK)
         rc = qt_alloc(d, cap * d->width, &v);
@@ -722,36 +663,22 @@ static int qt_reserve(chgpu_quantile * d, u64 need)
     }
     if (rc != CHGPU_OK)
     {
-        qt_free_mem(ctx, k);
-        qt_free_mem(ctx, v);
+        pair_free_mem(ctx, k);
+        pair_free_mem(ctx, v);
         return rc;
     }
-    qt_free_mem(ctx, d->k_mem); // reuse is ordered behind the copies above (same stream)
-    qt_free_mem(ctx, d->v_mem);
+    pair_free_mem(ctx, d->k_mem); // reuse is ordered behind the copies above (same stream)
+    pair_free_mem(ctx, d->v_mem);
     d->k_mem = k;
     d->v_mem = v;
     d->cap = cap;
     return CHGPU_OK;
 }
 
-static void qt_print_add(chgpu_quantile * d, const QtAddPlan & plan)
-{
-    if (chgpu_opt(d->ctx, "debug", 0) == 0)
-        return;
-    char line[256];
-    qt_format_add_plan(line, sizeof(line), plan);
-    fprintf(stderr, "%s\n", line);
-}
-
 extern "C" int chgpu_quantile_create(chgpu_ctx * ctx, int key_type, int value_type, chgpu_quantile ** out)
 {
     CHGPU_REQUIRE(ctx && out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    if (key_type >= 0)
-    {
-        CHGPU_REQUIRE(chgpu_type_size(key_type) != 0, CHGPU_ERR_BAD_ARGUMENTS, "quantile: unknown key type %d", key_type);
-        CHGPU_REQUIRE(chgpu_type_is_int(key_type), CHGPU_ERR_NOT_IMPLEMENTED, "quantile: key type %d: integer keys only (CPU path)", key_type);
-    }
-    CHGPU_REQUIRE(chgpu_type_size(value_type) != 0, CHGPU_ERR_BAD_ARGUMENTS, "quantile: unknown value type %d", value_type);
+    CHGPU_TRY(pair_check_create(QT_NAMES, key_type, value_type));
     ChgpuDeviceGuard guard(ctx);
     chgpu_quantile * d = new chgpu_quantile();
     d->ctx = ctx;
@@ -776,9 +703,9 @@ extern "C" int chgpu_quantile_free(chgpu_quantile * d)
         return CHGPU_OK;
     ChgpuDeviceGuard guard(d->ctx);
     qt_drop_final(d);
-    qt_free_mem(d->ctx, d->k_mem);
-    qt_free_mem(d->ctx, d->v_mem);
-    qt_free_mem(d->ctx, d->ctrl_mem);
+    pair_free_mem(d->ctx, d->k_mem);
+    pair_free_mem(d->ctx, d->v_mem);
+    pair_free_mem(d->ctx, d->ctrl_mem);
     chgpu_ctx * ctx = d->ctx;
     delete d;
     chgpu_ctx_release(ctx);
@@ -789,18 +716,9 @@ extern "C" int chgpu_quantile_add_block(chgpu_quantile * d, const chgpu_col * ke
                                         const chgpu_col * filter_u8)
 {
     CHGPU_REQUIRE(d && value_col, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_TRY(pair_check_add_block(QT_NAMES, *d, key_col, value_col, row_begin, row_end, filter_u8));
     const bool keyed = d->key_type >= 0;
-    CHGPU_REQUIRE(!keyed || key_col, CHGPU_ERR_BAD_ARGUMENTS, "NULL key column");
-    CHGPU_REQUIRE(!keyed || key_col->type == d->key_type, CHGPU_ERR_BAD_ARGUMENTS, "quantile: key column of type %d, the operator was made for %d", key_col->type, d->key_type);
-    CHGPU_REQUIRE(value_col->type == d->value_type, CHGPU_ERR_BAD_ARGUMENTS, "quantile: value column of type %d, the operator was made for %d", value_col->type,
-                  d->value_type);
-    CHGPU_REQUIRE(!filter_u8 || filter_u8->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "quantile: the filter must be UInt8");
     chgpu_ctx * ctx = d->ctx;
-    CHGPU_REQUIRE(value_col->ctx->device == ctx->device && (!keyed || key_col->ctx->device == ctx->device) && (!filter_u8 || filter_u8->ctx->device == ctx->device),
-                  CHGPU_ERR_BAD_ARGUMENTS, "quantile: a column lives on another device than the operator");
-    const char * msg = "";
-    const int code = qt_check_rows(keyed ? (int64_t)key_col->rows : -1, value_col->rows, filter_u8 ? (int64_t)filter_u8->rows : -1, row_begin, row_end, &msg);
-    CHGPU_REQUIRE(code == CHGPU_OK, code, "quantile: %s", msg);
     ChgpuDeviceGuard guard(ctx);
     qt_begin_call(d);
     const u64 n = row_end - row_begin;
@@ -820,7 +738,7 @@ extern "C" int chgpu_quantile_add_block(chgpu_quantile * d, const chgpu_col * ke
                                d->cap, ctrl);
         });
         ctx->counters[6] += 2;
-        rc = qt_launch_ok("append");
+        rc = pair_launch_ok(QT_NAMES, "append");
         QtCtrl c{};
         if (rc == CHGPU_OK)
             rc = chgpu_read_back(ctx, ctrl, &c, sizeof(c)); // the one blocking read of the call
@@ -835,16 +753,14 @@ extern "C" int chgpu_quantile_add_block(chgpu_quantile * d, const chgpu_col * ke
     }
     plan.held = d->held;
     plan.rc = rc;
-    qt_print_add(d, plan);
+    pair_print_plan(ctx, qt_format_add_plan, plan);
     return rc;
 }
 
 extern "C" int chgpu_quantile_merge(chgpu_quantile * dst, const chgpu_quantile * src)
 {
     CHGPU_REQUIRE(dst && src, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(dst->key_type == src->key_type && dst->value_type == src->value_type, CHGPU_ERR_BAD_ARGUMENTS,
-                  "quantile: merging an operator of (%d, %d) into one of (%d, %d)", src->key_type, src->value_type, dst->key_type, dst->value_type);
-    CHGPU_REQUIRE(dst->ctx->device == src->ctx->device, CHGPU_ERR_BAD_ARGUMENTS, "quantile: the operators live on different devices");
+    CHGPU_TRY(pair_check_merge(QT_NAMES, *dst, *src));
     chgpu_ctx * ctx = dst->ctx;
     ChgpuDeviceGuard guard(ctx);
     qt_begin_call(dst);
@@ -880,7 +796,7 @@ extern "C" int chgpu_quantile_merge(chgpu_quantile * dst, const chgpu_quantile *
     }
     plan.held = dst->held;
     plan.rc = rc;
-    qt_print_add(dst, plan);
+    pair_print_plan(ctx, qt_format_add_plan, plan);
     return rc;
 }
 
@@ -908,16 +824,13 @@ extern "C" int chgpu_quantile_export_pairs(chgpu_quantile * d, chgpu_col ** keys
     {
         const dim3 grid(qt_grid(ctx, d->held)), block(QT_T);
         if (keyed)
-            dispatch_width(chgpu_type_size(d->key_type), [&](auto tag) {
-                typedef decltype(tag) K;
-                hipLaunchKernelGGL(k_qt_export_keys<K>, grid, block, 0, ctx->stream, (const u64 *)d->k_mem.p, d->held, (K *)k->data);
-            });
+            pair_narrow(ctx, (const u64 *)d->k_mem.p, d->held, k);
         dispatch_width(d->width, [&](auto tag) {
             typedef decltype(tag) T;
             hipLaunchKernelGGL(k_qt_export_values<T>, grid, block, 0, ctx->stream, (const T *)d->v_mem.p, d->held, d->mode, (T *)v->data);
         });
         ctx->counters[6] += 2;
-        rc = qt_launch_ok("export");
+        rc = pair_launch_ok(QT_NAMES, "export");
     }
     if (rc != CHGPU_OK)
     {
@@ -936,40 +849,22 @@ extern "C" int chgpu_quantile_export_pairs(chgpu_quantile * d, chgpu_col ** keys
 struct QtTemps
 {
     chgpu_quantile * d;
-    std::vector<QtMem> mems;
+    std::vector<PairMem> mems;
     explicit QtTemps(chgpu_quantile * d_) : d(d_) {}
     ~QtTemps()
     {
-        for (QtMem & m : mems)
-            qt_free_mem(d->ctx, m);
+        for (PairMem & m : mems)
+            pair_free_mem(d->ctx, m);
     }
     int alloc(size_t bytes, void ** out)
     {
-        QtMem m;
+        PairMem m;
         CHGPU_TRY(qt_alloc(d, bytes, &m));
         mems.push_back(m);
         *out = m.p;
         return CHGPU_OK;
     }
 };
-
-// the group keys and counts of a keyed store: count() GROUP BY over its keys
-static int qt_count_groups(chgpu_quantile * d, chgpu_col ** keys, chgpu_col ** counts, u64 * groups)
-{
-    chgpu_ctx * ctx = d->ctx;
-    chgpu_agg * agg = nullptr;
-    const int kind = CHGPU_AGG_COUNT, arg_type = CHGPU_U64;
-    CHGPU_TRY(chgpu_agg_create(ctx, CHGPU_U64, 1, &kind, &arg_type, 0, &agg));
-    const chgpu_col kview = qt_view(ctx, CHGPU_U64, d->k_mem.p, d->held);
-    const chgpu_col * args[1] = {nullptr};
-    int rc = chgpu_agg_add_block(agg, &kview, args, 0, d->held);
-    chgpu_col * res[1] = {nullptr};
-    if (rc == CHGPU_OK)
-        rc = chgpu_agg_finalize(agg, keys, res, groups);
-    *counts = res[0];
-    chgpu_agg_free(agg);
-    return rc;
-}
 
 // groups, segment offsets, the classes of the segments, the key table and the segment array of the store as it stands
 static int qt_build_final(chgpu_quantile * d)
@@ -981,12 +876,12 @@ static int qt_build_final(chgpu_quantile * d)
     QtTemps tmp(d);
     chgpu_col * counts = nullptr;
     if (keyed)
-        CHGPU_TRY(qt_count_groups(d, &f.gkeys, &counts, &f.groups));
+        CHGPU_TRY(pair_count_groups(ctx, d->k_mem.p, d->held, nullptr, &f.gkeys, &counts, &f.groups));
     else
     {
         f.groups = 1;
         CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, 1, &counts));
-        hipLaunchKernelGGL(k_qt_set_u64, dim3(1), dim3(1), 0, ctx->stream, (u64 *)counts->data, d->held);
+        pair_set_u64(ctx, (u64 *)counts->data, d->held);
         ctx->counters[6] += 1;
     }
     struct FreeCol
@@ -1014,7 +909,7 @@ static int qt_build_final(chgpu_quantile * d)
     CHGPU_HIP(hipMemsetAsync(tot, 0, 3 * sizeof(u64), ctx->stream));
     hipLaunchKernelGGL(k_qt_classify, ggrid, block, 0, ctx->stream, (const u64 *)counts->data, G, c32, flag, units, (ull *)(tot + 2));
     ctx->counters[6] += 2;
-    CHGPU_TRY(qt_launch_ok("classify"));
+    CHGPU_TRY(pair_launch_ok(QT_NAMES, "classify"));
     void * scan_tmp = nullptr;
     const size_t scan_bytes = chgpu_scan_tmp_bytes(G);
     CHGPU_TRY(chgpu_scratch(ctx, scan_bytes, &scan_tmp));
@@ -1032,7 +927,7 @@ static int qt_build_final(chgpu_quantile * d)
         CHGPU_TRY(qt_alloc(d, f.large * sizeof(QtLarge), &f.lseg));
         hipLaunchKernelGGL(k_qt_large_list, ggrid, block, 0, ctx->stream, c32, offsets, flag, lidx, uoff, G, (QtLarge *)f.lseg.p);
         ctx->counters[6] += 1;
-        CHGPU_TRY(qt_launch_ok("large list"));
+        CHGPU_TRY(pair_launch_ok(QT_NAMES, "large list"));
     }
     if (!keyed)
         return CHGPU_OK; // one segment: the store's values
@@ -1041,9 +936,8 @@ static int qt_build_final(chgpu_quantile * d)
     CHGPU_TRY(qt_alloc(d, d->held * d->width, &f.seg));
     u32 * cursor = nullptr; // [G] cursors, then the count of values whose key found no group
     CHGPU_TRY(tmp.alloc((G + 1) * 4, (void **)&cursor));
-    CHGPU_HIP(hipMemsetAsync(f.cells.p, 0, f.cells_cap * 4, ctx->stream));
+    CHGPU_TRY(gt_fill(ctx, QT_NAMES.op, (const u64 *)f.gkeys->data, G, (u32 *)f.cells.p, f.cells_cap));
     CHGPU_HIP(hipMemsetAsync(cursor, 0, (G + 1) * 4, ctx->stream));
-    hipLaunchKernelGGL(k_qt_table_build, ggrid, block, 0, ctx->stream, (const u64 *)f.gkeys->data, G, (u32 *)f.cells.p, f.cells_cap);
     const dim3 vgrid(qt_grid(ctx, d->held));
     dispatch_width(d->width, [&](auto tag) {
         typedef decltype(tag) T;
@@ -1056,7 +950,7 @@ static int qt_build_final(chgpu_quantile * d)
                                (const u32 *)f.cells.p, f.cells_cap, (const u64 *)offsets, cursor, cursor + G, (T *)f.seg.p);
     });
     ctx->counters[6] += 4;
-    CHGPU_TRY(qt_launch_ok("scatter"));
+    CHGPU_TRY(pair_launch_ok(QT_NAMES, "scatter"));
     u32 lost = 0;
     CHGPU_TRY(chgpu_read_back(ctx, cursor + G, &lost, sizeof(lost)));
     CHGPU_REQUIRE(lost == 0, CHGPU_ERR_LOGICAL, "quantile: %u stored values found no place in their group's segment", lost);
@@ -1143,7 +1037,7 @@ static int qt_select(chgpu_quantile * d, int kind, u32 n_levels, const double * 
             }
         }
     });
-    CHGPU_TRY(qt_launch_ok("select"));
+    CHGPU_TRY(pair_launch_ok(QT_NAMES, "select"));
     plan->groups = f.groups;
     plan->values = f.values;
     plan->small = f.small;
@@ -1182,16 +1076,7 @@ static int qt_empty_cols(chgpu_quantile * d, u32 n_levels, u64 n, chgpu_col ** c
         hipLaunchKernelGGL(k_qt_fill<T>, dim3(qt_grid(ctx, n)), dim3(QT_T), 0, ctx->stream, out, n_levels, n, (T)empty);
     });
     ctx->counters[6] += 1;
-    return qt_launch_ok("fill");
-}
-
-static void qt_print_plan(chgpu_quantile * d, const QtPlan & plan)
-{
-    if (chgpu_opt(d->ctx, "debug", 0) == 0)
-        return;
-    char line[256];
-    qt_format_plan(line, sizeof(line), plan);
-    fprintf(stderr, "%s\n", line);
+    return pair_launch_ok(QT_NAMES, "fill");
 }
 
 extern "C" int chgpu_quantile_finalize(chgpu_quantile * d, int kind, uint32_t n_levels, const double * levels, chgpu_col ** keys_out, chgpu_col ** res_cols,
@@ -1228,12 +1113,9 @@ extern "C" int chgpu_quantile_finalize(chgpu_quantile * d, int kind, uint32_t n_
             rc = qt_col_new(d, d->key_type, rows, &k);
         if (rc == CHGPU_OK && keyed)
         {
-            dispatch_width(chgpu_type_size(d->key_type), [&](auto tag) {
-                typedef decltype(tag) K;
-                hipLaunchKernelGGL(k_qt_export_keys<K>, dim3(qt_grid(ctx, rows)), dim3(QT_T), 0, ctx->stream, (const u64 *)d->fin.gkeys->data, rows, (K *)k->data);
-            });
+            pair_narrow(ctx, (const u64 *)d->fin.gkeys->data, rows, k);
             ctx->counters[6] += 1;
-            rc = qt_launch_ok("keys");
+            rc = pair_launch_ok(QT_NAMES, "keys");
         }
     }
     if (rc != CHGPU_OK)
@@ -1242,7 +1124,7 @@ extern "C" int chgpu_quantile_finalize(chgpu_quantile * d, int kind, uint32_t n_
         if (k) chgpu_col_free(k);
         return rc;
     }
-    qt_print_plan(d, plan);
+    pair_print_plan(ctx, qt_format_plan, plan);
     for (u32 l = 0; l < n_levels; ++l)
         res_cols[l] = res[l];
     if (keys_out)
@@ -1254,13 +1136,12 @@ extern "C" int chgpu_quantile_finalize(chgpu_quantile * d, int kind, uint32_t n_
 extern "C" int chgpu_quantile_for_keys(chgpu_quantile * d, int kind, uint32_t n_levels, const double * levels, const chgpu_col * keys, chgpu_col ** res_cols)
 {
     CHGPU_REQUIRE(d && keys && res_cols, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(d->key_type >= 0, CHGPU_ERR_BAD_ARGUMENTS, "quantile: an operator without key has no keys to look up");
-    CHGPU_REQUIRE(keys->type == d->key_type, CHGPU_ERR_BAD_ARGUMENTS, "quantile: key column of type %d, the operator was made for %d", keys->type, d->key_type);
+    CHGPU_TRY(pair_check_keys(QT_NAMES, *d, keys));
     const char * msg = "";
     const int code = qt_check_levels(kind, n_levels, levels, &msg);
     CHGPU_REQUIRE(code == CHGPU_OK, code, "quantile: %s", msg);
+    CHGPU_TRY(pair_check_device(QT_NAMES, *d, keys));
     chgpu_ctx * ctx = d->ctx;
-    CHGPU_REQUIRE(keys->ctx->device == ctx->device, CHGPU_ERR_BAD_ARGUMENTS, "quantile: a column lives on another device than the operator");
     ChgpuDeviceGuard guard(ctx);
     qt_begin_call(d);
     chgpu_col * res[CHGPU_QUANTILE_MAX_LEVELS] = {nullptr};
@@ -1294,7 +1175,7 @@ extern "C" int chgpu_quantile_for_keys(chgpu_quantile * d, int kind, uint32_t n_
                                    f.cells_cap, (const void *)keys->data, (u32)chgpu_type_size(d->key_type), keys->rows, gres, out, n_levels, (T)empty);
             });
             ctx->counters[6] += 1;
-            rc = qt_launch_ok("for_keys");
+            rc = pair_launch_ok(QT_NAMES, "for_keys");
         }
         qt_free_cols(per_group, n_levels); // (reuse of the memory is ordered behind the gather on the stream)
     }
@@ -1303,7 +1184,7 @@ extern "C" int chgpu_quantile_for_keys(chgpu_quantile * d, int kind, uint32_t n_
         qt_free_cols(res, n_levels);
         return rc;
     }
-    qt_print_plan(d, plan);
+    pair_print_plan(ctx, qt_format_plan, plan);
     for (u32 l = 0; l < n_levels; ++l)
         res_cols[l] = res[l];
     return CHGPU_OK;

@@ -1,11 +1,13 @@
-// uniq_host.h — the parts of the uniqExact operator (uniq_kernels.hip) that need no device: table geometry, the entry checks of
-// chgpu_uniq_add_block and the `debug` option's plan line.  Plain C++, so that tests/uniq_exact_driver.cpp runs them under a sanitizer.
+// uniq_host.h — the parts of the uniqExact operator (uniq_kernels.hip) that need no device: table geometry and the `debug` option's
+// plan line; the row checks of chgpu_uniq_add_block are pair_host.h's.  Plain C++, so that tests/uniq_exact_driver.cpp runs them
+// under a sanitizer.
 #pragma once
 
 #include <cstdint>
 #include <cstdio>
 
 #include "../../include/chgpu.h"
+#include "pair_host.h"
 
 static constexpr uint64_t UQ_CAP_MIN = 2048;            // cells of the smallest table (a power of two, like every capacity)
 static constexpr uint64_t UQ_MAX_SLOTS = 1ull << 31;     // a cell holds store index + 1 in 32 bits; the 32-bit slot counter may pass the limit by a grid of lanes
@@ -30,33 +32,6 @@ static inline uint64_t uq_capacity_for(uint64_t pairs)
     while (uq_limit(cap) < pairs)
         cap *= 2;
     return cap;
-}
-
-// The row-range and length checks of chgpu_uniq_add_block.  key_rows < 0: no key column (without key); filter_rows < 0: no filter.
-// Returns CHGPU_OK or the error code, *msg then says why.
-static inline int uq_check_rows(int64_t key_rows, uint64_t value_rows, int64_t filter_rows, uint64_t row_begin, uint64_t row_end, const char ** msg)
-{
-    if (key_rows >= 0 && (uint64_t)key_rows != value_rows)
-    {
-        *msg = "key and value columns of different lengths";
-        return CHGPU_ERR_SIZES_MISMATCH;
-    }
-    if (filter_rows >= 0 && (uint64_t)filter_rows != value_rows)
-    {
-        *msg = "filter and value columns of different lengths";
-        return CHGPU_ERR_SIZES_MISMATCH;
-    }
-    if (row_begin > row_end)
-    {
-        *msg = "row_begin > row_end";
-        return CHGPU_ERR_BAD_ARGUMENTS;
-    }
-    if (row_end > value_rows)
-    {
-        *msg = "row range past the end of the column";
-        return CHGPU_ERR_BAD_ARGUMENTS;
-    }
-    return CHGPU_OK;
 }
 
 // what one chgpu_uniq_add_block / chgpu_uniq_merge did

@@ -22,9 +22,11 @@
 //   Only the rows that claimed a cell -- the tile's distinct pairs -- and the rows that found no room go on to the global table.
 //   Growth: the table holds capacity / 2 pairs.  A row that would insert beyond that sets its bit in the chunk's pending bitmap; the host
 //   grows the table (x4 to 2^23 cells, then x2), rebuilds the cells from the store and runs the pending rows again (k_uq_insert_pending).
+// What this operator shares with quantile_kernels.hip (element load, pool memory, entry checks, the groups of the store's keys, the
+// key -> group table) is pair_store.h / group_table.h.
 #include "chgpu_internal.h"
 
-#include "group_table.h"
+#include "pair_store.h"
 #include "uniq_host.h"
 
 typedef unsigned long long ull;
@@ -77,18 +79,6 @@ struct UqSrc
 __device__ __forceinline__ u64 uq_hash(u64 key, u64 val)
 {
     return dev_intHash64(val ^ key * UQ_KEY_MULT);
-}
-
-// raw bits of element i, zero-extended (keys as load_key_zext; values compared as their own bits: Float32 as 32 bits)
-__device__ __forceinline__ u64 uq_load(const void * p, u32 size, u64 i)
-{
-    switch (size)
-    {
-        case 1: return ((const u8 *)p)[i];
-        case 2: return ((const u16 *)p)[i];
-        case 4: return ((const u32 *)p)[i];
-        default: return ((const u64 *)p)[i];
-    }
 }
 
 __device__ __forceinline__ u64 uq_ld(const u64 * p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -250,8 +240,8 @@ __global__ __launch_bounds__(UQ_T) void k_uq_lookup(UqTable t, UqSrc s, u64 row_
             const u64 i = i0 + u * stride;
             const u64 r = row_begin + (i < n ? i : n - 1);
             in[u] = i < n && (!s.filter || s.filter[r] != 0);
-            key[u] = s.key_size ? uq_load(s.key, s.key_size, r) : 0;
-            val[u] = uq_load(s.val, s.val_size, r);
+            key[u] = s.key_size ? pair_load(s.key, s.key_size, r) : 0;
+            val[u] = pair_load(s.val, s.val_size, r);
         }
 #pragma unroll
         for (u32 u = 0; u < UQ_LOOKUP_U; ++u)
@@ -320,8 +310,8 @@ __global__ __launch_bounds__(UQ_T) void k_uq_insert_tiles(UqTable t, UqSrc s, u6
                 a = (todo[i >> 6] >> (i & 63)) & 1; // (the filter is in the bit already)
             else if (a && s.filter)
                 a = s.filter[row_begin + i] != 0;
-            kk[r] = a && s.key_size ? uq_load(s.key, s.key_size, row_begin + i) : 0;
-            vv[r] = a ? uq_load(s.val, s.val_size, row_begin + i) : 0;
+            kk[r] = a && s.key_size ? pair_load(s.key, s.key_size, row_begin + i) : 0;
+            vv[r] = a ? pair_load(s.val, s.val_size, row_begin + i) : 0;
             lk[j] = kk[r];
             lv[j] = vv[r];
             act |= (u32)a << r;
@@ -409,8 +399,8 @@ __global__ __launch_bounds__(UQ_T) void k_uq_insert_pending(UqTable t, UqSrc s, 
             continue;
         const bool active = (w >> lane) & 1;
         const u64 i = row_begin + g * 64 + lane;
-        const u64 key = active && s.key_size ? uq_load(s.key, s.key_size, i) : 0;
-        const u64 val = active ? uq_load(s.val, s.val_size, i) : 0;
+        const u64 key = active && s.key_size ? pair_load(s.key, s.key_size, i) : 0;
+        const u64 val = active ? pair_load(s.val, s.val_size, i) : 0;
         const bool deferred = uq_walk(t, active, key, val, UQ_NO_SLOT, y);
         const ull again = __ballot(deferred);
         if (lane == 0)
@@ -464,32 +454,13 @@ __global__ __launch_bounds__(UQ_T) void k_uq_alive(UqTable t, u64 n_slots, u8 * 
         alive[k] = uq_find(t, t.store_k[k], t.store_v[k]) == (u32)k;
 }
 
-// UInt64 words back to the column's own width
-template <typename T>
-__global__ __launch_bounds__(UQ_T) void k_uq_narrow(const u64 * __restrict__ in, u64 n, T * __restrict__ out)
-{
-    for (u64 i = (u64)blockIdx.x * UQ_T + threadIdx.x; i < n; i += (u64)gridDim.x * UQ_T)
-        out[i] = (T)in[i];
-}
-
-__global__ void k_uq_set_u64(u64 * out, u64 v)
-{
-    out[0] = v;
-}
-
-// counts_for_keys: a table over the finalised groups (group_table.h)
-__global__ __launch_bounds__(UQ_T) void k_uq_kc_build(const u64 * __restrict__ gkeys, u64 groups, u32 * __restrict__ cells, u64 cap)
-{
-    for (u64 g = (u64)blockIdx.x * UQ_T + threadIdx.x; g < groups; g += (u64)gridDim.x * UQ_T)
-        gt_insert(gkeys, g, cells, cap);
-}
-
+// counts_for_keys: the table over the finalised groups (group_table.h)
 __global__ __launch_bounds__(UQ_T) void k_uq_kc_lookup(const u64 * __restrict__ gkeys, const u64 * __restrict__ gcounts, const u32 * __restrict__ cells, u64 cap,
                                                        const void * __restrict__ keys, u32 key_size, u64 n, u64 * __restrict__ out)
 {
     for (u64 i = (u64)blockIdx.x * UQ_T + threadIdx.x; i < n; i += (u64)gridDim.x * UQ_T)
     {
-        const u32 g = gt_find(gkeys, cells, cap, uq_load(keys, key_size, i));
+        const u32 g = gt_find(gkeys, cells, cap, pair_load(keys, key_size, i));
         out[i] = g == GT_NONE ? 0 : gcounts[g];
     }
 }
@@ -497,36 +468,22 @@ __global__ __launch_bounds__(UQ_T) void k_uq_kc_lookup(const u64 * __restrict__ 
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-struct UqMem
-{
-    void * p = nullptr;
-    size_t cls = 0;
-};
+static constexpr PairNames UQ_NAMES{"uniq", "set", "a set"};
 
-struct chgpu_uniq
+struct chgpu_uniq : PairOp
 {
-    chgpu_ctx * ctx = nullptr;
-    int key_type = -1; // < 0: without key
-    int value_type = 0;
     UqTable t{};
-    UqMem cells_mem, sk_mem, sv_mem, ctrl_mem;
+    PairMem cells_mem, sk_mem, sv_mem, ctrl_mem;
     u64 n_slots = 0, holes = 0;
     // what finalize computed, kept until the set changes: the groups (UInt64 keys, counts); the key -> group table of counts_for_keys
     bool fin_valid = false;
     chgpu_col * fin_keys = nullptr;
     chgpu_col * fin_counts = nullptr;
     u64 fin_groups = 0;
-    UqMem kc_mem;
+    PairMem kc_mem;
     u64 kc_cap = 0;
     long long fail_growth = 0; // test hook: the growth with this number (1 = first of a call) answers OOM, so that the roll-back runs
 };
-
-static void uq_free_mem(chgpu_ctx * ctx, UqMem & m)
-{
-    if (m.p)
-        chgpu_pool_free(ctx, m.p, m.cls);
-    m = UqMem{};
-}
 
 static void uq_drop_final(chgpu_uniq * d)
 {
@@ -534,26 +491,9 @@ static void uq_drop_final(chgpu_uniq * d)
     if (d->fin_counts) chgpu_col_free(d->fin_counts);
     d->fin_keys = d->fin_counts = nullptr;
     d->fin_groups = 0;
-    uq_free_mem(d->ctx, d->kc_mem);
+    pair_free_mem(d->ctx, d->kc_mem);
     d->kc_cap = 0;
     d->fin_valid = false;
-}
-
-static chgpu_col uq_view(chgpu_ctx * ctx, int type, void * data, u64 rows)
-{
-    chgpu_col v;
-    v.ctx = ctx;
-    v.type = type;
-    v.rows = rows;
-    v.data = data;
-    return v;
-}
-
-static int uq_launch_ok(const char * what)
-{
-    if (hipGetLastError() != hipSuccess)
-        return chgpu_set_error(CHGPU_ERR_DEVICE, "uniq: %s launch failed", what);
-    return CHGPU_OK;
 }
 
 static int uq_rebuild(chgpu_uniq * d, u64 n_slots)
@@ -566,7 +506,7 @@ static int uq_rebuild(chgpu_uniq * d, u64 n_slots)
     hipLaunchKernelGGL(k_uq_rebuild, dim3(chgpu_grid_for(ctx, n_slots, UQ_T, 8)), dim3(UQ_T), 0, ctx->stream, d->t, n_slots);
     ctx->counters[6] += 2;
     ctx->counters[7] += 1;
-    return uq_launch_ok("rebuild");
+    return pair_launch_ok(UQ_NAMES, "rebuild");
 }
 
 // A table of `cap` cells (and a store of its limit) in place of the present one: every allocation first, so that a failure leaves the
@@ -575,15 +515,15 @@ static int uq_resize(chgpu_uniq * d, u64 cap)
 {
     chgpu_ctx * ctx = d->ctx;
     const u64 limit = uq_limit(cap);
-    UqMem cells, sk, sv;
+    PairMem cells, sk, sv;
     int rc = chgpu_pool_alloc(ctx, cap * 8, &cells.p, &cells.cls);
     if (rc == CHGPU_OK) rc = chgpu_pool_alloc(ctx, limit * 8, &sk.p, &sk.cls);
     if (rc == CHGPU_OK) rc = chgpu_pool_alloc(ctx, limit * 8, &sv.p, &sv.cls);
     if (rc != CHGPU_OK)
     {
-        uq_free_mem(ctx, cells);
-        uq_free_mem(ctx, sk);
-        uq_free_mem(ctx, sv);
+        pair_free_mem(ctx, cells);
+        pair_free_mem(ctx, sk);
+        pair_free_mem(ctx, sv);
         return rc;
     }
     if (d->n_slots)
@@ -593,15 +533,15 @@ static int uq_resize(chgpu_uniq * d, u64 cap)
             e = hipMemcpyAsync(sv.p, d->t.store_v, d->n_slots * 8, hipMemcpyDeviceToDevice, ctx->stream);
         if (e != hipSuccess)
         {
-            uq_free_mem(ctx, cells);
-            uq_free_mem(ctx, sk);
-            uq_free_mem(ctx, sv);
+            pair_free_mem(ctx, cells);
+            pair_free_mem(ctx, sk);
+            pair_free_mem(ctx, sv);
             return chgpu_set_error(CHGPU_ERR_DEVICE, "uniq: copying the store failed: %s", hipGetErrorString(e));
         }
     }
-    uq_free_mem(ctx, d->cells_mem); // reuse is ordered behind the copies above (same stream)
-    uq_free_mem(ctx, d->sk_mem);
-    uq_free_mem(ctx, d->sv_mem);
+    pair_free_mem(ctx, d->cells_mem); // reuse is ordered behind the copies above (same stream)
+    pair_free_mem(ctx, d->sk_mem);
+    pair_free_mem(ctx, d->sv_mem);
     d->cells_mem = cells;
     d->sk_mem = sk;
     d->sv_mem = sv;
@@ -663,7 +603,7 @@ static int uq_add_rows(chgpu_uniq * d, const UqSrc & s, u64 row_begin, u64 n, co
             else
                 hipLaunchKernelGGL(k_uq_insert_pending, dim3(chgpu_grid_for(ctx, m, UQ_T, 4)), dim3(UQ_T), 0, ctx->stream, d->t, s, row_begin + c0, m, pending);
             ctx->counters[6] += 2;
-            if ((rc = uq_launch_ok("insert")) != CHGPU_OK)
+            if ((rc = pair_launch_ok(UQ_NAMES, "insert")) != CHGPU_OK)
                 break;
             UqCtrl c; // the one blocking read of a round: 56 bytes
             if ((rc = chgpu_read_back(ctx, d->t.ctrl, &c, sizeof(c))) != CHGPU_OK)
@@ -711,12 +651,7 @@ static int uq_add_rows(chgpu_uniq * d, const UqSrc & s, u64 row_begin, u64 n, co
     plan.slots = d->n_slots;
     plan.holes = d->holes;
     plan.rc = rc;
-    if (chgpu_opt(ctx, "debug", 0) != 0)
-    {
-        char line[512];
-        uq_format_plan(line, sizeof(line), plan);
-        fprintf(stderr, "%s\n", line);
-    }
+    pair_print_plan(ctx, uq_format_plan, plan);
     return rc;
 }
 
@@ -729,7 +664,7 @@ static int uq_alive(const chgpu_uniq * d, chgpu_ctx * ctx, chgpu_col ** out)
     {
         hipLaunchKernelGGL(k_uq_alive, dim3(chgpu_grid_for(ctx, d->n_slots, UQ_T, 8)), dim3(UQ_T), 0, ctx->stream, d->t, d->n_slots, (u8 *)alive->data);
         ctx->counters[6] += 1;
-        const int rc = uq_launch_ok("alive");
+        const int rc = pair_launch_ok(UQ_NAMES, "alive");
         if (rc != CHGPU_OK)
         {
             chgpu_col_free(alive);
@@ -747,13 +682,9 @@ static int uq_narrow(chgpu_ctx * ctx, const u64 * words, u64 n, int type, chgpu_
     CHGPU_TRY(chgpu_col_new(ctx, type, n, &c));
     if (n)
     {
-        const dim3 grid(chgpu_grid_for(ctx, n, UQ_T, 8)), block(UQ_T);
-        dispatch_width(chgpu_type_size(type), [&](auto tag) {
-            typedef decltype(tag) T;
-            hipLaunchKernelGGL(k_uq_narrow<T>, grid, block, 0, ctx->stream, words, n, (T *)c->data);
-        });
+        pair_narrow(ctx, words, n, c);
         ctx->counters[6] += 1;
-        const int rc = uq_launch_ok("narrow");
+        const int rc = pair_launch_ok(UQ_NAMES, "narrow");
         if (rc != CHGPU_OK)
         {
             chgpu_col_free(c);
@@ -788,20 +719,7 @@ static int uq_finalize_groups(chgpu_uniq * d)
     {
         chgpu_col * alive = nullptr;
         CHGPU_TRY(uq_alive(d, ctx, &alive));
-        chgpu_agg * agg = nullptr;
-        const int kind = CHGPU_AGG_COUNT, arg_type = CHGPU_U64;
-        int rc = chgpu_agg_create(ctx, CHGPU_U64, 1, &kind, &arg_type, 0, &agg);
-        if (rc == CHGPU_OK)
-        {
-            const chgpu_col kview = uq_view(ctx, CHGPU_U64, d->t.store_k, d->n_slots);
-            const chgpu_col * args[1] = {nullptr};
-            rc = chgpu_agg_add_block_filtered(agg, &kview, args, 0, d->n_slots, alive);
-            chgpu_col * res[1] = {nullptr};
-            if (rc == CHGPU_OK)
-                rc = chgpu_agg_finalize(agg, &keys, res, &groups);
-            counts = res[0];
-            chgpu_agg_free(agg);
-        }
+        const int rc = pair_count_groups(ctx, d->t.store_k, d->n_slots, alive, &keys, &counts, &groups);
         chgpu_col_free(alive);
         if (rc != CHGPU_OK)
             return rc;
@@ -823,20 +741,17 @@ static int uq_key_table(chgpu_uniq * d)
     const u64 groups = d->fin_groups;
     CHGPU_REQUIRE(groups < 0xFFFFFFFFull, CHGPU_ERR_TOO_MANY_ROWS, "uniq: more than 2^32 - 2 groups");
     const u64 cap = gt_capacity_for(groups);
-    UqMem kc;
+    PairMem kc;
     CHGPU_TRY(chgpu_pool_alloc(ctx, cap * 4, &kc.p, &kc.cls));
-    int rc = CHGPU_OK;
-    if (hipMemsetAsync(kc.p, 0, cap * 4, ctx->stream) != hipSuccess)
-        rc = chgpu_set_error(CHGPU_ERR_DEVICE, "uniq: clearing the key table failed");
+    int rc = gt_fill(ctx, UQ_NAMES.op, (const u64 *)d->fin_keys->data, groups, (u32 *)kc.p, cap);
     if (rc == CHGPU_OK && groups)
     {
-        hipLaunchKernelGGL(k_uq_kc_build, dim3(chgpu_grid_for(ctx, groups, UQ_T, 8)), dim3(UQ_T), 0, ctx->stream, (const u64 *)d->fin_keys->data, groups, (u32 *)kc.p, cap);
         ctx->counters[6] += 1;
-        rc = uq_launch_ok("key table");
+        rc = pair_launch_ok(UQ_NAMES, "key table");
     }
     if (rc != CHGPU_OK)
     {
-        uq_free_mem(ctx, kc);
+        pair_free_mem(ctx, kc);
         return rc;
     }
     d->kc_mem = kc;
@@ -847,12 +762,7 @@ static int uq_key_table(chgpu_uniq * d)
 extern "C" int chgpu_uniq_create(chgpu_ctx * ctx, int key_type, int value_type, uint64_t size_hint, chgpu_uniq ** out)
 {
     CHGPU_REQUIRE(ctx && out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    if (key_type >= 0)
-    {
-        CHGPU_REQUIRE(chgpu_type_size(key_type) != 0, CHGPU_ERR_BAD_ARGUMENTS, "uniq: unknown key type %d", key_type);
-        CHGPU_REQUIRE(chgpu_type_is_int(key_type), CHGPU_ERR_NOT_IMPLEMENTED, "uniq: key type %d: integer keys only (CPU path)", key_type);
-    }
-    CHGPU_REQUIRE(chgpu_type_size(value_type) != 0, CHGPU_ERR_BAD_ARGUMENTS, "uniq: unknown value type %d", value_type);
+    CHGPU_TRY(pair_check_create(UQ_NAMES, key_type, value_type));
     const u64 cap = uq_capacity_for(size_hint);
     CHGPU_REQUIRE(cap != 0, CHGPU_ERR_TOO_MANY_ROWS, "uniq: a size hint of %llu pairs, at most %llu fit", (unsigned long long)size_hint, (unsigned long long)UQ_MAX_SLOTS);
     ChgpuDeviceGuard guard(ctx);
@@ -883,10 +793,10 @@ extern "C" int chgpu_uniq_free(chgpu_uniq * d)
         return CHGPU_OK;
     ChgpuDeviceGuard guard(d->ctx);
     uq_drop_final(d);
-    uq_free_mem(d->ctx, d->cells_mem);
-    uq_free_mem(d->ctx, d->sk_mem);
-    uq_free_mem(d->ctx, d->sv_mem);
-    uq_free_mem(d->ctx, d->ctrl_mem);
+    pair_free_mem(d->ctx, d->cells_mem);
+    pair_free_mem(d->ctx, d->sk_mem);
+    pair_free_mem(d->ctx, d->sv_mem);
+    pair_free_mem(d->ctx, d->ctrl_mem);
     chgpu_ctx * ctx = d->ctx;
     delete d;
     chgpu_ctx_release(ctx);
@@ -897,18 +807,9 @@ extern "C" int chgpu_uniq_add_block(chgpu_uniq * d, const chgpu_col * key_col, c
                                     const chgpu_col * filter_u8)
 {
     CHGPU_REQUIRE(d && value_col, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_TRY(pair_check_add_block(UQ_NAMES, *d, key_col, value_col, row_begin, row_end, filter_u8));
     const bool keyed = d->key_type >= 0;
-    CHGPU_REQUIRE(!keyed || key_col, CHGPU_ERR_BAD_ARGUMENTS, "NULL key column");
-    CHGPU_REQUIRE(!keyed || key_col->type == d->key_type, CHGPU_ERR_BAD_ARGUMENTS, "uniq: key column of type %d, the set was made for %d", key_col->type, d->key_type);
-    CHGPU_REQUIRE(value_col->type == d->value_type, CHGPU_ERR_BAD_ARGUMENTS, "uniq: value column of type %d, the set was made for %d", value_col->type, d->value_type);
-    CHGPU_REQUIRE(!filter_u8 || filter_u8->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "uniq: the filter must be UInt8");
-    chgpu_ctx * ctx = d->ctx;
-    CHGPU_REQUIRE(value_col->ctx->device == ctx->device && (!keyed || key_col->ctx->device == ctx->device) && (!filter_u8 || filter_u8->ctx->device == ctx->device),
-                  CHGPU_ERR_BAD_ARGUMENTS, "uniq: a column lives on another device than the set");
-    const char * msg = "";
-    const int code = uq_check_rows(keyed ? (int64_t)key_col->rows : -1, value_col->rows, filter_u8 ? (int64_t)filter_u8->rows : -1, row_begin, row_end, &msg);
-    CHGPU_REQUIRE(code == CHGPU_OK, code, "uniq: %s", msg);
-    ChgpuDeviceGuard guard(ctx);
+    ChgpuDeviceGuard guard(d->ctx);
     UqSrc s{};
     s.key = keyed ? key_col->data : nullptr;
     s.key_size = keyed ? (u32)chgpu_type_size(d->key_type) : 0;
@@ -921,9 +822,7 @@ extern "C" int chgpu_uniq_add_block(chgpu_uniq * d, const chgpu_col * key_col, c
 extern "C" int chgpu_uniq_merge(chgpu_uniq * dst, const chgpu_uniq * src)
 {
     CHGPU_REQUIRE(dst && src, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(dst->key_type == src->key_type && dst->value_type == src->value_type, CHGPU_ERR_BAD_ARGUMENTS,
-                  "uniq: merging a set of (%d, %d) into one of (%d, %d)", src->key_type, src->value_type, dst->key_type, dst->value_type);
-    CHGPU_REQUIRE(dst->ctx->device == src->ctx->device, CHGPU_ERR_BAD_ARGUMENTS, "uniq: the sets live on different devices");
+    CHGPU_TRY(pair_check_merge(UQ_NAMES, *dst, *src));
     if (dst == src)
         return CHGPU_OK;
     chgpu_ctx * ctx = dst->ctx;
@@ -969,7 +868,7 @@ extern "C" int chgpu_uniq_export_pairs(chgpu_uniq * d, chgpu_col ** keys_out, ch
     {
         chgpu_col * alive = nullptr;
         CHGPU_TRY(uq_alive(d, ctx, &alive));
-        const chgpu_col kview = uq_view(ctx, CHGPU_U64, d->t.store_k, d->n_slots), vview = uq_view(ctx, CHGPU_U64, d->t.store_v, d->n_slots);
+        const chgpu_col kview = pair_view(ctx, CHGPU_U64, d->t.store_k, d->n_slots), vview = pair_view(ctx, CHGPU_U64, d->t.store_v, d->n_slots);
         if (keyed)
             rc = chgpu_filter(ctx, &kview, alive, 0, &k64, &rows);
         if (rc == CHGPU_OK)
@@ -1006,9 +905,9 @@ extern "C" int chgpu_uniq_finalize(chgpu_uniq * d, chgpu_col ** keys_out, chgpu_
         // without key: exactly one row, 0 for the empty set
         chgpu_col * c = nullptr;
         CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, 1, &c));
-        hipLaunchKernelGGL(k_uq_set_u64, dim3(1), dim3(1), 0, ctx->stream, (u64 *)c->data, d->n_slots - d->holes);
+        pair_set_u64(ctx, (u64 *)c->data, d->n_slots - d->holes);
         ctx->counters[6] += 1;
-        const int rc = uq_launch_ok("finalize");
+        const int rc = pair_launch_ok(UQ_NAMES, "finalize");
         if (rc != CHGPU_OK)
         {
             chgpu_col_free(c);
@@ -1042,10 +941,9 @@ extern "C" int chgpu_uniq_finalize(chgpu_uniq * d, chgpu_col ** keys_out, chgpu_
 extern "C" int chgpu_uniq_counts_for_keys(chgpu_uniq * d, const chgpu_col * keys, chgpu_col ** counts_u64)
 {
     CHGPU_REQUIRE(d && keys && counts_u64, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(d->key_type >= 0, CHGPU_ERR_BAD_ARGUMENTS, "uniq: a set without key has no keys to look up");
-    CHGPU_REQUIRE(keys->type == d->key_type, CHGPU_ERR_BAD_ARGUMENTS, "uniq: key column of type %d, the set was made for %d", keys->type, d->key_type);
+    CHGPU_TRY(pair_check_keys(UQ_NAMES, *d, keys));
+    CHGPU_TRY(pair_check_device(UQ_NAMES, *d, keys));
     chgpu_ctx * ctx = d->ctx;
-    CHGPU_REQUIRE(keys->ctx->device == ctx->device, CHGPU_ERR_BAD_ARGUMENTS, "uniq: a column lives on another device than the set");
     ChgpuDeviceGuard guard(ctx);
     CHGPU_TRY(uq_key_table(d));
     chgpu_col * c = nullptr;
@@ -1055,7 +953,7 @@ extern "C" int chgpu_uniq_counts_for_keys(chgpu_uniq * d, const chgpu_col * keys
         hipLaunchKernelGGL(k_uq_kc_lookup, dim3(chgpu_grid_for(ctx, keys->rows, UQ_T, 8)), dim3(UQ_T), 0, ctx->stream, (const u64 *)d->fin_keys->data,
                            (const u64 *)d->fin_counts->data, (const u32 *)d->kc_mem.p, d->kc_cap, keys->data, (u32)chgpu_type_size(d->key_type), keys->rows, (u64 *)c->data);
         ctx->counters[6] += 1;
-        const int rc = uq_launch_ok("counts_for_keys");
+        const int rc = pair_launch_ok(UQ_NAMES, "counts_for_keys");
         if (rc != CHGPU_OK)
         {
             chgpu_col_free(c);

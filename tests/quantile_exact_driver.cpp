@@ -65,9 +65,9 @@ static void levels()
     for (int kind : {CHGPU_QUANTILE_EXACT_INCLUSIVE, CHGPU_QUANTILE_EXACT_EXCLUSIVE, CHGPU_QUANTILE_EXACT_WEIGHTED})
         REQUIRE(qt_check_levels(kind, 3, ok, &msg) == CHGPU_ERR_NOT_IMPLEMENTED);
     REQUIRE(qt_check_levels(-1, 3, ok, &msg) == CHGPU_ERR_BAD_ARGUMENTS && qt_check_levels(6, 3, ok, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
-    REQUIRE(qt_check_rows(10, 10, 10, 0, 10, &msg) == CHGPU_OK && qt_check_rows(-1, 10, -1, 3, 3, &msg) == CHGPU_OK);
-    REQUIRE(qt_check_rows(9, 10, -1, 0, 9, &msg) == CHGPU_ERR_SIZES_MISMATCH && qt_check_rows(10, 10, 11, 0, 9, &msg) == CHGPU_ERR_SIZES_MISMATCH);
-    REQUIRE(qt_check_rows(10, 10, -1, 6, 5, &msg) == CHGPU_ERR_BAD_ARGUMENTS && qt_check_rows(10, 10, -1, 0, 11, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    REQUIRE(pair_check_rows(10, 10, 10, 0, 10, &msg) == CHGPU_OK && pair_check_rows(-1, 10, -1, 3, 3, &msg) == CHGPU_OK);
+    REQUIRE(pair_check_rows(9, 10, -1, 0, 9, &msg) == CHGPU_ERR_SIZES_MISMATCH && pair_check_rows(10, 10, 11, 0, 9, &msg) == CHGPU_ERR_SIZES_MISMATCH);
+    REQUIRE(pair_check_rows(10, 10, -1, 6, 5, &msg) == CHGPU_ERR_BAD_ARGUMENTS && pair_check_rows(10, 10, -1, 0, 11, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
 }
 
 // the keys are a bijection on the width's bits and keep the value's order

@@ -73,6 +73,18 @@ def test_python_class_rejects_an_unknown_dtype_before_the_library(K):
         UniqExact(None, "float16", ctx=object())
 
 
+def test_the_pair_operators_keep_their_public_method_names():
+    # the two classes share a base (clickhouse_amd/_pairs.py); what a caller sees of either is this and no more
+    from clickhouse_amd.quantile import QuantileExact
+    from clickhouse_amd.uniq import UniqExact
+    shared = {"add_block", "close", "export_pairs", "finalize", "finalize_columns", "merge"}
+    public = lambda cls: {n for n in dir(cls) if not n.startswith("_")}
+    assert public(UniqExact) == shared | {"export_pair_columns", "counts_for_keys", "counts_for_keys_column"}
+    assert public(QuantileExact) == shared | {"export_pairs_columns", "quantiles_for_keys", "quantiles_for_keys_column"}
+    for cls in (UniqExact, QuantileExact):
+        assert callable(cls.__len__) and callable(cls.__del__) and all(callable(getattr(cls, n)) for n in public(cls))
+
+
 def test_shim_class_compiles_next_to_an_aggregator(tmp_path):
     # syntax-only: GpuUniqExact as a driver uses it (no GPU, no library)
     src = tmp_path / "snippet.cpp"

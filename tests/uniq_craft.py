@@ -18,7 +18,7 @@ UQ_LDS_PROBES = 16
 UQ_KEY_MULT = 0x9E3779B97F4A7C15
 INTHASH_MUL1 = 0xFF51AFD7ED558CCD
 INTHASH_MUL2 = 0xC4CEB9FE1A85EC53
-# uniq_host.h:10-15: the smallest table, the largest set, growth x4 up to 2^23 cells and then x2; the table holds capacity / 2 pairs
+# uniq_host.h:12-17: the smallest table, the largest set, growth x4 up to 2^23 cells and then x2; the table holds capacity / 2 pairs
 UQ_CAP_MIN = 2048
 UQ_MAX_SLOTS = 1 << 31
 
@@ -80,12 +80,12 @@ def lds_home(h):
 
 
 def grow(cap):
-    """uniq_host.h:15 (uq_grow)"""
+    """uniq_host.h:17 (uq_grow)"""
     return cap * 4 if cap < (1 << 23) else cap * 2
 
 
 def limit(cap):
-    """uniq_host.h:18 (uq_limit)"""
+    """uniq_host.h:20 (uq_limit)"""
     return min(cap // 2, UQ_MAX_SLOTS)
 
 

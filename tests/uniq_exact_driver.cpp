@@ -47,15 +47,15 @@ static void geometry()
 static void row_checks()
 {
     const char * msg = nullptr;
-    REQUIRE(uq_check_rows(10, 10, 10, 0, 10, &msg) == CHGPU_OK);
-    REQUIRE(uq_check_rows(-1, 10, -1, 3, 3, &msg) == CHGPU_OK);  // an empty range is not an error
-    REQUIRE(uq_check_rows(0, 0, 0, 0, 0, &msg) == CHGPU_OK);     // nor is a column of no rows
-    REQUIRE(uq_check_rows(9, 10, -1, 0, 9, &msg) == CHGPU_ERR_SIZES_MISMATCH && std::strstr(msg, "key"));
-    REQUIRE(uq_check_rows(10, 10, 11, 0, 9, &msg) == CHGPU_ERR_SIZES_MISMATCH && std::strstr(msg, "filter"));
-    REQUIRE(uq_check_rows(10, 10, -1, 6, 5, &msg) == CHGPU_ERR_BAD_ARGUMENTS && std::strstr(msg, "row_begin"));
-    REQUIRE(uq_check_rows(10, 10, -1, 0, 11, &msg) == CHGPU_ERR_BAD_ARGUMENTS && std::strstr(msg, "past"));
-    REQUIRE(uq_check_rows(-1, ~0ull, -1, ~0ull, ~0ull, &msg) == CHGPU_OK);
-    REQUIRE(uq_check_rows(-1, 5, -1, ~0ull, 0, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    REQUIRE(pair_check_rows(10, 10, 10, 0, 10, &msg) == CHGPU_OK);
+    REQUIRE(pair_check_rows(-1, 10, -1, 3, 3, &msg) == CHGPU_OK);  // an empty range is not an error
+    REQUIRE(pair_check_rows(0, 0, 0, 0, 0, &msg) == CHGPU_OK);     // nor is a column of no rows
+    REQUIRE(pair_check_rows(9, 10, -1, 0, 9, &msg) == CHGPU_ERR_SIZES_MISMATCH && std::strstr(msg, "key"));
+    REQUIRE(pair_check_rows(10, 10, 11, 0, 9, &msg) == CHGPU_ERR_SIZES_MISMATCH && std::strstr(msg, "filter"));
+    REQUIRE(pair_check_rows(10, 10, -1, 6, 5, &msg) == CHGPU_ERR_BAD_ARGUMENTS && std::strstr(msg, "row_begin"));
+    REQUIRE(pair_check_rows(10, 10, -1, 0, 11, &msg) == CHGPU_ERR_BAD_ARGUMENTS && std::strstr(msg, "past"));
+    REQUIRE(pair_check_rows(-1, ~0ull, -1, ~0ull, ~0ull, &msg) == CHGPU_OK);
+    REQUIRE(pair_check_rows(-1, 5, -1, ~0ull, 0, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
 }
 
 static void plan_line()
