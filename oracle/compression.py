@@ -265,6 +265,8 @@ def read_frames(buf: bytes) -> bytes:
         if method == METHOD_LZ4:
             out += lz4_decompress(payload, dsize)
         elif method == METHOD_NONE:
+            if size != dsize:
+                raise ValueError("CANNOT_DECOMPRESS: a stored frame's sizes differ")
             out += payload
         elif method == METHOD_DELTA:
             out += delta_decode(payload, dsize)
@@ -291,6 +293,8 @@ def _decode_stage(buf: bytes) -> bytes:
     if method == METHOD_DELTA:
         return delta_decode(payload, dsize)
     if method == METHOD_NONE:
+        if len(payload) != dsize:
+            raise ValueError("CANNOT_DECOMPRESS: a stored frame's sizes differ")
         return payload
     if method == METHOD_ZSTD:
         return zstd_decompress(payload, dsize)
