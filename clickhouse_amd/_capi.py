@@ -106,6 +106,8 @@ SIGNATURES = {
     "chgpu_unpack_fixed_key": (_i, [_vp, _vp, _u32, _i, _pp]),
     "chgpu_string_dictionary_encode": (_i, [_vp, _vp, _vp, _pp, _pp, _pu64]),
     "chgpu_string_filter": (_i, [_vp, _vp, _vp, _vp, _pp, _pp, _pu64]),
+    "chgpu_string_sort_permutation": (_i, [_vp, _vp, _vp, _vp, _i, _u64, _pp]),
+    "chgpu_string_index": (_i, [_vp, _vp, _vp, _vp, _u64, _pp, _pp]),
     "chgpu_string_cmp_const": (_i, [_vp, _vp, _vp, _i, C.c_char_p, _u64, _pp]),
     "chgpu_string_match_const": (_i, [_vp, _vp, _vp, _i, C.c_char_p, _u64, _i, _pp]),
     "chgpu_like_compile": (_i, [C.c_char_p, _u64, _vp]),

@@ -406,15 +406,21 @@ def filter_to_indices(filt: Column) -> Column:
 
 def sort_block(columns, description, limit: int = 0):
     """sortBlock (src/Interpreters/sortBlock.cpp): description = [(position, descending, nan_direction_hint), ...] most significant
-    first; every column of the block permuted (IColumn::permute == index), cut to `limit` rows when given."""
+    first; every column of the block permuted (IColumn::permute == index), cut to `limit` rows when given.  `columns` may hold
+    ColumnString objects, as sort keys and as carried columns; the nan hint of a String entry is ignored, and a String key that is the
+    most significant column takes the limit into its own sort."""
     description = list(description)
-    if limit and len(description) == 1:
+    is_string = lambda c: hasattr(c, "get_permutation")  # ColumnString (lowcardinality.py imports this module)
+    if limit and len(description) == 1 and not is_string(columns[description[0][0]]):
         pos, desc, hint = description[0]
         perm = sort_permutation_limit(columns[pos], limit, desc, hint)  # one sort column + LIMIT: only the candidate rows are sorted
         return [c.index(perm) for c in columns], perm
     perm = None
-    for pos, desc, hint in reversed(description):
-        perm = sort_permutation(columns[pos], perm, desc, hint)
+    for k, (pos, desc, hint) in reversed(list(enumerate(description))):
+        if is_string(columns[pos]):
+            perm = columns[pos].get_permutation(perm, desc, limit if k == 0 else 0)
+        else:
+            perm = sort_permutation(columns[pos], perm, desc, hint)
     if limit:
         perm = perm.cut(0, min(limit, perm.size()))
     return [c.index(perm) for c in columns], perm

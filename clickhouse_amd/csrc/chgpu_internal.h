@@ -179,6 +179,8 @@ size_t chgpu_scan_tmp_bytes(u64 n);
 // stable split of n_cols columns by sel[i] < num_shards (<= 256) into concatenated outputs (partition_kernels.hip); counts[num_shards] on the host
 int chgpu_partition_by_key_byte(chgpu_ctx * ctx, const chgpu_col * keys, u32 shift, u32 n_cols, const chgpu_col * const * cols, chgpu_col ** outs);
 int chgpu_partition_core(chgpu_ctx * ctx, const u32 * sel, u64 n, u32 num_shards, u32 n_cols, const chgpu_col * const * cols, chgpu_col ** outs, u64 * counts);
+// ColumnString invariant (string_kernels.hip): offsets strictly increase and end inside chars, else BAD_ARGUMENTS.  One read-back.
+int str_validate_offsets(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8);
 
 // ---------------------------------------------------------------------------------------------
 // a run-time value as a template argument (host side): every helper calls `fn` with a tag for the value it was given

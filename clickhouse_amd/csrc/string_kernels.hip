@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void k_str_check_offsets(const u64 * __restric
         *bad = 1;
 }
 
-static int str_validate_offsets(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8)
+int str_validate_offsets(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8) // shared with string_sort_kernels.hip
 {
     const u64 n = offsets_u64->rows;
     if (!n)

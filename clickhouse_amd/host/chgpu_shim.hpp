@@ -797,6 +797,24 @@ struct ColumnString
         check(chgpu_string_cmp_const(offsets->context()->get(), offsets->handle(), chars->handle(), op, value.data(), value.size(), &out));
         return std::make_shared<ColumnVector>(offsets->context(), out);
     }
+    /// ColumnString::getPermutation(direction, Stable, limit, ...) without collation: the UInt64 permutation that orders the values as
+    /// unsigned bytes, the shorter of two values that agree being the smaller; equal values keep their incoming order in both directions.
+    /// perm_in (may be null) composes a less significant sort, as in sortBlock; 0 < limit < rows cuts the result to its first `limit` entries.
+    ColumnPtr getPermutation(bool descending = false, uint64_t limit = 0, const ColumnVector * perm_in = nullptr) const
+    {
+        chgpu_col * out = nullptr;
+        check(chgpu_string_sort_permutation(offsets->context()->get(), offsets->handle(), chars->handle(), perm_in ? perm_in->handle() : nullptr,
+                                            descending ? 1 : 0, limit, &out));
+        return std::make_shared<ColumnVector>(offsets->context(), out);
+    }
+    /// ColumnString::permute / index: value[perm[i]] for i < (limit ? min(limit, perm.size()) : perm.size()) as a new ColumnString
+    ColumnString permute(const ColumnVector & perm, uint64_t limit = 0) const
+    {
+        chgpu_col * oo = nullptr, * oc = nullptr;
+        check(chgpu_string_index(offsets->context()->get(), offsets->handle(), chars->handle(), perm.handle(), limit, &oo, &oc));
+        return ColumnString{std::make_shared<ColumnVector>(offsets->context(), oo), std::make_shared<ColumnVector>(offsets->context(), oc)};
+    }
+
     ColumnPtr like(std::string_view pattern, bool negate = false) const { return match(CHGPU_STR_LIKE, pattern, negate); }
     ColumnPtr contains(std::string_view needle, bool negate = false) const { return match(CHGPU_STR_CONTAINS, needle, negate); }
     ColumnPtr startsWith(std::string_view needle, bool negate = false) const { return match(CHGPU_STR_STARTS_WITH, needle, negate); }
@@ -2142,6 +2160,46 @@ inline void sortBlock(Chunk & block, const SortDescription & description, uint64
     }
     if (take)
         block.num_rows = take;
+}
+
+/// sortBlock over a Block that carries String columns.  A Chunk holds ColumnVectors; the Block's ColumnStrings travel beside it in
+/// `strings`, and a description addresses them behind the Chunk's own columns: column_number < block.columns.size() is that ColumnVector,
+/// column_number - block.columns.size() indexes `strings`.  Every column of both lists is permuted.  nulls_direction of a String entry is
+/// ignored; a String key that is the most significant column takes the limit into its own sort, otherwise the permutation is cut.
+inline void sortBlock(Chunk & block, std::vector<ColumnString> & strings, const SortDescription & description, uint64_t limit = 0)
+{
+    if (strings.empty())
+        return sortBlock(block, description, limit);
+    const size_t n_vec = block.columns.size();
+    const uint64_t rows = strings[0].offsets->size();
+    if (description.empty() || rows == 0)
+        return;
+    ContextPtr ctx = strings[0].offsets->context();
+    chgpu_col * perm = nullptr;
+    for (size_t k = description.size(); k-- > 0;)
+    {
+        const auto & d = description[k];
+        chgpu_col * next = nullptr;
+        int rc;
+        if (d.column_number < n_vec)
+            rc = chgpu_sort_permutation(ctx->get(), block.columns[d.column_number]->handle(), perm, d.direction < 0, d.nulls_direction, &next);
+        else
+        {
+            const ColumnString & s = strings.at(d.column_number - n_vec);
+            rc = chgpu_string_sort_permutation(ctx->get(), s.offsets->handle(), s.chars->handle(), perm, d.direction < 0, k == 0 ? limit : 0, &next);
+        }
+        if (perm)
+            chgpu_col_free(perm);
+        check(rc);
+        perm = next;
+    }
+    ColumnVector permutation(ctx, perm);
+    const uint64_t take = limit && limit < rows ? limit : 0;
+    for (auto & col : block.columns)
+        col = col->index(permutation, take);
+    for (auto & s : strings)
+        s = s.permute(permutation, take);
+    block.num_rows = take ? take : rows;
 }
 
 /// CompressedReadBuffer + SerializationNumber::deserializeBinaryBulk for one numeric column file (MergeTree `<column>.bin`): the

@@ -116,6 +116,23 @@ class ColumnString:
         K.check(K.lib().chgpu_string_filter(ctx._h, self.offsets._h, self.chars._h, filt._h, C.byref(oo), C.byref(oc), C.byref(rows)))
         return ColumnString(Column(ctx, oo), Column(ctx, oc))
 
+    def get_permutation(self, perm_in: Column | None = None, descending: bool = False, limit: int = 0) -> Column:
+        """ColumnString::getPermutation(direction, Stable, limit) without collation -> UInt64 permutation Column: unsigned bytes, then
+        the shorter value is the smaller; equal values keep their incoming order (row order, or perm_in order) in both directions.
+        perm_in composes a previous (less significant) sort; 0 < limit < rows returns the first `limit` entries of the full permutation."""
+        h = C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(K.lib().chgpu_string_sort_permutation(ctx._h, self.offsets._h, self.chars._h, perm_in._h if perm_in is not None else None,
+                                                      1 if descending else 0, int(limit), C.byref(h)))
+        return Column(ctx, h)
+
+    def index(self, perm: Column, limit: int = 0) -> "ColumnString":
+        """ColumnString::permute / index: out[i] = value[perm[i]], i < (limit ? min(limit, perm.size()) : perm.size())"""
+        oo, oc = C.c_void_p(), C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(K.lib().chgpu_string_index(ctx._h, self.offsets._h, self.chars._h, perm._h, int(limit), C.byref(oo), C.byref(oc)))
+        return ColumnString(Column(ctx, oo), Column(ctx, oc))
+
     # -- predicates against a constant: a UInt8 Column of 0/1, one per row (the mask filter / and_ / execute_on_block(filter=) take) --
     def compare(self, op: int, value) -> Column:
         """equals .. greaterOrEquals (EQ .. GE) against a constant String: unsigned bytes, then the shorter one is the smaller

@@ -572,6 +572,28 @@ int chgpu_string_dictionary_encode(chgpu_ctx * ctx, const chgpu_col * offsets_u6
    whose filter byte is non-zero, in order, as a new ColumnString (offsets rebuilt, bytes moved together). */
 int chgpu_string_filter(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const chgpu_col * filter_u8,
                         chgpu_col ** out_offsets_u64, chgpu_col ** out_chars_u8, uint64_t * rows_out);
+/* §8(f) rank 4 over Strings -- ColumnString::getPermutation(direction, Stable, limit, ...) without collation (src/Columns/ColumnString.cpp),
+   the String half of sortBlock.  Order: values compare as UNSIGNED bytes over the first min(len_a, len_b) bytes, then the shorter value is
+   the smaller one; lengths exclude the terminating zero (the rule of chgpu_string_cmp_const).  Binary-safe: zero bytes and bytes >= 0x80
+   inside values are ordinary bytes, "ab" < "ab\0" < "ab\0\0" < "ab\1".  Stable: equal values keep their incoming order in both directions
+   (descending reverses the comparison, not the row order among ties); the incoming order is row order, or perm_in order when perm_in is
+   given -- the permutation is unique.  perm_in_u64 (may be NULL) as in chgpu_sort_permutation: sort the rows perm_in[i] and return the
+   composed permutation, so ORDER BY a, s is "sort by s, then stably by a" with either kind of column in either place; perm_in.rows > rows
+   answers CHGPU_ERR_SIZES_MISMATCH, an entry >= rows is treated as row 0 and never faults.  limit (0 = none): with 0 < limit < n the
+   result has `limit` rows, exactly the first `limit` entries of the full stable permutation (also with perm_in: the most significant
+   column of a description can take the query's LIMIT).  An MSD sort in 8-byte words, every round the stable radix passes of
+   chgpu_sort_permutation over the rows still undecided; a prefix shared by all rows of a tie costs no rounds.
+   Offsets that break the ColumnString invariant answer CHGPU_ERR_BAD_ARGUMENTS, as do wrong column types and NULL arguments; zero rows
+   give an empty column; chars needs the same 8 readable bytes after its end as for chgpu_string_dictionary_encode.  2^32 rows or more
+   answer CHGPU_ERR_NOT_IMPLEMENTED.  Not included: collations, Nullable(String), FixedString, a sampled-threshold LIMIT path. */
+int chgpu_string_sort_permutation(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const chgpu_col * perm_in_u64,
+                                  int descending, uint64_t limit, chgpu_col ** perm_out_u64);
+/* ColumnString::permute / index (ColumnString.cpp, indexImpl): out[i] = value[indexes[i]], i < (limit ? min(limit, indexes.rows) :
+   indexes.rows), as a new ColumnString: offsets rebuilt, every value followed by its zero byte.  Repeated indexes are allowed; indexes must
+   be CHGPU_U64; an index >= rows answers CHGPU_ERR_BAD_ARGUMENTS (a device flag, never a fault), a value of 4 GiB or more
+   CHGPU_ERR_NOT_IMPLEMENTED.  Offsets, types, NULL arguments, zero rows and the 8 readable bytes after chars: as above. */
+int chgpu_string_index(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const chgpu_col * indexes_u64,
+                       uint64_t limit, chgpu_col ** out_offsets_u64, chgpu_col ** out_chars_u8);
 /* ---- String predicates against a constant: a WHERE clause over a ColumnString -> a UInt8 column of 0/1, one byte per row (the mask
    chgpu_filter* / chgpu_and / chgpu_agg_add_block_filtered / chgpu_string_filter take).  Values, constants and patterns are binary-safe
    (zero bytes, bytes >= 0x80); `value` / `pattern` are host memory, no terminator, at most CHGPU_STR_CONST_MAX bytes -- a longer one
