@@ -15,6 +15,8 @@
 // Algorithmic bytes: compressed size read + decompressed size written (match sources are re-reads of fresh output: L1/L2).
 #include "chgpu_internal.h"
 
+#include <memory>
+
 struct FrameJob
 {
     u64 src_off;  // payload begin in the compressed buffer
@@ -32,49 +34,6 @@ struct FrameJob
 __device__ __forceinline__ u32 uni(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ u64 uni64(u64 v) { return ((u64)uni((u32)(v >> 32)) << 32) | uni((u32)v); }
 
-// Where codec M of a frame reads and writes.  stage == nullptr: the frames that ARE an application of M (CODEC(T64) alone).  Otherwise the
-// frames whose general-purpose stage left M's block in the stage buffer (CompressionCodecMultiple.cpp:68-130: every stage carries its own
-// 9-byte header -- method, compressed size incl. the header, decompressed size -- which must agree with what the outer frame promised).
-struct CodecIo
-{
-    const u8 * in;
-    u8 * out;
-    u32 isz, osz;
-    bool take, bad;
-};
-__device__ __forceinline__ CodecIo codec_io(const FrameJob & job, u32 M, const u8 * src, const u8 * stage, u8 * dst_out)
-{
-    CodecIo io{nullptr, nullptr, 0, 0, false, false};
-    if (!stage)
-    {
-        if (job.method != M)
-            return io;
-        io.take = true;
-        io.in = src + job.src_off;
-        io.out = dst_out + job.dst_off;
-        io.isz = job.src_size;
-        io.osz = job.dst_size;
-        return io;
-    }
-    if (job.post != M)
-        return io;
-    io.take = true;
-    const u8 * h = stage + job.dst_off;
-    const u32 ssz = job.dst_size;
-    if (ssz < 9)
-    {
-        io.bad = true;
-        return io;
-    }
-    const u32 csize = (u32)h[1] | ((u32)h[2] << 8) | ((u32)h[3] << 16) | ((u32)h[4] << 24), dsize = (u32)h[5] | ((u32)h[6] << 8) | ((u32)h[7] << 16) | ((u32)h[8] << 24);
-    io.bad = h[0] != M || csize != ssz || dsize != job.out_size;
-    io.in = h + 9;
-    io.isz = ssz - 9;
-    io.out = dst_out + job.out_off;
-    io.osz = job.out_size;
-    return io;
-}
-
 // Per wave: a window of the compressed input and a ring of the most recent output live in LDS, so the serial part of the format --
 // token, length bytes, offset -- and the short-distance matches that dominate column data (zero bytes 8 back, the previous value 8
 // back, runs) never wait for a global load: the first version read everything through global memory and spent ~1.7 us per
@@ -83,6 +42,20 @@ static constexpr u32 LZ_IN = 1024;    // input window bytes per wave
 static constexpr u32 LZ_RING = 4096;  // output ring bytes per wave (matches up to LZ_RING / 2 back are served from it); 20 KiB of LDS per
                                       // workgroup keeps 8 workgroups = 32 frames per CU in flight (8 KiB rings: 3 workgroups, two rounds for 6 K frames)
 static constexpr u32 LZ_CHUNK = LZ_RING / 2;
+
+// The copy of the general path: byte k of n is source(k); it goes to the output and into the ring.  LAST_ONLY (a compile-time choice): a run
+// that may be longer than the ring keeps only its last LZ_RING bytes there (and each ring byte is written once).
+template <bool LAST_ONLY, typename Source>
+__device__ __forceinline__ void lz_copy(u32 n, u32 lane, u8 * out, u8 * ring, u32 op, Source source)
+{
+    for (u32 k = lane; k < n; k += 64)
+    {
+        const u8 v = source(k);
+        out[op + k] = v;
+        if (!LAST_ONLY || n - k <= LZ_RING)
+            ring[(op + k) & (LZ_RING - 1)] = v;
+    }
+}
 
 __global__ __launch_bounds__(256) void k_lz4_decode(const u8 * __restrict__ src, u8 * dst_out, u8 * dst_stage, const FrameJob * __restrict__ jobs, u32 n_jobs, u32 * __restrict__ err)
 {
@@ -140,6 +113,19 @@ __global__ __launch_bounds__(256) void k_lz4_decode(const u8 * __restrict__ src,
                 }
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
             }
+            return true;
+        };
+        // the length bytes behind a token field of 15: every byte adds to len, the last one is below 255; false where the frame ends first
+        auto length_bytes = [&](u32 & len) -> bool {
+            u32 b;
+            do
+            {
+                if (!window(ip, 1))
+                    return false;
+                b = uni(lin[ip - in_base]);
+                ++ip;
+                len += b;
+            } while (b == 255);
             return true;
         };
         while (true)
@@ -205,22 +191,10 @@ __global__ __launch_bounds__(256) void k_lz4_decode(const u8 * __restrict__ src,
             const u32 token = uni(lin[ip - in_base]);
             ++ip;
             u32 lit = token >> 4;
-            if (lit == 15)
+            if (lit == 15 && !length_bytes(lit))
             {
-                u32 b;
-                do
-                {
-                    if (!window(ip, 1))
-                    {
-                        bad = true;
-                        break;
-                    }
-                    b = uni(lin[ip - in_base]);
-                    ++ip;
-                    lit += b;
-                } while (b == 255);
-                if (bad)
-                    break;
+                bad = true;
+                break;
             }
             if (lit > isz - ip || lit > osz - op)
             {
@@ -229,25 +203,10 @@ __global__ __launch_bounds__(256) void k_lz4_decode(const u8 * __restrict__ src,
             }
             if (lit)
             {
-                if (ip >= in_base && ip + lit <= in_base + in_len)
-                {
-                    for (u32 k = lane; k < lit; k += 64) // literals out of the LDS window
-                    {
-                        const u8 v = lin[ip - in_base + k];
-                        out[op + k] = v;
-                        ring[(op + k) & (LZ_RING - 1)] = v;
-                    }
-                }
-                else
-                {
-                    for (u32 k = lane; k < lit; k += 64) // a long literal run: straight from the compressed buffer
-                    {
-                        const u8 v = in[ip + k];
-                        out[op + k] = v;
-                        if (lit - k <= LZ_RING) // only the last LZ_RING bytes matter (and each ring byte is written once)
-                            ring[(op + k) & (LZ_RING - 1)] = v;
-                    }
-                }
+                if (ip >= in_base && ip + lit <= in_base + in_len) // literals out of the LDS window
+                    lz_copy<false>(lit, lane, out, ring, op, [&](u32 k) { return lin[ip - in_base + k]; });
+                else // a long literal run: straight from the compressed buffer
+                    lz_copy<true>(lit, lane, out, ring, op, [&](u32 k) { return in[ip + k]; });
                 ip += lit;
                 op += lit;
             }
@@ -261,22 +220,10 @@ __global__ __launch_bounds__(256) void k_lz4_decode(const u8 * __restrict__ src,
             const u32 offset = uni((u32)lin[ip - in_base] | ((u32)lin[ip - in_base + 1] << 8));
             ip += 2;
             u32 ml = token & 15;
-            if (ml == 15)
+            if (ml == 15 && !length_bytes(ml))
             {
-                u32 b;
-                do
-                {
-                    if (!window(ip, 1))
-                    {
-                        bad = true;
-                        break;
-                    }
-                    b = uni(lin[ip - in_base]);
-                    ++ip;
-                    ml += b;
-                } while (b == 255);
-                if (bad)
-                    break;
+                bad = true;
+                break;
             }
             ml += 4;
             if (offset == 0 || offset > op || ml > osz - op)
@@ -294,23 +241,9 @@ __global__ __launch_bounds__(256) void k_lz4_decode(const u8 * __restrict__ src,
                     const u32 c = ml < LZ_CHUNK ? ml : LZ_CHUNK;
                     const u32 wbase = op - offset;
                     if (offset >= c)
-                    {
-                        for (u32 k = lane; k < c; k += 64)
-                        {
-                            const u8 v = ring[(wbase + k) & (LZ_RING - 1)];
-                            out[op + k] = v;
-                            ring[(op + k) & (LZ_RING - 1)] = v;
-                        }
-                    }
+                        lz_copy<false>(c, lane, out, ring, op, [&](u32 k) { return ring[(wbase + k) & (LZ_RING - 1)]; });
                     else
-                    {
-                        for (u32 k = lane; k < c; k += 64)
-                        {
-                            const u8 v = ring[(wbase + k % offset) & (LZ_RING - 1)];
-                            out[op + k] = v;
-                            ring[(op + k) & (LZ_RING - 1)] = v;
-                        }
-                    }
+                        lz_copy<false>(c, lane, out, ring, op, [&](u32 k) { return ring[(wbase + k % offset) & (LZ_RING - 1)]; });
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     op += c;
                     ml -= c;
@@ -323,25 +256,9 @@ __global__ __launch_bounds__(256) void k_lz4_decode(const u8 * __restrict__ src,
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 const u8 * win = out + (op - offset);
                 if (offset >= ml)
-                {
-                    for (u32 k = lane; k < ml; k += 64)
-                    {
-                        const u8 v = win[k];
-                        out[op + k] = v;
-                        if (ml - k <= LZ_RING)
-                            ring[(op + k) & (LZ_RING - 1)] = v;
-                    }
-                }
+                    lz_copy<true>(ml, lane, out, ring, op, [&](u32 k) { return win[k]; });
                 else
-                {
-                    for (u32 k = lane; k < ml; k += 64)
-                    {
-                        const u8 v = win[k % offset];
-                        out[op + k] = v;
-                        if (ml - k <= LZ_RING)
-                            ring[(op + k) & (LZ_RING - 1)] = v;
-                    }
-                }
+                    lz_copy<true>(ml, lane, out, ring, op, [&](u32 k) { return win[k % offset]; });
                 __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                 op += ml;
             }
@@ -351,6 +268,94 @@ __global__ __launch_bounds__(256) void k_lz4_decode(const u8 * __restrict__ src,
         if (bad && lane == 0)
             atomicOr(err, 2u);
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The column codecs: Delta, T64, DoubleDelta, Gorilla.  What they share comes first.
+// ---------------------------------------------------------------------------------------------
+typedef u64 u64_a1 __attribute__((aligned(1)));
+typedef u32 u32_a1 __attribute__((aligned(1)));
+typedef u16 u16_a1 __attribute__((aligned(1)));
+
+// the bits of a value of `width` bytes
+__device__ __forceinline__ u64 width_mask(u32 width) { return width == 8 ? ~0ull : ((1ull << (8 * width)) - 1); }
+
+// one value of `width` bytes stored with ONE instruction (a memcpy of a run-time width is a byte loop)
+__device__ __forceinline__ void codec_store(u8 * d, u64 v, u32 width)
+{
+    if (width == 8)
+        *(u64_a1 *)d = v;
+    else if (width == 4)
+        *(u32_a1 *)d = (u32)v;
+    else if (width == 2)
+        *(u16_a1 *)d = (u16)v;
+    else
+        *d = (u8)v;
+}
+
+// Where codec M of a frame reads and writes.  stage == nullptr: the frames that ARE an application of M (CODEC(T64) alone).  Otherwise the
+// frames whose general-purpose stage left M's block in the stage buffer (CompressionCodecMultiple.cpp:68-130: every stage carries its own
+// 9-byte header -- method, compressed size incl. the header, decompressed size -- which must agree with what the outer frame promised).
+struct CodecIo
+{
+    const u8 * in;
+    u8 * out;
+    u32 isz, osz;
+    bool take, bad;
+};
+__device__ __forceinline__ CodecIo codec_io(const FrameJob & job, u32 M, const u8 * src, const u8 * stage, u8 * dst_out)
+{
+    CodecIo io{nullptr, nullptr, 0, 0, false, false};
+    if (!stage)
+    {
+        if (job.method != M)
+            return io;
+        io.take = true;
+        io.in = src + job.src_off;
+        io.out = dst_out + job.dst_off;
+        io.isz = job.src_size;
+        io.osz = job.dst_size;
+        return io;
+    }
+    if (job.post != M)
+        return io;
+    io.take = true;
+    const u8 * h = stage + job.dst_off;
+    const u32 ssz = job.dst_size;
+    if (ssz < 9)
+    {
+        io.bad = true;
+        return io;
+    }
+    const u32 csize = (u32)h[1] | ((u32)h[2] << 8) | ((u32)h[3] << 16) | ((u32)h[4] << 24), dsize = (u32)h[5] | ((u32)h[6] << 8) | ((u32)h[7] << 16) | ((u32)h[8] << 24);
+    io.bad = h[0] != M || csize != ssz || dsize != job.out_size;
+    io.in = h + 9;
+    io.isz = ssz - 9;
+    io.out = dst_out + job.out_off;
+    io.osz = job.out_size;
+    return io;
+}
+
+// [element width][bytes_to_skip][skipped bytes] in front of a Delta / DoubleDelta / Gorilla payload: the width is 1, 2, 4 or 8 and
+// bytes_to_skip = size % width (CompressionCodecDelta.cpp:109-133: a header that claims more is malformed), inside the payload and the
+// output.  pay / out: what follows the skipped bytes.  Copying them is the caller's (one byte per lane, or a loop in one lane).
+struct WidthSkip
+{
+    const u8 * pay;
+    u8 * out;
+    u32 width, skip;
+    bool bad;
+};
+__device__ __forceinline__ WidthSkip width_skip(const CodecIo & io)
+{
+    WidthSkip h{nullptr, nullptr, 0, 0, io.bad || io.isz < 2};
+    if (h.bad)
+        return h;
+    h.width = io.in[0], h.skip = io.in[1];
+    h.bad = !(h.width == 1 || h.width == 2 || h.width == 4 || h.width == 8) || h.skip >= h.width || h.skip > io.osz || 2 + h.skip > io.isz;
+    h.pay = io.in + 2 + h.skip;
+    h.out = io.out + h.skip;
+    return h;
 }
 
 // CompressionCodecDelta::doDecompressData (src/Compression/CompressionCodecDelta.cpp:84-175) as the second stage of
@@ -391,34 +396,24 @@ __device__ __forceinline__ void delta_frame(const u8 * __restrict__ pay, u32 n_e
     }
 }
 
-__global__ __launch_bounds__(256) void k_delta_decode(const u8 * __restrict__ stage, u8 * __restrict__ dst_out, const FrameJob * __restrict__ jobs, u32 n_jobs,
-                                                      u32 * __restrict__ err)
+__global__ __launch_bounds__(256) void k_delta_decode(const u8 * __restrict__ src, const u8 * __restrict__ stage, u8 * __restrict__ dst_out, const FrameJob * __restrict__ jobs,
+                                                      u32 n_jobs, u32 * __restrict__ err)
 {
     const u32 lane = threadIdx.x & 63;
     const u32 wave0 = (blockIdx.x * 256 + threadIdx.x) >> 6, n_waves = (gridDim.x * 256) >> 6;
     for (u32 j = wave0; j < n_jobs; j += n_waves)
     {
         const FrameJob job = jobs[j];
-        if (job.post != 0x92u)
+        const CodecIo io = codec_io(job, 0x92u, src, stage, dst_out);
+        if (!io.take)
             continue;
-        const u8 * in = stage + job.dst_off; // the LZ4 stage's output: [method][compressed size][decompressed size][payload]
-        const u32 ssz = job.dst_size;
-        bool bad = ssz < 11;
-        u32 w = 0, skip = 0, n_bytes = 0;
+        const WidthSkip h = width_skip(io); // (skip < width: the copy below moves one byte per lane)
+        bool bad = h.bad;
+        u32 n_bytes = 0;
         if (!bad)
         {
-            u32 csize, dsize;
-            __builtin_memcpy(&csize, in + 1, 4);
-            __builtin_memcpy(&dsize, in + 5, 4);
-            w = in[9], skip = in[10];
-            bad = in[0] != 0x92 || csize != ssz || dsize != job.out_size || !(w == 1 || w == 2 || w == 4 || w == 8) || skip >= w || 11 + skip > ssz || skip > job.out_size;
-            // (bytes_to_skip = size % width, CompressionCodecDelta.cpp:109-133: a header that claims more is malformed -- and the copy
-            //  below moves one byte per lane, i.e. at most 63)
-            if (!bad)
-            {
-                n_bytes = ssz - 11 - skip;
-                bad = n_bytes != job.out_size - skip || n_bytes % w != 0;
-            }
+            n_bytes = io.isz - 2 - h.skip;
+            bad = n_bytes != io.osz - h.skip || n_bytes % h.width != 0;
         }
         if (__builtin_amdgcn_readfirstlane((int)bad))
         {
@@ -426,16 +421,14 @@ __global__ __launch_bounds__(256) void k_delta_decode(const u8 * __restrict__ st
                 atomicOr(err, 4u);
             continue;
         }
-        u8 * out = dst_out + job.out_off;
-        if (lane < skip)
-            out[lane] = in[11 + lane];
-        const u8 * pay = in + 11 + skip;
-        switch (w)
+        if (lane < h.skip)
+            io.out[lane] = io.in[2 + lane];
+        switch (h.width)
         {
-            case 1: delta_frame<u8>(pay, n_bytes, out + skip, lane); break;
-            case 2: delta_frame<u16>(pay, n_bytes / 2, out + skip, lane); break;
-            case 4: delta_frame<u32>(pay, n_bytes / 4, out + skip, lane); break;
-            default: delta_frame<u64>(pay, n_bytes / 8, out + skip, lane); break;
+            case 1: delta_frame<u8>(h.pay, n_bytes, h.out, lane); break;
+            case 2: delta_frame<u16>(h.pay, n_bytes / 2, h.out, lane); break;
+            case 4: delta_frame<u32>(h.pay, n_bytes / 4, h.out, lane); break;
+            default: delta_frame<u64>(h.pay, n_bytes / 8, h.out, lane); break;
         }
     }
 }
@@ -515,7 +508,7 @@ __global__ __launch_bounds__(256) void k_t64_decode(const u8 * __restrict__ src,
                 atomicOr(err, 8u);
             continue;
         }
-        const u64 M = width == 8 ? ~0ull : ((1ull << (8 * width)) - 1);
+        const u64 M = width_mask(width);
         if (!num_bits)
         {
             for (u64 i = threadIdx.x; i < n; i += 256)
@@ -569,22 +562,6 @@ __global__ __launch_bounds__(256) void k_t64_decode(const u8 * __restrict__ src,
 // the frame is decoded front to back, here by ONE LANE PER FRAME -- the parallelism is across frames (a column file of N rows has
 // N / 8192 ... N / 131072 of them).  Functional first: the rate is reported in profiles/, not tuned.
 // ---------------------------------------------------------------------------------------------
-// one value of `width` bytes stored with ONE instruction (a memcpy of a run-time width is a byte loop)
-__device__ __forceinline__ void codec_store(u8 * d, u64 v, u32 width)
-{
-    typedef u64 u64_a1 __attribute__((aligned(1)));
-    typedef u32 u32_a1 __attribute__((aligned(1)));
-    typedef u16 u16_a1 __attribute__((aligned(1)));
-    if (width == 8)
-        *(u64_a1 *)d = v;
-    else if (width == 4)
-        *(u32_a1 *)d = (u32)v;
-    else if (width == 2)
-        *(u16_a1 *)d = (u16)v;
-    else
-        *d = (u8)v;
-}
-
 struct DdReader
 {
     // A lane is alone with its frame: every load is a full memory round trip with nothing else to hide it, so the reader keeps DEPTH
@@ -598,7 +575,6 @@ struct DdReader
     u32 bits;
     u64 q[DEPTH];
     u32 qn; // words in the queue
-    typedef u64 u64_a1 __attribute__((aligned(1)));
     // (every index into q[] is a compile-time constant: a run-time index would move the queue to scratch memory)
     __device__ __forceinline__ u64 request()
     {
@@ -680,52 +656,70 @@ struct DdReader
     }
 };
 
-__global__ __launch_bounds__(64) void k_double_delta_decode(const u8 * __restrict__ src, const u8 * __restrict__ stage, u8 * __restrict__ dst_out, const FrameJob * __restrict__ jobs,
-                                                            u32 n_jobs, u32 * __restrict__ err)
+// The opening both bit-stream codecs share: lane j's frame, its input and output (codec_io), [width][bytes_to_skip][skipped bytes], then
+// [items u32][first value].  The first value is stored and the positions stand behind it.  false = this lane is done: the frame is not
+// M's, or it is refused (err_bit is set), or -- silently, as in the reference -- the payload ends before the first value or items is 0.
+// enough_room(items, width, room) is the codec's own check of the output before the first store.
+struct BitStreamFrame
+{
+    const u8 * s, * s_end; // the payload behind the first value
+    u8 * d, * d_end;       // the output behind the first value
+    u32 width, items;
+    u64 M, first;
+};
+template <typename EnoughRoom>
+__device__ __forceinline__ bool bit_stream_open(BitStreamFrame & f, u32 M, u32 err_bit, EnoughRoom enough_room, const u8 * src, const u8 * stage, u8 * dst_out, const FrameJob * jobs,
+                                                u32 n_jobs, u32 * err)
 {
     const u32 j = blockIdx.x * 64 + threadIdx.x;
     if (j >= n_jobs)
-        return;
+        return false;
     const FrameJob job = jobs[j];
-    const CodecIo io = codec_io(job, 0x94u, src, stage, dst_out);
+    const CodecIo io = codec_io(job, M, src, stage, dst_out);
     if (!io.take)
-        return;
-    const u8 * in = io.in;
-    u8 * out = io.out;
-    const u32 isz = io.isz, osz = io.osz;
-    if (io.bad || isz < 2)
+        return false;
+    const WidthSkip h = width_skip(io);
+    if (h.bad)
     {
-        atomicOr(err, 16u);
-        return;
+        atomicOr(err, err_bit);
+        return false;
     }
-    const u32 width = in[0], skip = in[1];
-    if (!(width == 1 || width == 2 || width == 4 || width == 8) || skip >= width || skip > osz || 2 + skip > isz)
+    for (u32 k = 0; k < h.skip; ++k)
+        io.out[k] = io.in[2 + k];
+    f.width = h.width;
+    f.M = width_mask(h.width);
+    f.s = h.pay, f.s_end = io.in + io.isz;
+    f.d = h.out, f.d_end = io.out + io.osz;
+    if (f.s + 4 > f.s_end)
+        return false;
+    __builtin_memcpy(&f.items, f.s, 4);
+    f.s += 4;
+    if (f.s + f.width > f.s_end || f.items < 1)
+        return false;
+    if (!enough_room(f.items, f.width, (u32)(f.d_end - f.d)))
     {
-        atomicOr(err, 16u);
-        return;
+        atomicOr(err, err_bit);
+        return false;
     }
-    for (u32 k = 0; k < skip; ++k)
-        out[k] = in[2 + k];
-    const u8 * s = in + 2 + skip, * s_end = in + isz;
-    u8 * d = out + skip, * d_end = out + osz;
-    if (s + 4 > s_end)
+    f.first = 0;
+    __builtin_memcpy(&f.first, f.s, f.width);
+    codec_store(f.d, f.first, f.width);
+    f.s += f.width;
+    f.d += f.width;
+    return true;
+}
+
+__global__ __launch_bounds__(64) void k_double_delta_decode(const u8 * __restrict__ src, const u8 * __restrict__ stage, u8 * __restrict__ dst_out, const FrameJob * __restrict__ jobs,
+                                                            u32 n_jobs, u32 * __restrict__ err)
+{
+    BitStreamFrame f;
+    if (!bit_stream_open(f, 0x94u, 16u, [](u32, u32 width, u32 room) { return width <= room; }, src, stage, dst_out, jobs, n_jobs, err))
         return;
-    u32 items;
-    __builtin_memcpy(&items, s, 4);
-    s += 4;
-    const u64 M = width == 8 ? ~0ull : ((1ull << (8 * width)) - 1);
-    if (s + width > s_end || items < 1)
-        return;
-    u64 prev_value = 0, prev_delta = 0;
-    __builtin_memcpy(&prev_value, s, width);
-    if (d + width > d_end)
-    {
-        atomicOr(err, 16u);
-        return;
-    }
-    __builtin_memcpy(d, &prev_value, width);
-    s += width;
-    d += width;
+    const u8 * s = f.s, * s_end = f.s_end;
+    u8 * d = f.d, * d_end = f.d_end; // (every store is checked against it: `items` need not agree with the frame's size)
+    const u32 width = f.width, items = f.items;
+    const u64 M = f.M;
+    u64 prev_value = f.first, prev_delta = 0;
     if (s + width > s_end || items < 2)
         return;
     __builtin_memcpy(&prev_delta, s, width);
@@ -735,7 +729,7 @@ __global__ __launch_bounds__(64) void k_double_delta_decode(const u8 * __restric
         atomicOr(err, 16u);
         return;
     }
-    __builtin_memcpy(d, &prev_value, width);
+    codec_store(d, prev_value, width);
     s += width;
     d += width;
     DdReader r;
@@ -779,50 +773,16 @@ __global__ __launch_bounds__(64) void k_double_delta_decode(const u8 * __restric
 __global__ __launch_bounds__(64) void k_gorilla_decode(const u8 * __restrict__ src, const u8 * __restrict__ stage, u8 * __restrict__ dst_out, const FrameJob * __restrict__ jobs, u32 n_jobs,
                                                        u32 * __restrict__ err)
 {
-    const u32 j = blockIdx.x * 64 + threadIdx.x;
-    if (j >= n_jobs)
+    BitStreamFrame f;
+    // (all of the frame's values fit, checked once: the stores below are not checked one by one)
+    if (!bit_stream_open(f, 0x95u, 32u, [](u32 items, u32 width, u32 room) { return (u64)items * width <= room; }, src, stage, dst_out, jobs, n_jobs, err))
         return;
-    const FrameJob job = jobs[j];
-    const CodecIo io = codec_io(job, 0x95u, src, stage, dst_out);
-    if (!io.take)
-        return;
-    const u8 * in = io.in;
-    u8 * out = io.out;
-    const u32 isz = io.isz, osz = io.osz;
-    if (io.bad || isz < 2)
-    {
-        atomicOr(err, 32u);
-        return;
-    }
-    const u32 width = in[0], skip = in[1];
-    if (!(width == 1 || width == 2 || width == 4 || width == 8) || skip >= width || skip > osz || 2 + skip > isz)
-    {
-        atomicOr(err, 32u);
-        return;
-    }
-    for (u32 k = 0; k < skip; ++k)
-        out[k] = in[2 + k];
+    const u8 * s = f.s, * s_end = f.s_end;
+    u8 * d = f.d;
+    const u32 width = f.width, items = f.items;
+    const u64 M = f.M;
     const u32 X = 8 * width, DBL = width == 1 ? 4u : width == 2 ? 5u : width == 4 ? 6u : 7u, LZL = DBL - 1;
-    const u8 * s = in + 2 + skip, * s_end = in + isz;
-    u8 * d = out + skip;
-    if (s + 4 > s_end)
-        return;
-    u32 items;
-    __builtin_memcpy(&items, s, 4);
-    s += 4;
-    if (s + width > s_end || items < 1)
-        return;
-    if ((u64)items * width > osz - skip)
-    {
-        atomicOr(err, 32u);
-        return;
-    }
-    const u64 M = width == 8 ? ~0ull : ((1ull << X) - 1);
-    u64 prev = 0;
-    __builtin_memcpy(&prev, s, width);
-    __builtin_memcpy(d, &prev, width);
-    s += width;
-    d += width;
+    u64 prev = f.first;
     DdReader r;
     r.init(s, s_end);
     u32 p_lz = 0, p_db = 0, p_tz = 0;
@@ -854,6 +814,52 @@ __global__ __launch_bounds__(64) void k_gorilla_decode(const u8 * __restrict__ s
     }
 }
 
+// The column codecs the device decodes, in launch order.  A codec kernel takes the frames that are one application of it (stage == nullptr;
+// only where `alone`) or the frames whose general-purpose stage left its block in the stage buffer.
+typedef void (*CodecKernel)(const u8 *, const u8 *, u8 *, const FrameJob *, u32, u32 *);
+enum CodecGeometry
+{
+    WAVE_PER_FRAME,      // the LZ4 grid: a wave per frame, the waves take further frames in turn
+    WORKGROUP_PER_FRAME, // min(n_frames, 4096) x 256
+    LANE_PER_FRAME,      // ceil(n_frames / 64) x 64
+};
+struct DeviceCodec
+{
+    u8 method;
+    CodecKernel kernel;
+    CodecGeometry geometry;
+    bool alone;
+};
+static const DeviceCodec DEVICE_CODECS[] = {
+    {0x92, k_delta_decode, WAVE_PER_FRAME, false},
+    {0x93, k_t64_decode, WORKGROUP_PER_FRAME, true},
+    {0x94, k_double_delta_decode, LANE_PER_FRAME, true},
+    {0x95, k_gorilla_decode, LANE_PER_FRAME, true},
+};
+static constexpr u32 N_DEVICE_CODECS = sizeof(DEVICE_CODECS) / sizeof(DEVICE_CODECS[0]);
+using DeviceFrameMethods = OneOf<0x82, 0x02, 0x93, 0x94, 0x95>; // LZ4, NONE and the codecs that can stand alone
+
+// the table row of a method byte; N_DEVICE_CODECS = none
+static u32 device_codec_row(u32 method)
+{
+    u32 c = 0;
+    while (c < N_DEVICE_CODECS && DEVICE_CODECS[c].method != method)
+        ++c;
+    return c;
+}
+
+// blocks x threads of a codec kernel over n_frames frames; lz4_grid = the blocks k_lz4_decode runs with
+static void codec_launch_shape(CodecGeometry geometry, u32 lz4_grid, u32 n_frames, u32 & blocks, u32 & threads)
+{
+    threads = geometry == LANE_PER_FRAME ? 64 : 256;
+    switch (geometry)
+    {
+        case WAVE_PER_FRAME: blocks = lz4_grid; break;
+        case WORKGROUP_PER_FRAME: blocks = n_frames < 4096 ? n_frames : 4096; break;
+        default: blocks = (n_frames + 63) / 64; break;
+    }
+}
+
 /* Decompress n_frames frames of `compressed_u8` into one new UInt8 column of sum(decompressed_sizes) bytes.  Host arrays describe the
    frames: payload offset / size inside compressed_u8 and method byte of the (last applied) general-purpose stage, its output size
    (stage_sizes; NULL = decompressed_sizes) and, for CODEC(Delta, LZ4), post_methods[f] = 0x92 (NULL / 0 = single stage).
@@ -868,23 +874,17 @@ extern "C" int chgpu_decompress_frames(chgpu_ctx * ctx, const chgpu_col * compre
     CHGPU_REQUIRE(n_frames == 0 || (payload_offsets && payload_sizes && decompressed_sizes && methods), CHGPU_ERR_BAD_ARGUMENTS, "NULL frame arrays");
     std::vector<FrameJob> jobs(n_frames);
     u64 total = 0, stage_total = 0;
-    u32 n_t64 = 0, n_dd = 0, n_gor = 0, p_delta = 0, p_t64 = 0, p_dd = 0, p_gor = 0;
+    u32 n_as_method[N_DEVICE_CODECS + 1] = {}, n_as_post[N_DEVICE_CODECS + 1] = {}; // frames per table row (the last entry: no codec)
     for (u32 f = 0; f < n_frames; ++f)
     {
-        CHGPU_REQUIRE(methods[f] == 0x82 || methods[f] == 0x02 || methods[f] == 0x93 || methods[f] == 0x94 || methods[f] == 0x95, CHGPU_ERR_NOT_IMPLEMENTED,
-                      "compression method 0x%02x: CPU path", methods[f]);
-        n_t64 += methods[f] == 0x93;
-        n_dd += methods[f] == 0x94;
-        n_gor += methods[f] == 0x95;
+        CHGPU_REQUIRE(DeviceFrameMethods::has(methods[f]), CHGPU_ERR_NOT_IMPLEMENTED, "compression method 0x%02x: CPU path", methods[f]);
+        n_as_method[device_codec_row(methods[f])] += 1;
         CHGPU_REQUIRE(payload_offsets[f] + payload_sizes[f] <= compressed_u8->rows, CHGPU_ERR_BAD_ARGUMENTS, "frame %u lies outside the compressed buffer", f);
         const u32 post = post_methods ? post_methods[f] : 0;
-        CHGPU_REQUIRE(post == 0 || (post >= 0x92 && post <= 0x95), CHGPU_ERR_NOT_IMPLEMENTED, "codec 0x%02x in front of the general-purpose stage: CPU path", post);
+        CHGPU_REQUIRE(post == 0 || device_codec_row(post) < N_DEVICE_CODECS, CHGPU_ERR_NOT_IMPLEMENTED, "codec 0x%02x in front of the general-purpose stage: CPU path", post);
         CHGPU_REQUIRE(post == 0 || methods[f] == 0x82 || methods[f] == 0x02, CHGPU_ERR_NOT_IMPLEMENTED, "a codec stage behind method 0x%02x: CPU path", methods[f]);
         CHGPU_REQUIRE(post == 0 || stage_sizes, CHGPU_ERR_BAD_ARGUMENTS, "stage_sizes is NULL");
-        p_delta += post == 0x92;
-        p_t64 += post == 0x93;
-        p_dd += post == 0x94;
-        p_gor += post == 0x95;
+        n_as_post[device_codec_row(post)] += 1;
         FrameJob jb{};
         jb.src_off = payload_offsets[f];
         jb.src_size = payload_sizes[f];
@@ -906,21 +906,19 @@ extern "C" int chgpu_decompress_frames(chgpu_ctx * ctx, const chgpu_col * compre
         jobs[f] = jb;
         total += decompressed_sizes[f];
     }
-    chgpu_col * res = nullptr;
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, total, &res));
+    chgpu_col * res_col = nullptr;
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, total, &res_col));
+    std::unique_ptr<chgpu_col, int (*)(chgpu_col *)> res(res_col, chgpu_col_free); // freed on every error path below
     if (n_frames && total)
     {
         void * stage = nullptr;
         size_t stage_class = 0;
         void * scratch = nullptr;
         int rc = chgpu_scratch(ctx, sizeof(FrameJob) * (size_t)n_frames + 256, &scratch);
-        if (rc == CHGPU_OK && stage_total)
+        if (rc == CHGPU_OK && n_as_post[N_DEVICE_CODECS] != n_frames) // (also where every stage is empty: a codec kernel tells by the pointer which frames are its)
             rc = chgpu_pool_alloc(ctx, stage_total + 64, &stage, &stage_class);
         if (rc != CHGPU_OK)
-        {
-            chgpu_col_free(res);
             return rc;
-        }
         u32 * err = (u32 *)scratch;
         FrameJob * jd = (FrameJob *)((char *)scratch + 256);
         hipError_t e = hipMemsetAsync(err, 0, 256, ctx->stream);
@@ -934,48 +932,20 @@ extern "C" int chgpu_decompress_frames(chgpu_ctx * ctx, const chgpu_col * compre
             hipLaunchKernelGGL(k_lz4_decode, dim3(grid), dim3(256), 0, ctx->stream, (const u8 *)compressed_u8->data, (u8 *)res->data, (u8 *)stage, (const FrameJob *)jd,
                                n_frames, err);
             ctx->counters[6] += 1;
-            if (n_t64)
-            {
-                hipLaunchKernelGGL(k_t64_decode, dim3(n_frames < 4096 ? n_frames : 4096), dim3(256), 0, ctx->stream, (const u8 *)compressed_u8->data, (const u8 *)nullptr, (u8 *)res->data,
-                                   (const FrameJob *)jd, n_frames, err);
-                ctx->counters[6] += 1;
-            }
-            if (n_dd)
-            {
-                hipLaunchKernelGGL(k_double_delta_decode, dim3((n_frames + 63) / 64), dim3(64), 0, ctx->stream, (const u8 *)compressed_u8->data, (const u8 *)nullptr, (u8 *)res->data,
-                                   (const FrameJob *)jd, n_frames, err);
-                ctx->counters[6] += 1;
-            }
-            if (n_gor)
-            {
-                hipLaunchKernelGGL(k_gorilla_decode, dim3((n_frames + 63) / 64), dim3(64), 0, ctx->stream, (const u8 *)compressed_u8->data, (const u8 *)nullptr, (u8 *)res->data,
-                                   (const FrameJob *)jd, n_frames, err);
-                ctx->counters[6] += 1;
-            }
-            // the codec stages behind a general-purpose stage read its output in the stage buffer
-            if (p_delta)
-            {
-                hipLaunchKernelGGL(k_delta_decode, dim3(grid), dim3(256), 0, ctx->stream, (const u8 *)stage, (u8 *)res->data, (const FrameJob *)jd, n_frames, err);
-                ctx->counters[6] += 1;
-            }
-            if (p_t64)
-            {
-                hipLaunchKernelGGL(k_t64_decode, dim3(n_frames < 4096 ? n_frames : 4096), dim3(256), 0, ctx->stream, (const u8 *)compressed_u8->data, (const u8 *)stage, (u8 *)res->data,
-                                   (const FrameJob *)jd, n_frames, err);
-                ctx->counters[6] += 1;
-            }
-            if (p_dd)
-            {
-                hipLaunchKernelGGL(k_double_delta_decode, dim3((n_frames + 63) / 64), dim3(64), 0, ctx->stream, (const u8 *)compressed_u8->data, (const u8 *)stage, (u8 *)res->data,
-                                   (const FrameJob *)jd, n_frames, err);
-                ctx->counters[6] += 1;
-            }
-            if (p_gor)
-            {
-                hipLaunchKernelGGL(k_gorilla_decode, dim3((n_frames + 63) / 64), dim3(64), 0, ctx->stream, (const u8 *)compressed_u8->data, (const u8 *)stage, (u8 *)res->data,
-                                   (const FrameJob *)jd, n_frames, err);
-                ctx->counters[6] += 1;
-            }
+            // first the codecs whose frames stand alone, then the codec stages behind a general-purpose stage: they read its output in the
+            // stage buffer
+            for (u32 behind = 0; behind < 2; ++behind)
+                for (u32 c = 0; c < N_DEVICE_CODECS; ++c)
+                {
+                    const DeviceCodec & codec = DEVICE_CODECS[c];
+                    if (!(behind ? n_as_post[c] : codec.alone ? n_as_method[c] : 0))
+                        continue;
+                    u32 blocks, threads;
+                    codec_launch_shape(codec.geometry, grid, n_frames, blocks, threads);
+                    hipLaunchKernelGGL(codec.kernel, dim3(blocks), dim3(threads), 0, ctx->stream, (const u8 *)compressed_u8->data, (const u8 *)(behind ? stage : nullptr),
+                                       (u8 *)res->data, (const FrameJob *)jd, n_frames, err);
+                    ctx->counters[6] += 1;
+                }
             e = hipGetLastError();
         }
         u32 failed = 0;
@@ -988,12 +958,9 @@ extern "C" int chgpu_decompress_frames(chgpu_ctx * ctx, const chgpu_col * compre
         else if (rc == CHGPU_OK && failed)
             rc = chgpu_set_error(CHGPU_ERR_BAD_ARGUMENTS, "Cannot decompress: malformed frame (CANNOT_DECOMPRESS)");
         if (rc != CHGPU_OK)
-        {
-            chgpu_col_free(res);
             return rc;
-        }
     }
-    *out_u8 = res;
+    *out_u8 = res.release();
     return CHGPU_OK;
 }
 

@@ -286,6 +286,8 @@ def read_frames(buf: bytes) -> bytes:
 
 
 def _decode_stage(buf: bytes) -> bytes:
+    if len(buf) < HEADER:
+        raise ValueError("CANNOT_DECOMPRESS: a stage shorter than its header")
     method, csize, dsize = struct.unpack_from("<BII", buf, 0)
     payload = buf[HEADER:csize]
     if method == METHOD_LZ4:

@@ -1,6 +1,6 @@
 """Builders of compressed frames whose every field is given, for the decoders of clickhouse_amd/csrc/compress_kernels.hip: LZ4 blocks written
-sequence by sequence around the constants that choose a path in k_lz4_decode, malformed variants of one block, and Delta / DoubleDelta /
-Gorilla / T64 inputs at short and odd sizes.  No GPU and no assertions about a decoder here: tests/test_frame_craft.py checks every builder
+sequence by sequence around the constants that choose a path in k_lz4_decode, malformed variants of one block, Delta / DoubleDelta /
+Gorilla / T64 inputs at short and odd sizes, and codec frames with one header field changed.  No GPU and no assertions about a decoder here: tests/test_frame_craft.py checks every builder
 against the C oracle (oracle.compression) and asserts what the sets cover; tests/test_gpu_frame_decoder_edges.py sends them to the device.
 
 Nothing is imported from the kernel.  The four constants it branches on, restated once:"""
@@ -11,11 +11,11 @@ import numpy as np
 
 from oracle import compression as OC
 
-LZ_IN = 1024                # compress_kernels.hip:82   static constexpr u32 LZ_IN = 1024      (input window bytes per wave)
-LZ_RING = 4096              # compress_kernels.hip:83   static constexpr u32 LZ_RING = 4096    (output ring bytes per wave)
-LZ_CHUNK = LZ_RING // 2     # compress_kernels.hip:85   static constexpr u32 LZ_CHUNK = LZ_RING / 2   (ring-served matches: offset <= LZ_CHUNK)
-LZ_FAST_FAR = LZ_RING - 64  # compress_kernels.hip:168  the largest offset the fast path serves from the ring
-FAST_IN, FAST_OUT = 64, 32  # compress_kernels.hip:155  the fast path wants 64 readable window bytes and 32 free output bytes
+LZ_IN = 1024                # compress_kernels.hip:39   static constexpr u32 LZ_IN = 1024      (input window bytes per wave)
+LZ_RING = 4096              # compress_kernels.hip:40   static constexpr u32 LZ_RING = 4096    (output ring bytes per wave)
+LZ_CHUNK = LZ_RING // 2     # compress_kernels.hip:42   static constexpr u32 LZ_CHUNK = LZ_RING / 2   (ring-served matches: offset <= LZ_CHUNK)
+LZ_FAST_FAR = LZ_RING - 64  # compress_kernels.hip:152  the largest offset the fast path serves from the ring
+FAST_IN, FAST_OUT = 64, 32  # compress_kernels.hip:139  the fast path wants 64 readable window bytes and 32 free output bytes
 
 END = 70                    # literals of the closing sequence where a case does not say otherwise: with its token and length byte, 64 input
                             # bytes behind the token of a fast-path-shaped sequence in front of it, so that the fast path does take that one
@@ -221,8 +221,8 @@ def walk_sequences(block, with_offset_position=False):
 
 
 def decoder_trace(block, decoded_len):
-    """how a decoder that keeps LZ_IN input bytes at hand reads a well-formed block, by the rules of compress_kernels.hip:121-144, :155
-    and :168: a sequence of fast-path shape (fewer than 15 literals, a match below 19 from at most LZ_FAST_FAR back) whose next 64 input
+    """how a decoder that keeps LZ_IN input bytes at hand reads a well-formed block, by the rules of compress_kernels.hip:92-115, :139
+    and :152: a sequence of fast-path shape (fewer than 15 literals, a match below 19 from at most LZ_FAST_FAR back) whose next 64 input
     bytes are at hand, with 32 output bytes free, is read in one go; otherwise the token, every length byte and the two offset bytes are
     asked for one field at a time, and a field that is not wholly at hand makes the window begin anew at that field.
     -> (refills, fast): refills = [(field, input position, bytes of the field that were still at hand)], field one of "token", "literal
@@ -337,22 +337,22 @@ def malformed_lz4_cases():
     def add(name, bad_block, claimed, block, raw):
         cases.append((name, OC.METHOD_LZ4, bytes(bad_block), claimed, block, raw))
 
-    # Fewer than 64 input bytes follow the target in every truncated case, so `ip + 64 <= in_base + in_len` (:155) fails and the target
+    # Fewer than 64 input bytes follow the target in every truncated case, so `ip + 64 <= in_base + in_len` (:139) fails and the target
     # is parsed by the general path.
     block, raw, at, _ = _malformed_base((3, 5, 7))
-    # the token says 3 literals and 0 bytes are left: `lit > isz - ip` (:225)
+    # the token says 3 literals and 0 bytes are left: `lit > isz - ip` (:197)
     add("ends after a token with literals", block[:at + 1], len(raw), block, raw)
-    # after the 3 literals one byte is left: ip < isz, so no normal end (:254); `window(ip, 2)` is false for pos + 2 > isz (:122, :256)
+    # after the 3 literals one byte is left: ip < isz, so no normal end (:211); `window(ip, 2)` is false for pos + 2 > isz (:93, :213)
     add("ends after one offset byte", block[:at + 1 + 3 + 1], len(raw), block, raw)
     block, raw, at, _ = _malformed_base((0, 5, 7))
-    # the token says 0 literals and the input is used up: the loop ends as after a last sequence (:254), then `op != osz` (:349)
+    # the token says 0 literals and the input is used up: the loop ends as after a last sequence (:211), then `op != osz` (:264)
     add("ends after a token without literals", block[:at + 1], len(raw), block, raw)
     block, raw, at, _ = _malformed_base((300, 5, 7))
-    # the token's 15 and the byte 255 are read, the chain goes on and `window(ip, 1)` is false at ip == isz (:213)
+    # the token's 15 and the byte 255 are read, the chain goes on and `window(ip, 1)` is false at ip == isz (:121)
     assert block[at + 1] == 255
     add("ends inside a literal-length chain", block[:at + 2], len(raw), block, raw)
     block, raw, at, _ = _malformed_base((3, 5, 300))
-    # token, 3 literals, offset, the byte 255 of the match length: `window(ip, 1)` is false at ip == isz (:269)
+    # token, 3 literals, offset, the byte 255 of the match length: `window(ip, 1)` is false at ip == isz (:121)
     assert block[at + 1 + 3 + 2] == 255
     add("ends inside a match-length chain", block[:at + 1 + 3 + 2 + 1], len(raw), block, raw)
 
@@ -361,37 +361,37 @@ def malformed_lz4_cases():
     close = walk_sequences(block)[-1][3]
     bad = bytearray(block)
     bad[close] = 13 << 4
-    # 12 input bytes are left, and the output (claimed one byte longer) has room for 13: `lit > isz - ip` alone is true (:225)
+    # 12 input bytes are left, and the output (claimed one byte longer) has room for 13: `lit > isz - ip` alone is true (:197)
     add("literal length one more than the input left", bad, len(raw) + 1, block, raw)
-    # one more input byte so that 13 are there; the output has room for 12: `lit > osz - op` alone is true (:225)
+    # one more input byte so that 13 are there; the output has room for 12: `lit > osz - op` alone is true (:197)
     add("literal length one more than the output left", bad + b"\x00", len(raw), block, raw)
 
     # The target has fast-path shape and 72 input bytes behind it, so the fast path looks at it first: `offset - 1 < min(op + lit, 4032)`
-    # (:168) is false for offset 0 (offset - 1 wraps to 2^32 - 1) and for offset op + lit + 1, and the general path takes it over.
+    # (:152) is false for offset 0 (offset - 1 wraps to 2^32 - 1) and for offset op + lit + 1, and the general path takes it over.
     block, raw, at, op = _malformed_base((3, 5, 7), end=70)
     bad = bytearray(block)
     bad[at + 4:at + 6] = struct.pack("<H", 0)
-    add("offset 0", bad, len(raw), block, raw)                                   # `offset == 0` (:282)
+    add("offset 0", bad, len(raw), block, raw)                                   # `offset == 0` (:227)
     bad = bytearray(block)
     bad[at + 4:at + 6] = struct.pack("<H", op + 3 + 1)
-    add("offset one more than the output so far", bad, len(raw), block, raw)     # `offset > op` (:282), op counted behind the 3 literals
+    add("offset one more than the output so far", bad, len(raw), block, raw)     # `offset > op` (:227), op counted behind the 3 literals
 
     # match length 30 -> 30 + 12 + 1: the 30 and the closing 12 literals are all the output left; one length byte either way
     block, raw, at, _ = _malformed_base((3, 5, 30))
     bad = bytearray(block)
     assert bad[at + 6] == 30 - 19
     bad[at + 6] = 30 + SHORT_END + 1 - 19
-    add("match length one more than the output left", bad, len(raw), block, raw)  # `ml > osz - op` (:282)
+    add("match length one more than the output left", bad, len(raw), block, raw)  # `ml > osz - op` (:227)
 
     # a valid block under a header that claims one byte more or fewer
     block, raw, _, _ = _malformed_base((3, 5, 7))
-    add("header claims one byte more", block, len(raw) + 1, block, raw)          # everything decodes; `op != osz` (:349)
-    add("header claims one byte fewer", block, len(raw) - 1, block, raw)         # the closing 12 literals: `lit > osz - op` (:225)
+    add("header claims one byte more", block, len(raw) + 1, block, raw)          # everything decodes; `op != osz` (:264)
+    add("header claims one byte fewer", block, len(raw) - 1, block, raw)         # the closing 12 literals: `lit > osz - op` (:197)
     block, raw, _, _ = _malformed_base((3, 5, 7), end=0)                          # ... and a block that closes with an empty literal run
-    add("header claims one byte more, last bytes a match", block, len(raw) + 1, block, raw)   # `op != osz` (:349)
-    add("header claims one byte fewer, last bytes a match", block, len(raw) - 1, block, raw)  # the last match: `ml > osz - op` (:282)
+    add("header claims one byte more, last bytes a match", block, len(raw) + 1, block, raw)   # `op != osz` (:264)
+    add("header claims one byte fewer, last bytes a match", block, len(raw) - 1, block, raw)  # the last match: `ml > osz - op` (:227)
 
-    # method NONE: `isz != osz` (:107)
+    # method NONE: `isz != osz` (:78)
     rng = np.random.Generator(np.random.PCG64(77))
     stored = rng.integers(0, 256, size=100, dtype=np.uint8).tobytes()
     cases.append(("stored frame claims one byte more", OC.METHOD_NONE, stored, 101, stored, stored))
@@ -561,3 +561,209 @@ def t64_small_pool():
         seqs = t64_sequences(dt)
         pool += [s for s in seqs if s[2].shape[0] <= 65][::max(1, len(seqs) // 12)][:8]
     return pool
+
+
+# ---- 6. one well-formed codec frame, one header field changed -----------------------------------------------------------------------------
+CODEC_NAMES = {OC.METHOD_DELTA: "Delta", OC.METHOD_T64: "T64", OC.METHOD_DOUBLE_DELTA: "DoubleDelta", OC.METHOD_GORILLA: "Gorilla"}
+GENERAL_NAMES = {OC.METHOD_LZ4: "LZ4", OC.METHOD_NONE: "NONE"}
+WIDTH_SKIP_CODECS = (OC.METHOD_DELTA, OC.METHOD_DOUBLE_DELTA, OC.METHOD_GORILLA)
+
+
+def codec_column(codec, n=130, seed=0):
+    """n UInt32 values of the kind the codec is for: three T64 blocks, the last of two values; bit-stream codes of several lengths"""
+    rng = np.random.Generator(np.random.PCG64(600 + codec + seed))
+    if codec == OC.METHOD_T64:
+        return rng.integers(70_000, 75_000, size=n).astype(np.uint32)
+    if codec == OC.METHOD_GORILLA:
+        return (1000.0 + np.cumsum(rng.integers(-3, 4, size=n)) * 0.5).astype(np.float32).view(np.uint32)
+    return np.cumsum(rng.integers(0, 300, size=n)).astype(np.uint32)
+
+
+def codec_payload(codec, values):
+    if codec == OC.METHOD_T64:
+        return OC.t64_encode(values)
+    enc = {OC.METHOD_DELTA: OC.delta_encode, OC.METHOD_DOUBLE_DELTA: OC.double_delta_encode, OC.METHOD_GORILLA: OC.gorilla_encode}[codec]
+    return enc(values.tobytes() if isinstance(values, np.ndarray) else values, 4)
+
+
+def stage_bytes(codec, payload, out_size, method=None, csize_off=0, dsize_off=0):
+    """a codec stage as the general-purpose stage in front of it yields it: its own 9-byte header (each field can be set off) + payload"""
+    return struct.pack("<BII", codec if method is None else method, OC.HEADER + len(payload) + csize_off, out_size + dsize_off) + bytes(payload)
+
+
+def codec_frame(codec, payload, out_size, general=None, stage=None):
+    """general None: the frame that IS one application of the codec.  Otherwise CODEC(codec, general) as a Multiple frame whose general
+    stage (LZ4: one literal run; NONE: stored) yields `stage` (default: the well-formed stage of payload and out_size)."""
+    if general is None:
+        return OC._framed(OC._stage(codec, bytes(payload), out_size))
+    st1 = stage_bytes(codec, payload, out_size) if stage is None else stage
+    block = st1 if general == OC.METHOD_NONE else Lz4Builder(0, st1).end(len(st1))[0]
+    return OC._framed(OC._stage(OC.METHOD_MULTIPLE, bytes([2, codec, general]) + OC._stage(general, block, len(st1)), out_size))
+
+
+# The cases of malformed_codec_cases that the C oracle decodes without complaint (to bytes nobody asked for) and the kernel refuses: the
+# oracle reads a stage's payload as far as the buffer goes whatever the stage's compressed size says, takes the stage's method byte as
+# it stands, and does not check bytes_to_skip < width (what Delta and Gorilla read behind two bytes too many, it refuses for other
+# reasons).  tests/test_frame_craft.py asserts this set.
+KERNEL_STRICTER_THAN_ORACLE = frozenset(
+    [f"{c} behind {g}: stage header, compressed size one more" for c in CODEC_NAMES.values() for g in GENERAL_NAMES.values()]
+    + [f"{c} behind {g}: stage header, compressed size one fewer" for c in ("DoubleDelta", "Gorilla") for g in GENERAL_NAMES.values()]
+    + ["DoubleDelta: bytes_to_skip == width"])
+
+
+def malformed_codec_cases():
+    """-> [(name, codec, malformed frame, well-formed twin, the bytes the twin decodes to)].  Every malformed frame has a valid checksum
+    and outer sizes that hold, so the host's frame walk accepts it; the name says which field was changed and the comment next to the case
+    which check of compress_kernels.hip refuses it.  No case rests on an access out of range: each is refused by a comparison of header
+    fields with the frame's sizes before the bytes in question are touched."""
+    cases = []
+    DELTA, T64, DD, GOR = OC.METHOD_DELTA, OC.METHOD_T64, OC.METHOD_DOUBLE_DELTA, OC.METHOD_GORILLA
+
+    def add(name, codec, bad, good, raw):
+        cases.append((f"{CODEC_NAMES[codec]}{name}", codec, bad, good, raw))
+
+    # -- the stage header behind a general-purpose stage: codec_io() --
+    for codec in CODEC_NAMES:
+        raw = codec_column(codec).tobytes()
+        pay = codec_payload(codec, codec_column(codec))
+        for general, gname in GENERAL_NAMES.items():
+            good = codec_frame(codec, pay, len(raw), general)
+
+            def stage_case(what, stage):
+                add(f" behind {gname}: stage header, {what}", codec, codec_frame(codec, pay, len(raw), general, stage), good, raw)
+
+            other = DELTA if codec != DELTA else T64
+            stage_case("method byte of another codec", stage_bytes(codec, pay, len(raw), method=other))       # `h[0] != M`
+            stage_case("compressed size one more", stage_bytes(codec, pay, len(raw), csize_off=1))            # `csize != ssz`
+            stage_case("compressed size one fewer", stage_bytes(codec, pay, len(raw), csize_off=-1))          # `csize != ssz`
+            stage_case("decompressed size one more", stage_bytes(codec, pay, len(raw), dsize_off=1))          # `dsize != job.out_size`
+            stage_case("decompressed size one fewer", stage_bytes(codec, pay, len(raw), dsize_off=-1))        # `dsize != job.out_size`
+            stage_case("a stage of 8 bytes", stage_bytes(codec, pay, len(raw))[:8])                           # `ssz < 9`
+
+    # -- [width][bytes_to_skip][skipped bytes]: Delta behind LZ4, DoubleDelta and Gorilla as frames of their own --
+    for codec in WIDTH_SKIP_CODECS:
+        general = OC.METHOD_LZ4 if codec == DELTA else None
+        raw = codec_column(codec).tobytes()[:-2]      # 129 values and 2 bytes in front of them: bytes_to_skip = 2
+        pay = codec_payload(codec, raw)
+        assert pay[:2] == bytes([4, 2])
+        good = codec_frame(codec, pay, len(raw), general)
+
+        def changed(at, value):
+            return pay[:at] + bytes([value]) + pay[at + 1:]
+
+        for w in (0, 3, 16):
+            add(f": width {w}", codec, codec_frame(codec, changed(0, w), len(raw), general), good, raw)      # width not 1 / 2 / 4 / 8
+        add(": bytes_to_skip == width", codec, codec_frame(codec, changed(1, 4), len(raw), general), good, raw)   # `skip < width`
+        # 3 bytes in front of 4-byte values are all skipped bytes: [4][3][3 bytes] (and items = 0 for DoubleDelta and Gorilla).  The same payload in
+        # a frame that promises 2 bytes of output (the Delta stage's own header too): the width is valid, skip < width and `2 + skip <= isz`
+        # hold, `skip <= osz` alone refuses it -- before the skipped bytes are copied, which would write one byte into the next frame's output
+        tiny = raw[:3]
+        tpay = codec_payload(codec, tiny)
+        assert tpay[:2] == bytes([4, 3]) and len(tpay) >= 5
+        add(": bytes_to_skip larger than the output", codec, codec_frame(codec, tpay, 2, general), codec_frame(codec, tpay, 3, general), tiny)
+        # [width][1] and nothing else: `2 + skip <= isz`
+        add(": a payload of two bytes, bytes_to_skip 1", codec, codec_frame(codec, bytes([4, 1]), len(raw), general), good, raw)
+
+    # -- Delta: the deltas against the output --
+    raw = codec_column(DELTA).tobytes()[:-2]
+    pay = codec_payload(DELTA, raw)
+    good = codec_frame(DELTA, pay, len(raw), OC.METHOD_LZ4)
+    # bytes_to_skip 2 -> 1: the deltas are as many as out_size - skip, 4 * 129 + 1 of them: `n_bytes % w`
+    add(": deltas not a multiple of the width", DELTA, codec_frame(DELTA, bytes([4, 1]) + pay[2:], len(raw), OC.METHOD_LZ4), good, raw)
+    add(": deltas one element short", DELTA, codec_frame(DELTA, pay[:-4], len(raw), OC.METHOD_LZ4), good, raw)               # `n_bytes != out_size - skip`
+    add(": deltas one element beyond", DELTA, codec_frame(DELTA, pay + bytes(4), len(raw), OC.METHOD_LZ4), good, raw)        # `n_bytes != out_size - skip`
+
+    # -- DoubleDelta: every store is checked against the output's end (`d + width > d_end`, three places) --
+    raw = codec_column(DD).tobytes()
+    pay = codec_payload(DD, raw)
+    good = codec_frame(DD, pay, len(raw))
+    add(": output too small for the first value", DD, codec_frame(DD, pay, 3), good, raw)
+    add(": output too small for the second value", DD, codec_frame(DD, pay, 7), good, raw)
+    add(": output one value smaller than items", DD, codec_frame(DD, pay, len(raw) - 4), good, raw)
+
+    # -- Gorilla --
+    raw = codec_column(GOR).tobytes()
+    pay = codec_payload(GOR, raw)
+    good = codec_frame(GOR, pay, len(raw))
+    assert struct.unpack_from("<I", pay, 2)[0] == 130
+    add(": items one more than the output has room for", GOR, codec_frame(GOR, pay[:2] + struct.pack("<I", 131) + pay[6:], len(raw)), good, raw)   # `items * width > osz - skip`
+    # two equal values: the stream is the bit 0.  With 10 in its place the second value asks for the previous window of leading and trailing
+    # zeros, and there is none yet: `lz == 0 && db == 0 && tz == 0`
+    two = np.array([0x40490FDB, 0x40490FDB], dtype=np.uint32).tobytes()
+    tpay = codec_payload(GOR, two)
+    assert len(tpay) == 2 + 4 + 4 + 1 and tpay[-1] == 0
+    add(": control bits 10 before any window", GOR, codec_frame(GOR, tpay[:-1] + b"\x80", 8), codec_frame(GOR, tpay, 8), two)
+
+    # -- T64 --
+    values = codec_column(T64)
+    raw, pay = values.tobytes(), codec_payload(T64, values)
+    good = codec_frame(T64, pay, len(raw))
+    nb = t64_num_bits(pay)
+    assert len(pay) == 17 + 3 * 8 * nb and nb >= 9
+    for cookie in (0, 0x7F):
+        add(f": cookie {cookie:#x}", T64, codec_frame(T64, bytes([cookie]) + pay[1:], len(raw)), good, raw)   # no such MagicNumber: `default: bad = true`
+    add(": a payload of 16 bytes", T64, codec_frame(T64, pay[:16], len(raw)), good, raw)                      # `isz < 17`
+    add(": output not a multiple of the width", T64, codec_frame(T64, pay, len(raw) + 1), good, raw)          # `osz % width`
+    add(": body one byte long", T64, codec_frame(T64, pay + b"\x00", len(raw)), good, raw)                    # `body % shift`
+    add(": body one byte short", T64, codec_frame(T64, pay[:-1], len(raw)), good, raw)                        # `body % shift`
+    add(": body one block short", T64, codec_frame(T64, pay[:-8 * nb], len(raw)), good, raw)                  # `num_full * 64 + tail != n`
+    add(": body one block long", T64, codec_frame(T64, pay + bytes(8 * nb), len(raw)), good, raw)             # `num_full * 64 + tail != n`
+    return cases
+
+
+def quiet_codec_cases():
+    """DoubleDelta and Gorilla frames whose payload ends early: the reference returns without an error and so does the kernel.
+    -> [(name, codec, frame, bytes the format defines -- the skipped bytes and the values decoded before the payload ended; the frame
+    promises more output than that, and what stands behind them is not defined)]"""
+    cases = []
+    for codec in (OC.METHOD_DOUBLE_DELTA, OC.METHOD_GORILLA):
+        head = 2 if codec == OC.METHOD_DOUBLE_DELTA else 1      # values in front of the bit stream
+        # one-bit codes only (a constant step / a constant value), head + 8 * 16 values behind 2 skipped bytes: a stream of 16 whole bytes
+        n = head + 128
+        v = (1000 + 37 * np.arange(n)).astype(np.uint32) if codec == OC.METHOD_DOUBLE_DELTA else np.full(n, 0x40490FDB, dtype=np.uint32)
+        raw = b"\xAB\xCD" + v.tobytes()
+        pay = codec_payload(codec, raw)
+        at = 2 + 2 + 4 + 4 * head                             # where the bit stream begins
+        assert len(pay) == at + 16 and pay[:2] == bytes([4, 2])
+
+        def add(what, payload, defined):
+            cases.append((f"{CODEC_NAMES[codec]}: {what}", codec, codec_frame(codec, payload, len(raw)), raw[:defined]))
+
+        add("the stream ends after 5 of its 16 bytes", pay[:at + 5], 2 + 4 * (head + 40))
+        add("the payload ends inside items", pay[:2 + 2 + 3], 2)
+        add("the payload ends inside the first value", pay[:2 + 2 + 4 + 3], 2)
+        if codec == OC.METHOD_DOUBLE_DELTA:
+            add("the payload ends inside the first delta", pay[:2 + 2 + 4 + 4 + 3], 2 + 4)
+        add("items is 0", pay[:4] + bytes(4) + pay[8:], 2)
+    return cases
+
+
+def empty_stage_file(codec):
+    """three CODEC(codec, NONE) frames that promise 4 bytes each and whose stored stage is 0 bytes long: no stage header at all (`ssz < 9`
+    in codec_io).  The call's stage buffer has no bytes to hold, and the codec kernels must still take these frames as theirs."""
+    return codec_frame(codec, b"", 4, OC.METHOD_NONE, stage=b"") * 3
+
+
+def codec_payload_of(frame):
+    """-> (the codec's payload as its kernel sees it, the output size the frame promises), for a frame made by codec_frame"""
+    _, csize, out_size = struct.unpack_from("<BII", frame, OC.CHECKSUM)
+    body = frame[OC.CHECKSUM + OC.HEADER:OC.CHECKSUM + csize]
+    if frame[OC.CHECKSUM] != OC.METHOD_MULTIPLE:
+        return body, out_size
+    general, gsize, stage_size = struct.unpack_from("<BII", body, 3)
+    block = body[3 + OC.HEADER:3 + gsize]
+    stage = block if general == OC.METHOD_NONE else OC.lz4_decompress(block, stage_size)
+    return stage[OC.HEADER:], out_size
+
+
+def codec_neighbours(like):
+    """two well-formed frames of the codec chain of the frame `like` (CODEC(codec) or CODEC(codec, general)) to stand on both sides of a
+    malformed one -> [(frame, bytes)]"""
+    codec, general = like[OC.CHECKSUM], None
+    if codec == OC.METHOD_MULTIPLE:
+        codec, general = like[OC.CHECKSUM + OC.HEADER + 1], like[OC.CHECKSUM + OC.HEADER + 2]
+    out = []
+    for seed in (1, 2):
+        v = codec_column(codec, 200 + seed, seed)
+        out.append((codec_frame(codec, codec_payload(codec, v), v.nbytes, general), v.tobytes()))
+    return out

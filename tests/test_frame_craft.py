@@ -188,3 +188,65 @@ def test_t64_alias_cookies_decode_like_their_integer_type():
             assert frame[OC.CHECKSUM + OC.HEADER] & 0x7F == cookie and frame[OC.CHECKSUM + OC.HEADER] >> 7 == int(bit)
             assert OC.read_frames(frame) == values.tobytes() == OC.read_frames(F.t64_frame(values, bit)), cookie
     assert len(F.t64_small_pool()) >= 32
+
+
+def test_every_malformed_codec_case_has_the_recorded_verdict_of_the_oracle():
+    """the well-formed twin of every case decodes to the expected bytes; the malformed frame passes the frame walk (sizes and checksum hold)
+    and the oracle either refuses it or -- the cases of KERNEL_STRICTER_THAN_ORACLE, no others -- decodes it to something"""
+    cases = F.malformed_codec_cases()
+    names = [c[0] for c in cases]
+    assert len(set(names)) == len(names) and F.KERNEL_STRICTER_THAN_ORACLE <= set(names)
+    for codec, cname in F.CODEC_NAMES.items():
+        for general in F.GENERAL_NAMES.values():                 # six stage-header cases per codec and general-purpose stage
+            assert sum(n.startswith(f"{cname} behind {general}: stage header") for n in names) == 6
+    for cname in ("Delta", "DoubleDelta", "Gorilla"):
+        assert {f"{cname}: width {w}" for w in (0, 3, 16)} | {f"{cname}: bytes_to_skip == width", f"{cname}: bytes_to_skip larger than the output",
+                                                               f"{cname}: a payload of two bytes, bytes_to_skip 1"} <= set(names)
+    # the four conditions of the [width][bytes_to_skip] check, restated: each of its cases fails exactly the one its name states
+    named = {"width": 0, "bytes_to_skip == width": 1, "bytes_to_skip larger than the output": 2, "a payload of two bytes": 3}
+    seen = set()
+    for name, codec, bad, good, raw in cases:
+        which = [k for what, k in named.items() if f": {what}" in name]
+        if which:
+            pay, osz = F.codec_payload_of(bad)
+            holds = (pay[0] in (1, 2, 4, 8), pay[1] < pay[0], pay[1] <= osz, 2 + pay[1] <= len(pay))
+            failing = [k for k in range(4) if not holds[k]]
+            assert failing == which or (name.endswith("width 0") and failing == [0, 1]), (name, holds)   # (no skip is below width 0)
+            seen.add((codec, which[0]))
+            pay, osz = F.codec_payload_of(good)
+            assert pay[0] in (1, 2, 4, 8) and pay[1] < pay[0] and pay[1] <= osz and 2 + pay[1] <= len(pay), name
+    assert seen == {(c, k) for c in F.WIDTH_SKIP_CODECS for k in range(4)}
+    accepted = set()
+    for name, codec, bad, good, raw in cases:
+        assert len(raw) <= 4 * 300 and OC.read_frames(good) == raw, name
+        assert len(OC.parse_frames(bad)) == 1, name
+        try:
+            OC.read_frames(bad)
+            accepted.add(name)
+        except ValueError:
+            pass
+    assert accepted == F.KERNEL_STRICTER_THAN_ORACLE
+    chains = set()
+    for name, codec, bad, good, raw in cases:
+        sides = F.codec_neighbours(good)
+        chains.add(tuple(f for f, _ in sides))
+        assert all(OC.read_frames(f) == r and len(r) <= 4 * 300 for f, r in sides), name
+    assert len(chains) == 4 * 2 + 3                              # every codec behind LZ4 and NONE; T64, DoubleDelta and Gorilla alone
+
+
+def test_the_oracle_ends_the_quiet_codec_cases_without_an_error_behind_the_defined_bytes():
+    cases = F.quiet_codec_cases()
+    assert len(cases) == 9 and len({c[0] for c in cases}) == 9
+    for name, codec, frame, defined in cases:
+        got = OC.read_frames(frame)                              # no error
+        assert len(got) > len(defined) >= 2 and got[:len(defined)] == defined, name
+        assert not any(got[len(defined):]), name                 # nothing was decoded behind them (the oracle's buffer begins as zeros)
+
+
+def test_the_oracle_refuses_frames_whose_codec_stage_is_empty():
+    for codec in F.CODEC_NAMES:
+        buf = F.empty_stage_file(codec)
+        frames = OC.parse_frames(buf)
+        assert len(frames) == 3 and all(f[0] == OC.METHOD_MULTIPLE and f[3] == 4 for f in frames)
+        with pytest.raises(ValueError):
+            OC.read_frames(buf)

@@ -1,7 +1,8 @@
 """The frame decoders of compress_kernels.hip at their window, ring and bit-stream edges: crafted LZ4 blocks around LZ_IN / LZ_RING /
 LZ_CHUNK and the fast path's limits, more frames than the grid has waves (a wave's second frame finds the first one's bytes in its LDS
 ring and window), malformed variants of one block between well-formed neighbours, the Delta stage at every skip and block count, DoubleDelta
-and Gorilla streams of every short length, T64 at every num_bits and under every type cookie.
+and Gorilla streams of every short length, T64 at every num_bits and under every type cookie, and codec frames with one header field
+changed (or a payload that ends early) between well-formed neighbours.
 
 Every input comes from tests/frame_craft.py; tests/test_frame_craft.py asserts, without a GPU, that the C oracle decodes each of them to
 the expected bytes (or refuses it) and that the sets cover the paths named here.  Every comparison is byte for byte."""
@@ -185,3 +186,58 @@ def test_t64_alias_cookies_decode_like_their_integer_type(ch, ctx, cookie):
     assert OC.read_frames(b"".join(f for _, f, _ in alias)) == b"".join(r for _, _, r in alias)
     _check_file(ch, ctx, plain, f"integer cookie of {np.dtype(dt).name}")
     _check_file(ch, ctx, alias, f"cookie {cookie}")
+
+
+# ---- malformed and early-ending codec frames ---------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("codec", list(F.CODEC_NAMES), ids=list(F.CODEC_NAMES.values()))
+def test_malformed_codec_frame_between_well_formed_ones_is_refused(ch, ctx, codec):
+    """one header field of one codec frame changed (frame_craft.malformed_codec_cases names the field, and the check of the kernel that
+    refuses it); well-formed frames of the same codec chain stand on both sides.  The context then decodes the well-formed twins."""
+    from clickhouse_amd import compression as CC
+    cases = [c for c in F.malformed_codec_cases() if c[1] == codec]
+    assert len(cases) >= 20
+    not_refused, twins = [], []
+    for name, _, bad, good, raw in cases:
+        (before, raw_b), (after, raw_a) = F.codec_neighbours(good)
+        bad_file = before + bad + after
+        frames = CC.parse_frames(bad_file)   # sizes and checksums are in order
+        assert len(frames) == 3, name
+        try:
+            CC.decompress_frames(ctx, ctx.upload(np.frombuffer(bad_file, dtype=np.uint8)), frames)
+            not_refused.append(name)
+        except ch.ChgpuError as e:
+            assert e.code == ch._capi.ERR_BAD_ARGUMENTS, name
+        twins += [(f"before {name}", before, raw_b), (name, good, raw), (f"after {name}", after, raw_a)]
+    assert not not_refused
+    _check_file(ch, ctx, twins, f"the well-formed twins of {F.CODEC_NAMES[codec]}")
+
+
+def test_codec_payloads_that_end_early_end_quietly(ch, ctx):
+    """DoubleDelta / Gorilla payloads that end before `items` values, before the first value or the first delta, or with items 0: no error,
+    as in the reference, and the bytes the format defines stand in the frame's place.  What lies behind them is not compared."""
+    cases = F.quiet_codec_cases()
+    named = []
+    for name, codec, frame, defined in cases:
+        (before, raw_b), (after, raw_a) = F.codec_neighbours(frame)
+        named += [(before, raw_b, len(raw_b)), (frame, defined, len(OC.read_frames(frame))), (after, raw_a, len(raw_a))]
+    got, n = _decode(ch, ctx, b"".join(f for f, _, _ in named))
+    assert n == len(named) and len(got) == sum(size for _, _, size in named)
+    at = 0
+    for i, (_, defined, size) in enumerate(named):
+        assert got[at:at + len(defined)] == defined, cases[i // 3][0] + ("" if i % 3 == 1 else ": a neighbour")
+        at += size
+
+
+@pytest.mark.parametrize("codec", list(F.CODEC_NAMES), ids=list(F.CODEC_NAMES.values()))
+def test_a_file_whose_codec_stages_are_all_empty_is_refused(ch, ctx, codec):
+    """no byte of stage output in the whole call: every codec still takes the frames as stages of its own and refuses them (none has a
+    stage header), and the context then decodes a well-formed file of the same chain"""
+    from clickhouse_amd import compression as CC
+    buf = F.empty_stage_file(codec)
+    frames = CC.parse_frames(buf)
+    assert len(frames) == 3 and all(f[4] == codec and f[5] == 0 and f[3] == 4 for f in frames)
+    with pytest.raises(ch.ChgpuError) as e:
+        CC.decompress_frames(ctx, ctx.upload(np.frombuffer(buf, dtype=np.uint8)), frames)
+    assert e.value.code == ch._capi.ERR_BAD_ARGUMENTS
+    like = F.codec_frame(codec, F.codec_payload(codec, F.codec_column(codec)), 4 * 130, OC.METHOD_NONE)
+    _check_file(ch, ctx, [(f"neighbour {i}", f, r) for i, (f, r) in enumerate(F.codec_neighbours(like))], "after the empty stages")
