@@ -17,5 +17,6 @@ from .merging import AggregatedBlock, MergingAggregatedMemoryEfficientTransform
 from .keysfixed import KeyDict, KeysFixedAggregator, KeysFixedHashJoin, ColumnFixedString, FixedStringAggregator
 from .uniq import UniqExact
 from .quantile import QuantileExact
+from .group_array import GroupArray
 
 __all__ = [n for n in dir() if not n.startswith("_")]

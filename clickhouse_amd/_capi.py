@@ -173,6 +173,14 @@ SIGNATURES = {
     "chgpu_quantile_finalize": (_i, [_vp, _i, _u32, C.POINTER(C.c_double), _pp, _pp, _pu64]),
     "chgpu_quantile_for_keys": (_i, [_vp, _i, _u32, C.POINTER(C.c_double), _vp, _pp]),
     "chgpu_quantile_free": (_i, [_vp]),
+    "chgpu_group_array_create": (_i, [_vp, _i, _i, _u64, _pp]),
+    "chgpu_group_array_add_block": (_i, [_vp, _vp, _vp, _u64, _u64, _vp]),
+    "chgpu_group_array_merge": (_i, [_vp, _vp]),
+    "chgpu_group_array_size": (_i, [_vp, _pu64]),
+    "chgpu_group_array_export_pairs": (_i, [_vp, _pp, _pp, _pu64]),
+    "chgpu_group_array_finalize": (_i, [_vp, _pp, _pp, _pp, _pu64]),
+    "chgpu_group_array_for_keys": (_i, [_vp, _vp, _pp, _pp]),
+    "chgpu_group_array_free": (_i, [_vp]),
     "chgpu_comm_unique_id": (_i, [_vp]),
     "chgpu_comm_init": (_i, [_vp, _i, _i, _vp, _pp]),
     "chgpu_comm_destroy": (_i, [_vp]),

@@ -1231,6 +1231,92 @@ private:
     chgpu_quantile * h = nullptr;
 };
 
+/// A ColumnArray as the device hands it out: offsets[i] is where array i ends (ColumnArray::getOffsets), data holds the arrays one
+/// after another.  ColumnArray::create(data, offsets) of the two downloaded columns is the reference's column.
+struct GpuColumnArray
+{
+    ColumnPtr offsets; // UInt64, one row per array
+    ColumnPtr data;    // the value type
+};
+
+/// groupArray(x) / groupArray(N)(x) beside a GpuAggregator (chgpu_group_array_*): the (group key, value) pairs in HBM in arrival order.
+class GpuGroupArray
+{
+public:
+    GpuGroupArray(ContextPtr ctx_, int key_type_, int value_type_, uint64_t max_size_ = 0)
+        : ctx(std::move(ctx_)), key_type(key_type_), value_type(value_type_), max_size(max_size_)
+    {
+        check(chgpu_group_array_create(ctx->get(), key_type, value_type, max_size, &h));
+    }
+    ~GpuGroupArray() { chgpu_group_array_free(h); }
+    GpuGroupArray(const GpuGroupArray &) = delete;
+
+    /// executeOnBlock for this one function: the rows of [row_begin, row_end) whose filter byte is non-zero enter, in row order.  The
+    /// filter column is WHERE, the -If condition and the negated null map and-ed into one UInt8 column.
+    void add(const Columns & columns, size_t row_begin, size_t row_end, std::optional<size_t> key_position, size_t value_position,
+             std::optional<size_t> filter_position = std::nullopt)
+    {
+        const chgpu_col * key = key_position ? columns.at(*key_position)->handle() : nullptr;
+        const chgpu_col * filt = filter_position ? columns.at(*filter_position)->handle() : nullptr;
+        check(chgpu_group_array_add_block(h, key, columns.at(value_position)->handle(), row_begin, row_end, filt));
+    }
+    /// other's values behind this operator's, group by group; other stays valid
+    void merge(const GpuGroupArray & other) { check(chgpu_group_array_merge(h, other.h)); }
+    /// values held, all groups
+    size_t size() const
+    {
+        uint64_t n = 0;
+        check(chgpu_group_array_size(h, &n));
+        return n;
+    }
+    /// final = true: [key column,] offsets, data (without key: one row); final = false: the held pairs in store order, [key column,]
+    /// value column -- a peer takes them with add() and rebuilds the same arrays
+    Chunk convertToBlock(bool final = true) const
+    {
+        chgpu_col * keys = nullptr;
+        uint64_t rows = 0;
+        Chunk out;
+        if (final)
+        {
+            chgpu_col * offsets = nullptr;
+            chgpu_col * data = nullptr;
+            check(chgpu_group_array_finalize(h, &keys, &offsets, &data, &rows));
+            if (keys)
+                out.columns.push_back(std::make_shared<ColumnVector>(ctx, keys));
+            out.columns.push_back(std::make_shared<ColumnVector>(ctx, offsets));
+            out.columns.push_back(std::make_shared<ColumnVector>(ctx, data));
+        }
+        else
+        {
+            chgpu_col * vals = nullptr;
+            check(chgpu_group_array_export_pairs(h, &keys, &vals, &rows));
+            if (keys)
+                out.columns.push_back(std::make_shared<ColumnVector>(ctx, keys));
+            out.columns.push_back(std::make_shared<ColumnVector>(ctx, vals));
+        }
+        out.num_rows = rows;
+        return out;
+    }
+    /// the groupArray column of a GpuAggregator::convertToBlock chunk: keys = that chunk's key column; row i gets the array of keys[i],
+    /// the empty array for a group none of whose rows entered
+    GpuColumnArray arraysForKeys(const ColumnVector & keys) const
+    {
+        chgpu_col * offsets = nullptr;
+        chgpu_col * data = nullptr;
+        check(chgpu_group_array_for_keys(h, keys.handle(), &offsets, &data));
+        return GpuColumnArray{std::make_shared<ColumnVector>(ctx, offsets), std::make_shared<ColumnVector>(ctx, data)};
+    }
+    int keyType() const { return key_type; }
+    int valueType() const { return value_type; }
+    uint64_t maxSize() const { return max_size; }
+
+private:
+    ContextPtr ctx;
+    int key_type, value_type;
+    uint64_t max_size;
+    chgpu_group_array * h = nullptr;
+};
+
 /// ManyAggregatedData (AggregatingTransform.h:74-100): one AggregatedDataVariants per pipeline stream, shared by the streams'
 /// AggregatingTransforms; the stream that finishes LAST merges them (num_finished, AggregatingTransform.cpp:728-744).
 struct ManyAggregatedData

@@ -553,6 +553,44 @@ int chgpu_quantile_finalize(chgpu_quantile * quantile, int kind, uint32_t n_leve
 int chgpu_quantile_for_keys(chgpu_quantile * quantile, int kind, uint32_t n_levels, const double * levels, const chgpu_col * keys,
                             chgpu_col ** res_cols);
 int chgpu_quantile_free(chgpu_quantile * quantile);
+/* groupArray(x) / groupArray(N)(x) under GROUP BY (AggregateFunctionGroupArray over GroupArrayNumericImpl: an array per group, push_back
+   at add until max_elems, insert(end, rhs...) at merge).  A chgpu_group_array holds the (group key, value) pairs in one flat append-only
+   store in HBM IN ARRIVAL ORDER, beside the chgpu_agg that holds the GROUP BY's other aggregates: one per argument.  Adding a block is an
+   order-preserving filtered copy; finalising runs one stable radix pass per key byte that varies anywhere in the store, which leaves
+   equal keys adjacent and every group's values in arrival order, and hands the result out as a ColumnArray in two columns.
+   Types: keys as for chgpu_uniq / chgpu_quantile (integer types, zero-extended; a float key answers CHGPU_ERR_NOT_IMPLEMENTED; key_type
+   < 0 is without key); value_type is any of the ten types (UInt32 dictionary ids stand for a LowCardinality / String argument).
+   max_size: N of groupArray(N), 0 = no limit.
+   What enters: a row of [row_begin, row_end) whose filter_u8 byte is non-zero (NULL: every row); the filter is WHERE, the -If condition
+   and the negated null map in one byte, so groupArrayIf and a Nullable argument are this same call.  Nothing else is dropped: NaN of
+   any payload, +-inf and -0.0 are kept and every value comes back bit for bit.  A group exists only through a row that entered.
+   Order: a group's array holds its entered values by add_block call, then by row number within the call.  chgpu_group_array_merge puts
+   src's values behind dst's, src stays valid.  With max_size = N > 0 an array is the first N of that sequence (the reference's "stop
+   adding at N" and "take N - size from rhs"); the store still keeps every entered row.  Operators of different max_size do not merge.
+   The reference's order under several threads depends on their timing; this operator's order is fully determined by the calls.
+   Result: offsets_u64[i] is where array i ends (ColumnArray::getOffsets): array i is data[offsets[i - 1], offsets[i]) with offsets[-1]
+   = 0; data_out has the value type.  chgpu_group_array_finalize: one row per key that holds a value, the keys in the key type, row
+   order unspecified but the same across calls on an unchanged store; without key exactly one row, which may be the empty array
+   (keys_out may be NULL).  chgpu_group_array_for_keys: for every row of `keys` that key's array, in that call's row order: the column
+   beside those of chgpu_agg_finalize; a key the operator lacks gets the empty array, a key asked twice gets its array twice.
+   chgpu_group_array_export_pairs: the not-final form -- every held pair IN STORE ORDER; a peer that feeds them to
+   chgpu_group_array_add_block rebuilds the same arrays.  chgpu_group_array_size: values held, all groups.  finalize and for_keys may be
+   called repeatedly and between blocks.
+   Errors: NULL handles and outputs, type mismatches, row_begin > row_end, a range past the column, operators of different types,
+   max_size or devices -> CHGPU_ERR_BAD_ARGUMENTS; columns of different lengths -> CHGPU_ERR_SIZES_MISMATCH; 2^32 - 1 values or more ->
+   CHGPU_ERR_TOO_MANY_ROWS; after CHGPU_ERR_OOM the store holds exactly what it held before the call.  Empty inputs are not errors.  The
+   reference's wire bytes (VarUInt size + raw values per group) are not produced. */
+typedef struct chgpu_group_array chgpu_group_array;
+int chgpu_group_array_create(chgpu_ctx * ctx, int key_type, int value_type, uint64_t max_size, chgpu_group_array ** out);
+int chgpu_group_array_add_block(chgpu_group_array * group_array, const chgpu_col * key_col, const chgpu_col * value_col, uint64_t row_begin,
+                                uint64_t row_end, const chgpu_col * filter_u8);
+int chgpu_group_array_merge(chgpu_group_array * dst, const chgpu_group_array * src);
+int chgpu_group_array_size(chgpu_group_array * group_array, uint64_t * values);
+int chgpu_group_array_export_pairs(chgpu_group_array * group_array, chgpu_col ** keys_out, chgpu_col ** values_out, uint64_t * rows);
+int chgpu_group_array_finalize(chgpu_group_array * group_array, chgpu_col ** keys_out, chgpu_col ** offsets_u64, chgpu_col ** data_out,
+                               uint64_t * groups);
+int chgpu_group_array_for_keys(chgpu_group_array * group_array, const chgpu_col * keys, chgpu_col ** offsets_u64, chgpu_col ** data_out);
+int chgpu_group_array_free(chgpu_group_array * group_array);
 /* §8(f) rank 2 — LowCardinality keys (src/Columns/ColumnLowCardinality.h:27-69; low_cardinality_key* variants,
    AggregatedDataVariants.h:119-127; HashMethodSingleLowCardinalityColumn's per-position cache, ColumnsHashing.h:82-260).
    Every Block brings its own dictionary; the host resolves it against the query-wide dictionary into remap_u32[local position]
