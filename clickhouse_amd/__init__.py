@@ -18,5 +18,6 @@ from .keysfixed import KeyDict, KeysFixedAggregator, KeysFixedHashJoin, ColumnFi
 from .uniq import UniqExact
 from .quantile import QuantileExact
 from .group_array import GroupArray
+from .window import CURRENT_ROW, UNBOUNDED, Frame, Window, following, preceding
 
 __all__ = [n for n in dir() if not n.startswith("_")]

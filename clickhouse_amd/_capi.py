@@ -31,6 +31,10 @@ QUANTILE_EXACT, QUANTILE_EXACT_LOW, QUANTILE_EXACT_HIGH = 0, 1, 2
 QUANTILE_EXACT_INCLUSIVE, QUANTILE_EXACT_EXCLUSIVE, QUANTILE_EXACT_WEIGHTED = 3, 4, 5   # reserved: NOT_IMPLEMENTED
 QUANTILE_MAX_LEVELS = 16
 STR_CONST_MAX = 256   # bytes of a string constant / LIKE pattern the kernels carry
+(WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT, WIN_SUM, WIN_AVG, WIN_MIN, WIN_MAX, WIN_FIRST_VALUE, WIN_LAST_VALUE, WIN_LAG_IN_FRAME,
+ WIN_LEAD_IN_FRAME) = range(12)
+FRAME_ROWS, FRAME_RANGE = 0, 1
+BOUND_UNBOUNDED_PRECEDING, BOUND_OFFSET_PRECEDING, BOUND_CURRENT_ROW, BOUND_OFFSET_FOLLOWING, BOUND_UNBOUNDED_FOLLOWING = 0, 1, 2, 3, 4
 
 _vp, _i, _u32, _u64, _i64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_int64
 _pp = C.POINTER(C.c_void_p)
@@ -43,6 +47,12 @@ class LikePlan(C.Structure):
     _fields_ = [("route", C.c_int32), ("n_percent", C.c_uint32), ("n_underscore", C.c_uint32), ("literal_bytes", C.c_uint32),
                 ("n_tokens", C.c_uint32), ("token_meta", C.c_uint32 * (STR_CONST_MAX // 32)), ("literal", C.c_uint8 * STR_CONST_MAX),
                 ("tokens", C.c_uint8 * STR_CONST_MAX)]
+
+
+class WindowFrame(C.Structure):
+    """chgpu_window_frame: ROWS | RANGE, the two bounds and their offsets (chgpu_window_evaluate)"""
+    _fields_ = [("type", C.c_int32), ("begin_kind", C.c_int32), ("end_kind", C.c_int32), ("reserved", C.c_int32),
+                ("begin_offset", C.c_uint64), ("end_offset", C.c_uint64)]
 
 
 SIGNATURES = {
@@ -181,6 +191,10 @@ SIGNATURES = {
     "chgpu_group_array_finalize": (_i, [_vp, _pp, _pp, _pp, _pu64]),
     "chgpu_group_array_for_keys": (_i, [_vp, _vp, _pp, _pp]),
     "chgpu_group_array_free": (_i, [_vp]),
+    "chgpu_window_create": (_i, [_vp, _vp, _u32, _vp, _u32, _u64, _pp]),
+    "chgpu_window_counts": (_i, [_vp, _pu64, _pu64, _pu64]),
+    "chgpu_window_evaluate": (_i, [_vp, _i, C.POINTER(WindowFrame), _vp, _u64, _u64, _pp]),
+    "chgpu_window_free": (_i, [_vp]),
     "chgpu_comm_unique_id": (_i, [_vp]),
     "chgpu_comm_init": (_i, [_vp, _i, _i, _vp, _pp]),
     "chgpu_comm_destroy": (_i, [_vp]),

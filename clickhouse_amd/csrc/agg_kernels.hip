@@ -446,25 +446,8 @@ __device__ __forceinline__ u64 table_emplace(const AggTable & t, u64 key, bool s
 // exports move min / max words with no special case but the combining operation.  (A group only exists because a row created it, so
 // `has()` is always true for it.  Under a per-function condition that no longer holds: a conditioned min / max carries a `seen` word, the
 // number of rows that reached it, and finalize gives the type's default when it is 0 -- DESIGN.md §4.16.2.)  NaNs take their total-order place -- above +inf / below -inf by sign -- where the reference's answer
-// depends on which row came first (`NaN < x` is false either way).
-__device__ __host__ __forceinline__ u64 agg_order_key(u64 bits, int type)
-{
-    switch (type)
-    {
-        case CHGPU_I64: case CHGPU_I32: case CHGPU_I16: case CHGPU_I8: return bits ^ 0x8000000000000000ull; // (already sign-extended)
-        case CHGPU_F64: case CHGPU_F32: return (bits >> 63) ? ~bits : bits ^ 0x8000000000000000ull;
-        default: return bits;
-    }
-}
-__device__ __host__ __forceinline__ u64 agg_order_key_inverse(u64 key, int type)
-{
-    switch (type)
-    {
-        case CHGPU_I64: case CHGPU_I32: case CHGPU_I16: case CHGPU_I8: return key ^ 0x8000000000000000ull;
-        case CHGPU_F64: case CHGPU_F32: return (key >> 63) ? key ^ 0x8000000000000000ull : ~key;
-        default: return key;
-    }
-}
+// depends on which row came first (`NaN < x` is false either way).  agg_order_key / agg_order_key_inverse themselves are in
+// chgpu_internal.h: the window operator's running min / max (window_kernels.hip) orders by the same key.
 
 // argMin / argMax compare `val` with the reference's operator > / <, to which the two zeros are equal: the val key folds the zero's
 // sign away (val is never returned, so nothing is lost).  min / max keep agg_order_key: they return the value.

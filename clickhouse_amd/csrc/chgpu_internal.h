@@ -287,6 +287,27 @@ __device__ __forceinline__ u32 wave_allreduce_add_u32(u32 v)
     return v;
 }
 
+// The order key of min / max (agg_kernels.hip has the whole story): `bits` is the value widened to 64 bits -- integers sign- or
+// zero-extended, Float32 after its exact widening to Float64 -- and the key is an unsigned integer that sorts like the value.
+__device__ __host__ __forceinline__ u64 agg_order_key(u64 bits, int type)
+{
+    switch (type)
+    {
+        case CHGPU_I64: case CHGPU_I32: case CHGPU_I16: case CHGPU_I8: return bits ^ 0x8000000000000000ull; // (already sign-extended)
+        case CHGPU_F64: case CHGPU_F32: return (bits >> 63) ? ~bits : bits ^ 0x8000000000000000ull;
+        default: return bits;
+    }
+}
+__device__ __host__ __forceinline__ u64 agg_order_key_inverse(u64 key, int type)
+{
+    switch (type)
+    {
+        case CHGPU_I64: case CHGPU_I32: case CHGPU_I16: case CHGPU_I8: return key ^ 0x8000000000000000ull;
+        case CHGPU_F64: case CHGPU_F32: return (key >> 63) ? key ^ 0x8000000000000000ull : ~key;
+        default: return key;
+    }
+}
+
 // murmur finalizer == the reference's intHash64 (src/Common/HashTable/Hash.h:27-36): the device tables' placement hash.
 __device__ __forceinline__ u64 dev_intHash64(u64 x)
 {

@@ -2288,6 +2288,110 @@ inline void sortBlock(Chunk & block, std::vector<ColumnString> & strings, const 
     block.num_rows = take ? take : rows;
 }
 
+/// WindowFrame (src/Interpreters/WindowDescription.h): ROWS | RANGE and the two bounds.  The default is the reference's, RANGE UNBOUNDED
+/// PRECEDING .. CURRENT ROW.
+struct WindowFrame
+{
+    int type = CHGPU_FRAME_RANGE;
+    int begin_type = CHGPU_BOUND_UNBOUNDED_PRECEDING;
+    uint64_t begin_offset = 0;
+    int end_type = CHGPU_BOUND_CURRENT_ROW;
+    uint64_t end_offset = 0;
+    bool is_default = true; // passes NULL to the C ABI
+
+    static WindowFrame rows(int begin_type_, uint64_t begin_offset_, int end_type_, uint64_t end_offset_)
+    {
+        return WindowFrame{CHGPU_FRAME_ROWS, begin_type_, begin_offset_, end_type_, end_offset_, false};
+    }
+    static WindowFrame range(int begin_type_, int end_type_) { return WindowFrame{CHGPU_FRAME_RANGE, begin_type_, 0, end_type_, 0, false}; }
+    chgpu_window_frame toC() const
+    {
+        return chgpu_window_frame{type, begin_type, end_type, 0, begin_offset, end_offset};
+    }
+};
+
+/// WindowFunctionDescription (WindowDescription.h): one function OVER the window -- which CHGPU_WIN_* function, its argument's position
+/// in the chunk (none for row_number / rank / dense_rank / count), its frame, and lagInFrame / leadInFrame's offset and default.
+struct WindowFunctionDescription
+{
+    int function = CHGPU_WIN_ROW_NUMBER;
+    std::optional<size_t> argument;
+    WindowFrame frame;
+    uint64_t offset = 1;
+    uint64_t default_bits = 0; // the default value in the argument's type, zero-extended
+};
+
+/// WindowTransform (src/Processors/Transforms/WindowTransform.cpp) for one window definition behind a full sort (WindowStep after
+/// SortingStep): the input arrives sorted by (partition_by, order_by) in chunks.  A frame may look ahead of the rows seen so far, so the
+/// chunks are kept and glued (chgpu_col_concat, like a join's build side) and every function runs at finish(): input columns + one
+/// column per function.
+class GpuWindowTransform
+{
+public:
+    GpuWindowTransform(ContextPtr ctx_, std::vector<size_t> partition_by_, std::vector<size_t> order_by_, std::vector<WindowFunctionDescription> functions_)
+        : ctx(std::move(ctx_)), partition_by(std::move(partition_by_)), order_by(std::move(order_by_)), functions(std::move(functions_)) {}
+
+    void consume(Chunk chunk)
+    {
+        if (chunk.num_rows)
+            chunks.push_back(std::move(chunk));
+    }
+
+    Chunk finish()
+    {
+        Chunk out;
+        if (chunks.empty())
+            return out;
+        const size_t n_cols = chunks[0].columns.size();
+        for (size_t c = 0; c < n_cols; ++c)
+        {
+            if (chunks.size() == 1)
+            {
+                out.columns.push_back(chunks[0].columns[c]);
+                continue;
+            }
+            std::vector<const chgpu_col *> parts;
+            for (auto & ch : chunks)
+                parts.push_back(ch.columns.at(c)->handle());
+            chgpu_col * cat = nullptr;
+            check(chgpu_col_concat(ctx->get(), static_cast<uint32_t>(parts.size()), parts.data(), &cat));
+            out.columns.push_back(std::make_shared<ColumnVector>(ctx, cat));
+        }
+        for (auto & ch : chunks)
+            out.num_rows += ch.num_rows;
+        chunks.clear();
+
+        std::vector<const chgpu_col *> p, o;
+        for (size_t pos : partition_by)
+            p.push_back(out.columns.at(pos)->handle());
+        for (size_t pos : order_by)
+            o.push_back(out.columns.at(pos)->handle());
+        chgpu_window * w = nullptr;
+        check(chgpu_window_create(ctx->get(), p.data(), static_cast<uint32_t>(p.size()), o.data(), static_cast<uint32_t>(o.size()), out.num_rows, &w));
+        std::unique_ptr<chgpu_window, int (*)(chgpu_window *)> handle(w, chgpu_window_free);
+        check(chgpu_window_counts(w, nullptr, &partitions, &peer_groups));
+        for (const auto & f : functions)
+        {
+            const chgpu_window_frame frame = f.frame.toC();
+            const chgpu_col * arg = f.argument ? out.columns.at(*f.argument)->handle() : nullptr;
+            chgpu_col * res = nullptr;
+            check(chgpu_window_evaluate(w, f.function, f.frame.is_default ? nullptr : &frame, arg, f.offset, f.default_bits, &res));
+            out.columns.push_back(std::make_shared<ColumnVector>(ctx, res));
+        }
+        return out;
+    }
+    /// of the last finish()
+    uint64_t numPartitions() const { return partitions; }
+    uint64_t numPeerGroups() const { return peer_groups; }
+
+private:
+    ContextPtr ctx;
+    std::vector<size_t> partition_by, order_by;
+    std::vector<WindowFunctionDescription> functions;
+    std::vector<Chunk> chunks;
+    uint64_t partitions = 0, peer_groups = 0;
+};
+
 /// CompressedReadBuffer + SerializationNumber::deserializeBinaryBulk for one numeric column file (MergeTree `<column>.bin`): the
 /// host walks the frame headers (CompressedReadBufferBase.cpp:175-222), the compressed bytes cross PCIe once, the frames are decoded
 /// in HBM.  LZ4, NONE and CODEC(Delta, LZ4); any other codec throws NOT_IMPLEMENTED (the caller decompresses on the CPU as before).

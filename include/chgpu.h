@@ -591,6 +591,65 @@ int chgpu_group_array_finalize(chgpu_group_array * group_array, chgpu_col ** key
                                uint64_t * groups);
 int chgpu_group_array_for_keys(chgpu_group_array * group_array, const chgpu_col * keys, chgpu_col ** offsets_u64, chgpu_col ** data_out);
 int chgpu_group_array_free(chgpu_group_array * group_array);
+/* Window functions over a sorted block: WindowTransform (src/Processors/Transforms/WindowTransform.cpp: advancePartitionEnd,
+   advanceFrameStart / advanceFrameEnd, arePeers; the functions WindowFunctionRowNumber, WindowFunctionRank, WindowFunctionDenseRank,
+   WindowFunctionLagLeadInFrame and the aggregate functions run over a frame) with the frames of src/Interpreters/WindowDescription.h
+   (WindowFrame: FrameType, BoundaryType, checkValid).  `OVER (PARTITION BY p.. ORDER BY o.. ROWS|RANGE ..)` behind the sort this library
+   already does: the input is the WHOLE sorted input, the columns as chgpu_sort_permutation + chgpu_index leave them, at most 2^32 - 1
+   rows (more -> CHGPU_ERR_NOT_IMPLEMENTED).  There is no carry between blocks: a frame that looks ahead needs rows not yet seen, so a
+   caller glues its chunks with chgpu_col_concat first.
+   One handle is one window definition (WINDOW w AS (..)).  chgpu_window_create reads the key columns once and keeps only what it derives
+   from them -- a flag byte per row and, built on the first call that reads them, the rows' partition and peer-group bounds; it holds no
+   reference to the keys.  Each list holds 0 to 8 columns of any of the ten types (String / LowCardinality keys as dictionary ids);
+   n_partition = 0 is one partition, n_order = 0 makes all rows of a partition peers.  Row i starts a partition when i = 0 or a partition
+   column differs from row i - 1, and a peer group when it starts a partition or an order column differs; equality is compareAt == 0:
+   integers by value, floats with a == b or both NaN (so -0.0 equals +0.0).  [ps, pe) is the partition of row i, [gs, ge) its peer group.
+   chgpu_window_evaluate computes one function OVER w; several calls share a handle, each with its own frame (NULL: the reference's
+   default, RANGE UNBOUNDED PRECEDING .. CURRENT ROW).  The frame [fs, fe) of row i, all arithmetic saturating:
+     bound                  begin                 end
+     UNBOUNDED_PRECEDING    ps                    BAD_ARGUMENTS
+     OFFSET_PRECEDING k     max(ps, i - k)        max(ps, i - k + 1)
+     CURRENT_ROW            ROWS i, RANGE gs      ROWS i + 1, RANGE ge
+     OFFSET_FOLLOWING k     min(pe, i + k)        min(pe, i + k + 1)
+     UNBOUNDED_FOLLOWING    BAD_ARGUMENTS         pe
+   CURRENT_ROW .. k PRECEDING, k FOLLOWING .. CURRENT_ROW / m PRECEDING, k PRECEDING .. m PRECEDING with k < m and k FOLLOWING .. m
+   FOLLOWING with k > m are CHGPU_ERR_BAD_ARGUMENTS (WindowFrame::checkValid); a frame may be empty.  RANGE with an offset ->
+   CHGPU_ERR_NOT_IMPLEMENTED.  `reserved` is ignored.
+     function        arg               result          value
+     ROW_NUMBER      -                 UInt64          i - ps + 1                          (frame ignored)
+     RANK            -                 UInt64          gs - ps + 1                         (frame ignored)
+     DENSE_RANK      -                 UInt64          peer groups in [ps, i]              (frame ignored)
+     COUNT           -                 UInt64          fe - fs
+     SUM             8 integer types   Int64 / UInt64  wrap-around sum of the frame (SumSimple's result type)
+     AVG             8 integer types   Float64         that sum as Float64 / Float64(fe - fs), as CHGPU_AGG_AVG; empty frame: NaN
+     MIN / MAX       all ten           arg type        extremum in the order of chgpu_agg's min / max (NaN in its total-order place, +0.0
+                                                       above -0.0, the value's bits returned); empty frame: 0.  The frame must begin
+                                                       UNBOUNDED_PRECEDING or end UNBOUNDED_FOLLOWING, else CHGPU_ERR_NOT_IMPLEMENTED
+     FIRST_VALUE     all ten           arg type        x[fs], bits untouched; empty frame: 0
+     LAST_VALUE      all ten           arg type        x[fe - 1], bits untouched; empty frame: 0
+     LAG_IN_FRAME    all ten           arg type        t = i - offset: x[t] if fs <= t < fe, else default_bits narrowed to the type
+     LEAD_IN_FRAME   all ten           arg type        t = i + offset, likewise; offset 0 is the row itself, nothing wraps
+   SUM / AVG over Float32 / Float64 -> CHGPU_ERR_NOT_IMPLEMENTED.  `arg` must be NULL where the function takes none; `offset` and
+   `default_bits` are read by lag / lead only.  *out is a new column of `rows` rows, caller frees.
+   chgpu_window_counts: the rows, partitions and peer groups of the handle (any pointer may be NULL).
+   Errors: NULL handles, lists and outputs, more than 8 columns in a list, an unknown function, bound or type, an illegal frame, a missing
+   or surplus arg -> CHGPU_ERR_BAD_ARGUMENTS; a key column or arg whose length is not `rows` -> CHGPU_ERR_SIZES_MISMATCH.  A failed call
+   leaves nothing allocated and the handle usable.  Nullable keys and arguments, GROUPS frames, nth_value, ntile, percent_rank and
+   lag / lead without InFrame are not provided. */
+typedef struct chgpu_window chgpu_window;
+enum { CHGPU_WIN_ROW_NUMBER = 0, CHGPU_WIN_RANK, CHGPU_WIN_DENSE_RANK, CHGPU_WIN_COUNT, CHGPU_WIN_SUM, CHGPU_WIN_AVG,
+       CHGPU_WIN_MIN, CHGPU_WIN_MAX, CHGPU_WIN_FIRST_VALUE, CHGPU_WIN_LAST_VALUE, CHGPU_WIN_LAG_IN_FRAME, CHGPU_WIN_LEAD_IN_FRAME };
+enum { CHGPU_FRAME_ROWS = 0, CHGPU_FRAME_RANGE = 1 };
+enum { CHGPU_BOUND_UNBOUNDED_PRECEDING = 0, CHGPU_BOUND_OFFSET_PRECEDING, CHGPU_BOUND_CURRENT_ROW,
+       CHGPU_BOUND_OFFSET_FOLLOWING, CHGPU_BOUND_UNBOUNDED_FOLLOWING };
+typedef struct { int32_t type, begin_kind, end_kind, reserved; uint64_t begin_offset, end_offset; } chgpu_window_frame;
+int chgpu_window_create(chgpu_ctx * ctx, const chgpu_col * const * partition_cols, uint32_t n_partition,
+                        const chgpu_col * const * order_cols, uint32_t n_order, uint64_t rows, chgpu_window ** out);
+int chgpu_window_counts(chgpu_window * window, uint64_t * rows, uint64_t * partitions, uint64_t * peer_groups);
+int chgpu_window_evaluate(chgpu_window * window, int function, const chgpu_window_frame * frame /* NULL = default */,
+                          const chgpu_col * arg /* NULL where the function takes none */,
+                          uint64_t offset /* lag / lead */, uint64_t default_bits /* lag / lead */, chgpu_col ** out);
+int chgpu_window_free(chgpu_window * window);
 /* §8(f) rank 2 — LowCardinality keys (src/Columns/ColumnLowCardinality.h:27-69; low_cardinality_key* variants,
    AggregatedDataVariants.h:119-127; HashMethodSingleLowCardinalityColumn's per-position cache, ColumnsHashing.h:82-260).
    Every Block brings its own dictionary; the host resolves it against the query-wide dictionary into remap_u32[local position]
