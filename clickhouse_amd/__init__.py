@@ -18,6 +18,7 @@ from .keysfixed import KeyDict, KeysFixedAggregator, KeysFixedHashJoin, ColumnFi
 from .uniq import UniqExact
 from .quantile import QuantileExact
 from .group_array import GroupArray
+from .limit_by import BlockKeys, Distinct, LimitBy, distinct_block, limit_by_block
 from .window import CURRENT_ROW, UNBOUNDED, Frame, Window, following, preceding
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -191,6 +191,10 @@ SIGNATURES = {
     "chgpu_group_array_finalize": (_i, [_vp, _pp, _pp, _pp, _pu64]),
     "chgpu_group_array_for_keys": (_i, [_vp, _vp, _pp, _pp]),
     "chgpu_group_array_free": (_i, [_vp]),
+    "chgpu_limit_by_create": (_i, [_vp, _i, _u64, _u64, _u64, _pp]),
+    "chgpu_limit_by_filter_block": (_i, [_vp, _vp, _u64, _u64, _vp, _pp, _pu64]),
+    "chgpu_limit_by_keys": (_i, [_vp, _pu64]),
+    "chgpu_limit_by_free": (_i, [_vp]),
     "chgpu_window_create": (_i, [_vp, _vp, _u32, _vp, _u32, _u64, _pp]),
     "chgpu_window_counts": (_i, [_vp, _pu64, _pu64, _pu64]),
     "chgpu_window_evaluate": (_i, [_vp, _i, C.POINTER(WindowFrame), _vp, _u64, _u64, _pp]),

@@ -588,6 +588,124 @@ private:
     bool remove_filter_column = false;
 };
 
+/// LimitByTransform (src/Processors/Transforms/LimitByTransform.cpp): LIMIT group_length OFFSET group_offset BY the columns at
+/// key_positions.  The key -> counter table lives in HBM across chunks (chgpu_limit_by); a chunk is answered with one filter and every
+/// column is filtered by it.  Keys: one integer column as is; several fixed-width columns of <= 8 bytes together through packFixed
+/// (chgpu_pack_fixed_keys); wider ones through an exact dictionary's ids (chgpu_keydict, at most 32 bytes).  A chunk with no survivor
+/// is dropped, one whose rows all pass goes on untouched (:57-63).
+class GpuLimitByTransform : public ISimpleTransform
+{
+public:
+    GpuLimitByTransform(ContextPtr ctx_, std::vector<size_t> key_positions_, uint64_t group_length_, uint64_t group_offset_, uint64_t size_hint_ = 0)
+        : ctx(std::move(ctx_)), key_positions(std::move(key_positions_)), group_length(group_length_), group_offset(group_offset_), size_hint(size_hint_)
+    {
+        if (key_positions.empty())
+            throw Exception(CHGPU_ERR_BAD_ARGUMENTS, "LIMIT BY without a key column is a plain LIMIT");
+    }
+    ~GpuLimitByTransform() override
+    {
+        chgpu_limit_by_free(op);
+        if (dict)
+            chgpu_keydict_free(dict);
+    }
+    GpuLimitByTransform(const GpuLimitByTransform &) = delete;
+    std::string getName() const override { return "GpuLimitByTransform"; }
+    uint64_t passed_rows = 0;
+    /// keys counted at least once
+    uint64_t keys() const
+    {
+        uint64_t n = 0;
+        if (op)
+            check(chgpu_limit_by_keys(op, &n));
+        return n;
+    }
+
+protected:
+    /// the chunk's key columns as one integer column
+    ColumnPtr keyColumn(const Chunk & chunk)
+    {
+        if (key_positions.size() == 1)
+            return chunk.columns.at(key_positions[0]);
+        std::vector<const chgpu_col *> cols;
+        size_t bytes = 0;
+        for (size_t p : key_positions)
+        {
+            const ColumnVector & c = *chunk.columns.at(p);
+            cols.push_back(c.handle());
+            const int t = c.getDataType();
+            bytes += (t == CHGPU_I64 || t == CHGPU_U64 || t == CHGPU_F64) ? 8 : (t == CHGPU_U32 || t == CHGPU_I32 || t == CHGPU_F32) ? 4 : (t == CHGPU_U16 || t == CHGPU_I16) ? 2 : 1;
+        }
+        chgpu_col * key = nullptr;
+        if (bytes <= 8)
+            check(chgpu_pack_fixed_keys(ctx->get(), static_cast<uint32_t>(cols.size()), cols.data(), &key));
+        else
+        {
+            if (bytes > 32)
+                throw Exception(CHGPU_ERR_NOT_IMPLEMENTED, "LIMIT BY over more than 32 key bytes: CPU path");
+            if (!dict)
+                check(chgpu_keydict_create(ctx->get(), bytes <= 16 ? 16 : 32, size_hint, &dict));
+            check(chgpu_keydict_encode(dict, static_cast<uint32_t>(cols.size()), cols.data(), 0, chunk.num_rows, 1, &key));
+        }
+        return std::make_shared<ColumnVector>(ctx, key);
+    }
+
+    void transform(Chunk & chunk) override
+    {
+        const ColumnPtr key = keyColumn(chunk);
+        if (!op)
+            check(chgpu_limit_by_create(ctx->get(), key->getDataType(), group_length, group_offset, size_hint, &op));
+        chgpu_col * filter = nullptr;
+        uint64_t passed = 0;
+        check(chgpu_limit_by_filter_block(op, key->handle(), 0, chunk.num_rows, nullptr, &filter, &passed));
+        const ColumnVector mask(ctx, filter);
+        if (passed == 0)
+        {
+            chunk.clear();
+            return;
+        }
+        if (passed != chunk.num_rows)
+        {
+            filterColumns(chunk.columns, mask, static_cast<ssize_t>(passed));
+            chunk.num_rows = passed;
+        }
+        passed_rows += passed;
+    }
+
+    ContextPtr ctx;
+    std::vector<size_t> key_positions;
+    uint64_t group_length, group_offset, size_hint;
+    chgpu_limit_by * op = nullptr;
+    chgpu_keydict * dict = nullptr;
+};
+
+/// DistinctTransform (src/Processors/Transforms/DistinctTransform.cpp): SELECT DISTINCT over the columns at key_positions, which is LIMIT 1
+/// BY them.  limit_hint (the query's LIMIT, 0 = none): once the rows emitted reach it, the chunk that crossed it has gone out whole and
+/// no further chunk is taken (stopReading, :62-66).
+class GpuDistinctTransform : public GpuLimitByTransform
+{
+public:
+    GpuDistinctTransform(ContextPtr ctx_, std::vector<size_t> key_positions_, uint64_t limit_hint_ = 0, uint64_t size_hint_ = 0)
+        : GpuLimitByTransform(std::move(ctx_), std::move(key_positions_), 1, 0, size_hint_), limit_hint(limit_hint_) {}
+    std::string getName() const override { return "GpuDistinctTransform"; }
+
+protected:
+    void transform(Chunk & chunk) override
+    {
+        if (limit_hint && passed_rows >= limit_hint)
+        {
+            chunk.clear();
+            input_finished = true;
+            return;
+        }
+        GpuLimitByTransform::transform(chunk);
+        if (limit_hint && passed_rows >= limit_hint)
+            input_finished = true;
+    }
+
+private:
+    uint64_t limit_hint;
+};
+
 /// ActionsDAG (src/Interpreters/ActionsDAG.h): INPUT / COLUMN (constant) / FUNCTION nodes under the reference's function
 /// names; compile() is ExpressionActions' constructor (ExpressionActions.cpp:71-110) plus the run-time compiler the reference
 /// runs under compile_expressions (src/Interpreters/JIT/compileFunction.cpp): the whole DAG becomes one kernel.

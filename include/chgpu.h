@@ -591,6 +591,31 @@ int chgpu_group_array_finalize(chgpu_group_array * group_array, chgpu_col ** key
                                uint64_t * groups);
 int chgpu_group_array_for_keys(chgpu_group_array * group_array, const chgpu_col * keys, chgpu_col ** offsets_u64, chgpu_col ** data_out);
 int chgpu_group_array_free(chgpu_group_array * group_array);
+/* SELECT DISTINCT and LIMIT n [OFFSET m] BY key: DistinctTransform and LimitByTransform::transform
+   (src/Processors/Transforms/DistinctTransform.cpp, LimitByTransform.cpp), with exact keys in place of their SipHash128 of the key
+   columns.  Both clauses ask one thing of a row: how many earlier rows, over all blocks so far and in row order, had this key.  A
+   chgpu_limit_by keeps a key -> counter table in HBM across calls and answers a block with an ordinary IColumn::Filter (UInt8, 0 / 1)
+   for chgpu_filter_columns, chgpu_string_filter and ColumnLowCardinality.filter.
+   Semantics: walk the rows of [row_begin, row_end) in row order.  A row whose filter_u8 byte is zero (NULL: no such row; WHERE fused in,
+   as in chgpu_uniq_add_block) gets 0 and counts nowhere.  Any other row reads its key's counter c: if c < group_offset + group_length
+   the counter becomes c + 1 and the row passes iff c >= group_offset; else the row gets 0.  Counters persist over calls.  DISTINCT is
+   group_length = 1, group_offset = 0.  out_filter_u8 has row_end - row_begin bytes, *rows_passed is their sum (a transform drops an
+   empty chunk and passes a full one untouched).  The result is fully determined by the calls: the same in every run.
+   Keys: key_type is an integer type of 1-8 bytes, its raw bits zero-extended as for chgpu_agg and chgpu_uniq; every bit pattern is a
+   legal key, 0 and 2^64 - 1 included.  A float key and key_type < 0 (without a key the clause is a plain LIMIT) answer
+   CHGPU_ERR_NOT_IMPLEMENTED.  Ids from chgpu_keydict_*, chgpu_lc_remap and the String dictionary, and packed keys, are ordinary keys.
+   size_hint: expected number of keys (0: the table starts small and grows).  chgpu_limit_by_keys: keys counted at least once.
+   Errors: NULL handle or outputs, group_length == 0, row_begin > row_end, a range past the column, a key column of another type ->
+   CHGPU_ERR_BAD_ARGUMENTS; a filter of another length than the key column -> CHGPU_ERR_SIZES_MISMATCH; group_offset + group_length >
+   2^32 - 1 (counters are 32-bit and saturate at that sum) -> CHGPU_ERR_NOT_IMPLEMENTED; 2^32 rows or more in one call, or more
+   than 2^30 keys (a slot is a 32-bit cell index of a table at most half full) -> CHGPU_ERR_TOO_MANY_ROWS.  After CHGPU_ERR_OOM every counter holds what it held before the call (keys the failed
+   call inserted may stay with counter 0, which is what an absent key has).  An empty range is not an error: empty filter, 0 passed. */
+typedef struct chgpu_limit_by chgpu_limit_by;
+int chgpu_limit_by_create(chgpu_ctx * ctx, int key_type, uint64_t group_length, uint64_t group_offset, uint64_t size_hint, chgpu_limit_by ** out);
+int chgpu_limit_by_filter_block(chgpu_limit_by * lb, const chgpu_col * key_col, uint64_t row_begin, uint64_t row_end,
+                                const chgpu_col * filter_u8 /* may be NULL */, chgpu_col ** out_filter_u8, uint64_t * rows_passed);
+int chgpu_limit_by_keys(chgpu_limit_by * lb, uint64_t * keys);   /* keys that have been counted at least once */
+int chgpu_limit_by_free(chgpu_limit_by * lb);                    /* NULL is OK */
 /* Window functions over a sorted block: WindowTransform (src/Processors/Transforms/WindowTransform.cpp: advancePartitionEnd,
    advanceFrameStart / advanceFrameEnd, arePeers; the functions WindowFunctionRowNumber, WindowFunctionRank, WindowFunctionDenseRank,
    WindowFunctionLagLeadInFrame and the aggregate functions run over a frame) with the frames of src/Interpreters/WindowDescription.h
