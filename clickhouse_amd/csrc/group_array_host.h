@@ -1,6 +1,6 @@
 // group_array_host.h — the parts of the groupArray operator (group_array_kernels.hip) that need no device: which radix passes the two
-// key words ask for, the capacity of the doubling store, max_size, the geometry of the segmented copy's work units, and the `debug`
-// option's plan lines.  Plain C++ (the functions the kernels share are __host__ __device__ under hipcc), so that
+// key words ask for and the row limit of the store (over pair_host.h's planner and capacity rule), max_size, the geometry of the
+// segmented copy's work units, and the `debug` option's plan lines.  Plain C++ (the functions the kernels share are __host__ __device__ under hipcc), so that
 // tests/group_array_driver.cpp runs them under a sanitizer.
 #pragma once
 
@@ -23,30 +23,12 @@ static constexpr uint64_t GA_TILE = 2048;
 // output elements of one work unit of the segmented copy: 256 threads x 16 elements
 static constexpr uint64_t GA_UNIT = 4096;
 
-// capacity of the doubling store that takes `need` values: a power of two, at least 4096.  0: `need` is beyond the row limit.
-static inline uint64_t ga_capacity_for(uint64_t need)
-{
-    if (need >= GA_MAX_VALUES)
-        return 0;
-    uint64_t cap = 4096;
-    while (cap < need)
-        cap *= 2;
-    return cap;
-}
+// capacity of the store that takes `need` values (pair_host.h).  0: `need` is beyond the row limit.
+static inline uint64_t ga_capacity_for(uint64_t need) { return need >= GA_MAX_VALUES ? 0 : pair_capacity_for(need); }
 
-// The radix passes of finalize.  or_bits / and_bits are the OR and the AND of every key in the store (0 and ~0 for an empty one), so
-// or_bits & ~and_bits is the set of key bits that differ anywhere.  One stable 256-way pass per key BYTE that holds such a bit, least
-// significant first: shifts[0 .. return) are the passes' bit shifts.  A byte in which no bit varies is equal in all keys: a pass over it
-// would be the identity.
-static inline uint32_t ga_plan_passes(uint64_t or_bits, uint64_t and_bits, uint32_t shifts[8])
-{
-    const uint64_t vary = or_bits & ~and_bits;
-    uint32_t n = 0;
-    for (uint32_t b = 0; b < 8; ++b)
-        if ((vary >> (8 * b)) & 0xFF)
-            shifts[n++] = 8 * b;
-    return n;
-}
+// The radix passes of finalize: or_bits / and_bits are the OR and the AND of every key in the store (0 and ~0 for an empty one); the
+// planner itself is pair_plan_passes (pair_host.h), here over the eight bytes of a UInt64 key.
+static inline uint32_t ga_plan_passes(uint64_t or_bits, uint64_t and_bits, uint32_t shifts[8]) { return pair_plan_passes(or_bits & ~and_bits, 8, shifts); }
 
 // groupArray(N): the first N values of a group of `count`; N = 0 is no limit
 GA_HD uint64_t ga_trim(uint64_t count, uint64_t max_size) { return max_size && count > max_size ? max_size : count; }

@@ -8,31 +8,33 @@
 // Design (not a translation).  Nothing is allocated per group and no table is touched, at any time:
 //   store     u64 keys[cap] (keyed operators), T vals[cap]: T is the unsigned type of the value's width, the value's own bits.  Position
 //             in the store IS arrival order: a filtered block is appended by survivor counts per tile -> scan -> in-wave ballot ranks
-//             (k_ga_tile_counts / k_ga_append), an unfiltered one by a widening copy of the keys and a plain copy of the values.  No
+//             (k_tile_counts / k_ga_append), an unfiltered one by a widening copy of the keys and a plain copy of the values.  No
 //             workgroup waits for another and no place is taken by an atomic.  While keys are written they are folded into two device
 //             words, the OR and the AND of every key held (one wave reduction, one atomic pair per workgroup).
 //   segments  finalize reads the two words back: or & ~and is the set of key bits that differ anywhere.  One stable 256-way pass of
 //             chgpu_partition_by_key_byte over (key, value) per key byte that holds such a bit, least significant first: equal keys end up
-//             adjacent, groups in ascending key order, every group's values still in arrival order.  k_ga_tile_counts / k_ga_heads mark where
+//             adjacent, groups in ascending key order, every group's values still in arrival order.  k_tile_counts / k_ga_heads mark where
 //             the key changes and write the group keys and segment starts by the same counts -> scan -> ballot ranks.
 //   arrays    max_size and for_keys are one segmented copy (k_ga_seg_copy): work units of GA_UNIT OUTPUT elements that find their array
 //             by binary search over the output offsets, so the division of work does not depend on array lengths.  for_keys finds a
 //             key's segment by binary search over the group keys, which the passes left sorted: no table to build or keep.
-// What this operator shares with uniq_kernels.hip / quantile_kernels.hip (element load, pool memory, entry checks, narrowing, plan
-// printing) is pair_store.h.
+// What this operator shares with others is written once elsewhere: the ranked tile (coordinate, ballots, counts kernel, head predicate,
+// ranked-item loop, tile scan) is tile_rank.h, shared with limit_by_kernels.hip; the store (PairStore: reserve, merge's append, export
+// of the keys), the radix passes, element load, entry checks, narrowing and plan printing are pair_store.h / pair_host.h; pool memory,
+// the numbered allocations and a call's temporaries are pair_pool.h.  Its own: the append and head kernels, the value export, the row
+// limit in front of the shared reserve, the two key words.
 #include "chgpu_internal.h"
 
 #include "pair_store.h"
+#include "tile_rank.h"
 #include "group_array_host.h"
 
 typedef unsigned long long ull;
 
-static constexpr u32 GA_T = 256;                   // threads of every kernel here
-static constexpr u32 GA_R = (u32)(GA_TILE / GA_T); // steps of 64 rows a wave takes of a tile
-static constexpr u32 GA_WAVE_ROWS = GA_R * 64;
+static constexpr u32 GA_T = TILE_T; // threads of every kernel here
 static constexpr u32 GA_UNIT_R = (u32)(GA_UNIT / GA_T);
 
-static_assert(GA_TILE == (u64)GA_T * GA_R && GA_UNIT == (u64)GA_T * GA_UNIT_R, "tiles and units are whole steps of a workgroup");
+static_assert(GA_TILE == TILE_ITEMS && GA_UNIT == (u64)GA_T * GA_UNIT_R, "a tile is tile_rank.h's, a unit is whole steps of a workgroup");
 
 // the OR and the AND of every key in the store
 struct GaBits
@@ -81,63 +83,13 @@ __device__ __forceinline__ void ga_fold_bits(u64 o, u64 a, GaBits * bits)
     }
 }
 
-// ---- rows of a tile that satisfy a predicate, ranked in row order -------------------------------------------------------------------
-// A tile is taken wave-striped: step r of wave w covers the 64 consecutive rows from w * GA_WAVE_ROWS + r * 64, so the order (wave,
-// step, lane) is row order and a rank is: the lower waves' counts + the wave's lower steps + the set bits below the lane.
-struct GaFilterPred // the row's filter byte
+// the row's filter byte: the predicate of the filtered append (tile_rank.h)
+struct GaFilterPred
 {
     const u8 * f;
     u64 row_begin;
     __device__ __forceinline__ bool operator()(u64 i) const { return f[row_begin + i] != 0; }
 };
-
-struct GaHeadPred // the first row of a run of equal keys
-{
-    const u64 * k;
-    __device__ __forceinline__ bool operator()(u64 i) const { return i == 0 || k[i] != k[i - 1]; }
-};
-
-__device__ __forceinline__ u64 ga_tile_row(u64 tile, u32 r) { return tile * GA_TILE + (threadIdx.x >> 6) * GA_WAVE_ROWS + r * 64 + lane_id(); }
-
-// the ballots of this wave's steps; returns the number of the tile's rows that precede this wave's among those that satisfy `pred`
-template <typename P>
-__device__ __forceinline__ u32 ga_tile_ballots(const P & pred, u64 tile, u64 n, u64 (&m)[GA_R], u32 * s_wave /* [GA_T / 64] */)
-{
-    u32 cnt = 0;
-#pragma unroll
-    for (u32 r = 0; r < GA_R; ++r)
-    {
-        const u64 i = ga_tile_row(tile, r);
-        m[r] = __ballot(i < n && pred(i));
-        cnt += (u32)__popcll(m[r]);
-    }
-    if (lane_id() == 0)
-        s_wave[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    u32 before = 0;
-    for (u32 w = 0; w < (threadIdx.x >> 6); ++w)
-        before += s_wave[w];
-    return before;
-}
-
-template <typename P>
-__global__ __launch_bounds__(GA_T) void k_ga_tile_counts(P pred, u64 n, u64 n_tiles, u32 * __restrict__ counts)
-{
-    __shared__ u32 s_wave[GA_T / 64];
-    for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
-    {
-        u64 m[GA_R];
-        ga_tile_ballots(pred, tile, n, m, s_wave);
-        if (threadIdx.x == 0)
-        {
-            u32 total = 0;
-            for (u32 w = 0; w < GA_T / 64; ++w)
-                total += s_wave[w];
-            counts[tile] = total;
-        }
-        __syncthreads(); // before the next tile overwrites the counts
-    }
-}
 
 // add_block with a filter: the survivors of tile t go to held + tile_off[t] + their rank in the tile.  key_size 0: without key.
 template <typename T>
@@ -149,29 +101,22 @@ __global__ __launch_bounds__(GA_T) void k_ga_append(const void * __restrict__ ke
     u64 o = 0, a = ~0ull;
     for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
     {
-        u64 m[GA_R];
-        u64 pos = held + tile_off[tile] + ga_tile_ballots(pred, tile, n, m, s_wave);
-#pragma unroll
-        for (u32 r = 0; r < GA_R; ++r)
-        {
-            if ((m[r] >> lane_id()) & 1)
+        u64 m[TILE_R];
+        const u64 pos = held + tile_off[tile] + tile_ballots(pred, tile, n, m, s_wave);
+        tile_for_ranked(m, tile, pos, [&](u64 i, u64 at) {
+            const u64 row = pred.row_begin + i;
+            if (at < cap) // never past the store (the host reserved held + the survivors)
             {
-                const u64 row = pred.row_begin + ga_tile_row(tile, r);
-                const u64 at = pos + mbcnt(m[r]);
-                if (at < cap) // never past the store (the host reserved held + the survivors)
+                if (key_size)
                 {
-                    if (key_size)
-                    {
-                        const u64 k = pair_load(key, key_size, row);
-                        out_k[at] = k;
-                        o |= k;
-                        a &= k;
-                    }
-                    out_v[at] = val[row];
+                    const u64 k = pair_load(key, key_size, row);
+                    out_k[at] = k;
+                    o |= k;
+                    a &= k;
                 }
+                out_v[at] = val[row];
             }
-            pos += (u32)__popcll(m[r]);
-        }
+        });
         __syncthreads(); // before the next tile overwrites the counts
     }
     if (key_size)
@@ -197,28 +142,20 @@ __global__ __launch_bounds__(GA_T) void k_ga_heads(const u64 * __restrict__ sk, 
                                                    u64 * __restrict__ gkeys, u64 * __restrict__ src_off)
 {
     __shared__ u32 s_wave[GA_T / 64];
-    const GaHeadPred pred{sk};
+    const TileHeadPred<u64> pred{sk};
     if (blockIdx.x == 0 && threadIdx.x == 0)
         src_off[groups] = n;
     for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
     {
-        u64 m[GA_R];
-        u64 pos = tile_off[tile] + ga_tile_ballots(pred, tile, n, m, s_wave);
-#pragma unroll
-        for (u32 r = 0; r < GA_R; ++r)
-        {
-            if ((m[r] >> lane_id()) & 1)
+        u64 m[TILE_R];
+        const u64 pos = tile_off[tile] + tile_ballots(pred, tile, n, m, s_wave);
+        tile_for_ranked(m, tile, pos, [&](u64 i, u64 g) {
+            if (g < groups) // (the counts were taken from these keys)
             {
-                const u64 i = ga_tile_row(tile, r);
-                const u64 g = pos + mbcnt(m[r]);
-                if (g < groups) // (the counts were taken from these keys)
-                {
-                    gkeys[g] = sk[i];
-                    src_off[g] = i;
-                }
+                gkeys[g] = sk[i];
+                src_off[g] = i;
             }
-            pos += (u32)__popcll(m[r]);
-        }
+        });
         __syncthreads();
     }
 }
@@ -312,41 +249,12 @@ struct GaFinal
     chgpu_col * sorted_v = nullptr; // the values by group (passes != 0; else the store's values are that)
 };
 
-struct chgpu_group_array : PairOp
+struct chgpu_group_array : PairStore
 {
-    u32 width = 0;
     u64 max_size = 0;
-    u64 held = 0, cap = 0;
-    PairMem k_mem, v_mem, bits_mem;
+    PairMem bits_mem;
     GaFinal fin;
-    long long fail_alloc = 0, alloc_seq = 0; // test hook: allocation number fail_alloc of a call answers OOM
 };
-
-static void ga_begin_call(chgpu_group_array * d)
-{
-    d->alloc_seq = 0;
-    d->fail_alloc = chgpu_opt(d->ctx, "test_group_array_fail_alloc", 0);
-}
-
-static int ga_refused(chgpu_group_array * d)
-{
-    d->alloc_seq += 1;
-    if (d->fail_alloc && d->alloc_seq == d->fail_alloc)
-        return chgpu_set_error(CHGPU_ERR_OOM, "group_array: allocation %lld refused (test_group_array_fail_alloc)", d->alloc_seq);
-    return CHGPU_OK;
-}
-
-static int ga_alloc(chgpu_group_array * d, size_t bytes, PairMem * m)
-{
-    CHGPU_TRY(ga_refused(d));
-    return chgpu_pool_alloc(d->ctx, bytes ? bytes : 256, &m->p, &m->cls);
-}
-
-static int ga_col_new(chgpu_group_array * d, int type, u64 rows, chgpu_col ** out)
-{
-    CHGPU_TRY(ga_refused(d));
-    return chgpu_col_new(d->ctx, type, rows, out);
-}
 
 static void ga_drop_final(chgpu_group_array * d)
 {
@@ -361,73 +269,12 @@ static void ga_drop_final(chgpu_group_array * d)
 static u32 ga_grid(chgpu_ctx * ctx, u64 items) { return chgpu_grid_for(ctx, items, GA_T, 8); }
 static u64 ga_tiles(u64 n) { return (n + GA_TILE - 1) / GA_TILE; }
 
-// temporaries of one call, freed when it ends (reuse of the memory is ordered on the stream)
-struct GaTemps
-{
-    chgpu_group_array * d;
-    std::vector<PairMem> mems;
-    std::vector<chgpu_col *> cols;
-    explicit GaTemps(chgpu_group_array * d_) : d(d_) {}
-    ~GaTemps()
-    {
-        for (PairMem & m : mems)
-            pair_free_mem(d->ctx, m);
-        for (chgpu_col * c : cols)
-            if (c) chgpu_col_free(c);
-    }
-    int alloc(size_t bytes, void ** out)
-    {
-        PairMem m;
-        CHGPU_TRY(ga_alloc(d, bytes, &m));
-        mems.push_back(m);
-        *out = m.p;
-        return CHGPU_OK;
-    }
-};
-
-// counts[n_tiles] (already written) -> tile_off[n_tiles] and the total in *total_dev
-static int ga_scan_tiles(chgpu_ctx * ctx, const u32 * counts, u64 * tile_off, u64 n_tiles, u64 * total_dev, bool inclusive = false)
-{
-    void * scan_tmp = nullptr;
-    const size_t scan_bytes = chgpu_scan_tmp_bytes(n_tiles);
-    CHGPU_TRY(chgpu_scratch(ctx, scan_bytes, &scan_tmp));
-    return inclusive ? chgpu_scan_inclusive_u32_u64(ctx, counts, tile_off, n_tiles, total_dev, scan_tmp, scan_bytes)
-                     : chgpu_scan_exclusive_u32_u64(ctx, counts, tile_off, n_tiles, total_dev, scan_tmp, scan_bytes);
-}
-
-// room for `need` values: every allocation first, so that a failure leaves the store as it was; then what is held is copied
+// room for `need` values, or the row limit's answer
 static int ga_reserve(chgpu_group_array * d, u64 need)
 {
-    const u64 cap = ga_capacity_for(need);
-    CHGPU_REQUIRE(cap != 0, CHGPU_ERR_TOO_MANY_ROWS, "group_array: %llu values, fewer than %llu fit", (unsigned long long)need, (unsigned long long)GA_MAX_VALUES);
-    if (need <= d->cap)
-        return CHGPU_OK;
-    chgpu_ctx * ctx = d->ctx;
-    const bool keyed = d->key_type >= 0;
-    PairMem k, v;
-    int rc = keyed ? ga_alloc(d, cap * 8, &k) : CHGPU_OK;
-    if (rc == CHGPU_OK)
-        rc = ga_alloc(d, cap * d->width, &v);
-    if (rc == CHGPU_OK && d->held)
-    {
-        hipError_t e = keyed ? hipMemcpyAsync(k.p, d->k_mem.p, d->held * 8, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(v.p, d->v_mem.p, d->held * d->width, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess)
-            rc = chgpu_set_error(CHGPU_ERR_DEVICE, "group_array: copying the store failed: %s", hipGetErrorString(e));
-    }
-    if (rc != CHGPU_OK)
-    {
-        pair_free_mem(ctx, k);
-        pair_free_mem(ctx, v);
-        return rc;
-    }
-    pair_free_mem(ctx, d->k_mem); // reuse is ordered behind the copies above (same stream)
-    pair_free_mem(ctx, d->v_mem);
-    d->k_mem = k;
-    d->v_mem = v;
-    d->cap = cap;
-    return CHGPU_OK;
+    CHGPU_REQUIRE(ga_capacity_for(need) != 0, CHGPU_ERR_TOO_MANY_ROWS, "group_array: %llu values, fewer than %llu fit", (unsigned long long)need,
+                  (unsigned long long)GA_MAX_VALUES);
+    return pair_store_reserve(GA_NAMES, *d, need);
 }
 
 extern "C" int chgpu_group_array_create(chgpu_ctx * ctx, int key_type, int value_type, uint64_t max_size, chgpu_group_array ** out)
@@ -436,12 +283,8 @@ extern "C" int chgpu_group_array_create(chgpu_ctx * ctx, int key_type, int value
     CHGPU_TRY(pair_check_create(GA_NAMES, key_type, value_type));
     ChgpuDeviceGuard guard(ctx);
     chgpu_group_array * d = new chgpu_group_array();
-    d->ctx = ctx;
-    d->key_type = key_type < 0 ? -1 : key_type;
-    d->value_type = value_type;
-    d->width = (u32)chgpu_type_size(value_type);
+    pair_store_init(*d, ctx, key_type, value_type, GA_NAMES.op, "test_group_array_fail_alloc");
     d->max_size = max_size;
-    chgpu_ctx_retain(ctx);
     const int rc = chgpu_pool_alloc(ctx, 256, &d->bits_mem.p, &d->bits_mem.cls);
     if (rc != CHGPU_OK)
     {
@@ -460,8 +303,7 @@ extern "C" int chgpu_group_array_free(chgpu_group_array * d)
         return CHGPU_OK;
     ChgpuDeviceGuard guard(d->ctx);
     ga_drop_final(d);
-    pair_free_mem(d->ctx, d->k_mem);
-    pair_free_mem(d->ctx, d->v_mem);
+    pair_store_free(*d);
     pair_free_mem(d->ctx, d->bits_mem);
     chgpu_ctx * ctx = d->ctx;
     delete d;
@@ -493,7 +335,7 @@ static int ga_append(chgpu_group_array * d, const chgpu_col * key_col, const chg
         *entered = n;
         return CHGPU_OK;
     }
-    GaTemps tmp(d);
+    PairTemps tmp(d->mem);
     const u64 n_tiles = ga_tiles(n);
     u32 * counts = nullptr;
     u64 * tile_off = nullptr; // [n_tiles], then the total
@@ -501,9 +343,9 @@ static int ga_append(chgpu_group_array * d, const chgpu_col * key_col, const chg
     CHGPU_TRY(tmp.alloc((n_tiles + 1) * 8, (void **)&tile_off));
     const GaFilterPred pred{(const u8 *)filter_u8->data, row_begin};
     const dim3 grid(chgpu_grid_for(ctx, n_tiles, 1, 8)), block(GA_T);
-    hipLaunchKernelGGL(k_ga_tile_counts<GaFilterPred>, grid, block, 0, ctx->stream, pred, n, n_tiles, counts);
+    hipLaunchKernelGGL(k_tile_counts<GaFilterPred>, grid, block, 0, ctx->stream, pred, n, n_tiles, counts);
     ctx->counters[6] += 1;
-    CHGPU_TRY(ga_scan_tiles(ctx, counts, tile_off, n_tiles, tile_off + n_tiles));
+    CHGPU_TRY(tile_scan(ctx, counts, tile_off, n_tiles, tile_off + n_tiles));
     CHGPU_TRY(pair_launch_ok(GA_NAMES, "count"));
     u64 survivors = 0;
     CHGPU_TRY(chgpu_read_back(ctx, tile_off + n_tiles, &survivors, sizeof(u64)));
@@ -529,7 +371,7 @@ extern "C" int chgpu_group_array_add_block(chgpu_group_array * d, const chgpu_co
     CHGPU_TRY(pair_check_add_block(GA_NAMES, *d, key_col, value_col, row_begin, row_end, filter_u8));
     chgpu_ctx * ctx = d->ctx;
     ChgpuDeviceGuard guard(ctx);
-    ga_begin_call(d);
+    d->mem.begin_call();
     const u64 n = row_end - row_begin;
     GaAddPlan plan;
     plan.n = n;
@@ -556,41 +398,22 @@ extern "C" int chgpu_group_array_merge(chgpu_group_array * dst, const chgpu_grou
                   (unsigned long long)src->max_size, (unsigned long long)dst->max_size);
     chgpu_ctx * ctx = dst->ctx;
     ChgpuDeviceGuard guard(ctx);
-    ga_begin_call(dst);
+    dst->mem.begin_call();
     const u64 n = src->held; // (dst == src puts every array behind itself)
     GaAddPlan plan;
     plan.what = "merge";
     plan.n = n;
     plan.held_before = plan.held = dst->held;
-    int rc = CHGPU_OK;
-    if (n)
+    const int rc = pair_store_append_store(GA_NAMES, *dst, *src, [&](u64 need) { return ga_reserve(dst, need); }, [&] {
+        if (dst->key_type < 0)
+            return;
+        hipLaunchKernelGGL(k_ga_bits_merge, dim3(1), dim3(1), 0, ctx->stream, (GaBits *)dst->bits_mem.p, (const GaBits *)src->bits_mem.p);
+        ctx->counters[6] += 1;
+    });
+    if (rc == CHGPU_OK && n)
     {
-        if (src->ctx != ctx && hipStreamSynchronize(src->ctx->stream) != hipSuccess) // src's values were written on its own stream
-            rc = chgpu_set_error(CHGPU_ERR_DEVICE, "group_array: waiting for the source failed");
-        if (rc == CHGPU_OK)
-            rc = ga_reserve(dst, dst->held + n);
-        if (rc == CHGPU_OK)
-        {
-            const bool keyed = dst->key_type >= 0;
-            hipError_t e = keyed ? hipMemcpyAsync((u64 *)dst->k_mem.p + dst->held, src->k_mem.p, n * 8, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
-            if (e == hipSuccess)
-                e = hipMemcpyAsync((char *)dst->v_mem.p + dst->held * dst->width, src->v_mem.p, n * dst->width, hipMemcpyDeviceToDevice, ctx->stream);
-            if (e == hipSuccess && keyed)
-            {
-                hipLaunchKernelGGL(k_ga_bits_merge, dim3(1), dim3(1), 0, ctx->stream, (GaBits *)dst->bits_mem.p, (const GaBits *)src->bits_mem.p);
-                ctx->counters[6] += 1;
-            }
-            if (e == hipSuccess && src->ctx != ctx)
-                e = hipStreamSynchronize(ctx->stream); // src may change once this returns
-            if (e != hipSuccess)
-                rc = chgpu_set_error(CHGPU_ERR_DEVICE, "group_array: copying the source's store failed: %s", hipGetErrorString(e));
-        }
-        if (rc == CHGPU_OK)
-        {
-            ga_drop_final(dst);
-            dst->held += n;
-            plan.entered = n;
-        }
+        ga_drop_final(dst);
+        plan.entered = n;
     }
     plan.held = dst->held;
     plan.rc = rc;
@@ -608,39 +431,13 @@ extern "C" int chgpu_group_array_size(chgpu_group_array * d, uint64_t * values)
 extern "C" int chgpu_group_array_export_pairs(chgpu_group_array * d, chgpu_col ** keys_out, chgpu_col ** values_out, uint64_t * rows)
 {
     CHGPU_REQUIRE(d && values_out && rows, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    const bool keyed = d->key_type >= 0;
-    CHGPU_REQUIRE(!keyed || keys_out, CHGPU_ERR_BAD_ARGUMENTS, "NULL keys_out");
     chgpu_ctx * ctx = d->ctx;
-    ChgpuDeviceGuard guard(ctx);
-    ga_begin_call(d);
-    chgpu_col * k = nullptr;
-    chgpu_col * v = nullptr;
-    int rc = keyed ? ga_col_new(d, d->key_type, d->held, &k) : CHGPU_OK;
-    if (rc == CHGPU_OK)
-        rc = ga_col_new(d, d->value_type, d->held, &v);
-    if (rc == CHGPU_OK && d->held)
-    {
-        if (keyed)
-        {
-            pair_narrow(ctx, (const u64 *)d->k_mem.p, d->held, k);
-            ctx->counters[6] += 1;
-        }
+    return pair_store_export(GA_NAMES, *d, keys_out, values_out, rows, [&](chgpu_col * v) {
+        ctx->counters[6] += d->key_type >= 0; // (the keys' narrowing; the values are a plain copy)
         if (hipMemcpyAsync(v->data, d->v_mem.p, d->held * d->width, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
-            rc = chgpu_set_error(CHGPU_ERR_DEVICE, "group_array: copying the values failed");
-        if (rc == CHGPU_OK)
-            rc = pair_launch_ok(GA_NAMES, "export");
-    }
-    if (rc != CHGPU_OK)
-    {
-        if (k) chgpu_col_free(k);
-        if (v) chgpu_col_free(v);
-        return rc;
-    }
-    if (keys_out)
-        *keys_out = k;
-    *values_out = v;
-    *rows = d->held;
-    return CHGPU_OK;
+            return chgpu_set_error(CHGPU_ERR_DEVICE, "group_array: copying the values failed");
+        return (int)CHGPU_OK;
+    });
 }
 
 // group keys, segment starts, array ends and the values by group of a store that holds something
@@ -651,13 +448,13 @@ static int ga_build_final(chgpu_group_array * d)
     GaFinal & f = d->fin;
     const u64 H = d->held;
     f.values = H;
-    GaTemps tmp(d);
+    PairTemps tmp(d->mem);
     if (!keyed)
     {
         f.groups = 1;
         f.total_out = ga_trim(H, d->max_size);
-        CHGPU_TRY(ga_alloc(d, 2 * 8, &f.src_off));
-        CHGPU_TRY(ga_alloc(d, 8, &f.out_ends));
+        CHGPU_TRY(d->mem.alloc(2 * 8, &f.src_off));
+        CHGPU_TRY(d->mem.alloc(8, &f.out_ends));
         hipLaunchKernelGGL(k_ga_nokey_offsets, dim3(1), dim3(1), 0, ctx->stream, (u64 *)f.src_off.p, (u64 *)f.out_ends.p, H, d->max_size);
         ctx->counters[6] += 1;
         return pair_launch_ok(GA_NAMES, "offsets");
@@ -670,18 +467,7 @@ static int ga_build_final(chgpu_group_array * d)
     chgpu_col kview = pair_view(ctx, CHGPU_U64, d->k_mem.p, H), vview = pair_view(ctx, d->value_type, d->v_mem.p, H);
     const chgpu_col * cur[2] = {&kview, &vview};
     tmp.cols.assign(2, nullptr); // the pass's keys (freed with the call) and values (kept in the cache after the last pass)
-    for (u32 p = 0; p < f.passes; ++p)
-    {
-        CHGPU_TRY(ga_refused(d)); // the pass's two output columns count as one allocation of the call
-        chgpu_col * outs[2] = {nullptr, nullptr};
-        CHGPU_TRY(chgpu_partition_by_key_byte(ctx, cur[0], shifts[p], 2, cur, outs));
-        for (u32 c = 0; c < 2; ++c)
-        {
-            if (tmp.cols[c]) chgpu_col_free(tmp.cols[c]); // (reuse is ordered behind the pass that read it)
-            tmp.cols[c] = outs[c];
-            cur[c] = outs[c];
-        }
-    }
+    CHGPU_TRY(pair_run_passes(d->mem, shifts, f.passes, cur, tmp.cols.data()));
     const u64 * sk = (const u64 *)cur[0]->data;
     // run heads: counts per tile -> scan -> the group count (the second small read: the caller is told it anyway)
     const u64 n_tiles = ga_tiles(H);
@@ -690,16 +476,16 @@ static int ga_build_final(chgpu_group_array * d)
     CHGPU_TRY(tmp.alloc(n_tiles * 4, (void **)&counts));
     CHGPU_TRY(tmp.alloc((n_tiles + 1) * 8, (void **)&tile_off));
     const dim3 tgrid(chgpu_grid_for(ctx, n_tiles, 1, 8)), block(GA_T);
-    hipLaunchKernelGGL(k_ga_tile_counts<GaHeadPred>, tgrid, block, 0, ctx->stream, GaHeadPred{sk}, H, n_tiles, counts);
-    CHGPU_TRY(ga_scan_tiles(ctx, counts, tile_off, n_tiles, tile_off + n_tiles));
+    hipLaunchKernelGGL(k_tile_counts<TileHeadPred<u64>>, tgrid, block, 0, ctx->stream, TileHeadPred<u64>{sk}, H, n_tiles, counts);
+    CHGPU_TRY(tile_scan(ctx, counts, tile_off, n_tiles, tile_off + n_tiles));
     ctx->counters[6] += 1;
     CHGPU_TRY(pair_launch_ok(GA_NAMES, "boundaries"));
     u64 G = 0;
     CHGPU_TRY(chgpu_read_back(ctx, tile_off + n_tiles, &G, sizeof(G)));
     CHGPU_REQUIRE(G != 0 && G <= H, CHGPU_ERR_LOGICAL, "group_array: %llu groups over %llu values", (unsigned long long)G, (unsigned long long)H);
     f.groups = G;
-    CHGPU_TRY(ga_alloc(d, G * 8, &f.gkeys));
-    CHGPU_TRY(ga_alloc(d, (G + 1) * 8, &f.src_off));
+    CHGPU_TRY(d->mem.alloc(G * 8, &f.gkeys));
+    CHGPU_TRY(d->mem.alloc((G + 1) * 8, &f.src_off));
     hipLaunchKernelGGL(k_ga_heads, tgrid, block, 0, ctx->stream, sk, H, n_tiles, (const u64 *)tile_off, G, (u64 *)f.gkeys.p, (u64 *)f.src_off.p);
     ctx->counters[6] += 1;
     CHGPU_TRY(pair_launch_ok(GA_NAMES, "heads"));
@@ -710,10 +496,10 @@ static int ga_build_final(chgpu_group_array * d)
         u64 * tot = nullptr;
         CHGPU_TRY(tmp.alloc(G * 4, (void **)&len));
         CHGPU_TRY(tmp.alloc(256, (void **)&tot));
-        CHGPU_TRY(ga_alloc(d, G * 8, &f.out_ends));
+        CHGPU_TRY(d->mem.alloc(G * 8, &f.out_ends));
         hipLaunchKernelGGL(k_ga_lens, dim3(ga_grid(ctx, G)), block, 0, ctx->stream, (const u64 *)f.src_off.p, G, d->max_size, len);
         ctx->counters[6] += 1;
-        CHGPU_TRY(ga_scan_tiles(ctx, len, (u64 *)f.out_ends.p, G, tot, true));
+        CHGPU_TRY(tile_scan(ctx, len, (u64 *)f.out_ends.p, G, tot, true));
         CHGPU_TRY(chgpu_read_back(ctx, tot, &f.total_out, sizeof(u64))); // a limited operator only: how many values its arrays hold
         CHGPU_REQUIRE(f.total_out <= H, CHGPU_ERR_LOGICAL, "group_array: arrays of %llu values over %llu held", (unsigned long long)f.total_out, (unsigned long long)H);
     }
@@ -769,7 +555,7 @@ extern "C" int chgpu_group_array_finalize(chgpu_group_array * d, chgpu_col ** ke
     CHGPU_REQUIRE(!keyed || keys_out, CHGPU_ERR_BAD_ARGUMENTS, "NULL keys_out");
     chgpu_ctx * ctx = d->ctx;
     ChgpuDeviceGuard guard(ctx);
-    ga_begin_call(d);
+    d->mem.begin_call();
     chgpu_col * k = nullptr;
     chgpu_col * off = nullptr;
     chgpu_col * data = nullptr;
@@ -781,9 +567,9 @@ extern "C" int chgpu_group_array_finalize(chgpu_group_array * d, chgpu_col ** ke
             // nothing entered: no group; without key exactly one row, the empty array
             rows = keyed ? 0 : 1;
             if (keyed)
-                CHGPU_TRY(ga_col_new(d, d->key_type, 0, &k));
-            CHGPU_TRY(ga_col_new(d, CHGPU_U64, rows, &off));
-            CHGPU_TRY(ga_col_new(d, d->value_type, 0, &data));
+                CHGPU_TRY(d->mem.col_new(d->key_type, 0, &k));
+            CHGPU_TRY(d->mem.col_new(CHGPU_U64, rows, &off));
+            CHGPU_TRY(d->mem.col_new(d->value_type, 0, &data));
             if (rows)
                 CHGPU_HIP(hipMemsetAsync(off->data, 0, rows * 8, ctx->stream));
             return CHGPU_OK;
@@ -794,9 +580,9 @@ extern "C" int chgpu_group_array_finalize(chgpu_group_array * d, chgpu_col ** ke
         ga_fill_plan(d, cached, &plan);
         rows = f.groups;
         if (keyed)
-            CHGPU_TRY(ga_col_new(d, d->key_type, rows, &k));
-        CHGPU_TRY(ga_col_new(d, CHGPU_U64, rows, &off));
-        CHGPU_TRY(ga_col_new(d, d->value_type, f.total_out, &data));
+            CHGPU_TRY(d->mem.col_new(d->key_type, rows, &k));
+        CHGPU_TRY(d->mem.col_new(CHGPU_U64, rows, &off));
+        CHGPU_TRY(d->mem.col_new(d->value_type, f.total_out, &data));
         if (keyed)
         {
             pair_narrow(ctx, (const u64 *)f.gkeys.p, rows, k);
@@ -833,21 +619,21 @@ extern "C" int chgpu_group_array_for_keys(chgpu_group_array * d, const chgpu_col
     CHGPU_TRY(pair_check_device(GA_NAMES, *d, keys));
     chgpu_ctx * ctx = d->ctx;
     ChgpuDeviceGuard guard(ctx);
-    ga_begin_call(d);
+    d->mem.begin_call();
     chgpu_col * off = nullptr;
     chgpu_col * data = nullptr;
     GaPlan plan;
     plan.what = "for_keys";
     const u64 n = keys->rows;
     auto run = [&]() -> int {
-        GaTemps tmp(d);
-        CHGPU_TRY(ga_col_new(d, CHGPU_U64, n, &off));
+        PairTemps tmp(d->mem);
+        CHGPU_TRY(d->mem.col_new(CHGPU_U64, n, &off));
         if (d->held == 0 || n == 0)
         {
             // every asked key gets the empty array; nothing is built
             if (n)
                 CHGPU_HIP(hipMemsetAsync(off->data, 0, n * 8, ctx->stream));
-            return ga_col_new(d, d->value_type, 0, &data);
+            return d->mem.col_new(d->value_type, 0, &data);
         }
         int cached = 0;
         CHGPU_TRY(ga_ensure_final(d, &cached));
@@ -862,11 +648,11 @@ extern "C" int chgpu_group_array_for_keys(chgpu_group_array * d, const chgpu_col
         hipLaunchKernelGGL(k_ga_lookup, dim3(ga_grid(ctx, n)), dim3(GA_T), 0, ctx->stream, (const u64 *)f.gkeys.p, f.groups, ga_ends(f), (const void *)keys->data,
                            (u32)chgpu_type_size(d->key_type), n, gid, len);
         ctx->counters[6] += 1;
-        CHGPU_TRY(ga_scan_tiles(ctx, len, (u64 *)off->data, n, tot, true));
+        CHGPU_TRY(tile_scan(ctx, len, (u64 *)off->data, n, tot, true));
         u64 total = 0;
         CHGPU_TRY(chgpu_read_back(ctx, tot, &total, sizeof(total))); // the data column's length
         CHGPU_REQUIRE(total < (1ull << 40), CHGPU_ERR_TOO_MANY_ROWS, "group_array: the asked arrays hold %llu values", (unsigned long long)total);
-        CHGPU_TRY(ga_col_new(d, d->value_type, total, &data));
+        CHGPU_TRY(d->mem.col_new(d->value_type, total, &data));
         if (total)
             ga_launch_seg_copy(d, gid, (const u64 *)off->data, n, total, data);
         return pair_launch_ok(GA_NAMES, "for_keys");

@@ -1,6 +1,6 @@
 // limit_by_host.h — the parts of the DISTINCT / LIMIT BY operator (limit_by_kernels.hip) that need no device: table geometry and
-// growth, the checks of create and filter_block, which plan a block takes, which slot bytes the rank plan passes over, and the `debug`
-// option's plan line.  Plain C++, so that tests/limit_by_driver.cpp runs them under a sanitizer.
+// growth, the checks of create and filter_block, which plan a block takes, which slot bytes the rank plan passes over (the planner is pair_host.h's), and the
+// `debug` option's plan line.  Plain C++, so that tests/limit_by_driver.cpp runs them under a sanitizer.
 #pragma once
 
 #include <cstdint>
@@ -125,18 +125,9 @@ static inline LbPlanKind lb_choose_plan(uint64_t live, uint64_t bound /* offset 
 
 static inline const char * lb_plan_name(LbPlanKind k) { return k == LB_PLAN_DEAD ? "dead" : k == LB_PLAN_CLAIM ? "claim" : "rank"; }
 
-// The radix passes of the rank plan.  or_bits / and_bits are the OR and the AND of the live records' slots (0 and ~0 for none), so
-// or_bits & ~and_bits is the set of slot bits that differ among them.  One stable 256-way pass per slot BYTE that holds such a bit,
-// least significant first: shifts[0 .. return) are the passes' bit shifts.  No pass when one slot is live.
-static inline uint32_t lb_plan_passes(uint32_t or_bits, uint32_t and_bits, uint32_t shifts[4])
-{
-    const uint32_t vary = or_bits & ~and_bits;
-    uint32_t n = 0;
-    for (uint32_t b = 0; b < 4; ++b)
-        if ((vary >> (8 * b)) & 0xFF)
-            shifts[n++] = 8 * b;
-    return n;
-}
+// The radix passes of the rank plan: or_bits / and_bits are the OR and the AND of the live records' slots (0 and ~0 for none); the
+// planner itself is pair_plan_passes (pair_host.h), here over the four bytes of a slot.  No pass when one slot is live.
+static inline uint32_t lb_plan_passes(uint32_t or_bits, uint32_t and_bits, uint32_t shifts[4]) { return pair_plan_passes(or_bits & ~and_bits, 4, shifts); }
 
 // what one chgpu_limit_by_filter_block did
 struct LbPlan

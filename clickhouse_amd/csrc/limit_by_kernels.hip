@@ -25,16 +25,19 @@
 //             filter[row] = offset <= count + rank < offset + length; the counters are raised in a launch of their own (one lane per
 //             segment), so no lane reads a counter another lane of the launch writes.
 // Counters and claims are written only after the call's last allocation: a call that answers OOM leaves every counter as it was.
+// Shared with group_array_kernels.hip and written once elsewhere: the rank plan's head ballots, counts kernel, ranked-item loop and
+// tile scan (tile_rank.h), its pass planner and pass loop (pair_host.h, pair_store.h); the numbered allocations and the call's
+// temporaries are pair_pool.h.  k_lb_compact and k_lb_resolve rank lane-consecutive rows, another layout, and stay as they are.
 #include "chgpu_internal.h"
 
 #include "pair_store.h"
+#include "tile_rank.h"
 #include "limit_by_host.h"
 
-static constexpr u32 LB_T = 256; // threads of every kernel here
-static constexpr u32 LB_V = 4;   // consecutive rows of a lane in the resolve and compaction kernels
-static constexpr u32 LB_R = 8;   // steps of 64 records a wave takes of a record tile
-static constexpr u32 LB_RTILE = LB_T * LB_R;
-static constexpr u32 LB_WAVE_RECS = LB_R * 64;
+static constexpr u32 LB_T = TILE_T;         // threads of every kernel here
+static constexpr u32 LB_V = 4;              // consecutive rows of a lane in the resolve and compaction kernels
+static constexpr u32 LB_R = TILE_R;         // steps of LB_T records a workgroup takes of a record tile in the claim plan
+static constexpr u32 LB_RTILE = TILE_ITEMS; // records of a record tile: the claim plan's, and tile_rank.h's tile in the rank plan
 static constexpr u32 LB_LDS_CELLS = 1024; // the claim plan's workgroup set
 static constexpr u32 LB_LDS_PROBES = 16;
 
@@ -421,47 +424,8 @@ __global__ __launch_bounds__(LB_T) void k_lb_claim_pass(const u32 * __restrict__
 }
 
 // ---- plan rank ----------------------------------------------------------------------------------------------------------------
-// A record tile is taken wave-striped: step r of wave w covers the 64 consecutive records from w * LB_WAVE_RECS + r * 64, so the order
-// (wave, step, lane) is record order.  A head is the first record of a run of equal slots.
-__device__ __forceinline__ u64 lb_tile_rec(u64 tile, u32 r) { return tile * LB_RTILE + (threadIdx.x >> 6) * LB_WAVE_RECS + r * 64 + lane_id(); }
-
-// the head ballots of this wave's steps; returns the number of the tile's heads that precede this wave's
-__device__ __forceinline__ u32 lb_head_ballots(const u32 * __restrict__ ss, u64 tile, u64 n, u64 (&m)[LB_R], u32 * s_wave /* [LB_T / 64] */)
-{
-    u32 cnt = 0;
-#pragma unroll
-    for (u32 r = 0; r < LB_R; ++r)
-    {
-        const u64 i = lb_tile_rec(tile, r);
-        m[r] = __ballot(i < n && (i == 0 || ss[i] != ss[i - 1]));
-        cnt += (u32)__popcll(m[r]);
-    }
-    if (lane_id() == 0)
-        s_wave[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    u32 before = 0;
-    for (u32 w = 0; w < (threadIdx.x >> 6); ++w)
-        before += s_wave[w];
-    return before;
-}
-
-__global__ __launch_bounds__(LB_T) void k_lb_head_counts(const u32 * __restrict__ ss, u64 n, u64 n_tiles, u32 * __restrict__ counts)
-{
-    __shared__ u32 s_wave[LB_T / 64];
-    for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
-    {
-        u64 m[LB_R];
-        lb_head_ballots(ss, tile, n, m, s_wave);
-        if (threadIdx.x == 0)
-        {
-            u32 total = 0;
-            for (u32 w = 0; w < LB_T / 64; ++w)
-                total += s_wave[w];
-            counts[tile] = total;
-        }
-        __syncthreads();
-    }
-}
+// A head is the first record of a run of equal slots: TileHeadPred<u32> over the sorted slots, counted and ranked per record tile by
+// tile_rank.h.
 
 // segment g starts at seg_start[g]; seg_start[segments] = n.  seg_start has n + 1 entries, segments <= n is read from the scan's total.
 __global__ __launch_bounds__(LB_T) void k_lb_heads(const u32 * __restrict__ ss, u64 n, u64 n_tiles, const u64 * __restrict__ tile_off, const u64 * __restrict__ segments,
@@ -472,19 +436,12 @@ __global__ __launch_bounds__(LB_T) void k_lb_heads(const u32 * __restrict__ ss, 
         seg_start[*segments] = (u32)n;
     for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
     {
-        u64 m[LB_R];
-        u64 pos = tile_off[tile] + lb_head_ballots(ss, tile, n, m, s_wave);
-#pragma unroll
-        for (u32 r = 0; r < LB_R; ++r)
-        {
-            if ((m[r] >> lane_id()) & 1)
-            {
-                const u64 g = pos + mbcnt(m[r]);
-                if (g < n)
-                    seg_start[g] = (u32)lb_tile_rec(tile, r);
-            }
-            pos += (u32)__popcll(m[r]);
-        }
+        u64 m[TILE_R];
+        const u64 pos = tile_off[tile] + tile_ballots(TileHeadPred<u32>{ss}, tile, n, m, s_wave);
+        tile_for_ranked(m, tile, pos, [&](u64 i, u64 g) {
+            if (g < n)
+                seg_start[g] = (u32)i;
+        });
         __syncthreads();
     }
 }
@@ -498,12 +455,12 @@ __global__ __launch_bounds__(LB_T) void k_lb_rank_apply(const u32 * __restrict__
     u32 passed = 0;
     for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
     {
-        u64 m[LB_R];
-        u64 pos = tile_off[tile] + lb_head_ballots(ss, tile, n_live, m, s_wave);
+        u64 m[TILE_R];
+        u64 pos = tile_off[tile] + tile_ballots(TileHeadPred<u32>{ss}, tile, n_live, m, s_wave);
 #pragma unroll
-        for (u32 r = 0; r < LB_R; ++r)
+        for (u32 r = 0; r < TILE_R; ++r)
         {
-            const u64 i = lb_tile_rec(tile, r);
+            const u64 i = tile_item(tile, r);
             // heads at or before this record, over the whole input: its segment is that number - 1
             const u64 upto = pos + mbcnt(m[r]) + ((m[r] >> lane_id()) & 1);
             if (i < n_live && upto >= 1 && upto <= n_live)
@@ -549,61 +506,14 @@ __global__ __launch_bounds__(LB_T) void k_lb_count_update(const u32 * __restrict
 // ---------------------------------------------------------------------------------------------
 static constexpr PairNames LB_NAMES{"limit_by", "operator", "an operator"};
 
-struct chgpu_limit_by
+struct chgpu_limit_by : PairOp
 {
-    chgpu_ctx * ctx = nullptr;
-    int key_type = 0;
     u32 offset = 0, bound = 0; // group_offset, group_offset + group_length
     u64 cap = 0;
     u64 occupied = 0; // cells taken (keys of a failed call included)
     u64 counted = 0;  // counters > 0
     PairMem cells, count, claim, ctl;
-    long long fail_alloc = 0, alloc_seq = 0; // test hook: allocation number fail_alloc of a call answers OOM
-};
-
-static int lb_refused(chgpu_limit_by * d)
-{
-    d->alloc_seq += 1;
-    if (d->fail_alloc && d->alloc_seq == d->fail_alloc)
-        return chgpu_set_error(CHGPU_ERR_OOM, "limit_by: allocation %lld refused (test_limit_by_fail_alloc)", d->alloc_seq);
-    return CHGPU_OK;
-}
-
-static int lb_alloc(chgpu_limit_by * d, size_t bytes, PairMem * m)
-{
-    CHGPU_TRY(lb_refused(d));
-    return chgpu_pool_alloc(d->ctx, bytes ? bytes : 256, &m->p, &m->cls);
-}
-
-// temporaries of one call, freed when it ends (reuse of the memory is ordered on the stream)
-struct LbTemps
-{
-    chgpu_limit_by * d;
-    std::vector<PairMem> mems;
-    std::vector<chgpu_col *> cols;
-    explicit LbTemps(chgpu_limit_by * d_) : d(d_) {}
-    ~LbTemps()
-    {
-        for (PairMem & m : mems)
-            pair_free_mem(d->ctx, m);
-        for (chgpu_col * c : cols)
-            if (c) chgpu_col_free(c);
-    }
-    int alloc(size_t bytes, void ** out)
-    {
-        PairMem m;
-        CHGPU_TRY(lb_alloc(d, bytes, &m));
-        mems.push_back(m);
-        *out = m.p;
-        return CHGPU_OK;
-    }
-    int col(int type, u64 rows, chgpu_col ** out)
-    {
-        CHGPU_TRY(lb_refused(d));
-        CHGPU_TRY(chgpu_col_new(d->ctx, type, rows, out));
-        cols.push_back(*out);
-        return CHGPU_OK;
-    }
+    PairAllocs mem;
 };
 
 static u32 lb_grid(chgpu_ctx * ctx, u64 blocks_wanted)
@@ -626,11 +536,11 @@ static int lb_ctl_read(chgpu_limit_by * d, LbCtl * host) { return chgpu_read_bac
 static int lb_new_table(chgpu_limit_by * d, u64 cap, PairMem * cells, PairMem * count, PairMem * claim)
 {
     chgpu_ctx * ctx = d->ctx;
-    int rc = lb_alloc(d, cap * 8, cells);
+    int rc = d->mem.alloc(cap * 8, cells);
     if (rc == CHGPU_OK)
-        rc = lb_alloc(d, (cap + 1) * 4, count);
+        rc = d->mem.alloc((cap + 1) * 4, count);
     if (rc == CHGPU_OK)
-        rc = lb_alloc(d, (cap + 1) * 4, claim);
+        rc = d->mem.alloc((cap + 1) * 4, claim);
     if (rc == CHGPU_OK &&
         (hipMemsetAsync(cells->p, 0, cap * 8, ctx->stream) != hipSuccess || hipMemsetAsync(count->p, 0, (cap + 1) * 4, ctx->stream) != hipSuccess ||
          hipMemsetAsync(claim->p, 0xFF, (cap + 1) * 4, ctx->stream) != hipSuccess))
@@ -678,6 +588,7 @@ extern "C" int chgpu_limit_by_create(chgpu_ctx * ctx, int key_type, uint64_t gro
     chgpu_limit_by * d = new chgpu_limit_by();
     d->ctx = ctx;
     d->key_type = key_type;
+    d->mem = PairAllocs{ctx, LB_NAMES.op, "test_limit_by_fail_alloc"};
     d->offset = (u32)group_offset;
     d->bound = (u32)(group_offset + group_length);
     chgpu_ctx_retain(ctx);
@@ -791,18 +702,10 @@ static int lb_resolve_all(chgpu_limit_by * d, const LbBlock & b, LbCtl * seen, L
     }
 }
 
-static int lb_scan_tiles(chgpu_ctx * ctx, const u32 * counts, u64 * tile_off, u64 n_tiles, u64 * total_dev)
-{
-    void * scan_tmp = nullptr;
-    const size_t scan_bytes = chgpu_scan_tmp_bytes(n_tiles);
-    CHGPU_TRY(chgpu_scratch(ctx, scan_bytes, &scan_tmp));
-    return chgpu_scan_exclusive_u32_u64(ctx, counts, tile_off, n_tiles, total_dev, scan_tmp, scan_bytes);
-}
-
 static int lb_filter_block(chgpu_limit_by * d, const chgpu_col * key_col, u64 row_begin, u64 n, const chgpu_col * filter_u8, chgpu_col * out, LbPlan * plan)
 {
     chgpu_ctx * ctx = d->ctx;
-    LbTemps tmp(d);
+    PairTemps tmp(d->mem);
     LbBlock b{};
     b.key_size = (u32)chgpu_type_size(d->key_type);
     b.kp = (const char *)key_col->data + row_begin * b.key_size;
@@ -843,24 +746,16 @@ static int lb_filter_block(chgpu_limit_by * d, const chgpu_col * key_col, u64 ro
         CHGPU_TRY(tmp.alloc((rec_tiles + 1) * 8, (void **)&head_off));
         CHGPU_TRY(tmp.alloc((L + 1) * 4, (void **)&seg_start));
     }
-    CHGPU_TRY(lb_scan_tiles(ctx, b.tile_counts, tile_off, b.n_tiles, tile_off + b.n_tiles));
+    CHGPU_TRY(tile_scan(ctx, b.tile_counts, tile_off, b.n_tiles, tile_off + b.n_tiles));
     hipLaunchKernelGGL(k_lb_compact, dim3(lb_grid(ctx, b.n_tiles)), dim3(LB_T), 0, ctx->stream, (const u32 *)b.slot, b.lead, b.n_tiles, (const u64 *)tile_off, L,
                        (u32 *)rec_slot->data, (u32 *)rec_row->data);
     ctx->counters[6] += 1;
     CHGPU_TRY(pair_launch_ok(LB_NAMES, "compact"));
 
     const chgpu_col * cur[2] = {rec_slot, rec_row};
-    for (u32 p = 0; p < plan->passes; ++p)
-    {
-        CHGPU_TRY(lb_refused(d)); // the pass's two output columns count as one allocation of the call
-        chgpu_col * outs[2] = {nullptr, nullptr};
-        CHGPU_TRY(chgpu_partition_by_key_byte(ctx, cur[0], shifts[p], 2, cur, outs));
-        for (u32 c = 0; c < 2; ++c)
-        {
-            tmp.cols.push_back(outs[c]); // (freed with the call: reuse is ordered on the stream)
-            cur[c] = outs[c];
-        }
-    }
+    const size_t own = tmp.cols.size(); // the latest pass's two columns, freed with the call like the records
+    tmp.cols.resize(own + 2, nullptr);
+    CHGPU_TRY(pair_run_passes(d->mem, shifts, plan->passes, cur, &tmp.cols[own]));
     // from here on nothing is allocated: counters and claims change
     CHGPU_TRY(lb_ctl_reset(d));
     const u32 * ss = (const u32 *)cur[0]->data;
@@ -875,8 +770,8 @@ static int lb_filter_block(chgpu_limit_by * d, const chgpu_col * key_col, u64 ro
     }
     else
     {
-        hipLaunchKernelGGL(k_lb_head_counts, tgrid, block, 0, ctx->stream, ss, L, rec_tiles, head_counts);
-        CHGPU_TRY(lb_scan_tiles(ctx, head_counts, head_off, rec_tiles, head_off + rec_tiles));
+        hipLaunchKernelGGL(k_tile_counts<TileHeadPred<u32>>, tgrid, block, 0, ctx->stream, TileHeadPred<u32>{ss}, L, rec_tiles, head_counts);
+        CHGPU_TRY(tile_scan(ctx, head_counts, head_off, rec_tiles, head_off + rec_tiles));
         const u64 * segments = head_off + rec_tiles;
         hipLaunchKernelGGL(k_lb_heads, tgrid, block, 0, ctx->stream, ss, L, rec_tiles, (const u64 *)head_off, segments, seg_start);
         hipLaunchKernelGGL(k_lb_rank_apply, tgrid, block, 0, ctx->stream, ss, sr, L, rec_tiles, (const u64 *)head_off, (const u32 *)seg_start, (const u32 *)d->count.p,
@@ -899,24 +794,20 @@ extern "C" int chgpu_limit_by_filter_block(chgpu_limit_by * d, const chgpu_col *
     CHGPU_REQUIRE(d && key_col && out_filter_u8 && rows_passed, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
     CHGPU_REQUIRE(key_col->type == d->key_type, CHGPU_ERR_BAD_ARGUMENTS, "limit_by: key column of type %d, the operator was made for %d", key_col->type, d->key_type);
     CHGPU_REQUIRE(!filter_u8 || filter_u8->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "limit_by: the filter must be UInt8");
-    CHGPU_REQUIRE(key_col->ctx->device == d->ctx->device && (!filter_u8 || filter_u8->ctx->device == d->ctx->device), CHGPU_ERR_BAD_ARGUMENTS,
-                  "limit_by: a column lives on another device than the operator");
+    CHGPU_TRY(pair_check_device(LB_NAMES, *d, key_col, filter_u8));
     const char * msg = "";
     const int code = lb_check_rows(key_col->rows, filter_u8 ? (int64_t)filter_u8->rows : -1, row_begin, row_end, &msg);
     CHGPU_REQUIRE(code == CHGPU_OK, code, "limit_by: %s", msg);
     chgpu_ctx * ctx = d->ctx;
     ChgpuDeviceGuard guard(ctx);
-    d->alloc_seq = 0;
-    d->fail_alloc = chgpu_opt(ctx, "test_limit_by_fail_alloc", 0);
+    d->mem.begin_call();
     const u64 n = row_end - row_begin;
     LbPlan plan;
     plan.n = n;
     plan.keys_before = plan.keys = d->counted;
     plan.cap_before = plan.cap = d->cap;
     chgpu_col * out = nullptr;
-    int rc = lb_refused(d);
-    if (rc == CHGPU_OK)
-        rc = chgpu_col_new(ctx, CHGPU_U8, n, &out);
+    int rc = d->mem.col_new(CHGPU_U8, n, &out);
     if (rc == CHGPU_OK && n)
         rc = lb_filter_block(d, key_col, row_begin, n, filter_u8, out, &plan);
     plan.keys = d->counted;

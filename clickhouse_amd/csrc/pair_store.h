@@ -1,14 +1,18 @@
 // pair_store.h — what the operators that keep a flat store of (group key, value) pairs in HBM beside an aggregator share (uniqExact:
-// uniq_kernels.hip, quantileExact: quantile_kernels.hip): the element load, the pool memory they own, the entry checks of create /
-// add_block / merge / the keys look-up, the count() GROUP BY over the store's keys, and the small launches around them.  The key ->
-// group table is group_table.h.  A helper here launches and never counts or allocates: ctx->counters and every allocation stay with
-// the caller, which numbers them (test_quantile_fail_alloc).  Kernels are templates or static: two translation units include this file.
+// uniq_kernels.hip, quantileExact: quantile_kernels.hip, groupArray: group_array_kernels.hip; the entry helpers also serve
+// limit_by_kernels.hip): the element load, the entry checks of create / add_block / merge / the keys look-up, the count() GROUP BY over
+// the store's keys, the small launches around them, the append-only store itself (PairStore: reserve, append another store, export) and
+// the radix passes over (key, payload) columns.  Pool memory, the numbered allocations and a call's temporaries are pair_pool.h; the
+// key -> group table is group_table.h.  A helper here launches and never counts: ctx->counters stay with the caller.  What a helper
+// allocates goes through the caller's PairAllocs, in the order its comment states, so every call's numbering is written down
+// (test_quantile_fail_alloc).  Kernels are templates or static: several translation units include this file.
 #pragma once
 
 #include "chgpu_internal.h"
 
 #include "group_table.h"
 #include "pair_host.h"
+#include "pair_pool.h"
 
 // raw bits of element i of a column of `size`-byte elements, zero-extended (keys as load_key_zext; values as their own bits)
 __device__ __forceinline__ u64 pair_load(const void * p, u32 size, u64 i)
@@ -49,20 +53,6 @@ struct PairOp
     int key_type = -1; // < 0: without key
     int value_type = 0;
 };
-
-// memory from the context's pool
-struct PairMem
-{
-    void * p = nullptr;
-    size_t cls = 0;
-};
-
-static void pair_free_mem(chgpu_ctx * ctx, PairMem & m)
-{
-    if (m.p)
-        chgpu_pool_free(ctx, m.p, m.cls);
-    m = PairMem{};
-}
 
 static chgpu_col pair_view(chgpu_ctx * ctx, int type, void * data, u64 rows)
 {
@@ -175,5 +165,151 @@ static int pair_check_keys(const PairNames & nm, const PairOp & d, const chgpu_c
 {
     CHGPU_REQUIRE(d.key_type >= 0, CHGPU_ERR_BAD_ARGUMENTS, "%s: %s without key has no keys to look up", nm.op, nm.a_noun);
     CHGPU_REQUIRE(keys->type == d.key_type, CHGPU_ERR_BAD_ARGUMENTS, "%s: key column of type %d, the %s was made for %d", nm.op, keys->type, nm.noun, d.key_type);
+    return CHGPU_OK;
+}
+
+// ---- the flat append-only store: u64 keys[cap] (keyed operators) and `width`-byte values[cap], `held` of them in use ----
+struct PairStore : PairOp
+{
+    PairMem k_mem, v_mem;
+    u64 held = 0, cap = 0;
+    u32 width = 0;
+    PairAllocs mem; // the operator's numbered allocations, the store's among them
+};
+
+// create, once the arguments are checked: the fields above, and the context is retained
+static void pair_store_init(PairStore & s, chgpu_ctx * ctx, int key_type, int value_type, const char * op, const char * fail_option)
+{
+    s.ctx = ctx;
+    s.key_type = key_type < 0 ? -1 : key_type;
+    s.value_type = value_type;
+    s.width = (u32)chgpu_type_size(value_type);
+    s.mem.ctx = ctx;
+    s.mem.op = op;
+    s.mem.option = fail_option;
+    chgpu_ctx_retain(ctx);
+}
+
+static void pair_store_free(PairStore & s)
+{
+    pair_free_mem(s.ctx, s.k_mem);
+    pair_free_mem(s.ctx, s.v_mem);
+}
+
+// Room for `need` values (the caller has answered its own row limit).  Every allocation first (the keys' when keyed, then the
+// values'), so that a failure leaves the store as it was; then what is held is copied.
+static int pair_store_reserve(const PairNames & nm, PairStore & s, u64 need)
+{
+    if (need <= s.cap)
+        return CHGPU_OK;
+    chgpu_ctx * ctx = s.ctx;
+    const bool keyed = s.key_type >= 0;
+    const u64 cap = pair_capacity_for(need);
+    PairMem k, v;
+    int rc = keyed ? s.mem.alloc(cap * 8, &k) : CHGPU_OK;
+    if (rc == CHGPU_OK)
+        rc = s.mem.alloc(cap * s.width, &v);
+    if (rc == CHGPU_OK && s.held)
+    {
+        hipError_t e = keyed ? hipMemcpyAsync(k.p, s.k_mem.p, s.held * 8, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(v.p, s.v_mem.p, s.held * s.width, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess)
+            rc = chgpu_set_error(CHGPU_ERR_DEVICE, "%s: copying the store failed: %s", nm.op, hipGetErrorString(e));
+    }
+    if (rc != CHGPU_OK)
+    {
+        pair_free_mem(ctx, k);
+        pair_free_mem(ctx, v);
+        return rc;
+    }
+    pair_store_free(s); // reuse is ordered behind the copies above (same stream)
+    s.k_mem = k;
+    s.v_mem = v;
+    s.cap = cap;
+    return CHGPU_OK;
+}
+
+// merge: the whole of `src` behind what `dst` holds; dst may be src.  reserve(need) is the operator's own reserve, with its row limit.
+// after_copies() runs on dst's stream behind the two copies and BEFORE the wait that lets the source change: what else the operator
+// reads of the source (groupArray's key words) is launched there.
+template <typename Reserve, typename After>
+static int pair_store_append_store(const PairNames & nm, PairStore & dst, const PairStore & src, Reserve reserve, After after_copies)
+{
+    chgpu_ctx * ctx = dst.ctx;
+    const u64 n = src.held;
+    if (n == 0)
+        return CHGPU_OK;
+    if (src.ctx != ctx && hipStreamSynchronize(src.ctx->stream) != hipSuccess) // src's values were written on its own stream
+        return chgpu_set_error(CHGPU_ERR_DEVICE, "%s: waiting for the source failed", nm.op);
+    CHGPU_TRY(reserve(dst.held + n));
+    const bool keyed = dst.key_type >= 0;
+    hipError_t e = keyed ? hipMemcpyAsync((u64 *)dst.k_mem.p + dst.held, src.k_mem.p, n * 8, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
+    if (e == hipSuccess)
+        e = hipMemcpyAsync((char *)dst.v_mem.p + dst.held * dst.width, src.v_mem.p, n * dst.width, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e == hipSuccess)
+        after_copies();
+    if (e == hipSuccess && src.ctx != ctx)
+        e = hipStreamSynchronize(ctx->stream); // src may change once this returns
+    if (e != hipSuccess)
+        return chgpu_set_error(CHGPU_ERR_DEVICE, "%s: copying the source's store failed: %s", nm.op, hipGetErrorString(e));
+    dst.held += n;
+    return CHGPU_OK;
+}
+
+// export_pairs behind the caller's NULL checks: the keys column (keyed operators) and the values column are allocated in that order,
+// the keys narrowed to their type; export_values(column) launches or enqueues the operator's own copy of the values and counts both.
+template <typename Values>
+static int pair_store_export(const PairNames & nm, PairStore & s, chgpu_col ** keys_out, chgpu_col ** values_out, uint64_t * rows, Values export_values)
+{
+    const bool keyed = s.key_type >= 0;
+    CHGPU_REQUIRE(!keyed || keys_out, CHGPU_ERR_BAD_ARGUMENTS, "NULL keys_out");
+    ChgpuDeviceGuard guard(s.ctx);
+    s.mem.begin_call();
+    chgpu_col * k = nullptr;
+    chgpu_col * v = nullptr;
+    int rc = keyed ? s.mem.col_new(s.key_type, s.held, &k) : CHGPU_OK;
+    if (rc == CHGPU_OK)
+        rc = s.mem.col_new(s.value_type, s.held, &v);
+    if (rc == CHGPU_OK && s.held)
+    {
+        if (keyed)
+            pair_narrow(s.ctx, (const u64 *)s.k_mem.p, s.held, k);
+        rc = export_values(v);
+        if (rc == CHGPU_OK)
+            rc = pair_launch_ok(nm, "export");
+    }
+    if (rc != CHGPU_OK)
+    {
+        if (k) chgpu_col_free(k);
+        if (v) chgpu_col_free(v);
+        return rc;
+    }
+    if (keys_out)
+        *keys_out = k;
+    *values_out = v;
+    *rows = s.held;
+    return CHGPU_OK;
+}
+
+// ---- radix passes over (key column, payload column) ----
+// Pass p is one stable 256-way chgpu_partition_by_key_byte by the key's byte at shifts[p] and counts as ONE allocation of the call (its
+// two output columns).  cur[2]: the input on entry (it stays the caller's), the last pass's output on return.  own[2]: NULL on entry;
+// the columns of the latest pass, the caller's to free (its temporaries): a pass's input is freed as soon as the next pass has replaced
+// it (reuse is ordered on the stream behind the pass that read it), so at most two generations are alive.
+static int pair_run_passes(PairAllocs & mem, const u32 * shifts, u32 passes, const chgpu_col * cur[2], chgpu_col ** own /* [2] */)
+{
+    for (u32 p = 0; p < passes; ++p)
+    {
+        CHGPU_TRY(mem.refused());
+        chgpu_col * outs[2] = {nullptr, nullptr};
+        CHGPU_TRY(chgpu_partition_by_key_byte(mem.ctx, cur[0], shifts[p], 2, cur, outs));
+        for (u32 c = 0; c < 2; ++c)
+        {
+            if (own[c]) chgpu_col_free(own[c]);
+            own[c] = outs[c];
+            cur[c] = outs[c];
+        }
+    }
     return CHGPU_OK;
 }

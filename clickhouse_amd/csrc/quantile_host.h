@@ -161,14 +161,8 @@ static inline int qt_check_levels(int kind, uint32_t n_levels, const double * le
     return CHGPU_OK;
 }
 
-// capacity of the doubling store that takes `need` values: a power of two, at least 4096
-static inline uint64_t qt_capacity_for(uint64_t need)
-{
-    uint64_t cap = 4096;
-    while (cap < need)
-        cap *= 2;
-    return cap;
-}
+// capacity of the store that takes `need` values (pair_host.h; qt_reserve answers the row limit in front of it)
+static inline uint64_t qt_capacity_for(uint64_t need) { return pair_capacity_for(need); }
 
 // what one chgpu_quantile_add_block / chgpu_quantile_merge did
 struct QtAddPlan

@@ -18,8 +18,10 @@
 //            of the values that match the prefix fixed so far (k_qt_hist, 256 counters per level in LDS, then added to the segment's
 //            global counters); one wave per (segment, level) scans the 256 counters, fixes the byte, reduces the rank and clears them
 //            (k_qt_narrow).  No host synchronisation between passes; after the last byte the prefix is the answer.
-// What this operator shares with uniq_kernels.hip (element load, pool memory, entry checks, the groups of the store's keys, the
-// key -> group table) is pair_store.h / group_table.h.
+// What this operator shares with uniq_kernels.hip (element load, entry checks, the groups of the store's keys, the key -> group table)
+// is pair_store.h / group_table.h; the store itself (PairStore: reserve, merge's append, export of the keys) is pair_store.h too, shared
+// with group_array_kernels.hip; pool memory, the numbered allocations and a call's temporaries are pair_pool.h.  Its own: the append
+// kernel, the value export, the row limit in front of the shared reserve.
 #include "chgpu_internal.h"
 
 #include "pair_store.h"
@@ -590,41 +592,12 @@ struct QtFinal
     PairMem lseg;                  // QtLarge[large]
 };
 
-struct chgpu_quantile : PairOp
+struct chgpu_quantile : PairStore
 {
-    u32 width = 0;
     int mode = 0;
-    u64 held = 0, cap = 0;
-    PairMem k_mem, v_mem, ctrl_mem;
+    PairMem ctrl_mem;
     QtFinal fin;
-    long long fail_alloc = 0, alloc_seq = 0; // test hook: allocation number fail_alloc of a call answers OOM
 };
-
-static void qt_begin_call(chgpu_quantile * d)
-{
-    d->alloc_seq = 0;
-    d->fail_alloc = chgpu_opt(d->ctx, "test_quantile_fail_alloc", 0);
-}
-
-static bool qt_refused(chgpu_quantile * d)
-{
-    d->alloc_seq += 1;
-    return d->fail_alloc && d->alloc_seq == d->fail_alloc;
-}
-
-static int qt_alloc(chgpu_quantile * d, size_t bytes, PairMem * m)
-{
-    if (qt_refused(d))
-        return chgpu_set_error(CHGPU_ERR_OOM, "quantile: allocation %lld refused (test_quantile_fail_alloc)", d->alloc_seq);
-    return chgpu_pool_alloc(d->ctx, bytes ? bytes : 256, &m->p, &m->cls);
-}
-
-static int qt_col_new(chgpu_quantile * d, int type, u64 rows, chgpu_col ** out)
-{
-    if (qt_refused(d))
-        return chgpu_set_error(CHGPU_ERR_OOM, "quantile: allocation %lld refused (test_quantile_fail_alloc)", d->alloc_seq);
-    return chgpu_col_new(d->ctx, type, rows, out);
-}
 
 static void qt_drop_final(chgpu_quantile * d)
 {
@@ -640,39 +613,13 @@ static void qt_drop_final(chgpu_quantile * d)
 
 static u32 qt_grid(chgpu_ctx * ctx, u64 items) { return chgpu_grid_for(ctx, items, QT_T, 8); }
 
-// room for `need` values: every allocation first, so that a failure leaves the store as it was; then what is held is copied
+// room for `need` values, or the row limit's answer
 static int qt_reserve(chgpu_quantile * d, u64 need)
 {
     if (need <= d->cap)
         return CHGPU_OK;
     CHGPU_REQUIRE(need < QT_MAX_VALUES, CHGPU_ERR_TOO_MANY_ROWS, "quantile: %llu values, fewer than %llu fit", (unsigned long long)need, (unsigned long long)QT_MAX_VALUES);
-    chgpu_ctx * ctx = d->ctx;
-    const bool keyed = d->key_type >= 0;
-    const u64 cap = qt_capacity_for(need);
-    PairMem k, v;
-    int rc = keyed ? qt_alloc(d, cap * 8, &k) : CHGPU_OK;
-    if (rc == CHGPU_OK)
-        rc = qt_alloc(d, cap * d->width, &v);
-    if (rc == CHGPU_OK && d->held)
-    {
-        hipError_t e = keyed ? hipMemcpyAsync(k.p, d->k_mem.p, d->held * 8, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(v.p, d->v_mem.p, d->held * d->width, hipMemcpyDeviceToDevice, ctx->stream);
-        if (e != hipSuccess)
-            rc = chgpu_set_error(CHGPU_ERR_DEVICE, "quantile: copying the store failed: %s", hipGetErrorString(e));
-    }
-    if (rc != CHGPU_OK)
-    {
-        pair_free_mem(ctx, k);
-        pair_free_mem(ctx, v);
-        return rc;
-    }
-    pair_free_mem(ctx, d->k_mem); // reuse is ordered behind the copies above (same stream)
-    pair_free_mem(ctx, d->v_mem);
-    d->k_mem = k;
-    d->v_mem = v;
-    d->cap = cap;
-    return CHGPU_OK;
+    return pair_store_reserve(QT_NAMES, *d, need);
 }
 
 extern "C" int chgpu_quantile_create(chgpu_ctx * ctx, int key_type, int value_type, chgpu_quantile ** out)
@@ -681,12 +628,8 @@ extern "C" int chgpu_quantile_create(chgpu_ctx * ctx, int key_type, int value_ty
     CHGPU_TRY(pair_check_create(QT_NAMES, key_type, value_type));
     ChgpuDeviceGuard guard(ctx);
     chgpu_quantile * d = new chgpu_quantile();
-    d->ctx = ctx;
-    d->key_type = key_type < 0 ? -1 : key_type;
-    d->value_type = value_type;
-    d->width = (u32)chgpu_type_size(value_type);
+    pair_store_init(*d, ctx, key_type, value_type, QT_NAMES.op, "test_quantile_fail_alloc");
     d->mode = chgpu_type_is_float(value_type) ? QT_MODE_FLOAT : chgpu_type_is_signed(value_type) ? QT_MODE_SIGNED : QT_MODE_UNSIGNED;
-    chgpu_ctx_retain(ctx);
     const int rc = chgpu_pool_alloc(ctx, 256, &d->ctrl_mem.p, &d->ctrl_mem.cls);
     if (rc != CHGPU_OK)
     {
@@ -703,8 +646,7 @@ extern "C" int chgpu_quantile_free(chgpu_quantile * d)
         return CHGPU_OK;
     ChgpuDeviceGuard guard(d->ctx);
     qt_drop_final(d);
-    pair_free_mem(d->ctx, d->k_mem);
-    pair_free_mem(d->ctx, d->v_mem);
+    pair_store_free(*d);
     pair_free_mem(d->ctx, d->ctrl_mem);
     chgpu_ctx * ctx = d->ctx;
     delete d;
@@ -720,7 +662,7 @@ extern "C" int chgpu_quantile_add_block(chgpu_quantile * d, const chgpu_col * ke
     const bool keyed = d->key_type >= 0;
     chgpu_ctx * ctx = d->ctx;
     ChgpuDeviceGuard guard(ctx);
-    qt_begin_call(d);
+    d->mem.begin_call();
     const u64 n = row_end - row_begin;
     QtAddPlan plan;
     plan.n = n;
@@ -763,36 +705,17 @@ extern "C" int chgpu_quantile_merge(chgpu_quantile * dst, const chgpu_quantile *
     CHGPU_TRY(pair_check_merge(QT_NAMES, *dst, *src));
     chgpu_ctx * ctx = dst->ctx;
     ChgpuDeviceGuard guard(ctx);
-    qt_begin_call(dst);
+    dst->mem.begin_call();
     const u64 n = src->held; // (dst == src doubles every value: a multiset union with itself)
     QtAddPlan plan;
     plan.what = "merge";
     plan.n = n;
     plan.held_before = plan.held = dst->held;
-    int rc = CHGPU_OK;
-    if (n)
+    const int rc = pair_store_append_store(QT_NAMES, *dst, *src, [&](u64 need) { return qt_reserve(dst, need); }, [] {});
+    if (rc == CHGPU_OK && n)
     {
-        if (src->ctx != ctx && hipStreamSynchronize(src->ctx->stream) != hipSuccess) // src's values were written on its own stream
-            rc = chgpu_set_error(CHGPU_ERR_DEVICE, "quantile: waiting for the source failed");
-        if (rc == CHGPU_OK)
-            rc = qt_reserve(dst, dst->held + n);
-        if (rc == CHGPU_OK)
-        {
-            const bool keyed = dst->key_type >= 0;
-            hipError_t e = keyed ? hipMemcpyAsync((u64 *)dst->k_mem.p + dst->held, src->k_mem.p, n * 8, hipMemcpyDeviceToDevice, ctx->stream) : hipSuccess;
-            if (e == hipSuccess)
-                e = hipMemcpyAsync((char *)dst->v_mem.p + dst->held * dst->width, src->v_mem.p, n * dst->width, hipMemcpyDeviceToDevice, ctx->stream);
-            if (e == hipSuccess && src->ctx != ctx)
-                e = hipStreamSynchronize(ctx->stream); // src may change once this returns
-            if (e != hipSuccess)
-                rc = chgpu_set_error(CHGPU_ERR_DEVICE, "quantile: copying the source's store failed: %s", hipGetErrorString(e));
-        }
-        if (rc == CHGPU_OK)
-        {
-            qt_drop_final(dst);
-            dst->held += n;
-            plan.entered = n;
-        }
+        qt_drop_final(dst);
+        plan.entered = n;
     }
     plan.held = dst->held;
     plan.rc = rc;
@@ -810,61 +733,16 @@ extern "C" int chgpu_quantile_size(chgpu_quantile * d, uint64_t * values)
 extern "C" int chgpu_quantile_export_pairs(chgpu_quantile * d, chgpu_col ** keys_out, chgpu_col ** values_out, uint64_t * rows)
 {
     CHGPU_REQUIRE(d && values_out && rows, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    const bool keyed = d->key_type >= 0;
-    CHGPU_REQUIRE(!keyed || keys_out, CHGPU_ERR_BAD_ARGUMENTS, "NULL keys_out");
     chgpu_ctx * ctx = d->ctx;
-    ChgpuDeviceGuard guard(ctx);
-    qt_begin_call(d);
-    chgpu_col * k = nullptr;
-    chgpu_col * v = nullptr;
-    int rc = keyed ? qt_col_new(d, d->key_type, d->held, &k) : CHGPU_OK;
-    if (rc == CHGPU_OK)
-        rc = qt_col_new(d, d->value_type, d->held, &v);
-    if (rc == CHGPU_OK && d->held)
-    {
-        const dim3 grid(qt_grid(ctx, d->held)), block(QT_T);
-        if (keyed)
-            pair_narrow(ctx, (const u64 *)d->k_mem.p, d->held, k);
+    return pair_store_export(QT_NAMES, *d, keys_out, values_out, rows, [&](chgpu_col * v) {
         dispatch_width(d->width, [&](auto tag) {
             typedef decltype(tag) T;
-            hipLaunchKernelGGL(k_qt_export_values<T>, grid, block, 0, ctx->stream, (const T *)d->v_mem.p, d->held, d->mode, (T *)v->data);
+            hipLaunchKernelGGL(k_qt_export_values<T>, dim3(qt_grid(ctx, d->held)), dim3(QT_T), 0, ctx->stream, (const T *)d->v_mem.p, d->held, d->mode, (T *)v->data);
         });
         ctx->counters[6] += 2;
-        rc = pair_launch_ok(QT_NAMES, "export");
-    }
-    if (rc != CHGPU_OK)
-    {
-        if (k) chgpu_col_free(k);
-        if (v) chgpu_col_free(v);
-        return rc;
-    }
-    if (keys_out)
-        *keys_out = k;
-    *values_out = v;
-    *rows = d->held;
-    return CHGPU_OK;
-}
-
-// temporaries of one call, freed when it ends (reuse of the memory is ordered on the stream)
-struct QtTemps
-{
-    chgpu_quantile * d;
-    std::vector<PairMem> mems;
-    explicit QtTemps(chgpu_quantile * d_) : d(d_) {}
-    ~QtTemps()
-    {
-        for (PairMem & m : mems)
-            pair_free_mem(d->ctx, m);
-    }
-    int alloc(size_t bytes, void ** out)
-    {
-        PairMem m;
-        CHGPU_TRY(qt_alloc(d, bytes, &m));
-        mems.push_back(m);
-        *out = m.p;
         return CHGPU_OK;
-    }
-};
+    });
+}
 
 // groups, segment offsets, the classes of the segments, the key table and the segment array of the store as it stands
 static int qt_build_final(chgpu_quantile * d)
@@ -873,7 +751,7 @@ static int qt_build_final(chgpu_quantile * d)
     const bool keyed = d->key_type >= 0;
     QtFinal & f = d->fin;
     f.values = d->held;
-    QtTemps tmp(d);
+    PairTemps tmp(d->mem);
     chgpu_col * counts = nullptr;
     if (keyed)
         CHGPU_TRY(pair_count_groups(ctx, d->k_mem.p, d->held, nullptr, &f.gkeys, &counts, &f.groups));
@@ -896,8 +774,8 @@ static int qt_build_final(chgpu_quantile * d)
     u64 * lidx = nullptr;
     u64 * uoff = nullptr;
     u64 * tot = nullptr;
-    CHGPU_TRY(qt_alloc(d, G * 4, &f.counts));
-    CHGPU_TRY(qt_alloc(d, (G + 1) * 8, &f.offsets));
+    CHGPU_TRY(d->mem.alloc(G * 4, &f.counts));
+    CHGPU_TRY(d->mem.alloc((G + 1) * 8, &f.offsets));
     CHGPU_TRY(tmp.alloc(G * 4, (void **)&flag));
     CHGPU_TRY(tmp.alloc(G * 4, (void **)&units));
     CHGPU_TRY(tmp.alloc(G * 8, (void **)&lidx));
@@ -924,7 +802,7 @@ static int qt_build_final(chgpu_quantile * d)
     f.small = G - f.large;
     if (f.large)
     {
-        CHGPU_TRY(qt_alloc(d, f.large * sizeof(QtLarge), &f.lseg));
+        CHGPU_TRY(d->mem.alloc(f.large * sizeof(QtLarge), &f.lseg));
         hipLaunchKernelGGL(k_qt_large_list, ggrid, block, 0, ctx->stream, c32, offsets, flag, lidx, uoff, G, (QtLarge *)f.lseg.p);
         ctx->counters[6] += 1;
         CHGPU_TRY(pair_launch_ok(QT_NAMES, "large list"));
@@ -932,8 +810,8 @@ static int qt_build_final(chgpu_quantile * d)
     if (!keyed)
         return CHGPU_OK; // one segment: the store's values
     f.cells_cap = gt_capacity_for(G);
-    CHGPU_TRY(qt_alloc(d, f.cells_cap * 4, &f.cells));
-    CHGPU_TRY(qt_alloc(d, d->held * d->width, &f.seg));
+    CHGPU_TRY(d->mem.alloc(f.cells_cap * 4, &f.cells));
+    CHGPU_TRY(d->mem.alloc(d->held * d->width, &f.seg));
     u32 * cursor = nullptr; // [G] cursors, then the count of values whose key found no group
     CHGPU_TRY(tmp.alloc((G + 1) * 4, (void **)&cursor));
     CHGPU_TRY(gt_fill(ctx, QT_NAMES.op, (const u64 *)f.gkeys->data, G, (u32 *)f.cells.p, f.cells_cap));
@@ -980,13 +858,13 @@ static int qt_select(chgpu_quantile * d, int kind, u32 n_levels, const double * 
     int cached = 0;
     CHGPU_TRY(qt_ensure_final(d, &cached));
     const QtFinal & f = d->fin;
-    QtTemps tmp(d);
+    PairTemps tmp(d->mem);
     QtLevels lv{};
     QtOut out{};
     for (u32 l = 0; l < n_levels; ++l)
     {
         lv.l[l] = levels[l];
-        CHGPU_TRY(qt_col_new(d, d->value_type, f.groups, &res[l]));
+        CHGPU_TRY(d->mem.col_new(d->value_type, f.groups, &res[l]));
         out.p[l] = res[l]->data;
     }
     const u32 bl = qt_level_batch(f.large, n_levels, (u64)chgpu_opt(ctx, "test_quantile_hist_budget", (long long)QT_HIST_BUDGET));
@@ -1065,7 +943,7 @@ static int qt_empty_cols(chgpu_quantile * d, u32 n_levels, u64 n, chgpu_col ** c
     QtOut out{};
     for (u32 l = 0; l < n_levels; ++l)
     {
-        CHGPU_TRY(qt_col_new(d, d->value_type, n, &cols[l]));
+        CHGPU_TRY(d->mem.col_new(d->value_type, n, &cols[l]));
         out.p[l] = cols[l]->data;
     }
     if (!n)
@@ -1090,7 +968,7 @@ extern "C" int chgpu_quantile_finalize(chgpu_quantile * d, int kind, uint32_t n_
     CHGPU_REQUIRE(code == CHGPU_OK, code, "quantile: %s", msg);
     chgpu_ctx * ctx = d->ctx;
     ChgpuDeviceGuard guard(ctx);
-    qt_begin_call(d);
+    d->mem.begin_call();
     chgpu_col * res[CHGPU_QUANTILE_MAX_LEVELS] = {nullptr};
     chgpu_col * k = nullptr;
     QtPlan plan;
@@ -1103,14 +981,14 @@ extern "C" int chgpu_quantile_finalize(chgpu_quantile * d, int kind, uint32_t n_
         rows = keyed ? 0 : 1;
         rc = qt_empty_cols(d, n_levels, rows, res);
         if (rc == CHGPU_OK && keyed)
-            rc = qt_col_new(d, d->key_type, 0, &k);
+            rc = d->mem.col_new(d->key_type, 0, &k);
     }
     else
     {
         rc = qt_select(d, kind, n_levels, levels, res, &plan);
         rows = d->fin.groups;
         if (rc == CHGPU_OK && keyed)
-            rc = qt_col_new(d, d->key_type, rows, &k);
+            rc = d->mem.col_new(d->key_type, rows, &k);
         if (rc == CHGPU_OK && keyed)
         {
             pair_narrow(ctx, (const u64 *)d->fin.gkeys->data, rows, k);
@@ -1143,7 +1021,7 @@ extern "C" int chgpu_quantile_for_keys(chgpu_quantile * d, int kind, uint32_t n_
     CHGPU_TRY(pair_check_device(QT_NAMES, *d, keys));
     chgpu_ctx * ctx = d->ctx;
     ChgpuDeviceGuard guard(ctx);
-    qt_begin_call(d);
+    d->mem.begin_call();
     chgpu_col * res[CHGPU_QUANTILE_MAX_LEVELS] = {nullptr};
     chgpu_col * per_group[CHGPU_QUANTILE_MAX_LEVELS] = {nullptr};
     QtPlan plan;
@@ -1158,7 +1036,7 @@ extern "C" int chgpu_quantile_for_keys(chgpu_quantile * d, int kind, uint32_t n_
         QtOut gres{}, out{};
         for (u32 l = 0; l < n_levels && rc == CHGPU_OK; ++l)
         {
-            rc = qt_col_new(d, d->value_type, keys->rows, &res[l]);
+            rc = d->mem.col_new(d->value_type, keys->rows, &res[l]);
             if (rc == CHGPU_OK)
             {
                 gres.p[l] = per_group[l]->data;

@@ -16,7 +16,9 @@
 //   output     k_win_out_rank (row_number / rank / dense_rank / count), k_win_out_sum (sum / avg), k_win_out_extremum (min / max),
 //              k_win_out_pick<W> (first_value / last_value / lagInFrame / leadInFrame): row i, its bounds, the scan array -> the result;
 //              the frame itself is win_frame_of (window_host.h), the code the host driver tests
+// The handle's pool memory and a call's temporaries are pair_pool.h (PairMem, PairAllocs without a refusal hook, PairTemps).
 #include "chgpu_internal.h"
+#include "pair_pool.h"
 #include "window_host.h"
 
 static constexpr u32 WIN_INF = 0xFFFFFFFFu;
@@ -668,52 +670,17 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_out_pick(int pick, chgpu_wi
 // ---------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------
-struct WinMem
-{
-    void * p = nullptr;
-    size_t cls = 0;
-};
-
 struct chgpu_window
 {
     chgpu_ctx * ctx = nullptr;
     u64 rows = 0, n_tiles = 0;
-    WinMem flags;     // u8[padded rows]
-    WinMem part;      // u32[WIN_P_KINDS * n_tiles], scanned, then u32 totals[2]
-    WinMem bounds[5]; // u32[padded rows] each: ps, pe, gs, ge, dense; built on first use
+    PairMem flags;     // u8[padded rows]
+    PairMem part;      // u32[WIN_P_KINDS * n_tiles], scanned, then u32 totals[2]
+    PairMem bounds[5]; // u32[padded rows] each: ps, pe, gs, ge, dense; built on first use
     WinLazy lazy;
     bool have_totals = false;
     u64 partitions = 0, peer_groups = 0;
-};
-
-static void win_free_mem(chgpu_ctx * ctx, WinMem & m)
-{
-    if (m.p)
-        chgpu_pool_free(ctx, m.p, m.cls);
-    m = WinMem{};
-}
-
-static int win_alloc(chgpu_ctx * ctx, size_t bytes, WinMem * m) { return chgpu_pool_alloc(ctx, bytes ? bytes : 256, &m->p, &m->cls); }
-
-// temporaries of one call, handed back when it ends (their reuse is ordered on the stream behind the kernels that read them)
-struct WinTemps
-{
-    chgpu_ctx * ctx;
-    std::vector<WinMem> mems;
-    explicit WinTemps(chgpu_ctx * c) : ctx(c) {}
-    ~WinTemps()
-    {
-        for (WinMem & m : mems)
-            win_free_mem(ctx, m);
-    }
-    int alloc(size_t bytes, void ** out)
-    {
-        WinMem m;
-        CHGPU_TRY(win_alloc(ctx, bytes, &m));
-        mems.push_back(m);
-        *out = m.p;
-        return CHGPU_OK;
-    }
+    PairAllocs mem; // (pair_pool.h; no refusal hook here)
 };
 
 static u32 * win_totals(const chgpu_window * w) { return (u32 *)w->part.p + WIN_P_KINDS * w->n_tiles; }
@@ -750,15 +717,15 @@ extern "C" int chgpu_window_create(chgpu_ctx * ctx, const chgpu_col * const * pa
     CHGPU_TRY(win_add_keys(ctx, order_cols, n_order, rows, "order", &keys));
     ChgpuDeviceGuard guard(ctx);
     chgpu_window * w = new chgpu_window();
-    w->ctx = ctx;
+    w->ctx = w->mem.ctx = ctx;
     w->rows = rows;
     w->n_tiles = win_tiles(rows);
     chgpu_ctx_retain(ctx);
     if (rows)
     {
-        int rc = win_alloc(ctx, win_padded_rows(rows), &w->flags);
+        int rc = w->mem.alloc(win_padded_rows(rows), &w->flags);
         if (rc == CHGPU_OK)
-            rc = win_alloc(ctx, (WIN_P_KINDS * w->n_tiles + 2) * sizeof(u32), &w->part);
+            rc = w->mem.alloc((WIN_P_KINDS * w->n_tiles + 2) * sizeof(u32), &w->part);
         if (rc != CHGPU_OK)
         {
             chgpu_window_free(w);
@@ -783,10 +750,10 @@ extern "C" int chgpu_window_free(chgpu_window * w)
     if (!w)
         return CHGPU_OK;
     ChgpuDeviceGuard guard(w->ctx);
-    win_free_mem(w->ctx, w->flags);
-    win_free_mem(w->ctx, w->part);
-    for (WinMem & m : w->bounds)
-        win_free_mem(w->ctx, m);
+    pair_free_mem(w->ctx, w->flags);
+    pair_free_mem(w->ctx, w->part);
+    for (PairMem & m : w->bounds)
+        pair_free_mem(w->ctx, m);
     chgpu_ctx * ctx = w->ctx;
     delete w;
     chgpu_ctx_release(ctx);
@@ -818,15 +785,15 @@ static int win_ensure_bounds(chgpu_window * w, u32 needs)
     if (!missing)
         return CHGPU_OK;
     chgpu_ctx * ctx = w->ctx;
-    WinMem fresh[5];
+    PairMem fresh[5];
     int rc = CHGPU_OK;
     for (u32 k = 0; k < 5 && rc == CHGPU_OK; ++k)
         if (missing & (1u << k))
-            rc = win_alloc(ctx, win_padded_rows(w->rows) * sizeof(u32), &fresh[k]);
+            rc = w->mem.alloc(win_padded_rows(w->rows) * sizeof(u32), &fresh[k]);
     if (rc != CHGPU_OK)
     {
-        for (WinMem & m : fresh)
-            win_free_mem(ctx, m);
+        for (PairMem & m : fresh)
+            pair_free_mem(ctx, m);
         return rc;
     }
     const u8 * flags = (const u8 *)w->flags.p;
@@ -898,7 +865,7 @@ extern "C" int chgpu_window_evaluate(chgpu_window * w, int function, const chgpu
         return CHGPU_OK;
     }
     // every allocation of the call before its first launch that writes: temporaries, then the lazy bounds, then the result
-    WinTemps tmp(ctx);
+    PairTemps tmp(w->mem);
     u64 * scan = nullptr;   // P[n + 1] or M[n]
     void * tiles = nullptr; // u64 / WinSeg per tile
     const bool is_sum = function == CHGPU_WIN_SUM || function == CHGPU_WIN_AVG;

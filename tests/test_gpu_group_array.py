@@ -263,6 +263,32 @@ def test_every_pass_is_stable_and_only_varying_bytes_are_passed(ch, ctx, capfd, 
         p.close()
 
 
+@pytest.mark.parametrize("extra", [0, 1])
+@pytest.mark.parametrize("size", [64, 512, GA_TILE])
+def test_run_heads_on_lane_zero_step_and_tile_boundaries(ch, ctx, capfd, size, extra):
+    # With groups of equal size the run heads of the sorted keys are the multiples of the size whatever order the keys sort into: lane 0
+    # of a 64-row step (64), a wave's first step (512), a tile's first row (GA_TILE).  One more row (a key of its own) opens a fourth
+    # tile of a single row.
+    rng = _rng(900 + size + extra)
+    groups = 3 * GA_TILE // size
+    n = groups * size + extra
+    ids = (rng.permutation(1 << 20)[:groups + 1] + 1).astype(np.uint32)
+    i = np.arange(n)
+    keys = np.where(i < groups * size, ids[i % groups], ids[groups])   # interleaved in arrival, contiguous once sorted
+    values = np.arange(n, dtype=np.uint64)
+    p = Pair(ch, ctx, np.uint32, np.uint64)
+    try:
+        p.add(capfd, keys, values)
+        plan = p.check(capfd)
+        assert plan["groups"] == groups + extra and plan["values"] == n
+        _, off, data = p.op.finalize()
+        assert _increasing_inside_every_array(off, data)
+        ask = np.concatenate([ids[::-1], np.array([0], dtype=np.uint32)])   # every group (the spare id too), then an absent key
+        assert p.check_for_keys(capfd, ask)["cached"] == 1
+    finally:
+        p.close()
+
+
 def test_one_mid_size_shape_with_three_varying_bytes(ch, ctx, capfd):
     rng = _rng(5)
     n, groups = 1_200_000, 300_000

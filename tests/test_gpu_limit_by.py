@@ -121,6 +121,27 @@ def test_equal_keys_straddle_waves_tiles_and_workgroups(pair, capfd, length, off
     q.feed(capfd, (i % 3).astype(np.uint16))
 
 
+@pytest.mark.parametrize("length,offset", [(2, 1), (3, 5)])
+@pytest.mark.parametrize("extra", [0, 1])
+@pytest.mark.parametrize("size", [64, 512, 2048])
+def test_rank_plan_segment_heads_on_lane_zero_step_and_record_tile_boundaries(pair, capfd, size, extra, length, offset):
+    # Every row of a fresh operator's first block is live, and the rank plan sorts the records by slot.  With groups of equal size the
+    # segment heads are the multiples of the size whatever order the slots sort into: lane 0 of a 64-record step (64), a wave's first
+    # step (512), a record tile's first record (2048).  One more row (a key of its own) opens a fourth tile of a single record.
+    rng = _rng(size + extra)
+    groups = 3 * 2048 // size
+    n = groups * size + extra
+    ids = (rng.permutation(1 << 20)[:groups + 1] + 1).astype(np.uint32)
+    i = np.arange(n)
+    contiguous = ids[i // size]
+    interleaved = np.where(i < groups * size, ids[i % groups], ids[groups])
+    for keys in (contiguous, interleaved):
+        p = pair(np.uint32, length, offset)
+        plan = p.feed(capfd, keys)
+        assert plan["plan"] == "rank" and plan["live"] == n and plan["passes"] >= 1
+        p.feed(capfd, keys[::-1].copy())                # the counters the first block left are carried into the ranks
+
+
 @pytest.mark.parametrize("dtype", [np.uint8, np.uint16, np.uint32, np.uint64])
 @pytest.mark.parametrize("begin,end_cut", [(1, 0), (3, 5), (2, 1), (T + 1, 3)])
 def test_unaligned_row_ranges_and_views(ch, ctx, pair, capfd, dtype, begin, end_cut):
