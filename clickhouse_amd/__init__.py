@@ -20,5 +20,6 @@ from .quantile import QuantileExact
 from .group_array import GroupArray
 from .limit_by import BlockKeys, Distinct, LimitBy, distinct_block, limit_by_block
 from .window import CURRENT_ROW, UNBOUNDED, Frame, Window, following, preceding
+from .merge_sorted import MergeSorting, is_sorted, merge_sorted_blocks, merge_sorted_permutation
 
 __all__ = [n for n in dir() if not n.startswith("_")]

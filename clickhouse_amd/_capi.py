@@ -35,6 +35,7 @@ STR_CONST_MAX = 256   # bytes of a string constant / LIKE pattern the kernels ca
  WIN_LEAD_IN_FRAME) = range(12)
 FRAME_ROWS, FRAME_RANGE = 0, 1
 BOUND_UNBOUNDED_PRECEDING, BOUND_OFFSET_PRECEDING, BOUND_CURRENT_ROW, BOUND_OFFSET_FOLLOWING, BOUND_UNBOUNDED_FOLLOWING = 0, 1, 2, 3, 4
+MERGE_CHECK_SORTED = 1   # chgpu_merge_sorted_permutation flags
 
 _vp, _i, _u32, _u64, _i64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_int64
 _pp = C.POINTER(C.c_void_p)
@@ -108,6 +109,8 @@ SIGNATURES = {
     "chgpu_sort_permutation": (_i, [_vp, _vp, _vp, _i, _i, _pp]),
     "chgpu_sort_permutation_limit": (_i, [_vp, _vp, _i, _i, _u64, _pp]),
     "chgpu_filter_to_indices": (_i, [_vp, _vp, _pp, _pu64]),
+    "chgpu_merge_sorted_permutation": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _u64, _u32, _pp]),
+    "chgpu_is_sorted": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _pu64]),
     "chgpu_weak_hash32": (_i, [_vp, _vp, _vp]),
     "chgpu_hash_to_selector": (_i, [_vp, _vp, _u32, _pp]),
     "chgpu_scatter": (_i, [_vp, _vp, _vp, _u32, _pp]),

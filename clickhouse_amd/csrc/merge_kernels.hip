@@ -1,0 +1,461 @@
+// merge_kernels.hip — the other half of ORDER BY: the stable merge of runs that are already sorted.  MergingSortedAlgorithm
+// (src/Processors/Merges/Algorithms/MergingSortedAlgorithm.cpp) over SortCursor (src/Core/SortCursor.h: column by column, ties by the
+// cursor's `order`), which is what MergeSortingTransform (src/Processors/Transforms/MergeSortingTransform.cpp) does with the chunks
+// PartialSortingTransform sorted and MergingSortedTransform with the streams; and isAlreadySorted (src/Interpreters/sortBlock.cpp).
+// The key columns are the runs glued end to end; the result is the permutation of concatenated row numbers, bit-equal to what the
+// stable sort of the concatenation gives (sort_kernels.hip), because both compare the SortKey words of sort_key.h.
+//   k_merge_keys       first key column -> (order-preserving u64 word, u32 row number), every run cut to the limit
+//   k_merge_split      per round, ONE launch: for every tile edge of every pair, the merge-path crossing of its diagonal (binary search
+//                      over the pair's two runs in HBM)
+//   k_merge_tiles      per round, ONE launch: a workgroup stages its tile's two input pieces in LDS, every thread finds its own diagonal
+//                      there and merges MRG_ITEMS consecutive outputs, the tile goes out coalesced
+//   k_merge_perm       the last round's row numbers widened to the UInt64 permutation
+//   k_merge_is_sorted  adjacent rows compared under the same order, never across a run boundary; per-tile minimum of the violating row
+//   k_merge_min        one workgroup folds the tile minima: the LOWEST violating row, the same in every run
+// The comparator reads the words first; on equal words (and n_keys > 1) the remaining columns through the row numbers; all equal: the
+// left run's element first (merge_host.h keeps the invariant).  No atomics anywhere.
+// Algorithmic bytes per row: key build sizeof(T) + 12; a round 2 x 12; the permutation 4 + 8.  is_sorted: the key columns once.
+#include "chgpu_internal.h"
+#include "merge_host.h"
+#include "pair_pool.h"
+#include "sort_key.h"
+
+struct MergeKeys
+{
+    const void * data[MRG_MAX_KEYS];
+    i32 type[MRG_MAX_KEYS];
+    i32 desc[MRG_MAX_KEYS];
+    i32 hint[MRG_MAX_KEYS];
+    u32 n;
+};
+
+template <typename T>
+__device__ __forceinline__ u64 mrg_key_of(const void * data, u64 row, int desc, int hint)
+{
+    typedef typename SortKey<T>::K K;
+    const K k = SortKey<T>::key(((const T *)data)[row], hint);
+    return (u64)(desc ? (K)~k : k); // the complement inside the key's width, as k_sort_keys takes it
+}
+
+// column j of `keys` at `row` as a u64 word that orders like the column does under its description
+__device__ __forceinline__ u64 mrg_key(const MergeKeys & keys, u32 j, u64 row)
+{
+    const void * d = keys.data[j];
+    const int desc = keys.desc[j], hint = keys.hint[j];
+    switch (keys.type[j])
+    {
+        case CHGPU_I64: return mrg_key_of<i64>(d, row, desc, hint);
+        case CHGPU_U64: return mrg_key_of<u64>(d, row, desc, hint);
+        case CHGPU_I32: return mrg_key_of<i32>(d, row, desc, hint);
+        case CHGPU_U32: return mrg_key_of<u32>(d, row, desc, hint);
+        case CHGPU_I16: return mrg_key_of<i16>(d, row, desc, hint);
+        case CHGPU_U16: return mrg_key_of<u16>(d, row, desc, hint);
+        case CHGPU_I8: return mrg_key_of<i8>(d, row, desc, hint);
+        case CHGPU_U8: return mrg_key_of<u8>(d, row, desc, hint);
+        case CHGPU_F64: return mrg_key_of<double>(d, row, desc, hint);
+        default: return mrg_key_of<float>(d, row, desc, hint);
+    }
+}
+
+// Does (wb, rb) order STRICTLY before (wa, ra)?  Equal on every column answers false: the caller then takes the left run's element.
+__device__ __forceinline__ bool mrg_before(const MergeKeys & keys, u64 wb, u32 rb, u64 wa, u32 ra)
+{
+    if (wb != wa)
+        return wb < wa;
+    for (u32 j = 1; j < keys.n; ++j)
+    {
+        const u64 x = mrg_key(keys, j, rb), y = mrg_key(keys, j, ra);
+        if (x != y)
+            return x < y;
+    }
+    return false;
+}
+
+// cut_off[n_runs + 1]: where each (cut) run starts in the arrays; src_off[n_runs]: its first row in the columns.  n_runs == 0: nothing
+// was cut, entry i is row i.
+__global__ __launch_bounds__(256) void k_merge_keys(MergeKeys keys, const u32 * __restrict__ cut_off, const u32 * __restrict__ src_off, u32 n_runs, u32 n,
+                                                    u64 * __restrict__ words, u32 * __restrict__ rows)
+{
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
+    {
+        u32 src = (u32)i;
+        if (n_runs)
+        {
+            u32 lo = 0, hi = n_runs; // cut_off[lo] <= i < cut_off[hi]
+            while (hi - lo > 1)
+            {
+                const u32 mid = lo + (hi - lo) / 2;
+                if (cut_off[mid] <= (u32)i)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            src = src_off[lo] + ((u32)i - cut_off[lo]);
+        }
+        words[i] = mrg_key(keys, 0, src);
+        rows[i] = src;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_merge_split(MergeKeys keys, const MergePair * __restrict__ pairs, u32 n_pairs, u32 n_splits, const u64 * __restrict__ words,
+                                                     const u32 * __restrict__ rows, u32 * __restrict__ splits)
+{
+    const u32 s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= n_splits)
+        return;
+    const MergePair p = pairs[merge_pair_of<&MergePair::split_begin>(pairs, n_pairs, s)];
+    const u64 edge = (u64)(s - p.split_begin) * MRG_TILE;
+    const u32 diag = edge < p.out_len ? (u32)edge : p.out_len;
+    const u64 * wa = words + p.a_begin, * wb = words + p.b_begin;
+    const u32 * ra = rows + p.a_begin, * rb = rows + p.b_begin;
+    splits[s] = merge_path(diag, p.a_len, p.b_len, [&](u32 bi, u32 ai) { return mrg_before(keys, wb[bi], rb[bi], wa[ai], ra[ai]); });
+}
+
+__global__ __launch_bounds__(MRG_THREADS) void k_merge_tiles(MergeKeys keys, const MergePair * __restrict__ pairs, u32 n_pairs, const u32 * __restrict__ splits,
+                                                             const u64 * __restrict__ words_in, const u32 * __restrict__ rows_in, u64 * __restrict__ words_out,
+                                                             u32 * __restrict__ rows_out)
+{
+    __shared__ u64 sw[MRG_TILE];
+    __shared__ u32 sr[MRG_TILE];
+    const u32 tid = threadIdx.x;
+    const MergePair p = pairs[merge_pair_of<&MergePair::tile_begin>(pairs, n_pairs, blockIdx.x)];
+    const u32 k = blockIdx.x - p.tile_begin;
+    const u32 d0 = k * MRG_TILE; // < out_len: the pair has this tile
+    const u32 n = p.out_len - d0 < MRG_TILE ? p.out_len - d0 : MRG_TILE;
+    const u32 a0 = splits[p.split_begin + k];
+    u32 a1 = splits[p.split_begin + k + 1];
+    // Sorted runs give a0 <= a1 <= a0 + n.  Runs that are not sorted (the caller's error without CHGPU_MERGE_CHECK_SORTED) may not: the
+    // order is then unspecified, but every index stays inside the pair
+    a1 = a1 < a0 ? a0 : a1 - a0 > n ? a0 + n : a1;
+    const u32 b0 = d0 - a0;
+    const u32 na = a1 - a0, nb = n - na;
+    for (u32 e = tid; e < n; e += MRG_THREADS)
+    {
+        const u32 src = e < na ? p.a_begin + a0 + e : p.b_begin + b0 + (e - na);
+        sw[e] = words_in[src];
+        sr[e] = rows_in[src];
+    }
+    __syncthreads();
+    const u32 d = tid * MRG_ITEMS < n ? tid * MRG_ITEMS : n;
+    const u32 count = n - d < MRG_ITEMS ? n - d : MRG_ITEMS;
+    const u64 * la = sw, * lb = sw + na;
+    const u32 * lra = sr, * lrb = sr + na;
+    u32 ai = merge_path(d, na, nb, [&](u32 bi, u32 ai_) { return mrg_before(keys, lb[bi], lrb[bi], la[ai_], lra[ai_]); });
+    u32 bi = d - ai;
+    u64 ow[MRG_ITEMS];
+    u32 orow[MRG_ITEMS];
+#pragma unroll
+    for (u32 i = 0; i < MRG_ITEMS; ++i)
+    {
+        if (i < count)
+        {
+            // all equal: the left run's element goes first (the invariant of merge_host.h)
+            const bool take_b = bi < nb && (ai >= na || mrg_before(keys, lb[bi], lrb[bi], la[ai], lra[ai]));
+            ow[i] = take_b ? lb[bi] : la[ai];
+            orow[i] = take_b ? lrb[bi] : lra[ai];
+            bi += take_b ? 1 : 0;
+            ai += take_b ? 0 : 1;
+        }
+    }
+    __syncthreads(); // every thread has read its inputs: the tile's LDS now takes the outputs
+#pragma unroll
+    for (u32 i = 0; i < MRG_ITEMS; ++i)
+        if (i < count)
+        {
+            sw[d + i] = ow[i];
+            sr[d + i] = orow[i];
+        }
+    __syncthreads();
+    const u32 out = p.out_begin + d0;
+    for (u32 e = tid; e < n; e += MRG_THREADS)
+    {
+        words_out[out + e] = sw[e];
+        rows_out[out + e] = sr[e];
+    }
+}
+
+// rows == NULL: the identity
+__global__ __launch_bounds__(256) void k_merge_perm(const u32 * __restrict__ rows, u64 n, u64 * __restrict__ perm)
+{
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
+        perm[i] = rows ? rows[i] : i;
+}
+
+__device__ __forceinline__ u64 mrg_block_min(u64 v, u64 * lds /* MRG_THREADS / WAVE */)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1)
+    {
+        const u64 o = shfl_down_u64(v, d);
+        v = o < v ? o : v;
+    }
+    if ((threadIdx.x & 63) == 0)
+        lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    u64 m = lds[0];
+    for (u32 w = 1; w < MRG_THREADS / WAVE; ++w)
+        m = lds[w] < m ? lds[w] : m;
+    __syncthreads();
+    return m;
+}
+
+// run_off[n_runs + 1]; partial[blockIdx.x] = the lowest row i of this tile that is no run's first row and orders strictly before
+// row i - 1, or ~0
+__global__ __launch_bounds__(MRG_THREADS) void k_merge_is_sorted(MergeKeys keys, const u32 * __restrict__ run_off, u32 n_runs, u32 n, u64 * __restrict__ partial)
+{
+    __shared__ u64 lds[MRG_THREADS / WAVE];
+    // a thread's rows are MRG_THREADS apart, so that a wave reads consecutive rows
+    const u64 first = (u64)blockIdx.x * MRG_TILE + threadIdx.x;
+    u64 found = ~0ull;
+    if (first < n)
+    {
+        u32 lo = 0, hi = n_runs + 1; // the first offset >= first (run_off[n_runs] == n > first: it exists)
+        while (lo < hi)
+        {
+            const u32 mid = lo + (hi - lo) / 2;
+            if (run_off[mid] < (u32)first)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        u32 pos = lo;
+        for (u32 t = 0; t < MRG_ITEMS && found == ~0ull; ++t)
+        {
+            const u64 i = first + (u64)t * MRG_THREADS;
+            if (i >= n)
+                break;
+            while (pos <= n_runs && run_off[pos] < (u32)i)
+                pos += 1;
+            if (pos <= n_runs && run_off[pos] == (u32)i)
+                continue; // the first row of a run: nothing before it to compare with
+            for (u32 j = 0; j < keys.n; ++j)
+            {
+                const u64 x = mrg_key(keys, j, i), y = mrg_key(keys, j, i - 1);
+                if (x != y)
+                {
+                    if (x < y)
+                        found = i;
+                    break;
+                }
+            }
+        }
+    }
+    const u64 m = mrg_block_min(found, lds);
+    if (threadIdx.x == 0)
+        partial[blockIdx.x] = m;
+}
+
+__global__ __launch_bounds__(MRG_THREADS) void k_merge_min(const u64 * __restrict__ partial, u32 n, u64 * __restrict__ out)
+{
+    __shared__ u64 lds[MRG_THREADS / WAVE];
+    u64 v = ~0ull;
+    for (u32 i = threadIdx.x; i < n; i += MRG_THREADS)
+        v = partial[i] < v ? partial[i] : v;
+    const u64 m = mrg_block_min(v, lds);
+    if (threadIdx.x == 0)
+        out[0] = m;
+}
+
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+static int merge_validate(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, u32 n_keys,
+                          const uint64_t * run_offsets, u32 n_runs, MergeKeys * keys, u64 * rows)
+{
+    CHGPU_REQUIRE(ctx && key_cols && descending && nan_direction_hint && run_offsets, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    CHGPU_REQUIRE(n_keys >= 1 && n_keys <= MRG_MAX_KEYS, CHGPU_ERR_BAD_ARGUMENTS, "%u key columns: a sort description has 1 to %u", n_keys, MRG_MAX_KEYS);
+    const char * msg = nullptr;
+    const int rc = merge_check_offsets(run_offsets, n_runs, rows, &msg);
+    CHGPU_REQUIRE(rc == CHGPU_OK, rc, "%s", msg);
+    *keys = MergeKeys{};
+    keys->n = n_keys;
+    for (u32 j = 0; j < n_keys; ++j)
+    {
+        CHGPU_REQUIRE(key_cols[j], CHGPU_ERR_BAD_ARGUMENTS, "key column %u is NULL", j);
+        CHGPU_REQUIRE(chgpu_type_size(key_cols[j]->type), CHGPU_ERR_BAD_ARGUMENTS, "key column %u has the unknown type %d", j, key_cols[j]->type);
+        CHGPU_REQUIRE(key_cols[j]->rows == *rows, CHGPU_ERR_SIZES_MISMATCH, "key column %u has %llu rows, the run offsets end at %llu", j,
+                      (unsigned long long)key_cols[j]->rows, (unsigned long long)*rows);
+        keys->data[j] = key_cols[j]->data;
+        keys->type[j] = key_cols[j]->type;
+        keys->desc[j] = descending[j] ? 1 : 0;
+        keys->hint[j] = nan_direction_hint[j];
+    }
+    return CHGPU_OK;
+}
+
+// u32 host values into pool memory of the call (the host vector is consumed before hipMemcpyAsync returns: it is pageable)
+static int merge_upload(chgpu_ctx * ctx, PairTemps & tmp, const void * host, size_t bytes, void ** dev)
+{
+    CHGPU_TRY(tmp.alloc(bytes, dev));
+    if (bytes)
+        CHGPU_HIP(hipMemcpyAsync(*dev, host, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return CHGPU_OK;
+}
+
+// *first_unsorted_row: ~0, or the lowest row that orders before its predecessor inside one run.  rows >= 1.
+static int merge_is_sorted(chgpu_ctx * ctx, const MergeKeys & keys, const uint64_t * run_offsets, u32 n_runs, u64 rows, u64 * first_unsorted_row)
+{
+    PairAllocs mem;
+    mem.ctx = ctx, mem.op = "is_sorted";
+    mem.begin_call();
+    PairTemps tmp(mem);
+    std::vector<u32> off(n_runs + 1);
+    for (u32 r = 0; r <= n_runs; ++r)
+        off[r] = (u32)run_offsets[r];
+    void * off_dev = nullptr, * partial = nullptr;
+    CHGPU_TRY(merge_upload(ctx, tmp, off.data(), off.size() * sizeof(u32), &off_dev));
+    const u32 tiles = merge_tiles((u32)rows);
+    CHGPU_TRY(tmp.alloc(((size_t)tiles + 1) * sizeof(u64), &partial));
+    hipLaunchKernelGGL(k_merge_is_sorted, dim3(tiles), dim3(MRG_THREADS), 0, ctx->stream, keys, (const u32 *)off_dev, n_runs, (u32)rows, (u64 *)partial);
+    hipLaunchKernelGGL(k_merge_min, dim3(1), dim3(MRG_THREADS), 0, ctx->stream, (const u64 *)partial, tiles, (u64 *)partial + tiles);
+    ctx->counters[6] += 2;
+    return chgpu_read_back(ctx, (const u64 *)partial + tiles, first_unsorted_row, sizeof(u64));
+}
+
+extern "C" int chgpu_is_sorted(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, uint32_t n_keys,
+                               const uint64_t * run_offsets, uint32_t n_runs, uint64_t * first_unsorted_row)
+{
+    ChgpuDeviceGuard _dev_guard(ctx);
+    CHGPU_REQUIRE(first_unsorted_row, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    MergeKeys keys;
+    u64 rows = 0;
+    CHGPU_TRY(merge_validate(ctx, key_cols, descending, nan_direction_hint, n_keys, run_offsets, n_runs, &keys, &rows));
+    *first_unsorted_row = ~0ull;
+    if (rows < 2)
+        return CHGPU_OK;
+    return merge_is_sorted(ctx, keys, run_offsets, n_runs, rows, first_unsorted_row);
+}
+
+// the merge tree over runs cut to `lens`; *perm_out: n_out entries
+static int merge_tree(chgpu_ctx * ctx, const MergeKeys & keys, const uint64_t * run_offsets, u32 n_runs, u64 rows, const std::vector<u32> & lens, u64 cut_rows,
+                      u64 limit, u64 n_out, chgpu_col ** perm_out)
+{
+    PairAllocs mem;
+    mem.ctx = ctx, mem.op = "merge_sorted";
+    mem.begin_call();
+    PairTemps tmp(mem);
+    const std::vector<MergeRound> rounds = merge_rounds(lens, limit);
+    // one table for the whole call: the key build's run map (only when a run was cut), then every round's pairs
+    std::vector<u32> map;
+    if (cut_rows != rows)
+    {
+        map.resize(2 * (size_t)n_runs + 1);
+        u32 pos = 0;
+        for (u32 r = 0; r < n_runs; ++r)
+        {
+            map[r] = pos;
+            map[n_runs + 1 + r] = (u32)run_offsets[r];
+            pos += lens[r];
+        }
+        map[n_runs] = pos;
+    }
+    std::vector<MergePair> pairs;
+    u32 max_splits = 0;
+    for (const MergeRound & rd : rounds)
+    {
+        pairs.insert(pairs.end(), rd.pairs.begin(), rd.pairs.end());
+        max_splits = rd.n_splits > max_splits ? rd.n_splits : max_splits;
+    }
+    void * map_dev = nullptr, * pairs_dev = nullptr, * splits = nullptr, * words[2] = {nullptr, nullptr}, * rws[2] = {nullptr, nullptr};
+    CHGPU_TRY(merge_upload(ctx, tmp, map.data(), map.size() * sizeof(u32), &map_dev));
+    CHGPU_TRY(merge_upload(ctx, tmp, pairs.data(), pairs.size() * sizeof(MergePair), &pairs_dev));
+    CHGPU_TRY(tmp.alloc((size_t)max_splits * sizeof(u32), &splits));
+    for (int b = 0; b < 2; ++b)
+    {
+        CHGPU_TRY(tmp.alloc(cut_rows * sizeof(u64), &words[b]));
+        CHGPU_TRY(tmp.alloc(cut_rows * sizeof(u32), &rws[b]));
+    }
+    chgpu_col * perm = nullptr;
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, n_out, &perm));
+    const u32 n_map = map.empty() ? 0 : n_runs;
+    hipLaunchKernelGGL(k_merge_keys, dim3(chgpu_grid_for(ctx, cut_rows, 256, 8)), dim3(256), 0, ctx->stream, keys, (const u32 *)map_dev,
+                       (const u32 *)map_dev + n_runs + 1, n_map, (u32)cut_rows, (u64 *)words[0], (u32 *)rws[0]);
+    ctx->counters[6] += 1;
+    int cur = 0;
+    const MergePair * round_pairs = (const MergePair *)pairs_dev;
+    for (const MergeRound & rd : rounds)
+    {
+        const u32 n_pairs = (u32)rd.pairs.size();
+        if (rd.n_tiles)
+        {
+            hipLaunchKernelGGL(k_merge_split, dim3((rd.n_splits + 255) / 256), dim3(256), 0, ctx->stream, keys, round_pairs, n_pairs, rd.n_splits,
+                               (const u64 *)words[cur], (const u32 *)rws[cur], (u32 *)splits);
+            hipLaunchKernelGGL(k_merge_tiles, dim3(rd.n_tiles), dim3(MRG_THREADS), 0, ctx->stream, keys, round_pairs, n_pairs, (const u32 *)splits,
+                               (const u64 *)words[cur], (const u32 *)rws[cur], (u64 *)words[cur ^ 1], (u32 *)rws[cur ^ 1]);
+            ctx->counters[6] += 2;
+        }
+        round_pairs += n_pairs;
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL(k_merge_perm, dim3(chgpu_grid_for(ctx, n_out, 256, 8)), dim3(256), 0, ctx->stream, (const u32 *)rws[cur], n_out, (u64 *)perm->data);
+    ctx->counters[6] += 1;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess)
+    {
+        chgpu_col_free(perm);
+        return chgpu_set_error(CHGPU_ERR_DEVICE, "merge_sorted: %s", hipGetErrorString(e));
+    }
+    *perm_out = perm;
+    return CHGPU_OK;
+}
+
+// the other plan: the stable radix sort of the concatenation, from the last key column to the first
+static int merge_by_sort(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const MergeKeys & keys, u64 n_out, chgpu_col ** perm_out)
+{
+    chgpu_col * perm = nullptr;
+    for (u32 j = keys.n; j-- > 0;)
+    {
+        chgpu_col * next = nullptr;
+        const int rc = chgpu_sort_permutation(ctx, key_cols[j], perm, keys.desc[j], keys.hint[j], &next);
+        if (perm)
+            chgpu_col_free(perm);
+        if (rc != CHGPU_OK)
+            return rc;
+        perm = next;
+    }
+    perm->rows = n_out; // IColumn::Permutation is simply cut (the buffer keeps its size class)
+    *perm_out = perm;
+    return CHGPU_OK;
+}
+
+extern "C" int chgpu_merge_sorted_permutation(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint,
+                                              uint32_t n_keys, const uint64_t * run_offsets, uint32_t n_runs, uint64_t limit, uint32_t flags, chgpu_col ** perm_out_u64)
+{
+    ChgpuDeviceGuard _dev_guard(ctx);
+    CHGPU_REQUIRE(perm_out_u64, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    MergeKeys keys;
+    u64 rows = 0;
+    CHGPU_TRY(merge_validate(ctx, key_cols, descending, nan_direction_hint, n_keys, run_offsets, n_runs, &keys, &rows));
+    CHGPU_REQUIRE(!(flags & ~(u32)CHGPU_MERGE_CHECK_SORTED), CHGPU_ERR_BAD_ARGUMENTS, "unknown flag bits 0x%x", flags & ~(u32)CHGPU_MERGE_CHECK_SORTED);
+    if ((flags & CHGPU_MERGE_CHECK_SORTED) && rows >= 2)
+    {
+        u64 bad = ~0ull;
+        CHGPU_TRY(merge_is_sorted(ctx, keys, run_offsets, n_runs, rows, &bad));
+        CHGPU_REQUIRE(bad == ~0ull, CHGPU_ERR_BAD_ARGUMENTS, "a run is not sorted: row %llu orders before row %llu", (unsigned long long)bad,
+                      (unsigned long long)(bad - 1));
+    }
+    const u64 n_out = merge_cut(rows, limit);
+    if (n_out == 0 || n_runs == 1)
+    {
+        // nothing to merge: empty, or the identity cut to the limit
+        chgpu_col * perm = nullptr;
+        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, n_out, &perm));
+        if (n_out)
+        {
+            hipLaunchKernelGGL(k_merge_perm, dim3(chgpu_grid_for(ctx, n_out, 256, 8)), dim3(256), 0, ctx->stream, (const u32 *)nullptr, n_out, (u64 *)perm->data);
+            ctx->counters[6] += 1;
+        }
+        *perm_out_u64 = perm;
+        return CHGPU_OK;
+    }
+    const std::vector<u32> lens = merge_initial_runs(run_offsets, n_runs, limit);
+    u64 cut_rows = 0;
+    u32 key_sizes[MRG_MAX_KEYS];
+    for (u32 len : lens)
+        cut_rows += len;
+    for (u32 j = 0; j < n_keys; ++j)
+        key_sizes[j] = (u32)chgpu_type_size(keys.type[j]);
+    if (merge_plan(key_sizes, n_keys, rows, cut_rows, n_runs) == MERGE_PLAN_SORT)
+        return merge_by_sort(ctx, key_cols, keys, n_out, perm_out_u64);
+    return merge_tree(ctx, keys, run_offsets, n_runs, rows, lens, cut_rows, limit, n_out, perm_out_u64);
+}

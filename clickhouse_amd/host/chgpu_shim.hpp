@@ -16,6 +16,7 @@
 //   ColumnLowCardinality + low_cardinality_key* methods   src/Columns/ColumnLowCardinality.h:27-69, ColumnsHashing.h:82-260   chgpu::ColumnLowCardinality, LowCardinalityDictionary
 //   ColumnString as a key       src/Columns/ColumnString.h:40-49, ColumnUnique.h:520-620     chgpu::ColumnString::dictionaryEncode
 //   sortBlock / SortDescription src/Interpreters/sortBlock.cpp:240-330, Core/SortDescription.h   chgpu::sortBlock
+//   MergingSortedTransform / MergeSortingTransform   src/Processors/Merges/MergingSortedTransform.h, Transforms/MergeSortingTransform.cpp   chgpu::GpuMergingSortedTransform, GpuMergeSortingTransform
 //   CompressedReadBuffer        src/Compression/CompressedReadBufferBase.cpp:175-222         chgpu::readCompressedColumn
 //   IAggregateFunction          src/AggregateFunctions/IAggregateFunction.h:55-399      chgpu::AggregateDescription (closed POD set)
 //   Aggregator                  src/Interpreters/Aggregator.h:179-265          chgpu::GpuAggregator
@@ -2508,6 +2509,105 @@ private:
     std::vector<WindowFunctionDescription> functions;
     std::vector<Chunk> chunks;
     uint64_t partitions = 0, peer_groups = 0;
+};
+
+/// The merge of sorted runs of one Block layout: the runs' columns glued (chgpu_col_concat), merged by the description
+/// (chgpu_merge_sorted_permutation: MergingSortedAlgorithm over SortCursor) and every column permuted.  check_sorted: an unsorted run
+/// throws BAD_ARGUMENTS instead of giving an unspecified order.
+inline Chunk mergeSortedChunks(const ContextPtr & ctx, std::vector<Chunk> & runs, const SortDescription & description, uint64_t limit, bool check_sorted)
+{
+    Chunk out;
+    if (runs.empty() || description.empty())
+        return out;
+    const size_t n_cols = runs[0].columns.size();
+    std::vector<uint64_t> offsets{0};
+    for (auto & run : runs)
+        offsets.push_back(offsets.back() + run.num_rows);
+    for (size_t c = 0; c < n_cols; ++c)
+    {
+        std::vector<const chgpu_col *> parts;
+        for (auto & run : runs)
+            parts.push_back(run.columns.at(c)->handle());
+        chgpu_col * cat = nullptr;
+        check(chgpu_col_concat(ctx->get(), static_cast<uint32_t>(parts.size()), parts.data(), &cat));
+        out.columns.push_back(std::make_shared<ColumnVector>(ctx, cat));
+    }
+    std::vector<const chgpu_col *> keys;
+    std::vector<int32_t> descending, hints;
+    for (const auto & d : description)
+    {
+        keys.push_back(out.columns.at(d.column_number)->handle());
+        descending.push_back(d.direction < 0);
+        hints.push_back(d.nulls_direction);
+    }
+    chgpu_col * perm = nullptr;
+    check(chgpu_merge_sorted_permutation(ctx->get(), keys.data(), descending.data(), hints.data(), static_cast<uint32_t>(keys.size()), offsets.data(),
+                                         static_cast<uint32_t>(runs.size()), limit, check_sorted ? CHGPU_MERGE_CHECK_SORTED : 0, &perm));
+    ColumnVector permutation(ctx, perm);
+    for (auto & col : out.columns)
+        col = col->index(permutation, 0);
+    out.num_rows = permutation.size();
+    runs.clear();
+    return out;
+}
+
+/// MergingSortedTransform (src/Processors/Merges/MergingSortedTransform.h): K inputs of sorted chunks, a SortDescription and a limit.
+/// The chunks of one input follow each other in its order, so each is a run of its own and the runs are numbered input by input: rows
+/// equal on every key come out by input, then by arrival (SortCursor's tie on `order`).  All inputs are read before the merge.
+class GpuMergingSortedTransform
+{
+public:
+    GpuMergingSortedTransform(ContextPtr ctx_, size_t num_inputs, SortDescription description_, uint64_t limit_ = 0)
+        : ctx(std::move(ctx_)), description(std::move(description_)), limit(limit_), inputs(num_inputs) {}
+
+    void consume(size_t input, Chunk chunk)
+    {
+        if (chunk.num_rows)
+            inputs.at(input).push_back(std::move(chunk));
+    }
+
+    Chunk finish()
+    {
+        std::vector<Chunk> runs;
+        for (auto & in : inputs)
+        {
+            for (auto & chunk : in)
+                runs.push_back(std::move(chunk));
+            in.clear();
+        }
+        return mergeSortedChunks(ctx, runs, description, limit, true); // the inputs come from outside: an unsorted one throws
+    }
+
+private:
+    ContextPtr ctx;
+    SortDescription description;
+    uint64_t limit;
+    std::vector<std::vector<Chunk>> inputs;
+};
+
+/// MergeSortingTransform (src/Processors/Transforms/MergeSortingTransform.cpp) without the spill: consume() sorts a chunk as it arrives
+/// (sortBlock, cut to the limit: PartialSortingTransform) and keeps it; generate() merges the sorted chunks.
+class GpuMergeSortingTransform
+{
+public:
+    GpuMergeSortingTransform(ContextPtr ctx_, SortDescription description_, uint64_t limit_ = 0)
+        : ctx(std::move(ctx_)), description(std::move(description_)), limit(limit_) {}
+
+    void consume(Chunk chunk)
+    {
+        if (!chunk.num_rows)
+            return;
+        sortBlock(chunk, description, limit);
+        chunks.push_back(std::move(chunk));
+    }
+
+    Chunk generate() { return mergeSortedChunks(ctx, chunks, description, limit, false); }
+
+private:
+    ContextPtr ctx;
+    SortDescription description;
+    uint64_t limit;
+    std::vector<Chunk> chunks;
 };
 
 /// CompressedReadBuffer + SerializationNumber::deserializeBinaryBulk for one numeric column file (MergeTree `<column>.bin`): the

@@ -420,6 +420,34 @@ int chgpu_sort_permutation_limit(chgpu_ctx * ctx, const chgpu_col * col, int des
 /* filterToIndices (src/Columns/ColumnsCommon.cpp:384-470): row numbers whose filter byte is non-zero, ascending */
 int chgpu_filter_to_indices(chgpu_ctx * ctx, const chgpu_col * filter_u8, chgpu_col ** indexes_u64, uint64_t * rows_out);
 
+/* Ordered output, the other half: the stable merge of runs that are ALREADY sorted -- MergingSortedAlgorithm
+   (src/Processors/Merges/Algorithms/MergingSortedAlgorithm.cpp) over SortCursor (src/Core/SortCursor.h), which is what
+   MergeSortingTransform (src/Processors/Transforms/MergeSortingTransform.cpp) does with its sorted chunks, MergingSortedTransform with
+   sorted streams and the initiator of a Distributed ORDER BY with the shards' results.
+   key_cols[n_keys] (1 to 8, most significant first, any of the ten numeric types) are the runs glued end to end, as chgpu_col_concat
+   leaves them; run r is the rows [run_offsets[r], run_offsets[r + 1]) (run_offsets: HOST, n_runs + 1 cumulative entries,
+   run_offsets[0] = 0; a run may be empty).  The result is the permutation P of concatenated row numbers for which chgpu_index(col, P)
+   is the merged column.  The order of key column j is exactly the one chgpu_sort_permutation(col, .., descending[j],
+   nan_direction_hint[j]) defines (-0.0 == 0.0, NaN with NaN, NaN above or below every number by the hint, the complement for
+   descending); rows equal on all columns come out by run number, then by row within the run (SortCursor's tie on `order`), that is by
+   concatenated row number.  So for runs that are sorted P is bit-equal to the stable sort of the concatenation under the same
+   description.  limit > 0: only the first min(limit, rows) entries of P (every run and every merged run is cut to them on the way).
+   No rows or no runs: an empty permutation; one run: the identity, cut to the limit.
+   flags: CHGPU_MERGE_CHECK_SORTED runs chgpu_is_sorted first and answers BAD_ARGUMENTS naming the row; without it an unsorted run is
+   the caller's error and the order is unspecified (nothing is read or written out of bounds).
+   Errors: BAD_ARGUMENTS (a NULL ctx, list or output; n_keys of 0 or above 8; an unknown type; offsets that do not start at 0 or
+   decrease; unknown flag bits), SIZES_MISMATCH (a key column whose length is not run_offsets[n_runs]), NOT_IMPLEMENTED (2^32 rows or
+   more: row numbers travel as UInt32 inside, as in the window operator).  A failed call leaves nothing allocated. */
+enum { CHGPU_MERGE_CHECK_SORTED = 1 };
+int chgpu_merge_sorted_permutation(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint,
+                                   uint32_t n_keys, const uint64_t * run_offsets, uint32_t n_runs, uint64_t limit, uint32_t flags,
+                                   chgpu_col ** perm_out_u64);
+/* isAlreadySorted (src/Interpreters/sortBlock.cpp) per run, under the same order and with the same arguments and errors:
+   *first_unsorted_row = ~0ull when every run is sorted, else the LOWEST concatenated row number i (not the first of its run) for
+   which row i orders strictly before row i - 1.  Rows are never compared across a run boundary.  The same answer in every run. */
+int chgpu_is_sorted(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, uint32_t n_keys,
+                    const uint64_t * run_offsets, uint32_t n_runs, uint64_t * first_unsorted_row);
+
 /* ================================================================================================
  * a11/a21 hashing & sharding  —  ColumnVector::getWeakHash32 (ColumnVector.cpp:78-95), ConcurrentHashJoin
  * hashToSelector (src/Interpreters/ConcurrentHashJoin.cpp:426-440), IColumn::scatter (src/Columns/IColumn.cpp:245-269).
