@@ -86,7 +86,8 @@ struct SelSrc
     u32 mode;  // 0: UInt32 selector column; 1/2/4/8: key column of that many bytes, shard = (key >> shift) & 0xFF
     u32 shift;
 };
-__device__ __forceinline__ u32 sel_at(const SelSrc & s, u64 i, u32 num_shards)
+// `fold`: the number of shards the caller hands out (<= the power of two the kernels address by bit pattern)
+__device__ __forceinline__ u32 sel_at(const SelSrc & s, u64 i, u32 fold)
 {
     u32 v;
     switch (s.mode)
@@ -97,7 +98,7 @@ __device__ __forceinline__ u32 sel_at(const SelSrc & s, u64 i, u32 num_shards)
         case 4: v = (((const u32 *)s.p)[i] >> s.shift) & 0xFFu; break;
         default: v = (u32)(((const u64 *)s.p)[i] >> s.shift) & 0xFFu; break;
     }
-    return v < num_shards ? v : 0; // a selector beyond the shard count is a caller bug: folded into shard 0
+    return v < fold ? v : 0; // a selector beyond the shard count is a caller bug: folded into shard 0
 }
 
 #ifndef PL_RPT_V
@@ -108,7 +109,7 @@ static constexpr u32 PL_TILE = PT * PL_RPT;   // 4096 rows per workgroup tile (A
 static constexpr u32 PL_WAVE_ROWS = PL_TILE / (PT / 64);
 
 // (a wave-per-tile variant without workgroup barriers was measured 3-5 % slower on the 256-shard radix passes, same box A/B)
-__global__ __launch_bounds__(PT) void k_part_hist_lds(SelSrc sel, u64 n, u32 num_shards, u64 n_tiles, u32 * __restrict__ counts)
+__global__ __launch_bounds__(PT) void k_part_hist_lds(SelSrc sel, u64 n, u32 num_shards, u32 fold, u64 n_tiles, u32 * __restrict__ counts)
 {
     __shared__ u32 hist[MAX_SHARDS];
     for (u64 tile = blockIdx.x; tile < n_tiles; tile += gridDim.x)
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(PT) void k_part_hist_lds(SelSrc sel, u64 n, u32 num
                 for (u32 r = 0; r < 4; ++r)
                 {
                     const u32 x = (a[r] >> sh) & mk;
-                    v[j * 4 + r] = x < num_shards ? x : 0;
+                    v[j * 4 + r] = x < fold ? x : 0;
                 }
             }
         }
@@ -144,8 +145,8 @@ __global__ __launch_bounds__(PT) void k_part_hist_lds(SelSrc sel, u64 n, u32 num
             {
                 const ulonglong2 q = *(const ulonglong2 *)((const u64 *)sel.p + base + ((u64)j * PT + threadIdx.x) * 2);
                 const u32 x0 = (u32)(q.x >> sel.shift) & 0xFFu, x1 = (u32)(q.y >> sel.shift) & 0xFFu;
-                v[j * 2] = x0 < num_shards ? x0 : 0;
-                v[j * 2 + 1] = x1 < num_shards ? x1 : 0;
+                v[j * 2] = x0 < fold ? x0 : 0;
+                v[j * 2 + 1] = x1 < fold ? x1 : 0;
             }
         }
         else
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(PT) void k_part_hist_lds(SelSrc sel, u64 n, u32 num
             for (u32 j = 0; j < PL_RPT; ++j)
             {
                 const u64 i = base + (u64)j * PT + threadIdx.x;
-                v[j] = i < n ? sel_at(sel, i, num_shards) : ~0u;
+                v[j] = i < n ? sel_at(sel, i, fold) : ~0u;
             }
         }
         if (num_shards <= 8)
@@ -214,7 +215,7 @@ __device__ __forceinline__ void part_move_column(const T * __restrict__ src, T *
     __syncthreads();
 }
 
-__global__ __launch_bounds__(PT) void k_part_scatter_lds(SelSrc sel, u64 n, u32 num_shards, u32 shard_bits, u64 n_tiles,
+__global__ __launch_bounds__(PT) void k_part_scatter_lds(SelSrc sel, u64 n, u32 num_shards, u32 fold, u32 shard_bits, u64 n_tiles,
                                                          const u64 * __restrict__ offsets, PartCols cols)
 {
     __shared__ __attribute__((aligned(16))) u64 stage[PL_TILE]; // one column of the tile in destination order (32 KiB)
@@ -238,7 +239,7 @@ __global__ __launch_bounds__(PT) void k_part_scatter_lds(SelSrc sel, u64 n, u32 
         for (u32 j = 0; j < PL_RPT; ++j)
         {
             const u32 r = wave * PL_WAVE_ROWS + j * 64 + lane;
-            sv[j] = r < tile_rows ? sel_at(sel, base + r, num_shards) : ~0u;
+            sv[j] = r < tile_rows ? sel_at(sel, base + r, fold) : ~0u;
         }
 #pragma unroll
         for (u32 j = 0; j < PL_RPT; ++j)
@@ -381,8 +382,9 @@ extern "C" int chgpu_hash_to_selector(chgpu_ctx * ctx, const chgpu_col * keys, u
 }
 
 // Stable split of n_cols columns by shard into concatenated outputs; counts[num_shards] on the host (counts == nullptr: no
-// read-back, no host synchronisation -- the radix sort's passes).
-static int partition_core_src(chgpu_ctx * ctx, SelSrc sel, u64 n, u32 num_shards, u32 n_cols, const chgpu_col * const * cols,
+// read-back, no host synchronisation -- the radix sort's passes).  num_shards is a power of two; selectors >= fold (<= num_shards)
+// go to shard 0, in the histogram and in the scatter alike.
+static int partition_core_src(chgpu_ctx * ctx, SelSrc sel, u64 n, u32 num_shards, u32 fold, u32 n_cols, const chgpu_col * const * cols,
                               chgpu_col ** outs, u64 * counts)
 {
     CHGPU_REQUIRE(n_cols >= 1 && n_cols <= MAX_PART_COLS, CHGPU_ERR_NOT_IMPLEMENTED, "at most %u columns per partition call", MAX_PART_COLS);
@@ -435,9 +437,9 @@ static int partition_core_src(chgpu_ctx * ctx, SelSrc sel, u64 n, u32 num_shards
     {
         constexpr u32 wg_per_cu = PL_RPT >= 32 ? 2 : PL_RPT >= 16 ? 3 : 5; // what LDS (9 B per tile row + 7 KiB) and the VGPR count allow
         const u32 grid = (u32)std::min<u64>(n_tiles, (u64)ctx->num_cus * wg_per_cu);
-        hipLaunchKernelGGL(k_part_hist_lds, dim3((u32)std::min<u64>(n_tiles, (u64)ctx->num_cus * 8)), dim3(PT), 0, ctx->stream, sel, n, num_shards, n_tiles, cnt);
+        hipLaunchKernelGGL(k_part_hist_lds, dim3((u32)std::min<u64>(n_tiles, (u64)ctx->num_cus * 8)), dim3(PT), 0, ctx->stream, sel, n, num_shards, fold, n_tiles, cnt);
         CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, cnt, offs, m, starts + num_shards, tmp, tmp_b));
-        hipLaunchKernelGGL(k_part_scatter_lds, dim3(grid), dim3(PT), 0, ctx->stream, sel, n, num_shards, shard_bits, n_tiles, (const u64 *)offs, pc);
+        hipLaunchKernelGGL(k_part_scatter_lds, dim3(grid), dim3(PT), 0, ctx->stream, sel, n, num_shards, fold, shard_bits, n_tiles, (const u64 *)offs, pc);
     }
     ctx->counters[6] += 3;
     hipError_t e = hipGetLastError();
@@ -462,13 +464,13 @@ static int partition_core_src(chgpu_ctx * ctx, SelSrc sel, u64 n, u32 num_shards
 
 int chgpu_partition_core(chgpu_ctx * ctx, const u32 * sel, u64 n, u32 num_shards, u32 n_cols, const chgpu_col * const * cols, chgpu_col ** outs, u64 * counts)
 {
-    return partition_core_src(ctx, SelSrc{sel, 0, 0}, n, num_shards, n_cols, cols, outs, counts);
+    return partition_core_src(ctx, SelSrc{sel, 0, 0}, n, num_shards, num_shards, n_cols, cols, outs, counts);
 }
 
 // one radix pass: stable 256-way split of cols[] by byte `shift / 8` of the key column (no selector column, no host synchronisation)
 int chgpu_partition_by_key_byte(chgpu_ctx * ctx, const chgpu_col * keys, u32 shift, u32 n_cols, const chgpu_col * const * cols, chgpu_col ** outs)
 {
-    return partition_core_src(ctx, SelSrc{keys->data, (u32)chgpu_type_size(keys->type), shift}, keys->rows, 256, n_cols, cols, outs, nullptr);
+    return partition_core_src(ctx, SelSrc{keys->data, (u32)chgpu_type_size(keys->type), shift}, keys->rows, 256, 256, n_cols, cols, outs, nullptr);
 }
 
 extern "C" int chgpu_partition_by_hash(chgpu_ctx * ctx, const chgpu_col * keys, uint32_t num_shards, uint32_t n_cols,
@@ -492,14 +494,15 @@ extern "C" int chgpu_scatter(chgpu_ctx * ctx, const chgpu_col * col, const chgpu
     CHGPU_REQUIRE(selector->type == CHGPU_U32, CHGPU_ERR_BAD_ARGUMENTS, "selector must be a UInt32 column");
     CHGPU_REQUIRE(selector->rows == col->rows, CHGPU_ERR_SIZES_MISMATCH, "Size of selector (%llu) doesn't match size of column (%llu)",
                   (unsigned long long)selector->rows, (unsigned long long)col->rows);
-    // the split kernel addresses shards by bit pattern: round the shard count up to a power of two (extra shards stay empty)
+    // the split kernel addresses shards by bit pattern: round the shard count up to a power of two; the extra shards stay empty because
+    // the kernels fold every selector >= num_columns (a caller bug) into shard 0
     u32 shards_p2 = 1;
     while (shards_p2 < num_columns)
         shards_p2 <<= 1;
     chgpu_col * cat = nullptr;
     u64 counts[MAX_SHARDS];
     const chgpu_col * in[1] = {col};
-    CHGPU_TRY(chgpu_partition_core(ctx, (const u32 *)selector->data, col->rows, shards_p2, 1, in, &cat, counts));
+    CHGPU_TRY(partition_core_src(ctx, SelSrc{selector->data, 0, 0}, col->rows, shards_p2, num_columns, 1, in, &cat, counts));
     // hand the concatenated buffer out as num_columns columns sharing one allocation
     int * refs = new int(0);
     u64 pos = 0;
@@ -520,7 +523,6 @@ extern "C" int chgpu_scatter(chgpu_ctx * ctx, const chgpu_col * col, const chgpu
         outs[s] = v;
         pos += counts[s];
     }
-    // rows whose selector was >= num_columns (a caller bug) were folded into shard 0 by the kernels
     cat->owns = false;
     chgpu_col_free(cat);
     return CHGPU_OK;

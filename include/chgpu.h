@@ -457,7 +457,8 @@ int chgpu_is_sorted(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const i
 int chgpu_weak_hash32(chgpu_ctx * ctx, const chgpu_col * col, chgpu_col * hash_u32);
 /* selector[i] = ((crc32c(key) >> 24) & 0xFF) & (num_shards-1); num_shards power of two <= 256; out: CHGPU_U32 */
 int chgpu_hash_to_selector(chgpu_ctx * ctx, const chgpu_col * keys, uint32_t num_shards, chgpu_col ** selector_u32);
-/* stable split of col by selector into num_columns new columns (outs[num_columns]) */
+/* stable split of col by selector into num_columns new columns (outs[num_columns]); num_columns <= 256; a selector >= num_columns
+ * (a caller bug) counts as 0, so the sizes of the new columns always sum to the rows of col */
 int chgpu_scatter(chgpu_ctx * ctx, const chgpu_col * col, const chgpu_col * selector_u32, uint32_t num_columns,
                   chgpu_col ** outs);
 /* one-call hash partition of n_cols columns by keys (cols[0] must be the key column or any payload): computes the
