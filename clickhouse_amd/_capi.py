@@ -36,6 +36,7 @@ STR_CONST_MAX = 256   # bytes of a string constant / LIKE pattern the kernels ca
 FRAME_ROWS, FRAME_RANGE = 0, 1
 BOUND_UNBOUNDED_PRECEDING, BOUND_OFFSET_PRECEDING, BOUND_CURRENT_ROW, BOUND_OFFSET_FOLLOWING, BOUND_UNBOUNDED_FOLLOWING = 0, 1, 2, 3, 4
 MERGE_CHECK_SORTED = 1   # chgpu_merge_sorted_permutation flags
+FOLD_SUM, FOLD_MIN, FOLD_MAX = 0, 1, 2   # chgpu_merge_folding kinds
 
 _vp, _i, _u32, _u64, _i64 = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_int64
 _pp = C.POINTER(C.c_void_p)
@@ -111,6 +112,10 @@ SIGNATURES = {
     "chgpu_filter_to_indices": (_i, [_vp, _vp, _pp, _pu64]),
     "chgpu_merge_sorted_permutation": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _u64, _u32, _pp]),
     "chgpu_is_sorted": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _pu64]),
+    "chgpu_merge_replacing": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _u32, _vp, _vp, C.c_int32, _pp]),
+    "chgpu_merge_collapsing": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _u32, _vp, _pp]),
+    "chgpu_merge_folding": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _u32, _vp, C.POINTER(C.c_int32), _u32, C.c_int32,
+                                 _pp, _pp, _pp]),
     "chgpu_weak_hash32": (_i, [_vp, _vp, _vp]),
     "chgpu_hash_to_selector": (_i, [_vp, _vp, _u32, _pp]),
     "chgpu_scatter": (_i, [_vp, _vp, _vp, _u32, _pp]),

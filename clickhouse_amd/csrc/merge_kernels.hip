@@ -10,52 +10,14 @@
 //   k_merge_tiles      per round, ONE launch: a workgroup stages its tile's two input pieces in LDS, every thread finds its own diagonal
 //                      there and merges MRG_ITEMS consecutive outputs, the tile goes out coalesced
 //   k_merge_perm       the last round's row numbers widened to the UInt64 permutation
+//   k_merge_pairs_of   the (word, row) pairs of a merged order known as a permutation: what merge_order (merge_keys.h) hands the folding
+//                      merges where the plan is the sort chain, or there is one run
 //   k_merge_is_sorted  adjacent rows compared under the same order, never across a run boundary; per-tile minimum of the violating row
 //   k_merge_min        one workgroup folds the tile minima: the LOWEST violating row, the same in every run
 // The comparator reads the words first; on equal words (and n_keys > 1) the remaining columns through the row numbers; all equal: the
 // left run's element first (merge_host.h keeps the invariant).  No atomics anywhere.
 // Algorithmic bytes per row: key build sizeof(T) + 12; a round 2 x 12; the permutation 4 + 8.  is_sorted: the key columns once.
-#include "chgpu_internal.h"
-#include "merge_host.h"
-#include "pair_pool.h"
-#include "sort_key.h"
-
-struct MergeKeys
-{
-    const void * data[MRG_MAX_KEYS];
-    i32 type[MRG_MAX_KEYS];
-    i32 desc[MRG_MAX_KEYS];
-    i32 hint[MRG_MAX_KEYS];
-    u32 n;
-};
-
-template <typename T>
-__device__ __forceinline__ u64 mrg_key_of(const void * data, u64 row, int desc, int hint)
-{
-    typedef typename SortKey<T>::K K;
-    const K k = SortKey<T>::key(((const T *)data)[row], hint);
-    return (u64)(desc ? (K)~k : k); // the complement inside the key's width, as k_sort_keys takes it
-}
-
-// column j of `keys` at `row` as a u64 word that orders like the column does under its description
-__device__ __forceinline__ u64 mrg_key(const MergeKeys & keys, u32 j, u64 row)
-{
-    const void * d = keys.data[j];
-    const int desc = keys.desc[j], hint = keys.hint[j];
-    switch (keys.type[j])
-    {
-        case CHGPU_I64: return mrg_key_of<i64>(d, row, desc, hint);
-        case CHGPU_U64: return mrg_key_of<u64>(d, row, desc, hint);
-        case CHGPU_I32: return mrg_key_of<i32>(d, row, desc, hint);
-        case CHGPU_U32: return mrg_key_of<u32>(d, row, desc, hint);
-        case CHGPU_I16: return mrg_key_of<i16>(d, row, desc, hint);
-        case CHGPU_U16: return mrg_key_of<u16>(d, row, desc, hint);
-        case CHGPU_I8: return mrg_key_of<i8>(d, row, desc, hint);
-        case CHGPU_U8: return mrg_key_of<u8>(d, row, desc, hint);
-        case CHGPU_F64: return mrg_key_of<double>(d, row, desc, hint);
-        default: return mrg_key_of<float>(d, row, desc, hint);
-    }
-}
+#include "merge_keys.h"
 
 // Does (wb, rb) order STRICTLY before (wa, ra)?  Equal on every column answers false: the caller then takes the left run's element.
 __device__ __forceinline__ bool mrg_before(const MergeKeys & keys, u64 wb, u32 rb, u64 wa, u32 ra)
@@ -174,29 +136,22 @@ __global__ __launch_bounds__(MRG_THREADS) void k_merge_tiles(MergeKeys keys, con
     }
 }
 
+// the (word, row) pairs of a merged order that is known as a permutation (perm == NULL: the identity), for merge_order
+__global__ __launch_bounds__(256) void k_merge_pairs_of(MergeKeys keys, const u64 * __restrict__ perm, u32 n, u64 * __restrict__ words, u32 * __restrict__ rows)
+{
+    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
+    {
+        const u32 src = perm ? (u32)perm[i] : (u32)i;
+        words[i] = mrg_key(keys, 0, src);
+        rows[i] = src;
+    }
+}
+
 // rows == NULL: the identity
 __global__ __launch_bounds__(256) void k_merge_perm(const u32 * __restrict__ rows, u64 n, u64 * __restrict__ perm)
 {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
         perm[i] = rows ? rows[i] : i;
-}
-
-__device__ __forceinline__ u64 mrg_block_min(u64 v, u64 * lds /* MRG_THREADS / WAVE */)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-    {
-        const u64 o = shfl_down_u64(v, d);
-        v = o < v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0)
-        lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 m = lds[0];
-    for (u32 w = 1; w < MRG_THREADS / WAVE; ++w)
-        m = lds[w] < m ? lds[w] : m;
-    __syncthreads();
-    return m;
 }
 
 // run_off[n_runs + 1]; partial[blockIdx.x] = the lowest row i of this tile that is no run's first row and orders strictly before
@@ -259,8 +214,8 @@ __global__ __launch_bounds__(MRG_THREADS) void k_merge_min(const u64 * __restric
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-static int merge_validate(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, u32 n_keys,
-                          const uint64_t * run_offsets, u32 n_runs, MergeKeys * keys, u64 * rows)
+int merge_validate(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, u32 n_keys,
+                   const uint64_t * run_offsets, u32 n_runs, MergeKeys * keys, u64 * rows)
 {
     CHGPU_REQUIRE(ctx && key_cols && descending && nan_direction_hint && run_offsets, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
     CHGPU_REQUIRE(n_keys >= 1 && n_keys <= MRG_MAX_KEYS, CHGPU_ERR_BAD_ARGUMENTS, "%u key columns: a sort description has 1 to %u", n_keys, MRG_MAX_KEYS);
@@ -292,6 +247,12 @@ static int merge_upload(chgpu_ctx * ctx, PairTemps & tmp, const void * host, siz
     return CHGPU_OK;
 }
 
+void merge_lowest(chgpu_ctx * ctx, const u64 * partial, u32 n, u64 * out)
+{
+    hipLaunchKernelGGL(k_merge_min, dim3(1), dim3(MRG_THREADS), 0, ctx->stream, partial, n, out);
+    ctx->counters[6] += 1;
+}
+
 // *first_unsorted_row: ~0, or the lowest row that orders before its predecessor inside one run.  rows >= 1.
 static int merge_is_sorted(chgpu_ctx * ctx, const MergeKeys & keys, const uint64_t * run_offsets, u32 n_runs, u64 rows, u64 * first_unsorted_row)
 {
@@ -307,9 +268,18 @@ static int merge_is_sorted(chgpu_ctx * ctx, const MergeKeys & keys, const uint64
     const u32 tiles = merge_tiles((u32)rows);
     CHGPU_TRY(tmp.alloc(((size_t)tiles + 1) * sizeof(u64), &partial));
     hipLaunchKernelGGL(k_merge_is_sorted, dim3(tiles), dim3(MRG_THREADS), 0, ctx->stream, keys, (const u32 *)off_dev, n_runs, (u32)rows, (u64 *)partial);
-    hipLaunchKernelGGL(k_merge_min, dim3(1), dim3(MRG_THREADS), 0, ctx->stream, (const u64 *)partial, tiles, (u64 *)partial + tiles);
-    ctx->counters[6] += 2;
+    ctx->counters[6] += 1;
+    merge_lowest(ctx, (const u64 *)partial, tiles, (u64 *)partial + tiles);
     return chgpu_read_back(ctx, (const u64 *)partial + tiles, first_unsorted_row, sizeof(u64));
+}
+
+int merge_require_sorted(chgpu_ctx * ctx, const MergeKeys & keys, const uint64_t * run_offsets, u32 n_runs, u64 rows)
+{
+    u64 bad = ~0ull;
+    CHGPU_TRY(merge_is_sorted(ctx, keys, run_offsets, n_runs, rows, &bad));
+    CHGPU_REQUIRE(bad == ~0ull, CHGPU_ERR_BAD_ARGUMENTS, "a run is not sorted: row %llu orders before row %llu", (unsigned long long)bad,
+                  (unsigned long long)(bad - 1));
+    return CHGPU_OK;
 }
 
 extern "C" int chgpu_is_sorted(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, uint32_t n_keys,
@@ -326,14 +296,10 @@ extern "C" int chgpu_is_sorted(chgpu_ctx * ctx, const chgpu_col * const * key_co
     return merge_is_sorted(ctx, keys, run_offsets, n_runs, rows, first_unsorted_row);
 }
 
-// the merge tree over runs cut to `lens`; *perm_out: n_out entries
-static int merge_tree(chgpu_ctx * ctx, const MergeKeys & keys, const uint64_t * run_offsets, u32 n_runs, u64 rows, const std::vector<u32> & lens, u64 cut_rows,
-                      u64 limit, u64 n_out, chgpu_col ** perm_out)
+// the merge tree over runs cut to `lens`: the last round's (word, row) arrays, in `tmp`
+static int merge_tree_pairs(chgpu_ctx * ctx, PairTemps & tmp, const MergeKeys & keys, const uint64_t * run_offsets, u32 n_runs, u64 rows, const std::vector<u32> & lens,
+                            u64 cut_rows, u64 limit, const u64 ** words_out, const u32 ** rows_out)
 {
-    PairAllocs mem;
-    mem.ctx = ctx, mem.op = "merge_sorted";
-    mem.begin_call();
-    PairTemps tmp(mem);
     const std::vector<MergeRound> rounds = merge_rounds(lens, limit);
     // one table for the whole call: the key build's run map (only when a run was cut), then every round's pairs
     std::vector<u32> map;
@@ -365,8 +331,6 @@ static int merge_tree(chgpu_ctx * ctx, const MergeKeys & keys, const uint64_t * 
         CHGPU_TRY(tmp.alloc(cut_rows * sizeof(u64), &words[b]));
         CHGPU_TRY(tmp.alloc(cut_rows * sizeof(u32), &rws[b]));
     }
-    chgpu_col * perm = nullptr;
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, n_out, &perm));
     const u32 n_map = map.empty() ? 0 : n_runs;
     hipLaunchKernelGGL(k_merge_keys, dim3(chgpu_grid_for(ctx, cut_rows, 256, 8)), dim3(256), 0, ctx->stream, keys, (const u32 *)map_dev,
                        (const u32 *)map_dev + n_runs + 1, n_map, (u32)cut_rows, (u64 *)words[0], (u32 *)rws[0]);
@@ -387,7 +351,25 @@ static int merge_tree(chgpu_ctx * ctx, const MergeKeys & keys, const uint64_t * 
         round_pairs += n_pairs;
         cur ^= 1;
     }
-    hipLaunchKernelGGL(k_merge_perm, dim3(chgpu_grid_for(ctx, n_out, 256, 8)), dim3(256), 0, ctx->stream, (const u32 *)rws[cur], n_out, (u64 *)perm->data);
+    *words_out = (const u64 *)words[cur];
+    *rows_out = (const u32 *)rws[cur];
+    return CHGPU_OK;
+}
+
+// *perm_out: the first n_out row numbers of the tree's last round
+static int merge_tree(chgpu_ctx * ctx, const MergeKeys & keys, const uint64_t * run_offsets, u32 n_runs, u64 rows, const std::vector<u32> & lens, u64 cut_rows,
+                      u64 limit, u64 n_out, chgpu_col ** perm_out)
+{
+    PairAllocs mem;
+    mem.ctx = ctx, mem.op = "merge_sorted";
+    mem.begin_call();
+    PairTemps tmp(mem);
+    const u64 * words = nullptr;
+    const u32 * rws = nullptr;
+    CHGPU_TRY(merge_tree_pairs(ctx, tmp, keys, run_offsets, n_runs, rows, lens, cut_rows, limit, &words, &rws));
+    chgpu_col * perm = nullptr;
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, n_out, &perm));
+    hipLaunchKernelGGL(k_merge_perm, dim3(chgpu_grid_for(ctx, n_out, 256, 8)), dim3(256), 0, ctx->stream, rws, n_out, (u64 *)perm->data);
     ctx->counters[6] += 1;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
@@ -418,6 +400,32 @@ static int merge_by_sort(chgpu_ctx * ctx, const chgpu_col * const * key_cols, co
     return CHGPU_OK;
 }
 
+int merge_order(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const MergeKeys & keys, const uint64_t * run_offsets, u32 n_runs, u64 rows, PairTemps & tmp,
+                const u64 ** words, const u32 ** row_numbers)
+{
+    u32 key_sizes[MRG_MAX_KEYS];
+    for (u32 j = 0; j < keys.n; ++j)
+        key_sizes[j] = (u32)chgpu_type_size(keys.type[j]);
+    if (n_runs > 1 && merge_plan(key_sizes, keys.n, rows, rows, n_runs) == MERGE_PLAN_TREE)
+        return merge_tree_pairs(ctx, tmp, keys, run_offsets, n_runs, rows, merge_initial_runs(run_offsets, n_runs, 0), rows, 0, words, row_numbers);
+    // one run: M is the identity; the sort chain: M is its permutation.  The pairs are built from it.
+    chgpu_col * perm = nullptr;
+    if (n_runs > 1)
+    {
+        CHGPU_TRY(merge_by_sort(ctx, key_cols, keys, rows, &perm));
+        tmp.cols.push_back(perm);
+    }
+    void * w = nullptr, * r = nullptr;
+    CHGPU_TRY(tmp.alloc(rows * sizeof(u64), &w));
+    CHGPU_TRY(tmp.alloc(rows * sizeof(u32), &r));
+    hipLaunchKernelGGL(k_merge_pairs_of, dim3(chgpu_grid_for(ctx, rows, 256, 8)), dim3(256), 0, ctx->stream, keys, perm ? (const u64 *)perm->data : (const u64 *)nullptr,
+                       (u32)rows, (u64 *)w, (u32 *)r);
+    ctx->counters[6] += 1;
+    *words = (const u64 *)w;
+    *row_numbers = (const u32 *)r;
+    return CHGPU_OK;
+}
+
 extern "C" int chgpu_merge_sorted_permutation(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint,
                                               uint32_t n_keys, const uint64_t * run_offsets, uint32_t n_runs, uint64_t limit, uint32_t flags, chgpu_col ** perm_out_u64)
 {
@@ -428,12 +436,7 @@ extern "C" int chgpu_merge_sorted_permutation(chgpu_ctx * ctx, const chgpu_col *
     CHGPU_TRY(merge_validate(ctx, key_cols, descending, nan_direction_hint, n_keys, run_offsets, n_runs, &keys, &rows));
     CHGPU_REQUIRE(!(flags & ~(u32)CHGPU_MERGE_CHECK_SORTED), CHGPU_ERR_BAD_ARGUMENTS, "unknown flag bits 0x%x", flags & ~(u32)CHGPU_MERGE_CHECK_SORTED);
     if ((flags & CHGPU_MERGE_CHECK_SORTED) && rows >= 2)
-    {
-        u64 bad = ~0ull;
-        CHGPU_TRY(merge_is_sorted(ctx, keys, run_offsets, n_runs, rows, &bad));
-        CHGPU_REQUIRE(bad == ~0ull, CHGPU_ERR_BAD_ARGUMENTS, "a run is not sorted: row %llu orders before row %llu", (unsigned long long)bad,
-                      (unsigned long long)(bad - 1));
-    }
+        CHGPU_TRY(merge_require_sorted(ctx, keys, run_offsets, n_runs, rows));
     const u64 n_out = merge_cut(rows, limit);
     if (n_out == 0 || n_runs == 1)
     {

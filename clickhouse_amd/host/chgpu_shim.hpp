@@ -2610,6 +2610,190 @@ private:
     std::vector<Chunk> chunks;
 };
 
+/// The inputs of the folding merges below: K inputs of sorted chunks numbered input by input (as GpuMergingSortedTransform numbers them),
+/// glued into one Block with the arguments every chgpu_merge_* entry point shares.
+class GpuFoldingMergeInputs
+{
+public:
+    GpuFoldingMergeInputs(ContextPtr ctx_, size_t num_inputs, SortDescription description_)
+        : ctx(std::move(ctx_)), description(std::move(description_)), inputs(num_inputs) {}
+
+    void consume(size_t input, Chunk chunk)
+    {
+        if (chunk.num_rows)
+            inputs.at(input).push_back(std::move(chunk));
+    }
+
+protected:
+    /// false: nothing was consumed
+    bool glue()
+    {
+        std::vector<Chunk> runs;
+        for (auto & in : inputs)
+        {
+            for (auto & chunk : in)
+                runs.push_back(std::move(chunk));
+            in.clear();
+        }
+        glued = Chunk();
+        offsets.assign(1, 0);
+        keys.clear(), descending.clear(), hints.clear();
+        if (runs.empty() || description.empty())
+            return false;
+        for (auto & run : runs)
+            offsets.push_back(offsets.back() + run.num_rows);
+        for (size_t c = 0; c < runs[0].columns.size(); ++c)
+        {
+            std::vector<const chgpu_col *> parts;
+            for (auto & run : runs)
+                parts.push_back(run.columns.at(c)->handle());
+            chgpu_col * cat = nullptr;
+            check(chgpu_col_concat(ctx->get(), static_cast<uint32_t>(parts.size()), parts.data(), &cat));
+            glued.columns.push_back(std::make_shared<ColumnVector>(ctx, cat));
+        }
+        for (const auto & d : description)
+        {
+            keys.push_back(glued.columns.at(d.column_number)->handle());
+            descending.push_back(d.direction < 0);
+            hints.push_back(d.nulls_direction);
+        }
+        return true;
+    }
+    uint32_t numKeys() const { return static_cast<uint32_t>(keys.size()); }
+    uint32_t numRuns() const { return static_cast<uint32_t>(offsets.size() - 1); }
+    /// every glued column indexed with the surviving rows
+    Chunk indexed(chgpu_col * rows)
+    {
+        ColumnVector selected(ctx, rows);
+        Chunk out;
+        for (auto & col : glued.columns)
+            out.columns.push_back(col->index(selected, 0));
+        out.num_rows = selected.size();
+        glued = Chunk();
+        return out;
+    }
+
+    ContextPtr ctx;
+    SortDescription description;
+    std::vector<std::vector<Chunk>> inputs;
+    Chunk glued;
+    std::vector<uint64_t> offsets;
+    std::vector<const chgpu_col *> keys;
+    std::vector<int32_t> descending, hints;
+};
+
+/// ReplacingSortedTransform (src/Processors/Merges/Algorithms/ReplacingSortedAlgorithm.cpp): per group of equal sorting key the last
+/// row among those of the greatest version; version_column / is_deleted_column are positions, -1: none.
+class GpuReplacingSortedTransform : public GpuFoldingMergeInputs
+{
+public:
+    GpuReplacingSortedTransform(ContextPtr ctx_, size_t num_inputs, SortDescription description_, int version_column_ = -1, int is_deleted_column_ = -1,
+                                bool cleanup_ = false)
+        : GpuFoldingMergeInputs(std::move(ctx_), num_inputs, std::move(description_)), version_column(version_column_),
+          is_deleted_column(is_deleted_column_), cleanup(cleanup_) {}
+
+    Chunk finish()
+    {
+        if (!glue())
+            return Chunk();
+        chgpu_col * rows = nullptr;
+        check(chgpu_merge_replacing(ctx->get(), keys.data(), descending.data(), hints.data(), numKeys(), offsets.data(), numRuns(), CHGPU_MERGE_CHECK_SORTED,
+                                    version_column < 0 ? nullptr : glued.columns.at(version_column)->handle(),
+                                    is_deleted_column < 0 ? nullptr : glued.columns.at(is_deleted_column)->handle(), cleanup ? 1 : 0, &rows));
+        return indexed(rows);
+    }
+
+private:
+    int version_column, is_deleted_column;
+    bool cleanup;
+};
+
+/// CollapsingSortedTransform (src/Processors/Merges/Algorithms/CollapsingSortedAlgorithm.cpp); sign_column: the position of the Int8 sign
+class GpuCollapsingSortedTransform : public GpuFoldingMergeInputs
+{
+public:
+    GpuCollapsingSortedTransform(ContextPtr ctx_, size_t num_inputs, SortDescription description_, size_t sign_column_)
+        : GpuFoldingMergeInputs(std::move(ctx_), num_inputs, std::move(description_)), sign_column(sign_column_) {}
+
+    Chunk finish()
+    {
+        if (!glue())
+            return Chunk();
+        chgpu_col * rows = nullptr;
+        check(chgpu_merge_collapsing(ctx->get(), keys.data(), descending.data(), hints.data(), numKeys(), offsets.data(), numRuns(), CHGPU_MERGE_CHECK_SORTED,
+                                     glued.columns.at(sign_column)->handle(), &rows));
+        return indexed(rows);
+    }
+
+private:
+    size_t sign_column;
+};
+
+/// AggregatingSortedTransform over SimpleAggregateFunction columns (src/Processors/Merges/Algorithms/AggregatingSortedAlgorithm.cpp):
+/// folds[position] = CHGPU_FOLD_SUM / MIN / MAX, last_columns: positions that take the group's last row (anyLast); every other column
+/// takes the group's first row (any).  drop_zero: Summing's rule.
+class GpuAggregatingSortedTransform : public GpuFoldingMergeInputs
+{
+public:
+    GpuAggregatingSortedTransform(ContextPtr ctx_, size_t num_inputs, SortDescription description_, std::map<size_t, int> folds_,
+                                  std::vector<size_t> last_columns_ = {}, bool drop_zero_ = false)
+        : GpuFoldingMergeInputs(std::move(ctx_), num_inputs, std::move(description_)), folds(std::move(folds_)), last_columns(std::move(last_columns_)),
+          drop_zero(drop_zero_) {}
+
+    Chunk finish()
+    {
+        if (!glue())
+            return Chunk();
+        std::vector<const chgpu_col *> values;
+        std::vector<int32_t> kinds;
+        for (const auto & [position, kind] : folds)
+        {
+            values.push_back(glued.columns.at(position)->handle());
+            kinds.push_back(kind);
+        }
+        chgpu_col * first = nullptr, * last = nullptr;
+        std::vector<chgpu_col *> results(values.size() + 1, nullptr);
+        check(chgpu_merge_folding(ctx->get(), keys.data(), descending.data(), hints.data(), numKeys(), offsets.data(), numRuns(), CHGPU_MERGE_CHECK_SORTED,
+                                  values.data(), kinds.data(), static_cast<uint32_t>(values.size()), drop_zero ? 1 : 0, &first, &last, results.data()));
+        ColumnVector first_rows(ctx, first), last_rows(ctx, last);
+        Chunk out;
+        size_t folded = 0;
+        for (size_t c = 0; c < glued.columns.size(); ++c)
+        {
+            if (folds.count(c))
+                out.columns.push_back(std::make_shared<ColumnVector>(ctx, results[folded++]));
+            else
+                out.columns.push_back(glued.columns[c]->index(std::find(last_columns.begin(), last_columns.end(), c) != last_columns.end() ? last_rows : first_rows, 0));
+        }
+        out.num_rows = first_rows.size();
+        glued = Chunk();
+        return out;
+    }
+
+private:
+    std::map<size_t, int> folds;
+    std::vector<size_t> last_columns;
+    bool drop_zero;
+};
+
+/// SummingSortedTransform (src/Processors/Merges/Algorithms/SummingSortedAlgorithm.cpp): columns_to_sum (positions of integer columns)
+/// summed with wrap-around, groups whose sums are all 0 dropped, every other column the group's first row's.
+class GpuSummingSortedTransform : public GpuAggregatingSortedTransform
+{
+public:
+    GpuSummingSortedTransform(ContextPtr ctx_, size_t num_inputs, SortDescription description_, const std::vector<size_t> & columns_to_sum)
+        : GpuAggregatingSortedTransform(std::move(ctx_), num_inputs, std::move(description_), sums(columns_to_sum), {}, true) {}
+
+private:
+    static std::map<size_t, int> sums(const std::vector<size_t> & columns)
+    {
+        std::map<size_t, int> m;
+        for (size_t c : columns)
+            m[c] = CHGPU_FOLD_SUM;
+        return m;
+    }
+};
+
 /// CompressedReadBuffer + SerializationNumber::deserializeBinaryBulk for one numeric column file (MergeTree `<column>.bin`): the
 /// host walks the frame headers (CompressedReadBufferBase.cpp:175-222), the compressed bytes cross PCIe once, the frames are decoded
 /// in HBM.  LZ4, NONE and CODEC(Delta, LZ4); any other codec throws NOT_IMPLEMENTED (the caller decompresses on the CPU as before).

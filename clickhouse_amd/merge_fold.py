@@ -1,0 +1,202 @@
+"""The merges of MergeTree that fold rows of equal sorting key while they merge, over the C ABI: ReplacingSortedAlgorithm,
+CollapsingSortedAlgorithm, SummingSortedAlgorithm and AggregatingSortedAlgorithm over SimpleAggregateFunction columns
+(src/Processors/Merges/Algorithms/).  The input is what merge_sorted takes -- sorted runs glued end to end -- and the answer is the rows
+that survive, in merged order, as concatenated row numbers (and, for the folding form, one result column per folded column).  Numeric
+columns only; String columns, Float value columns and bad descriptions raise before the library is touched.
+
+The *_rows functions return the raw outputs; the Block-level functions glue the blocks, call them and index every column."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _capi as K
+from .columns import Column, Context, concat
+from .merge_sorted import _check_blocks, _check_column, _check_description, _prepare
+
+TILE = 2048       # T: merged positions of one fold tile (FOLD_TILE of csrc/merge_fold_host.h)
+MAX_VALUES = 8    # value columns of one folding call (FOLD_MAX_VALUES)
+KINDS = {"sum": K.FOLD_SUM, "min": K.FOLD_MIN, "max": K.FOLD_MAX}
+
+
+def _dtype_of(c):
+    return c.dtype if isinstance(c, Column) else np.asarray(c).dtype
+
+
+def _check_typed(c, what, kinds, expect):
+    """a numeric column whose dtype kind is one of `kinds` (and, when given, exactly `expect`)"""
+    _check_column(c, what)
+    dt = _dtype_of(c)
+    if dt.kind not in kinds or (expect is not None and dt != np.dtype(expect)):
+        raise TypeError(f"{what} has dtype {dt}: it must be {np.dtype(expect).name if expect is not None else 'an integer column'}")
+
+
+def _check_values(values, kinds):
+    values, kinds = list(values), list(kinds)
+    if len(values) != len(kinds):
+        raise ValueError(f"{len(values)} value columns and {len(kinds)} kinds")
+    if len(values) > MAX_VALUES:
+        raise ValueError(f"{len(values)} value columns: one folding call takes at most {MAX_VALUES}")
+    codes = []
+    for k, (v, kind) in enumerate(zip(values, kinds)):
+        if kind not in KINDS:
+            raise ValueError(f"value column {k}: the fold kind {kind!r} is not one of {sorted(KINDS)}")
+        _check_typed(v, f"value column {k}", "iu", None)   # a Float column: the reference's sequential sum rounds differently from a scan
+        codes.append(KINDS[kind])
+    return values, codes
+
+
+def _flags(check):
+    return K.MERGE_CHECK_SORTED if check else 0
+
+
+def _handle(ctx, cols, c):
+    """the handle of an argument column, uploaded to the keys' context (kept alive in cols)"""
+    c = ctx.column(c)
+    cols.append(c)
+    return c._h
+
+
+def replacing_merge_rows(key_cols, description, run_offsets, version=None, is_deleted=None, cleanup: bool = False, check: bool = True) -> Column:
+    """per group of equal keys the last row in merged order among those of the greatest version (without a version: the group's last
+    row) -> the UInt64 Column of their concatenated row numbers.  is_deleted (UInt8, needs a version): with cleanup a group whose
+    selected row is deleted emits nothing."""
+    if version is not None:
+        _check_typed(version, "the version column", "iu", None)
+    if is_deleted is not None:
+        if version is None:
+            raise ValueError("is_deleted without a version column is not implemented")
+        _check_typed(is_deleted, "the is_deleted column", "u", np.uint8)
+    ctx, cols, args = _prepare(key_cols, description, run_offsets)
+    v = _handle(ctx, cols, version) if version is not None else None
+    d = _handle(ctx, cols, is_deleted) if is_deleted is not None else None
+    out = C.c_void_p()
+    K.check(K.lib().chgpu_merge_replacing(ctx._live(), *args, _flags(check), v, d, 1 if cleanup else 0, C.byref(out)))
+    return Column(ctx, out)
+
+
+def collapsing_merge_rows(key_cols, description, run_offsets, sign, check: bool = True) -> Column:
+    """CollapsingSortedAlgorithm: per group nothing, the first negative row, the last positive row, or both -> their row numbers"""
+    _check_typed(sign, "the sign column", "i", np.int8)
+    ctx, cols, args = _prepare(key_cols, description, run_offsets)
+    s = _handle(ctx, cols, sign)
+    out = C.c_void_p()
+    K.check(K.lib().chgpu_merge_collapsing(ctx._live(), *args, _flags(check), s, C.byref(out)))
+    return Column(ctx, out)
+
+
+def aggregating_merge_rows(key_cols, description, run_offsets, values, kinds, drop_zero: bool = False, check: bool = True):
+    """values[i] folded by kinds[i] in ("sum", "min", "max") per group of equal keys
+    -> (first_rows, last_rows, [result Column per value]); drop_zero: Summing's rule"""
+    values, codes = _check_values(values, kinds)
+    ctx, cols, args = _prepare(key_cols, description, run_offsets)
+    n = len(values)
+    handles = (C.c_void_p * max(n, 1))(*[_handle(ctx, cols, v) for v in values])
+    first, last = C.c_void_p(), C.c_void_p()
+    res = (C.c_void_p * max(n, 1))()
+    K.check(K.lib().chgpu_merge_folding(ctx._live(), *args, _flags(check), handles, (C.c_int32 * max(n, 1))(*codes), n, 1 if drop_zero else 0, C.byref(first),
+                                        C.byref(last), res))
+    return Column(ctx, first), Column(ctx, last), [Column(ctx, C.c_void_p(res[k])) for k in range(n)]
+
+
+def summing_merge_rows(key_cols, description, run_offsets, values, check: bool = True):
+    """SummingSortedAlgorithm: every value column summed with wrap-around, groups whose sums are all 0 dropped"""
+    values = list(values)
+    return aggregating_merge_rows(key_cols, description, run_offsets, values, ["sum"] * len(values), drop_zero=True, check=check)
+
+
+def _glue(blocks, description):
+    blocks, width = _check_blocks(blocks)
+    description = _check_description(description, width)
+    return blocks, width, description
+
+
+def _position(pos, width, what):
+    if not isinstance(pos, (int, np.integer)) or not 0 <= pos < width:
+        raise ValueError(f"{what} position {pos!r} is not one of the {width} columns")
+    return int(pos)
+
+
+def _upload_and_glue(blocks, width):
+    ctx = next((c.ctx for block in blocks for c in block if isinstance(c, Column)), None) or Context(0)
+    blocks = [[ctx.column(c) for c in block] for block in blocks]
+    offsets = [0]
+    for block in blocks:
+        offsets.append(offsets[-1] + (len(block[0]) if block else 0))
+    return [concat([block[k] for block in blocks]) for k in range(width)], offsets
+
+
+def replacing_merge(blocks, description, version=None, is_deleted=None, cleanup: bool = False, check: bool = True):
+    """ReplacingSortedTransform over sorted Blocks; version / is_deleted are column positions.  -> (columns, rows)"""
+    blocks, width, description = _glue(blocks, description)
+    if version is not None:
+        version = _position(version, width, "the version")
+        _check_typed(blocks[0][version], "the version column", "iu", None)
+    if is_deleted is not None:
+        if version is None:
+            raise ValueError("is_deleted without a version column is not implemented")
+        is_deleted = _position(is_deleted, width, "the is_deleted")
+        _check_typed(blocks[0][is_deleted], "the is_deleted column", "u", np.uint8)
+    glued, offsets = _upload_and_glue(blocks, width)
+    rows = replacing_merge_rows(glued, description, offsets, None if version is None else glued[version], None if is_deleted is None else glued[is_deleted],
+                                cleanup=cleanup, check=check)
+    return [c.index(rows) for c in glued], rows
+
+
+def collapsing_merge(blocks, description, sign, check: bool = True):
+    """CollapsingSortedTransform over sorted Blocks; sign is the position of the Int8 sign column.  -> (columns, rows)"""
+    blocks, width, description = _glue(blocks, description)
+    sign = _position(sign, width, "the sign")
+    _check_typed(blocks[0][sign], "the sign column", "i", np.int8)
+    glued, offsets = _upload_and_glue(blocks, width)
+    rows = collapsing_merge_rows(glued, description, offsets, glued[sign], check=check)
+    return [c.index(rows) for c in glued], rows
+
+
+def _folding_merge(blocks, width, description, kinds, drop_zero, check):
+    """kinds: {position: "sum" | "min" | "max" | "any" | "anyLast"}; every other column is `any`"""
+    folded = [p for p in sorted(kinds) if kinds[p] in KINDS]
+    for p in folded:
+        _check_typed(blocks[0][p], f"column {p}", "iu", None)
+    if len(folded) > MAX_VALUES:
+        raise ValueError(f"{len(folded)} folded columns: one folding call takes at most {MAX_VALUES}")
+    glued, offsets = _upload_and_glue(blocks, width)
+    first, last, results = aggregating_merge_rows(glued, description, offsets, [glued[p] for p in folded], [kinds[p] for p in folded], drop_zero=drop_zero,
+                                                  check=check)
+    out = []
+    for p in range(width):
+        if p in folded:
+            out.append(results[folded.index(p)])
+        else:
+            out.append(glued[p].index(last if kinds.get(p) == "anyLast" else first))
+    return out, first, last
+
+
+def summing_merge(blocks, description, columns_to_sum=None, check: bool = True):
+    """SummingSortedTransform over sorted Blocks: columns_to_sum (positions) summed, None: every integer column that is not a key; every
+    other column is the group's first row's.  -> (columns, first_rows)"""
+    blocks, width, description = _glue(blocks, description)
+    key_positions = {pos for pos, _, _ in description}
+    if columns_to_sum is None:
+        columns_to_sum = [p for p in range(width) if p not in key_positions and _dtype_of(blocks[0][p]).kind in "iu"]
+    columns_to_sum = [_position(p, width, "a summed column's") for p in columns_to_sum]
+    if any(p in key_positions for p in columns_to_sum):
+        raise ValueError("a key column cannot be summed")
+    out, first, _ = _folding_merge(blocks, width, description, {p: "sum" for p in columns_to_sum}, True, check)
+    return out, first
+
+
+def aggregating_merge(blocks, description, kinds, check: bool = True):
+    """AggregatingSortedTransform over SimpleAggregateFunction columns: kinds = {position: "sum" | "min" | "max" | "any" | "anyLast"};
+    keys and every column not named are `any`.  -> (columns, first_rows)"""
+    blocks, width, description = _glue(blocks, description)
+    key_positions = {pos for pos, _, _ in description}
+    kinds = {_position(p, width, "a folded column's"): k for p, k in dict(kinds).items()}
+    for p, k in kinds.items():
+        if k not in KINDS and k not in ("any", "anyLast"):
+            raise ValueError(f"column {p}: {k!r} is not one of sum, min, max, any, anyLast")
+        if p in key_positions:
+            raise ValueError(f"column {p} is a key column: it cannot be folded")
+    out, first, _ = _folding_merge(blocks, width, description, kinds, False, check)
+    return out, first

@@ -448,6 +448,53 @@ int chgpu_merge_sorted_permutation(chgpu_ctx * ctx, const chgpu_col * const * ke
 int chgpu_is_sorted(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, uint32_t n_keys,
                     const uint64_t * run_offsets, uint32_t n_runs, uint64_t * first_unsorted_row);
 
+/* The merges of MergeTree that FOLD rows of equal sorting key while they merge -- every background merge of the Replacing / Collapsing /
+   Summing / Aggregating engines and every SELECT .. FINAL.  Restated from
+   src/Processors/Merges/Algorithms/ReplacingSortedAlgorithm.cpp, src/Processors/Merges/Algorithms/CollapsingSortedAlgorithm.cpp,
+   src/Processors/Merges/Algorithms/SummingSortedAlgorithm.cpp and src/Processors/Merges/Algorithms/AggregatingSortedAlgorithm.cpp.
+   Common: the arguments up to n_runs and `flags` are those of chgpu_merge_sorted_permutation (1 to 8 numeric key columns over the glued
+   runs, at most 2^32 - 1 rows) with n_runs >= 1 -- one run is a merge of a single part -- and no limit; CHGPU_MERGE_CHECK_SORTED is
+   honoured.  Rows are visited in the order of that permutation, the merged order M: rows equal on every key come lowest concatenated row
+   number first.  A GROUP is a maximal stretch of M whose rows are equal on every key column, equal meaning equal order words
+   (hasEqualSortColumnsWith, compareAt(.., 1) == 0: -0.0 = +0.0, NaN = NaN).  Output rows keep M's order and every result is the same bit
+   for bit in every run.  An empty input gives empty columns.  Errors as chgpu_merge_sorted_permutation's, before any device work, and
+   those named below; a failed call leaves nothing allocated.
+
+   chgpu_merge_replacing: per group the LAST row in M among those with the greatest version (the reference compares with >= 0); without
+   a version column (NULL) the group's last row.  version: any integer column, compared in its own signedness; a Float version answers
+   NOT_IMPLEMENTED.  is_deleted_u8 (may be NULL; UInt8; without a version NOT_IMPLEMENTED): a value other than 0 or 1 answers
+   BAD_ARGUMENTS naming the lowest concatenated row that holds one; with cleanup != 0 a group whose selected row has is_deleted = 1 emits
+   nothing.  rows_out_u64: the concatenated row numbers of the selected rows.
+
+   chgpu_merge_collapsing: sign_i8 is Int8; a value other than +1 or -1 answers BAD_ARGUMENTS naming the lowest concatenated row that
+   holds it.  Per group cp = the number of +1 rows, cn = the number of -1 rows, first_negative = the first -1 row in M, last_positive =
+   the last +1 row in M, last_is_positive = the sign of the group's last row.  Nothing is emitted unless last_is_positive || cp != cn;
+   otherwise first_negative if cp <= cn, then last_positive if cp >= cn: 0, 1 or 2 rows, the negative one first.  rows_out_u64: their
+   concatenated row numbers.  The reference's log line for |cp - cn| > 1, only_positive_sign and VersionedCollapsing have no
+   counterpart here.
+
+   chgpu_merge_folding (Summing; Aggregating over SimpleAggregateFunction columns): value_cols[n_values] with kinds[n_values] of
+   CHGPU_FOLD_SUM (wrap-around addition in the column's own type, sumWithOverflow), CHGPU_FOLD_MIN, CHGPU_FOLD_MAX (in the column's
+   signedness).  Integer columns only; a Float value column answers NOT_IMPLEMENTED (the reference adds a group's rows one after another
+   and a parallel scan rounds differently); more than 8 value columns in one call answer NOT_IMPLEMENTED.  first_rows_u64: the
+   concatenated row number of each surviving group's first row in M -- keys and every column the engine does not fold are indexed with
+   it (any); last_rows_u64: the same for the group's last row (anyLast); res_cols[n_values]: one result column per value column, in the
+   value's type.  drop_zero != 0 is Summing's rule: a group is dropped when n_values > 0 and EVERY SUM result is 0 (with no SUM among the
+   kinds that holds for every group); with no value columns nothing is dropped.  SummingMergeTree is every value column SUM with
+   drop_zero; AggregatingMergeTree over simple functions is the given kinds without it.  Map / nested summing and AggregateFunction
+   state columns are out. */
+enum { CHGPU_FOLD_SUM = 0, CHGPU_FOLD_MIN = 1, CHGPU_FOLD_MAX = 2 };
+int chgpu_merge_replacing(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint,
+                          uint32_t n_keys, const uint64_t * run_offsets, uint32_t n_runs, uint32_t flags, const chgpu_col * version,
+                          const chgpu_col * is_deleted_u8, int32_t cleanup, chgpu_col ** rows_out_u64);
+int chgpu_merge_collapsing(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint,
+                           uint32_t n_keys, const uint64_t * run_offsets, uint32_t n_runs, uint32_t flags, const chgpu_col * sign_i8,
+                           chgpu_col ** rows_out_u64);
+int chgpu_merge_folding(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint,
+                        uint32_t n_keys, const uint64_t * run_offsets, uint32_t n_runs, uint32_t flags, const chgpu_col * const * value_cols,
+                        const int32_t * kinds, uint32_t n_values, int32_t drop_zero, chgpu_col ** first_rows_u64, chgpu_col ** last_rows_u64,
+                        chgpu_col ** res_cols);
+
 /* ================================================================================================
  * a11/a21 hashing & sharding  —  ColumnVector::getWeakHash32 (ColumnVector.cpp:78-95), ConcurrentHashJoin
  * hashToSelector (src/Interpreters/ConcurrentHashJoin.cpp:426-440), IColumn::scatter (src/Columns/IColumn.cpp:245-269).

@@ -78,7 +78,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--out", default="")
+    ap.add_argument("--keysets", default=",".join(KEYSETS), help="comma-separated subset of " + ", ".join(KEYSETS))
+    ap.add_argument("--run-counts", default=",".join(str(k) for k in RUN_COUNTS), help="comma-separated run counts (the LIMIT 10 shape runs with 8)")
     args = ap.parse_args()
+    keysets = {name: KEYSETS[name] for name in args.keysets.split(",")}
+    run_counts = tuple(int(k) for k in args.run_counts.split(","))
 
     import torch
 
@@ -116,7 +120,7 @@ def main():
                 ch.concat([copy_src])
         return run, reps * 2 * chunk
 
-    for name, (dtypes, spec) in KEYSETS.items():
+    for name, (dtypes, spec) in keysets.items():
         key_sizes = [np.dtype(d).itemsize for d in dtypes]
         # the small check against numpy, K = 8 and 1024
         small = make_columns(rng, dtypes, args.check_rows)
@@ -129,7 +133,7 @@ def main():
             assert np.array_equal(got, want), f"{name} K={k}: the merge differs from numpy's stable lexsort at {args.check_rows} rows"
         del small_dev
         raw = [ctx.upload(c) for c in make_columns(rng, dtypes, args.rows)]
-        for k, limit in [(k, 0) for k in RUN_COUNTS] + [(8, 10)]:
+        for k, limit in [(k, 0) for k in run_counts] + ([(8, 10)] if 8 in run_counts else []):
             label = f"{name}_k{k}" + (f"_limit{limit}" if limit else "")
             cols, offs = sorted_runs(raw, spec, k, args.rows)
             cut_rows = sum(min(b - a, limit) if limit else b - a for a, b in zip(offs, offs[1:]))
