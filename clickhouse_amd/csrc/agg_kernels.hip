@@ -1173,23 +1173,8 @@ __global__ __launch_bounds__(GBP_THREADS) void k_gb_scatter(const void * __restr
         // 2. exclusive scan of tile_cnt[P] -> tile_off[P]   (P <= 2 * threads)
         {
             const u32 e0 = threadIdx.x * 2, e1 = e0 + 1;
-            const u32 c0 = e0 < P ? tile_cnt[e0] : 0, c1 = e1 < P ? tile_cnt[e1] : 0;
-            u32 v = c0 + c1;
-            const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-            u32 inc = v;
-#pragma unroll
-            for (int dlt = 1; dlt < 64; dlt <<= 1)
-            {
-                const u32 o = __shfl_up(inc, dlt, WAVE);
-                if (lane >= (u32)dlt)
-                    inc += o;
-            }
-            if (lane == 63)
-                wave_tot[wave] = inc;
-            __syncthreads();
-            u32 base = inc - v;
-            for (u32 w = 0; w < wave; ++w)
-                base += wave_tot[w];
+            u32 c0, c1;
+            const u32 base = rp_scan_counters<false>(tile_cnt, P, wave_tot, c0, c1);
             // the same thread that scanned partition p also advances its cursor and clears its counter for the next tile:
             // step 1 of the next tile only starts after the barrier below, and nobody reads cursor[] again in this tile
             if (e0 < P)

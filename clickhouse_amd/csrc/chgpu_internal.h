@@ -278,15 +278,6 @@ __device__ __forceinline__ u64 wave_reduce_max_u64(u64 v)
     return v; // valid in lane 0
 }
 
-// the sum in EVERY lane (butterfly), for a wave that goes on to branch on it
-__device__ __forceinline__ u32 wave_allreduce_add_u32(u32 v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        v += __shfl_xor(v, d, WAVE);
-    return v;
-}
-
 // The order key of min / max (agg_kernels.hip has the whole story): `bits` is the value widened to 64 bits -- integers sign- or
 // zero-extended, Float32 after its exact widening to Float64 -- and the key is an unsigned integer that sorts like the value.
 __device__ __host__ __forceinline__ u64 agg_order_key(u64 bits, int type)

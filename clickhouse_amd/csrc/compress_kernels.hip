@@ -13,7 +13,7 @@
 //                   method NONE (0x02): payload copied as is
 //   k_delta_decode  the Delta stage of CODEC(Delta, LZ4): running sums of 1/2/4/8-byte elements, wave scan + uniform carry
 // Algorithmic bytes: compressed size read + decompressed size written (match sources are re-reads of fresh output: L1/L2).
-#include "chgpu_internal.h"
+#include "block_scan.h"
 
 #include <memory>
 
@@ -366,6 +366,8 @@ __device__ __forceinline__ WidthSkip width_skip(const CodecIo & io)
 template <typename T>
 __device__ __forceinline__ void delta_frame(const u8 * __restrict__ pay, u32 n_el, u8 * __restrict__ out, u32 lane)
 {
+    // a narrow T is summed in 32 bits: its low bits are the wrap-around sum of its own width
+    typedef typename std::conditional<sizeof(T) == 8, AddU64, AddU32>::type Add;
     T carry = 0;
     for (u32 base = 0; base < n_el; base += 64)
     {
@@ -373,26 +375,11 @@ __device__ __forceinline__ void delta_frame(const u8 * __restrict__ pay, u32 n_e
         T v = 0;
         if (i < n_el)
             __builtin_memcpy(&v, pay + (size_t)i * sizeof(T), sizeof(T));
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1)
-        {
-            T o;
-            if constexpr (sizeof(T) == 8)
-                o = (T)(((u64)__shfl_up((u32)((u64)v >> 32), d, 64) << 32) | __shfl_up((u32)(u64)v, d, 64));
-            else
-                o = (T)__shfl_up((u32)v, d, 64);
-            if (lane >= (u32)d)
-                v += o;
-        }
+        v = (T)wave_scan_inclusive<Add>((typename Add::T)v, lane);
         v += carry;
         if (i < n_el)
             __builtin_memcpy(out + (size_t)i * sizeof(T), &v, sizeof(T));
-        T last;
-        if constexpr (sizeof(T) == 8)
-            last = (T)(((u64)__shfl((u32)((u64)v >> 32), 63, 64) << 32) | __shfl((u32)(u64)v, 63, 64));
-        else
-            last = (T)__shfl((u32)v, 63, 64);
-        carry = last; // lanes beyond n_el hold the running sum too (their delta is 0)
+        carry = (T)shfl_lane((typename Add::T)v, 63); // lanes beyond n_el hold the running sum too (their delta is 0)
     }
 }
 

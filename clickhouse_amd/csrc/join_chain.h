@@ -326,12 +326,12 @@ __global__ __launch_bounds__(JCT_THREADS) void k_chain_tail(ChainTailArgs a, con
                     word &= ~(1ull << bit);
         }
         // steps over an exact bitmap while many rows are alive: the unit's keys read whole
-        u32 total = wave_allreduce_add_u32((u32)__popcll(word));
+        u32 total = wave_reduce_all<AddU32>((u32)__popcll(word));
         while (s < a.n_steps && whole && total >= JCT_COAL_MIN && a.s[s].dense && (a.s[s].key_type == CHGPU_U32 || a.s[s].key_type == CHGPU_I32)
                && ((uintptr_t)a.s[s].keys & 15) == 0 && ((uintptr_t)a.s[s].null_map & 3) == 0)
         {
             word = jc_tail_step_coalesced(a.s[s], word, row0, lane);
-            total = wave_allreduce_add_u32((u32)__popcll(word));
+            total = wave_reduce_all<AddU32>((u32)__popcll(word));
             ++s;
         }
         sv[lane] = 0;
@@ -346,14 +346,7 @@ __global__ __launch_bounds__(JCT_THREADS) void k_chain_tail(ChainTailArgs a, con
                 const u64 wpart = n_pass == 1 ? word : (word >> (16 * pass)) & 0xffffull;
                 const u32 bit0 = n_pass == 1 ? 0u : 16u * pass;
                 const u32 c = (u32)__popcll(wpart);
-                u32 incl = c;
-#pragma unroll
-                for (int d = 1; d < 64; d <<= 1)
-                {
-                    const u32 o = __shfl_up(incl, d, 64);
-                    if ((int)lane >= d)
-                        incl += o;
-                }
+                const u32 incl = wave_scan_inclusive<AddU32>(c, lane);
                 const u32 ptotal = __shfl(incl, 63, 64);
                 u32 pos = incl - c;
                 for (u64 w = wpart; w; w &= w - 1)
@@ -413,7 +406,7 @@ __global__ __launch_bounds__(JCT_THREADS) void k_chain_tail(ChainTailArgs a, con
         }
         const u64 out = ((u64)sv[2 * lane + 1] << 32) | sv[2 * lane]; // rows row0 + 64 * lane ... + 63
         mask_words[unit * 64 + lane] = out;
-        const u32 cnt = wave_allreduce_add_u32((u32)__popcll(out)); // (only lane 0 needs it, but wave_reduce_add_u32 costs this kernel 6 VGPRs)
+        const u32 cnt = wave_reduce_all<AddU32>((u32)__popcll(out)); // (only lane 0 needs it, but wave_reduce_add_u32 costs this kernel 6 VGPRs)
         if (lane == 0)
             unit_counts[unit] = cnt;
     }
@@ -478,14 +471,7 @@ __global__ __launch_bounds__(JCT_THREADS) void k_chain_indexes(const u64 * __res
         if (!indexes)
             continue;
         const u32 c = (u32)__popcll(word);
-        u32 incl = c;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1)
-        {
-            const u32 o = __shfl_up(incl, d, 64);
-            if ((int)lane >= d)
-                incl += o;
-        }
+        const u32 incl = wave_scan_inclusive<AddU32>(c, lane);
         const u32 total = __shfl(incl, 63, 64);
         if (total == 0)
             continue;

@@ -28,7 +28,7 @@
 // Shared with group_array_kernels.hip and written once elsewhere: the rank plan's head ballots, counts kernel, ranked-item loop and
 // tile scan (tile_rank.h), its pass planner and pass loop (pair_host.h, pair_store.h); the numbered allocations and the call's
 // temporaries are pair_pool.h.  k_lb_compact and k_lb_resolve rank lane-consecutive rows, another layout, and stay as they are.
-#include "chgpu_internal.h"
+#include "block_scan.h"
 
 #include "pair_store.h"
 #include "tile_rank.h"
@@ -63,14 +63,6 @@ struct alignas(16) LbSlots
 {
     u32 v[LB_V];
 };
-
-__device__ __forceinline__ u32 lb_wave_or(u32 v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        v |= __shfl_xor(v, d, WAVE);
-    return v;
-}
 
 // Rows are addressed by v = row - row_begin + lead, where `lead` (< 4) makes v = 0 fall on a 4-element boundary of the key column's
 // memory; kp / fp point at the range's first row.  slot_out[v]: the live row's slot, LB_MISSING, or LB_NONE.
@@ -196,8 +188,8 @@ __global__ __launch_bounds__(LB_T) void k_lb_resolve(const K * __restrict__ kp, 
     entered = wave_reduce_add_u32(entered);
     live = wave_reduce_add_u32(live);
     missing = wave_reduce_add_u32(missing);
-    ob = lb_wave_or(ob);
-    nb = lb_wave_or(nb);
+    ob = wave_reduce_all<OrU32>(ob);
+    nb = wave_reduce_all<OrU32>(nb);
     if (lane_id() == 0)
     {
         atomicAdd(&s_acc[0], entered);

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(MRG_THREADS) void k_merge_is_sorted(MergeKeys keys,
             }
         }
     }
-    const u64 m = mrg_block_min(found, lds);
+    const u64 m = block_reduce<MinU64>(found, lds);
     if (threadIdx.x == 0)
         partial[blockIdx.x] = m;
 }
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(MRG_THREADS) void k_merge_min(const u64 * __restric
     u64 v = ~0ull;
     for (u32 i = threadIdx.x; i < n; i += MRG_THREADS)
         v = partial[i] < v ? partial[i] : v;
-    const u64 m = mrg_block_min(v, lds);
+    const u64 m = block_reduce<MinU64>(v, lds);
     if (threadIdx.x == 0)
         out[0] = m;
 }

@@ -1,9 +1,9 @@
 // merge_keys.h — what merge_kernels.hip shares with the operators that sit on its merged order (merge_fold_kernels.hip): the sort
-// description as the kernels take it, a key column's order word, the block minimum of the "lowest offending row" checks, and the host
-// entry to the merged order itself.  Device code except for the declarations at the end.
+// description as the kernels take it, a key column's order word, and the host entry to the merged order itself (the block minimum of the
+// "lowest offending row" checks is block_scan.h's block_reduce<MinU64>).  Device code except for the declarations at the end.
 #pragma once
 
-#include "chgpu_internal.h"
+#include "block_scan.h"
 #include "merge_host.h"
 #include "pair_pool.h"
 #include "sort_key.h"
@@ -43,25 +43,6 @@ __device__ __forceinline__ u64 mrg_key(const MergeKeys & keys, u32 j, u64 row)
         case CHGPU_F64: return mrg_key_of<double>(d, row, desc, hint);
         default: return mrg_key_of<float>(d, row, desc, hint);
     }
-}
-
-// the minimum of v over a workgroup of MRG_THREADS, in every thread
-__device__ __forceinline__ u64 mrg_block_min(u64 v, u64 * lds /* MRG_THREADS / WAVE */)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-    {
-        const u64 o = shfl_down_u64(v, d);
-        v = o < v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0)
-        lds[threadIdx.x >> 6] = v;
-    __syncthreads();
-    u64 m = lds[0];
-    for (u32 w = 1; w < MRG_THREADS / WAVE; ++w)
-        m = lds[w] < m ? lds[w] : m;
-    __syncthreads();
-    return m;
 }
 
 // ---- merge_kernels.hip, for the operators over the merged order ----

@@ -11,7 +11,7 @@
 // (crc is GF(2)-affine in the message).  The partition is a stable three-pass split (per-tile histogram -> scan ->
 // ordered scatter through LDS, see k_part_scatter_lds), so each shard's rows keep their input order exactly like the
 // reference's sequential insertFrom loop.
-#include "chgpu_internal.h"
+#include "block_scan.h"
 
 #include <algorithm>
 
@@ -277,14 +277,7 @@ __global__ __launch_bounds__(PT) void k_part_scatter_lds(SelSrc sel, u64 n, u32 
                     tot += c;
                 }
             }
-            u32 inc = tot;
-#pragma unroll
-            for (int dlt = 1; dlt < 64; dlt <<= 1)
-            {
-                const u32 o = __shfl_up(inc, dlt, WAVE);
-                if (lane >= (u32)dlt)
-                    inc += o;
-            }
+            const u32 inc = wave_scan_inclusive<AddU32>(tot, lane);
             if (lane == 63)
                 wave_sum[wave] = inc;
             __syncthreads();

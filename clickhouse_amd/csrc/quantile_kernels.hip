@@ -22,7 +22,7 @@
 // is pair_store.h / group_table.h; the store itself (PairStore: reserve, merge's append, export of the keys) is pair_store.h too, shared
 // with group_array_kernels.hip; pool memory, the numbered allocations and a call's temporaries are pair_pool.h.  Its own: the append
 // kernel, the value export, the row limit in front of the shared reserve.
-#include "chgpu_internal.h"
+#include "block_scan.h"
 
 #include "pair_store.h"
 #include "quantile_host.h"
@@ -528,14 +528,7 @@ __global__ __launch_bounds__(QT_T) void k_qt_narrow(const QtLarge * __restrict__
         c[k] = h[lane * 4 + k];
         s += c[k];
     }
-    u32 incl = s;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-        const u32 o = __shfl_up(incl, d, 64);
-        if (lane >= (u32)d)
-            incl += o;
-    }
+    const u32 incl = wave_scan_inclusive<AddU32>(s, lane);
     const u64 e = li * n_levels + l;
     const u64 r = rank[e];
     const u64 hit = __ballot((u64)incl > r);

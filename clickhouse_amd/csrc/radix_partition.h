@@ -2,11 +2,32 @@
 // (agg_kernels.hip: rows -> partitions that fit an LDS table) and the join probe (join_kernels.hip: probe keys -> table regions that
 // fit an XCD's L2).  The partition function is a functor so both callers run the same code.
 #pragma once
-#include "chgpu_internal.h"
+#include "block_scan.h"
 
 static constexpr u32 RP_THREADS = 1024;
 static constexpr u32 RP_MAX_P = 1024;
 static constexpr u32 RP_SCATTER_SLACK = 12288; // rows of slack k_rp_scatter needs behind each of its output arrays
+
+// Exclusive scan of a tile's counters cnt[0 .. P) (WITH_DUMMY: cnt[0 .. P], the dummy partition last), two per thread: thread t owns
+// e0 = 2 t and e1 = e0 + 1 (counters <= 2 * threads).  c0 / c1: their counts, 0 past the end; returns where e0's rows start inside the
+// tile (e1's: + c0).  wave_tot: one word per wave.  One barrier inside; the caller's own stand before the call and behind its epilogue.
+template <bool WITH_DUMMY>
+__device__ __forceinline__ u32 rp_scan_counters(const u32 * cnt, u32 P, u32 * wave_tot, u32 & c0, u32 & c1)
+{
+    const u32 e0 = threadIdx.x * 2, e1 = e0 + 1;
+    c0 = (WITH_DUMMY ? e0 <= P : e0 < P) ? cnt[e0] : 0;
+    c1 = (WITH_DUMMY ? e1 <= P : e1 < P) ? cnt[e1] : 0;
+    const u32 v = c0 + c1;
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u32 inc = wave_scan_inclusive<AddU32>(v, lane);
+    if (lane == 63)
+        wave_tot[wave] = inc;
+    __syncthreads();
+    u32 off = inc - v;
+    for (u32 w = 0; w < wave; ++w)
+        off += wave_tot[w];
+    return off;
+}
 
 // Same histogram with 16-byte nontemporal key loads (4- and 8-byte keys whose first row is 16-byte aligned): four loads
 // per lane are issued before the first LDS atomic.
@@ -143,23 +164,8 @@ __global__ __launch_bounds__(RP_THREADS) void k_rp_scatter(const KT * __restrict
     auto step_scan = [&]() {
         __syncthreads();
         const u32 e0 = threadIdx.x * 2, e1 = e0 + 1;
-        const u32 c0 = e0 <= P ? tile_cnt[e0] : 0, c1 = e1 <= P ? tile_cnt[e1] : 0;
-        const u32 v = c0 + c1;
-        const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        u32 inc = v;
-#pragma unroll
-        for (int dlt = 1; dlt < 64; dlt <<= 1)
-        {
-            const u32 o = __shfl_up(inc, dlt, 64);
-            if (lane >= (u32)dlt)
-                inc += o;
-        }
-        if (lane == 63)
-            wave_tot[wave] = inc;
-        __syncthreads();
-        u32 off = inc - v;
-        for (u32 w = 0; w < wave; ++w)
-            off += wave_tot[w];
+        u32 c0, c1;
+        const u32 off = rp_scan_counters<true>(tile_cnt, P, wave_tot, c0, c1);
         if (e0 <= P)
         {
             tile_off[e0] = off;
@@ -370,23 +376,8 @@ __global__ __launch_bounds__(THREADS) void k_rp_tilesort(const KT * __restrict__
     auto step_scan = [&]() {
         __syncthreads();
         const u32 e0 = threadIdx.x * 2, e1 = e0 + 1;
-        const u32 c0 = e0 <= P ? tile_cnt[e0] : 0, c1 = e1 <= P ? tile_cnt[e1] : 0;
-        const u32 v = c0 + c1;
-        const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        u32 inc = v;
-#pragma unroll
-        for (int dlt = 1; dlt < 64; dlt <<= 1)
-        {
-            const u32 o = __shfl_up(inc, dlt, 64);
-            if (lane >= (u32)dlt)
-                inc += o;
-        }
-        if (lane == 63)
-            wave_tot[wave] = inc;
-        __syncthreads();
-        u32 off = inc - v;
-        for (u32 w = 0; w < wave; ++w)
-            off += wave_tot[w];
+        u32 c0, c1;
+        const u32 off = rp_scan_counters<true>(tile_cnt, P, wave_tot, c0, c1);
         if (e0 <= P)
         {
             tile_off[e0] = off;
@@ -559,23 +550,8 @@ __global__ __launch_bounds__(THREADS) void k_rp_tilesort_keys(const u64 * __rest
     auto step_scan = [&]() {
         __syncthreads();
         const u32 e0 = threadIdx.x * 2, e1 = e0 + 1;
-        const u32 c0 = e0 <= P ? tile_cnt[e0] : 0, c1 = e1 <= P ? tile_cnt[e1] : 0;
-        const u32 v = c0 + c1;
-        const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        u32 inc = v;
-#pragma unroll
-        for (int dlt = 1; dlt < 64; dlt <<= 1)
-        {
-            const u32 o = __shfl_up(inc, dlt, 64);
-            if (lane >= (u32)dlt)
-                inc += o;
-        }
-        if (lane == 63)
-            wave_tot[wave] = inc;
-        __syncthreads();
-        u32 off = inc - v;
-        for (u32 w = 0; w < wave; ++w)
-            off += wave_tot[w];
+        u32 c0, c1;
+        const u32 off = rp_scan_counters<true>(tile_cnt, P, wave_tot, c0, c1);
         if (e0 <= P)
         {
             tile_off[e0] = off;

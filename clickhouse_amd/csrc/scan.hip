@@ -1,42 +1,11 @@
 // scan.hip — device-wide prefix sums (u32 counts -> u64 offsets) used by filter compaction, scatter and join output.
 // Reduce-then-scan in three launches: tile sums -> scan of tile sums (one workgroup) -> per-tile scan + offset.
 // HBM traffic: 4 B/elem (pass 1) + 4 B read + 8 B write (pass 3); the tile-sum array is n/2048 u64.
-#include "chgpu_internal.h"
+#include "block_scan.h"
 
 static constexpr int SCAN_THREADS = 256;
 static constexpr int SCAN_ITEMS = 8;
 static constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
-
-__device__ __forceinline__ u64 block_reduce_u64(u64 v, u64 * lds /* >= 4 */)
-{
-    v = wave_reduce_add_u64(v);
-    const u32 wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-        lds[wave] = v;
-    __syncthreads();
-    u64 r = 0;
-    const u32 n_waves = blockDim.x >> 6;
-    for (u32 w = 0; w < n_waves; ++w)
-        r += lds[w];
-    __syncthreads();
-    return r; // every thread
-}
-
-// inclusive wave scan (Hillis-Steele over 64 lanes)
-__device__ __forceinline__ u64 wave_scan_inclusive_u64(u64 v)
-{
-    const u32 lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-        u32 lo = __shfl_up((u32)v, d, WAVE);
-        u32 hi = __shfl_up((u32)(v >> 32), d, WAVE);
-        u64 o = ((u64)hi << 32) | lo;
-        if (lane >= (u32)d)
-            v += o;
-    }
-    return v;
-}
 
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_tile_sums(const u32 * __restrict__ in, u64 n, u64 * __restrict__ tile_sums)
 {
@@ -50,7 +19,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_tile_sums(const u32 * __r
         if (i < n)
             s += in[i];
     }
-    s = block_reduce_u64(s, lds);
+    s = block_reduce<AddU64>(s, lds);
     if (threadIdx.x == 0)
         tile_sums[blockIdx.x] = s;
 }
@@ -58,33 +27,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_tile_sums(const u32 * __r
 // one workgroup: exclusive scan of tile_sums in place, total -> *total
 __global__ __launch_bounds__(1024) void k_scan_tile_offsets(u64 * __restrict__ tile_sums, u64 n_tiles, u64 * __restrict__ total)
 {
-    __shared__ u64 wave_tot[16];
-    __shared__ u64 carry_s;
+    const u64 all = block_scan_array<AddU64, false>(tile_sums, tile_sums, n_tiles, 0);
     if (threadIdx.x == 0)
-        carry_s = 0;
-    __syncthreads();
-    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (u64 base = 0; base < n_tiles; base += 1024)
-    {
-        u64 i = base + threadIdx.x;
-        u64 v = i < n_tiles ? tile_sums[i] : 0;
-        u64 inc = wave_scan_inclusive_u64(v);
-        if (lane == 63)
-            wave_tot[wave] = inc;
-        __syncthreads();
-        u64 woff = 0;
-        for (u32 w = 0; w < wave; ++w)
-            woff += wave_tot[w];
-        u64 carry = carry_s;
-        if (i < n_tiles)
-            tile_sums[i] = carry + woff + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 1023)
-            carry_s = carry + woff + inc;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0)
-        *total = carry_s;
+        *total = all;
 }
 
 template <bool INCLUSIVE>
@@ -126,8 +71,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_apply(const u32 * __restr
             s += v[k];
         }
     }
-    u64 inc = wave_scan_inclusive_u64(s);
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 inc = wave_scan_inclusive<AddU64>(s, lane);
     if (lane == 63)
         wave_tot[wave] = inc;
     __syncthreads();

@@ -24,7 +24,7 @@
 // + ~50 B per row of flags and scans.
 //
 // chgpu_string_index has the shape of chgpu_string_filter: sizes gathered through the indexes, one scan, one move pass.
-#include "chgpu_internal.h"
+#include "block_scan.h"
 
 #include <algorithm>
 
@@ -65,17 +65,6 @@ __global__ __launch_bounds__(256) void k_ss_init(const u64 * __restrict__ perm_i
     }
 }
 
-__device__ __forceinline__ u64 ss_wave_min_u64(u64 v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-    {
-        const u64 o = ((u64)__shfl_xor((u32)(v >> 32), d, WAVE) << 32) | __shfl_xor((u32)v, d, WAVE);
-        v = o < v ? o : v;
-    }
-    return v; // in every lane
-}
-
 // Every wave folds what its lanes found for one segment into ONE atomicMin: in round 0 all rows belong to one segment, and a lane-wise
 // atomicMin would queue every resident lane of the first sweep on a single address.
 __global__ __launch_bounds__(256) void k_ss_lcp(const u64 * __restrict__ offsets, const u8 * __restrict__ chars, const u64 * __restrict__ row,
@@ -110,7 +99,7 @@ __global__ __launch_bounds__(256) void k_ss_lcp(const u64 * __restrict__ offsets
             const u32 leader = (u32)__ffsll((unsigned long long)todo) - 1;
             const u32 ls = __shfl(s, leader, WAVE);
             const bool mine = lower && s == ls;
-            const u64 least = ss_wave_min_u64(mine ? k : SS_NONE);
+            const u64 least = wave_reduce_all<MinU64>(mine ? k : SS_NONE);
             if (lane == leader)
                 atomicMin((unsigned long long *)&t.adv[ls], (unsigned long long)least);
             lower = lower && !mine;

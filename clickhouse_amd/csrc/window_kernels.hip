@@ -17,19 +17,15 @@
 //              k_win_out_pick<W> (first_value / last_value / lagInFrame / leadInFrame): row i, its bounds, the scan array -> the result;
 //              the frame itself is win_frame_of (window_host.h), the code the host driver tests
 // The handle's pool memory and a call's temporaries are pair_pool.h (PairMem, PairAllocs without a refusal hook, PairTemps).
-#include "chgpu_internal.h"
+#include "block_scan.h"
 #include "pair_pool.h"
 #include "window_host.h"
 
 static constexpr u32 WIN_INF = 0xFFFFFFFFu;
 
 // ---------------------------------------------------------------------------------------------
-// scans inside a workgroup
+// the scans inside a workgroup are block_scan.h's; the one Op of this file's own:
 // ---------------------------------------------------------------------------------------------
-struct WinMaxU32 { typedef u32 T; static __device__ __forceinline__ T id() { return 0; } static __device__ __forceinline__ T comb(T a, T b) { return a > b ? a : b; } };
-struct WinMinU32 { typedef u32 T; static __device__ __forceinline__ T id() { return WIN_INF; } static __device__ __forceinline__ T comb(T a, T b) { return a < b ? a : b; } };
-struct WinAddU32 { typedef u32 T; static __device__ __forceinline__ T id() { return 0; } static __device__ __forceinline__ T comb(T a, T b) { return a + b; } };
-struct WinAddU64 { typedef u64 T; static __device__ __forceinline__ T id() { return 0; } static __device__ __forceinline__ T comb(T a, T b) { return a + b; } };
 // a running maximum that starts again at every element whose flag is set: (a then b) = b where b starts a segment, else the larger
 struct WinSeg { u64 v; u32 f; };
 struct WinSegMax
@@ -39,74 +35,7 @@ struct WinSegMax
     static __device__ __forceinline__ T comb(T a, T b) { return WinSeg{b.f ? b.v : (a.v > b.v ? a.v : b.v), a.f | b.f}; }
 };
 
-__device__ __forceinline__ u32 win_shfl_up(u32 v, int d) { return __shfl_up(v, d, WAVE); }
-__device__ __forceinline__ u64 win_shfl_up(u64 v, int d) { return ((u64)__shfl_up((u32)(v >> 32), d, WAVE) << 32) | __shfl_up((u32)v, d, WAVE); }
-__device__ __forceinline__ WinSeg win_shfl_up(WinSeg v, int d) { return WinSeg{win_shfl_up(v.v, d), win_shfl_up(v.f, d)}; }
-
-// Exclusive scan of one value per thread over the workgroup, in thread order (blockDim.x a multiple of 64, at most 1024).  Returns the
-// combination of the values of all threads before this one; *total (when given) is the combination of all.  lds: 16 elements.
-template <typename Op>
-__device__ __forceinline__ typename Op::T win_block_scan(typename Op::T v, typename Op::T * lds, typename Op::T * total = nullptr)
-{
-    typedef typename Op::T T;
-    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    T inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1)
-    {
-        const T o = win_shfl_up(inc, d);
-        if (lane >= (u32)d)
-            inc = Op::comb(o, inc);
-    }
-    T exc = win_shfl_up(inc, 1);
-    if (lane == 0)
-        exc = Op::id();
-    __syncthreads(); // (lds may still be read by an earlier call)
-    if (lane == 63)
-        lds[wave] = inc;
-    __syncthreads();
-    T before = Op::id();
-    for (u32 w = 0; w < wave; ++w)
-        before = Op::comb(before, lds[w]);
-    if (total)
-    {
-        T all = before;
-        for (u32 w = wave; w < n_waves; ++w)
-            all = Op::comb(all, lds[w]);
-        *total = all;
-    }
-    return Op::comb(before, exc);
-}
-
-// One workgroup: in[0 .. n) -> out[j] = the combination of in[0 .. j) (REVERSE: of in(j .. n), taken from the far end), WIN_PASS
-// elements a pass, the carry of the passes in LDS.  Returns the combination of all in every thread.
-template <typename Op, bool REVERSE>
-__device__ __forceinline__ typename Op::T win_scan_array(const typename Op::T * in, typename Op::T * out, u64 n, typename Op::T first)
-{
-    typedef typename Op::T T;
-    __shared__ T lds[16];
-    __shared__ T carry_s;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        carry_s = first;
-    __syncthreads();
-    for (u64 base = 0; base < n; base += WIN_PASS)
-    {
-        const u64 q = base + threadIdx.x;
-        const u64 j = REVERSE ? n - 1 - q : q;
-        const T v = q < n ? in[j] : Op::id();
-        T total;
-        const T exc = win_block_scan<Op>(v, lds, &total);
-        const T carry = carry_s;
-        if (q < n)
-            out[j] = Op::comb(carry, exc);
-        __syncthreads();
-        if (threadIdx.x == 0)
-            carry_s = Op::comb(carry, total);
-        __syncthreads();
-    }
-    return carry_s;
-}
+__device__ __forceinline__ WinSeg shfl_up(WinSeg v, int d) { return WinSeg{shfl_up(v.v, d), shfl_up(v.f, d)}; }
 
 // ---------------------------------------------------------------------------------------------
 // heads
@@ -148,16 +77,6 @@ __device__ __forceinline__ bool win_key_equal(const void * p, u32 width, bool is
 // the six partials of a tile, part[k * n_tiles + tile]
 enum { WIN_P_LAST_P = 0, WIN_P_LAST_G, WIN_P_FIRST_P, WIN_P_FIRST_G, WIN_P_COUNT_P, WIN_P_COUNT_G, WIN_P_KINDS };
 
-// the combination over the wave, in every lane
-template <typename Op>
-__device__ __forceinline__ u32 win_wave_reduce(u32 v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-        v = Op::comb(v, (u32)__shfl_xor(v, d, WAVE));
-    return v;
-}
-
 // One workgroup per tile.  flags is whole tiles long: the rows past `n` of the last tile get 0.
 __global__ __launch_bounds__(WIN_THREADS) void k_win_heads(WinKeys keys, u64 n, u64 n_tiles, u8 * __restrict__ flags, u32 * __restrict__ part)
 {
@@ -198,12 +117,12 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_heads(WinKeys keys, u64 n, 
         }
         s_flags[k * WIN_THREADS + threadIdx.x] = (u8)f;
     }
-    last_p = win_wave_reduce<WinMaxU32>(last_p);
-    last_g = win_wave_reduce<WinMaxU32>(last_g);
-    first_p = win_wave_reduce<WinMinU32>(first_p);
-    first_g = win_wave_reduce<WinMinU32>(first_g);
-    count_p = win_wave_reduce<WinAddU32>(count_p);
-    count_g = win_wave_reduce<WinAddU32>(count_g);
+    last_p = wave_reduce_all<MaxU32>(last_p);
+    last_g = wave_reduce_all<MaxU32>(last_g);
+    first_p = wave_reduce_all<MinU32>(first_p);
+    first_g = wave_reduce_all<MinU32>(first_g);
+    count_p = wave_reduce_all<AddU32>(count_p);
+    count_g = wave_reduce_all<AddU32>(count_g);
     if ((threadIdx.x & 63) == 0)
     {
         const u32 wave = threadIdx.x >> 6;
@@ -221,7 +140,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_heads(WinKeys keys, u64 n, 
         const u32 k = threadIdx.x;
         u32 r = red[k][0];
         for (u32 w = 1; w < WIN_THREADS / 64; ++w)
-            r = k <= WIN_P_LAST_G ? WinMaxU32::comb(r, red[k][w]) : k <= WIN_P_FIRST_G ? WinMinU32::comb(r, red[k][w]) : r + red[k][w];
+            r = k <= WIN_P_LAST_G ? MaxU32::comb(r, red[k][w]) : k <= WIN_P_FIRST_G ? MinU32::comb(r, red[k][w]) : r + red[k][w];
         part[k * n_tiles + blockIdx.x] = r;
     }
 }
@@ -234,12 +153,12 @@ __global__ __launch_bounds__(WIN_PASS) void k_win_scan_partials(u32 * __restrict
     const u32 kind = blockIdx.x;
     u32 * a = part + kind * n_tiles;
     if (kind <= WIN_P_LAST_G)
-        win_scan_array<WinMaxU32, false>(a, a, n_tiles, 0);
+        block_scan_array<MaxU32, false>(a, a, n_tiles, 0);
     else if (kind <= WIN_P_FIRST_G)
-        win_scan_array<WinMinU32, true>(a, a, n_tiles, rows);
+        block_scan_array<MinU32, true>(a, a, n_tiles, rows);
     else
     {
-        const u32 total = win_scan_array<WinAddU32, false>(a, a, n_tiles, 0);
+        const u32 total = block_scan_array<AddU32, false>(a, a, n_tiles, 0);
         if (threadIdx.x == 0)
             totals[kind - WIN_P_COUNT_P] = total;
     }
@@ -253,7 +172,7 @@ enum { WIN_M_FWD_MAX = 0, WIN_M_BWD_MIN = 1, WIN_M_FWD_COUNT = 2 };
 template <int MODE>
 __global__ __launch_bounds__(WIN_THREADS) void k_win_bound(const u8 * __restrict__ flags, u32 bit, const u32 * __restrict__ carry, u32 * __restrict__ out)
 {
-    typedef typename std::conditional<MODE == WIN_M_FWD_MAX, WinMaxU32, typename std::conditional<MODE == WIN_M_BWD_MIN, WinMinU32, WinAddU32>::type>::type Op;
+    typedef typename std::conditional<MODE == WIN_M_FWD_MAX, MaxU32, typename std::conditional<MODE == WIN_M_BWD_MIN, MinU32, AddU32>::type>::type Op;
     __shared__ u32 lds[16];
     const u64 tile0 = (u64)blockIdx.x * WIN_TILE;
     // backward: thread 0 owns the LAST eight rows of the tile, so that the scan in thread order runs from the far end
@@ -269,7 +188,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_bound(const u8 * __restrict
         v[k] = MODE == WIN_M_FWD_COUNT ? (head ? 1u : 0u) : head ? (u32)(r0 + k) : Op::id();
         mine = Op::comb(mine, v[k]);
     }
-    u32 run = Op::comb(carry[blockIdx.x], win_block_scan<Op>(mine, lds));
+    u32 run = Op::comb(carry[blockIdx.x], block_scan_exclusive<Op>(mine, lds));
     u32 o[WIN_ITEMS];
     if (MODE == WIN_M_BWD_MIN)
     {
@@ -326,15 +245,14 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_tile_sums(const void * __re
         if (i < n)
             s += win_load_bits(x, type, i);
     }
-    u64 total;
-    win_block_scan<WinAddU64>(s, lds, &total);
+    const u64 total = block_reduce<AddU64>(s, lds);
     if (threadIdx.x == 0)
         tile_sums[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(WIN_PASS) void k_win_scan_tile_sums(u64 * __restrict__ tile_sums, u64 n_tiles)
 {
-    win_scan_array<WinAddU64, false>(tile_sums, tile_sums, n_tiles, 0);
+    block_scan_array<AddU64, false>(tile_sums, tile_sums, n_tiles, 0);
 }
 
 // P[0] = 0, P[i + 1] = x[0] + .. + x[i] (wrap-around).  The tile goes through LDS both ways, so that memory sees consecutive addresses
@@ -359,7 +277,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_prefix_apply(const void * _
         v[k] = s[threadIdx.x * WIN_ITEMS + k];
         mine += v[k];
     }
-    u64 run = tile_off[blockIdx.x] + win_block_scan<WinAddU64>(mine, lds);
+    u64 run = tile_off[blockIdx.x] + block_scan_exclusive<AddU64>(mine, lds);
 #pragma unroll
     for (u32 k = 0; k < WIN_ITEMS; ++k)
     {
@@ -410,26 +328,14 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_seg_tiles(const void * __re
             m = key > m ? key : m;
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-    {
-        const u64 o = ((u64)__shfl_xor((u32)(m >> 32), d, WAVE) << 32) | __shfl_xor((u32)m, d, WAVE);
-        m = o > m ? o : m;
-    }
-    if ((threadIdx.x & 63) == 0)
-        lds[threadIdx.x >> 6] = m;
-    __syncthreads();
+    m = block_reduce<MaxU64>(m, lds);
     if (threadIdx.x == 0)
-    {
-        for (u32 w = 1; w < WIN_THREADS / 64; ++w)
-            m = lds[w] > m ? lds[w] : m;
         agg[blockIdx.x] = WinSeg{m, start >= tile0 ? 1u : 0u};
-    }
 }
 
 __global__ __launch_bounds__(WIN_PASS) void k_win_scan_seg_tiles(WinSeg * __restrict__ agg, u64 n_tiles)
 {
-    win_scan_array<WinSegMax, false>(agg, agg, n_tiles, WinSeg{0, 0});
+    block_scan_array<WinSegMax, false>(agg, agg, n_tiles, WinSeg{0, 0});
 }
 
 // M[row] = the extremum key over the row's partition up to and including the row, in scan order
@@ -459,7 +365,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_seg_apply(const void * __re
         v[k] = WinSeg{s[threadIdx.x * WIN_ITEMS + k], s_head[threadIdx.x * WIN_ITEMS + k]};
         mine = WinSegMax::comb(mine, v[k]);
     }
-    WinSeg run = WinSegMax::comb(WinSeg{carry[blockIdx.x].v, 0}, win_block_scan<WinSegMax>(mine, lds));
+    WinSeg run = WinSegMax::comb(WinSeg{carry[blockIdx.x].v, 0}, block_scan_exclusive<WinSegMax>(mine, lds));
 #pragma unroll
     for (u32 k = 0; k < WIN_ITEMS; ++k)
     {

@@ -140,6 +140,39 @@ def test_257_runs_and_a_group_from_every_run(ch, ctx, T):
     check_all(ch, ctx, [key], ASC, offs, rng)
 
 
+def test_more_tiles_than_threads_of_the_one_workgroup_kernels(ch, ctx, T):
+    """2 * 256 * T + T + 5 rows in two runs: 514 tiles, so k_fold_carry's threads own up to three tiles each and k_fold_offsets scans the
+    tile counts in three passes of 256 with a carry between them.  Seeded group lengths of 1 .. 9, and one group from seven positions
+    before the end of tile 255 to eleven positions into tile 257 (it covers tile 256 whole and crosses the edge between the passes)."""
+    rng = np.random.Generator(np.random.PCG64(514))
+    total, start, long = 2 * 256 * T + T + 5, 256 * T - 7, T + 18
+
+    def short(n):
+        lens = rng.integers(1, 10, n)              # more than enough: cut where the sum reaches n, the last one shortened to fit
+        ends = np.cumsum(lens)
+        k = int(np.searchsorted(ends, n))
+        lens[k] -= ends[k] - n
+        return lens[:k + 1]
+
+    lens = np.concatenate([short(start), [long], short(total - start - long)])
+    assert lens.sum() == total and lens.min() >= 1
+    first = np.cumsum(lens) - lens
+    g = int(np.flatnonzero(lens == long)[0])
+    assert first[g] // T == 255 and (first[g] + long - 1) // T == 257
+    key, offs, _ = layout(lens, 2, rng)
+    assert len(key) == total
+    sign = np.where(rng.integers(0, 2, total) == 1, 1, -1).astype(np.int8)
+    got = check_collapsing(ch, ctx, [key], ASC, offs, sign)
+    assert len(got) > 256 * T // 9                  # outputs in every pass of the offsets
+    values = [rng.integers(-1, 2, total).astype(np.int8), R.random_column(rng, np.uint64, total, 2)]
+    d = R.describe([key], ASC)
+    want = F.folding_vector(d, values, ["sum", "sum"], True)
+    first_rows, last_rows, results = ch.summing_merge_rows([ctx.upload(key)], ASC, offs, values)
+    assert np.array_equal(first_rows.numpy(), want[0]) and np.array_equal(last_rows.numpy(), want[1])
+    for r, w, v in zip(results, want[2], values):
+        assert r.numpy().dtype == v.dtype and np.array_equal(r.numpy(), w)
+
+
 def test_zeros_and_nans_of_different_runs_share_a_group(ch, ctx):
     rng = np.random.Generator(np.random.PCG64(5))
     for dtype in (np.float64, np.float32):
