@@ -120,7 +120,7 @@ static std::mutex g_opt_mu;
 static std::map<std::string, long long> g_opt_defaults;
 static const char * const CHGPU_OPTION_NAMES[] = {
     "agg_no_partition", "debug", "deterministic_float_sums", "test_chain_grid", "test_group_array_fail_alloc", "test_keydict_chunk_rows", "test_keydict_weak_tags", "test_limit_by_fail_alloc", "test_limit_by_grid", "test_quantile_fail_alloc", "test_quantile_hist_budget",
-    "test_uniq_fail_growth",
+    "test_string_fail_alloc", "test_uniq_fail_growth",
     "tune_agg_lds_threads", "tune_agg_no_ranged", "tune_agg_ranged_s", "tune_cmp_wg", "tune_expr_wg", "tune_exprn_wg", "tune_fcount_wg",
     "tune_filter_no_multi", "tune_fs2_wg", "tune_fs_wg", "tune_fscatter_wg", "tune_gb_kib", "tune_gb_no_tiled",
     "tune_gb_no_word_passes", "tune_gb_no_two_level", "tune_gb_nocnt32", "tune_gb_noops", "tune_gb_nowide", "tune_gb_s", "tune_gb_tile",

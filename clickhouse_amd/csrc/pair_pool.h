@@ -1,6 +1,6 @@
 // pair_pool.h — the pool memory an operator owns, the numbered allocations of one call and the call's temporaries, written once for
-// quantile_kernels.hip, group_array_kernels.hip, limit_by_kernels.hip and window_kernels.hip.  Host code only, and nothing of
-// group_table.h or pair_store.h comes with it.
+// quantile_kernels.hip, group_array_kernels.hip, limit_by_kernels.hip, window_kernels.hip, merge_kernels.hip, merge_fold_kernels.hip
+// and the ColumnString operators (string_column.h).  Host code only, and nothing of group_table.h or pair_store.h comes with it.
 #pragma once
 
 #include <vector>
@@ -76,6 +76,12 @@ struct PairTemps
         mems.push_back(m);
         *out = m.p;
         return CHGPU_OK;
+    }
+    // gives one allocation back before the call ends (a round of the string sort); its emptied entry stays
+    void release(void * p)
+    {
+        for (PairMem & m : mems)
+            if (m.p == p) pair_free_mem(mem.ctx, m);
     }
     int col(int type, u64 rows, chgpu_col ** out)
     {

@@ -15,14 +15,9 @@
 //   scan of the "I am a first row" flags -> dense ids in order of first appearance; k_str_ids gathers them per row
 // The hash is internal (placement only).  Algorithmic bytes: chars once + 8 B offsets + 4 B id per row; the table traffic is
 // random 16-byte cells, two touches per row.
-#include "chgpu_internal.h"
-
-__device__ __forceinline__ u64 str_load8(const u8 * p)
-{
-    u64 v;
-    __builtin_memcpy(&v, p, 8); // unaligned: global memory allows it; the column's 64-byte pad covers the over-read
-    return v;
-}
+// Further down: ColumnString::filter and the predicates against a constant.  What the String entry points share (a value's begin and
+// size, the copy loop, the prologue, the call's allocations, the layout pass) is string_column.h; the buffer layouts are string_host.h.
+#include "string_column.h"
 
 __device__ __forceinline__ u64 str_hash_bytes(const u8 * p, u64 len)
 {
@@ -72,7 +67,7 @@ __global__ __launch_bounds__(256) void k_str_check_offsets(const u64 * __restric
         *bad = 1;
 }
 
-int str_validate_offsets(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8) // shared with string_sort_kernels.hip
+int str_validate_offsets(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8) // (called by str_column_begin, string_column.h)
 {
     const u64 n = offsets_u64->rows;
     if (!n)
@@ -185,96 +180,61 @@ extern "C" int chgpu_string_dictionary_encode(chgpu_ctx * ctx, const chgpu_col *
                                               chgpu_col ** first_rows_u64, uint64_t * n_distinct)
 {
     ChgpuDeviceGuard _dev_guard(ctx);
-    CHGPU_REQUIRE(ctx && offsets_u64 && chars_u8 && ids_u32 && first_rows_u64 && n_distinct, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(offsets_u64->type == CHGPU_U64 && chars_u8->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "ColumnString = UInt64 offsets + UInt8 chars");
-    const u64 n = offsets_u64->rows;
-    CHGPU_REQUIRE(n < (1ull << 32), CHGPU_ERR_NOT_IMPLEMENTED, "more than 2^32 rows per call");
-    chgpu_col * ids = nullptr, * dict = nullptr;
-    *n_distinct = 0;
-    if (n == 0)
-    {
-        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U32, 0, &ids));
-        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, 0, &dict));
-        *ids_u32 = ids, *first_rows_u64 = dict;
-        return CHGPU_OK;
-    }
-    // the last offset must equal the size of chars (ColumnString invariant); checked with one read-back
-    u64 last = 0;
-    CHGPU_TRY(chgpu_read_back(ctx, (const u64 *)offsets_u64->data + (n - 1), &last, sizeof(last)));
-    CHGPU_REQUIRE(last == chars_u8->rows, CHGPU_ERR_SIZES_MISMATCH, "offsets.back() (%llu) != chars.size() (%llu)", (unsigned long long)last,
-                  (unsigned long long)chars_u8->rows);
-    CHGPU_TRY(str_validate_offsets(ctx, offsets_u64, chars_u8));
-    u64 cap = 1024;
-    while (cap < 2 * n)
-        cap <<= 1;
-    // temporaries: hash u64[n] | rep_row u64[n] | is_first u32[n] | prefix u64[n] | tags u64[cap] | first_row u64[cap] | fail u32 | scan tmp
-    auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t b_hash = al(n * 8), b_rep = al(n * 8), b_first = al(n * 4), b_prefix = al(n * 8), b_tags = al(cap * 8), b_rows = al(cap * 8), b_flag = 256;
-    const size_t b_tmp = chgpu_scan_tmp_bytes(n);
-    void * mem = nullptr;
-    size_t mem_class = 0;
-    CHGPU_TRY(chgpu_pool_alloc(ctx, b_hash + b_rep + b_first + b_prefix + b_tags + b_rows + b_flag + 256 + b_tmp, &mem, &mem_class));
-    char * p = (char *)mem;
-    u64 * hash = (u64 *)p; p += b_hash;
-    u64 * rep = (u64 *)p; p += b_rep;
-    u32 * isf = (u32 *)p; p += b_first;
-    u64 * prefix = (u64 *)p; p += b_prefix;
-    u64 * tags = (u64 *)p; p += b_tags;
-    unsigned long long * rows = (unsigned long long *)p; p += b_rows;
-    u32 * fail = (u32 *)p; p += b_flag;
-    u64 * total_dev = (u64 *)p; p += 256;
-    void * tmp = p;
-    int rc = CHGPU_OK;
-    auto done = [&](int code) {
-        chgpu_pool_free(ctx, mem, mem_class);
-        if (code != CHGPU_OK)
-        {
-            if (ids)
-                chgpu_col_free(ids);
-            if (dict)
-                chgpu_col_free(dict);
-        }
-        return code;
-    };
-    if (hipMemsetAsync(tags, 0, b_tags, ctx->stream) != hipSuccess || hipMemsetAsync(rows, 0xFF, b_rows, ctx->stream) != hipSuccess ||
-        hipMemsetAsync(fail, 0, b_flag, ctx->stream) != hipSuccess)
-        return done(chgpu_set_error(CHGPU_ERR_DEVICE, "memset failed"));
+    StrColumn col;
+    CHGPU_TRY(str_column_begin(ctx, offsets_u64, chars_u8, ids_u32 && first_rows_u64 && n_distinct, [&] {
+        const u64 n = offsets_u64->rows;
+        CHGPU_REQUIRE(n < (1ull << 32), CHGPU_ERR_NOT_IMPLEMENTED, "more than 2^32 rows per call");
+        *n_distinct = 0;
+        if (n == 0)
+            return (int)CHGPU_OK;
+        // the last offset must equal the size of chars (ColumnString invariant); checked with one read-back
+        u64 last = 0;
+        CHGPU_TRY(chgpu_read_back(ctx, (const u64 *)offsets_u64->data + (n - 1), &last, sizeof(last)));
+        CHGPU_REQUIRE(last == chars_u8->rows, CHGPU_ERR_SIZES_MISMATCH, "offsets.back() (%llu) != chars.size() (%llu)", (unsigned long long)last,
+                      (unsigned long long)chars_u8->rows);
+        return (int)CHGPU_OK;
+    }, &col));
+    const u64 n = col.rows;
     const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
-    const u64 * offs = (const u64 *)offsets_u64->data;
-    const u8 * chars = (const u8 *)chars_u8->data;
-    hipLaunchKernelGGL(k_str_hash, dim3(grid), dim3(256), 0, ctx->stream, offs, chars, n, hash);
-    hipLaunchKernelGGL(k_str_insert, dim3(grid), dim3(256), 0, ctx->stream, (const u64 *)hash, n, tags, rows, cap - 1, fail);
-    hipLaunchKernelGGL(k_str_resolve, dim3(grid), dim3(256), 0, ctx->stream, offs, chars, (const u64 *)hash, n, (const u64 *)tags, (const unsigned long long *)rows,
-                       cap - 1, rep, isf, fail);
-    ctx->counters[6] += 3;
-    rc = chgpu_scan_exclusive_u32_u64(ctx, isf, prefix, n, total_dev, tmp, b_tmp);
-    if (rc != CHGPU_OK)
-        return done(rc);
-    struct { u64 total; } hb;
-    rc = chgpu_read_back(ctx, total_dev, &hb.total, sizeof(u64));
-    if (rc != CHGPU_OK)
-        return done(rc);
-    u32 failed = 0;
-    rc = chgpu_read_back(ctx, fail, &failed, sizeof(failed));
-    if (rc != CHGPU_OK)
-        return done(rc);
-    if (failed == 2)
-        return done(chgpu_set_error(CHGPU_ERR_NOT_IMPLEMENTED, "two different strings share a 64-bit hash tag in this block: CPU path"));
-    if (failed)
-        return done(chgpu_set_error(CHGPU_ERR_LOGICAL, "string table probe did not terminate"));
-    rc = chgpu_col_new(ctx, CHGPU_U32, n, &ids);
-    if (rc == CHGPU_OK)
-        rc = chgpu_col_new(ctx, CHGPU_U64, hb.total, &dict);
-    if (rc != CHGPU_OK)
-        return done(rc);
-    hipLaunchKernelGGL(k_str_ids, dim3(grid), dim3(256), 0, ctx->stream, (const u64 *)rep, (const u32 *)isf, (const u64 *)prefix, n, (u32 *)ids->data, (u64 *)dict->data);
-    ctx->counters[6] += 1;
-    if (hipGetLastError() != hipSuccess)
-        return done(chgpu_set_error(CHGPU_ERR_DEVICE, "string dictionary kernels failed to launch"));
-    *ids_u32 = ids;
-    *first_rows_u64 = dict;
-    *n_distinct = hb.total;
-    return done(CHGPU_OK);
+    PairAllocs mem = str_call(ctx, "string dictionary_encode");
+    PairTemps tmp(mem);
+    StrDictLayout l;
+    u64 total = 0;
+    if (n)
+    {
+        u64 cap = 1024;
+        while (cap < 2 * n)
+            cap <<= 1; // cells of the table: a power of two, at least two per row
+        const size_t b_tmp = chgpu_scan_tmp_bytes(n);
+        CHGPU_TRY(str_carve(tmp, [&](uintptr_t base) { return str_dict_lay(base, n, cap, b_tmp, &l); }));
+        CHGPU_HIP(hipMemsetAsync(l.tags, 0, cap * 8, ctx->stream));
+        CHGPU_HIP(hipMemsetAsync(l.first_row, 0xFF, cap * 8, ctx->stream));
+        CHGPU_HIP(hipMemsetAsync(l.fail, 0, 256, ctx->stream));
+        hipLaunchKernelGGL(k_str_hash, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, col.chars, n, l.hash);
+        hipLaunchKernelGGL(k_str_insert, dim3(grid), dim3(256), 0, ctx->stream, (const u64 *)l.hash, n, l.tags, l.first_row, cap - 1, l.fail);
+        hipLaunchKernelGGL(k_str_resolve, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, col.chars, (const u64 *)l.hash, n, (const u64 *)l.tags,
+                           (const unsigned long long *)l.first_row, cap - 1, l.rep_row, l.is_first, l.fail);
+        ctx->counters[6] += 3;
+        CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, l.is_first, l.prefix, n, l.total, l.scan_tmp, b_tmp));
+        CHGPU_TRY(chgpu_read_back(ctx, l.total, &total, sizeof(total)));
+        u32 failed = 0;
+        CHGPU_TRY(chgpu_read_back(ctx, l.fail, &failed, sizeof(failed)));
+        CHGPU_REQUIRE(failed != 2, CHGPU_ERR_NOT_IMPLEMENTED, "two different strings share a 64-bit hash tag in this block: CPU path");
+        CHGPU_REQUIRE(!failed, CHGPU_ERR_LOGICAL, "string table probe did not terminate");
+    }
+    StrCols<> out; // ids, first rows
+    CHGPU_TRY(mem.col_new(CHGPU_U32, n, &out.v[0]));
+    CHGPU_TRY(mem.col_new(CHGPU_U64, total, &out.v[1]));
+    if (n)
+    {
+        hipLaunchKernelGGL(k_str_ids, dim3(grid), dim3(256), 0, ctx->stream, (const u64 *)l.rep_row, (const u32 *)l.is_first, (const u64 *)l.prefix, n,
+                           (u32 *)out.v[0]->data, (u64 *)out.v[1]->data);
+        ctx->counters[6] += 1;
+        CHGPU_REQUIRE(hipGetLastError() == hipSuccess, CHGPU_ERR_DEVICE, "string dictionary kernels failed to launch");
+    }
+    out.give(ids_u32, first_rows_u64);
+    *n_distinct = total;
+    return CHGPU_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -292,11 +252,9 @@ __global__ __launch_bounds__(256) void k_str_filter_sizes(const u64 * __restrict
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
     {
         const u32 f = mask[i] != 0;
-        const u64 sz = offsets[i] - (i ? offsets[i - 1] : 0);
-        if (f && sz >= (1ull << 32))
-            *too_long = 1;
+        const StrValue v = str_value(offsets, i);
         flag[i] = f;
-        bytes[i] = f ? (u32)sz : 0u;
+        bytes[i] = f ? str_size_u32(v.size, too_long) : 0u;
     }
 }
 
@@ -308,18 +266,10 @@ __global__ __launch_bounds__(256) void k_str_filter_move(const u64 * __restrict_
     {
         if (!flag[i])
             continue;
-        const u64 begin = i ? offsets[i - 1] : 0;
-        const u64 sz = offsets[i] - begin;
+        const StrValue v = str_value(offsets, i);
         const u64 dst = byte_pos[i];
-        out_offsets[row_pos[i]] = dst + sz;
-        u64 k = 0;
-        for (; k + 8 <= sz; k += 8)
-        {
-            const u64 v = str_load8(chars + begin + k);
-            __builtin_memcpy(out_chars + dst + k, &v, 8);
-        }
-        for (; k < sz; ++k)
-            out_chars[dst + k] = chars[begin + k];
+        out_offsets[row_pos[i]] = dst + v.size;
+        str_copy_value(out_chars + dst, chars + v.begin, v.size);
     }
 }
 
@@ -327,86 +277,40 @@ extern "C" int chgpu_string_filter(chgpu_ctx * ctx, const chgpu_col * offsets_u6
                                    chgpu_col ** out_offsets_u64, chgpu_col ** out_chars_u8, uint64_t * rows_out)
 {
     ChgpuDeviceGuard _dev_guard(ctx);
-    CHGPU_REQUIRE(ctx && offsets_u64 && chars_u8 && filter_u8 && out_offsets_u64 && out_chars_u8 && rows_out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(offsets_u64->type == CHGPU_U64 && chars_u8->type == CHGPU_U8 && filter_u8->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS,
-                  "ColumnString = UInt64 offsets + UInt8 chars; the filter is a UInt8 column");
-    const u64 n = offsets_u64->rows;
-    CHGPU_REQUIRE(filter_u8->rows == n, CHGPU_ERR_SIZES_MISMATCH, "Size of filter (%llu) doesn't match size of column (%llu)",
-                  (unsigned long long)filter_u8->rows, (unsigned long long)n); // ColumnsCommon.cpp:199-200
-    chgpu_col * oo = nullptr, * oc = nullptr;
-    u64 kept_rows = 0, kept_bytes = 0;
-    CHGPU_TRY(str_validate_offsets(ctx, offsets_u64, chars_u8));
+    StrColumn col;
+    CHGPU_TRY(str_column_begin(ctx, offsets_u64, chars_u8, filter_u8 && out_offsets_u64 && out_chars_u8 && rows_out, [&] {
+        CHGPU_REQUIRE(filter_u8->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "the filter is a UInt8 column");
+        CHGPU_REQUIRE(filter_u8->rows == offsets_u64->rows, CHGPU_ERR_SIZES_MISMATCH, "Size of filter (%llu) doesn't match size of column (%llu)",
+                      (unsigned long long)filter_u8->rows, (unsigned long long)offsets_u64->rows); // ColumnsCommon.cpp:199-200
+        return (int)CHGPU_OK;
+    }, &col));
+    const u64 n = col.rows;
+    const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
+    PairAllocs mem = str_call(ctx, "string filter");
+    PairTemps tmp(mem);
+    StrValuesLayout l{};
     if (n)
     {
-        auto al = [](size_t b) { return (b + 255) / 256 * 256; };
-        const size_t b_flag = al(n * 4), b_bytes = al(n * 4), b_rpos = al(n * 8), b_bpos = al(n * 8), b_tmp = chgpu_scan_tmp_bytes(n);
-        void * mem = nullptr;
-        size_t mem_class = 0;
-        CHGPU_TRY(chgpu_pool_alloc(ctx, b_flag + b_bytes + b_rpos + b_bpos + 512 + b_tmp, &mem, &mem_class));
-        char * p = (char *)mem;
-        u32 * flag = (u32 *)p; p += b_flag;
-        u32 * bytes = (u32 *)p; p += b_bytes;
-        u64 * rpos = (u64 *)p; p += b_rpos;
-        u64 * bpos = (u64 *)p; p += b_bpos;
-        u64 * totals = (u64 *)p; p += 256; // [0] rows, [1] bytes
-        u32 * too_long = (u32 *)p; p += 256;
-        void * tmp = p;
-        auto done = [&](int code) {
-            chgpu_pool_free(ctx, mem, mem_class);
-            if (code != CHGPU_OK)
-            {
-                if (oo)
-                    chgpu_col_free(oo);
-                if (oc)
-                    chgpu_col_free(oc);
-            }
-            return code;
-        };
-        if (hipMemsetAsync(too_long, 0, 256, ctx->stream) != hipSuccess)
-            return done(chgpu_set_error(CHGPU_ERR_DEVICE, "memset failed"));
-        const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
-        hipLaunchKernelGGL(k_str_filter_sizes, dim3(grid), dim3(256), 0, ctx->stream, (const u64 *)offsets_u64->data, (const u8 *)filter_u8->data, n, flag, bytes, too_long);
-        int rc = chgpu_scan_exclusive_u32_u64(ctx, flag, rpos, n, totals, tmp, b_tmp);
-        if (rc == CHGPU_OK)
-            rc = chgpu_scan_exclusive_u32_u64(ctx, bytes, bpos, n, totals + 1, tmp, b_tmp);
-        u64 host_totals[2] = {0, 0};
-        u32 host_long = 0;
-        if (rc == CHGPU_OK)
-            rc = chgpu_read_back(ctx, totals, host_totals, sizeof(host_totals));
-        if (rc == CHGPU_OK)
-            rc = chgpu_read_back(ctx, too_long, &host_long, sizeof(host_long));
-        if (rc == CHGPU_OK && host_long)
-            rc = chgpu_set_error(CHGPU_ERR_NOT_IMPLEMENTED, "a value of 4 GiB or more");
-        if (rc != CHGPU_OK)
-            return done(rc);
-        kept_rows = host_totals[0], kept_bytes = host_totals[1];
-        rc = chgpu_col_new(ctx, CHGPU_U64, kept_rows, &oo);
-        if (rc == CHGPU_OK)
-            rc = chgpu_col_new(ctx, CHGPU_U8, kept_bytes, &oc);
-        if (rc != CHGPU_OK)
-            return done(rc);
-        if (kept_rows)
-            hipLaunchKernelGGL(k_str_filter_move, dim3(grid), dim3(256), 0, ctx->stream, (const u64 *)offsets_u64->data, (const u8 *)chars_u8->data, (const u32 *)flag,
-                               (const u64 *)rpos, (const u64 *)bpos, n, (u64 *)oo->data, (u8 *)oc->data);
-        ctx->counters[6] += 2;
-        ctx->counters[0] += kept_rows;
-        if (hipGetLastError() != hipSuccess)
-            return done(chgpu_set_error(CHGPU_ERR_DEVICE, "string filter kernels failed to launch"));
-        done(CHGPU_OK);
+        CHGPU_TRY(str_carve(tmp, [&](uintptr_t base) { return str_values_lay(base, n, true, chgpu_scan_tmp_bytes(n), &l); }));
+        CHGPU_HIP(hipMemsetAsync(l.words, 0, sizeof(StrLayoutWords), ctx->stream));
+        hipLaunchKernelGGL(k_str_filter_sizes, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, (const u8 *)filter_u8->data, n, l.flag, l.sizes,
+                           (u32 *)&l.words->too_long);
+        CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, l.flag, l.row_pos, n, &l.words->rows, l.scan_tmp, chgpu_scan_tmp_bytes(n)));
     }
-    else
+    StrLayoutWords words;
+    StrCols<> out;
+    CHGPU_TRY(str_layout_values(ctx, mem, l, n, true, n, &words, &out));
+    if (n)
     {
-        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, 0, &oo));
-        int rc = chgpu_col_new(ctx, CHGPU_U8, 0, &oc);
-        if (rc != CHGPU_OK)
-        {
-            chgpu_col_free(oo);
-            return rc;
-        }
+        if (words.rows)
+            hipLaunchKernelGGL(k_str_filter_move, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, col.chars, (const u32 *)l.flag, (const u64 *)l.row_pos,
+                               (const u64 *)l.pos, n, (u64 *)out.v[0]->data, (u8 *)out.v[1]->data);
+        ctx->counters[6] += 2;
+        ctx->counters[0] += words.rows;
+        CHGPU_REQUIRE(hipGetLastError() == hipSuccess, CHGPU_ERR_DEVICE, "string filter kernels failed to launch");
     }
-    *out_offsets_u64 = oo;
-    *out_chars_u8 = oc;
-    *rows_out = kept_rows;
+    out.give(out_offsets_u64, out_chars_u8);
+    *rows_out = words.rows;
     return CHGPU_OK;
 }
 
@@ -818,15 +722,19 @@ static StrConst str_const_of(const void * bytes, u64 n)
     return c;
 }
 
-// the arguments every predicate shares; *out receives an empty UInt8 column when there are no rows
+// the arguments every predicate shares, then `own_checks` (the entry point's), the offsets, and *out: a UInt8 column of one byte per row
+template <class OwnChecks>
 static int str_predicate_begin(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const void * constant, u64 constant_bytes,
-                               chgpu_col ** out_u8)
+                               OwnChecks && own_checks, chgpu_col ** out_u8, chgpu_col ** out)
 {
-    CHGPU_REQUIRE(ctx && offsets_u64 && chars_u8 && out_u8 && (constant || !constant_bytes), CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(offsets_u64->type == CHGPU_U64 && chars_u8->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "ColumnString = UInt64 offsets + UInt8 chars");
-    CHGPU_REQUIRE(constant_bytes <= CHGPU_STR_CONST_MAX, CHGPU_ERR_NOT_IMPLEMENTED, "a string constant of %llu bytes (the kernels carry %d): CPU path",
-                  (unsigned long long)constant_bytes, CHGPU_STR_CONST_MAX);
-    return CHGPU_OK;
+    StrColumn col;
+    CHGPU_TRY(str_column_begin(ctx, offsets_u64, chars_u8, out_u8 && (constant || !constant_bytes), [&] {
+        CHGPU_REQUIRE(constant_bytes <= CHGPU_STR_CONST_MAX, CHGPU_ERR_NOT_IMPLEMENTED, "a string constant of %llu bytes (the kernels carry %d): CPU path",
+                      (unsigned long long)constant_bytes, CHGPU_STR_CONST_MAX);
+        return own_checks();
+    }, &col));
+    PairAllocs mem = str_call(ctx, "string predicate");
+    return mem.col_new(CHGPU_U8, col.rows, out);
 }
 
 static int str_launch_row(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int mode, int op, const StrConst & c, int negate, chgpu_col * out)
@@ -872,16 +780,11 @@ static int str_launch_like(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const
     return CHGPU_OK;
 }
 
-static int str_predicate_end(int rc, chgpu_col * out, chgpu_col ** out_u8)
+static int str_predicate_end(int rc, StrCols<> & out, chgpu_col ** out_u8)
 {
-    if (rc == CHGPU_OK && hipGetLastError() != hipSuccess)
-        rc = chgpu_set_error(CHGPU_ERR_DEVICE, "string predicate kernels failed to launch");
-    if (rc != CHGPU_OK)
-    {
-        chgpu_col_free(out);
-        return rc;
-    }
-    *out_u8 = out;
+    CHGPU_TRY(rc);
+    CHGPU_REQUIRE(hipGetLastError() == hipSuccess, CHGPU_ERR_DEVICE, "string predicate kernels failed to launch");
+    out.give(out_u8);
     return CHGPU_OK;
 }
 
@@ -889,24 +792,20 @@ extern "C" int chgpu_string_cmp_const(chgpu_ctx * ctx, const chgpu_col * offsets
                                       chgpu_col ** out_u8)
 {
     ChgpuDeviceGuard _dev_guard(ctx);
-    CHGPU_TRY(str_predicate_begin(ctx, offsets_u64, chars_u8, value, value_bytes, out_u8));
-    CHGPU_REQUIRE(op >= CHGPU_EQ && op <= CHGPU_GE, CHGPU_ERR_BAD_ARGUMENTS, "unknown comparison %d", op);
-    CHGPU_TRY(str_validate_offsets(ctx, offsets_u64, chars_u8));
-    chgpu_col * out = nullptr;
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, offsets_u64->rows, &out));
+    StrCols<> out; // the mask
+    CHGPU_TRY(str_predicate_begin(ctx, offsets_u64, chars_u8, value, value_bytes, [&] {
+        CHGPU_REQUIRE(op >= CHGPU_EQ && op <= CHGPU_GE, CHGPU_ERR_BAD_ARGUMENTS, "unknown comparison %d", op);
+        return (int)CHGPU_OK;
+    }, out_u8, &out.v[0]));
     if (!offsets_u64->rows)
         return str_predicate_end(CHGPU_OK, out, out_u8);
-    return str_predicate_end(str_launch_row(ctx, offsets_u64, chars_u8, SM_CMP, op, str_const_of(value, value_bytes), 0, out), out, out_u8);
+    return str_predicate_end(str_launch_row(ctx, offsets_u64, chars_u8, SM_CMP, op, str_const_of(value, value_bytes), 0, out.v[0]), out, out_u8);
 }
 
-extern "C" int chgpu_string_match_const(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int kind, const void * pattern,
-                                        uint64_t pattern_bytes, int negate, chgpu_col ** out_u8)
+// every kind is a route of the LIKE plan; a needle is its own literal
+static int str_match_plan(chgpu_ctx * ctx, int kind, const void * pattern, u64 pattern_bytes, chgpu_like_plan & plan)
 {
-    ChgpuDeviceGuard _dev_guard(ctx);
-    CHGPU_TRY(str_predicate_begin(ctx, offsets_u64, chars_u8, pattern, pattern_bytes, out_u8));
     CHGPU_REQUIRE(kind >= CHGPU_STR_LIKE && kind <= CHGPU_STR_ENDS_WITH, CHGPU_ERR_BAD_ARGUMENTS, "unknown string predicate %d", kind);
-    // every kind is a route of the LIKE plan; a needle is its own literal
-    chgpu_like_plan plan;
     if (kind == CHGPU_STR_LIKE)
         CHGPU_TRY(chgpu_like_compile(pattern, pattern_bytes, &plan));
     else
@@ -928,9 +827,16 @@ extern "C" int chgpu_string_match_const(chgpu_ctx * ctx, const chgpu_col * offse
         plan.token_meta[(plan.n_tokens - 1) >> 5] |= 1u << ((plan.n_tokens - 1) & 31);
         plan.route = CHGPU_STR_ROUTE_GENERAL;
     }
-    CHGPU_TRY(str_validate_offsets(ctx, offsets_u64, chars_u8));
-    chgpu_col * out = nullptr;
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, offsets_u64->rows, &out));
+    return CHGPU_OK;
+}
+
+extern "C" int chgpu_string_match_const(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int kind, const void * pattern,
+                                        uint64_t pattern_bytes, int negate, chgpu_col ** out_u8)
+{
+    ChgpuDeviceGuard _dev_guard(ctx);
+    chgpu_like_plan plan;
+    StrCols<> out; // the mask
+    CHGPU_TRY(str_predicate_begin(ctx, offsets_u64, chars_u8, pattern, pattern_bytes, [&] { return str_match_plan(ctx, kind, pattern, pattern_bytes, plan); }, out_u8, &out.v[0]));
     if (!offsets_u64->rows)
         return str_predicate_end(CHGPU_OK, out, out_u8);
     int rc = CHGPU_OK;
@@ -938,17 +844,17 @@ extern "C" int chgpu_string_match_const(chgpu_ctx * ctx, const chgpu_col * offse
     {
         StrConst c = str_const_of(plan.tokens, plan.n_tokens);
         memcpy(c.meta, plan.token_meta, sizeof(c.meta));
-        rc = str_launch_like(ctx, offsets_u64, chars_u8, c, negate, out);
+        rc = str_launch_like(ctx, offsets_u64, chars_u8, c, negate, out.v[0]);
     }
     else
     {
         const StrConst c = str_const_of(plan.literal, plan.literal_bytes);
         if (plan.route == CHGPU_STR_ROUTE_CONTAINS)
-            rc = str_launch_contains(ctx, offsets_u64, chars_u8, c, negate, out);
+            rc = str_launch_contains(ctx, offsets_u64, chars_u8, c, negate, out.v[0]);
         else if (plan.route == CHGPU_STR_ROUTE_EQUALS)
-            rc = str_launch_row(ctx, offsets_u64, chars_u8, SM_CMP, negate ? CHGPU_NE : CHGPU_EQ, c, 0, out);
+            rc = str_launch_row(ctx, offsets_u64, chars_u8, SM_CMP, negate ? CHGPU_NE : CHGPU_EQ, c, 0, out.v[0]);
         else
-            rc = str_launch_row(ctx, offsets_u64, chars_u8, plan.route == CHGPU_STR_ROUTE_STARTS_WITH ? SM_STARTS : SM_ENDS, 0, c, negate, out);
+            rc = str_launch_row(ctx, offsets_u64, chars_u8, plan.route == CHGPU_STR_ROUTE_STARTS_WITH ? SM_STARTS : SM_ENDS, 0, c, negate, out.v[0]);
     }
     return str_predicate_end(rc, out, out_u8);
 }

@@ -23,29 +23,14 @@
 // Algorithmic bytes per round over m active rows: 2 value gathers (lcp, keys) + (9 + segment-id bytes) passes x 21 B read and written
 // + ~50 B per row of flags and scans.
 //
-// chgpu_string_index has the shape of chgpu_string_filter: sizes gathered through the indexes, one scan, one move pass.
+// chgpu_string_index has the shape of chgpu_string_filter: sizes gathered through the indexes, the layout pass, one move pass.
+// (Both routines are string_column.h's; SsSegs and the layouts of a round's pool allocations are string_host.h's.)
 #include "block_scan.h"
+#include "string_column.h"
 
 #include <algorithm>
 
 static constexpr u64 SS_NONE = ~0ull;
-
-// as in string_kernels.hip
-__device__ __forceinline__ u64 str_load8(const u8 * p)
-{
-    u64 v;
-    __builtin_memcpy(&v, p, 8); // unaligned: global memory allows it; the column's pad covers the over-read
-    return v;
-}
-
-struct SsSegs // per segment, device arrays
-{
-    u64 * start; // first position of the segment in the output permutation
-    u64 * first; // index of its first row in the active arrays
-    u64 * depth; // words every row of the segment is known to share (and to have)
-    u64 * adv;   // further words all of its rows share (k_ss_lcp); SS_NONE: no pair of rows looked
-    u64 * head;  // index of its head row in the previous round's sorted arrays
-};
 
 __device__ __forceinline__ u64 ss_adv(const SsSegs & t, u32 s)
 {
@@ -204,204 +189,117 @@ __global__ __launch_bounds__(256) void k_ss_compact(const u32 * __restrict__ act
     }
 }
 
-namespace
-{
-// what a call holds until it returns, on every path
-struct SsHold
-{
-    chgpu_ctx * ctx;
-    std::vector<std::pair<void *, size_t>> mem;
-    explicit SsHold(chgpu_ctx * c) : ctx(c) {}
-    ~SsHold()
-    {
-        for (auto & m : mem)
-            chgpu_pool_free(ctx, m.first, m.second);
-    }
-    int alloc(size_t bytes, void ** out)
-    {
-        size_t cls = 0;
-        CHGPU_TRY(chgpu_pool_alloc(ctx, bytes, out, &cls));
-        mem.emplace_back(*out, cls);
-        return CHGPU_OK;
-    }
-    void release(void * p)
-    {
-        for (size_t i = 0; i < mem.size(); ++i)
-            if (mem[i].first == p)
-            {
-                chgpu_pool_free(ctx, p, mem[i].second);
-                mem.erase(mem.begin() + i);
-                return;
-            }
-    }
-};
-
-size_t ss_al(size_t b) { return (b + 255) / 256 * 256; }
-
-int ss_new_segs(SsHold & hold, u64 cap, SsSegs * t, void ** base)
-{
-    const size_t one = ss_al(cap * 8);
-    CHGPU_TRY(hold.alloc(one * 5, base));
-    char * p = (char *)*base;
-    t->start = (u64 *)p;
-    t->first = (u64 *)(p + one);
-    t->depth = (u64 *)(p + 2 * one);
-    t->adv = (u64 *)(p + 3 * one);
-    t->head = (u64 *)(p + 4 * one);
-    return CHGPU_OK;
-}
-
-struct SsCols // the active rows: word, c, segment, row
-{
-    chgpu_col * v[4] = {nullptr, nullptr, nullptr, nullptr};
-    ~SsCols() { drop(); }
-    void drop()
-    {
-        for (auto & c : v)
-        {
-            if (c)
-                chgpu_col_free(c);
-            c = nullptr;
-        }
-    }
-};
+typedef StrCols<4> SsCols; // the active rows: word, c, segment, row
 
 // one stable pass over all four columns by a byte of column `key`
-int ss_pass(chgpu_ctx * ctx, SsCols & a, int key, u32 shift)
+static int ss_pass(PairAllocs & mem, SsCols & a, int key, u32 shift)
 {
     chgpu_col * out[4] = {nullptr, nullptr, nullptr, nullptr};
-    CHGPU_TRY(chgpu_partition_by_key_byte(ctx, a.v[key], shift, 4, a.v, out));
+    CHGPU_TRY(mem.refused()); // the pass allocates inside: one number for all of it
+    CHGPU_TRY(chgpu_partition_by_key_byte(mem.ctx, a.v[key], shift, 4, a.v, out));
     a.drop();
     for (int i = 0; i < 4; ++i)
         a.v[i] = out[i];
     return CHGPU_OK;
-}
 }
 
 extern "C" int chgpu_string_sort_permutation(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const chgpu_col * perm_in_u64,
                                              int descending, uint64_t limit, chgpu_col ** perm_out_u64)
 {
     ChgpuDeviceGuard _dev_guard(ctx);
-    CHGPU_REQUIRE(ctx && offsets_u64 && chars_u8 && perm_out_u64, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(offsets_u64->type == CHGPU_U64 && chars_u8->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "ColumnString = UInt64 offsets + UInt8 chars");
-    CHGPU_REQUIRE(!perm_in_u64 || perm_in_u64->type == CHGPU_U64, CHGPU_ERR_BAD_ARGUMENTS, "a permutation is a UInt64 column (IColumn::Permutation)");
-    const u64 rows = offsets_u64->rows;
-    CHGPU_REQUIRE(!perm_in_u64 || perm_in_u64->rows <= rows, CHGPU_ERR_SIZES_MISMATCH, "Size of permutation (%llu) is greater than the column (%llu)",
-                  (unsigned long long)(perm_in_u64 ? perm_in_u64->rows : 0), (unsigned long long)rows);
-    const u64 n = perm_in_u64 ? perm_in_u64->rows : rows;
-    CHGPU_REQUIRE(n < (1ull << 32), CHGPU_ERR_NOT_IMPLEMENTED, "2^32 rows or more in one String sort");
-    CHGPU_TRY(str_validate_offsets(ctx, offsets_u64, chars_u8));
+    StrColumn col;
+    CHGPU_TRY(str_column_begin(ctx, offsets_u64, chars_u8, perm_out_u64 != nullptr, [&] {
+        CHGPU_REQUIRE(!perm_in_u64 || perm_in_u64->type == CHGPU_U64, CHGPU_ERR_BAD_ARGUMENTS, "a permutation is a UInt64 column (IColumn::Permutation)");
+        CHGPU_REQUIRE(!perm_in_u64 || perm_in_u64->rows <= offsets_u64->rows, CHGPU_ERR_SIZES_MISMATCH, "Size of permutation (%llu) is greater than the column (%llu)",
+                      (unsigned long long)(perm_in_u64 ? perm_in_u64->rows : 0), (unsigned long long)offsets_u64->rows);
+        CHGPU_REQUIRE((perm_in_u64 ? perm_in_u64->rows : offsets_u64->rows) < (1ull << 32), CHGPU_ERR_NOT_IMPLEMENTED, "2^32 rows or more in one String sort");
+        return (int)CHGPU_OK;
+    }, &col));
+    const u64 n = perm_in_u64 ? perm_in_u64->rows : col.rows;
     const u64 lim = limit && limit < n ? limit : SS_NONE;
     const u32 cont = descending ? 0u : 9u;
-    const u64 * offsets = (const u64 *)offsets_u64->data;
-    const u8 * chars = (const u8 *)chars_u8->data;
 
-    chgpu_col * out = nullptr;
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, n, &out));
-    struct OutGuard
-    {
-        chgpu_col *& c;
-        ~OutGuard()
-        {
-            if (c)
-                chgpu_col_free(c);
-        }
-    } out_guard{out};
+    PairAllocs mem = str_call(ctx, "string sort");
+    PairTemps hold(mem);
+    StrCols<> out_guard; // the permutation
+    chgpu_col *& out = out_guard.v[0];
+    CHGPU_TRY(mem.col_new(CHGPU_U64, n, &out));
     if (n == 0)
     {
-        *perm_out_u64 = out;
-        out = nullptr;
+        out_guard.give(perm_out_u64);
         return CHGPU_OK;
     }
 
-    SsHold hold(ctx);
     SsCols act;
     SsSegs segs;
-    void * segs_mem = nullptr;
-    CHGPU_TRY(ss_new_segs(hold, 1, &segs, &segs_mem));
-    CHGPU_HIP(hipMemsetAsync(segs_mem, 0, ss_al(8) * 3, ctx->stream));           // start = first = depth = 0
+    CHGPU_TRY(str_carve(hold, [&](uintptr_t base) { return ss_segs_lay(base, 1, &segs); }));
+    CHGPU_HIP(hipMemsetAsync(segs.start, 0, 256 * 3, ctx->stream));              // start = first = depth = 0
     CHGPU_HIP(hipMemsetAsync(segs.adv, 0xFF, 8, ctx->stream));
     u64 m = n, n_segs = 1;
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, m, &act.v[3]));
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U32, m, &act.v[2]));
-    hipLaunchKernelGGL(k_ss_init, dim3(chgpu_grid_for(ctx, m, 256, 8)), dim3(256), 0, ctx->stream, perm_in_u64 ? (const u64 *)perm_in_u64->data : nullptr, rows, m,
+    CHGPU_TRY(mem.col_new(CHGPU_U64, m, &act.v[3]));
+    CHGPU_TRY(mem.col_new(CHGPU_U32, m, &act.v[2]));
+    hipLaunchKernelGGL(k_ss_init, dim3(chgpu_grid_for(ctx, m, 256, 8)), dim3(256), 0, ctx->stream, perm_in_u64 ? (const u64 *)perm_in_u64->data : nullptr, col.rows, m,
                        (u64 *)act.v[3]->data, (u32 *)act.v[2]->data);
     ctx->counters[6] += 1;
 
     while (m)
     {
         const u32 grid = chgpu_grid_for(ctx, m, 256, 8);
-        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, m, &act.v[0]));
-        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U8, m, &act.v[1]));
-        hipLaunchKernelGGL(k_ss_lcp, dim3(grid), dim3(256), 0, ctx->stream, offsets, chars, (const u64 *)act.v[3]->data, (const u32 *)act.v[2]->data, m, segs);
-        hipLaunchKernelGGL(k_ss_keys, dim3(grid), dim3(256), 0, ctx->stream, offsets, chars, (const u64 *)act.v[3]->data, (const u32 *)act.v[2]->data, m, segs,
+        CHGPU_TRY(mem.col_new(CHGPU_U64, m, &act.v[0]));
+        CHGPU_TRY(mem.col_new(CHGPU_U8, m, &act.v[1]));
+        hipLaunchKernelGGL(k_ss_lcp, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, col.chars, (const u64 *)act.v[3]->data, (const u32 *)act.v[2]->data, m, segs);
+        hipLaunchKernelGGL(k_ss_keys, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, col.chars, (const u64 *)act.v[3]->data, (const u32 *)act.v[2]->data, m, segs,
                            descending, (u64 *)act.v[0]->data, (u8 *)act.v[1]->data);
         ctx->counters[6] += 2;
-        CHGPU_TRY(ss_pass(ctx, act, 1, 0));
+        CHGPU_TRY(ss_pass(mem, act, 1, 0));
         for (u32 b = 0; b < 8; ++b)
-            CHGPU_TRY(ss_pass(ctx, act, 0, b * 8));
+            CHGPU_TRY(ss_pass(mem, act, 0, b * 8));
         for (u32 b = 0; b < 4 && ((n_segs - 1) >> (8 * b)); ++b)
-            CHGPU_TRY(ss_pass(ctx, act, 2, b * 8));
+            CHGPU_TRY(ss_pass(mem, act, 2, b * 8));
 
         // flags, scans and the next round's segment table
-        const size_t b_u32 = ss_al(m * 4), b_u64 = ss_al(m * 8), b_tmp = ss_al(chgpu_scan_tmp_bytes(m));
-        void * tmp_mem = nullptr;
-        CHGPU_TRY(hold.alloc(2 * b_u32 + 2 * b_u64 + 256 + b_tmp, &tmp_mem));
-        char * p = (char *)tmp_mem;
-        u32 * new_head = (u32 *)p; p += b_u32;
-        u32 * active = (u32 *)p; p += b_u32;
-        u64 * seg_no = (u64 *)p; p += b_u64;
-        u64 * slot = (u64 *)p; p += b_u64;
-        u64 * totals = (u64 *)p; p += 256; // [0] next segments, [1] next active rows
-        void * tmp = p;
+        const size_t b_tmp = chgpu_scan_tmp_bytes(m);
+        SsRoundLayout l;
+        CHGPU_TRY(str_carve(hold, [&](uintptr_t base) { return ss_round_lay(base, m, b_tmp, &l); }));
         SsSegs next;
-        void * next_mem = nullptr;
-        CHGPU_TRY(ss_new_segs(hold, m / 2 + 1, &next, &next_mem));
+        CHGPU_TRY(str_carve(hold, [&](uintptr_t base) { return ss_segs_lay(base, m / 2 + 1, &next); }));
         const u64 * word = (const u64 *)act.v[0]->data;
         const u8 * c = (const u8 *)act.v[1]->data;
         const u32 * seg = (const u32 *)act.v[2]->data;
         const u64 * row = (const u64 *)act.v[3]->data;
-        hipLaunchKernelGGL(k_ss_heads, dim3(grid), dim3(256), 0, ctx->stream, word, c, seg, row, m, segs, cont, lim, n, (u64 *)out->data, new_head);
-        CHGPU_TRY(chgpu_scan_inclusive_u32_u64(ctx, new_head, seg_no, m, totals, tmp, b_tmp));
-        hipLaunchKernelGGL(k_ss_segs, dim3(grid), dim3(256), 0, ctx->stream, (const u32 *)new_head, (const u64 *)seg_no, seg, m, segs, next);
-        hipLaunchKernelGGL(k_ss_active, dim3(grid), dim3(256), 0, ctx->stream, word, c, seg, (const u64 *)seg_no, m, next, cont, active);
-        CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, active, slot, m, totals + 1, tmp, b_tmp));
+        hipLaunchKernelGGL(k_ss_heads, dim3(grid), dim3(256), 0, ctx->stream, word, c, seg, row, m, segs, cont, lim, n, (u64 *)out->data, l.new_head);
+        CHGPU_TRY(chgpu_scan_inclusive_u32_u64(ctx, l.new_head, l.seg_no, m, l.totals, l.scan_tmp, b_tmp));
+        hipLaunchKernelGGL(k_ss_segs, dim3(grid), dim3(256), 0, ctx->stream, (const u32 *)l.new_head, (const u64 *)l.seg_no, seg, m, segs, next);
+        hipLaunchKernelGGL(k_ss_active, dim3(grid), dim3(256), 0, ctx->stream, word, c, seg, (const u64 *)l.seg_no, m, next, cont, l.active);
+        CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, l.active, l.slot, m, l.totals + 1, l.scan_tmp, b_tmp));
         ctx->counters[6] += 3;
         u64 host_totals[2] = {0, 0};
-        CHGPU_TRY(chgpu_read_back(ctx, totals, host_totals, sizeof(host_totals)));
+        CHGPU_TRY(chgpu_read_back(ctx, l.totals, host_totals, sizeof(host_totals)));
         CHGPU_HIP(hipGetLastError());
         const u64 m_next = host_totals[1];
         CHGPU_REQUIRE(m_next <= m && host_totals[0] <= m / 2, CHGPU_ERR_LOGICAL, "string sort: a round grew its active set");
         if (m_next)
         {
-            chgpu_col * row_next = nullptr, * seg_next = nullptr;
-            CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, m_next, &row_next));
-            int rc = chgpu_col_new(ctx, CHGPU_U32, m_next, &seg_next);
-            if (rc != CHGPU_OK)
-            {
-                chgpu_col_free(row_next);
-                return rc;
-            }
-            hipLaunchKernelGGL(k_ss_compact, dim3(grid), dim3(256), 0, ctx->stream, (const u32 *)active, (const u64 *)slot, (const u32 *)new_head,
-                               (const u64 *)seg_no, row, m, next, (u64 *)row_next->data, (u32 *)seg_next->data);
+            StrCols<> next_rows; // row, segment
+            CHGPU_TRY(mem.col_new(CHGPU_U64, m_next, &next_rows.v[0]));
+            CHGPU_TRY(mem.col_new(CHGPU_U32, m_next, &next_rows.v[1]));
+            hipLaunchKernelGGL(k_ss_compact, dim3(grid), dim3(256), 0, ctx->stream, (const u32 *)l.active, (const u64 *)l.slot, (const u32 *)l.new_head,
+                               (const u64 *)l.seg_no, row, m, next, (u64 *)next_rows.v[0]->data, (u32 *)next_rows.v[1]->data);
             ctx->counters[6] += 1;
             act.drop(); // back to the pool; reuse is ordered behind the kernel above on this stream
-            act.v[3] = row_next;
-            act.v[2] = seg_next;
+            next_rows.give(&act.v[3], &act.v[2]);
         }
         else
             act.drop();
-        hold.release(tmp_mem);
-        hold.release(segs_mem);
+        hold.release(l.new_head);
+        hold.release(segs.start);
         segs = next;
-        segs_mem = next_mem;
         n_segs = host_totals[0];
         m = m_next;
     }
     if (lim != SS_NONE)
         out->rows = lim; // IColumn::Permutation is simply cut (the buffer keeps its size class)
-    *perm_out_u64 = out;
-    out = nullptr;
+    out_guard.give(perm_out_u64);
     return CHGPU_OK;
 }
 
@@ -422,13 +320,8 @@ __global__ __launch_bounds__(256) void k_str_index_sizes(const u64 * __restrict_
         if (r >= rows)
             *bad_index = 1;
         else
-            sz = offsets[r] - (r ? offsets[r - 1] : 0);
-        if (sz >= (1ull << 32))
-        {
-            *too_long = 1;
-            sz = 0;
-        }
-        bytes[i] = (u32)sz;
+            sz = str_value(offsets, r).size;
+        bytes[i] = str_size_u32(sz, too_long);
     }
 }
 
@@ -438,21 +331,11 @@ __global__ __launch_bounds__(256) void k_str_index_move(const u64 * __restrict__
 {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
     {
-        const u64 r = indexes[i];
         const u64 sz = bytes[i]; // 0 only for an index the sizes pass flagged: the call fails, nothing is read through it
         const u64 dst = byte_pos[i];
         out_offsets[i] = dst + sz;
-        if (!sz)
-            continue;
-        const u64 begin = r ? offsets[r - 1] : 0;
-        u64 k = 0;
-        for (; k + 8 <= sz; k += 8)
-        {
-            const u64 v = str_load8(chars + begin + k);
-            __builtin_memcpy(out_chars + dst + k, &v, 8);
-        }
-        for (; k < sz; ++k)
-            out_chars[dst + k] = chars[begin + k];
+        if (sz)
+            str_copy_value(out_chars + dst, chars + str_value(offsets, indexes[i]).begin, sz);
     }
 }
 
@@ -460,58 +343,34 @@ extern "C" int chgpu_string_index(chgpu_ctx * ctx, const chgpu_col * offsets_u64
                                   chgpu_col ** out_offsets_u64, chgpu_col ** out_chars_u8)
 {
     ChgpuDeviceGuard _dev_guard(ctx);
-    CHGPU_REQUIRE(ctx && offsets_u64 && chars_u8 && indexes_u64 && out_offsets_u64 && out_chars_u8, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    CHGPU_REQUIRE(offsets_u64->type == CHGPU_U64 && chars_u8->type == CHGPU_U8 && indexes_u64->type == CHGPU_U64, CHGPU_ERR_BAD_ARGUMENTS,
-                  "ColumnString = UInt64 offsets + UInt8 chars; the indexes are a UInt64 column");
-    const u64 rows = offsets_u64->rows;
+    StrColumn col;
+    CHGPU_TRY(str_column_begin(ctx, offsets_u64, chars_u8, indexes_u64 && out_offsets_u64 && out_chars_u8, [&] {
+        CHGPU_REQUIRE(indexes_u64->type == CHGPU_U64, CHGPU_ERR_BAD_ARGUMENTS, "the indexes are a UInt64 column");
+        return (int)CHGPU_OK;
+    }, &col));
     const u64 n = limit && limit < indexes_u64->rows ? limit : indexes_u64->rows;
-    CHGPU_TRY(str_validate_offsets(ctx, offsets_u64, chars_u8));
-    chgpu_col * oo = nullptr, * oc = nullptr;
-    auto fail = [&](int code) {
-        if (oo)
-            chgpu_col_free(oo);
-        if (oc)
-            chgpu_col_free(oc);
-        return code;
-    };
-    u64 out_bytes = 0;
-    SsHold hold(ctx);
-    u32 * bytes = nullptr;
-    u64 * bpos = nullptr;
+    const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
+    PairAllocs mem = str_call(ctx, "string index");
+    PairTemps tmp(mem);
+    StrValuesLayout l{};
     if (n)
     {
-        const size_t b_bytes = ss_al(n * 4), b_bpos = ss_al(n * 8), b_tmp = ss_al(chgpu_scan_tmp_bytes(n));
-        void * mem = nullptr;
-        CHGPU_TRY(hold.alloc(b_bytes + b_bpos + 256 + b_tmp, &mem));
-        char * p = (char *)mem;
-        bytes = (u32 *)p; p += b_bytes;
-        bpos = (u64 *)p; p += b_bpos;
-        u64 * totals = (u64 *)p; p += 256; // [0] bytes, [1] bad index flag, [2] too long flag
-        void * tmp = p;
-        CHGPU_HIP(hipMemsetAsync(totals, 0, 256, ctx->stream));
-        hipLaunchKernelGGL(k_str_index_sizes, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const u64 *)offsets_u64->data, rows,
-                           (const u64 *)indexes_u64->data, n, bytes, (u32 *)(totals + 1), (u32 *)(totals + 2));
+        CHGPU_TRY(str_carve(tmp, [&](uintptr_t base) { return str_values_lay(base, n, false, chgpu_scan_tmp_bytes(n), &l); }));
+        CHGPU_HIP(hipMemsetAsync(l.words, 0, sizeof(StrLayoutWords), ctx->stream));
+        hipLaunchKernelGGL(k_str_index_sizes, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, col.rows, (const u64 *)indexes_u64->data, n, l.sizes,
+                           (u32 *)&l.words->bad_index, (u32 *)&l.words->too_long);
         ctx->counters[6] += 1;
-        CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, bytes, bpos, n, totals, tmp, b_tmp));
-        u64 host_totals[3] = {0, 0, 0};
-        CHGPU_TRY(chgpu_read_back(ctx, totals, host_totals, sizeof(host_totals)));
-        CHGPU_REQUIRE(!host_totals[1], CHGPU_ERR_BAD_ARGUMENTS, "an index is not below the column's %llu rows", (unsigned long long)rows);
-        CHGPU_REQUIRE(!host_totals[2], CHGPU_ERR_NOT_IMPLEMENTED, "a value of 4 GiB or more");
-        out_bytes = host_totals[0];
     }
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, n, &oo));
-    int rc = chgpu_col_new(ctx, CHGPU_U8, out_bytes, &oc);
-    if (rc != CHGPU_OK)
-        return fail(rc);
+    StrLayoutWords words;
+    StrCols<> out;
+    CHGPU_TRY(str_layout_values(ctx, mem, l, n, false, col.rows, &words, &out));
     if (n)
     {
-        hipLaunchKernelGGL(k_str_index_move, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const u64 *)offsets_u64->data,
-                           (const u8 *)chars_u8->data, (const u64 *)indexes_u64->data, (const u32 *)bytes, (const u64 *)bpos, n, (u64 *)oo->data, (u8 *)oc->data);
+        hipLaunchKernelGGL(k_str_index_move, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, col.chars, (const u64 *)indexes_u64->data, (const u32 *)l.sizes,
+                           (const u64 *)l.pos, n, (u64 *)out.v[0]->data, (u8 *)out.v[1]->data);
         ctx->counters[6] += 1;
-        if (hipGetLastError() != hipSuccess)
-            return fail(chgpu_set_error(CHGPU_ERR_DEVICE, "string index kernels failed to launch"));
+        CHGPU_REQUIRE(hipGetLastError() == hipSuccess, CHGPU_ERR_DEVICE, "string index kernels failed to launch");
     }
-    *out_offsets_u64 = oo;
-    *out_chars_u8 = oc;
+    out.give(out_offsets_u64, out_chars_u8);
     return CHGPU_OK;
 }

@@ -353,13 +353,14 @@ def test_string_hash_matches_the_kernel_source_compiled_for_the_host(tmp_path):
     import subprocess
     src = open(STRING_SRC).read()
     internal = open(os.path.join(os.path.dirname(STRING_SRC), "chgpu_internal.h")).read()
+    column = open(os.path.join(os.path.dirname(STRING_SRC), "string_column.h")).read()   # the one str_load8 of the string kernels
 
     def cut(text, head):
         m = re.search(r"__device__ __forceinline__ " + re.escape(head) + r"\s*\{.*?\n\}", text, re.S)
         assert m, head
         return m.group(0)
     code = "\n".join(["#include <cstdint>", "typedef uint64_t u64; typedef uint8_t u8;", "#define __device__", "#define __forceinline__ inline",
-                      cut(internal, "u64 dev_intHash64(u64 x)"), cut(src, "u64 str_load8(const u8 * p)"), cut(src, "u64 str_hash_bytes(const u8 * p, u64 len)"),
+                      cut(internal, "u64 dev_intHash64(u64 x)"), cut(column, "u64 str_load8(const u8 * p)"), cut(src, "u64 str_hash_bytes(const u8 * p, u64 len)"),
                       'extern "C" u64 host_str_hash(const u8 * p, u64 len) { return str_hash_bytes(p, len); }', ""])
     (tmp_path / "h.cpp").write_text(code)
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-shared", "-fPIC", str(tmp_path / "h.cpp"), "-o", str(tmp_path / "h.so")])

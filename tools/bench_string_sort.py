@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """ORDER BY over a String column on the device: chgpu_string_sort_permutation (MSD sort in 8-byte words, every round the stable radix
-passes of the numeric sort) and chgpu_string_index, HBM-resident inputs.  Next to every case: the same number of rows sorted as a UInt64
-column by chgpu_sort_permutation on the same build (the floor of a one-round sort: 8 passes against 9 plus the key gather), and a
+passes of the numeric sort), chgpu_string_index and chgpu_string_filter by a 50 % random mask, HBM-resident inputs.  Next to every
+case: the same number of rows sorted as a UInt64 column by chgpu_sort_permutation on the same build (the floor of a one-round sort: 8 passes against 9 plus the key gather), and a
 one-core numpy stable argsort of the same values as a fixed-width byte dtype.
 usage: bench_string_sort.py [rows]  -> one JSON object"""
 import json
@@ -127,6 +127,14 @@ for name, make in cases:
     perm = cs.get_permutation()
     di = best_of(lambda: cs.index(perm))
     del perm
+    # ColumnString.filter by a random mask that keeps half of the rows: 9 bytes per row (offset, mask byte), the kept values read and written
+    keep = torch.rand(rows, device=dev, generator=g) < 0.5
+    kept = int(keep.sum())
+    mask8 = keep.to(torch.uint8)
+    mask = ctx.wrap(mask8.data_ptr(), np.uint8, rows, keepalive=mask8)
+    assert cs.filter(mask).size() == kept
+    df = best_of(lambda: cs.filter(mask))
+    del mask, mask8, keep
     m = min(rows, 5_000_000)
     host = body[:m].cpu().numpy().copy().view(f"S{width}").reshape(m)
     t0 = time.perf_counter(); np.argsort(host, kind="stable"); tc = time.perf_counter() - t0
@@ -134,6 +142,7 @@ for name, make in cases:
                 "ms": dt * 1e3, "ms_per_active_Mrow": dt * 1e3 / (sum(active) / 1e6), "ms_descending": dd * 1e3, "ms_limit_10": dl * 1e3, "rows_per_s": rows / dt,
                 "ratio_to_uint64_sort": dt / u64_s, "ratio_to_uint64_sort_per_active_row": dt / (sum(active) / rows) / u64_s,
                 "string_index_by_the_permutation_ms": di * 1e3, "string_index_GBps": (2 * (width + 1) + 32) * rows / di / 1e9,
+                "string_filter_half_ms": df * 1e3, "string_filter_half_GBps": (2 * (width + 1) * kept + 9 * rows) / df / 1e9,
                 "cpu_numpy_stable_argsort_rows_per_s_1thread": m / tc, "cpu_sample_rows": m, "speedup_over_numpy_1thread": (rows / dt) / (m / tc)})
     del cs, body
     ctx.trim()
