@@ -206,6 +206,7 @@ SIGNATURES = {
     "chgpu_window_create": (_i, [_vp, _vp, _u32, _vp, _u32, _u64, _pp]),
     "chgpu_window_counts": (_i, [_vp, _pu64, _pu64, _pu64]),
     "chgpu_window_evaluate": (_i, [_vp, _i, C.POINTER(WindowFrame), _vp, _u64, _u64, _pp]),
+    "chgpu_window_evaluate_framed": (_i, [_vp, _i, C.POINTER(WindowFrame), _vp, _i, _vp, _u64, _u64, _pp]),
     "chgpu_window_free": (_i, [_vp]),
     "chgpu_comm_unique_id": (_i, [_vp]),
     "chgpu_comm_init": (_i, [_vp, _i, _i, _vp, _pp]),

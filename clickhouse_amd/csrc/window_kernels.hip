@@ -16,9 +16,14 @@
 //   output     k_win_out_rank (row_number / rank / dense_rank / count), k_win_out_sum (sum / avg), k_win_out_extremum (min / max),
 //              k_win_out_pick<W> (first_value / last_value / lagInFrame / leadInFrame): row i, its bounds, the scan array -> the result;
 //              the frame itself is win_frame_of (window_host.h), the code the host driver tests
+//   framed     chgpu_window_evaluate_framed (window_frames_host.h): k_win_range_bound<X> searches the ORDER BY column for the bounds of a
+//              RANGE frame with offsets into a call's own fs[] / fe[], which every output kernel reads through win_row_frame;
+//              k_win_ext_masks (a monotone-stack mask per row of a 64-row block), k_win_ext_level (one level of the sparse table over the
+//              blocks' extrema per launch) and k_win_out_extremum_any<W> are min / max over any frame
 // The handle's pool memory and a call's temporaries are pair_pool.h (PairMem, PairAllocs without a refusal hook, PairTemps).
 #include "block_scan.h"
 #include "pair_pool.h"
+#include "window_frames_host.h"
 #include "window_host.h"
 
 static constexpr u32 WIN_INF = 0xFFFFFFFFu;
@@ -393,11 +398,13 @@ struct WinBounds
     const u32 * gs;
     const u32 * ge;
     const u32 * dense;
+    const u32 * fs; // a call's own per-row frame begins / ends (the search behind a RANGE offset); NULL: the bound comes from win_frame_of
+    const u32 * fe;
 };
 
 struct WinRow4
 {
-    u32 ps[4], pe[4], gs[4], ge[4];
+    u32 ps[4], pe[4], gs[4], ge[4], fs[4], fe[4];
 };
 
 __device__ __forceinline__ void win_load4(const u32 * __restrict__ p, u64 i0, u32 out[4])
@@ -417,6 +424,18 @@ __device__ __forceinline__ void win_load_bounds(const WinBounds & b, u64 i0, Win
     win_load4(b.pe, i0, r->pe);
     win_load4(b.gs, i0, r->gs);
     win_load4(b.ge, i0, r->ge);
+    win_load4(b.fs, i0, r->fs);
+    win_load4(b.fe, i0, r->fe);
+}
+
+// the frame of row i, the k-th of the thread's four: win_frame_of, with the bounds that were searched taken from their arrays
+__device__ __forceinline__ void win_row_frame(const chgpu_window_frame & frame, const WinBounds & b, const WinRow4 & r, u32 k, u64 i, u64 * fs, u64 * fe)
+{
+    win_frame_of(frame, i, r.ps[k], r.pe[k], r.gs[k], r.ge[k], fs, fe);
+    if (b.fs)
+        *fs = r.fs[k];
+    if (b.fe)
+        *fe = r.fe[k];
 }
 
 // four values of W bytes to out[i0 .. i0 + 4): one access where all four rows exist, else row by row
@@ -473,7 +492,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_out_rank(int function, chgp
         else
         {
             u64 fs, fe;
-            win_frame_of(frame, i, r.ps[k], r.pe[k], r.gs[k], r.ge[k], &fs, &fe);
+            win_row_frame(frame, b, r, k, i, &fs, &fe);
             v[k] = fe - fs;
         }
     }
@@ -498,7 +517,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_out_sum(int is_avg, int num
         if (i >= n)
             continue;
         u64 fs, fe;
-        win_frame_of(frame, i, r.ps[k], r.pe[k], r.gs[k], r.ge[k], &fs, &fe);
+        win_row_frame(frame, b, r, k, i, &fs, &fe);
         const u64 sum = P[fe] - P[fs];
         if (is_avg)
         {
@@ -530,7 +549,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_out_extremum(int type, int 
         if (i >= n)
             continue;
         u64 fs, fe;
-        win_frame_of(frame, i, r.ps[k], r.pe[k], r.gs[k], r.ge[k], &fs, &fe);
+        win_row_frame(frame, b, r, k, i, &fs, &fe);
         if (fs >= fe)
             continue;
         const u64 key = M[backward ? fs : fe - 1];
@@ -561,7 +580,7 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_out_pick(int pick, chgpu_wi
         if (i >= n)
             continue;
         u64 fs, fe;
-        win_frame_of(frame, i, r.ps[k], r.pe[k], r.gs[k], r.ge[k], &fs, &fe);
+        win_row_frame(frame, b, r, k, i, &fs, &fe);
         if (pick == WIN_PICK_FIRST || pick == WIN_PICK_LAST)
             v[k] = fs < fe ? (u64)x[pick == WIN_PICK_FIRST ? fs : fe - 1] : 0;
         else
@@ -569,6 +588,117 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_out_pick(int pick, chgpu_wi
             u64 t;
             v[k] = win_shifted_row(pick == WIN_PICK_LEAD, i, offset, fs, fe, &t) ? (u64)x[t] : (u64)(W)default_bits;
         }
+    }
+    win_store4(out, i0, n, v);
+}
+
+// ---------------------------------------------------------------------------------------------
+// frames of the framed entry (chgpu_window_evaluate_framed): the search behind a RANGE offset, and min / max over any frame
+// ---------------------------------------------------------------------------------------------
+// one searched bound: `k PRECEDING` or `k FOLLOWING` (k > 0) into out[]; out == NULL: the bound is not searched
+struct WinRangeSide
+{
+    u32 * out;
+    u64 k;
+    int following;
+};
+
+// A thread per row: win_range_bound_of (window_frames_host.h) from the row's own position towards the partition edge the bound names.
+// Neighbouring lanes start at neighbouring rows and gallop in step, so a wave's loads fall into the same few lines.
+template <typename X>
+__global__ __launch_bounds__(WIN_THREADS) void k_win_range_bound(const X * __restrict__ x, int descending, const u32 * __restrict__ ps, const u32 * __restrict__ pe, u64 n,
+                                                                 WinRangeSide begin, WinRangeSide end)
+{
+    const u64 i = (u64)blockIdx.x * WIN_THREADS + threadIdx.x;
+    if (i >= n)
+        return;
+    if (begin.out)
+        begin.out[i] = (u32)win_range_bound_of(x, i, begin.following ? 0 : (u64)ps[i], begin.following ? (u64)pe[i] : 0, begin.following != 0, false, descending != 0, begin.k);
+    if (end.out)
+        end.out[i] = (u32)win_range_bound_of(x, i, end.following ? 0 : (u64)ps[i], end.following ? (u64)pe[i] : 0, end.following != 0, true, descending != 0, end.k);
+}
+
+// One wave per block of 64 rows, a lane per row.  mask[r] bit p: no row q in (p, r] of the block has key[q] >= key[p].  For every p the
+// wave broadcasts key[p] and ballots key >= key[p]; the lowest such row above p ends the run of rows whose mask holds p.  Rows past the
+// input hold the worst key, 0; they lie above every row of the input, so no mask of a row of the input sees them.  top[block]: the
+// block's extremum key, level 0 of the table.
+__global__ __launch_bounds__(WIN_THREADS) void k_win_ext_masks(const void * __restrict__ x, int type, int is_min, u64 n, u64 n_blocks, u64 * __restrict__ mask,
+                                                               u64 * __restrict__ top)
+{
+    const u32 lane = threadIdx.x & 63;
+    const u64 block = (u64)blockIdx.x * (WIN_THREADS / 64) + (threadIdx.x >> 6);
+    if (block >= n_blocks) // (whole waves leave: no barrier below)
+        return;
+    const u64 row = block * WIN_EXT_BLOCK + lane;
+    const u64 key = row < n ? win_ext_key(x, type, is_min != 0, row) : 0;
+    u64 m = 0;
+#pragma unroll // (all 64: p is a constant in every copy, so a copy touches one half of m and compares the lane with constants)
+    for (u32 p = 0; p < 64; ++p)
+    {
+        const u64 kp = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(key >> 32), (int)p) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)key, (int)p);
+        const u64 ge = __ballot(key >= kp) & ~(((u64)2 << p) - 1); // the rows above p that end it (p = 63: 2 << 63 wraps to 0, none)
+        const u32 held = (ge ? (u32)__builtin_ctzll(ge) : 64) - p; // the rows p .. p + held - 1 hold bit p
+        if (lane - p < held)                                       // (unsigned: a lane below p wraps past every `held`)
+            m |= (u64)1 << p;
+    }
+    mask[row] = m; // (the mask array is whole blocks long)
+    const u64 best = wave_reduce_all<MaxU64>(key);
+    if (lane == 0)
+        top[block] = best;
+}
+
+// one level of the sparse table from the level below: cur[b] = max(prev[b], prev[b + half]), where both cells exist
+__global__ __launch_bounds__(WIN_THREADS) void k_win_ext_level(const u64 * __restrict__ prev, u64 * __restrict__ cur, u64 n_blocks, u64 half)
+{
+    const u64 b = (u64)blockIdx.x * WIN_THREADS + threadIdx.x;
+    if (b >= n_blocks)
+        return;
+    const u64 a = prev[b];
+    cur[b] = b + half < n_blocks ? MaxU64::comb(a, prev[b + half]) : a;
+}
+
+// min / max over [fs, fe): inside one block the mask of the last row answers; over several blocks the first block's suffix (the mask of
+// its last row), the last block's prefix (the mask of the frame's last row) and two cells of the table for the blocks between
+template <typename W>
+__global__ __launch_bounds__(WIN_THREADS) void k_win_out_extremum_any(int type, int is_min, chgpu_window_frame frame, WinBounds b, u64 n, const void * __restrict__ x,
+                                                                      const u64 * __restrict__ mask, const u64 * __restrict__ table, u64 n_blocks, W * __restrict__ out)
+{
+    const u64 i0 = win_first_row();
+    if (i0 >= n)
+        return;
+    WinRow4 r;
+    win_load_bounds(b, i0, &r);
+    u64 v[4];
+#pragma unroll
+    for (u32 k = 0; k < 4; ++k)
+    {
+        const u64 i = i0 + k;
+        v[k] = 0;
+        if (i >= n)
+            continue;
+        u64 fs, fe;
+        win_row_frame(frame, b, r, k, i, &fs, &fe);
+        if (fs >= fe)
+            continue;
+        const u64 l = fs, last = fe - 1, bl = l / WIN_EXT_BLOCK, br = last / WIN_EXT_BLOCK;
+        u64 key;
+        if (bl == br)
+            key = win_ext_key(x, type, is_min != 0, win_ext_in_block(mask[last], l));
+        else
+        {
+            const u64 k0 = win_ext_key(x, type, is_min != 0, win_ext_in_block(mask[bl * WIN_EXT_BLOCK + WIN_EXT_BLOCK - 1], l));
+            const u64 k1 = win_ext_key(x, type, is_min != 0, win_ext_in_block(mask[last], br * WIN_EXT_BLOCK));
+            key = MaxU64::comb(k0, k1);
+            if (br - bl > 1)
+            {
+                u32 level;
+                u64 c0, c1;
+                win_ext_cells(bl, br, &level, &c0, &c1);
+                key = MaxU64::comb(key, MaxU64::comb(table[level * n_blocks + c0], table[level * n_blocks + c1]));
+            }
+        }
+        const u64 bits = agg_order_key_inverse(is_min ? ~key : key, type);
+        v[k] = type == CHGPU_F32 ? (u64)__float_as_uint((float)__longlong_as_double((long long)bits)) : bits;
     }
     win_store4(out, i0, n, v);
 }
@@ -586,6 +716,8 @@ struct chgpu_window
     WinLazy lazy;
     bool have_totals = false;
     u64 partitions = 0, peer_groups = 0;
+    u32 n_order = 0;     // ORDER BY columns given to create, and the type of the first (-1: none): what a RANGE offset checks its
+    int order_type = -1; // order column against
     PairAllocs mem; // (pair_pool.h; no refusal hook here)
 };
 
@@ -626,6 +758,8 @@ extern "C" int chgpu_window_create(chgpu_ctx * ctx, const chgpu_col * const * pa
     w->ctx = w->mem.ctx = ctx;
     w->rows = rows;
     w->n_tiles = win_tiles(rows);
+    w->n_order = n_order;
+    w->order_type = n_order ? order_cols[0]->type : -1;
     chgpu_ctx_retain(ctx);
     if (rows)
     {
@@ -737,31 +871,32 @@ static int win_result_type(int function, int arg_type)
     }
 }
 
-extern "C" int chgpu_window_evaluate(chgpu_window * w, int function, const chgpu_window_frame * frame_in, const chgpu_col * arg, uint64_t offset,
-                                     uint64_t default_bits, chgpu_col ** out)
+// the eight integer types an ORDER BY column of a RANGE offset has: fn(X{})
+template <typename F>
+static void win_dispatch_order_type(int type, F && fn)
 {
-    CHGPU_REQUIRE(w && out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    chgpu_ctx * ctx = w->ctx;
-    const char * msg = "";
-    chgpu_window_frame frame = frame_in ? *frame_in : win_default_frame();
-    int rc = CHGPU_OK;
-    if (win_function_ignores_frame(function))
-        frame = win_default_frame();
-    else if ((rc = win_check_frame(frame, &msg)) != CHGPU_OK)
-        return chgpu_set_error(rc, "window: %s", msg);
-    if (arg)
+    switch (type)
     {
-        CHGPU_REQUIRE(chgpu_type_size(arg->type) != 0, CHGPU_ERR_BAD_ARGUMENTS, "window: the argument column has an unknown type");
-        CHGPU_REQUIRE(arg->ctx && arg->ctx->device == ctx->device, CHGPU_ERR_BAD_ARGUMENTS, "window: the argument column lives on another device");
+        case CHGPU_I64: return fn(i64{});
+        case CHGPU_U64: return fn(u64{});
+        case CHGPU_I32: return fn(i32{});
+        case CHGPU_U32: return fn(u32{});
+        case CHGPU_I16: return fn(i16{});
+        case CHGPU_U16: return fn(u16{});
+        case CHGPU_I8: return fn(i8{});
+        default: return fn(u8{});
     }
-    u32 needs = 0;
-    bool backward = false;
-    if ((rc = win_plan(function, frame, arg ? arg->type : -1, &needs, &backward, &msg)) != CHGPU_OK)
-        return chgpu_set_error(rc, "window: %s", msg);
-    CHGPU_REQUIRE(!arg || arg->rows == w->rows, CHGPU_ERR_SIZES_MISMATCH, "window: the argument has %llu rows, the window %llu", (unsigned long long)arg->rows,
-                  (unsigned long long)w->rows);
+}
+
+// One validated call: `frame` and `plan` are what win_check_frame + win_plan (the old entry) or their _framed forms answered.  `order`
+// is read only where the plan searches a bound.
+static int win_run(chgpu_window * w, int function, const chgpu_window_frame & frame, const WinFramedPlan & plan, const chgpu_col * order, int descending,
+                   const chgpu_col * arg, uint64_t offset, uint64_t default_bits, chgpu_col ** out)
+{
+    chgpu_ctx * ctx = w->ctx;
     ChgpuDeviceGuard guard(ctx);
     const u64 n = w->rows;
+    const u32 needs = plan.needs;
     const int arg_type = arg ? arg->type : -1;
     chgpu_col * res = nullptr;
     if (n == 0)
@@ -774,13 +909,29 @@ extern "C" int chgpu_window_evaluate(chgpu_window * w, int function, const chgpu
     PairTemps tmp(w->mem);
     u64 * scan = nullptr;   // P[n + 1] or M[n]
     void * tiles = nullptr; // u64 / WinSeg per tile
+    u64 * mask = nullptr;   // general min / max: u64 per row of the whole blocks, then the table's levels of n_blocks cells each
+    u64 * table = nullptr;
+    u32 * fs = nullptr;     // searched bounds, whole tiles long; a call's own, not kept in the handle
+    u32 * fe = nullptr;
     const bool is_sum = function == CHGPU_WIN_SUM || function == CHGPU_WIN_AVG;
     const bool is_ext = function == CHGPU_WIN_MIN || function == CHGPU_WIN_MAX;
-    if (is_sum || is_ext)
+    const bool general = plan.ext == WIN_EXT_GENERAL, backward = plan.ext == WIN_EXT_BACKWARD;
+    const u64 n_blocks = win_ext_blocks(n);
+    const u32 levels = general ? win_ext_levels(plan.width, n_blocks) : 0;
+    if (general)
+    {
+        CHGPU_TRY(tmp.alloc(n_blocks * WIN_EXT_BLOCK * sizeof(u64), (void **)&mask));
+        CHGPU_TRY(tmp.alloc(n_blocks * (levels ? levels : 1) * sizeof(u64), (void **)&table));
+    }
+    else if (is_sum || is_ext)
     {
         CHGPU_TRY(tmp.alloc((n + 1) * sizeof(u64), (void **)&scan));
         CHGPU_TRY(tmp.alloc(w->n_tiles * sizeof(WinSeg), &tiles));
     }
+    if (plan.search_begin)
+        CHGPU_TRY(tmp.alloc(win_padded_rows(n) * sizeof(u32), (void **)&fs));
+    if (plan.search_end)
+        CHGPU_TRY(tmp.alloc(win_padded_rows(n) * sizeof(u32), (void **)&fe));
     CHGPU_TRY(win_ensure_bounds(w, needs));
     CHGPU_TRY(chgpu_col_new(ctx, win_result_type(function, arg_type), n, &res));
 
@@ -790,8 +941,21 @@ extern "C" int chgpu_window_evaluate(chgpu_window * w, int function, const chgpu
     b.gs = needs & WIN_B_GS ? (const u32 *)w->bounds[2].p : nullptr;
     b.ge = needs & WIN_B_GE ? (const u32 *)w->bounds[3].p : nullptr;
     b.dense = needs & WIN_B_DENSE ? (const u32 *)w->bounds[4].p : nullptr;
+    b.fs = fs;
+    b.fe = fe;
     const dim3 tile_grid((u32)w->n_tiles), block(WIN_THREADS), out_grid((u32)win_out_blocks(n));
     hipStream_t st = ctx->stream;
+    if (fs || fe)
+    {
+        const WinRangeSide begin{fs, frame.begin_offset, frame.begin_kind == CHGPU_BOUND_OFFSET_FOLLOWING ? 1 : 0};
+        const WinRangeSide end{fe, frame.end_offset, frame.end_kind == CHGPU_BOUND_OFFSET_FOLLOWING ? 1 : 0};
+        const dim3 row_grid((u32)(n / WIN_THREADS + (n % WIN_THREADS != 0)));
+        win_dispatch_order_type(order->type, [&](auto tag) {
+            typedef decltype(tag) X;
+            hipLaunchKernelGGL(k_win_range_bound<X>, row_grid, block, 0, st, (const X *)order->data, descending ? 1 : 0, b.ps, b.pe, n, begin, end);
+        });
+        ctx->counters[6] += 1;
+    }
     if (is_sum)
     {
         hipLaunchKernelGGL(k_win_tile_sums, tile_grid, block, 0, st, (const void *)arg->data, arg_type, n, (u64 *)tiles);
@@ -800,6 +964,22 @@ extern "C" int chgpu_window_evaluate(chgpu_window * w, int function, const chgpu
         hipLaunchKernelGGL(k_win_out_sum, out_grid, block, 0, st, function == CHGPU_WIN_AVG ? 1 : 0, chgpu_type_is_signed(arg_type) ? 1 : 0, frame, b, n,
                            (const u64 *)scan, (u64 *)res->data);
         ctx->counters[6] += 4;
+    }
+    else if (general)
+    {
+        const int is_min = function == CHGPU_WIN_MIN ? 1 : 0;
+        const u32 waves = WIN_THREADS / 64;
+        hipLaunchKernelGGL(k_win_ext_masks, dim3((u32)(n_blocks / waves + (n_blocks % waves != 0))), block, 0, st, (const void *)arg->data, arg_type, is_min, n, n_blocks,
+                           mask, table);
+        const dim3 level_grid((u32)(n_blocks / WIN_THREADS + (n_blocks % WIN_THREADS != 0)));
+        for (u32 j = 1; j < levels; ++j) // every level a launch of its own: it reads what the launch before wrote
+            hipLaunchKernelGGL(k_win_ext_level, level_grid, block, 0, st, (const u64 *)(table + (j - 1) * n_blocks), table + j * n_blocks, n_blocks, (u64)1 << (j - 1));
+        dispatch_width(chgpu_type_size(arg_type), [&](auto tag) {
+            typedef decltype(tag) W;
+            hipLaunchKernelGGL(k_win_out_extremum_any<W>, out_grid, block, 0, st, arg_type, is_min, frame, b, n, (const void *)arg->data, (const u64 *)mask,
+                               (const u64 *)table, n_blocks, (W *)res->data);
+        });
+        ctx->counters[6] += 2 + (levels > 1 ? levels - 1 : 0);
     }
     else if (is_ext)
     {
@@ -846,4 +1026,76 @@ extern "C" int chgpu_window_evaluate(chgpu_window * w, int function, const chgpu
     }
     *out = res;
     return CHGPU_OK;
+}
+
+static int win_check_arg(const chgpu_ctx * ctx, const chgpu_col * arg)
+{
+    if (arg)
+    {
+        CHGPU_REQUIRE(chgpu_type_size(arg->type) != 0, CHGPU_ERR_BAD_ARGUMENTS, "window: the argument column has an unknown type");
+        CHGPU_REQUIRE(arg->ctx && arg->ctx->device == ctx->device, CHGPU_ERR_BAD_ARGUMENTS, "window: the argument column lives on another device");
+    }
+    return CHGPU_OK;
+}
+
+extern "C" int chgpu_window_evaluate(chgpu_window * w, int function, const chgpu_window_frame * frame_in, const chgpu_col * arg, uint64_t offset,
+                                     uint64_t default_bits, chgpu_col ** out)
+{
+    CHGPU_REQUIRE(w && out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    const char * msg = "";
+    chgpu_window_frame frame = frame_in ? *frame_in : win_default_frame();
+    int rc = CHGPU_OK;
+    if (win_function_ignores_frame(function))
+        frame = win_default_frame();
+    else if ((rc = win_check_frame(frame, &msg)) != CHGPU_OK)
+        return chgpu_set_error(rc, "window: %s", msg);
+    CHGPU_TRY(win_check_arg(w->ctx, arg));
+    u32 needs = 0;
+    bool backward = false;
+    if ((rc = win_plan(function, frame, arg ? arg->type : -1, &needs, &backward, &msg)) != CHGPU_OK)
+        return chgpu_set_error(rc, "window: %s", msg);
+    CHGPU_REQUIRE(!arg || arg->rows == w->rows, CHGPU_ERR_SIZES_MISMATCH, "window: the argument has %llu rows, the window %llu", (unsigned long long)arg->rows,
+                  (unsigned long long)w->rows);
+    WinFramedPlan plan;
+    plan.needs = needs;
+    plan.ext = function == CHGPU_WIN_MIN || function == CHGPU_WIN_MAX ? (backward ? WIN_EXT_BACKWARD : WIN_EXT_FORWARD) : WIN_EXT_NONE;
+    return win_run(w, function, frame, plan, nullptr, 0, arg, offset, default_bits, out);
+}
+
+extern "C" int chgpu_window_evaluate_framed(chgpu_window * w, int function, const chgpu_window_frame * frame_in, const chgpu_col * order, int descending,
+                                            const chgpu_col * arg, uint64_t offset, uint64_t default_bits, chgpu_col ** out)
+{
+    CHGPU_REQUIRE(w && out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    const char * msg = "";
+    chgpu_window_frame frame = frame_in ? *frame_in : win_default_frame();
+    int rc = CHGPU_OK;
+    if (win_function_ignores_frame(function))
+        frame = win_default_frame();
+    else if ((rc = win_check_frame_framed(frame, &msg)) != CHGPU_OK)
+        return chgpu_set_error(rc, "window: %s", msg);
+    CHGPU_TRY(win_check_arg(w->ctx, arg));
+    if (order)
+    {
+        CHGPU_REQUIRE(chgpu_type_size(order->type) != 0, CHGPU_ERR_BAD_ARGUMENTS, "window: the order column has an unknown type");
+        CHGPU_REQUIRE(order->ctx && order->ctx->device == w->ctx->device, CHGPU_ERR_BAD_ARGUMENTS, "window: the order column lives on another device");
+    }
+    WinFramedPlan plan;
+    if ((rc = win_plan_framed(function, frame, arg ? arg->type : -1, order ? order->type : -1, &plan, &msg)) != CHGPU_OK
+        && !(rc == CHGPU_ERR_NOT_IMPLEMENTED && order && (w->n_order != 1 || order->type != w->order_type))) // (what the handle refuses comes first)
+        return chgpu_set_error(rc, "window: %s", msg);
+    if (order)
+    {
+        CHGPU_REQUIRE(w->n_order == 1, CHGPU_ERR_BAD_ARGUMENTS, "window: a RANGE frame with an offset needs a window with exactly one ORDER BY column, this one has %u",
+                      w->n_order);
+        CHGPU_REQUIRE(order->type == w->order_type, CHGPU_ERR_BAD_ARGUMENTS, "window: the order column's type differs from the one the window was created with");
+        CHGPU_REQUIRE(order->rows == w->rows, CHGPU_ERR_SIZES_MISMATCH, "window: the order column has %llu rows, the window %llu", (unsigned long long)order->rows,
+                      (unsigned long long)w->rows);
+    }
+    if (rc != CHGPU_OK)
+        return chgpu_set_error(rc, "window: %s", msg);
+    CHGPU_REQUIRE(!arg || arg->rows == w->rows, CHGPU_ERR_SIZES_MISMATCH, "window: the argument has %llu rows, the window %llu", (unsigned long long)arg->rows,
+                  (unsigned long long)w->rows);
+    if (plan.old_entry)
+        return chgpu_window_evaluate(w, function, frame_in, arg, offset, default_bits, out);
+    return win_run(w, function, win_frame_without_zero_range_offsets(frame), plan, order, descending, arg, offset, default_bits, out);
 }

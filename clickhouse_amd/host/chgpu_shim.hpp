@@ -2423,6 +2423,16 @@ struct WindowFrame
         return WindowFrame{CHGPU_FRAME_ROWS, begin_type_, begin_offset_, end_type_, end_offset_, false};
     }
     static WindowFrame range(int begin_type_, int end_type_) { return WindowFrame{CHGPU_FRAME_RANGE, begin_type_, 0, end_type_, 0, false}; }
+    /// RANGE with offsets over the ORDER BY column's values (a framed function: WindowFunctionDescription::framed)
+    static WindowFrame range(int begin_type_, uint64_t begin_offset_, int end_type_, uint64_t end_offset_)
+    {
+        return WindowFrame{CHGPU_FRAME_RANGE, begin_type_, begin_offset_, end_type_, end_offset_, false};
+    }
+    bool hasRangeOffset() const
+    {
+        const auto is_offset = [](int t) { return t == CHGPU_BOUND_OFFSET_PRECEDING || t == CHGPU_BOUND_OFFSET_FOLLOWING; };
+        return type == CHGPU_FRAME_RANGE && (is_offset(begin_type) || is_offset(end_type));
+    }
     chgpu_window_frame toC() const
     {
         return chgpu_window_frame{type, begin_type, end_type, 0, begin_offset, end_offset};
@@ -2431,6 +2441,8 @@ struct WindowFrame
 
 /// WindowFunctionDescription (WindowDescription.h): one function OVER the window -- which CHGPU_WIN_* function, its argument's position
 /// in the chunk (none for row_number / rank / dense_rank / count), its frame, and lagInFrame / leadInFrame's offset and default.
+/// framed: the function goes through chgpu_window_evaluate_framed, which also serves min / max over any frame and RANGE frames with
+/// offsets (those read the transform's first ORDER BY column and its direction).
 struct WindowFunctionDescription
 {
     int function = CHGPU_WIN_ROW_NUMBER;
@@ -2438,6 +2450,7 @@ struct WindowFunctionDescription
     WindowFrame frame;
     uint64_t offset = 1;
     uint64_t default_bits = 0; // the default value in the argument's type, zero-extended
+    bool framed = false;
 };
 
 /// WindowTransform (src/Processors/Transforms/WindowTransform.cpp) for one window definition behind a full sort (WindowStep after
@@ -2447,8 +2460,11 @@ struct WindowFunctionDescription
 class GpuWindowTransform
 {
 public:
-    GpuWindowTransform(ContextPtr ctx_, std::vector<size_t> partition_by_, std::vector<size_t> order_by_, std::vector<WindowFunctionDescription> functions_)
-        : ctx(std::move(ctx_)), partition_by(std::move(partition_by_)), order_by(std::move(order_by_)), functions(std::move(functions_)) {}
+    /// order_descending: the direction of order_by[0], read by framed functions over a RANGE frame with an offset
+    GpuWindowTransform(ContextPtr ctx_, std::vector<size_t> partition_by_, std::vector<size_t> order_by_, std::vector<WindowFunctionDescription> functions_,
+                       bool order_descending_ = false)
+        : ctx(std::move(ctx_)), partition_by(std::move(partition_by_)), order_by(std::move(order_by_)), functions(std::move(functions_)),
+          order_descending(order_descending_) {}
 
     void consume(Chunk chunk)
     {
@@ -2494,7 +2510,15 @@ public:
             const chgpu_window_frame frame = f.frame.toC();
             const chgpu_col * arg = f.argument ? out.columns.at(*f.argument)->handle() : nullptr;
             chgpu_col * res = nullptr;
-            check(chgpu_window_evaluate(w, f.function, f.frame.is_default ? nullptr : &frame, arg, f.offset, f.default_bits, &res));
+            if (f.framed)
+            {
+                const bool reads_frame = f.function >= CHGPU_WIN_COUNT;
+                const chgpu_col * order = reads_frame && !f.frame.is_default && f.frame.hasRangeOffset() && !o.empty() ? o[0] : nullptr;
+                check(chgpu_window_evaluate_framed(w, f.function, f.frame.is_default ? nullptr : &frame, order, order_descending ? 1 : 0, arg, f.offset,
+                                                   f.default_bits, &res));
+            }
+            else
+                check(chgpu_window_evaluate(w, f.function, f.frame.is_default ? nullptr : &frame, arg, f.offset, f.default_bits, &res));
             out.columns.push_back(std::make_shared<ColumnVector>(ctx, res));
         }
         return out;
@@ -2509,6 +2533,7 @@ private:
     std::vector<WindowFunctionDescription> functions;
     std::vector<Chunk> chunks;
     uint64_t partitions = 0, peer_groups = 0;
+    bool order_descending = false;
 };
 
 /// The merge of sorted runs of one Block layout: the runs' columns glued (chgpu_col_concat), merged by the description

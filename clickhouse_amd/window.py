@@ -46,8 +46,8 @@ def following(k):
 
 
 class Frame:
-    """ROWS | RANGE BETWEEN begin AND end.  Illegal frames (WindowFrame::checkValid) raise ValueError here; a legal frame the device does
-    not serve (RANGE with an offset) is answered by the library with NOT_IMPLEMENTED."""
+    """ROWS | RANGE BETWEEN begin AND end.  Illegal frames (WindowFrame::checkValid) raise ValueError here.  Window's own methods answer
+    a RANGE frame with an offset with NOT_IMPLEMENTED; Window.over(frame, order=...) serves it."""
 
     def __init__(self, type, begin, end):
         if type not in (K.FRAME_ROWS, K.FRAME_RANGE):
@@ -171,6 +171,11 @@ class Window:
                                               offset, bits, C.byref(out)))
         return Column(self.ctx, out)
 
+    def over(self, frame: Frame | None = None, order=None, descending: bool = False) -> "FramedWindow":
+        """this window with one frame, served by chgpu_window_evaluate_framed: every frame the methods below take, min / max over any
+        of them, and RANGE frames with offsets -- those need `order`, the window's one ORDER BY column, and its direction"""
+        return FramedWindow(self, frame, order, descending)
+
     def _eval(self, function, frame=None, x=None, offset=0, default=0):
         return self.evaluate_column(function, frame, x, offset, default).numpy()
 
@@ -194,7 +199,7 @@ class Window:
         return self._eval(K.WIN_AVG, frame, x)
 
     def min(self, x, frame: Frame | None = None):
-        """the frame must begin UNBOUNDED or end UNBOUNDED"""
+        """the frame must begin UNBOUNDED or end UNBOUNDED (Window.over(frame).min(x) takes any frame)"""
         return self._eval(K.WIN_MIN, frame, x)
 
     def max(self, x, frame: Frame | None = None):
@@ -211,3 +216,79 @@ class Window:
 
     def lead_in_frame(self, x, offset: int = 1, default=0, frame: Frame | None = None):
         return self._eval(K.WIN_LEAD_IN_FRAME, frame, x, offset, default)
+
+
+class FramedWindow:
+    """Window.over(frame, order, descending): one function per method over that frame through chgpu_window_evaluate_framed.  A RANGE
+    frame with an offset takes `order` (an integer column of the window's length, the one it was created with) -- checked here, before
+    the library is touched; any other frame takes none."""
+
+    def __init__(self, window: Window, frame: Frame | None = None, order=None, descending: bool = False):
+        if frame is not None and not isinstance(frame, Frame):
+            raise ValueError("frame must be a Frame or None (the default frame)")
+        offsets = (K.BOUND_OFFSET_PRECEDING, K.BOUND_OFFSET_FOLLOWING)
+        searched = frame is not None and frame.type == K.FRAME_RANGE and (frame.begin_kind in offsets or frame.end_kind in offsets)
+        if searched and order is None:
+            raise ValueError("a RANGE frame with an offset needs order=, the window's ORDER BY column")
+        if not searched and order is not None:
+            raise ValueError("order= is taken only with a RANGE frame that has an offset")
+        if order is not None:
+            if _tag_of(order, "order key") not in _INT_TAGS:
+                raise ValueError("a RANGE frame with an offset takes an integer ORDER BY column, not Float32 / Float64")
+            if len(order) != window.rows:
+                raise ValueError(f"the order column has {len(order)} rows, the window {window.rows}")
+            order = window.ctx.column(order)
+        self.window, self.frame, self.order, self.descending = window, frame, order, bool(descending)
+
+    def evaluate_column(self, function: int, x=None, offset: int = 0, default=0) -> Column:
+        """chgpu_window_evaluate_framed -> the result Column resident in HBM"""
+        w = self.window
+        takes_arg = function >= K.WIN_SUM
+        if takes_arg != (x is not None):
+            raise ValueError("the function takes an argument column" if takes_arg else "the function takes no argument column")
+        bits = 0
+        if takes_arg:
+            tag = _tag_of(x, "argument")
+            if len(x) != w.rows:
+                raise ValueError(f"the argument has {len(x)} rows, the window {w.rows}")
+            offset = _offset(offset)
+            if function in (K.WIN_LAG_IN_FRAME, K.WIN_LEAD_IN_FRAME):
+                bits = default_bits(tag, default)
+            x = w.ctx.column(x)
+        out = C.c_void_p()
+        fc = self.frame._c() if self.frame is not None else None
+        K.check(K.lib().chgpu_window_evaluate_framed(w._h, function, C.byref(fc) if fc is not None else None, self.order._h if self.order is not None else None,
+                                                     1 if self.descending else 0, x._h if x is not None else None, offset, bits, C.byref(out)))
+        return Column(w.ctx, out)
+
+    def _eval(self, function, x=None, offset=0, default=0):
+        return self.evaluate_column(function, x, offset, default).numpy()
+
+    def count(self):
+        return self._eval(K.WIN_COUNT)
+
+    def sum(self, x):
+        """integer arguments; Int64 / UInt64 wrap-around like SumSimple"""
+        return self._eval(K.WIN_SUM, x)
+
+    def avg(self, x):
+        return self._eval(K.WIN_AVG, x)
+
+    def min(self, x):
+        """any legal frame"""
+        return self._eval(K.WIN_MIN, x)
+
+    def max(self, x):
+        return self._eval(K.WIN_MAX, x)
+
+    def first_value(self, x):
+        return self._eval(K.WIN_FIRST_VALUE, x)
+
+    def last_value(self, x):
+        return self._eval(K.WIN_LAST_VALUE, x)
+
+    def lag_in_frame(self, x, offset: int = 1, default=0):
+        return self._eval(K.WIN_LAG_IN_FRAME, x, offset, default)
+
+    def lead_in_frame(self, x, offset: int = 1, default=0):
+        return self._eval(K.WIN_LEAD_IN_FRAME, x, offset, default)

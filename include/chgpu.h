@@ -751,6 +751,38 @@ int chgpu_window_evaluate(chgpu_window * window, int function, const chgpu_windo
                           const chgpu_col * arg /* NULL where the function takes none */,
                           uint64_t offset /* lag / lead */, uint64_t default_bits /* lag / lead */, chgpu_col ** out);
 int chgpu_window_free(chgpu_window * window);
+/* chgpu_window_evaluate_framed: chgpu_window_evaluate plus the two kinds of frame it refuses.  Everything chgpu_window_evaluate serves
+   is served here with the same results bit for bit (the same code runs), with `order` NULL.  On top of that:
+   (a) MIN / MAX over every legal frame, ROWS or RANGE: bounded on both sides, not containing the current row (5 PRECEDING .. 2
+       PRECEDING), empty (-> 0).  The extremum is taken in the order of chgpu_agg's min / max as above (NaN in its total-order place, +0.0
+       above -0.0) and the value's bits are returned.  A frame that begins UNBOUNDED_PRECEDING or ends UNBOUNDED_FOLLOWING keeps the
+       running extremum; every other one reads a 64-bit mask per row (the monotone stack of the row's 64-row block) and a sparse table
+       over the blocks' extrema: a few gathers per row whatever the frame's width.
+   (b) RANGE frames with OFFSET_PRECEDING / OFFSET_FOLLOWING bounds for COUNT, SUM, AVG, MIN, MAX, FIRST_VALUE, LAST_VALUE, LAG_IN_FRAME
+       and LEAD_IN_FRAME.  `order` is the window's one ORDER BY column x, sorted as it was given to chgpu_window_create, `descending` its
+       direction (0: ASC, 1: DESC; read only with `order`).  All arithmetic on values is exact, as if in unbounded integers: x[i] - k may
+       lie below the type's minimum (every row is >= it) and x[i] + k above its maximum (no row is) -- compareValuesWithOffset's overflow
+       branches.  Ascending, [ps, pe) the partition of row i:
+         bound           begin fs = first j in [ps, pe) with .. (else pe)    end fe = first j in [ps, pe) with .. (else pe)
+         k PRECEDING     x[j] >= x[i] - k                                    x[j] > x[i] - k
+         CURRENT_ROW     gs                                                  ge
+         k FOLLOWING     x[j] >= x[i] + k                                    x[j] > x[i] + k
+         UNBOUNDED       ps                                                  pe
+       Descending: the same over the negated values (k PRECEDING begins at the first j with x[j] <= x[i] + k).  An offset of 0 gives
+       gs / ge.  The legality rules are those above; a legal frame has fs <= fe.  `order` is one of the eight integer types; a
+       Float32 / Float64 order column -> CHGPU_ERR_NOT_IMPLEMENTED.  The handle must have been created with exactly one ORDER BY column
+       of that type and length (create records the count and the type, no reference to the keys).
+   Errors beyond those of chgpu_window_evaluate: NULL `order` with a RANGE frame that has an offset, `order` given with any other frame
+   (or with a function that ignores the frame), a handle created with 0 or >= 2 order columns, an order column whose type differs from
+   the one recorded at create -> CHGPU_ERR_BAD_ARGUMENTS; an order column of another length -> CHGPU_ERR_SIZES_MISMATCH.  That `order`
+   is the column the handle was created with, sorted that way, is not checked: if it is not sorted within its partitions the results
+   are unspecified, but every index a kernel forms stays inside [ps, pe] and every loop ends.  SUM / AVG over Float32 / Float64 stay
+   CHGPU_ERR_NOT_IMPLEMENTED, GROUPS frames and the rest of the list above stay not provided.  A failed call allocates nothing and leaves
+   the handle usable; *out is as for chgpu_window_evaluate.  The searched bounds are a call's temporaries, not kept in the handle. */
+int chgpu_window_evaluate_framed(chgpu_window * window, int function, const chgpu_window_frame * frame /* NULL = default */,
+                                 const chgpu_col * order /* the one ORDER BY column; required by a RANGE frame with an offset, else NULL */,
+                                 int descending /* 0: ORDER BY o ASC, 1: DESC; read only with `order` */,
+                                 const chgpu_col * arg, uint64_t offset, uint64_t default_bits, chgpu_col ** out);
 /* §8(f) rank 2 — LowCardinality keys (src/Columns/ColumnLowCardinality.h:27-69; low_cardinality_key* variants,
    AggregatedDataVariants.h:119-127; HashMethodSingleLowCardinalityColumn's per-position cache, ColumnsHashing.h:82-260).
    Every Block brings its own dictionary; the host resolves it against the query-wide dictionary into remap_u32[local position]
