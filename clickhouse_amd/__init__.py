@@ -21,7 +21,7 @@ from .group_array import GroupArray
 from .limit_by import BlockKeys, Distinct, LimitBy, distinct_block, limit_by_block
 from .window import CURRENT_ROW, UNBOUNDED, Frame, FramedWindow, Window, following, preceding
 from .merge_fold import (aggregating_merge, aggregating_merge_rows, collapsing_merge, collapsing_merge_rows, replacing_merge,
-                         replacing_merge_rows, summing_merge, summing_merge_rows)
+                         replacing_merge_rows, summing_merge, summing_merge_rows, versioned_collapsing_merge, versioned_collapsing_merge_rows)
 from .merge_sorted import MergeSorting, is_sorted, merge_sorted_blocks, merge_sorted_permutation
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -114,6 +114,7 @@ SIGNATURES = {
     "chgpu_is_sorted": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _pu64]),
     "chgpu_merge_replacing": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _u32, _vp, _vp, C.c_int32, _pp]),
     "chgpu_merge_collapsing": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _u32, _vp, _pp]),
+    "chgpu_merge_versioned_collapsing": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _u32, _vp, _pp, _pu64]),
     "chgpu_merge_folding": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), _u32, _pu64, _u32, _u32, _vp, C.POINTER(C.c_int32), _u32, C.c_int32,
                                  _pp, _pp, _pp]),
     "chgpu_weak_hash32": (_i, [_vp, _vp, _vp]),

@@ -294,15 +294,10 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_fold_offsets(const u32 * __res
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-struct FoldPrefix
-{
-    MergeKeys keys;
-    u64 rows = 0;
-};
-
+// (fold_validate, fold_check_column, fold_require_domain and fold_heads are declared in merge_keys.h: merge_versioned_kernels.hip takes them)
 // the shared argument prefix, in front of the device
-static int fold_validate(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, u32 n_keys,
-                         const uint64_t * run_offsets, u32 n_runs, u32 flags, FoldPrefix * px)
+int fold_validate(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, u32 n_keys,
+                  const uint64_t * run_offsets, u32 n_runs, u32 flags, FoldPrefix * px)
 {
     CHGPU_TRY(merge_validate(ctx, key_cols, descending, nan_direction_hint, n_keys, run_offsets, n_runs, &px->keys, &px->rows));
     CHGPU_REQUIRE(n_runs >= 1, CHGPU_ERR_BAD_ARGUMENTS, "no runs: a folding merge takes at least one");
@@ -310,7 +305,7 @@ static int fold_validate(chgpu_ctx * ctx, const chgpu_col * const * key_cols, co
     return CHGPU_OK;
 }
 
-static int fold_check_column(const chgpu_col * c, const char * what, int want_type, const char * type_name, u64 rows)
+int fold_check_column(const chgpu_col * c, const char * what, int want_type, const char * type_name, u64 rows)
 {
     CHGPU_REQUIRE(c->type == want_type, CHGPU_ERR_BAD_ARGUMENTS, "the %s column has the type %d: it is %s", what, c->type, type_name);
     CHGPU_REQUIRE(c->rows == rows, CHGPU_ERR_SIZES_MISMATCH, "the %s column has %llu rows, the run offsets end at %llu", what, (unsigned long long)c->rows,
@@ -319,7 +314,7 @@ static int fold_check_column(const chgpu_col * c, const char * what, int want_ty
 }
 
 // BAD_ARGUMENTS naming the lowest concatenated row whose value is outside the column's domain
-static int fold_require_domain(chgpu_ctx * ctx, PairTemps & tmp, const chgpu_col * c, int mode, u64 rows)
+int fold_require_domain(chgpu_ctx * ctx, PairTemps & tmp, const chgpu_col * c, int mode, u64 rows)
 {
     const u32 tiles = merge_tiles((u32)rows);
     void * partial = nullptr;
@@ -333,6 +328,12 @@ static int fold_require_domain(chgpu_ctx * ctx, PairTemps & tmp, const chgpu_col
         CHGPU_REQUIRE(bad == ~0ull, CHGPU_ERR_BAD_ARGUMENTS, "the sign of row %llu is neither 1 nor -1", (unsigned long long)bad);
     CHGPU_REQUIRE(bad == ~0ull, CHGPU_ERR_BAD_ARGUMENTS, "is_deleted of row %llu is neither 0 nor 1", (unsigned long long)bad);
     return CHGPU_OK;
+}
+
+void fold_heads(chgpu_ctx * ctx, const MergeKeys & keys, const u64 * words, const u32 * rows, u32 n, u8 * heads)
+{
+    hipLaunchKernelGGL(k_fold_heads, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, keys, words, rows, n, heads);
+    ctx->counters[6] += 1;
 }
 
 static void fold_free_cols(chgpu_col ** cols, u32 n)
@@ -382,13 +383,13 @@ static int fold_run(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const F
         CHGPU_TRY(tmp.alloc((size_t)tiles * sizeof(State), &carry));
         CHGPU_TRY(tmp.alloc((size_t)tiles * sizeof(u32), &counts));
         CHGPU_TRY(tmp.alloc(((size_t)tiles + 1) * sizeof(u64), &off));
-        hipLaunchKernelGGL(k_fold_heads, dim3(chgpu_grid_for(ctx, rows, 256, 8)), dim3(256), 0, ctx->stream, px.keys, words, rws, (u32)rows, (u8 *)heads);
+        fold_heads(ctx, px.keys, words, rws, (u32)rows, (u8 *)heads);
         hipLaunchKernelGGL(k_fold_tile<A>, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, a, (const u8 *)heads, rws, (u32)rows, (State *)agg_s, (u8 *)agg_f);
         hipLaunchKernelGGL(k_fold_carry<A>, dim3(1), dim3(FOLD_THREADS), 0, ctx->stream, a, (const State *)agg_s, (const u8 *)agg_f, tiles, (State *)carry);
         hipLaunchKernelGGL((k_fold_apply<A, false>), dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, a, (const u8 *)heads, rws, (u32)rows, (const State *)carry,
                            (u32 *)counts, (u8 *)thread_counts, (const u64 *)nullptr, (u64 *)nullptr, (u64 *)nullptr);
         hipLaunchKernelGGL(k_fold_offsets, dim3(1), dim3(FOLD_THREADS), 0, ctx->stream, (const u32 *)counts, tiles, (u64 *)off);
-        ctx->counters[6] += 5;
+        ctx->counters[6] += 4;
         tile_off = (const u64 *)off;
         CHGPU_TRY(chgpu_read_back(ctx, tile_off + tiles, &total, sizeof(u64)));
     }

@@ -58,3 +58,18 @@ int merge_order(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const Merge
                 const u64 ** words, const u32 ** row_numbers);
 // partial[n] -> out[0] = the minimum, by one workgroup (k_merge_min): one launch, counted
 void merge_lowest(chgpu_ctx * ctx, const u64 * partial, u32 n, u64 * out);
+
+// ---- merge_fold_kernels.hip, for the further operator over its groups (merge_versioned_kernels.hip) ----
+struct FoldPrefix
+{
+    MergeKeys keys;
+    u64 rows = 0;
+};
+// the argument prefix every folding merge shares, in front of the device
+int fold_validate(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, u32 n_keys,
+                  const uint64_t * run_offsets, u32 n_runs, u32 flags, FoldPrefix * px);
+int fold_check_column(const chgpu_col * c, const char * what, int want_type, const char * type_name, u64 rows);
+// BAD_ARGUMENTS naming the lowest concatenated row whose value is outside the column's domain (mode 0: Int8 sign, 1: UInt8 is_deleted)
+int fold_require_domain(chgpu_ctx * ctx, PairTemps & tmp, const chgpu_col * c, int mode, u64 rows);
+// heads[p] = position p of M starts a group (k_fold_heads): one launch, counted
+void fold_heads(chgpu_ctx * ctx, const MergeKeys & keys, const u64 * words, const u32 * rows, u32 n, u8 * heads);

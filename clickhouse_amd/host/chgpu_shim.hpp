@@ -2754,6 +2754,33 @@ private:
     size_t sign_column;
 };
 
+/// VersionedCollapsingTransform (src/Processors/Merges/Algorithms/VersionedCollapsingAlgorithm.cpp); the description is the engine's: the
+/// primary key with the version column last.  sign_column: the position of the Int8 sign.  The device's queue is unbounded: after
+/// finish() compare maxBalance() -- the most rows the reference's queue would have held -- with the reference's max_rows_in_queue; below
+/// it the two outputs are the same, at or above it the reference would have emitted a queue's front row early.
+class GpuVersionedCollapsingSortedTransform : public GpuFoldingMergeInputs
+{
+public:
+    GpuVersionedCollapsingSortedTransform(ContextPtr ctx_, size_t num_inputs, SortDescription description_, size_t sign_column_)
+        : GpuFoldingMergeInputs(std::move(ctx_), num_inputs, std::move(description_)), sign_column(sign_column_) {}
+
+    Chunk finish()
+    {
+        max_balance = 0;
+        if (!glue())
+            return Chunk();
+        chgpu_col * rows = nullptr;
+        check(chgpu_merge_versioned_collapsing(ctx->get(), keys.data(), descending.data(), hints.data(), numKeys(), offsets.data(), numRuns(),
+                                               CHGPU_MERGE_CHECK_SORTED, glued.columns.at(sign_column)->handle(), &rows, &max_balance));
+        return indexed(rows);
+    }
+    uint64_t maxBalance() const { return max_balance; }
+
+private:
+    size_t sign_column;
+    uint64_t max_balance = 0;
+};
+
 /// AggregatingSortedTransform over SimpleAggregateFunction columns (src/Processors/Merges/Algorithms/AggregatingSortedAlgorithm.cpp):
 /// folds[position] = CHGPU_FOLD_SUM / MIN / MAX, last_columns: positions that take the group's last row (anyLast); every other column
 /// takes the group's first row (any).  drop_zero: Summing's rule.

@@ -1,6 +1,6 @@
 """The merges of MergeTree that fold rows of equal sorting key while they merge, over the C ABI: ReplacingSortedAlgorithm,
-CollapsingSortedAlgorithm, SummingSortedAlgorithm and AggregatingSortedAlgorithm over SimpleAggregateFunction columns
-(src/Processors/Merges/Algorithms/).  The input is what merge_sorted takes -- sorted runs glued end to end -- and the answer is the rows
+CollapsingSortedAlgorithm, VersionedCollapsingAlgorithm, SummingSortedAlgorithm and AggregatingSortedAlgorithm over
+SimpleAggregateFunction columns (src/Processors/Merges/Algorithms/).  The input is what merge_sorted takes -- sorted runs glued end to end -- and the answer is the rows
 that survive, in merged order, as concatenated row numbers (and, for the folding form, one result column per folded column).  Numeric
 columns only; String columns, Float value columns and bad descriptions raise before the library is touched.
 
@@ -86,6 +86,19 @@ def collapsing_merge_rows(key_cols, description, run_offsets, sign, check: bool 
     return Column(ctx, out)
 
 
+def versioned_collapsing_merge_rows(key_cols, description, run_offsets, sign, check: bool = True):
+    """VersionedCollapsingAlgorithm: the version is the last key column, so a group is equal on the key and the version; within it a
+    row cancels the nearest unmatched earlier row of the other sign and every unmatched row survives (|cp - cn| rows of the majority
+    sign) -> (their row numbers, max_balance).  The queue is unbounded: the answer is the reference's whenever max_balance, the largest
+    number of rows its queue would have held, is below the reference's max_rows_in_queue."""
+    _check_typed(sign, "the sign column", "i", np.int8)
+    ctx, cols, args = _prepare(key_cols, description, run_offsets)
+    s = _handle(ctx, cols, sign)
+    out, balance = C.c_void_p(), C.c_uint64(0)
+    K.check(K.lib().chgpu_merge_versioned_collapsing(ctx._live(), *args, _flags(check), s, C.byref(out), C.byref(balance)))
+    return Column(ctx, out), int(balance.value)
+
+
 def aggregating_merge_rows(key_cols, description, run_offsets, values, kinds, drop_zero: bool = False, check: bool = True):
     """values[i] folded by kinds[i] in ("sum", "min", "max") per group of equal keys
     -> (first_rows, last_rows, [result Column per value]); drop_zero: Summing's rule"""
@@ -152,6 +165,17 @@ def collapsing_merge(blocks, description, sign, check: bool = True):
     glued, offsets = _upload_and_glue(blocks, width)
     rows = collapsing_merge_rows(glued, description, offsets, glued[sign], check=check)
     return [c.index(rows) for c in glued], rows
+
+
+def versioned_collapsing_merge(blocks, description, sign, check: bool = True):
+    """VersionedCollapsingTransform over sorted Blocks; the description ends with the version column, sign is the position of the Int8
+    sign column.  -> (columns, rows, max_balance)"""
+    blocks, width, description = _glue(blocks, description)
+    sign = _position(sign, width, "the sign")
+    _check_typed(blocks[0][sign], "the sign column", "i", np.int8)
+    glued, offsets = _upload_and_glue(blocks, width)
+    rows, balance = versioned_collapsing_merge_rows(glued, description, offsets, glued[sign], check=check)
+    return [c.index(rows) for c in glued], rows, balance
 
 
 def _folding_merge(blocks, width, description, kinds, drop_zero, check):

@@ -470,8 +470,21 @@ int chgpu_is_sorted(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const i
    holds it.  Per group cp = the number of +1 rows, cn = the number of -1 rows, first_negative = the first -1 row in M, last_positive =
    the last +1 row in M, last_is_positive = the sign of the group's last row.  Nothing is emitted unless last_is_positive || cp != cn;
    otherwise first_negative if cp <= cn, then last_positive if cp >= cn: 0, 1 or 2 rows, the negative one first.  rows_out_u64: their
-   concatenated row numbers.  The reference's log line for |cp - cn| > 1, only_positive_sign and VersionedCollapsing have no
+   concatenated row numbers.  The reference's log line for |cp - cn| > 1, only_positive_sign have no
    counterpart here.
+
+   chgpu_merge_versioned_collapsing (src/Processors/Merges/Algorithms/VersionedCollapsingAlgorithm.cpp): the engine's sort description
+   is the primary key with the version column appended, so the caller passes the version as the LAST key column and a group is a stretch
+   equal on the key and the version; there is no separate version argument.  sign_i8 as above.  Within a group the reference keeps a
+   queue that only ever holds rows of one sign (sign_in_queue): a row that meets an empty queue sets the sign and is pushed, a row of
+   the queue's sign is pushed, a row of the other sign removes the queue's back row and both vanish, and the group's end emits the queue
+   front to back.  A group therefore emits |cp - cn| rows, all of the majority sign, in M's order.  Which rows: with B_0 = 0 and
+   B_t = B_(t-1) + sign_t over the group's rows in M, row t of sign s survives iff s * B_t >= 1 and s * B_u >= s * B_t for every later row
+   u of its group.  rows_out_u64: the concatenated row numbers of the surviving rows, in M's order; empty when everything cancels.
+   *max_balance (may be NULL): the largest |B_t| over all rows, 0 for an empty input.  ONE DIFFERENCE: the queue here is unbounded.  The
+   reference bounds its queue (max_rows_in_queue, derived from max_block_size) and, when it is full, emits the front row early and for
+   good, which makes its output depend on a block-size setting; that bound is not modelled.  The two agree whenever max_balance is below
+   the reference's bound, so a caller compares max_balance with its own setting.
 
    chgpu_merge_folding (Summing; Aggregating over SimpleAggregateFunction columns): value_cols[n_values] with kinds[n_values] of
    CHGPU_FOLD_SUM (wrap-around addition in the column's own type, sumWithOverflow), CHGPU_FOLD_MIN, CHGPU_FOLD_MAX (in the column's
@@ -490,6 +503,9 @@ int chgpu_merge_replacing(chgpu_ctx * ctx, const chgpu_col * const * key_cols, c
 int chgpu_merge_collapsing(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint,
                            uint32_t n_keys, const uint64_t * run_offsets, uint32_t n_runs, uint32_t flags, const chgpu_col * sign_i8,
                            chgpu_col ** rows_out_u64);
+int chgpu_merge_versioned_collapsing(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint,
+                                     uint32_t n_keys, const uint64_t * run_offsets, uint32_t n_runs, uint32_t flags, const chgpu_col * sign_i8,
+                                     chgpu_col ** rows_out_u64, uint64_t * max_balance /* may be NULL */);
 int chgpu_merge_folding(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint,
                         uint32_t n_keys, const uint64_t * run_offsets, uint32_t n_runs, uint32_t flags, const chgpu_col * const * value_cols,
                         const int32_t * kinds, uint32_t n_values, int32_t drop_zero, chgpu_col ** first_rows_u64, chgpu_col ** last_rows_u64,
