@@ -1,123 +1,10 @@
-// window_frames_host.h — the parts of chgpu_window_evaluate_framed (window_kernels.hip) that need no device, beside window_host.h: which
-// frames and plans the framed entry serves, the search over the ORDER BY column's values behind a RANGE frame with an offset, and the
+// window_frames_host.h — the parts of the framed calls (chgpu_window_evaluate_framed, window_kernels.hip) that need no device, beside
+// window_host.h, which checks and plans them: the search over the ORDER BY column's values behind a RANGE frame with an offset, and the
 // block / level arithmetic of the general min / max (64-row masks plus a sparse table over the blocks' extrema).  Plain C++; what the
 // kernels share is __host__ __device__ under hipcc, so that tests/window_frames_driver.cpp runs the very code under a sanitizer.
 #pragma once
 
 #include "window_host.h"
-
-// ---------------------------------------------------------------------------------------------
-// frames and plans
-// ---------------------------------------------------------------------------------------------
-static inline bool win_frame_has_range_offset(const chgpu_window_frame & f)
-{
-    return f.type == CHGPU_FRAME_RANGE && (win_bound_is_offset(f.begin_kind) || win_bound_is_offset(f.end_kind));
-}
-
-// win_check_frame, except that a legal RANGE frame with an offset passes
-static inline int win_check_frame_framed(const chgpu_window_frame & f, const char ** msg)
-{
-    int rc = win_check_frame(f, msg);
-    if (rc == CHGPU_ERR_NOT_IMPLEMENTED && win_frame_has_range_offset(f))
-        return *msg = nullptr, CHGPU_OK;
-    return rc;
-}
-
-static inline bool win_order_type_is_served(int type)
-{
-    switch (type)
-    {
-        case CHGPU_I64: case CHGPU_U64: case CHGPU_I32: case CHGPU_U32: case CHGPU_I16: case CHGPU_U16: case CHGPU_I8: case CHGPU_U8: return true;
-        default: return false;
-    }
-}
-
-// A RANGE offset of 0 is the peer group's edge: `0 PRECEDING` / `0 FOLLOWING` become CURRENT ROW (the search runs away from the row and
-// could not find an end that lies on the row's other side).
-static inline chgpu_window_frame win_frame_without_zero_range_offsets(chgpu_window_frame f)
-{
-    if (f.type != CHGPU_FRAME_RANGE)
-        return f;
-    if (win_bound_is_offset(f.begin_kind) && f.begin_offset == 0)
-        f.begin_kind = CHGPU_BOUND_CURRENT_ROW;
-    if (win_bound_is_offset(f.end_kind) && f.end_offset == 0)
-        f.end_kind = CHGPU_BOUND_CURRENT_ROW;
-    return f;
-}
-
-// how min / max run
-enum
-{
-    WIN_EXT_NONE = 0, // not min / max
-    WIN_EXT_FORWARD,  // the running extremum from the partition's first row (window_host.h's plan)
-    WIN_EXT_BACKWARD, // ... up to its last row
-    WIN_EXT_GENERAL   // block masks + sparse table: any frame
-};
-
-struct WinFramedPlan
-{
-    uint32_t needs = 0;     // the handle's bound arrays the call reads
-    int ext = WIN_EXT_NONE;
-    bool old_entry = false; // window_host.h's win_check_frame + win_plan serve it: the framed entry runs the old path
-    bool search_begin = false, search_end = false; // fs[] / fe[] come from the search over the order column
-    uint64_t width = 0;     // GENERAL: the most rows a frame can hold (~0: unknown), which bounds the levels of the table
-};
-
-// the most rows a ROWS frame whose bounds are offsets or CURRENT ROW can hold; ~0 for every other frame
-static inline uint64_t win_frame_max_width(const chgpu_window_frame & f)
-{
-    const int b = f.begin_kind, e = f.end_kind;
-    if (f.type != CHGPU_FRAME_ROWS || b == CHGPU_BOUND_UNBOUNDED_PRECEDING || e == CHGPU_BOUND_UNBOUNDED_FOLLOWING)
-        return ~0ull;
-    const uint64_t bo = b == CHGPU_BOUND_CURRENT_ROW ? 0 : f.begin_offset, eo = e == CHGPU_BOUND_CURRENT_ROW ? 0 : f.end_offset;
-    const bool b_before = b != CHGPU_BOUND_OFFSET_FOLLOWING, e_before = e == CHGPU_BOUND_OFFSET_PRECEDING;
-    if (b_before && !e_before)
-        return win_sat_add(win_sat_add(bo, eo), 1); // k PRECEDING .. m FOLLOWING
-    if (b_before)
-        return bo - eo + 1;                         // k PRECEDING .. m PRECEDING, k >= m
-    return eo - bo + 1;                             // k FOLLOWING .. m FOLLOWING, k <= m
-}
-
-// Is this (function, frame, argument type, order column) served by the framed entry, and how?  `frame` has passed win_check_frame_framed
-// (it is not looked at for the three rank functions).  arg_type < 0: no argument; order_type < 0: no order column given.
-static inline int win_plan_framed(int function, const chgpu_window_frame & frame_in, int arg_type, int order_type, WinFramedPlan * plan, const char ** msg)
-{
-    *plan = WinFramedPlan{};
-    const bool searched = !win_function_ignores_frame(function) && win_frame_has_range_offset(frame_in);
-    if (searched && order_type < 0)
-        return *msg = "a RANGE frame with an offset needs the ORDER BY column (NULL given)", CHGPU_ERR_BAD_ARGUMENTS;
-    if (!searched && order_type >= 0)
-        return *msg = "an ORDER BY column is taken only with a RANGE frame that has an offset", CHGPU_ERR_BAD_ARGUMENTS;
-    const chgpu_window_frame frame = searched ? win_frame_without_zero_range_offsets(frame_in) : frame_in;
-    bool backward = false;
-    const char * old_msg = nullptr;
-    // the old plan over the frame as ROWS answers everything but the two gaps: unknown functions, arguments, float sums, the bounds read
-    chgpu_window_frame as_rows = frame;
-    if (searched)
-        as_rows.type = CHGPU_FRAME_ROWS;
-    int rc = win_plan(function, as_rows, arg_type, &plan->needs, &backward, &old_msg);
-    const bool is_ext = function == CHGPU_WIN_MIN || function == CHGPU_WIN_MAX;
-    const bool two_sided = is_ext && rc == CHGPU_ERR_NOT_IMPLEMENTED; // (the one thing the old plan refuses min / max for)
-    if (rc != CHGPU_OK && !two_sided)
-        return *msg = old_msg, rc;
-    if (searched && !win_order_type_is_served(order_type))
-        return *msg = "a RANGE frame with an offset over a Float32 / Float64 ORDER BY column is not implemented", CHGPU_ERR_NOT_IMPLEMENTED;
-    if (!win_function_ignores_frame(function))
-        plan->needs = win_frame_needs(frame);
-    plan->search_begin = searched && win_bound_is_offset(frame.begin_kind);
-    plan->search_end = searched && win_bound_is_offset(frame.end_kind);
-    if (is_ext)
-    {
-        // a frame that is searched goes through the general structure even when one side is UNBOUNDED: the running extremum would do,
-        // but one path less is one path less to test
-        if (two_sided || searched)
-            plan->ext = WIN_EXT_GENERAL, plan->width = win_frame_max_width(frame);
-        else
-            plan->ext = backward ? WIN_EXT_BACKWARD : WIN_EXT_FORWARD, plan->needs |= backward ? WIN_B_PE : WIN_B_PS;
-    }
-    plan->old_entry = !searched && !two_sided;
-    return CHGPU_OK;
-}
 
 // ---------------------------------------------------------------------------------------------
 // the search behind a RANGE offset

@@ -1,10 +1,11 @@
-// window_host.h — the parts of the window operator (window_kernels.hip) that need no device: frame validation, the frame of a row, which
-// bound arrays a call needs and the bookkeeping of their lazy construction, and the tile / grid arithmetic of the scans.  Plain C++ (the
-// functions the kernels share are __host__ __device__ under hipcc), so that tests/window_driver.cpp runs the very code the kernels run
-// under a sanitizer.
+// window_host.h — the parts of the window operator (window_kernels.hip) that need no device: the one frame check (win_check_frame) and
+// the one plan (win_plan) both entries, chgpu_window_evaluate and chgpu_window_evaluate_framed, go through, the frame of a row, the
+// bookkeeping of the bound arrays' lazy construction, and the tile / grid arithmetic of the scans.  Plain C++ (the functions the kernels
+// share are __host__ __device__ under hipcc), so that tests/window_driver.cpp runs the very code the kernels run under a sanitizer.
 #pragma once
 
 #include <cstdint>
+#include <string>
 
 #include "../../include/chgpu.h"
 
@@ -44,9 +45,15 @@ static inline chgpu_window_frame win_default_frame()
 
 static inline bool win_bound_is_offset(int kind) { return kind == CHGPU_BOUND_OFFSET_PRECEDING || kind == CHGPU_BOUND_OFFSET_FOLLOWING; }
 
+// a RANGE frame with an offset: its bounds come from a search over the order column's values
+static inline bool win_frame_has_range_offset(const chgpu_window_frame & f)
+{
+    return f.type == CHGPU_FRAME_RANGE && (win_bound_is_offset(f.begin_kind) || win_bound_is_offset(f.end_kind));
+}
+
 // WindowFrame::checkValid (WindowDescription.cpp).  CHGPU_OK, or the code with *msg saying why.  A legal RANGE frame with an offset is
-// NOT_IMPLEMENTED: it needs a search over the order column's values.
-static inline int win_check_frame(const chgpu_window_frame & f, const char ** msg)
+// NOT_IMPLEMENTED for an entry that does not serve such frames (chgpu_window_evaluate: it has no order column to search).
+static inline int win_check_frame(const chgpu_window_frame & f, bool serves_range_offsets, const char ** msg)
 {
     const int b = f.begin_kind, e = f.end_kind;
     if (f.type != CHGPU_FRAME_ROWS && f.type != CHGPU_FRAME_RANGE)
@@ -65,7 +72,7 @@ static inline int win_check_frame(const chgpu_window_frame & f, const char ** ms
         return *msg = "frame begin is closer to the current row than its end (both PRECEDING)", CHGPU_ERR_BAD_ARGUMENTS;
     if (b == CHGPU_BOUND_OFFSET_FOLLOWING && e == CHGPU_BOUND_OFFSET_FOLLOWING && f.begin_offset > f.end_offset)
         return *msg = "frame begin is further from the current row than its end (both FOLLOWING)", CHGPU_ERR_BAD_ARGUMENTS;
-    if (f.type == CHGPU_FRAME_RANGE && (win_bound_is_offset(b) || win_bound_is_offset(e)))
+    if (!serves_range_offsets && win_frame_has_range_offset(f))
         return *msg = "RANGE frames with an offset are not implemented", CHGPU_ERR_NOT_IMPLEMENTED;
     return CHGPU_OK;
 }
@@ -132,40 +139,106 @@ static inline uint32_t win_frame_needs(const chgpu_window_frame & f)
     return n;
 }
 
+// A RANGE offset of 0 is the peer group's edge: `0 PRECEDING` / `0 FOLLOWING` become CURRENT ROW (the search runs away from the row and
+// could not find an end that lies on the row's other side).
+static inline chgpu_window_frame win_frame_without_zero_range_offsets(chgpu_window_frame f)
+{
+    if (f.type != CHGPU_FRAME_RANGE)
+        return f;
+    if (win_bound_is_offset(f.begin_kind) && f.begin_offset == 0)
+        f.begin_kind = CHGPU_BOUND_CURRENT_ROW;
+    if (win_bound_is_offset(f.end_kind) && f.end_offset == 0)
+        f.end_kind = CHGPU_BOUND_CURRENT_ROW;
+    return f;
+}
+
+// the most rows a ROWS frame whose bounds are offsets or CURRENT ROW can hold; ~0 for every other frame
+static inline uint64_t win_frame_max_width(const chgpu_window_frame & f)
+{
+    const int b = f.begin_kind, e = f.end_kind;
+    if (f.type != CHGPU_FRAME_ROWS || b == CHGPU_BOUND_UNBOUNDED_PRECEDING || e == CHGPU_BOUND_UNBOUNDED_FOLLOWING)
+        return ~0ull;
+    const uint64_t bo = b == CHGPU_BOUND_CURRENT_ROW ? 0 : f.begin_offset, eo = e == CHGPU_BOUND_CURRENT_ROW ? 0 : f.end_offset;
+    const bool b_before = b != CHGPU_BOUND_OFFSET_FOLLOWING, e_before = e == CHGPU_BOUND_OFFSET_PRECEDING;
+    if (b_before && !e_before)
+        return win_sat_add(win_sat_add(bo, eo), 1); // k PRECEDING .. m FOLLOWING
+    if (b_before)
+        return bo - eo + 1;                         // k PRECEDING .. m PRECEDING, k >= m
+    return eo - bo + 1;                             // k FOLLOWING .. m FOLLOWING, k <= m
+}
+
 static inline bool win_function_takes_arg(int function) { return function >= CHGPU_WIN_SUM && function <= CHGPU_WIN_LEAD_IN_FRAME; }
 static inline bool win_function_ignores_frame(int function) { return function >= CHGPU_WIN_ROW_NUMBER && function <= CHGPU_WIN_DENSE_RANK; }
 static inline bool win_type_is_float(int type) { return type == CHGPU_F64 || type == CHGPU_F32; }
 
-// Is this (function, frame, argument type) served, and which arrays does it read?  `frame` has passed win_check_frame (it is not looked
-// at for the three rank functions).  arg_type < 0: no argument.
-static inline int win_plan(int function, const chgpu_window_frame & frame, int arg_type, uint32_t * needs, bool * backward, const char ** msg)
+// how min / max run
+enum
 {
-    *needs = 0;
-    *backward = false;
+    WIN_EXT_NONE = 0, // not min / max
+    WIN_EXT_FORWARD,  // the running extremum from the partition's first row
+    WIN_EXT_BACKWARD, // ... up to its last row
+    WIN_EXT_GENERAL   // block masks + sparse table: any frame
+};
+
+struct WinPlan
+{
+    uint32_t needs = 0; // the handle's bound arrays the call reads
+    int ext = WIN_EXT_NONE;
+    bool search_begin = false, search_end = false; // fs[] / fe[] come from the search over the order column
+    uint64_t width = 0; // GENERAL: the most rows a frame can hold (~0: unknown), which bounds the levels of the table
+};
+
+// Is this call served, and how?  `framed`: chgpu_window_evaluate_framed asks, else chgpu_window_evaluate, which takes no order column
+// and refuses min / max over a frame bounded on both sides.  `frame` has passed win_check_frame for that entry (it is not looked at for
+// the three rank functions).  arg_type / order_type < 0: no such column given.  n_order and recorded_order_type are what the handle's
+// create saw: how many ORDER BY columns, and the type of the first.  The order of the checks decides the code of a call with two faults.
+static inline int win_plan(bool framed, int function, const chgpu_window_frame & frame_in, int arg_type, int order_type, uint32_t n_order, int recorded_order_type,
+                           WinPlan * plan, std::string * msg)
+{
+    *plan = WinPlan{};
+    const bool searched = !win_function_ignores_frame(function) && win_frame_has_range_offset(frame_in);
+    if (searched && order_type < 0)
+        return *msg = "a RANGE frame with an offset needs the ORDER BY column (NULL given)", CHGPU_ERR_BAD_ARGUMENTS;
+    if (!searched && order_type >= 0)
+        return *msg = "an ORDER BY column is taken only with a RANGE frame that has an offset", CHGPU_ERR_BAD_ARGUMENTS;
     if (function < CHGPU_WIN_ROW_NUMBER || function > CHGPU_WIN_LEAD_IN_FRAME)
         return *msg = "unknown window function", CHGPU_ERR_BAD_ARGUMENTS;
     if (win_function_takes_arg(function) != (arg_type >= 0))
         return *msg = win_function_takes_arg(function) ? "the function takes an argument column (NULL given)" : "the function takes no argument column", CHGPU_ERR_BAD_ARGUMENTS;
-    switch (function)
-    {
-        case CHGPU_WIN_ROW_NUMBER: *needs = WIN_B_PS; return CHGPU_OK;
-        case CHGPU_WIN_RANK: *needs = WIN_B_PS | WIN_B_GS; return CHGPU_OK;
-        case CHGPU_WIN_DENSE_RANK: *needs = WIN_B_PS | WIN_B_DENSE; return CHGPU_OK;
-        default: break;
-    }
-    *needs = win_frame_needs(frame);
+    if (order_type >= 0 && n_order != 1)
+        return *msg = "a RANGE frame with an offset needs a window with exactly one ORDER BY column, this one has " + std::to_string(n_order), CHGPU_ERR_BAD_ARGUMENTS;
+    if (order_type >= 0 && order_type != recorded_order_type)
+        return *msg = "the order column's type differs from the one the window was created with", CHGPU_ERR_BAD_ARGUMENTS;
     if ((function == CHGPU_WIN_SUM || function == CHGPU_WIN_AVG) && win_type_is_float(arg_type))
         return *msg = "sum / avg over a Float32 / Float64 argument is not implemented (a parallel scan rounds differently)", CHGPU_ERR_NOT_IMPLEMENTED;
-    if (function == CHGPU_WIN_MIN || function == CHGPU_WIN_MAX)
+    if (searched && win_type_is_float(order_type))
+        return *msg = "a RANGE frame with an offset over a Float32 / Float64 ORDER BY column is not implemented", CHGPU_ERR_NOT_IMPLEMENTED;
+    const bool is_ext = function == CHGPU_WIN_MIN || function == CHGPU_WIN_MAX;
+    const bool two_sided = frame_in.begin_kind != CHGPU_BOUND_UNBOUNDED_PRECEDING && frame_in.end_kind != CHGPU_BOUND_UNBOUNDED_FOLLOWING;
+    if (!framed && is_ext && two_sided)
+        return *msg = "min / max over a frame bounded on both sides is not implemented", CHGPU_ERR_NOT_IMPLEMENTED;
+    switch (function)
     {
-        // the running extremum is segmented by partition: forward from ps it also reads ps, backward from pe it reads pe
-        if (frame.begin_kind == CHGPU_BOUND_UNBOUNDED_PRECEDING)
-            *needs |= WIN_B_PS;
-        else if (frame.end_kind == CHGPU_BOUND_UNBOUNDED_FOLLOWING)
-            *needs |= WIN_B_PE, *backward = true;
-        else
-            return *msg = "min / max over a frame bounded on both sides is not implemented", CHGPU_ERR_NOT_IMPLEMENTED;
+        case CHGPU_WIN_ROW_NUMBER: plan->needs = WIN_B_PS; return CHGPU_OK;
+        case CHGPU_WIN_RANK: plan->needs = WIN_B_PS | WIN_B_GS; return CHGPU_OK;
+        case CHGPU_WIN_DENSE_RANK: plan->needs = WIN_B_PS | WIN_B_DENSE; return CHGPU_OK;
+        default: break;
     }
+    const chgpu_window_frame frame = win_frame_without_zero_range_offsets(frame_in); // the frame the kernels get
+    plan->needs = win_frame_needs(frame);
+    plan->search_begin = searched && win_bound_is_offset(frame.begin_kind);
+    plan->search_end = searched && win_bound_is_offset(frame.end_kind);
+    if (!is_ext)
+        return CHGPU_OK;
+    // A frame that is searched goes through the general structure even when one side is UNBOUNDED: the running extremum would do, but
+    // one path less is one path less to test.  The running extremum is segmented by partition: forward from ps it also reads ps,
+    // backward from pe it reads pe.
+    if (two_sided || searched)
+        plan->ext = WIN_EXT_GENERAL, plan->width = win_frame_max_width(frame);
+    else if (frame.begin_kind == CHGPU_BOUND_UNBOUNDED_PRECEDING)
+        plan->ext = WIN_EXT_FORWARD, plan->needs |= WIN_B_PS;
+    else
+        plan->ext = WIN_EXT_BACKWARD, plan->needs |= WIN_B_PE;
     return CHGPU_OK;
 }
 

@@ -15,12 +15,14 @@
 //              complement) since the partition's first row -- or, backward, up to its last row
 //   output     k_win_out_rank (row_number / rank / dense_rank / count), k_win_out_sum (sum / avg), k_win_out_extremum (min / max),
 //              k_win_out_pick<W> (first_value / last_value / lagInFrame / leadInFrame): row i, its bounds, the scan array -> the result;
-//              the frame itself is win_frame_of (window_host.h), the code the host driver tests
-//   framed     chgpu_window_evaluate_framed (window_frames_host.h): k_win_range_bound<X> searches the ORDER BY column for the bounds of a
-//              RANGE frame with offsets into a call's own fs[] / fe[], which every output kernel reads through win_row_frame;
-//              k_win_ext_masks (a monotone-stack mask per row of a 64-row block), k_win_ext_level (one level of the sparse table over the
-//              blocks' extrema per launch) and k_win_out_extremum_any<W> are min / max over any frame
-// The handle's pool memory and a call's temporaries are pair_pool.h (PairMem, PairAllocs without a refusal hook, PairTemps).
+//              what they share around their rows is win_out_rows, and the frame itself is win_frame_of (window_host.h), the code the
+//              host driver tests
+//   framed     what chgpu_window_evaluate_framed alone serves (window_frames_host.h): k_win_range_bound<X> searches the ORDER BY column
+//              for the bounds of a RANGE frame with offsets into a call's own fs[] / fe[], which every output kernel reads through
+//              win_row_frame; k_win_ext_masks (a monotone-stack mask per row of a 64-row block), k_win_ext_level (one level of the sparse
+//              table over the blocks' extrema per launch) and k_win_out_extremum_any<W> are min / max over any frame
+// Both entries are win_evaluate: win_check_frame and win_plan (window_host.h) in one order of checks, then win_run, which launches what
+// the plan says.  The handle's pool memory and a call's temporaries are pair_pool.h (PairMem, PairAllocs without a refusal hook, PairTemps).
 #include "block_scan.h"
 #include "pair_pool.h"
 #include "window_frames_host.h"
@@ -404,7 +406,7 @@ struct WinBounds
 
 struct WinRow4
 {
-    u32 ps[4], pe[4], gs[4], ge[4], fs[4], fe[4];
+    u32 ps[4], pe[4], gs[4], ge[4], dense[4], fs[4], fe[4];
 };
 
 __device__ __forceinline__ void win_load4(const u32 * __restrict__ p, u64 i0, u32 out[4])
@@ -424,6 +426,7 @@ __device__ __forceinline__ void win_load_bounds(const WinBounds & b, u64 i0, Win
     win_load4(b.pe, i0, r->pe);
     win_load4(b.gs, i0, r->gs);
     win_load4(b.ge, i0, r->ge);
+    win_load4(b.dense, i0, r->dense); // (given to dense_rank alone)
     win_load4(b.fs, i0, r->fs);
     win_load4(b.fe, i0, r->fe);
 }
@@ -466,68 +469,65 @@ __device__ __forceinline__ void win_store4(W * __restrict__ out, u64 i0, u64 n, 
 
 __device__ __forceinline__ u64 win_first_row() { return ((u64)blockIdx.x * WIN_THREADS + threadIdx.x) * WIN_OUT_ROWS; }
 
-__global__ __launch_bounds__(WIN_THREADS) void k_win_out_rank(int function, chgpu_window_frame frame, WinBounds b, u64 n, u64 * __restrict__ out)
+// What every output kernel does around its rows: the thread's four rows, their bounds in one load per array, body(i, k, r) -> the 64
+// result bits of row i, the k-th of the four (rows past the input are skipped), and the store.  The body asks win_row_frame for the
+// row's frame where it reads one.  The bodies capture by value: what they capture are kernel arguments, the same in every lane, and a
+// copy leaves them in scalar registers where a reference made the compiler test `frame` again for every row.
+template <typename W, typename Body>
+__device__ __forceinline__ void win_out_rows(const WinBounds & b, u64 n, W * __restrict__ out, Body && body)
 {
     const u64 i0 = win_first_row();
     if (i0 >= n)
         return;
     WinRow4 r;
     win_load_bounds(b, i0, &r);
-    u32 dense[4];
-    win_load4(function == CHGPU_WIN_DENSE_RANK ? b.dense : nullptr, i0, dense);
     u64 v[4];
 #pragma unroll
     for (u32 k = 0; k < 4; ++k)
     {
         const u64 i = i0 + k;
         v[k] = 0;
-        if (i >= n)
-            continue;
-        if (function == CHGPU_WIN_ROW_NUMBER)
-            v[k] = i - r.ps[k] + 1;
-        else if (function == CHGPU_WIN_RANK)
-            v[k] = (u64)r.gs[k] - r.ps[k] + 1;
-        else if (function == CHGPU_WIN_DENSE_RANK)
-            v[k] = (u64)dense[k] - b.dense[r.ps[k]] + 1; // (the partition's first row is a peer head itself)
-        else
-        {
-            u64 fs, fe;
-            win_row_frame(frame, b, r, k, i, &fs, &fe);
-            v[k] = fe - fs;
-        }
+        if (i < n)
+            v[k] = body(i, k, r);
     }
     win_store4(out, i0, n, v);
+}
+
+__global__ __launch_bounds__(WIN_THREADS) void k_win_out_rank(int function, chgpu_window_frame frame, WinBounds b, u64 n, u64 * __restrict__ out)
+{
+    win_out_rows(b, n, out, [=](u64 i, u32 k, const WinRow4 & r) -> u64 {
+        if (function == CHGPU_WIN_ROW_NUMBER)
+            return i - r.ps[k] + 1;
+        if (function == CHGPU_WIN_RANK)
+            return (u64)r.gs[k] - r.ps[k] + 1;
+        if (function == CHGPU_WIN_DENSE_RANK)
+            return (u64)r.dense[k] - b.dense[r.ps[k]] + 1; // (the partition's first row is a peer head itself)
+        u64 fs, fe;
+        win_row_frame(frame, b, r, k, i, &fs, &fe);
+        return fe - fs;
+    });
 }
 
 // sum: P[fe] - P[fs]; avg: that as Float64 (signed: num_signed) over Float64(fe - fs), AvgFraction::divide as k_avg_divide has it
 __global__ __launch_bounds__(WIN_THREADS) void k_win_out_sum(int is_avg, int num_signed, chgpu_window_frame frame, WinBounds b, u64 n, const u64 * __restrict__ P,
                                                              u64 * __restrict__ out)
 {
-    const u64 i0 = win_first_row();
-    if (i0 >= n)
-        return;
-    WinRow4 r;
-    win_load_bounds(b, i0, &r);
-    u64 v[4];
-#pragma unroll
-    for (u32 k = 0; k < 4; ++k)
-    {
-        const u64 i = i0 + k;
-        v[k] = 0;
-        if (i >= n)
-            continue;
+    win_out_rows(b, n, out, [=](u64 i, u32 k, const WinRow4 & r) -> u64 {
         u64 fs, fe;
         win_row_frame(frame, b, r, k, i, &fs, &fe);
         const u64 sum = P[fe] - P[fs];
-        if (is_avg)
-        {
-            const double num = num_signed ? (double)(i64)sum : (double)sum;
-            v[k] = (u64)__double_as_longlong(num / (double)(fe - fs));
-        }
-        else
-            v[k] = sum;
-    }
-    win_store4(out, i0, n, v);
+        if (!is_avg)
+            return sum;
+        const double num = num_signed ? (double)(i64)sum : (double)sum;
+        return (u64)__double_as_longlong(num / (double)(fe - fs));
+    });
+}
+
+// an extremum's key back to the value's bits: agg_order_key's inverse (min: of the complement), Float32 narrowed from its exact widening
+__device__ __forceinline__ u64 win_ext_value_bits(u64 key, int type, int is_min)
+{
+    const u64 bits = agg_order_key_inverse(is_min ? ~key : key, type);
+    return type == CHGPU_F32 ? (u64)__float_as_uint((float)__longlong_as_double((long long)bits)) : bits;
 }
 
 // min / max: forward the answer stands at the frame's last row, backward at its first; the key goes back to the value's bits
@@ -535,28 +535,11 @@ template <typename W>
 __global__ __launch_bounds__(WIN_THREADS) void k_win_out_extremum(int type, int is_min, int backward, chgpu_window_frame frame, WinBounds b, u64 n,
                                                                   const u64 * __restrict__ M, W * __restrict__ out)
 {
-    const u64 i0 = win_first_row();
-    if (i0 >= n)
-        return;
-    WinRow4 r;
-    win_load_bounds(b, i0, &r);
-    u64 v[4];
-#pragma unroll
-    for (u32 k = 0; k < 4; ++k)
-    {
-        const u64 i = i0 + k;
-        v[k] = 0;
-        if (i >= n)
-            continue;
+    win_out_rows(b, n, out, [=](u64 i, u32 k, const WinRow4 & r) -> u64 {
         u64 fs, fe;
         win_row_frame(frame, b, r, k, i, &fs, &fe);
-        if (fs >= fe)
-            continue;
-        const u64 key = M[backward ? fs : fe - 1];
-        const u64 bits = agg_order_key_inverse(is_min ? ~key : key, type);
-        v[k] = type == CHGPU_F32 ? (u64)__float_as_uint((float)__longlong_as_double((long long)bits)) : bits;
-    }
-    win_store4(out, i0, n, v);
+        return fs < fe ? win_ext_value_bits(M[backward ? fs : fe - 1], type, is_min) : 0;
+    });
 }
 
 enum { WIN_PICK_FIRST = 0, WIN_PICK_LAST, WIN_PICK_LAG, WIN_PICK_LEAD };
@@ -566,30 +549,15 @@ template <typename W>
 __global__ __launch_bounds__(WIN_THREADS) void k_win_out_pick(int pick, chgpu_window_frame frame, WinBounds b, u64 n, const W * __restrict__ x, u64 offset, u64 default_bits,
                                                               W * __restrict__ out)
 {
-    const u64 i0 = win_first_row();
-    if (i0 >= n)
-        return;
-    WinRow4 r;
-    win_load_bounds(b, i0, &r);
-    u64 v[4];
-#pragma unroll
-    for (u32 k = 0; k < 4; ++k)
-    {
-        const u64 i = i0 + k;
-        v[k] = 0;
-        if (i >= n)
-            continue;
-        u64 fs, fe;
+    win_out_rows(b, n, out, [=](u64 i, u32 k, const WinRow4 & r) -> u64 {
+        u64 fs, fe, t, v;
         win_row_frame(frame, b, r, k, i, &fs, &fe);
         if (pick == WIN_PICK_FIRST || pick == WIN_PICK_LAST)
-            v[k] = fs < fe ? (u64)x[pick == WIN_PICK_FIRST ? fs : fe - 1] : 0;
+            v = fs < fe ? (u64)x[pick == WIN_PICK_FIRST ? fs : fe - 1] : 0;
         else
-        {
-            u64 t;
-            v[k] = win_shifted_row(pick == WIN_PICK_LEAD, i, offset, fs, fe, &t) ? (u64)x[t] : (u64)(W)default_bits;
-        }
-    }
-    win_store4(out, i0, n, v);
+            v = win_shifted_row(pick == WIN_PICK_LEAD, i, offset, fs, fe, &t) ? (u64)x[t] : (u64)(W)default_bits;
+        return v;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -663,23 +631,11 @@ template <typename W>
 __global__ __launch_bounds__(WIN_THREADS) void k_win_out_extremum_any(int type, int is_min, chgpu_window_frame frame, WinBounds b, u64 n, const void * __restrict__ x,
                                                                       const u64 * __restrict__ mask, const u64 * __restrict__ table, u64 n_blocks, W * __restrict__ out)
 {
-    const u64 i0 = win_first_row();
-    if (i0 >= n)
-        return;
-    WinRow4 r;
-    win_load_bounds(b, i0, &r);
-    u64 v[4];
-#pragma unroll
-    for (u32 k = 0; k < 4; ++k)
-    {
-        const u64 i = i0 + k;
-        v[k] = 0;
-        if (i >= n)
-            continue;
+    win_out_rows(b, n, out, [=](u64 i, u32 k, const WinRow4 & r) -> u64 {
         u64 fs, fe;
         win_row_frame(frame, b, r, k, i, &fs, &fe);
         if (fs >= fe)
-            continue;
+            return 0;
         const u64 l = fs, last = fe - 1, bl = l / WIN_EXT_BLOCK, br = last / WIN_EXT_BLOCK;
         u64 key;
         if (bl == br)
@@ -697,10 +653,8 @@ __global__ __launch_bounds__(WIN_THREADS) void k_win_out_extremum_any(int type, 
                 key = MaxU64::comb(key, MaxU64::comb(table[level * n_blocks + c0], table[level * n_blocks + c1]));
             }
         }
-        const u64 bits = agg_order_key_inverse(is_min ? ~key : key, type);
-        v[k] = type == CHGPU_F32 ? (u64)__float_as_uint((float)__longlong_as_double((long long)bits)) : bits;
-    }
-    win_store4(out, i0, n, v);
+        return win_ext_value_bits(key, type, is_min);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -888,10 +842,10 @@ static void win_dispatch_order_type(int type, F && fn)
     }
 }
 
-// One validated call: `frame` and `plan` are what win_check_frame + win_plan (the old entry) or their _framed forms answered.  `order`
-// is read only where the plan searches a bound.
-static int win_run(chgpu_window * w, int function, const chgpu_window_frame & frame, const WinFramedPlan & plan, const chgpu_col * order, int descending,
-                   const chgpu_col * arg, uint64_t offset, uint64_t default_bits, chgpu_col ** out)
+// One validated call: `frame` and `plan` are what win_check_frame and win_plan answered.  `order` is read only where the plan searches a
+// bound.
+static int win_run(chgpu_window * w, int function, const chgpu_window_frame & frame, const WinPlan & plan, const chgpu_col * order, int descending, const chgpu_col * arg,
+                   uint64_t offset, uint64_t default_bits, chgpu_col ** out)
 {
     chgpu_ctx * ctx = w->ctx;
     ChgpuDeviceGuard guard(ctx);
@@ -914,8 +868,8 @@ static int win_run(chgpu_window * w, int function, const chgpu_window_frame & fr
     u32 * fs = nullptr;     // searched bounds, whole tiles long; a call's own, not kept in the handle
     u32 * fe = nullptr;
     const bool is_sum = function == CHGPU_WIN_SUM || function == CHGPU_WIN_AVG;
-    const bool is_ext = function == CHGPU_WIN_MIN || function == CHGPU_WIN_MAX;
-    const bool general = plan.ext == WIN_EXT_GENERAL, backward = plan.ext == WIN_EXT_BACKWARD;
+    const bool is_ext = plan.ext != WIN_EXT_NONE, general = plan.ext == WIN_EXT_GENERAL;
+    const int is_min = function == CHGPU_WIN_MIN ? 1 : 0;
     const u64 n_blocks = win_ext_blocks(n);
     const u32 levels = general ? win_ext_levels(plan.width, n_blocks) : 0;
     if (general)
@@ -967,7 +921,6 @@ static int win_run(chgpu_window * w, int function, const chgpu_window_frame & fr
     }
     else if (general)
     {
-        const int is_min = function == CHGPU_WIN_MIN ? 1 : 0;
         const u32 waves = WIN_THREADS / 64;
         hipLaunchKernelGGL(k_win_ext_masks, dim3((u32)(n_blocks / waves + (n_blocks % waves != 0))), block, 0, st, (const void *)arg->data, arg_type, is_min, n, n_blocks,
                            mask, table);
@@ -983,23 +936,16 @@ static int win_run(chgpu_window * w, int function, const chgpu_window_frame & fr
     }
     else if (is_ext)
     {
-        const int is_min = function == CHGPU_WIN_MIN ? 1 : 0;
-        const u32 * bound = backward ? b.pe : b.ps;
-        if (backward)
-        {
-            hipLaunchKernelGGL(k_win_seg_tiles<true>, tile_grid, block, 0, st, (const void *)arg->data, arg_type, is_min, bound, n, (WinSeg *)tiles);
+        dispatch_const<0, 1>(plan.ext == WIN_EXT_BACKWARD ? 1 : 0, [&](auto back) {
+            constexpr bool BACK = decltype(back)::value != 0;
+            const u32 * bound = BACK ? b.pe : b.ps;
+            hipLaunchKernelGGL(k_win_seg_tiles<BACK>, tile_grid, block, 0, st, (const void *)arg->data, arg_type, is_min, bound, n, (WinSeg *)tiles);
             hipLaunchKernelGGL(k_win_scan_seg_tiles, dim3(1), dim3(WIN_PASS), 0, st, (WinSeg *)tiles, w->n_tiles);
-            hipLaunchKernelGGL(k_win_seg_apply<true>, tile_grid, block, 0, st, (const void *)arg->data, arg_type, is_min, bound, n, (const WinSeg *)tiles, scan);
-        }
-        else
-        {
-            hipLaunchKernelGGL(k_win_seg_tiles<false>, tile_grid, block, 0, st, (const void *)arg->data, arg_type, is_min, bound, n, (WinSeg *)tiles);
-            hipLaunchKernelGGL(k_win_scan_seg_tiles, dim3(1), dim3(WIN_PASS), 0, st, (WinSeg *)tiles, w->n_tiles);
-            hipLaunchKernelGGL(k_win_seg_apply<false>, tile_grid, block, 0, st, (const void *)arg->data, arg_type, is_min, bound, n, (const WinSeg *)tiles, scan);
-        }
-        dispatch_width(chgpu_type_size(arg_type), [&](auto tag) {
-            typedef decltype(tag) W;
-            hipLaunchKernelGGL(k_win_out_extremum<W>, out_grid, block, 0, st, arg_type, is_min, backward ? 1 : 0, frame, b, n, (const u64 *)scan, (W *)res->data);
+            hipLaunchKernelGGL(k_win_seg_apply<BACK>, tile_grid, block, 0, st, (const void *)arg->data, arg_type, is_min, bound, n, (const WinSeg *)tiles, scan);
+            dispatch_width(chgpu_type_size(arg_type), [&](auto tag) {
+                typedef decltype(tag) W;
+                hipLaunchKernelGGL(k_win_out_extremum<W>, out_grid, block, 0, st, arg_type, is_min, BACK ? 1 : 0, frame, b, n, (const u64 *)scan, (W *)res->data);
+            });
         });
         ctx->counters[6] += 4;
     }
@@ -1028,74 +974,57 @@ static int win_run(chgpu_window * w, int function, const chgpu_window_frame & fr
     return CHGPU_OK;
 }
 
-static int win_check_arg(const chgpu_ctx * ctx, const chgpu_col * arg)
+// a column a call was given, or NULL: a known type, on the window's device
+static int win_check_col(const chgpu_ctx * ctx, const chgpu_col * col, const char * what)
 {
-    if (arg)
+    if (col)
     {
-        CHGPU_REQUIRE(chgpu_type_size(arg->type) != 0, CHGPU_ERR_BAD_ARGUMENTS, "window: the argument column has an unknown type");
-        CHGPU_REQUIRE(arg->ctx && arg->ctx->device == ctx->device, CHGPU_ERR_BAD_ARGUMENTS, "window: the argument column lives on another device");
+        CHGPU_REQUIRE(chgpu_type_size(col->type) != 0, CHGPU_ERR_BAD_ARGUMENTS, "window: the %s column has an unknown type", what);
+        CHGPU_REQUIRE(col->ctx && col->ctx->device == ctx->device, CHGPU_ERR_BAD_ARGUMENTS, "window: the %s column lives on another device", what);
     }
     return CHGPU_OK;
+}
+
+static int win_check_rows(const chgpu_window * w, const chgpu_col * col, const char * what)
+{
+    CHGPU_REQUIRE(!col || col->rows == w->rows, CHGPU_ERR_SIZES_MISMATCH, "window: the %s has %llu rows, the window %llu", what, (unsigned long long)col->rows,
+                  (unsigned long long)w->rows);
+    return CHGPU_OK;
+}
+
+// Both entries: the checks in the one order that decides the code of a call with two faults (NULLs; the frame; the columns' types and
+// devices; win_plan: what is given, what the handle recorded, what is not implemented; the columns' rows), then win_run.  `framed`:
+// chgpu_window_evaluate_framed asks; chgpu_window_evaluate has no order column to give.
+static int win_evaluate(bool framed, chgpu_window * w, int function, const chgpu_window_frame * frame_in, const chgpu_col * order, int descending, const chgpu_col * arg,
+                        uint64_t offset, uint64_t default_bits, chgpu_col ** out)
+{
+    CHGPU_REQUIRE(w && out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
+    const char * msg = "";
+    chgpu_window_frame frame = frame_in ? *frame_in : win_default_frame();
+    int rc = CHGPU_OK;
+    if (win_function_ignores_frame(function))
+        frame = win_default_frame();
+    else if ((rc = win_check_frame(frame, framed, &msg)) != CHGPU_OK)
+        return chgpu_set_error(rc, "window: %s", msg);
+    CHGPU_TRY(win_check_col(w->ctx, arg, "argument"));
+    CHGPU_TRY(win_check_col(w->ctx, order, "order"));
+    WinPlan plan;
+    std::string why;
+    if ((rc = win_plan(framed, function, frame, arg ? arg->type : -1, order ? order->type : -1, w->n_order, w->order_type, &plan, &why)) != CHGPU_OK)
+        return chgpu_set_error(rc, "window: %s", why.c_str());
+    CHGPU_TRY(win_check_rows(w, order, "order column"));
+    CHGPU_TRY(win_check_rows(w, arg, "argument"));
+    return win_run(w, function, win_frame_without_zero_range_offsets(frame), plan, order, descending, arg, offset, default_bits, out);
 }
 
 extern "C" int chgpu_window_evaluate(chgpu_window * w, int function, const chgpu_window_frame * frame_in, const chgpu_col * arg, uint64_t offset,
                                      uint64_t default_bits, chgpu_col ** out)
 {
-    CHGPU_REQUIRE(w && out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    const char * msg = "";
-    chgpu_window_frame frame = frame_in ? *frame_in : win_default_frame();
-    int rc = CHGPU_OK;
-    if (win_function_ignores_frame(function))
-        frame = win_default_frame();
-    else if ((rc = win_check_frame(frame, &msg)) != CHGPU_OK)
-        return chgpu_set_error(rc, "window: %s", msg);
-    CHGPU_TRY(win_check_arg(w->ctx, arg));
-    u32 needs = 0;
-    bool backward = false;
-    if ((rc = win_plan(function, frame, arg ? arg->type : -1, &needs, &backward, &msg)) != CHGPU_OK)
-        return chgpu_set_error(rc, "window: %s", msg);
-    CHGPU_REQUIRE(!arg || arg->rows == w->rows, CHGPU_ERR_SIZES_MISMATCH, "window: the argument has %llu rows, the window %llu", (unsigned long long)arg->rows,
-                  (unsigned long long)w->rows);
-    WinFramedPlan plan;
-    plan.needs = needs;
-    plan.ext = function == CHGPU_WIN_MIN || function == CHGPU_WIN_MAX ? (backward ? WIN_EXT_BACKWARD : WIN_EXT_FORWARD) : WIN_EXT_NONE;
-    return win_run(w, function, frame, plan, nullptr, 0, arg, offset, default_bits, out);
+    return win_evaluate(false, w, function, frame_in, nullptr, 0, arg, offset, default_bits, out);
 }
 
 extern "C" int chgpu_window_evaluate_framed(chgpu_window * w, int function, const chgpu_window_frame * frame_in, const chgpu_col * order, int descending,
                                             const chgpu_col * arg, uint64_t offset, uint64_t default_bits, chgpu_col ** out)
 {
-    CHGPU_REQUIRE(w && out, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument");
-    const char * msg = "";
-    chgpu_window_frame frame = frame_in ? *frame_in : win_default_frame();
-    int rc = CHGPU_OK;
-    if (win_function_ignores_frame(function))
-        frame = win_default_frame();
-    else if ((rc = win_check_frame_framed(frame, &msg)) != CHGPU_OK)
-        return chgpu_set_error(rc, "window: %s", msg);
-    CHGPU_TRY(win_check_arg(w->ctx, arg));
-    if (order)
-    {
-        CHGPU_REQUIRE(chgpu_type_size(order->type) != 0, CHGPU_ERR_BAD_ARGUMENTS, "window: the order column has an unknown type");
-        CHGPU_REQUIRE(order->ctx && order->ctx->device == w->ctx->device, CHGPU_ERR_BAD_ARGUMENTS, "window: the order column lives on another device");
-    }
-    WinFramedPlan plan;
-    if ((rc = win_plan_framed(function, frame, arg ? arg->type : -1, order ? order->type : -1, &plan, &msg)) != CHGPU_OK
-        && !(rc == CHGPU_ERR_NOT_IMPLEMENTED && order && (w->n_order != 1 || order->type != w->order_type))) // (what the handle refuses comes first)
-        return chgpu_set_error(rc, "window: %s", msg);
-    if (order)
-    {
-        CHGPU_REQUIRE(w->n_order == 1, CHGPU_ERR_BAD_ARGUMENTS, "window: a RANGE frame with an offset needs a window with exactly one ORDER BY column, this one has %u",
-                      w->n_order);
-        CHGPU_REQUIRE(order->type == w->order_type, CHGPU_ERR_BAD_ARGUMENTS, "window: the order column's type differs from the one the window was created with");
-        CHGPU_REQUIRE(order->rows == w->rows, CHGPU_ERR_SIZES_MISMATCH, "window: the order column has %llu rows, the window %llu", (unsigned long long)order->rows,
-                      (unsigned long long)w->rows);
-    }
-    if (rc != CHGPU_OK)
-        return chgpu_set_error(rc, "window: %s", msg);
-    CHGPU_REQUIRE(!arg || arg->rows == w->rows, CHGPU_ERR_SIZES_MISMATCH, "window: the argument has %llu rows, the window %llu", (unsigned long long)arg->rows,
-                  (unsigned long long)w->rows);
-    if (plan.old_entry)
-        return chgpu_window_evaluate(w, function, frame_in, arg, offset, default_bits, out);
-    return win_run(w, function, win_frame_without_zero_range_offsets(frame), plan, order, descending, arg, offset, default_bits, out);
+    return win_evaluate(true, w, function, frame_in, order, descending, arg, offset, default_bits, out);
 }

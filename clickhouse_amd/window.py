@@ -100,6 +100,28 @@ def default_bits(tag: int, value) -> int:
     return scalar_bits(tag, value)
 
 
+def _evaluate(window: "Window", function: int, frame, x, offset: int, default, entry) -> Column:
+    """What both evaluate_column methods do: the argument checks, the lag / lead default bits, the upload and the call.  `entry` is the
+    caller's entry point, called only after the checks: entry(frame pointer or None, argument handle or None, offset, default bits,
+    pointer to the result handle) -> return code."""
+    takes_arg = function >= K.WIN_SUM
+    if takes_arg != (x is not None):
+        raise ValueError("the function takes an argument column" if takes_arg else "the function takes no argument column")
+    bits = 0
+    if takes_arg:
+        tag = _tag_of(x, "argument")
+        if len(x) != window.rows:
+            raise ValueError(f"the argument has {len(x)} rows, the window {window.rows}")
+        offset = _offset(offset)
+        if function in (K.WIN_LAG_IN_FRAME, K.WIN_LEAD_IN_FRAME):
+            bits = default_bits(tag, default)
+        x = window.ctx.column(x)
+    out = C.c_void_p()
+    fc = frame._c() if frame is not None else None
+    K.check(entry(C.byref(fc) if fc is not None else None, x._h if x is not None else None, offset, bits, C.byref(out)))
+    return Column(window.ctx, out)
+
+
 class Window:
     def __init__(self, partition_by=(), order_by=(), ctx: Context | None = None, rows: int | None = None):
         """partition_by / order_by: sequences of Columns / arrays, 0 to 8 each, already sorted by (partition_by, order_by).  rows is
@@ -153,23 +175,7 @@ class Window:
         """chgpu_window_evaluate -> the result Column resident in HBM"""
         if frame is not None and not isinstance(frame, Frame):
             raise ValueError("frame must be a Frame or None (the default frame)")
-        takes_arg = function >= K.WIN_SUM
-        if takes_arg != (x is not None):
-            raise ValueError("the function takes an argument column" if takes_arg else "the function takes no argument column")
-        bits = 0
-        if takes_arg:
-            tag = _tag_of(x, "argument")
-            if len(x) != self.rows:
-                raise ValueError(f"the argument has {len(x)} rows, the window {self.rows}")
-            offset = _offset(offset)
-            if function in (K.WIN_LAG_IN_FRAME, K.WIN_LEAD_IN_FRAME):
-                bits = default_bits(tag, default)
-            x = self.ctx.column(x)
-        out = C.c_void_p()
-        fc = frame._c() if frame is not None else None
-        K.check(K.lib().chgpu_window_evaluate(self._h, function, C.byref(fc) if fc is not None else None, x._h if x is not None else None,
-                                              offset, bits, C.byref(out)))
-        return Column(self.ctx, out)
+        return _evaluate(self, function, frame, x, offset, default, lambda fc, *rest: K.lib().chgpu_window_evaluate(self._h, function, fc, *rest))
 
     def over(self, frame: Frame | None = None, order=None, descending: bool = False) -> "FramedWindow":
         """this window with one frame, served by chgpu_window_evaluate_framed: every frame the methods below take, min / max over any
@@ -242,24 +248,9 @@ class FramedWindow:
 
     def evaluate_column(self, function: int, x=None, offset: int = 0, default=0) -> Column:
         """chgpu_window_evaluate_framed -> the result Column resident in HBM"""
-        w = self.window
-        takes_arg = function >= K.WIN_SUM
-        if takes_arg != (x is not None):
-            raise ValueError("the function takes an argument column" if takes_arg else "the function takes no argument column")
-        bits = 0
-        if takes_arg:
-            tag = _tag_of(x, "argument")
-            if len(x) != w.rows:
-                raise ValueError(f"the argument has {len(x)} rows, the window {w.rows}")
-            offset = _offset(offset)
-            if function in (K.WIN_LAG_IN_FRAME, K.WIN_LEAD_IN_FRAME):
-                bits = default_bits(tag, default)
-            x = w.ctx.column(x)
-        out = C.c_void_p()
-        fc = self.frame._c() if self.frame is not None else None
-        K.check(K.lib().chgpu_window_evaluate_framed(w._h, function, C.byref(fc) if fc is not None else None, self.order._h if self.order is not None else None,
-                                                     1 if self.descending else 0, x._h if x is not None else None, offset, bits, C.byref(out)))
-        return Column(w.ctx, out)
+        w, order = self.window, self.order._h if self.order is not None else None
+        return _evaluate(w, function, self.frame, x, offset, default,
+                         lambda fc, *rest: K.lib().chgpu_window_evaluate_framed(w._h, function, fc, order, 1 if self.descending else 0, *rest))
 
     def _eval(self, function, x=None, offset=0, default=0):
         return self.evaluate_column(function, x, offset, default).numpy()

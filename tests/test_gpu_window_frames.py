@@ -407,6 +407,10 @@ def test_refusals_leave_the_handle_usable(ch, ctx, T):
     fcol = ctx.upload(of)
     fails(K.ERR_NOT_IMPLEMENTED, lambda: raw(K.WIN_SUM, c_week, fcol, xcol, handle=floats.win), on=floats)
     fails(K.ERR_BAD_ARGUMENTS, lambda: raw(K.WIN_SUM, c_week, ocol, xcol, handle=floats.win), on=floats)   # Int64 is not what create saw
+    # a float order column on a handle that would not take the column anyway: what the handle refuses comes before NOT_IMPLEMENTED
+    fails(K.ERR_BAD_ARGUMENTS, lambda: raw(K.WIN_SUM, c_week, fcol, xcol, handle=none.win), on=none)
+    fails(K.ERR_BAD_ARGUMENTS, lambda: raw(K.WIN_SUM, c_week, fcol, xcol, handle=two.win), on=two)
+    fails(K.ERR_BAD_ARGUMENTS, lambda: raw(K.WIN_SUM, c_week, fcol, xcol))                       # w recorded Int64
 
 
 def test_an_empty_input(ch, ctx):

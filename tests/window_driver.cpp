@@ -46,26 +46,30 @@ static void test_frame_validation()
         for (int b = UP; b <= UF; ++b)
             for (int e = UP; e <= UF; ++e)
             {
-                const char * msg = nullptr;
-                const int rc = win_check_frame(frame_of(type, b, 3, e, 3), &msg);
+                // an entry that serves no RANGE offsets refuses the legal ones; for every other frame the flag changes nothing
                 const bool offset = b == OP || b == OF || e == OP || e == OF;
-                const int want = !legal[b][e] ? CHGPU_ERR_BAD_ARGUMENTS : (type == CHGPU_FRAME_RANGE && offset) ? CHGPU_ERR_NOT_IMPLEMENTED : CHGPU_OK;
-                CHECK(rc == want);
-                CHECK((rc == CHGPU_OK) == (msg == nullptr));
+                for (int serves = 0; serves < 2; ++serves)
+                {
+                    const char * msg = nullptr;
+                    const int rc = win_check_frame(frame_of(type, b, 3, e, 3), serves != 0, &msg);
+                    const int want = !legal[b][e] ? CHGPU_ERR_BAD_ARGUMENTS : (type == CHGPU_FRAME_RANGE && offset && !serves) ? CHGPU_ERR_NOT_IMPLEMENTED : CHGPU_OK;
+                    CHECK(rc == want);
+                    CHECK((rc == CHGPU_OK) == (msg == nullptr));
+                }
                 seen += 1;
             }
     CHECK(seen == 50);
     const char * msg = nullptr;
-    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, OP, 1, OP, 2), &msg) == CHGPU_ERR_BAD_ARGUMENTS);
-    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, OP, 2, OP, 1), &msg) == CHGPU_OK);
-    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, OF, 2, OF, 1), &msg) == CHGPU_ERR_BAD_ARGUMENTS);
-    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, OF, 1, OF, 2), &msg) == CHGPU_OK);
-    CHECK(win_check_frame(frame_of(CHGPU_FRAME_RANGE, OP, 1, OP, 2), &msg) == CHGPU_ERR_BAD_ARGUMENTS); // illegal before unimplemented
-    CHECK(win_check_frame(frame_of(2, UP, 0, CR, 0), &msg) == CHGPU_ERR_BAD_ARGUMENTS);
-    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, -1, 0, CR, 0), &msg) == CHGPU_ERR_BAD_ARGUMENTS);
-    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, UP, 0, 5, 0), &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, OP, 1, OP, 2), false, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, OP, 2, OP, 1), false, &msg) == CHGPU_OK);
+    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, OF, 2, OF, 1), false, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, OF, 1, OF, 2), false, &msg) == CHGPU_OK);
+    CHECK(win_check_frame(frame_of(CHGPU_FRAME_RANGE, OP, 1, OP, 2), false, &msg) == CHGPU_ERR_BAD_ARGUMENTS); // illegal before unimplemented
+    CHECK(win_check_frame(frame_of(2, UP, 0, CR, 0), false, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, -1, 0, CR, 0), false, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(win_check_frame(frame_of(CHGPU_FRAME_ROWS, UP, 0, 5, 0), false, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
     const chgpu_window_frame d = win_default_frame();
-    CHECK(d.type == CHGPU_FRAME_RANGE && d.begin_kind == UP && d.end_kind == CR && win_check_frame(d, &msg) == CHGPU_OK);
+    CHECK(d.type == CHGPU_FRAME_RANGE && d.begin_kind == UP && d.end_kind == CR && win_check_frame(d, false, &msg) == CHGPU_OK);
 }
 
 // is row j of the partition inside the frame of row i?  Straight from the definition, in arithmetic that cannot wrap.
@@ -105,7 +109,7 @@ static void test_frames_against_brute_force()
                         {
                             const chgpu_window_frame f = frame_of(type, b, bo, e, eo);
                             const char * msg = nullptr;
-                            if (win_check_frame(f, &msg) != CHGPU_OK)
+                            if (win_check_frame(f, false, &msg) != CHGPU_OK)
                                 continue;
                             const uint64_t ps = L.ps, pe = L.ps + L.len;
                             for (uint64_t i = ps; i < pe; ++i)
@@ -135,7 +139,7 @@ static void test_frames_against_brute_force()
             {
                 const chgpu_window_frame f = frame_of(type, b, 2, e, 2);
                 const char * msg = nullptr;
-                if (win_check_frame(f, &msg) != CHGPU_OK)
+                if (win_check_frame(f, false, &msg) != CHGPU_OK)
                     continue;
                 const uint32_t needs = win_frame_needs(f);
                 uint64_t fs = 0, fe = 0, gs2 = 0, ge2 = 0;
@@ -171,27 +175,28 @@ static void test_plans_and_lazy_bounds()
     const chgpu_window_frame ahead = frame_of(CHGPU_FRAME_ROWS, CHGPU_BOUND_CURRENT_ROW, 0, CHGPU_BOUND_UNBOUNDED_FOLLOWING, 0);
     const chgpu_window_frame self = frame_of(CHGPU_FRAME_ROWS, CHGPU_BOUND_CURRENT_ROW, 0, CHGPU_BOUND_CURRENT_ROW, 0);
     const chgpu_window_frame two_sided = frame_of(CHGPU_FRAME_ROWS, CHGPU_BOUND_OFFSET_PRECEDING, 1, CHGPU_BOUND_OFFSET_FOLLOWING, 1);
-    uint32_t needs = 0;
-    bool back = false;
-    const char * msg = nullptr;
-    CHECK(win_plan(CHGPU_WIN_ROW_NUMBER, dflt, -1, &needs, &back, &msg) == CHGPU_OK && needs == WIN_B_PS);
-    CHECK(win_plan(CHGPU_WIN_RANK, dflt, -1, &needs, &back, &msg) == CHGPU_OK && needs == (WIN_B_PS | WIN_B_GS)); // rank() never builds pe
-    CHECK(win_plan(CHGPU_WIN_DENSE_RANK, dflt, -1, &needs, &back, &msg) == CHGPU_OK && needs == (WIN_B_PS | WIN_B_DENSE));
-    CHECK(win_plan(CHGPU_WIN_COUNT, dflt, -1, &needs, &back, &msg) == CHGPU_OK && needs == (WIN_B_PS | WIN_B_GE));
-    CHECK(win_plan(CHGPU_WIN_COUNT, self, -1, &needs, &back, &msg) == CHGPU_OK && needs == 0);
-    CHECK(win_plan(CHGPU_WIN_SUM, rows_running, CHGPU_I64, &needs, &back, &msg) == CHGPU_OK && needs == WIN_B_PS);
-    CHECK(win_plan(CHGPU_WIN_SUM, sliding, CHGPU_U8, &needs, &back, &msg) == CHGPU_OK && needs == WIN_B_PS);
-    CHECK(win_plan(CHGPU_WIN_AVG, two_sided, CHGPU_I16, &needs, &back, &msg) == CHGPU_OK && needs == (WIN_B_PS | WIN_B_PE));
-    CHECK(win_plan(CHGPU_WIN_MAX, whole, CHGPU_F64, &needs, &back, &msg) == CHGPU_OK && needs == (WIN_B_PS | WIN_B_PE) && !back);
-    CHECK(win_plan(CHGPU_WIN_MIN, ahead, CHGPU_F32, &needs, &back, &msg) == CHGPU_OK && needs == WIN_B_PE && back);
-    CHECK(win_plan(CHGPU_WIN_MIN, two_sided, CHGPU_I64, &needs, &back, &msg) == CHGPU_ERR_NOT_IMPLEMENTED);
-    CHECK(win_plan(CHGPU_WIN_SUM, whole, CHGPU_F64, &needs, &back, &msg) == CHGPU_ERR_NOT_IMPLEMENTED);
-    CHECK(win_plan(CHGPU_WIN_AVG, whole, CHGPU_F32, &needs, &back, &msg) == CHGPU_ERR_NOT_IMPLEMENTED);
-    CHECK(win_plan(CHGPU_WIN_LAG_IN_FRAME, whole, CHGPU_F32, &needs, &back, &msg) == CHGPU_OK && needs == (WIN_B_PS | WIN_B_PE));
-    CHECK(win_plan(CHGPU_WIN_SUM, whole, -1, &needs, &back, &msg) == CHGPU_ERR_BAD_ARGUMENTS);  // no argument
-    CHECK(win_plan(CHGPU_WIN_RANK, whole, CHGPU_I64, &needs, &back, &msg) == CHGPU_ERR_BAD_ARGUMENTS); // a surplus one
-    CHECK(win_plan(-1, whole, -1, &needs, &back, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
-    CHECK(win_plan(CHGPU_WIN_LEAD_IN_FRAME + 1, whole, CHGPU_I64, &needs, &back, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    // chgpu_window_evaluate's plans: no order column, and a handle whose facts do not enter without one
+    WinPlan plan;
+    std::string msg;
+    const auto plan_of = [&](int function, const chgpu_window_frame & frame, int arg_type) { return win_plan(false, function, frame, arg_type, -1, 0, -1, &plan, &msg); };
+    CHECK(plan_of(CHGPU_WIN_ROW_NUMBER, dflt, -1) == CHGPU_OK && plan.needs == WIN_B_PS);
+    CHECK(plan_of(CHGPU_WIN_RANK, dflt, -1) == CHGPU_OK && plan.needs == (WIN_B_PS | WIN_B_GS)); // rank() never builds pe
+    CHECK(plan_of(CHGPU_WIN_DENSE_RANK, dflt, -1) == CHGPU_OK && plan.needs == (WIN_B_PS | WIN_B_DENSE));
+    CHECK(plan_of(CHGPU_WIN_COUNT, dflt, -1) == CHGPU_OK && plan.needs == (WIN_B_PS | WIN_B_GE));
+    CHECK(plan_of(CHGPU_WIN_COUNT, self, -1) == CHGPU_OK && plan.needs == 0);
+    CHECK(plan_of(CHGPU_WIN_SUM, rows_running, CHGPU_I64) == CHGPU_OK && plan.needs == WIN_B_PS);
+    CHECK(plan_of(CHGPU_WIN_SUM, sliding, CHGPU_U8) == CHGPU_OK && plan.needs == WIN_B_PS);
+    CHECK(plan_of(CHGPU_WIN_AVG, two_sided, CHGPU_I16) == CHGPU_OK && plan.needs == (WIN_B_PS | WIN_B_PE));
+    CHECK(plan_of(CHGPU_WIN_MAX, whole, CHGPU_F64) == CHGPU_OK && plan.needs == (WIN_B_PS | WIN_B_PE) && plan.ext == WIN_EXT_FORWARD);
+    CHECK(plan_of(CHGPU_WIN_MIN, ahead, CHGPU_F32) == CHGPU_OK && plan.needs == WIN_B_PE && plan.ext == WIN_EXT_BACKWARD);
+    CHECK(plan_of(CHGPU_WIN_MIN, two_sided, CHGPU_I64) == CHGPU_ERR_NOT_IMPLEMENTED);
+    CHECK(plan_of(CHGPU_WIN_SUM, whole, CHGPU_F64) == CHGPU_ERR_NOT_IMPLEMENTED);
+    CHECK(plan_of(CHGPU_WIN_AVG, whole, CHGPU_F32) == CHGPU_ERR_NOT_IMPLEMENTED);
+    CHECK(plan_of(CHGPU_WIN_LAG_IN_FRAME, whole, CHGPU_F32) == CHGPU_OK && plan.needs == (WIN_B_PS | WIN_B_PE));
+    CHECK(plan_of(CHGPU_WIN_SUM, whole, -1) == CHGPU_ERR_BAD_ARGUMENTS);  // no argument
+    CHECK(plan_of(CHGPU_WIN_RANK, whole, CHGPU_I64) == CHGPU_ERR_BAD_ARGUMENTS); // a surplus one
+    CHECK(plan_of(-1, whole, -1) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(plan_of(CHGPU_WIN_LEAD_IN_FRAME + 1, whole, CHGPU_I64) == CHGPU_ERR_BAD_ARGUMENTS);
 
     WinLazy lazy;
     CHECK(lazy.missing(WIN_B_PS | WIN_B_GS) == (WIN_B_PS | WIN_B_GS));

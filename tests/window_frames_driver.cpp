@@ -2,7 +2,8 @@
 // stand-alone program, built with -fsanitize=address,undefined by tests/test_window_frames_abi.py: the search behind a RANGE offset against
 // a linear scan in 128-bit arithmetic (all eight types, both directions, values at the types' limits, unsorted data), a host restatement
 // of the block masks plus the query arithmetic of the general min / max against brute force, the level count, and which frames and plans
-// the framed entry accepts.
+// the framed entry accepts: the one frame check and the one plan of window_host.h, asked as the framed entry and as the old one, with
+// the order of their refusals.
 #include <cstdio>
 #include <cstdlib>
 #include <limits>
@@ -303,22 +304,23 @@ static void test_frames_and_plans()
 {
     const int UP = CHGPU_BOUND_UNBOUNDED_PRECEDING, OP = CHGPU_BOUND_OFFSET_PRECEDING, CR = CHGPU_BOUND_CURRENT_ROW, OF = CHGPU_BOUND_OFFSET_FOLLOWING,
               UF = CHGPU_BOUND_UNBOUNDED_FOLLOWING;
-    // every pair of bounds: the framed check answers what the old one does, except that a legal RANGE offset passes
+    // every pair of bounds: the one check answers the same for both entries, except that a legal RANGE offset passes where the entry serves it
     for (int type = 0; type < 2; ++type)
         for (int b = UP; b <= UF; ++b)
             for (int e = UP; e <= UF; ++e)
             {
                 const char * msg = nullptr, * old_msg = nullptr;
                 const chgpu_window_frame f = frame_of(type, b, 3, e, 3);
-                const int rc = win_check_frame_framed(f, &msg), old = win_check_frame(f, &old_msg);
+                const int rc = win_check_frame(f, true, &msg), old = win_check_frame(f, false, &old_msg);
                 CHECK(rc == (old == CHGPU_ERR_NOT_IMPLEMENTED ? CHGPU_OK : old));
-                CHECK((rc == CHGPU_OK) == (msg == nullptr));
+                CHECK((old == CHGPU_ERR_NOT_IMPLEMENTED) == (rc == CHGPU_OK && win_frame_has_range_offset(f)));
+                CHECK((rc == CHGPU_OK) == (msg == nullptr) && (old == CHGPU_OK) == (old_msg == nullptr));
             }
     const char * msg = nullptr;
-    CHECK(win_check_frame_framed(frame_of(CHGPU_FRAME_RANGE, OP, 1, OP, 2), &msg) == CHGPU_ERR_BAD_ARGUMENTS);
-    CHECK(win_check_frame_framed(frame_of(CHGPU_FRAME_RANGE, OF, 2, OF, 1), &msg) == CHGPU_ERR_BAD_ARGUMENTS);
-    CHECK(win_check_frame_framed(frame_of(CHGPU_FRAME_RANGE, OP, 2, OP, 1), &msg) == CHGPU_OK);
-    CHECK(win_check_frame_framed(frame_of(2, OP, 2, OP, 1), &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(win_check_frame(frame_of(CHGPU_FRAME_RANGE, OP, 1, OP, 2), true, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(win_check_frame(frame_of(CHGPU_FRAME_RANGE, OF, 2, OF, 1), true, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(win_check_frame(frame_of(CHGPU_FRAME_RANGE, OP, 2, OP, 1), true, &msg) == CHGPU_OK);
+    CHECK(win_check_frame(frame_of(2, OP, 2, OP, 1), true, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
 
     const chgpu_window_frame dflt = win_default_frame();
     const chgpu_window_frame whole = frame_of(CHGPU_FRAME_ROWS, UP, 0, UF, 0);
@@ -329,17 +331,35 @@ static void test_frames_and_plans()
     const chgpu_window_frame week = frame_of(CHGPU_FRAME_RANGE, OP, 604800, CR, 0);
     const chgpu_window_frame band = frame_of(CHGPU_FRAME_RANGE, OP, 10, OF, 0);
     const chgpu_window_frame tail = frame_of(CHGPU_FRAME_RANGE, OF, 3, UF, 0);
-    WinFramedPlan plan;
-    // what the old entry serves runs the old path, with the old plan's arrays
-    CHECK(win_plan_framed(CHGPU_WIN_RANK, dflt, -1, -1, &plan, &msg) == CHGPU_OK && plan.old_entry && plan.needs == (WIN_B_PS | WIN_B_GS));
-    CHECK(win_plan_framed(CHGPU_WIN_SUM, around, CHGPU_I32, -1, &plan, &msg) == CHGPU_OK && plan.old_entry && plan.needs == (WIN_B_PS | WIN_B_PE));
-    CHECK(win_plan_framed(CHGPU_WIN_MAX, whole, CHGPU_F64, -1, &plan, &msg) == CHGPU_OK && plan.old_entry && plan.ext == WIN_EXT_FORWARD);
-    CHECK(win_plan_framed(CHGPU_WIN_MIN, ahead, CHGPU_F32, -1, &plan, &msg) == CHGPU_OK && plan.old_entry && plan.ext == WIN_EXT_BACKWARD && plan.needs == WIN_B_PE);
+    WinPlan plan;
+    std::string why;
+    // the framed entry on a handle that recorded the very order column given (or any handle, where none is given)
+    const auto framed = [&](int function, const chgpu_window_frame & frame, int arg_type, int order_type) {
+        return win_plan(true, function, frame, arg_type, order_type, 1, order_type, &plan, &why);
+    };
+    // `plan` is, field for field, what chgpu_window_evaluate plans for the call
+    const auto same_as_unframed = [&](int function, const chgpu_window_frame & frame, int arg_type) {
+        WinPlan old;
+        std::string old_why;
+        return win_plan(false, function, frame, arg_type, -1, 1, -1, &old, &old_why) == CHGPU_OK && old.needs == plan.needs && old.ext == plan.ext
+            && old.search_begin == plan.search_begin && old.search_end == plan.search_end && old.width == plan.width;
+    };
+    const auto unframed_refuses = [&](int function, const chgpu_window_frame & frame, int arg_type) {
+        WinPlan old;
+        std::string old_why;
+        const char * m = nullptr;
+        return win_check_frame(frame, false, &m) == CHGPU_ERR_NOT_IMPLEMENTED || win_plan(false, function, frame, arg_type, -1, 1, -1, &old, &old_why) == CHGPU_ERR_NOT_IMPLEMENTED;
+    };
+    // what the old entry serves gets the old entry's plan
+    CHECK(framed(CHGPU_WIN_RANK, dflt, -1, -1) == CHGPU_OK && same_as_unframed(CHGPU_WIN_RANK, dflt, -1) && plan.needs == (WIN_B_PS | WIN_B_GS));
+    CHECK(framed(CHGPU_WIN_SUM, around, CHGPU_I32, -1) == CHGPU_OK && same_as_unframed(CHGPU_WIN_SUM, around, CHGPU_I32) && plan.needs == (WIN_B_PS | WIN_B_PE));
+    CHECK(framed(CHGPU_WIN_MAX, whole, CHGPU_F64, -1) == CHGPU_OK && same_as_unframed(CHGPU_WIN_MAX, whole, CHGPU_F64) && plan.ext == WIN_EXT_FORWARD);
+    CHECK(framed(CHGPU_WIN_MIN, ahead, CHGPU_F32, -1) == CHGPU_OK && same_as_unframed(CHGPU_WIN_MIN, ahead, CHGPU_F32) && plan.ext == WIN_EXT_BACKWARD && plan.needs == WIN_B_PE);
     // (a) min / max over a frame bounded on both sides
-    CHECK(win_plan_framed(CHGPU_WIN_MAX, around, CHGPU_I64, -1, &plan, &msg) == CHGPU_OK && !plan.old_entry && plan.ext == WIN_EXT_GENERAL);
+    CHECK(framed(CHGPU_WIN_MAX, around, CHGPU_I64, -1) == CHGPU_OK && unframed_refuses(CHGPU_WIN_MAX, around, CHGPU_I64) && plan.ext == WIN_EXT_GENERAL);
     CHECK(plan.width == 2001 && plan.needs == (WIN_B_PS | WIN_B_PE) && !plan.search_begin && !plan.search_end);
-    CHECK(win_plan_framed(CHGPU_WIN_MIN, before, CHGPU_F32, -1, &plan, &msg) == CHGPU_OK && plan.ext == WIN_EXT_GENERAL && plan.width == 4 && plan.needs == WIN_B_PS);
-    CHECK(win_plan_framed(CHGPU_WIN_MIN, peers, CHGPU_U8, -1, &plan, &msg) == CHGPU_OK && plan.ext == WIN_EXT_GENERAL && plan.width == ~0ull);
+    CHECK(framed(CHGPU_WIN_MIN, before, CHGPU_F32, -1) == CHGPU_OK && plan.ext == WIN_EXT_GENERAL && plan.width == 4 && plan.needs == WIN_B_PS);
+    CHECK(framed(CHGPU_WIN_MIN, peers, CHGPU_U8, -1) == CHGPU_OK && plan.ext == WIN_EXT_GENERAL && plan.width == ~0ull);
     CHECK(plan.needs == (WIN_B_GS | WIN_B_GE));
     CHECK(win_frame_max_width(frame_of(CHGPU_FRAME_ROWS, OP, ~0ull, OF, ~0ull)) == ~0ull && win_frame_max_width(frame_of(CHGPU_FRAME_ROWS, CR, 0, CR, 0)) == 1);
     CHECK(win_frame_max_width(frame_of(CHGPU_FRAME_ROWS, OF, 2, OF, 9)) == 8 && win_frame_max_width(frame_of(CHGPU_FRAME_ROWS, OP, 3, CR, 0)) == 4);
@@ -348,28 +368,50 @@ static void test_frames_and_plans()
     for (int ot : order_types)
         for (int fn = CHGPU_WIN_COUNT; fn <= CHGPU_WIN_LEAD_IN_FRAME; ++fn)
         {
-            CHECK(win_plan_framed(fn, week, fn == CHGPU_WIN_COUNT ? -1 : CHGPU_I64, ot, &plan, &msg) == CHGPU_OK);
-            CHECK(!plan.old_entry && plan.search_begin && !plan.search_end && plan.needs == (WIN_B_PS | WIN_B_GE));
+            CHECK(framed(fn, week, fn == CHGPU_WIN_COUNT ? -1 : CHGPU_I64, ot) == CHGPU_OK);
+            CHECK(unframed_refuses(fn, week, fn == CHGPU_WIN_COUNT ? -1 : CHGPU_I64) && plan.search_begin && !plan.search_end && plan.needs == (WIN_B_PS | WIN_B_GE));
             CHECK(plan.ext == (fn == CHGPU_WIN_MIN || fn == CHGPU_WIN_MAX ? WIN_EXT_GENERAL : WIN_EXT_NONE));
         }
-    CHECK(win_plan_framed(CHGPU_WIN_SUM, band, CHGPU_U16, CHGPU_I64, &plan, &msg) == CHGPU_OK && plan.search_begin && !plan.search_end); // 0 FOLLOWING: ge
+    CHECK(framed(CHGPU_WIN_SUM, band, CHGPU_U16, CHGPU_I64) == CHGPU_OK && plan.search_begin && !plan.search_end); // 0 FOLLOWING: ge
     CHECK(plan.needs == (WIN_B_PS | WIN_B_GE));
-    CHECK(win_plan_framed(CHGPU_WIN_MAX, tail, CHGPU_F64, CHGPU_U8, &plan, &msg) == CHGPU_OK && plan.ext == WIN_EXT_GENERAL && plan.search_begin && plan.needs == WIN_B_PE);
+    CHECK(framed(CHGPU_WIN_MAX, tail, CHGPU_F64, CHGPU_U8) == CHGPU_OK && plan.ext == WIN_EXT_GENERAL && plan.search_begin && plan.needs == WIN_B_PE);
     CHECK(plan.width == ~0ull);
     // the refusals and their codes
-    CHECK(win_plan_framed(CHGPU_WIN_SUM, week, CHGPU_I64, -1, &plan, &msg) == CHGPU_ERR_BAD_ARGUMENTS);          // no order column
-    CHECK(win_plan_framed(CHGPU_WIN_SUM, around, CHGPU_I64, CHGPU_I64, &plan, &msg) == CHGPU_ERR_BAD_ARGUMENTS); // a surplus one
-    CHECK(win_plan_framed(CHGPU_WIN_RANK, week, -1, CHGPU_I64, &plan, &msg) == CHGPU_ERR_BAD_ARGUMENTS);         // rank ignores the frame
-    CHECK(win_plan_framed(CHGPU_WIN_RANK, week, -1, -1, &plan, &msg) == CHGPU_OK && plan.old_entry);
-    CHECK(win_plan_framed(CHGPU_WIN_SUM, week, CHGPU_I64, CHGPU_F64, &plan, &msg) == CHGPU_ERR_NOT_IMPLEMENTED);
-    CHECK(win_plan_framed(CHGPU_WIN_COUNT, week, -1, CHGPU_F32, &plan, &msg) == CHGPU_ERR_NOT_IMPLEMENTED);
-    CHECK(win_plan_framed(CHGPU_WIN_SUM, week, CHGPU_F64, CHGPU_I64, &plan, &msg) == CHGPU_ERR_NOT_IMPLEMENTED); // float sums stay out
-    CHECK(win_plan_framed(CHGPU_WIN_AVG, around, CHGPU_F32, -1, &plan, &msg) == CHGPU_ERR_NOT_IMPLEMENTED);
-    CHECK(win_plan_framed(CHGPU_WIN_SUM, week, -1, CHGPU_I64, &plan, &msg) == CHGPU_ERR_BAD_ARGUMENTS);          // no argument
-    CHECK(win_plan_framed(CHGPU_WIN_COUNT, week, CHGPU_I64, CHGPU_I64, &plan, &msg) == CHGPU_ERR_BAD_ARGUMENTS); // a surplus one
-    CHECK(win_plan_framed(CHGPU_WIN_MAX, around, -1, -1, &plan, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
-    CHECK(win_plan_framed(12, around, CHGPU_I64, -1, &plan, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
-    CHECK(win_plan_framed(-1, week, CHGPU_I64, CHGPU_I64, &plan, &msg) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(framed(CHGPU_WIN_SUM, week, CHGPU_I64, -1) == CHGPU_ERR_BAD_ARGUMENTS);          // no order column
+    CHECK(framed(CHGPU_WIN_SUM, around, CHGPU_I64, CHGPU_I64) == CHGPU_ERR_BAD_ARGUMENTS); // a surplus one
+    CHECK(framed(CHGPU_WIN_RANK, week, -1, CHGPU_I64) == CHGPU_ERR_BAD_ARGUMENTS);         // rank ignores the frame
+    CHECK(framed(CHGPU_WIN_RANK, week, -1, -1) == CHGPU_OK && same_as_unframed(CHGPU_WIN_RANK, week, -1));
+    CHECK(framed(CHGPU_WIN_SUM, week, CHGPU_I64, CHGPU_F64) == CHGPU_ERR_NOT_IMPLEMENTED);
+    CHECK(framed(CHGPU_WIN_COUNT, week, -1, CHGPU_F32) == CHGPU_ERR_NOT_IMPLEMENTED);
+    CHECK(framed(CHGPU_WIN_SUM, week, CHGPU_F64, CHGPU_I64) == CHGPU_ERR_NOT_IMPLEMENTED); // float sums stay out
+    CHECK(framed(CHGPU_WIN_AVG, around, CHGPU_F32, -1) == CHGPU_ERR_NOT_IMPLEMENTED);
+    CHECK(framed(CHGPU_WIN_SUM, week, -1, CHGPU_I64) == CHGPU_ERR_BAD_ARGUMENTS);          // no argument
+    CHECK(framed(CHGPU_WIN_COUNT, week, CHGPU_I64, CHGPU_I64) == CHGPU_ERR_BAD_ARGUMENTS); // a surplus one
+    CHECK(framed(CHGPU_WIN_MAX, around, -1, -1) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(framed(12, around, CHGPU_I64, -1) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(framed(-1, week, CHGPU_I64, CHGPU_I64) == CHGPU_ERR_BAD_ARGUMENTS);
+
+    // what the handle recorded at create comes before what is not implemented: (ORDER BY columns, type of the first) of three handles
+    // that cannot take an Int64 order column, and of the three that cannot take a Float64 one
+    const auto on_handle = [&](int function, int arg_type, int order_type, uint32_t n_order, int recorded) {
+        return win_plan(true, function, week, arg_type, order_type, n_order, recorded, &plan, &why);
+    };
+    struct Handle { uint32_t n_order; int recorded; };
+    for (const Handle & h : {Handle{0, -1}, Handle{2, CHGPU_I64}, Handle{1, CHGPU_I32}})
+    {
+        CHECK(on_handle(CHGPU_WIN_SUM, CHGPU_I64, CHGPU_I64, h.n_order, h.recorded) == CHGPU_ERR_BAD_ARGUMENTS);
+        CHECK(on_handle(CHGPU_WIN_SUM, CHGPU_F64, CHGPU_I64, h.n_order, h.recorded) == CHGPU_ERR_BAD_ARGUMENTS); // a float sum as well
+        CHECK(on_handle(CHGPU_WIN_SUM, -1, CHGPU_I64, h.n_order, h.recorded) == CHGPU_ERR_BAD_ARGUMENTS);        // the missing argument is found first
+        CHECK(why.find("takes an argument column") != std::string::npos);
+    }
+    for (const Handle & h : {Handle{0, -1}, Handle{2, CHGPU_F64}, Handle{1, CHGPU_I64}})
+        CHECK(on_handle(CHGPU_WIN_SUM, CHGPU_I64, CHGPU_F64, h.n_order, h.recorded) == CHGPU_ERR_BAD_ARGUMENTS);
+    CHECK(on_handle(CHGPU_WIN_SUM, CHGPU_I64, CHGPU_F64, 1, CHGPU_F64) == CHGPU_ERR_NOT_IMPLEMENTED); // the handle matches: a float order column
+    CHECK(on_handle(CHGPU_WIN_SUM, CHGPU_F64, CHGPU_I64, 1, CHGPU_I64) == CHGPU_ERR_NOT_IMPLEMENTED); // ... a float sum
+    CHECK(on_handle(CHGPU_WIN_SUM, CHGPU_I64, CHGPU_I64, 2, CHGPU_I64) == CHGPU_ERR_BAD_ARGUMENTS && why.find("this one has 2") != std::string::npos);
+    // an unknown function with a legal RANGE offset: the old entry stops at the frame, the framed one at the function
+    CHECK(win_check_frame(week, false, &msg) == CHGPU_ERR_NOT_IMPLEMENTED);
+    CHECK(win_check_frame(week, true, &msg) == CHGPU_OK && framed(12, week, CHGPU_I64, CHGPU_I64) == CHGPU_ERR_BAD_ARGUMENTS && why == "unknown window function");
 }
 
 int main()
