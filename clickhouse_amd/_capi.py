@@ -26,6 +26,8 @@ STRICT_ANY, STRICT_ALL, STRICT_SEMI, STRICT_ANTI = 0, 1, 2, 3
 N_COUNTERS = 8
 VAL_COL, VAL_MUL, VAL_PLUS, VAL_MINUS = 0, 1, 2, 3
 STR_LIKE, STR_CONTAINS, STR_STARTS_WITH, STR_ENDS_WITH = 0, 1, 2, 3
+STR_LENGTH, STR_LENGTH_UTF8, STR_EMPTY, STR_NOT_EMPTY = 0, 1, 2, 3   # chgpu_string_length kinds
+STR_LOWER, STR_UPPER = 0, 1                                         # chgpu_string_map_case kinds
 STR_ROUTE_EQUALS, STR_ROUTE_STARTS_WITH, STR_ROUTE_ENDS_WITH, STR_ROUTE_CONTAINS, STR_ROUTE_GENERAL = 0, 1, 2, 3, 4
 QUANTILE_EXACT, QUANTILE_EXACT_LOW, QUANTILE_EXACT_HIGH = 0, 1, 2
 QUANTILE_EXACT_INCLUSIVE, QUANTILE_EXACT_EXCLUSIVE, QUANTILE_EXACT_WEIGHTED = 3, 4, 5   # reserved: NOT_IMPLEMENTED
@@ -49,6 +51,11 @@ class LikePlan(C.Structure):
     _fields_ = [("route", C.c_int32), ("n_percent", C.c_uint32), ("n_underscore", C.c_uint32), ("literal_bytes", C.c_uint32),
                 ("n_tokens", C.c_uint32), ("token_meta", C.c_uint32 * (STR_CONST_MAX // 32)), ("literal", C.c_uint8 * STR_CONST_MAX),
                 ("tokens", C.c_uint8 * STR_CONST_MAX)]
+
+
+class StringArg(C.Structure):
+    """chgpu_string_arg: one argument of chgpu_string_concat, a column (offsets, chars) or a constant in host memory (value, value_bytes)"""
+    _fields_ = [("offsets", C.c_void_p), ("chars", C.c_void_p), ("value", C.c_char_p), ("value_bytes", C.c_uint64)]
 
 
 class WindowFrame(C.Structure):
@@ -130,6 +137,12 @@ SIGNATURES = {
     "chgpu_string_cmp_const": (_i, [_vp, _vp, _vp, _i, C.c_char_p, _u64, _pp]),
     "chgpu_string_match_const": (_i, [_vp, _vp, _vp, _i, C.c_char_p, _u64, _i, _pp]),
     "chgpu_like_compile": (_i, [C.c_char_p, _u64, _vp]),
+    "chgpu_string_length": (_i, [_vp, _vp, _vp, _i, _pp]),
+    "chgpu_string_map_case": (_i, [_vp, _vp, _vp, _i, _pp, _pp]),
+    "chgpu_string_cmp_columns": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _pp]),
+    "chgpu_string_substring": (_i, [_vp, _vp, _vp, _i64, _i, _u64, _pp, _pp]),
+    "chgpu_string_concat": (_i, [_vp, _vp, _u32, _pp, _pp]),
+    "chgpu_string_position_const": (_i, [_vp, _vp, _vp, C.c_char_p, _u64, _pp]),
     "chgpu_lc_remap": (_i, [_vp, _vp, _vp, _pp]),
     "chgpu_agg_create": (_i, [_vp, _i, _u32, C.POINTER(_i), C.POINTER(_i), _u64, _pp]),
     "chgpu_agg_add_block": (_i, [_vp, _vp, _pp, _u64, _u64]),

@@ -1,6 +1,7 @@
-// string_column.h — what a kernel or an entry point of string_kernels.hip and string_sort_kernels.hip needs to know about a
-// ColumnString (src/Columns/ColumnString.h:40-52: `chars` with a terminating zero after every value, `offsets[i]` = end of value i
-// including that zero), written once.  Device: str_load8, str_value, str_copy_value, str_size_u32.  Host: the entry points' prologue
+// string_column.h — what a kernel or an entry point of string_kernels.hip, string_sort_kernels.hip and string_func_kernels.hip needs to
+// know about a ColumnString (src/Columns/ColumnString.h:40-52: `chars` with a terminating zero after every value, `offsets[i]` = end of
+// value i including that zero), written once.  Device: str_load8, str_value, str_copy_value, str_size_u32, and the constant a kernel
+// argument carries (StrConst, str_stage_const) with the two word tests made against it (str_tail_mask, str_zero_bytes).  Host: the entry points' prologue
 // (str_column_begin), the call's numbered allocations (str_call: pair_pool.h with `test_string_fail_alloc`) and its one pool
 // allocation divided by a layout of string_host.h (str_carve), the guard of a call's columns (StrCols), the layout pass.
 #pragma once
@@ -47,6 +48,52 @@ __device__ __forceinline__ u32 str_size_u32(u64 sz, u32 * __restrict__ too_long)
     if (sz >= (1ull << 32))
         *too_long = 1, sz = 0;
     return (u32)sz;
+}
+
+// A constant (a value, a needle, a LIKE pattern, the constant parts of a concat) travels in the kernel argument -- no device allocation,
+// no upload -- and is staged into LDS once per workgroup, where every lane reads it at its own index.
+static constexpr u32 SM_MAX = CHGPU_STR_CONST_MAX; // bytes of a constant / tokens of a pattern a kernel argument carries
+
+struct StrConst
+{
+    u64 w[SM_MAX / 8];     // the bytes (little endian words), zero padded
+    u32 meta[SM_MAX / 32]; // k_str_like: bit i set = token i is a wildcard
+    u32 len;
+    u32 pad;
+};
+
+// kernel argument -> LDS with constant indices only (a lane-indexed read of the argument itself would go through scratch)
+__device__ __forceinline__ void str_stage_const(u64 * s_w, const StrConst & c)
+{
+    if (threadIdx.x == 0)
+    {
+#pragma unroll
+        for (u32 k = 0; k < SM_MAX / 8; ++k)
+            s_w[k] = c.w[k];
+    }
+}
+
+__device__ __forceinline__ u64 str_tail_mask(u64 bytes) // 1 <= bytes <= 7
+{
+    return ~0ull >> (8 * (8 - bytes));
+}
+
+// bit k set = byte k of x is zero
+__device__ __forceinline__ u32 str_zero_bytes(u64 x)
+{
+    const u64 l = 0x7F7F7F7F7F7F7F7Full;
+    const u64 z = ~(((x & l) + l) | x | l); // 0x80 in every zero byte, exact
+    return (u32)(((z >> 7) * 0x0102040810204080ull) >> 56);
+}
+
+static StrConst str_const_of(const void * bytes, u64 n)
+{
+    StrConst c;
+    memset(&c, 0, sizeof(c));
+    if (n)
+        memcpy(c.w, bytes, n);
+    c.len = (u32)n;
+    return c;
 }
 
 struct StrColumn // a validated ColumnString

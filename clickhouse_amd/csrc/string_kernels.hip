@@ -331,34 +331,10 @@ extern "C" int chgpu_string_filter(chgpu_ctx * ctx, const chgpu_col * offsets_u6
 //   k_str_like              any pattern with `_` or an inner `%`: one lane per row, the two-pointer wildcard match (the last `%` and the
 //                           haystack mark are remembered; a mismatch resumes after that `%` with the mark advanced by one byte).
 // ---------------------------------------------------------------------------------------------
-static constexpr u32 SM_MAX = CHGPU_STR_CONST_MAX; // bytes of a constant / tokens of a pattern a kernel argument carries
-static constexpr u32 SM_TILE = 4096;               // bytes of chars per workgroup step: 256 lanes x 16 B
-static constexpr u32 SM_ROWS_LDS = 1024;           // a tile with more rows than this searches its offsets in global memory
+static constexpr u32 SM_TILE = 4096;     // bytes of chars per workgroup step: 256 lanes x 16 B
+static constexpr u32 SM_ROWS_LDS = 1024; // a tile with more rows than this searches its offsets in global memory
 enum { SM_CMP = 0, SM_STARTS = 1, SM_ENDS = 2 };
-
-struct StrConst
-{
-    u64 w[SM_MAX / 8];     // the bytes (little endian words), zero padded
-    u32 meta[SM_MAX / 32]; // k_str_like: bit i set = token i is a wildcard
-    u32 len;
-    u32 pad;
-};
-
-// kernel argument -> LDS with constant indices only (a lane-indexed read of the argument itself would go through scratch)
-__device__ __forceinline__ void str_stage_const(u64 * s_w, const StrConst & c)
-{
-    if (threadIdx.x == 0)
-    {
-#pragma unroll
-        for (u32 k = 0; k < SM_MAX / 8; ++k)
-            s_w[k] = c.w[k];
-    }
-}
-
-__device__ __forceinline__ u64 str_tail_mask(u64 bytes) // 1 <= bytes <= 7
-{
-    return ~0ull >> (8 * (8 - bytes));
-}
+// (SM_MAX, StrConst, str_stage_const, str_tail_mask, str_zero_bytes and str_const_of are string_column.h's: the String functions use them, too)
 
 template <int MODE>
 __global__ __launch_bounds__(256) void k_str_row_const(const u64 * __restrict__ offsets, const u8 * __restrict__ chars, u64 n, const StrConst c, int op, u32 negate,
@@ -547,14 +523,6 @@ __device__ __forceinline__ uint4 str_load_chunk(const u8 * __restrict__ grid, u6
     return make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32));
 }
 
-// bit k set = byte k of x is zero
-__device__ __forceinline__ u32 str_zero_bytes(u64 x)
-{
-    const u64 l = 0x7F7F7F7F7F7F7F7Full;
-    const u64 z = ~(((x & l) + l) | x | l); // 0x80 in every zero byte, exact
-    return (u32)(((z >> 7) * 0x0102040810204080ull) >> 56);
-}
-
 __global__ __launch_bounds__(256) void k_str_contains_flat(const u64 * __restrict__ offsets, const u8 * __restrict__ chars, u64 n, u64 size,
                                                            const u64 * __restrict__ tile_row, u64 ntiles, const StrConst c, u8 hit_value, u8 * __restrict__ out)
 {
@@ -710,16 +678,6 @@ extern "C" int chgpu_like_compile(const void * pattern, uint64_t pattern_bytes, 
     else
         out->route = lead && trail ? CHGPU_STR_ROUTE_CONTAINS : lead ? CHGPU_STR_ROUTE_ENDS_WITH : trail ? CHGPU_STR_ROUTE_STARTS_WITH : CHGPU_STR_ROUTE_EQUALS;
     return CHGPU_OK;
-}
-
-static StrConst str_const_of(const void * bytes, u64 n)
-{
-    StrConst c;
-    memset(&c, 0, sizeof(c));
-    if (n)
-        memcpy(c.w, bytes, n);
-    c.len = (u32)n;
-    return c;
 }
 
 // the arguments every predicate shares, then `own_checks` (the entry point's), the offsets, and *out: a UInt8 column of one byte per row

@@ -15,6 +15,7 @@
 //   ExpressionTransform         src/Processors/Transforms/ExpressionTransform.cpp:22-30      chgpu::GpuExpressionTransform, GpuExpressionFilterTransform
 //   ColumnLowCardinality + low_cardinality_key* methods   src/Columns/ColumnLowCardinality.h:27-69, ColumnsHashing.h:82-260   chgpu::ColumnLowCardinality, LowCardinalityDictionary
 //   ColumnString as a key       src/Columns/ColumnString.h:40-49, ColumnUnique.h:520-620     chgpu::ColumnString::dictionaryEncode
+//   String functions (length, lower, substring, concat, position, a <op> b)   src/Functions/FunctionStringOrArrayToT.h, LowerUpperImpl.h, FunctionsStringSearch.h, FunctionsComparison.h   chgpu::ColumnString::length .. concat
 //   sortBlock / SortDescription src/Interpreters/sortBlock.cpp:240-330, Core/SortDescription.h   chgpu::sortBlock
 //   MergingSortedTransform / MergeSortingTransform   src/Processors/Merges/MergingSortedTransform.h, Transforms/MergeSortingTransform.cpp   chgpu::GpuMergingSortedTransform, GpuMergeSortingTransform
 //   CompressedReadBuffer        src/Compression/CompressedReadBufferBase.cpp:175-222         chgpu::readCompressedColumn
@@ -939,7 +940,85 @@ struct ColumnString
     ColumnPtr startsWith(std::string_view needle, bool negate = false) const { return match(CHGPU_STR_STARTS_WITH, needle, negate); }
     ColumnPtr endsWith(std::string_view needle, bool negate = false) const { return match(CHGPU_STR_ENDS_WITH, needle, negate); }
 
+    /// Functions that compute a new column from this one.  Offsets and lengths count bytes; the UTF8, case-insensitive and
+    /// non-constant-argument forms have no entry point and stay on the CPU.
+    /// length (LengthImpl): UInt64
+    ColumnPtr length() const { return lengthKind(CHGPU_STR_LENGTH); }
+    /// lengthUTF8 (LengthUTF8Impl, UTF8::countCodePoints): the bytes that are no continuation byte, UInt64
+    ColumnPtr lengthUTF8() const { return lengthKind(CHGPU_STR_LENGTH_UTF8); }
+    /// empty / notEmpty (EmptyImpl): UInt8 0/1
+    ColumnPtr empty() const { return lengthKind(CHGPU_STR_EMPTY); }
+    ColumnPtr notEmpty() const { return lengthKind(CHGPU_STR_NOT_EMPTY); }
+    /// lower / upper (LowerUpperImpl<'A', 'Z'> / <'a', 'z'>): the ASCII forms
+    ColumnString lower() const { return mapCase(CHGPU_STR_LOWER); }
+    ColumnString upper() const { return mapCase(CHGPU_STR_UPPER); }
+    /// substring(s, offset[, length]) with constant arguments (FunctionsStringSubstring, SubstringImpl): offset >= 1 from the front,
+    /// offset <= -1 from the back, the window clipped to the value; offset == 0 throws NOT_IMPLEMENTED
+    ColumnString substring(int64_t offset) const { return substringImpl(offset, 0, 0); }
+    ColumnString substring(int64_t offset, uint64_t length) const { return substringImpl(offset, 1, length); }
+    /// position(haystack, needle) with a constant needle (PositionImpl::vectorConstant, bytes): 1-based, 0 without an occurrence, UInt64
+    ColumnPtr position(std::string_view needle) const
+    {
+        chgpu_col * out = nullptr;
+        check(chgpu_string_position_const(offsets->context()->get(), offsets->handle(), chars->handle(), needle.data(), needle.size(), &out));
+        return std::make_shared<ColumnVector>(offsets->context(), out);
+    }
+    /// equals .. greaterOrEquals against another String column (StringComparisonImpl::string_vector_string_vector): UInt8 0/1
+    ColumnPtr compareColumn(int op, const ColumnString & other) const
+    {
+        chgpu_col * out = nullptr;
+        check(chgpu_string_cmp_columns(offsets->context()->get(), offsets->handle(), chars->handle(), other.offsets->handle(), other.chars->handle(), op, &out));
+        return std::make_shared<ColumnVector>(offsets->context(), out);
+    }
+    /// One argument of concat: a column, or a constant (binary-safe; the view must outlive the call)
+    struct ConcatArg
+    {
+        const ColumnString * column = nullptr;
+        std::string_view constant;
+        ConcatArg(const ColumnString & c) : column(&c) {}
+        ConcatArg(std::string_view s) : constant(s) {}
+        ConcatArg(const char * s) : constant(s) {}
+    };
+    /// concat(a, b, ...) (ConcatImpl): 2 to 8 arguments, at least one of them a column
+    static ColumnString concat(const std::vector<ConcatArg> & args)
+    {
+        std::vector<chgpu_string_arg> raw(args.size());
+        ContextPtr ctx;
+        for (size_t i = 0; i < args.size(); ++i)
+        {
+            if (args[i].column)
+            {
+                raw[i] = chgpu_string_arg{args[i].column->offsets->handle(), args[i].column->chars->handle(), nullptr, 0};
+                if (!ctx)
+                    ctx = args[i].column->offsets->context();
+            }
+            else
+                raw[i] = chgpu_string_arg{nullptr, nullptr, args[i].constant.data(), args[i].constant.size()};
+        }
+        chgpu_col * oo = nullptr, * oc = nullptr;
+        check(chgpu_string_concat(ctx ? ctx->get() : nullptr, raw.data(), static_cast<uint32_t>(raw.size()), &oo, &oc));
+        return ColumnString{std::make_shared<ColumnVector>(ctx, oo), std::make_shared<ColumnVector>(ctx, oc)};
+    }
+
 private:
+    ColumnPtr lengthKind(int kind) const
+    {
+        chgpu_col * out = nullptr;
+        check(chgpu_string_length(offsets->context()->get(), offsets->handle(), chars->handle(), kind, &out));
+        return std::make_shared<ColumnVector>(offsets->context(), out);
+    }
+    ColumnString mapCase(int kind) const
+    {
+        chgpu_col * oo = nullptr, * oc = nullptr;
+        check(chgpu_string_map_case(offsets->context()->get(), offsets->handle(), chars->handle(), kind, &oo, &oc));
+        return ColumnString{std::make_shared<ColumnVector>(offsets->context(), oo), std::make_shared<ColumnVector>(offsets->context(), oc)};
+    }
+    ColumnString substringImpl(int64_t offset, int has_length, uint64_t length) const
+    {
+        chgpu_col * oo = nullptr, * oc = nullptr;
+        check(chgpu_string_substring(offsets->context()->get(), offsets->handle(), chars->handle(), offset, has_length, length, &oo, &oc));
+        return ColumnString{std::make_shared<ColumnVector>(offsets->context(), oo), std::make_shared<ColumnVector>(offsets->context(), oc)};
+    }
     ColumnPtr match(int kind, std::string_view pattern, bool negate) const
     {
         chgpu_col * out = nullptr;

@@ -62,6 +62,17 @@ def _const_bytes(value) -> bytes:
     return value.encode("utf-8") if isinstance(value, str) else bytes(value)
 
 
+def _const_arg(value) -> bytes:
+    """_const_bytes for the String functions: anything but str and the bytes-likes is a TypeError before the library is touched"""
+    if not isinstance(value, (str, bytes, bytearray, memoryview)):
+        raise TypeError(f"a constant String argument is bytes or str, not {type(value).__name__}")
+    return _const_bytes(value)
+
+
+def _is_int(value) -> bool:
+    return isinstance(value, (int, np.integer)) and not isinstance(value, bool)
+
+
 def like_compile(pattern) -> dict:
     """chgpu_like_compile: what a LIKE pattern compiles to (host only, no context): route (STR_ROUTE_*), the unescaped literal of the
     four literal routes, the number of % and _ tokens, and the token string the general matcher walks."""
@@ -163,6 +174,97 @@ class ColumnString:
 
     def ends_with(self, needle, negate: bool = False) -> Column:
         return self._match(K.STR_ENDS_WITH, needle, negate)
+
+    # -- functions: a new column computed from this one, on the device (string_func_kernels.hip) --
+    def _length(self, kind: int) -> Column:
+        h = C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(K.lib().chgpu_string_length(ctx._h, self.offsets._h, self.chars._h, kind, C.byref(h)))
+        return Column(ctx, h)
+
+    def length(self) -> Column:
+        """length: the bytes of every value, a UInt64 Column"""
+        return self._length(K.STR_LENGTH)
+
+    def length_utf8(self) -> Column:
+        """lengthUTF8: the bytes that are no continuation byte (10xxxxxx), on valid and invalid UTF-8 alike, a UInt64 Column"""
+        return self._length(K.STR_LENGTH_UTF8)
+
+    def empty(self) -> Column:
+        """empty: a UInt8 Column of 0/1"""
+        return self._length(K.STR_EMPTY)
+
+    def not_empty(self) -> Column:
+        """notEmpty: a UInt8 Column of 0/1"""
+        return self._length(K.STR_NOT_EMPTY)
+
+    def _map_case(self, kind: int) -> "ColumnString":
+        oo, oc = C.c_void_p(), C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(K.lib().chgpu_string_map_case(ctx._h, self.offsets._h, self.chars._h, kind, C.byref(oo), C.byref(oc)))
+        return ColumnString(Column(ctx, oo), Column(ctx, oc))
+
+    def lower(self) -> "ColumnString":
+        """lower, the ASCII form: 'A'..'Z' become 'a'..'z', every other byte is copied"""
+        return self._map_case(K.STR_LOWER)
+
+    def upper(self) -> "ColumnString":
+        """upper, the ASCII form: 'a'..'z' become 'A'..'Z', every other byte is copied"""
+        return self._map_case(K.STR_UPPER)
+
+    def substring(self, offset: int, length: int | None = None) -> "ColumnString":
+        """substring(s, offset[, length]) with constant arguments, in bytes: offset >= 1 counts from the front, offset <= -1 from the
+        back; the window is clipped to the value.  offset == 0 is NOT_IMPLEMENTED (the reference's answer changed between versions)."""
+        if not _is_int(offset) or not (length is None or _is_int(length)):
+            raise TypeError("substring takes an integer offset and an integer length or None")
+        offset = int(offset)
+        if not -2**63 <= offset < 2**63:
+            raise ValueError("substring: the offset is an Int64")
+        if length is not None and not 0 <= int(length) < 2**64:
+            raise ValueError("substring: the length is a UInt64 (a negative length is not supported)")
+        oo, oc = C.c_void_p(), C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(K.lib().chgpu_string_substring(ctx._h, self.offsets._h, self.chars._h, offset, 0 if length is None else 1, 0 if length is None else int(length),
+                                               C.byref(oo), C.byref(oc)))
+        return ColumnString(Column(ctx, oo), Column(ctx, oc))
+
+    def position(self, needle) -> Column:
+        """position(haystack, needle): the 1-based byte index of the first occurrence inside the value, 0 without one; a UInt64 Column.
+        The empty needle is found at 1."""
+        needle = _const_arg(needle)
+        h = C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(K.lib().chgpu_string_position_const(ctx._h, self.offsets._h, self.chars._h, needle, len(needle), C.byref(h)))
+        return Column(ctx, h)
+
+    def compare_column(self, op: int, other: "ColumnString") -> Column:
+        """equals .. greaterOrEquals (EQ .. GE) against another String column, row by row, in the order of compare(): a UInt8 Column"""
+        if not isinstance(other, ColumnString):
+            raise TypeError("compare_column takes a ColumnString")
+        if not _is_int(op):
+            raise TypeError("compare_column takes one of EQ .. GE")
+        h = C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(K.lib().chgpu_string_cmp_columns(ctx._h, self.offsets._h, self.chars._h, other.offsets._h, other.chars._h, int(op), C.byref(h)))
+        return Column(ctx, h)
+
+    @staticmethod
+    def concat(*args) -> "ColumnString":
+        """concat(a, b, ...): 2 to 8 arguments, each a ColumnString or a constant (bytes / str), at least one of them a column"""
+        consts = [None if isinstance(a, ColumnString) else _const_arg(a) for a in args]
+        arr = (K.StringArg * max(len(args), 1))()
+        ctx = None
+        for slot, a, c in zip(arr, args, consts):
+            if c is None:
+                slot.offsets, slot.chars = a.offsets._h.value, a.chars._h.value
+                ctx = ctx or a.offsets.ctx
+            else:
+                slot.value, slot.value_bytes = c, len(c)
+        if ctx is None:
+            raise ValueError("concat takes at least one ColumnString (there is no context for constants alone)")
+        oo, oc = C.c_void_p(), C.c_void_p()
+        K.check(K.lib().chgpu_string_concat(ctx._h, arr, len(args), C.byref(oo), C.byref(oc)))
+        return ColumnString(Column(ctx, oo), Column(ctx, oc))
 
     def to_list(self) -> list:
         """the values on the host (tests)"""

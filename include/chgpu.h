@@ -882,6 +882,57 @@ typedef struct chgpu_like_plan
     uint8_t tokens[CHGPU_STR_CONST_MAX];
 } chgpu_like_plan;
 int chgpu_like_compile(const void * pattern, uint64_t pattern_bytes, chgpu_like_plan * out);
+/* ---- String functions: a new column computed from a ColumnString, on the device.  The conventions of the String calls above hold for
+   all six: values are binary-safe (zero bytes and bytes >= 0x80 are ordinary bytes); lengths exclude the terminating zero; offsets that
+   break the ColumnString invariant answer CHGPU_ERR_BAD_ARGUMENTS, as do NULL arguments and wrong column types; zero rows give empty
+   columns; chars needs its 8 readable bytes after the end; a result ColumnString is an ordinary one (a zero after every value, cumulative
+   offsets, out_chars.rows == offsets.back()); a value of 4 GiB or more answers CHGPU_ERR_NOT_IMPLEMENTED; a failed call frees what it
+   allocated and leaves every *out untouched.  Every check that needs no device (NULL arguments, types, row counts, argument domains,
+   constant sizes) is made before the first device call.
+   chgpu_string_length (FunctionStringOrArrayToT over LengthImpl, LengthUTF8Impl, EmptyImpl): CHGPU_STR_LENGTH is length, the bytes, a
+     UInt64 column; CHGPU_STR_LENGTH_UTF8 is lengthUTF8, the number of bytes b with (b & 0xC0) != 0x80 -- the reference's code-point count
+     (UTF8::countCodePoints): every byte that is not a continuation byte, on valid and invalid UTF-8 alike -- a UInt64 column;
+     CHGPU_STR_EMPTY and CHGPU_STR_NOT_EMPTY give a UInt8 0/1.
+   chgpu_string_map_case (LowerUpperImpl): CHGPU_STR_LOWER is lower, CHGPU_STR_UPPER is upper, the ASCII forms: a byte in 'A'..'Z' (or
+     'a'..'z') has bit 0x20 flipped, every other byte is copied.  The offsets are copied.  Bytes of a wrapped chars buffer behind
+     offsets.back() are neither read into the result nor counted.  lowerUTF8 / upperUTF8 have no kind.
+   chgpu_string_cmp_columns (StringComparisonImpl::string_vector_string_vector): CHGPU_EQ .. CHGPU_GE row by row, in the order of
+     chgpu_string_cmp_const: unsigned bytes over the common prefix, then the shorter value is the smaller.  Different row counts answer
+     CHGPU_ERR_SIZES_MISMATCH.  a and b may be the same column.
+   chgpu_string_substring (FunctionsStringSubstring, SubstringImpl): substring(s, offset[, length]) with constant arguments, counted in
+     bytes.  The result is the value's bytes inside a window: for offset >= 1 the window begins at byte index offset - 1; for
+     offset <= -1 it begins at index size - |offset|, which may be negative; it covers `length` indexes (has_length != 0), or runs to the
+     end of the value without a length; it is clipped to [0, size).  So substring('abc', -5, 3) = 'a', substring('abc', -5) = 'abc' and
+     substring('abc', 4) = ''.  All arithmetic saturates: offset = INT64_MIN, offset - 1 + length past 2^64 and length = 2^64 - 1 are legal
+     inputs.  offset == 0 answers CHGPU_ERR_NOT_IMPLEMENTED (the reference's answer there has changed between versions, so it is left
+     out, not guessed).  A negative length, column arguments and substringUTF8 cannot be expressed.
+   chgpu_string_concat (ConcatImpl): an argument is a column when offsets != NULL, otherwise a constant of value_bytes bytes in host memory.
+     2 <= n_args <= 8 and at least one argument is a column, otherwise CHGPU_ERR_BAD_ARGUMENTS.  The constant bytes of one call together
+     are at most CHGPU_STR_CONST_MAX, otherwise CHGPU_ERR_NOT_IMPLEMENTED (one kernel argument carries them: no upload per call).  All
+     columns have the same row count, otherwise CHGPU_ERR_SIZES_MISMATCH.  The same column may appear several times.
+   chgpu_string_position_const (PositionImpl::vectorConstant, the byte form): position(haystack, needle), the 1-based byte index of the
+     first occurrence that lies wholly inside the value -- the rule of CHGPU_STR_CONTAINS: an occurrence never touches the terminating
+     zero or the next row -- and 0 when there is none; a UInt64 column.  The empty needle gives 1 for every row.  A needle longer than
+     CHGPU_STR_CONST_MAX answers CHGPU_ERR_NOT_IMPLEMENTED.  positionUTF8 and the case-insensitive forms have no entry point. */
+enum { CHGPU_STR_LENGTH = 0, CHGPU_STR_LENGTH_UTF8 = 1, CHGPU_STR_EMPTY = 2, CHGPU_STR_NOT_EMPTY = 3 };
+enum { CHGPU_STR_LOWER = 0, CHGPU_STR_UPPER = 1 };
+typedef struct chgpu_string_arg
+{
+    const chgpu_col * offsets, * chars; /* a column; offsets == NULL: a constant */
+    const void * value;                 /* the constant's bytes in host memory, no terminator */
+    uint64_t value_bytes;
+} chgpu_string_arg;
+int chgpu_string_length(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int kind, chgpu_col ** out);
+int chgpu_string_map_case(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int kind,
+                          chgpu_col ** out_offsets_u64, chgpu_col ** out_chars_u8);
+int chgpu_string_cmp_columns(chgpu_ctx * ctx, const chgpu_col * a_offsets_u64, const chgpu_col * a_chars_u8, const chgpu_col * b_offsets_u64,
+                             const chgpu_col * b_chars_u8, int op, chgpu_col ** out_u8);
+int chgpu_string_substring(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int64_t offset, int has_length,
+                           uint64_t length, chgpu_col ** out_offsets_u64, chgpu_col ** out_chars_u8);
+int chgpu_string_concat(chgpu_ctx * ctx, const chgpu_string_arg * args, uint32_t n_args, chgpu_col ** out_offsets_u64,
+                        chgpu_col ** out_chars_u8);
+int chgpu_string_position_const(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const void * needle,
+                                uint64_t needle_bytes, chgpu_col ** out_u64);
 int chgpu_agg_create(chgpu_ctx * ctx, int key_type, uint32_t n_aggs, const int * agg_kinds, const int * arg_types,
                      uint64_t size_hint, chgpu_agg ** out);
 /* executeOnBlock over rows [row_begin,row_end) of the key column and the argument columns (arg_cols[j] may be NULL
