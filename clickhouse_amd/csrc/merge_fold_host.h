@@ -1,6 +1,7 @@
 // merge_fold_host.h — the folds of the Replacing / Collapsing / Summing / Aggregating merges (merge_fold_kernels.hip) as plain C++: each
 // algorithm's state, its combine operator and what a group emits at its tail, the segmented combine that stops at a group's head, and
-// the three walks the kernels are made of (a thread's items, a workgroup's tiles, the apply with its tail counts).  Everything is
+// the three walks the kernels are made of (a thread's items, a workgroup's tiles, the apply with its tail counts), and a tile's geometry
+// (a thread's positions, the padded staging slot).  Everything is
 // __host__ __device__ under hipcc and reads its columns through plain pointers, so that tests/merge_fold_driver.cpp replays the very code
 // the kernels run, tile by tile, under a sanitizer.
 //
@@ -34,6 +35,21 @@ static constexpr uint32_t FOLD_MAX_OUT = 2;        // outputs of one group (Coll
 
 // flags of a scan element: it covers at least one position / a group's head is among them
 enum : uint8_t { FOLD_ANY = 1, FOLD_HEAD = 2 };
+
+// ---- the geometry of a tile, for every kernel behind the heads (the folds' and merge_versioned_kernels.hip's) and for the drivers ----
+// the positions of thread `thread` of tile `tile`: [p0, p1), cut at n (empty past it).  p0 is a multiple of FOLD_ITEMS wherever the
+// range is whole (p1 - p0 == FOLD_ITEMS).
+FOLD_HD void fold_thread_range(uint32_t tile, uint32_t thread, uint64_t n, uint64_t & p0, uint64_t & p1)
+{
+    p0 = (uint64_t)tile * FOLD_TILE + (uint64_t)thread * FOLD_ITEMS;
+    p1 = p0 + FOLD_ITEMS;
+    p0 = p0 < n ? p0 : n;
+    p1 = p1 < n ? p1 : n;
+}
+// Where a tile's element e waits in LDS when the states are staged (merge_fold_kernels.hip): one slot of padding per FOLD_ITEMS states,
+// so that neighbouring lanes are 9 states apart, not 8, and their 16-byte reads fall on different banks.
+static constexpr uint32_t FOLD_STAGE_SLOTS = FOLD_TILE + FOLD_TILE / FOLD_ITEMS;
+FOLD_HD uint32_t fold_stage_slot(uint32_t e) { return e + e / FOLD_ITEMS; }
 
 // ---- integer columns by their type tag ----
 FOLD_HD bool fold_type_is_int(int type)

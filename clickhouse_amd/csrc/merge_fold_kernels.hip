@@ -12,8 +12,11 @@
 //   k_fold_apply    the tile again behind its carry; a group's result is known at its TAIL, which emits 0, 1 or 2 outputs.
 //                   EMIT = false: the tile's and its threads' output counts.  EMIT = true: the outputs, compacted through LDS, stored
 //                   coalesced at the tile's offset; the folding form stores its result columns through the same offsets
-//   k_fold_offsets  one workgroup: the exclusive sum of the tile counts, and the total
-// The states, the combine operators and the walks are merge_fold_host.h's.  No atomics; nothing depends on which workgroup runs first.
+//   k_fold_offsets  one workgroup: the exclusive sum of the tile counts, the total and, where the caller has per-tile maxima
+//                   (merge_versioned_kernels.hip), their maximum
+// The states, the combine operators, the walks and a thread's positions are merge_fold_host.h's.  No atomics; nothing depends on which
+// workgroup runs first.  Host side: FoldCall (merge_keys.h) is the frame of a call -- the checks, the merged order, the heads, the
+// epilogue -- for fold_run here and for the VersionedCollapsing merge, and fold_offsets the step behind the tile counts.
 // Algorithmic bytes per row behind the merge: heads 12 + 1; tile 1 + 4 + the gathered columns; apply twice the same (+ 1 / 8 for the
 // threads' counts); outputs 8 per row number and the value widths per surviving group.
 #include "merge_fold_host.h"
@@ -85,24 +88,12 @@ __device__ __forceinline__ void fold_block_scan(const A & a, typename A::State &
     }
 }
 
-// the positions of thread t of tile `tile`: [p0, p1), empty past n
-__device__ __forceinline__ void fold_thread_range(u32 n, u64 & p0, u64 & p1)
-{
-    p0 = (u64)blockIdx.x * FOLD_TILE + (u64)threadIdx.x * FOLD_ITEMS;
-    p1 = p0 + FOLD_ITEMS;
-    p0 = p0 < n ? p0 : n;
-    p1 = p1 < n ? p1 : n;
-}
-
 // A tile's states are loaded ONCE in the order the positions lie -- a wave's lanes read consecutive positions, so the row numbers are
 // read coalesced and the gathers through them walk the K runs as K dense streams -- and wait in LDS for the threads, each of which then
-// folds FOLD_ITEMS consecutive positions (one slot of padding per FOLD_ITEMS states: neighbouring lanes are 9 states apart, not 8, and
-// their 16-byte reads fall on different banks).  States wider than FOLD_STAGE_BYTES would not fit beside the scan and the output stage:
+// folds FOLD_ITEMS consecutive positions (in padded slots: fold_stage_slot of merge_fold_host.h).  States wider than FOLD_STAGE_BYTES would not fit beside the scan and the output stage:
 // those algorithms read every position where it lies.  So does Collapsing: its argument is one byte a row, the runs' sign bytes of a
 // tile are a few cache lines, and staging its 16-byte state measured slower than reading them in place.
 static constexpr u32 FOLD_STAGE_BYTES = 16;
-static constexpr u32 FOLD_STAGE_SLOTS = FOLD_TILE + FOLD_TILE / FOLD_ITEMS;
-__device__ __forceinline__ u32 fold_stage_slot(u32 e) { return e + e / FOLD_ITEMS; }
 template <class A>
 struct FoldStages
 {
@@ -155,7 +146,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_fold_tile(A a, const u8 * __re
     __shared__ typename A::State lstage[FoldTileSrc<A>::STAGED ? FOLD_STAGE_SLOTS : 1];
     const FoldTileSrc<A> src = fold_tile_src(a, heads, rows, n, lstage);
     u64 p0, p1;
-    fold_thread_range(n, p0, p1);
+    fold_thread_range(blockIdx.x, threadIdx.x, n, p0, p1);
     typename A::State s = {};
     u8 fl = 0;
     fold_aggregate(a, src, p0, p1, s, fl);
@@ -225,7 +216,7 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_fold_apply(A a, const u8 * __r
     __shared__ typename A::State lstage[FoldTileSrc<A>::STAGED ? FOLD_STAGE_SLOTS : 1];
     const FoldTileSrc<A> src = fold_tile_src(a, heads, rows, n, lstage);
     u64 p0, p1;
-    fold_thread_range(n, p0, p1);
+    fold_thread_range(blockIdx.x, threadIdx.x, n, p0, p1);
     typename A::State s = {};
     u8 fl = 0;
     fold_aggregate(a, src, p0, p1, s, fl);
@@ -272,37 +263,43 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_fold_apply(A a, const u8 * __r
                 for (u32 j = 0; j < c; ++j)
                     stage0[at++] = o[j];
         });
-        __syncthreads();
-        for (u32 e = threadIdx.x; e < total; e += FOLD_THREADS)
-        {
-            out0[base + e] = stage0[e];
-            if constexpr (A::PAIRED)
-                out1[base + e] = stage1[e];
-        }
+        fold_store_staged(stage0, total, out0, base, true);
+        if constexpr (A::PAIRED)
+            fold_store_staged(stage1, total, out1, base, false);
     }
 }
 
-// off[t] = counts[0] + .. + counts[t - 1]; off[n_tiles] = the total
+// off[t] = counts[0] + .. + counts[t - 1]; off[n_tiles] = the total; with tile_max, off[n_tiles + 1] = the greatest of tile_max
 // (FOLD_THREADS tile counts a pass: the launch is the one it was)
-__global__ __launch_bounds__(FOLD_THREADS) void k_fold_offsets(const u32 * __restrict__ counts, u32 n_tiles, u64 * __restrict__ off)
+__global__ __launch_bounds__(FOLD_THREADS) void k_fold_offsets(const u32 * __restrict__ counts, const u64 * __restrict__ tile_max /* NULL: none */, u32 n_tiles,
+                                                               u64 * __restrict__ off)
 {
+    __shared__ u64 lmax[FOLD_THREADS / WAVE];
     const u64 total = block_scan_array<AddU64, false>(counts, off, n_tiles, 0);
     if (threadIdx.x == 0)
         off[n_tiles] = total;
+    if (tile_max)
+    {
+        u64 m = 0;
+        for (u32 t = threadIdx.x; t < n_tiles; t += FOLD_THREADS)
+            m = tile_max[t] > m ? tile_max[t] : m;
+        m = block_reduce<MaxU64>(m, lmax);
+        if (threadIdx.x == 0)
+            off[n_tiles + 1] = m;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// (fold_validate, fold_check_column, fold_require_domain and fold_heads are declared in merge_keys.h: merge_versioned_kernels.hip takes them)
+// (fold_validate, fold_check_column, FoldCall and fold_offsets are declared in merge_keys.h: merge_versioned_kernels.hip takes them)
 // the shared argument prefix, in front of the device
 int fold_validate(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint, u32 n_keys,
                   const uint64_t * run_offsets, u32 n_runs, u32 flags, FoldPrefix * px)
 {
     CHGPU_TRY(merge_validate(ctx, key_cols, descending, nan_direction_hint, n_keys, run_offsets, n_runs, &px->keys, &px->rows));
     CHGPU_REQUIRE(n_runs >= 1, CHGPU_ERR_BAD_ARGUMENTS, "no runs: a folding merge takes at least one");
-    CHGPU_REQUIRE(!(flags & ~(u32)CHGPU_MERGE_CHECK_SORTED), CHGPU_ERR_BAD_ARGUMENTS, "unknown flag bits 0x%x", flags & ~(u32)CHGPU_MERGE_CHECK_SORTED);
-    return CHGPU_OK;
+    return merge_check_flags(flags);
 }
 
 int fold_check_column(const chgpu_col * c, const char * what, int want_type, const char * type_name, u64 rows)
@@ -313,37 +310,68 @@ int fold_check_column(const chgpu_col * c, const char * what, int want_type, con
     return CHGPU_OK;
 }
 
-// BAD_ARGUMENTS naming the lowest concatenated row whose value is outside the column's domain
-int fold_require_domain(chgpu_ctx * ctx, PairTemps & tmp, const chgpu_col * c, int mode, u64 rows)
+// BAD_ARGUMENTS naming the lowest concatenated row whose value is outside the column's domain (mode 0: Int8 sign, 1: UInt8 is_deleted)
+static int fold_require_domain(chgpu_ctx * ctx, PairTemps & tmp, const chgpu_col * c, int mode, u64 rows)
 {
     const u32 tiles = merge_tiles((u32)rows);
-    void * partial = nullptr;
-    CHGPU_TRY(tmp.alloc(((size_t)tiles + 1) * sizeof(u64), &partial));
-    hipLaunchKernelGGL(k_fold_bad, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, (const u8 *)c->data, mode, (u32)rows, (u64 *)partial);
-    ctx->counters[6] += 1;
-    merge_lowest(ctx, (const u64 *)partial, tiles, (u64 *)partial + tiles);
     u64 bad = ~0ull;
-    CHGPU_TRY(chgpu_read_back(ctx, (const u64 *)partial + tiles, &bad, sizeof(u64)));
+    CHGPU_TRY(merge_lowest_row(ctx, tmp, tiles, [&](u64 * partial) {
+        hipLaunchKernelGGL(k_fold_bad, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, (const u8 *)c->data, mode, (u32)rows, partial);
+    }, &bad));
     if (mode == 0)
         CHGPU_REQUIRE(bad == ~0ull, CHGPU_ERR_BAD_ARGUMENTS, "the sign of row %llu is neither 1 nor -1", (unsigned long long)bad);
     CHGPU_REQUIRE(bad == ~0ull, CHGPU_ERR_BAD_ARGUMENTS, "is_deleted of row %llu is neither 0 nor 1", (unsigned long long)bad);
     return CHGPU_OK;
 }
 
-void fold_heads(chgpu_ctx * ctx, const MergeKeys & keys, const u64 * words, const u32 * rows, u32 n, u8 * heads)
+int FoldCall::open(const chgpu_col * const * key_cols, const FoldPrefix & px, const uint64_t * run_offsets, u32 n_runs, u32 flags, const chgpu_col * const * domain,
+                   const int * domain_mode, u32 n_domain)
 {
-    hipLaunchKernelGGL(k_fold_heads, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, keys, words, rows, n, heads);
+    chgpu_ctx * ctx = mem.ctx;
+    const u64 n = px.rows;
+    tiles = merge_tiles((u32)n);
+    if (!n)
+        return CHGPU_OK;
+    if ((flags & CHGPU_MERGE_CHECK_SORTED) && n >= 2)
+        CHGPU_TRY(merge_require_sorted(ctx, px.keys, run_offsets, n_runs, n));
+    for (u32 i = 0; i < n_domain; ++i)
+        CHGPU_TRY(fold_require_domain(ctx, tmp, domain[i], domain_mode[i], n));
+    CHGPU_TRY(merge_order(ctx, key_cols, px.keys, run_offsets, n_runs, n, tmp, &words, &rows));
+    void * h = nullptr;
+    CHGPU_TRY(tmp.alloc(n, &h));
+    heads = (u8 *)h;
+    hipLaunchKernelGGL(k_fold_heads, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, px.keys, words, rows, (u32)n, heads);
     ctx->counters[6] += 1;
+    return CHGPU_OK;
 }
 
-static void fold_free_cols(chgpu_col ** cols, u32 n)
+int FoldCall::close(int rc, chgpu_col ** outs, u32 n_outs)
 {
-    for (u32 i = 0; i < n; ++i)
-        if (cols[i])
-        {
-            chgpu_col_free(cols[i]);
-            cols[i] = nullptr;
-        }
+    if (rc == CHGPU_OK)
+    {
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess)
+            rc = chgpu_set_error(CHGPU_ERR_DEVICE, "%s: %s", mem.op, hipGetErrorString(e));
+    }
+    if (rc != CHGPU_OK)
+        for (u32 i = 0; i < n_outs; ++i)
+            if (outs[i])
+            {
+                chgpu_col_free(outs[i]);
+                outs[i] = nullptr;
+            }
+    return rc;
+}
+
+int fold_offsets(chgpu_ctx * ctx, PairTemps & tmp, const u32 * counts, const u64 * tile_max, u32 tiles, const u64 ** tile_off, u64 * result)
+{
+    const u32 n_results = tile_max ? 2 : 1;
+    void * off = nullptr;
+    CHGPU_TRY(tmp.alloc(((size_t)tiles + n_results) * sizeof(u64), &off));
+    hipLaunchKernelGGL(k_fold_offsets, dim3(1), dim3(FOLD_THREADS), 0, ctx->stream, counts, tile_max, tiles, (u64 *)off);
+    ctx->counters[6] += 1;
+    *tile_off = (const u64 *)off;
+    return chgpu_read_back(ctx, *tile_off + tiles, result, n_results * sizeof(u64));
 }
 
 // Everything behind the validation.  domain[0..n_domain): the columns to check with their modes.  outs: the row-number columns (one, or
@@ -358,40 +386,27 @@ static int fold_run(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const F
         n_outs += a.d.n;
     for (u32 i = 0; i < n_outs; ++i)
         outs[i] = nullptr;
-    PairAllocs mem;
-    mem.ctx = ctx, mem.op = "merge_fold";
-    mem.begin_call();
-    PairTemps tmp(mem);
-    const u64 rows = px.rows;
+    FoldCall call(ctx, "merge_fold");
+    const u32 n = (u32)px.rows;
     u64 total = 0;
-    const u64 * words = nullptr, * tile_off = nullptr;
-    const u32 * rws = nullptr;
-    void * heads = nullptr, * carry = nullptr, * thread_counts = nullptr;
-    const u32 tiles = merge_tiles((u32)rows);
-    if (rows)
+    const u64 * tile_off = nullptr;
+    void * carry = nullptr, * thread_counts = nullptr;
+    CHGPU_TRY(call.open(key_cols, px, run_offsets, n_runs, flags, domain, domain_mode, n_domain));
+    const u32 tiles = call.tiles;
+    if (n)
     {
-        if ((flags & CHGPU_MERGE_CHECK_SORTED) && rows >= 2)
-            CHGPU_TRY(merge_require_sorted(ctx, px.keys, run_offsets, n_runs, rows));
-        for (u32 i = 0; i < n_domain; ++i)
-            CHGPU_TRY(fold_require_domain(ctx, tmp, domain[i], domain_mode[i], rows));
-        CHGPU_TRY(merge_order(ctx, key_cols, px.keys, run_offsets, n_runs, rows, tmp, &words, &rws));
-        void * agg_s = nullptr, * agg_f = nullptr, * counts = nullptr, * off = nullptr;
-        CHGPU_TRY(tmp.alloc((size_t)tiles * FOLD_THREADS, &thread_counts));
-        CHGPU_TRY(tmp.alloc(rows, &heads));
-        CHGPU_TRY(tmp.alloc((size_t)tiles * sizeof(State), &agg_s));
-        CHGPU_TRY(tmp.alloc(tiles, &agg_f));
-        CHGPU_TRY(tmp.alloc((size_t)tiles * sizeof(State), &carry));
-        CHGPU_TRY(tmp.alloc((size_t)tiles * sizeof(u32), &counts));
-        CHGPU_TRY(tmp.alloc(((size_t)tiles + 1) * sizeof(u64), &off));
-        fold_heads(ctx, px.keys, words, rws, (u32)rows, (u8 *)heads);
-        hipLaunchKernelGGL(k_fold_tile<A>, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, a, (const u8 *)heads, rws, (u32)rows, (State *)agg_s, (u8 *)agg_f);
+        void * agg_s = nullptr, * agg_f = nullptr, * counts = nullptr;
+        CHGPU_TRY(call.tmp.alloc((size_t)tiles * FOLD_THREADS, &thread_counts));
+        CHGPU_TRY(call.tmp.alloc((size_t)tiles * sizeof(State), &agg_s));
+        CHGPU_TRY(call.tmp.alloc(tiles, &agg_f));
+        CHGPU_TRY(call.tmp.alloc((size_t)tiles * sizeof(State), &carry));
+        CHGPU_TRY(call.tmp.alloc((size_t)tiles * sizeof(u32), &counts));
+        hipLaunchKernelGGL(k_fold_tile<A>, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, a, (const u8 *)call.heads, call.rows, n, (State *)agg_s, (u8 *)agg_f);
         hipLaunchKernelGGL(k_fold_carry<A>, dim3(1), dim3(FOLD_THREADS), 0, ctx->stream, a, (const State *)agg_s, (const u8 *)agg_f, tiles, (State *)carry);
-        hipLaunchKernelGGL((k_fold_apply<A, false>), dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, a, (const u8 *)heads, rws, (u32)rows, (const State *)carry,
+        hipLaunchKernelGGL((k_fold_apply<A, false>), dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, a, (const u8 *)call.heads, call.rows, n, (const State *)carry,
                            (u32 *)counts, (u8 *)thread_counts, (const u64 *)nullptr, (u64 *)nullptr, (u64 *)nullptr);
-        hipLaunchKernelGGL(k_fold_offsets, dim3(1), dim3(FOLD_THREADS), 0, ctx->stream, (const u32 *)counts, tiles, (u64 *)off);
-        ctx->counters[6] += 4;
-        tile_off = (const u64 *)off;
-        CHGPU_TRY(chgpu_read_back(ctx, tile_off + tiles, &total, sizeof(u64)));
+        ctx->counters[6] += 3;
+        CHGPU_TRY(fold_offsets(ctx, call.tmp, (const u32 *)counts, nullptr, tiles, &tile_off, &total));
     }
     int rc = CHGPU_OK;
     for (u32 i = 0; i < n_outs && rc == CHGPU_OK; ++i)
@@ -407,19 +422,11 @@ static int fold_run(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const F
         if constexpr (A::PAIRED)
             for (u32 k = 0; k < a.d.n; ++k)
                 a.d.out[k] = outs[2 + k]->data;
-        hipLaunchKernelGGL((k_fold_apply<A, true>), dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, a, (const u8 *)heads, rws, (u32)rows, (const State *)carry,
+        hipLaunchKernelGGL((k_fold_apply<A, true>), dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, a, (const u8 *)call.heads, call.rows, n, (const State *)carry,
                            (u32 *)nullptr, (u8 *)thread_counts, tile_off, (u64 *)outs[0]->data, A::PAIRED ? (u64 *)outs[1]->data : (u64 *)nullptr);
         ctx->counters[6] += 1;
     }
-    if (rc == CHGPU_OK)
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            rc = chgpu_set_error(CHGPU_ERR_DEVICE, "merge_fold: %s", hipGetErrorString(e));
-    }
-    if (rc != CHGPU_OK)
-        fold_free_cols(outs, n_outs);
-    return rc;
+    return call.close(rc, outs, n_outs);
 }
 
 extern "C" int chgpu_merge_replacing(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const int32_t * descending, const int32_t * nan_direction_hint,

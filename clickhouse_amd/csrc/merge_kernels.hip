@@ -4,18 +4,21 @@
 // PartialSortingTransform sorted and MergingSortedTransform with the streams; and isAlreadySorted (src/Interpreters/sortBlock.cpp).
 // The key columns are the runs glued end to end; the result is the permutation of concatenated row numbers, bit-equal to what the
 // stable sort of the concatenation gives (sort_kernels.hip), because both compare the SortKey words of sort_key.h.
-//   k_merge_keys       first key column -> (order-preserving u64 word, u32 row number), every run cut to the limit
+//   k_merge_pairs      first key column -> (order-preserving u64 word, u32 row number) for the source row of every entry, ONE kernel
+//                      over where that row comes from: the runs cut to the limit (MergeCutRows), a merged order known as a permutation
+//                      (MergePermRows: what merge_order hands the folding merges where the plan is the sort chain) or the identity
 //   k_merge_split      per round, ONE launch: for every tile edge of every pair, the merge-path crossing of its diagonal (binary search
 //                      over the pair's two runs in HBM)
 //   k_merge_tiles      per round, ONE launch: a workgroup stages its tile's two input pieces in LDS, every thread finds its own diagonal
 //                      there and merges MRG_ITEMS consecutive outputs, the tile goes out coalesced
 //   k_merge_perm       the last round's row numbers widened to the UInt64 permutation
-//   k_merge_pairs_of   the (word, row) pairs of a merged order known as a permutation: what merge_order (merge_keys.h) hands the folding
-//                      merges where the plan is the sort chain, or there is one run
 //   k_merge_is_sorted  adjacent rows compared under the same order, never across a run boundary; per-tile minimum of the violating row
 //   k_merge_min        one workgroup folds the tile minima: the LOWEST violating row, the same in every run
 // The comparator reads the words first; on equal words (and n_keys > 1) the remaining columns through the row numbers; all equal: the
 // left run's element first (merge_host.h keeps the invariant).  No atomics anywhere.
+// Host side, each written once: merge_pairs launches the pair build for the tree and for merge_order, merge_plan_of
+// holds the plan's choice, merge_new_perm the UInt64 permutation, merge_lowest_row the "lowest offending row" of a check (also the
+// folds' domain check), merge_check_flags the flag check.
 // Algorithmic bytes per row: key build sizeof(T) + 12; a round 2 x 12; the permutation 4 + 8.  is_sorted: the key columns once.
 #include "merge_keys.h"
 
@@ -33,27 +36,42 @@ __device__ __forceinline__ bool mrg_before(const MergeKeys & keys, u64 wb, u32 r
     return false;
 }
 
-// cut_off[n_runs + 1]: where each (cut) run starts in the arrays; src_off[n_runs]: its first row in the columns.  n_runs == 0: nothing
-// was cut, entry i is row i.
-__global__ __launch_bounds__(256) void k_merge_keys(MergeKeys keys, const u32 * __restrict__ cut_off, const u32 * __restrict__ src_off, u32 n_runs, u32 n,
-                                                    u64 * __restrict__ words, u32 * __restrict__ rows)
+// The source row of entry i of the pair arrays, three ways.
+// cut_off[n_runs + 1]: where each (cut) run starts in the arrays; src_off[n_runs]: its first row in the columns
+struct MergeCutRows
+{
+    const u32 * __restrict__ cut_off, * __restrict__ src_off;
+    u32 n_runs;
+    __device__ __forceinline__ u32 operator()(u32 i) const
+    {
+        u32 lo = 0, hi = n_runs; // cut_off[lo] <= i < cut_off[hi]
+        while (hi - lo > 1)
+        {
+            const u32 mid = lo + (hi - lo) / 2;
+            if (cut_off[mid] <= i)
+                lo = mid;
+            else
+                hi = mid;
+        }
+        return src_off[lo] + (i - cut_off[lo]);
+    }
+};
+struct MergePermRows
+{
+    const u64 * __restrict__ perm;
+    __device__ __forceinline__ u32 operator()(u32 i) const { return (u32)perm[i]; }
+};
+struct MergeIdentityRows
+{
+    __device__ __forceinline__ u32 operator()(u32 i) const { return i; }
+};
+
+template <class Source>
+__global__ __launch_bounds__(256) void k_merge_pairs(MergeKeys keys, Source source, u32 n, u64 * __restrict__ words, u32 * __restrict__ rows)
 {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
     {
-        u32 src = (u32)i;
-        if (n_runs)
-        {
-            u32 lo = 0, hi = n_runs; // cut_off[lo] <= i < cut_off[hi]
-            while (hi - lo > 1)
-            {
-                const u32 mid = lo + (hi - lo) / 2;
-                if (cut_off[mid] <= (u32)i)
-                    lo = mid;
-                else
-                    hi = mid;
-            }
-            src = src_off[lo] + ((u32)i - cut_off[lo]);
-        }
+        const u32 src = source((u32)i);
         words[i] = mrg_key(keys, 0, src);
         rows[i] = src;
     }
@@ -133,17 +151,6 @@ __global__ __launch_bounds__(MRG_THREADS) void k_merge_tiles(MergeKeys keys, con
     {
         words_out[out + e] = sw[e];
         rows_out[out + e] = sr[e];
-    }
-}
-
-// the (word, row) pairs of a merged order that is known as a permutation (perm == NULL: the identity), for merge_order
-__global__ __launch_bounds__(256) void k_merge_pairs_of(MergeKeys keys, const u64 * __restrict__ perm, u32 n, u64 * __restrict__ words, u32 * __restrict__ rows)
-{
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
-    {
-        const u32 src = perm ? (u32)perm[i] : (u32)i;
-        words[i] = mrg_key(keys, 0, src);
-        rows[i] = src;
     }
 }
 
@@ -247,10 +254,27 @@ static int merge_upload(chgpu_ctx * ctx, PairTemps & tmp, const void * host, siz
     return CHGPU_OK;
 }
 
-void merge_lowest(chgpu_ctx * ctx, const u64 * partial, u32 n, u64 * out)
+int merge_check_flags(u32 flags)
+{
+    CHGPU_REQUIRE(!(flags & ~(u32)CHGPU_MERGE_CHECK_SORTED), CHGPU_ERR_BAD_ARGUMENTS, "unknown flag bits 0x%x", flags & ~(u32)CHGPU_MERGE_CHECK_SORTED);
+    return CHGPU_OK;
+}
+
+// partial[n] -> out[0] = the minimum, by one workgroup: one launch, counted
+static void merge_lowest(chgpu_ctx * ctx, const u64 * partial, u32 n, u64 * out)
 {
     hipLaunchKernelGGL(k_merge_min, dim3(1), dim3(MRG_THREADS), 0, ctx->stream, partial, n, out);
     ctx->counters[6] += 1;
+}
+
+int merge_lowest_row(chgpu_ctx * ctx, PairTemps & tmp, u32 tiles, const std::function<void(u64 * partial)> & launch_tiles, u64 * lowest)
+{
+    void * partial = nullptr;
+    CHGPU_TRY(tmp.alloc(((size_t)tiles + 1) * sizeof(u64), &partial));
+    launch_tiles((u64 *)partial);
+    ctx->counters[6] += 1;
+    merge_lowest(ctx, (const u64 *)partial, tiles, (u64 *)partial + tiles);
+    return chgpu_read_back(ctx, (const u64 *)partial + tiles, lowest, sizeof(u64));
 }
 
 // *first_unsorted_row: ~0, or the lowest row that orders before its predecessor inside one run.  rows >= 1.
@@ -263,14 +287,12 @@ static int merge_is_sorted(chgpu_ctx * ctx, const MergeKeys & keys, const uint64
     std::vector<u32> off(n_runs + 1);
     for (u32 r = 0; r <= n_runs; ++r)
         off[r] = (u32)run_offsets[r];
-    void * off_dev = nullptr, * partial = nullptr;
+    void * off_dev = nullptr;
     CHGPU_TRY(merge_upload(ctx, tmp, off.data(), off.size() * sizeof(u32), &off_dev));
     const u32 tiles = merge_tiles((u32)rows);
-    CHGPU_TRY(tmp.alloc(((size_t)tiles + 1) * sizeof(u64), &partial));
-    hipLaunchKernelGGL(k_merge_is_sorted, dim3(tiles), dim3(MRG_THREADS), 0, ctx->stream, keys, (const u32 *)off_dev, n_runs, (u32)rows, (u64 *)partial);
-    ctx->counters[6] += 1;
-    merge_lowest(ctx, (const u64 *)partial, tiles, (u64 *)partial + tiles);
-    return chgpu_read_back(ctx, (const u64 *)partial + tiles, first_unsorted_row, sizeof(u64));
+    return merge_lowest_row(ctx, tmp, tiles, [&](u64 * partial) {
+        hipLaunchKernelGGL(k_merge_is_sorted, dim3(tiles), dim3(MRG_THREADS), 0, ctx->stream, keys, (const u32 *)off_dev, n_runs, (u32)rows, partial);
+    }, first_unsorted_row);
 }
 
 int merge_require_sorted(chgpu_ctx * ctx, const MergeKeys & keys, const uint64_t * run_offsets, u32 n_runs, u64 rows)
@@ -294,6 +316,47 @@ extern "C" int chgpu_is_sorted(chgpu_ctx * ctx, const chgpu_col * const * key_co
     if (rows < 2)
         return CHGPU_OK;
     return merge_is_sorted(ctx, keys, run_offsets, n_runs, rows, first_unsorted_row);
+}
+
+// The (word, row) pairs of n entries into `tmp`, one launch, counted.  The source rows: the runs cut by `cut_map` (cut_off[n_runs + 1]
+// followed by src_off[n_runs]), else the permutation `perm`, else (both NULL) the identity.
+static int merge_pairs(chgpu_ctx * ctx, PairTemps & tmp, const MergeKeys & keys, u64 n, const u32 * cut_map, u32 n_runs, const u64 * perm, void ** words, void ** rows)
+{
+    CHGPU_TRY(tmp.alloc(n * sizeof(u64), words));
+    CHGPU_TRY(tmp.alloc(n * sizeof(u32), rows));
+    const dim3 grid(chgpu_grid_for(ctx, n, 256, 8));
+    if (cut_map)
+        hipLaunchKernelGGL(k_merge_pairs<MergeCutRows>, grid, dim3(256), 0, ctx->stream, keys, MergeCutRows{cut_map, cut_map + n_runs + 1, n_runs}, (u32)n, (u64 *)*words,
+                           (u32 *)*rows);
+    else if (perm)
+        hipLaunchKernelGGL(k_merge_pairs<MergePermRows>, grid, dim3(256), 0, ctx->stream, keys, MergePermRows{perm}, (u32)n, (u64 *)*words, (u32 *)*rows);
+    else
+        hipLaunchKernelGGL(k_merge_pairs<MergeIdentityRows>, grid, dim3(256), 0, ctx->stream, keys, MergeIdentityRows{}, (u32)n, (u64 *)*words, (u32 *)*rows);
+    ctx->counters[6] += 1;
+    return CHGPU_OK;
+}
+
+// merge_plan's choice for these keys
+static int merge_plan_of(const MergeKeys & keys, u64 rows, u64 cut_rows, u32 n_runs)
+{
+    u32 key_sizes[MRG_MAX_KEYS];
+    for (u32 j = 0; j < keys.n; ++j)
+        key_sizes[j] = (u32)chgpu_type_size(keys.type[j]);
+    return merge_plan(key_sizes, keys.n, rows, cut_rows, n_runs);
+}
+
+// *perm_out: a new UInt64 column of n_out rows, rows[0 .. n_out) widened (rows == NULL: the identity); the launch is counted
+static int merge_new_perm(chgpu_ctx * ctx, const u32 * rows, u64 n_out, chgpu_col ** perm_out)
+{
+    chgpu_col * perm = nullptr;
+    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, n_out, &perm));
+    if (n_out)
+    {
+        hipLaunchKernelGGL(k_merge_perm, dim3(chgpu_grid_for(ctx, n_out, 256, 8)), dim3(256), 0, ctx->stream, rows, n_out, (u64 *)perm->data);
+        ctx->counters[6] += 1;
+    }
+    *perm_out = perm;
+    return CHGPU_OK;
 }
 
 // the merge tree over runs cut to `lens`: the last round's (word, row) arrays, in `tmp`
@@ -326,15 +389,9 @@ static int merge_tree_pairs(chgpu_ctx * ctx, PairTemps & tmp, const MergeKeys & 
     CHGPU_TRY(merge_upload(ctx, tmp, map.data(), map.size() * sizeof(u32), &map_dev));
     CHGPU_TRY(merge_upload(ctx, tmp, pairs.data(), pairs.size() * sizeof(MergePair), &pairs_dev));
     CHGPU_TRY(tmp.alloc((size_t)max_splits * sizeof(u32), &splits));
-    for (int b = 0; b < 2; ++b)
-    {
-        CHGPU_TRY(tmp.alloc(cut_rows * sizeof(u64), &words[b]));
-        CHGPU_TRY(tmp.alloc(cut_rows * sizeof(u32), &rws[b]));
-    }
-    const u32 n_map = map.empty() ? 0 : n_runs;
-    hipLaunchKernelGGL(k_merge_keys, dim3(chgpu_grid_for(ctx, cut_rows, 256, 8)), dim3(256), 0, ctx->stream, keys, (const u32 *)map_dev,
-                       (const u32 *)map_dev + n_runs + 1, n_map, (u32)cut_rows, (u64 *)words[0], (u32 *)rws[0]);
-    ctx->counters[6] += 1;
+    CHGPU_TRY(tmp.alloc(cut_rows * sizeof(u64), &words[1]));
+    CHGPU_TRY(tmp.alloc(cut_rows * sizeof(u32), &rws[1]));
+    CHGPU_TRY(merge_pairs(ctx, tmp, keys, cut_rows, map.empty() ? nullptr : (const u32 *)map_dev, n_runs, nullptr, &words[0], &rws[0]));
     int cur = 0;
     const MergePair * round_pairs = (const MergePair *)pairs_dev;
     for (const MergeRound & rd : rounds)
@@ -368,9 +425,7 @@ static int merge_tree(chgpu_ctx * ctx, const MergeKeys & keys, const uint64_t * 
     const u32 * rws = nullptr;
     CHGPU_TRY(merge_tree_pairs(ctx, tmp, keys, run_offsets, n_runs, rows, lens, cut_rows, limit, &words, &rws));
     chgpu_col * perm = nullptr;
-    CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, n_out, &perm));
-    hipLaunchKernelGGL(k_merge_perm, dim3(chgpu_grid_for(ctx, n_out, 256, 8)), dim3(256), 0, ctx->stream, rws, n_out, (u64 *)perm->data);
-    ctx->counters[6] += 1;
+    CHGPU_TRY(merge_new_perm(ctx, rws, n_out, &perm));
     hipError_t e = hipGetLastError();
     if (e != hipSuccess)
     {
@@ -403,10 +458,7 @@ static int merge_by_sort(chgpu_ctx * ctx, const chgpu_col * const * key_cols, co
 int merge_order(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const MergeKeys & keys, const uint64_t * run_offsets, u32 n_runs, u64 rows, PairTemps & tmp,
                 const u64 ** words, const u32 ** row_numbers)
 {
-    u32 key_sizes[MRG_MAX_KEYS];
-    for (u32 j = 0; j < keys.n; ++j)
-        key_sizes[j] = (u32)chgpu_type_size(keys.type[j]);
-    if (n_runs > 1 && merge_plan(key_sizes, keys.n, rows, rows, n_runs) == MERGE_PLAN_TREE)
+    if (n_runs > 1 && merge_plan_of(keys, rows, rows, n_runs) == MERGE_PLAN_TREE)
         return merge_tree_pairs(ctx, tmp, keys, run_offsets, n_runs, rows, merge_initial_runs(run_offsets, n_runs, 0), rows, 0, words, row_numbers);
     // one run: M is the identity; the sort chain: M is its permutation.  The pairs are built from it.
     chgpu_col * perm = nullptr;
@@ -416,11 +468,7 @@ int merge_order(chgpu_ctx * ctx, const chgpu_col * const * key_cols, const Merge
         tmp.cols.push_back(perm);
     }
     void * w = nullptr, * r = nullptr;
-    CHGPU_TRY(tmp.alloc(rows * sizeof(u64), &w));
-    CHGPU_TRY(tmp.alloc(rows * sizeof(u32), &r));
-    hipLaunchKernelGGL(k_merge_pairs_of, dim3(chgpu_grid_for(ctx, rows, 256, 8)), dim3(256), 0, ctx->stream, keys, perm ? (const u64 *)perm->data : (const u64 *)nullptr,
-                       (u32)rows, (u64 *)w, (u32 *)r);
-    ctx->counters[6] += 1;
+    CHGPU_TRY(merge_pairs(ctx, tmp, keys, rows, nullptr, 0, perm ? (const u64 *)perm->data : nullptr, &w, &r));
     *words = (const u64 *)w;
     *row_numbers = (const u32 *)r;
     return CHGPU_OK;
@@ -434,31 +482,17 @@ extern "C" int chgpu_merge_sorted_permutation(chgpu_ctx * ctx, const chgpu_col *
     MergeKeys keys;
     u64 rows = 0;
     CHGPU_TRY(merge_validate(ctx, key_cols, descending, nan_direction_hint, n_keys, run_offsets, n_runs, &keys, &rows));
-    CHGPU_REQUIRE(!(flags & ~(u32)CHGPU_MERGE_CHECK_SORTED), CHGPU_ERR_BAD_ARGUMENTS, "unknown flag bits 0x%x", flags & ~(u32)CHGPU_MERGE_CHECK_SORTED);
+    CHGPU_TRY(merge_check_flags(flags));
     if ((flags & CHGPU_MERGE_CHECK_SORTED) && rows >= 2)
         CHGPU_TRY(merge_require_sorted(ctx, keys, run_offsets, n_runs, rows));
     const u64 n_out = merge_cut(rows, limit);
     if (n_out == 0 || n_runs == 1)
-    {
-        // nothing to merge: empty, or the identity cut to the limit
-        chgpu_col * perm = nullptr;
-        CHGPU_TRY(chgpu_col_new(ctx, CHGPU_U64, n_out, &perm));
-        if (n_out)
-        {
-            hipLaunchKernelGGL(k_merge_perm, dim3(chgpu_grid_for(ctx, n_out, 256, 8)), dim3(256), 0, ctx->stream, (const u32 *)nullptr, n_out, (u64 *)perm->data);
-            ctx->counters[6] += 1;
-        }
-        *perm_out_u64 = perm;
-        return CHGPU_OK;
-    }
+        return merge_new_perm(ctx, nullptr, n_out, perm_out_u64); // nothing to merge: empty, or the identity cut to the limit
     const std::vector<u32> lens = merge_initial_runs(run_offsets, n_runs, limit);
     u64 cut_rows = 0;
-    u32 key_sizes[MRG_MAX_KEYS];
     for (u32 len : lens)
         cut_rows += len;
-    for (u32 j = 0; j < n_keys; ++j)
-        key_sizes[j] = (u32)chgpu_type_size(keys.type[j]);
-    if (merge_plan(key_sizes, n_keys, rows, cut_rows, n_runs) == MERGE_PLAN_SORT)
+    if (merge_plan_of(keys, rows, cut_rows, n_runs) == MERGE_PLAN_SORT)
         return merge_by_sort(ctx, key_cols, keys, n_out, perm_out_u64);
     return merge_tree(ctx, keys, run_offsets, n_runs, rows, lens, cut_rows, limit, n_out, perm_out_u64);
 }

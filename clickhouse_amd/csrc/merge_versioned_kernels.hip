@@ -1,7 +1,8 @@
 // merge_versioned_kernels.hip — the merge of VersionedCollapsingMergeTree (src/Processors/Merges/Algorithms/VersionedCollapsingAlgorithm.cpp):
 // within a group of equal sort columns, the version included, a row of one sign cancels the nearest unmatched earlier row of the other, and
 // every unmatched row survives -- any number of rows of a group, each living or dying on its own.  In front of it everything is the folding
-// merges': the merged order M as (key word, row) pairs (merge_kernels.hip), the sign check, the group heads (merge_fold_kernels.hip).
+// merges', through their call frame (FoldCall of merge_keys.h): the merged order M as (key word, row) pairs (merge_kernels.hip), the sign
+// check, the group heads (merge_fold_kernels.hip); so are the offsets step behind the tile counts and the tail of the emit.
 // Behind the heads, over the tiles of FOLD_TILE positions, a thread owning FOLD_ITEMS consecutive ones:
 //   k_vc_tile     the signs of the tile's rows gathered ONCE in position order (a wave's lanes read consecutive row numbers, and a ballot
 //                 turns their signs into 64 bits in LDS), kept as one bit a position for the pass below; the tile as one element of the
@@ -11,7 +12,7 @@
 //                 every tile, VcAfter of those behind it
 //   k_vc_decide   the tile again between its two carries: every position's balance and what follows it in its group give the survive
 //                 rule; one mask byte a thread, the tile's survivor count and its largest |balance|
-//   k_vc_offsets  one workgroup: the exclusive sum of the tile counts, the total, and the maximum of the tiles' |balance|
+//   (k_fold_offsets of merge_fold_kernels.hip: the exclusive sum of the tile counts, the total, and the maximum of the tiles' |balance|)
 //   k_vc_emit     the surviving row numbers of a tile, compacted through LDS and stored coalesced as UInt64 at the tile's offset
 // The states, the combines, the survive rule and the threads' walks are merge_versioned_host.h's; the scans inside a workgroup are
 // block_scan.h's.  No atomics; nothing depends on which workgroup runs first.
@@ -70,19 +71,14 @@ __device__ __forceinline__ void vc_block_scans(const VcSum & f, const VcAfter & 
 // the thread's positions [p0, p0 + FOLD_ITEMS) cut at n: the head bytes as one word, and how many positions are real
 __device__ __forceinline__ VcItems vc_items_heads(const u8 * __restrict__ heads, u32 n)
 {
-    const u64 p0 = (u64)blockIdx.x * FOLD_TILE + (u64)threadIdx.x * FOLD_ITEMS;
-    VcItems it{0, 0, 0};
-    if (p0 + FOLD_ITEMS <= n)
-    {
+    u64 p0, p1;
+    fold_thread_range(blockIdx.x, threadIdx.x, n, p0, p1);
+    VcItems it{0, 0, (u32)(p1 - p0)};
+    if (it.count == FOLD_ITEMS)
         it.heads = *(const u64 *)(heads + p0);  // p0 is a multiple of 8 and the array begins a pool allocation
-        it.count = FOLD_ITEMS;
-    }
-    else if (p0 < n)
-    {
-        it.count = (u32)(n - p0);
+    else
         for (u32 i = 0; i < it.count; ++i)
             it.heads |= (u64)heads[p0 + i] << (8 * i);
-    }
     return it;
 }
 
@@ -153,22 +149,6 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_vc_decide(const u8 * __restric
     }
 }
 
-// off[t] = counts[0] + .. + counts[t - 1]; off[n_tiles] = the total; off[n_tiles + 1] = the greatest of tile_max
-__global__ __launch_bounds__(FOLD_THREADS) void k_vc_offsets(const u32 * __restrict__ counts, const u64 * __restrict__ tile_max, u32 n_tiles, u64 * __restrict__ off)
-{
-    __shared__ u64 lmax[FOLD_THREADS / WAVE];
-    const u64 total = block_scan_array<AddU64, false>(counts, off, n_tiles, 0);
-    u64 m = 0;
-    for (u32 t = threadIdx.x; t < n_tiles; t += FOLD_THREADS)
-        m = tile_max[t] > m ? tile_max[t] : m;
-    m = block_reduce<MaxU64>(m, lmax);
-    if (threadIdx.x == 0)
-    {
-        off[n_tiles] = total;
-        off[n_tiles + 1] = m;
-    }
-}
-
 __global__ __launch_bounds__(FOLD_THREADS) void k_vc_emit(const u8 * __restrict__ masks, const u32 * __restrict__ rows, u32 n, const u64 * __restrict__ tile_offsets,
                                                           u64 * __restrict__ out)
 {
@@ -179,25 +159,23 @@ __global__ __launch_bounds__(FOLD_THREADS) void k_vc_emit(const u8 * __restrict_
     u32 at = block_scan_exclusive<AddU32>((u32)__popc(mask), lcount, &total);
     if (mask)
     {
-        const u64 p0 = (u64)blockIdx.x * FOLD_TILE + (u64)threadIdx.x * FOLD_ITEMS;
+        u64 p0, p1;
+        fold_thread_range(blockIdx.x, threadIdx.x, n, p0, p1);
         u32 r[FOLD_ITEMS] = {};
-        if (p0 + FOLD_ITEMS <= n)
+        if (p1 - p0 == FOLD_ITEMS)
         {
             const uint4 lo = *(const uint4 *)(rows + p0), hi = *(const uint4 *)(rows + p0 + 4);  // 32-byte aligned: p0 is a multiple of 8
             r[0] = lo.x, r[1] = lo.y, r[2] = lo.z, r[3] = lo.w, r[4] = hi.x, r[5] = hi.y, r[6] = hi.z, r[7] = hi.w;
         }
         else
             for (u32 i = 0; i < FOLD_ITEMS; ++i)  // a mask bit is only ever set below n
-                if (p0 + i < n)
+                if (p0 + i < p1)
                     r[i] = rows[p0 + i];
         for (u32 i = 0; i < FOLD_ITEMS; ++i)
             if ((mask >> i) & 1)
                 stage[at++] = r[i];  // at < total <= FOLD_TILE
     }
-    __syncthreads();
-    const u64 base = tile_offsets[blockIdx.x];
-    for (u32 e = threadIdx.x; e < total; e += FOLD_THREADS)
-        out[base + e] = stage[e];
+    fold_store_staged(stage, total, out, tile_offsets[blockIdx.x], true);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -212,62 +190,39 @@ extern "C" int chgpu_merge_versioned_collapsing(chgpu_ctx * ctx, const chgpu_col
     FoldPrefix px;
     CHGPU_TRY(fold_validate(ctx, key_cols, descending, nan_direction_hint, n_keys, run_offsets, n_runs, flags, &px));
     CHGPU_TRY(fold_check_column(sign_i8, "sign", CHGPU_I8, "Int8", px.rows));
-    PairAllocs mem;
-    mem.ctx = ctx, mem.op = "merge_versioned_collapsing";
-    mem.begin_call();
-    PairTemps tmp(mem);
-    const u64 rows = px.rows;
-    const u32 tiles = merge_tiles((u32)rows);
+    FoldCall call(ctx, "merge_versioned_collapsing");
+    const u32 n = (u32)px.rows;
+    const int sign_mode = 0;
+    CHGPU_TRY(call.open(key_cols, px, run_offsets, n_runs, flags, &sign_i8, &sign_mode, 1));
+    const u32 tiles = call.tiles;
     u64 result[2] = {0, 0};  // the survivors, the greatest |balance|
-    const u32 * rws = nullptr;
     const u64 * tile_off = nullptr;
     void * masks = nullptr;
-    if (rows)
+    if (n)
     {
-        if ((flags & CHGPU_MERGE_CHECK_SORTED) && rows >= 2)
-            CHGPU_TRY(merge_require_sorted(ctx, px.keys, run_offsets, n_runs, rows));
-        CHGPU_TRY(fold_require_domain(ctx, tmp, sign_i8, 0, rows));
-        const u64 * words = nullptr;
-        CHGPU_TRY(merge_order(ctx, key_cols, px.keys, run_offsets, n_runs, rows, tmp, &words, &rws));
-        void * heads = nullptr, * positive = nullptr, * agg_f = nullptr, * agg_g = nullptr, * counts = nullptr, * tile_max = nullptr, * off = nullptr;
-        CHGPU_TRY(tmp.alloc(rows, &heads));
-        CHGPU_TRY(tmp.alloc((size_t)tiles * FOLD_THREADS, &positive));
-        CHGPU_TRY(tmp.alloc((size_t)tiles * FOLD_THREADS, &masks));
-        CHGPU_TRY(tmp.alloc((size_t)tiles * sizeof(VcSum), &agg_f));
-        CHGPU_TRY(tmp.alloc((size_t)tiles * sizeof(VcAfter), &agg_g));
-        CHGPU_TRY(tmp.alloc((size_t)tiles * sizeof(u32), &counts));
-        CHGPU_TRY(tmp.alloc((size_t)tiles * sizeof(u64), &tile_max));
-        CHGPU_TRY(tmp.alloc(((size_t)tiles + 2) * sizeof(u64), &off));
-        fold_heads(ctx, px.keys, words, rws, (u32)rows, (u8 *)heads);
-        hipLaunchKernelGGL(k_vc_tile, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, (const i8 *)sign_i8->data, (const u8 *)heads, rws, (u32)rows, (u8 *)positive,
+        void * positive = nullptr, * agg_f = nullptr, * agg_g = nullptr, * counts = nullptr, * tile_max = nullptr;
+        CHGPU_TRY(call.tmp.alloc((size_t)tiles * FOLD_THREADS, &positive));
+        CHGPU_TRY(call.tmp.alloc((size_t)tiles * FOLD_THREADS, &masks));
+        CHGPU_TRY(call.tmp.alloc((size_t)tiles * sizeof(VcSum), &agg_f));
+        CHGPU_TRY(call.tmp.alloc((size_t)tiles * sizeof(VcAfter), &agg_g));
+        CHGPU_TRY(call.tmp.alloc((size_t)tiles * sizeof(u32), &counts));
+        CHGPU_TRY(call.tmp.alloc((size_t)tiles * sizeof(u64), &tile_max));
+        hipLaunchKernelGGL(k_vc_tile, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, (const i8 *)sign_i8->data, (const u8 *)call.heads, call.rows, n, (u8 *)positive,
                            (VcSum *)agg_f, (VcAfter *)agg_g);
         hipLaunchKernelGGL(k_vc_carry, dim3(2), dim3(FOLD_THREADS), 0, ctx->stream, (VcSum *)agg_f, (VcAfter *)agg_g, tiles);
-        hipLaunchKernelGGL(k_vc_decide, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, (const u8 *)heads, (const u8 *)positive, (u32)rows, (const VcSum *)agg_f,
+        hipLaunchKernelGGL(k_vc_decide, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, (const u8 *)call.heads, (const u8 *)positive, n, (const VcSum *)agg_f,
                            (const VcAfter *)agg_g, (u8 *)masks, (u32 *)counts, (u64 *)tile_max);
-        hipLaunchKernelGGL(k_vc_offsets, dim3(1), dim3(FOLD_THREADS), 0, ctx->stream, (const u32 *)counts, (const u64 *)tile_max, tiles, (u64 *)off);
-        ctx->counters[6] += 4;
-        tile_off = (const u64 *)off;
-        CHGPU_TRY(chgpu_read_back(ctx, tile_off + tiles, result, sizeof(result)));
+        ctx->counters[6] += 3;
+        CHGPU_TRY(fold_offsets(ctx, call.tmp, (const u32 *)counts, (const u64 *)tile_max, tiles, &tile_off, result));
     }
     chgpu_col * out = nullptr;
     int rc = chgpu_col_new(ctx, CHGPU_U64, result[0], &out);
     if (rc == CHGPU_OK && result[0])
     {
-        hipLaunchKernelGGL(k_vc_emit, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, (const u8 *)masks, rws, (u32)rows, tile_off, (u64 *)out->data);
+        hipLaunchKernelGGL(k_vc_emit, dim3(tiles), dim3(FOLD_THREADS), 0, ctx->stream, (const u8 *)masks, call.rows, n, tile_off, (u64 *)out->data);
         ctx->counters[6] += 1;
     }
-    if (rc == CHGPU_OK)
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            rc = chgpu_set_error(CHGPU_ERR_DEVICE, "merge_versioned_collapsing: %s", hipGetErrorString(e));
-    }
-    if (rc != CHGPU_OK)
-    {
-        if (out)
-            chgpu_col_free(out);
-        return rc;
-    }
+    CHGPU_TRY(call.close(rc, &out, 1));
     *rows_out_u64 = out;
     if (max_balance)
         *max_balance = result[1];

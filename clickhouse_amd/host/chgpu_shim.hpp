@@ -2615,62 +2615,70 @@ private:
     bool order_descending = false;
 };
 
-/// The merge of sorted runs of one Block layout: the runs' columns glued (chgpu_col_concat), merged by the description
-/// (chgpu_merge_sorted_permutation: MergingSortedAlgorithm over SortCursor) and every column permuted.  check_sorted: an unsorted run
-/// throws BAD_ARGUMENTS instead of giving an unspecified order.
-inline Chunk mergeSortedChunks(const ContextPtr & ctx, std::vector<Chunk> & runs, const SortDescription & description, uint64_t limit, bool check_sorted)
+/// Sorted runs of one Block layout glued end to end (chgpu_col_concat, column by column), with the arguments every chgpu_merge_* entry
+/// point shares: the cumulative run offsets and the description's key handles, directions and NaN hints.
+struct GluedRuns
 {
-    Chunk out;
-    if (runs.empty() || description.empty())
-        return out;
-    const size_t n_cols = runs[0].columns.size();
+    Chunk chunk;
     std::vector<uint64_t> offsets{0};
-    for (auto & run : runs)
-        offsets.push_back(offsets.back() + run.num_rows);
-    for (size_t c = 0; c < n_cols; ++c)
+    std::vector<const chgpu_col *> keys;
+    std::vector<int32_t> descending, hints;
+
+    /// no runs or no description: nothing to merge
+    bool empty() const { return keys.empty(); }
+    uint32_t numKeys() const { return static_cast<uint32_t>(keys.size()); }
+    uint32_t numRuns() const { return static_cast<uint32_t>(offsets.size() - 1); }
+    /// every glued column indexed with `rows` (a permutation, or the surviving rows), which is taken over
+    Chunk indexed(const ContextPtr & ctx, chgpu_col * rows) const
+    {
+        ColumnVector selected(ctx, rows);
+        Chunk out;
+        for (const auto & col : chunk.columns)
+            out.columns.push_back(col->index(selected, 0));
+        out.num_rows = selected.size();
+        return out;
+    }
+};
+
+inline GluedRuns glueSortedRuns(const ContextPtr & ctx, const std::vector<Chunk> & runs, const SortDescription & description)
+{
+    GluedRuns g;
+    if (runs.empty() || description.empty())
+        return g;
+    for (const auto & run : runs)
+        g.offsets.push_back(g.offsets.back() + run.num_rows);
+    for (size_t c = 0; c < runs[0].columns.size(); ++c)
     {
         std::vector<const chgpu_col *> parts;
-        for (auto & run : runs)
+        for (const auto & run : runs)
             parts.push_back(run.columns.at(c)->handle());
         chgpu_col * cat = nullptr;
         check(chgpu_col_concat(ctx->get(), static_cast<uint32_t>(parts.size()), parts.data(), &cat));
-        out.columns.push_back(std::make_shared<ColumnVector>(ctx, cat));
+        g.chunk.columns.push_back(std::make_shared<ColumnVector>(ctx, cat));
     }
-    std::vector<const chgpu_col *> keys;
-    std::vector<int32_t> descending, hints;
     for (const auto & d : description)
     {
-        keys.push_back(out.columns.at(d.column_number)->handle());
-        descending.push_back(d.direction < 0);
-        hints.push_back(d.nulls_direction);
+        g.keys.push_back(g.chunk.columns.at(d.column_number)->handle());
+        g.descending.push_back(d.direction < 0);
+        g.hints.push_back(d.nulls_direction);
     }
-    chgpu_col * perm = nullptr;
-    check(chgpu_merge_sorted_permutation(ctx->get(), keys.data(), descending.data(), hints.data(), static_cast<uint32_t>(keys.size()), offsets.data(),
-                                         static_cast<uint32_t>(runs.size()), limit, check_sorted ? CHGPU_MERGE_CHECK_SORTED : 0, &perm));
-    ColumnVector permutation(ctx, perm);
-    for (auto & col : out.columns)
-        col = col->index(permutation, 0);
-    out.num_rows = permutation.size();
-    runs.clear();
-    return out;
+    return g;
 }
 
-/// MergingSortedTransform (src/Processors/Merges/MergingSortedTransform.h): K inputs of sorted chunks, a SortDescription and a limit.
-/// The chunks of one input follow each other in its order, so each is a run of its own and the runs are numbered input by input: rows
-/// equal on every key come out by input, then by arrival (SortCursor's tie on `order`).  All inputs are read before the merge.
-class GpuMergingSortedTransform
+/// K inputs of sorted chunks.  The chunks of one input follow each other in its order, so each is a run of its own and the runs are
+/// numbered input by input: rows equal on every key come out by input, then by arrival (SortCursor's tie on `order`).
+class SortedRunInputs
 {
 public:
-    GpuMergingSortedTransform(ContextPtr ctx_, size_t num_inputs, SortDescription description_, uint64_t limit_ = 0)
-        : ctx(std::move(ctx_)), description(std::move(description_)), limit(limit_), inputs(num_inputs) {}
+    explicit SortedRunInputs(size_t num_inputs) : inputs(num_inputs) {}
 
     void consume(size_t input, Chunk chunk)
     {
         if (chunk.num_rows)
             inputs.at(input).push_back(std::move(chunk));
     }
-
-    Chunk finish()
+    /// the runs in their numbering; nothing is kept
+    std::vector<Chunk> take()
     {
         std::vector<Chunk> runs;
         for (auto & in : inputs)
@@ -2679,6 +2687,42 @@ public:
                 runs.push_back(std::move(chunk));
             in.clear();
         }
+        return runs;
+    }
+
+private:
+    std::vector<std::vector<Chunk>> inputs;
+};
+
+/// The merge of sorted runs of one Block layout: the runs' columns glued (chgpu_col_concat), merged by the description
+/// (chgpu_merge_sorted_permutation: MergingSortedAlgorithm over SortCursor) and every column permuted.  check_sorted: an unsorted run
+/// throws BAD_ARGUMENTS instead of giving an unspecified order.
+inline Chunk mergeSortedChunks(const ContextPtr & ctx, std::vector<Chunk> & runs, const SortDescription & description, uint64_t limit, bool check_sorted)
+{
+    GluedRuns g = glueSortedRuns(ctx, runs, description);
+    if (g.empty())
+        return Chunk();
+    chgpu_col * perm = nullptr;
+    check(chgpu_merge_sorted_permutation(ctx->get(), g.keys.data(), g.descending.data(), g.hints.data(), g.numKeys(), g.offsets.data(), g.numRuns(), limit,
+                                         check_sorted ? CHGPU_MERGE_CHECK_SORTED : 0, &perm));
+    Chunk out = g.indexed(ctx, perm);
+    runs.clear();
+    return out;
+}
+
+/// MergingSortedTransform (src/Processors/Merges/MergingSortedTransform.h): K inputs of sorted chunks, a SortDescription and a limit.
+/// The runs are numbered as SortedRunInputs numbers them.  All inputs are read before the merge.
+class GpuMergingSortedTransform
+{
+public:
+    GpuMergingSortedTransform(ContextPtr ctx_, size_t num_inputs, SortDescription description_, uint64_t limit_ = 0)
+        : ctx(std::move(ctx_)), description(std::move(description_)), limit(limit_), inputs(num_inputs) {}
+
+    void consume(size_t input, Chunk chunk) { inputs.consume(input, std::move(chunk)); }
+
+    Chunk finish()
+    {
+        std::vector<Chunk> runs = inputs.take();
         return mergeSortedChunks(ctx, runs, description, limit, true); // the inputs come from outside: an unsorted one throws
     }
 
@@ -2686,7 +2730,7 @@ private:
     ContextPtr ctx;
     SortDescription description;
     uint64_t limit;
-    std::vector<std::vector<Chunk>> inputs;
+    SortedRunInputs inputs;
 };
 
 /// MergeSortingTransform (src/Processors/Transforms/MergeSortingTransform.cpp) without the spill: consume() sorts a chunk as it arrives
@@ -2722,68 +2766,28 @@ public:
     GpuFoldingMergeInputs(ContextPtr ctx_, size_t num_inputs, SortDescription description_)
         : ctx(std::move(ctx_)), description(std::move(description_)), inputs(num_inputs) {}
 
-    void consume(size_t input, Chunk chunk)
-    {
-        if (chunk.num_rows)
-            inputs.at(input).push_back(std::move(chunk));
-    }
+    void consume(size_t input, Chunk chunk) { inputs.consume(input, std::move(chunk)); }
 
 protected:
     /// false: nothing was consumed
     bool glue()
     {
-        std::vector<Chunk> runs;
-        for (auto & in : inputs)
-        {
-            for (auto & chunk : in)
-                runs.push_back(std::move(chunk));
-            in.clear();
-        }
-        glued = Chunk();
-        offsets.assign(1, 0);
-        keys.clear(), descending.clear(), hints.clear();
-        if (runs.empty() || description.empty())
-            return false;
-        for (auto & run : runs)
-            offsets.push_back(offsets.back() + run.num_rows);
-        for (size_t c = 0; c < runs[0].columns.size(); ++c)
-        {
-            std::vector<const chgpu_col *> parts;
-            for (auto & run : runs)
-                parts.push_back(run.columns.at(c)->handle());
-            chgpu_col * cat = nullptr;
-            check(chgpu_col_concat(ctx->get(), static_cast<uint32_t>(parts.size()), parts.data(), &cat));
-            glued.columns.push_back(std::make_shared<ColumnVector>(ctx, cat));
-        }
-        for (const auto & d : description)
-        {
-            keys.push_back(glued.columns.at(d.column_number)->handle());
-            descending.push_back(d.direction < 0);
-            hints.push_back(d.nulls_direction);
-        }
-        return true;
+        g = GluedRuns();
+        g = glueSortedRuns(ctx, inputs.take(), description);
+        return !g.empty();
     }
-    uint32_t numKeys() const { return static_cast<uint32_t>(keys.size()); }
-    uint32_t numRuns() const { return static_cast<uint32_t>(offsets.size() - 1); }
-    /// every glued column indexed with the surviving rows
+    /// every glued column indexed with the surviving rows; the glued Block is let go
     Chunk indexed(chgpu_col * rows)
     {
-        ColumnVector selected(ctx, rows);
-        Chunk out;
-        for (auto & col : glued.columns)
-            out.columns.push_back(col->index(selected, 0));
-        out.num_rows = selected.size();
-        glued = Chunk();
+        Chunk out = g.indexed(ctx, rows);
+        g = GluedRuns();
         return out;
     }
 
     ContextPtr ctx;
     SortDescription description;
-    std::vector<std::vector<Chunk>> inputs;
-    Chunk glued;
-    std::vector<uint64_t> offsets;
-    std::vector<const chgpu_col *> keys;
-    std::vector<int32_t> descending, hints;
+    SortedRunInputs inputs;
+    GluedRuns g;
 };
 
 /// ReplacingSortedTransform (src/Processors/Merges/Algorithms/ReplacingSortedAlgorithm.cpp): per group of equal sorting key the last
@@ -2801,9 +2805,9 @@ public:
         if (!glue())
             return Chunk();
         chgpu_col * rows = nullptr;
-        check(chgpu_merge_replacing(ctx->get(), keys.data(), descending.data(), hints.data(), numKeys(), offsets.data(), numRuns(), CHGPU_MERGE_CHECK_SORTED,
-                                    version_column < 0 ? nullptr : glued.columns.at(version_column)->handle(),
-                                    is_deleted_column < 0 ? nullptr : glued.columns.at(is_deleted_column)->handle(), cleanup ? 1 : 0, &rows));
+        check(chgpu_merge_replacing(ctx->get(), g.keys.data(), g.descending.data(), g.hints.data(), g.numKeys(), g.offsets.data(), g.numRuns(), CHGPU_MERGE_CHECK_SORTED,
+                                    version_column < 0 ? nullptr : g.chunk.columns.at(version_column)->handle(),
+                                    is_deleted_column < 0 ? nullptr : g.chunk.columns.at(is_deleted_column)->handle(), cleanup ? 1 : 0, &rows));
         return indexed(rows);
     }
 
@@ -2824,8 +2828,8 @@ public:
         if (!glue())
             return Chunk();
         chgpu_col * rows = nullptr;
-        check(chgpu_merge_collapsing(ctx->get(), keys.data(), descending.data(), hints.data(), numKeys(), offsets.data(), numRuns(), CHGPU_MERGE_CHECK_SORTED,
-                                     glued.columns.at(sign_column)->handle(), &rows));
+        check(chgpu_merge_collapsing(ctx->get(), g.keys.data(), g.descending.data(), g.hints.data(), g.numKeys(), g.offsets.data(), g.numRuns(), CHGPU_MERGE_CHECK_SORTED,
+                                     g.chunk.columns.at(sign_column)->handle(), &rows));
         return indexed(rows);
     }
 
@@ -2849,8 +2853,8 @@ public:
         if (!glue())
             return Chunk();
         chgpu_col * rows = nullptr;
-        check(chgpu_merge_versioned_collapsing(ctx->get(), keys.data(), descending.data(), hints.data(), numKeys(), offsets.data(), numRuns(),
-                                               CHGPU_MERGE_CHECK_SORTED, glued.columns.at(sign_column)->handle(), &rows, &max_balance));
+        check(chgpu_merge_versioned_collapsing(ctx->get(), g.keys.data(), g.descending.data(), g.hints.data(), g.numKeys(), g.offsets.data(), g.numRuns(),
+                                               CHGPU_MERGE_CHECK_SORTED, g.chunk.columns.at(sign_column)->handle(), &rows, &max_balance));
         return indexed(rows);
     }
     uint64_t maxBalance() const { return max_balance; }
@@ -2879,25 +2883,25 @@ public:
         std::vector<int32_t> kinds;
         for (const auto & [position, kind] : folds)
         {
-            values.push_back(glued.columns.at(position)->handle());
+            values.push_back(g.chunk.columns.at(position)->handle());
             kinds.push_back(kind);
         }
         chgpu_col * first = nullptr, * last = nullptr;
         std::vector<chgpu_col *> results(values.size() + 1, nullptr);
-        check(chgpu_merge_folding(ctx->get(), keys.data(), descending.data(), hints.data(), numKeys(), offsets.data(), numRuns(), CHGPU_MERGE_CHECK_SORTED,
+        check(chgpu_merge_folding(ctx->get(), g.keys.data(), g.descending.data(), g.hints.data(), g.numKeys(), g.offsets.data(), g.numRuns(), CHGPU_MERGE_CHECK_SORTED,
                                   values.data(), kinds.data(), static_cast<uint32_t>(values.size()), drop_zero ? 1 : 0, &first, &last, results.data()));
         ColumnVector first_rows(ctx, first), last_rows(ctx, last);
         Chunk out;
         size_t folded = 0;
-        for (size_t c = 0; c < glued.columns.size(); ++c)
+        for (size_t c = 0; c < g.chunk.columns.size(); ++c)
         {
             if (folds.count(c))
                 out.columns.push_back(std::make_shared<ColumnVector>(ctx, results[folded++]));
             else
-                out.columns.push_back(glued.columns[c]->index(std::find(last_columns.begin(), last_columns.end(), c) != last_columns.end() ? last_rows : first_rows, 0));
+                out.columns.push_back(g.chunk.columns[c]->index(std::find(last_columns.begin(), last_columns.end(), c) != last_columns.end() ? last_rows : first_rows, 0));
         }
         out.num_rows = first_rows.size();
-        glued = Chunk();
+        g = GluedRuns();
         return out;
     }
 

@@ -110,17 +110,26 @@ def _check_blocks(blocks):
     return blocks, width
 
 
-def merge_sorted_blocks(blocks, description, limit: int = 0, check: bool = True):
-    """MergingSortedTransform over sorted Blocks (each a list of Columns / arrays): concatenates every column, merges by the description
-    (that of sort_block) and indexes every column.  -> (columns, perm)"""
+def _glue_blocks(blocks, description, check_layout=None):
+    """Sorted Blocks (each a list of Columns / arrays) as what the *_rows functions take: the blocks and the description are checked,
+    then check_layout(first block, width, description) raises for what its caller asks of the layout -- all of that before the
+    library is touched -- and the blocks are uploaded to one context and concatenated column by column.
+    -> (glued columns, description, run offsets, what check_layout returned)"""
     blocks, width = _check_blocks(blocks)
     description = _check_description(description, width)
+    layout = check_layout(blocks[0], width, description) if check_layout is not None else None
     ctx = next((c.ctx for block in blocks for c in block if isinstance(c, Column)), None) or Context(0)
     blocks = [[ctx.column(c) for c in block] for block in blocks]
     offsets = [0]
     for block in blocks:
         offsets.append(offsets[-1] + (len(block[0]) if block else 0))
-    glued = [concat([block[k] for block in blocks]) for k in range(width)]
+    return [concat([block[k] for block in blocks]) for k in range(width)], description, offsets, layout
+
+
+def merge_sorted_blocks(blocks, description, limit: int = 0, check: bool = True):
+    """MergingSortedTransform over sorted Blocks (each a list of Columns / arrays): concatenates every column, merges by the description
+    (that of sort_block) and indexes every column.  -> (columns, perm)"""
+    glued, description, offsets, _ = _glue_blocks(blocks, description)
     perm = merge_sorted_permutation(glued, description, offsets, limit=limit, check=check)
     return [c.index(perm) for c in glued], perm
 

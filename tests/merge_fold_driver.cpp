@@ -77,14 +77,6 @@ static void block_scan(const A & a, std::vector<typename A::State> & s, std::vec
     }
 }
 
-static void thread_range(u32 tile, u32 t, u64 n, u64 & p0, u64 & p1)
-{
-    p0 = (u64)tile * FOLD_TILE + (u64)t * FOLD_ITEMS;
-    p1 = p0 + FOLD_ITEMS;
-    p0 = p0 < n ? p0 : n;
-    p1 = p1 < n ? p1 : n;
-}
-
 template <class A>
 static void tile_scan(const A & a, const Layout & l, u32 tile, std::vector<typename A::State> & s, std::vector<u8> & f)
 {
@@ -94,7 +86,7 @@ static void tile_scan(const A & a, const Layout & l, u32 tile, std::vector<typen
     for (u32 t = 0; t < FOLD_THREADS; ++t)
     {
         u64 p0, p1;
-        thread_range(tile, t, n, p0, p1);
+        fold_thread_range(tile, t, n, p0, p1);
         fold_aggregate(a, FoldColumns<A>{a, l.heads.data(), l.rows.data(), n}, p0, p1, s[t], f[t]);
     }
     block_scan(a, s, f);
@@ -155,7 +147,7 @@ static Emitted replay(const Layout & l, MakeA make_a)
                 if (t)
                     fold_seg_combine(a, ps, pf, s[t - 1], f[t - 1]);
                 u64 p0, p1;
-                thread_range(tile, t, n, p0, p1);
+                fold_thread_range(tile, t, n, p0, p1);
                 fold_apply(a, FoldColumns<A>{a, l.heads.data(), l.rows.data(), n}, p0, p1, ps, pf, [&](u64, const State & st, u32 c, const u32 * o) {
                     REQUIRE(c <= FOLD_MAX_OUT);
                     if (pass && c)

@@ -172,7 +172,9 @@ static Result replay(const Input & in, size_t carry_pass)
         for (u32 t = 0; t < FOLD_THREADS; ++t)
         {
             const size_t slot = (size_t)tile * FOLD_THREADS + t;
-            items[slot] = vc_items_load(in.heads.data(), in.rows.data(), in.sign.data(), (u64)tile * FOLD_TILE + (u64)t * FOLD_ITEMS, n);
+            u64 p0, p1;
+            fold_thread_range(tile, t, n, p0, p1);
+            items[slot] = vc_items_load(in.heads.data(), in.rows.data(), in.sign.data(), p0, n);
             vc_aggregate(items[slot], f[t], g[t]);
         }
         const std::vector<VcSum> bf = scan_exclusive<Forward>(f, 64, &agg_f[tile]);
@@ -208,9 +210,13 @@ static Result replay(const Input & in, size_t carry_pass)
     {
         u64 at = off[tile];
         for (u32 t = 0; t < FOLD_THREADS; ++t)
+        {
+            u64 p0, p1;
+            fold_thread_range(tile, t, n, p0, p1);
             for (u32 i = 0; i < FOLD_ITEMS; ++i)
                 if ((masks[(size_t)tile * FOLD_THREADS + t] >> i) & 1)
-                    r.rows[at++] = in.rows[(u64)tile * FOLD_TILE + (u64)t * FOLD_ITEMS + i];
+                    r.rows[at++] = in.rows[p0 + i];
+        }
         REQUIRE(at == off[tile + 1]);
     }
     return r;

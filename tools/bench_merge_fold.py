@@ -18,9 +18,10 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
+
+from merge_bench_common import merge_tree_bytes, stats, timed
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -32,17 +33,9 @@ SPEC = [(0, False, 1)]
 ARG_BYTES = {"replacing": 8, "collapsing": 1, "summing": 16}
 
 
-def round_count(k):
-    t, n = 0, 1
-    while n < k:
-        n, t = n * 2, t + 1
-    return t
-
-
 def model_bytes(algo, rows, n_runs, outputs):
-    tree = rows * (8 + 12 + 24 * round_count(n_runs) + 12)
     out = outputs * (8 + 8 + 16 if algo == "summing" else 8)
-    return tree + rows * (13 + 3 * (5 + ARG_BYTES[algo])) + out
+    return merge_tree_bytes(8, rows, n_runs) + rows * (13 + 3 * (5 + ARG_BYTES[algo])) + out
 
 
 def make_columns(rng, rows, per_group):
@@ -50,19 +43,6 @@ def make_columns(rng, rows, per_group):
     return [rng.integers(0, max(1, rows // per_group), size=rows, dtype=np.int64), rng.integers(0, 4, size=rows, dtype=np.uint64),
             np.where(rng.integers(0, 2, size=rows, dtype=np.int8) == 1, 1, -1).astype(np.int8), rng.integers(0, 2**40, size=rows, dtype=np.uint64),
             rng.integers(0, 3, size=rows, dtype=np.uint64)]
-
-
-def timed(ctx, fn):
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    ctx.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
-def stats(ms):
-    ms = sorted(ms)
-    return {"ms": [round(x, 3) for x in ms], "median_ms": round(ms[len(ms) // 2], 3), "min_ms": round(ms[0], 3), "max_ms": round(ms[-1], 3)}
 
 
 def main():

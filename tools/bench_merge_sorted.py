@@ -4,7 +4,7 @@
   merge      merge_sorted_permutation(keys, description, run_offsets, limit, check=False) + index of the key columns by it
   sort       sort_block(keys, description, limit) of the concatenation: the operator a caller has today (it sorts again from nothing)
   copy       chgpu_col_concat of a UInt8 column, repeated until it has read + written the bytes the plan's byte model says the merge
-             moves (merge_tree_bytes / merge_sort_bytes of csrc/merge_host.h, restated below): the time those bytes cost at copy speed
+             moves (merge_tree_bytes / merge_sort_bytes of csrc/merge_host.h, restated in merge_bench_common.py and below): the time those bytes cost at copy speed
   check      is_sorted over the same runs (what check=True adds)
 
 Shapes, --rows rows in total in K = 2, 8, 64, 1024 equal runs: Int64 keys; UInt8 keys; (UInt32 of 1000 distinct values, Int64), where
@@ -17,9 +17,10 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
+
+from merge_bench_common import merge_tree_bytes, stats, timed
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -32,16 +33,9 @@ KEYSETS = {
 RUN_COUNTS = (2, 8, 64, 1024)
 
 
-def round_count(k):
-    t, n = 0, 1
-    while n < k:
-        n, t = n * 2, t + 1
-    return t
-
-
 def model(key_sizes, rows, cut_rows, n_runs):
-    """merge_tree_bytes, merge_sort_bytes and merge_plan of csrc/merge_host.h"""
-    tree = cut_rows * (key_sizes[0] + 12 + 24 * round_count(n_runs) + 12)
+    """the tree's bytes, merge_sort_bytes and merge_plan of csrc/merge_host.h"""
+    tree = merge_tree_bytes(key_sizes[0], cut_rows, n_runs)
     sort = rows * sum((s + 1) * 2 * (s + 8) for s in key_sizes)
     return tree, sort, "tree" if tree <= 2 * sort else "sort"   # MRG_SORT_BYTE_COST
 
@@ -56,19 +50,6 @@ def make_columns(rng, dtypes, rows):
         else:
             cols.append(rng.integers(-2**62, 2**62, size=rows, dtype=np.int64))
     return cols
-
-
-def timed(ctx, fn):
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    ctx.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
-def stats(ms):
-    ms = sorted(ms)
-    return {"ms": [round(x, 3) for x in ms], "median_ms": round(ms[len(ms) // 2], 3), "min_ms": round(ms[0], 3), "max_ms": round(ms[-1], 3)}
 
 
 def main():

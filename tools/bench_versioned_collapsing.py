@@ -21,9 +21,10 @@ import argparse
 import json
 import os
 import sys
-import time
 
 import numpy as np
+
+from merge_bench_common import merge_tree_bytes, stats, timed
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
@@ -36,23 +37,12 @@ SPEC = [(0, False, 1), (1, False, 1)]
 NEW_PASS_BYTES_PER_ROW = 1 + 13 + (4 + 1 + 1 + 0.125) + (1 + 0.125 + 0.125) + (0.125 + 4)
 
 
-def round_count(k):
-    t, n = 0, 1
-    while n < k:
-        n, t = n * 2, t + 1
-    return t
-
-
-def tree_bytes(rows, n_runs):
-    return rows * (8 + 12 + 24 * round_count(n_runs) + 12)
-
-
 def model_bytes(rows, n_runs, outputs):
-    return int(tree_bytes(rows, n_runs) + rows * NEW_PASS_BYTES_PER_ROW + 8 * outputs)
+    return int(merge_tree_bytes(8, rows, n_runs) + rows * NEW_PASS_BYTES_PER_ROW + 8 * outputs)
 
 
 def collapsing_model_bytes(rows, n_runs, outputs):
-    return int(tree_bytes(rows, n_runs) + rows * (13 + 3 * (5 + 1)) + 8 * outputs)
+    return int(merge_tree_bytes(8, rows, n_runs) + rows * (13 + 3 * (5 + 1)) + 8 * outputs)
 
 
 def make_keys(rng, rows, per_group):
@@ -65,19 +55,6 @@ def make_sign(mix, rows):
     if mix == "cancel":
         sign[rows // 2:] = -1       # K is even: a run holds one sign
     return sign
-
-
-def timed(ctx, fn):
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    ctx.synchronize()
-    return (time.perf_counter() - t0) * 1e3, out
-
-
-def stats(ms):
-    ms = sorted(ms)
-    return {"ms": [round(x, 3) for x in ms], "median_ms": round(ms[len(ms) // 2], 3), "min_ms": round(ms[0], 3), "max_ms": round(ms[-1], 3)}
 
 
 def main():
