@@ -6,21 +6,22 @@
 //
 //   k_sf_length<KIND>   length / empty / notEmpty: the offsets alone.  lengthUTF8: one lane per row, 8 bytes a step, the popcount of
 //                       the bytes that are no continuation byte (10xxxxxx), the tail masked.
-//   k_sf_map_case       lower / upper walk no rows: a flat sweep over chars[0, offsets.back()) in 16-byte chunks cut on the grid of the
-//                       chars ADDRESS (as k_str_contains_flat cuts its tiles), so that a view that starts anywhere loads aligned.  The
-//                       flip is SWAR on the two 8-byte words: a per-byte range mask, shifted to bit 0x20.  The two edge chunks go byte
-//                       by byte; nothing in front of the view or behind offsets.back() is read or written.  The offsets are copied.
-//   k_sf_cmp_columns    one lane per row, 8 bytes a step from both sides; differing words are ordered by one compare of the
-//                       byte-swapped words (as k_str_row_const), then the shorter value is the smaller.
+//   k_sf_map_case       lower / upper walk no rows: a flat sweep over chars[0, offsets.back()) in the 16-byte chunks of StrGrid, loaded
+//                       through str_load_chunk.  The flip is SWAR on the two 8-byte words: a per-byte range mask, shifted to bit 0x20.
+//                       A whole chunk is stored in one piece, the two edge chunks byte by byte; nothing in front of the view or behind
+//                       offsets.back() is read or written.  The offsets are copied.
+//   k_sf_cmp_columns    one lane per row: str_compare over both values in global memory, str_cmp_holds.
 //   k_sf_substring_sizes / _move, k_sf_concat_sizes / _move
-//                       the shape of chgpu_string_filter: sizes from the offsets alone (too_long through str_size_u32), the layout
-//                       pass of string_column.h, then str_copy_value per part and the zero, which the move writes itself.
-//                       concat's constant parts are staged into LDS once per workgroup from the kernel argument.
+//                       sizes from the offsets alone (too_long through str_size_u32), then str_copy_value per part and the zero,
+//                       which the move writes itself.  concat's constant parts are staged into LDS once per workgroup from the kernel
+//                       argument.  Between the two kernels: str_build_values, as for filter and index.
 //   k_sf_position       one lane per row: candidates for the needle's first byte 8 bytes a step (SWAR zero-byte test), the rest of the
-//                       needle verified against the constant in LDS, stop at the first hit.  Start positions behind size - needle are
-//                       masked off, so an occurrence never takes in the terminating zero or the next row.
-// What these share with the other String operators (a value's begin and size, the copy loop, the prologue, the call's allocations, the
-// layout pass) is string_column.h; the one pool allocation of substring / concat is divided by str_values_lay of string_host.h.
+//                       needle verified against the constant in LDS (str_equals_words), stop at the first hit.  Start positions behind
+//                       size - needle are masked off, so an occurrence never takes in the terminating zero or the next row.
+// Everything these share with the other String operators is string_column.h: a value's begin and size, the copy loop, the compare and
+// equality loops, the grid; the prologue and a second column argument; the entry point of one result column (str_one_column: length,
+// cmp_columns, position) and the one that builds a ColumnString (str_build_values: substring, concat -- the call's allocations of
+// str_call, its one pool allocation divided by str_carve over str_values_lay of string_host.h, the layout pass str_layout_values).
 #include "string_column.h"
 
 static constexpr u32 SF_ARGS = 8; // arguments of one concat
@@ -75,26 +76,21 @@ __global__ __launch_bounds__(256) void k_sf_map_case(const u8 * __restrict__ cha
 {
     const u32 first = upper ? 'a' : 'A';
     const u64 add_ge = 0x0101010101010101ull * (0x80 - first), add_gt = 0x0101010101010101ull * (0x80 - first - 26);
-    const u64 a0 = (u64)chars & 15;
-    const u8 * grid = chars - a0; // 16-byte aligned; only [a0, end) is read
-    const u64 end = a0 + size;
-    for (u64 q = ((u64)blockIdx.x * 256 + threadIdx.x) * 16; q < end; q += (u64)gridDim.x * 256 * 16)
+    const StrGrid g(chars, size);
+    for (u64 q = ((u64)blockIdx.x * 256 + threadIdx.x) * 16; q < g.end; q += (u64)gridDim.x * 256 * 16)
     {
-        if (q >= a0 && q + 16 <= end)
+        const uint4 v = str_load_chunk(g, q);
+        const u64 lo = sf_flip_word((u64)v.x | ((u64)v.y << 32), add_ge, add_gt), hi = sf_flip_word((u64)v.z | ((u64)v.w << 32), add_ge, add_gt);
+        if (q >= g.a0 && q + 16 <= g.end)
         {
-            const uint4 v = *(const uint4 *)(grid + q);
-            const u64 lo = sf_flip_word((u64)v.x | ((u64)v.y << 32), add_ge, add_gt), hi = sf_flip_word((u64)v.z | ((u64)v.w << 32), add_ge, add_gt);
             const uint4 r = make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32));
-            __builtin_memcpy(out + (q - a0), &r, 16); // the result starts on its own grid: this store is unaligned when the view is
+            __builtin_memcpy(out + (q - g.a0), &r, 16); // the result starts on its own grid: this store is unaligned when the view is
         }
         else
         {
             for (u32 k = 0; k < 16; ++k) // the chunk holding the view's first byte, and the one holding its last
-                if (q + k >= a0 && q + k < end)
-                {
-                    const u32 b = grid[q + k];
-                    out[q + k - a0] = (u8)(b - first < 26u ? b ^ 0x20u : b);
-                }
+                if (q + k >= g.a0 && q + k < g.end)
+                    out[q + k - g.a0] = (u8)((k < 8 ? lo : hi) >> (8 * (k & 7)));
         }
     }
 }
@@ -114,28 +110,9 @@ __global__ __launch_bounds__(256) void k_sf_cmp_columns(const u64 * __restrict__
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
     {
         const StrValue va = str_value(a_offsets, i), vb = str_value(b_offsets, i);
-        const u64 la = va.size - 1, lb = vb.size - 1;
-        const u64 k = la < lb ? la : lb;
         const u8 * pa = a_chars + va.begin, * pb = b_chars + vb.begin;
-        int cmp = 0;
-        for (u64 j = 0; j < k; j += 8)
-        {
-            u64 a = str_load8(pa + j), b = str_load8(pb + j);
-            if (k - j < 8)
-            {
-                const u64 tm = str_tail_mask(k - j);
-                a &= tm, b &= tm;
-            }
-            if (a != b)
-            {
-                cmp = __builtin_bswap64(a) < __builtin_bswap64(b) ? -1 : 1; // the first byte is the most significant one
-                break;
-            }
-        }
-        if (cmp == 0)
-            cmp = la < lb ? -1 : la > lb ? 1 : 0;
-        const bool res = op == CHGPU_EQ ? cmp == 0 : op == CHGPU_NE ? cmp != 0 : op == CHGPU_LT ? cmp < 0 : op == CHGPU_GT ? cmp > 0 : op == CHGPU_LE ? cmp <= 0 : cmp >= 0;
-        out[i] = res ? 1 : 0;
+        const int cmp = str_compare([&](u64 j) { return str_load8(pa + j); }, [&](u64 j) { return str_load8(pb + j); }, va.size - 1, vb.size - 1);
+        out[i] = str_cmp_holds(op, cmp) ? 1 : 0;
     }
 }
 
@@ -287,19 +264,7 @@ __global__ __launch_bounds__(256) void k_sf_position(const u64 * __restrict__ of
                 {
                     const u64 s = j + __builtin_ctz(cand);
                     cand &= cand - 1;
-                    bool eq = true;
-                    for (u32 k = 0; k < m; k += 8)
-                    {
-                        u64 x = str_load8(p + s + k) ^ s_w[k >> 3];
-                        if (m - k < 8)
-                            x &= str_tail_mask(m - k);
-                        if (x)
-                        {
-                            eq = false;
-                            break;
-                        }
-                    }
-                    if (eq)
+                    if (str_equals_words([&](u32 k) { return str_load8(p + s + k); }, [&](u32 k) { return s_w[k >> 3]; }, m))
                     {
                         res = s + 1;
                         break;
@@ -314,12 +279,6 @@ __global__ __launch_bounds__(256) void k_sf_position(const u64 * __restrict__ of
 // ---------------------------------------------------------------------------------------------
 // entry points
 // ---------------------------------------------------------------------------------------------
-static int sf_end(const char * what)
-{
-    CHGPU_REQUIRE(hipGetLastError() == hipSuccess, CHGPU_ERR_DEVICE, "string %s kernels failed to launch", what);
-    return CHGPU_OK;
-}
-
 extern "C" int chgpu_string_length(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int kind, chgpu_col ** out)
 {
     ChgpuDeviceGuard _dev_guard(ctx);
@@ -330,13 +289,8 @@ extern "C" int chgpu_string_length(chgpu_ctx * ctx, const chgpu_col * offsets_u6
     }, &col));
     const u64 n = col.rows;
     const bool wide = kind == CHGPU_STR_LENGTH || kind == CHGPU_STR_LENGTH_UTF8;
-    PairAllocs mem = str_call(ctx, "string length");
-    StrCols<> res;
-    CHGPU_TRY(mem.col_new(wide ? CHGPU_U64 : CHGPU_U8, n, &res.v[0]));
-    if (n)
-    {
+    return str_one_column(ctx, "string length", wide ? CHGPU_U64 : CHGPU_U8, n, [&](void * dst) {
         const dim3 grid(chgpu_grid_for(ctx, n, 256, 8)), block(256);
-        void * dst = res.v[0]->data;
         if (kind == CHGPU_STR_LENGTH)
             hipLaunchKernelGGL(k_sf_length<CHGPU_STR_LENGTH>, grid, block, 0, ctx->stream, col.offsets, col.chars, n, dst);
         else if (kind == CHGPU_STR_LENGTH_UTF8)
@@ -346,10 +300,8 @@ extern "C" int chgpu_string_length(chgpu_ctx * ctx, const chgpu_col * offsets_u6
         else
             hipLaunchKernelGGL(k_sf_length<CHGPU_STR_NOT_EMPTY>, grid, block, 0, ctx->stream, col.offsets, col.chars, n, dst);
         ctx->counters[6] += 1;
-        CHGPU_TRY(sf_end("length"));
-    }
-    res.give(out);
-    return CHGPU_OK;
+        return (int)CHGPU_OK;
+    }, out);
 }
 
 extern "C" int chgpu_string_map_case(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int kind, chgpu_col ** out_offsets_u64,
@@ -372,11 +324,10 @@ extern "C" int chgpu_string_map_case(chgpu_ctx * ctx, const chgpu_col * offsets_
     if (n)
     {
         hipLaunchKernelGGL(k_sf_copy_u64, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, col.offsets, n, (u64 *)res.v[0]->data);
-        const u64 chunks = (((u64)(uintptr_t)col.chars & 15) + size + 15) / 16;
-        hipLaunchKernelGGL(k_sf_map_case, dim3(chgpu_grid_for(ctx, chunks, 256, 8)), dim3(256), 0, ctx->stream, col.chars, size, (u32)(kind == CHGPU_STR_UPPER),
-                           (u8 *)res.v[1]->data);
+        hipLaunchKernelGGL(k_sf_map_case, dim3(chgpu_grid_for(ctx, str_grid_chunks(StrGrid(col.chars, size)), 256, 8)), dim3(256), 0, ctx->stream, col.chars, size,
+                           (u32)(kind == CHGPU_STR_UPPER), (u8 *)res.v[1]->data);
         ctx->counters[6] += 2;
-        CHGPU_TRY(sf_end("map_case"));
+        CHGPU_TRY(str_launched("string map_case"));
     }
     res.give(out_offsets_u64, out_chars_u8);
     return CHGPU_OK;
@@ -386,56 +337,18 @@ extern "C" int chgpu_string_cmp_columns(chgpu_ctx * ctx, const chgpu_col * a_off
                                         const chgpu_col * b_chars_u8, int op, chgpu_col ** out_u8)
 {
     ChgpuDeviceGuard _dev_guard(ctx);
-    StrColumn a;
+    StrColumn a, b;
     CHGPU_TRY(str_column_begin(ctx, a_offsets_u64, a_chars_u8, b_offsets_u64 && b_chars_u8 && out_u8, [&] {
-        CHGPU_REQUIRE(b_offsets_u64->type == CHGPU_U64 && b_chars_u8->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "ColumnString = UInt64 offsets + UInt8 chars");
         CHGPU_REQUIRE(op >= CHGPU_EQ && op <= CHGPU_GE, CHGPU_ERR_BAD_ARGUMENTS, "unknown comparison %d", op);
-        CHGPU_REQUIRE(a_offsets_u64->rows == b_offsets_u64->rows, CHGPU_ERR_SIZES_MISMATCH, "the columns have %llu and %llu rows",
-                      (unsigned long long)a_offsets_u64->rows, (unsigned long long)b_offsets_u64->rows);
-        return (int)CHGPU_OK;
+        return str_column_also_checks(a_offsets_u64, b_offsets_u64, b_chars_u8, 1);
     }, &a));
-    if (b_offsets_u64 != a_offsets_u64 || b_chars_u8 != a_chars_u8)
-        CHGPU_TRY(str_validate_offsets(ctx, b_offsets_u64, b_chars_u8));
+    CHGPU_TRY(str_column_also(ctx, a_offsets_u64, a_chars_u8, b_offsets_u64, b_chars_u8, &b));
     const u64 n = a.rows;
-    PairAllocs mem = str_call(ctx, "string cmp_columns");
-    StrCols<> res;
-    CHGPU_TRY(mem.col_new(CHGPU_U8, n, &res.v[0]));
-    if (n)
-    {
-        hipLaunchKernelGGL(k_sf_cmp_columns, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, a.offsets, a.chars, (const u64 *)b_offsets_u64->data,
-                           (const u8 *)b_chars_u8->data, n, op, (u8 *)res.v[0]->data);
+    return str_one_column(ctx, "string cmp_columns", CHGPU_U8, n, [&](void * dst) {
+        hipLaunchKernelGGL(k_sf_cmp_columns, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, a.offsets, a.chars, b.offsets, b.chars, n, op, (u8 *)dst);
         ctx->counters[6] += 1;
-        CHGPU_TRY(sf_end("cmp_columns"));
-    }
-    res.give(out_u8);
-    return CHGPU_OK;
-}
-
-// the shape substring and concat share with filter and index: `sizes(l)` launches the sizes kernel, `move(l, out)` the move kernel
-template <class Sizes, class Move>
-static int sf_build_values(chgpu_ctx * ctx, const char * op, u64 n, Sizes && sizes, Move && move, chgpu_col ** out_offsets_u64, chgpu_col ** out_chars_u8)
-{
-    PairAllocs mem = str_call(ctx, op);
-    PairTemps tmp(mem);
-    StrValuesLayout l{};
-    if (n)
-    {
-        CHGPU_TRY(str_carve(tmp, [&](uintptr_t base) { return str_values_lay(base, n, false, chgpu_scan_tmp_bytes(n), &l); }));
-        CHGPU_HIP(hipMemsetAsync(l.words, 0, sizeof(StrLayoutWords), ctx->stream));
-        sizes(l);
-        ctx->counters[6] += 1;
-    }
-    StrLayoutWords words;
-    StrCols<> res;
-    CHGPU_TRY(str_layout_values(ctx, mem, l, n, false, n, &words, &res));
-    if (n)
-    {
-        move(l, res);
-        ctx->counters[6] += 1;
-        CHGPU_TRY(sf_end(op));
-    }
-    res.give(out_offsets_u64, out_chars_u8);
-    return CHGPU_OK;
+        return (int)CHGPU_OK;
+    }, out_u8);
 }
 
 extern "C" int chgpu_string_substring(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int64_t offset, int has_length, uint64_t length,
@@ -450,7 +363,7 @@ extern "C" int chgpu_string_substring(chgpu_ctx * ctx, const chgpu_col * offsets
     const u64 n = col.rows;
     const dim3 grid(chgpu_grid_for(ctx, n, 256, 8)), block(256);
     const u32 has = has_length != 0;
-    return sf_build_values(ctx, "substring", n,
+    return str_build_values(ctx, "substring", n, n,
         [&](const StrValuesLayout & l) {
             hipLaunchKernelGGL(k_sf_substring_sizes, grid, block, 0, ctx->stream, col.offsets, n, (i64)offset, has, (u64)length, l.sizes, (u32 *)&l.words->too_long);
         },
@@ -483,9 +396,7 @@ extern "C" int chgpu_string_concat(chgpu_ctx * ctx, const chgpu_string_arg * arg
             if (g.offsets)
             {
                 CHGPU_REQUIRE(g.chars, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument (chars of argument %u)", p);
-                CHGPU_REQUIRE(g.offsets->type == CHGPU_U64 && g.chars->type == CHGPU_U8, CHGPU_ERR_BAD_ARGUMENTS, "ColumnString = UInt64 offsets + UInt8 chars");
-                CHGPU_REQUIRE(g.offsets->rows == first->offsets->rows, CHGPU_ERR_SIZES_MISMATCH, "argument %u has %llu rows, not %llu", p,
-                              (unsigned long long)g.offsets->rows, (unsigned long long)first->offsets->rows);
+                CHGPU_TRY(str_column_also_checks(first->offsets, g.offsets, g.chars, p));
                 continue;
             }
             CHGPU_REQUIRE(g.value || !g.value_bytes, CHGPU_ERR_BAD_ARGUMENTS, "NULL argument (value of argument %u)", p);
@@ -503,16 +414,17 @@ extern "C" int chgpu_string_concat(chgpu_ctx * ctx, const chgpu_string_arg * arg
         const chgpu_string_arg & g = args[p];
         if (!g.offsets)
             continue;
-        bool seen = false; // the same column may appear several times: its offsets are walked once
+        const chgpu_string_arg * walked = first; // the same column may appear several times: its offsets are walked once
         for (u32 q = 0; q < p; ++q)
-            seen = seen || (args[q].offsets == g.offsets && args[q].chars == g.chars);
-        if (!seen && &g != first)
-            CHGPU_TRY(str_validate_offsets(ctx, g.offsets, g.chars));
-        a.offsets[p] = (const u64 *)g.offsets->data, a.chars[p] = (const u8 *)g.chars->data;
+            if (args[q].offsets == g.offsets && args[q].chars == g.chars)
+                walked = &args[q];
+        StrColumn also;
+        CHGPU_TRY(str_column_also(ctx, walked->offsets, walked->chars, g.offsets, g.chars, &also));
+        a.offsets[p] = also.offsets, a.chars[p] = also.chars;
     }
     const u64 n = col.rows;
     const dim3 grid(chgpu_grid_for(ctx, n, 256, 8)), block(256);
-    return sf_build_values(ctx, "concat", n,
+    return str_build_values(ctx, "concat", n, n,
         [&](const StrValuesLayout & l) { hipLaunchKernelGGL(k_sf_concat_sizes, grid, block, 0, ctx->stream, a, n, l.sizes, (u32 *)&l.words->too_long); },
         [&](const StrValuesLayout & l, StrCols<> & res) {
             hipLaunchKernelGGL(k_sf_concat_move, grid, block, 0, ctx->stream, a, (const u64 *)l.pos, n, (u64 *)res.v[0]->data, (u8 *)res.v[1]->data);
@@ -530,16 +442,10 @@ extern "C" int chgpu_string_position_const(chgpu_ctx * ctx, const chgpu_col * of
         return (int)CHGPU_OK;
     }, &col));
     const u64 n = col.rows;
-    PairAllocs mem = str_call(ctx, "string position");
-    StrCols<> res;
-    CHGPU_TRY(mem.col_new(CHGPU_U64, n, &res.v[0]));
-    if (n)
-    {
-        hipLaunchKernelGGL(k_sf_position, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, col.offsets, col.chars, n,
-                           str_const_of(needle, needle_bytes), (u64 *)res.v[0]->data);
+    return str_one_column(ctx, "string position", CHGPU_U64, n, [&](void * dst) {
+        hipLaunchKernelGGL(k_sf_position, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, col.offsets, col.chars, n, str_const_of(needle, needle_bytes),
+                           (u64 *)dst);
         ctx->counters[6] += 1;
-        CHGPU_TRY(sf_end("position"));
-    }
-    res.give(out_u64);
-    return CHGPU_OK;
+        return (int)CHGPU_OK;
+    }, out_u64);
 }

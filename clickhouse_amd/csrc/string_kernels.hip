@@ -15,8 +15,10 @@
 //   scan of the "I am a first row" flags -> dense ids in order of first appearance; k_str_ids gathers them per row
 // The hash is internal (placement only).  Algorithmic bytes: chars once + 8 B offsets + 4 B id per row; the table traffic is
 // random 16-byte cells, two touches per row.
-// Further down: ColumnString::filter and the predicates against a constant.  What the String entry points share (a value's begin and
-// size, the copy loop, the prologue, the call's allocations, the layout pass) is string_column.h; the buffer layouts are string_host.h.
+// Further down: ColumnString::filter and the predicates against a constant.  What the String kernels and entry points share is
+// string_column.h: a value's begin and size, the copy loop, the ordered compare and the equality test of two byte ranges, the grid of
+// the chars address; the prologue, the call's allocations, the entry point of one result column (every predicate) and the one that
+// builds a ColumnString (filter).  The buffer layouts are string_host.h.
 #include "string_column.h"
 
 __device__ __forceinline__ u64 str_hash_bytes(const u8 * p, u64 len)
@@ -30,26 +32,12 @@ __device__ __forceinline__ u64 str_hash_bytes(const u8 * p, u64 len)
     }
     if (i < len)
     {
-        const u64 tail = str_load8(p + i) & (~0ull >> (8 * (8 - (len - i))));
+        const u64 tail = str_load8(p + i) & (~0ull >> (8 * (8 - (len - i)))); // (str_tail_mask, spelled out: tests/keycraft.py restates this function)
         h = (h ^ tail) * 0xc4ceb9fe1a85ec53ull;
         h ^= h >> 29;
     }
     h = dev_intHash64(h);
     return h | 1ull; // 0 marks an empty cell
-}
-
-__device__ __forceinline__ bool str_equal(const u8 * a, const u8 * b, u64 len)
-{
-    u64 i = 0;
-    for (; i + 8 <= len; i += 8)
-        if (str_load8(a + i) != str_load8(b + i))
-            return false;
-    if (i < len)
-    {
-        const u64 m = ~0ull >> (8 * (8 - (len - i)));
-        return ((str_load8(a + i) ^ str_load8(b + i)) & m) == 0;
-    }
-    return true;
 }
 
 // ColumnString invariant (ColumnString.h:40-52): offsets strictly increase (every value has at least its terminating zero) and end inside
@@ -87,9 +75,8 @@ __global__ __launch_bounds__(256) void k_str_hash(const u64 * __restrict__ offse
 {
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
     {
-        const u64 begin = i ? offsets[i - 1] : 0;
-        const u64 len = offsets[i] - begin - 1; // without the terminating zero (ColumnString.h:48-52)
-        hash[i] = str_hash_bytes(chars + begin, len);
+        const StrValue v = str_value(offsets, i);
+        hash[i] = str_hash_bytes(chars + v.begin, v.size - 1); // without the terminating zero (ColumnString.h:48-52)
     }
 }
 
@@ -155,9 +142,9 @@ __global__ __launch_bounds__(256) void k_str_resolve(const u64 * __restrict__ of
         }
         if (r != i)
         {
-            const u64 b0 = i ? offsets[i - 1] : 0, l0 = offsets[i] - b0 - 1;
-            const u64 b1 = r ? offsets[r - 1] : 0, l1 = offsets[r] - b1 - 1;
-            if (l0 != l1 || !str_equal(chars + b0, chars + b1, l0))
+            const StrValue v0 = str_value(offsets, i), v1 = str_value(offsets, r);
+            const u8 * p0 = chars + v0.begin, * p1 = chars + v1.begin;
+            if (v0.size != v1.size || !str_equals_words([&](u64 k) { return str_load8(p0 + k); }, [&](u64 k) { return str_load8(p1 + k); }, v0.size - 1))
                 *fail = 2; // two different values under one 64-bit tag
         }
         rep_row[i] = r;
@@ -230,7 +217,7 @@ extern "C" int chgpu_string_dictionary_encode(chgpu_ctx * ctx, const chgpu_col *
         hipLaunchKernelGGL(k_str_ids, dim3(grid), dim3(256), 0, ctx->stream, (const u64 *)l.rep_row, (const u32 *)l.is_first, (const u64 *)l.prefix, n,
                            (u32 *)out.v[0]->data, (u64 *)out.v[1]->data);
         ctx->counters[6] += 1;
-        CHGPU_REQUIRE(hipGetLastError() == hipSuccess, CHGPU_ERR_DEVICE, "string dictionary kernels failed to launch");
+        CHGPU_TRY(str_launched("string dictionary"));
     }
     out.give(ids_u32, first_rows_u64);
     *n_distinct = total;
@@ -285,33 +272,16 @@ extern "C" int chgpu_string_filter(chgpu_ctx * ctx, const chgpu_col * offsets_u6
         return (int)CHGPU_OK;
     }, &col));
     const u64 n = col.rows;
-    const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
-    PairAllocs mem = str_call(ctx, "string filter");
-    PairTemps tmp(mem);
-    StrValuesLayout l{};
-    if (n)
-    {
-        CHGPU_TRY(str_carve(tmp, [&](uintptr_t base) { return str_values_lay(base, n, true, chgpu_scan_tmp_bytes(n), &l); }));
-        CHGPU_HIP(hipMemsetAsync(l.words, 0, sizeof(StrLayoutWords), ctx->stream));
-        hipLaunchKernelGGL(k_str_filter_sizes, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, (const u8 *)filter_u8->data, n, l.flag, l.sizes,
-                           (u32 *)&l.words->too_long);
-        CHGPU_TRY(chgpu_scan_exclusive_u32_u64(ctx, l.flag, l.row_pos, n, &l.words->rows, l.scan_tmp, chgpu_scan_tmp_bytes(n)));
-    }
-    StrLayoutWords words;
-    StrCols<> out;
-    CHGPU_TRY(str_layout_values(ctx, mem, l, n, true, n, &words, &out));
-    if (n)
-    {
-        if (words.rows)
-            hipLaunchKernelGGL(k_str_filter_move, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, col.chars, (const u32 *)l.flag, (const u64 *)l.row_pos,
-                               (const u64 *)l.pos, n, (u64 *)out.v[0]->data, (u8 *)out.v[1]->data);
-        ctx->counters[6] += 2;
-        ctx->counters[0] += words.rows;
-        CHGPU_REQUIRE(hipGetLastError() == hipSuccess, CHGPU_ERR_DEVICE, "string filter kernels failed to launch");
-    }
-    out.give(out_offsets_u64, out_chars_u8);
-    *rows_out = words.rows;
-    return CHGPU_OK;
+    const dim3 grid(chgpu_grid_for(ctx, n, 256, 8)), block(256);
+    return str_build_values(ctx, "string filter", n, n,
+        [&](const StrValuesLayout & l) {
+            hipLaunchKernelGGL(k_str_filter_sizes, grid, block, 0, ctx->stream, col.offsets, (const u8 *)filter_u8->data, n, l.flag, l.sizes, (u32 *)&l.words->too_long);
+        },
+        [&](const StrValuesLayout & l, StrCols<> & out) {
+            hipLaunchKernelGGL(k_str_filter_move, grid, block, 0, ctx->stream, col.offsets, col.chars, (const u32 *)l.flag, (const u64 *)l.row_pos, (const u64 *)l.pos, n,
+                               (u64 *)out.v[0]->data, (u8 *)out.v[1]->data);
+        },
+        out_offsets_u64, out_chars_u8, rows_out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -319,11 +289,13 @@ extern "C" int chgpu_string_filter(chgpu_ctx * ctx, const chgpu_col * offsets_u6
 // string_vector_constant; FunctionsStringSearch.h / MatchImpl.h for like, position, startsWith, endsWith).  (offsets, chars, constant) -> one
 // 0/1 byte per row.  The constant travels in the kernel argument (no device allocation, no upload) and is staged into LDS once per
 // workgroup, where every lane reads it at its own index.  Three kernels:
-//   k_str_row_const<MODE>   one lane per row: comparison, startsWith, endsWith.  8 bytes per step (str_load8), tail masked; at most
-//                           min(len, constant) bytes of the value matter.  Algorithmic bytes: 8 B offset + <= constant bytes + 1 B per row.
-//   k_str_contains_flat     substring search that never walks rows: the chars buffer is swept in tiles of SM_TILE bytes (one 16-byte load
-//                           per lane into LDS + a halo of needle - 1 bytes of the next tile); every lane tests its 16 start positions
-//                           (first byte in registers, the rest out of LDS).  A hit at byte p belongs to the first row r with offsets[r] > p
+//   k_str_row_const<MODE>   one lane per row: comparison (str_compare, str_cmp_holds), startsWith, endsWith (str_equals_words) of the value
+//                           in global memory and the constant in LDS; at most min(len, constant) bytes of the value matter.
+//                           Algorithmic bytes: 8 B offset + <= constant bytes + 1 B per row.
+//   k_str_contains_flat     substring search that never walks rows: the chars buffer is swept in tiles of SM_TILE bytes of StrGrid (one
+//                           16-byte str_load_chunk per lane into LDS + a halo of needle - 1 bytes of the next tile); every lane tests its
+//                           16 start positions (first byte in registers, the rest out of LDS through str_equals_words, whose tile side
+//                           shifts two LDS words together).  A hit at byte p belongs to the first row r with offsets[r] > p
 //                           and counts when p + needle <= offsets[r] - 1.  k_str_tile_rows resolves the first row of every tile beforehand
 //                           (one binary search per TILE); the tile's own offsets are staged in LDS, so a hit costs an LDS search over the
 //                           tile's rows.  Result bytes are idempotent plain stores into a mask pre-filled with `negate`.
@@ -334,7 +306,6 @@ extern "C" int chgpu_string_filter(chgpu_ctx * ctx, const chgpu_col * offsets_u6
 static constexpr u32 SM_TILE = 4096;     // bytes of chars per workgroup step: 256 lanes x 16 B
 static constexpr u32 SM_ROWS_LDS = 1024; // a tile with more rows than this searches its offsets in global memory
 enum { SM_CMP = 0, SM_STARTS = 1, SM_ENDS = 2 };
-// (SM_MAX, StrConst, str_stage_const, str_tail_mask, str_zero_bytes and str_const_of are string_column.h's: the String functions use them, too)
 
 template <int MODE>
 __global__ __launch_bounds__(256) void k_str_row_const(const u64 * __restrict__ offsets, const u8 * __restrict__ chars, u64 n, const StrConst c, int op, u32 negate,
@@ -344,55 +315,18 @@ __global__ __launch_bounds__(256) void k_str_row_const(const u64 * __restrict__ 
     str_stage_const(s_w, c);
     __syncthreads();
     const u64 m = c.len;
+    const auto constant = [&](u64 j) { return s_w[j >> 3]; };
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
     {
-        const u64 begin = i ? offsets[i - 1] : 0;
-        const u64 len = offsets[i] - begin - 1;
+        const StrValue v = str_value(offsets, i);
+        const u64 len = v.size - 1;
+        const u8 * p = chars + v.begin + (MODE == SM_ENDS && len >= m ? len - m : 0);
+        const auto value = [&](u64 j) { return str_load8(p + j); };
         bool res;
         if (MODE == SM_CMP)
-        {
-            // memcmpSmallAllowOverflow15: the common prefix as unsigned bytes, then the shorter one is smaller
-            const u64 k = len < m ? len : m;
-            const u8 * p = chars + begin;
-            int cmp = 0;
-            for (u64 j = 0; j < k; j += 8)
-            {
-                u64 a = str_load8(p + j), b = s_w[j >> 3];
-                if (k - j < 8)
-                {
-                    const u64 tm = str_tail_mask(k - j);
-                    a &= tm, b &= tm;
-                }
-                if (a != b)
-                {
-                    cmp = __builtin_bswap64(a) < __builtin_bswap64(b) ? -1 : 1; // the first byte is the most significant one
-                    break;
-                }
-            }
-            if (cmp == 0)
-                cmp = len < m ? -1 : len > m ? 1 : 0;
-            res = op == CHGPU_EQ ? cmp == 0 : op == CHGPU_NE ? cmp != 0 : op == CHGPU_LT ? cmp < 0 : op == CHGPU_GT ? cmp > 0 : op == CHGPU_LE ? cmp <= 0 : cmp >= 0;
-        }
+            res = str_cmp_holds(op, str_compare(value, constant, len, m));
         else
-        {
-            res = len >= m;
-            if (res)
-            {
-                const u8 * p = chars + begin + (MODE == SM_ENDS ? len - m : 0);
-                for (u64 j = 0; j < m; j += 8)
-                {
-                    u64 x = str_load8(p + j) ^ s_w[j >> 3];
-                    if (m - j < 8)
-                        x &= str_tail_mask(m - j);
-                    if (x)
-                    {
-                        res = false;
-                        break;
-                    }
-                }
-            }
-            res = res != (negate != 0);
-        }
+            res = (len >= m && str_equals_words(value, constant, m)) != (negate != 0);
         out[i] = res ? 1 : 0;
     }
 }
@@ -427,9 +361,9 @@ __global__ __launch_bounds__(256) void k_str_like(const u64 * __restrict__ offse
     const u32 plen = c.len;
     for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256)
     {
-        const u64 begin = i ? offsets[i - 1] : 0;
-        const u64 len = offsets[i] - begin - 1;
-        const u8 * s = chars + begin;
+        const StrValue v = str_value(offsets, i);
+        const u64 len = v.size - 1;
+        const u8 * s = chars + v.begin;
         u64 h = 0, mark = 0;
         u32 p = 0;
         int star = -1;
@@ -501,28 +435,6 @@ __global__ __launch_bounds__(256) void k_str_tile_rows(const u64 * __restrict__ 
     }
 }
 
-// 16 bytes at grid position q (a multiple of 16; `grid` is 16-byte aligned) of which only [a0, end) belong to chars: nothing outside is read
-__device__ __forceinline__ uint4 str_load_chunk(const u8 * __restrict__ grid, u64 q, u64 a0, u64 end)
-{
-    if (q >= a0 && q + 16 <= end)
-        return *(const uint4 *)(grid + q);
-    u64 lo = 0, hi = 0;
-    if (q + 16 > a0 && q < end)
-    {
-#pragma unroll
-        for (u32 k = 0; k < 16; ++k)
-            if (q + k >= a0 && q + k < end)
-            {
-                const u64 b = grid[q + k];
-                if (k < 8)
-                    lo |= b << (8 * k);
-                else
-                    hi |= b << (8 * (k - 8));
-            }
-    }
-    return make_uint4((u32)lo, (u32)(lo >> 32), (u32)hi, (u32)(hi >> 32));
-}
-
 __global__ __launch_bounds__(256) void k_str_contains_flat(const u64 * __restrict__ offsets, const u8 * __restrict__ chars, u64 n, u64 size,
                                                            const u64 * __restrict__ tile_row, u64 ntiles, const StrConst c, u8 hit_value, u8 * __restrict__ out)
 {
@@ -532,9 +444,8 @@ __global__ __launch_bounds__(256) void k_str_contains_flat(const u64 * __restric
     str_stage_const(s_w, c);
     const u32 m = c.len; // >= 1
     const u32 tid = threadIdx.x;
-    const u64 a0 = (u64)chars & 15;
-    const u8 * grid = chars - a0;
-    const u64 end = a0 + size;
+    const StrGrid g(chars, size);
+    const u64 a0 = g.a0;
     const u64 first = 0x0101010101010101ull * (c.w[0] & 0xFF);
     const u64 * s_tile8 = (const u64 *)s_tile4;
     for (u64 t = blockIdx.x; t < ntiles; t += gridDim.x)
@@ -548,10 +459,10 @@ __global__ __launch_bounds__(256) void k_str_contains_flat(const u64 * __restric
         const u64 q0 = t * SM_TILE;
         const u64 pos0 = t ? q0 - a0 : 0;
         __syncthreads(); // the previous tile's readers are done (and the staged constant is visible)
-        const uint4 v = str_load_chunk(grid, q0 + tid * 16, a0, end);
+        const uint4 v = str_load_chunk(g, q0 + tid * 16);
         s_tile4[tid] = v;
         if (tid <= SM_MAX / 16)
-            s_tile4[SM_TILE / 16 + tid] = tid * 16 + 1 < m ? str_load_chunk(grid, q0 + SM_TILE + tid * 16, a0, end) : make_uint4(0, 0, 0, 0);
+            s_tile4[SM_TILE / 16 + tid] = tid * 16 + 1 < m ? str_load_chunk(g, q0 + SM_TILE + tid * 16) : make_uint4(0, 0, 0, 0);
         const bool rows_in_lds = cnt <= SM_ROWS_LDS;
         if (rows_in_lds)
             for (u32 k = tid; k < cnt; k += 256)
@@ -568,21 +479,12 @@ __global__ __launch_bounds__(256) void k_str_contains_flat(const u64 * __restric
             const u32 o = tid * 16 + j;
             if (q0 + o < a0)
                 continue; // in front of chars
-            bool eq = true;
-            for (u32 k = 0; k < m; k += 8)
-            {
+            const auto tile = [&](u32 k) { // the 8 bytes at byte o + k of the tile: two words of LDS, shifted together
                 const u32 oo = o + k, sh = (oo & 7) * 8;
                 const u64 lo = s_tile8[oo >> 3], hi = s_tile8[(oo >> 3) + 1];
-                u64 x = (sh ? (lo >> sh) | (hi << (64 - sh)) : lo) ^ s_w[k >> 3];
-                if (m - k < 8)
-                    x &= str_tail_mask(m - k);
-                if (x)
-                {
-                    eq = false;
-                    break;
-                }
-            }
-            if (!eq)
+                return sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+            };
+            if (!str_equals_words(tile, [&](u32 k) { return s_w[k >> 3]; }, m))
                 continue;
             // the row of the hit: first row of this tile's rows whose end lies behind the hit
             const u64 rel = q0 + o - a0 - pos0; // < SM_TILE
@@ -680,10 +582,11 @@ extern "C" int chgpu_like_compile(const void * pattern, uint64_t pattern_bytes, 
     return CHGPU_OK;
 }
 
-// the arguments every predicate shares, then `own_checks` (the entry point's), the offsets, and *out: a UInt8 column of one byte per row
-template <class OwnChecks>
-static int str_predicate_begin(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const void * constant, u64 constant_bytes,
-                               OwnChecks && own_checks, chgpu_col ** out_u8, chgpu_col ** out)
+// A predicate: the arguments all of them share, then `own_checks` (the entry point's), the walk over the offsets, and a UInt8 column of
+// one byte per row, which `launch(col, mask) -> int` fills
+template <class OwnChecks, class Launch>
+static int str_predicate(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const void * constant, u64 constant_bytes, OwnChecks && own_checks,
+                         Launch && launch, chgpu_col ** out_u8)
 {
     StrColumn col;
     CHGPU_TRY(str_column_begin(ctx, offsets_u64, chars_u8, out_u8 && (constant || !constant_bytes), [&] {
@@ -691,58 +594,44 @@ static int str_predicate_begin(chgpu_ctx * ctx, const chgpu_col * offsets_u64, c
                       (unsigned long long)constant_bytes, CHGPU_STR_CONST_MAX);
         return own_checks();
     }, &col));
-    PairAllocs mem = str_call(ctx, "string predicate");
-    return mem.col_new(CHGPU_U8, col.rows, out);
+    return str_one_column(ctx, "string predicate", CHGPU_U8, col.rows, [&](void * mask) { return launch(col, (u8 *)mask); }, out_u8);
 }
 
-static int str_launch_row(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, int mode, int op, const StrConst & c, int negate, chgpu_col * out)
+static int str_launch_row(chgpu_ctx * ctx, const StrColumn & col, int mode, int op, const StrConst & c, int negate, u8 * out)
 {
-    const u64 n = offsets_u64->rows;
+    const u64 n = col.rows;
     const dim3 grid(chgpu_grid_for(ctx, n, 256, 8)), block(256);
-    const u64 * offs = (const u64 *)offsets_u64->data;
-    const u8 * chars = (const u8 *)chars_u8->data;
     if (mode == SM_CMP)
-        hipLaunchKernelGGL(k_str_row_const<SM_CMP>, grid, block, 0, ctx->stream, offs, chars, n, c, op, 0u, (u8 *)out->data);
+        hipLaunchKernelGGL(k_str_row_const<SM_CMP>, grid, block, 0, ctx->stream, col.offsets, col.chars, n, c, op, 0u, out);
     else if (mode == SM_STARTS)
-        hipLaunchKernelGGL(k_str_row_const<SM_STARTS>, grid, block, 0, ctx->stream, offs, chars, n, c, 0, (u32)(negate != 0), (u8 *)out->data);
+        hipLaunchKernelGGL(k_str_row_const<SM_STARTS>, grid, block, 0, ctx->stream, col.offsets, col.chars, n, c, 0, (u32)(negate != 0), out);
     else
-        hipLaunchKernelGGL(k_str_row_const<SM_ENDS>, grid, block, 0, ctx->stream, offs, chars, n, c, 0, (u32)(negate != 0), (u8 *)out->data);
+        hipLaunchKernelGGL(k_str_row_const<SM_ENDS>, grid, block, 0, ctx->stream, col.offsets, col.chars, n, c, 0, (u32)(negate != 0), out);
     ctx->counters[6] += 1;
     return CHGPU_OK;
 }
 
-static int str_launch_contains(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const StrConst & c, int negate, chgpu_col * out)
+static int str_launch_contains(chgpu_ctx * ctx, const StrColumn & col, u64 size, const StrConst & c, int negate, u8 * out)
 {
-    const u64 n = offsets_u64->rows, size = chars_u8->rows;
-    CHGPU_HIP(hipMemsetAsync(out->data, (negate != 0) != (c.len == 0) ? 1 : 0, n, ctx->stream));
+    const u64 n = col.rows;
+    CHGPU_HIP(hipMemsetAsync(out, (negate != 0) != (c.len == 0) ? 1 : 0, n, ctx->stream));
     if (c.len == 0) // the empty needle is found in every row
         return CHGPU_OK;
-    const u64 a0 = (u64)(uintptr_t)chars_u8->data & 15;
-    const u64 ntiles = (a0 + size + SM_TILE - 1) / SM_TILE;
+    const StrGrid g(col.chars, size);
+    const u64 ntiles = (str_grid_chunks(g) + SM_TILE / 16 - 1) / (SM_TILE / 16);
     void * tile_row = nullptr;
     CHGPU_TRY(chgpu_scratch(ctx, (ntiles + 1) * sizeof(u64), &tile_row));
-    hipLaunchKernelGGL(k_str_tile_rows, dim3(chgpu_grid_for(ctx, ntiles + 1, 256, 8)), dim3(256), 0, ctx->stream, (const u64 *)offsets_u64->data, n, a0, ntiles,
-                       (u64 *)tile_row);
-    hipLaunchKernelGGL(k_str_contains_flat, dim3(chgpu_grid_for(ctx, ntiles * 256, 256, 8)), dim3(256), 0, ctx->stream, (const u64 *)offsets_u64->data,
-                       (const u8 *)chars_u8->data, n, size, (const u64 *)tile_row, ntiles, c, (u8)(negate ? 0 : 1), (u8 *)out->data);
+    hipLaunchKernelGGL(k_str_tile_rows, dim3(chgpu_grid_for(ctx, ntiles + 1, 256, 8)), dim3(256), 0, ctx->stream, col.offsets, n, g.a0, ntiles, (u64 *)tile_row);
+    hipLaunchKernelGGL(k_str_contains_flat, dim3(chgpu_grid_for(ctx, ntiles * 256, 256, 8)), dim3(256), 0, ctx->stream, col.offsets, col.chars, n, size,
+                       (const u64 *)tile_row, ntiles, c, (u8)(negate ? 0 : 1), out);
     ctx->counters[6] += 2;
     return CHGPU_OK;
 }
 
-static int str_launch_like(chgpu_ctx * ctx, const chgpu_col * offsets_u64, const chgpu_col * chars_u8, const StrConst & c, int negate, chgpu_col * out)
+static int str_launch_like(chgpu_ctx * ctx, const StrColumn & col, const StrConst & c, int negate, u8 * out)
 {
-    const u64 n = offsets_u64->rows;
-    hipLaunchKernelGGL(k_str_like, dim3(chgpu_grid_for(ctx, n, 256, 8)), dim3(256), 0, ctx->stream, (const u64 *)offsets_u64->data, (const u8 *)chars_u8->data, n, c,
-                       (u32)(negate != 0), (u8 *)out->data);
+    hipLaunchKernelGGL(k_str_like, dim3(chgpu_grid_for(ctx, col.rows, 256, 8)), dim3(256), 0, ctx->stream, col.offsets, col.chars, col.rows, c, (u32)(negate != 0), out);
     ctx->counters[6] += 1;
-    return CHGPU_OK;
-}
-
-static int str_predicate_end(int rc, StrCols<> & out, chgpu_col ** out_u8)
-{
-    CHGPU_TRY(rc);
-    CHGPU_REQUIRE(hipGetLastError() == hipSuccess, CHGPU_ERR_DEVICE, "string predicate kernels failed to launch");
-    out.give(out_u8);
     return CHGPU_OK;
 }
 
@@ -750,14 +639,10 @@ extern "C" int chgpu_string_cmp_const(chgpu_ctx * ctx, const chgpu_col * offsets
                                       chgpu_col ** out_u8)
 {
     ChgpuDeviceGuard _dev_guard(ctx);
-    StrCols<> out; // the mask
-    CHGPU_TRY(str_predicate_begin(ctx, offsets_u64, chars_u8, value, value_bytes, [&] {
+    return str_predicate(ctx, offsets_u64, chars_u8, value, value_bytes, [&] {
         CHGPU_REQUIRE(op >= CHGPU_EQ && op <= CHGPU_GE, CHGPU_ERR_BAD_ARGUMENTS, "unknown comparison %d", op);
         return (int)CHGPU_OK;
-    }, out_u8, &out.v[0]));
-    if (!offsets_u64->rows)
-        return str_predicate_end(CHGPU_OK, out, out_u8);
-    return str_predicate_end(str_launch_row(ctx, offsets_u64, chars_u8, SM_CMP, op, str_const_of(value, value_bytes), 0, out.v[0]), out, out_u8);
+    }, [&](const StrColumn & col, u8 * mask) { return str_launch_row(ctx, col, SM_CMP, op, str_const_of(value, value_bytes), 0, mask); }, out_u8);
 }
 
 // every kind is a route of the LIKE plan; a needle is its own literal
@@ -793,26 +678,19 @@ extern "C" int chgpu_string_match_const(chgpu_ctx * ctx, const chgpu_col * offse
 {
     ChgpuDeviceGuard _dev_guard(ctx);
     chgpu_like_plan plan;
-    StrCols<> out; // the mask
-    CHGPU_TRY(str_predicate_begin(ctx, offsets_u64, chars_u8, pattern, pattern_bytes, [&] { return str_match_plan(ctx, kind, pattern, pattern_bytes, plan); }, out_u8, &out.v[0]));
-    if (!offsets_u64->rows)
-        return str_predicate_end(CHGPU_OK, out, out_u8);
-    int rc = CHGPU_OK;
-    if (plan.route == CHGPU_STR_ROUTE_GENERAL)
-    {
-        StrConst c = str_const_of(plan.tokens, plan.n_tokens);
-        memcpy(c.meta, plan.token_meta, sizeof(c.meta));
-        rc = str_launch_like(ctx, offsets_u64, chars_u8, c, negate, out.v[0]);
-    }
-    else
-    {
-        const StrConst c = str_const_of(plan.literal, plan.literal_bytes);
-        if (plan.route == CHGPU_STR_ROUTE_CONTAINS)
-            rc = str_launch_contains(ctx, offsets_u64, chars_u8, c, negate, out.v[0]);
-        else if (plan.route == CHGPU_STR_ROUTE_EQUALS)
-            rc = str_launch_row(ctx, offsets_u64, chars_u8, SM_CMP, negate ? CHGPU_NE : CHGPU_EQ, c, 0, out.v[0]);
-        else
-            rc = str_launch_row(ctx, offsets_u64, chars_u8, plan.route == CHGPU_STR_ROUTE_STARTS_WITH ? SM_STARTS : SM_ENDS, 0, c, negate, out.v[0]);
-    }
-    return str_predicate_end(rc, out, out_u8);
+    return str_predicate(ctx, offsets_u64, chars_u8, pattern, pattern_bytes, [&] { return str_match_plan(ctx, kind, pattern, pattern_bytes, plan); },
+        [&](const StrColumn & col, u8 * mask) {
+            if (plan.route == CHGPU_STR_ROUTE_GENERAL)
+            {
+                StrConst c = str_const_of(plan.tokens, plan.n_tokens);
+                memcpy(c.meta, plan.token_meta, sizeof(c.meta));
+                return str_launch_like(ctx, col, c, negate, mask);
+            }
+            const StrConst c = str_const_of(plan.literal, plan.literal_bytes);
+            if (plan.route == CHGPU_STR_ROUTE_CONTAINS)
+                return str_launch_contains(ctx, col, chars_u8->rows, c, negate, mask);
+            if (plan.route == CHGPU_STR_ROUTE_EQUALS)
+                return str_launch_row(ctx, col, SM_CMP, negate ? CHGPU_NE : CHGPU_EQ, c, 0, mask);
+            return str_launch_row(ctx, col, plan.route == CHGPU_STR_ROUTE_STARTS_WITH ? SM_STARTS : SM_ENDS, 0, c, negate, mask);
+        }, out_u8);
 }

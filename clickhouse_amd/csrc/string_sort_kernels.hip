@@ -23,8 +23,8 @@
 // Algorithmic bytes per round over m active rows: 2 value gathers (lcp, keys) + (9 + segment-id bytes) passes x 21 B read and written
 // + ~50 B per row of flags and scans.
 //
-// chgpu_string_index has the shape of chgpu_string_filter: sizes gathered through the indexes, the layout pass, one move pass.
-// (Both routines are string_column.h's; SsSegs and the layouts of a round's pool allocations are string_host.h's.)
+// chgpu_string_index is a str_build_values of string_column.h, as filter, substring and concat are: sizes gathered through the indexes,
+// the layout pass, one move pass.  (SsSegs and the layouts of a round's pool allocations are string_host.h's.)
 #include "block_scan.h"
 #include "string_column.h"
 
@@ -68,6 +68,8 @@ __global__ __launch_bounds__(256) void k_ss_lcp(const u64 * __restrict__ offsets
             const u64 cap = j == t.first[s] ? 0 : __hip_atomic_load(&t.adv[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (cap) // a pair that shares `cap` words or more cannot lower the minimum
             {
+                // (begin and length by hand, not through str_value: with it the kernel came out two instructions longer and the
+                // two-round shape of tools/bench_string_sort.py 5 to 8 % slower in two sessions out of two)
                 const u64 ra = row[j - 1], rb = row[j];
                 const u64 ba = ra ? offsets[ra - 1] : 0, bb = rb ? offsets[rb - 1] : 0;
                 const u64 la = offsets[ra] - ba - 1, lb = offsets[rb] - bb - 1;
@@ -103,9 +105,8 @@ __global__ __launch_bounds__(256) void k_ss_keys(const u64 * __restrict__ offset
     {
         const u32 s = seg[j];
         const u64 d = t.depth[s] + ss_adv(t, s);
-        const u64 r = row[j];
-        const u64 begin = r ? offsets[r - 1] : 0;
-        const u64 len = offsets[r] - begin - 1;
+        const StrValue v = str_value(offsets, row[j]);
+        const u64 begin = v.begin, len = v.size - 1;
         const u64 rem = len > 8 * d ? len - 8 * d : 0;
         u64 w = 0;
         if (rem)
@@ -349,28 +350,16 @@ extern "C" int chgpu_string_index(chgpu_ctx * ctx, const chgpu_col * offsets_u64
         return (int)CHGPU_OK;
     }, &col));
     const u64 n = limit && limit < indexes_u64->rows ? limit : indexes_u64->rows;
-    const u32 grid = chgpu_grid_for(ctx, n, 256, 8);
-    PairAllocs mem = str_call(ctx, "string index");
-    PairTemps tmp(mem);
-    StrValuesLayout l{};
-    if (n)
-    {
-        CHGPU_TRY(str_carve(tmp, [&](uintptr_t base) { return str_values_lay(base, n, false, chgpu_scan_tmp_bytes(n), &l); }));
-        CHGPU_HIP(hipMemsetAsync(l.words, 0, sizeof(StrLayoutWords), ctx->stream));
-        hipLaunchKernelGGL(k_str_index_sizes, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, col.rows, (const u64 *)indexes_u64->data, n, l.sizes,
-                           (u32 *)&l.words->bad_index, (u32 *)&l.words->too_long);
-        ctx->counters[6] += 1;
-    }
-    StrLayoutWords words;
-    StrCols<> out;
-    CHGPU_TRY(str_layout_values(ctx, mem, l, n, false, col.rows, &words, &out));
-    if (n)
-    {
-        hipLaunchKernelGGL(k_str_index_move, dim3(grid), dim3(256), 0, ctx->stream, col.offsets, col.chars, (const u64 *)indexes_u64->data, (const u32 *)l.sizes,
-                           (const u64 *)l.pos, n, (u64 *)out.v[0]->data, (u8 *)out.v[1]->data);
-        ctx->counters[6] += 1;
-        CHGPU_REQUIRE(hipGetLastError() == hipSuccess, CHGPU_ERR_DEVICE, "string index kernels failed to launch");
-    }
-    out.give(out_offsets_u64, out_chars_u8);
-    return CHGPU_OK;
+    const dim3 grid(chgpu_grid_for(ctx, n, 256, 8)), block(256);
+    const u64 * indexes = (const u64 *)indexes_u64->data;
+    return str_build_values(ctx, "string index", n, col.rows,
+        [&](const StrValuesLayout & l) {
+            hipLaunchKernelGGL(k_str_index_sizes, grid, block, 0, ctx->stream, col.offsets, col.rows, indexes, n, l.sizes, (u32 *)&l.words->bad_index,
+                               (u32 *)&l.words->too_long);
+        },
+        [&](const StrValuesLayout & l, StrCols<> & out) {
+            hipLaunchKernelGGL(k_str_index_move, grid, block, 0, ctx->stream, col.offsets, col.chars, indexes, (const u32 *)l.sizes, (const u64 *)l.pos, n,
+                               (u64 *)out.v[0]->data, (u8 *)out.v[1]->data);
+        },
+        out_offsets_u64, out_chars_u8);
 }

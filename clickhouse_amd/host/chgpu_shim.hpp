@@ -911,29 +911,16 @@ struct ColumnString
     /// GpuFilterTransform takes.  compare: equals .. greaterOrEquals (CHGPU_EQ .. CHGPU_GE; FunctionsComparison.h, StringComparisonImpl::
     /// string_vector_constant); like / contains / startsWith / endsWith: MatchImpl, position() != 0, FunctionStartsEndsWith.  A constant
     /// longer than CHGPU_STR_CONST_MAX throws NOT_IMPLEMENTED: the caller keeps its CPU function.
-    ColumnPtr compare(int op, std::string_view value) const
-    {
-        chgpu_col * out = nullptr;
-        check(chgpu_string_cmp_const(offsets->context()->get(), offsets->handle(), chars->handle(), op, value.data(), value.size(), &out));
-        return std::make_shared<ColumnVector>(offsets->context(), out);
-    }
+    ColumnPtr compare(int op, std::string_view value) const { return oneColumn(chgpu_string_cmp_const, op, value.data(), value.size()); }
     /// ColumnString::getPermutation(direction, Stable, limit, ...) without collation: the UInt64 permutation that orders the values as
     /// unsigned bytes, the shorter of two values that agree being the smaller; equal values keep their incoming order in both directions.
     /// perm_in (may be null) composes a less significant sort, as in sortBlock; 0 < limit < rows cuts the result to its first `limit` entries.
     ColumnPtr getPermutation(bool descending = false, uint64_t limit = 0, const ColumnVector * perm_in = nullptr) const
     {
-        chgpu_col * out = nullptr;
-        check(chgpu_string_sort_permutation(offsets->context()->get(), offsets->handle(), chars->handle(), perm_in ? perm_in->handle() : nullptr,
-                                            descending ? 1 : 0, limit, &out));
-        return std::make_shared<ColumnVector>(offsets->context(), out);
+        return oneColumn(chgpu_string_sort_permutation, perm_in ? perm_in->handle() : nullptr, descending ? 1 : 0, limit);
     }
     /// ColumnString::permute / index: value[perm[i]] for i < (limit ? min(limit, perm.size()) : perm.size()) as a new ColumnString
-    ColumnString permute(const ColumnVector & perm, uint64_t limit = 0) const
-    {
-        chgpu_col * oo = nullptr, * oc = nullptr;
-        check(chgpu_string_index(offsets->context()->get(), offsets->handle(), chars->handle(), perm.handle(), limit, &oo, &oc));
-        return ColumnString{std::make_shared<ColumnVector>(offsets->context(), oo), std::make_shared<ColumnVector>(offsets->context(), oc)};
-    }
+    ColumnString permute(const ColumnVector & perm, uint64_t limit = 0) const { return newString(chgpu_string_index, perm.handle(), limit); }
 
     ColumnPtr like(std::string_view pattern, bool negate = false) const { return match(CHGPU_STR_LIKE, pattern, negate); }
     ColumnPtr contains(std::string_view needle, bool negate = false) const { return match(CHGPU_STR_CONTAINS, needle, negate); }
@@ -943,33 +930,23 @@ struct ColumnString
     /// Functions that compute a new column from this one.  Offsets and lengths count bytes; the UTF8, case-insensitive and
     /// non-constant-argument forms have no entry point and stay on the CPU.
     /// length (LengthImpl): UInt64
-    ColumnPtr length() const { return lengthKind(CHGPU_STR_LENGTH); }
+    ColumnPtr length() const { return oneColumn(chgpu_string_length, CHGPU_STR_LENGTH); }
     /// lengthUTF8 (LengthUTF8Impl, UTF8::countCodePoints): the bytes that are no continuation byte, UInt64
-    ColumnPtr lengthUTF8() const { return lengthKind(CHGPU_STR_LENGTH_UTF8); }
+    ColumnPtr lengthUTF8() const { return oneColumn(chgpu_string_length, CHGPU_STR_LENGTH_UTF8); }
     /// empty / notEmpty (EmptyImpl): UInt8 0/1
-    ColumnPtr empty() const { return lengthKind(CHGPU_STR_EMPTY); }
-    ColumnPtr notEmpty() const { return lengthKind(CHGPU_STR_NOT_EMPTY); }
+    ColumnPtr empty() const { return oneColumn(chgpu_string_length, CHGPU_STR_EMPTY); }
+    ColumnPtr notEmpty() const { return oneColumn(chgpu_string_length, CHGPU_STR_NOT_EMPTY); }
     /// lower / upper (LowerUpperImpl<'A', 'Z'> / <'a', 'z'>): the ASCII forms
-    ColumnString lower() const { return mapCase(CHGPU_STR_LOWER); }
-    ColumnString upper() const { return mapCase(CHGPU_STR_UPPER); }
+    ColumnString lower() const { return newString(chgpu_string_map_case, CHGPU_STR_LOWER); }
+    ColumnString upper() const { return newString(chgpu_string_map_case, CHGPU_STR_UPPER); }
     /// substring(s, offset[, length]) with constant arguments (FunctionsStringSubstring, SubstringImpl): offset >= 1 from the front,
     /// offset <= -1 from the back, the window clipped to the value; offset == 0 throws NOT_IMPLEMENTED
-    ColumnString substring(int64_t offset) const { return substringImpl(offset, 0, 0); }
-    ColumnString substring(int64_t offset, uint64_t length) const { return substringImpl(offset, 1, length); }
+    ColumnString substring(int64_t offset) const { return newString(chgpu_string_substring, offset, 0, uint64_t(0)); }
+    ColumnString substring(int64_t offset, uint64_t length) const { return newString(chgpu_string_substring, offset, 1, length); }
     /// position(haystack, needle) with a constant needle (PositionImpl::vectorConstant, bytes): 1-based, 0 without an occurrence, UInt64
-    ColumnPtr position(std::string_view needle) const
-    {
-        chgpu_col * out = nullptr;
-        check(chgpu_string_position_const(offsets->context()->get(), offsets->handle(), chars->handle(), needle.data(), needle.size(), &out));
-        return std::make_shared<ColumnVector>(offsets->context(), out);
-    }
+    ColumnPtr position(std::string_view needle) const { return oneColumn(chgpu_string_position_const, needle.data(), needle.size()); }
     /// equals .. greaterOrEquals against another String column (StringComparisonImpl::string_vector_string_vector): UInt8 0/1
-    ColumnPtr compareColumn(int op, const ColumnString & other) const
-    {
-        chgpu_col * out = nullptr;
-        check(chgpu_string_cmp_columns(offsets->context()->get(), offsets->handle(), chars->handle(), other.offsets->handle(), other.chars->handle(), op, &out));
-        return std::make_shared<ColumnVector>(offsets->context(), out);
-    }
+    ColumnPtr compareColumn(int op, const ColumnString & other) const { return oneColumn(chgpu_string_cmp_columns, other.offsets->handle(), other.chars->handle(), op); }
     /// One argument of concat: a column, or a constant (binary-safe; the view must outlive the call)
     struct ConcatArg
     {
@@ -1001,29 +978,25 @@ struct ColumnString
     }
 
 private:
-    ColumnPtr lengthKind(int kind) const
+    /// fn(context, offsets, chars, args..., &out): an entry point that gives one new column ...
+    template <typename Fn, typename... Args>
+    ColumnPtr oneColumn(Fn fn, Args... args) const
     {
         chgpu_col * out = nullptr;
-        check(chgpu_string_length(offsets->context()->get(), offsets->handle(), chars->handle(), kind, &out));
+        check(fn(offsets->context()->get(), offsets->handle(), chars->handle(), args..., &out));
         return std::make_shared<ColumnVector>(offsets->context(), out);
     }
-    ColumnString mapCase(int kind) const
+    /// ... and fn(context, offsets, chars, args..., &out_offsets, &out_chars): one that gives a new ColumnString
+    template <typename Fn, typename... Args>
+    ColumnString newString(Fn fn, Args... args) const
     {
         chgpu_col * oo = nullptr, * oc = nullptr;
-        check(chgpu_string_map_case(offsets->context()->get(), offsets->handle(), chars->handle(), kind, &oo, &oc));
-        return ColumnString{std::make_shared<ColumnVector>(offsets->context(), oo), std::make_shared<ColumnVector>(offsets->context(), oc)};
-    }
-    ColumnString substringImpl(int64_t offset, int has_length, uint64_t length) const
-    {
-        chgpu_col * oo = nullptr, * oc = nullptr;
-        check(chgpu_string_substring(offsets->context()->get(), offsets->handle(), chars->handle(), offset, has_length, length, &oo, &oc));
+        check(fn(offsets->context()->get(), offsets->handle(), chars->handle(), args..., &oo, &oc));
         return ColumnString{std::make_shared<ColumnVector>(offsets->context(), oo), std::make_shared<ColumnVector>(offsets->context(), oc)};
     }
     ColumnPtr match(int kind, std::string_view pattern, bool negate) const
     {
-        chgpu_col * out = nullptr;
-        check(chgpu_string_match_const(offsets->context()->get(), offsets->handle(), chars->handle(), kind, pattern.data(), pattern.size(), negate ? 1 : 0, &out));
-        return std::make_shared<ColumnVector>(offsets->context(), out);
+        return oneColumn(chgpu_string_match_const, kind, pattern.data(), pattern.size(), negate ? 1 : 0);
     }
 };
 

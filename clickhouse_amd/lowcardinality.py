@@ -119,47 +119,45 @@ class ColumnString:
         cuts = np.concatenate(([0], np.cumsum(lens)))
         return [data[int(cuts[k]):int(cuts[k + 1])] for k in range(rows.shape[0])]
 
+    def _one(self, fn, *args) -> Column:
+        """fn(context, offsets, chars, *args, &out): an entry point that gives one new column ..."""
+        h = C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(fn(ctx._h, self.offsets._h, self.chars._h, *args, C.byref(h)))
+        return Column(ctx, h)
+
+    def _pair(self, fn, *args, behind=()) -> "ColumnString":
+        """... and fn(context, offsets, chars, *args, &out_offsets, &out_chars, *behind): one that gives a new ColumnString"""
+        oo, oc = C.c_void_p(), C.c_void_p()
+        ctx = self.offsets.ctx
+        K.check(fn(ctx._h, self.offsets._h, self.chars._h, *args, C.byref(oo), C.byref(oc), *behind))
+        return ColumnString(Column(ctx, oo), Column(ctx, oc))
+
     def filter(self, filt: Column) -> "ColumnString":
         """ColumnString::filter (ColumnString.cpp:270-290): the kept values, in order"""
-        oo, oc = C.c_void_p(), C.c_void_p()
-        rows = C.c_uint64(0)
-        ctx = self.offsets.ctx
-        K.check(K.lib().chgpu_string_filter(ctx._h, self.offsets._h, self.chars._h, filt._h, C.byref(oo), C.byref(oc), C.byref(rows)))
-        return ColumnString(Column(ctx, oo), Column(ctx, oc))
+        rows = C.c_uint64(0)   # the result's rows: its offsets column has them
+        return self._pair(K.lib().chgpu_string_filter, filt._h, behind=(C.byref(rows),))
 
     def get_permutation(self, perm_in: Column | None = None, descending: bool = False, limit: int = 0) -> Column:
         """ColumnString::getPermutation(direction, Stable, limit) without collation -> UInt64 permutation Column: unsigned bytes, then
         the shorter value is the smaller; equal values keep their incoming order (row order, or perm_in order) in both directions.
         perm_in composes a previous (less significant) sort; 0 < limit < rows returns the first `limit` entries of the full permutation."""
-        h = C.c_void_p()
-        ctx = self.offsets.ctx
-        K.check(K.lib().chgpu_string_sort_permutation(ctx._h, self.offsets._h, self.chars._h, perm_in._h if perm_in is not None else None,
-                                                      1 if descending else 0, int(limit), C.byref(h)))
-        return Column(ctx, h)
+        return self._one(K.lib().chgpu_string_sort_permutation, perm_in._h if perm_in is not None else None, 1 if descending else 0, int(limit))
 
     def index(self, perm: Column, limit: int = 0) -> "ColumnString":
         """ColumnString::permute / index: out[i] = value[perm[i]], i < (limit ? min(limit, perm.size()) : perm.size())"""
-        oo, oc = C.c_void_p(), C.c_void_p()
-        ctx = self.offsets.ctx
-        K.check(K.lib().chgpu_string_index(ctx._h, self.offsets._h, self.chars._h, perm._h, int(limit), C.byref(oo), C.byref(oc)))
-        return ColumnString(Column(ctx, oo), Column(ctx, oc))
+        return self._pair(K.lib().chgpu_string_index, perm._h, int(limit))
 
     # -- predicates against a constant: a UInt8 Column of 0/1, one per row (the mask filter / and_ / execute_on_block(filter=) take) --
     def compare(self, op: int, value) -> Column:
         """equals .. greaterOrEquals (EQ .. GE) against a constant String: unsigned bytes, then the shorter one is the smaller
         (FunctionsComparison.h, StringComparisonImpl::string_vector_constant)"""
         value = _const_bytes(value)
-        h = C.c_void_p()
-        ctx = self.offsets.ctx
-        K.check(K.lib().chgpu_string_cmp_const(ctx._h, self.offsets._h, self.chars._h, int(op), value, len(value), C.byref(h)))
-        return Column(ctx, h)
+        return self._one(K.lib().chgpu_string_cmp_const, int(op), value, len(value))
 
     def _match(self, kind: int, pattern, negate: bool) -> Column:
         pattern = _const_bytes(pattern)
-        h = C.c_void_p()
-        ctx = self.offsets.ctx
-        K.check(K.lib().chgpu_string_match_const(ctx._h, self.offsets._h, self.chars._h, kind, pattern, len(pattern), 1 if negate else 0, C.byref(h)))
-        return Column(ctx, h)
+        return self._one(K.lib().chgpu_string_match_const, kind, pattern, len(pattern), 1 if negate else 0)
 
     def like(self, pattern, negate: bool = False) -> Column:
         """like / notLike (MatchImpl): % any run of bytes, _ one UTF-8 character, \\% \\_ \\\\ the literal bytes"""
@@ -176,41 +174,29 @@ class ColumnString:
         return self._match(K.STR_ENDS_WITH, needle, negate)
 
     # -- functions: a new column computed from this one, on the device (string_func_kernels.hip) --
-    def _length(self, kind: int) -> Column:
-        h = C.c_void_p()
-        ctx = self.offsets.ctx
-        K.check(K.lib().chgpu_string_length(ctx._h, self.offsets._h, self.chars._h, kind, C.byref(h)))
-        return Column(ctx, h)
-
     def length(self) -> Column:
         """length: the bytes of every value, a UInt64 Column"""
-        return self._length(K.STR_LENGTH)
+        return self._one(K.lib().chgpu_string_length, K.STR_LENGTH)
 
     def length_utf8(self) -> Column:
         """lengthUTF8: the bytes that are no continuation byte (10xxxxxx), on valid and invalid UTF-8 alike, a UInt64 Column"""
-        return self._length(K.STR_LENGTH_UTF8)
+        return self._one(K.lib().chgpu_string_length, K.STR_LENGTH_UTF8)
 
     def empty(self) -> Column:
         """empty: a UInt8 Column of 0/1"""
-        return self._length(K.STR_EMPTY)
+        return self._one(K.lib().chgpu_string_length, K.STR_EMPTY)
 
     def not_empty(self) -> Column:
         """notEmpty: a UInt8 Column of 0/1"""
-        return self._length(K.STR_NOT_EMPTY)
-
-    def _map_case(self, kind: int) -> "ColumnString":
-        oo, oc = C.c_void_p(), C.c_void_p()
-        ctx = self.offsets.ctx
-        K.check(K.lib().chgpu_string_map_case(ctx._h, self.offsets._h, self.chars._h, kind, C.byref(oo), C.byref(oc)))
-        return ColumnString(Column(ctx, oo), Column(ctx, oc))
+        return self._one(K.lib().chgpu_string_length, K.STR_NOT_EMPTY)
 
     def lower(self) -> "ColumnString":
         """lower, the ASCII form: 'A'..'Z' become 'a'..'z', every other byte is copied"""
-        return self._map_case(K.STR_LOWER)
+        return self._pair(K.lib().chgpu_string_map_case, K.STR_LOWER)
 
     def upper(self) -> "ColumnString":
         """upper, the ASCII form: 'a'..'z' become 'A'..'Z', every other byte is copied"""
-        return self._map_case(K.STR_UPPER)
+        return self._pair(K.lib().chgpu_string_map_case, K.STR_UPPER)
 
     def substring(self, offset: int, length: int | None = None) -> "ColumnString":
         """substring(s, offset[, length]) with constant arguments, in bytes: offset >= 1 counts from the front, offset <= -1 from the
@@ -222,20 +208,13 @@ class ColumnString:
             raise ValueError("substring: the offset is an Int64")
         if length is not None and not 0 <= int(length) < 2**64:
             raise ValueError("substring: the length is a UInt64 (a negative length is not supported)")
-        oo, oc = C.c_void_p(), C.c_void_p()
-        ctx = self.offsets.ctx
-        K.check(K.lib().chgpu_string_substring(ctx._h, self.offsets._h, self.chars._h, offset, 0 if length is None else 1, 0 if length is None else int(length),
-                                               C.byref(oo), C.byref(oc)))
-        return ColumnString(Column(ctx, oo), Column(ctx, oc))
+        return self._pair(K.lib().chgpu_string_substring, offset, 0 if length is None else 1, 0 if length is None else int(length))
 
     def position(self, needle) -> Column:
         """position(haystack, needle): the 1-based byte index of the first occurrence inside the value, 0 without one; a UInt64 Column.
         The empty needle is found at 1."""
         needle = _const_arg(needle)
-        h = C.c_void_p()
-        ctx = self.offsets.ctx
-        K.check(K.lib().chgpu_string_position_const(ctx._h, self.offsets._h, self.chars._h, needle, len(needle), C.byref(h)))
-        return Column(ctx, h)
+        return self._one(K.lib().chgpu_string_position_const, needle, len(needle))
 
     def compare_column(self, op: int, other: "ColumnString") -> Column:
         """equals .. greaterOrEquals (EQ .. GE) against another String column, row by row, in the order of compare(): a UInt8 Column"""
@@ -243,10 +222,7 @@ class ColumnString:
             raise TypeError("compare_column takes a ColumnString")
         if not _is_int(op):
             raise TypeError("compare_column takes one of EQ .. GE")
-        h = C.c_void_p()
-        ctx = self.offsets.ctx
-        K.check(K.lib().chgpu_string_cmp_columns(ctx._h, self.offsets._h, self.chars._h, other.offsets._h, other.chars._h, int(op), C.byref(h)))
-        return Column(ctx, h)
+        return self._one(K.lib().chgpu_string_cmp_columns, other.offsets._h, other.chars._h, int(op))
 
     @staticmethod
     def concat(*args) -> "ColumnString":

@@ -278,6 +278,49 @@ def test_compare_column_agrees_with_compare_const(ch, ctx, cols):
             assert col.compare_column(op, same).numpy().tolist()[:256] == col.compare(op, const).numpy().tolist()[:256]
 
 
+CMP_LENGTHS = [0, 1, 7, 8, 9, 15, 16, 17]
+CMP_BYTES = (0x00, 0x01, 0x7F, 0x80, 0xFF)
+
+
+def _cmp_table():
+    """(a, b) for every pair of lengths: equal over the common prefix of k bytes, and different in exactly one byte, at 0 or at k - 1; the
+    two bytes there run through all ordered pairs of CMP_BYTES.  What the longer one has behind the prefix is random."""
+    rng = random.Random(15)
+    byte_pairs = [(x, y) for x in CMP_BYTES for y in CMP_BYTES if x != y]
+    pairs, turn = [], 0
+    for la in CMP_LENGTHS:
+        for lb in CMP_LENGTHS:
+            k = min(la, lb)
+            prefix = _random_value(rng, k)
+            a, b = prefix + _random_value(rng, la - k), prefix + _random_value(rng, lb - k)
+            pairs.append((a, b))
+            for p in sorted({0, k - 1} if k else ()):
+                x, y = byte_pairs[turn % len(byte_pairs)]
+                turn += 1
+                pairs.append((a[:p] + bytes([x]) + a[p + 1:], b[:p] + bytes([y]) + b[p + 1:]))
+    assert turn >= 2 * len(byte_pairs) and len(pairs) < 300
+    pairs.append((NEEDLE_Z[:2], NEEDLE_Z[:2]))
+    return [p[0] for p in pairs], [p[1] for p in pairs]
+
+
+@pytest.mark.parametrize("misalign", MISALIGN)
+def test_one_compare_table_through_both_entries(ch, ctx, misalign):
+    """compare_column and compare share one ordered compare of two byte ranges (str_compare): the same pairs go through both, against
+    the order of Python's bytes"""
+    import operator
+    K = ch._capi
+    ops = {K.EQ: operator.eq, K.NE: operator.ne, K.LT: operator.lt, K.GT: operator.gt, K.LE: operator.le, K.GE: operator.ge}
+    a_values, b_values = _cmp_table()
+    a, b = _column(ch, ctx, a_values, misalign), _column(ch, ctx, b_values, (misalign * 3) % 16)
+    for op, holds in ops.items():
+        want = [int(holds(x, y)) for x, y in zip(a_values, b_values)]
+        assert 0 < sum(want) < len(want)
+        assert _numbers(a.compare_column(op, b), np.uint8) == want, op
+    for const in sorted(set(b_values)):
+        for op, holds in ops.items():
+            assert _numbers(a.compare(op, const), np.uint8) == [int(holds(x, const)) for x in a_values], (op, const)
+
+
 # ---- position ----
 def _position_values(needle):
     m = len(needle)
@@ -332,6 +375,47 @@ def test_position_never_takes_in_a_terminator_or_the_next_row(ch, ctx):
     assert e.value.code == ch._capi.ERR_NOT_IMPLEMENTED
 
 
+NEEDLE_LENGTHS = [1, 7, 8, 9, 16, 17, 255, 256]
+
+
+def _needle_table(m, misalign):
+    """(values, needles) for a needle N of m bytes: N at the front, at the end and across an edge of the 16-byte grid of the chars
+    address; near misses in N's last byte alone, which is the value's last byte or its terminator; N without its last byte in front
+    of a row that begins with that byte.  NZ and NX are N with a zero as its last byte / in front of its last byte: only a terminator
+    (and the next row's first byte) would complete them."""
+    N = bytes(0x41 + i % 26 for i in range(m))
+    last, miss, o = N[-1:], bytes([N[-1] ^ 0x20]), b"#"
+    values = [N, N + o, o + N, o * 3 + N, N + N, N[:-1] + miss, o + N[:-1] + miss, miss + N[:-1], N[:-1], last + o, N[:-2], last, o + N[:-1], N[1:], b""]
+
+    def straddling(tail):
+        # the pad that puts N's first byte on the last byte of a 16-byte chunk (N itself, when it is one byte)
+        at = misalign + sum(len(v) + 1 for v in values)
+        return o * ((15 - at) % 16) + N + tail
+
+    values += [straddling(b"")]
+    values += [straddling(o * 3)]
+    values += [straddling(N[:-1] + miss)]
+    needles = [N, N[:-1] + b"\0"] + ([N[:-2] + b"\0" + last] if m >= 2 else [])
+    return values + [o + NEEDLE_Z[:2]], needles
+
+
+@pytest.mark.parametrize("misalign", MISALIGN)
+def test_one_needle_table_through_four_entries(ch, ctx, misalign):
+    """starts_with, ends_with, contains and position share one test of m bytes against the constant (str_equals_words): the same
+    haystacks and needles go through all four"""
+    for m in NEEDLE_LENGTHS:
+        values, needles = _needle_table(m, misalign)
+        col = _column(ch, ctx, values, misalign)
+        assert (col.chars.device_ptr + sum(len(v) + 1 for v in values[:15]) + values[15].index(needles[0])) % 16 == 15
+        for needle in needles:
+            assert _numbers(col.starts_with(needle), np.uint8) == [int(v.startswith(needle)) for v in values], (m, needle[-3:])
+            assert _numbers(col.ends_with(needle), np.uint8) == [int(v.endswith(needle)) for v in values], (m, needle[-3:])
+            assert _numbers(col.contains(needle), np.uint8) == [int(needle in v) for v in values], (m, needle[-3:])
+            assert _numbers(col.position(needle), np.uint64) == [v.find(needle) + 1 for v in values], (m, needle[-3:])
+        found = [v.find(needles[0]) + 1 for v in values]
+        assert sum(1 for f in found if f) >= 8 and sum(1 for f in found if not f) >= 8
+
+
 # ---- broken offsets ----
 def test_offsets_that_break_the_invariant_are_bad_arguments(ch, ctx):
     chars = ctx.upload(np.zeros(64, dtype=np.uint8))
@@ -349,13 +433,17 @@ def test_offsets_that_break_the_invariant_are_bad_arguments(ch, ctx):
 # ---- allocation failure ----
 ALLOC_CALLS = ["length", "map_case", "cmp_columns", "substring", "concat", "position"]
 ALLOCATIONS = {"length": 1, "map_case": 2, "cmp_columns": 1, "substring": 3, "concat": 3, "position": 1}     # results, and the one pool allocation
+# KernelLaunches one call adds, as a run of the library of the commit before str_one_column / str_build_values printed them.  The walk
+# over a column's offsets counts one, a scan its three kernels: length 1 + 1, map_case 1 + 2, cmp_columns 2 + 1, substring 1 + 2 + 3,
+# concat 2 + 2 + 3, position 1 + 1.
+LAUNCHES = {"length": 2, "map_case": 3, "cmp_columns": 3, "substring": 6, "concat": 7, "position": 2}
 
 
-@pytest.mark.parametrize("name", ALLOC_CALLS)
-def test_a_refused_allocation_is_an_error_and_the_same_call_then_succeeds(ch, ctx, cols, name):
+def _alloc_call(ch, cols, name):
+    """(call, reference) of one entry point over the columns of 257 rows; the call returns plain host values"""
     values, col = cols(257, 7)
     other_values, other = cols(257, 1, 1)
-    call, want = {
+    return {
         "length": (lambda: col.length_utf8().numpy().tolist(), [R.length_utf8(v) for v in values]),
         "map_case": (lambda: _strings(col.lower()), [R.lower(v) for v in values]),
         "cmp_columns": (lambda: col.compare_column(ch._capi.LT, other).numpy().tolist(), [int(x < y) for x, y in zip(values, other_values)]),
@@ -363,6 +451,21 @@ def test_a_refused_allocation_is_an_error_and_the_same_call_then_succeeds(ch, ct
         "concat": (lambda: _strings(ch.ColumnString.concat(col, b"/", other)), [x + b"/" + y for x, y in zip(values, other_values)]),
         "position": (lambda: col.position(b"aZ").numpy().tolist(), [R.position(v, b"aZ") for v in values]),
     }[name]
+
+
+@pytest.mark.parametrize("name", ALLOC_CALLS)
+def test_the_kernel_launches_of_a_call_are_as_they_were(ch, ctx, cols, name):
+    call, want = _alloc_call(ch, cols, name)
+    before = ctx.counters()["KernelLaunches"]
+    assert call() == want
+    delta = ctx.counters()["KernelLaunches"] - before
+    print(f"KernelLaunches[{name}] = {delta}")
+    assert delta == LAUNCHES[name], (name, delta)
+
+
+@pytest.mark.parametrize("name", ALLOC_CALLS)
+def test_a_refused_allocation_is_an_error_and_the_same_call_then_succeeds(ch, ctx, cols, name):
+    call, want = _alloc_call(ch, cols, name)
 
     def rows_and_bytes():
         c = ctx.counters()
