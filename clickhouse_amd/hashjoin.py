@@ -188,11 +188,17 @@ class AsofJoin:
     one fixed-width integer key + one numeric asof column; `inequality` as ASOFJoinInequality with the LEFT value on the left."""
 
     def __init__(self, kind: int, inequality: int = K.ASOF_GREATER_OR_EQUALS, key_dtype=np.uint64, asof_dtype=np.uint32, ctx: Context | None = None):
+        tags = []
+        for what, dtype in (("key", key_dtype), ("asof", asof_dtype)):
+            try:
+                tags.append(TAG_OF[np.dtype(dtype)])
+            except (KeyError, TypeError):
+                raise ValueError(f"{what} dtype {dtype!r} is not one of the column types") from None
         self.ctx = ctx if ctx is not None else Context(0)
         self.kind, self.inequality = kind, inequality
         self.key_dtype, self.asof_dtype = np.dtype(key_dtype), np.dtype(asof_dtype)
         h = C.c_void_p()
-        K.check(K.lib().chgpu_asof_create(self.ctx._h, TAG_OF[self.key_dtype], TAG_OF[self.asof_dtype], kind, inequality, C.byref(h)))
+        K.check(K.lib().chgpu_asof_create(self.ctx._h, tags[0], tags[1], kind, inequality, C.byref(h)))
         self._h = h
 
     def close(self):

@@ -48,11 +48,12 @@ def call(K):
     """-> (replacing, collapsing, folding) over one Int64 key column of 4 rows in 2 runs; keyword arguments replace the defaults"""
     L = K.lib()
     # a context is looked at first and never dereferenced in the checks in front of the device
-    fake = C.c_void_p(C.addressof(C.create_string_buffer(1 << 16)))
+    ctx_bytes = C.create_string_buffer(1 << 16)   # zeroes, alive for as long as `fake` is used
+    fake = C.c_void_p(C.addressof(ctx_bytes))
     key = _col(K.I64, 4)
     base = dict(ctx=fake, cols=(C.c_void_p * 9)(*([C.addressof(key)] * 9)), desc=(C.c_int32 * 9)(*([0] * 9)), hint=(C.c_int32 * 9)(*([1] * 9)), n_keys=1,
                 offs=(C.c_uint64 * 3)(0, 2, 4), n_runs=2, flags=0)
-    keep = [key]
+    keep = [key, ctx_bytes]
 
     def prefix(kw):
         a = dict(base, **{k: v for k, v in kw.items() if k in base})

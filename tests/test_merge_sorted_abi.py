@@ -70,7 +70,8 @@ def test_null_arguments_are_bad_arguments(K):
     _expect_bad(K, L.chgpu_is_sorted(None, cols, desc, hint, 1, offs, 1, C.byref(row)), "NULL")
     _expect_bad(K, L.chgpu_is_sorted(None, cols, desc, hint, 1, offs, 1, None), "NULL")
     # a context is looked at first and never dereferenced: any non-NULL pointer stands for one in the checks in front of the device
-    fake = C.c_void_p(C.addressof(C.create_string_buffer(1 << 16)))
+    ctx_bytes = C.create_string_buffer(1 << 16)   # zeroes, alive for as long as `fake` is used
+    fake = C.c_void_p(C.addressof(ctx_bytes))
     _expect_bad(K, L.chgpu_merge_sorted_permutation(fake, None, desc, hint, 1, offs, 1, 0, 0, C.byref(out)), "NULL")
     _expect_bad(K, L.chgpu_merge_sorted_permutation(fake, cols, None, hint, 1, offs, 1, 0, 0, C.byref(out)), "NULL")
     _expect_bad(K, L.chgpu_merge_sorted_permutation(fake, cols, desc, None, 1, offs, 1, 0, 0, C.byref(out)), "NULL")
@@ -83,7 +84,8 @@ def test_null_arguments_are_bad_arguments(K):
 def test_key_counts_and_malformed_offsets_are_bad_arguments(K):
     L = K.lib()
     out, row = C.c_void_p(), C.c_uint64(0)
-    fake = C.c_void_p(C.addressof(C.create_string_buffer(1 << 16)))
+    ctx_bytes = C.create_string_buffer(1 << 16)   # zeroes, alive for as long as `fake` is used
+    fake = C.c_void_p(C.addressof(ctx_bytes))
     cols = (C.c_void_p * 9)(*([None] * 9))
     desc, hint = (C.c_int32 * 9)(*([0] * 9)), (C.c_int32 * 9)(*([1] * 9))
     offs = (C.c_uint64 * 3)(0, 2, 4)

@@ -49,11 +49,12 @@ def call(K):
     that neither output was written."""
     L = K.lib()
     # a context is looked at first and never dereferenced in the checks in front of the device
-    fake = C.c_void_p(C.addressof(C.create_string_buffer(1 << 16)))
+    ctx_bytes = C.create_string_buffer(1 << 16)   # zeroes, alive for as long as `fake` is used
+    fake = C.c_void_p(C.addressof(ctx_bytes))
     key, version = _col(K.I64, 4), _col(K.U32, 4)
     base = dict(ctx=fake, cols=(C.c_void_p * 9)(C.addressof(key), *([C.addressof(version)] * 8)), desc=(C.c_int32 * 9)(*([0] * 9)),
                 hint=(C.c_int32 * 9)(*([1] * 9)), n_keys=2, offs=(C.c_uint64 * 3)(0, 2, 4), n_runs=2, flags=0)
-    keep = [key, version]
+    keep = [key, version, ctx_bytes]
 
     def versioned(sign=None, out=True, balance=True, **kw):
         a = dict(base, **kw)
